@@ -19,12 +19,22 @@ Frames enter as uint8 640x480 host arrays; every env step preprocesses its frame
 reference's PIL path) INSIDE the timed region, as the reference loop does (streamvln_eval.py:271-274); `value` = 4 * turns / time
 over all ranks (frame in -> action ids out).  `generate_boundary` is the same run with the image-processor time taken out.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the JSON line.  `--full` adds everything else (their objects are null
+without it):
   roofline      the gate/up SwiGLU GEMV of the decode step (largest single weight stream: 2*I*H*2 B = 271.6 MB per
                 launch, HBM-bound); `achieved` = those bytes / its mean duration, measured live with HIP events
                 on the engine's stream around the layer-0 launch of the first decode step of every turn in the timed region.
+  with_feature_cache / fp8_decode_weights / memory_prune_32 / batched_envs
+                the opt-in modes, each timed in a pass of its own after the headline pass.
+  metric_allreduce_check
+                the 5-scalar metric all-reduce of the eval loop on synthetic metrics.
   cpu_baseline  the CPU oracle (fp32 port of the reference path, torch CPU, all host threads) on a bounded sample of
                 the same steady turn (rank 0, N = 1 only).
+The --no-* options switch single parts of `--full` off.
+
+--dump-outputs DIR writes what the last timed step returned (rank 0): DIR/sequences.npy (the turn's generated token ids, float64)
+and DIR/hidden.npy (the final-norm hidden rows of those tokens, float32).  Weights, frames and prompts are seeded, so the same
+arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -60,7 +70,13 @@ def parse():
                     "measured slower than the six launches at this size, DESIGN.md 4.1: A/B only)")
     ap.add_argument("--pageable-frames", action="store_true", help="camera frames in ordinary numpy arrays instead of the engine's pinned frame ring")
     ap.add_argument("--own-torch-stream", action="store_true", help="leave torch on its default stream (cross-stream ordering per frame / turn) instead of the engine's")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also the roofline probes, the opt-in passes, the metric all-reduce check and the CPU "
+                    "baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def self_launch(a):
@@ -168,6 +184,15 @@ def timed_pass(model, turn, steps, warmup, world, lat=None):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     return dt
+
+
+def dump_outputs(d, run, model):
+    """--dump-outputs: what the last timed turn returned to its caller (generate's `sequences`, exact in float64) and the final-norm
+    hidden rows of the tokens it generated (float32); read after the clock stopped"""
+    os.makedirs(d, exist_ok=True)
+    seq = run.agent.turn_log[-1]["out"].sequences
+    np.save(os.path.join(d, "sequences.npy"), seq.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(d, "hidden.npy"), model.last_hidden().astype(np.float32))
 
 
 def cpu_baseline(cfg_true):
@@ -284,6 +309,8 @@ def main():
     from streamvln_amd.eval_harness import reduce_metrics
     import torch.distributed as dist
 
+    if not a.full:              # a plain run: the headline pass only (the batched pass is skipped below; --batched-envs still sizes the engine)
+        a.no_probe = a.no_cpu_baseline = a.no_feature_cache_pass = a.no_fp8_pass = a.no_prune_pass = True
     rank, world, local = init_distributed_mode(backend=a.backend)
     if a.single_device:
         local = 0
@@ -359,6 +386,8 @@ def main():
                      "launches_timed": n2.value,
                      "weight_stream": {"bound": "hbm", "achieved": round(wb2.value / t2 / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
                                        "frac": round(wb2.value / t2 / 8e12, 4), "bytes_per_launch": wb2.value}}
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, run, model)
 
     def extra_pass(setup, teardown):
         setup()
@@ -449,7 +478,7 @@ def main():
                            "restatement); changes the model input, not the headline value")
     # BASELINE configs[4]-style concurrent envs on this GPU through generate_batch (build-side extension).
     batched = None
-    if not a.no_batched_pass and n_benv > 1:
+    if a.full and not a.no_batched_pass and n_benv > 1:
         from streamvln_amd.agent import BatchedAgents, StreamingAgent
         from streamvln_amd.synthetic import SyntheticPromptEncoder
         model.reset(n_benv)
@@ -490,7 +519,10 @@ def main():
                                             "weight and activation scales, fp32 accumulate, bf16 out); lm_head, attention, vision bf16",
                                    "note": "opt-in extension, no reference counterpart; reduced precision, never the headline"}
     # the one exchange of the path: per-episode metrics -> 5-scalar RCCL all-reduce (synthetic metrics here)
-    summary = reduce_metrics([{"success": 1.0, "spl": 0.5, "os": 1.0, "ne": float(rank)}], device="cuda" if (dist.is_initialized() and dist.get_backend() == "nccl") else "cpu")
+    summary = None
+    if a.full:
+        summary = reduce_metrics([{"success": 1.0, "spl": 0.5, "os": 1.0, "ne": float(rank)}],
+                                 device="cuda" if (dist.is_initialized() and dist.get_backend() == "nccl") else "cpu")
     turns_total = a.steps * world
     value = NUM_FUTURE * turns_total / dt
     if rank == 0:

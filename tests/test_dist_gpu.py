@@ -21,7 +21,7 @@ def _free_port():
     return port
 
 
-BENCH_ARGS = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "tiny", "--backend", "gloo", "--single-device", "--no-cpu-baseline",
+BENCH_ARGS = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "tiny", "--backend", "gloo", "--single-device", "--full", "--no-cpu-baseline",
               "--no-feature-cache-pass", "--no-fp8-pass", "--no-prune-pass", "--batched-envs", "2"]
 
 
@@ -56,7 +56,7 @@ def test_bench_rccl_branch_one_rank():
     runs -- torch.cuda.set_device(LOCAL_RANK), init_process_group("nccl"), barrier, the max-over-ranks all-reduce and the 5-scalar
     metric all-reduce on CUDA tensors (bench.py: timed_pass / reduce_metrics)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--config", "tiny", "--backend", "nccl",
-           "--no-cpu-baseline", "--no-feature-cache-pass", "--no-fp8-pass", "--no-prune-pass", "--no-batched-pass"]
+           "--full", "--no-cpu-baseline", "--no-feature-cache-pass", "--no-fp8-pass", "--no-prune-pass", "--no-batched-pass"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)

@@ -7,9 +7,9 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$R
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-echo "== bench plain"; python3 bench.py --steps 20 --warmup 5 > $OUT/${R}_bench_plain.json 2> $OUT/bench_plain.err
+echo "== bench plain"; python3 bench.py --steps 20 --warmup 5 --full > $OUT/${R}_bench_plain.json 2> $OUT/bench_plain.err
 echo "== bench under rocprofv3"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${R}_bench_under_rocprof.json 2> $OUT/bench_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/${R}_bench_under_rocprof.json 2> $OUT/bench_prof.err
 T=$(ls $OUT/trace/*/*kernel_trace.csv | head -1)
 python3 profiles/analyze_trace.py $T 90 > $OUT/${R}_bench_kernel_trace_by_shape.txt
 python3 profiles/turn_breakdown.py $T 6 > $OUT/${R}_steady_turn_phases.txt
