@@ -246,6 +246,24 @@ int svln_op_layernorm(svln_engine* h, const void* x, const void* g, const void* 
 int svln_op_attention_llm(svln_engine* h, void* qkv, int ld, int T, int P, const void* ctx_qkv, int ctx_T, void* out, int o_stride,
                           int nsplit);
 int svln_op_attention_vit(svln_engine* h, const void* qkv, int ld, int F, void* out, int o_stride);
+/* one decode step of B in {1, 2, 4, 8} envs on layer 0, through the engine's own decode attention (fused RoPE of q / k, K / V append,
+ * split-KV partials + merge).  Env b first gets pos[b] context rows (ctx_qkv + b * ctx_rows * ld, roped in place + appended as in
+ * svln_op_attention_llm), then its un-roped q|k|v row qkv_new[b * ld] is decoded at position pos[b] -> out[b * o_stride].
+ * B == 1 takes the single-env step, B > 1 the batched one. */
+int svln_op_attention_decode(svln_engine* h, int B, const void* ctx_qkv, int ld, int64_t ctx_rows, const int32_t* pos, const void* qkv_new,
+                             void* out, int o_stride);
+/* roped K and V rows of positions [start, start + n) of env's layer-0 KV pages -> host fp32 [n][kv_heads][128] each; env = -1 reads
+ * the raw pools (position p = slot p % 64 of physical page p / 64).  The attention ops reset their envs on entry only, so this reads
+ * what the last op wrote. */
+int svln_op_kv_read(svln_engine* h, int env, int start, int n, float* k_out, float* v_out);
+/* the prefill q|k|v product of one env's turn on layer 0 (env 0, positions P .. P + T - 1) as a prefill runs it: x = the normed input
+ * rows [T][hidden] (device); roped q rows -> q_out [T][q_stride], roped k / v appended to env 0's pages; *fused = 1 when the product's
+ * split-K reduce did the RoPE + append, 0 when the separate RoPE + append kernel did */
+int svln_op_llm_qkv_rope(svln_engine* h, const void* x, int T, int P, void* q_out, int q_stride, int32_t* fused);
+/* test control: the attention ops give env these pages (in this order: logical page i -> pages[i]); n = 0 restores the free list */
+int svln_op_set_pages(svln_engine* h, int env, const int32_t* pages, int n);
+/* test control: fill the layer-0 K / V pools with a finite value and (part_nan) the split-KV partial workspace with NaN */
+int svln_op_fill_attn_state(svln_engine* h, float pool_value, int part_nan);
 int svln_op_pool(svln_engine* h, const void* in, void* out, int F);
 int svln_op_patchify(svln_engine* h, const float* pix, void* out, int F);
 

@@ -106,6 +106,11 @@ SIGNATURES = {
     "svln_op_layernorm": (_I, [_P, _P, _P, _P, _P, _I, _I, _F]),
     "svln_op_attention_llm": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I]),
     "svln_op_attention_vit": (_I, [_P, _P, _I, _I, _P, _I]),
+    "svln_op_attention_decode": (_I, [_P, _I, _P, _I, _I64, _PI32, _P, _P, _I]),
+    "svln_op_kv_read": (_I, [_P, _I, _I, _I, _PF, _PF]),
+    "svln_op_llm_qkv_rope": (_I, [_P, _P, _I, _I, _P, _I, _PI32]),
+    "svln_op_set_pages": (_I, [_P, _I, _PI32, _I]),
+    "svln_op_fill_attn_state": (_I, [_P, _F, _I]),
     "svln_op_pool": (_I, [_P, _P, _P, _I]),
     "svln_op_patchify": (_I, [_P, _P, _P, _I]),
 }

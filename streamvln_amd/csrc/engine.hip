@@ -8,6 +8,7 @@
 //   Qwen2 decoder stack + DynamicCache + greedy _sample   transformers 4.45.1 (requirements.txt:140)
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -119,6 +120,12 @@ struct EngineBase {
     virtual void op_layernorm(const void* x, const void* g, const void* b, void* y, int rows, int n, float eps) = 0;
     virtual void op_attention_llm(void* qkv, int ld, int T, int P, const void* ctx, int ctx_T, void* out, int o_stride, int nsplit) = 0;
     virtual void op_attention_vit(const void* qkv, int ld, int F, void* out, int o_stride) = 0;
+    virtual void op_attention_decode(int B, const void* ctx, int ld, int64_t ctx_rows, const int32_t* pos, const void* qkv_new, void* out,
+                                     int o_stride) = 0;
+    virtual void op_kv_read(int env, int start, int n, float* k_out, float* v_out) = 0;
+    virtual void op_llm_qkv_rope(const void* x, int T, int P, void* q_out, int q_stride, int32_t* fused) = 0;
+    virtual void op_set_pages(int env, const int32_t* pages, int n) = 0;
+    virtual void op_fill_attn_state(float pool_value, int part_nan) = 0;
     virtual void op_pool(const void* in, void* out, int F) = 0;
     virtual void op_patchify(const float* pix, void* out, int F) = 0;
 };
@@ -854,6 +861,21 @@ public:
     }
 
     struct Seg { Env* e; int P, Tn, off; };       // rows [off, off + Tn) of the prefill batch belong to env e at positions P..
+    RopeKvArgs rope_kv_args(const LLayer& L, const Seg& g) {
+        RopeKvArgs r; r.qkv = qkv + (size_t)g.off * qkv_dim; r.ld = qkv_dim; r.Kpool = L.kpool; r.Vpool = L.vpool; r.rope_tab = rope_tab;
+        r.nq = nq; r.nkv = nkv; r.dyn_pos = nullptr; r.page_table = g.e->d_pages; r.T = g.Tn; r.P = g.P;
+        return r;
+    }
+    // q|k|v product of the M prefill rows (xn -> qkv) of layer L.  One env's turn alone in the batch (`single`): the product's split-K
+    // reduce also ropes q / k and appends k / v to the env's pages -- returns true when it did; otherwise every segment is roped and
+    // appended by prefill_rope_append.  op_llm_qkv_rope runs these same two members.
+    bool prefill_qkv(const LLayer& L, int M, const Seg* single) {
+        GemmArgs aq = gemm_args(xn, H, L.qkv_w, H, qkv, qkv_dim, L.qkv_b, nullptr, 0, 0, M, qkv_dim, H, EPI_NONE);
+        RopeKvArgs r0;
+        if (single) { r0 = rope_kv_args(L, *single); aq.rope = &r0; }
+        return llm_gemm(aq, L.qkv8);
+    }
+    void prefill_rope_append(const LLayer& L, const Seg& g) { launch_rope_kv<T>(st, rope_kv_args(L, g)); }
     // Qwen2DecoderLayer stack (modeling_qwen2.py:269-299) over the concatenated new rows of one or several envs:
     // the dense products run once on all rows; RoPE + KV append and attention run per env (own pages / positions).
     // n_dec > 0 (mixed iteration of the multi-env scheduler): rows [0, n_dec) are single-token decode rows of n_dec other envs
@@ -870,23 +892,12 @@ public:
             const bool probing = taps && i == probe_layer;
             if (probing) { probe_copy(0, x, M); probe_rows = M; }
             if (!xn_ready) launch_rmsnorm<T>(st, x, L.in_norm, xn, M, H, c.rms_eps);
-            // one env's turn alone in the batch: the QKV product's split-K reduce also applies RoPE and appends k / v to its pages
-            RopeKvArgs r0; r0.qkv = qkv; r0.ld = qkv_dim; r0.Kpool = L.kpool; r0.Vpool = L.vpool; r0.rope_tab = rope_tab;
-            r0.nq = nq; r0.nkv = nkv; r0.dyn_pos = nullptr;
-            GemmArgs aq = gemm_args(xn, H, L.qkv_w, H, qkv, qkv_dim, L.qkv_b, nullptr, 0, 0, M, qkv_dim, H, EPI_NONE);
-            if (segs.size() == 1 && n_dec == 0) { r0.page_table = segs[0].e->d_pages; r0.T = segs[0].Tn; r0.P = segs[0].P; aq.rope = &r0; }
             if (probing) probe_copy(6, xn, M);
-            const bool roped = llm_gemm(aq, L.qkv8);
-            if (n_dec > 0) {
-                AttnArgs a = batched_decode_attn_args(L, n_dec);
-                launch_attention<T>(st, a, 128, 1);
-                launch_attention_combine<T>(st, a, 128);
-            }
+            const bool roped = prefill_qkv(L, M, segs.size() == 1 && n_dec == 0 ? &segs[0] : nullptr);
+            if (n_dec > 0) decode_attention(batched_decode_attn_args(L, n_dec));
             for (const Seg& g : segs) {
                 T* q_g = qkv + (size_t)g.off * qkv_dim;
-                RopeKvArgs r = r0; r.qkv = q_g; r.page_table = g.e->d_pages;
-                r.T = g.Tn; r.P = g.P;
-                if (!roped) launch_rope_kv<T>(st, r);
+                if (!roped) prefill_rope_append(L, g);
                 AttnArgs a = llm_attn_args(L, *g.e, q_g, qkv_dim, attn + (size_t)g.off * qd, qd, g.Tn, g.P, g.P + g.Tn, false);
                 launch_attention<T>(st, a, 128, 4);
                 if (a.nsplit > 1) launch_attention_combine<T>(st, a, 128);
@@ -911,11 +922,19 @@ public:
             }
         }
     }
+    // decode-step attention of layer L: one env (its page table, position / kv length in d_ctl) or B envs of the batched step (d_slots).
+    // q|k|v rows in qkv (un-roped; RoPE of q / k and the append of k / v^T are fused), output rows in attn.  op_attention_decode runs
+    // these same builders and launches.
+    AttnArgs decode_attn_args(const LLayer& L, const Env& e) { return llm_attn_args(L, e, qkv, qkv_dim, attn, nq * 128, 1, 0, 0, true); }
     AttnArgs batched_decode_attn_args(const LLayer& L, int B) {
-        AttnArgs a = llm_attn_args(L, envs[0], qkv, qkv_dim, attn, nq * 128, 1, 0, 0, true);
+        AttnArgs a = decode_attn_args(L, envs[0]);
         a.page_table = nullptr; a.dyn_kv_len = nullptr; a.dyn_pos = nullptr; a.skip = nullptr;
         a.slots = d_slots; a.batch = B; a.part_bstride = (size_t)nsplit_max * nkv * 32 * (128 + ATTN_PART_PAD);
         return a;
+    }
+    void decode_attention(const AttnArgs& a) {
+        launch_attention<T>(st, a, 128, 1);
+        launch_attention_combine<T>(st, a, 128);
     }
     void prefill(Env& e, int P, int Tn) {
         std::vector<Seg> segs{Seg{&e, P, Tn, 0}};
@@ -1017,8 +1036,7 @@ public:
             // op 1: layer 0's q|k|v rows; then per layer: decode attention (RoPE, KV append, per-page partials), the persistent layer
             if (on()) launch_gemv<T>(st, guarded(gemv_args(ll[0].qkv_w, H, x, ll[0].in_norm, ll[0].qkv_b, nullptr, qkv, qkv_dim, H, EPI_NONE)));
             for (int i = 0; i < c.layers; ++i) {
-                AttnArgs a = llm_attn_args(ll[i], e, qkv, qkv_dim, attn, qd, 1, 0, 0, true);
-                if (on()) launch_attention<T>(st, a, 128, 1);
+                if (on()) launch_attention<T>(st, decode_attn_args(ll[i], e), 128, 1);
                 if (on()) launch_decode_layer<T>(st, layer_args(i), n_cus);
             }
             return;
@@ -1026,7 +1044,7 @@ public:
         for (int i = 0; i < c.layers; ++i) {
             const LLayer& L = ll[i];
             if (on()) launch_gemv<T>(st, guarded(with8(gemv_args(L.qkv_w, H, x, L.in_norm, L.qkv_b, nullptr, qkv, qkv_dim, H, EPI_NONE), L.qkv8)));
-            AttnArgs a = llm_attn_args(L, e, qkv, qkv_dim, attn, qd, 1, 0, 0, true);
+            const AttnArgs a = decode_attn_args(L, e);
             if (on()) launch_attention<T>(st, a, 128, 1);
             if (on()) launch_attention_combine<T>(st, a, 128);
             if (on()) launch_gemv<T>(st, guarded(with8(gemv_args(L.o_w, qd, attn, nullptr, nullptr, x, x, H, qd, EPI_NONE), L.o8)));
@@ -1160,9 +1178,7 @@ public:
             if (!xn_ready) launch_rmsnorm<T>(st, x, L.in_norm, xn, B, H, c.rms_eps);
             if (mfma) llm_gemm(gemm_args(xn, H, L.qkv_w, H, qkv, qkv_dim, L.qkv_b, nullptr, 0, 0, B, qkv_dim, H, EPI_NONE), L.qkv8);
             else launch_gemv_batched<T>(st, gemvb_args(L.qkv_w, H, xn, H, nullptr, L.qkv_b, nullptr, 0, qkv, qkv_dim, qkv_dim, H, EPI_NONE, B));
-            AttnArgs a = batched_decode_attn_args(L, B);
-            launch_attention<T>(st, a, 128, 1);
-            launch_attention_combine<T>(st, a, 128);
+            decode_attention(batched_decode_attn_args(L, B));
             if (mfma) {
                 GemmArgs ao = gemm_args(attn, qd, L.o_w, qd, x, H, nullptr, x, H, 0, B, H, qd, EPI_NONE);
                 ao.norm_w = L.post_norm; ao.norm_out = xn; ao.norm_eps = c.rms_eps;
@@ -1785,19 +1801,116 @@ public:
     void op_layernorm(const void* xi, const void* g, const void* b, void* y, int rows, int n, float eps) override {
         launch_layernorm<T>(st, xi, g, b, y, rows, n, eps); sync();
     }
+    // ---- attention ops.  An op resets the envs it uses on entry (never on exit: svln_op_kv_read sees what the op wrote) and gives each
+    // the pages op_set_pages fixed for it, in that order, or else pages from the free list.
+    std::vector<std::vector<int>> op_pages;
+    void op_env_begin(int env, int positions) {
+        Env& e = env_at(env);
+        reset_env(env);
+        const std::vector<int> want = env < (int)op_pages.size() ? op_pages[env] : std::vector<int>();
+        if (want.empty()) { ensure_pages(e, positions); return; }
+        const int need = (positions + PAGE - 1) / PAGE;
+        REQUIRE(need <= (int)want.size(), "op_set_pages: fewer pages than the op's positions need");
+        for (int i = 0; i < need; ++i) {
+            auto it = std::find(free_pages.begin(), free_pages.end(), want[i]);
+            REQUIRE(it != free_pages.end(), "op_set_pages: page is held by another env");
+            free_pages.erase(it);
+            e.pages[e.n_pages++] = want[i];
+        }
+        HIP_CHECK(hipMemcpyAsync(e.d_pages, e.pages.data(), need * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    void op_set_pages(int env, const int32_t* pages, int n) override {
+        env_at(env);
+        REQUIRE(n >= 0 && n <= pages_per_env && (n == 0 || pages), "op_set_pages: 0 .. pages_per_env pages");
+        std::vector<int> v(pages, pages + n);
+        for (int p : v) REQUIRE(p >= 0 && p < pages_total, "op_set_pages: page out of range");
+        if ((int)op_pages.size() < c.max_envs) op_pages.resize(c.max_envs);
+        op_pages[env] = v;
+    }
+    static void host_from_f32(float v, float& out) { out = v; }
+    static void host_from_f32(float v, bf16& out) {       // round to nearest even (finite values)
+        uint32_t u; std::memcpy(&u, &v, 4);
+        const unsigned short b = (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+        std::memcpy(&out, &b, 2);
+    }
+    // layer-0 K / V^T pools := pool_value (rounded to the engine dtype; finite: masked keys meet stale data in production too),
+    // split-KV partials := NaN (part_nan): a slot an op leaves unwritten, or a partial the merge reads without a workgroup having
+    // written it, then shows in the output
+    void op_fill_attn_state(float pool_value, int part_nan) override {
+        REQUIRE(std::isfinite(pool_value), "the pool value must be finite");
+        const LLayer& L = ll[0];
+        const size_t n = (size_t)pages_total * nkv * PAGE * 128;
+        T v; host_from_f32(pool_value, v);
+        std::vector<T> h(n, v);
+        sync();
+        HIP_CHECK(hipMemcpy(L.kpool, h.data(), n * sizeof(T), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(L.vpool, h.data(), n * sizeof(T), hipMemcpyHostToDevice));
+        if (part_nan) HIP_CHECK(hipMemsetAsync(attn_part, 0xff, attn_part_elems * sizeof(float), st));
+        sync();
+    }
+    // roped K and V rows of positions [start, start + n) of env's layer-0 pages -> fp32 [n][nkv][128] each.  env = -1: the raw pools,
+    // position p = slot p % 64 of physical page p / 64 (every page, whoever holds it)
+    void op_kv_read(int env, int start, int n, float* k_out, float* v_out) override {
+        REQUIRE(k_out && v_out, "null output pointer");
+        const int limit = env < 0 ? pages_total * PAGE : env_at(env).n_pages * PAGE;
+        REQUIRE(start >= 0 && n >= 0 && start + n <= limit, "op_kv_read: positions outside the env's pages");
+        const LLayer& L = ll[0];
+        const size_t page_elems = (size_t)nkv * PAGE * 128;
+        std::vector<T> kp(page_elems), vp(page_elems);
+        sync();
+        for (int pg = start / PAGE; pg * PAGE < start + n; ++pg) {
+            const int phys = env < 0 ? pg : envs[env].pages[pg];
+            HIP_CHECK(hipMemcpy(kp.data(), L.kpool + (size_t)phys * page_elems, page_elems * sizeof(T), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(vp.data(), L.vpool + (size_t)phys * page_elems, page_elems * sizeof(T), hipMemcpyDeviceToHost));
+            for (int off = 0; off < PAGE; ++off) {
+                const int p = pg * PAGE + off;
+                if (p < start || p >= start + n) continue;
+                for (int kh = 0; kh < nkv; ++kh)
+                    for (int d = 0; d < 128; ++d) {
+                        const size_t o = ((size_t)(p - start) * nkv + kh) * 128 + d;
+                        k_out[o] = host_to_f32(kp[((size_t)kh * PAGE + off) * 128 + d]);
+                        v_out[o] = host_to_f32(vp[((size_t)kh * 128 + d) * PAGE + off]);
+                    }
+            }
+        }
+    }
+    // the prefill q|k|v product of one env's turn on layer 0 (env 0, positions P .. P + T - 1) through prefill_qkv / prefill_rope_append,
+    // as prefill_rows runs it: x = the normed input rows [T][hidden]; the roped q rows -> q_out, k / v in the env's pages;
+    // *fused = 1 when the product's split-K reduce did the RoPE + append, 0 when launch_rope_kv did
+    void op_llm_qkv_rope(const void* xin, int Tn, int P, void* q_out, int q_stride, int32_t* fused) override {
+        REQUIRE(xin && q_out && fused, "null pointer");
+        REQUIRE(Tn >= 1 && P >= 0 && P + Tn <= c.max_positions, "positions out of range");
+        REQUIRE(q_stride >= nq * 128, "q_stride");
+        Env& e = env_at(0);
+        op_env_begin(0, P + Tn);
+        const LLayer& L = ll[0];
+        HIP_CHECK(hipMemcpyAsync(xn, xin, (size_t)Tn * H * sizeof(T), hipMemcpyDeviceToDevice, st));
+        const Seg g{&e, P, Tn, 0};
+        const bool roped = prefill_qkv(L, Tn, &g);
+        if (!roped) prefill_rope_append(L, g);
+        HIP_CHECK(hipMemcpy2DAsync(q_out, (size_t)q_stride * sizeof(T), qkv, (size_t)qkv_dim * sizeof(T), (size_t)nq * 128 * sizeof(T), Tn,
+                                   hipMemcpyDeviceToDevice, st));
+        sync();
+        LAUNCH_CHECK("op_llm_qkv_rope");
+        *fused = roped ? 1 : 0;
+    }
+    void op_rope_append(Env& e, const LLayer& L, void* rows, int ld, int Tn, int P) {
+        RopeKvArgs r; r.Kpool = L.kpool; r.Vpool = L.vpool; r.page_table = e.d_pages; r.rope_tab = rope_tab; r.nq = nq; r.nkv = nkv; r.dyn_pos = nullptr;
+        r.ld = ld; r.qkv = rows; r.T = Tn; r.P = P;
+        launch_rope_kv<T>(st, r);
+    }
     // LLM attention on layer-0 pools / env 0: context rows (ctx_T positions from 0) are roped + appended first, then the T new rows
     void op_attention_llm(void* qkv_new, int ld, int Tn, int P, const void* ctx, int ctx_T, void* out, int o_stride, int nsplit) override {
         Env& e = env_at(0);
         REQUIRE(ctx_T == P, "context length must equal P");
-        reset_env(0);
-        ensure_pages(e, P + Tn);
+        op_env_begin(0, P + Tn);
         const LLayer& L = ll[0];
-        RopeKvArgs r; r.Kpool = L.kpool; r.Vpool = L.vpool; r.page_table = e.d_pages; r.rope_tab = rope_tab; r.nq = nq; r.nkv = nkv; r.dyn_pos = nullptr;
-        r.ld = ld;
-        if (ctx_T > 0) { r.qkv = const_cast<void*>(ctx); r.T = ctx_T; r.P = 0; launch_rope_kv<T>(st, r); }
-        r.qkv = qkv_new; r.T = Tn; r.P = P; launch_rope_kv<T>(st, r);
+        if (ctx_T > 0) op_rope_append(e, L, const_cast<void*>(ctx), ld, ctx_T, 0);
+        op_rope_append(e, L, qkv_new, ld, Tn, P);
         AttnArgs a = llm_attn_args(L, e, qkv_new, ld, out, o_stride, Tn, P, P + Tn, false);
-        if (nsplit > 1) {           // decode-style: one wave per kv head and key page
+        if (nsplit > 1) {
+            // split-KV with one wave per kv head and key page: attn_kernel<T, 128, 1>, which the engine itself never launches (its decode
+            // steps take attn_decode_kernel through decode_attn_args, with fused RoPE + append: op_attention_decode tests that one)
             REQUIRE(Tn * (nq / nkv) <= 32, "split-KV path takes at most 32 rows per kv head");
             a.nsplit = nsplit_max; a.tiles_per_split = tiles_per_split; a.rows_pad = 32;
             launch_attention<T>(st, a, 128, 1);
@@ -1807,7 +1920,44 @@ public:
             if (a.nsplit > 1) launch_attention_combine<T>(st, a, 128);
         }
         sync();
-        reset_env(0);
+    }
+    // one decode step of B envs on layer 0, through the engine's own decode attention (decode_attn_args / batched_decode_attn_args +
+    // decode_attention).  Env b first gets pos[b] context rows (ctx + b * ctx_rows * ld, roped in place + appended like
+    // op_attention_llm); then its un-roped q|k|v row qkv_new[b] is decoded at position pos[b] (RoPE, K / V append, attention, merge).
+    // B == 1 takes the single-env step (d_ctl), B > 1 the batched step (d_slots).
+    void op_attention_decode(int B, const void* ctx, int ld, int64_t ctx_rows, const int32_t* pos, const void* qkv_new, void* out,
+                             int o_stride) override {
+        REQUIRE(B == 1 || B == 2 || B == 4 || B == 8, "B must be 1, 2, 4 or 8");
+        REQUIRE(B <= c.max_envs, "B exceeds max_envs");
+        REQUIRE(pos && qkv_new && out, "null pointer");
+        REQUIRE(ld >= qkv_dim && o_stride >= nq * 128, "row strides");
+        const LLayer& L = ll[0];
+        for (int b = 0; b < B; ++b) {
+            REQUIRE(pos[b] >= 0 && pos[b] < c.max_positions && pos[b] <= ctx_rows, "decode position out of range");
+            REQUIRE(pos[b] == 0 || ctx, "null context rows");
+            reset_env(b);
+        }
+        for (int b = 0; b < B; ++b) {
+            Env& e = env_at(b);
+            op_env_begin(b, pos[b] + 1);
+            if (pos[b] > 0) op_rope_append(e, L, (char*)const_cast<void*>(ctx) + (size_t)b * ctx_rows * ld * sizeof(T), ld, pos[b], 0);
+        }
+        HIP_CHECK(hipMemcpy2DAsync(qkv, (size_t)qkv_dim * sizeof(T), qkv_new, (size_t)ld * sizeof(T), (size_t)qkv_dim * sizeof(T), B,
+                                   hipMemcpyDeviceToDevice, st));
+        if (B == 1) {
+            h_ctl->pos = pos[0]; h_ctl->kv_len = pos[0] + 1; h_ctl->done = 0; h_ctl->count = 0; h_ctl->max_new = 0; h_ctl->n_eos = 0;
+            h_ctl->pad0 = h_ctl->pad1 = 0;
+            HIP_CHECK(hipMemcpyAsync(d_ctl, h_ctl, sizeof(GenCtl), hipMemcpyHostToDevice, st));
+            decode_attention(decode_attn_args(L, env_at(0)));
+        } else {
+            for (int b = 0; b < B; ++b) { h_slots[b].page_table = envs[b].d_pages; h_slots[b].pos = pos[b]; h_slots[b].pad = 0; }
+            HIP_CHECK(hipMemcpyAsync(d_slots, h_slots, B * sizeof(DecodeSlot), hipMemcpyHostToDevice, st));
+            decode_attention(batched_decode_attn_args(L, B));
+        }
+        HIP_CHECK(hipMemcpy2DAsync(out, (size_t)o_stride * sizeof(T), attn, (size_t)nq * 128 * sizeof(T), (size_t)nq * 128 * sizeof(T), B,
+                                   hipMemcpyDeviceToDevice, st));
+        sync();
+        LAUNCH_CHECK("op_attention_decode");
     }
     void op_attention_vit(const void* qkv_buf, int ld, int F, void* out, int o_stride) override {
         REQUIRE(F >= 1 && F <= c.max_frames, "frames");
@@ -2013,6 +2163,16 @@ int svln_op_attention_llm(svln_engine* h, void* qkv, int ld, int T, int P, const
     API_BEGIN_H h->impl->op_attention_llm(qkv, ld, T, P, ctx, ctx_T, out, o_stride, nsplit); API_END
 }
 int svln_op_attention_vit(svln_engine* h, const void* qkv, int ld, int F, void* out, int o_stride) { API_BEGIN_H h->impl->op_attention_vit(qkv, ld, F, out, o_stride); API_END }
+int svln_op_attention_decode(svln_engine* h, int B, const void* ctx_qkv, int ld, int64_t ctx_rows, const int32_t* pos, const void* qkv_new, void* out,
+                             int o_stride) {
+    API_BEGIN_H h->impl->op_attention_decode(B, ctx_qkv, ld, ctx_rows, pos, qkv_new, out, o_stride); API_END
+}
+int svln_op_kv_read(svln_engine* h, int env, int start, int n, float* k_out, float* v_out) { API_BEGIN_H h->impl->op_kv_read(env, start, n, k_out, v_out); API_END }
+int svln_op_llm_qkv_rope(svln_engine* h, const void* x, int T, int P, void* q_out, int q_stride, int32_t* fused) {
+    API_BEGIN_H h->impl->op_llm_qkv_rope(x, T, P, q_out, q_stride, fused); API_END
+}
+int svln_op_set_pages(svln_engine* h, int env, const int32_t* pages, int n) { API_BEGIN_H h->impl->op_set_pages(env, pages, n); API_END }
+int svln_op_fill_attn_state(svln_engine* h, float pool_value, int part_nan) { API_BEGIN_H h->impl->op_fill_attn_state(pool_value, part_nan); API_END }
 int svln_op_pool(svln_engine* h, const void* in, void* out, int F) { API_BEGIN_H h->impl->op_pool(in, out, F); API_END }
 int svln_op_patchify(svln_engine* h, const float* pix, void* out, int F) { API_BEGIN_H h->impl->op_patchify(pix, out, F); API_END }
 
