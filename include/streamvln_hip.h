@@ -264,6 +264,17 @@ int svln_op_llm_qkv_rope(svln_engine* h, const void* x, int T, int P, void* q_ou
 int svln_op_set_pages(svln_engine* h, int env, const int32_t* pages, int n);
 /* test control: fill the layer-0 K / V pools with a finite value and (part_nan) the split-KV partial workspace with NaN */
 int svln_op_fill_attn_state(svln_engine* h, float pool_value, int part_nan);
+/* ViT layer `layer`'s q|k|v product and attention as the vision tower runs them (the product packs the K / V^T pages where its launch
+ * can): x = the normed rows [F * 729][v_hidden] (device), qkv_out [F * 729][3 * v_hidden], attn_out [F * 729][o_stride]; *packer = the
+ * writer of the pages: 0 = the standalone packer, 1 = the split-K reduce, 2 = the 128x128 tile epilogue.  force_split: 0 = the
+ * engine's own launch choice; > 1 = that many K splits (tests: the reduce's fused pack at shapes where the engine does not split) */
+int svln_op_vit_qkv_attention(svln_engine* h, int layer, const void* x, int F, void* qkv_out, void* attn_out, int o_stride,
+                              int force_split, int32_t* packer);
+/* test control: fill the ViT K / V^T pools with a finite value and (part_nan) the split-KV partial workspace with NaN */
+int svln_op_fill_vit_state(svln_engine* h, float pool_value, int part_nan);
+/* the raw ViT pools over their whole allocation (pages = key tiles * max_frames * v_heads) -> host fp32 K [page][64][HDP] and
+ * V^T [page][VROWS][64] (HDP = head dim padded to an even number of 16-byte chunks, VROWS = 96) */
+int svln_op_vit_kv_read(svln_engine* h, float* k_out, float* v_out);
 int svln_op_pool(svln_engine* h, const void* in, void* out, int F);
 int svln_op_patchify(svln_engine* h, const float* pix, void* out, int F);
 

@@ -111,6 +111,9 @@ SIGNATURES = {
     "svln_op_llm_qkv_rope": (_I, [_P, _P, _I, _I, _P, _I, _PI32]),
     "svln_op_set_pages": (_I, [_P, _I, _PI32, _I]),
     "svln_op_fill_attn_state": (_I, [_P, _F, _I]),
+    "svln_op_vit_qkv_attention": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _PI32]),
+    "svln_op_fill_vit_state": (_I, [_P, _F, _I]),
+    "svln_op_vit_kv_read": (_I, [_P, _PF, _PF]),
     "svln_op_pool": (_I, [_P, _P, _P, _I]),
     "svln_op_patchify": (_I, [_P, _P, _P, _I]),
 }

@@ -126,6 +126,10 @@ struct EngineBase {
     virtual void op_llm_qkv_rope(const void* x, int T, int P, void* q_out, int q_stride, int32_t* fused) = 0;
     virtual void op_set_pages(int env, const int32_t* pages, int n) = 0;
     virtual void op_fill_attn_state(float pool_value, int part_nan) = 0;
+    virtual void op_vit_qkv_attention(int layer, const void* x, int F, void* qkv_out, void* attn_out, int o_stride, int force_split,
+                                      int32_t* packer) = 0;
+    virtual void op_fill_vit_state(float pool_value, int part_nan) = 0;
+    virtual void op_vit_kv_read(float* k_out, float* v_out) = 0;
     virtual void op_pool(const void* in, void* out, int F) = 0;
     virtual void op_patchify(const float* pix, void* out, int F) = 0;
 };
@@ -510,6 +514,20 @@ public:
         launch_attention<T>(st, a, vhd, 4);
         if (a.nsplit > 1) launch_attention_combine<T>(st, a, vhd);
     }
+    // q|k|v product of one SigLIP layer on the normed rows x [F*S][Hv] -> qkv_out [F*S][3 Hv] and its attention -> attn_out [F*S][o_stride]
+    // (siglip_encoder.py:197-232).  The product also packs the K / V^T pages where its launch can (one frame: the split-K reduce or the
+    // tile epilogue), else vit_attention packs them.  Returns the writer of the pages (launch_gemm's vit_packer: 0, 1 or 2).
+    // run_vit and op_vit_qkv_attention run this member; force_split (tests, GemmArgs::force_split) is 0 on the engine's path.
+    int vit_qkv_attention(const VLayer& L, const T* x, int F, T* qkv_out, T* attn_out, int o_stride, int force_split = 0) {
+        GemmArgs aq = gemm_args(x, Hv, L.qkv_w, Hv, qkv_out, 3 * Hv, L.qkv_b, nullptr, 0, 0, F * S, 3 * Hv, Hv, EPI_NONE);
+        aq.force_split = force_split;
+        const VitPackArgs vpk{vkpool, vvpool, F, S, vheads, vhd};
+        aq.vitpack = &vpk;
+        int packer = 0;
+        const bool packed = launch_gemm<T>(st, aq, &packer);
+        vit_attention(qkv_out, 3 * Hv, F, attn_out, o_stride, packed);
+        return packer;
+    }
     // SigLIP tower + projector + pool on F frames of `pixbuf` (fp32 [F,3,S,S]) -> dst [F*otok][H]
     void run_vit(const float* pixbuf, int F, T* dst) {
         const int M = F * S;
@@ -520,12 +538,7 @@ public:
         for (int i = 0; i < c.v_layers; ++i) {      // SigLipEncoderLayer (siglip_encoder.py:269-305)
             const VLayer& L = vl[i];
             if (!vn_ready) launch_layernorm<T>(st, vx, L.ln1_w, L.ln1_b, vn, M, Hv, c.v_eps);
-            // (one frame: the product runs split-K and its slab reduce also packs the K / V^T pages of the attention)
-            GemmArgs aq = gemm_args(vn, Hv, L.qkv_w, Hv, vqkv, 3 * Hv, L.qkv_b, nullptr, 0, 0, M, 3 * Hv, Hv, EPI_NONE);
-            const VitPackArgs vpk{vkpool, vvpool, F, S, vheads, vhd};
-            aq.vitpack = &vpk;
-            const bool packed = launch_gemm<T>(st, aq);
-            vit_attention(vqkv, 3 * Hv, F, vattn, Hv, packed);
+            vit_qkv_attention(L, vn, F, vqkv, vattn, Hv);
             // out_proj / fc2 run split-K at one frame: their slab reduce also emits the following LayerNorm
             GemmArgs ao = gemm_args(vattn, Hv, L.out_w, Hv, vx, Hv, L.out_b, vx, Hv, 0, M, Hv, Hv, EPI_NONE);
             ao.norm_w = L.ln2_w; ao.norm_b = L.ln2_b; ao.norm_out = vn; ao.norm_eps = c.v_eps;
@@ -1963,6 +1976,45 @@ public:
         REQUIRE(F >= 1 && F <= c.max_frames, "frames");
         vit_attention(qkv_buf, ld, F, out, o_stride); sync();
     }
+    // ViT layer `layer`'s q|k|v product + attention through vit_qkv_attention, as run_vit runs it, on caller buffers: x [F*S][Hv] (the
+    // normed rows), qkv_out [F*S][3 Hv], attn_out [F*S][o_stride]; *packer = the writer of the K / V^T pages (0 = launch_vit_kv_pack,
+    // 1 = the split-K reduce, 2 = the tile epilogue).  force_split > 1: the product takes that many K splits (GemmArgs::force_split; the
+    // reduce's fused pack is reached this way where no real shape of the dtype takes it), 0 = the engine's choice
+    void op_vit_qkv_attention(int layer, const void* x, int F, void* qkv_out, void* attn_out, int o_stride, int force_split,
+                              int32_t* packer) override {
+        REQUIRE(layer >= 0 && layer < c.v_layers, "layer out of range");
+        REQUIRE(F >= 1 && F <= c.max_frames, "frames");
+        REQUIRE(force_split == 0 || force_split > 1, "force_split: 0 or > 1");
+        REQUIRE(x && qkv_out && attn_out && packer, "null pointer");
+        REQUIRE(o_stride >= Hv, "o_stride");
+        const int pk = vit_qkv_attention(vl[layer], (const T*)x, F, (T*)qkv_out, (T*)attn_out, o_stride, force_split);
+        sync();
+        LAUNCH_CHECK("op_vit_qkv_attention");
+        *packer = pk;
+    }
+    // ViT K / V^T pools := pool_value (rounded to the engine dtype), split-KV partials := NaN (part_nan): see op_fill_attn_state
+    void op_fill_vit_state(float pool_value, int part_nan) override {
+        REQUIRE(std::isfinite(pool_value), "the pool value must be finite");
+        const size_t pages = (size_t)vtiles * c.max_frames * vheads, nk = pages * PAGE * vhdp, nv = pages * vvrows * PAGE;
+        T v; host_from_f32(pool_value, v);
+        std::vector<T> h(nk > nv ? nk : nv, v);
+        sync();
+        HIP_CHECK(hipMemcpy(vkpool, h.data(), nk * sizeof(T), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(vvpool, h.data(), nv * sizeof(T), hipMemcpyHostToDevice));
+        if (part_nan) HIP_CHECK(hipMemsetAsync(attn_part, 0xff, attn_part_elems * sizeof(float), st));
+        sync();
+    }
+    // the raw ViT pools over the whole allocation (vtiles * max_frames * heads pages) -> fp32 k_out [page][64][HDP], v_out [page][VROWS][64]
+    void op_vit_kv_read(float* k_out, float* v_out) override {
+        REQUIRE(k_out && v_out, "null output pointer");
+        const size_t pages = (size_t)vtiles * c.max_frames * vheads, nk = pages * PAGE * vhdp, nv = pages * vvrows * PAGE;
+        std::vector<T> h(nk > nv ? nk : nv);
+        sync();
+        HIP_CHECK(hipMemcpy(h.data(), vkpool, nk * sizeof(T), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < nk; ++i) k_out[i] = host_to_f32(h[i]);
+        HIP_CHECK(hipMemcpy(h.data(), vvpool, nv * sizeof(T), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < nv; ++i) v_out[i] = host_to_f32(h[i]);
+    }
     void op_pool(const void* in, void* out, int F) override { launch_pool<T>(st, in, out, tap_idx, tap_w, F, side, oside, H); sync(); }
     void op_patchify(const float* p, void* out, int F) override { launch_patchify<T>(st, p, out, F, c.v_image, c.v_patch, kp); sync(); }
 };
@@ -2173,6 +2225,12 @@ int svln_op_llm_qkv_rope(svln_engine* h, const void* x, int T, int P, void* q_ou
 }
 int svln_op_set_pages(svln_engine* h, int env, const int32_t* pages, int n) { API_BEGIN_H h->impl->op_set_pages(env, pages, n); API_END }
 int svln_op_fill_attn_state(svln_engine* h, float pool_value, int part_nan) { API_BEGIN_H h->impl->op_fill_attn_state(pool_value, part_nan); API_END }
+int svln_op_vit_qkv_attention(svln_engine* h, int layer, const void* x, int F, void* qkv_out, void* attn_out, int o_stride, int force_split,
+                              int32_t* packer) {
+    API_BEGIN_H h->impl->op_vit_qkv_attention(layer, x, F, qkv_out, attn_out, o_stride, force_split, packer); API_END
+}
+int svln_op_fill_vit_state(svln_engine* h, float pool_value, int part_nan) { API_BEGIN_H h->impl->op_fill_vit_state(pool_value, part_nan); API_END }
+int svln_op_vit_kv_read(svln_engine* h, float* k_out, float* v_out) { API_BEGIN_H h->impl->op_vit_kv_read(k_out, v_out); API_END }
 int svln_op_pool(svln_engine* h, const void* in, void* out, int F) { API_BEGIN_H h->impl->op_pool(in, out, F); API_END }
 int svln_op_patchify(svln_engine* h, const float* pix, void* out, int F) { API_BEGIN_H h->impl->op_patchify(pix, out, F); API_END }
 

@@ -57,7 +57,9 @@ struct GemmArgs {
     VitPackArgs vp; int vp_on;    // filled by the launcher: device-side copy of *vitpack for the unsplit kernels that pack in their epilogue
     int force_cfg, force_split;   // tests: 0 = heuristic; force_cfg 129 -> 128x128 tiles with two in-workgroup K groups; force_cfg low bits 128 -> 128x128 tiles, 264 -> 256x64 tiles; force_split S -> 256x128 tiles, S splits
 };
-template <typename T> bool launch_gemm(hipStream_t s, const GemmArgs& a);   // true: a.norm_out was produced
+// true: a.norm_out was produced, or the K / V^T pages of a.vitpack were.  vit_packer (host, optional): the writer of those pages --
+// 0 = none (the caller runs launch_vit_kv_pack), 1 = the split-K reduce (splitk_qkv_vitpack_kernel), 2 = the 128x128 tile epilogue
+template <typename T> bool launch_gemm(hipStream_t s, const GemmArgs& a, int* vit_packer = nullptr);
 template <typename T> int launch_gemm_argmax(hipStream_t s, GemmArgs a);    // EPI_ARGMAX form (M <= 32); returns the partials per row
 
 // y[N] = epi(W[N,K] . x'[K] + bias) + res,  x' = x or rmsnorm(x) * norm_w (fused prologue).

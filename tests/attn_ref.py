@@ -215,11 +215,9 @@ class Case:
         kk = k.repeat_interleave(self.G, 1)
         qpos = torch.as_tensor(self.qpos, device=device)
         vis = (torch.arange(self.L, device=device)[None] <= qpos[:, None]).double()     # [R, L]
-        prod = torch.einsum("rhd,shd->rhs", q.abs(), kk.abs()) * self.scale * vis[:, None]
-        A = prod.amax(-1)                                                                 # [R, nq]
-        coef = 2 * u + 2 * (128 * e * A + 8 * e) + 2 * self.L * e
         mv = self.v.to(device).abs().amax(-1).amax(0).repeat_interleave(self.G)          # [nq]
-        tol = (coef * mv[None])[..., None]
+        tol = rounding_tolerance(q, kk, vis, self.scale, mv, self.dtype, self.L)
+        A = (torch.einsum("rhd,shd->rhs", q.abs(), kk.abs()) * self.scale * vis[:, None]).amax(-1)
         if q_flips:
             if self.dtype == torch.bfloat16:
                 term = (q.abs()[:, :, None, :] * kk.abs().permute(1, 0, 2)[None]).amax(-1) * self.scale     # [R, nq, L]
@@ -234,6 +232,15 @@ class Case:
             sens = torch.einsum("rhs,rhsd->rhd", p, (vv.permute(1, 0, 2)[None] - out[:, :, None]).abs())
             tol = tol + 2 * ds[..., None] * sens
         return tol
+
+
+def rounding_tolerance(q, kk, vis, scale, mv, dtype, L, hd=HD):
+    """the part of Case.tolerance without q flips (see there), for hd-term dot products: q [R, H, hd], keys kk [L, H, hd], vis [R, L]
+    (1 = visible key), mv [H] = max |V| of the head's keys -> [R, H, 1]"""
+    u, e = EPS[dtype], 2.0 ** -24
+    A = (torch.einsum("rhd,shd->rhs", q.abs(), kk.abs()) * scale * vis[:, None]).amax(-1)         # [R, H]
+    coef = 2 * u + 2 * (hd * e * A + 8 * e) + 2 * L * e
+    return (coef * mv[None])[..., None]
 
 
 MUTANTS = ["drop_newest", "admit_masked", "diag_shift", "rope_off", "no_rescale", "page_swap", "stale_k", "drop_split"]
@@ -316,3 +323,172 @@ def prefill_mutants(cfg, T, P):
     if ns > 1:
         m.append("drop_split")
     return m
+
+
+# ---------------------------------------------------------------------------------------------------------- ViT
+# SigLIP attention (siglip_encoder.py:197-232): per frame and head, 729 query rows against the frame's 729 keys, non-causal, head_dim 72,
+# no RoPE.  The engine packs K into pages [tile][F * heads][64][HDP] and V^T into [tile][F * heads][96][64] (12 key tiles, the last one
+# holding 25 keys), then runs either the plain 4-wave kernel over all 12 tiles or, when that would be too few workgroups, key groups:
+# group g of KG walks tiles g, g + KG, ... and the groups' (m, l, O) are merged through LDS with exp2(m_g - M).
+VHD = 72
+VS = 729
+VTILES = (VS + PAGE - 1) // PAGE
+VROWS = 96
+VIT_PATTERNS = ["key0", "self", "key63", "rising", "key64", "key703", "two", "group_first", "key728", "falling"]
+VIT_CASES = [("tiny", 1), ("tiny", 3), ("true_dims_1layer", 1), ("true_dims_1layer", 2), ("true_dims_1layer", 9)]
+
+
+def vit_hdp(dtype):
+    """padded K row of the ViT pools: 72 rounded to an even number of 16-byte chunks"""
+    epc = 8 if dtype == torch.bfloat16 else 4
+    return ((((VHD + epc - 1) // epc) + 1) & ~1) * epc
+
+
+def vit_key_groups(cfg, F, dtype):
+    """KG of the engine's ViT attention (vit_attn_args): key groups when the plain kernel would have fewer than 192 workgroups
+    (attn_key_groups: 4 for bf16, 3 for fp32), else 1 (the plain kernel)"""
+    if ((VS + 127) // 128) * F * cfg.v_heads < 192:
+        return 4 if dtype == torch.bfloat16 else 3
+    return 1
+
+
+class VitCase:
+    """F frames of ViT q / k / v [F, 729, heads, 72] (float64 holding dtype values) and their float64 attention, tolerance and mutants.
+    rows: the query rows evaluated (all 729 by default)."""
+
+    def __init__(self, cfg, dtype, F, q, k, v, rows=None):
+        self.cfg, self.dtype, self.F = cfg, dtype, F
+        self.heads = cfg.v_heads
+        self.KG = vit_key_groups(cfg, F, dtype)
+        self.q, self.k, self.v = q, k, v
+        self.rows = torch.arange(VS) if rows is None else torch.as_tensor(rows)
+        self.scale = VHD ** -0.5
+
+    def qkv_rows(self):
+        """[F * 729, 3 * heads * 72] q | k | v rows as the engine's qkv buffer holds them"""
+        n = self.F * VS
+        return torch.cat([self.q.reshape(n, -1), self.k.reshape(n, -1), self.v.reshape(n, -1)], 1)
+
+    def mutants(self):
+        m = ["drop_last_tile", "admit_pad", "no_rescale", "wrong_frame", "vt_swap"]
+        if self.KG > 1:
+            m += [f"drop_group{g}" for g in range(self.KG)] + ["merge_no_rescale"]
+        else:
+            m += ["drop_tile1"]
+        return m
+
+    def attend(self, mutant=None, device="cpu"):
+        """float64 attention of the evaluated rows -> [F, R, heads, 72].  mutant: None or one of self.mutants():
+          drop_last_tile  the partial tile (keys 704 .. 728) left out
+          admit_pad       keys 729 .. 767 of the last tile admitted (the packers zero them)
+          drop_group<g>   key group g's tiles left out of the merge; drop_tile1: tile 1 left out (plain kernel)
+          no_rescale      online softmax whose O is never rescaled when the running max moves (per key group; merge right)
+          merge_no_rescale  key groups right, merged without exp2(m_g - M)
+          wrong_frame     frame f reads frame f + 1's pages (F >= 2), or head h reads head h + 1's (F = 1)
+          vt_swap         V^T keys swapped between the two halves of every tile"""
+        keys = torch.arange(VTILES * PAGE, device=device)
+        allowed = keys < VS
+        tile = keys // PAGE
+        if mutant == "drop_last_tile":
+            allowed = keys < (VTILES - 1) * PAGE
+        elif mutant == "admit_pad":
+            allowed = torch.ones_like(allowed)
+        elif mutant is not None and mutant.startswith("drop_group"):
+            allowed = allowed & (tile % self.KG != int(mutant[len("drop_group"):]))
+        elif mutant == "drop_tile1":
+            allowed = allowed & (tile != 1)
+        out = []
+        for f in range(self.F):
+            q = self.q[f, self.rows].to(device)                                   # [R, H, 72]
+            k, v = self.k[f].to(device), self.v[f].to(device)                     # [729, H, 72]
+            if mutant == "wrong_frame":
+                k, v = (self.k[(f + 1) % self.F].to(device), self.v[(f + 1) % self.F].to(device)) if self.F > 1 else \
+                       (torch.roll(k, -1, 1), torch.roll(v, -1, 1))
+            pad = torch.zeros((VTILES * PAGE - VS,) + k.shape[1:], dtype=k.dtype, device=device)
+            k, v = torch.cat([k, pad]), torch.cat([v, pad])
+            if mutant == "vt_swap":
+                v = v[keys ^ 32]
+            s = torch.einsum("rhd,shd->rhs", q, k) * self.scale
+            s = s.masked_fill(~allowed[None, None], float("-inf"))
+            if mutant in ("no_rescale", "merge_no_rescale"):
+                out.append(self._grouped(s, v, online_rescale=mutant != "no_rescale", merge_rescale=mutant != "merge_no_rescale"))
+            else:
+                out.append(torch.einsum("rhs,shd->rhd", torch.nan_to_num(torch.softmax(s, -1)), v))
+        return torch.stack(out)
+
+    def _grouped(self, s, v, online_rescale, merge_rescale):
+        """the kernel's schedule: key group g walks tiles g, g + KG, ... with an online softmax, the groups are merged at the end"""
+        os_, ms, ls = [], [], []
+        for g in range(self.KG):
+            idx = torch.cat([torch.arange(t * PAGE, (t + 1) * PAGE) for t in range(g, VTILES, self.KG)]).to(s.device)
+            sg = s[..., idx]
+            m = torch.full(s.shape[:2], float("-inf"), dtype=s.dtype, device=s.device)
+            o = torch.zeros(s.shape[:2] + (VHD,), dtype=s.dtype, device=s.device)
+            for t0 in range(0, idx.numel(), PAGE):
+                st = sg[..., t0:t0 + PAGE]
+                mnew = torch.maximum(m, st.amax(-1))
+                if online_rescale:
+                    o = o * torch.nan_to_num(torch.exp(m - mnew))[..., None]
+                m = mnew
+                o = o + torch.einsum("rhs,shd->rhd", torch.nan_to_num(torch.exp(st - m[..., None])), v[idx[t0:t0 + PAGE]])
+            os_.append(o), ms.append(m), ls.append(torch.nan_to_num(torch.exp(sg - m[..., None])).sum(-1))
+        M = torch.stack(ms).amax(0)
+        w = [torch.nan_to_num(torch.exp(m - M)) if merge_rescale else torch.ones_like(M) for m in ms]
+        num = sum(wg[..., None] * og for wg, og in zip(w, os_))
+        den = sum(wg * lg for wg, lg in zip(w, ls))
+        return num / den.clamp_min(1e-300)[..., None]
+
+    def tolerance(self, device="cpu"):
+        """[F, R, heads, 1]: rounding_tolerance over the frame's 729 keys (no q flips: q is read as stored)"""
+        vis = torch.ones((len(self.rows), VS), dtype=torch.float64, device=device)
+        tol = []
+        for f in range(self.F):
+            mv = self.v[f].to(device).abs().amax(-1).amax(0)                  # [H]
+            tol.append(rounding_tolerance(self.q[f, self.rows].to(device), self.k[f].to(device), vis, self.scale, mv,
+                                          self.dtype, VS, hd=VHD))
+        return torch.stack(tol)
+
+
+def vit_case(cfg, dtype, F, rows=None):
+    """sharp ViT inputs, the LLM design in 72 dimensions (no RoPE): keys k[s] = a_s u + n_s per (frame, head) with sign vectors u, n_s
+    (u removed from n_s) and a_s = s / 728; V rows distinct (uniform in +-1).  Query row s of head h in frame f takes pattern
+    VIT_PATTERNS[(s + h + 3 f) % 10] (needle placements move from frame to frame):
+      key0 / key63 / key64 / key703 / key728 (the last valid key, in the partial tile) / self: q = c n_j, a needle of logit ~60 at key j;
+      group_first: the first key of key group g's first tile (key 64 g, g = (s // 10) % KG, KG = 4 for the plain kernel);
+      two: equal needles at keys 0 and 728 (different key groups);  rising / falling: q = +-c u, logits +-60 a_s over all 729 keys."""
+    seed = 11000 + 97 * F + (1 if dtype == torch.bfloat16 else 0) + (500 if cfg.name != "tiny" else 0)
+    g = torch.Generator().manual_seed(seed)
+    H = cfg.v_heads
+    sign = lambda *s: (torch.randint(0, 2, s, generator=g).double() * 2 - 1) / math.sqrt(VHD)
+    u = sign(F, 1, H, VHD)
+    n = sign(F, VS, H, VHD)
+    n = n - (n * u).sum(-1, keepdim=True) * u
+    a = torch.arange(VS, dtype=torch.float64) / (VS - 1)
+    k = a[None, :, None, None] * u + n
+    v = torch.rand((F, VS, H, VHD), generator=g, dtype=torch.float64) * 2 - 1
+    c = LOGIT * math.sqrt(VHD)
+    kg = vit_key_groups(cfg, F, dtype)
+    kg = kg if kg > 1 else 4
+    q = torch.zeros((F, VS, H, VHD), dtype=torch.float64)
+    fixed = {"key0": 0, "key63": 63, "key64": 64, "key703": 703, "key728": VS - 1}
+    for f in range(F):
+        for s in range(VS):
+            for h in range(H):
+                pat = VIT_PATTERNS[(s + h + 3 * f) % len(VIT_PATTERNS)]
+                if pat == "rising":
+                    q[f, s, h] = c * u[f, 0, h]
+                elif pat == "falling":
+                    q[f, s, h] = -c * u[f, 0, h]
+                elif pat == "two":
+                    q[f, s, h] = c * (n[f, 0, h] + n[f, VS - 1, h])
+                else:
+                    j = fixed.get(pat, s if pat == "self" else PAGE * ((s // len(VIT_PATTERNS)) % kg))
+                    q[f, s, h] = c * n[f, j, h]
+    return VitCase(cfg, dtype, F, rnd_dtype(q, dtype), rnd_dtype(k, dtype), rnd_dtype(v, dtype), rows=rows)
+
+
+def vit_mutant_ratios(case, device="cpu"):
+    """{mutant: max over elements of |mutant - reference| / tolerance}"""
+    ref = case.attend(device=device)
+    tol = case.tolerance(device=device)
+    return {mname: float(((case.attend(mutant=mname, device=device) - ref).abs() / tol).amax()) for mname in case.mutants()}

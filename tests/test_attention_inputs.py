@@ -56,3 +56,28 @@ def test_reference_is_rope_consistent():
     assert float(p[1, 0]) > 0.999             # head 1: "sink"
     assert float(p[2, 640]) > 0.999           # head 2: "tile_first" (700 // 64 * 64)
     assert int(p[3].argmax()) == 700          # head 3: "rising": the max is the newest key
+
+
+# ViT: the first and last rows, the rows around the key-tile edge 64 and the partial tile (every pattern of every head and frame occurs)
+VIT_ROWS = list(range(0, 40)) + list(range(60, 70)) + list(range(R.VS - 29, R.VS))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cfg,F", R.VIT_CASES)
+def test_attention_inputs_are_discriminating_vit(dtype, cfg, F):
+    case = R.vit_case(CONFIGS[cfg], dtype, F, rows=VIT_ROWS)
+    _check(R.vit_mutant_ratios(case), f"vit {cfg} F{F}")
+
+
+def test_vit_reference_is_sharp():
+    """needle rows put ~all their weight on their key, "two" splits it between keys 0 and 728, the ramps peak at their ends"""
+    c = CONFIGS["true_dims_1layer"]
+    case = R.vit_case(c, torch.bfloat16, 2, rows=list(range(10)))
+    s = torch.einsum("rhd,shd->rhs", case.q[1, :10], case.k[1]) * case.scale
+    p = torch.softmax(s, -1)[:, 0]                    # frame 1, head 0: row r takes VIT_PATTERNS[(r + 3) % 10]
+    last = R.VS - 1
+    for r, key in ((1, 64), (2, 703), (4, 0), (5, last), (7, 0), (8, 8), (9, 63)):       # key64 key703 group_first key728 key0 self key63
+        assert float(p[r, key]) > 0.999, (r, key, float(p[r, key]))
+    # rising, falling (steps of 60 / 728 logits: bf16 rounding may reorder neighbouring keys)
+    assert int(p[0].argmax()) >= last - 3 and int(p[6].argmax()) <= 3
+    assert float(p[3, 0] + p[3, last]) > 0.999 and min(float(p[3, 0]), float(p[3, last])) > 0.2     # two
