@@ -176,6 +176,14 @@ int svln_probe_decode_layer(svln_engine* h, int layer, unsigned long long* out, 
  * weights (one fp32 scale per output row, quantised on the device from the loaded tensors at the first enable) instead of the bf16
  * ones -- half the HBM bytes per generated token.  bf16 engines only; prefill, vision and svln_generate_batch keep bf16 weights. */
 int svln_set_fp8_decode(svln_engine* h, int enable);
+/* Opt-in, no reference counterpart: the single-env decode step's four projections and every lm_head product (the
+ * prefill's token included) stream OCP MXFP4 copies of the LLM weights instead of the bf16 ones -- E2M1 elements, one E8M0 power-of-two
+ * scale per 32 consecutive elements of a row, 4.25 bits per weight, quantised on the device from the loaded tensors at the first enable
+ * (~4.0 GB beside the bf16 copy at the 7B size).  Numeric scheme: svln_op_quant_mxfp4.  bf16 engines only; hidden, intermediate and
+ * q_heads * 128 must be multiples of 32.  Prefill, vision, attention, norms, svln_generate_batch and the scheduler keep bf16 weights.
+ * Mutually exclusive with svln_set_fp8_decode: enabling one while the other is on fails.  Captured decode graphs are dropped when the
+ * mode changes; while it is on the launched GEMVs are kept (svln_set_decode_persistent has no effect). */
+int svln_set_mxfp4_decode(svln_engine* h, int enable);
 /* Opt-in, no reference counterpart (BASELINE configs[4] "fp8 MFMA on QKV/MLP GEMMs"): the LLM's dense products with more
  * than one row -- prefill, and the decode steps of >= 4 envs batched by svln_generate_batch / svln_batch_step -- run as e4m3 x e4m3 MFMA
  * products (fp32 accumulate, bf16 out) on the e4m3 weight copies above with per-row activation scales computed on the fly.  bf16 engines
@@ -238,6 +246,17 @@ int svln_op_memory_prune(svln_engine* h, const void* mem, int n_rows, int keep, 
 int svln_op_quant_fp8(svln_engine* h, const void* w_bf16, int64_t rows, int cols, void* w8, float* scale);
 int svln_op_gemv_fp8(svln_engine* h, const void* w8, const float* scale, int ldw, const void* x, const void* norm_w, float eps, const void* bias,
                      const void* res, void* y, int N, int K, int epi, int32_t* host_token);
+/* MXFP4 weight-only pieces of svln_set_mxfp4_decode (no reference counterpart).  svln_op_quant_mxfp4: the OCP MX conversion of a bf16
+ * matrix [rows][cols] (device, cols % 32 == 0).  Every run of 32 consecutive elements of a row is one block: e = floor(log2(max |w|)) - 2
+ * clamped to [-127, 127] (0 for an all-zero block), e8 = e + 127 (E8M0, scale 2^e); element code = E2M1 of w / 2^e on the grid
+ * {0, 0.5, 1, 1.5, 2, 3, 4, 6}, round to nearest even (5 -> 4, 3.5 -> 4, 2.5 -> 2, 1.75 -> 2, 1.25 -> 1, 0.75 -> 1, 0.25 -> 0),
+ * saturating at 6, sign in bit 3; element 2j in the low nibble and 2j + 1 in the high nibble of byte j.
+ * q4 [rows][cols / 2] and e8 [rows][cols / 32] bytes, row-major (device): one 16-byte run of q4 is one block.
+ * svln_op_gemv_mxfp4: the GEMV over such a matrix, y = epi(Wq . x' + bias) + res with the epilogues of svln_op_gemv; ldw (the row
+ * stride) and K in elements, both multiples of 32.  fp32 engines refuse both. */
+int svln_op_quant_mxfp4(svln_engine* h, const void* w_bf16, int64_t rows, int cols, void* q4, void* e8);
+int svln_op_gemv_mxfp4(svln_engine* h, const void* q4, const void* e8, int ldw, const void* x, const void* norm_w, float eps, const void* bias,
+                       const void* res, void* y, int N, int K, int epi, int32_t* host_token);
 int svln_op_rmsnorm(svln_engine* h, const void* x, const void* g, void* y, int rows, int n, float eps);
 int svln_op_layernorm(svln_engine* h, const void* x, const void* g, const void* b, void* y, int rows, int n, float eps);
 /* attention over caller-provided q [T][q_stride] and k/v [S][kv_stride] (engine packs them into pages):

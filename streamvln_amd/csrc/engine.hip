@@ -103,6 +103,7 @@ struct EngineBase {
     virtual void probe_decode_layer(int layer, unsigned long long* out, int max_wgs, int32_t* n_wgs) = 0;
     virtual void set_fp8_decode(int enable) = 0;
     virtual void set_fp8_gemm(int enable) = 0;
+    virtual void set_mxfp4_decode(int enable) = 0;
     virtual bool op_gemm_fp8(const GemmArgs& a) = 0;
     virtual void set_memory_prune(int keep) = 0;
     virtual void op_memory_prune(const void* m, int n_rows, int keep, int32_t* out_idx, float* out_score) = 0;
@@ -116,6 +117,7 @@ struct EngineBase {
     virtual void op_gemv(GemvArgs a, int32_t* host_token) = 0;
     virtual void op_gemv_batched(GemvBatchArgs a, int32_t* host_tokens) = 0;
     virtual void op_quant_fp8(const void* w, int64_t rows, int cols, void* w8, float* scale) = 0;
+    virtual void op_quant_mxfp4(const void* w, int64_t rows, int cols, void* q4, uint8_t* e8) = 0;
     virtual void op_rmsnorm(const void* x, const void* g, void* y, int rows, int n, float eps) = 0;
     virtual void op_layernorm(const void* x, const void* g, const void* b, void* y, int rows, int n, float eps) = 0;
     virtual void op_attention_llm(void* qkv, int ld, int T, int P, const void* ctx, int ctx_T, void* out, int o_stride, int nsplit) = 0;
@@ -150,8 +152,10 @@ public:
 
     struct VLayer { T *ln1_w, *ln1_b, *qkv_w, *qkv_b, *out_w, *out_b, *ln2_w, *ln2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b; };
     struct Q8 { uint8_t* q = nullptr; float* s = nullptr; };      // fp8 (e4m3) copy of a weight matrix + per-row scales (opt-in decode mode)
-    struct LLayer { T *in_norm, *qkv_w, *qkv_b, *o_w, *post_norm, *gu_w, *down_w, *kpool, *vpool; Q8 qkv8, o8, gu8, down8; };
+    struct Q4 { uint8_t* q = nullptr; uint8_t* e8 = nullptr; };   // MXFP4 copy of a weight matrix: E2M1 code pairs + one E8M0 scale byte per 32 (opt-in decode mode)
+    struct LLayer { T *in_norm, *qkv_w, *qkv_b, *o_w, *post_norm, *gu_w, *down_w, *kpool, *vpool; Q8 qkv8, o8, gu8, down8; Q4 qkv4, o4, gu4, down4; };
     Q8 lm_head8; bool fp8_on = false, fp8_built = false;
+    Q4 lm_head4; bool mx4_on = false, mx4_built = false;
     bool fp8_gemm_on = false; uint8_t* act8 = nullptr; float* act8_scale = nullptr;      // opt-in fp8 MFMA products: quantised activation rows
     T *patch_w, *patch_b, *pos_emb, *proj0_w, *proj0_b, *proj2_w, *proj2_b, *embed, *final_norm, *lm_head;
     std::vector<VLayer> vl;
@@ -960,6 +964,7 @@ public:
         a.epi = epi; a.part_val = part_val; a.part_idx = part_idx; a.w8 = nullptr; a.scale = nullptr; a.skip = nullptr; return a;
     }
     GemvArgs with8(GemvArgs a, const Q8& q) { if (fp8_on) { a.w8 = q.q; a.scale = q.s; } return a; }
+    GemvArgs with4(GemvArgs a, const Q4& q) { if (mx4_on) { a.w4 = q.q; a.e8 = q.e8; } return a; }
     GemvArgs guarded(GemvArgs a) { a.skip = &d_ctl->done; return a; }      // decode-step launch: no-op once the generation is done
     // final norm -> hidden tap row -> lm_head arg-max -> d_token  (lm_head on the LAST position only).
     // `gen`: the arg-max also runs one step of the greedy loop on the device (GenCtl: append, EOS / max_new stop, advance the position)
@@ -975,7 +980,7 @@ public:
         } else {
             launch_rmsnorm<T>(st, xrow, final_norm, tap, 1, H, c.rms_eps, skip);
         }
-        GemvArgs a = with8(gemv_args(lm_head, H, tap, nullptr, nullptr, nullptr, nullptr, V, H, EPI_ARGMAX), lm_head8);
+        GemvArgs a = with4(with8(gemv_args(lm_head, H, tap, nullptr, nullptr, nullptr, nullptr, V, H, EPI_ARGMAX), lm_head8), lm_head4);
         a.skip = skip;
         const bool pen = gen && rep_penalty != 1.0f;
         if (pen) { a.pen_flags = pen_flags; a.pen = rep_penalty; }
@@ -1037,7 +1042,7 @@ public:
         HIP_CHECK(hipFree(d));
         *n_wgs = n;
     }
-    bool persistent_active() const { return persistent_on && !fp8_on; }       // (the e4m3 decode weights keep the launched GEMVs)
+    bool persistent_active() const { return persistent_on && !fp8_on && !mx4_on; }       // (the e4m3 / MXFP4 decode weights keep the launched GEMVs)
     int probe_op() const { return persistent_active() ? 3 : 1 + 4; }          // the launch the roofline probe times (layer 0)
     int total_ops() const { return persistent_active() ? 2 + 2 * c.layers : 1 + c.layers * OPS_PER_LAYER; }
     void decode_ops(Env& e, int lo, int hi) {
@@ -1056,13 +1061,13 @@ public:
         }
         for (int i = 0; i < c.layers; ++i) {
             const LLayer& L = ll[i];
-            if (on()) launch_gemv<T>(st, guarded(with8(gemv_args(L.qkv_w, H, x, L.in_norm, L.qkv_b, nullptr, qkv, qkv_dim, H, EPI_NONE), L.qkv8)));
+            if (on()) launch_gemv<T>(st, guarded(with4(with8(gemv_args(L.qkv_w, H, x, L.in_norm, L.qkv_b, nullptr, qkv, qkv_dim, H, EPI_NONE), L.qkv8), L.qkv4)));
             const AttnArgs a = decode_attn_args(L, e);
             if (on()) launch_attention<T>(st, a, 128, 1);
             if (on()) launch_attention_combine<T>(st, a, 128);
-            if (on()) launch_gemv<T>(st, guarded(with8(gemv_args(L.o_w, qd, attn, nullptr, nullptr, x, x, H, qd, EPI_NONE), L.o8)));
-            if (on()) launch_gemv<T>(st, guarded(with8(gemv_args(L.gu_w, H, x, L.post_norm, nullptr, nullptr, hbuf, 2 * I, H, EPI_SWIGLU), L.gu8)));
-            if (on()) launch_gemv<T>(st, guarded(with8(gemv_args(L.down_w, I, hbuf, nullptr, nullptr, x, x, H, I, EPI_NONE), L.down8)));
+            if (on()) launch_gemv<T>(st, guarded(with4(with8(gemv_args(L.o_w, qd, attn, nullptr, nullptr, x, x, H, qd, EPI_NONE), L.o8), L.o4)));
+            if (on()) launch_gemv<T>(st, guarded(with4(with8(gemv_args(L.gu_w, H, x, L.post_norm, nullptr, nullptr, hbuf, 2 * I, H, EPI_SWIGLU), L.gu8), L.gu4)));
+            if (on()) launch_gemv<T>(st, guarded(with4(with8(gemv_args(L.down_w, I, hbuf, nullptr, nullptr, x, x, H, I, EPI_NONE), L.down8), L.down4)));
         }
     }
 
@@ -1070,8 +1075,8 @@ public:
     void probe_launch(Env&) {
         const LLayer& L = ll[0];
         if (persistent_active()) launch_decode_layer<T>(st, layer_args(0), n_cus, probe_ev[probe_used], probe_ev[probe_used + 1]);
-        else launch_gemv_timed<T>(st, guarded(with8(gemv_args(L.gu_w, H, x, L.post_norm, nullptr, nullptr, hbuf, 2 * I, H, EPI_SWIGLU), L.gu8)), probe_ev[probe_used],
-                                  probe_ev[probe_used + 1]);
+        else launch_gemv_timed<T>(st, guarded(with4(with8(gemv_args(L.gu_w, H, x, L.post_norm, nullptr, nullptr, hbuf, 2 * I, H, EPI_SWIGLU), L.gu8), L.gu4)),
+                                  probe_ev[probe_used], probe_ev[probe_used + 1]);
         probe_used += 2;
     }
     // graph of: ops [lo, hi) of one decode step (+ the head when hi is the end of the step), then `more` further whole steps
@@ -1682,9 +1687,42 @@ public:
     }
     void set_fp8_decode(int enable) override {
         if (!enable) { if (fp8_on) drop_graphs(); fp8_on = false; return; }
+        REQUIRE(!mx4_on, "svln_set_fp8_decode: the MXFP4 decode weights are on (svln_set_mxfp4_decode); switch them off first");
         build_fp8_weights();
         if (!fp8_on) drop_graphs();
         fp8_on = true;
+    }
+    // Opt-in (no reference counterpart): the single-env decode step's four projections and every lm_head product read
+    // OCP MXFP4 copies of the LLM weights (E2M1 elements, one E8M0 scale per 32 elements of a row: 4.25 bits per weight) instead of the
+    // bf16 ones; prefill, vision, attention, norms and the lockstep multi-env path keep bf16.  Both copies stay resident (15.2 + 4.0 GB).
+    // Quantised from the tensors loaded at the time of the first enable.
+    void build_mxfp4_weights() {
+        REQUIRE(sizeof(T) == 2, "MXFP4 weights need the bf16 engine");
+        REQUIRE(weights_missing() == 0, g_err);
+        REQUIRE(H % 32 == 0 && I % 32 == 0 && (nq * 128) % 32 == 0, "MXFP4 weights need hidden, intermediate and q sizes that are multiples of 32");
+        if (mx4_built) return;
+        auto build = [&](Q4& q, const T* w, int64_t rows, int cols) {
+            q.q = dalloc<uint8_t>((size_t)rows * (cols / 2));
+            q.e8 = dalloc<uint8_t>((size_t)rows * (cols / 32));
+            launch_quant_mxfp4_rows(st, w, cols, q.q, q.e8, rows, cols);
+        };
+        for (auto& L : ll) {
+            build(L.qkv4, L.qkv_w, qkv_dim, H);
+            build(L.o4, L.o_w, H, nq * 128);
+            build(L.gu4, L.gu_w, 2 * I, H);
+            build(L.down4, L.down_w, H, I);
+        }
+        build(lm_head4, lm_head, V, H);
+        HIP_CHECK(hipStreamSynchronize(st));
+        LAUNCH_CHECK("build_mxfp4_weights");
+        mx4_built = true;
+    }
+    void set_mxfp4_decode(int enable) override {
+        if (!enable) { if (mx4_on) drop_graphs(); mx4_on = false; return; }
+        REQUIRE(!fp8_on, "svln_set_mxfp4_decode: the e4m3 decode weights are on (svln_set_fp8_decode); switch them off first");
+        build_mxfp4_weights();
+        if (!mx4_on) drop_graphs();
+        mx4_on = true;
     }
     // Opt-in (no reference counterpart): the LLM's dense products with more than one row -- prefill (svln_generate,
     // the scheduler) and the decode steps of >= 4 lockstep envs -- run as e4m3 x e4m3 MFMA products (v_mfma_f32_32x32x16_fp8_fp8, fp32
@@ -1739,6 +1777,7 @@ public:
         if (pprobe_ev.empty()) { pprobe_ev.resize(512); for (auto& ev : pprobe_ev) HIP_CHECK(hipEventCreate(&ev)); }
         probe_used = 0; probe_on = true; pprobe_used = 0; pprobe_rows = 0;
         probe_bytes = (double)2 * I * H * sizeof(T);
+        if (mx4_on) probe_bytes = (double)2 * I * (H / 2) + (double)2 * I * (H / 32);                // E2M1 code pairs + E8M0 scale bytes
         // persistent layer: the four products one launch streams (o, gate/up, down, the next layer's q|k|v)
         if (persistent_active()) probe_bytes = ((double)H * nq * 128 + (double)2 * I * H + (double)H * I + (double)qkv_dim * H) * sizeof(T);
     }
@@ -1779,6 +1818,7 @@ public:
     }
     void op_gemv(GemvArgs a, int32_t* host_token) override {
         REQUIRE(a.w8 == nullptr || sizeof(T) == 2, "fp8 weights need the bf16 engine");
+        REQUIRE(a.w4 == nullptr || sizeof(T) == 2, "MXFP4 weights need the bf16 engine");
         a.part_val = part_val; a.part_idx = part_idx;
         launch_gemv<T>(st, a);
         if (a.epi == EPI_ARGMAX) {
@@ -1809,6 +1849,14 @@ public:
         REQUIRE(cols % 16 == 0, "cols must be a multiple of 16");
         launch_quant_fp8_rows(st, w, cols, w8, scale, rows, cols);
         sync();
+    }
+    void op_quant_mxfp4(const void* w, int64_t rows, int cols, void* q4, uint8_t* e8) override {
+        REQUIRE(sizeof(T) == 2, "MXFP4 quantisation reads bf16 weights");
+        REQUIRE(w && q4 && e8, "null pointer");
+        REQUIRE(rows >= 0 && cols > 0 && cols % 32 == 0, "cols must be a positive multiple of 32");
+        if (rows > 0) launch_quant_mxfp4_rows(st, w, cols, q4, e8, rows, cols);
+        sync();
+        LAUNCH_CHECK("op_quant_mxfp4");
     }
     void op_rmsnorm(const void* xi, const void* g, void* y, int rows, int n, float eps) override { launch_rmsnorm<T>(st, xi, g, y, rows, n, eps); sync(); }
     void op_layernorm(const void* xi, const void* g, const void* b, void* y, int rows, int n, float eps) override {
@@ -2127,6 +2175,7 @@ int svln_probe_decode_layer(svln_engine* h, int layer, unsigned long long* out, 
 }
 int svln_set_fp8_decode(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_fp8_decode(enable); API_END }
 int svln_set_fp8_gemm(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_fp8_gemm(enable); API_END }
+int svln_set_mxfp4_decode(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_mxfp4_decode(enable); API_END }
 int svln_set_memory_prune(svln_engine* h, int keep_tokens) { API_BEGIN_H h->impl->set_memory_prune(keep_tokens); API_END }
 int svln_op_memory_prune(svln_engine* h, const void* mem, int n_rows, int keep, int32_t* out_idx, float* out_score) {
     API_BEGIN_H h->impl->op_memory_prune(mem, n_rows, keep, out_idx, out_score); API_END
@@ -2204,6 +2253,22 @@ int svln_op_gemv_fp8(svln_engine* h, const void* w8, const float* scale, int ldw
     if (K % 16 != 0) throw std::runtime_error("K must be a multiple of 16");
     GemvArgs a; a.W = nullptr; a.ldw = ldw; a.x = x; a.norm_w = norm_w; a.eps = eps; a.bias = bias; a.res = res; a.y = y; a.N = N; a.K = K; a.epi = epi;
     a.part_val = nullptr; a.part_idx = nullptr; a.w8 = w8; a.scale = scale; a.skip = nullptr;
+    h->impl->op_gemv(a, host_token);
+    API_END
+}
+int svln_op_quant_mxfp4(svln_engine* h, const void* w_bf16, int64_t rows, int cols, void* q4, void* e8) {
+    API_BEGIN_H h->impl->op_quant_mxfp4(w_bf16, rows, cols, q4, (uint8_t*)e8); API_END
+}
+int svln_op_gemv_mxfp4(svln_engine* h, const void* q4, const void* e8, int ldw, const void* x, const void* norm_w, float eps, const void* bias,
+                       const void* res, void* y, int N, int K, int epi, int32_t* host_token) {
+    API_BEGIN_H
+    if (!q4 || !e8 || !x) throw std::runtime_error("null pointer");
+    if (N < 1 || K < 32 || K % 32 != 0 || ldw % 32 != 0 || ldw < K) throw std::runtime_error("K and ldw must be multiples of 32, ldw >= K, N >= 1");
+    if (epi != EPI_NONE && epi != EPI_SWIGLU && epi != EPI_ARGMAX) throw std::runtime_error("epilogue: EPI_NONE, EPI_SWIGLU or EPI_ARGMAX");
+    if (epi == EPI_SWIGLU && N % 64 != 0) throw std::runtime_error("SwiGLU needs N % 64 == 0 (32-row gate / up blocks)");
+    if (epi != EPI_ARGMAX && !y) throw std::runtime_error("null output pointer");
+    GemvArgs a; a.W = nullptr; a.ldw = ldw; a.x = x; a.norm_w = norm_w; a.eps = eps; a.bias = bias; a.res = res; a.y = y; a.N = N; a.K = K; a.epi = epi;
+    a.part_val = nullptr; a.part_idx = nullptr; a.w8 = nullptr; a.scale = nullptr; a.skip = nullptr; a.w4 = q4; a.e8 = (const uint8_t*)e8;
     h->impl->op_gemv(a, host_token);
     API_END
 }

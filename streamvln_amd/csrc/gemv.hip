@@ -718,6 +718,301 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16* w, int 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ MXFP4 weight-only variants
+// Opt-in decode mode (svln_set_mxfp4_decode): the weights are OCP MXFP4 -- E2M1 elements on the grid {0, 0.5, 1, 1.5, 2, 3, 4, 6} with
+// the sign in bit 3, element 2j in the low nibble and 2j + 1 in the high nibble of byte j, and one E8M0 scale byte (2^(byte - 127)) per
+// block of 32 consecutive elements of a row: q4 [N][K/2] bytes, e8 [N][K/32] bytes, 4.25 bits per weight.  One 16-byte chunk is one
+// MX block.  Same structure as the e4m3 kernels; per chunk one scale byte is shifted into a float's exponent field and sixteen
+// v_cvt_scalef32_pk_f32_fp4 (one byte -> two scaled fp32 values each) feed v_pk_fma_f32 against 32 activations.  There is no per-row
+// scale: the block scale is applied by the conversion.
+SVLN_DEV float e8m0_to_f32(unsigned b) { return __uint_as_float(b << 23); }
+// acc (two partial sums) += one MX block (32 E2M1 weights, scale sc) . 32 activations; x2[k] = activations 2k, 2k + 1 of the block
+SVLN_DEV void fp4x32_dot(const uint4& w, float sc, const f32x2* x2, f32x2& acc) {
+    const unsigned d[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 0), x2[4 * q], acc);
+        acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 1), x2[4 * q + 1], acc);
+        acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 2), x2[4 * q + 2], acc);
+        acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 3), x2[4 * q + 3], acc);
+    }
+}
+// x (bf16 in global memory) -> LDS fp32 in eight 16-byte planes per 32-element block: element 32*cj + 4*p + e lives at
+// xs[p * nch4 * 4 + cj * 4 + e], so consecutive lanes read consecutive 16 B in every plane.
+SVLN_DEV float stage_x4(float* xs, const GemvArgs& p, int nch4) {
+    __shared__ float red4[GEMV_WAVES];
+    const bf16* x = (const bf16*)p.x;
+    const bf16* g = (const bf16*)p.norm_w;
+    const int tid = threadIdx.x, nch = p.K / 8;
+    float ss = 0.0f;
+    for (int ci = tid; ci < nch; ci += GEMV_THREADS) {
+        float f[8];
+        chunk_to_f32<bf16>(*(const uint4*)(x + (size_t)ci * 8), f);
+        if (g) {
+            float gf[8];
+            chunk_to_f32<bf16>(*(const uint4*)(g + (size_t)ci * 8), gf);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { ss = fmaf(f[e], f[e], ss); f[e] *= gf[e]; }
+        }
+        const int cj = ci >> 2, p0 = (ci & 3) * 2;
+        *(float4*)(xs + (size_t)p0 * nch4 * 4 + (size_t)cj * 4) = make_float4(f[0], f[1], f[2], f[3]);
+        *(float4*)(xs + (size_t)(p0 + 1) * nch4 * 4 + (size_t)cj * 4) = make_float4(f[4], f[5], f[6], f[7]);
+    }
+    if (g) {
+        ss = wave_sum(ss);
+        if ((tid & 63) == 0) red4[tid >> 6] = ss;
+    }
+    __syncthreads();
+    if (!g) return 1.0f;
+    float tot = 0.0f;
+#pragma unroll
+    for (int w = 0; w < GEMV_WAVES; ++w) tot += red4[w];
+    return rsqrtf(tot / (float)p.K + p.eps);     // applied in the epilogue: y = rstd * (Wq . (g * x))
+}
+SVLN_DEV void load_x4(const float* xs, int nch4, int cj, f32x2* x2) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const float4 v = *(const float4*)(xs + (size_t)q * nch4 * 4 + (size_t)cj * 4);
+        x2[2 * q] = f32x2{v.x, v.y};
+        x2[2 * q + 1] = f32x2{v.z, v.w};
+    }
+}
+// R dot products of MXFP4 rows (q4 bytes, e8 scale bytes) against the LDS copy of x; two blocks per row in flight
+template <int R>
+SVLN_DEV void dot4_rows(const uint8_t* const (&rows)[R], const uint8_t* const (&srow)[R], const float* xs, int nch4, int lane, float (&acc)[R]) {
+    f32x2 a2[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) a2[r] = f32x2{0.0f, 0.0f};
+    int ci = lane;
+    for (; ci + 64 < nch4; ci += 128) {
+        uint4 w0[R], w1[R];
+        unsigned s0[R], s1[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            w0[r] = load_nt(rows[r] + (size_t)ci * 16);
+            w1[r] = load_nt(rows[r] + (size_t)(ci + 64) * 16);
+            s0[r] = srow[r][ci];
+            s1[r] = srow[r][ci + 64];
+        }
+        f32x2 x0[16];
+        load_x4(xs, nch4, ci, x0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) fp4x32_dot(w0[r], e8m0_to_f32(s0[r]), x0, a2[r]);
+        load_x4(xs, nch4, ci + 64, x0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) fp4x32_dot(w1[r], e8m0_to_f32(s1[r]), x0, a2[r]);
+    }
+    for (; ci < nch4; ci += 64) {
+        uint4 w0[R];
+        unsigned s0[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) { w0[r] = load_nt(rows[r] + (size_t)ci * 16); s0[r] = srow[r][ci]; }
+        f32x2 x0[16];
+        load_x4(xs, nch4, ci, x0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) fp4x32_dot(w0[r], e8m0_to_f32(s0[r]), x0, a2[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = wave_sum(a2[r][0] + a2[r][1]);
+}
+
+template <int EPI>
+__global__ __launch_bounds__(GEMV_THREADS) void gemv4_kernel(GemvArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    float* xs = (float*)smem_raw;
+    const int skip = p.skip ? *p.skip : 0;
+    constexpr int R = 4;
+    const int nch4 = p.K / 32;
+    const float xscale = stage_x4(xs, p, nch4);
+    if (skip) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int gw = blockIdx.x * GEMV_WAVES + wave, nw = gridDim.x * GEMV_WAVES;
+    const uint8_t* W = (const uint8_t*)p.w4;
+    const size_t ldq = (size_t)p.ldw / 2, lds = (size_t)p.ldw / 32;        // row strides of q4 / e8 in bytes
+    if (EPI == EPI_SWIGLU) {
+        const int n_out = p.N >> 1;
+        bf16* y = (bf16*)p.y;
+        for (int j0 = gw * 2; j0 < n_out; j0 += nw * 2) {
+            const uint8_t* rows[R];
+            const uint8_t* srow[R];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int j = min(j0 + u, n_out - 1);
+                const size_t gr = (size_t)(j >> 5) * 64 + (j & 31);
+                rows[2 * u] = W + gr * ldq;          srow[2 * u] = p.e8 + gr * lds;
+                rows[2 * u + 1] = W + (gr + 32) * ldq; srow[2 * u + 1] = p.e8 + (gr + 32) * lds;
+            }
+            float acc[R];
+            dot4_rows<R>(rows, srow, xs, nch4, lane, acc);
+            if (lane < 2 && j0 + lane < n_out) {
+                const float gt = (lane == 0 ? acc[0] : acc[2]) * xscale, up = (lane == 0 ? acc[1] : acc[3]) * xscale;
+                y[j0 + lane] = from_f32<bf16>(silu_f(gt) * up);
+            }
+        }
+        return;
+    }
+    float best = -INFINITY;
+    int best_i = 0x7FFFFFFF;
+    for (int n0 = gw * R; n0 < p.N; n0 += nw * R) {
+        const uint8_t* rows[R];
+        const uint8_t* srow[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const size_t n = (size_t)min(n0 + r, p.N - 1);
+            rows[r] = W + n * ldq; srow[r] = p.e8 + n * lds;
+        }
+        float acc[R];
+        dot4_rows<R>(rows, srow, xs, nch4, lane, acc);
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] *= xscale;
+        if (EPI == EPI_ARGMAX) {
+            if (p.pen_flags) {
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    if (n0 + r < p.N && p.pen_flags[n0 + r]) acc[r] = acc[r] < 0.0f ? acc[r] * p.pen : acc[r] / p.pen;
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (n0 + r < p.N && acc[r] > best) { best = acc[r]; best_i = n0 + r; }
+        } else if (lane < R && n0 + lane < p.N) {
+            const int n = n0 + lane;
+            float v = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+            if (p.bias) v += to_f32(((const bf16*)p.bias)[n]);
+            if (p.res) v += to_f32(((const bf16*)p.res)[n]);
+            ((bf16*)p.y)[n] = from_f32<bf16>(v);
+        }
+    }
+    if (EPI == EPI_ARGMAX) {
+        __shared__ float bv[GEMV_WAVES];
+        __shared__ int bi[GEMV_WAVES];
+        if (lane == 0) { bv[wave] = best; bi[wave] = best_i; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float v = bv[0]; int i = bi[0];
+#pragma unroll
+            for (int w = 1; w < GEMV_WAVES; ++w)
+                if (bv[w] > v || (bv[w] == v && bi[w] < i)) { v = bv[w]; i = bi[w]; }
+            p.part_val[blockIdx.x] = v;
+            p.part_idx[blockIdx.x] = i;
+        }
+    }
+}
+
+// small-N MXFP4 variant, RMSNorm folded in without a prologue (as gemv8_ksplit_kernel).  A row of K = 3584 is only 112 blocks, fewer
+// than two waves' worth of lanes, so the split is a template parameter: KW of the workgroup's 4 waves split K and the 4 / KW groups of
+// KW waves take R rows each (KW = 2 for K <= 4096: 2 x R rows per workgroup; KW = 4 for the down projection's K = 18944).
+template <bool NORM, int R, int KW>
+__global__ __launch_bounds__(GEMV_THREADS) void gemv4_ksplit_kernel(GemvArgs p) {
+    constexpr int RG = GEMV_WAVES / KW;             // row groups per workgroup
+    __shared__ float part[GEMV_WAVES][R + 1];
+    if (p.skip && *p.skip) return;
+    const int nch4 = p.K / 32;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int kw = wave % KW, rg = wave / KW;
+    const uint8_t* W = (const uint8_t*)p.w4;
+    const size_t ldq = (size_t)p.ldw / 2, lds = (size_t)p.ldw / 32;
+    const bf16* xg = (const bf16*)p.x;
+    const bf16* gg = (const bf16*)p.norm_w;
+    for (int b0 = blockIdx.x * RG * R; b0 < p.N; b0 += gridDim.x * RG * R) {
+        const int n0 = b0 + rg * R;                 // (may lie beyond N for the last workgroup: rows clamp, nothing is written)
+        const uint8_t* rows[R];
+        const uint8_t* srow[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const size_t n = (size_t)min(n0 + r, p.N - 1);
+            rows[r] = W + n * ldq; srow[r] = p.e8 + n * lds;
+        }
+        float ss = 0.0f;
+        f32x2 a2[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) a2[r] = f32x2{0.0f, 0.0f};
+        for (int ci = kw * 64 + lane; ci < nch4; ci += 64 * KW) {
+            uint4 w[R];
+            unsigned sb[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) { w[r] = load_nt(rows[r] + (size_t)ci * 16); sb[r] = srow[r][ci]; }
+            f32x2 x2[16];
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                float xf[8];
+                chunk_to_f32<bf16>(*(const uint4*)(xg + (size_t)ci * 32 + h * 8), xf);
+                if (NORM) {
+                    float gf[8];
+                    chunk_to_f32<bf16>(*(const uint4*)(gg + (size_t)ci * 32 + h * 8), gf);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) { ss = fmaf(xf[e], xf[e], ss); xf[e] *= gf[e]; }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x2[4 * h + e] = f32x2{xf[2 * e], xf[2 * e + 1]};
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) fp4x32_dot(w[r], e8m0_to_f32(sb[r]), x2, a2[r]);
+        }
+        float acc[R + 1];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = wave_sum(a2[r][0] + a2[r][1]);
+        acc[R] = NORM ? wave_sum(ss) : 0.0f;
+        if (lane == 0) {
+#pragma unroll
+            for (int r = 0; r <= R; ++r) part[wave][r] = acc[r];
+        }
+        __syncthreads();
+        if (threadIdx.x < RG * R) {
+            const int g2 = threadIdx.x / R, r = threadIdx.x % R, n = b0 + g2 * R + r;
+            if (n < p.N) {
+                float v = 0.0f, s2 = 0.0f;
+#pragma unroll
+                for (int k = 0; k < KW; ++k) { v += part[g2 * KW + k][r]; s2 += part[g2 * KW + k][R]; }
+                if (NORM) v *= rsqrtf(s2 / (float)p.K + p.eps);
+                if (p.bias) v += to_f32(((const bf16*)p.bias)[n]);
+                if (p.res) v += to_f32(((const bf16*)p.res)[n]);
+                ((bf16*)p.y)[n] = from_f32<bf16>(v);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// MXFP4 quantisation of a bf16 matrix (OCP MX conversion): one workgroup per row, one thread per block of 32 elements.
+//   e = floor(log2(max |w|)) - 2 clamped to [-127, 127] (0 for an all-zero block), scale byte e + 127;
+//   code = E2M1 of w / 2^e (exact in fp32), round to nearest even, saturating at 6.
+// The rounding is written as comparisons against the seven midpoints of the grid (ties to the code with an even mantissa bit) rather
+// than with v_cvt_scalef32_pk_fp4_f32: this runs once per weight load, and the bytes are then defined by this text alone.
+SVLN_DEV unsigned e2m1_code(float v) {
+    const float a = fabsf(v);
+    const unsigned c = (unsigned)(a > 0.25f) + (unsigned)(a >= 0.75f) + (unsigned)(a > 1.25f) + (unsigned)(a >= 1.75f) + (unsigned)(a > 2.5f) +
+                       (unsigned)(a >= 3.5f) + (unsigned)(a > 5.0f);
+    return c | (v < 0.0f ? 8u : 0u);
+}
+__global__ __launch_bounds__(256) void quant_mxfp4_rows_kernel(const bf16* w, int ld, uint8_t* q, uint8_t* e8, int cols) {
+    const size_t row = blockIdx.x;
+    const bf16* wr = w + row * ld;
+    const int nblk = cols / 32;
+    for (int bi = threadIdx.x; bi < nblk; bi += 256) {
+        float f[32];
+#pragma unroll
+        for (int h = 0; h < 4; ++h) chunk_to_f32<bf16>(*(const uint4*)(wr + (size_t)bi * 32 + h * 8), f + 8 * h);
+        float amax = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 32; ++e) amax = fmaxf(amax, fabsf(f[e]));
+        int ex = 0;
+        if (amax > 0.0f) {
+            ex = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127 - 2;        // (a subnormal amax reads as -129 and clamps)
+            ex = ex < -127 ? -127 : ex > 127 ? 127 : ex;
+        }
+        unsigned d[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            unsigned v = 0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v |= e2m1_code(ldexpf(f[8 * k + e], -ex)) << (4 * e);
+            d[k] = v;
+        }
+        *(uint4*)(q + row * (size_t)(cols / 2) + (size_t)bi * 16) = make_uint4(d[0], d[1], d[2], d[3]);
+        e8[row * (size_t)nblk + bi] = (uint8_t)(ex + 127);
+    }
+}
+
 // final arg-max over per-workgroup partials: greatest value, lowest index on ties (torch.argmax on CPU)
 // With `ctl` it is also one step of the greedy loop (GenerationMixin._sample: append, stop on EOS / max_new_tokens): see GenCtl.
 __global__ __launch_bounds__(256) void argmax_final_kernel(const float* pv, const int* pi, int n, int* out_token, float* out_top, GenCtl* ctl,
@@ -791,6 +1086,32 @@ template <typename T> void launch_gemv(hipStream_t s, const GemvArgs& a) { launc
     } while (0)
 template <typename T> void launch_gemv_timed(hipStream_t s, const GemvArgs& a, hipEvent_t start, hipEvent_t stop) {
     dim3 b(GEMV_THREADS);
+    if (a.w4) {                                   // MXFP4 weights (bf16 engine only; the engine refuses to enable it otherwise)
+        if (a.epi == EPI_NONE && a.N <= 8192) {
+            constexpr int R = 4;
+            const bool wide = a.K > 4096;         // K / 32 blocks per row: more than 128 -> all four waves split K
+            const int per_wg = wide ? R : 2 * R;
+            int grid = (a.N + per_wg - 1) / per_wg;
+            if (grid > 2048) grid = 2048;
+            if (wide) {
+                if (a.norm_w) SVLN_LAUNCH((gemv4_ksplit_kernel<true, R, 4>), dim3(grid), b, 0);
+                else SVLN_LAUNCH((gemv4_ksplit_kernel<false, R, 4>), dim3(grid), b, 0);
+            } else {
+                if (a.norm_w) SVLN_LAUNCH((gemv4_ksplit_kernel<true, R, 2>), dim3(grid), b, 0);
+                else SVLN_LAUNCH((gemv4_ksplit_kernel<false, R, 2>), dim3(grid), b, 0);
+            }
+            return;
+        }
+        const size_t lds4 = (size_t)a.K * sizeof(float);
+        dim3 g4(gemv_grid(a.N));
+        switch (a.epi) {
+            case EPI_NONE: SVLN_LAUNCH((gemv4_kernel<EPI_NONE>), g4, b, lds4); break;
+            case EPI_SWIGLU: SVLN_LAUNCH((gemv4_kernel<EPI_SWIGLU>), g4, b, lds4); break;
+            case EPI_ARGMAX: SVLN_LAUNCH((gemv4_kernel<EPI_ARGMAX>), g4, b, lds4); break;
+            default: break;
+        }
+        return;
+    }
     if (a.w8) {                                   // fp8 weights (bf16 engine only; the engine refuses to enable it otherwise)
         if (a.epi == EPI_NONE && a.N <= 8192) {
             constexpr int R = 4;
@@ -867,8 +1188,14 @@ template <typename T, int EPI> static void gemv_attr() {
 void launch_quant_fp8_rows(hipStream_t s, const void* w_bf16, int ld, void* w8, float* scale, int64_t rows, int cols) {
     hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, (const bf16*)w_bf16, ld, (uint8_t*)w8, scale, cols);
 }
+void launch_quant_mxfp4_rows(hipStream_t s, const void* w_bf16, int ld, void* q4, uint8_t* e8, int64_t rows, int cols) {
+    hipLaunchKernelGGL(quant_mxfp4_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, (const bf16*)w_bf16, ld, (uint8_t*)q4, e8, cols);
+}
 void gemv_init_attrs() {
     // (every kernel that may ask for more than 64 KiB of dynamic LDS goes through set_max_lds: a refusal is reported at engine creation)
+    set_max_lds((const void*)gemv4_kernel<EPI_NONE>, 160 * 1024 - 256);
+    set_max_lds((const void*)gemv4_kernel<EPI_SWIGLU>, 160 * 1024 - 256);
+    set_max_lds((const void*)gemv4_kernel<EPI_ARGMAX>, 160 * 1024 - 256);
     set_max_lds((const void*)gemv8_kernel<EPI_NONE>, 160 * 1024 - 256);
     set_max_lds((const void*)gemv8_kernel<EPI_SWIGLU>, 160 * 1024 - 256);
     set_max_lds((const void*)gemv8_kernel<EPI_ARGMAX>, 160 * 1024 - 256);

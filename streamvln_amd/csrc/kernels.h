@@ -78,6 +78,10 @@ struct GemvArgs {
     // optional fp8 (OCP e4m3) weight-only path (bf16 engine, opt-in): w8 [N][K] bytes, one fp32 scale per row,
     // W[n][k] ~= scale[n] * e4m3(w8[n][k]); when set, W is ignored
     const void* w8; const float* scale;
+    // optional MXFP4 weight-only path (bf16 engine, opt-in): w4 [N][ldw / 2] bytes (two E2M1 codes per byte, element 2j in the low
+    // nibble), e8 [N][ldw / 32] E8M0 scale bytes, W[n][k] = 2^(e8[n][k / 32] - 127) * e2m1(code); ldw in elements, a multiple of 32;
+    // when set, W and w8 are ignored
+    const void* w4 = nullptr; const uint8_t* e8 = nullptr;
     const int* skip;              // optional device flag: the launch is a no-op when *skip != 0 (generation finished: run-ahead decode steps)
     // EPI_ARGMAX only, optional: HF RepetitionPenaltyLogitsProcessor on the fp32 logits before the arg-max (a checkpoint's
     // generation_config.json `repetition_penalty`): pen_flags[n] != 0 marks token n as already generated in this turn;
@@ -87,6 +91,8 @@ struct GemvArgs {
 template <typename T> void launch_gemv(hipStream_t s, const GemvArgs& a);
 // per-row e4m3 quantisation of a bf16 matrix [rows][cols] (cols % 16 == 0): scale[r] = max|W[r]| / 448
 void launch_quant_fp8_rows(hipStream_t s, const void* w_bf16, int ld, void* w8, float* scale, int64_t rows, int cols);
+// OCP MXFP4 quantisation of a bf16 matrix [rows][cols] (cols % 32 == 0): q4 [rows][cols / 2], e8 [rows][cols / 32] (see GemvArgs)
+void launch_quant_mxfp4_rows(hipStream_t s, const void* w_bf16, int ld, void* q4, uint8_t* e8, int64_t rows, int cols);
 template <typename T> void launch_gemv_timed(hipStream_t s, const GemvArgs& a, hipEvent_t start, hipEvent_t stop);   // events get the kernel's own begin/end
 int gemv_grid(int N);                       // workgroups launch_gemv uses for N rows
 

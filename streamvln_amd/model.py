@@ -721,6 +721,12 @@ class StreamVLNForCausalLM:
         weights (per-row scale).  Prefill, vision and generate_batch keep bf16.  bf16 engines only."""
         _check(self._lib.svln_set_fp8_decode(self._h, int(enable)))
 
+    def set_mxfp4_decode(self, enable: bool):
+        """Opt-in extension (the reference is bf16 only): decode steps and the lm_head read OCP MXFP4 copies of the LLM
+        weights (E2M1 elements, one E8M0 scale per 32: 4.25 bits per weight).  Prefill, vision and generate_batch keep bf16.  bf16
+        engines only; refused while set_fp8_decode is on (and the other way round)."""
+        _check(self._lib.svln_set_mxfp4_decode(self._h, int(enable)))
+
     def set_fp8_gemm(self, enable: bool):
         """Opt-in extension (SURVEY.md 8f-2 / BASELINE configs[4]): the LLM's multi-row products (prefill; decode steps of >= 4 batched
         envs) run as e4m3 MFMA products with per-row weight and activation scales.  bf16 engines only; reduced precision."""
