@@ -121,6 +121,9 @@ SVLN_DEV float gelu_erf_f(float x) {       // nn.GELU()  (multimodal_projector/b
 }
 SVLN_DEV float silu_f(float x) { return x * sigmoid_f(x); }
 
+// EPI_SWIGLU weight packing: 64-row blocks = [gate 32 | up 32].  The gate row of output j; its up row lies 32 further.
+SVLN_DEV size_t swiglu_gate_row(int j) { return (size_t)(j >> 5) * 64 + (j & 31); }
+
 // ---- synthetic weights: identical arithmetic to streamvln_amd/weights.py ---------------------
 SVLN_DEV uint64_t splitmix64(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

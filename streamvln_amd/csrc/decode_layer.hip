@@ -57,8 +57,7 @@ struct Op {            // one product as this CU sees it
 
 SVLN_DEV size_t op_row(const Op& o, int j) {                   // matrix row of stream row j
     if (!o.pair) return (size_t)(o.first + j);
-    const int out = o.first + (j >> 1);
-    return (size_t)(out >> 5) * 64 + (out & 31) + (j & 1) * 32;
+    return swiglu_gate_row(o.first + (j >> 1)) + (j & 1) * 32;
 }
 // slots of wave w in op o (chunks of o.ch blocks dealt round-robin), rounded up to whole groups of PF
 SVLN_DEV int op_slots(const Op& o, int w) {

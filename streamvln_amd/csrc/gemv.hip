@@ -1,15 +1,21 @@
 // Decode-path GEMV  y[N] = epi(W[N,K] . x'[K] + bias) + res  -- the HBM-bound weight stream that
 // dominates a batch-1 action-token decode (14.1 GB of bf16 weights per token).
 //
-// Structure (gfx950): 256-thread workgroups; the activation vector is staged ONCE per workgroup
-// into LDS as fp32 (with a fused RMSNorm the copy holds g * x and rsqrt(mean x^2 + eps) is applied
-// once per output in the epilogue: one pass over x, one barrier), then every
-// wave streams whole weight rows straight HBM -> VGPR with 16-byte loads (lane i takes chunks
-// i, i+64, ... of the row: each wave instruction reads 1 KiB contiguous), R rows per wave in
-// flight for memory-level parallelism, fp32 FMA accumulate, wave-shuffle reduction, fused epilogue
-// (bias / residual / SwiGLU / arg-max).  No LDS round trip for weights (each byte is used once).
+// Two kernels, each written once over a WEIGHT-FORMAT POLICY (WPlain<T>, WE4m3, WMxfp4 below):
+//   gemv_rows_kernel<P, EPI>         256-thread workgroups; the activation vector is staged ONCE per workgroup into LDS as fp32 (with a
+//       fused RMSNorm the copy holds g * x and rsqrt(mean x^2 + eps) is applied once per output in the epilogue: one pass over x, one
+//       barrier), then every wave streams whole weight rows straight HBM -> VGPR with 16-byte loads (lane i takes chunks i, i+64, ... of
+//       the row: each wave instruction reads 1 KiB contiguous), 4 rows per wave and two chunks per row in flight for memory-level
+//       parallelism, wave-shuffle reduction, fused epilogue (bias / residual / SwiGLU / arg-max).  No LDS round trip for weights (each
+//       byte is used once).
+//   gemv_ksplit_kernel<P, NORM, KW>  small N (qkv / o / down of a decode step): a workgroup owns a few rows and its waves split K.
+// A policy says what a weight format is and nothing else: elements per 16-byte chunk (hence the LDS planes of the staged activations),
+// the per-row handle and the loads of one chunk position, the accumulator and the chunk . x step, the per-row scale after the
+// reduction, and the K-split geometry that was measured best for the format.  Staging, the row loop and its clamp, the SwiGLU row
+// mapping, the arg-max, the bias / residual / store epilogue, the skip flag and the dispatch exist once, outside the policies.
+// gemv_batched_kernel (B environments in lockstep, bf16 / fp32 weights only) is a separate kernel further down.
 //
-// Roofline: HBM.  Algorithmic bytes per launch = N*K*sizeof(T) (+ x, y: negligible).
+// Roofline: HBM.  Algorithmic bytes per launch = the weight matrix in its format (+ x, y: negligible).
 #include <hip/hip_ext.h>
 
 #include <cstdlib>
@@ -22,34 +28,139 @@ namespace svln {
 namespace {
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int GEMV_THREADS = 256;
 constexpr int GEMV_WAVES = GEMV_THREADS / 64;
 
-// x in LDS, split in 16-byte planes so that consecutive lanes read consecutive 16 B (conflict-free):
-// floats of chunk ci, part p (4 floats each) live at xs[p * nch * 4 + ci * 4 ...].
+// ------------------------------------------------------------------------------------------------ weight-format policies
+// Common shape of a policy P:
+//   X                activation / bias / residual / output type
+//   EPC              weights per 16-byte chunk; the staged activations have EPC / 4 LDS planes
+//   Row, row(p, n)   handle of weight row n built from GemvArgs;  Chunk, load(row, ci): what chunk position ci of a row needs
+//   Acc, zero(), fma(chunk, x2, acc), sum(acc)   the accumulator and the chunk . x step (x2[k]: activations 2k, 2k + 1 under the chunk, fp32)
+//   row_scale(p, n)  factor applied to row n's dot product after the reduction
+//   X_LATE           row kernel: load the second chunk's activations only after the first chunk's products
+//   KS_R, KS_KW_NARROW, KS_PAIRED   K-split kernel: rows per row group; waves on K when K <= 4096 (4 above: see launch_gemv_fmt);
+//                    two chunks per row in flight in the un-normalised form
+// The per-format values of the last four are measured choices, not noise: keep them when touching a policy.
+
+// bf16 / fp32 weights in the engine's storage type: one fp32 fmaf chain per row.
+template <typename T> struct WPlain {
+    using X = T;
+    static constexpr int EPC = Elt<T>::PER_CHUNK;
+    struct Row { const T* w; };
+    using Chunk = uint4;
+    using Acc = float;
+    static constexpr bool X_LATE = false;
+    static constexpr int KS_R = 2;                  // (R = 4 / 8 measured slower at N <= 8192)
+    static constexpr int KS_KW_NARROW = 4;
+    static constexpr bool KS_PAIRED = true;         // two chunks per row in flight without the norm, one with it: both as measured
+    SVLN_DEV static Row row(const GemvArgs& p, size_t n) { return {(const T*)p.W + n * p.ldw}; }
+    SVLN_DEV static Chunk load(const Row& r, int ci) { return load_nt(r.w + (size_t)ci * EPC); }
+    SVLN_DEV static Acc zero() { return 0.0f; }
+    SVLN_DEV static void fma(const Chunk& w, const f32x2* x2, Acc& acc) {
+        float f[EPC];
+        chunk_to_f32<T>(w, f);
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) acc = fmaf(f[e], x2[e / 2][e % 2], acc);
+    }
+    SVLN_DEV static float sum(Acc a) { return a; }
+    SVLN_DEV static float row_scale(const GemvArgs&, size_t) { return 1.0f; }
+};
+
+// e4m3 and MXFP4 accumulate in two lanes of packed fp32 FMAs (v_pk_fma_f32: the conversions deliver pairs), summed before the wave
+// reduction.  Both are opt-in modes of the bf16 engine (the engine refuses to enable them otherwise): X = bf16.
+struct WPacked {
+    using X = bf16;
+    using Acc = f32x2;
+    SVLN_DEV static Acc zero() { return f32x2{0.0f, 0.0f}; }
+    SVLN_DEV static float sum(Acc a) { return a[0] + a[1]; }
+};
+
+// Opt-in decode mode: OCP e4m3 bytes with one fp32 scale per output row, applied once after the wave reduction.
+// 16 weights per chunk (v_cvt_pk_f32_fp8: 2 weights per instruction).  Halves the HBM bytes of a decode step; VALU work per byte
+// doubles but stays far below the issue limit.
+struct WE4m3 : WPacked {
+    static constexpr int EPC = 16;
+    struct Row { const uint8_t* w; };
+    using Chunk = uint4;
+    static constexpr bool X_LATE = false;
+    static constexpr int KS_R = 4;
+    static constexpr int KS_KW_NARROW = 4;
+    static constexpr bool KS_PAIRED = false;
+    SVLN_DEV static Row row(const GemvArgs& p, size_t n) { return {(const uint8_t*)p.w8 + n * p.ldw}; }
+    SVLN_DEV static Chunk load(const Row& r, int ci) { return load_nt(r.w + (size_t)ci * 16); }
+    SVLN_DEV static void fma(const Chunk& w, const f32x2* x2, Acc& acc) {
+        const unsigned d[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)d[q], false);
+            const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)d[q], true);
+            acc = __builtin_elementwise_fma(lo, x2[2 * q], acc);
+            acc = __builtin_elementwise_fma(hi, x2[2 * q + 1], acc);
+        }
+    }
+    SVLN_DEV static float row_scale(const GemvArgs& p, size_t n) { return p.scale[n]; }
+};
+
+// Opt-in decode mode (svln_set_mxfp4_decode): OCP MXFP4 -- E2M1 elements on the grid {0, 0.5, 1, 1.5, 2, 3, 4, 6} with the sign in
+// bit 3, element 2j in the low nibble and 2j + 1 in the high nibble of byte j, and one E8M0 scale byte (2^(byte - 127)) per block of 32
+// consecutive elements of a row: q4 [N][K/2] bytes, e8 [N][K/32] bytes, 4.25 bits per weight.  One 16-byte chunk is one MX block; its
+// scale byte is shifted into a float's exponent field and sixteen v_cvt_scalef32_pk_f32_fp4 (one byte -> two scaled fp32 values each)
+// feed v_pk_fma_f32 against 32 activations.  There is no per-row scale: the block scale is applied by the conversion.
+struct WMxfp4 : WPacked {
+    static constexpr int EPC = 32;
+    struct Row { const uint8_t* q; const uint8_t* s; };
+    struct Chunk { uint4 q; unsigned s; };
+    static constexpr bool X_LATE = true;            // register pressure: the row kernels sit at 163-179 VGPRs
+    static constexpr int KS_R = 4;
+    static constexpr int KS_KW_NARROW = 2;          // a row of K = 3584 is only 112 blocks, fewer than two waves' worth of lanes
+    static constexpr bool KS_PAIRED = false;
+    SVLN_DEV static Row row(const GemvArgs& p, size_t n) {      // row strides of q4 / e8 in bytes: ldw / 2, ldw / 32
+        return {(const uint8_t*)p.w4 + n * ((size_t)p.ldw / 2), p.e8 + n * ((size_t)p.ldw / 32)};
+    }
+    SVLN_DEV static Chunk load(const Row& r, int ci) { return {load_nt(r.q + (size_t)ci * 16), r.s[ci]}; }
+    SVLN_DEV static void fma(const Chunk& w, const f32x2* x2, Acc& acc) {
+        const unsigned d[4] = {w.q.x, w.q.y, w.q.z, w.q.w};
+        const float sc = __uint_as_float(w.s << 23);            // E8M0 -> fp32
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 0), x2[4 * q], acc);
+            acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 1), x2[4 * q + 1], acc);
+            acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 2), x2[4 * q + 2], acc);
+            acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 3), x2[4 * q + 3], acc);
+        }
+    }
+    SVLN_DEV static float row_scale(const GemvArgs&, size_t) { return 1.0f; }
+};
+
+// ------------------------------------------------------------------------------------------------ shared pieces
+// x in LDS as fp32, split in PLANES 16-byte planes per weight chunk so that consecutive lanes read consecutive 16 B (conflict-free):
+// element 4 * q + e of the activations under weight chunk cj lives at xs[q * nch * 4 + cj * 4 + e]  (nch = weight chunks per row).
 // With a fused RMSNorm the LDS copy holds g * x (one pass over x, one barrier) and the function returns rsqrt(mean(x^2) + eps):
 // y = rstd * (W . (g * x)) -- the scale is applied once per output in the epilogue (same folding as gemv_ksplit_kernel).
-template <typename T>
+template <typename X, int PLANES>
 SVLN_DEV float stage_x(float* xs, const GemvArgs& p, int nch) {
-    constexpr int EPC = Elt<T>::PER_CHUNK;
-    constexpr int PARTS = EPC / 4;
+    constexpr int XEPC = Elt<X>::PER_CHUNK;         // one activation chunk fills XP planes; XPW of them lie under one weight chunk
+    constexpr int XP = XEPC / 4, XPW = PLANES / XP;
     __shared__ float red[GEMV_WAVES];
-    const T* x = (const T*)p.x;
-    const T* g = (const T*)p.norm_w;
-    const int tid = threadIdx.x;
+    const X* x = (const X*)p.x;
+    const X* g = (const X*)p.norm_w;
+    const int tid = threadIdx.x, nxch = p.K / XEPC;
     float ss = 0.0f;
-    for (int ci = tid; ci < nch; ci += GEMV_THREADS) {
-        float f[EPC];
-        chunk_to_f32<T>(*(const uint4*)(x + (size_t)ci * EPC), f);
+    for (int ci = tid; ci < nxch; ci += GEMV_THREADS) {
+        float f[XEPC];
+        chunk_to_f32<X>(*(const uint4*)(x + (size_t)ci * XEPC), f);
         if (g) {
-            float gf[EPC];
-            chunk_to_f32<T>(*(const uint4*)(g + (size_t)ci * EPC), gf);
+            float gf[XEPC];
+            chunk_to_f32<X>(*(const uint4*)(g + (size_t)ci * XEPC), gf);
 #pragma unroll
-            for (int e = 0; e < EPC; ++e) { ss = fmaf(f[e], f[e], ss); f[e] *= gf[e]; }
+            for (int e = 0; e < XEPC; ++e) { ss = fmaf(f[e], f[e], ss); f[e] *= gf[e]; }
         }
+        const int cj = ci / XPW, p0 = (ci % XPW) * XP;
 #pragma unroll
-        for (int q = 0; q < PARTS; ++q)
-            *(float4*)(xs + (size_t)q * nch * 4 + (size_t)ci * 4) = make_float4(f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]);
+        for (int q = 0; q < XP; ++q)
+            *(float4*)(xs + (size_t)(p0 + q) * nch * 4 + (size_t)cj * 4) = make_float4(f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]);
     }
     if (g) {
         ss = wave_sum(ss);
@@ -63,137 +174,228 @@ SVLN_DEV float stage_x(float* xs, const GemvArgs& p, int nch) {
     return rsqrtf(tot / (float)p.K + p.eps);
 }
 
-template <typename T>
-SVLN_DEV void load_x(const float* xs, int nch, int ci, float* f) {
-    constexpr int PARTS = Elt<T>::PER_CHUNK / 4;
+// the activations under weight chunk ci as fp32 pairs (x2[k] = activations 2k, 2k + 1): from the staged LDS copy, or straight from
+// global memory (L2-resident, 7-37 KB)
+template <int PLANES>
+SVLN_DEV void load_x(const float* xs, int nch, int ci, f32x2* x2) {
 #pragma unroll
-    for (int q = 0; q < PARTS; ++q) {
+    for (int q = 0; q < PLANES; ++q) {
         const float4 v = *(const float4*)(xs + (size_t)q * nch * 4 + (size_t)ci * 4);
-        f[4 * q] = v.x; f[4 * q + 1] = v.y; f[4 * q + 2] = v.z; f[4 * q + 3] = v.w;
+        x2[2 * q] = f32x2{v.x, v.y};
+        x2[2 * q + 1] = f32x2{v.z, v.w};
     }
 }
+// (global form) NORM: x2 holds g * x, and the squares of x are added to ss in element order; returns the new ss
+template <typename P, bool NORM>
+SVLN_DEV float load_xg(const typename P::X* xg, const typename P::X* gg, int ci, f32x2* x2, float ss) {
+    using X = typename P::X;
+    constexpr int XEPC = Elt<X>::PER_CHUNK;
+#pragma unroll
+    for (int h = 0; h < P::EPC / XEPC; ++h) {
+        float fh[XEPC];
+        chunk_to_f32<X>(*(const uint4*)(xg + (size_t)ci * P::EPC + h * XEPC), fh);
+        if (NORM) {
+            float gf[XEPC];
+            chunk_to_f32<X>(*(const uint4*)(gg + (size_t)ci * P::EPC + h * XEPC), gf);
+#pragma unroll
+            for (int e = 0; e < XEPC; ++e) { ss = fmaf(fh[e], fh[e], ss); fh[e] *= gf[e]; }
+        }
+#pragma unroll
+        for (int e = 0; e < XEPC / 2; ++e) x2[h * (XEPC / 2) + e] = f32x2{fh[2 * e], fh[2 * e + 1]};
+    }
+    return ss;
+}
 
-// R dot products against x over the chunks ci = c0 + lane + 64*k*cstep (k = 0, 1, ...) below nch.
-// XLDS: x comes from the workgroup's LDS copy (fp32, possibly RMS-normalised); otherwise each lane reads the
-// x chunk it needs straight from global memory (L2-resident, 7-37 KB) next to its weight chunks.
-template <typename T, int R, bool XLDS>
-SVLN_DEV void dot_accum(const T* const (&rows)[R], const float* xs, const T* xg, int nch, int c0, int cstep, int lane, float (&acc)[R]) {
-    constexpr int EPC = Elt<T>::PER_CHUNK;
+// acc[r] += row r . x over the chunks ci = c0 + lane + 64*k*cstep (k = 0, 1, ...) below nch, two chunks per row in flight
+// (2R x 1 KiB per wave).  XLDS: x comes from the workgroup's LDS copy (possibly RMS-normalised); otherwise each lane reads the
+// x chunk it needs from global memory next to its weight chunks.
+template <typename P, int R, bool XLDS>
+SVLN_DEV void dot_accum(const typename P::Row (&rows)[R], const float* xs, const typename P::X* xg, int nch, int c0, int cstep, int lane,
+                        typename P::Acc (&acc)[R]) {
+    constexpr int EPC = P::EPC;
+    auto get_x = [&](int ci, f32x2* x2) {
+        if (XLDS) load_x<EPC / 4>(xs, nch, ci, x2);
+        else load_xg<P, false>(xg, nullptr, ci, x2, 0.0f);
+    };
     const int stride = 64 * cstep;
     int ci = c0 + lane;
-    for (; ci + stride < nch; ci += 2 * stride) {      // two chunks per row in flight: 2R x 1 KiB per wave
-        uint4 w0[R], w1[R];
+    for (; ci + stride < nch; ci += 2 * stride) {
+        typename P::Chunk w0[R], w1[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            w0[r] = load_nt(rows[r] + (size_t)ci * EPC);
-            w1[r] = load_nt(rows[r] + (size_t)(ci + stride) * EPC);
+            w0[r] = P::load(rows[r], ci);
+            w1[r] = P::load(rows[r], ci + stride);
         }
-        float x0[EPC], x1[EPC];
-        if (XLDS) {
-            load_x<T>(xs, nch, ci, x0);
-            load_x<T>(xs, nch, ci + stride, x1);
+        f32x2 x0[EPC / 2];
+        get_x(ci, x0);
+        if (P::X_LATE) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) P::fma(w0[r], x0, acc[r]);
+            get_x(ci + stride, x0);
+#pragma unroll
+            for (int r = 0; r < R; ++r) P::fma(w1[r], x0, acc[r]);
         } else {
-            chunk_to_f32<T>(*(const uint4*)(xg + (size_t)ci * EPC), x0);
-            chunk_to_f32<T>(*(const uint4*)(xg + (size_t)(ci + stride) * EPC), x1);
-        }
+            f32x2 x1[EPC / 2];
+            get_x(ci + stride, x1);
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            float f[EPC];
-            chunk_to_f32<T>(w0[r], f);
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) acc[r] = fmaf(f[e], x0[e], acc[r]);
-            chunk_to_f32<T>(w1[r], f);
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) acc[r] = fmaf(f[e], x1[e], acc[r]);
+            for (int r = 0; r < R; ++r) {
+                P::fma(w0[r], x0, acc[r]);
+                P::fma(w1[r], x1, acc[r]);
+            }
         }
     }
     for (; ci < nch; ci += stride) {
-        float x0[EPC];
-        if (XLDS) load_x<T>(xs, nch, ci, x0);
-        else chunk_to_f32<T>(*(const uint4*)(xg + (size_t)ci * EPC), x0);
+        typename P::Chunk w0[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            float f[EPC];
-            chunk_to_f32<T>(load_nt(rows[r] + (size_t)ci * EPC), f);
+        for (int r = 0; r < R; ++r) w0[r] = P::load(rows[r], ci);
+        f32x2 x0[EPC / 2];
+        get_x(ci, x0);
 #pragma unroll
-            for (int e = 0; e < EPC; ++e) acc[r] = fmaf(f[e], x0[e], acc[r]);
+        for (int r = 0; r < R; ++r) P::fma(w0[r], x0, acc[r]);
+    }
+}
+
+// bias / residual / store of output n
+template <typename X>
+SVLN_DEV void store_out(const GemvArgs& p, int n, float v) {
+    if (p.bias) v += to_f32(((const X*)p.bias)[n]);
+    if (p.res) v += to_f32(((const X*)p.res)[n]);
+    ((X*)p.y)[n] = from_f32<X>(v);
+}
+
+// ------------------------------------------------------------------------------------------------ wave-per-rows kernel
+// A wave takes groups of R = 4 weight rows: R consecutive outputs, or with EPI_SWIGLU the (gate, up) rows of 2 consecutive outputs.
+template <typename P, int EPI>
+__global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
+    using X = typename P::X;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    float* xs = (float*)smem_raw;
+    const int skip = p.skip ? *p.skip : 0;        // checked after the activation staging, so the flag's load latency hides behind it
+    constexpr int R = 4, OUTS = EPI == EPI_SWIGLU ? R / 2 : R;     // rows / outputs per group
+    const int nch = p.K / P::EPC;
+    const float xscale = stage_x<X, P::EPC / 4>(xs, p, nch);
+    if (skip) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int gw = blockIdx.x * GEMV_WAVES + wave, nw = gridDim.x * GEMV_WAVES;
+    const int n_out = EPI == EPI_SWIGLU ? p.N >> 1 : p.N;
+
+    float best = -INFINITY;                       // EPI_ARGMAX
+    int best_i = 0x7FFFFFFF;
+    for (int n0 = gw * OUTS; n0 < n_out; n0 += nw * OUTS) {
+        size_t rn[R];                             // the group's weight rows; a ragged last group repeats the last output's rows
+#pragma unroll
+        for (int u = 0; u < OUTS; ++u) {
+            const int j = min(n0 + u, n_out - 1);
+            if (EPI == EPI_SWIGLU) { rn[2 * u] = swiglu_gate_row(j); rn[2 * u + 1] = rn[2 * u] + 32; }
+            else rn[u] = (size_t)j;
+        }
+        typename P::Row rows[R];
+        typename P::Acc a[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) { rows[r] = P::row(p, rn[r]); a[r] = P::zero(); }
+        dot_accum<P, R, true>(rows, xs, nullptr, nch, 0, 1, lane, a);
+        float acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = wave_sum(P::sum(a[r])) * (P::row_scale(p, rn[r]) * xscale);
+        if (EPI == EPI_SWIGLU) {
+            if (lane < OUTS && n0 + lane < n_out) {
+                const float gt = lane == 0 ? acc[0] : acc[2], up = lane == 0 ? acc[1] : acc[3];
+                ((X*)p.y)[n0 + lane] = from_f32<X>(silu_f(gt) * up);
+            }
+        } else if (EPI == EPI_ARGMAX) {
+            if (p.pen_flags) {
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    if (n0 + r < p.N && p.pen_flags[n0 + r]) acc[r] = acc[r] < 0.0f ? acc[r] * p.pen : acc[r] / p.pen;
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (n0 + r < p.N && acc[r] > best) { best = acc[r]; best_i = n0 + r; }     // rows ascend: first max wins
+        } else if (lane < R && n0 + lane < p.N) {
+            store_out<X>(p, n0 + lane, lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3]);
+        }
+    }
+    if (EPI == EPI_ARGMAX) {
+        __shared__ float bv[GEMV_WAVES];
+        __shared__ int bi[GEMV_WAVES];
+        if (lane == 0) { bv[wave] = best; bi[wave] = best_i; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float v = bv[0]; int i = bi[0];
+#pragma unroll
+            for (int w = 1; w < GEMV_WAVES; ++w)
+                if (bv[w] > v || (bv[w] == v && bi[w] < i)) { v = bv[w]; i = bi[w]; }
+            p.part_val[blockIdx.x] = v;
+            p.part_idx[blockIdx.x] = i;
         }
     }
 }
-template <typename T, int R, bool XLDS>
-SVLN_DEV void dot_rows(const T* const (&rows)[R], const float* xs, const T* xg, int nch, int c0, int cstep, int lane, float (&acc)[R]) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = 0.0f;
-    dot_accum<T, R, XLDS>(rows, xs, xg, nch, c0, cstep, lane, acc);
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
-}
 
-// Small-N variant (qkv / o / down projections of a decode step: N <= 8192 rows is only 224-288 workgroups of the
-// wave-per-rows kernel, i.e. < 1 per CU).  Here a workgroup owns 4 rows and its 4 waves split K (interleaved
-// 1 KiB blocks), so N/4 workgroups exist (3.5-4.5 per CU) and their prologues overlap other workgroups' streams.
-template <typename T, bool NORM, int R>
+// ------------------------------------------------------------------------------------------------ K-split kernel
+// Small-N variant (qkv / o / down projections of a decode step: N <= 8192 rows is only 224-288 workgroups of the wave-per-rows kernel,
+// i.e. < 1 per CU).  KW of the workgroup's 4 waves split K (interleaved 1 KiB blocks) and the 4 / KW groups of KW waves take
+// R = P::KS_R rows each, so N / (R * 4 / KW) workgroups exist (3.5-4.5 per CU) and their prologues overlap other workgroups' streams.
+// RMSNorm is folded into the product, no prologue:  y = rsqrt(mean(x^2) + eps) * sum_i W[n][i] * (g[i] * x[i]); every wave reads its
+// K share of x and g from global memory next to its weight chunks (L2-resident, 7 KB each).  No staging to hide the skip flag's load
+// behind: the kernel returns at once.
+template <typename P, bool NORM, int KW>
 __global__ __launch_bounds__(GEMV_THREADS) void gemv_ksplit_kernel(GemvArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    __shared__ float part[GEMV_WAVES][R + 1];
+    using X = typename P::X;
+    constexpr int R = P::KS_R, EPC = P::EPC;
+    constexpr int RG = GEMV_WAVES / KW;             // row groups per workgroup
+    __shared__ float part[GEMV_WAVES][R + 1];       // [.][R] = the wave's share of sum(x^2) when NORM
     if (p.skip && *p.skip) return;
-    constexpr int EPC = Elt<T>::PER_CHUNK;
     const int nch = p.K / EPC;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const T* W = (const T*)p.W;
-    const T* xg = (const T*)p.x;
-    const T* gg = (const T*)p.norm_w;
-    constexpr int STRIDE = 64 * GEMV_WAVES;
-    for (int n0 = blockIdx.x * R; n0 < p.N; n0 += gridDim.x * R) {
-        const T* rows[R];
+    const int kw = RG == 1 ? wave : wave % KW, rg = RG == 1 ? 0 : wave / KW;      // (rg spelled out as 0: the row index stays scalar)
+    const X* xg = (const X*)p.x;
+    const X* gg = (const X*)p.norm_w;
+    for (int b0 = blockIdx.x * RG * R; b0 < p.N; b0 += gridDim.x * RG * R) {
+        const int n0 = b0 + rg * R;                 // (may lie beyond N for the last workgroup: rows clamp, nothing is written)
+        typename P::Row rows[R];
+        typename P::Acc a[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) rows[r] = W + (size_t)min(n0 + r, p.N - 1) * p.ldw;
-        float acc[R + 1];                      // acc[R] = this wave's share of sum(x^2) when NORM
-#pragma unroll
-        for (int r = 0; r <= R; ++r) acc[r] = 0.0f;
-        if (NORM) {
-            // RMSNorm folded into the product, no prologue:  y = rsqrt(mean(x^2) + eps) * sum_i W[n][i] * (g[i] * x[i]);
-            // every wave reads its K share of x and g next to its weight chunks (L2-resident, 7 KB each)
-            for (int ci = wave * 64 + lane; ci < nch; ci += STRIDE) {
-                uint4 w[R];
-#pragma unroll
-                for (int r = 0; r < R; ++r) w[r] = load_nt(rows[r] + (size_t)ci * EPC);
-                float xf[EPC], gf[EPC];
-                chunk_to_f32<T>(*(const uint4*)(xg + (size_t)ci * EPC), xf);
-                chunk_to_f32<T>(*(const uint4*)(gg + (size_t)ci * EPC), gf);
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) { acc[R] = fmaf(xf[e], xf[e], acc[R]); xf[e] *= gf[e]; }
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    float f[EPC];
-                    chunk_to_f32<T>(w[r], f);
-#pragma unroll
-                    for (int e = 0; e < EPC; ++e) acc[r] = fmaf(f[e], xf[e], acc[r]);
-                }
-            }
-            acc[R] = wave_sum(acc[R]);
+        for (int r = 0; r < R; ++r) { rows[r] = P::row(p, (size_t)min(n0 + r, p.N - 1)); a[r] = P::zero(); }
+        float ss = 0.0f;
+        if (!NORM && P::KS_PAIRED) {
+            dot_accum<P, R, false>(rows, nullptr, xg, nch, kw * 64, KW, lane, a);
         } else {
-            float a4[R];
+            for (int ci = kw * 64 + lane; ci < nch; ci += 64 * KW) {
+                typename P::Chunk w[R];
 #pragma unroll
-            for (int r = 0; r < R; ++r) a4[r] = 0.0f;
-            dot_accum<T, R, false>(rows, nullptr, xg, nch, wave * 64, GEMV_WAVES, lane, a4);
+                for (int r = 0; r < R; ++r) w[r] = P::load(rows[r], ci);
+                // all R weight loads are issued before anything else of the iteration: left alone, the scheduler sinks some of them
+                // below the norm arithmetic and waits for each in turn (seen in the e4m3 NORM form)
+                __builtin_amdgcn_sched_barrier(0);
+                f32x2 xf[EPC / 2];
+                ss = load_xg<P, NORM>(xg, gg, ci, xf, ss);
 #pragma unroll
-            for (int r = 0; r < R; ++r) acc[r] = a4[r];
+                for (int r = 0; r < R; ++r) P::fma(w[r], xf, a[r]);
+            }
         }
+        // the accumulators stay R separate values: without this the SLP vectoriser, seeded by the R horizontal sums below, fuses the
+        // rows' packed FMAs of the e4m3 NORM form into <8 x float> operations (88 VGPRs instead of 80, one wave per SIMD fewer)
 #pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
+        for (int r = 0; r < R; ++r) asm volatile("" : "+v"(a[r]));
+        float acc[R + 1];
+        acc[R] = NORM ? wave_sum(ss) : 0.0f;
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = wave_sum(P::sum(a[r]));
         if (lane == 0) {
 #pragma unroll
             for (int r = 0; r <= R; ++r) part[wave][r] = acc[r];
         }
         __syncthreads();
-        if (threadIdx.x < R && n0 + threadIdx.x < p.N) {
-            const int n = n0 + threadIdx.x;
-            float v = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-            if (NORM) v *= rsqrtf((part[0][R] + part[1][R] + part[2][R] + part[3][R]) / (float)p.K + p.eps);
-            if (p.bias) v += to_f32(((const T*)p.bias)[n]);
-            if (p.res) v += to_f32(((const T*)p.res)[n]);
-            ((T*)p.y)[n] = from_f32<T>(v);
+        if (threadIdx.x < RG * R) {
+            const int g2 = threadIdx.x / R, r = threadIdx.x % R, n = b0 + g2 * R + r;
+            if (n < p.N) {
+                float v = part[g2 * KW][r], s2 = part[g2 * KW][R];
+#pragma unroll
+                for (int k = 1; k < KW; ++k) { v += part[g2 * KW + k][r]; s2 += part[g2 * KW + k][R]; }
+                v *= P::row_scale(p, n);
+                if (NORM) v *= rsqrtf(s2 / (float)p.K + p.eps);
+                store_out<X>(p, n, v);
+            }
         }
         __syncthreads();
     }
@@ -224,7 +426,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
             n0 = j0;
 #pragma unroll
             for (int o = 0; o < R / 2; ++o) {
-                const size_t gr = (size_t)((j0 + o) >> 5) * 64 + ((j0 + o) & 31);
+                const size_t gr = swiglu_gate_row(j0 + o);
                 rows[2 * o] = W + gr * p.ldw;
                 rows[2 * o + 1] = W + (gr + 32) * p.ldw;
             }
@@ -358,333 +560,6 @@ __global__ __launch_bounds__(256) void argmax_final_batched_kernel(const float* 
     if (threadIdx.x == 0) out_tokens[blockIdx.x] = si[0] == 0x7FFFFFFF ? -1 : si[0];    // no finite logit: -1 (in-range for the next gather, an error on the host)
 }
 
-template <typename T, int EPI>
-__global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel(GemvArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* xs = (float*)smem_raw;
-    const int skip = p.skip ? *p.skip : 0;        // checked after the activation staging, so the flag's load latency hides behind it
-    constexpr int EPC = Elt<T>::PER_CHUNK;
-    constexpr int R = 4;
-    const int nch = p.K / EPC;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int gw = blockIdx.x * GEMV_WAVES + wave, nw = gridDim.x * GEMV_WAVES;
-    const T* W = (const T*)p.W;
-
-    if (EPI == EPI_SWIGLU) {
-        // packed rows: 64-row blocks = [32 gate | 32 up]; one group = 2 outputs (2 gate + 2 up rows)
-        const int n_out = p.N >> 1;
-        T* y = (T*)p.y;
-        auto group_rows = [&](int j0, const T* (&rows)[R]) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int j = min(j0 + u, n_out - 1);
-                const size_t gr = (size_t)(j >> 5) * 64 + (j & 31);
-                rows[2 * u] = W + gr * p.ldw;
-                rows[2 * u + 1] = W + (gr + 32) * p.ldw;
-            }
-        };
-        const float xscale = stage_x<T>(xs, p, nch);
-        if (skip) return;
-        auto finish = [&](int j0, const float (&acc)[R]) {
-            if (lane < 2 && j0 + lane < n_out) {
-                const float gt = (lane == 0 ? acc[0] : acc[2]) * xscale, up = (lane == 0 ? acc[1] : acc[3]) * xscale;
-                y[j0 + lane] = from_f32<T>(silu_f(gt) * up);
-            }
-        };
-        for (int j0 = gw * 2; j0 < n_out; j0 += nw * 2) {
-            const T* rows[R];
-            group_rows(j0, rows);
-            float acc[R];
-            dot_rows<T, R, true>(rows, xs, nullptr, nch, 0, 1, lane, acc);
-            finish(j0, acc);
-        }
-        return;
-    }
-    const float xscale = stage_x<T>(xs, p, nch);
-    if (skip) return;
-
-    float best = -INFINITY;
-    int best_i = 0x7FFFFFFF;
-    for (int n0 = gw * R; n0 < p.N; n0 += nw * R) {
-        const T* rows[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) rows[r] = W + (size_t)min(n0 + r, p.N - 1) * p.ldw;
-        float acc[R];
-        dot_rows<T, R, true>(rows, xs, nullptr, nch, 0, 1, lane, acc);
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] *= xscale;
-        if (EPI == EPI_ARGMAX) {
-            if (p.pen_flags) {
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                    if (n0 + r < p.N && p.pen_flags[n0 + r]) acc[r] = acc[r] < 0.0f ? acc[r] * p.pen : acc[r] / p.pen;
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-                if (n0 + r < p.N && acc[r] > best) { best = acc[r]; best_i = n0 + r; }     // rows ascend: first max wins
-        } else if (lane < R && n0 + lane < p.N) {
-            const int n = n0 + lane;
-            float v = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
-            if (p.bias) v += to_f32(((const T*)p.bias)[n]);
-            if (p.res) v += to_f32(((const T*)p.res)[n]);
-            ((T*)p.y)[n] = from_f32<T>(v);
-        }
-    }
-    if (EPI == EPI_ARGMAX) {
-        __shared__ float bv[GEMV_WAVES];
-        __shared__ int bi[GEMV_WAVES];
-        if (lane == 0) { bv[wave] = best; bi[wave] = best_i; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float v = bv[0]; int i = bi[0];
-#pragma unroll
-            for (int w = 1; w < GEMV_WAVES; ++w)
-                if (bv[w] > v || (bv[w] == v && bi[w] < i)) { v = bv[w]; i = bi[w]; }
-            p.part_val[blockIdx.x] = v;
-            p.part_idx[blockIdx.x] = i;
-        }
-    }
-}
-
-
-// ------------------------------------------------------------------------------------------------ fp8 weight-only variants
-// Opt-in decode mode: the weights are stored as OCP e4m3 bytes with one fp32 scale per output row, the
-// activations stay bf16/fp32.  Same structure as the bf16 kernels above with 16 weights per 16-byte chunk
-// (v_cvt_pk_f32_fp8: 2 weights per instruction), the row scale applied once after the wave reduction.  Halves the HBM bytes of
-// a decode step; VALU work per byte doubles but stays far below the issue limit.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-SVLN_DEV void fp8x16_to_f32(const uint4& w, float* f) {
-    const unsigned d[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)d[q], false);
-        const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)d[q], true);
-        f[4 * q] = lo[0]; f[4 * q + 1] = lo[1]; f[4 * q + 2] = hi[0]; f[4 * q + 3] = hi[1];
-    }
-}
-// acc (two partial sums) += 16 e4m3 weights . 16 activations, as packed fp32 FMAs (v_pk_fma_f32: the conversion delivers pairs)
-SVLN_DEV void fp8x16_dot(const uint4& w, const f32x2* x2, f32x2& acc) {
-    const unsigned d[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)d[q], false);
-        const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)d[q], true);
-        acc = __builtin_elementwise_fma(lo, x2[2 * q], acc);
-        acc = __builtin_elementwise_fma(hi, x2[2 * q + 1], acc);
-    }
-}
-// x (bf16 in global memory) -> LDS fp32 in four 16-byte planes per 16-element chunk: element 16*cj + 4*p + e lives at
-// xs[p * nch8 * 4 + cj * 4 + e], so consecutive lanes read consecutive 16 B in every plane.
-SVLN_DEV float stage_x8(float* xs, const GemvArgs& p, int nch8) {
-    __shared__ float red8[GEMV_WAVES];
-    const bf16* x = (const bf16*)p.x;
-    const bf16* g = (const bf16*)p.norm_w;
-    const int tid = threadIdx.x, nch = p.K / 8;
-    float ss = 0.0f;
-    for (int ci = tid; ci < nch; ci += GEMV_THREADS) {
-        float f[8];
-        chunk_to_f32<bf16>(*(const uint4*)(x + (size_t)ci * 8), f);
-        if (g) {
-            float gf[8];
-            chunk_to_f32<bf16>(*(const uint4*)(g + (size_t)ci * 8), gf);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { ss = fmaf(f[e], f[e], ss); f[e] *= gf[e]; }
-        }
-        const int cj = ci >> 1, p0 = (ci & 1) * 2;
-        *(float4*)(xs + (size_t)p0 * nch8 * 4 + (size_t)cj * 4) = make_float4(f[0], f[1], f[2], f[3]);
-        *(float4*)(xs + (size_t)(p0 + 1) * nch8 * 4 + (size_t)cj * 4) = make_float4(f[4], f[5], f[6], f[7]);
-    }
-    if (g) {
-        ss = wave_sum(ss);
-        if ((tid & 63) == 0) red8[tid >> 6] = ss;
-    }
-    __syncthreads();
-    if (!g) return 1.0f;
-    float tot = 0.0f;
-#pragma unroll
-    for (int w = 0; w < GEMV_WAVES; ++w) tot += red8[w];
-    return rsqrtf(tot / (float)p.K + p.eps);     // applied in the epilogue: y = rstd * scale[n] * (Wq . (g * x))
-}
-SVLN_DEV void load_x8(const float* xs, int nch8, int cj, f32x2* x2) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = *(const float4*)(xs + (size_t)q * nch8 * 4 + (size_t)cj * 4);
-        x2[2 * q] = f32x2{v.x, v.y};
-        x2[2 * q + 1] = f32x2{v.z, v.w};
-    }
-}
-// R dot products of fp8 rows against the LDS copy of x; two chunks per row in flight
-template <int R>
-SVLN_DEV void dot8_rows(const uint8_t* const (&rows)[R], const float* xs, int nch8, int lane, float (&acc)[R]) {
-    f32x2 a2[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) a2[r] = f32x2{0.0f, 0.0f};
-    int ci = lane;
-    for (; ci + 64 < nch8; ci += 128) {
-        uint4 w0[R], w1[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            w0[r] = load_nt(rows[r] + (size_t)ci * 16);
-            w1[r] = load_nt(rows[r] + (size_t)(ci + 64) * 16);
-        }
-        f32x2 x0[8], x1[8];
-        load_x8(xs, nch8, ci, x0);
-        load_x8(xs, nch8, ci + 64, x1);
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            fp8x16_dot(w0[r], x0, a2[r]);
-            fp8x16_dot(w1[r], x1, a2[r]);
-        }
-    }
-    for (; ci < nch8; ci += 64) {
-        f32x2 x0[8];
-        load_x8(xs, nch8, ci, x0);
-#pragma unroll
-        for (int r = 0; r < R; ++r) fp8x16_dot(load_nt(rows[r] + (size_t)ci * 16), x0, a2[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = wave_sum(a2[r][0] + a2[r][1]);
-}
-
-template <int EPI>
-__global__ __launch_bounds__(GEMV_THREADS) void gemv8_kernel(GemvArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* xs = (float*)smem_raw;
-    const int skip = p.skip ? *p.skip : 0;
-    constexpr int R = 4;
-    const int nch8 = p.K / 16;
-    const float xscale = stage_x8(xs, p, nch8);
-    if (skip) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int gw = blockIdx.x * GEMV_WAVES + wave, nw = gridDim.x * GEMV_WAVES;
-    const uint8_t* W = (const uint8_t*)p.w8;
-    if (EPI == EPI_SWIGLU) {
-        const int n_out = p.N >> 1;
-        bf16* y = (bf16*)p.y;
-        for (int j0 = gw * 2; j0 < n_out; j0 += nw * 2) {
-            const uint8_t* rows[R];
-            size_t gr[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int j = min(j0 + u, n_out - 1);
-                gr[u] = (size_t)(j >> 5) * 64 + (j & 31);
-                rows[2 * u] = W + gr[u] * p.ldw;
-                rows[2 * u + 1] = W + (gr[u] + 32) * p.ldw;
-            }
-            float acc[R];
-            dot8_rows<R>(rows, xs, nch8, lane, acc);
-            if (lane < 2 && j0 + lane < n_out) {
-                const size_t g0 = gr[lane];
-                const float gt = (lane == 0 ? acc[0] : acc[2]) * (p.scale[g0] * xscale), up = (lane == 0 ? acc[1] : acc[3]) * (p.scale[g0 + 32] * xscale);
-                y[j0 + lane] = from_f32<bf16>(silu_f(gt) * up);
-            }
-        }
-        return;
-    }
-    float best = -INFINITY;
-    int best_i = 0x7FFFFFFF;
-    for (int n0 = gw * R; n0 < p.N; n0 += nw * R) {
-        const uint8_t* rows[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) rows[r] = W + (size_t)min(n0 + r, p.N - 1) * p.ldw;
-        float acc[R];
-        dot8_rows<R>(rows, xs, nch8, lane, acc);
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] *= p.scale[min(n0 + r, p.N - 1)] * xscale;
-        if (EPI == EPI_ARGMAX) {
-            if (p.pen_flags) {
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                    if (n0 + r < p.N && p.pen_flags[n0 + r]) acc[r] = acc[r] < 0.0f ? acc[r] * p.pen : acc[r] / p.pen;
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-                if (n0 + r < p.N && acc[r] > best) { best = acc[r]; best_i = n0 + r; }
-        } else if (lane < R && n0 + lane < p.N) {
-            const int n = n0 + lane;
-            float v = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
-            if (p.bias) v += to_f32(((const bf16*)p.bias)[n]);
-            if (p.res) v += to_f32(((const bf16*)p.res)[n]);
-            ((bf16*)p.y)[n] = from_f32<bf16>(v);
-        }
-    }
-    if (EPI == EPI_ARGMAX) {
-        __shared__ float bv[GEMV_WAVES];
-        __shared__ int bi[GEMV_WAVES];
-        if (lane == 0) { bv[wave] = best; bi[wave] = best_i; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float v = bv[0]; int i = bi[0];
-#pragma unroll
-            for (int w = 1; w < GEMV_WAVES; ++w)
-                if (bv[w] > v || (bv[w] == v && bi[w] < i)) { v = bv[w]; i = bi[w]; }
-            p.part_val[blockIdx.x] = v;
-            p.part_idx[blockIdx.x] = i;
-        }
-    }
-}
-
-// small-N fp8 variant: workgroup = R rows, its 4 waves split K; RMSNorm folded in without a prologue (as gemv_ksplit_kernel)
-template <bool NORM, int R>
-__global__ __launch_bounds__(GEMV_THREADS) void gemv8_ksplit_kernel(GemvArgs p) {
-    __shared__ float part[GEMV_WAVES][R + 1];
-    if (p.skip && *p.skip) return;
-    const int nch8 = p.K / 16;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint8_t* W = (const uint8_t*)p.w8;
-    const bf16* xg = (const bf16*)p.x;
-    const bf16* gg = (const bf16*)p.norm_w;
-    for (int n0 = blockIdx.x * R; n0 < p.N; n0 += gridDim.x * R) {
-        const uint8_t* rows[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) rows[r] = W + (size_t)min(n0 + r, p.N - 1) * p.ldw;
-        float acc[R + 1];
-        f32x2 a2[R];
-#pragma unroll
-        for (int r = 0; r <= R; ++r) acc[r] = 0.0f;
-#pragma unroll
-        for (int r = 0; r < R; ++r) a2[r] = f32x2{0.0f, 0.0f};
-        for (int ci = wave * 64 + lane; ci < nch8; ci += 64 * GEMV_WAVES) {
-            uint4 w[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r) w[r] = load_nt(rows[r] + (size_t)ci * 16);
-            float xf[16];
-            chunk_to_f32<bf16>(*(const uint4*)(xg + (size_t)ci * 16), xf);
-            chunk_to_f32<bf16>(*(const uint4*)(xg + (size_t)ci * 16 + 8), xf + 8);
-            if (NORM) {
-                float gf[16];
-                chunk_to_f32<bf16>(*(const uint4*)(gg + (size_t)ci * 16), gf);
-                chunk_to_f32<bf16>(*(const uint4*)(gg + (size_t)ci * 16 + 8), gf + 8);
-#pragma unroll
-                for (int e = 0; e < 16; ++e) { acc[R] = fmaf(xf[e], xf[e], acc[R]); xf[e] *= gf[e]; }
-            }
-            f32x2 x2[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x2[e] = f32x2{xf[2 * e], xf[2 * e + 1]};
-#pragma unroll
-            for (int r = 0; r < R; ++r) fp8x16_dot(w[r], x2, a2[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = a2[r][0] + a2[r][1];
-#pragma unroll
-        for (int r = 0; r <= R; ++r) acc[r] = wave_sum(acc[r]);
-        if (lane == 0) {
-#pragma unroll
-            for (int r = 0; r <= R; ++r) part[wave][r] = acc[r];
-        }
-        __syncthreads();
-        if (threadIdx.x < R && n0 + threadIdx.x < p.N) {
-            const int n = n0 + threadIdx.x;
-            float v = (part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]) * p.scale[n];
-            if (NORM) v *= rsqrtf((part[0][R] + part[1][R] + part[2][R] + part[3][R]) / (float)p.K + p.eps);
-            if (p.bias) v += to_f32(((const bf16*)p.bias)[n]);
-            if (p.res) v += to_f32(((const bf16*)p.res)[n]);
-            ((bf16*)p.y)[n] = from_f32<bf16>(v);
-        }
-        __syncthreads();
-    }
-}
-
 // per-row e4m3 quantisation: one workgroup per row, scale = max|w| / 448 (1 for an all-zero row), round-to-nearest-even
 __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16* w, int ld, uint8_t* q, float* scale, int cols) {
     __shared__ float red[4];
@@ -715,261 +590,6 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16* w, int 
         hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
         hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
         *(uint2*)(q + row * cols + (size_t)ci * 8) = make_uint2((unsigned)lo, (unsigned)hi);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ MXFP4 weight-only variants
-// Opt-in decode mode (svln_set_mxfp4_decode): the weights are OCP MXFP4 -- E2M1 elements on the grid {0, 0.5, 1, 1.5, 2, 3, 4, 6} with
-// the sign in bit 3, element 2j in the low nibble and 2j + 1 in the high nibble of byte j, and one E8M0 scale byte (2^(byte - 127)) per
-// block of 32 consecutive elements of a row: q4 [N][K/2] bytes, e8 [N][K/32] bytes, 4.25 bits per weight.  One 16-byte chunk is one
-// MX block.  Same structure as the e4m3 kernels; per chunk one scale byte is shifted into a float's exponent field and sixteen
-// v_cvt_scalef32_pk_f32_fp4 (one byte -> two scaled fp32 values each) feed v_pk_fma_f32 against 32 activations.  There is no per-row
-// scale: the block scale is applied by the conversion.
-SVLN_DEV float e8m0_to_f32(unsigned b) { return __uint_as_float(b << 23); }
-// acc (two partial sums) += one MX block (32 E2M1 weights, scale sc) . 32 activations; x2[k] = activations 2k, 2k + 1 of the block
-SVLN_DEV void fp4x32_dot(const uint4& w, float sc, const f32x2* x2, f32x2& acc) {
-    const unsigned d[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 0), x2[4 * q], acc);
-        acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 1), x2[4 * q + 1], acc);
-        acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 2), x2[4 * q + 2], acc);
-        acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 3), x2[4 * q + 3], acc);
-    }
-}
-// x (bf16 in global memory) -> LDS fp32 in eight 16-byte planes per 32-element block: element 32*cj + 4*p + e lives at
-// xs[p * nch4 * 4 + cj * 4 + e], so consecutive lanes read consecutive 16 B in every plane.
-SVLN_DEV float stage_x4(float* xs, const GemvArgs& p, int nch4) {
-    __shared__ float red4[GEMV_WAVES];
-    const bf16* x = (const bf16*)p.x;
-    const bf16* g = (const bf16*)p.norm_w;
-    const int tid = threadIdx.x, nch = p.K / 8;
-    float ss = 0.0f;
-    for (int ci = tid; ci < nch; ci += GEMV_THREADS) {
-        float f[8];
-        chunk_to_f32<bf16>(*(const uint4*)(x + (size_t)ci * 8), f);
-        if (g) {
-            float gf[8];
-            chunk_to_f32<bf16>(*(const uint4*)(g + (size_t)ci * 8), gf);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { ss = fmaf(f[e], f[e], ss); f[e] *= gf[e]; }
-        }
-        const int cj = ci >> 2, p0 = (ci & 3) * 2;
-        *(float4*)(xs + (size_t)p0 * nch4 * 4 + (size_t)cj * 4) = make_float4(f[0], f[1], f[2], f[3]);
-        *(float4*)(xs + (size_t)(p0 + 1) * nch4 * 4 + (size_t)cj * 4) = make_float4(f[4], f[5], f[6], f[7]);
-    }
-    if (g) {
-        ss = wave_sum(ss);
-        if ((tid & 63) == 0) red4[tid >> 6] = ss;
-    }
-    __syncthreads();
-    if (!g) return 1.0f;
-    float tot = 0.0f;
-#pragma unroll
-    for (int w = 0; w < GEMV_WAVES; ++w) tot += red4[w];
-    return rsqrtf(tot / (float)p.K + p.eps);     // applied in the epilogue: y = rstd * (Wq . (g * x))
-}
-SVLN_DEV void load_x4(const float* xs, int nch4, int cj, f32x2* x2) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const float4 v = *(const float4*)(xs + (size_t)q * nch4 * 4 + (size_t)cj * 4);
-        x2[2 * q] = f32x2{v.x, v.y};
-        x2[2 * q + 1] = f32x2{v.z, v.w};
-    }
-}
-// R dot products of MXFP4 rows (q4 bytes, e8 scale bytes) against the LDS copy of x; two blocks per row in flight
-template <int R>
-SVLN_DEV void dot4_rows(const uint8_t* const (&rows)[R], const uint8_t* const (&srow)[R], const float* xs, int nch4, int lane, float (&acc)[R]) {
-    f32x2 a2[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) a2[r] = f32x2{0.0f, 0.0f};
-    int ci = lane;
-    for (; ci + 64 < nch4; ci += 128) {
-        uint4 w0[R], w1[R];
-        unsigned s0[R], s1[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            w0[r] = load_nt(rows[r] + (size_t)ci * 16);
-            w1[r] = load_nt(rows[r] + (size_t)(ci + 64) * 16);
-            s0[r] = srow[r][ci];
-            s1[r] = srow[r][ci + 64];
-        }
-        f32x2 x0[16];
-        load_x4(xs, nch4, ci, x0);
-#pragma unroll
-        for (int r = 0; r < R; ++r) fp4x32_dot(w0[r], e8m0_to_f32(s0[r]), x0, a2[r]);
-        load_x4(xs, nch4, ci + 64, x0);
-#pragma unroll
-        for (int r = 0; r < R; ++r) fp4x32_dot(w1[r], e8m0_to_f32(s1[r]), x0, a2[r]);
-    }
-    for (; ci < nch4; ci += 64) {
-        uint4 w0[R];
-        unsigned s0[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) { w0[r] = load_nt(rows[r] + (size_t)ci * 16); s0[r] = srow[r][ci]; }
-        f32x2 x0[16];
-        load_x4(xs, nch4, ci, x0);
-#pragma unroll
-        for (int r = 0; r < R; ++r) fp4x32_dot(w0[r], e8m0_to_f32(s0[r]), x0, a2[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = wave_sum(a2[r][0] + a2[r][1]);
-}
-
-template <int EPI>
-__global__ __launch_bounds__(GEMV_THREADS) void gemv4_kernel(GemvArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* xs = (float*)smem_raw;
-    const int skip = p.skip ? *p.skip : 0;
-    constexpr int R = 4;
-    const int nch4 = p.K / 32;
-    const float xscale = stage_x4(xs, p, nch4);
-    if (skip) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int gw = blockIdx.x * GEMV_WAVES + wave, nw = gridDim.x * GEMV_WAVES;
-    const uint8_t* W = (const uint8_t*)p.w4;
-    const size_t ldq = (size_t)p.ldw / 2, lds = (size_t)p.ldw / 32;        // row strides of q4 / e8 in bytes
-    if (EPI == EPI_SWIGLU) {
-        const int n_out = p.N >> 1;
-        bf16* y = (bf16*)p.y;
-        for (int j0 = gw * 2; j0 < n_out; j0 += nw * 2) {
-            const uint8_t* rows[R];
-            const uint8_t* srow[R];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int j = min(j0 + u, n_out - 1);
-                const size_t gr = (size_t)(j >> 5) * 64 + (j & 31);
-                rows[2 * u] = W + gr * ldq;          srow[2 * u] = p.e8 + gr * lds;
-                rows[2 * u + 1] = W + (gr + 32) * ldq; srow[2 * u + 1] = p.e8 + (gr + 32) * lds;
-            }
-            float acc[R];
-            dot4_rows<R>(rows, srow, xs, nch4, lane, acc);
-            if (lane < 2 && j0 + lane < n_out) {
-                const float gt = (lane == 0 ? acc[0] : acc[2]) * xscale, up = (lane == 0 ? acc[1] : acc[3]) * xscale;
-                y[j0 + lane] = from_f32<bf16>(silu_f(gt) * up);
-            }
-        }
-        return;
-    }
-    float best = -INFINITY;
-    int best_i = 0x7FFFFFFF;
-    for (int n0 = gw * R; n0 < p.N; n0 += nw * R) {
-        const uint8_t* rows[R];
-        const uint8_t* srow[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const size_t n = (size_t)min(n0 + r, p.N - 1);
-            rows[r] = W + n * ldq; srow[r] = p.e8 + n * lds;
-        }
-        float acc[R];
-        dot4_rows<R>(rows, srow, xs, nch4, lane, acc);
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] *= xscale;
-        if (EPI == EPI_ARGMAX) {
-            if (p.pen_flags) {
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                    if (n0 + r < p.N && p.pen_flags[n0 + r]) acc[r] = acc[r] < 0.0f ? acc[r] * p.pen : acc[r] / p.pen;
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-                if (n0 + r < p.N && acc[r] > best) { best = acc[r]; best_i = n0 + r; }
-        } else if (lane < R && n0 + lane < p.N) {
-            const int n = n0 + lane;
-            float v = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
-            if (p.bias) v += to_f32(((const bf16*)p.bias)[n]);
-            if (p.res) v += to_f32(((const bf16*)p.res)[n]);
-            ((bf16*)p.y)[n] = from_f32<bf16>(v);
-        }
-    }
-    if (EPI == EPI_ARGMAX) {
-        __shared__ float bv[GEMV_WAVES];
-        __shared__ int bi[GEMV_WAVES];
-        if (lane == 0) { bv[wave] = best; bi[wave] = best_i; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float v = bv[0]; int i = bi[0];
-#pragma unroll
-            for (int w = 1; w < GEMV_WAVES; ++w)
-                if (bv[w] > v || (bv[w] == v && bi[w] < i)) { v = bv[w]; i = bi[w]; }
-            p.part_val[blockIdx.x] = v;
-            p.part_idx[blockIdx.x] = i;
-        }
-    }
-}
-
-// small-N MXFP4 variant, RMSNorm folded in without a prologue (as gemv8_ksplit_kernel).  A row of K = 3584 is only 112 blocks, fewer
-// than two waves' worth of lanes, so the split is a template parameter: KW of the workgroup's 4 waves split K and the 4 / KW groups of
-// KW waves take R rows each (KW = 2 for K <= 4096: 2 x R rows per workgroup; KW = 4 for the down projection's K = 18944).
-template <bool NORM, int R, int KW>
-__global__ __launch_bounds__(GEMV_THREADS) void gemv4_ksplit_kernel(GemvArgs p) {
-    constexpr int RG = GEMV_WAVES / KW;             // row groups per workgroup
-    __shared__ float part[GEMV_WAVES][R + 1];
-    if (p.skip && *p.skip) return;
-    const int nch4 = p.K / 32;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int kw = wave % KW, rg = wave / KW;
-    const uint8_t* W = (const uint8_t*)p.w4;
-    const size_t ldq = (size_t)p.ldw / 2, lds = (size_t)p.ldw / 32;
-    const bf16* xg = (const bf16*)p.x;
-    const bf16* gg = (const bf16*)p.norm_w;
-    for (int b0 = blockIdx.x * RG * R; b0 < p.N; b0 += gridDim.x * RG * R) {
-        const int n0 = b0 + rg * R;                 // (may lie beyond N for the last workgroup: rows clamp, nothing is written)
-        const uint8_t* rows[R];
-        const uint8_t* srow[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const size_t n = (size_t)min(n0 + r, p.N - 1);
-            rows[r] = W + n * ldq; srow[r] = p.e8 + n * lds;
-        }
-        float ss = 0.0f;
-        f32x2 a2[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) a2[r] = f32x2{0.0f, 0.0f};
-        for (int ci = kw * 64 + lane; ci < nch4; ci += 64 * KW) {
-            uint4 w[R];
-            unsigned sb[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r) { w[r] = load_nt(rows[r] + (size_t)ci * 16); sb[r] = srow[r][ci]; }
-            f32x2 x2[16];
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                float xf[8];
-                chunk_to_f32<bf16>(*(const uint4*)(xg + (size_t)ci * 32 + h * 8), xf);
-                if (NORM) {
-                    float gf[8];
-                    chunk_to_f32<bf16>(*(const uint4*)(gg + (size_t)ci * 32 + h * 8), gf);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { ss = fmaf(xf[e], xf[e], ss); xf[e] *= gf[e]; }
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) x2[4 * h + e] = f32x2{xf[2 * e], xf[2 * e + 1]};
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) fp4x32_dot(w[r], e8m0_to_f32(sb[r]), x2, a2[r]);
-        }
-        float acc[R + 1];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = wave_sum(a2[r][0] + a2[r][1]);
-        acc[R] = NORM ? wave_sum(ss) : 0.0f;
-        if (lane == 0) {
-#pragma unroll
-            for (int r = 0; r <= R; ++r) part[wave][r] = acc[r];
-        }
-        __syncthreads();
-        if (threadIdx.x < RG * R) {
-            const int g2 = threadIdx.x / R, r = threadIdx.x % R, n = b0 + g2 * R + r;
-            if (n < p.N) {
-                float v = 0.0f, s2 = 0.0f;
-#pragma unroll
-                for (int k = 0; k < KW; ++k) { v += part[g2 * KW + k][r]; s2 += part[g2 * KW + k][R]; }
-                if (NORM) v *= rsqrtf(s2 / (float)p.K + p.eps);
-                if (p.bias) v += to_f32(((const bf16*)p.bias)[n]);
-                if (p.res) v += to_f32(((const bf16*)p.res)[n]);
-                ((bf16*)p.y)[n] = from_f32<bf16>(v);
-            }
-        }
-        __syncthreads();
     }
 }
 
@@ -1084,72 +704,36 @@ template <typename T> void launch_gemv(hipStream_t s, const GemvArgs& a) { launc
         if (start || stop) hipExtLaunchKernelGGL(kern, grid, block, lds, s, start, stop, 0, a);   \
         else hipLaunchKernelGGL(kern, grid, block, lds, s, a);                                    \
     } while (0)
-template <typename T> void launch_gemv_timed(hipStream_t s, const GemvArgs& a, hipEvent_t start, hipEvent_t stop) {
-    dim3 b(GEMV_THREADS);
-    if (a.w4) {                                   // MXFP4 weights (bf16 engine only; the engine refuses to enable it otherwise)
-        if (a.epi == EPI_NONE && a.N <= 8192) {
-            constexpr int R = 4;
-            const bool wide = a.K > 4096;         // K / 32 blocks per row: more than 128 -> all four waves split K
-            const int per_wg = wide ? R : 2 * R;
-            int grid = (a.N + per_wg - 1) / per_wg;
-            if (grid > 2048) grid = 2048;
-            if (wide) {
-                if (a.norm_w) SVLN_LAUNCH((gemv4_ksplit_kernel<true, R, 4>), dim3(grid), b, 0);
-                else SVLN_LAUNCH((gemv4_ksplit_kernel<false, R, 4>), dim3(grid), b, 0);
-            } else {
-                if (a.norm_w) SVLN_LAUNCH((gemv4_ksplit_kernel<true, R, 2>), dim3(grid), b, 0);
-                else SVLN_LAUNCH((gemv4_ksplit_kernel<false, R, 2>), dim3(grid), b, 0);
-            }
-            return;
-        }
-        const size_t lds4 = (size_t)a.K * sizeof(float);
-        dim3 g4(gemv_grid(a.N));
-        switch (a.epi) {
-            case EPI_NONE: SVLN_LAUNCH((gemv4_kernel<EPI_NONE>), g4, b, lds4); break;
-            case EPI_SWIGLU: SVLN_LAUNCH((gemv4_kernel<EPI_SWIGLU>), g4, b, lds4); break;
-            case EPI_ARGMAX: SVLN_LAUNCH((gemv4_kernel<EPI_ARGMAX>), g4, b, lds4); break;
-            default: break;
-        }
-        return;
-    }
-    if (a.w8) {                                   // fp8 weights (bf16 engine only; the engine refuses to enable it otherwise)
-        if (a.epi == EPI_NONE && a.N <= 8192) {
-            constexpr int R = 4;
-            int grid = (a.N + R - 1) / R;
-            if (grid > 2048) grid = 2048;
-            if (a.norm_w) SVLN_LAUNCH((gemv8_ksplit_kernel<true, R>), dim3(grid), b, 0);
-            else SVLN_LAUNCH((gemv8_ksplit_kernel<false, R>), dim3(grid), b, 0);
-            return;
-        }
-        const size_t lds8 = (size_t)a.K * sizeof(float);
-        dim3 g8(gemv_grid(a.N));
-        switch (a.epi) {
-            case EPI_NONE: SVLN_LAUNCH((gemv8_kernel<EPI_NONE>), g8, b, lds8); break;
-            case EPI_SWIGLU: SVLN_LAUNCH((gemv8_kernel<EPI_SWIGLU>), g8, b, lds8); break;
-            case EPI_ARGMAX: SVLN_LAUNCH((gemv8_kernel<EPI_ARGMAX>), g8, b, lds8); break;
-            default: break;
-        }
-        return;
-    }
+template <typename P, int KW> static void launch_ksplit(hipStream_t s, const GemvArgs& a, hipEvent_t start, hipEvent_t stop) {
+    const int per_wg = P::KS_R * (GEMV_WAVES / KW);
+    int grid = (a.N + per_wg - 1) / per_wg;
+    if (grid > 2048) grid = 2048;
+    if (a.norm_w) SVLN_LAUNCH((gemv_ksplit_kernel<P, true, KW>), dim3(grid), dim3(GEMV_THREADS), 0);
+    else SVLN_LAUNCH((gemv_ksplit_kernel<P, false, KW>), dim3(grid), dim3(GEMV_THREADS), 0);
+}
+template <typename P> static void launch_gemv_fmt(hipStream_t s, const GemvArgs& a, hipEvent_t start, hipEvent_t stop) {
     if (a.epi == EPI_NONE && a.N <= 8192) {
-        constexpr int R = 2;                       // rows per workgroup (R = 4 / 8 measured slower at N <= 8192)
-        int grid = (a.N + R - 1) / R;
-        if (grid > 2048) grid = 2048;
-        if (a.norm_w) SVLN_LAUNCH((gemv_ksplit_kernel<T, true, R>), dim3(grid), b, 0);
-        else SVLN_LAUNCH((gemv_ksplit_kernel<T, false, R>), dim3(grid), b, 0);
+        // a row of more than 128 chunks (K > 4096 for MXFP4, the only format that asks) gives all four waves a share of K
+        if (a.K > 4096) launch_ksplit<P, GEMV_WAVES>(s, a, start, stop);
+        else launch_ksplit<P, P::KS_KW_NARROW>(s, a, start, stop);
         return;
     }
-    const int grid = gemv_grid(a.N);
     const size_t lds = (size_t)a.K * sizeof(float);
-    dim3 g(grid);
+    dim3 g(gemv_grid(a.N)), b(GEMV_THREADS);
     switch (a.epi) {
-        case EPI_NONE: SVLN_LAUNCH((gemv_kernel<T, EPI_NONE>), g, b, lds); break;
-        case EPI_SWIGLU: SVLN_LAUNCH((gemv_kernel<T, EPI_SWIGLU>), g, b, lds); break;
-        case EPI_ARGMAX: SVLN_LAUNCH((gemv_kernel<T, EPI_ARGMAX>), g, b, lds); break;
+        case EPI_NONE: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_NONE>), g, b, lds); break;
+        case EPI_SWIGLU: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SWIGLU>), g, b, lds); break;
+        case EPI_ARGMAX: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX>), g, b, lds); break;
         default: break;
     }
 }
 #undef SVLN_LAUNCH
+template <typename T> void launch_gemv_timed(hipStream_t s, const GemvArgs& a, hipEvent_t start, hipEvent_t stop) {
+    // (MXFP4 / e4m3 weights: bf16 engine only; the engine refuses to enable them otherwise)
+    if (a.w4) launch_gemv_fmt<WMxfp4>(s, a, start, stop);
+    else if (a.w8) launch_gemv_fmt<WE4m3>(s, a, start, stop);
+    else launch_gemv_fmt<WPlain<T>>(s, a, start, stop);
+}
 int gemv_batched_grid(int N, int epi, int B) {
     const int R = 4;
     (void)B;
@@ -1182,25 +766,20 @@ void launch_argmax_final_batched(hipStream_t s, const float* pv, const int* pi, 
 }
 template void launch_gemv_timed<bf16>(hipStream_t, const GemvArgs&, hipEvent_t, hipEvent_t);
 template void launch_gemv_timed<float>(hipStream_t, const GemvArgs&, hipEvent_t, hipEvent_t);
-template <typename T, int EPI> static void gemv_attr() {
-    set_max_lds((const void*)gemv_kernel<T, EPI>, 160 * 1024 - 256);
-}
 void launch_quant_fp8_rows(hipStream_t s, const void* w_bf16, int ld, void* w8, float* scale, int64_t rows, int cols) {
     hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, (const bf16*)w_bf16, ld, (uint8_t*)w8, scale, cols);
 }
 void launch_quant_mxfp4_rows(hipStream_t s, const void* w_bf16, int ld, void* q4, uint8_t* e8, int64_t rows, int cols) {
     hipLaunchKernelGGL(quant_mxfp4_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, (const bf16*)w_bf16, ld, (uint8_t*)q4, e8, cols);
 }
+// (every kernel that may ask for more than 64 KiB of dynamic LDS goes through set_max_lds: a refusal is reported at engine creation)
+template <typename P> static void gemv_rows_attrs() {
+    set_max_lds((const void*)gemv_rows_kernel<P, EPI_NONE>, 160 * 1024 - 256);
+    set_max_lds((const void*)gemv_rows_kernel<P, EPI_SWIGLU>, 160 * 1024 - 256);
+    set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX>, 160 * 1024 - 256);
+}
 void gemv_init_attrs() {
-    // (every kernel that may ask for more than 64 KiB of dynamic LDS goes through set_max_lds: a refusal is reported at engine creation)
-    set_max_lds((const void*)gemv4_kernel<EPI_NONE>, 160 * 1024 - 256);
-    set_max_lds((const void*)gemv4_kernel<EPI_SWIGLU>, 160 * 1024 - 256);
-    set_max_lds((const void*)gemv4_kernel<EPI_ARGMAX>, 160 * 1024 - 256);
-    set_max_lds((const void*)gemv8_kernel<EPI_NONE>, 160 * 1024 - 256);
-    set_max_lds((const void*)gemv8_kernel<EPI_SWIGLU>, 160 * 1024 - 256);
-    set_max_lds((const void*)gemv8_kernel<EPI_ARGMAX>, 160 * 1024 - 256);
-    gemv_attr<bf16, EPI_NONE>(); gemv_attr<bf16, EPI_SWIGLU>(); gemv_attr<bf16, EPI_ARGMAX>();
-    gemv_attr<float, EPI_NONE>(); gemv_attr<float, EPI_SWIGLU>(); gemv_attr<float, EPI_ARGMAX>();
+    gemv_rows_attrs<WMxfp4>(); gemv_rows_attrs<WE4m3>(); gemv_rows_attrs<WPlain<bf16>>(); gemv_rows_attrs<WPlain<float>>();
 }
 template void launch_gemv<bf16>(hipStream_t, const GemvArgs&);
 template void launch_gemv<float>(hipStream_t, const GemvArgs&);

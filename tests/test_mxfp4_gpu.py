@@ -212,7 +212,7 @@ def _compare(what, cfg, eng, emu, bound):
 
 
 def test_repetition_penalty_rides_on_the_mxfp4_lm_head():
-    """tiny_penalty (generation_config.repetition_penalty = 1.3) with the mode on: the penalty flags are applied inside gemv4_kernel's
+    """tiny_penalty (generation_config.repetition_penalty = 1.3) with the mode on: the penalty flags are applied inside gemv_rows_kernel<WMxfp4, EPI_ARGMAX>'s
     arg-max epilogue; against Mxfp4Emu with the same knob, teacher-forced."""
     sc = SCENARIOS["tiny_penalty"]
     cfg = sc["cfg"]

@@ -84,6 +84,29 @@ def main():
             for i in range(reps):
                 W = Ws[i % nw]
                 _lib.check(lib.svln_op_gemv(h, ptr(W), K, ptr(x), ptr(g), 1e-6, None, None, ptr(y), N, K, epi, C.byref(tok)))
+    elif what == "gemv8":
+        # the decode shapes over e4m3 weights with per-row scales (svln_set_fp8_decode)
+        import ctypes as C
+        for (N, K, norm, epi) in [(37888, 3584, True, _lib.EPI_SWIGLU), (4608, 3584, True, 0), (3584, 3584, False, 0),
+                                  (3584, 18944, False, 0), (152064, 3584, False, _lib.EPI_ARGMAX)]:
+            nw = 1 if os.environ.get("KBENCH_HOT") else max(1, min(8, -(-768 * 2**20 // (N * K))))
+            Ws = []
+            for _ in range(nw):
+                W = ((torch.rand(N, K, device="cuda") - 0.5) * 0.05).to(dt)
+                w8 = torch.zeros(N, K, dtype=torch.uint8, device="cuda")
+                sc = torch.zeros(N, dtype=torch.float32, device="cuda")
+                torch.cuda.synchronize()
+                _lib.check(lib.svln_op_quant_fp8(h, ptr(W), N, K, ptr(w8), ptr(sc)))
+                Ws.append((w8, sc))
+                del W
+            x = (torch.rand(K, device="cuda") - 0.5).to(dt)
+            g = torch.ones(K, device="cuda", dtype=dt) if norm else None
+            y = torch.zeros(N, device="cuda", dtype=dt)
+            tok = C.c_int32()
+            torch.cuda.synchronize()
+            for i in range(reps):
+                w8, sc = Ws[i % nw]
+                _lib.check(lib.svln_op_gemv_fp8(h, ptr(w8), ptr(sc), K, ptr(x), ptr(g), 1e-6, None, None, ptr(y), N, K, epi, C.byref(tok)))
     elif what == "gemv4":
         # the decode shapes over MXFP4 weights (svln_set_mxfp4_decode): q|k|v, o, gate/up SwiGLU, down, lm_head arg-max
         import ctypes as C

@@ -20,18 +20,18 @@ for C in FETCH_SIZE WRITE_SIZE; do
   echo "== pmc $C"
   rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_$C -- python3 tools/kbench.py gemv 5 > $OUT/pmc_$C.log 2>&1
   F=$(ls $OUT/pmc_$C/*/*counter_collection.csv | head -1)
-  head -1 $F > $OUT/${R}_gemv_pmc_$C.csv; grep "gemv_kernel" $F >> $OUT/${R}_gemv_pmc_$C.csv
+  head -1 $F > $OUT/${R}_gemv_pmc_$C.csv; grep "gemv_rows_kernel" $F >> $OUT/${R}_gemv_pmc_$C.csv
   rm -rf $OUT/pmc_$C
 done
 python3 - <<PY
 import csv, json, os
 R, OUT = "$R", "$OUT"
 def mean(c):
-    rows = [r for r in csv.DictReader(open(f"{OUT}/{R}_gemv_pmc_{c}.csv")) if "Li3E" in r["Kernel_Name"] and r["Grid_Size"] == str(1184 * 256)]
+    rows = [r for r in csv.DictReader(open(f"{OUT}/{R}_gemv_pmc_{c}.csv")) if "WPlainIDF16bEELi3E" in r["Kernel_Name"] and r["Grid_Size"] == str(1184 * 256)]
     return sum(float(r["Counter_Value"]) for r in rows) / max(len(rows), 1), len(rows)
 f, nf = mean("FETCH_SIZE"); w, nw = mean("WRITE_SIZE")
 alg = 2 * 18944 * 3584 * 2
-d = {"kernel": "gemv_kernel<bf16, EPI_SWIGLU> N=37888 K=3584 (decode gate/up projection)",
+d = {"kernel": "gemv_rows_kernel<WPlain<bf16>, EPI_SWIGLU> N=37888 K=3584 (decode gate/up projection)",
      "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE (separate passes) -- python tools/kbench.py gemv 5",
      "launches": [nf, nw], "FETCH_SIZE_KB_per_launch": f, "WRITE_SIZE_KB_per_launch": w,
      "correction": "gfx950: FETCH_SIZE reports exactly half of a wide coalesced 16 B/lane stream (MI355X_MICROARCH.md, HBM) -> x2; WRITE_SIZE exact",

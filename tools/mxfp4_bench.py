@@ -10,7 +10,7 @@ episode on the SAME prompt stream as the bf16 pass (the prompt encoder is reset 
 saw identical inputs.
 
 --ref-lib: the library of ANOTHER build of the engine (tools/build_ref_lib.sh <commit>), so that the code under test is not its own
-yardstick: its bf16 and e4m3 passes run in a child process of their own, alternating with this build's passes `--rounds` times.  The
+yardstick: its passes (--ref-passes, default bf16,fp8: the parent of the MXFP4 change had no third mode) run in a child process of their own, alternating with this build's passes `--rounds` times.  The
 parent process never opens the GPU; every child runs under its own time limit, and nothing is started after a child that failed.
 Prints ONE JSON line (committed as profiles/mxfp4_decode.json).
 """
@@ -128,6 +128,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--child-timeout", type=int, default=280)
     ap.add_argument("--passes", default="bf16,fp8,mxfp4")
+    ap.add_argument("--ref-passes", default="bf16,fp8", help="passes of the --ref-lib build (a build older than the MXFP4 mode has only bf16,fp8)")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--box", default=None, help="free text naming the box the run was made on")
     a = ap.parse_args()
@@ -138,7 +139,7 @@ def main():
     for _ in range(a.rounds):
         rnd = {}
         if a.ref_lib:
-            rnd["parent_build"] = spawn(a, a.ref_lib, "bf16,fp8")
+            rnd["parent_build"] = spawn(a, a.ref_lib, a.ref_passes)
         rnd["this_build"] = spawn(a, None, a.passes)
         out["rounds"].append(rnd)
 

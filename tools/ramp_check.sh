@@ -14,7 +14,7 @@ for turn in (6, 7, 9):
     seg = rows[idx[turn]:idx[turn + 1]]
     q = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in seg if "gemm_glds" in r["Kernel_Name"] and r["Grid_Size_X"] == str(162 * 256)]
     print("turn", turn, "ViT qkv GEMM per layer:", " ".join(f"{x:.1f}" for x in q))
-    g = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in seg if "gemv_kernel" in r["Kernel_Name"] and "Li3E" in r["Kernel_Name"]]
+    g = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in seg if "gemv_rows_kernel" in r["Kernel_Name"] and "WPlainIDF16bEELi3E" in r["Kernel_Name"]]
     print("   decode gate/up GEMV first 12:", " ".join(f"{x:.1f}" for x in g[:12]), " last 4:", " ".join(f"{x:.1f}" for x in g[-4:]))
     p = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in seg if "Li256ELi128" in r["Kernel_Name"] and r["Grid_Size_X"] == str(256 * 512)]
     print("   prefill gate/up main:", " ".join(f"{x:.1f}" for x in p))
