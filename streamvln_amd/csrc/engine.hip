@@ -1819,6 +1819,16 @@ public:
     void op_gemv(GemvArgs a, int32_t* host_token) override {
         REQUIRE(a.w8 == nullptr || sizeof(T) == 2, "fp8 weights need the bf16 engine");
         REQUIRE(a.w4 == nullptr || sizeof(T) == 2, "MXFP4 weights need the bf16 engine");
+        // refusals before launch, the same for every weight format: `chunk` = weights per 16-byte load of the format
+        const int chunk = a.w4 ? 32 : a.w8 ? 16 : Elt<T>::PER_CHUNK;
+        REQUIRE(a.x && (a.w4 ? a.e8 != nullptr : a.w8 ? a.scale != nullptr : a.W != nullptr), "null pointer");
+        REQUIRE(a.N >= 1 && a.K >= chunk && a.K % chunk == 0, "N >= 1, K a positive multiple of the format's 16-byte chunk");
+        REQUIRE(a.ldw >= a.K && a.ldw % chunk == 0, "ldw >= K, a multiple of the format's 16-byte chunk (aligned row loads)");
+        REQUIRE(a.epi == EPI_NONE || a.epi == EPI_SWIGLU || a.epi == EPI_ARGMAX, "epilogue: EPI_NONE, EPI_SWIGLU or EPI_ARGMAX");
+        REQUIRE(a.epi != EPI_SWIGLU || a.N % 64 == 0, "SwiGLU needs N % 64 == 0 (32-row gate / up blocks)");
+        REQUIRE(a.epi == EPI_ARGMAX || a.y, "null output pointer");
+        REQUIRE((a.epi == EPI_NONE && a.N <= 8192) || (size_t)a.K * sizeof(float) <= (size_t)GEMV_ROWS_MAX_LDS,
+                "the wave-per-rows kernel stages K fp32 activations in LDS: K too large");
         a.part_val = part_val; a.part_idx = part_idx;
         launch_gemv<T>(st, a);
         if (a.epi == EPI_ARGMAX) {

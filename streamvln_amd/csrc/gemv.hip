@@ -774,9 +774,9 @@ void launch_quant_mxfp4_rows(hipStream_t s, const void* w_bf16, int ld, void* q4
 }
 // (every kernel that may ask for more than 64 KiB of dynamic LDS goes through set_max_lds: a refusal is reported at engine creation)
 template <typename P> static void gemv_rows_attrs() {
-    set_max_lds((const void*)gemv_rows_kernel<P, EPI_NONE>, 160 * 1024 - 256);
-    set_max_lds((const void*)gemv_rows_kernel<P, EPI_SWIGLU>, 160 * 1024 - 256);
-    set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX>, 160 * 1024 - 256);
+    set_max_lds((const void*)gemv_rows_kernel<P, EPI_NONE>, GEMV_ROWS_MAX_LDS);
+    set_max_lds((const void*)gemv_rows_kernel<P, EPI_SWIGLU>, GEMV_ROWS_MAX_LDS);
+    set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX>, GEMV_ROWS_MAX_LDS);
 }
 void gemv_init_attrs() {
     gemv_rows_attrs<WMxfp4>(); gemv_rows_attrs<WE4m3>(); gemv_rows_attrs<WPlain<bf16>>(); gemv_rows_attrs<WPlain<float>>();

@@ -95,6 +95,7 @@ void launch_quant_fp8_rows(hipStream_t s, const void* w_bf16, int ld, void* w8, 
 void launch_quant_mxfp4_rows(hipStream_t s, const void* w_bf16, int ld, void* q4, uint8_t* e8, int64_t rows, int cols);
 template <typename T> void launch_gemv_timed(hipStream_t s, const GemvArgs& a, hipEvent_t start, hipEvent_t stop);   // events get the kernel's own begin/end
 int gemv_grid(int N);                       // workgroups launch_gemv uses for N rows
+constexpr int GEMV_ROWS_MAX_LDS = 160 * 1024 - 256;    // dynamic LDS the wave-per-rows kernel may ask for (K fp32 activations): N > 8192 or an epilogue
 
 // B (1, 2, 4 or 8) activation vectors against one weight stream: x [B][ldx], y [B][ldy], res [B][ldr].
 // EPI_ARGMAX: part_val / part_idx are [B][gemv_batched_grid(N, epi, B)]; launch_argmax_final_batched reduces them to B tokens.
