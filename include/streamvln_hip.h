@@ -174,20 +174,34 @@ int svln_set_decode_persistent(svln_engine* h, int enable);
 int svln_probe_decode_layer(svln_engine* h, int layer, unsigned long long* out, int max_wgs, int32_t* n_wgs);
 /* Opt-in, no reference counterpart: the single-env decode step and the lm_head stream OCP e4m3 copies of the LLM
  * weights (one fp32 scale per output row, quantised on the device from the loaded tensors at the first enable) instead of the bf16
- * ones -- half the HBM bytes per generated token.  bf16 engines only; prefill, vision and svln_generate_batch keep bf16 weights. */
+ * ones -- half the HBM bytes per generated token.  bf16 engines only; prefill, vision and svln_generate_batch keep bf16 weights (the
+ * batched paths have svln_set_fp8_gemm and svln_set_mxfp4_batched).  Refused while svln_set_mxfp4_batched is on. */
 int svln_set_fp8_decode(svln_engine* h, int enable);
 /* Opt-in, no reference counterpart: the single-env decode step's four projections and every lm_head product (the
  * prefill's token included) stream OCP MXFP4 copies of the LLM weights instead of the bf16 ones -- E2M1 elements, one E8M0 power-of-two
  * scale per 32 consecutive elements of a row, 4.25 bits per weight, quantised on the device from the loaded tensors at the first enable
  * (~4.0 GB beside the bf16 copy at the 7B size).  Numeric scheme: svln_op_quant_mxfp4.  bf16 engines only; hidden, intermediate and
- * q_heads * 128 must be multiples of 32.  Prefill, vision, attention, norms, svln_generate_batch and the scheduler keep bf16 weights.
- * Mutually exclusive with svln_set_fp8_decode: enabling one while the other is on fails.  Captured decode graphs are dropped when the
+ * q_heads * 128 must be multiples of 32.  Prefill, vision, attention and norms keep bf16 weights; svln_generate_batch and the scheduler
+ * keep them too unless svln_set_mxfp4_batched (below) is on.  Mutually exclusive with svln_set_fp8_decode: enabling one while the other
+ * is on fails.  Captured decode graphs are dropped when the
  * mode changes; while it is on the launched GEMVs are kept (svln_set_decode_persistent has no effect). */
 int svln_set_mxfp4_decode(svln_engine* h, int enable);
+/* Opt-in, no reference counterpart: the same MXFP4 weight copies for the envs that svln_generate_batch / svln_batch_step carry.  While it
+ * is on, the batched decode step runs q|k|v, o_proj, gate/up and down_proj at every batch size (1, 2, 4, 8) on a weight-only MFMA kernel
+ * (bf16 activations x exactly dequantised weights, fp32 accumulate: svln_op_gemv_mxfp4_batched), and every lm_head product of the
+ * scheduler -- the token that follows a prefill included -- reads the MXFP4 lm_head.  Prefill rows keep the bf16 products; a scheduler
+ * iteration that holds decode rows and prefill rows runs the decode rows as a batched decode step of their own, then the prefill
+ * segments as a bf16 pass, so every env is computed by the scheme of svln_set_mxfp4_decode (prefill bf16, decode projections and
+ * lm_head MXFP4) whatever its neighbours do.  bf16 engines only.  Independent of svln_set_mxfp4_decode (either or both may be on);
+ * mutually exclusive with svln_set_fp8_decode and svln_set_fp8_gemm: enabling it while one of them is on fails, and they fail while it
+ * is on.  A call that would change the mode (on -> off as well as off -> on) fails while scheduler turns are in flight; a call that changes
+ * nothing always succeeds.  Captured batched decode graphs are dropped when it changes. */
+int svln_set_mxfp4_batched(svln_engine* h, int enable);
 /* Opt-in, no reference counterpart (BASELINE configs[4] "fp8 MFMA on QKV/MLP GEMMs"): the LLM's dense products with more
  * than one row -- prefill, and the decode steps of >= 4 envs batched by svln_generate_batch / svln_batch_step -- run as e4m3 x e4m3 MFMA
  * products (fp32 accumulate, bf16 out) on the e4m3 weight copies above with per-row activation scales computed on the fly.  bf16 engines
- * only; vision, attention, norms, lm_head and the batch-1 decode GEMVs are unaffected (the latter have svln_set_fp8_decode). */
+ * only; vision, attention, norms, lm_head and the batch-1 decode GEMVs are unaffected (the latter have svln_set_fp8_decode).  Refused
+ * while svln_set_mxfp4_batched is on. */
 int svln_set_fp8_gemm(svln_engine* h, int enable);
 /* Opt-in slow-memory pruning (BASELINE configs[3]; the reference has NO counterpart -- its memory is all num_history x 196 pooled
  * tokens, streamvln_eval.py:313-321 -- so this is pinned only by the project's own CPU restatement, oracle: prune_memory_tokens):
@@ -257,6 +271,20 @@ int svln_op_gemv_fp8(svln_engine* h, const void* w8, const float* scale, int ldw
 int svln_op_quant_mxfp4(svln_engine* h, const void* w_bf16, int64_t rows, int cols, void* q4, void* e8);
 int svln_op_gemv_mxfp4(svln_engine* h, const void* q4, const void* e8, int ldw, const void* x, const void* norm_w, float eps, const void* bias,
                        const void* res, void* y, int N, int K, int epi, int32_t* host_token);
+/* the product behind svln_set_mxfp4_batched: B (1 .. 8) bf16 activation vectors x [B][ldx] against one MXFP4 weight stream (q4 / e8 / ldw
+ * as svln_op_gemv_mxfp4: the layout is shared), Y[b][n] = epi(Wq[n] . x[b] + bias[n]) + res[b][n] with y [B][ldy], res [B][ldr]; epi =
+ * EPI_NONE, EPI_SWIGLU (y has N / 2 columns) or EPI_ARGMAX (no y: one token per vector to host_tokens[B], lowest index on ties, -1 for a
+ * row without a finite logit).  No fused RMSNorm.  Precondition (not checked): q4 and x are 16-byte aligned base pointers (the
+ * kernel loads 16-byte runs of both; with ldw % 32 == 0 and ldx % 8 == 0 every row then is).  Refused before any launch: an fp32 engine, null operands, B outside 1 .. 8, N < 1, K or
+ * ldw not a positive multiple of 32, ldw < K, ldx < K or not a multiple of 8, SwiGLU with N % 64 != 0. */
+int svln_op_gemv_mxfp4_batched(svln_engine* h, const void* q4, const void* e8, int ldw, const void* x, int ldx, const void* bias, const void* res,
+                               int ldr, void* y, int ldy, int N, int K, int epi, int B, int32_t* host_tokens);
+/* TEST-ONLY entry, not part of the product surface: the EPI_ARGMAX form above with the repetition penalty of svln_set_repetition_penalty
+ * as the scheduler applies it (the flags are otherwise the engine's own, so no caller needs this): pen_flags [rows][N] bytes and
+ * pen_rows [B] (device) -- vector b uses flag row pen_rows[b]; a flagged
+ * logit becomes v < 0 ? v * penalty : v / penalty before the arg-max.  Same refusals; penalty must be > 0. */
+int svln_op_gemv_mxfp4_batched_argmax_pen(svln_engine* h, const void* q4, const void* e8, int ldw, const void* x, int ldx, int N, int K, int B,
+                                          const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens);
 int svln_op_rmsnorm(svln_engine* h, const void* x, const void* g, void* y, int rows, int n, float eps);
 int svln_op_layernorm(svln_engine* h, const void* x, const void* g, const void* b, void* y, int rows, int n, float eps);
 /* attention over caller-provided q [T][q_stride] and k/v [S][kv_stride] (engine packs them into pages):

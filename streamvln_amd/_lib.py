@@ -87,6 +87,7 @@ SIGNATURES = {
     "svln_set_fp8_decode": (_I, [_P, _I]),
     "svln_set_fp8_gemm": (_I, [_P, _I]),
     "svln_set_mxfp4_decode": (_I, [_P, _I]),
+    "svln_set_mxfp4_batched": (_I, [_P, _I]),
     "svln_set_memory_prune": (_I, [_P, _I]),
     "svln_op_memory_prune": (_I, [_P, _P, _I, _I, _PI32, _PF]),
     "svln_probe_reset": (_I, [_P]),
@@ -105,6 +106,8 @@ SIGNATURES = {
     "svln_op_gemv_fp8": (_I, [_P, _P, _P, _I, _P, _P, _F, _P, _P, _P, _I, _I, _I, _PI32]),
     "svln_op_quant_mxfp4": (_I, [_P, _P, _I64, _I, _P, _P]),
     "svln_op_gemv_mxfp4": (_I, [_P, _P, _P, _I, _P, _P, _F, _P, _P, _P, _I, _I, _I, _PI32]),
+    "svln_op_gemv_mxfp4_batched": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _PI32]),
+    "svln_op_gemv_mxfp4_batched_argmax_pen": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _PI32]),
     "svln_op_rmsnorm": (_I, [_P, _P, _P, _P, _I, _I, _F]),
     "svln_op_layernorm": (_I, [_P, _P, _P, _P, _P, _I, _I, _F]),
     "svln_op_attention_llm": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I]),

@@ -104,6 +104,7 @@ struct EngineBase {
     virtual void set_fp8_decode(int enable) = 0;
     virtual void set_fp8_gemm(int enable) = 0;
     virtual void set_mxfp4_decode(int enable) = 0;
+    virtual void set_mxfp4_batched(int enable) = 0;
     virtual bool op_gemm_fp8(const GemmArgs& a) = 0;
     virtual void set_memory_prune(int keep) = 0;
     virtual void op_memory_prune(const void* m, int n_rows, int keep, int32_t* out_idx, float* out_score) = 0;
@@ -116,6 +117,7 @@ struct EngineBase {
     virtual bool op_gemm(const GemmArgs& a) = 0;
     virtual void op_gemv(GemvArgs a, int32_t* host_token) = 0;
     virtual void op_gemv_batched(GemvBatchArgs a, int32_t* host_tokens) = 0;
+    virtual void op_gemv_mxfp4_batched(GemvMx4BatchArgs a, int32_t* host_tokens) = 0;
     virtual void op_quant_fp8(const void* w, int64_t rows, int cols, void* w8, float* scale) = 0;
     virtual void op_quant_mxfp4(const void* w, int64_t rows, int cols, void* q4, uint8_t* e8) = 0;
     virtual void op_rmsnorm(const void* x, const void* g, void* y, int rows, int n, float eps) = 0;
@@ -156,6 +158,7 @@ public:
     struct LLayer { T *in_norm, *qkv_w, *qkv_b, *o_w, *post_norm, *gu_w, *down_w, *kpool, *vpool; Q8 qkv8, o8, gu8, down8; Q4 qkv4, o4, gu4, down4; };
     Q8 lm_head8; bool fp8_on = false, fp8_built = false;
     Q4 lm_head4; bool mx4_on = false, mx4_built = false;
+    bool mx4b_on = false;            // opt-in MXFP4 weights in the batched (multi-env) decode step and the scheduler's lm_head: svln_set_mxfp4_batched
     bool fp8_gemm_on = false; uint8_t* act8 = nullptr; float* act8_scale = nullptr;      // opt-in fp8 MFMA products: quantised activation rows
     T *patch_w, *patch_b, *pos_emb, *proj0_w, *proj0_b, *proj2_w, *proj2_b, *embed, *final_norm, *lm_head;
     std::vector<VLayer> vl;
@@ -201,7 +204,7 @@ public:
     bool use_graph = false;
     struct GraphSet { std::unordered_map<int, hipGraphExec_t> ex; };     // key: steps (whole batch) | 1000 (head of a probed step) | 2000 + steps (its tail)
     std::vector<GraphSet> graphs;
-    std::unordered_map<int, hipGraphExec_t> bgraphs;          // batched decode step: key = B | penalty << 8 | fp8 gemm << 9
+    std::unordered_map<int, hipGraphExec_t> bgraphs;          // batched decode step: key = B | penalty << 8 | fp8 gemm << 9 | MXFP4 batched << 10
     // per-turn truncation of the spliced rows (the reference's config.tokenizer_model_max_length, stream_video_vln.py:241-244); 0 = none
     int turn_row_limit = 0;
     // HF repetition penalty of the checkpoint's generation_config (1 = off): flags of the tokens generated in the current turn
@@ -1179,13 +1182,44 @@ public:
     }
     void head_batched(const T* rows, int B, bool pen = false) {
         launch_rmsnorm<T>(st, rows, final_norm, xn, B, H, c.rms_eps);
+        if (mx4b_on) {
+            GemvMx4BatchArgs hb = gemvb4_args(lm_head4, H, xn, H, nullptr, nullptr, 0, nullptr, 0, V, H, EPI_ARGMAX, B);
+            if (pen) { hb.pen_flags = pen_flags_b; hb.pen_rows = d_pen_rows; hb.pen = rep_penalty; }
+            launch_gemv_mx4b(st, hb);
+            launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_mx4b_grid(V, EPI_ARGMAX), B, d_tok_b);
+            return;
+        }
         argmax_rows(lm_head, H, xn, H, V, H, B, pen);
+    }
+    // svln_set_mxfp4_batched: one product of the batched step on the MXFP4 copy `q` of a weight matrix (gemv_mx4b.hip)
+    GemvMx4BatchArgs gemvb4_args(const Q4& q, int ldw, const void* xin, int ldx, const void* bias, const void* res, int ldr, void* y, int ldy,
+                                 int N, int K, int epi, int B) {
+        GemvMx4BatchArgs a; a.q4 = q.q; a.e8 = q.e8; a.ldw = ldw; a.x = xin; a.ldx = ldx; a.bias = bias; a.res = res; a.ldr = ldr; a.y = y; a.ldy = ldy;
+        a.N = N; a.K = K; a.epi = epi; a.B = B; a.part_val = part_val_b; a.part_idx = part_idx_b; return a;
+    }
+    // the batched step with svln_set_mxfp4_batched on: every B takes the same five launches per layer beside the attention (RMSNorm as
+    // its own launch, the four projections on gemv_mx4b_kernel), then the MXFP4 lm_head
+    void decode_ops_batched_mx4(int B, bool pen) {
+        const int qd = nq * 128;
+        launch_gather_rows<T>(st, d_tok_b, embed, feats, x, B, H);
+        for (int i = 0; i < c.layers; ++i) {
+            const LLayer& L = ll[i];
+            launch_rmsnorm<T>(st, x, L.in_norm, xn, B, H, c.rms_eps);
+            launch_gemv_mx4b(st, gemvb4_args(L.qkv4, H, xn, H, L.qkv_b, nullptr, 0, qkv, qkv_dim, qkv_dim, H, EPI_NONE, B));
+            decode_attention(batched_decode_attn_args(L, B));
+            launch_gemv_mx4b(st, gemvb4_args(L.o4, qd, attn, qd, nullptr, x, H, x, H, H, qd, EPI_NONE, B));
+            launch_rmsnorm<T>(st, x, L.post_norm, xn, B, H, c.rms_eps);
+            launch_gemv_mx4b(st, gemvb4_args(L.gu4, H, xn, H, nullptr, nullptr, 0, hbuf, I, 2 * I, H, EPI_SWIGLU, B));
+            launch_gemv_mx4b(st, gemvb4_args(L.down4, I, hbuf, I, nullptr, x, H, x, H, H, I, EPI_NONE, B));
+        }
+        head_batched(x, B, pen);
     }
     // One decode step for B envs (B in {1,2,4,8}; d_slots / d_tok_b already set): every weight matrix is streamed once.
     // B >= 4: the projections run as 32-row MFMA products (gemm.hip CfgSkinny: the weight stream goes through LDS-DMA, the B rows
     // ride along; the batched GEMV is dot-product-issue bound from B = 4 up) and the split-K reduce of o_proj / down_proj also emits
     // the following RMSNorm.  B <= 2: the batched GEMV (HBM-bound there).
     void decode_ops_batched(int B, bool pen = false) {
+        if (mx4b_on) { decode_ops_batched_mx4(B, pen); return; }
         const int qd = nq * 128;
         const bool mfma = B >= batched_mfma_min;
         launch_gather_rows<T>(st, d_tok_b, embed, feats, x, B, H);
@@ -1262,7 +1296,7 @@ public:
         pen_flags_b = dalloc<uint8_t>((size_t)MAXB * V, true);
         d_pen_rows = dalloc<int>(MAXB, true);
         d_pen_ids = dalloc<int>((size_t)c.max_positions + 8);
-        HIP_CHECK(hipHostMalloc((void**)&h_pen_rows, MAXB * sizeof(int)));
+        HIP_CHECK(hipHostMalloc((void**)&h_pen_rows, 2 * MAXB * sizeof(int)));      // [MAXB ..): the second upload of a split iteration
         HIP_CHECK(hipHostMalloc((void**)&h_pen_ids, ((size_t)c.max_positions + 8) * sizeof(int)));
         HIP_CHECK(hipStreamSynchronize(st));
     }
@@ -1339,9 +1373,13 @@ public:
         const bool pen = rep_penalty != 1.0f;
         // prefill jobs that fit the row workspaces next to the decode rows (the rest wait for the next iteration; a turn of up to
         // max_positions rows runs as soon as no decode row shares the pass)
+        // svln_set_mxfp4_batched: decode rows never ride through the bf16 prefill products.  An iteration that holds both kinds is split:
+        // the decode rows run as a pure batched decode step on the MXFP4 weights, then the prefill segments as a bf16 pass of their own
+        // (rows from 0) with one lm_head for their last rows -- every env keeps the scheme of the solo mode whatever its neighbours do.
+        const bool split_mixed = mx4b_on;
         std::vector<Seg> segs;
         std::vector<int> pre_now;
-        int M = nd;
+        int M = split_mixed ? 0 : nd;
         for (int k : pre) {
             Env& e = envs[jobs[k].env];
             const int Tn = e.n_embeds - e.kv_len;
@@ -1356,7 +1394,8 @@ public:
         std::vector<int> order;                         // job slot of each output token of this iteration
         if (nd > 0) {
             int B = nd;
-            if (segs.empty()) { B = 1; while (B < nd) B <<= 1; }      // the pure decode kernels come in power-of-two batch sizes
+            const bool pure = segs.empty() || split_mixed;
+            if (pure) { B = 1; while (B < nd) B <<= 1; }              // the pure decode kernels come in power-of-two batch sizes
             for (int k = 0; k < B; ++k) {
                 const int kk = k < nd ? k : 0;                          // padding slots replay slot 0 (same writes, ignored outputs)
                 Env& e = envs[jobs[dec[kk]].env];
@@ -1368,12 +1407,12 @@ public:
             }
             HIP_CHECK(hipMemcpyAsync(d_slots, h_slots, B * sizeof(DecodeSlot), hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemcpyAsync(d_tok_b, h_tok_b, B * sizeof(int), hipMemcpyHostToDevice, st));
-            if (segs.empty()) {
+            if (pure) {
                 if (pen) HIP_CHECK(hipMemcpyAsync(d_pen_rows, h_pen_rows, B * sizeof(int), hipMemcpyHostToDevice, st));
                 // gather + 28 layers + head for B decode rows -> d_tok_b, xn = final-norm rows.  With hipGraph replay on, the step of each
                 // (B, fp8, penalty) combination is captured once: every run-time value (page tables, positions, fed tokens) is in d_slots / d_tok_b.
                 if (use_graph) {
-                    const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0);
+                    const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0);
                     auto it = bgraphs.find(key);
                     if (it == bgraphs.end())      // (a failed capture leaves no entry behind)
                         it = bgraphs.emplace(key, capture_graph([&] { decode_ops_batched(B, pen); })).first;
@@ -1386,35 +1425,51 @@ public:
             }
             for (int k = 0; k < nd; ++k) order.push_back(dec[k]);
         }
+        // a split iteration: the decode step above is complete (d_tok_b, xn = its final-norm rows); its taps and tokens are taken
+        // before the prefill pass reuses xn / d_tok_b, and ph_ev[4] divides the iteration's time between the two phase timers
+        const bool split = split_mixed && nd > 0 && !segs.empty();
+        const int head0 = split ? nd : 0;               // first entry of `order` that the lm_head pass below produces
+        if (split) {
+            for (int q = 0; q < nd; ++q) tap_copy(xn + (size_t)q * H, jobs[order[q]].count, order[q]);
+            HIP_CHECK(hipMemcpyAsync(h_tok_b, d_tok_b, nd * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipEventRecord(ph_ev[4], st));
+        }
         if (!segs.empty()) {
-            prefill_rows(segs, M, nd);
-            // last row of every job of this iteration -> one lm_head pass
-            const int nj = nd + (int)segs.size();
-            for (int k = 0; k < nd; ++k)
+            const int nrow = split_mixed ? 0 : nd;      // decode rows that share the prefill pass
+            prefill_rows(segs, M, nrow);
+            // last row of every job of this pass -> one lm_head pass
+            const int nj = nrow + (int)segs.size();
+            for (int k = 0; k < nrow; ++k)
                 HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)k * H, x + (size_t)k * H, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
             for (size_t q = 0; q < segs.size(); ++q) {
                 const T* last = x + (size_t)(segs[q].off + segs[q].Tn - 1) * H;
-                HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)(nd + q) * H, last, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
+                HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)(nrow + q) * H, last, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
                 order.push_back(pre_now[q]);
             }
             int Bp = 1; while (Bp < nj) Bp <<= 1;
             for (int k = nj; k < Bp; ++k)
                 HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)k * H, last_rows, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
             if (pen) {
-                for (int k = 0; k < Bp; ++k) h_pen_rows[k] = order[k < nj ? k : 0];
-                HIP_CHECK(hipMemcpyAsync(d_pen_rows, h_pen_rows, Bp * sizeof(int), hipMemcpyHostToDevice, st));
+                int* hp = h_pen_rows + (split ? MAXB : 0);      // (the decode step's upload may still be pending on the first half)
+                for (int k = 0; k < Bp; ++k) hp[k] = order[head0 + (k < nj ? k : 0)];
+                HIP_CHECK(hipMemcpyAsync(d_pen_rows, hp, Bp * sizeof(int), hipMemcpyHostToDevice, st));
             }
             head_batched(last_rows, Bp, pen);
         }
         const int nj = (int)order.size();
-        for (int q = 0; q < nj; ++q) tap_copy(xn + (size_t)q * H, jobs[order[q]].count, order[q]);
+        for (int q = head0; q < nj; ++q) tap_copy(xn + (size_t)(q - head0) * H, jobs[order[q]].count, order[q]);
         HIP_CHECK(hipEventRecord(ph_ev[3], st));
-        HIP_CHECK(hipMemcpyAsync(h_tok_b, d_tok_b, nj * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h_tok_b + head0, d_tok_b, (nj - head0) * sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         LAUNCH_CHECK("batch_step");
         {
             float t = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[3])); ph_ms[segs.empty() ? 2 : 1] += t;
+            if (split) {
+                HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[4])); ph_ms[2] += t;
+                HIP_CHECK(hipEventElapsedTime(&t, ph_ev[4], ph_ev[3])); ph_ms[1] += t;
+            } else {
+                HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[3])); ph_ms[segs.empty() ? 2 : 1] += t;
+            }
             if (vision_pending) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
         }
         for (int q = 0; q < nj; ++q) {
@@ -1688,13 +1743,15 @@ public:
     void set_fp8_decode(int enable) override {
         if (!enable) { if (fp8_on) drop_graphs(); fp8_on = false; return; }
         REQUIRE(!mx4_on, "svln_set_fp8_decode: the MXFP4 decode weights are on (svln_set_mxfp4_decode); switch them off first");
+        REQUIRE(!mx4b_on, "svln_set_fp8_decode: the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
         build_fp8_weights();
         if (!fp8_on) drop_graphs();
         fp8_on = true;
     }
     // Opt-in (no reference counterpart): the single-env decode step's four projections and every lm_head product read
     // OCP MXFP4 copies of the LLM weights (E2M1 elements, one E8M0 scale per 32 elements of a row: 4.25 bits per weight) instead of the
-    // bf16 ones; prefill, vision, attention, norms and the lockstep multi-env path keep bf16.  Both copies stay resident (15.2 + 4.0 GB).
+    // bf16 ones; prefill, vision, attention and norms keep bf16, and so does the lockstep multi-env path unless svln_set_mxfp4_batched is on.
+    // Both copies stay resident (15.2 + 4.0 GB).
     // Quantised from the tensors loaded at the time of the first enable.
     void build_mxfp4_weights() {
         REQUIRE(sizeof(T) == 2, "MXFP4 weights need the bf16 engine");
@@ -1724,12 +1781,29 @@ public:
         if (!mx4_on) drop_graphs();
         mx4_on = true;
     }
+    // Opt-in (no reference counterpart): the batched decode step of svln_generate_batch / svln_batch_step (q|k|v, o_proj, gate/up and
+    // down_proj at every B) and every lm_head product of the scheduler read the MXFP4 copies above through gemv_mx4b_kernel (weight-only:
+    // bf16 activations on the MFMA path); prefill rows keep the bf16 products, and an iteration that holds decode rows and prefill rows is
+    // split so that no decode row rides through them (batch_step_run).  Independent of svln_set_mxfp4_decode (the single-env step).
+    void set_mxfp4_batched(int enable) override {
+        if ((enable != 0) == mx4b_on) return;      // nothing changes
+        // an env must not change scheme in the middle of a turn, in either direction
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_mxfp4_batched cannot change while scheduler turns are in flight");
+        if (!enable) { drop_graphs(); mx4b_on = false; return; }
+        REQUIRE(sizeof(T) == 2, "svln_set_mxfp4_batched: MXFP4 weights need the bf16 engine");
+        REQUIRE(!fp8_on, "svln_set_mxfp4_batched: the e4m3 decode weights are on (svln_set_fp8_decode); switch them off first");
+        REQUIRE(!fp8_gemm_on, "svln_set_mxfp4_batched: the e4m3 MFMA products are on (svln_set_fp8_gemm); switch them off first");
+        build_mxfp4_weights();
+        drop_graphs();
+        mx4b_on = true;
+    }
     // Opt-in (no reference counterpart): the LLM's dense products with more than one row -- prefill (svln_generate,
     // the scheduler) and the decode steps of >= 4 lockstep envs -- run as e4m3 x e4m3 MFMA products (v_mfma_f32_32x32x16_fp8_fp8, fp32
     // accumulate, bf16 out): per-row weight scales (the copies of svln_set_fp8_decode), per-row activation scales computed on the fly.
     // Half the operand bytes per k through HBM / L2 / LDS.  Vision, attention, norms and the lm_head stay bf16.
     void set_fp8_gemm(int enable) override {
         if (!enable) { fp8_gemm_on = false; return; }
+        REQUIRE(!mx4b_on, "svln_set_fp8_gemm: the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
         build_fp8_weights();
         if (!act8) {
             const size_t widest = (size_t)(I > nq * 128 ? I : nq * 128);
@@ -1853,6 +1927,29 @@ public:
         }
         sync();
         LAUNCH_CHECK("op_gemv_batched");
+    }
+    void op_gemv_mxfp4_batched(GemvMx4BatchArgs a, int32_t* host_tokens) override {
+        // refusals before any launch
+        REQUIRE(sizeof(T) == 2, "MXFP4 weights need the bf16 engine");
+        REQUIRE(a.q4 && a.e8 && a.x, "null pointer");
+        REQUIRE(a.B >= 1 && a.B <= MAXB, "B must be 1 .. 8");
+        REQUIRE(a.N >= 1 && a.K >= 32 && a.K % 32 == 0, "N >= 1, K a positive multiple of 32");
+        REQUIRE(a.ldw >= a.K && a.ldw % 32 == 0, "ldw >= K, a multiple of 32");
+        REQUIRE(a.ldx >= a.K && a.ldx % 8 == 0, "ldx >= K, a multiple of 8 (aligned 16-byte loads)");
+        REQUIRE(a.epi == EPI_NONE || a.epi == EPI_SWIGLU || a.epi == EPI_ARGMAX, "epilogue: EPI_NONE, EPI_SWIGLU or EPI_ARGMAX");
+        REQUIRE(a.epi != EPI_SWIGLU || a.N % 64 == 0, "SwiGLU needs N % 64 == 0 (32-row gate / up blocks)");
+        REQUIRE(a.epi == EPI_ARGMAX || a.y, "null output pointer");
+        REQUIRE(!a.pen_flags || (a.epi == EPI_ARGMAX && a.pen_rows && a.pen > 0.0f), "penalty flags: arg-max only, with their row table and a factor > 0");
+        a.part_val = part_val_b; a.part_idx = part_idx_b;
+        launch_gemv_mx4b(st, a);
+        if (a.epi == EPI_ARGMAX) {
+            launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_mx4b_grid(a.N, EPI_ARGMAX), a.B, d_tok_b);
+            HIP_CHECK(hipMemcpyAsync(h_tok_b, d_tok_b, a.B * sizeof(int), hipMemcpyDeviceToHost, st));
+            sync();
+            if (host_tokens) for (int b = 0; b < a.B; ++b) host_tokens[b] = h_tok_b[b];
+        }
+        sync();
+        LAUNCH_CHECK("op_gemv_mxfp4_batched");
     }
     void op_quant_fp8(const void* w, int64_t rows, int cols, void* w8, float* scale) override {
         REQUIRE(sizeof(T) == 2, "fp8 quantisation reads bf16 weights");
@@ -2186,6 +2283,7 @@ int svln_probe_decode_layer(svln_engine* h, int layer, unsigned long long* out, 
 int svln_set_fp8_decode(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_fp8_decode(enable); API_END }
 int svln_set_fp8_gemm(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_fp8_gemm(enable); API_END }
 int svln_set_mxfp4_decode(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_mxfp4_decode(enable); API_END }
+int svln_set_mxfp4_batched(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_mxfp4_batched(enable); API_END }
 int svln_set_memory_prune(svln_engine* h, int keep_tokens) { API_BEGIN_H h->impl->set_memory_prune(keep_tokens); API_END }
 int svln_op_memory_prune(svln_engine* h, const void* mem, int n_rows, int keep, int32_t* out_idx, float* out_score) {
     API_BEGIN_H h->impl->op_memory_prune(mem, n_rows, keep, out_idx, out_score); API_END
@@ -2280,6 +2378,24 @@ int svln_op_gemv_mxfp4(svln_engine* h, const void* q4, const void* e8, int ldw, 
     GemvArgs a; a.W = nullptr; a.ldw = ldw; a.x = x; a.norm_w = norm_w; a.eps = eps; a.bias = bias; a.res = res; a.y = y; a.N = N; a.K = K; a.epi = epi;
     a.part_val = nullptr; a.part_idx = nullptr; a.w8 = nullptr; a.scale = nullptr; a.skip = nullptr; a.w4 = q4; a.e8 = (const uint8_t*)e8;
     h->impl->op_gemv(a, host_token);
+    API_END
+}
+int svln_op_gemv_mxfp4_batched(svln_engine* h, const void* q4, const void* e8, int ldw, const void* x, int ldx, const void* bias, const void* res,
+                               int ldr, void* y, int ldy, int N, int K, int epi, int B, int32_t* host_tokens) {
+    API_BEGIN_H
+    GemvMx4BatchArgs a; a.q4 = q4; a.e8 = (const uint8_t*)e8; a.ldw = ldw; a.x = x; a.ldx = ldx; a.bias = bias; a.res = res; a.ldr = ldr;
+    a.y = y; a.ldy = ldy; a.N = N; a.K = K; a.epi = epi; a.B = B; a.part_val = nullptr; a.part_idx = nullptr;
+    h->impl->op_gemv_mxfp4_batched(a, host_tokens);
+    API_END
+}
+int svln_op_gemv_mxfp4_batched_argmax_pen(svln_engine* h, const void* q4, const void* e8, int ldw, const void* x, int ldx, int N, int K, int B,
+                                          const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens) {
+    API_BEGIN_H
+    if (!pen_flags || !pen_rows) throw std::runtime_error("null pointer");
+    GemvMx4BatchArgs a; a.q4 = q4; a.e8 = (const uint8_t*)e8; a.ldw = ldw; a.x = x; a.ldx = ldx; a.bias = nullptr; a.res = nullptr; a.ldr = 0;
+    a.y = nullptr; a.ldy = 0; a.N = N; a.K = K; a.epi = EPI_ARGMAX; a.B = B; a.part_val = nullptr; a.part_idx = nullptr;
+    a.pen_flags = (const uint8_t*)pen_flags; a.pen_rows = pen_rows; a.pen = penalty;
+    h->impl->op_gemv_mxfp4_batched(a, host_tokens);
     API_END
 }
 int svln_op_rmsnorm(svln_engine* h, const void* x, const void* g, void* y, int rows, int n, float eps) { API_BEGIN_H h->impl->op_rmsnorm(x, g, y, rows, n, eps); API_END }

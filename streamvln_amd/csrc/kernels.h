@@ -114,6 +114,22 @@ struct GemvBatchArgs {
 template <typename T> void launch_gemv_batched(hipStream_t s, const GemvBatchArgs& a);
 int gemv_batched_grid(int N, int epi, int B);
 void launch_argmax_final_batched(hipStream_t s, const float* part_val, const int* part_idx, int n, int B, int* out_tokens);
+// B (1 .. 8) bf16 activation vectors against one MXFP4 weight stream on v_mfma_f32_16x16x32_bf16 (gemv_mx4b.hip; bf16 engine, opt-in):
+// q4 / e8 / ldw as GemvArgs::w4 / e8 / ldw (the layout of the batch-1 GEMVs), x [B][ldx], y [B][ldy], res [B][ldr]; K, ldw multiples of 32,
+// ldx a multiple of 8.  No fused RMSNorm.  EPI_SWIGLU as above.  EPI_ARGMAX: part_val / part_idx are [B][gemv_mx4b_grid(N, epi)], reduced
+// by launch_argmax_final_batched; optional repetition penalty as in GemvBatchArgs.
+struct GemvMx4BatchArgs {
+    const void* q4; const uint8_t* e8; int ldw;
+    const void* x; int ldx;
+    const void* bias;
+    const void* res; int ldr;
+    void* y; int ldy;
+    int N, K, epi, B;
+    float* part_val; int* part_idx;
+    const uint8_t* pen_flags = nullptr; const int* pen_rows = nullptr; float pen = 1.0f;
+};
+void launch_gemv_mx4b(hipStream_t s, const GemvMx4BatchArgs& a);
+int gemv_mx4b_grid(int N, int epi);
 void launch_argmax_final(hipStream_t s, const float* part_val, const int* part_idx, int n, int* out_token,
                          float* out_top /*[2]: best, runner-up of partial maxima (diagnostic)*/);
 // Device-side state of one greedy generation (GenerationMixin._sample: append the arg-max, stop on EOS or max_new_tokens), so that

@@ -718,14 +718,24 @@ class StreamVLNForCausalLM:
 
     def set_fp8_decode(self, enable: bool):
         """Opt-in extension (the reference is bf16 only): decode steps and the lm_head read e4m3 copies of the LLM
-        weights (per-row scale).  Prefill, vision and generate_batch keep bf16.  bf16 engines only."""
+        weights (per-row scale).  Prefill, vision and generate_batch keep bf16 (the batched paths have set_fp8_gemm and
+        set_mxfp4_batched).  bf16 engines only; refused while set_mxfp4_decode or set_mxfp4_batched is on."""
         _check(self._lib.svln_set_fp8_decode(self._h, int(enable)))
 
     def set_mxfp4_decode(self, enable: bool):
         """Opt-in extension (the reference is bf16 only): decode steps and the lm_head read OCP MXFP4 copies of the LLM
-        weights (E2M1 elements, one E8M0 scale per 32: 4.25 bits per weight).  Prefill, vision and generate_batch keep bf16.  bf16
-        engines only; refused while set_fp8_decode is on (and the other way round)."""
+        weights (E2M1 elements, one E8M0 scale per 32: 4.25 bits per weight).  Prefill and vision keep bf16; generate_batch and the
+        scheduler keep bf16 too unless set_mxfp4_batched is on.  bf16 engines only; refused while set_fp8_decode is on (and the other
+        way round)."""
         _check(self._lib.svln_set_mxfp4_decode(self._h, int(enable)))
+
+    def set_mxfp4_batched(self, enable: bool):
+        """Opt-in extension (the reference is bf16 only): the decode steps of generate_batch / submit + step_batch (every batch size)
+        and every lm_head product of the scheduler read the MXFP4 weight copies of set_mxfp4_decode on a weight-only MFMA kernel;
+        prefill rows keep bf16, and an iteration that mixes prefill and decode rows is split so that each env is computed as in the
+        single-env mode.  Independent of set_mxfp4_decode; bf16 engines only; refused while set_fp8_decode or set_fp8_gemm is on (and
+        they are refused while it is on)."""
+        _check(self._lib.svln_set_mxfp4_batched(self._h, int(enable)))
 
     def set_fp8_gemm(self, enable: bool):
         """Opt-in extension (SURVEY.md 8f-2 / BASELINE configs[4]): the LLM's multi-row products (prefill; decode steps of >= 4 batched
