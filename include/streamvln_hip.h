@@ -228,7 +228,11 @@ int svln_feature_cache_stats(svln_engine* h, int64_t* hits, int64_t* misses);
  * (M <= 256), 64 = 64x64, 32 = 32x128 (M <= 32); flag bits: 0x1000 row tiles fastest in the workgroup order, 0x10000 column tiles
  * fastest, 0x4000 stage-ring kernel for the 256x256 tile, 0x8000 32x32x16 form of the 8-phase schedule, 0x20000 direct 2-byte stores in the 8-phase
  * epilogue instead of the LDS-staged 16-byte row chunks.
- * force_split: 0 = heuristic, S >= 1 = 256x128 tiles (256x64 with force_cfg 264) with S K-splits */
+ * force_split: 0 = heuristic, S >= 1 = 256x128 tiles (256x64 with force_cfg 264) with S K-splits.
+ * Every svln_op_gemm* call is refused (non-zero, svln_last_error) before any launch when A, W or C is null or A / W not 16-byte aligned, an
+ * extent is negative, K, lda or ldw is not a multiple of the operand format's 16-byte chunk (4 fp32, 8 bf16, 16 e4m3 values), lda or
+ * ldw < K, ldc below the output width, a residual has ldr < N, res_mod < 0, SwiGLU meets N % 64 != 0, or epi is not NONE, GELU_TANH,
+ * GELU_ERF or SWIGLU. */
 int svln_op_gemm(svln_engine* h, const void* A, int lda, const void* W, int ldw, void* C, int ldc, const void* bias, const void* res,
                  int ldr, int res_mod, int M, int N, int K, int epi, int force_cfg, int force_split);
 /* C = A . W^T + bias + res, and -- when the product takes the split-K path (few rows, N <= 4096) -- norm_out = norm(C) from the same slab

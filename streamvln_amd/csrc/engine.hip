@@ -1835,12 +1835,8 @@ public:
         REQUIRE(sizeof(T) == 2, "fp8 products need the bf16 engine");
         GemmArgs a = a0; a.ws = gemm_ws; a.ws_elems = gemm_ws_elems; a.zeros = zero_line;
         REQUIRE(a.a_scale && a.w_scale, "missing scales");
-        REQUIRE(a.K % 16 == 0 && a.lda % 16 == 0 && a.ldw % 16 == 0, "K and the row strides must be multiples of 16");
         REQUIRE(a.epi == EPI_NONE || a.epi == EPI_SWIGLU, "fp8 products: plain or SwiGLU epilogue");
-        if (a.force_split > 1) {
-            REQUIRE((size_t)a.force_split * a.M * a.N <= gemm_ws_elems, "force_split: S * M * N exceeds the split-K workspace");
-            REQUIRE(a.N % 4 == 0 && !(a.epi == EPI_SWIGLU && a.N % 64 != 0), "force_split: N must be a multiple of 4 (64 with SwiGLU)");
-        }
+        gemm_refusals(a, 16);
         const bool fused = launch_gemm<T>(st, a);
         sync();
         LAUNCH_CHECK("op_gemm_fp8");
@@ -1879,15 +1875,33 @@ public:
     }
 
     // ------------------------------------------------------------------------------- op-level entry points
-    bool op_gemm(const GemmArgs& a0) override {
-        GemmArgs a = a0; a.ws = gemm_ws; a.ws_elems = gemm_ws_elems; a.zeros = zero_line;
+    // refusals of svln_op_gemm* before any launch: `chunk` = operand values per 16-byte LDS-DMA piece (the kernels index K in chunks and
+    // stage whole chunks: a K or a row stride off that grid would be truncated or misalign the DMA); launch_gemm knows four epilogues
+    void gemm_refusals(const GemmArgs& a, int chunk) {
+        REQUIRE(a.A && a.W && a.C, "null pointer");
         REQUIRE(a.M >= 0 && a.N >= 0 && a.K >= 0, "negative GEMM extent");
+        REQUIRE(a.epi == EPI_NONE || a.epi == EPI_GELU_TANH || a.epi == EPI_GELU_ERF || a.epi == EPI_SWIGLU,
+                "epilogue: EPI_NONE, EPI_GELU_TANH, EPI_GELU_ERF or EPI_SWIGLU");
+        REQUIRE(a.K % chunk == 0, "K must be a multiple of the format's 16-byte chunk");
+        REQUIRE(a.lda >= a.K && a.ldw >= a.K && a.lda % chunk == 0 && a.ldw % chunk == 0,
+                "lda, ldw >= K, multiples of the format's 16-byte chunk (aligned LDS-DMA)");
+        REQUIRE(((size_t)a.A & 15) == 0 && ((size_t)a.W & 15) == 0, "A and W must be 16-byte aligned (LDS-DMA)");
+        REQUIRE(a.epi != EPI_SWIGLU || a.N % 64 == 0, "SwiGLU needs N % 64 == 0 (32-row gate / up blocks)");
+        REQUIRE(a.ldc >= (a.epi == EPI_SWIGLU ? a.N / 2 : a.N), "ldc below the output width");
+        REQUIRE(!a.res || a.ldr >= a.N, "residual: ldr below N");
+        REQUIRE(a.res_mod >= 0, "negative res_mod");
+        REQUIRE(!a.norm_out || a.norm_w, "norm_out without norm_w");
         if (a.force_split > 1) {
             REQUIRE((size_t)a.force_split * a.M * a.N <= gemm_ws_elems, "force_split: S * M * N exceeds the split-K workspace");
-            REQUIRE(a.N % 4 == 0 && !(a.epi == EPI_SWIGLU && a.N % 64 != 0), "force_split: N must be a multiple of 4 (64 with SwiGLU)");
+            REQUIRE(a.N % 4 == 0, "force_split: N must be a multiple of 4");
         }
+    }
+    bool op_gemm(const GemmArgs& a0) override {
+        GemmArgs a = a0; a.ws = gemm_ws; a.ws_elems = gemm_ws_elems; a.zeros = zero_line;
+        gemm_refusals(a, Elt<T>::PER_CHUNK);
         const bool fused = launch_gemm<T>(st, a);
         sync();
+        LAUNCH_CHECK("op_gemm");
         return fused;
     }
     void op_gemv(GemvArgs a, int32_t* host_token) override {
