@@ -248,6 +248,29 @@ int svln_op_gemm_norm_q8(svln_engine* h, const void* A, int lda, const void* W, 
                          const void* norm_w, void* norm_out, float eps, int M, int N, int K, int force_split, void* q8, float* q8_scale, int* fused);
 int svln_op_gemv(svln_engine* h, const void* W, int ldw, const void* x, const void* norm_w, float eps, const void* bias, const void* res,
                  void* y, int N, int K, int epi, int32_t* host_token);
+/* What the GEMM dispatcher does with one product, without launching it: needs no engine and no device.  The problem holds what the
+ * dispatcher reads of a call: dtype SVLN_BF16 / SVLN_F32, epi as above, the extents, 0 / 1 flags for the optional pointers (fp8 = e4m3
+ * operands with scales, has_ws / ws_elems = the split-K workspace in fp32 elements, has_zeros = the zero line, norm_out, norm_w, res), the
+ * fused-tail requests with their extents (rope: q heads, kv heads, rows; vitpack: frames, rows per frame, heads, head_dim) and force_cfg /
+ * force_split.  The plan holds the one or two tile launches (tile: 0 32x128, 1 64x64, 2 128x128, 3 128x128 for more than one round,
+ * 4 128x128 with two K groups, 5 256x128, 6 256x64, 7 256x256 stage ring, 8 256x256 8-phase, 9 its 32x32x16 form; the kernel variant;
+ * the launcher-filled GemmArgs fields; grid, block, dynamic LDS), the reducer after a K-split launch (0 none, 1 epilogue, 2 row norm,
+ * 3 q|k|v RoPE + KV append, 4 ViT K / V^T pack) with its grid and block, `fused` (what svln_op_gemm_norm reports) and vit_packer.
+ * Refused with a message: a null argument, an unknown dtype or epilogue, an extent outside int32. */
+typedef struct svln_gemm_problem {
+    int64_t dtype, epi, M, N, K, fp8, has_ws;
+    uint64_t ws_elems;
+    int64_t has_zeros, norm_out, norm_w, res, rope, rope_nq, rope_nkv, rope_T, vitpack, vit_F, vit_S, vit_heads, vit_head_dim, force_cfg, force_split;
+} svln_gemm_problem;
+typedef struct svln_gemm_launch {
+    int32_t tile, splitk, fp8, ntw, vp, tile_base, launch_tiles, nsplit, grid, block, lds_bytes, bm, bn;
+    int32_t reducer, reducer_grid[3], reducer_block, reduce_too_large;
+} svln_gemm_launch;
+typedef struct svln_gemm_plan_out {
+    int32_t nt_w, bn_fast, n_launches, fused, vit_packer;
+    svln_gemm_launch launch[2];
+} svln_gemm_plan_out;
+int svln_gemm_plan(const svln_gemm_problem* problem, svln_gemm_plan_out* plan);
 /* the product behind svln_set_fp8_gemm: C [M][N] (bf16) = epi(a_scale[m] * w_scale[n] * (A8 [M][K] . W8 [N][K]^T) + bias) + res, e4m3 operands
  * (svln_op_quant_fp8 makes them), epi = EPI_NONE or EPI_SWIGLU, K % 16 == 0 */
 int svln_op_gemm_fp8(svln_engine* h, const void* A8, const float* a_scale, int lda, const void* W8, const float* w_scale, int ldw, void* C, int ldc,

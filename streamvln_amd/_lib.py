@@ -38,6 +38,35 @@ class SvlnTurnArgs(C.Structure):
     ]
 
 
+class SvlnGemmProblem(C.Structure):
+    """svln_gemm_problem of include/streamvln_hip.h"""
+    _fields_ = [(n, C.c_uint64 if n == "ws_elems" else C.c_int64) for n in (
+        "dtype", "epi", "M", "N", "K", "fp8", "has_ws", "ws_elems", "has_zeros", "norm_out", "norm_w", "res", "rope", "rope_nq", "rope_nkv",
+        "rope_T", "vitpack", "vit_F", "vit_S", "vit_heads", "vit_head_dim", "force_cfg", "force_split")]
+
+
+class SvlnGemmLaunch(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tile", "splitk", "fp8", "ntw", "vp", "tile_base", "launch_tiles", "nsplit", "grid", "block",
+                                         "lds_bytes", "bm", "bn", "reducer")] + \
+               [("reducer_grid", C.c_int32 * 3), ("reducer_block", C.c_int32), ("reduce_too_large", C.c_int32)]
+
+
+class SvlnGemmPlan(C.Structure):
+    """svln_gemm_plan_out of include/streamvln_hip.h"""
+    _fields_ = [(n, C.c_int32) for n in ("nt_w", "bn_fast", "n_launches", "fused", "vit_packer")] + [("launch", SvlnGemmLaunch * 2)]
+
+
+GEMM_TILES = ("skinny", "c64", "c128", "c128L", "c128K2", "c256", "c256n64", "big", "p8", "p8_32")      # svln_gemm_launch.tile
+GEMM_REDUCERS = (None, "epilogue", "rownorm", "qkv_rope", "vitpack")                                     # svln_gemm_launch.reducer
+
+
+def gemm_plan(**problem) -> SvlnGemmPlan:
+    """svln_gemm_plan for the given svln_gemm_problem fields (the others 0): what the GEMM dispatcher does with the product; no GPU needed"""
+    plan = SvlnGemmPlan()
+    check(load().svln_gemm_plan(C.byref(SvlnGemmProblem(**problem)), C.byref(plan)))
+    return plan
+
+
 _P, _I, _F, _I64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
 _PI32, _PI64, _PF, _PD = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_double)
 
@@ -99,6 +128,7 @@ SIGNATURES = {
     "svln_op_gemm": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I]),
     "svln_op_gemm_norm": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _F, _I, _I, _I, _I, _PI32]),
     "svln_op_gemm_norm_q8": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _F, _I, _I, _I, _I, _P, _P, _PI32]),
+    "svln_gemm_plan": (_I, [C.POINTER(SvlnGemmProblem), C.POINTER(SvlnGemmPlan)]),
     "svln_op_gemv": (_I, [_P, _P, _I, _P, _P, _F, _P, _P, _P, _I, _I, _I, _PI32]),
     "svln_op_gemm_fp8": (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
     "svln_op_gemv_batched": (_I, [_P, _P, _I, _P, _I, _P, _F, _P, _P, _I, _P, _I, _I, _I, _I, _I, _PI32]),

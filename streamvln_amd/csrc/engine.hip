@@ -20,6 +20,7 @@
 
 #include "../../include/streamvln_hip.h"
 #include "common.h"
+#include "gemm_plan.h"
 #include "kernels.h"
 
 namespace svln {
@@ -2339,6 +2340,36 @@ int svln_op_gemm_norm_q8(svln_engine* h, const void* A, int lda, const void* W, 
     a.norm_q8 = q8; a.norm_q8_scale = q8_scale; a.pen = 1.0f;
     const bool f = h->impl->op_gemm(a);
     if (fused) *fused = f ? 1 : 0;
+    API_END
+}
+int svln_gemm_plan(const svln_gemm_problem* q, svln_gemm_plan_out* out) {
+    API_BEGIN
+    REQUIRE(q && out, "null argument");
+    REQUIRE(q->dtype == SVLN_BF16 || q->dtype == SVLN_F32, "dtype: SVLN_BF16 or SVLN_F32");
+    REQUIRE(q->epi == EPI_NONE || q->epi == EPI_GELU_TANH || q->epi == EPI_GELU_ERF || q->epi == EPI_SWIGLU,
+            "epilogue: EPI_NONE, EPI_GELU_TANH, EPI_GELU_ERF or EPI_SWIGLU");
+    for (int64_t v : {q->M, q->N, q->K, q->rope_nq, q->rope_nkv, q->rope_T, q->vit_F, q->vit_S, q->vit_heads, q->vit_head_dim, q->force_cfg, q->force_split})
+        REQUIRE(v >= INT32_MIN && v <= INT32_MAX, "extent outside int32");
+    GemmProblem p;
+    p.elt_bytes = q->dtype == SVLN_F32 ? 4 : 2; p.epi = (int)q->epi; p.M = (int)q->M; p.N = (int)q->N; p.K = (int)q->K;
+    p.fp8 = q->fp8 != 0; p.has_ws = q->has_ws != 0; p.ws_elems = (size_t)q->ws_elems; p.has_zeros = q->has_zeros != 0;
+    p.norm_out = q->norm_out != 0; p.norm_w = q->norm_w != 0; p.res = q->res != 0;
+    p.rope = q->rope != 0; p.rope_nq = (int)q->rope_nq; p.rope_nkv = (int)q->rope_nkv; p.rope_T = (int)q->rope_T;
+    p.vitpack = q->vitpack != 0; p.vit_F = (int)q->vit_F; p.vit_S = (int)q->vit_S; p.vit_heads = (int)q->vit_heads; p.vit_head_dim = (int)q->vit_head_dim;
+    p.force_cfg = (int)q->force_cfg; p.force_split = (int)q->force_split;
+    const GemmPlan g = plan_gemm(p);
+    std::memset(out, 0, sizeof(*out));
+    out->nt_w = g.nt_w; out->bn_fast = g.bn_fast; out->n_launches = g.n_launches; out->fused = g.fused ? 1 : 0; out->vit_packer = g.vit_packer;
+    for (int i = 0; i < g.n_launches; ++i) {
+        const GemmLaunch& l = g.launch[i];
+        const TileGeom& t = TILE_GEOM[l.tile];
+        svln_gemm_launch& o = out->launch[i];
+        o.tile = l.tile; o.splitk = l.splitk; o.fp8 = l.fp8; o.ntw = l.ntw; o.vp = l.vp;
+        o.tile_base = l.tile_base; o.launch_tiles = l.launch_tiles; o.nsplit = l.nsplit; o.grid = l.wgs;
+        o.block = t.threads; o.lds_bytes = t.lds_bytes; o.bm = t.bm; o.bn = t.bn;
+        o.reducer = l.reducer; o.reducer_block = l.rblock; o.reduce_too_large = l.reduce_too_large;
+        for (int j = 0; j < 3; ++j) o.reducer_grid[j] = (int32_t)l.rgrid[j];
+    }
     API_END
 }
 int svln_op_gemv(svln_engine* h, const void* W, int ldw, const void* x, const void* norm_w, float eps, const void* bias, const void* res, void* y,

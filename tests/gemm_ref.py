@@ -24,6 +24,7 @@ import math
 import torch
 
 from oracle import streamvln_oracle as O
+from streamvln_amd import _lib
 
 EPS = 1e-6
 EPC = {"fp32": 4, "bf16": 8, "e4m3": 16}             # operand values per 16-byte chunk
@@ -32,9 +33,10 @@ POISON = 2.0 ** 60
 FILL = 777.0                                         # sentinel of the output buffers (guard rows, ldc padding)
 WS_ELEMS = 8 * 3 * 729 * 1024                        # split-K workspace of the TINY engine the GPU test creates (max_frames 3), fp32 elements
 DIRTY = 16384.0                                      # what the slabs hold before a split case (the GPU test runs a product that leaves it)
-# tile configurations of gemm.hip: (BM, BN, ring depth | "p8", K groups)
-CFGS = {"skinny": (32, 128, 3, 1), "c64": (64, 64, 6, 1), "c128": (128, 128, 2, 1), "c128L": (128, 128, 2, 1), "c128K2": (128, 128, 2, 2),
-        "c256": (256, 128, 3, 1), "c256n64": (256, 64, 3, 1), "big": (256, 256, 2, 1), "p8": (256, 256, "p8", 1), "p8_32": (256, 256, "p8", 1)}
+# what the reference needs of a tile configuration of gemm.hip and the plan does not report: (ring depth | "p8", K groups)
+CFGS = {"skinny": (3, 1), "c64": (6, 1), "c128": (2, 1), "c128L": (2, 1), "c128K2": (2, 2), "c256": (3, 1), "c256n64": (3, 1), "big": (2, 1),
+        "p8": ("p8", 1), "p8_32": ("p8", 1)}
+EPI_ID = {"none": 0, "gelu_tanh": 1, "gelu_erf": 2, "swiglu": 3}
 
 
 def cdiv(a, b):
@@ -45,72 +47,16 @@ def representable(v, dtype):
     return v.to(dtype).to(torch.float64) == v
 
 
-# ---------------------------------------------------------------------------------------------------------- launch_epi, restated
-def route(bf16, fp8, M, N, K, epc, epi, force_cfg=0, force_split=0, norm=False, ws=WS_ELEMS):
-    """restatement of gemm.hip launch_epi: {cfg, S (K slices of the main launch), tail (None | (first tile, S of the tail launch)), fused
-    (the reduce emits the norm)}.  It places the cases (coverage, which mutants apply); no expected value depends on it."""
-    glu = epi == "swiglu"
-    can = N % 4 == 0 and not (glu and N % 64 != 0)
-    fs, fc = force_split, force_cfg & 0xFFF
-    st = cdiv(K // epc, 8)
-
-    def fit(S):
-        while S > 1 and S * M * N > ws:
-            S -= 1
-        return S
-
-    def out(cfg, S=1, tail=None):
-        return {"cfg": cfg, "S": S, "tail": tail, "fused": bool(S > 1 and norm and epi == "none" and N <= 4096 and N % 4 == 0)}
-
-    if fs > 1:
-        fs = fit(fs) if can else 1
-    if M <= 32 and fc in (0, 32):
-        tiles_n, S = cdiv(N, 128), 1
-        if fs > 0:
-            S = fs
-        elif tiles_n < 192 and can:
-            S = 512 // tiles_n
-            if S > st // 2:
-                S = max(st // 2, 1)
-            S = fit(min(S, 16))
-        return out("skinny", S)
-    tilesbig = cdiv(M, 256) * cdiv(N, 256)
-    if bf16 and not fp8 and can and 2 * M * N <= ws and \
-            ((96 <= tilesbig <= 128 and M > 512 and st >= 128 and fs == 0 and fc == 0) or fc == 258):
-        return out("p8", 2)
-    if (tilesbig >= 140 and M > 512 and fs == 0 and fc == 0) or fc == 256:
-        if bf16 and not fp8 and not force_cfg & 0x4000:
-            return out("p8_32" if force_cfg & 0x8000 else "p8")
-        return out("big")
-    tiles128 = cdiv(M, 128) * cdiv(N, 128)
-    n64 = fc == 0 and fs == 0 and epi == "none" and 32 < M <= 256 and 1024 <= N <= 4608 and 1024 <= K <= 4096
-    vit64 = fc == 0 and fs == 0 and epi == "none" and 512 < M <= 768 and N <= 1280 and K <= 1280 and norm
-    if vit64:
-        fs = 3
-    if (fc == 264 or n64 or vit64) and not fp8:
-        S = fs if fs > 0 else max(256 // (cdiv(M, 256) * cdiv(N, 64)), 1)
-        if S > st // 2:
-            S = max(st // 2, 1)
-        return out("c256n64", fit(S) if can else 1)
-    if fc == 64:
-        return out("c64")
-    if fs == 0 and ((fc == 0 and M > 256 and 96 <= tiles128 <= 256 and st >= 8 and not norm) or fc == 129):
-        return out("c128K2")
-    if (M > 256 and tiles128 >= 256 and fs == 0) or fc == 128:
-        return out("c128L" if tiles128 > 256 else "c128")
-    tiles_n = cdiv(N, 128)
-
-    def pick(tiles):
-        S = max(256 // tiles, 1)
-        if S > st // 2:
-            S = max(st // 2, 1)
-        return fit(min(S, 16)) if can else 1
-
-    if fs > 0:
-        return out("c256", fs)
-    if M <= 256 and 256 < tiles_n < 512 and can and pick(tiles_n - 256) > 1:
-        return out("c256", 1, (256, pick(tiles_n - 256)))
-    return out("c256", pick(cdiv(M, 256) * tiles_n))
+# ---------------------------------------------------------------------------------------------------------- the dispatcher's plan
+def plan(bf16, fp8, M, N, K, epi, force_cfg=0, force_split=0, norm=False, res=False):
+    """what the dispatcher itself (gemm_plan.h through svln_gemm_plan; no GPU) does with a product issued by the op entry points of the GPU
+    test's engine: {cfg, BM, BN, S (K slices of the main launch), tail (None | (first tile, S of the tail launch)), fused (the reduce emits
+    the norm)}.  It places the cases (coverage, which mutants apply); no expected value depends on it."""
+    g = _lib.gemm_plan(dtype=_lib.SVLN_BF16 if bf16 else _lib.SVLN_F32, epi=EPI_ID[epi], M=M, N=N, K=K, fp8=int(fp8), has_ws=1, ws_elems=WS_ELEMS,
+                       has_zeros=1, norm_out=int(norm), norm_w=int(norm), res=int(res), force_cfg=force_cfg, force_split=force_split)
+    main, tail = g.launch[0], g.launch[1] if g.n_launches == 2 else None
+    return {"cfg": _lib.GEMM_TILES[main.tile], "BM": main.bm, "BN": main.bn, "S": main.nsplit, "tail": (tail.tile_base, tail.nsplit) if tail else None,
+            "fused": bool(g.fused)}
 
 
 def k_slices(stages, S):
@@ -140,8 +86,9 @@ class Case:
         self.entry = "fp8" if fp8 else "q8" if q8 else "norm" if norm else "gemm"
         self.exact = epi == "none"
         assert not (inplace and (res_mod or epi == "swiglu")) and not (fp8 and not self.bf16) and not (norm and (cfg or epi != "none" or res_mod))
-        self.geom = route(self.bf16, fp8, M, N, self.K, self.epc, epi, cfg, split, norm is not None)
-        self.BM, self.BN, self.ring, self.KG = CFGS[self.geom["cfg"]]
+        self.geom = plan(self.bf16, fp8, M, N, self.K, epi, cfg, split, norm is not None, self.res_on)
+        self.BM, self.BN = self.geom["BM"], self.geom["BN"]
+        self.ring, self.KG = CFGS[self.geom["cfg"]]
         self.stages = cdiv(kc, 8)
         S, tail = self.geom["S"], self.geom["tail"]
         self.split_S = tail[1] if tail else S                                   # K slices of the split launch (1: none)
@@ -445,7 +392,7 @@ def cases():
     for i, (kc, kw) in enumerate(((1, dict(cfg=32, M=19)), (9, dict(cfg=64, M=101)), (17, dict(cfg=128, M=165)), (25, dict(cfg=129, M=165)),
                                   (16, dict(split=1, M=70)), (57, dict(cfg=256, M=293)), (24, dict(cfg=128, M=165)), (8, dict(cfg=64, M=101)))):
         M = kw.pop("M")
-        add(BF16, M, CFGS[route(True, True, M, 1024, kc * 16, 16, "none", kw.get("cfg", 0), kw.get("split", 0))["cfg"]][1] + 75, kc, fp8=True, bias=True, res=i % 2 == 0, **kw)
+        add(BF16, M, plan(True, True, M, 1024, kc * 16, "none", kw.get("cfg", 0), kw.get("split", 0))["BN"] + 75, kc, fp8=True, bias=True, res=i % 2 == 0, **kw)
     add(BF16, 70, 128 + 76, 17, split=3, fp8=True, bias=True, res=True)
     add(BF16, 19, 128 + 76, 25, cfg=32, split=5, fp8=True, bias=True)
     add(BF16, 165, 128 + 64, 9, cfg=128, fp8=True, epi="swiglu")

@@ -115,6 +115,7 @@ def test_gemm_cases(case):
         assert_close(got, ref, dt, c.id)
     if c.norm:
         assert fused == 1, f"{c.id}: the reduce did not emit the norm"
+        assert fused == int(c.geom["fused"]), f"{c.id}: the launch reports fused = {fused}, the plan {c.geom['fused']}"
         assert bool((Y[:GUARD] == R.FILL).all()) and bool((Y[GUARD + M * N:] == R.FILL).all()), f"{c.id}: guard band of norm_out written"
         assert torch.equal(_bits(Y), _bits(again[2])), f"{c.id}: two launches differ in norm_out"
         y = Y[GUARD:GUARD + M * N].view(M, N)

@@ -33,7 +33,7 @@ def test_gemm_inputs_are_discriminating(case):
 
 
 def test_gemm_case_coverage():
-    """the case list reaches what it is named for (R.route restates launch_epi; k_slices / groups the stage and slice arithmetic)"""
+    """the case list reaches what it is named for (R.plan asks the dispatcher itself, svln_gemm_plan; k_slices / groups restate the stage and slice arithmetic)"""
     by_cfg = {}
     for c in R.CASES:
         by_cfg.setdefault(c.geom["cfg"], []).append(c)
