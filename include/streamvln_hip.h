@@ -203,6 +203,13 @@ int svln_set_mxfp4_batched(svln_engine* h, int enable);
  * only; vision, attention, norms, lm_head and the batch-1 decode GEMVs are unaffected (the latter have svln_set_fp8_decode).  Refused
  * while svln_set_mxfp4_batched is on. */
 int svln_set_fp8_gemm(svln_engine* h, int enable);
+/* Opt-in, default off: the instruction form of the svln_set_fp8_gemm products.  Off: v_mfma_f32_32x32x16_fp8_fp8 (the bf16 MFMA rate).  On:
+ * the block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 (v_mfma_scale_f32_16x16x128_f8f6f4 on the 8-phase 256x256 schedule, which e4m3 products
+ * may take only in this form) with e4m3 operands and neutral block scales (E8M0 127): twice the bf16 work per clock on the SAME e4m3
+ * bytes and per-row fp32 scales -- no numeric scheme changes, the products are the same sums in fp32.  No effect while svln_set_fp8_gemm is
+ * off.  bf16 engines only.  A call that would change the form fails while scheduler turns are in flight; a call that changes nothing
+ * always succeeds.  Captured batched decode graphs are keyed by the form. */
+int svln_set_fp8_scaled_mfma(svln_engine* h, int enable);
 /* Opt-in slow-memory pruning (BASELINE configs[3]; the reference has NO counterpart -- its memory is all num_history x 196 pooled
  * tokens, streamvln_eval.py:313-321 -- so this is pinned only by the project's own CPU restatement, oracle: prune_memory_tokens):
  * with keep_tokens > 0 a `<memory>` sentinel expands to the keep_tokens memory tokens least similar (cosine) to the mean memory
@@ -227,7 +234,8 @@ int svln_feature_cache_stats(svln_engine* h, int64_t* hits, int64_t* misses);
  * 129 = 128x128 with two in-workgroup K groups, 256 = 256x256 (bf16: 8-phase schedule), 258 = 256x256 with two K slices, 264 = 256x64
  * (M <= 256), 64 = 64x64, 32 = 32x128 (M <= 32); flag bits: 0x1000 row tiles fastest in the workgroup order, 0x10000 column tiles
  * fastest, 0x4000 stage-ring kernel for the 256x256 tile, 0x8000 32x32x16 form of the 8-phase schedule, 0x20000 direct 2-byte stores in the 8-phase
- * epilogue instead of the LDS-staged 16-byte row chunks.
+ * epilogue instead of the LDS-staged 16-byte row chunks, 0x40000 (svln_op_gemm_fp8 only; what the engine passes while
+ * svln_set_fp8_scaled_mfma is on) the block-scaled MFMA form of an e4m3 product, with which force_cfg 256 means the 8-phase schedule.
  * force_split: 0 = heuristic, S >= 1 = 256x128 tiles (256x64 with force_cfg 264) with S K-splits.
  * Every svln_op_gemm* call is refused (non-zero, svln_last_error) before any launch when A, W or C is null or A / W not 16-byte aligned, an
  * extent is negative, K, lda or ldw is not a multiple of the operand format's 16-byte chunk (4 fp32, 8 bf16, 16 e4m3 values), lda or
@@ -250,7 +258,7 @@ int svln_op_gemv(svln_engine* h, const void* W, int ldw, const void* x, const vo
                  void* y, int N, int K, int epi, int32_t* host_token);
 /* What the GEMM dispatcher does with one product, without launching it: needs no engine and no device.  The problem holds what the
  * dispatcher reads of a call: dtype SVLN_BF16 / SVLN_F32, epi as above, the extents, 0 / 1 flags for the optional pointers (fp8 = e4m3
- * operands with scales, has_ws / ws_elems = the split-K workspace in fp32 elements, has_zeros = the zero line, norm_out, norm_w, res), the
+ * operands with scales; fp8 = 2: on the block-scaled MFMAs, reported as fp8 = 2 in each launch, has_ws / ws_elems = the split-K workspace in fp32 elements, has_zeros = the zero line, norm_out, norm_w, res), the
  * fused-tail requests with their extents (rope: q heads, kv heads, rows; vitpack: frames, rows per frame, heads, head_dim) and force_cfg /
  * force_split.  The plan holds the one or two tile launches (tile: 0 32x128, 1 64x64, 2 128x128, 3 128x128 for more than one round,
  * 4 128x128 with two K groups, 5 256x128, 6 256x64, 7 256x256 stage ring, 8 256x256 8-phase, 9 its 32x32x16 form; the kernel variant;

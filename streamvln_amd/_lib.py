@@ -57,6 +57,7 @@ class SvlnGemmPlan(C.Structure):
 
 
 GEMM_TILES = ("skinny", "c64", "c128", "c128L", "c128K2", "c256", "c256n64", "big", "p8", "p8_32")      # svln_gemm_launch.tile
+GEMM_FORCE_FP8_SCALED = 0x40000        # force_cfg bit of svln_op_gemm_fp8: the block-scaled MFMA form (svln_set_fp8_scaled_mfma)
 GEMM_REDUCERS = (None, "epilogue", "rownorm", "qkv_rope", "vitpack")                                     # svln_gemm_launch.reducer
 
 
@@ -115,6 +116,7 @@ SIGNATURES = {
     "svln_probe_decode_layer": (_I, [_P, _I, C.POINTER(C.c_uint64), _I, _PI32]),
     "svln_set_fp8_decode": (_I, [_P, _I]),
     "svln_set_fp8_gemm": (_I, [_P, _I]),
+    "svln_set_fp8_scaled_mfma": (_I, [_P, _I]),
     "svln_set_mxfp4_decode": (_I, [_P, _I]),
     "svln_set_mxfp4_batched": (_I, [_P, _I]),
     "svln_set_memory_prune": (_I, [_P, _I]),

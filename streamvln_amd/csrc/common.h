@@ -94,6 +94,26 @@ template <> SVLN_DEV void mma_chunk<fp8_t>(const uint4& a, const uint4& b, f32x1
     acc = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a1, b1, acc, 0, 0, 0);
 }
 
+// The same e4m3 bytes on the block-scaled instructions (opt-in, svln_set_fp8_scaled_mfma): fp8s_t is the operand tag of that form.  A lane
+// holds 32 bytes per operand -- for the 32x32x64 form the two chunks (2s + h) and (2(s + 1) + h) that lane half h reads for the macro
+// steps s and s + 1 above, for the 16x16x128 form two chunks of lane group l >> 4 -- and again both operands use the same byte -> k
+// assignment, so the products pair up whatever k order the instruction gives the 32 bytes.  Format selectors 0 = e4m3 (OCP e4m3fn); the
+// E8M0 block scales are neutral (127 = 2^0 in every byte, opsel 0): the numeric scheme is that of mma_chunk<fp8_t>, at twice the rate.
+// Accumulator layouts: 32x32 as acc_row below, 16x16 as v_mfma_f32_16x16x32_bf16.
+struct fp8s_t { uint8_t v; };
+template <> struct Elt<fp8s_t> { static constexpr int PER_CHUNK = 16; static constexpr int BYTES = 1; };
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+constexpr int E8M0_ONE_X4 = 0x7f7f7f7f;
+SVLN_DEV i32x8 frag32(const u32x4& lo, const u32x4& hi) {
+    return i32x8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+}
+SVLN_DEV void mma_scaled_32x32x64(const i32x8& a, const i32x8& b, f32x16& acc) {
+    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, 0, 0, 0, E8M0_ONE_X4, 0, E8M0_ONE_X4);
+}
+SVLN_DEV void mma_scaled_16x16x128(const i32x8& a, const i32x8& b, f32x4& acc) {
+    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, 0, 0, 0, E8M0_ONE_X4, 0, E8M0_ONE_X4);
+}
+
 SVLN_DEV int acc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
 
 SVLN_DEV float wave_sum(float v) {

@@ -104,6 +104,7 @@ struct EngineBase {
     virtual void probe_decode_layer(int layer, unsigned long long* out, int max_wgs, int32_t* n_wgs) = 0;
     virtual void set_fp8_decode(int enable) = 0;
     virtual void set_fp8_gemm(int enable) = 0;
+    virtual void set_fp8_scaled_mfma(int enable) = 0;
     virtual void set_mxfp4_decode(int enable) = 0;
     virtual void set_mxfp4_batched(int enable) = 0;
     virtual bool op_gemm_fp8(const GemmArgs& a) = 0;
@@ -160,6 +161,7 @@ public:
     Q8 lm_head8; bool fp8_on = false, fp8_built = false;
     Q4 lm_head4; bool mx4_on = false, mx4_built = false;
     bool mx4b_on = false;            // opt-in MXFP4 weights in the batched (multi-env) decode step and the scheduler's lm_head: svln_set_mxfp4_batched
+    bool fp8_scaled_on = false;         // the e4m3 products run on the block-scaled MFMAs (svln_set_fp8_scaled_mfma)
     bool fp8_gemm_on = false; uint8_t* act8 = nullptr; float* act8_scale = nullptr;      // opt-in fp8 MFMA products: quantised activation rows
     T *patch_w, *patch_b, *pos_emb, *proj0_w, *proj0_b, *proj2_w, *proj2_b, *embed, *final_norm, *lm_head;
     std::vector<VLayer> vl;
@@ -205,7 +207,7 @@ public:
     bool use_graph = false;
     struct GraphSet { std::unordered_map<int, hipGraphExec_t> ex; };     // key: steps (whole batch) | 1000 (head of a probed step) | 2000 + steps (its tail)
     std::vector<GraphSet> graphs;
-    std::unordered_map<int, hipGraphExec_t> bgraphs;          // batched decode step: key = B | penalty << 8 | fp8 gemm << 9 | MXFP4 batched << 10
+    std::unordered_map<int, hipGraphExec_t> bgraphs;          // batched decode step: key = B | penalty << 8 | fp8 gemm << 9 | MXFP4 batched << 10 | scaled fp8 form << 11
     // per-turn truncation of the spliced rows (the reference's config.tokenizer_model_max_length, stream_video_vln.py:241-244); 0 = none
     int turn_row_limit = 0;
     // HF repetition penalty of the checkpoint's generation_config (1 = off): flags of the tokens generated in the current turn
@@ -1413,7 +1415,7 @@ public:
                 // gather + 28 layers + head for B decode rows -> d_tok_b, xn = final-norm rows.  With hipGraph replay on, the step of each
                 // (B, fp8, penalty) combination is captured once: every run-time value (page tables, positions, fed tokens) is in d_slots / d_tok_b.
                 if (use_graph) {
-                    const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0);
+                    const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0) | (fp8_gemm_on && fp8_scaled_on ? 2048 : 0);
                     auto it = bgraphs.find(key);
                     if (it == bgraphs.end())      // (a failed capture leaves no entry behind)
                         it = bgraphs.emplace(key, capture_graph([&] { decode_ops_batched(B, pen); })).first;
@@ -1813,6 +1815,15 @@ public:
         }
         fp8_gemm_on = true;
     }
+    // Opt-in: the instruction form of those products.  On: v_mfma_scale_f32_32x32x64_f8f6f4 (v_mfma_scale_f32_16x16x128_f8f6f4 on the 8-phase
+    // 256x256 tile) with neutral block scales -- the same e4m3 bytes, per-row scales and fp32 accumulation at twice the MFMA rate -- and
+    // the large-tile products may take the 8-phase schedule as bf16 ones do.  No effect while svln_set_fp8_gemm is off.
+    void set_fp8_scaled_mfma(int enable) override {
+        if ((enable != 0) == fp8_scaled_on) return;
+        REQUIRE(sizeof(T) == 2, "svln_set_fp8_scaled_mfma: the e4m3 products need the bf16 engine");
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_fp8_scaled_mfma cannot change while scheduler turns are in flight");
+        fp8_scaled_on = enable != 0;
+    }
     // C = A . W^T (+ epilogue) for an LLM linear: bf16 operands, or -- with svln_set_fp8_gemm -- the rows of A quantised on the fly
     // against the e4m3 copy of W
     // act8_src: the rows whose e4m3 copy act8 currently holds because the reduce that produced them also quantised them (the normalised
@@ -1825,6 +1836,7 @@ public:
             if (a.norm_out && a.norm_w && !a.norm_b && (size_t)a.N <= (size_t)H) { a.norm_q8 = act8; a.norm_q8_scale = act8_scale; }
             const void* nout = a.norm_out; const int rows = a.M;
             a.A = act8; a.lda = a.K; a.W = q.q; a.ldw = a.K; a.a_scale = act8_scale; a.w_scale = q.s;
+            if (fp8_scaled_on) a.force_cfg |= GEMM_FORCE_FP8_SCALED;
             const bool fused = launch_gemm<T>(st, a);
             if (fused && a.norm_q8) { act8_src = nout; act8_rows = rows; }      // the reduce ran after the product had consumed act8
             return fused;
@@ -2297,6 +2309,7 @@ int svln_probe_decode_layer(svln_engine* h, int layer, unsigned long long* out, 
 }
 int svln_set_fp8_decode(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_fp8_decode(enable); API_END }
 int svln_set_fp8_gemm(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_fp8_gemm(enable); API_END }
+int svln_set_fp8_scaled_mfma(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_fp8_scaled_mfma(enable); API_END }
 int svln_set_mxfp4_decode(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_mxfp4_decode(enable); API_END }
 int svln_set_mxfp4_batched(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_mxfp4_batched(enable); API_END }
 int svln_set_memory_prune(svln_engine* h, int keep_tokens) { API_BEGIN_H h->impl->set_memory_prune(keep_tokens); API_END }
@@ -2352,7 +2365,7 @@ int svln_gemm_plan(const svln_gemm_problem* q, svln_gemm_plan_out* out) {
         REQUIRE(v >= INT32_MIN && v <= INT32_MAX, "extent outside int32");
     GemmProblem p;
     p.elt_bytes = q->dtype == SVLN_F32 ? 4 : 2; p.epi = (int)q->epi; p.M = (int)q->M; p.N = (int)q->N; p.K = (int)q->K;
-    p.fp8 = q->fp8 != 0; p.has_ws = q->has_ws != 0; p.ws_elems = (size_t)q->ws_elems; p.has_zeros = q->has_zeros != 0;
+    p.fp8 = q->fp8 != 0; p.fp8_scaled = q->fp8 == 2 || (p.fp8 && (q->force_cfg & GEMM_FORCE_FP8_SCALED)); p.has_ws = q->has_ws != 0; p.ws_elems = (size_t)q->ws_elems; p.has_zeros = q->has_zeros != 0;
     p.norm_out = q->norm_out != 0; p.norm_w = q->norm_w != 0; p.res = q->res != 0;
     p.rope = q->rope != 0; p.rope_nq = (int)q->rope_nq; p.rope_nkv = (int)q->rope_nkv; p.rope_T = (int)q->rope_T;
     p.vitpack = q->vitpack != 0; p.vit_F = (int)q->vit_F; p.vit_S = (int)q->vit_S; p.vit_heads = (int)q->vit_heads; p.vit_head_dim = (int)q->vit_head_dim;
@@ -2364,7 +2377,7 @@ int svln_gemm_plan(const svln_gemm_problem* q, svln_gemm_plan_out* out) {
         const GemmLaunch& l = g.launch[i];
         const TileGeom& t = TILE_GEOM[l.tile];
         svln_gemm_launch& o = out->launch[i];
-        o.tile = l.tile; o.splitk = l.splitk; o.fp8 = l.fp8; o.ntw = l.ntw; o.vp = l.vp;
+        o.tile = l.tile; o.splitk = l.splitk; o.fp8 = l.fp8 ? (l.scaled ? 2 : 1) : 0; o.ntw = l.ntw; o.vp = l.vp;
         o.tile_base = l.tile_base; o.launch_tiles = l.launch_tiles; o.nsplit = l.nsplit; o.grid = l.wgs;
         o.block = t.threads; o.lds_bytes = t.lds_bytes; o.bm = t.bm; o.bn = t.bn;
         o.reducer = l.reducer; o.reducer_block = l.rblock; o.reduce_too_large = l.reduce_too_large;

@@ -742,6 +742,12 @@ class StreamVLNForCausalLM:
         envs) run as e4m3 MFMA products with per-row weight and activation scales.  bf16 engines only; reduced precision."""
         _check(self._lib.svln_set_fp8_gemm(self._h, int(enable)))
 
+    def set_fp8_scaled_mfma(self, enable: bool):
+        """Opt-in, default off: the products of set_fp8_gemm run on the block-scaled e4m3 MFMAs (neutral block scales: the same e4m3
+        bytes, per-row scales and fp32 sums at twice the MFMA rate) and may take the 8-phase 256x256 schedule.  No effect while
+        set_fp8_gemm is off; bf16 engines only; a change is refused while scheduler turns are in flight."""
+        _check(self._lib.svln_set_fp8_scaled_mfma(self._h, int(enable)))
+
     def sync(self):
         _check(self._lib.svln_sync(self._h))
 
