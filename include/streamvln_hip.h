@@ -147,7 +147,7 @@ int svln_get_hidden_batch(svln_engine* h, int slot, float* host_out, int max_row
 int svln_get_hidden(svln_engine* h, float* host_out, int max_rows, int32_t* n_rows);  /* final-norm hidden per generated token of the last generate */
 int svln_get_embeds(svln_engine* h, int env, int start_row, int n_rows, float* host_out);
 int svln_get_frame_feats(svln_engine* h, int start_row, int n_rows, float* host_out);
-int svln_get_top2(svln_engine* h, float* host_out2);
+int svln_get_top2(svln_engine* h, float* host_out2);       /* refused when the last token of the last turn came from a verify pass (svln_set_speculative) */
 /* prefill taps of svln_generate (single env): enable != 0 records the LAST row of the residual stream after every decoder layer of the
  * next prefills (svln_get_layer_taps: host_out [layers][hidden]); probe_layer >= 0 additionally records, for every row of the prefill,
  * the operands the products of that one layer actually saw (svln_get_layer_probe, which: 0 = x entering the layer, 1 = x leaving it,
@@ -210,6 +210,33 @@ int svln_set_fp8_gemm(svln_engine* h, int enable);
  * off.  bf16 engines only.  A call that would change the form fails while scheduler turns are in flight; a call that changes nothing
  * always succeeds.  Captured batched decode graphs are keyed by the form. */
 int svln_set_fp8_scaled_mfma(svln_engine* h, int enable);
+/* Opt-in, default off, no reference counterpart: draft-verified greedy decode -- several tokens per pass over the weights, the SAME ids as
+ * the plain greedy loop (exactly so on the fp32 engine; on the bf16 engine a verify row runs the batched step's products, whose summation
+ * order differs from the batch-1 GEMVs, so a near-tie arg-max can fall the other way, as between svln_generate and
+ * svln_generate_batch).  rows = 0 switches it off (today's behaviour, launch for launch); rows in {2, 4, 8} = rows per verify pass.  With
+ * c >= 1 tokens of a turn emitted and an armed draft D (svln_set_draft), a verify pass feeds the last emitted token at position
+ * L + c - 1 (row 0) and D[c + i - 1] at L + c - 1 + i (rows i >= 1) as the rows of one pass -- the batched decode step's products at
+ * B = rows, with an attention that ropes, appends and masks every row at its own position -- and takes the arg-max o_i of every row.
+ * o_0 is always emitted; o_i iff every earlier row was emitted without stopping and o_{i-1} == D[c + i - 1].  Stops are those of the
+ * plain loop (an EOS id, appended and not fed; max_new_tokens; a non-finite arg-max).  Fewer rows are used when the draft runs out, when
+ * max_new_tokens leaves room for fewer or when a row would reach max_positions; K / V rows of rejected positions lie at or beyond the
+ * env's kv length and are overwritten later.  Host policy: after the prefill one pass is enqueued if a guessed row exists; a further pass
+ * follows while every emitted id from index 1 on equals the draft and guessed rows remain; otherwise ordinary decode steps finish the turn.
+ * Refused: rows outside {0, 2, 4, 8}; rows * (q_heads / kv_heads) > 32 (the verify attention keeps the decode kernel's 32 query rows
+ * per kv head: Qwen2-7B, G = 7, takes rows <= 4); while svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm,
+ * svln_set_mxfp4_batched or svln_set_decode_persistent is on (a verify pass must compute each row in the numeric scheme of the single
+ * step it replaces), and each of those is refused while this mode is on; while scheduler turns are in flight.  A call that changes nothing
+ * always succeeds.  Captured decode graphs are dropped when it changes. */
+int svln_set_speculative(svln_engine* h, int rows);
+/* Arms a draft for env's next svln_generate / svln_turn / svln_generate_fixed: the caller's guess of the WHOLE id sequence of that turn,
+ * index 0 included (never needed: the prefill emits it), so the previous turn's output can be passed verbatim.  Consumed by that call
+ * whether or not it helped; n = 0 clears it; svln_reset_env / svln_kv_reset leave it armed.  Host-only: no GPU work, no synchronisation.
+ * Refused: an unknown env, n < 0, n > max_positions.  An id outside [0, vocab) ends the usable draft at its index.  Ignored (not an error)
+ * while the mode is off or a repetition penalty != 1 is set, and by svln_generate_batch / the scheduler (which leave it armed). */
+int svln_set_draft(svln_engine* h, int env, const int64_t* ids, int n);
+/* Counters since the last reset, over svln_generate / svln_turn / svln_generate_fixed: verify passes run, tokens they emitted, tokens
+ * emitted by ordinary decode steps.  The prefill's own token counts in none of them.  Any pointer may be null. */
+int svln_draft_stats(svln_engine* h, int64_t* verify_passes, int64_t* tokens_from_verify, int64_t* single_steps, int reset);
 /* Opt-in slow-memory pruning (BASELINE configs[3]; the reference has NO counterpart -- its memory is all num_history x 196 pooled
  * tokens, streamvln_eval.py:313-321 -- so this is pinned only by the project's own CPU restatement, oracle: prune_memory_tokens):
  * with keep_tokens > 0 a `<memory>` sentinel expands to the keep_tokens memory tokens least similar (cosine) to the mean memory
@@ -331,9 +358,23 @@ int svln_op_attention_vit(svln_engine* h, const void* qkv, int ld, int F, void* 
 /* one decode step of B in {1, 2, 4, 8} envs on layer 0, through the engine's own decode attention (fused RoPE of q / k, K / V append,
  * split-KV partials + merge).  Env b first gets pos[b] context rows (ctx_qkv + b * ctx_rows * ld, roped in place + appended as in
  * svln_op_attention_llm), then its un-roped q|k|v row qkv_new[b * ld] is decoded at position pos[b] -> out[b * o_stride].
- * B == 1 takes the single-env step, B > 1 the batched one. */
+ * B == 1 takes the single-env step, B > 1 the batched one.  B == 1 with ctx_qkv == NULL and pos[0] > 0: env 0 is NOT reset and nothing is
+ * re-appended -- the step runs on the pages and rows the last op left (which must cover the position), e.g. behind
+ * svln_op_attention_verify, whose appended rows it then reads. */
 int svln_op_attention_decode(svln_engine* h, int B, const void* ctx_qkv, int ld, int64_t ctx_rows, const int32_t* pos, const void* qkv_new,
                              void* out, int o_stride);
+/* the attention of one verify pass (svln_set_speculative) on layer 0 / env 0, through the engine's own verify attention.  Env 0 first gets
+ * ctx_rows context rows as in svln_op_attention_decode, then the `rows` (1 .. 8, rows * G <= 32) un-roped q|k|v rows qkv_new[i * ld] are
+ * verified at positions ctx_rows + i -> out[i * o_stride]: RoPE of q / k per row, K / V append of every row (the rows may straddle a
+ * page), per-row causal mask, split-KV partials + merge.  svln_op_kv_read / svln_op_set_pages / svln_op_fill_attn_state work with it as
+ * with the decode op. */
+int svln_op_attention_verify(svln_engine* h, int rows, const void* ctx_qkv, int ld, int ctx_rows, const void* qkv_new, void* out,
+                             int o_stride);
+/* one verify-step launch on caller-given host arrays: fed[rows] = the tokens the rows were fed (fed[0] is not read), cand[rows] = their
+ * arg-maxes, from `count` emitted tokens, with max_new and eos[n_eos <= 16] as svln_generate takes them.  *new_count, *done, the emitted
+ * ids in emitted[0 .. *new_count - count) (the rest of emitted[rows] = -3) and *next_token (the last emitted token; -3 when none). */
+int svln_op_verify_step(svln_engine* h, int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos,
+                        int n_eos, int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token);
 /* roped K and V rows of positions [start, start + n) of env's layer-0 KV pages -> host fp32 [n][kv_heads][128] each; env = -1 reads
  * the raw pools (position p = slot p % 64 of physical page p / 64).  The attention ops reset their envs on entry only, so this reads
  * what the last op wrote. */

@@ -119,6 +119,9 @@ SIGNATURES = {
     "svln_set_fp8_scaled_mfma": (_I, [_P, _I]),
     "svln_set_mxfp4_decode": (_I, [_P, _I]),
     "svln_set_mxfp4_batched": (_I, [_P, _I]),
+    "svln_set_speculative": (_I, [_P, _I]),
+    "svln_set_draft": (_I, [_P, _I, _PI64, _I]),
+    "svln_draft_stats": (_I, [_P, _PI64, _PI64, _PI64, _I]),
     "svln_set_memory_prune": (_I, [_P, _I]),
     "svln_op_memory_prune": (_I, [_P, _P, _I, _I, _PI32, _PF]),
     "svln_probe_reset": (_I, [_P]),
@@ -145,6 +148,8 @@ SIGNATURES = {
     "svln_op_attention_llm": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I]),
     "svln_op_attention_vit": (_I, [_P, _P, _I, _I, _P, _I]),
     "svln_op_attention_decode": (_I, [_P, _I, _P, _I, _I64, _PI32, _P, _P, _I]),
+    "svln_op_attention_verify": (_I, [_P, _I, _P, _I, _I, _P, _P, _I]),
+    "svln_op_verify_step": (_I, [_P, _I, _PI32, _PI32, _I, _I, _PI64, _I, _PI32, _PI32, _PI64, _PI32]),
     "svln_op_kv_read": (_I, [_P, _I, _I, _I, _PF, _PF]),
     "svln_op_llm_qkv_rope": (_I, [_P, _P, _I, _I, _P, _I, _PI32]),
     "svln_op_set_pages": (_I, [_P, _I, _PI32, _I]),

@@ -609,19 +609,223 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs p) {
     if (wave == 0 && h == 0) { dst[128] = m; dst[129] = l; }
 }
 
+// Draft-verify pass attention (svln_set_speculative): ONE env, R <= p.T consecutive query positions pos0 .. pos0 + R - 1 (pos0 = *dyn_pos,
+// R = *dyn_rows, both device scalars), rows rho = i * G + g <= 32 per kv head in the decode kernel's single 32-row tile.  Same workgroup
+// shape, page loads, LDS tiles and partial layout as attn_decode_kernel; what differs: row rho is roped at its OWN position pos0 + i, the
+// RoPE + K / V^T append covers all R new rows (the workgroup that owns a page patches the rows that fall into it: a pass may straddle a
+// page boundary and so two key splits), and the causal mask is per row (key <= pos0 + i).  A row of an earlier position sees no key of
+// the page a straddling pass opens: there the first key of the tile is NOT valid for it, so a row without a visible key keeps m = -inf,
+// l = 0, O = 0 (no exp2(-inf - -inf)) and still writes that partial -- the workspace may hold anything, and the merge gives it weight 0.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_verify_kernel(AttnArgs p) {
+    using G = AttnGeom<T, 128>;
+    constexpr int EPC = G::EPC, NT = 256;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (p.skip && *p.skip) return;
+    char* sK = smem;
+    char* sV = smem + G::K_TILE_BYTES;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int kh = blockIdx.x, z = blockIdx.y;
+    const int kt0 = z * p.tiles_per_split;
+    const int page0 = p.page_table[kt0];
+    const int pos0 = *p.dyn_pos;
+    const int R = min(*p.dyn_rows, p.T);
+    if (R <= 0) return;
+    const int kv_len = pos0 + R;
+    const int tiles = (kv_len + 63) >> 6;
+    if (kt0 >= tiles) return;                                   // the merge only reads splits below ceil(tiles / tiles_per_split)
+    const int kt_end = min(tiles, kt0 + p.tiles_per_split);
+    const size_t k_page_stride = (size_t)p.n_kv_total * 64 * 128 * sizeof(T);
+    const bool valid = r < R * p.G;
+    const int qi = valid ? r / p.G : 0, qg = valid ? r - qi * p.G : 0;
+    const int qpos = pos0 + qi;
+
+    // roped Q fragments of row rho = r (query position qi, q head kh*G + qg), identical in every wave
+    uint4 qf[G::HDC / 2];
+    {
+        const T* qrow = (const T*)p.Q + (size_t)qi * p.q_stride + (size_t)(kh * p.G + qg) * 128;
+#pragma unroll
+        for (int s = 0; s < G::HDC / 2; ++s) qf[s] = valid ? *(const uint4*)(qrow + (2 * s + h) * EPC) : zero_chunk();
+        const float* tab = p.rope_tab + (size_t)qpos * 128;
+#pragma unroll
+        for (int s = 0; s < G::HDC / 4; ++s) {
+            const int d0 = (2 * s + h) * EPC;
+            float x1[EPC], x2[EPC], o1[EPC], o2[EPC];
+            chunk_to_f32<T>(qf[s], x1);
+            chunk_to_f32<T>(qf[s + G::HDC / 4], x2);
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) {
+                const float c = tab[d0 + e], sn = tab[64 + d0 + e];
+                o1[e] = x1[e] * c - x2[e] * sn;
+                o2[e] = x2[e] * c + x1[e] * sn;
+            }
+            qf[s] = f32_to_chunk<T>(o1);
+            qf[s + G::HDC / 4] = f32_to_chunk<T>(o2);
+        }
+    }
+
+    const float scale2 = p.scale * 1.4426950408889634f;
+    f32x16 O;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) O[e] = 0.0f;
+    float m = -INFINITY, l = 0.0f;
+
+    for (int kt = kt0; kt < kt_end; ++kt) {
+        const int page = kt == kt0 ? page0 : p.page_table[kt];
+        const char* gK = (const char*)p.Kpool + (size_t)page * k_page_stride + (size_t)kh * 64 * 128 * sizeof(T);
+        const char* gV = (const char*)p.Vpool + (size_t)page * k_page_stride + (size_t)kh * 128 * 64 * sizeof(T);
+        constexpr int KL = 64 * G::HDC / NT, VL = 128 * G::VC / NT;
+        uint4 tk[KL], tv[VL];
+#pragma unroll
+        for (int u = 0; u < KL; ++u) tk[u] = *(const uint4*)(gK + (size_t)(tid + u * NT) * 16);
+#pragma unroll
+        for (int u = 0; u < VL; ++u) tv[u] = *(const uint4*)(gV + (size_t)(tid + u * NT) * 16);
+#pragma unroll
+        for (int u = 0; u < KL; ++u) {
+            const int q = tid + u * NT, row = q / G::HDC, c = q - row * G::HDC;
+            *(uint4*)(sK + k_off<G>(row, c)) = tk[u];
+        }
+#pragma unroll
+        for (int u = 0; u < VL; ++u) {
+            const int q = tid + u * NT, row = q / G::VC, c = q - row * G::VC;
+            if (sizeof(T) == 4) {
+                *(uint4*)(sV + v_off_f32(row, c)) = tv[u];
+            } else {
+                *(uint2*)(sV + v_off_bf16(row, 2 * c)) = make_uint2(tv[u].x, tv[u].y);
+                *(uint2*)(sV + v_off_bf16(row, 2 * c + 1)) = make_uint2(tv[u].z, tv[u].w);
+            }
+        }
+        if (kt >= (pos0 >> 6)) {          // (kt < tiles: the page holds at least one of the new positions)
+            __syncthreads();
+            // a wave per new row (i = w >> 6), lane d pairs (d, d + 64): rope k, append k / v^T to the pools, patch the LDS tiles
+            for (int w = tid; w < R * 64; w += NT) {
+                const int i = w >> 6, d = w & 63, pos = pos0 + i;
+                if ((pos >> 6) != kt) continue;
+                const int off = pos & 63;
+                const T* qkv_row = (const T*)p.Q + (size_t)i * p.q_stride;
+                const T* krow = qkv_row + (size_t)(p.nq_heads + kh) * 128;
+                const T* vrow = qkv_row + (size_t)(p.nq_heads + p.n_kv_total + kh) * 128;
+                const float* tab = p.rope_tab + (size_t)pos * 128;
+                const float k1 = to_f32(krow[d]), k2 = to_f32(krow[d + 64]);
+                const float c = tab[d], sn = tab[64 + d];
+                const T ko1 = from_f32<T>(k1 * c - k2 * sn), ko2 = from_f32<T>(k2 * c + k1 * sn);
+                const T v1 = vrow[d], v2 = vrow[d + 64];
+                T* gk = (T*)(const_cast<char*>(gK)) + (size_t)off * 128;
+                T* gv = (T*)(const_cast<char*>(gV));
+                gk[d] = ko1; gk[d + 64] = ko2;
+                gv[(size_t)d * 64 + off] = v1; gv[(size_t)(d + 64) * 64 + off] = v2;
+                *(T*)(sK + k_off<G>(off, d / EPC) + (d % EPC) * sizeof(T)) = ko1;
+                *(T*)(sK + k_off<G>(off, (d + 64) / EPC) + ((d + 64) % EPC) * sizeof(T)) = ko2;
+                if (sizeof(T) == 4) {
+                    *(T*)(sV + v_off_f32(d, off >> 2) + (off & 3) * 4) = v1;
+                    *(T*)(sV + v_off_f32(d + 64, off >> 2) + (off & 3) * 4) = v2;
+                } else {
+                    *(T*)(sV + v_off_bf16(d, off >> 2) + (off & 3) * 2) = v1;
+                    *(T*)(sV + v_off_bf16(d + 64, off >> 2) + (off & 3) * 2) = v2;
+                }
+            }
+        }
+        __syncthreads();
+
+        f32x16 S[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) S[j][e] = 0.0f;
+#pragma unroll
+        for (int s = 0; s < G::HDC / 2; ++s)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) mma_chunk<T>(*(const uint4*)(sK + k_off<G>(j * 32 + r, 2 * s + h)), qf[s], S[j]);
+        float mloc = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int key = kt * 64 + j * 32 + acc_row(e, lane);
+                const float sv = key <= qpos ? S[j][e] * scale2 : -INFINITY;        // per-row causal mask (qpos < kv_len)
+                S[j][e] = sv;
+                mloc = fmaxf(mloc, sv);
+            }
+        mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+        const float mnew = fmaxf(m, mloc);
+        float alpha = 1.0f, psum = 0.0f;
+        if (mnew == -INFINITY) {          // no visible key so far (both lanes of the row agree: mloc is the row's)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) S[j][e] = 0.0f;
+        } else {
+            alpha = fast_exp2(m - mnew);     // m = -inf -> 0
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const float pv = fast_exp2(S[j][e] - mnew);
+                    S[j][e] = pv;
+                    psum += pv;
+                }
+        }
+        l = l * alpha + psum;
+        m = mnew;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) O[e] *= alpha;
+        const int row = wave * 32 + r;                // this wave's 32 output channels
+        if (sizeof(T) == 2) {
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const int j = ks >> 1, b0 = 8 * (ks & 1);
+                const uint4 pf = make_uint4(pack_bf16x2(S[j][b0 + 0], S[j][b0 + 1]), pack_bf16x2(S[j][b0 + 2], S[j][b0 + 3]),
+                                            pack_bf16x2(S[j][b0 + 4], S[j][b0 + 5]), pack_bf16x2(S[j][b0 + 6], S[j][b0 + 7]));
+                const uint2 lo = *(const uint2*)(sV + v_off_bf16(row, 4 * ks + h));
+                const uint2 hi = *(const uint2*)(sV + v_off_bf16(row, 4 * ks + 2 + h));
+                O = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y)),
+                                                            __builtin_bit_cast(bf16x8, pf), O, 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const uint4 a = *(const uint4*)(sV + v_off_f32(row, j * 8 + 2 * g4 + h));
+                    O = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), S[j][4 * g4 + 0], O, 0, 0, 0);
+                    O = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), S[j][4 * g4 + 1], O, 0, 0, 0);
+                    O = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), S[j][4 * g4 + 2], O, 0, 0, 0);
+                    O = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), S[j][4 * g4 + 3], O, 0, 0, 0);
+                }
+        }
+        __syncthreads();
+    }
+    l += __shfl_xor(l, 32, 64);
+    if (!valid) return;
+    float* dst = p.part + (((size_t)z * p.n_kv_total + kh) * p.rows_pad + r) * (128 + ATTN_PART_PAD);
+#pragma unroll
+    for (int e4 = 0; e4 < 4; ++e4)
+        *(float4*)(dst + wave * 32 + acc_row(e4 * 4, lane)) = make_float4(O[4 * e4], O[4 * e4 + 1], O[4 * e4 + 2], O[4 * e4 + 3]);
+    if (wave == 0 && h == 0) { dst[128] = m; dst[129] = l; }
+}
+
 // merge split-KV partials: one wave per (kh, rho).  Pass 1: lane z owns split z (m_z, l_z) -> wave max / weights;
 // pass 2: lane d owns output channels d and d + 64 and sums the weighted partial rows (independent loads).
 // A wave per row; four rows per workgroup when there are many rows (prefill / ViT: thousands of single-wave workgroups are dispatch-bound),
 // one row per workgroup for the few rows of a decode step (spread over as many CUs as possible: 5.8 us against 9.4 with four per workgroup).
-template <typename T, int HD>
+// VERIFY (attn_verify_kernel's partials): *dyn_rows query positions from *dyn_pos on, so the keys reach *dyn_pos + rows, not GenCtl.kv_len
+template <typename T, int HD, bool VERIFY = false>
 __global__ __launch_bounds__(256) void attn_combine_kernel(AttnArgs p) {
     __shared__ float wsh_all[4][64];
     if (p.skip && *p.skip) return;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float* wsh = wsh_all[wave];         // written and read by this wave only
     const int rho = blockIdx.x * (blockDim.x >> 6) + wave, kh = blockIdx.y, env = blockIdx.z;
-    if (rho >= p.T * p.G) return;
-    const int kv_len = p.slots ? p.slots[env].pos + 1 : (p.dyn_kv_len ? *p.dyn_kv_len : p.kv_len);
+    int kv_len;
+    if constexpr (VERIFY) {
+        const int rows = min(*p.dyn_rows, p.T);
+        if (rho >= rows * p.G) return;
+        kv_len = *p.dyn_pos + rows;
+    } else {
+        if (rho >= p.T * p.G) return;
+        kv_len = p.slots ? p.slots[env].pos + 1 : (p.dyn_kv_len ? *p.dyn_kv_len : p.kv_len);
+    }
     const int tiles = (kv_len + 63) >> 6;
     const int nsplit = min(min(p.nsplit, 64), (tiles + p.tiles_per_split - 1) / p.tiles_per_split);
     const size_t split_stride = (size_t)p.n_kv_total * p.rows_pad * (HD + ATTN_PART_PAD);
@@ -701,12 +905,21 @@ template <typename T> void launch_attention_combine(hipStream_t s, const AttnArg
     if (head_dim == 128) hipLaunchKernelGGL((attn_combine_kernel<T, 128>), grid, block, 0, s, a);
     else if (head_dim == 72) hipLaunchKernelGGL((attn_combine_kernel<T, 72>), grid, block, 0, s, a);
 }
+// the verify pass of one env: a.T = the most rows a pass may carry (grid of the merge), *a.dyn_rows the rows of this pass
+template <typename T> void launch_attention_verify(hipStream_t s, const AttnArgs& a) {
+    using G = AttnGeom<T, 128>;
+    if (!(a.T >= 1 && a.T * a.G <= 32 && a.dyn_rows && a.dyn_pos && a.page_table && a.rows_pad >= 32 && a.fuse_rope_append))
+        throw std::runtime_error("verify attention: 1 <= rows, rows * G <= 32, device row count / position and a page table");
+    hipLaunchKernelGGL((attn_verify_kernel<T>), dim3(a.n_kv_total, a.nsplit), dim3(256), G::K_TILE_BYTES + G::V_TILE_BYTES, s, a);
+    hipLaunchKernelGGL((attn_combine_kernel<T, 128, true>), dim3(a.T * a.G, a.n_kv_total), dim3(64), 0, s, a);
+}
 template <typename T, int HD, int WAVES> static void attn_attr() {
     using G = AttnGeom<T, HD>;
     set_max_lds((const void*)attn_kernel<T, HD, WAVES>, G::K_TILE_BYTES + G::V_TILE_BYTES);
 }
 void attention_init_attrs() {
     set_max_lds((const void*)attn_decode_kernel<float>, AttnGeom<float, 128>::K_TILE_BYTES + AttnGeom<float, 128>::V_TILE_BYTES);
+    set_max_lds((const void*)attn_verify_kernel<float>, AttnGeom<float, 128>::K_TILE_BYTES + AttnGeom<float, 128>::V_TILE_BYTES);
     attn_attr<bf16, 128, 1>(); attn_attr<bf16, 128, 4>(); attn_attr<bf16, 72, 1>(); attn_attr<bf16, 72, 4>();
     attn_attr<float, 128, 1>(); attn_attr<float, 128, 4>(); attn_attr<float, 72, 1>(); attn_attr<float, 72, 4>();
     set_max_lds((const void*)attn_kernel<bf16, 72, 2, VitGroups<bf16>::KG, VitGroups<bf16>::PF>, GroupGeom<bf16, 72, VitGroups<bf16>::KG>::LDS);
@@ -717,6 +930,8 @@ template int attn_key_groups<bf16>(int);
 template int attn_key_groups<float>(int);
 template void launch_attention<bf16>(hipStream_t, const AttnArgs&, int, int);
 template void launch_attention<float>(hipStream_t, const AttnArgs&, int, int);
+template void launch_attention_verify<bf16>(hipStream_t, const AttnArgs&);
+template void launch_attention_verify<float>(hipStream_t, const AttnArgs&);
 template void launch_attention_combine<bf16>(hipStream_t, const AttnArgs&, int);
 template void launch_attention_combine<float>(hipStream_t, const AttnArgs&, int);
 

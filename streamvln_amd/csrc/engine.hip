@@ -107,6 +107,12 @@ struct EngineBase {
     virtual void set_fp8_scaled_mfma(int enable) = 0;
     virtual void set_mxfp4_decode(int enable) = 0;
     virtual void set_mxfp4_batched(int enable) = 0;
+    virtual void set_speculative(int rows) = 0;
+    virtual void set_draft(int env, const int64_t* ids, int n) = 0;
+    virtual void draft_stats(int64_t* verify_passes, int64_t* tokens_from_verify, int64_t* single_steps, int reset) = 0;
+    virtual void op_attention_verify(int rows, const void* ctx, int ld, int ctx_rows, const void* qkv_new, void* out, int o_stride) = 0;
+    virtual void op_verify_step(int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos, int n_eos,
+                                int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token) = 0;
     virtual bool op_gemm_fp8(const GemmArgs& a) = 0;
     virtual void set_memory_prune(int keep) = 0;
     virtual void op_memory_prune(const void* m, int n_rows, int keep, int32_t* out_idx, float* out_score) = 0;
@@ -200,6 +206,15 @@ public:
     std::vector<Env> envs;
     std::vector<int> free_pages;
     int n_generated = 0;
+    // Opt-in draft-verified greedy decode (svln_set_speculative; no reference counterpart: the emitted ids are those of the plain greedy
+    // loop).  A verify pass feeds the last emitted token and up to spec_rows - 1 guessed tokens as the rows of ONE pass over the weights
+    // (the batched step's products at B = spec_rows, the verify attention, the verify step) and keeps the longest confirmed prefix.
+    int spec_rows = 0;                       // 0 = off, else rows per verify pass (2, 4, 8)
+    std::vector<std::vector<int64_t>> drafts; std::vector<char> draft_armed;     // per env: the caller's guess of the next turn's ids (svln_set_draft)
+    int *d_draft = nullptr, *h_draft = nullptr;      // the armed draft of the running turn (device copy / pinned staging)
+    int *d_vctl = nullptr, *h_vctl = nullptr;        // [0] usable draft length, [1] rows of the pass, [2] passes, [3] tokens of the turn; d_vctl[8 ..] = fed rows
+    int64_t st_passes = 0, st_vtokens = 0, st_single = 0;
+    bool top2_stale = false;                 // the last token of the last turn came from a verify pass (which keeps no top-2 logits)
 
     // decode graph + probes.  The step graph holds the env's page-table pointer, so there is one set per env (a round-robin over several
     // envs through svln_generate replays instead of re-capturing); [0] = the whole step, [1] / [2] = the halves around the probed launch
@@ -416,6 +431,8 @@ public:
         (void)hipHostFree(h_src); (void)hipHostFree(h_token); (void)hipHostFree(h_top2);
         if (h_sel) (void)hipHostFree(h_sel);
         (void)hipHostFree(h_slots); (void)hipHostFree(h_tok_b);
+        if (h_draft) (void)hipHostFree(h_draft);
+        if (h_vctl) (void)hipHostFree(h_vctl);
         if (h_pen_rows) (void)hipHostFree(h_pen_rows);
         if (h_pen_ids) (void)hipHostFree(h_pen_ids);
         (void)hipStreamDestroy(st);
@@ -743,11 +760,16 @@ public:
     // splice + greedy generation -- svln_encode_frames, svln_kv_reset / svln_reset_env, svln_append_turn, svln_generate in that order.
     void turn(const svln_turn_args& a, int64_t* out, int cap, int32_t* n_out, int32_t* kv_len) override {
         Env& e = env_at(a.env);
-        REQUIRE(a.ids && a.n_ids >= 1 && out && n_out, "svln_turn: null / empty argument");
-        encode_frames(a.pixels, a.n_frames, a.pixels_on_device);
-        if (a.new_window) kv_reset(a.env);                      // past_key_values = None (streamvln_eval.py:349)
-        if (a.new_episode && e.n_embeds != 0) reset_env(a.env); // curr_t == 0: the env's inputs_embeds start over (stream_video_vln.py:396-401)
-        append_turn(a.env, a.ids, a.n_ids, 0, a.n_memory);
+        try {
+            REQUIRE(a.ids && a.n_ids >= 1 && out && n_out, "svln_turn: null / empty argument");
+            encode_frames(a.pixels, a.n_frames, a.pixels_on_device);
+            if (a.new_window) kv_reset(a.env);                      // past_key_values = None (streamvln_eval.py:349)
+            if (a.new_episode && e.n_embeds != 0) reset_env(a.env); // curr_t == 0: the env's inputs_embeds start over (stream_video_vln.py:396-401)
+            append_turn(a.env, a.ids, a.n_ids, 0, a.n_memory);
+        } catch (...) {
+            disarm_draft(a.env);          // an armed draft (svln_set_draft) is consumed by this call even when it fails before generating
+            throw;
+        }
         generate(a.env, a.max_new_tokens, a.eos_ids, a.n_eos, out, cap, n_out, false);
         if (kv_len) *kv_len = e.kv_len;
     }
@@ -955,6 +977,12 @@ public:
         a.slots = d_slots; a.batch = B; a.part_bstride = (size_t)nsplit_max * nkv * 32 * (128 + ATTN_PART_PAD);
         return a;
     }
+    // verify pass: `rows` = the most query positions a pass carries; this pass's count is d_vctl[1], its first position GenCtl.pos
+    AttnArgs verify_attn_args(const LLayer& L, const Env& e, int rows) {
+        AttnArgs a = decode_attn_args(L, e);
+        a.T = rows; a.dyn_rows = d_vctl + 1;
+        return a;
+    }
     void decode_attention(const AttnArgs& a) {
         launch_attention<T>(st, a, 128, 1);
         launch_attention_combine<T>(st, a, 128);
@@ -1017,6 +1045,7 @@ public:
     void set_decode_persistent(int enable) override {
         HIP_CHECK(hipStreamSynchronize(st));
         if (!enable) { if (persistent_on) drop_graphs(); persistent_on = false; return; }
+        refuse_while_speculative("svln_set_decode_persistent");
         if (!n_cus) { hipDeviceProp_t pr; HIP_CHECK(hipGetDeviceProperties(&pr, device)); n_cus = pr.multiProcessorCount; }
         DecodeLayerArgs a = layer_args(0);
         REQUIRE(decode_layer_supported<T>(a, n_cus), "persistent decode layer: this configuration is not supported (per-CU slices of hidden / inter / q|k|v "
@@ -1221,11 +1250,17 @@ public:
     // B >= 4: the projections run as 32-row MFMA products (gemm.hip CfgSkinny: the weight stream goes through LDS-DMA, the B rows
     // ride along; the batched GEMV is dot-product-issue bound from B = 4 up) and the split-K reduce of o_proj / down_proj also emits
     // the following RMSNorm.  B <= 2: the batched GEMV (HBM-bound there).
-    void decode_ops_batched(int B, bool pen = false) {
+    // verify != null (a verify pass of svln_set_speculative, B = spec_rows): the rows are one env's fed tokens (d_vctl + 8) at consecutive
+    // positions and the attention is the verify attention on that env's pages; the dense products and the lm_head are the same launches.
+    // A pass that uses fewer than B rows (d_vctl[1]) still carries B rows through the products: the unused rows are fed row 0's token,
+    // the verify attention writes no output for them, so from o_proj on they hold stale buffer contents -- the products are independent
+    // per row and the verify step never reads their arg-maxes.
+    void decode_ops_batched(int B, bool pen = false, const Env* verify = nullptr) {
         if (mx4b_on) { decode_ops_batched_mx4(B, pen); return; }
         const int qd = nq * 128;
         const bool mfma = B >= batched_mfma_min;
-        launch_gather_rows<T>(st, d_tok_b, embed, feats, x, B, H);
+        if (verify) launch_gather_rows<T>(st, d_vctl + 8, embed, feats, x, B, H, &d_ctl->done);
+        else launch_gather_rows<T>(st, d_tok_b, embed, feats, x, B, H);
         bool xn_ready = false;
         for (int i = 0; i < c.layers; ++i) {
             const LLayer& L = ll[i];
@@ -1233,7 +1268,8 @@ public:
             if (!xn_ready) launch_rmsnorm<T>(st, x, L.in_norm, xn, B, H, c.rms_eps);
             if (mfma) llm_gemm(gemm_args(xn, H, L.qkv_w, H, qkv, qkv_dim, L.qkv_b, nullptr, 0, 0, B, qkv_dim, H, EPI_NONE), L.qkv8);
             else launch_gemv_batched<T>(st, gemvb_args(L.qkv_w, H, xn, H, nullptr, L.qkv_b, nullptr, 0, qkv, qkv_dim, qkv_dim, H, EPI_NONE, B));
-            decode_attention(batched_decode_attn_args(L, B));
+            if (verify) launch_attention_verify<T>(st, verify_attn_args(L, *verify, B));
+            else decode_attention(batched_decode_attn_args(L, B));
             if (mfma) {
                 GemmArgs ao = gemm_args(attn, qd, L.o_w, qd, x, H, nullptr, x, H, 0, B, H, qd, EPI_NONE);
                 ao.norm_w = L.post_norm; ao.norm_out = xn; ao.norm_eps = c.rms_eps;
@@ -1250,6 +1286,69 @@ public:
             }
         }
         head_batched(x, B, pen);
+    }
+    // One verify pass of env e, enqueued only (GenCtl, the fed token and the draft live in device memory, so the pass is one fixed launch
+    // sequence per (env, rows) and replays as a graph): feed rows -> the batched step's products with the verify attention -> lm_head
+    // arg-max of every row (d_tok_b) -> verify step.  Every launch that writes state a later step reads is a no-op once done is set.
+    void verify_pass_ops(const Env& e) {
+        launch_verify_feed(st, d_ctl, d_token, d_draft, d_vctl, d_vctl + 8, spec_rows, c.max_positions);
+        decode_ops_batched(spec_rows, false, &e);           // (its head leaves the final-norm rows in xn)
+        launch_verify_step<T>(st, d_vctl + 8, d_tok_b, d_vctl + 1, spec_rows, d_ctl, d_eos, d_out_ids, d_token, xn, hid_tap, H, HID_TAP_ROWS, d_vctl + 2);
+    }
+    void verify_pass(const Env& e, int env) {
+        if (!use_graph) { verify_pass_ops(e); return; }
+        GraphSet& gs = graphs[env];
+        const int key = 3000 + spec_rows;
+        auto it = gs.ex.find(key);
+        if (it == gs.ex.end()) it = gs.ex.emplace(key, capture_graph([&] { verify_pass_ops(e); })).first;
+        HIP_CHECK(hipGraphLaunch(it->second, st));
+    }
+    void set_speculative_buffers() {
+        if (d_draft) return;
+        d_draft = dalloc<int>((size_t)c.max_positions + 8, true);
+        d_vctl = dalloc<int>(16, true);
+        HIP_CHECK(hipHostMalloc((void**)&h_draft, ((size_t)c.max_positions + 8) * sizeof(int)));
+        HIP_CHECK(hipHostMalloc((void**)&h_vctl, 16 * sizeof(int)));
+        for (int k = 0; k < 16; ++k) h_vctl[k] = 0;
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    bool spec_exclusive_on() const { return fp8_on || mx4_on || fp8_gemm_on || mx4b_on || persistent_on; }
+    void set_speculative(int rows) override {
+        if (rows == spec_rows) return;         // nothing changes
+        REQUIRE(rows == 0 || rows == 2 || rows == 4 || rows == 8, "svln_set_speculative: rows must be 0 (off), 2, 4 or 8");
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_speculative cannot change while scheduler turns are in flight");
+        if (rows > 0) {
+            REQUIRE(rows * (nq / nkv) <= 32, "svln_set_speculative: rows * (q_heads / kv_heads) must be <= 32 (the verify attention keeps 32 query rows per kv head)");
+            // a verify pass must compute each row in the numeric scheme of the single step it replaces
+            REQUIRE(!spec_exclusive_on(), "svln_set_speculative: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, "
+                                          "svln_set_fp8_gemm, svln_set_mxfp4_batched, svln_set_decode_persistent); switch it off first");
+            set_speculative_buffers();
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+        drop_graphs();
+        spec_rows = rows;
+    }
+    bool disarm_draft(int env) {
+        if (env < 0 || env >= (int)draft_armed.size() || !draft_armed[env]) return false;
+        draft_armed[env] = 0;
+        return true;
+    }
+    void refuse_while_speculative(const char* who) {
+        REQUIRE(spec_rows == 0, std::string(who) + ": draft-verified decode is on (svln_set_speculative); switch it off first");
+    }
+    void set_draft(int env, const int64_t* ids, int n) override {
+        env_at(env);
+        REQUIRE(n >= 0 && n <= c.max_positions, "svln_set_draft: 0 <= n <= max_positions");
+        REQUIRE(n == 0 || ids, "svln_set_draft: null ids");
+        if (drafts.empty()) { drafts.resize(envs.size()); draft_armed.assign(envs.size(), 0); }
+        drafts[env].assign(ids, ids + n);
+        draft_armed[env] = n > 0;
+    }
+    void draft_stats(int64_t* verify_passes, int64_t* tokens_from_verify, int64_t* single_steps, int reset) override {
+        if (verify_passes) *verify_passes = st_passes;
+        if (tokens_from_verify) *tokens_from_verify = st_vtokens;
+        if (single_steps) *single_steps = st_single;
+        if (reset) st_passes = st_vtokens = st_single = 0;
     }
     bool taps_on = true;
     void tap_copy(const T* row, int token_idx, int slot) {       // parity tap: hid_tap[min(token,7)][slot]
@@ -1555,6 +1654,7 @@ public:
     // enqueued past the end of the generation are no-ops (every kernel checks the done flag).
     void generate(int env, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, bool fixed) override {
         Env& e = env_at(env);
+        const bool had_draft = disarm_draft(env);      // consumed by this call whether it helps, is ignored or the call fails
         REQUIRE(weights_missing() == 0, g_err);
         const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
         REQUIRE(Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
@@ -1572,7 +1672,22 @@ public:
                 eos_valid = true;
             }
         }
+        // the env's armed draft is consumed by this call whether or not it helps; usable: the mode is on, no repetition penalty (its flags
+        // change the logits token by token), ids in the vocabulary (the first one outside ends the draft) and a guess beyond index 0
+        int dlen = 0;
+        if (had_draft) {
+            if (spec_rows > 0 && rep_penalty == 1.0f) {
+                const std::vector<int64_t>& D = drafts[env];
+                while (dlen < (int)D.size() && D[dlen] >= 0 && D[dlen] < V) { h_draft[dlen] = (int)D[dlen]; ++dlen; }
+            }
+        }
+        const bool spec = dlen >= 2;
         ensure_pages(e, L);
+        if (spec) {
+            h_vctl[0] = dlen; h_vctl[1] = h_vctl[2] = h_vctl[3] = 0;
+            HIP_CHECK(hipMemcpyAsync(d_draft, h_draft, (size_t)dlen * sizeof(int), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(d_vctl, h_vctl, 4 * sizeof(int), hipMemcpyHostToDevice, st));
+        }
         // the first decode step feeds token 0 at position L: pos / kv_len advance when the arg-max step appends without stopping
         h_ctl->pos = L - 1; h_ctl->kv_len = L; h_ctl->done = 0; h_ctl->count = 0; h_ctl->max_new = limit; h_ctl->n_eos = n_eos;
         h_ctl->pad0 = h_ctl->pad1 = 0;
@@ -1587,7 +1702,46 @@ public:
         int enq = 1;                      // tokens whose arg-max step has been enqueued
         int n = 0;
         bool done = false, decoded = false;
-        while (true) {
+        int vtokens = 0;                  // tokens of this turn that verify passes emitted
+        if (spec) {
+            // Verify passes while the draft holds: with cnt tokens emitted a pass carries rows_at(cnt) rows (verify_feed_kernel computes the
+            // same number on the device); one is enqueued while the draft has a guess for the next token (cnt < dlen), even where max_new
+            // or max_positions cut it to one row.  After each the host reads the ids: a further pass follows only if every id from index 1
+            // on equals the draft, else the single steps below take over.
+            auto rows_at = [&](int cnt) {
+                int r = spec_rows;
+                r = std::min(r, std::max(dlen - cnt + 1, 1));
+                r = std::min(r, limit - cnt);
+                r = std::min(r, c.max_positions - (L + cnt - 1));
+                return r;
+            };
+            int cnt = 1;
+            while (!done && cnt < dlen && rows_at(cnt) >= 1) {
+                const int r = rows_at(cnt);
+                ensure_pages(e, L + cnt - 1 + r);              // row i writes position L + cnt - 1 + i
+                verify_pass(e, env);
+                decoded = true;
+                HIP_CHECK(hipEventRecord(ph_ev[4], st));
+                HIP_CHECK(hipMemcpyAsync(h_ctl, d_ctl, sizeof(GenCtl), hipMemcpyDeviceToHost, st));
+                HIP_CHECK(hipMemcpyAsync(h_out_ids, d_out_ids, (size_t)(cnt + r) * sizeof(int), hipMemcpyDeviceToHost, st));
+                HIP_CHECK(hipMemcpyAsync(h_vctl, d_vctl, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+                HIP_CHECK(hipStreamSynchronize(st));
+                LAUNCH_CHECK("generate (verify pass)");
+                n = h_ctl->count;
+                done = h_ctl->done != 0;
+                REQUIRE(n >= cnt && n <= cnt + r, "generation state out of range");
+                for (int k = 0; k < n; ++k)
+                    REQUIRE(h_out_ids[k] >= 0 && h_out_ids[k] < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+                bool held = n > cnt;
+                for (int k = 1; k < n && k < dlen; ++k) held = held && h_out_ids[k] == h_draft[k];
+                cnt = n;
+                if (!held) break;
+            }
+            enq = cnt;
+            vtokens = h_vctl[3];
+            st_passes += h_vctl[2];
+        }
+        while (!done) {
             int steps = limit - enq;
             if (steps > RUN_AHEAD) steps = RUN_AHEAD;
             if (steps > c.max_positions - (L + enq - 1)) steps = c.max_positions - (L + enq - 1);       // step k feeds position L + enq - 1
@@ -1629,6 +1783,8 @@ public:
             if (decoded) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[3], ph_ev[4])); ph_ms[2] += t; }
         }
         n_generated = n;
+        st_vtokens += vtokens; st_single += n - 1 - vtokens;
+        top2_stale = vtokens > 0 && n - 1 - vtokens == 0;
         *n_out = n;
     }
 
@@ -1690,7 +1846,10 @@ public:
         REQUIRE(start >= 0 && n >= 0 && start + n <= n_feat_frames * otok, "feats range");
         read_rows_f32(feats + (size_t)start * H, (size_t)n * H, out);
     }
-    void get_top2(float* out) override { out[0] = h_top2[0]; out[1] = h_top2[1]; }
+    void get_top2(float* out) override {
+        REQUIRE(!top2_stale, "svln_get_top2: the last token of the last turn came from a verify pass (svln_set_speculative), which keeps no top-2 logits");
+        out[0] = h_top2[0]; out[1] = h_top2[1];
+    }
     void sync() override { HIP_CHECK(hipStreamSynchronize(st)); }
     void set_graph(int enable) override { use_graph = enable != 0; if (!use_graph) drop_graphs(); }
     void ensure_prune_scratch() {
@@ -1745,6 +1904,7 @@ public:
     }
     void set_fp8_decode(int enable) override {
         if (!enable) { if (fp8_on) drop_graphs(); fp8_on = false; return; }
+        refuse_while_speculative("svln_set_fp8_decode");
         REQUIRE(!mx4_on, "svln_set_fp8_decode: the MXFP4 decode weights are on (svln_set_mxfp4_decode); switch them off first");
         REQUIRE(!mx4b_on, "svln_set_fp8_decode: the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
         build_fp8_weights();
@@ -1779,6 +1939,7 @@ public:
     }
     void set_mxfp4_decode(int enable) override {
         if (!enable) { if (mx4_on) drop_graphs(); mx4_on = false; return; }
+        refuse_while_speculative("svln_set_mxfp4_decode");
         REQUIRE(!fp8_on, "svln_set_mxfp4_decode: the e4m3 decode weights are on (svln_set_fp8_decode); switch them off first");
         build_mxfp4_weights();
         if (!mx4_on) drop_graphs();
@@ -1793,6 +1954,7 @@ public:
         // an env must not change scheme in the middle of a turn, in either direction
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_mxfp4_batched cannot change while scheduler turns are in flight");
         if (!enable) { drop_graphs(); mx4b_on = false; return; }
+        refuse_while_speculative("svln_set_mxfp4_batched");
         REQUIRE(sizeof(T) == 2, "svln_set_mxfp4_batched: MXFP4 weights need the bf16 engine");
         REQUIRE(!fp8_on, "svln_set_mxfp4_batched: the e4m3 decode weights are on (svln_set_fp8_decode); switch them off first");
         REQUIRE(!fp8_gemm_on, "svln_set_mxfp4_batched: the e4m3 MFMA products are on (svln_set_fp8_gemm); switch them off first");
@@ -1806,6 +1968,7 @@ public:
     // Half the operand bytes per k through HBM / L2 / LDS.  Vision, attention, norms and the lm_head stay bf16.
     void set_fp8_gemm(int enable) override {
         if (!enable) { fp8_gemm_on = false; return; }
+        refuse_while_speculative("svln_set_fp8_gemm");
         REQUIRE(!mx4b_on, "svln_set_fp8_gemm: the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
         build_fp8_weights();
         if (!act8) {
@@ -2127,12 +2290,16 @@ public:
         REQUIRE(pos && qkv_new && out, "null pointer");
         REQUIRE(ld >= qkv_dim && o_stride >= nq * 128, "row strides");
         const LLayer& L = ll[0];
+        // B == 1 with null context rows and pos > 0: the step runs on env 0 AS THE LAST OP LEFT IT (no reset, nothing re-appended): its
+        // pages must already cover the position.  So a step can follow a verify pass and read the rows that pass appended.
+        const bool keep = B == 1 && !ctx && pos[0] > 0;
         for (int b = 0; b < B; ++b) {
-            REQUIRE(pos[b] >= 0 && pos[b] < c.max_positions && pos[b] <= ctx_rows, "decode position out of range");
-            REQUIRE(pos[b] == 0 || ctx, "null context rows");
-            reset_env(b);
+            REQUIRE(pos[b] >= 0 && pos[b] < c.max_positions && (keep || pos[b] <= ctx_rows), "decode position out of range");
+            REQUIRE(pos[b] == 0 || ctx || keep, "null context rows");
+            if (!keep) reset_env(b);
         }
-        for (int b = 0; b < B; ++b) {
+        if (keep) REQUIRE(pos[0] < env_at(0).n_pages * PAGE, "null context rows: env 0 holds no page for this position (run the op that fills it first)");
+        for (int b = 0; b < B && !keep; ++b) {
             Env& e = env_at(b);
             op_env_begin(b, pos[b] + 1);
             if (pos[b] > 0) op_rope_append(e, L, (char*)const_cast<void*>(ctx) + (size_t)b * ctx_rows * ld * sizeof(T), ld, pos[b], 0);
@@ -2153,6 +2320,67 @@ public:
                                    hipMemcpyDeviceToDevice, st));
         sync();
         LAUNCH_CHECK("op_attention_decode");
+    }
+    // one verify pass's attention on layer 0 / env 0 through verify_attn_args + launch_attention_verify, as a verify pass runs it: env 0
+    // first gets ctx_rows context rows (roped in place + appended like op_attention_llm), then the `rows` un-roped q|k|v rows qkv_new are
+    // verified at positions ctx_rows .. ctx_rows + rows - 1 (RoPE per row, K / V append of every row, per-row mask, merge)
+    void op_attention_verify(int rows, const void* ctx, int ld, int ctx_rows, const void* qkv_new, void* out, int o_stride) override {
+        REQUIRE(rows >= 1 && rows <= MAXB && rows * (nq / nkv) <= 32, "rows must be 1 .. 8 with rows * (q_heads / kv_heads) <= 32");
+        REQUIRE(qkv_new && out, "null pointer");
+        REQUIRE(ld >= qkv_dim && o_stride >= nq * 128, "row strides");
+        REQUIRE(ctx_rows >= 0 && ctx_rows + rows <= c.max_positions, "verify positions out of range");
+        REQUIRE(ctx_rows == 0 || ctx, "null context rows");
+        set_speculative_buffers();
+        const LLayer& L = ll[0];
+        Env& e = env_at(0);
+        op_env_begin(0, ctx_rows + rows);
+        if (ctx_rows > 0) op_rope_append(e, L, const_cast<void*>(ctx), ld, ctx_rows, 0);
+        HIP_CHECK(hipMemcpy2DAsync(qkv, (size_t)qkv_dim * sizeof(T), qkv_new, (size_t)ld * sizeof(T), (size_t)qkv_dim * sizeof(T), rows,
+                                   hipMemcpyDeviceToDevice, st));
+        h_ctl->pos = ctx_rows; h_ctl->kv_len = ctx_rows + 1; h_ctl->done = 0; h_ctl->count = 0; h_ctl->max_new = 0; h_ctl->n_eos = 0;
+        h_ctl->pad0 = h_ctl->pad1 = 0;
+        HIP_CHECK(hipMemcpyAsync(d_ctl, h_ctl, sizeof(GenCtl), hipMemcpyHostToDevice, st));
+        h_vctl[0] = 0; h_vctl[1] = rows; h_vctl[2] = h_vctl[3] = 0;
+        HIP_CHECK(hipMemcpyAsync(d_vctl, h_vctl, 4 * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_attention_verify<T>(st, verify_attn_args(L, e, rows));
+        HIP_CHECK(hipMemcpy2DAsync(out, (size_t)o_stride * sizeof(T), attn, (size_t)nq * 128 * sizeof(T), (size_t)nq * 128 * sizeof(T), rows,
+                                   hipMemcpyDeviceToDevice, st));
+        sync();
+        LAUNCH_CHECK("op_attention_verify");
+    }
+    // one verify-step launch on caller-given row tokens and arg-maxes, from `count` emitted tokens (host arrays)
+    void op_verify_step(int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos, int n_eos,
+                        int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token) override {
+        REQUIRE(rows >= 1 && rows <= MAXB, "rows must be 1 .. 8");
+        REQUIRE(fed && cand && new_count && done && emitted && next_token, "null pointer");
+        REQUIRE(count >= 0 && count + rows <= c.max_positions, "count out of range");
+        REQUIRE(n_eos >= 0 && n_eos <= 16 && (n_eos == 0 || eos), "0 .. 16 eos ids");
+        set_speculative_buffers();
+        sync();
+        eos_valid = false;                 // d_eos is rewritten here
+        int he[16];
+        for (int k = 0; k < n_eos; ++k) he[k] = eos[k] >= 0 && eos[k] < V ? (int)eos[k] : -2;
+        if (n_eos) HIP_CHECK(hipMemcpy(d_eos, he, (size_t)n_eos * sizeof(int), hipMemcpyHostToDevice));
+        int hv[16] = {0};
+        hv[1] = rows;
+        for (int i = 0; i < rows; ++i) hv[8 + i] = fed[i];
+        HIP_CHECK(hipMemcpy(d_vctl, hv, sizeof(hv), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_tok_b, cand, (size_t)rows * sizeof(int), hipMemcpyHostToDevice));
+        const int tok0 = -3;
+        HIP_CHECK(hipMemcpy(d_token, &tok0, sizeof(int), hipMemcpyHostToDevice));
+        GenCtl g; g.pos = count; g.kv_len = count + 1; g.done = 0; g.count = count; g.max_new = max_new; g.n_eos = n_eos; g.pad0 = g.pad1 = 0;
+        HIP_CHECK(hipMemcpy(d_ctl, &g, sizeof(g), hipMemcpyHostToDevice));
+        launch_verify_step<T>(st, d_vctl + 8, d_tok_b, d_vctl + 1, rows, d_ctl, d_eos, d_out_ids, d_token, xn, hid_tap, H, HID_TAP_ROWS, d_vctl + 2);
+        sync();
+        LAUNCH_CHECK("op_verify_step");
+        HIP_CHECK(hipMemcpy(&g, d_ctl, sizeof(g), hipMemcpyDeviceToHost));
+        REQUIRE(g.count >= count && g.count <= count + rows, "verify step: count out of range");
+        std::vector<int> ids(rows, -3);
+        if (g.count > count) HIP_CHECK(hipMemcpy(ids.data(), d_out_ids + count, (size_t)(g.count - count) * sizeof(int), hipMemcpyDeviceToHost));
+        for (int i = 0; i < rows; ++i) emitted[i] = i < g.count - count ? ids[i] : -3;
+        int tk = 0;
+        HIP_CHECK(hipMemcpy(&tk, d_token, sizeof(int), hipMemcpyDeviceToHost));
+        *new_count = g.count; *done = g.done; *next_token = tk;
     }
     void op_attention_vit(const void* qkv_buf, int ld, int F, void* out, int o_stride) override {
         REQUIRE(F >= 1 && F <= c.max_frames, "frames");
@@ -2312,6 +2540,11 @@ int svln_set_fp8_gemm(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_fp8
 int svln_set_fp8_scaled_mfma(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_fp8_scaled_mfma(enable); API_END }
 int svln_set_mxfp4_decode(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_mxfp4_decode(enable); API_END }
 int svln_set_mxfp4_batched(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_mxfp4_batched(enable); API_END }
+int svln_set_speculative(svln_engine* h, int rows) { API_BEGIN_H h->impl->set_speculative(rows); API_END }
+int svln_set_draft(svln_engine* h, int env, const int64_t* ids, int n) { API_BEGIN_H h->impl->set_draft(env, ids, n); API_END }
+int svln_draft_stats(svln_engine* h, int64_t* verify_passes, int64_t* tokens_from_verify, int64_t* single_steps, int reset) {
+    API_BEGIN_H h->impl->draft_stats(verify_passes, tokens_from_verify, single_steps, reset); API_END
+}
 int svln_set_memory_prune(svln_engine* h, int keep_tokens) { API_BEGIN_H h->impl->set_memory_prune(keep_tokens); API_END }
 int svln_op_memory_prune(svln_engine* h, const void* mem, int n_rows, int keep, int32_t* out_idx, float* out_score) {
     API_BEGIN_H h->impl->op_memory_prune(mem, n_rows, keep, out_idx, out_score); API_END
@@ -2467,6 +2700,13 @@ int svln_op_attention_vit(svln_engine* h, const void* qkv, int ld, int F, void* 
 int svln_op_attention_decode(svln_engine* h, int B, const void* ctx_qkv, int ld, int64_t ctx_rows, const int32_t* pos, const void* qkv_new, void* out,
                              int o_stride) {
     API_BEGIN_H h->impl->op_attention_decode(B, ctx_qkv, ld, ctx_rows, pos, qkv_new, out, o_stride); API_END
+}
+int svln_op_attention_verify(svln_engine* h, int rows, const void* ctx_qkv, int ld, int ctx_rows, const void* qkv_new, void* out, int o_stride) {
+    API_BEGIN_H h->impl->op_attention_verify(rows, ctx_qkv, ld, ctx_rows, qkv_new, out, o_stride); API_END
+}
+int svln_op_verify_step(svln_engine* h, int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos, int n_eos,
+                        int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token) {
+    API_BEGIN_H h->impl->op_verify_step(rows, fed, cand, count, max_new, eos, n_eos, new_count, done, emitted, next_token); API_END
 }
 int svln_op_kv_read(svln_engine* h, int env, int start, int n, float* k_out, float* v_out) { API_BEGIN_H h->impl->op_kv_read(env, start, n, k_out, v_out); API_END }
 int svln_op_llm_qkv_rope(svln_engine* h, const void* x, int T, int P, void* q_out, int q_stride, int32_t* fused) {

@@ -146,6 +146,15 @@ struct GenCtl {
 // pen_flags (optional): the emitted token's byte is set (repetition penalty of the following steps)
 void launch_argmax_step(hipStream_t s, const float* part_val, const int* part_idx, int n, int* out_token, float* out_top, GenCtl* ctl,
                         const int* eos, int* out_ids, uint8_t* pen_flags = nullptr);
+// Draft-verified greedy decode (svln_set_speculative; misc.hip).  launch_verify_feed builds the rows of the next verify pass from GenCtl,
+// the last token and the device copy of the draft: fed[0 .. rows) and vctl[1] = rows used (vctl[0] = usable draft length, set by the
+// host).  launch_verify_step applies the verify rule to the rows' arg-maxes `cand`: appends the accepted tokens to out_ids, advances
+// GenCtl as that many launch_argmax_step calls would, sets *out_token, copies the final-norm rows xn[i] of the emitted tokens to
+// hid_tap[min(token index, tap_cap - 1)] and adds to stats[0] (passes run) / stats[1] (tokens emitted).  Both are no-ops once done is set.
+void launch_verify_feed(hipStream_t s, const GenCtl* ctl, const int* token, const int* draft, int* vctl, int* fed, int rows, int max_positions);
+template <typename T> void launch_verify_step(hipStream_t s, const int* fed, const int* cand, const int* n_rows, int max_rows, GenCtl* ctl,
+                                              const int* eos, int* out_ids, int* out_token, const void* xn, void* hid_tap, int H, int tap_cap,
+                                              int* stats);
 // flags[ids[k]] = value for k < *count (count: device scalar) or k < n_host when count is null; ids < 0 are skipped
 void launch_set_flags(hipStream_t s, uint8_t* flags, const int* ids, const int* count, int n_host, int value);
 
@@ -186,8 +195,13 @@ struct AttnArgs {
     int batch;
     const int* skip;              // optional device flag: decode attention / combine are no-ops when *skip != 0
     int key_groups;               // > 1: split-KV inside the workgroup (64 query rows x key groups, merged through LDS); nsplit > 1 on top: the merge writes the split's partial row
+    const int* dyn_rows;          // verify pass only (launch_attention_verify): device scalar, query positions of this pass (<= T)
 };
 template <typename T> void launch_attention(hipStream_t s, const AttnArgs& a, int head_dim, int waves);
+// Draft-verify pass of ONE env (svln_set_speculative): min(*dyn_rows, T) query positions from *dyn_pos on, Q = their un-roped q|k|v rows
+// [T][q_stride]; RoPE at each row's own position, K / V^T append of every row, per-row causal mask, decode split-KV partials + merge
+// -> O [T][o_stride].  T * G <= 32; a no-op when *skip != 0 or *dyn_rows <= 0.  The caller owns the pages of every position written.
+template <typename T> void launch_attention_verify(hipStream_t s, const AttnArgs& a);
 template <typename T> void launch_attention_combine(hipStream_t s, const AttnArgs& a, int head_dim);
 template <typename T> int attn_key_groups(int head_dim);       // the key-group count launch_attention<T> is built for at this head dim (AttnArgs::key_groups)
 

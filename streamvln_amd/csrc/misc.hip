@@ -235,6 +235,76 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const int* src, const 
 }
 
 
+// ------------------------------------------------------------------------------ draft-verified greedy decode
+// The rows of the next verify pass (svln_set_speculative).  c = tokens emitted so far, row 0 = the last emitted token at position
+// GenCtl.pos, row i >= 1 = draft[c + i - 1] at pos + i.  Rows used: up to `rows`, fewer when the draft runs out, when max_new leaves room
+// for fewer tokens or when pos + i would reach max_positions; the FED TOKENS of the rows past them repeat row 0's (the dense products
+// always carry `rows` rows; the attention and the verify step read vctl[1], so the attention output of those rows is never written and
+// what they carry from o_proj on is stale buffer contents, which nothing reads).  vctl: [0] = usable draft length (host), [1] = rows used (written here).
+__global__ __launch_bounds__(64) void verify_feed_kernel(const GenCtl* ctl, const int* token, const int* draft, int* vctl, int* fed, int rows,
+                                                        int max_positions) {
+    if (ctl->done) return;
+    const int i = threadIdx.x;
+    if (i >= rows) return;
+    const int c = ctl->count, dlen = vctl[0];
+    int n = rows;
+    n = min(n, max(dlen - c + 1, 1));
+    n = min(n, ctl->max_new - c);
+    n = min(n, max_positions - ctl->pos);
+    n = max(n, 0);
+    fed[i] = (i >= 1 && i < n) ? draft[c + i - 1] : *token;
+    if (i == 0) vctl[1] = n;
+}
+
+// One verify step on the arg-maxes cand[0 .. n) of the n = min(*n_rows, max_rows) rows fed with fed[0 .. n): cand[0] is always emitted,
+// cand[i] iff every earlier row was emitted without stopping and cand[i - 1] == fed[i] (the guess that row i was fed is what the model
+// emitted).  Stops are launch_argmax_step's: an EOS id (appended, not fed), the max_new-th token, a non-finite arg-max (-1).  Appends to
+// out_ids, advances GenCtl, leaves the last emitted token in *out_token, copies the final-norm row xn[i] of every emitted token to
+// hid_tap[min(its index, tap_cap - 1)] and adds to stats[0] (passes) / stats[1] (tokens emitted by passes).  No-op when done is set.
+template <typename T>
+__global__ __launch_bounds__(256) void verify_step_kernel(const int* fed, const int* cand, const int* n_rows, int max_rows, GenCtl* ctl,
+                                                          const int* eos, int* out_ids, int* out_token, const T* xn, T* hid_tap, int H,
+                                                          int tap_cap, int* stats) {
+    constexpr int EPC = Elt<T>::PER_CHUNK;
+    __shared__ int s_emit, s_c0, s_eos[8];
+    const int was_done = ctl->done, n = min(min(*n_rows, max_rows), 8), n_eos = ctl->n_eos;
+    if (was_done) return;                  // (uniform: thread 0 writes the flag only behind the barriers below)
+    for (int i = 0; i < n; ++i) {          // is cand[i] an EOS id?  (the set may be large: all threads search it)
+        int hit = 0;
+        for (int k = threadIdx.x; k < n_eos; k += 256) hit |= eos[k] == cand[i];
+        hit = __syncthreads_or(hit);
+        if (threadIdx.x == 0) s_eos[i] = hit;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int c = ctl->count, max_new = ctl->max_new;
+        int e = 0, stop = 0, last = -1;
+        for (int i = 0; i < n && !stop; ++i) {
+            if (i > 0 && cand[i - 1] != fed[i]) break;
+            const int tok = cand[i];
+            out_ids[c + e] = tok;
+            ++e;
+            last = tok;
+            stop = tok < 0 || c + e >= max_new || s_eos[i];
+        }
+        if (e > 0) {
+            *out_token = last;
+            ctl->count = c + e;
+            const int adv = stop ? e - 1 : e;          // the stopping token is appended, never fed
+            ctl->pos += adv; ctl->kv_len += adv;
+            if (stop) ctl->done = 1;
+        }
+        stats[0] += 1; stats[1] += e;
+        s_emit = e; s_c0 = c;
+    }
+    __syncthreads();
+    const int e = s_emit, c0 = s_c0, nch = H / EPC;
+    for (int q = threadIdx.x; q < e * nch; q += 256) {
+        const int j = q / nch, ci = q - j * nch;
+        *(uint4*)(hid_tap + (size_t)min(c0 + j, tap_cap - 1) * H + (size_t)ci * EPC) = *(const uint4*)(xn + (size_t)j * H + (size_t)ci * EPC);
+    }
+}
+
 // --------------------------------------------------------------------------- slow-memory token pruning
 // OPT-IN EXTENSION (BASELINE configs[3]; SURVEY.md a-13: the reference has no counterpart, parity is pinned only by this
 // project's own CPU restatement oracle/streamvln_oracle.py: prune_memory_tokens).  Rule: score_i = cos(M_i, mean_j M_j) over the
@@ -394,6 +464,15 @@ template <typename T> void launch_gather_rows(hipStream_t s, const int* src, con
     if (rows <= 0) return;
     hipLaunchKernelGGL((gather_rows_kernel<T>), dim3(rows), dim3(256), 0, s, src, (const T*)embed, (const T*)feats, (T*)out, n, skip);
 }
+void launch_verify_feed(hipStream_t s, const GenCtl* ctl, const int* token, const int* draft, int* vctl, int* fed, int rows, int max_positions) {
+    hipLaunchKernelGGL(verify_feed_kernel, dim3(1), dim3(64), 0, s, ctl, token, draft, vctl, fed, rows, max_positions);
+}
+template <typename T> void launch_verify_step(hipStream_t s, const int* fed, const int* cand, const int* n_rows, int max_rows, GenCtl* ctl,
+                                              const int* eos, int* out_ids, int* out_token, const void* xn, void* hid_tap, int H, int tap_cap,
+                                              int* stats) {
+    hipLaunchKernelGGL((verify_step_kernel<T>), dim3(1), dim3(256), 0, s, fed, cand, n_rows, max_rows, ctl, eos, out_ids, out_token, (const T*)xn,
+                       (T*)hid_tap, H, tap_cap, stats);
+}
 // scratch: partial [ceil(n/64)][H] floats, mean [H], score [n]; sel [keep] ints (ascending row indices)
 template <typename T> void launch_memory_prune(hipStream_t s, const void* m, int n_rows, int H, int keep, float* partial, float* mean, float* score,
                                                int* sel) {
@@ -430,6 +509,8 @@ template <typename T> void launch_from_f32(hipStream_t s, const float* src, void
     template void launch_patchify<T>(hipStream_t, const float*, void*, int, int, int, int);                                       \
     template void launch_pool<T>(hipStream_t, const void*, void*, const int*, const float*, int, int, int, int);                  \
     template void launch_gather_rows<T>(hipStream_t, const int*, const void*, const void*, void*, int, int, const int*);                      \
+    template void launch_verify_step<T>(hipStream_t, const int*, const int*, const int*, int, GenCtl*, const int*, int*, int*, const void*,    \
+                                        void*, int, int, int*);                                                                  \
     template void launch_memory_prune<T>(hipStream_t, const void*, int, int, int, float*, float*, float*, int*);                   \
     template void launch_synth<T>(hipStream_t, void*, int, int64_t, int, RowMap, uint64_t, float, float);                          \
     template void launch_convert<T>(hipStream_t, void*, int, int64_t, int, RowMap, const void*, int);                              \

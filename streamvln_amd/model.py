@@ -186,6 +186,8 @@ class StreamVLNForCausalLM:
         self.generation_config = SimpleNamespace(eos_token_id=[151645, 151643], repetition_penalty=1.0)
         self._row_limit, self._rep_penalty = 0, 1.0           # what the engine currently holds
         self._tickets: Dict[int, tuple] = {}
+        self._auto_draft = False                                   # set_auto_draft: guess that a turn repeats the env's previous one
+        self._last_out: Dict[int, torch.Tensor] = {}
         self.reset(max_envs)
 
     # ---- construction -------------------------------------------------------------------------
@@ -398,6 +400,7 @@ class StreamVLNForCausalLM:
         self.curr_t = [0] * env_num
         self._epoch = [0] * env_num
         self._slots: Dict[int, int] = {}
+        self._last_out = {}                                        # auto-draft: the previous turn's ids per env_id
         _check(self._lib.svln_batch_cancel(self._h, -1))           # turns still in the scheduler belong to the old state
         self._tickets.clear()
         for i in range(self.max_envs):
@@ -419,6 +422,7 @@ class StreamVLNForCausalLM:
             raise IndexError(f"env_id {env_idx} out of range")
         self.curr_t[env_idx] = 0
         self._epoch[env_idx] += 1
+        self._last_out.pop(env_idx, None)
         if env_idx in self._slots:
             _check(self._lib.svln_reset_env(self._h, self._slots[env_idx]))       # (drops the env's scheduler turn, if any)
         for slot in [k for k, v in self._tickets.items() if v[0] == env_idx]:
@@ -486,9 +490,11 @@ class StreamVLNForCausalLM:
 
     @torch.no_grad()
     def generate(self, inputs=None, images=None, image_sizes=None, depths=None, poses=None, intrinsics=None, task_ids=None,
-                 **kwargs):
+                 draft_ids=None, **kwargs):
         """One model turn = ONE crossing into the engine (svln_turn: encode_rgbd, the KV / embeds bookkeeping of the reference's generate,
-        splice, prefill + greedy decode)."""
+        splice, prefill + greedy decode).  draft_ids (optional, set_speculative): a guess of this turn's whole id sequence; with
+        set_auto_draft(True) and no explicit draft, the env's previous turn output is the guess."""
+        draft = draft_ids
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
         self._sync_call_config()
         # the reference's bookkeeping that needs no engine call: the KV handle must be this env's current one; curr_t counts the turns
@@ -503,6 +509,12 @@ class StreamVLNForCausalLM:
         a.pixels, a.n_frames, a.pixels_on_device, a.env = pix.data_ptr(), V, on_dev, slot
         a.ids, a.n_ids, a.n_memory = ids_np.ctypes.data, ids_np.size, n_memory
         a.new_window, a.new_episode, a.max_new_tokens = int(past is None), int(self.curr_t[env_id] == 0), max_new
+        auto = self._auto_draft
+        if draft is None and auto:
+            draft = self._last_out.get(env_id)
+        if draft is not None:
+            d_np = np.ascontiguousarray(torch.as_tensor(draft).reshape(-1).to("cpu", torch.int64).numpy())
+            _check(self._lib.svln_set_draft(self._h, slot, d_np.ctypes.data_as(C.POINTER(C.c_int64)), int(d_np.size)))
         if on_dev:
             self._order_engine_after(pix)
         rc = self._lib.svln_turn(self._h, buf["args_ref"], buf["out_p"], cap, buf["n_out_ref"], buf["kv_ref"])
@@ -512,6 +524,8 @@ class StreamVLNForCausalLM:
         self.curr_t[env_id] += 1
         dev = inputs.device if isinstance(inputs, torch.Tensor) else "cpu"
         seq = torch.from_numpy(buf["out"][: buf["n_out"].value].copy()).unsqueeze(0)
+        if auto:
+            self._last_out[env_id] = seq[0].clone()
         if dev != "cpu" and str(dev) != "cpu":
             seq = seq.to(dev)
         return GenerateOutput(sequences=seq, past_key_values=KVHandle(env_id, self._epoch[env_id], buf["kv"].value))
@@ -736,6 +750,23 @@ class StreamVLNForCausalLM:
         single-env mode.  Independent of set_mxfp4_decode; bf16 engines only; refused while set_fp8_decode or set_fp8_gemm is on (and
         they are refused while it is on)."""
         _check(self._lib.svln_set_mxfp4_batched(self._h, int(enable)))
+
+    def set_speculative(self, rows: int):
+        """opt-in draft-verified greedy decode (svln_set_speculative): rows = 0 off, 2 / 4 / 8 = rows per verify pass.  Same ids as the
+        plain greedy loop; a turn whose draft (generate(draft_ids=...) or set_auto_draft) is right takes one pass over the weights per
+        `rows` tokens instead of one per token.  Refused while a reduced-precision or persistent decode mode is on."""
+        _check(self._lib.svln_set_speculative(self._h, int(rows)))
+
+    def set_auto_draft(self, enable: bool):
+        """with no explicit draft_ids, generate() guesses that a turn repeats the env's previous turn; cleared by reset / reset_for_env"""
+        self._auto_draft = bool(enable)
+        self._last_out = {}
+
+    def draft_stats(self, reset: bool = False):
+        """(verify passes run, tokens they emitted, tokens emitted by ordinary decode steps) since the last reset"""
+        v = [C.c_int64() for _ in range(3)]
+        _check(self._lib.svln_draft_stats(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), int(reset)))
+        return tuple(int(x.value) for x in v)
 
     def set_fp8_gemm(self, enable: bool):
         """Opt-in extension (SURVEY.md 8f-2 / BASELINE configs[4]): the LLM's multi-row products (prefill; decode steps of >= 4 batched
