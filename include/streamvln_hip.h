@@ -147,7 +147,7 @@ int svln_get_hidden_batch(svln_engine* h, int slot, float* host_out, int max_row
 int svln_get_hidden(svln_engine* h, float* host_out, int max_rows, int32_t* n_rows);  /* final-norm hidden per generated token of the last generate */
 int svln_get_embeds(svln_engine* h, int env, int start_row, int n_rows, float* host_out);
 int svln_get_frame_feats(svln_engine* h, int start_row, int n_rows, float* host_out);
-int svln_get_top2(svln_engine* h, float* host_out2);       /* refused when the last token of the last turn came from a verify pass (svln_set_speculative) */
+int svln_get_top2(svln_engine* h, float* host_out2);       /* refused when the last token of the last turn came from a verify pass (svln_set_speculative) or a ride (svln_set_prefill_draft) */
 /* prefill taps of svln_generate (single env): enable != 0 records the LAST row of the residual stream after every decoder layer of the
  * next prefills (svln_get_layer_taps: host_out [layers][hidden]); probe_layer >= 0 additionally records, for every row of the prefill,
  * the operands the products of that one layer actually saw (svln_get_layer_probe, which: 0 = x entering the layer, 1 = x leaving it,
@@ -237,6 +237,28 @@ int svln_set_draft(svln_engine* h, int env, const int64_t* ids, int n);
 /* Counters since the last reset, over svln_generate / svln_turn / svln_generate_fixed: verify passes run, tokens they emitted, tokens
  * emitted by ordinary decode steps.  The prefill's own token counts in none of them.  Any pointer may be null. */
 int svln_draft_stats(svln_engine* h, int64_t* verify_passes, int64_t* tokens_from_verify, int64_t* single_steps, int reset);
+/* Opt-in, default off, no reference counterpart: drafts inside the prefill pass ("rides") -- a turn whose armed draft (svln_set_draft)
+ * is right needs NO decode pass.  With L rows of inputs_embeds, Tn of them new, and a usable draft D (ids up to the first one outside
+ * the vocabulary; one id is enough), the prefill of svln_generate / svln_turn / svln_generate_fixed carries
+ *     k = min(len(D), 7, tokens the call may emit - 1, max_positions - L), cut further at the first D[j] in the EOS set
+ * extra rows: the token embeddings of D[0 .. k) at positions L .. L + k - 1 of the same sequence (RoPE, KV append and the causal prefill
+ * attention at any T; there is no rows * (q_heads / kv_heads) limit).  The lm_head arg-max o_i of the last k + 1 rows then goes through
+ * the verify rule of svln_set_speculative from zero emitted tokens: o_0 (the plain turn's token 0) is always emitted, o_i iff every
+ * earlier row was emitted without stopping and o_{i-1} == D[i - 1].  K / V rows of rejected positions lie at or beyond the env's kv
+ * length and are overwritten later.  One synchronisation reads the result: a finished turn returns with no decode step enqueued; an
+ * unfinished one whose emitted ids all equal the draft continues with verify passes when svln_set_speculative is on and guesses remain;
+ * otherwise ordinary decode steps finish it (a failed ride costs k rows and one extra synchronisation).  k = 0 (no draft, a draft that
+ * opens with an EOS id, max_new_tokens = 1, no position left, a repetition penalty != 1): the plain turn, launch for launch, bit-identical
+ * to mode off.  Ids are those of the plain loop exactly on the fp32 engine's fixtures; the product plans depend on the row count, so with
+ * k > 0 the prompt rows' sums may be ordered differently than in a plain turn and a ridden row's differently than a decode step's: on the
+ * bf16 engine a near-tie arg-max can fall the other way, as between svln_generate and svln_generate_batch.  Independent of
+ * svln_set_speculative (either, both or neither).  Refused like it: while svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm,
+ * svln_set_mxfp4_batched or svln_set_decode_persistent is on, and each of those is refused while this mode is on; while scheduler turns
+ * are in flight.  A call that changes nothing always succeeds.  svln_generate_batch and the scheduler ignore the mode. */
+int svln_set_prefill_draft(svln_engine* h, int on);
+/* Counters since the last reset: rides run, tokens they emitted (the turn's token 0 included), draft rows they fed (the k's summed).
+ * svln_draft_stats keeps its meaning: a token emitted by a ride counts in none of its three counters.  Any pointer may be null. */
+int svln_prefill_draft_stats(svln_engine* h, int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int reset);
 /* Opt-in slow-memory pruning (BASELINE configs[3]; the reference has NO counterpart -- its memory is all num_history x 196 pooled
  * tokens, streamvln_eval.py:313-321 -- so this is pinned only by the project's own CPU restatement, oracle: prune_memory_tokens):
  * with keep_tokens > 0 a `<memory>` sentinel expands to the keep_tokens memory tokens least similar (cosine) to the mean memory

@@ -110,6 +110,8 @@ struct EngineBase {
     virtual void set_speculative(int rows) = 0;
     virtual void set_draft(int env, const int64_t* ids, int n) = 0;
     virtual void draft_stats(int64_t* verify_passes, int64_t* tokens_from_verify, int64_t* single_steps, int reset) = 0;
+    virtual void set_prefill_draft(int on) = 0;
+    virtual void prefill_draft_stats(int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int reset) = 0;
     virtual void op_attention_verify(int rows, const void* ctx, int ld, int ctx_rows, const void* qkv_new, void* out, int o_stride) = 0;
     virtual void op_verify_step(int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos, int n_eos,
                                 int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token) = 0;
@@ -214,7 +216,14 @@ public:
     int *d_draft = nullptr, *h_draft = nullptr;      // the armed draft of the running turn (device copy / pinned staging)
     int *d_vctl = nullptr, *h_vctl = nullptr;        // [0] usable draft length, [1] rows of the pass, [2] passes, [3] tokens of the turn; d_vctl[8 ..] = fed rows
     int64_t st_passes = 0, st_vtokens = 0, st_single = 0;
-    bool top2_stale = false;                 // the last token of the last turn came from a verify pass (which keeps no top-2 logits)
+    bool top2_stale = false;                 // the last token of the last turn came from a verify pass or a ride (which keep no top-2 logits)
+    // Opt-in drafts inside the prefill pass (svln_set_prefill_draft; no reference counterpart, same ids as the plain loop).  A "ride" is a
+    // prefill whose last k rows are the embeddings of the draft's first k ids at positions L .. L + k - 1: the lm_head arg-max of its
+    // last k + 1 rows goes through the verify step from count = 0, so a confirmed turn needs no decode pass at all.  Ride state in
+    // d_vctl: [4] rides run, [5] tokens they emitted, [6] head rows of the ride (k + 1).
+    bool ride_on = false;
+    static constexpr int RIDE_MAX_ROWS = 7;  // fed draft rows per ride: the verify step holds 8 head rows
+    int64_t st_rides = 0, st_rtokens = 0, st_rrows = 0;
 
     // decode graph + probes.  The step graph holds the env's page-table pointer, so there is one set per env (a round-robin over several
     // envs through svln_generate replays instead of re-capturing); [0] = the whole step, [1] / [2] = the halves around the probed launch
@@ -926,10 +935,14 @@ public:
     // n_dec > 0 (mixed iteration of the multi-env scheduler): rows [0, n_dec) are single-token decode rows of n_dec other envs
     // (x already holds their token embeddings, d_slots their page tables / positions); they share every dense product with the
     // prefill rows and run the batched decode attention (fused RoPE + KV append) instead of the per-segment prefill attention.
-    void prefill_rows(const std::vector<Seg>& segs, int M, int n_dec = 0) {
+    // n_draft > 0 (a ride of svln_set_prefill_draft; one env alone in the batch): the segment's last n_draft rows are not rows of the env's
+    // embeds but the token embeddings of d_draft[0 .. n_draft), gathered here; RoPE, KV append and the causal attention treat them as the
+    // next positions of the same sequence.
+    void prefill_rows(const std::vector<Seg>& segs, int M, int n_dec = 0, int n_draft = 0) {
         const int qd = nq * 128;
         for (const Seg& g : segs)
-            HIP_CHECK(hipMemcpyAsync(x + (size_t)g.off * H, g.e->embeds + (size_t)g.P * H, (size_t)g.Tn * H * sizeof(T), hipMemcpyDeviceToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(x + (size_t)g.off * H, g.e->embeds + (size_t)g.P * H, (size_t)(g.Tn - n_draft) * H * sizeof(T), hipMemcpyDeviceToDevice, st));
+        if (n_draft > 0) launch_gather_rows<T>(st, d_draft, embed, feats, x + (size_t)(M - n_draft) * H, n_draft, H);
         bool xn_ready = false;        // xn already holds rmsnorm(x) * in_norm (written by the previous layer's down_proj epilogue)
         const bool taps = layer_taps_on && segs.size() == 1 && n_dec == 0;
         for (int i = 0; i < c.layers; ++i) {
@@ -987,9 +1000,9 @@ public:
         launch_attention<T>(st, a, 128, 1);
         launch_attention_combine<T>(st, a, 128);
     }
-    void prefill(Env& e, int P, int Tn) {
+    void prefill(Env& e, int P, int Tn, int n_draft = 0) {        // Tn rows in all, the last n_draft of them draft rows
         std::vector<Seg> segs{Seg{&e, P, Tn, 0}};
-        prefill_rows(segs, Tn);
+        prefill_rows(segs, Tn, 0, n_draft);
     }
 
     GemvArgs gemv_args(const void* W, int ldw, const void* xin, const void* norm_w, const void* bias, const void* res, void* y, int N, int K,
@@ -1223,6 +1236,19 @@ public:
         }
         argmax_rows(lm_head, H, xn, H, V, H, B, pen);
     }
+    // rows argmax_rows is given for n >= 2 head rows of a ride: the 32-row MFMA tiles take any row count from batched_mfma_min up, the
+    // batched GEMV 2, 4 or 8 (the pad rows are stale rows of xn: readable, their arg-maxes never read)
+    int ride_head_rows(int n) const {
+        if (n >= batched_mfma_min && H % Elt<T>::PER_CHUNK == 0 && (V + 127) / 128 <= 2048) return n;
+        return n <= 2 ? 2 : n <= 4 ? 4 : 8;
+    }
+    // head of a ride: final norm of the last n rows of the M prefill rows -> xn[0 .. n), lm_head arg-max of every row -> d_tok_b, then
+    // the verify step from count = 0 on fed = d_vctl + 8 (fed[i] = draft[i - 1]); its counters are d_vctl[4], [5]
+    void ride_head(int M, int n) {
+        launch_rmsnorm<T>(st, x + (size_t)(M - n) * H, final_norm, xn, n, H, c.rms_eps);
+        argmax_rows(lm_head, H, xn, H, V, H, ride_head_rows(n), false);
+        launch_verify_step<T>(st, d_vctl + 8, d_tok_b, d_vctl + 6, n, d_ctl, d_eos, d_out_ids, d_token, xn, hid_tap, H, HID_TAP_ROWS, d_vctl + 4);
+    }
     // svln_set_mxfp4_batched: one product of the batched step on the MXFP4 copy `q` of a weight matrix (gemv_mx4b.hip)
     GemvMx4BatchArgs gemvb4_args(const Q4& q, int ldw, const void* xin, int ldx, const void* bias, const void* res, int ldr, void* y, int ldy,
                                  int N, int K, int epi, int B) {
@@ -1335,6 +1361,27 @@ public:
     }
     void refuse_while_speculative(const char* who) {
         REQUIRE(spec_rows == 0, std::string(who) + ": draft-verified decode is on (svln_set_speculative); switch it off first");
+        REQUIRE(!ride_on, std::string(who) + ": drafts inside the prefill pass are on (svln_set_prefill_draft); switch them off first");
+    }
+    void set_prefill_draft(int on) override {
+        const bool want = on != 0;
+        if (want == ride_on) return;           // nothing changes
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_prefill_draft cannot change while scheduler turns are in flight");
+        if (want) {
+            // a ridden row must be computed in the numeric scheme of the pass it replaces
+            REQUIRE(!spec_exclusive_on(), "svln_set_prefill_draft: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, "
+                                          "svln_set_fp8_gemm, svln_set_mxfp4_batched, svln_set_decode_persistent); switch it off first");
+            REQUIRE(c.max_positions >= MAXB, "svln_set_prefill_draft: max_positions too small");
+            set_speculative_buffers();
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+        ride_on = want;
+    }
+    void prefill_draft_stats(int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int reset) override {
+        if (rides) *rides = st_rides;
+        if (tokens_from_rides) *tokens_from_rides = st_rtokens;
+        if (rows_fed) *rows_fed = st_rrows;
+        if (reset) st_rides = st_rtokens = st_rrows = 0;
     }
     void set_draft(int env, const int64_t* ids, int n) override {
         env_at(env);
@@ -1672,21 +1719,38 @@ public:
                 eos_valid = true;
             }
         }
-        // the env's armed draft is consumed by this call whether or not it helps; usable: the mode is on, no repetition penalty (its flags
-        // change the logits token by token), ids in the vocabulary (the first one outside ends the draft) and a guess beyond index 0
+        // the env's armed draft is consumed by this call whether or not it helps; usable: a draft mode is on, no repetition penalty (its
+        // flags change the logits token by token), ids in the vocabulary (the first one outside ends the draft); verify passes need a guess
+        // beyond index 0, a ride is served by index 0 alone
         int dlen = 0;
         if (had_draft) {
-            if (spec_rows > 0 && rep_penalty == 1.0f) {
+            if ((spec_rows > 0 || ride_on) && rep_penalty == 1.0f) {
                 const std::vector<int64_t>& D = drafts[env];
                 while (dlen < (int)D.size() && D[dlen] >= 0 && D[dlen] < V) { h_draft[dlen] = (int)D[dlen]; ++dlen; }
             }
         }
-        const bool spec = dlen >= 2;
-        ensure_pages(e, L);
-        if (spec) {
-            h_vctl[0] = dlen; h_vctl[1] = h_vctl[2] = h_vctl[3] = 0;
+        const bool spec = spec_rows > 0 && dlen >= 2;
+        // Ride (svln_set_prefill_draft): draft ids 0 .. k - 1 are fed as k more prefill rows at positions L .. L + k - 1; k is cut by the
+        // verify step's 8 head rows, by the tokens the call may emit (a row's arg-max beyond them is useless), by max_positions and at
+        // the first draft id in the EOS set (an EOS is appended, never fed).  k = 0: the plain turn, launch for launch.
+        int k_ride = 0;
+        if (ride_on && dlen >= 1) {
+            k_ride = std::max(std::min(std::min(dlen, RIDE_MAX_ROWS), std::min(limit - 1, c.max_positions - L)), 0);
+            for (int j = 0; j < k_ride; ++j)
+                if (std::find(eos_cached.begin(), eos_cached.end(), h_draft[j]) != eos_cached.end()) { k_ride = j; break; }
+        }
+        const bool ride = k_ride >= 1;
+        const int n_head = k_ride + 1;
+        ensure_pages(e, L + k_ride);
+        if (spec || ride) {
+            h_vctl[0] = dlen;
+            for (int j = 1; j < 16; ++j) h_vctl[j] = 0;
+            if (ride) {
+                h_vctl[6] = n_head;
+                for (int i = 1; i < n_head; ++i) h_vctl[8 + i] = h_draft[i - 1];       // fed[i]: the token row Tn + i - 1 was given
+            }
             HIP_CHECK(hipMemcpyAsync(d_draft, h_draft, (size_t)dlen * sizeof(int), hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync(d_vctl, h_vctl, 4 * sizeof(int), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(d_vctl, h_vctl, 16 * sizeof(int), hipMemcpyHostToDevice, st));
         }
         // the first decode step feeds token 0 at position L: pos / kv_len advance when the arg-max step appends without stopping
         h_ctl->pos = L - 1; h_ctl->kv_len = L; h_ctl->done = 0; h_ctl->count = 0; h_ctl->max_new = limit; h_ctl->n_eos = n_eos;
@@ -1695,15 +1759,40 @@ public:
             launch_set_flags(st, pen_flags, d_out_ids, &d_ctl->count, 0, 0);
         HIP_CHECK(hipMemcpyAsync(d_ctl, h_ctl, sizeof(GenCtl), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipEventRecord(ph_ev[2], st));
-        prefill(e, P, Tn);
-        head(x + (size_t)(Tn - 1) * H, 0, true);
+        if (ride) {
+            prefill(e, P, Tn + k_ride, k_ride);
+            ride_head(Tn + k_ride, n_head);
+        } else {
+            prefill(e, P, Tn);
+            head(x + (size_t)(Tn - 1) * H, 0, true);
+        }
         e.kv_len = L;
         HIP_CHECK(hipEventRecord(ph_ev[3], st));
         int enq = 1;                      // tokens whose arg-max step has been enqueued
         int n = 0;
         bool done = false, decoded = false;
         int vtokens = 0;                  // tokens of this turn that verify passes emitted
-        if (spec) {
+        int rtokens = 0;                  // tokens of this turn that the ride emitted (token 0 included)
+        bool ride_held = true;            // every id the ride emitted equals the draft
+        if (ride) {
+            // one synchronisation reads what the ride emitted: a finished turn returns with no decode pass enqueued; otherwise verify
+            // passes continue while the draft holds (svln_set_speculative on and guesses left), else single steps finish the turn
+            HIP_CHECK(hipMemcpyAsync(h_ctl, d_ctl, sizeof(GenCtl), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(h_out_ids, d_out_ids, (size_t)n_head * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(h_vctl, d_vctl, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            LAUNCH_CHECK("generate (ride)");
+            n = h_ctl->count;
+            done = h_ctl->done != 0;
+            REQUIRE(n >= 1 && n <= n_head, "generation state out of range");
+            for (int k = 0; k < n; ++k)
+                REQUIRE(h_out_ids[k] >= 0 && h_out_ids[k] < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+            for (int k = 0; k < n && k < dlen; ++k) ride_held = ride_held && h_out_ids[k] == h_draft[k];
+            rtokens = h_vctl[5];
+            st_rides += h_vctl[4]; st_rtokens += rtokens; st_rrows += k_ride;
+            enq = n;
+        }
+        if (spec && ride_held && !done) {
             // Verify passes while the draft holds: with cnt tokens emitted a pass carries rows_at(cnt) rows (verify_feed_kernel computes the
             // same number on the device); one is enqueued while the draft has a guess for the next token (cnt < dlen), even where max_new
             // or max_positions cut it to one row.  After each the host reads the ids: a further pass follows only if every id from index 1
@@ -1715,7 +1804,7 @@ public:
                 r = std::min(r, c.max_positions - (L + cnt - 1));
                 return r;
             };
-            int cnt = 1;
+            int cnt = enq;
             while (!done && cnt < dlen && rows_at(cnt) >= 1) {
                 const int r = rows_at(cnt);
                 ensure_pages(e, L + cnt - 1 + r);              // row i writes position L + cnt - 1 + i
@@ -1783,8 +1872,9 @@ public:
             if (decoded) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[3], ph_ev[4])); ph_ms[2] += t; }
         }
         n_generated = n;
-        st_vtokens += vtokens; st_single += n - 1 - vtokens;
-        top2_stale = vtokens > 0 && n - 1 - vtokens == 0;
+        const int singles = n - vtokens - (ride ? rtokens : 1);      // (the prefill's own token counts in none of the draft counters)
+        st_vtokens += vtokens; st_single += singles;
+        top2_stale = (vtokens > 0 || ride) && singles == 0;
         *n_out = n;
     }
 
@@ -1847,7 +1937,8 @@ public:
         read_rows_f32(feats + (size_t)start * H, (size_t)n * H, out);
     }
     void get_top2(float* out) override {
-        REQUIRE(!top2_stale, "svln_get_top2: the last token of the last turn came from a verify pass (svln_set_speculative), which keeps no top-2 logits");
+        REQUIRE(!top2_stale, "svln_get_top2: the last token of the last turn came from a verify pass (svln_set_speculative) or a ride "
+                             "(svln_set_prefill_draft), which keep no top-2 logits");
         out[0] = h_top2[0]; out[1] = h_top2[1];
     }
     void sync() override { HIP_CHECK(hipStreamSynchronize(st)); }
@@ -2544,6 +2635,10 @@ int svln_set_speculative(svln_engine* h, int rows) { API_BEGIN_H h->impl->set_sp
 int svln_set_draft(svln_engine* h, int env, const int64_t* ids, int n) { API_BEGIN_H h->impl->set_draft(env, ids, n); API_END }
 int svln_draft_stats(svln_engine* h, int64_t* verify_passes, int64_t* tokens_from_verify, int64_t* single_steps, int reset) {
     API_BEGIN_H h->impl->draft_stats(verify_passes, tokens_from_verify, single_steps, reset); API_END
+}
+int svln_set_prefill_draft(svln_engine* h, int on) { API_BEGIN_H h->impl->set_prefill_draft(on); API_END }
+int svln_prefill_draft_stats(svln_engine* h, int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int reset) {
+    API_BEGIN_H h->impl->prefill_draft_stats(rides, tokens_from_rides, rows_fed, reset); API_END
 }
 int svln_set_memory_prune(svln_engine* h, int keep_tokens) { API_BEGIN_H h->impl->set_memory_prune(keep_tokens); API_END }
 int svln_op_memory_prune(svln_engine* h, const void* mem, int n_rows, int keep, int32_t* out_idx, float* out_score) {

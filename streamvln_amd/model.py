@@ -492,7 +492,7 @@ class StreamVLNForCausalLM:
     def generate(self, inputs=None, images=None, image_sizes=None, depths=None, poses=None, intrinsics=None, task_ids=None,
                  draft_ids=None, **kwargs):
         """One model turn = ONE crossing into the engine (svln_turn: encode_rgbd, the KV / embeds bookkeeping of the reference's generate,
-        splice, prefill + greedy decode).  draft_ids (optional, set_speculative): a guess of this turn's whole id sequence; with
+        splice, prefill + greedy decode).  draft_ids (optional, set_speculative / set_prefill_draft): a guess of this turn's whole id sequence; with
         set_auto_draft(True) and no explicit draft, the env's previous turn output is the guess."""
         draft = draft_ids
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
@@ -766,6 +766,18 @@ class StreamVLNForCausalLM:
         """(verify passes run, tokens they emitted, tokens emitted by ordinary decode steps) since the last reset"""
         v = [C.c_int64() for _ in range(3)]
         _check(self._lib.svln_draft_stats(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), int(reset)))
+        return tuple(int(x.value) for x in v)
+
+    def set_prefill_draft(self, enable: bool):
+        """opt-in drafts inside the prefill pass (svln_set_prefill_draft): the first ids of a turn's draft (generate(draft_ids=...) or
+        set_auto_draft) ride the prefill as extra rows, so a turn whose draft is right needs no decode pass at all.  Same ids as the plain
+        greedy loop; independent of set_speculative.  Refused while a reduced-precision or persistent decode mode is on."""
+        _check(self._lib.svln_set_prefill_draft(self._h, int(bool(enable))))
+
+    def prefill_draft_stats(self, reset: bool = False):
+        """(rides run, tokens they emitted -- token 0 included, draft rows they fed) since the last reset"""
+        v = [C.c_int64() for _ in range(3)]
+        _check(self._lib.svln_prefill_draft_stats(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), int(reset)))
         return tuple(int(x.value) for x in v)
 
     def set_fp8_gemm(self, enable: bool):
