@@ -232,7 +232,8 @@ int svln_set_speculative(svln_engine* h, int rows);
  * index 0 included (never needed: the prefill emits it), so the previous turn's output can be passed verbatim.  Consumed by that call
  * whether or not it helped; n = 0 clears it; svln_reset_env / svln_kv_reset leave it armed.  Host-only: no GPU work, no synchronisation.
  * Refused: an unknown env, n < 0, n > max_positions.  An id outside [0, vocab) ends the usable draft at its index.  Ignored (not an error)
- * while the mode is off or a repetition penalty != 1 is set, and by svln_generate_batch / the scheduler (which leave it armed). */
+ * while the mode is off or a repetition penalty != 1 is set, and by svln_generate_batch / the scheduler (which leave it armed) unless
+ * svln_set_batch_draft is on: then svln_batch_submit consumes it. */
 int svln_set_draft(svln_engine* h, int env, const int64_t* ids, int n);
 /* Counters since the last reset, over svln_generate / svln_turn / svln_generate_fixed: verify passes run, tokens they emitted, tokens
  * emitted by ordinary decode steps.  The prefill's own token counts in none of them.  Any pointer may be null. */
@@ -254,11 +255,41 @@ int svln_draft_stats(svln_engine* h, int64_t* verify_passes, int64_t* tokens_fro
  * bf16 engine a near-tie arg-max can fall the other way, as between svln_generate and svln_generate_batch.  Independent of
  * svln_set_speculative (either, both or neither).  Refused like it: while svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm,
  * svln_set_mxfp4_batched or svln_set_decode_persistent is on, and each of those is refused while this mode is on; while scheduler turns
- * are in flight.  A call that changes nothing always succeeds.  svln_generate_batch and the scheduler ignore the mode. */
+ * are in flight.  A call that changes nothing always succeeds.  svln_generate_batch and the scheduler ignore the mode (their own
+ * switch is svln_set_batch_draft). */
 int svln_set_prefill_draft(svln_engine* h, int on);
 /* Counters since the last reset: rides run, tokens they emitted (the turn's token 0 included), draft rows they fed (the k's summed).
  * svln_draft_stats keeps its meaning: a token emitted by a ride counts in none of its three counters.  Any pointer may be null. */
 int svln_prefill_draft_stats(svln_engine* h, int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int reset);
+/* Opt-in, default off, no reference counterpart: drafts in the prefill pass of the multi-env scheduler (svln_batch_submit /
+ * svln_batch_step / svln_generate_batch) -- a lockstep turn whose drafts are all right is ONE scheduler iteration.  Independent of
+ * svln_set_speculative and svln_set_prefill_draft, which the scheduler goes on ignoring.  With the switch on, svln_batch_submit consumes
+ * the env's armed draft (svln_set_draft) whether or not it helps; it is usable if the repetition penalty is 1, up to its first id outside
+ * the vocabulary, and the job keeps it.  When an iteration packs the prefill segments in slot order, a job with a usable draft D, Tn new
+ * rows and M rows packed before it gets
+ *     k = min(len(D), 7, max_new_tokens - 1, max_positions - n_embeds), cut at the first D[j] in the job's EOS set,
+ *         and cut to max_positions - M - Tn, the rows the workspace still holds
+ * extra rows: the token embeddings of D[0 .. k) at positions n_embeds .. n_embeds + k - 1 of that env, behind its prompt rows (a job
+ * whose Tn rows do not fit waits for the next iteration, as without the switch, and keeps its draft).  Decode rows of other envs share
+ * the pass as before.  The lm_head arg-max runs on one row per decode row and k + 1 rows per segment, at most 64 in all, in chunks of
+ * at most 32 rows.  After the iteration's one synchronisation the host applies the verify rule of svln_set_speculative from zero
+ * emitted tokens to each job: o_0 is always emitted, o_i iff every earlier one was emitted without stopping and o_{i-1} == D[i - 1];
+ * stops are an EOS id (appended, never fed), the max_new_tokens-th token, a non-finite arg-max.  With e tokens emitted the env's kv
+ * length is n_embeds + e - 1; K / V rows of rejected positions lie beyond it and are overwritten later.  A job that did not stop goes on
+ * as an ordinary decode row; its draft is dropped after the ride (there are no batched verify passes).  svln_get_hidden_batch returns
+ * the final-norm rows of the emitted tokens as before.  An iteration in which no job rides is launch for launch the one without the
+ * switch, bit-identical.  With rides the row count of the pass, and so the product plans, differ from a plain iteration: fp32 ids equal
+ * the plain run's on the fixtures; on the bf16 engine a near-tie arg-max can fall the other way.  Refused: while scheduler turns are in
+ * flight; while svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm, svln_set_mxfp4_batched or svln_set_decode_persistent is
+ * on (a ridden row must be computed in the numeric scheme of the decode row it replaces: under svln_set_fp8_gemm a batched step of
+ * B <= 2 runs bf16 GEMVs while the prefill products run e4m3), and each of those is refused while this switch is on.  A call that
+ * changes nothing always succeeds. */
+int svln_set_batch_draft(svln_engine* h, int on);
+/* Counters of the scheduler since the last reset: rides run (jobs prefilled with k >= 1), tokens they emitted (the turn's token 0
+ * included), draft rows they fed (the k's summed), iterations (passes svln_batch_step executed; counted with the switch off as well),
+ * decode rows fed one token at a time.  Any pointer may be null. */
+int svln_batch_draft_stats(svln_engine* h, int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int64_t* iterations,
+                           int64_t* single_rows, int reset);
 /* Opt-in slow-memory pruning (BASELINE configs[3]; the reference has NO counterpart -- its memory is all num_history x 196 pooled
  * tokens, streamvln_eval.py:313-321 -- so this is pinned only by the project's own CPU restatement, oracle: prune_memory_tokens):
  * with keep_tokens > 0 a `<memory>` sentinel expands to the keep_tokens memory tokens least similar (cosine) to the mean memory

@@ -124,6 +124,8 @@ SIGNATURES = {
     "svln_draft_stats": (_I, [_P, _PI64, _PI64, _PI64, _I]),
     "svln_set_prefill_draft": (_I, [_P, _I]),
     "svln_prefill_draft_stats": (_I, [_P, _PI64, _PI64, _PI64, _I]),
+    "svln_set_batch_draft": (_I, [_P, _I]),
+    "svln_batch_draft_stats": (_I, [_P, _PI64, _PI64, _PI64, _PI64, _PI64, _I]),
     "svln_set_memory_prune": (_I, [_P, _I]),
     "svln_op_memory_prune": (_I, [_P, _P, _I, _I, _PI32, _PF]),
     "svln_probe_reset": (_I, [_P]),

@@ -112,6 +112,8 @@ struct EngineBase {
     virtual void draft_stats(int64_t* verify_passes, int64_t* tokens_from_verify, int64_t* single_steps, int reset) = 0;
     virtual void set_prefill_draft(int on) = 0;
     virtual void prefill_draft_stats(int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int reset) = 0;
+    virtual void set_batch_draft(int on) = 0;
+    virtual void batch_draft_stats(int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int64_t* iterations, int64_t* single_rows, int reset) = 0;
     virtual void op_attention_verify(int rows, const void* ctx, int ld, int ctx_rows, const void* qkv_new, void* out, int o_stride) = 0;
     virtual void op_verify_step(int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos, int n_eos,
                                 int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token) = 0;
@@ -224,6 +226,15 @@ public:
     bool ride_on = false;
     static constexpr int RIDE_MAX_ROWS = 7;  // fed draft rows per ride: the verify step holds 8 head rows
     int64_t st_rides = 0, st_rtokens = 0, st_rrows = 0;
+    // Opt-in drafts in the scheduler's prefill pass (svln_set_batch_draft; independent of the two switches above).  A job keeps the usable
+    // part of the draft its env had armed at the submit; the iteration that prefills the job appends k of its ids as rows of the job's
+    // segment and the host applies the verify rule to the k + 1 arg-maxes of that job.  Head rows of such an iteration: one per decode
+    // row, k + 1 per segment, at most HEAD_ROWS; the lists of the indexed norm and of the ragged gather are staged in pinned memory.
+    bool bdraft_on = false;
+    static constexpr int HEAD_ROWS = 64;     // MAXB jobs x (RIDE_MAX_ROWS + 1) head rows
+    int *d_head_src = nullptr, *d_head_tap = nullptr, *d_ride_list = nullptr;       // device lists: [HEAD_ROWS], [HEAD_ROWS], [HEAD_ROWS] pairs
+    int *h_head_src = nullptr, *h_head_tap = nullptr, *h_ride_list = nullptr;       // pinned
+    int64_t st_brides = 0, st_btokens = 0, st_brows = 0, st_biters = 0, st_bsingle = 0;
 
     // decode graph + probes.  The step graph holds the env's page-table pointer, so there is one set per env (a round-robin over several
     // envs through svln_generate replays instead of re-capturing); [0] = the whole step, [1] / [2] = the halves around the probed launch
@@ -392,11 +403,14 @@ public:
         d_eos = dalloc<int>((size_t)(V > 16 ? V : 16)); d_out_ids = dalloc<int>((size_t)c.max_positions + 8);
         HIP_CHECK(hipHostMalloc((void**)&h_ctl, sizeof(GenCtl)));
         HIP_CHECK(hipHostMalloc((void**)&h_out_ids, ((size_t)c.max_positions + 8) * sizeof(int)));
-        d_slots = dalloc<DecodeSlot>(MAXB, true); d_tok_b = dalloc<int>(MAXB, true);
-        part_val_b = dalloc<float>((size_t)MAXB * 2048); part_idx_b = dalloc<int>((size_t)MAXB * 2048);
-        last_rows = dalloc<T>((size_t)MAXB * H);
+        d_slots = dalloc<DecodeSlot>(MAXB, true); d_tok_b = dalloc<int>(HEAD_ROWS + MAXB, true);
+        part_val_b = dalloc<float>((size_t)HEAD_ROWS * 2048); part_idx_b = dalloc<int>((size_t)HEAD_ROWS * 2048);
+        last_rows = dalloc<T>((size_t)HEAD_ROWS * H);
         HIP_CHECK(hipHostMalloc((void**)&h_slots, MAXB * sizeof(DecodeSlot)));
-        HIP_CHECK(hipHostMalloc((void**)&h_tok_b, MAXB * sizeof(int)));
+        HIP_CHECK(hipHostMalloc((void**)&h_tok_b, (HEAD_ROWS + MAXB) * sizeof(int)));
+        d_head_src = dalloc<int>(4 * HEAD_ROWS, true); d_head_tap = d_head_src + HEAD_ROWS; d_ride_list = d_head_src + 2 * HEAD_ROWS;
+        HIP_CHECK(hipHostMalloc((void**)&h_head_src, 4 * HEAD_ROWS * sizeof(int)));
+        h_head_tap = h_head_src + HEAD_ROWS; h_ride_list = h_head_src + 2 * HEAD_ROWS;
         d_src = dalloc<int>(rt);
         HIP_CHECK(hipHostMalloc((void**)&h_src, rt * sizeof(int)));
         HIP_CHECK(hipHostMalloc((void**)&h_token, 16));
@@ -440,6 +454,7 @@ public:
         (void)hipHostFree(h_src); (void)hipHostFree(h_token); (void)hipHostFree(h_top2);
         if (h_sel) (void)hipHostFree(h_sel);
         (void)hipHostFree(h_slots); (void)hipHostFree(h_tok_b);
+        if (h_head_src) (void)hipHostFree(h_head_src);
         if (h_draft) (void)hipHostFree(h_draft);
         if (h_vctl) (void)hipHostFree(h_vctl);
         if (h_pen_rows) (void)hipHostFree(h_pen_rows);
@@ -914,7 +929,8 @@ public:
         return a;
     }
 
-    struct Seg { Env* e; int P, Tn, off; };       // rows [off, off + Tn) of the prefill batch belong to env e at positions P..
+    // rows [off, off + Tn) of the prefill batch belong to env e at positions P..; the last n_draft of them are draft rows (a ride)
+    struct Seg { Env* e; int P, Tn, off; int n_draft = 0; };
     RopeKvArgs rope_kv_args(const LLayer& L, const Seg& g) {
         RopeKvArgs r; r.qkv = qkv + (size_t)g.off * qkv_dim; r.ld = qkv_dim; r.Kpool = L.kpool; r.Vpool = L.vpool; r.rope_tab = rope_tab;
         r.nq = nq; r.nkv = nkv; r.dyn_pos = nullptr; r.page_table = g.e->d_pages; r.T = g.Tn; r.P = g.P;
@@ -935,14 +951,18 @@ public:
     // n_dec > 0 (mixed iteration of the multi-env scheduler): rows [0, n_dec) are single-token decode rows of n_dec other envs
     // (x already holds their token embeddings, d_slots their page tables / positions); they share every dense product with the
     // prefill rows and run the batched decode attention (fused RoPE + KV append) instead of the per-segment prefill attention.
-    // n_draft > 0 (a ride of svln_set_prefill_draft; one env alone in the batch): the segment's last n_draft rows are not rows of the env's
-    // embeds but the token embeddings of d_draft[0 .. n_draft), gathered here; RoPE, KV append and the causal attention treat them as the
-    // next positions of the same sequence.
-    void prefill_rows(const std::vector<Seg>& segs, int M, int n_dec = 0, int n_draft = 0) {
+    // Seg.n_draft > 0 (a ride): the segment's last n_draft rows are not rows of the env's embeds but token embeddings of draft ids, gathered
+    // here; RoPE, KV append and the causal attention treat them as the next positions of the same sequence.  n_ragged = 0
+    // (svln_set_prefill_draft; one env alone in the batch): the ids are d_draft[0 .. n_draft).  n_ragged > 0 (svln_set_batch_draft): the
+    // draft rows of all segments are the n_ragged (row, id) pairs of d_ride_list, written by one launch.
+    void prefill_rows(const std::vector<Seg>& segs, int M, int n_dec = 0, int n_ragged = 0) {
         const int qd = nq * 128;
-        for (const Seg& g : segs)
-            HIP_CHECK(hipMemcpyAsync(x + (size_t)g.off * H, g.e->embeds + (size_t)g.P * H, (size_t)(g.Tn - n_draft) * H * sizeof(T), hipMemcpyDeviceToDevice, st));
-        if (n_draft > 0) launch_gather_rows<T>(st, d_draft, embed, feats, x + (size_t)(M - n_draft) * H, n_draft, H);
+        for (const Seg& g : segs) {
+            HIP_CHECK(hipMemcpyAsync(x + (size_t)g.off * H, g.e->embeds + (size_t)g.P * H, (size_t)(g.Tn - g.n_draft) * H * sizeof(T), hipMemcpyDeviceToDevice, st));
+            if (g.n_draft > 0 && n_ragged == 0)
+                launch_gather_rows<T>(st, d_draft, embed, feats, x + (size_t)(g.off + g.Tn - g.n_draft) * H, g.n_draft, H);
+        }
+        launch_gather_rows_ragged<T>(st, d_ride_list, embed, x, n_ragged, H);
         bool xn_ready = false;        // xn already holds rmsnorm(x) * in_norm (written by the previous layer's down_proj epilogue)
         const bool taps = layer_taps_on && segs.size() == 1 && n_dec == 0;
         for (int i = 0; i < c.layers; ++i) {
@@ -1001,8 +1021,8 @@ public:
         launch_attention_combine<T>(st, a, 128);
     }
     void prefill(Env& e, int P, int Tn, int n_draft = 0) {        // Tn rows in all, the last n_draft of them draft rows
-        std::vector<Seg> segs{Seg{&e, P, Tn, 0}};
-        prefill_rows(segs, Tn, 0, n_draft);
+        std::vector<Seg> segs{Seg{&e, P, Tn, 0, n_draft}};
+        prefill_rows(segs, Tn);
     }
 
     GemvArgs gemv_args(const void* W, int ldw, const void* xin, const void* norm_w, const void* bias, const void* res, void* y, int N, int K,
@@ -1211,19 +1231,19 @@ public:
     // pen: the repetition penalty is on and d_pen_rows[0..B) holds the job slot (= flag row) of every batch row
     // arg-max over W [N][K] . x_b for B rows -> d_tok_b.  B >= 4: one pass of 32-row MFMA tiles with the arg-max in the epilogue (the
     // batched GEMV is dot-product-issue bound from B = 4: 386 us at B = 8 on the full vocabulary); B <= 2: the batched GEMV.
-    void argmax_rows(const void* W, int ldw, const T* xrows, int ldx, int N, int K, int B, bool pen) {
+    void argmax_rows(const void* W, int ldw, const T* xrows, int ldx, int N, int K, int B, bool pen, int tok0 = 0) {       // -> d_tok_b[tok0 ..)
         if (B >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048) {
             GemmArgs a = gemm_args(xrows, ldx, W, ldw, nullptr, 0, nullptr, nullptr, 0, 0, B, N, K, EPI_ARGMAX);
             a.part_val = part_val_b; a.part_idx = part_idx_b;
             if (pen) { a.pen_flags = pen_flags_b; a.pen_rows = d_pen_rows; a.pen = rep_penalty; }
             const int n = launch_gemm_argmax<T>(st, a);
-            launch_argmax_final_batched(st, part_val_b, part_idx_b, n, B, d_tok_b);
+            launch_argmax_final_batched(st, part_val_b, part_idx_b, n, B, d_tok_b + tok0);
             return;
         }
         GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, EPI_ARGMAX, B);
         if (pen) { hb.pen_flags = pen_flags_b; hb.pen_rows = d_pen_rows; hb.pen = rep_penalty; }
         launch_gemv_batched<T>(st, hb);
-        launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(N, EPI_ARGMAX, B), B, d_tok_b);
+        launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(N, EPI_ARGMAX, B), B, d_tok_b + tok0);
     }
     void head_batched(const T* rows, int B, bool pen = false) {
         launch_rmsnorm<T>(st, rows, final_norm, xn, B, H, c.rms_eps);
@@ -1362,6 +1382,28 @@ public:
     void refuse_while_speculative(const char* who) {
         REQUIRE(spec_rows == 0, std::string(who) + ": draft-verified decode is on (svln_set_speculative); switch it off first");
         REQUIRE(!ride_on, std::string(who) + ": drafts inside the prefill pass are on (svln_set_prefill_draft); switch them off first");
+        REQUIRE(!bdraft_on, std::string(who) + ": drafts in the scheduler's prefill pass are on (svln_set_batch_draft); switch them off first");
+    }
+    void set_batch_draft(int on) override {
+        const bool want = on != 0;
+        if (want == bdraft_on) return;         // nothing changes
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_batch_draft cannot change while scheduler turns are in flight");
+        if (want) {
+            // a ridden row must be computed in the numeric scheme of the decode row it replaces
+            REQUIRE(!spec_exclusive_on(), "svln_set_batch_draft: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, "
+                                          "svln_set_fp8_gemm, svln_set_mxfp4_batched, svln_set_decode_persistent); switch it off first");
+            REQUIRE(c.max_positions >= HEAD_ROWS + MAXB, "svln_set_batch_draft: max_positions too small");
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+        bdraft_on = want;
+    }
+    void batch_draft_stats(int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int64_t* iterations, int64_t* single_rows, int reset) override {
+        if (rides) *rides = st_brides;
+        if (tokens_from_rides) *tokens_from_rides = st_btokens;
+        if (rows_fed) *rows_fed = st_brows;
+        if (iterations) *iterations = st_biters;
+        if (single_rows) *single_rows = st_bsingle;
+        if (reset) st_brides = st_btokens = st_brows = st_biters = st_bsingle = 0;
     }
     void set_prefill_draft(int on) override {
         const bool want = on != 0;
@@ -1413,6 +1455,7 @@ public:
         bool used = false, finished = false, prefill = true;
         int env = -1, max_new = 0, count = 0, last_tok = -1;
         std::vector<int64_t> out, eos;
+        std::vector<int> draft;      // svln_set_batch_draft: the usable draft the submit consumed, kept until the job's prefill iteration
     };
     Job jobs[MAXB];
     // forget a job: its slot becomes free, its repetition-penalty flags are cleared (the stream is idle between scheduler calls)
@@ -1485,6 +1528,10 @@ public:
         j.used = true; j.env = env; j.max_new = max_new < c.max_positions ? max_new : c.max_positions;
         j.eos.assign(eos, eos + n_eos);
         n_generated_b[slot] = 0;
+        // svln_set_batch_draft: the env's armed draft is consumed by the submit whether or not it helps (the rule of svln_generate); usable:
+        // no repetition penalty, ids in the vocabulary (the first one outside ends the draft)
+        if (bdraft_on && disarm_draft(env) && rep_penalty == 1.0f)
+            for (int64_t id : drafts[env]) { if (id < 0 || id >= V) break; j.draft.push_back((int)id); }
         return slot;
     }
     // one iteration; returns the number of jobs still running afterwards, finished_slots = jobs that completed in this iteration
@@ -1513,6 +1560,33 @@ public:
             throw;
         }
     }
+    // Head of an iteration with rides (svln_set_batch_draft): a fixed number of launches whatever the row count.  Head rows = the nrow decode
+    // rows, then the last prompt row and the draft rows of every segment; one indexed final norm writes them to xn[0 .. nh) and to their
+    // parity taps (head row i of a segment -> tap row i of its job), the arg-max product takes them in chunks of <= 32 rows into
+    // d_tok_b[0 .. nh) (the pad rows of a chunk's row count are stale rows of xn: readable, their arg-maxes never read).  Returns nh.
+    int head_with_rides(const std::vector<int>& dec, int nrow, const std::vector<Seg>& segs, const std::vector<int>& pre_now, std::vector<int>& order) {
+        int nh = 0;
+        auto head_row = [&](int src, int tap_idx, int slot) {
+            h_head_src[nh] = src;
+            h_head_tap[nh] = taps_on ? (tap_idx < 8 ? tap_idx : 7) * MAXB + slot : -1;
+            ++nh;
+        };
+        for (int k = 0; k < nrow; ++k) head_row(k, jobs[dec[k]].count, dec[k]);
+        for (size_t q = 0; q < segs.size(); ++q) {
+            const Seg& g = segs[q];
+            for (int i = 0; i <= g.n_draft; ++i) head_row(g.off + g.Tn - 1 - g.n_draft + i, i, pre_now[q]);
+            order.push_back(pre_now[q]);
+        }
+        REQUIRE(nh <= HEAD_ROWS, "batch_step: more head rows than the workspace holds");
+        HIP_CHECK(hipMemcpyAsync(d_head_src, h_head_src, (size_t)nh * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_head_tap, h_head_tap, (size_t)nh * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_rmsnorm_indexed<T>(st, x, final_norm, xn, d_head_src, d_head_tap, hid_tap, nh, H, c.rms_eps);
+        for (int r0 = 0; r0 < nh; r0 += 32) {
+            const int n = std::min(nh - r0, 32);
+            argmax_rows(lm_head, H, xn + (size_t)r0 * H, H, V, H, n == 1 ? 1 : ride_head_rows(n), false, r0);
+        }
+        return nh;
+    }
     int batch_step_run(int32_t* finished_slots, int32_t* n_finished) {
         std::vector<int> dec, pre;                      // job slots decoding / prefilling in this iteration
         for (int k = 0; k < MAXB; ++k)
@@ -1528,17 +1602,31 @@ public:
         const bool split_mixed = mx4b_on;
         std::vector<Seg> segs;
         std::vector<int> pre_now;
+        int n_ride = 0;                                 // draft rows of this iteration: (row, id) pairs in h_ride_list
         int M = split_mixed ? 0 : nd;
         for (int k : pre) {
             Env& e = envs[jobs[k].env];
             const int Tn = e.n_embeds - e.kv_len;
             REQUIRE(Tn >= 1 && Tn <= c.max_positions, "prefill length out of range");
-            if (M + Tn > c.max_positions) continue;
-            ensure_pages(e, e.n_embeds);
-            segs.push_back(Seg{&e, e.kv_len, Tn, M});
+            if (M + Tn > c.max_positions) continue;          // (a waiting job keeps its draft)
+            // svln_set_batch_draft: k ids of the job's draft ride as the segment's last rows -- the rule of the single-env ride (k of
+            // svln_set_prefill_draft), cut further to the rows the workspace still holds.  The draft is dropped with its ride.
+            int kd = 0;
+            Job& j = jobs[k];
+            if (!j.draft.empty()) {
+                kd = std::max(std::min(std::min((int)j.draft.size(), RIDE_MAX_ROWS), std::min(j.max_new - 1, c.max_positions - e.n_embeds)), 0);
+                for (int q = 0; q < kd; ++q)
+                    if (std::find(j.eos.begin(), j.eos.end(), (int64_t)j.draft[q]) != j.eos.end()) { kd = q; break; }
+                kd = std::min(kd, c.max_positions - M - Tn);
+                for (int q = 0; q < kd; ++q) { h_ride_list[2 * n_ride] = M + Tn + q; h_ride_list[2 * n_ride + 1] = j.draft[q]; ++n_ride; }
+            }
+            ensure_pages(e, e.n_embeds + kd);
+            segs.push_back(Seg{&e, e.kv_len, Tn + kd, M, kd});
             pre_now.push_back(k);
-            M += Tn;
+            M += Tn + kd;
         }
+        const bool rides = n_ride > 0;                  // (never under a repetition penalty or svln_set_mxfp4_batched: no draft is usable / the switch excludes it)
+        if (rides) HIP_CHECK(hipMemcpyAsync(d_ride_list, h_ride_list, (size_t)n_ride * 2 * sizeof(int), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipEventRecord(ph_ev[2], st));
         std::vector<int> order;                         // job slot of each output token of this iteration
         if (nd > 0) {
@@ -1578,6 +1666,7 @@ public:
         // before the prefill pass reuses xn / d_tok_b, and ph_ev[4] divides the iteration's time between the two phase timers
         const bool split = split_mixed && nd > 0 && !segs.empty();
         const int head0 = split ? nd : 0;               // first entry of `order` that the lm_head pass below produces
+        int n_head = 0;                                 // arg-maxes the lm_head pass below leaves in d_tok_b
         if (split) {
             for (int q = 0; q < nd; ++q) tap_copy(xn + (size_t)q * H, jobs[order[q]].count, order[q]);
             HIP_CHECK(hipMemcpyAsync(h_tok_b, d_tok_b, nd * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1585,30 +1674,37 @@ public:
         }
         if (!segs.empty()) {
             const int nrow = split_mixed ? 0 : nd;      // decode rows that share the prefill pass
-            prefill_rows(segs, M, nrow);
-            // last row of every job of this pass -> one lm_head pass
-            const int nj = nrow + (int)segs.size();
-            for (int k = 0; k < nrow; ++k)
-                HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)k * H, x + (size_t)k * H, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
-            for (size_t q = 0; q < segs.size(); ++q) {
-                const T* last = x + (size_t)(segs[q].off + segs[q].Tn - 1) * H;
-                HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)(nrow + q) * H, last, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
-                order.push_back(pre_now[q]);
+            prefill_rows(segs, M, nrow, n_ride);
+            if (rides) {
+                n_head = head_with_rides(dec, nrow, segs, pre_now, order);
+            } else {
+                // last row of every job of this pass -> one lm_head pass
+                const int nj = nrow + (int)segs.size();
+                for (int k = 0; k < nrow; ++k)
+                    HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)k * H, x + (size_t)k * H, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
+                for (size_t q = 0; q < segs.size(); ++q) {
+                    const T* last = x + (size_t)(segs[q].off + segs[q].Tn - 1) * H;
+                    HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)(nrow + q) * H, last, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
+                    order.push_back(pre_now[q]);
+                }
+                int Bp = 1; while (Bp < nj) Bp <<= 1;
+                for (int k = nj; k < Bp; ++k)
+                    HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)k * H, last_rows, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
+                if (pen) {
+                    int* hp = h_pen_rows + (split ? MAXB : 0);      // (the decode step's upload may still be pending on the first half)
+                    for (int k = 0; k < Bp; ++k) hp[k] = order[head0 + (k < nj ? k : 0)];
+                    HIP_CHECK(hipMemcpyAsync(d_pen_rows, hp, Bp * sizeof(int), hipMemcpyHostToDevice, st));
+                }
+                head_batched(last_rows, Bp, pen);
             }
-            int Bp = 1; while (Bp < nj) Bp <<= 1;
-            for (int k = nj; k < Bp; ++k)
-                HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)k * H, last_rows, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
-            if (pen) {
-                int* hp = h_pen_rows + (split ? MAXB : 0);      // (the decode step's upload may still be pending on the first half)
-                for (int k = 0; k < Bp; ++k) hp[k] = order[head0 + (k < nj ? k : 0)];
-                HIP_CHECK(hipMemcpyAsync(d_pen_rows, hp, Bp * sizeof(int), hipMemcpyHostToDevice, st));
-            }
-            head_batched(last_rows, Bp, pen);
         }
         const int nj = (int)order.size();
-        for (int q = head0; q < nj; ++q) tap_copy(xn + (size_t)(q - head0) * H, jobs[order[q]].count, order[q]);
+        if (!rides) {
+            for (int q = head0; q < nj; ++q) tap_copy(xn + (size_t)(q - head0) * H, jobs[order[q]].count, order[q]);
+            n_head = nj - head0;
+        }
         HIP_CHECK(hipEventRecord(ph_ev[3], st));
-        HIP_CHECK(hipMemcpyAsync(h_tok_b + head0, d_tok_b, (nj - head0) * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h_tok_b + head0, d_tok_b, n_head * sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         LAUNCH_CHECK("batch_step");
         {
@@ -1621,18 +1717,38 @@ public:
             }
             if (vision_pending) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
         }
+        st_biters += 1;
+        st_bsingle += nd;
+        int hq = 0;                                     // head row of h_tok_b the next job starts at
         for (int q = 0; q < nj; ++q) {
             Job& j = jobs[order[q]];
             Env& e = envs[j.env];
-            const int tok = h_tok_b[q];
-            REQUIRE(tok >= 0 && tok < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
-            if (j.prefill) { e.kv_len = e.n_embeds; j.prefill = false; }      // this iteration prefilled the turn
-            else e.kv_len += 1;                                               // ... or fed the previous token
-            j.out.push_back(tok);
-            j.count += 1;
+            // a job's k + 1 arg-maxes (k = 0 without a ride) under the verify rule from zero emitted tokens: row 0's is always emitted,
+            // row i's iff every earlier one was emitted without stopping and equals the draft id row i was fed; a stopping token is
+            // appended, never fed.  K / V rows of rejected positions lie beyond kv_len and are overwritten later.
+            const int kd = j.prefill && rides ? segs[q - (nj - (int)segs.size())].n_draft : 0;
+            int tok = -1, emitted = 0;
+            bool stop = false;
+            for (int i = 0; i <= kd && !stop; ++i) {
+                if (i > 0 && tok != j.draft[i - 1]) break;
+                tok = h_tok_b[hq + i];
+                REQUIRE(tok >= 0 && tok < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+                j.out.push_back(tok);
+                j.count += 1;
+                ++emitted;
+                stop = j.count >= j.max_new;
+                for (int64_t id : j.eos) stop |= id == tok;
+            }
+            hq += kd + 1;
+            if (j.prefill) {                                                  // this iteration prefilled the turn
+                e.kv_len = e.n_embeds + emitted - 1;
+                j.prefill = false;
+                if (kd > 0) { st_brides += 1; st_btokens += emitted; st_brows += kd; }
+                std::vector<int>().swap(j.draft);
+            } else {
+                e.kv_len += 1;                                                // ... or fed the previous token
+            }
             j.last_tok = tok;
-            bool stop = j.count >= j.max_new;
-            for (int64_t id : j.eos) stop |= id == tok;
             if (pen && !stop) {                                               // the token counts as generated for this job's next arg-max
                 h_pen_ids[q] = tok;
                 HIP_CHECK(hipMemcpyAsync(d_pen_ids + q, h_pen_ids + q, sizeof(int), hipMemcpyHostToDevice, st));
@@ -2639,6 +2755,11 @@ int svln_draft_stats(svln_engine* h, int64_t* verify_passes, int64_t* tokens_fro
 int svln_set_prefill_draft(svln_engine* h, int on) { API_BEGIN_H h->impl->set_prefill_draft(on); API_END }
 int svln_prefill_draft_stats(svln_engine* h, int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int reset) {
     API_BEGIN_H h->impl->prefill_draft_stats(rides, tokens_from_rides, rows_fed, reset); API_END
+}
+int svln_set_batch_draft(svln_engine* h, int on) { API_BEGIN_H h->impl->set_batch_draft(on); API_END }
+int svln_batch_draft_stats(svln_engine* h, int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int64_t* iterations, int64_t* single_rows,
+                           int reset) {
+    API_BEGIN_H h->impl->batch_draft_stats(rides, tokens_from_rides, rows_fed, iterations, single_rows, reset); API_END
 }
 int svln_set_memory_prune(svln_engine* h, int keep_tokens) { API_BEGIN_H h->impl->set_memory_prune(keep_tokens); API_END }
 int svln_op_memory_prune(svln_engine* h, const void* mem, int n_rows, int keep, int32_t* out_idx, float* out_score) {

@@ -229,6 +229,10 @@ void decode_layer_init_attrs();
 // y2 / y2_row / y2_cap: optional second copy of the rows at row *y2_row (device scalar) of y2, clamped to y2_cap rows
 template <typename T> void launch_rmsnorm(hipStream_t s, const void* x, const void* g, void* y, int rows, int n, float eps, const int* skip = nullptr,
                                           void* y2 = nullptr, const int* y2_row = nullptr, int y2_cap = 0);
+// indexed form: y[r] = rmsnorm(x[src_rows[r]]) * g for r < rows, bit-equal to launch_rmsnorm on that row; the row also goes to
+// tap[tap_rows[r]] unless tap_rows[r] < 0.  src_rows / tap_rows: device arrays of `rows` ints.
+template <typename T> void launch_rmsnorm_indexed(hipStream_t s, const void* x, const void* g, void* y, const int* src_rows, const int* tap_rows,
+                                                  void* tap, int rows, int n, float eps);
 template <typename T> void launch_layernorm(hipStream_t s, const void* x, const void* g, const void* b, void* y, int rows, int n, float eps);
 
 // RoPE on q,k (in place on q) + append roped k and v to the paged cache.
@@ -264,6 +268,8 @@ template <typename T> void launch_memory_prune(hipStream_t s, const void* m, int
                                                int* sel);
 template <typename T> void launch_gather_rows(hipStream_t s, const int* src, const void* embed, const void* feats, void* out,
                                               int rows, int n, const int* skip = nullptr);
+// ragged form: out[list[2 i]][:] = embed[list[2 i + 1]][:] for i < rows (list: device array of (destination row, token id) pairs)
+template <typename T> void launch_gather_rows_ragged(hipStream_t s, const int* list, const void* embed, void* out, int rows, int n);
 
 // weights: synthesize (see weights.py) or convert canonical rows into packed rows
 // dst row = (r / blk) * blk * nint + phase * blk + r % blk ; cols copied to [0, cols), dst_ld >= cols

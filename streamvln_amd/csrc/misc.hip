@@ -10,19 +10,10 @@ namespace svln {
 namespace {
 
 // ------------------------------------------------------------------------------------------ norms
-// one wave per row; three cached passes (the row stays in L1/L2): statistics in fp32.
-// y2 (optional): a second copy of the normalised rows starting at row *y2_row (device scalar, clamped to y2_cap - 1) of y2 -- the hidden tap
-// of a decode step whose index only the device knows (GenCtl.count), so the launch can sit in a captured graph
+// one wave per row; three cached passes (the row stays in L1/L2): statistics in fp32.  y2r (optional): a second copy of the normalised row.
 template <typename T>
-__global__ __launch_bounds__(256) void rmsnorm_kernel(const T* x, const T* g, T* y, int rows, int n, float eps, const int* skip, T* y2,
-                                                      const int* y2_row, int y2_cap) {
+__device__ __forceinline__ void rmsnorm_row(const T* xr, const T* g, T* yr, T* y2r, int n, float eps, int lane) {
     constexpr int EPC = Elt<T>::PER_CHUNK;
-    if (skip && *skip) return;
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const T* xr = x + (size_t)row * n;
-    T* yr = y + (size_t)row * n;
     const int nch = n / EPC;
     float ss = 0.0f;
     for (int ci = lane; ci < nch; ci += 64) {
@@ -41,11 +32,32 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const T* x, const T* g, T*
         for (int e = 0; e < EPC; ++e) f[e] = gf[e] * (f[e] * sc);
         const uint4 o = f32_to_chunk<T>(f);
         *(uint4*)(yr + (size_t)ci * EPC) = o;
-        if (y2) {
-            const int r2 = min(*y2_row + row, y2_cap - 1);
-            *(uint4*)(y2 + (size_t)r2 * n + (size_t)ci * EPC) = o;
-        }
+        if (y2r) *(uint4*)(y2r + (size_t)ci * EPC) = o;
     }
+}
+// y2 (optional): a second copy of the normalised rows starting at row *y2_row (device scalar, clamped to y2_cap - 1) of y2 -- the hidden tap
+// of a decode step whose index only the device knows (GenCtl.count), so the launch can sit in a captured graph
+template <typename T>
+__global__ __launch_bounds__(256) void rmsnorm_kernel(const T* x, const T* g, T* y, int rows, int n, float eps, const int* skip, T* y2,
+                                                      const int* y2_row, int y2_cap) {
+    if (skip && *skip) return;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    T* y2r = y2 ? y2 + (size_t)min(*y2_row + row, y2_cap - 1) * n : nullptr;
+    rmsnorm_row<T>(x + (size_t)row * n, g, y + (size_t)row * n, y2r, n, eps, lane);
+}
+// The head of a scheduler iteration that carries rides (svln_set_batch_draft): row r of y = the norm of row src_rows[r] of x (rmsnorm_row:
+// bit-equal to rmsnorm_kernel on that row), copied as well to row tap_rows[r] of `tap` unless that is < 0.  Both lists are device arrays
+// of `rows` ints the host has checked against the row counts of x and tap.
+template <typename T>
+__global__ __launch_bounds__(256) void rmsnorm_indexed_kernel(const T* x, const T* g, T* y, const int* src_rows, const int* tap_rows, T* tap,
+                                                              int rows, int n, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int t = tap_rows[row];
+    rmsnorm_row<T>(x + (size_t)src_rows[row] * n, g, y + (size_t)row * n, t >= 0 ? tap + (size_t)t * n : nullptr, n, eps, lane);
 }
 
 template <typename T>
@@ -224,14 +236,23 @@ __global__ __launch_bounds__(256) void pool_kernel(const T* in, T* out, const in
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void gather_rows_kernel(const int* src, const T* embed, const T* feats, T* out, int n, const int* skip) {
+__device__ __forceinline__ void copy_row(T* o, const T* s, int n) {       // one workgroup of 256 threads, 16 bytes per access
     constexpr int EPC = Elt<T>::PER_CHUNK;
+    for (int ci = threadIdx.x; ci < n / EPC; ci += 256) *(uint4*)(o + (size_t)ci * EPC) = *(const uint4*)(s + (size_t)ci * EPC);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void gather_rows_kernel(const int* src, const T* embed, const T* feats, T* out, int n, const int* skip) {
     if (skip && *skip) return;
     const int row = blockIdx.x;
     const int sidx = src[row];
-    const T* s = sidx >= 0 ? embed + (size_t)sidx * n : feats + (size_t)(-(sidx + 1)) * n;
-    T* o = out + (size_t)row * n;
-    for (int ci = threadIdx.x; ci < n / EPC; ci += 256) *(uint4*)(o + (size_t)ci * EPC) = *(const uint4*)(s + (size_t)ci * EPC);
+    copy_row<T>(out + (size_t)row * n, sidx >= 0 ? embed + (size_t)sidx * n : feats + (size_t)(-(sidx + 1)) * n, n);
+}
+// ragged form for the draft rows of several prefill segments (svln_set_batch_draft): list[i] = (destination row of out, token id); the
+// host has checked both against the row workspace and the vocabulary
+template <typename T>
+__global__ __launch_bounds__(256) void gather_rows_ragged_kernel(const int2* list, const T* embed, T* out, int n) {
+    const int2 d = list[blockIdx.x];
+    copy_row<T>(out + (size_t)d.x * n, embed + (size_t)d.y * n, n);
 }
 
 
@@ -429,6 +450,12 @@ template <typename T> void launch_rmsnorm(hipStream_t s, const void* x, const vo
     hipLaunchKernelGGL((rmsnorm_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, (const T*)x, (const T*)g, (T*)y, rows, n, eps, skip, (T*)y2,
                        y2_row, y2_cap);
 }
+template <typename T> void launch_rmsnorm_indexed(hipStream_t s, const void* x, const void* g, void* y, const int* src_rows, const int* tap_rows,
+                                                  void* tap, int rows, int n, float eps) {
+    if (rows <= 0) return;
+    hipLaunchKernelGGL((rmsnorm_indexed_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, (const T*)x, (const T*)g, (T*)y, src_rows, tap_rows,
+                       (T*)tap, rows, n, eps);
+}
 template <typename T> void launch_layernorm(hipStream_t s, const void* x, const void* g, const void* b, void* y, int rows, int n, float eps) {
     if (rows <= 0) return;
     hipLaunchKernelGGL((layernorm_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, (const T*)x, (const T*)g, (const T*)b, (T*)y, rows, n, eps);
@@ -463,6 +490,10 @@ template <typename T> void launch_gather_rows(hipStream_t s, const int* src, con
                                               const int* skip) {
     if (rows <= 0) return;
     hipLaunchKernelGGL((gather_rows_kernel<T>), dim3(rows), dim3(256), 0, s, src, (const T*)embed, (const T*)feats, (T*)out, n, skip);
+}
+template <typename T> void launch_gather_rows_ragged(hipStream_t s, const int* list, const void* embed, void* out, int rows, int n) {
+    if (rows <= 0) return;
+    hipLaunchKernelGGL((gather_rows_ragged_kernel<T>), dim3(rows), dim3(256), 0, s, (const int2*)list, (const T*)embed, (T*)out, n);
 }
 void launch_verify_feed(hipStream_t s, const GenCtl* ctl, const int* token, const int* draft, int* vctl, int* fed, int rows, int max_positions) {
     hipLaunchKernelGGL(verify_feed_kernel, dim3(1), dim3(64), 0, s, ctl, token, draft, vctl, fed, rows, max_positions);
@@ -503,7 +534,9 @@ template <typename T> void launch_from_f32(hipStream_t s, const float* src, void
 
 #define SVLN_INST(T)                                                                                                              \
     template void launch_rmsnorm<T>(hipStream_t, const void*, const void*, void*, int, int, float, const int*, void*, const int*, int);                              \
+    template void launch_rmsnorm_indexed<T>(hipStream_t, const void*, const void*, void*, const int*, const int*, void*, int, int, float);                          \
     template void launch_layernorm<T>(hipStream_t, const void*, const void*, const void*, void*, int, int, float);               \
+    template void launch_gather_rows_ragged<T>(hipStream_t, const int*, const void*, void*, int, int);                            \
     template void launch_rope_kv<T>(hipStream_t, const RopeKvArgs&);                                                              \
     template void launch_vit_kv_pack<T>(hipStream_t, const void*, int, void*, void*, int, int, int, int);                         \
     template void launch_patchify<T>(hipStream_t, const float*, void*, int, int, int, int);                                       \

@@ -188,6 +188,7 @@ class StreamVLNForCausalLM:
         self._tickets: Dict[int, tuple] = {}
         self._auto_draft = False                                   # set_auto_draft: guess that a turn repeats the env's previous one
         self._last_out: Dict[int, torch.Tensor] = {}
+        self._batch_draft = False                                  # set_batch_draft: the scheduler consumes drafts
         self.reset(max_envs)
 
     # ---- construction -------------------------------------------------------------------------
@@ -530,6 +531,24 @@ class StreamVLNForCausalLM:
             seq = seq.to(dev)
         return GenerateOutput(sequences=seq, past_key_values=KVHandle(env_id, self._epoch[env_id], buf["kv"].value))
 
+    def _arm_batch_draft(self, env_id, draft):
+        """set_batch_draft on: arm env_id's draft for the submit that follows -- explicit ids, or the env's previous output under
+        set_auto_draft.  Off: nothing is armed."""
+        if not self._batch_draft:
+            return
+        if draft is None and self._auto_draft:
+            draft = self._last_out.get(env_id)
+        if draft is None:
+            return
+        d_np = np.ascontiguousarray(torch.as_tensor(draft).reshape(-1).to("cpu", torch.int64).numpy())
+        _check(self._lib.svln_set_draft(self._h, self._slot(env_id), d_np.ctypes.data_as(C.POINTER(C.c_int64)), int(d_np.size)))
+
+    def _batch_result(self, env_id, tokens, inputs):
+        res = self._result(env_id, tokens, inputs)
+        if self._auto_draft:
+            self._last_out[env_id] = res.sequences[0].to("cpu").clone()
+        return res
+
     def _turn_buffers(self, cap, eos):
         """ctypes scratch of generate(), built once per (capacity, eos list): no per-turn allocation or pointer casting"""
         key = (cap, tuple(eos))
@@ -549,12 +568,14 @@ class StreamVLNForCausalLM:
         """Several envs' turns executed together (build-side extension, SURVEY.md 8f-1 / BASELINE configs[4]).
         `requests`: list of kwargs dicts as passed to `generate` (distinct env_id, at most 8).  Per-env results are those of
         `generate` called env by env (same protocol, same KV / embeds state); the dense layers and every decode step run
-        once for the whole batch.  Returns a list of GenerateOutput in request order."""
+        once for the whole batch.  A request's `draft_ids` (or, under set_auto_draft, the env's previous output) is armed for the turn
+        while set_batch_draft is on, and ignored otherwise.  Returns a list of GenerateOutput in request order."""
         if not (1 <= len(requests) <= 8):
             raise ValueError("1..8 requests per batch")
-        parsed = []
+        parsed, drafts = [], []
         for r in requests:
             r = dict(r)
+            drafts.append(r.pop("draft_ids", None))
             r.setdefault("max_new_tokens", max_new_tokens)
             if eos_token_ids is not None:
                 r.setdefault("eos_token_ids", eos_token_ids)
@@ -590,6 +611,8 @@ class StreamVLNForCausalLM:
                 _check(self._lib.svln_append_turn_at(self._h, self._slot(env_id), ids_np.ctypes.data_as(C.POINTER(C.c_int64)), ids_np.size, base, n_memory))
                 base += V
             i = j
+        for p, d in zip(parsed, drafts):
+            self._arm_batch_draft(p[5], d)
         envs = np.asarray([self._slot(p[5]) for p in parsed], dtype=np.int32)
         cap = min(max_new, self.cfg.max_positions)
         out = np.zeros((len(parsed), cap), dtype=np.int64)
@@ -598,14 +621,16 @@ class StreamVLNForCausalLM:
         _check(self._lib.svln_generate_batch(self._h, envs.ctypes.data_as(C.POINTER(C.c_int32)), len(parsed), max_new,
                                              eos_np.ctypes.data_as(C.POINTER(C.c_int64)), eos_np.size,
                                              out.ctypes.data_as(C.POINTER(C.c_int64)), cap, n_out.ctypes.data_as(C.POINTER(C.c_int32))))
-        return [self._result(p[5], out[k, : n_out[k]], requests[k].get("inputs")) for k, p in enumerate(parsed)]
+        return [self._batch_result(p[5], out[k, : n_out[k]], requests[k].get("inputs")) for k, p in enumerate(parsed)]
 
     # ---- iteration-level scheduler: envs whose turns fall due at different times (streamvln_dagger.py:232-313) ----
     @torch.no_grad()
     def submit(self, inputs=None, images=None, **kwargs):
         """Start one env's turn without waiting for it: same arguments as `generate`.  The turn joins the next `step_batch`
         iteration, sharing its pass over the weights with whatever the other envs in flight are doing (prefill or decode).
-        Returns a ticket; the result arrives from `step_batch`."""
+        `draft_ids` (or the env's previous output under set_auto_draft) is armed for the turn while set_batch_draft is on, and ignored
+        otherwise.  Returns a ticket; the result arrives from `step_batch`."""
+        draft = kwargs.pop("draft_ids", None)
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
         # refuse BEFORE the env's state changes (frames encoded, curr_t advanced, rows spliced): a turn the scheduler cannot take must
         # leave the env exactly as it was, so that the caller can retry it later
@@ -625,6 +650,7 @@ class StreamVLNForCausalLM:
         _check(self._lib.svln_append_turn(self._h, self._slot(env_id), ids_np.ctypes.data_as(C.POINTER(C.c_int64)), ids_np.size, n_memory))
         eos_np = np.asarray(eos, dtype=np.int64)
         slot = C.c_int32()
+        self._arm_batch_draft(env_id, draft)
         _check(self._lib.svln_batch_submit(self._h, self._slot(env_id), min(max_new, self.cfg.max_positions),
                                            eos_np.ctypes.data_as(C.POINTER(C.c_int64)), eos_np.size, C.byref(slot)))
         self._tickets[slot.value] = (env_id, inputs)
@@ -650,7 +676,7 @@ class StreamVLNForCausalLM:
             n, env = C.c_int32(), C.c_int32()
             _check(self._lib.svln_batch_result(self._h, fin[k], C.byref(env), out.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n)))
             env_id, inputs = self._tickets.pop(fin[k])
-            done.append((SimpleNamespace(env_id=env_id, slot=fin[k]), self._result(env_id, out[: n.value], inputs)))
+            done.append((SimpleNamespace(env_id=env_id, slot=fin[k]), self._batch_result(env_id, out[: n.value], inputs)))
         return done, running.value
 
     def cancel(self, ticket=None):
@@ -778,6 +804,21 @@ class StreamVLNForCausalLM:
         """(rides run, tokens they emitted -- token 0 included, draft rows they fed) since the last reset"""
         v = [C.c_int64() for _ in range(3)]
         _check(self._lib.svln_prefill_draft_stats(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), int(reset)))
+        return tuple(int(x.value) for x in v)
+
+    def set_batch_draft(self, enable: bool):
+        """opt-in drafts in the scheduler's prefill pass (svln_set_batch_draft): the first ids of a turn's draft (`draft_ids` of submit /
+        of a generate_batch request, or set_auto_draft) ride the prefill rows of that env's segment, so a lockstep turn whose drafts
+        are all right is one scheduler iteration.  Same ids as the plain scheduler on the fp32 engine; independent of set_speculative
+        and set_prefill_draft; refused with the reduced-precision / persistent decode modes and while turns are in flight."""
+        _check(self._lib.svln_set_batch_draft(self._h, int(bool(enable))))
+        self._batch_draft = bool(enable)
+
+    def batch_draft_stats(self, reset: bool = False):
+        """(rides run, tokens they emitted -- token 0 included, draft rows they fed, scheduler iterations, decode rows fed one token at
+        a time) since the last reset"""
+        v = [C.c_int64() for _ in range(5)]
+        _check(self._lib.svln_batch_draft_stats(self._h, *[C.byref(x) for x in v], int(reset)))
         return tuple(int(x.value) for x in v)
 
     def set_fp8_gemm(self, enable: bool):
