@@ -148,6 +148,25 @@ int svln_get_hidden(svln_engine* h, float* host_out, int max_rows, int32_t* n_ro
 int svln_get_embeds(svln_engine* h, int env, int start_row, int n_rows, float* host_out);
 int svln_get_frame_feats(svln_engine* h, int start_row, int n_rows, float* host_out);
 int svln_get_top2(svln_engine* h, float* host_out2);       /* refused when the last token of the last turn came from a verify pass (svln_set_speculative) or a ride (svln_set_prefill_draft) */
+/* Opt-in, default off, no reference counterpart: token log-probabilities.  While on, every lm_head product runs a sibling kernel that
+ * computes the arg-max exactly as before (same accumulators, compare order and partials: the ids are bit-identical) and, beside every
+ * arg-max partial, sum exp(l - partial max) over the logits the partial owns; the final arg-max kernel merges the partials,
+ * S = sum_k part_sum[k] * exp(part_val[k] - V), and writes logprob = -log S = l_t - logsumexp_j(l_j) of the emitted token t over the
+ * PROCESSED fp32 logits (after the repetition penalty, as HF's `scores`).  No logit reaches memory and the lm_head is not read twice;
+ * the scores travel in the synchronisation that already reads the ids.  A NaN logit makes that token's score NaN; so does token -1.
+ * Works with svln_set_fp8_decode, svln_set_mxfp4_decode (the quantised lm_heads), svln_set_fp8_gemm / svln_set_fp8_scaled_mfma and the
+ * repetition penalty.  Refused, and each of these refused while it is on: svln_set_speculative, svln_set_prefill_draft,
+ * svln_set_batch_draft (their tokens leave the verify step, which carries no scores), svln_set_decode_persistent and
+ * svln_set_mxfp4_batched (its lm_head kernel has no scored form).  A change is refused while scheduler turns are in flight; a call that
+ * changes nothing always succeeds.  Captured decode graphs are dropped when it changes.
+ * svln_get_token_scores: the scores of the last svln_generate / svln_turn / svln_generate_fixed, *n = the number of ids it returned
+ * (out receives min(*n, cap) of them).  svln_batch_scores: those of the finished scheduler turn in `slot`, valid until svln_batch_result
+ * frees the slot.  svln_generate_batch_scores: those of env index `index` (its place in the envs list) of the last svln_generate_batch.
+ * All three fail, with svln_last_error saying so, when the switch was off for that turn. */
+int svln_set_token_scores(svln_engine* h, int enable);
+int svln_get_token_scores(svln_engine* h, float* host_out, int cap, int32_t* n);
+int svln_batch_scores(svln_engine* h, int slot, float* host_out, int cap, int32_t* n);
+int svln_generate_batch_scores(svln_engine* h, int index, float* host_out, int cap, int32_t* n);
 /* prefill taps of svln_generate (single env): enable != 0 records the LAST row of the residual stream after every decoder layer of the
  * next prefills (svln_get_layer_taps: host_out [layers][hidden]); probe_layer >= 0 additionally records, for every row of the prefill,
  * the operands the products of that one layer actually saw (svln_get_layer_probe, which: 0 = x entering the layer, 1 = x leaving it,
@@ -400,6 +419,24 @@ int svln_op_gemv_mxfp4_batched(svln_engine* h, const void* q4, const void* e8, i
  * logit becomes v < 0 ? v * penalty : v / penalty before the arg-max.  Same refusals; penalty must be > 0. */
 int svln_op_gemv_mxfp4_batched_argmax_pen(svln_engine* h, const void* q4, const void* e8, int ldw, const void* x, int ldx, int N, int K, int B,
                                           const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens);
+/* TEST-ONLY entries, not part of the product surface: one lm_head product of svln_set_token_scores with optional repetition-penalty
+ * flags (device pointers; null = none), tokens and log-probabilities to the host.  host_logprob(s) null: the plain EPI_ARGMAX kernels
+ * on the same inputs (the tokens of the two forms are bit-equal).
+ * svln_op_gemv_argmax_scores: the single-env head; fmt 0 = W in the engine dtype, 1 = e4m3 bytes with aux = fp32 row scales, 2 = MXFP4
+ * codes with aux = E8M0 scale bytes (layouts of svln_op_gemv_fp8 / svln_op_gemv_mxfp4); pen_flags [N] bytes.
+ * svln_op_gemv_batched_argmax_scores: the batched GEMV itself at B = 1, 2, 4, 8 (no routing to the MFMA form), optional fused RMSNorm;
+ * the arg-max ignores the norm's positive row factor (as the plain form does), the log-probability is that of the normalised logits;
+ * pen_flags [rows][N], pen_rows [B]: vector b uses flag row pen_rows[b].
+ * svln_op_gemm_argmax_scores: the 32 x 128 MFMA tiles, 1 <= M <= 32 rows of A [M][lda]; pen_rows [M].
+ * Refused before any launch: null operands, extents below 1, K / the leading dimensions not positive multiples of the format's 16-byte
+ * chunk or below K, B outside {1, 2, 4, 8}, M outside 1 .. 32, N above 262144 (MFMA form), flags without their row table, penalty <= 0,
+ * fmt 1 / 2 on an fp32 engine, A / W not 16-byte aligned (MFMA form). */
+int svln_op_gemv_argmax_scores(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
+                               float penalty, int32_t* host_token, float* host_logprob);
+int svln_op_gemv_batched_argmax_scores(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
+                                       const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs);
+int svln_op_gemm_argmax_scores(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
+                               const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs);
 int svln_op_rmsnorm(svln_engine* h, const void* x, const void* g, void* y, int rows, int n, float eps);
 int svln_op_layernorm(svln_engine* h, const void* x, const void* g, const void* b, void* y, int rows, int n, float eps);
 /* attention over caller-provided q [T][q_stride] and k/v [S][kv_stride] (engine packs them into pages):

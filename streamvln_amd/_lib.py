@@ -108,6 +108,10 @@ SIGNATURES = {
     "svln_get_embeds": (_I, [_P, _I, _I, _I, _PF]),
     "svln_get_frame_feats": (_I, [_P, _I, _I, _PF]),
     "svln_get_top2": (_I, [_P, _PF]),
+    "svln_set_token_scores": (_I, [_P, _I]),
+    "svln_get_token_scores": (_I, [_P, _PF, _I, _PI32]),
+    "svln_batch_scores": (_I, [_P, _I, _PF, _I, _PI32]),
+    "svln_generate_batch_scores": (_I, [_P, _I, _PF, _I, _PI32]),
     "svln_set_layer_taps": (_I, [_P, _I, _I]),
     "svln_get_layer_taps": (_I, [_P, _PF]),
     "svln_get_layer_probe": (_I, [_P, _I, _PF, _I64, _PI32, _PI32]),
@@ -147,6 +151,9 @@ SIGNATURES = {
     "svln_op_gemv_mxfp4": (_I, [_P, _P, _P, _I, _P, _P, _F, _P, _P, _P, _I, _I, _I, _PI32]),
     "svln_op_gemv_mxfp4_batched": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _PI32]),
     "svln_op_gemv_mxfp4_batched_argmax_pen": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _PI32]),
+    "svln_op_gemv_argmax_scores": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _F, _PI32, _PF]),
+    "svln_op_gemv_batched_argmax_scores": (_I, [_P, _P, _I, _P, _I, _P, _F, _I, _I, _I, _P, _P, _F, _PI32, _PF]),
+    "svln_op_gemm_argmax_scores": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _PI32, _PF]),
     "svln_op_rmsnorm": (_I, [_P, _P, _P, _P, _I, _I, _F]),
     "svln_op_layernorm": (_I, [_P, _P, _P, _P, _P, _I, _I, _F]),
     "svln_op_attention_llm": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I]),

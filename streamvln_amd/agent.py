@@ -77,6 +77,10 @@ class StreamingAgent:
         self.action_seq: List[int] = []
         self.output_ids = None
         self.past_key_values = None
+        # model confidence of the last model turn (model.set_token_scores): log-probability of every emitted id [1, n_new] and their sum,
+        # the joint log-probability of the turn; None when the model provides no scores
+        self.last_token_logprobs = None
+        self.last_turn_logprob = None
         self.step_id = 0
         self.last_image = None
         self.model.reset_for_env(self.env_id)
@@ -125,6 +129,9 @@ class StreamingAgent:
     def _consume(self, out):
         self.output_ids = out.sequences
         self.past_key_values = out.past_key_values
+        lp = out.get("token_logprobs") if isinstance(out, dict) else getattr(out, "token_logprobs", None)
+        self.last_token_logprobs = lp
+        self.last_turn_logprob = None if lp is None else float(lp.sum())
         self.turn_log.append(dict(self._pending, out=out))
         actions = list(self.decode_actions(out.sequences))
         return actions if len(actions) else [0]               # streamvln_eval.py:340-341

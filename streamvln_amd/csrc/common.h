@@ -127,6 +127,19 @@ SVLN_DEV float wave_max(float v) {
     return v;
 }
 
+// Online log-sum-exp pieces of EPI_ARGMAX_LSE (kernels.h) on v_exp_f32 / v_log_f32.  A partial is (m, s): the maximum of the logits it
+// owns and s = sum exp(l - m) over them; the partial that owns nothing is (-inf, 0).
+SVLN_DEV float lse_exp(float d) { return __builtin_amdgcn_exp2f(1.4426950408889634f * d); }
+// logit v joins (m, s): a new maximum rescales the sum (from m = -inf: 0 * 0 = 0); a -inf logit adds 0, not exp(-inf - -inf)
+SVLN_DEV void lse_add(float v, float& m, float& s) {
+    if (v > m) { s = fmaf(s, lse_exp(m - v), 1.0f); m = v; }
+    else s += v == -INFINITY ? 0.0f : lse_exp(v - m);
+}
+// (m, s) seen from a maximum V >= m: s * exp(m - V); the empty partial is 0 whatever V is (a NaN sum stays NaN)
+SVLN_DEV float lse_rescale(float s, float m, float V) { return s == 0.0f ? 0.0f : s * lse_exp(m - V); }
+// log-probability of the winning logit from S = sum exp(l - V) >= 1
+SVLN_DEV float lse_logprob(float S) { return -0.6931471805599453f * __builtin_amdgcn_logf(S); }
+
 // activation functions (fp32).  sigmoid on the hardware transcendentals (v_exp_f32 / v_rcp_f32, ~1 ulp each: a few ulp of fp32 in all, far
 // inside the 1e-3 parity bar) instead of libm's expf / tanhf and an IEEE division: an epilogue evaluates 64-128 activations per lane per
 // 256 x 256 tile, and with libm (~35-50 instructions each) that was 35 of the 90 us of the nine-frame fc1 product and ~10 % of gate/up at

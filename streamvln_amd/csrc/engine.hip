@@ -98,6 +98,13 @@ struct EngineBase {
     virtual void get_embeds(int env, int start, int n, float* out) = 0;
     virtual void get_feats(int start, int n, float* out) = 0;
     virtual void get_top2(float* out) = 0;
+    virtual void set_token_scores(int enable) = 0;
+    virtual void get_token_scores(float* out, int cap, int32_t* n) = 0;
+    virtual void batch_scores(int slot, float* out, int cap, int32_t* n) = 0;
+    virtual void generate_batch_scores(int index, float* out, int cap, int32_t* n) = 0;
+    virtual void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob) = 0;
+    virtual void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs) = 0;
+    virtual void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs) = 0;
     virtual void sync() = 0;
     virtual void set_graph(int enable) = 0;
     virtual void set_decode_persistent(int enable) = 0;
@@ -202,6 +209,15 @@ public:
     int prune_keep = 0; float *prune_partial = nullptr, *prune_mean = nullptr, *prune_score = nullptr; int *d_sel = nullptr, *h_sel = nullptr;
     int* h_token;                // pinned
     float* h_top2;
+    // Opt-in token log-probabilities (svln_set_token_scores; no reference counterpart): every lm_head product runs its EPI_ARGMAX_LSE
+    // sibling (kernels.h) -- the same tokens, plus log softmax of the emitted token over the processed fp32 logits.  Partial sums beside
+    // part_val / part_val_b; the scores of a single-env turn in d_scores[0 .. count) beside d_out_ids, those of a scheduler iteration in
+    // d_score_b beside d_tok_b: both are read in the synchronisation that reads the ids.
+    bool scores_on = false;
+    float *part_sum = nullptr, *part_sum_b = nullptr, *d_scores = nullptr, *h_scores = nullptr, *d_score_b = nullptr, *h_score_b = nullptr;
+    float* row_scale_b = nullptr;            // [MAXB]: the row factors of a scored batched GEMV with a fused norm (svln_op_gemv_batched_argmax_scores only)
+    std::vector<float> last_scores; bool last_scores_valid = false;           // of the last svln_generate / svln_turn / svln_generate_fixed
+    std::vector<std::vector<float>> gb_scores; bool gb_scores_valid = false;  // of the last svln_generate_batch, per listed env
 
     struct Env {
         T* embeds = nullptr; int n_embeds = 0; int kv_len = 0;
@@ -240,9 +256,9 @@ public:
     // envs through svln_generate replays instead of re-capturing); [0] = the whole step, [1] / [2] = the halves around the probed launch
     // (captured only while the roofline probe is on); a run-ahead batch of several steps is one graph.
     bool use_graph = false;
-    struct GraphSet { std::unordered_map<int, hipGraphExec_t> ex; };     // key: steps (whole batch) | 1000 (head of a probed step) | 2000 + steps (its tail)
+    struct GraphSet { std::unordered_map<int, hipGraphExec_t> ex; };     // key: steps (whole batch) | 1000 (head of a probed step) | 2000 + steps (its tail) | 3000 + rows (verify pass); + 10000 with svln_set_token_scores
     std::vector<GraphSet> graphs;
-    std::unordered_map<int, hipGraphExec_t> bgraphs;          // batched decode step: key = B | penalty << 8 | fp8 gemm << 9 | MXFP4 batched << 10 | scaled fp8 form << 11
+    std::unordered_map<int, hipGraphExec_t> bgraphs;          // batched decode step: key = B | penalty << 8 | fp8 gemm << 9 | MXFP4 batched << 10 | scaled fp8 form << 11 | token scores << 12
     // per-turn truncation of the spliced rows (the reference's config.tokenizer_model_max_length, stream_video_vln.py:241-244); 0 = none
     int turn_row_limit = 0;
     // HF repetition penalty of the checkpoint's generation_config (1 = off): flags of the tokens generated in the current turn
@@ -397,7 +413,11 @@ public:
             attn_part_elems = dec > pre ? dec : pre;
             attn_part = dalloc<float>(attn_part_elems);
         }
-        part_val = dalloc<float>(2048); part_idx = dalloc<int>(2048);
+        part_val = dalloc<float>(2048); part_idx = dalloc<int>(2048); part_sum = dalloc<float>(2048);
+        d_scores = dalloc<float>((size_t)c.max_positions + 8, true); d_score_b = dalloc<float>(HEAD_ROWS + MAXB, true);
+        part_sum_b = dalloc<float>((size_t)HEAD_ROWS * 2048); row_scale_b = dalloc<float>(MAXB, true);
+        HIP_CHECK(hipHostMalloc((void**)&h_scores, ((size_t)c.max_positions + 8) * sizeof(float)));
+        HIP_CHECK(hipHostMalloc((void**)&h_score_b, (HEAD_ROWS + MAXB) * sizeof(float)));
         d_token = dalloc<int>(4, true); d_top2 = dalloc<float>(4, true);
         d_ctl = (GenCtl*)dalloc<int>(sizeof(GenCtl) / sizeof(int), true);
         d_eos = dalloc<int>((size_t)(V > 16 ? V : 16)); d_out_ids = dalloc<int>((size_t)c.max_positions + 8);
@@ -447,7 +467,7 @@ public:
         for (auto e : probe_ev) (void)hipEventDestroy(e);
         for (auto e : pprobe_ev) (void)hipEventDestroy(e);
         for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ph_ev[i]);
-        (void)hipHostFree(h_ctl); (void)hipHostFree(h_out_ids);
+        (void)hipHostFree(h_ctl); (void)hipHostFree(h_out_ids); (void)hipHostFree(h_scores); (void)hipHostFree(h_score_b);
         if (h_giveup) (void)hipHostFree(h_giveup);
         if (h_hash) (void)hipHostFree(h_hash);
         for (void* p : allocs) (void)hipFree(p);
@@ -1047,13 +1067,15 @@ public:
         } else {
             launch_rmsnorm<T>(st, xrow, final_norm, tap, 1, H, c.rms_eps, skip);
         }
-        GemvArgs a = with4(with8(gemv_args(lm_head, H, tap, nullptr, nullptr, nullptr, nullptr, V, H, EPI_ARGMAX), lm_head8), lm_head4);
+        GemvArgs a = with4(with8(gemv_args(lm_head, H, tap, nullptr, nullptr, nullptr, nullptr, V, H, scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX), lm_head8), lm_head4);
         a.skip = skip;
         const bool pen = gen && rep_penalty != 1.0f;
         if (pen) { a.pen_flags = pen_flags; a.pen = rep_penalty; }
+        const float* ps = scores_on ? part_sum : nullptr;          // svln_set_token_scores: the sibling kernels, scores[count] beside out_ids[count]
+        a.part_sum = part_sum;
         launch_gemv<T>(st, a);
-        if (gen) launch_argmax_step(st, part_val, part_idx, gemv_grid(V), d_token, d_top2, d_ctl, d_eos, d_out_ids, pen ? pen_flags : nullptr);
-        else launch_argmax_final(st, part_val, part_idx, gemv_grid(V), d_token, d_top2);
+        if (gen) launch_argmax_step(st, part_val, part_idx, gemv_grid(V), d_token, d_top2, d_ctl, d_eos, d_out_ids, pen ? pen_flags : nullptr, ps, d_scores);
+        else launch_argmax_final(st, part_val, part_idx, gemv_grid(V), d_token, d_top2, ps, d_scores);
     }
     // One decode step as a fixed op sequence; every run-time scalar is read from device memory (d_ctl,
     // d_token) so any sub-range [lo, hi) of the sequence can be captured once and graph-replayed.
@@ -1079,6 +1101,7 @@ public:
         HIP_CHECK(hipStreamSynchronize(st));
         if (!enable) { if (persistent_on) drop_graphs(); persistent_on = false; return; }
         refuse_while_speculative("svln_set_decode_persistent");
+        refuse_while_scores("svln_set_decode_persistent");
         if (!n_cus) { hipDeviceProp_t pr; HIP_CHECK(hipGetDeviceProperties(&pr, device)); n_cus = pr.multiProcessorCount; }
         DecodeLayerArgs a = layer_args(0);
         REQUIRE(decode_layer_supported<T>(a, n_cus), "persistent decode layer: this configuration is not supported (per-CU slices of hidden / inter / q|k|v "
@@ -1195,17 +1218,18 @@ public:
         const bool probing = probe_on && first_tap_row == 1 && probe_used + 2 <= probe_ev.size();
         if (use_graph) {
             GraphSet& gs = graphs[env];
+            const int sk = scores_on ? 10000 : 0;      // the captured head is the scored or the plain one
             auto get = [&](int key, int lo, int hi, int more) {
                 auto it = gs.ex.find(key);
                 if (it == gs.ex.end()) it = gs.ex.emplace(key, capture(e, lo, hi, more)).first;
                 return it->second;
             };
             if (!probing) {
-                HIP_CHECK(hipGraphLaunch(get(steps, 0, n_ops, steps - 1), st));
+                HIP_CHECK(hipGraphLaunch(get(sk + steps, 0, n_ops, steps - 1), st));
             } else {
-                HIP_CHECK(hipGraphLaunch(get(1000, 0, probe_op(), 0), st));
+                HIP_CHECK(hipGraphLaunch(get(sk + 1000, 0, probe_op(), 0), st));
                 probe_launch(e);
-                HIP_CHECK(hipGraphLaunch(get(2000 + steps, probe_op() + 1, n_ops, steps - 1), st));
+                HIP_CHECK(hipGraphLaunch(get(sk + 2000 + steps, probe_op() + 1, n_ops, steps - 1), st));
             }
             return;
         }
@@ -1231,19 +1255,23 @@ public:
     // pen: the repetition penalty is on and d_pen_rows[0..B) holds the job slot (= flag row) of every batch row
     // arg-max over W [N][K] . x_b for B rows -> d_tok_b.  B >= 4: one pass of 32-row MFMA tiles with the arg-max in the epilogue (the
     // batched GEMV is dot-product-issue bound from B = 4: 386 us at B = 8 on the full vocabulary); B <= 2: the batched GEMV.
+    // svln_set_token_scores: the EPI_ARGMAX_LSE siblings, row b's log-probability -> d_score_b[tok0 + b]
     void argmax_rows(const void* W, int ldw, const T* xrows, int ldx, int N, int K, int B, bool pen, int tok0 = 0) {       // -> d_tok_b[tok0 ..)
+        const float* ps = scores_on ? part_sum_b : nullptr;
         if (B >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048) {
             GemmArgs a = gemm_args(xrows, ldx, W, ldw, nullptr, 0, nullptr, nullptr, 0, 0, B, N, K, EPI_ARGMAX);
             a.part_val = part_val_b; a.part_idx = part_idx_b;
+            if (scores_on) a.part_sum = part_sum_b;
             if (pen) { a.pen_flags = pen_flags_b; a.pen_rows = d_pen_rows; a.pen = rep_penalty; }
             const int n = launch_gemm_argmax<T>(st, a);
-            launch_argmax_final_batched(st, part_val_b, part_idx_b, n, B, d_tok_b + tok0);
+            launch_argmax_final_batched(st, part_val_b, part_idx_b, n, B, d_tok_b + tok0, ps, d_score_b + tok0);
             return;
         }
-        GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, EPI_ARGMAX, B);
+        GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX, B);
+        hb.part_sum = part_sum_b;
         if (pen) { hb.pen_flags = pen_flags_b; hb.pen_rows = d_pen_rows; hb.pen = rep_penalty; }
         launch_gemv_batched<T>(st, hb);
-        launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(N, EPI_ARGMAX, B), B, d_tok_b + tok0);
+        launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(N, EPI_ARGMAX, B), B, d_tok_b + tok0, ps, d_score_b + tok0);
     }
     void head_batched(const T* rows, int B, bool pen = false) {
         launch_rmsnorm<T>(st, rows, final_norm, xn, B, H, c.rms_eps);
@@ -1364,6 +1392,7 @@ public:
         REQUIRE(rows == 0 || rows == 2 || rows == 4 || rows == 8, "svln_set_speculative: rows must be 0 (off), 2, 4 or 8");
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_speculative cannot change while scheduler turns are in flight");
         if (rows > 0) {
+            refuse_while_scores("svln_set_speculative");
             REQUIRE(rows * (nq / nkv) <= 32, "svln_set_speculative: rows * (q_heads / kv_heads) must be <= 32 (the verify attention keeps 32 query rows per kv head)");
             // a verify pass must compute each row in the numeric scheme of the single step it replaces
             REQUIRE(!spec_exclusive_on(), "svln_set_speculative: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, "
@@ -1384,11 +1413,51 @@ public:
         REQUIRE(!ride_on, std::string(who) + ": drafts inside the prefill pass are on (svln_set_prefill_draft); switch them off first");
         REQUIRE(!bdraft_on, std::string(who) + ": drafts in the scheduler's prefill pass are on (svln_set_batch_draft); switch them off first");
     }
+    void refuse_while_scores(const char* who) {
+        REQUIRE(!scores_on, std::string(who) + ": token log-probabilities are on (svln_set_token_scores); switch them off first");
+    }
+    // svln_set_token_scores.  Refused with the modes whose tokens do not come out of a scored arg-max: the three draft switches (their
+    // tokens leave verify_step_kernel), the persistent decode layer and the batched MXFP4 weights (gemv_mx4b_kernel has no scored form).
+    void set_token_scores(int enable) override {
+        const bool want = enable != 0;
+        if (want == scores_on) return;         // nothing changes
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_token_scores cannot change while scheduler turns are in flight");
+        if (want) {
+            refuse_while_speculative("svln_set_token_scores");
+            REQUIRE(!persistent_on, "svln_set_token_scores: the persistent decode layer is on (svln_set_decode_persistent); switch it off first");
+            REQUIRE(!mx4b_on, "svln_set_token_scores: the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+        drop_graphs();           // the captured lm_head / arg-max launches are the plain or the scored kernels
+        scores_on = want;
+    }
+    void get_token_scores(float* out, int cap, int32_t* n) override {
+        REQUIRE(last_scores_valid, "svln_get_token_scores: token log-probabilities were off for the last turn (svln_set_token_scores), or no turn has run");
+        const int m = (int)last_scores.size();
+        for (int k = 0; k < m && k < cap; ++k) out[k] = last_scores[k];
+        *n = m;
+    }
+    void batch_scores(int slot, float* out, int cap, int32_t* n) override {
+        REQUIRE(slot >= 0 && slot < MAXB && jobs[slot].used && jobs[slot].finished, "no finished turn in this slot");
+        const Job& j = jobs[slot];
+        REQUIRE(j.scored, "svln_batch_scores: token log-probabilities were off for this turn (svln_set_token_scores)");
+        const int m = (int)j.scores.size();
+        for (int k = 0; k < m && k < cap; ++k) out[k] = j.scores[k];
+        *n = m;
+    }
+    void generate_batch_scores(int index, float* out, int cap, int32_t* n) override {
+        REQUIRE(gb_scores_valid, "svln_generate_batch_scores: token log-probabilities were off for the last svln_generate_batch (svln_set_token_scores), or none has run");
+        REQUIRE(index >= 0 && index < (int)gb_scores.size(), "svln_generate_batch_scores: no such env index in the last batch");
+        const int m = (int)gb_scores[index].size();
+        for (int k = 0; k < m && k < cap; ++k) out[k] = gb_scores[index][k];
+        *n = m;
+    }
     void set_batch_draft(int on) override {
         const bool want = on != 0;
         if (want == bdraft_on) return;         // nothing changes
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_batch_draft cannot change while scheduler turns are in flight");
         if (want) {
+            refuse_while_scores("svln_set_batch_draft");
             // a ridden row must be computed in the numeric scheme of the decode row it replaces
             REQUIRE(!spec_exclusive_on(), "svln_set_batch_draft: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, "
                                           "svln_set_fp8_gemm, svln_set_mxfp4_batched, svln_set_decode_persistent); switch it off first");
@@ -1410,6 +1479,7 @@ public:
         if (want == ride_on) return;           // nothing changes
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_prefill_draft cannot change while scheduler turns are in flight");
         if (want) {
+            refuse_while_scores("svln_set_prefill_draft");
             // a ridden row must be computed in the numeric scheme of the pass it replaces
             REQUIRE(!spec_exclusive_on(), "svln_set_prefill_draft: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, "
                                           "svln_set_fp8_gemm, svln_set_mxfp4_batched, svln_set_decode_persistent); switch it off first");
@@ -1455,6 +1525,7 @@ public:
         bool used = false, finished = false, prefill = true;
         int env = -1, max_new = 0, count = 0, last_tok = -1;
         std::vector<int64_t> out, eos;
+        std::vector<float> scores; bool scored = false;      // svln_set_token_scores: log-probability of every id of `out`
         std::vector<int> draft;      // svln_set_batch_draft: the usable draft the submit consumed, kept until the job's prefill iteration
     };
     Job jobs[MAXB];
@@ -1527,6 +1598,7 @@ public:
         j = Job();
         j.used = true; j.env = env; j.max_new = max_new < c.max_positions ? max_new : c.max_positions;
         j.eos.assign(eos, eos + n_eos);
+        j.scored = scores_on;
         n_generated_b[slot] = 0;
         // svln_set_batch_draft: the env's armed draft is consumed by the submit whether or not it helps (the rule of svln_generate); usable:
         // no repetition penalty, ids in the vocabulary (the first one outside ends the draft)
@@ -1649,7 +1721,7 @@ public:
                 // gather + 28 layers + head for B decode rows -> d_tok_b, xn = final-norm rows.  With hipGraph replay on, the step of each
                 // (B, fp8, penalty) combination is captured once: every run-time value (page tables, positions, fed tokens) is in d_slots / d_tok_b.
                 if (use_graph) {
-                    const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0) | (fp8_gemm_on && fp8_scaled_on ? 2048 : 0);
+                    const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0) | (fp8_gemm_on && fp8_scaled_on ? 2048 : 0) | (scores_on ? 4096 : 0);
                     auto it = bgraphs.find(key);
                     if (it == bgraphs.end())      // (a failed capture leaves no entry behind)
                         it = bgraphs.emplace(key, capture_graph([&] { decode_ops_batched(B, pen); })).first;
@@ -1705,6 +1777,7 @@ public:
         }
         HIP_CHECK(hipEventRecord(ph_ev[3], st));
         HIP_CHECK(hipMemcpyAsync(h_tok_b + head0, d_tok_b, n_head * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (scores_on) HIP_CHECK(hipMemcpyAsync(h_score_b + head0, d_score_b, n_head * sizeof(float), hipMemcpyDeviceToHost, st));      // (never split: the switches exclude each other)
         HIP_CHECK(hipStreamSynchronize(st));
         LAUNCH_CHECK("batch_step");
         {
@@ -1734,6 +1807,7 @@ public:
                 tok = h_tok_b[hq + i];
                 REQUIRE(tok >= 0 && tok < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
                 j.out.push_back(tok);
+                if (j.scored) j.scores.push_back(h_score_b[hq + i]);
                 j.count += 1;
                 ++emitted;
                 stop = j.count >= j.max_new;
@@ -1783,6 +1857,7 @@ public:
         for (int s = 0; s < n_envs; ++s)
             for (int t = 0; t < s; ++t) REQUIRE(env_ids[t] != env_ids[s], "duplicate env in batch");
         std::vector<int> slots(n_envs);
+        gb_scores_valid = false;
         try {
             for (int s = 0; s < n_envs; ++s) slots[s] = batch_submit(env_ids[s], max_new < cap ? max_new : cap, eos, n_eos);
             int32_t fin[MAXB], nf = 0;
@@ -1791,10 +1866,13 @@ public:
             for (int k = 0; k < MAXB; ++k) drop_job(k);
             throw;
         }
+        gb_scores.assign(n_envs, std::vector<float>());
         for (int s = 0; s < n_envs; ++s) {
             int32_t env = 0;
+            if (scores_on) gb_scores[s] = jobs[slots[s]].scores;
             batch_result(slots[s], &env, out + (size_t)s * cap, cap, &n_out[s]);
         }
+        gb_scores_valid = scores_on;          // (only once every env's scores are in place)
     }
     void get_hidden_batch(int slot, float* out, int max_rows, int32_t* n_rows) override {
         REQUIRE(slot >= 0 && slot < MAXB, "slot");
@@ -1817,6 +1895,7 @@ public:
     // enqueued past the end of the generation are no-ops (every kernel checks the done flag).
     void generate(int env, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, bool fixed) override {
         Env& e = env_at(env);
+        last_scores_valid = false;
         const bool had_draft = disarm_draft(env);      // consumed by this call whether it helps, is ignored or the call fails
         REQUIRE(weights_missing() == 0, g_err);
         const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
@@ -1959,6 +2038,7 @@ public:
             if (decoded) HIP_CHECK(hipEventRecord(ph_ev[4], st));
             HIP_CHECK(hipMemcpyAsync(h_ctl, d_ctl, sizeof(GenCtl), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipMemcpyAsync(h_out_ids, d_out_ids, (size_t)enq * sizeof(int), hipMemcpyDeviceToHost, st));
+            if (scores_on) HIP_CHECK(hipMemcpyAsync(h_scores, d_scores, (size_t)enq * sizeof(float), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipMemcpyAsync(h_top2, d_top2, 2 * sizeof(float), hipMemcpyDeviceToHost, st));
             if (persistent_on) HIP_CHECK(hipMemcpyAsync(h_giveup, dl_giveup, sizeof(unsigned), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
@@ -1980,6 +2060,7 @@ public:
             REQUIRE(steps > 0, "sequence exceeds max_positions during decode");
         }
         for (int k = 0; k < n; ++k) out[k] = h_out_ids[k];
+        if (scores_on) { last_scores.assign(h_scores, h_scores + n); last_scores_valid = true; }      // (the draft modes are off: every id left the scored arg-max step)
         e.kv_len = L + n - 1;             // EOS (or the last token) is appended to the ids but never fed
         {
             float t = 0.f;
@@ -2162,6 +2243,7 @@ public:
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_mxfp4_batched cannot change while scheduler turns are in flight");
         if (!enable) { drop_graphs(); mx4b_on = false; return; }
         refuse_while_speculative("svln_set_mxfp4_batched");
+        refuse_while_scores("svln_set_mxfp4_batched");
         REQUIRE(sizeof(T) == 2, "svln_set_mxfp4_batched: MXFP4 weights need the bf16 engine");
         REQUIRE(!fp8_on, "svln_set_mxfp4_batched: the e4m3 decode weights are on (svln_set_fp8_decode); switch them off first");
         REQUIRE(!fp8_gemm_on, "svln_set_mxfp4_batched: the e4m3 MFMA products are on (svln_set_fp8_gemm); switch them off first");
@@ -2308,6 +2390,60 @@ public:
             if (host_token) *host_token = t;
         }
         sync();
+    }
+    // TEST-ONLY: one lm_head product in its plain (host_logprob null: EPI_ARGMAX) or scored (EPI_ARGMAX_LSE) form with optional penalty flags
+    void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob) override {
+        REQUIRE(a.w8 == nullptr || sizeof(T) == 2, "fp8 weights need the bf16 engine");
+        REQUIRE(a.w4 == nullptr || sizeof(T) == 2, "MXFP4 weights need the bf16 engine");
+        const int chunk = a.w4 ? 32 : a.w8 ? 16 : Elt<T>::PER_CHUNK;
+        REQUIRE(a.x && host_token && (a.w4 ? a.e8 != nullptr : a.w8 ? a.scale != nullptr : a.W != nullptr), "null pointer");
+        REQUIRE(a.N >= 1 && a.K >= chunk && a.K % chunk == 0, "N >= 1, K a positive multiple of the format's 16-byte chunk");
+        REQUIRE(a.ldw >= a.K && a.ldw % chunk == 0, "ldw >= K, a multiple of the format's 16-byte chunk (aligned row loads)");
+        REQUIRE((size_t)a.K * sizeof(float) <= (size_t)GEMV_ROWS_MAX_LDS, "the wave-per-rows kernel stages K fp32 activations in LDS: K too large");
+        REQUIRE(!a.pen_flags || a.pen > 0.0f, "penalty flags need a factor > 0");
+        a.epi = host_logprob ? EPI_ARGMAX_LSE : EPI_ARGMAX;
+        a.part_val = part_val; a.part_idx = part_idx; a.part_sum = part_sum;
+        launch_gemv<T>(st, a);
+        launch_argmax_final(st, part_val, part_idx, gemv_grid(a.N), d_token, d_top2, host_logprob ? part_sum : nullptr, d_scores);
+        if (host_logprob) HIP_CHECK(hipMemcpyAsync(h_scores, d_scores, sizeof(float), hipMemcpyDeviceToHost, st));
+        *host_token = read_token();
+        if (host_logprob) *host_logprob = h_scores[0];
+        LAUNCH_CHECK("op_gemv_scores");
+    }
+    void batched_scores_out(int B, int32_t* host_tokens, float* host_logprobs, const char* who) {
+        HIP_CHECK(hipMemcpyAsync(h_tok_b, d_tok_b, B * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (host_logprobs) HIP_CHECK(hipMemcpyAsync(h_score_b, d_score_b, B * sizeof(float), hipMemcpyDeviceToHost, st));
+        sync();
+        LAUNCH_CHECK(who);
+        for (int b = 0; b < B; ++b) { host_tokens[b] = h_tok_b[b]; if (host_logprobs) host_logprobs[b] = h_score_b[b]; }
+    }
+    void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs) override {
+        REQUIRE(a.W && a.x && host_tokens, "null pointer");
+        REQUIRE(a.B == 1 || a.B == 2 || a.B == 4 || a.B == 8, "B must be 1, 2, 4 or 8");
+        REQUIRE(a.N >= 1 && a.K >= Elt<T>::PER_CHUNK && a.K % Elt<T>::PER_CHUNK == 0, "N >= 1, K a positive multiple of the 16-byte chunk");
+        REQUIRE(a.ldw >= a.K && a.ldw % Elt<T>::PER_CHUNK == 0 && a.ldx >= a.K && a.ldx % Elt<T>::PER_CHUNK == 0, "ldw, ldx >= K, multiples of the 16-byte chunk");
+        REQUIRE(!a.pen_flags || (a.pen_rows && a.pen > 0.0f), "penalty flags come with their row table and a factor > 0");
+        a.epi = host_logprobs ? EPI_ARGMAX_LSE : EPI_ARGMAX;
+        a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b;
+        a.row_scale = row_scale_b;
+        launch_gemv_batched<T>(st, a);
+        launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), a.B, d_tok_b, host_logprobs ? part_sum_b : nullptr, d_score_b,
+                                    host_logprobs && a.norm_w ? a.row_scale : nullptr);
+        batched_scores_out(a.B, host_tokens, host_logprobs, "op_gemv_batched_scores");
+    }
+    void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs) override {
+        constexpr int chunk = Elt<T>::PER_CHUNK;
+        REQUIRE(a.A && a.W && host_tokens, "null pointer");
+        REQUIRE(a.M >= 1 && a.M <= 32 && a.N >= 1 && (a.N + 127) / 128 <= 2048, "1 <= M <= 32 rows, 1 <= N <= 262144");
+        REQUIRE(a.K >= chunk && a.K % chunk == 0 && a.lda >= a.K && a.ldw >= a.K && a.lda % chunk == 0 && a.ldw % chunk == 0,
+                "K a positive multiple of the 16-byte chunk; lda, ldw >= K, multiples of it (aligned LDS-DMA)");
+        REQUIRE(((size_t)a.A & 15) == 0 && ((size_t)a.W & 15) == 0, "A and W must be 16-byte aligned (LDS-DMA)");
+        REQUIRE(!a.pen_flags || (a.pen_rows && a.pen > 0.0f), "penalty flags come with their row table and a factor > 0");
+        a.zeros = zero_line; a.epi = EPI_ARGMAX;
+        a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = host_logprobs ? part_sum_b : nullptr;
+        const int n = launch_gemm_argmax<T>(st, a);
+        launch_argmax_final_batched(st, part_val_b, part_idx_b, n, a.M, d_tok_b, a.part_sum, d_score_b);
+        batched_scores_out(a.M, host_tokens, host_logprobs, "op_gemm_argmax_scores");
     }
     void op_gemv_batched(GemvBatchArgs a, int32_t* host_tokens) override {
         REQUIRE(a.B == 1 || a.B == 2 || a.B == 4 || a.B == 8, "B must be 1, 2, 4 or 8");
@@ -2737,6 +2873,48 @@ int svln_get_layer_probe(svln_engine* h, int which, float* out, int64_t max_elem
 int svln_get_embeds(svln_engine* h, int env, int start, int n, float* out) { API_BEGIN_H h->impl->get_embeds(env, start, n, out); API_END }
 int svln_get_frame_feats(svln_engine* h, int start, int n, float* out) { API_BEGIN_H h->impl->get_feats(start, n, out); API_END }
 int svln_get_top2(svln_engine* h, float* out) { API_BEGIN_H h->impl->get_top2(out); API_END }
+int svln_set_token_scores(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_token_scores(enable); API_END }
+int svln_get_token_scores(svln_engine* h, float* out, int cap, int32_t* n) {
+    API_BEGIN_H REQUIRE(out && n && cap >= 0, "null output pointer"); h->impl->get_token_scores(out, cap, n); API_END
+}
+int svln_batch_scores(svln_engine* h, int slot, float* out, int cap, int32_t* n) {
+    API_BEGIN_H REQUIRE(out && n && cap >= 0, "null output pointer"); h->impl->batch_scores(slot, out, cap, n); API_END
+}
+int svln_generate_batch_scores(svln_engine* h, int index, float* out, int cap, int32_t* n) {
+    API_BEGIN_H REQUIRE(out && n && cap >= 0, "null output pointer"); h->impl->generate_batch_scores(index, out, cap, n); API_END
+}
+int svln_op_gemv_argmax_scores(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
+                               float penalty, int32_t* host_token, float* host_logprob) {
+    API_BEGIN_H
+    REQUIRE(fmt >= 0 && fmt <= 2, "fmt: 0 = engine dtype, 1 = e4m3 + row scales, 2 = MXFP4");
+    GemvArgs a; a.W = nullptr; a.ldw = ldw; a.x = x; a.norm_w = nullptr; a.eps = 0.0f; a.bias = nullptr; a.res = nullptr; a.y = nullptr; a.N = N; a.K = K;
+    a.epi = EPI_ARGMAX; a.part_val = nullptr; a.part_idx = nullptr; a.w8 = nullptr; a.scale = nullptr; a.skip = nullptr;
+    if (fmt == 0) a.W = W;
+    else if (fmt == 1) { a.w8 = W; a.scale = (const float*)aux; }
+    else { a.w4 = W; a.e8 = (const uint8_t*)aux; }
+    REQUIRE(W, "null pointer");
+    a.pen_flags = (const uint8_t*)pen_flags; a.pen = penalty;
+    h->impl->op_gemv_scores(a, host_token, host_logprob);
+    API_END
+}
+int svln_op_gemv_batched_argmax_scores(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
+                                       const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs) {
+    API_BEGIN_H
+    GemvBatchArgs a; a.W = W; a.ldw = ldw; a.x = x; a.ldx = ldx; a.norm_w = norm_w; a.eps = eps; a.bias = nullptr; a.res = nullptr; a.ldr = 0;
+    a.y = nullptr; a.ldy = 0; a.N = N; a.K = K; a.epi = EPI_ARGMAX; a.B = B; a.part_val = nullptr; a.part_idx = nullptr;
+    a.pen_flags = (const uint8_t*)pen_flags; a.pen_rows = pen_rows; a.pen = penalty;
+    h->impl->op_gemv_batched_scores(a, host_tokens, host_logprobs);
+    API_END
+}
+int svln_op_gemm_argmax_scores(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
+                               const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs) {
+    API_BEGIN_H
+    GemmArgs a; std::memset(&a, 0, sizeof(a));
+    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.epi = EPI_ARGMAX; a.nsplit = 1;
+    a.pen_flags = (const uint8_t*)pen_flags; a.pen_rows = pen_rows; a.pen = penalty;
+    h->impl->op_gemm_argmax_scores(a, host_tokens, host_logprobs);
+    API_END
+}
 int svln_set_decode_graph(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_graph(enable); API_END }
 int svln_set_decode_persistent(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_decode_persistent(enable); API_END }
 int svln_probe_decode_layer(svln_engine* h, int layer, unsigned long long* out, int max_wgs, int32_t* n_wgs) {

@@ -279,8 +279,10 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
     const int gw = blockIdx.x * GEMV_WAVES + wave, nw = gridDim.x * GEMV_WAVES;
     const int n_out = EPI == EPI_SWIGLU ? p.N >> 1 : p.N;
 
+    constexpr bool AMAX = epi_is_argmax(EPI), LSE = EPI == EPI_ARGMAX_LSE;
     float best = -INFINITY;                       // EPI_ARGMAX
     int best_i = 0x7FFFFFFF;
+    float lm = -INFINITY, ls = 0.0f;              // EPI_ARGMAX_LSE: wave-uniform (max, sum exp(l - max)) over the wave's rows
     for (int n0 = gw * OUTS; n0 < n_out; n0 += nw * OUTS) {
         size_t rn[R];                             // the group's weight rows; a ragged last group repeats the last output's rows
 #pragma unroll
@@ -302,7 +304,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
                 const float gt = lane == 0 ? acc[0] : acc[2], up = lane == 0 ? acc[1] : acc[3];
                 ((X*)p.y)[n0 + lane] = from_f32<X>(silu_f(gt) * up);
             }
-        } else if (EPI == EPI_ARGMAX) {
+        } else if (AMAX) {
             if (p.pen_flags) {
 #pragma unroll
                 for (int r = 0; r < R; ++r)
@@ -311,15 +313,35 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
 #pragma unroll
             for (int r = 0; r < R; ++r)
                 if (n0 + r < p.N && acc[r] > best) { best = acc[r]; best_i = n0 + r; }     // rows ascend: first max wins
+            if (LSE) {                            // the penalised values; the repeated rows of a ragged last group (n0 + r >= N) count once
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    if (n0 + r < p.N) lse_add(acc[r], lm, ls);
+            }
         } else if (lane < R && n0 + lane < p.N) {
             store_out<X>(p, n0 + lane, lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3]);
         }
     }
-    if (EPI == EPI_ARGMAX) {
+    if (AMAX) {
         __shared__ float bv[GEMV_WAVES];
         __shared__ int bi[GEMV_WAVES];
         if (lane == 0) { bv[wave] = best; bi[wave] = best_i; }
-        __syncthreads();
+        if constexpr (LSE) {
+            __shared__ float bs[GEMV_WAVES];
+            if (lane == 0) bs[wave] = ls;         // (lm == best: the same compares in the same order)
+            __syncthreads();
+            if (threadIdx.x == 0) {               // a wave without a row is (-inf, 0) and adds 0
+                float v = bv[0];
+#pragma unroll
+                for (int w = 1; w < GEMV_WAVES; ++w) v = bv[w] > v ? bv[w] : v;
+                float sum = 0.0f;
+#pragma unroll
+                for (int w = 0; w < GEMV_WAVES; ++w) sum += lse_rescale(bs[w], bv[w], v);
+                p.part_sum[blockIdx.x] = sum;
+            }
+        } else {
+            __syncthreads();
+        }
         if (threadIdx.x == 0) {
             float v = bv[0]; int i = bi[0];
 #pragma unroll
@@ -416,8 +438,10 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
     const T* xg = (const T*)p.x;
     const T* gg = (const T*)p.norm_w;
     const int n_units = EPI == EPI_SWIGLU ? p.N / R : (p.N + R - 1) / R;      // one unit = R weight rows
+    constexpr bool AMAX = epi_is_argmax(EPI), LSE = EPI == EPI_ARGMAX_LSE;
     float best = -INFINITY;                                                   // EPI_ARGMAX: thread b < B tracks env b
     int best_i = 0x7FFFFFFF;
+    float lm = -INFINITY, ls = 0.0f;                                          // EPI_ARGMAX_LSE: env b's (max, sum exp(l - max)) over the workgroup's units
     for (int u = blockIdx.x; u < n_units; u += gridDim.x) {
         const T* rows[R];
         int n0;
@@ -506,7 +530,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
                 const float gt = total((2 * o) * B + b) * sc, up = total((2 * o + 1) * B + b) * sc;
                 ((T*)p.y)[(size_t)b * p.ldy + n0 + o] = from_f32<T>(silu_f(gt) * up);
             }
-        } else if (EPI == EPI_ARGMAX) {
+        } else if (AMAX) {
             if (tid < B) {
                 const uint8_t* fl = p.pen_flags ? p.pen_flags + (size_t)p.pen_rows[tid] * p.N : nullptr;
 #pragma unroll
@@ -514,6 +538,10 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
                     float v = total(r * B + tid);
                     if (fl && n0 + r < p.N && fl[n0 + r]) v = v < 0.0f ? v * p.pen : v / p.pen;
                     if (n0 + r < p.N && v > best) { best = v; best_i = n0 + r; }      // units ascend per workgroup: first max wins
+                    // (the clamped rows of the last unit count once.  The arg-max ignores a fused norm's positive row factor, as the plain
+                    // form does; a probability cannot: the SUM takes fl(v * factor), whose maximum is fl(best * factor) -- rounding is
+                    // monotone -- so the final kernel rebuilds the partial's maximum from part_val and row_scale[b])
+                    if (LSE && n0 + r < p.N) lse_add(NORM ? v * rsqrtf(total(R * B + tid) / (float)p.K + p.eps) : v, lm, ls);
                 }
             }
         } else if (tid < R * B) {
@@ -528,14 +556,34 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
         }
         __syncthreads();
     }
-    if (EPI == EPI_ARGMAX && tid < B) {
+    if (AMAX && tid < B) {
         p.part_val[(size_t)tid * gridDim.x + blockIdx.x] = best;
         p.part_idx[(size_t)tid * gridDim.x + blockIdx.x] = best_i;
+        if (LSE) {
+            p.part_sum[(size_t)tid * gridDim.x + blockIdx.x] = ls;
+            // every workgroup computes the same factor from the same sums in the same order: workgroup 0 publishes it
+            if (NORM && blockIdx.x == 0) p.row_scale[tid] = rsqrtf((part[0][R * B + tid] + part[1][R * B + tid] + part[2][R * B + tid] + part[3][R * B + tid]) / (float)p.K + p.eps);
+        }
     }
 }
 
+// S = sum over the 256 threads' shares `mine` of the rescaled partial sums, through `red` (a fixed tree: the same bits every launch)
+SVLN_DEV float block_sum_256(float mine, float* red) {
+    red[threadIdx.x] = mine;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
 // final arg-max of env b = blockIdx.x over its per-workgroup partials
-__global__ __launch_bounds__(256) void argmax_final_batched_kernel(const float* pv, const int* pi, int n, int* out_tokens) {
+// LSE: also env b's log-probability of that token from its partial sums ps (NaN for token -1); rs (optional): the positive factor of
+// row b by which the producer scaled the logits it summed (a fused norm), so that partial k's maximum there is fl(pv[k] * rs[b])
+template <bool LSE>
+__global__ __launch_bounds__(256) void argmax_final_batched_kernel(const float* pv, const int* pi, int n, int* out_tokens, const float* ps,
+                                                                   float* scores, const float* rs) {
     __shared__ float sv[256];
     __shared__ int si[256];
     const float* v0 = pv + (size_t)blockIdx.x * n;
@@ -558,6 +606,16 @@ __global__ __launch_bounds__(256) void argmax_final_batched_kernel(const float* 
         __syncthreads();
     }
     if (threadIdx.x == 0) out_tokens[blockIdx.x] = si[0] == 0x7FFFFFFF ? -1 : si[0];    // no finite logit: -1 (in-range for the next gather, an error on the host)
+    if (LSE) {
+        const float sc = rs ? rs[blockIdx.x] : 1.0f;
+        const float V = sv[0] * sc;
+        const int tok = si[0];
+        __syncthreads();                          // sv is reused by the sum
+        float mine = 0.0f;
+        for (int k = threadIdx.x; k < n; k += 256) mine += lse_rescale(ps[(size_t)blockIdx.x * n + k], v0[k] * sc, V);
+        const float S = block_sum_256(mine, sv);
+        if (threadIdx.x == 0) scores[blockIdx.x] = tok == 0x7FFFFFFF ? __builtin_nanf("") : lse_logprob(S);
+    }
 }
 
 // per-row e4m3 quantisation: one workgroup per row, scale = max|w| / 448 (1 for an all-zero row), round-to-nearest-even
@@ -635,8 +693,10 @@ __global__ __launch_bounds__(256) void quant_mxfp4_rows_kernel(const bf16* w, in
 
 // final arg-max over per-workgroup partials: greatest value, lowest index on ties (torch.argmax on CPU)
 // With `ctl` it is also one step of the greedy loop (GenerationMixin._sample: append, stop on EOS / max_new_tokens): see GenCtl.
+// LSE: also the token's log-probability from the partial sums ps, to scores[ctl->count] before the count advances (scores[0] without ctl)
+template <bool LSE>
 __global__ __launch_bounds__(256) void argmax_final_kernel(const float* pv, const int* pi, int n, int* out_token, float* out_top, GenCtl* ctl,
-                                                           const int* eos, int* out_ids, uint8_t* pen_flags) {
+                                                           const int* eos, int* out_ids, uint8_t* pen_flags, const float* ps, float* scores) {
     __shared__ float sv[256];
     if (ctl && ctl->done) return;
     __shared__ int si[256];
@@ -665,6 +725,14 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const float* pv, cons
     if (threadIdx.x == 0) {
         *out_token = tok;
         if (out_top) { out_top[0] = sv[0]; out_top[1] = s2[0]; }
+    }
+    if (LSE) {
+        const float V = sv[0];
+        __syncthreads();                          // sv / s2 have been read: s2 is reused by the sum
+        float mine = 0.0f;
+        for (int k = threadIdx.x; k < n; k += 256) mine += lse_rescale(ps[k], pv[k], V);
+        const float S = block_sum_256(mine, s2);
+        if (threadIdx.x == 0) scores[ctl ? ctl->count : 0] = tok < 0 ? __builtin_nanf("") : lse_logprob(S);
     }
     if (ctl) {
         int hit = 0;
@@ -724,6 +792,7 @@ template <typename P> static void launch_gemv_fmt(hipStream_t s, const GemvArgs&
         case EPI_NONE: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_NONE>), g, b, lds); break;
         case EPI_SWIGLU: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SWIGLU>), g, b, lds); break;
         case EPI_ARGMAX: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX>), g, b, lds); break;
+        case EPI_ARGMAX_LSE: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX_LSE>), g, b, lds); break;
         default: break;
     }
 }
@@ -756,13 +825,16 @@ template <typename T> void launch_gemv_batched(hipStream_t s, const GemvBatchArg
         case EPI_NONE: if (norm) launch_gb<T, EPI_NONE, true>(s, a); else launch_gb<T, EPI_NONE, false>(s, a); break;
         case EPI_SWIGLU: if (norm) launch_gb<T, EPI_SWIGLU, true>(s, a); else launch_gb<T, EPI_SWIGLU, false>(s, a); break;
         case EPI_ARGMAX: if (norm) launch_gb<T, EPI_ARGMAX, true>(s, a); else launch_gb<T, EPI_ARGMAX, false>(s, a); break;
+        case EPI_ARGMAX_LSE: if (norm) launch_gb<T, EPI_ARGMAX_LSE, true>(s, a); else launch_gb<T, EPI_ARGMAX_LSE, false>(s, a); break;
         default: break;
     }
 }
 template void launch_gemv_batched<bf16>(hipStream_t, const GemvBatchArgs&);
 template void launch_gemv_batched<float>(hipStream_t, const GemvBatchArgs&);
-void launch_argmax_final_batched(hipStream_t s, const float* pv, const int* pi, int n, int B, int* out_tokens) {
-    hipLaunchKernelGGL(argmax_final_batched_kernel, dim3(B), dim3(256), 0, s, pv, pi, n, out_tokens);
+void launch_argmax_final_batched(hipStream_t s, const float* pv, const int* pi, int n, int B, int* out_tokens, const float* ps, float* scores,
+                                 const float* rs) {
+    if (ps) hipLaunchKernelGGL(argmax_final_batched_kernel<true>, dim3(B), dim3(256), 0, s, pv, pi, n, out_tokens, ps, scores, rs);
+    else hipLaunchKernelGGL(argmax_final_batched_kernel<false>, dim3(B), dim3(256), 0, s, pv, pi, n, out_tokens, ps, scores, rs);
 }
 template void launch_gemv_timed<bf16>(hipStream_t, const GemvArgs&, hipEvent_t, hipEvent_t);
 template void launch_gemv_timed<float>(hipStream_t, const GemvArgs&, hipEvent_t, hipEvent_t);
@@ -777,6 +849,7 @@ template <typename P> static void gemv_rows_attrs() {
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_NONE>, GEMV_ROWS_MAX_LDS);
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_SWIGLU>, GEMV_ROWS_MAX_LDS);
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX>, GEMV_ROWS_MAX_LDS);
+    set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX_LSE>, GEMV_ROWS_MAX_LDS);
 }
 void gemv_init_attrs() {
     gemv_rows_attrs<WMxfp4>(); gemv_rows_attrs<WE4m3>(); gemv_rows_attrs<WPlain<bf16>>(); gemv_rows_attrs<WPlain<float>>();
@@ -784,13 +857,13 @@ void gemv_init_attrs() {
 template void launch_gemv<bf16>(hipStream_t, const GemvArgs&);
 template void launch_gemv<float>(hipStream_t, const GemvArgs&);
 
-void launch_argmax_final(hipStream_t s, const float* pv, const int* pi, int n, int* out_token, float* out_top) {
-    hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, s, pv, pi, n, out_token, out_top, (GenCtl*)nullptr, (const int*)nullptr, (int*)nullptr,
-                       (uint8_t*)nullptr);
-}
 void launch_argmax_step(hipStream_t s, const float* pv, const int* pi, int n, int* out_token, float* out_top, GenCtl* ctl, const int* eos,
-                        int* out_ids, uint8_t* pen_flags) {
-    hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, s, pv, pi, n, out_token, out_top, ctl, eos, out_ids, pen_flags);
+                        int* out_ids, uint8_t* pen_flags, const float* ps, float* scores) {
+    if (ps) hipLaunchKernelGGL(argmax_final_kernel<true>, dim3(1), dim3(256), 0, s, pv, pi, n, out_token, out_top, ctl, eos, out_ids, pen_flags, ps, scores);
+    else hipLaunchKernelGGL(argmax_final_kernel<false>, dim3(1), dim3(256), 0, s, pv, pi, n, out_token, out_top, ctl, eos, out_ids, pen_flags, ps, scores);
+}
+void launch_argmax_final(hipStream_t s, const float* pv, const int* pi, int n, int* out_token, float* out_top, const float* ps, float* scores) {
+    launch_argmax_step(s, pv, pi, n, out_token, out_top, nullptr, nullptr, nullptr, nullptr, ps, scores);
 }
 namespace {
 __global__ __launch_bounds__(256) void set_flags_kernel(uint8_t* flags, const int* ids, const int* count, int n_host, int value) {

@@ -188,6 +188,7 @@ class StreamVLNForCausalLM:
         self._tickets: Dict[int, tuple] = {}
         self._auto_draft = False                                   # set_auto_draft: guess that a turn repeats the env's previous one
         self._last_out: Dict[int, torch.Tensor] = {}
+        self._token_scores = False                                 # set_token_scores: results carry token_logprobs
         self._batch_draft = False                                  # set_batch_draft: the scheduler consumes drafts
         self.reset(max_envs)
 
@@ -489,12 +490,23 @@ class StreamVLNForCausalLM:
         seq = torch.from_numpy(np.asarray(tokens, dtype=np.int64).copy()).unsqueeze(0).to(dev)
         return GenerateOutput(sequences=seq, past_key_values=KVHandle(env_id, self._epoch[env_id], kl.value))
 
+    def _scores(self, getter, *args, n_new, device):
+        """token_logprobs [1, n_new] (fp32, on `device`) of a finished turn from one of the engine's score getters"""
+        buf = np.empty(max(n_new, 1), dtype=np.float32)
+        n = C.c_int32()
+        _check(getter(self._h, *args, buf.ctypes.data_as(C.POINTER(C.c_float)), int(buf.size), C.byref(n)))
+        if n.value != n_new:
+            raise RuntimeError(f"the engine holds {n.value} token scores for a turn of {n_new} ids")
+        return torch.from_numpy(buf[:n_new].copy()).unsqueeze(0).to(device)
+
     @torch.no_grad()
     def generate(self, inputs=None, images=None, image_sizes=None, depths=None, poses=None, intrinsics=None, task_ids=None,
                  draft_ids=None, **kwargs):
         """One model turn = ONE crossing into the engine (svln_turn: encode_rgbd, the KV / embeds bookkeeping of the reference's generate,
         splice, prefill + greedy decode).  draft_ids (optional, set_speculative / set_prefill_draft): a guess of this turn's whole id sequence; with
-        set_auto_draft(True) and no explicit draft, the env's previous turn output is the guess."""
+        set_auto_draft(True) and no explicit draft, the env's previous turn output is the guess.
+        While set_token_scores is on the result also carries `token_logprobs`, fp32 [1, n_new] aligned with `sequences` (see there).  HF's
+        `output_scores` / `output_logits` stay ignored: a [n_new, vocab] tensor is exactly what this engine exists not to build."""
         draft = draft_ids
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
         self._sync_call_config()
@@ -529,7 +541,10 @@ class StreamVLNForCausalLM:
             self._last_out[env_id] = seq[0].clone()
         if dev != "cpu" and str(dev) != "cpu":
             seq = seq.to(dev)
-        return GenerateOutput(sequences=seq, past_key_values=KVHandle(env_id, self._epoch[env_id], buf["kv"].value))
+        res = GenerateOutput(sequences=seq, past_key_values=KVHandle(env_id, self._epoch[env_id], buf["kv"].value))
+        if self._token_scores:
+            res["token_logprobs"] = self._scores(self._lib.svln_get_token_scores, n_new=int(seq.shape[1]), device=seq.device)
+        return res
 
     def _arm_batch_draft(self, env_id, draft):
         """set_batch_draft on: arm env_id's draft for the submit that follows -- explicit ids, or the env's previous output under
@@ -543,8 +558,10 @@ class StreamVLNForCausalLM:
         d_np = np.ascontiguousarray(torch.as_tensor(draft).reshape(-1).to("cpu", torch.int64).numpy())
         _check(self._lib.svln_set_draft(self._h, self._slot(env_id), d_np.ctypes.data_as(C.POINTER(C.c_int64)), int(d_np.size)))
 
-    def _batch_result(self, env_id, tokens, inputs):
+    def _batch_result(self, env_id, tokens, inputs, scores=None):
         res = self._result(env_id, tokens, inputs)
+        if scores is not None:
+            res["token_logprobs"] = scores.to(res.sequences.device)
         if self._auto_draft:
             self._last_out[env_id] = res.sequences[0].to("cpu").clone()
         return res
@@ -621,7 +638,10 @@ class StreamVLNForCausalLM:
         _check(self._lib.svln_generate_batch(self._h, envs.ctypes.data_as(C.POINTER(C.c_int32)), len(parsed), max_new,
                                              eos_np.ctypes.data_as(C.POINTER(C.c_int64)), eos_np.size,
                                              out.ctypes.data_as(C.POINTER(C.c_int64)), cap, n_out.ctypes.data_as(C.POINTER(C.c_int32))))
-        return [self._batch_result(p[5], out[k, : n_out[k]], requests[k].get("inputs")) for k, p in enumerate(parsed)]
+        scores = [None] * len(parsed)
+        if self._token_scores:
+            scores = [self._scores(self._lib.svln_generate_batch_scores, k, n_new=int(n_out[k]), device="cpu") for k in range(len(parsed))]
+        return [self._batch_result(p[5], out[k, : n_out[k]], requests[k].get("inputs"), scores[k]) for k, p in enumerate(parsed)]
 
     # ---- iteration-level scheduler: envs whose turns fall due at different times (streamvln_dagger.py:232-313) ----
     @torch.no_grad()
@@ -674,9 +694,15 @@ class StreamVLNForCausalLM:
         for k in range(nf.value):
             out = np.zeros(cap, dtype=np.int64)
             n, env = C.c_int32(), C.c_int32()
+            scores = None
+            if self._token_scores:             # (valid until svln_batch_result frees the slot; a turn holds at most max_new <= cap ids)
+                ns = C.c_int32()
+                sbuf = np.empty(cap, dtype=np.float32)
+                _check(self._lib.svln_batch_scores(self._h, fin[k], sbuf.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(ns)))
+                scores = torch.from_numpy(sbuf[: ns.value].copy()).unsqueeze(0)
             _check(self._lib.svln_batch_result(self._h, fin[k], C.byref(env), out.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n)))
             env_id, inputs = self._tickets.pop(fin[k])
-            done.append((SimpleNamespace(env_id=env_id, slot=fin[k]), self._batch_result(env_id, out[: n.value], inputs)))
+            done.append((SimpleNamespace(env_id=env_id, slot=fin[k]), self._batch_result(env_id, out[: n.value], inputs, scores)))
         return done, running.value
 
     def cancel(self, ticket=None):
@@ -805,6 +831,17 @@ class StreamVLNForCausalLM:
         v = [C.c_int64() for _ in range(3)]
         _check(self._lib.svln_prefill_draft_stats(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), int(reset)))
         return tuple(int(x.value) for x in v)
+
+    def set_token_scores(self, enable: bool):
+        """Opt-in, default off (svln_set_token_scores): while on, every GenerateOutput of generate / generate_batch / step_batch carries
+        `token_logprobs`: fp32 [1, n_new] on the device of `sequences`, the log-probability (log softmax over the processed fp32 logits,
+        after the repetition penalty) the model gave each id it emitted.  The lm_head kernels compute it beside their fused arg-max: no
+        logits in memory, no second pass over the lm_head, the ids unchanged bit for bit.  While off the key is absent.  HF's
+        `output_scores` / `output_logits` stay ignored: a [n_new, vocab] tensor is exactly what this engine exists not to build.
+        Refused with set_speculative / set_prefill_draft / set_batch_draft, set_decode_persistent and set_mxfp4_batched (and they while
+        it is on), and while scheduler turns are in flight."""
+        _check(self._lib.svln_set_token_scores(self._h, int(bool(enable))))
+        self._token_scores = bool(enable)
 
     def set_batch_draft(self, enable: bool):
         """opt-in drafts in the scheduler's prefill pass (svln_set_batch_draft): the first ids of a turn's draft (`draft_ids` of submit /
