@@ -164,6 +164,23 @@ int svln_get_top2(svln_engine* h, float* host_out2);       /* refused when the l
  * frees the slot.  svln_generate_batch_scores: those of env index `index` (its place in the envs list) of the last svln_generate_batch.
  * All three fail, with svln_last_error saying so, when the switch was off for that turn. */
 int svln_set_token_scores(svln_engine* h, int enable);
+/* Opt-in, default off, no reference counterpart: temperature sampling.  While on, every lm_head product runs a sibling kernel
+ * (EPI_SAMPLE) and token t of an env is  argmax_n ( fl(x_n * invT) + G(seed, stream, draw, n) ),  lowest column on ties, -1 for a row
+ * with no finite value: by the Gumbel-max identity an exact sample of softmax(x / T).  x_n is the PROCESSED fp32 logit (after the
+ * repetition penalty: processors before warpers, as HF), invT = fl(1 / temperature) computed once on the host, stream = the engine env
+ * slot, draw = the number of tokens that env has emitted since the last svln_set_sampling call.  The noise is a pure function of
+ * (seed, stream, draw, column) -- Philox4x32-10 on counter (column, draw, stream, 0) and key (seed lo, seed hi), output word 0 = w;
+ * u = ((w >> 9) + 0.5) * 2^-23; G = -ln(-ln u) -- so svln_generate, svln_generate_batch and the scheduler emit the same ids for the
+ * same seed wherever their logits agree.  No logit reaches memory and the lm_head is not read twice.
+ * The sampled kernels also compute log softmax(x / T)[token]; it is delivered through the svln_set_token_scores getters while that
+ * switch is on (HF's `scores` under sampling).
+ * enable != 0 requires a finite temperature > 0.  EVERY call, on or off, resets every env's draw counter to 0 and drops the captured
+ * decode graphs; it is refused while scheduler turns are in flight.  Works with svln_set_fp8_decode, svln_set_mxfp4_decode,
+ * svln_set_fp8_gemm / svln_set_fp8_scaled_mfma, the repetition penalty, svln_set_token_scores, svln_set_memory_prune and
+ * svln_set_feature_cache.  Refused, and each of these refused while it is on: svln_set_speculative, svln_set_prefill_draft,
+ * svln_set_batch_draft (their verify rule is written for greedy rows), svln_set_decode_persistent and svln_set_mxfp4_batched (its
+ * lm_head kernel has no sampled form).  svln_get_top2 is refused after a sampled turn: the values are perturbed, not logits. */
+int svln_set_sampling(svln_engine* h, int enable, float temperature, uint64_t seed);
 int svln_get_token_scores(svln_engine* h, float* host_out, int cap, int32_t* n);
 int svln_batch_scores(svln_engine* h, int slot, float* host_out, int cap, int32_t* n);
 int svln_generate_batch_scores(svln_engine* h, int index, float* host_out, int cap, int32_t* n);
@@ -437,6 +454,20 @@ int svln_op_gemv_batched_argmax_scores(svln_engine* h, const void* W, int ldw, c
                                        const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs);
 int svln_op_gemm_argmax_scores(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
                                const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs);
+/* TEST-ONLY entries: the sampled forms (EPI_SAMPLE, see svln_set_sampling) of the three entries above, on the given temperature, seed
+ * and per-row streams / draws (host values; the engine's own switch and counters are not touched).  host_logprob(s) receive
+ * log softmax(x / T)[token] and must not be null.  The refusals of the entries above apply, plus: temperature not finite or <= 0,
+ * negative streams / draws, and norm_w with the batched form (it has no fused-norm kernel) -- all before any launch.
+ * svln_op_gumbel: host_out[k] = G(seed, stream, draw, n0 + k) for k < count, as the kernels evaluate it. */
+int svln_op_gemv_argmax_sample(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
+                               float penalty, float temperature, uint64_t seed, int32_t stream, int32_t draw, int32_t* host_token, float* host_logprob);
+int svln_op_gemv_batched_argmax_sample(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
+                                       const void* pen_flags, const int32_t* pen_rows, float penalty, float temperature, uint64_t seed,
+                                       const int32_t* streams, const int32_t* draws, int32_t* host_tokens, float* host_logprobs);
+int svln_op_gemm_argmax_sample(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
+                               const int32_t* pen_rows, float penalty, float temperature, uint64_t seed, const int32_t* streams,
+                               const int32_t* draws, int32_t* host_tokens, float* host_logprobs);
+int svln_op_gumbel(svln_engine* h, uint64_t seed, int32_t stream, int32_t draw, int32_t n0, int32_t count, float* host_out);
 int svln_op_rmsnorm(svln_engine* h, const void* x, const void* g, void* y, int rows, int n, float eps);
 int svln_op_layernorm(svln_engine* h, const void* x, const void* g, const void* b, void* y, int rows, int n, float eps);
 /* attention over caller-provided q [T][q_stride] and k/v [S][kv_stride] (engine packs them into pages):

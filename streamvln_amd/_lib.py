@@ -68,7 +68,7 @@ def gemm_plan(**problem) -> SvlnGemmPlan:
     return plan
 
 
-_P, _I, _F, _I64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
+_P, _I, _F, _I64, _U64 = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64
 _PI32, _PI64, _PF, _PD = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_double)
 
 #: every symbol include/streamvln_hip.h declares: name -> (restype, argtypes)
@@ -112,6 +112,7 @@ SIGNATURES = {
     "svln_get_token_scores": (_I, [_P, _PF, _I, _PI32]),
     "svln_batch_scores": (_I, [_P, _I, _PF, _I, _PI32]),
     "svln_generate_batch_scores": (_I, [_P, _I, _PF, _I, _PI32]),
+    "svln_set_sampling": (_I, [_P, _I, _F, _U64]),
     "svln_set_layer_taps": (_I, [_P, _I, _I]),
     "svln_get_layer_taps": (_I, [_P, _PF]),
     "svln_get_layer_probe": (_I, [_P, _I, _PF, _I64, _PI32, _PI32]),
@@ -154,6 +155,10 @@ SIGNATURES = {
     "svln_op_gemv_argmax_scores": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _F, _PI32, _PF]),
     "svln_op_gemv_batched_argmax_scores": (_I, [_P, _P, _I, _P, _I, _P, _F, _I, _I, _I, _P, _P, _F, _PI32, _PF]),
     "svln_op_gemm_argmax_scores": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _PI32, _PF]),
+    "svln_op_gemv_argmax_sample": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _F, _F, _U64, _I, _I, _PI32, _PF]),
+    "svln_op_gemv_batched_argmax_sample": (_I, [_P, _P, _I, _P, _I, _P, _F, _I, _I, _I, _P, _P, _F, _F, _U64, _PI32, _PI32, _PI32, _PF]),
+    "svln_op_gemm_argmax_sample": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _F, _U64, _PI32, _PI32, _PI32, _PF]),
+    "svln_op_gumbel": (_I, [_P, _U64, _I, _I, _I, _I, _PF]),
     "svln_op_rmsnorm": (_I, [_P, _P, _P, _P, _I, _I, _F]),
     "svln_op_layernorm": (_I, [_P, _P, _P, _P, _P, _I, _I, _F]),
     "svln_op_attention_llm": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I]),

@@ -51,8 +51,11 @@ class StreamingAgent:
                  num_history: Optional[int] = 8, env_id: int = 0, device: str = "cpu",
                  image_dtype: torch.dtype = torch.float32, max_new_tokens: int = 10000,
                  eos_token_ids: Sequence[int] = (), decode_actions: Optional[Callable] = None,
-                 preprocess: Optional[Callable] = None, ids_device: Optional[str] = "cpu"):
+                 preprocess: Optional[Callable] = None, ids_device: Optional[str] = "cpu",
+                 do_sample: bool = False, temperature: Optional[float] = None):
         self.model = model
+        # sampled turns (model.set_sampling): passed through to generate / submit; the defaults are the reference's greedy call
+        self.do_sample, self.temperature = bool(do_sample), temperature
         self.prompt_encoder = prompt_encoder
         self.num_frames, self.num_future_steps, self.num_history = num_frames, num_future_steps, num_history
         self.env_id, self.device, self.image_dtype = env_id, device, image_dtype
@@ -109,11 +112,13 @@ class StreamingAgent:
         aux = self._aux.get(V)
         if aux is None:              # depths / poses / intrinsics are built by the reference callers and ignored by the model
             aux = self._aux[V] = (torch.zeros(1, V, 1, 1), torch.zeros(1, V, 4, 4), torch.zeros(1, V, 4, 4))
+        sampling = {"temperature": float(self.temperature)} if self.do_sample and self.temperature is not None else {}
         return {
+            **sampling,
             "images": stacked.unsqueeze(0).to(self.device).to(self.image_dtype),
             "depths": aux[0], "poses": aux[1], "intrinsics": aux[2],
             "inputs": ids.to(self.ids_device), "env_id": env_id, "time_ids": [list(self.time_ids)], "task_type": [0],
-            "do_sample": False, "num_beams": 1, "max_new_tokens": self.max_new_tokens, "use_cache": True,
+            "do_sample": self.do_sample, "num_beams": 1, "max_new_tokens": self.max_new_tokens, "use_cache": True,
             "return_dict_in_generate": True, "past_key_values": self.past_key_values, "eos_token_ids": self.eos_token_ids,
         }
 

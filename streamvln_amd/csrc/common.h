@@ -140,6 +140,31 @@ SVLN_DEV float lse_rescale(float s, float m, float V) { return s == 0.0f ? 0.0f 
 // log-probability of the winning logit from S = sum exp(l - V) >= 1
 SVLN_DEV float lse_logprob(float S) { return -0.6931471805599453f * __builtin_amdgcn_logf(S); }
 
+// Noise of EPI_SAMPLE (kernels.h): a pure function of (seed, stream, draw, column), whatever kernel, tile, wave or row evaluates it.
+// Philox4x32-10 (Salmon et al., SC'11) on counter (column, draw, stream, 0) and key (seed lo, seed hi); output word 0.
+SVLN_DEV uint32_t philox4x32_10_w0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+// standard Gumbel from 23 random bits: u = ((w >> 9) + 0.5) * 2^-23 is exact in fp32 and lies in [2^-24, 1 - 2^-24] (24 bits would round
+// 16777215.5 to 2^24: u = 1, G = +inf); E = -ln u in [2^-24 (1 + ..), 16.64], G = -ln E.  Both logarithms are v_log_f32 (1 ulp of log2,
+// also next to u = 1 where the result is small: its error is relative) times fl(ln 2): E is good to ~2 ulp over the whole range, which
+// the upper tail of G (u -> 1), where the winners come from, needs; |G error| <= 2^-18 max(1, |G|) is the tested bound.
+SVLN_DEV float gumbel_from_bits(uint32_t w) {
+    const float u = ((float)(w >> 9) + 0.5f) * 0x1p-23f;
+    const float E = -0.6931471805599453f * __builtin_amdgcn_logf(u);
+    return -0.6931471805599453f * __builtin_amdgcn_logf(E);
+}
+SVLN_DEV float gumbel_noise(uint32_t seed_lo, uint32_t seed_hi, int stream, int draw, int column) {
+    return gumbel_from_bits(philox4x32_10_w0((uint32_t)column, (uint32_t)draw, (uint32_t)stream, 0u, seed_lo, seed_hi));
+}
+
 // activation functions (fp32).  sigmoid on the hardware transcendentals (v_exp_f32 / v_rcp_f32, ~1 ulp each: a few ulp of fp32 in all, far
 // inside the 1e-3 parity bar) instead of libm's expf / tanhf and an IEEE division: an epilogue evaluates 64-128 activations per lane per
 // 256 x 256 tile, and with libm (~35-50 instructions each) that was 35 of the 90 us of the nine-frame fc1 product and ~10 % of gate/up at

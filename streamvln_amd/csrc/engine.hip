@@ -64,6 +64,8 @@ struct Slot {            // canonical tensor -> where its rows live in the packe
     void* dst; int ld; int64_t rows; int cols; RowMap map; bool filled;
 };
 
+// the sampled form of a test-only lm_head op (svln_op_*_argmax_sample): streams / draws are host arrays, one entry per row of the product
+struct OpSample { float temperature; uint64_t seed; const int32_t* streams; const int32_t* draws; };
 struct EngineBase {
     virtual ~EngineBase() {}
     virtual void synth_tensor(const char* name, uint64_t seed_t, float hw, float base) = 0;
@@ -102,9 +104,11 @@ struct EngineBase {
     virtual void get_token_scores(float* out, int cap, int32_t* n) = 0;
     virtual void batch_scores(int slot, float* out, int cap, int32_t* n) = 0;
     virtual void generate_batch_scores(int index, float* out, int cap, int32_t* n) = 0;
-    virtual void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob) = 0;
-    virtual void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs) = 0;
-    virtual void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs) = 0;
+    virtual void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob, const OpSample* smp) = 0;
+    virtual void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp) = 0;
+    virtual void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp) = 0;
+    virtual void set_sampling(int enable, float temperature, uint64_t seed) = 0;
+    virtual void op_gumbel(uint64_t seed, int stream, int draw, int n0, int count, float* out) = 0;
     virtual void sync() = 0;
     virtual void set_graph(int enable) = 0;
     virtual void set_decode_persistent(int enable) = 0;
@@ -217,6 +221,22 @@ public:
     float *part_sum = nullptr, *part_sum_b = nullptr, *d_scores = nullptr, *h_scores = nullptr, *d_score_b = nullptr, *h_score_b = nullptr;
     float* row_scale_b = nullptr;            // [MAXB]: the row factors of a scored batched GEMV with a fused norm (svln_op_gemv_batched_argmax_scores only)
     std::vector<float> last_scores; bool last_scores_valid = false;           // of the last svln_generate / svln_turn / svln_generate_fixed
+    // Opt-in temperature sampling (svln_set_sampling; no reference counterpart): every lm_head product runs its EPI_SAMPLE sibling
+    // (kernels.h): token = argmax_n (fl(x_n * inv_t) + G(seed, stream, draw, n)), an exact sample of softmax(x / T).  stream = the env slot,
+    // draw = env_draws[env] + the tokens of this turn.  A single-env turn carries both in GenCtl (draw0, stream); the scheduler uploads
+    // d_smp[0 .. rows) = streams, d_smp[SMP_ROWS .. + rows) = draws per iteration.  The sampled kernels always compute the token's
+    // log-probability under softmax(x / T) (d_scores / d_score_b); it is delivered only while svln_set_token_scores is on.
+    static constexpr int SMP_ROWS = 64 + 8;  // HEAD_ROWS + MAXB
+    bool smp_on = false; float smp_inv_t = 1.0f; uint64_t smp_seed = 0;
+    float *part_raw = nullptr, *part_max = nullptr, *part_raw_b = nullptr, *part_max_b = nullptr;
+    int *d_smp = nullptr, *h_smp = nullptr;
+    std::vector<int> env_draws;              // tokens every env has emitted since the last svln_set_sampling
+    bool top2_sampled = false;               // the last turn was sampled: d_top2 holds perturbed values, not logits
+    // an op-level override of the engine's own switch (svln_op_*_argmax_sample): the product's SampleArgs scalars
+    SampleArgs smp_args(const int* stream, const int* draw, const int* count, float* raw, float* mx) const {
+        SampleArgs q; q.stream = stream; q.draw = draw; q.count = count; q.inv_t = smp_inv_t;
+        q.seed_lo = (uint32_t)smp_seed; q.seed_hi = (uint32_t)(smp_seed >> 32); q.part_raw = raw; q.part_max = mx; return q;
+    }
     std::vector<std::vector<float>> gb_scores; bool gb_scores_valid = false;  // of the last svln_generate_batch, per listed env
 
     struct Env {
@@ -416,6 +436,11 @@ public:
         part_val = dalloc<float>(2048); part_idx = dalloc<int>(2048); part_sum = dalloc<float>(2048);
         d_scores = dalloc<float>((size_t)c.max_positions + 8, true); d_score_b = dalloc<float>(HEAD_ROWS + MAXB, true);
         part_sum_b = dalloc<float>((size_t)HEAD_ROWS * 2048); row_scale_b = dalloc<float>(MAXB, true);
+        static_assert(SMP_ROWS == HEAD_ROWS + MAXB, "SMP_ROWS");
+        part_raw = dalloc<float>(2048); part_max = dalloc<float>(2048);
+        part_raw_b = dalloc<float>((size_t)HEAD_ROWS * 2048); part_max_b = dalloc<float>((size_t)HEAD_ROWS * 2048);
+        d_smp = dalloc<int>(2 * SMP_ROWS, true);
+        HIP_CHECK(hipHostMalloc((void**)&h_smp, 2 * SMP_ROWS * sizeof(int)));
         HIP_CHECK(hipHostMalloc((void**)&h_scores, ((size_t)c.max_positions + 8) * sizeof(float)));
         HIP_CHECK(hipHostMalloc((void**)&h_score_b, (HEAD_ROWS + MAXB) * sizeof(float)));
         d_token = dalloc<int>(4, true); d_top2 = dalloc<float>(4, true);
@@ -436,6 +461,7 @@ public:
         HIP_CHECK(hipHostMalloc((void**)&h_token, 16));
         HIP_CHECK(hipHostMalloc((void**)&h_top2, 16));
         envs.resize(c.max_envs);
+        env_draws.assign(c.max_envs, 0);
         graphs.resize(c.max_envs);
         for (auto& e : envs) {
             e.embeds = dalloc<T>(rt * H);
@@ -468,6 +494,7 @@ public:
         for (auto e : pprobe_ev) (void)hipEventDestroy(e);
         for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ph_ev[i]);
         (void)hipHostFree(h_ctl); (void)hipHostFree(h_out_ids); (void)hipHostFree(h_scores); (void)hipHostFree(h_score_b);
+        if (h_smp) (void)hipHostFree(h_smp);
         if (h_giveup) (void)hipHostFree(h_giveup);
         if (h_hash) (void)hipHostFree(h_hash);
         for (void* p : allocs) (void)hipFree(p);
@@ -1067,15 +1094,18 @@ public:
         } else {
             launch_rmsnorm<T>(st, xrow, final_norm, tap, 1, H, c.rms_eps, skip);
         }
-        GemvArgs a = with4(with8(gemv_args(lm_head, H, tap, nullptr, nullptr, nullptr, nullptr, V, H, scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX), lm_head8), lm_head4);
+        GemvArgs a = with4(with8(gemv_args(lm_head, H, tap, nullptr, nullptr, nullptr, nullptr, V, H, smp_on ? EPI_SAMPLE : scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX), lm_head8), lm_head4);
         a.skip = skip;
         const bool pen = gen && rep_penalty != 1.0f;
         if (pen) { a.pen_flags = pen_flags; a.pen = rep_penalty; }
-        const float* ps = scores_on ? part_sum : nullptr;          // svln_set_token_scores: the sibling kernels, scores[count] beside out_ids[count]
+        const float* ps = scores_on || smp_on ? part_sum : nullptr;          // svln_set_token_scores: the sibling kernels, scores[count] beside out_ids[count]
         a.part_sum = part_sum;
+        // svln_set_sampling: stream and draw come from GenCtl on the device (the turn wrote them), so a captured step stays valid
+        if (smp_on) a.smp = smp_args(&d_ctl->stream, &d_ctl->draw0, &d_ctl->count, part_raw, part_max);
+        const float *pr = smp_on ? part_raw : nullptr, *pm = smp_on ? part_max : nullptr;
         launch_gemv<T>(st, a);
-        if (gen) launch_argmax_step(st, part_val, part_idx, gemv_grid(V), d_token, d_top2, d_ctl, d_eos, d_out_ids, pen ? pen_flags : nullptr, ps, d_scores);
-        else launch_argmax_final(st, part_val, part_idx, gemv_grid(V), d_token, d_top2, ps, d_scores);
+        if (gen) launch_argmax_step(st, part_val, part_idx, gemv_grid(V), d_token, d_top2, d_ctl, d_eos, d_out_ids, pen ? pen_flags : nullptr, ps, d_scores, pr, pm);
+        else launch_argmax_final(st, part_val, part_idx, gemv_grid(V), d_token, d_top2, ps, d_scores, pr, pm);
     }
     // One decode step as a fixed op sequence; every run-time scalar is read from device memory (d_ctl,
     // d_token) so any sub-range [lo, hi) of the sequence can be captured once and graph-replayed.
@@ -1102,6 +1132,7 @@ public:
         if (!enable) { if (persistent_on) drop_graphs(); persistent_on = false; return; }
         refuse_while_speculative("svln_set_decode_persistent");
         refuse_while_scores("svln_set_decode_persistent");
+        refuse_while_sampling("svln_set_decode_persistent");
         if (!n_cus) { hipDeviceProp_t pr; HIP_CHECK(hipGetDeviceProperties(&pr, device)); n_cus = pr.multiProcessorCount; }
         DecodeLayerArgs a = layer_args(0);
         REQUIRE(decode_layer_supported<T>(a, n_cus), "persistent decode layer: this configuration is not supported (per-CU slices of hidden / inter / q|k|v "
@@ -1218,7 +1249,7 @@ public:
         const bool probing = probe_on && first_tap_row == 1 && probe_used + 2 <= probe_ev.size();
         if (use_graph) {
             GraphSet& gs = graphs[env];
-            const int sk = scores_on ? 10000 : 0;      // the captured head is the scored or the plain one
+            const int sk = (scores_on ? 10000 : 0) + (smp_on ? 20000 : 0);      // the captured head is the plain, the scored or the sampled one
             auto get = [&](int key, int lo, int hi, int more) {
                 auto it = gs.ex.find(key);
                 if (it == gs.ex.end()) it = gs.ex.emplace(key, capture(e, lo, hi, more)).first;
@@ -1257,21 +1288,26 @@ public:
     // batched GEMV is dot-product-issue bound from B = 4: 386 us at B = 8 on the full vocabulary); B <= 2: the batched GEMV.
     // svln_set_token_scores: the EPI_ARGMAX_LSE siblings, row b's log-probability -> d_score_b[tok0 + b]
     void argmax_rows(const void* W, int ldw, const T* xrows, int ldx, int N, int K, int B, bool pen, int tok0 = 0) {       // -> d_tok_b[tok0 ..)
-        const float* ps = scores_on ? part_sum_b : nullptr;
+        // svln_set_sampling: the EPI_SAMPLE siblings; row b's stream / draw are d_smp[tok0 + b] / d_smp[SMP_ROWS + tok0 + b]
+        const float* ps = scores_on || smp_on ? part_sum_b : nullptr;
+        const float *pr = smp_on ? part_raw_b : nullptr, *pm = smp_on ? part_max_b : nullptr;
+        const SampleArgs sa = smp_args(d_smp + tok0, d_smp + SMP_ROWS + tok0, nullptr, part_raw_b, part_max_b);
         if (B >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048) {
             GemmArgs a = gemm_args(xrows, ldx, W, ldw, nullptr, 0, nullptr, nullptr, 0, 0, B, N, K, EPI_ARGMAX);
             a.part_val = part_val_b; a.part_idx = part_idx_b;
-            if (scores_on) a.part_sum = part_sum_b;
+            if (scores_on || smp_on) a.part_sum = part_sum_b;
+            if (smp_on) a.smp = sa;
             if (pen) { a.pen_flags = pen_flags_b; a.pen_rows = d_pen_rows; a.pen = rep_penalty; }
             const int n = launch_gemm_argmax<T>(st, a);
-            launch_argmax_final_batched(st, part_val_b, part_idx_b, n, B, d_tok_b + tok0, ps, d_score_b + tok0);
+            launch_argmax_final_batched(st, part_val_b, part_idx_b, n, B, d_tok_b + tok0, ps, d_score_b + tok0, nullptr, pr, pm);
             return;
         }
-        GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX, B);
+        GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, smp_on ? EPI_SAMPLE : scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX, B);
         hb.part_sum = part_sum_b;
+        if (smp_on) hb.smp = sa;
         if (pen) { hb.pen_flags = pen_flags_b; hb.pen_rows = d_pen_rows; hb.pen = rep_penalty; }
         launch_gemv_batched<T>(st, hb);
-        launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(N, EPI_ARGMAX, B), B, d_tok_b + tok0, ps, d_score_b + tok0);
+        launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(N, EPI_ARGMAX, B), B, d_tok_b + tok0, ps, d_score_b + tok0, nullptr, pr, pm);
     }
     void head_batched(const T* rows, int B, bool pen = false) {
         launch_rmsnorm<T>(st, rows, final_norm, xn, B, H, c.rms_eps);
@@ -1393,6 +1429,7 @@ public:
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_speculative cannot change while scheduler turns are in flight");
         if (rows > 0) {
             refuse_while_scores("svln_set_speculative");
+            refuse_while_sampling("svln_set_speculative");
             REQUIRE(rows * (nq / nkv) <= 32, "svln_set_speculative: rows * (q_heads / kv_heads) must be <= 32 (the verify attention keeps 32 query rows per kv head)");
             // a verify pass must compute each row in the numeric scheme of the single step it replaces
             REQUIRE(!spec_exclusive_on(), "svln_set_speculative: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, "
@@ -1412,6 +1449,65 @@ public:
         REQUIRE(spec_rows == 0, std::string(who) + ": draft-verified decode is on (svln_set_speculative); switch it off first");
         REQUIRE(!ride_on, std::string(who) + ": drafts inside the prefill pass are on (svln_set_prefill_draft); switch them off first");
         REQUIRE(!bdraft_on, std::string(who) + ": drafts in the scheduler's prefill pass are on (svln_set_batch_draft); switch them off first");
+    }
+    void refuse_while_sampling(const char* who) {
+        REQUIRE(!smp_on, std::string(who) + ": temperature sampling is on (svln_set_sampling); switch it off first");
+    }
+    // svln_set_sampling.  Refused with the modes whose tokens do not come out of a sampled arg-max: the three draft switches (their verify
+    // rule is written for greedy rows), the persistent decode layer and the batched MXFP4 weights (gemv_mx4b_kernel has no sampled form).
+    // Every call, on or off, restarts the draw counters and drops the captured steps (seed and 1 / T are launch scalars).
+    void set_sampling(int enable, float temperature, uint64_t seed) override {
+        const bool want = enable != 0;
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_sampling cannot change while scheduler turns are in flight");
+        float inv_t = 1.0f;
+        if (want) {
+            REQUIRE(std::isfinite(temperature) && temperature > 0.0f, "svln_set_sampling: the temperature must be finite and > 0");
+            inv_t = 1.0f / temperature;
+            REQUIRE(std::isfinite(inv_t), "svln_set_sampling: 1 / temperature overflows fp32");
+            refuse_while_speculative("svln_set_sampling");
+            REQUIRE(!persistent_on, "svln_set_sampling: the persistent decode layer is on (svln_set_decode_persistent); switch it off first");
+            REQUIRE(!mx4b_on, "svln_set_sampling: the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+        drop_graphs();
+        smp_on = want; smp_inv_t = inv_t; smp_seed = want ? seed : 0;
+        std::fill(env_draws.begin(), env_draws.end(), 0);
+    }
+    // rows [0, n) of the next sampled lm_head pass: job slot order[k] per row (rows beyond n_jobs replay row 0)
+    void upload_sample_rows(const int* job_of_row, int n_jobs, int n) {
+        for (int k = 0; k < n; ++k) {
+            const int env = jobs[job_of_row[k < n_jobs ? k : 0]].env;
+            h_smp[k] = env; h_smp[SMP_ROWS + k] = env_draws[env];
+        }
+        HIP_CHECK(hipMemcpyAsync(d_smp, h_smp, n * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_smp + SMP_ROWS, h_smp + SMP_ROWS, n * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    void op_gumbel(uint64_t seed, int stream, int draw, int n0, int count, float* out) override {
+        REQUIRE(out && count >= 1 && n0 >= 0 && (int64_t)n0 + count <= (int64_t)1 << 31, "svln_op_gumbel: out, count >= 1, 0 <= n0, n0 + count <= 2^31");
+        REQUIRE(stream >= 0 && draw >= 0, "svln_op_gumbel: stream and draw must be >= 0");
+        float* d = nullptr;
+        HIP_CHECK(hipMalloc((void**)&d, (size_t)count * sizeof(float)));
+        launch_gumbel(st, (uint32_t)seed, (uint32_t)(seed >> 32), stream, draw, n0, count, d);
+        const hipError_t err = hipMemcpyAsync(out, d, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, st);
+        const hipError_t err2 = hipStreamSynchronize(st);
+        (void)hipFree(d);
+        HIP_CHECK(err); HIP_CHECK(err2);
+        LAUNCH_CHECK("op_gumbel");
+    }
+    // stage the rows of a sampled test op and return its SampleArgs
+    SampleArgs op_sample_args(const OpSample& q, int rows, float* raw, float* mx, bool want_logprob) {
+        REQUIRE(want_logprob, "the sampled form writes log-probabilities: host_logprob(s) must not be null");
+        REQUIRE(q.streams && q.draws, "null pointer");
+        REQUIRE(std::isfinite(q.temperature) && q.temperature > 0.0f && std::isfinite(1.0f / q.temperature), "the temperature must be finite and > 0");
+        REQUIRE(rows >= 1 && rows <= SMP_ROWS, "rows");
+        for (int k = 0; k < rows; ++k) REQUIRE(q.streams[k] >= 0 && q.draws[k] >= 0, "streams and draws must be >= 0");
+        HIP_CHECK(hipStreamSynchronize(st));       // (h_smp of an earlier call is no longer being read)
+        for (int k = 0; k < rows; ++k) { h_smp[k] = q.streams[k]; h_smp[SMP_ROWS + k] = q.draws[k]; }
+        HIP_CHECK(hipMemcpyAsync(d_smp, h_smp, rows * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_smp + SMP_ROWS, h_smp + SMP_ROWS, rows * sizeof(int), hipMemcpyHostToDevice, st));
+        SampleArgs a; a.stream = d_smp; a.draw = d_smp + SMP_ROWS; a.count = nullptr; a.inv_t = 1.0f / q.temperature;
+        a.seed_lo = (uint32_t)q.seed; a.seed_hi = (uint32_t)(q.seed >> 32); a.part_raw = raw; a.part_max = mx;
+        return a;
     }
     void refuse_while_scores(const char* who) {
         REQUIRE(!scores_on, std::string(who) + ": token log-probabilities are on (svln_set_token_scores); switch them off first");
@@ -1458,6 +1554,7 @@ public:
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_batch_draft cannot change while scheduler turns are in flight");
         if (want) {
             refuse_while_scores("svln_set_batch_draft");
+            refuse_while_sampling("svln_set_batch_draft");
             // a ridden row must be computed in the numeric scheme of the decode row it replaces
             REQUIRE(!spec_exclusive_on(), "svln_set_batch_draft: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, "
                                           "svln_set_fp8_gemm, svln_set_mxfp4_batched, svln_set_decode_persistent); switch it off first");
@@ -1480,6 +1577,7 @@ public:
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_prefill_draft cannot change while scheduler turns are in flight");
         if (want) {
             refuse_while_scores("svln_set_prefill_draft");
+            refuse_while_sampling("svln_set_prefill_draft");
             // a ridden row must be computed in the numeric scheme of the pass it replaces
             REQUIRE(!spec_exclusive_on(), "svln_set_prefill_draft: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, "
                                           "svln_set_fp8_gemm, svln_set_mxfp4_batched, svln_set_decode_persistent); switch it off first");
@@ -1718,10 +1816,11 @@ public:
             HIP_CHECK(hipMemcpyAsync(d_tok_b, h_tok_b, B * sizeof(int), hipMemcpyHostToDevice, st));
             if (pure) {
                 if (pen) HIP_CHECK(hipMemcpyAsync(d_pen_rows, h_pen_rows, B * sizeof(int), hipMemcpyHostToDevice, st));
+                if (smp_on) upload_sample_rows(dec.data(), nd, B);
                 // gather + 28 layers + head for B decode rows -> d_tok_b, xn = final-norm rows.  With hipGraph replay on, the step of each
                 // (B, fp8, penalty) combination is captured once: every run-time value (page tables, positions, fed tokens) is in d_slots / d_tok_b.
                 if (use_graph) {
-                    const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0) | (fp8_gemm_on && fp8_scaled_on ? 2048 : 0) | (scores_on ? 4096 : 0);
+                    const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0) | (fp8_gemm_on && fp8_scaled_on ? 2048 : 0) | (scores_on ? 4096 : 0) | (smp_on ? 8192 : 0);
                     auto it = bgraphs.find(key);
                     if (it == bgraphs.end())      // (a failed capture leaves no entry behind)
                         it = bgraphs.emplace(key, capture_graph([&] { decode_ops_batched(B, pen); })).first;
@@ -1767,6 +1866,7 @@ public:
                     for (int k = 0; k < Bp; ++k) hp[k] = order[head0 + (k < nj ? k : 0)];
                     HIP_CHECK(hipMemcpyAsync(d_pen_rows, hp, Bp * sizeof(int), hipMemcpyHostToDevice, st));
                 }
+                if (smp_on) upload_sample_rows(order.data() + head0, nj, Bp);
                 head_batched(last_rows, Bp, pen);
             }
         }
@@ -1808,6 +1908,7 @@ public:
                 REQUIRE(tok >= 0 && tok < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
                 j.out.push_back(tok);
                 if (j.scored) j.scores.push_back(h_score_b[hq + i]);
+                if (smp_on) env_draws[j.env] += 1;
                 j.count += 1;
                 ++emitted;
                 stop = j.count >= j.max_new;
@@ -1949,7 +2050,7 @@ public:
         }
         // the first decode step feeds token 0 at position L: pos / kv_len advance when the arg-max step appends without stopping
         h_ctl->pos = L - 1; h_ctl->kv_len = L; h_ctl->done = 0; h_ctl->count = 0; h_ctl->max_new = limit; h_ctl->n_eos = n_eos;
-        h_ctl->pad0 = h_ctl->pad1 = 0;
+        h_ctl->draw0 = smp_on ? env_draws[env] : 0; h_ctl->stream = smp_on ? env : 0;
         if (rep_penalty != 1.0f)      // tokens of the previous generate (still listed in d_out_ids[0 .. d_ctl.count)) no longer count
             launch_set_flags(st, pen_flags, d_out_ids, &d_ctl->count, 0, 0);
         HIP_CHECK(hipMemcpyAsync(d_ctl, h_ctl, sizeof(GenCtl), hipMemcpyHostToDevice, st));
@@ -2072,6 +2173,8 @@ public:
         const int singles = n - vtokens - (ride ? rtokens : 1);      // (the prefill's own token counts in none of the draft counters)
         st_vtokens += vtokens; st_single += singles;
         top2_stale = (vtokens > 0 || ride) && singles == 0;
+        top2_sampled = smp_on;
+        if (smp_on) env_draws[env] += n;
         *n_out = n;
     }
 
@@ -2134,6 +2237,7 @@ public:
         read_rows_f32(feats + (size_t)start * H, (size_t)n * H, out);
     }
     void get_top2(float* out) override {
+        REQUIRE(!top2_sampled, "svln_get_top2: the last turn was sampled (svln_set_sampling): the top-2 values of its last arg-max are perturbed by the noise, not logits");
         REQUIRE(!top2_stale, "svln_get_top2: the last token of the last turn came from a verify pass (svln_set_speculative) or a ride "
                              "(svln_set_prefill_draft), which keep no top-2 logits");
         out[0] = h_top2[0]; out[1] = h_top2[1];
@@ -2244,6 +2348,7 @@ public:
         if (!enable) { drop_graphs(); mx4b_on = false; return; }
         refuse_while_speculative("svln_set_mxfp4_batched");
         refuse_while_scores("svln_set_mxfp4_batched");
+        refuse_while_sampling("svln_set_mxfp4_batched");
         REQUIRE(sizeof(T) == 2, "svln_set_mxfp4_batched: MXFP4 weights need the bf16 engine");
         REQUIRE(!fp8_on, "svln_set_mxfp4_batched: the e4m3 decode weights are on (svln_set_fp8_decode); switch them off first");
         REQUIRE(!fp8_gemm_on, "svln_set_mxfp4_batched: the e4m3 MFMA products are on (svln_set_fp8_gemm); switch them off first");
@@ -2392,7 +2497,8 @@ public:
         sync();
     }
     // TEST-ONLY: one lm_head product in its plain (host_logprob null: EPI_ARGMAX) or scored (EPI_ARGMAX_LSE) form with optional penalty flags
-    void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob) override {
+    // smp: the sampled form (EPI_SAMPLE) on the given temperature, seed, streams and draws, whatever the engine's own switch says
+    void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob, const OpSample* smp) override {
         REQUIRE(a.w8 == nullptr || sizeof(T) == 2, "fp8 weights need the bf16 engine");
         REQUIRE(a.w4 == nullptr || sizeof(T) == 2, "MXFP4 weights need the bf16 engine");
         const int chunk = a.w4 ? 32 : a.w8 ? 16 : Elt<T>::PER_CHUNK;
@@ -2401,10 +2507,11 @@ public:
         REQUIRE(a.ldw >= a.K && a.ldw % chunk == 0, "ldw >= K, a multiple of the format's 16-byte chunk (aligned row loads)");
         REQUIRE((size_t)a.K * sizeof(float) <= (size_t)GEMV_ROWS_MAX_LDS, "the wave-per-rows kernel stages K fp32 activations in LDS: K too large");
         REQUIRE(!a.pen_flags || a.pen > 0.0f, "penalty flags need a factor > 0");
-        a.epi = host_logprob ? EPI_ARGMAX_LSE : EPI_ARGMAX;
+        a.epi = smp ? EPI_SAMPLE : host_logprob ? EPI_ARGMAX_LSE : EPI_ARGMAX;
         a.part_val = part_val; a.part_idx = part_idx; a.part_sum = part_sum;
+        if (smp) a.smp = op_sample_args(*smp, 1, part_raw, part_max, host_logprob != nullptr);
         launch_gemv<T>(st, a);
-        launch_argmax_final(st, part_val, part_idx, gemv_grid(a.N), d_token, d_top2, host_logprob ? part_sum : nullptr, d_scores);
+        launch_argmax_final(st, part_val, part_idx, gemv_grid(a.N), d_token, d_top2, host_logprob ? part_sum : nullptr, d_scores, a.smp.part_raw, a.smp.part_max);
         if (host_logprob) HIP_CHECK(hipMemcpyAsync(h_scores, d_scores, sizeof(float), hipMemcpyDeviceToHost, st));
         *host_token = read_token();
         if (host_logprob) *host_logprob = h_scores[0];
@@ -2417,21 +2524,23 @@ public:
         LAUNCH_CHECK(who);
         for (int b = 0; b < B; ++b) { host_tokens[b] = h_tok_b[b]; if (host_logprobs) host_logprobs[b] = h_score_b[b]; }
     }
-    void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs) override {
+    void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp) override {
         REQUIRE(a.W && a.x && host_tokens, "null pointer");
         REQUIRE(a.B == 1 || a.B == 2 || a.B == 4 || a.B == 8, "B must be 1, 2, 4 or 8");
         REQUIRE(a.N >= 1 && a.K >= Elt<T>::PER_CHUNK && a.K % Elt<T>::PER_CHUNK == 0, "N >= 1, K a positive multiple of the 16-byte chunk");
         REQUIRE(a.ldw >= a.K && a.ldw % Elt<T>::PER_CHUNK == 0 && a.ldx >= a.K && a.ldx % Elt<T>::PER_CHUNK == 0, "ldw, ldx >= K, multiples of the 16-byte chunk");
         REQUIRE(!a.pen_flags || (a.pen_rows && a.pen > 0.0f), "penalty flags come with their row table and a factor > 0");
-        a.epi = host_logprobs ? EPI_ARGMAX_LSE : EPI_ARGMAX;
+        REQUIRE(!smp || !a.norm_w, "the sampled batched GEMV has no fused-norm form");
+        a.epi = smp ? EPI_SAMPLE : host_logprobs ? EPI_ARGMAX_LSE : EPI_ARGMAX;
         a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b;
         a.row_scale = row_scale_b;
+        if (smp) a.smp = op_sample_args(*smp, a.B, part_raw_b, part_max_b, host_logprobs != nullptr);
         launch_gemv_batched<T>(st, a);
         launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), a.B, d_tok_b, host_logprobs ? part_sum_b : nullptr, d_score_b,
-                                    host_logprobs && a.norm_w ? a.row_scale : nullptr);
+                                    host_logprobs && a.norm_w ? a.row_scale : nullptr, a.smp.part_raw, a.smp.part_max);
         batched_scores_out(a.B, host_tokens, host_logprobs, "op_gemv_batched_scores");
     }
-    void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs) override {
+    void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp) override {
         constexpr int chunk = Elt<T>::PER_CHUNK;
         REQUIRE(a.A && a.W && host_tokens, "null pointer");
         REQUIRE(a.M >= 1 && a.M <= 32 && a.N >= 1 && (a.N + 127) / 128 <= 2048, "1 <= M <= 32 rows, 1 <= N <= 262144");
@@ -2441,8 +2550,9 @@ public:
         REQUIRE(!a.pen_flags || (a.pen_rows && a.pen > 0.0f), "penalty flags come with their row table and a factor > 0");
         a.zeros = zero_line; a.epi = EPI_ARGMAX;
         a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = host_logprobs ? part_sum_b : nullptr;
+        if (smp) a.smp = op_sample_args(*smp, a.M, part_raw_b, part_max_b, host_logprobs != nullptr);
         const int n = launch_gemm_argmax<T>(st, a);
-        launch_argmax_final_batched(st, part_val_b, part_idx_b, n, a.M, d_tok_b, a.part_sum, d_score_b);
+        launch_argmax_final_batched(st, part_val_b, part_idx_b, n, a.M, d_tok_b, a.part_sum, d_score_b, nullptr, a.smp.part_raw, a.smp.part_max);
         batched_scores_out(a.M, host_tokens, host_logprobs, "op_gemm_argmax_scores");
     }
     void op_gemv_batched(GemvBatchArgs a, int32_t* host_tokens) override {
@@ -2450,6 +2560,8 @@ public:
         REQUIRE(a.K % Elt<T>::PER_CHUNK == 0 && a.N >= 1, "bad GEMV extents");
         REQUIRE(a.epi != EPI_SWIGLU || a.N % 64 == 0, "SwiGLU needs N % 64 == 0 (32-row gate / up blocks)");
         a.part_val = part_val_b; a.part_idx = part_idx_b;
+        // (argmax_rows follows the engine's switches: under svln_set_sampling it would sample on whatever rows d_smp last held)
+        REQUIRE(!(smp_on && a.epi == EPI_ARGMAX && !a.norm_w), "svln_op_gemv_batched: temperature sampling is on (svln_set_sampling); switch it off first, or use svln_op_gemv_batched_argmax_sample");
         if (a.epi == EPI_ARGMAX && !a.norm_w) argmax_rows(a.W, a.ldw, (const T*)a.x, a.ldx, a.N, a.K, a.B, false);      // the engine's own routing (MFMA tiles from B = 4)
         else launch_gemv_batched<T>(st, a);
         if (a.epi == EPI_ARGMAX) {
@@ -2651,7 +2763,7 @@ public:
                                    hipMemcpyDeviceToDevice, st));
         if (B == 1) {
             h_ctl->pos = pos[0]; h_ctl->kv_len = pos[0] + 1; h_ctl->done = 0; h_ctl->count = 0; h_ctl->max_new = 0; h_ctl->n_eos = 0;
-            h_ctl->pad0 = h_ctl->pad1 = 0;
+            h_ctl->draw0 = h_ctl->stream = 0;
             HIP_CHECK(hipMemcpyAsync(d_ctl, h_ctl, sizeof(GenCtl), hipMemcpyHostToDevice, st));
             decode_attention(decode_attn_args(L, env_at(0)));
         } else {
@@ -2681,7 +2793,7 @@ public:
         HIP_CHECK(hipMemcpy2DAsync(qkv, (size_t)qkv_dim * sizeof(T), qkv_new, (size_t)ld * sizeof(T), (size_t)qkv_dim * sizeof(T), rows,
                                    hipMemcpyDeviceToDevice, st));
         h_ctl->pos = ctx_rows; h_ctl->kv_len = ctx_rows + 1; h_ctl->done = 0; h_ctl->count = 0; h_ctl->max_new = 0; h_ctl->n_eos = 0;
-        h_ctl->pad0 = h_ctl->pad1 = 0;
+        h_ctl->draw0 = h_ctl->stream = 0;
         HIP_CHECK(hipMemcpyAsync(d_ctl, h_ctl, sizeof(GenCtl), hipMemcpyHostToDevice, st));
         h_vctl[0] = 0; h_vctl[1] = rows; h_vctl[2] = h_vctl[3] = 0;
         HIP_CHECK(hipMemcpyAsync(d_vctl, h_vctl, 4 * sizeof(int), hipMemcpyHostToDevice, st));
@@ -2711,7 +2823,7 @@ public:
         HIP_CHECK(hipMemcpy(d_tok_b, cand, (size_t)rows * sizeof(int), hipMemcpyHostToDevice));
         const int tok0 = -3;
         HIP_CHECK(hipMemcpy(d_token, &tok0, sizeof(int), hipMemcpyHostToDevice));
-        GenCtl g; g.pos = count; g.kv_len = count + 1; g.done = 0; g.count = count; g.max_new = max_new; g.n_eos = n_eos; g.pad0 = g.pad1 = 0;
+        GenCtl g; g.pos = count; g.kv_len = count + 1; g.done = 0; g.count = count; g.max_new = max_new; g.n_eos = n_eos; g.draw0 = g.stream = 0;
         HIP_CHECK(hipMemcpy(d_ctl, &g, sizeof(g), hipMemcpyHostToDevice));
         launch_verify_step<T>(st, d_vctl + 8, d_tok_b, d_vctl + 1, rows, d_ctl, d_eos, d_out_ids, d_token, xn, hid_tap, H, HID_TAP_ROWS, d_vctl + 2);
         sync();
@@ -2883,8 +2995,8 @@ int svln_batch_scores(svln_engine* h, int slot, float* out, int cap, int32_t* n)
 int svln_generate_batch_scores(svln_engine* h, int index, float* out, int cap, int32_t* n) {
     API_BEGIN_H REQUIRE(out && n && cap >= 0, "null output pointer"); h->impl->generate_batch_scores(index, out, cap, n); API_END
 }
-int svln_op_gemv_argmax_scores(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
-                               float penalty, int32_t* host_token, float* host_logprob) {
+static int op_gemv_argmax_any(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
+                              float penalty, int32_t* host_token, float* host_logprob, const OpSample* smp) {
     API_BEGIN_H
     REQUIRE(fmt >= 0 && fmt <= 2, "fmt: 0 = engine dtype, 1 = e4m3 + row scales, 2 = MXFP4");
     GemvArgs a; a.W = nullptr; a.ldw = ldw; a.x = x; a.norm_w = nullptr; a.eps = 0.0f; a.bias = nullptr; a.res = nullptr; a.y = nullptr; a.N = N; a.K = K;
@@ -2894,26 +3006,60 @@ int svln_op_gemv_argmax_scores(svln_engine* h, int fmt, const void* W, const voi
     else { a.w4 = W; a.e8 = (const uint8_t*)aux; }
     REQUIRE(W, "null pointer");
     a.pen_flags = (const uint8_t*)pen_flags; a.pen = penalty;
-    h->impl->op_gemv_scores(a, host_token, host_logprob);
+    h->impl->op_gemv_scores(a, host_token, host_logprob, smp);
     API_END
 }
-int svln_op_gemv_batched_argmax_scores(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
-                                       const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs) {
+int svln_op_gemv_argmax_scores(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
+                               float penalty, int32_t* host_token, float* host_logprob) {
+    return op_gemv_argmax_any(h, fmt, W, aux, ldw, x, N, K, pen_flags, penalty, host_token, host_logprob, nullptr);
+}
+int svln_op_gemv_argmax_sample(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
+                               float penalty, float temperature, uint64_t seed, int32_t stream, int32_t draw, int32_t* host_token, float* host_logprob) {
+    const OpSample q{temperature, seed, &stream, &draw};
+    return op_gemv_argmax_any(h, fmt, W, aux, ldw, x, N, K, pen_flags, penalty, host_token, host_logprob, &q);
+}
+static int op_gemv_batched_argmax_any(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
+                                      const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs,
+                                      const OpSample* smp) {
     API_BEGIN_H
     GemvBatchArgs a; a.W = W; a.ldw = ldw; a.x = x; a.ldx = ldx; a.norm_w = norm_w; a.eps = eps; a.bias = nullptr; a.res = nullptr; a.ldr = 0;
     a.y = nullptr; a.ldy = 0; a.N = N; a.K = K; a.epi = EPI_ARGMAX; a.B = B; a.part_val = nullptr; a.part_idx = nullptr;
     a.pen_flags = (const uint8_t*)pen_flags; a.pen_rows = pen_rows; a.pen = penalty;
-    h->impl->op_gemv_batched_scores(a, host_tokens, host_logprobs);
+    h->impl->op_gemv_batched_scores(a, host_tokens, host_logprobs, smp);
     API_END
 }
-int svln_op_gemm_argmax_scores(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
-                               const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs) {
+int svln_op_gemv_batched_argmax_scores(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
+                                       const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs) {
+    return op_gemv_batched_argmax_any(h, W, ldw, x, ldx, norm_w, eps, N, K, B, pen_flags, pen_rows, penalty, host_tokens, host_logprobs, nullptr);
+}
+int svln_op_gemv_batched_argmax_sample(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
+                                       const void* pen_flags, const int32_t* pen_rows, float penalty, float temperature, uint64_t seed,
+                                       const int32_t* streams, const int32_t* draws, int32_t* host_tokens, float* host_logprobs) {
+    const OpSample q{temperature, seed, streams, draws};
+    return op_gemv_batched_argmax_any(h, W, ldw, x, ldx, norm_w, eps, N, K, B, pen_flags, pen_rows, penalty, host_tokens, host_logprobs, &q);
+}
+static int op_gemm_argmax_any(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
+                              const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs, const OpSample* smp) {
     API_BEGIN_H
     GemmArgs a; std::memset(&a, 0, sizeof(a));
     a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.epi = EPI_ARGMAX; a.nsplit = 1;
     a.pen_flags = (const uint8_t*)pen_flags; a.pen_rows = pen_rows; a.pen = penalty;
-    h->impl->op_gemm_argmax_scores(a, host_tokens, host_logprobs);
+    h->impl->op_gemm_argmax_scores(a, host_tokens, host_logprobs, smp);
     API_END
+}
+int svln_op_gemm_argmax_scores(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
+                               const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs) {
+    return op_gemm_argmax_any(h, A, lda, W, ldw, M, N, K, pen_flags, pen_rows, penalty, host_tokens, host_logprobs, nullptr);
+}
+int svln_op_gemm_argmax_sample(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
+                               const int32_t* pen_rows, float penalty, float temperature, uint64_t seed, const int32_t* streams,
+                               const int32_t* draws, int32_t* host_tokens, float* host_logprobs) {
+    const OpSample q{temperature, seed, streams, draws};
+    return op_gemm_argmax_any(h, A, lda, W, ldw, M, N, K, pen_flags, pen_rows, penalty, host_tokens, host_logprobs, &q);
+}
+int svln_set_sampling(svln_engine* h, int enable, float temperature, uint64_t seed) { API_BEGIN_H h->impl->set_sampling(enable, temperature, seed); API_END }
+int svln_op_gumbel(svln_engine* h, uint64_t seed, int32_t stream, int32_t draw, int32_t n0, int32_t count, float* host_out) {
+    API_BEGIN_H h->impl->op_gumbel(seed, stream, draw, n0, count, host_out); API_END
 }
 int svln_set_decode_graph(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_graph(enable); API_END }
 int svln_set_decode_persistent(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_decode_persistent(enable); API_END }

@@ -19,6 +19,7 @@
 #include <hip/hip_ext.h>
 
 #include <cstdlib>
+#include <stdexcept>
 
 #include "common.h"
 #include "kernels.h"
@@ -279,10 +280,13 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
     const int gw = blockIdx.x * GEMV_WAVES + wave, nw = gridDim.x * GEMV_WAVES;
     const int n_out = EPI == EPI_SWIGLU ? p.N >> 1 : p.N;
 
-    constexpr bool AMAX = epi_is_argmax(EPI), LSE = EPI == EPI_ARGMAX_LSE;
-    float best = -INFINITY;                       // EPI_ARGMAX
+    constexpr bool AMAX = epi_is_argmax(EPI), LSE = EPI == EPI_ARGMAX_LSE, SMP = EPI == EPI_SAMPLE;
+    float best = -INFINITY;                       // EPI_ARGMAX (EPI_SAMPLE: the best perturbed value z)
     int best_i = 0x7FFFFFFF;
-    float lm = -INFINITY, ls = 0.0f;              // EPI_ARGMAX_LSE: wave-uniform (max, sum exp(l - max)) over the wave's rows
+    float lm = -INFINITY, ls = 0.0f;              // EPI_ARGMAX_LSE: wave-uniform (max, sum exp(l - max)) over the wave's rows (EPI_SAMPLE: over y)
+    [[maybe_unused]] float best_raw = -INFINITY;  // EPI_SAMPLE: the y of the best z
+    [[maybe_unused]] int smp_stream = 0, smp_draw = 0;
+    if constexpr (SMP) { smp_stream = p.smp.stream[0]; smp_draw = p.smp.draw[0] + (p.smp.count ? *p.smp.count : 0); }
     for (int n0 = gw * OUTS; n0 < n_out; n0 += nw * OUTS) {
         size_t rn[R];                             // the group's weight rows; a ragged last group repeats the last output's rows
 #pragma unroll
@@ -310,9 +314,22 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
                 for (int r = 0; r < R; ++r)
                     if (n0 + r < p.N && p.pen_flags[n0 + r]) acc[r] = acc[r] < 0.0f ? acc[r] * p.pen : acc[r] / p.pen;
             }
+            if constexpr (SMP) {
+                // lane l evaluates the noise of column n0 + (l & 3) -- one Philox per group, not four -- and the wave reads lanes 0 .. 3
+                const float gq = gumbel_noise(p.smp.seed_lo, p.smp.seed_hi, smp_stream, smp_draw, n0 + (lane & 3));
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const float y = acc[r] * p.smp.inv_t, z = y + __shfl(gq, r, 64);
+                    if (n0 + r < p.N) {
+                        if (z > best) { best = z; best_i = n0 + r; best_raw = y; }         // rows ascend: first max wins
+                        lse_add(y, lm, ls);
+                    }
+                }
+            } else {
 #pragma unroll
             for (int r = 0; r < R; ++r)
                 if (n0 + r < p.N && acc[r] > best) { best = acc[r]; best_i = n0 + r; }     // rows ascend: first max wins
+            }
             if (LSE) {                            // the penalised values; the repeated rows of a ragged last group (n0 + r >= N) count once
 #pragma unroll
                 for (int r = 0; r < R; ++r)
@@ -326,6 +343,25 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
         __shared__ float bv[GEMV_WAVES];
         __shared__ int bi[GEMV_WAVES];
         if (lane == 0) { bv[wave] = best; bi[wave] = best_i; }
+        if constexpr (SMP) {
+            __shared__ float bs[GEMV_WAVES], bm[GEMV_WAVES], br[GEMV_WAVES];
+            if (lane == 0) { bs[wave] = ls; bm[wave] = lm; br[wave] = best_raw; }
+            __syncthreads();
+            if (threadIdx.x == 0) {               // a wave without a row is (-inf, 0) and adds 0
+                float v = bv[0], m = bm[0], raw = br[0]; int i = bi[0];
+#pragma unroll
+                for (int w = 1; w < GEMV_WAVES; ++w) {
+                    if (bv[w] > v || (bv[w] == v && bi[w] < i)) { v = bv[w]; i = bi[w]; raw = br[w]; }
+                    m = bm[w] > m ? bm[w] : m;
+                }
+                float sum = 0.0f;
+#pragma unroll
+                for (int w = 0; w < GEMV_WAVES; ++w) sum += lse_rescale(bs[w], bm[w], m);
+                p.part_val[blockIdx.x] = v; p.part_idx[blockIdx.x] = i; p.smp.part_raw[blockIdx.x] = raw;
+                p.smp.part_max[blockIdx.x] = m; p.part_sum[blockIdx.x] = sum;
+            }
+            return;
+        }
         if constexpr (LSE) {
             __shared__ float bs[GEMV_WAVES];
             if (lane == 0) bs[wave] = ls;         // (lm == best: the same compares in the same order)
@@ -438,10 +474,16 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
     const T* xg = (const T*)p.x;
     const T* gg = (const T*)p.norm_w;
     const int n_units = EPI == EPI_SWIGLU ? p.N / R : (p.N + R - 1) / R;      // one unit = R weight rows
-    constexpr bool AMAX = epi_is_argmax(EPI), LSE = EPI == EPI_ARGMAX_LSE;
-    float best = -INFINITY;                                                   // EPI_ARGMAX: thread b < B tracks env b
+    constexpr bool AMAX = epi_is_argmax(EPI), LSE = EPI == EPI_ARGMAX_LSE, SMP = EPI == EPI_SAMPLE;
+    static_assert(!(SMP && NORM), "EPI_SAMPLE has no fused-norm form");
+    float best = -INFINITY;                                                   // EPI_ARGMAX: thread b < B tracks env b (EPI_SAMPLE: the best z)
     int best_i = 0x7FFFFFFF;
     float lm = -INFINITY, ls = 0.0f;                                          // EPI_ARGMAX_LSE: env b's (max, sum exp(l - max)) over the workgroup's units
+    [[maybe_unused]] float best_raw = -INFINITY;                              // EPI_SAMPLE: the y of the best z
+    // EPI_SAMPLE: thread r * B + b evaluates the noise of column n0 + r for env b (one Philox per thread and unit); thread b reads its R values
+    [[maybe_unused]] __shared__ float gn[SMP ? R * B : 1];
+    [[maybe_unused]] int smp_stream = 0, smp_draw = 0;
+    if constexpr (SMP) if (tid < R * B) { smp_stream = p.smp.stream[tid % B]; smp_draw = p.smp.draw[tid % B]; }
     for (int u = blockIdx.x; u < n_units; u += gridDim.x) {
         const T* rows[R];
         int n0;
@@ -513,6 +555,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
 #pragma unroll
             for (int r = 0; r < R; ++r) acc[r][b] = wave_sum(acc[r][b]);
         }
+        if constexpr (SMP) if (tid < R * B) gn[tid] = gumbel_noise(p.smp.seed_lo, p.smp.seed_hi, smp_stream, smp_draw, u * R + tid / B);
         if (lane == 0) {
 #pragma unroll
             for (int b = 0; b < B; ++b) {
@@ -537,6 +580,14 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
                 for (int r = 0; r < R; ++r) {
                     float v = total(r * B + tid);
                     if (fl && n0 + r < p.N && fl[n0 + r]) v = v < 0.0f ? v * p.pen : v / p.pen;
+                    if constexpr (SMP) {
+                        const float y = v * p.smp.inv_t, z = y + gn[r * B + tid];
+                        if (n0 + r < p.N) {
+                            if (z > best) { best = z; best_i = n0 + r; best_raw = y; }
+                            lse_add(y, lm, ls);
+                        }
+                        continue;
+                    }
                     if (n0 + r < p.N && v > best) { best = v; best_i = n0 + r; }      // units ascend per workgroup: first max wins
                     // (the clamped rows of the last unit count once.  The arg-max ignores a fused norm's positive row factor, as the plain
                     // form does; a probability cannot: the SUM takes fl(v * factor), whose maximum is fl(best * factor) -- rounding is
@@ -559,6 +610,11 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
     if (AMAX && tid < B) {
         p.part_val[(size_t)tid * gridDim.x + blockIdx.x] = best;
         p.part_idx[(size_t)tid * gridDim.x + blockIdx.x] = best_i;
+        if constexpr (SMP) {
+            p.part_sum[(size_t)tid * gridDim.x + blockIdx.x] = ls;
+            p.smp.part_max[(size_t)tid * gridDim.x + blockIdx.x] = lm;
+            p.smp.part_raw[(size_t)tid * gridDim.x + blockIdx.x] = best_raw;
+        }
         if (LSE) {
             p.part_sum[(size_t)tid * gridDim.x + blockIdx.x] = ls;
             // every workgroup computes the same factor from the same sums in the same order: workgroup 0 publishes it
@@ -578,12 +634,43 @@ SVLN_DEV float block_sum_256(float mine, float* red) {
     return red[0];
 }
 
+// EPI_SAMPLE merge of one row's n partials on 256 threads: raw = pr[k] of the partial with pi[k] == tok (unique; 0 when tok owns none),
+// V = max_k pm[k], S = sum_k ps[k] * exp(pm[k] - V), all on fixed trees.  red / redi: 256 words each, free to overwrite; ends synchronised.
+struct SampleMerge { float raw, V, S; };
+SVLN_DEV SampleMerge sample_merge(const int* pi, const float* pr, const float* pm, const float* ps, int n, int tok, float* red, int* redi) {
+    __syncthreads();                              // red / redi have been read by every thread
+    float m = -INFINITY, raw = 0.0f;
+    for (int k = threadIdx.x; k < n; k += 256) {
+        m = pm[k] > m ? pm[k] : m;
+        if (pi[k] == tok) raw = pr[k];
+    }
+    red[threadIdx.x] = m; redi[threadIdx.x] = __float_as_int(raw);
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+            red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
+            redi[threadIdx.x] |= redi[threadIdx.x + s];       // one thread holds the bits, the others 0
+        }
+        __syncthreads();
+    }
+    SampleMerge r;
+    r.V = red[0]; r.raw = __int_as_float(redi[0]);
+    __syncthreads();
+    float mine = 0.0f;
+    for (int k = threadIdx.x; k < n; k += 256) mine += lse_rescale(ps[k], pm[k], r.V);
+    r.S = block_sum_256(mine, red);
+    return r;
+}
+
 // final arg-max of env b = blockIdx.x over its per-workgroup partials
 // LSE: also env b's log-probability of that token from its partial sums ps (NaN for token -1); rs (optional): the positive factor of
 // row b by which the producer scaled the logits it summed (a fused norm), so that partial k's maximum there is fl(pv[k] * rs[b])
-template <bool LSE>
+// SMP (with LSE): the EPI_SAMPLE merge -- the token on (pv, pi) as before; its y from pr of the partial that owns it; the log-sum-exp on
+// (pm, ps); score = y - V - log S
+template <bool LSE, bool SMP = false>
 __global__ __launch_bounds__(256) void argmax_final_batched_kernel(const float* pv, const int* pi, int n, int* out_tokens, const float* ps,
-                                                                   float* scores, const float* rs) {
+                                                                   float* scores, const float* rs, const float* pr = nullptr,
+                                                                   const float* pm = nullptr) {
     __shared__ float sv[256];
     __shared__ int si[256];
     const float* v0 = pv + (size_t)blockIdx.x * n;
@@ -606,6 +693,13 @@ __global__ __launch_bounds__(256) void argmax_final_batched_kernel(const float* 
         __syncthreads();
     }
     if (threadIdx.x == 0) out_tokens[blockIdx.x] = si[0] == 0x7FFFFFFF ? -1 : si[0];    // no finite logit: -1 (in-range for the next gather, an error on the host)
+    if constexpr (SMP) {
+        const int tok = si[0];
+        const size_t o = (size_t)blockIdx.x * n;
+        const SampleMerge mg = sample_merge(pi + o, pr + o, pm + o, ps + o, n, tok, sv, si);
+        if (threadIdx.x == 0) scores[blockIdx.x] = tok == 0x7FFFFFFF ? __builtin_nanf("") : mg.raw - mg.V + lse_logprob(mg.S);
+        return;
+    }
     if (LSE) {
         const float sc = rs ? rs[blockIdx.x] : 1.0f;
         const float V = sv[0] * sc;
@@ -694,9 +788,11 @@ __global__ __launch_bounds__(256) void quant_mxfp4_rows_kernel(const bf16* w, in
 // final arg-max over per-workgroup partials: greatest value, lowest index on ties (torch.argmax on CPU)
 // With `ctl` it is also one step of the greedy loop (GenerationMixin._sample: append, stop on EOS / max_new_tokens): see GenCtl.
 // LSE: also the token's log-probability from the partial sums ps, to scores[ctl->count] before the count advances (scores[0] without ctl)
-template <bool LSE>
+// SMP (with LSE): the EPI_SAMPLE merge (sample_merge) instead: score = y of the token - V - log S
+template <bool LSE, bool SMP = false>
 __global__ __launch_bounds__(256) void argmax_final_kernel(const float* pv, const int* pi, int n, int* out_token, float* out_top, GenCtl* ctl,
-                                                           const int* eos, int* out_ids, uint8_t* pen_flags, const float* ps, float* scores) {
+                                                           const int* eos, int* out_ids, uint8_t* pen_flags, const float* ps, float* scores,
+                                                           const float* pr = nullptr, const float* pm = nullptr) {
     __shared__ float sv[256];
     if (ctl && ctl->done) return;
     __shared__ int si[256];
@@ -726,7 +822,10 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const float* pv, cons
         *out_token = tok;
         if (out_top) { out_top[0] = sv[0]; out_top[1] = s2[0]; }
     }
-    if (LSE) {
+    if constexpr (SMP) {
+        const SampleMerge mg = sample_merge(pi, pr, pm, ps, n, si[0], s2, si);
+        if (threadIdx.x == 0) scores[ctl ? ctl->count : 0] = tok < 0 ? __builtin_nanf("") : mg.raw - mg.V + lse_logprob(mg.S);
+    } else if (LSE) {
         const float V = sv[0];
         __syncthreads();                          // sv / s2 have been read: s2 is reused by the sum
         float mine = 0.0f;
@@ -793,6 +892,7 @@ template <typename P> static void launch_gemv_fmt(hipStream_t s, const GemvArgs&
         case EPI_SWIGLU: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SWIGLU>), g, b, lds); break;
         case EPI_ARGMAX: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX>), g, b, lds); break;
         case EPI_ARGMAX_LSE: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX_LSE>), g, b, lds); break;
+        case EPI_SAMPLE: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SAMPLE>), g, b, lds); break;
         default: break;
     }
 }
@@ -826,15 +926,20 @@ template <typename T> void launch_gemv_batched(hipStream_t s, const GemvBatchArg
         case EPI_SWIGLU: if (norm) launch_gb<T, EPI_SWIGLU, true>(s, a); else launch_gb<T, EPI_SWIGLU, false>(s, a); break;
         case EPI_ARGMAX: if (norm) launch_gb<T, EPI_ARGMAX, true>(s, a); else launch_gb<T, EPI_ARGMAX, false>(s, a); break;
         case EPI_ARGMAX_LSE: if (norm) launch_gb<T, EPI_ARGMAX_LSE, true>(s, a); else launch_gb<T, EPI_ARGMAX_LSE, false>(s, a); break;
+        case EPI_SAMPLE:
+            if (norm) throw std::runtime_error("batched GEMV: EPI_SAMPLE has no fused-norm form");
+            launch_gb<T, EPI_SAMPLE, false>(s, a);
+            break;
         default: break;
     }
 }
 template void launch_gemv_batched<bf16>(hipStream_t, const GemvBatchArgs&);
 template void launch_gemv_batched<float>(hipStream_t, const GemvBatchArgs&);
 void launch_argmax_final_batched(hipStream_t s, const float* pv, const int* pi, int n, int B, int* out_tokens, const float* ps, float* scores,
-                                 const float* rs) {
-    if (ps) hipLaunchKernelGGL(argmax_final_batched_kernel<true>, dim3(B), dim3(256), 0, s, pv, pi, n, out_tokens, ps, scores, rs);
-    else hipLaunchKernelGGL(argmax_final_batched_kernel<false>, dim3(B), dim3(256), 0, s, pv, pi, n, out_tokens, ps, scores, rs);
+                                 const float* rs, const float* pr, const float* pm) {
+    if (pr) hipLaunchKernelGGL((argmax_final_batched_kernel<true, true>), dim3(B), dim3(256), 0, s, pv, pi, n, out_tokens, ps, scores, rs, pr, pm);
+    else if (ps) hipLaunchKernelGGL((argmax_final_batched_kernel<true, false>), dim3(B), dim3(256), 0, s, pv, pi, n, out_tokens, ps, scores, rs, pr, pm);
+    else hipLaunchKernelGGL((argmax_final_batched_kernel<false, false>), dim3(B), dim3(256), 0, s, pv, pi, n, out_tokens, ps, scores, rs, pr, pm);
 }
 template void launch_gemv_timed<bf16>(hipStream_t, const GemvArgs&, hipEvent_t, hipEvent_t);
 template void launch_gemv_timed<float>(hipStream_t, const GemvArgs&, hipEvent_t, hipEvent_t);
@@ -850,6 +955,7 @@ template <typename P> static void gemv_rows_attrs() {
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_SWIGLU>, GEMV_ROWS_MAX_LDS);
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX>, GEMV_ROWS_MAX_LDS);
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX_LSE>, GEMV_ROWS_MAX_LDS);
+    set_max_lds((const void*)gemv_rows_kernel<P, EPI_SAMPLE>, GEMV_ROWS_MAX_LDS);
 }
 void gemv_init_attrs() {
     gemv_rows_attrs<WMxfp4>(); gemv_rows_attrs<WE4m3>(); gemv_rows_attrs<WPlain<bf16>>(); gemv_rows_attrs<WPlain<float>>();
@@ -858,12 +964,23 @@ template void launch_gemv<bf16>(hipStream_t, const GemvArgs&);
 template void launch_gemv<float>(hipStream_t, const GemvArgs&);
 
 void launch_argmax_step(hipStream_t s, const float* pv, const int* pi, int n, int* out_token, float* out_top, GenCtl* ctl, const int* eos,
-                        int* out_ids, uint8_t* pen_flags, const float* ps, float* scores) {
-    if (ps) hipLaunchKernelGGL(argmax_final_kernel<true>, dim3(1), dim3(256), 0, s, pv, pi, n, out_token, out_top, ctl, eos, out_ids, pen_flags, ps, scores);
-    else hipLaunchKernelGGL(argmax_final_kernel<false>, dim3(1), dim3(256), 0, s, pv, pi, n, out_token, out_top, ctl, eos, out_ids, pen_flags, ps, scores);
+                        int* out_ids, uint8_t* pen_flags, const float* ps, float* scores, const float* pr, const float* pm) {
+    if (pr) hipLaunchKernelGGL((argmax_final_kernel<true, true>), dim3(1), dim3(256), 0, s, pv, pi, n, out_token, out_top, ctl, eos, out_ids, pen_flags, ps, scores, pr, pm);
+    else if (ps) hipLaunchKernelGGL((argmax_final_kernel<true, false>), dim3(1), dim3(256), 0, s, pv, pi, n, out_token, out_top, ctl, eos, out_ids, pen_flags, ps, scores, pr, pm);
+    else hipLaunchKernelGGL((argmax_final_kernel<false, false>), dim3(1), dim3(256), 0, s, pv, pi, n, out_token, out_top, ctl, eos, out_ids, pen_flags, ps, scores, pr, pm);
 }
-void launch_argmax_final(hipStream_t s, const float* pv, const int* pi, int n, int* out_token, float* out_top, const float* ps, float* scores) {
-    launch_argmax_step(s, pv, pi, n, out_token, out_top, nullptr, nullptr, nullptr, nullptr, ps, scores);
+void launch_argmax_final(hipStream_t s, const float* pv, const int* pi, int n, int* out_token, float* out_top, const float* ps, float* scores,
+                         const float* pr, const float* pm) {
+    launch_argmax_step(s, pv, pi, n, out_token, out_top, nullptr, nullptr, nullptr, nullptr, ps, scores, pr, pm);
+}
+namespace {
+__global__ __launch_bounds__(256) void gumbel_kernel(uint32_t seed_lo, uint32_t seed_hi, int stream, int draw, int n0, int count, float* out) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < count) out[k] = gumbel_noise(seed_lo, seed_hi, stream, draw, n0 + k);
+}
+}  // namespace
+void launch_gumbel(hipStream_t s, uint32_t seed_lo, uint32_t seed_hi, int stream, int draw, int n0, int count, float* out) {
+    hipLaunchKernelGGL(gumbel_kernel, dim3((count + 255) / 256), dim3(256), 0, s, seed_lo, seed_hi, stream, draw, n0, count, out);
 }
 namespace {
 __global__ __launch_bounds__(256) void set_flags_kernel(uint8_t* flags, const int* ids, const int* count, int n_host, int value) {

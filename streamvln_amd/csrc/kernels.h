@@ -9,12 +9,25 @@
 
 namespace svln {
 
-enum Epi : int { EPI_NONE = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_SWIGLU = 3, EPI_ARGMAX = 4, EPI_ARGMAX_LSE = 5 };
+enum Epi : int { EPI_NONE = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_SWIGLU = 3, EPI_ARGMAX = 4, EPI_ARGMAX_LSE = 5, EPI_SAMPLE = 6 };
 // EPI_ARGMAX_LSE (svln_set_token_scores): EPI_ARGMAX -- same accumulators, same compares, same partials, hence the same tokens -- plus one
 // fp32 per partial, part_sum[k] = sum exp(l_j - part_val[k]) over the (penalised) logits partial k owns.  The final kernels merge them,
 // S = sum_k part_sum[k] * exp(part_val[k] - V) with V the winning value, and write the token's log-probability -log S.  A partial that
 // owns no logit has (max -inf, sum 0) and merges as 0.
-constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE; }
+// EPI_SAMPLE (svln_set_sampling): temperature sampling as an arg-max (Gumbel-max).  With x the processed fp32 logit of column n (after the
+// repetition penalty), y = fl(x * inv_t) and z = y + G(seed, stream, draw, n) (gumbel_noise, common.h: a pure function of those four), the
+// token is argmax_n z, lowest column on ties.  A partial carries five values: part_val = its best z, part_idx, part_raw = the y of that
+// winner, part_max = max y, part_sum = sum exp(y - part_max) over the logits it owns (-inf, 0 for none).  The final kernels pick the token
+// on (part_val, part_idx), take the part_raw of the partial that owns it (a column belongs to one partial), V = max_k part_max[k],
+// S = sum_k part_sum[k] * exp(part_max[k] - V), and write the token's log-probability under softmax(x * inv_t): part_raw - V - log S.
+constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE || epi == EPI_SAMPLE; }
+// Inputs of EPI_SAMPLE.  stream / draw are device arrays indexed by the row of the product (row 0 of a GEMV), read by the kernel: nothing a
+// captured launch would freeze.  count (GEMV only, optional): a device scalar added to draw[0] (GenCtl::count: the tokens of this turn).
+struct SampleArgs {
+    const int* stream = nullptr; const int* draw = nullptr; const int* count = nullptr;
+    float inv_t = 1.0f; uint32_t seed_lo = 0, seed_hi = 0;
+    float* part_raw = nullptr; float* part_max = nullptr;      // beside part_val / part_sum, same shape
+};
 
 struct RopeKvArgs;
 // K / V^T pools of the ViT attention (layout of launch_vit_kv_pack): the fused tail of the SigLIP QKV product
@@ -60,13 +73,14 @@ struct GemmArgs {
     float* part_val = nullptr; int* part_idx = nullptr;
     const uint8_t* pen_flags = nullptr; const int* pen_rows = nullptr; float pen = 1.0f;
     float* part_sum = nullptr;    // non-null: the EPI_ARGMAX_LSE form, [m][tiles] beside part_val
+    SampleArgs smp;               // smp.part_raw non-null: the EPI_SAMPLE form (part_sum too)
     VitPackArgs vp; int vp_on;    // filled by the launcher: device-side copy of *vitpack for the unsplit kernels that pack in their epilogue
     int force_cfg, force_split;   // tests: 0 = heuristic; force_cfg 129 -> 128x128 tiles with two in-workgroup K groups; force_cfg low bits 128 -> 128x128 tiles, 264 -> 256x64 tiles; force_split S -> 256x128 tiles, S splits
 };
 // true: a.norm_out was produced, or the K / V^T pages of a.vitpack were.  vit_packer (host, optional): the writer of those pages --
 // 0 = none (the caller runs launch_vit_kv_pack), 1 = the split-K reduce (splitk_qkv_vitpack_kernel), 2 = the 128x128 tile epilogue
 template <typename T> bool launch_gemm(hipStream_t s, const GemmArgs& a, int* vit_packer = nullptr);
-template <typename T> int launch_gemm_argmax(hipStream_t s, GemmArgs a);    // EPI_ARGMAX form (M <= 32; EPI_ARGMAX_LSE when a.part_sum is set); returns the partials per row
+template <typename T> int launch_gemm_argmax(hipStream_t s, GemmArgs a);    // EPI_ARGMAX form (M <= 32; EPI_ARGMAX_LSE when a.part_sum is set, EPI_SAMPLE when a.smp.part_raw is); returns the partials per row
 
 // y[N] = epi(W[N,K] . x'[K] + bias) + res,  x' = x or rmsnorm(x) * norm_w (fused prologue).
 // EPI_SWIGLU as above (y has N/2 entries).  EPI_ARGMAX: no y; per-workgroup (max, lowest index)
@@ -93,7 +107,8 @@ struct GemvArgs {
     // generation_config.json `repetition_penalty`): pen_flags[n] != 0 marks token n as already generated in this turn;
     // its logit becomes v < 0 ? v * pen : v / pen.  null = no penalty.
     const uint8_t* pen_flags = nullptr; float pen = 1.0f;
-    float* part_sum = nullptr;    // EPI_ARGMAX_LSE only: [gemv_grid(N)] beside part_val
+    float* part_sum = nullptr;    // EPI_ARGMAX_LSE / EPI_SAMPLE: [gemv_grid(N)] beside part_val
+    SampleArgs smp;               // EPI_SAMPLE only
 };
 template <typename T> void launch_gemv(hipStream_t s, const GemvArgs& a);
 // per-row e4m3 quantisation of a bf16 matrix [rows][cols] (cols % 16 == 0): scale[r] = max|W[r]| / 448
@@ -117,15 +132,18 @@ struct GemvBatchArgs {
     float* part_val; int* part_idx;
     // EPI_ARGMAX only, optional repetition penalty (see GemvArgs): row b of the batch uses the flag row pen_rows[b] of pen_flags [.][N]
     const uint8_t* pen_flags = nullptr; const int* pen_rows = nullptr; float pen = 1.0f;
-    float* part_sum = nullptr;    // EPI_ARGMAX_LSE only: [B][grid] beside part_val
+    float* part_sum = nullptr;    // EPI_ARGMAX_LSE / EPI_SAMPLE: [B][grid] beside part_val
+    SampleArgs smp;               // EPI_SAMPLE only (no fused norm: launch_gemv_batched throws)
     float* row_scale = nullptr;   // EPI_ARGMAX_LSE with norm_w only: [B], the norm's row factor (the arg-max ignores it, the sums are taken on the scaled logits)
 };
 template <typename T> void launch_gemv_batched(hipStream_t s, const GemvBatchArgs& a);
 int gemv_batched_grid(int N, int epi, int B);
 // part_sum / scores (both or neither): the EPI_ARGMAX_LSE merge, scores[b] = log-probability of out_tokens[b] (NaN for token -1);
 // row_scale (optional, [B]): GemvBatchArgs::row_scale of the producer
+// part_raw / part_max (both or neither, with part_sum / scores): the EPI_SAMPLE merge instead (see there)
 void launch_argmax_final_batched(hipStream_t s, const float* part_val, const int* part_idx, int n, int B, int* out_tokens,
-                                 const float* part_sum = nullptr, float* scores = nullptr, const float* row_scale = nullptr);
+                                 const float* part_sum = nullptr, float* scores = nullptr, const float* row_scale = nullptr,
+                                 const float* part_raw = nullptr, const float* part_max = nullptr);
 // B (1 .. 8) bf16 activation vectors against one MXFP4 weight stream on v_mfma_f32_16x16x32_bf16 (gemv_mx4b.hip; bf16 engine, opt-in):
 // q4 / e8 / ldw as GemvArgs::w4 / e8 / ldw (the layout of the batch-1 GEMVs), x [B][ldx], y [B][ldy], res [B][ldr]; K, ldw multiples of 32,
 // ldx a multiple of 8.  No fused RMSNorm.  EPI_SWIGLU as above.  EPI_ARGMAX: part_val / part_idx are [B][gemv_mx4b_grid(N, epi)], reduced
@@ -145,7 +163,7 @@ int gemv_mx4b_grid(int N, int epi);
 // part_sum / scores (both or neither): the EPI_ARGMAX_LSE merge; the token's log-probability goes to scores[0]
 void launch_argmax_final(hipStream_t s, const float* part_val, const int* part_idx, int n, int* out_token,
                          float* out_top /*[2]: best, runner-up of partial maxima (diagnostic)*/, const float* part_sum = nullptr,
-                         float* scores = nullptr);
+                         float* scores = nullptr, const float* part_raw = nullptr, const float* part_max = nullptr);
 // Device-side state of one greedy generation (GenerationMixin._sample: append the arg-max, stop on EOS or max_new_tokens), so that
 // decode steps can be enqueued ahead of the host: every kernel of a step is a no-op once `done` is set.
 struct GenCtl {
@@ -153,14 +171,19 @@ struct GenCtl {
     int kv_len;     // keys visible to that step (= pos + 1)
     int done;       // set by the arg-max step that emitted EOS / the max_new-th token / a non-finite arg-max (-1)
     int count;      // tokens emitted so far (out_ids[0 .. count))
-    int max_new, n_eos, pad0, pad1;
+    int max_new, n_eos;
+    int draw0, stream;  // EPI_SAMPLE (svln_set_sampling): the env's draw counter at the start of the turn (token t draws draw0 + count) and its noise stream
 };
 // launch_argmax_final + the bookkeeping above: out_ids[count++] = token; done |= token in eos[0 .. n_eos) || count == max_new || token < 0;
 // otherwise pos / kv_len advance by one.  No-op when ctl->done is already set.
 // pen_flags (optional): the emitted token's byte is set (repetition penalty of the following steps)
 // part_sum / scores (both or neither): the EPI_ARGMAX_LSE merge; scores[count] = the token's log-probability, written before count advances
+// part_raw / part_max (both or neither, with part_sum / scores): the EPI_SAMPLE merge instead
 void launch_argmax_step(hipStream_t s, const float* part_val, const int* part_idx, int n, int* out_token, float* out_top, GenCtl* ctl,
-                        const int* eos, int* out_ids, uint8_t* pen_flags = nullptr, const float* part_sum = nullptr, float* scores = nullptr);
+                        const int* eos, int* out_ids, uint8_t* pen_flags = nullptr, const float* part_sum = nullptr, float* scores = nullptr,
+                        const float* part_raw = nullptr, const float* part_max = nullptr);
+// TEST-ONLY: out[k] = gumbel_noise(seed, stream, draw, n0 + k) for k < count
+void launch_gumbel(hipStream_t s, uint32_t seed_lo, uint32_t seed_hi, int stream, int draw, int n0, int count, float* out);
 // Draft-verified greedy decode (svln_set_speculative; misc.hip).  launch_verify_feed builds the rows of the next verify pass from GenCtl,
 // the last token and the device copy of the draft: fed[0 .. rows) and vctl[1] = rows used (vctl[0] = usable draft length, set by the
 // host).  launch_verify_step applies the verify rule to the rows' arg-maxes `cand`: appends the accepted tokens to out_ids, advances

@@ -189,6 +189,8 @@ class StreamVLNForCausalLM:
         self._auto_draft = False                                   # set_auto_draft: guess that a turn repeats the env's previous one
         self._last_out: Dict[int, torch.Tensor] = {}
         self._token_scores = False                                 # set_token_scores: results carry token_logprobs
+        self._sampling = None                                      # set_sampling: None (greedy) or (temperature, seed) the engine holds
+        self.sampling_seed = 0                                     # seed of the noise of generate(do_sample=True) (see set_sampling)
         self._batch_draft = False                                  # set_batch_draft: the scheduler consumes drafts
         self.reset(max_envs)
 
@@ -265,6 +267,8 @@ class StreamVLNForCausalLM:
             if not float(rp) > 0:
                 raise ValueError(f"generation_config.repetition_penalty must be > 0, got {rp}")
             self.generation_config.repetition_penalty = float(rp)
+        if gen.get("temperature") is not None:                   # read by do_sample=True calls only (inert under the greedy call)
+            self.generation_config.temperature = float(gen["temperature"])
         bad = []
         for k, neutral in self._UNSUPPORTED_GENERATION_KEYS.items():
             v = gen.get(k, neutral)
@@ -444,8 +448,14 @@ class StreamVLNForCausalLM:
         past = kwargs.pop("past_key_values", None)
         max_new = int(kwargs.pop("max_new_tokens", 10000))
         eos = kwargs.pop("eos_token_ids", None)
-        if kwargs.get("do_sample", False) or kwargs.get("num_beams", 1) != 1:
-            raise NotImplementedError("only greedy decoding (do_sample=False, num_beams=1) is on the path")
+        if kwargs.get("num_beams", 1) != 1:
+            raise NotImplementedError(f"num_beams={kwargs.get('num_beams')!r}: only greedy decoding and temperature sampling (num_beams=1) are on the path")
+        if kwargs.get("do_sample", False):
+            # temperature sampling only (set_sampling): truncated sampling would need the sorted distribution, which the engine never builds
+            if kwargs.get("top_k") not in (None, 0):
+                raise NotImplementedError(f"top_k={kwargs['top_k']!r}: do_sample=True supports the temperature only (top_k None or 0)")
+            if kwargs.get("top_p") not in (None, 1.0):
+                raise NotImplementedError(f"top_p={kwargs['top_p']!r}: do_sample=True supports the temperature only (top_p None or 1.0)")
         if eos is None:
             eos = self.generation_config.eos_token_id
         eos = [int(e) for e in (eos if isinstance(eos, (list, tuple)) else [eos])]
@@ -490,6 +500,22 @@ class StreamVLNForCausalLM:
         seq = torch.from_numpy(np.asarray(tokens, dtype=np.int64).copy()).unsqueeze(0).to(dev)
         return GenerateOutput(sequences=seq, past_key_values=KVHandle(env_id, self._epoch[env_id], kl.value))
 
+    def _sync_sampling(self, kwargs):
+        """`do_sample` of a call -> the engine switch, flipped only when it differs from what the engine holds (a flip restarts the draw
+        counters).  do_sample=True: the temperature of the call, else generation_config.temperature, else 1.0; the seed is
+        self.sampling_seed.  do_sample=False -- the reference harness's call -- is the untouched greedy path whatever a checkpoint's
+        generation_config says.  A call without the key leaves the switch as set_sampling left it."""
+        if "do_sample" not in kwargs:
+            return
+        want = None
+        if kwargs["do_sample"]:
+            t = kwargs.get("temperature")
+            if t is None:
+                t = getattr(self.generation_config, "temperature", None)
+            want = (float(1.0 if t is None else t), int(self.sampling_seed))
+        if want != self._sampling:
+            self.set_sampling(None) if want is None else self.set_sampling(*want)
+
     def _scores(self, getter, *args, n_new, device):
         """token_logprobs [1, n_new] (fp32, on `device`) of a finished turn from one of the engine's score getters"""
         buf = np.empty(max(n_new, 1), dtype=np.float32)
@@ -510,6 +536,7 @@ class StreamVLNForCausalLM:
         draft = draft_ids
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
         self._sync_call_config()
+        self._sync_sampling(kwargs)
         # the reference's bookkeeping that needs no engine call: the KV handle must be this env's current one; curr_t counts the turns
         if past is not None and (not isinstance(past, KVHandle) or past.env_id != env_id or past.epoch != self._epoch[env_id]):
             raise ValueError("past_key_values does not belong to this env's current window")
@@ -605,6 +632,10 @@ class StreamVLNForCausalLM:
         if self._tickets:
             raise RuntimeError("generate_batch needs an idle scheduler: collect or cancel the submitted turns first")
         self._sync_call_config()
+        modes = {(bool(p[0].get("do_sample", False)), p[0].get("temperature")) if "do_sample" in p[0] else None for p in parsed}
+        if len(modes) != 1:
+            raise ValueError("do_sample / temperature must be the same for every request of a batch")
+        self._sync_sampling(parsed[0][0])
         # vision: encode the frames of as many requests as fit the frame buffer per call, then splice per env
         i = 0
         while i < len(parsed):
@@ -659,6 +690,7 @@ class StreamVLNForCausalLM:
         if len(self._tickets) >= 8:
             raise RuntimeError("at most 8 turns in flight: collect finished turns with step_batch first")
         self._sync_call_config()
+        self._sync_sampling(kwargs)               # (a flip while other turns are in flight is refused by the engine: nothing has changed yet)
         on_dev = int(pix.is_cuda)
         if on_dev:
             self._order_engine_after(pix)
@@ -842,6 +874,29 @@ class StreamVLNForCausalLM:
         it is on), and while scheduler turns are in flight."""
         _check(self._lib.svln_set_token_scores(self._h, int(bool(enable))))
         self._token_scores = bool(enable)
+
+    def set_sampling(self, temperature: Optional[float] = 1.0, seed: int = 0):
+        """Opt-in, default off (svln_set_sampling).  set_sampling(T, seed): every turn samples its ids from softmax(processed logits / T)
+        instead of taking the arg-max -- exactly, by the Gumbel-max identity: the lm_head kernels add noise G(seed, env slot, draw, column)
+        to logit / T inside their fused arg-max, so there are still no logits in memory and no second pass over the lm_head.  The noise
+        is a pure function of those four, so generate, generate_batch and the scheduler emit the same ids for the same seed wherever
+        their logits agree, and a run is reproducible.  `draw` counts the ids the env has emitted since this call: EVERY call, also
+        one that repeats the current setting, restarts the counters.  With set_token_scores on, `token_logprobs` is
+        log softmax(processed / T)[id] (HF's `scores` under sampling).  set_sampling(None): off, the greedy path.
+        generate / generate_batch / submit flip the switch themselves from `do_sample=` / `temperature=` (see _sync_sampling), with
+        self.sampling_seed as the seed.  An explicit `do_sample=False` -- StreamingAgent's default request carries it -- switches the
+        engine back to greedy: set_sampling alone samples only for calls that pass do_sample=True or leave the key out; build the agents
+        with do_sample=True.  Refused with set_speculative / set_prefill_draft / set_batch_draft, set_decode_persistent and
+        set_mxfp4_batched (and they while it is on), and while scheduler turns are in flight."""
+        if temperature is None:
+            _check(self._lib.svln_set_sampling(self._h, 0, 1.0, 0))
+            self._sampling = None
+            return
+        t, sd = float(temperature), int(seed)
+        if not (t > 0 and np.isfinite(t)):
+            raise ValueError(f"set_sampling: the temperature must be finite and > 0, got {temperature!r}")
+        _check(self._lib.svln_set_sampling(self._h, 1, t, sd & 0xFFFFFFFFFFFFFFFF))
+        self._sampling = (t, sd)
 
     def set_batch_draft(self, enable: bool):
         """opt-in drafts in the scheduler's prefill pass (svln_set_batch_draft): the first ids of a turn's draft (`draft_ids` of submit /
