@@ -468,8 +468,27 @@ int svln_op_gemm_argmax_sample(svln_engine* h, const void* A, int lda, const voi
                                const int32_t* pen_rows, float penalty, float temperature, uint64_t seed, const int32_t* streams,
                                const int32_t* draws, int32_t* host_tokens, float* host_logprobs);
 int svln_op_gumbel(svln_engine* h, uint64_t seed, int32_t stream, int32_t draw, int32_t n0, int32_t count, float* host_out);
+/* the row helpers between the products (misc.hip), rows of n values of the engine type on the device.  Every op refuses null pointers,
+ * rows < 0 and an n that is not a positive multiple of the 16-byte chunk (8 bf16 / 4 fp32 values: the kernels move whole chunks). */
 int svln_op_rmsnorm(svln_engine* h, const void* x, const void* g, void* y, int rows, int n, float eps);
 int svln_op_layernorm(svln_engine* h, const void* x, const void* g, const void* b, void* y, int rows, int n, float eps);
+/* the RMSNorm launch of a graph-replayed decode step: a device skip word (non-zero: nothing is written) and a second copy of the rows at
+ * row min(y2_row_value + r, y2_cap - 1) of y2, the row index read from a device word */
+int svln_op_rmsnorm_tap(svln_engine* h, const void* x, const void* g, void* y, int rows, int n, float eps, int skip_value, void* y2, int y2_row_value,
+                        int y2_cap);
+/* y[r] = RMSNorm(x[src_rows[r]]), copied to tap[tap_rows[r]] unless that is -1.  src_rows / tap_rows: host arrays of `rows` ints, refused
+ * when an entry lies outside [0, x_rows) / [-1, tap_cap) */
+int svln_op_rmsnorm_indexed(svln_engine* h, const void* x, int x_rows, const void* g, void* y, const int32_t* src_rows, const int32_t* tap_rows,
+                            void* tap, int tap_cap, int rows, int n, float eps);
+/* out[r] = embed[src[r]] for src[r] >= 0, feats[-(src[r] + 1)] otherwise (the embedding splice); src: host array, refused outside
+ * [-feat_rows, embed_rows).  A non-zero skip_value (a device word, like GenCtl.done) leaves out untouched. */
+int svln_op_gather_rows(svln_engine* h, const int32_t* src, int rows, const void* embed, int embed_rows, const void* feats, int feat_rows, void* out,
+                        int n, int skip_value);
+/* out[list[2 i]] = embed[list[2 i + 1]] for i < rows; list: host array of (destination row, token id) pairs, refused outside
+ * [0, out_rows) / [0, embed_rows) */
+int svln_op_gather_rows_ragged(svln_engine* h, const int32_t* list, int rows, const void* embed, int embed_rows, void* out, int out_rows, int n);
+/* the 128-bit content keys of the feature cache: F frames of words_per_frame 32-bit words each (device) -> out_keys[2 F] (host) */
+int svln_op_frame_hash(svln_engine* h, const void* pix_dev, int F, int64_t words_per_frame, uint64_t* out_keys);
 /* attention over caller-provided q [T][q_stride] and k/v [S][kv_stride] (engine packs them into pages):
  * llm: rope = 1 applies RoPE at positions P + i to q and k (head_dim 128, GQA G = nq/nkv, causal)
  * vit: head_dim 72, non-causal, frames * heads */

@@ -161,6 +161,11 @@ SIGNATURES = {
     "svln_op_gumbel": (_I, [_P, _U64, _I, _I, _I, _I, _PF]),
     "svln_op_rmsnorm": (_I, [_P, _P, _P, _P, _I, _I, _F]),
     "svln_op_layernorm": (_I, [_P, _P, _P, _P, _P, _I, _I, _F]),
+    "svln_op_rmsnorm_tap": (_I, [_P, _P, _P, _P, _I, _I, _F, _I, _P, _I, _I]),
+    "svln_op_rmsnorm_indexed": (_I, [_P, _P, _I, _P, _P, _PI32, _PI32, _P, _I, _I, _I, _F]),
+    "svln_op_gather_rows": (_I, [_P, _PI32, _I, _P, _I, _P, _I, _P, _I, _I]),
+    "svln_op_gather_rows_ragged": (_I, [_P, _PI32, _I, _P, _I, _P, _I, _I]),
+    "svln_op_frame_hash": (_I, [_P, _P, _I, _I64, C.POINTER(C.c_uint64)]),
     "svln_op_attention_llm": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _I]),
     "svln_op_attention_vit": (_I, [_P, _P, _I, _I, _P, _I]),
     "svln_op_attention_decode": (_I, [_P, _I, _P, _I, _I64, _PI32, _P, _P, _I]),

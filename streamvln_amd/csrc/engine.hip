@@ -145,6 +145,14 @@ struct EngineBase {
     virtual void op_quant_mxfp4(const void* w, int64_t rows, int cols, void* q4, uint8_t* e8) = 0;
     virtual void op_rmsnorm(const void* x, const void* g, void* y, int rows, int n, float eps) = 0;
     virtual void op_layernorm(const void* x, const void* g, const void* b, void* y, int rows, int n, float eps) = 0;
+    virtual void op_rmsnorm_tap(const void* x, const void* g, void* y, int rows, int n, float eps, int skip_value, void* y2, int y2_row_value,
+                                int y2_cap) = 0;
+    virtual void op_rmsnorm_indexed(const void* x, int x_rows, const void* g, void* y, const int32_t* src_rows, const int32_t* tap_rows, void* tap,
+                                    int tap_cap, int rows, int n, float eps) = 0;
+    virtual void op_gather_rows(const int32_t* src, int rows, const void* embed, int embed_rows, const void* feats, int feat_rows, void* out, int n,
+                                int skip_value) = 0;
+    virtual void op_gather_rows_ragged(const int32_t* list, int rows, const void* embed, int embed_rows, void* out, int out_rows, int n) = 0;
+    virtual void op_frame_hash(const void* pix, int F, int64_t words_per_frame, uint64_t* out_keys) = 0;
     virtual void op_attention_llm(void* qkv, int ld, int T, int P, const void* ctx, int ctx_T, void* out, int o_stride, int nsplit) = 0;
     virtual void op_attention_vit(const void* qkv, int ld, int F, void* out, int o_stride) = 0;
     virtual void op_attention_decode(int B, const void* ctx, int ld, int64_t ctx_rows, const int32_t* pos, const void* qkv_new, void* out,
@@ -2610,9 +2618,112 @@ public:
         sync();
         LAUNCH_CHECK("op_quant_mxfp4");
     }
-    void op_rmsnorm(const void* xi, const void* g, void* y, int rows, int n, float eps) override { launch_rmsnorm<T>(st, xi, g, y, rows, n, eps); sync(); }
+    // ---- row helpers (misc.hip).  The ops check what the engine's own callers guarantee; lists arrive on the host, are range-checked and
+    // go to a device buffer that lives for the call.  Test surface only, not for a hot path: every call allocates and frees device memory
+    // (hipFree synchronises the device) and ends with a stream sync.
+    void require_row_width(int n) {
+        constexpr int EPC = Elt<T>::PER_CHUNK;
+        REQUIRE(n > 0 && n % EPC == 0,
+                std::string("n must be a positive multiple of the 16-byte chunk (") + std::to_string(EPC) + " values of the engine type)");
+    }
+    struct OpInts {          // `count` ints on the device for the length of one op
+        int* d = nullptr;
+        OpInts(const int32_t* host, size_t count) {
+            HIP_CHECK(hipMalloc((void**)&d, (count ? count : 1) * sizeof(int)));
+            if (count && hipMemcpy(d, host, count * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+                (void)hipFree(d);
+                REQUIRE(false, "op: list upload failed");
+            }
+        }
+        ~OpInts() { (void)hipFree(d); }
+        OpInts(const OpInts&) = delete;
+        OpInts& operator=(const OpInts&) = delete;
+    };
+    void op_rmsnorm(const void* xi, const void* g, void* y, int rows, int n, float eps) override {
+        REQUIRE(xi && g && y, "null pointer");
+        REQUIRE(rows >= 0, "rows must be >= 0");
+        require_row_width(n);
+        launch_rmsnorm<T>(st, xi, g, y, rows, n, eps);
+        sync();
+        LAUNCH_CHECK("op_rmsnorm");
+    }
     void op_layernorm(const void* xi, const void* g, const void* b, void* y, int rows, int n, float eps) override {
-        launch_layernorm<T>(st, xi, g, b, y, rows, n, eps); sync();
+        REQUIRE(xi && g && b && y, "null pointer");
+        REQUIRE(rows >= 0, "rows must be >= 0");
+        require_row_width(n);
+        launch_layernorm<T>(st, xi, g, b, y, rows, n, eps);
+        sync();
+        LAUNCH_CHECK("op_layernorm");
+    }
+    void op_rmsnorm_tap(const void* xi, const void* g, void* y, int rows, int n, float eps, int skip_value, void* y2, int y2_row_value,
+                        int y2_cap) override {
+        REQUIRE(xi && g && y && y2, "null pointer");
+        REQUIRE(rows >= 0, "rows must be >= 0");
+        require_row_width(n);
+        REQUIRE(y2_cap >= 1 && y2_row_value >= 0, "y2_cap must be >= 1 and y2_row >= 0");
+        const int32_t words[2] = {skip_value, y2_row_value};
+        OpInts d(words, 2);
+        launch_rmsnorm<T>(st, xi, g, y, rows, n, eps, d.d, y2, d.d + 1, y2_cap);
+        sync();
+        LAUNCH_CHECK("op_rmsnorm_tap");
+    }
+    void op_rmsnorm_indexed(const void* xi, int x_rows, const void* g, void* y, const int32_t* src_rows, const int32_t* tap_rows, void* tap,
+                            int tap_cap, int rows, int n, float eps) override {
+        REQUIRE(xi && g && y && src_rows && tap_rows && tap, "null pointer");
+        REQUIRE(rows >= 0 && x_rows >= 1 && tap_cap >= 1, "rows must be >= 0, x_rows and tap_cap >= 1");
+        require_row_width(n);
+        for (int r = 0; r < rows; ++r) {
+            REQUIRE(src_rows[r] >= 0 && src_rows[r] < x_rows, "src_rows entry out of range");
+            REQUIRE(tap_rows[r] >= -1 && tap_rows[r] < tap_cap, "tap_rows entry out of range");
+        }
+        std::vector<int32_t> both(src_rows, src_rows + rows);
+        both.insert(both.end(), tap_rows, tap_rows + rows);
+        OpInts d(both.data(), both.size());
+        launch_rmsnorm_indexed<T>(st, xi, g, y, d.d, d.d + rows, tap, rows, n, eps);
+        sync();
+        LAUNCH_CHECK("op_rmsnorm_indexed");
+    }
+    void op_gather_rows(const int32_t* src, int rows, const void* emb, int embed_rows, const void* ft, int feat_rows, void* out, int n,
+                        int skip_value) override {
+        REQUIRE(src && emb && ft && out, "null pointer");
+        REQUIRE(rows >= 0 && embed_rows >= 1 && feat_rows >= 1, "rows must be >= 0, embed_rows and feat_rows >= 1");
+        require_row_width(n);
+        for (int r = 0; r < rows; ++r) REQUIRE(src[r] < embed_rows && src[r] >= -feat_rows, "src entry out of range");
+        std::vector<int32_t> h(src, src + rows);
+        h.push_back(skip_value);
+        OpInts d(h.data(), h.size());
+        launch_gather_rows<T>(st, d.d, emb, ft, out, rows, n, d.d + rows);
+        sync();
+        LAUNCH_CHECK("op_gather_rows");
+    }
+    void op_gather_rows_ragged(const int32_t* list, int rows, const void* emb, int embed_rows, void* out, int out_rows, int n) override {
+        REQUIRE(list && emb && out, "null pointer");
+        REQUIRE(rows >= 0 && embed_rows >= 1 && out_rows >= 1, "rows must be >= 0, embed_rows and out_rows >= 1");
+        require_row_width(n);
+        for (int r = 0; r < rows; ++r) {
+            REQUIRE(list[2 * r] >= 0 && list[2 * r] < out_rows, "destination row out of range");
+            REQUIRE(list[2 * r + 1] >= 0 && list[2 * r + 1] < embed_rows, "token id out of range");
+        }
+        OpInts d(list, (size_t)2 * rows);
+        launch_gather_rows_ragged<T>(st, d.d, emb, out, rows, n);
+        sync();
+        LAUNCH_CHECK("op_gather_rows_ragged");
+    }
+    void op_frame_hash(const void* p, int F, int64_t words_per_frame, uint64_t* out_keys) override {
+        REQUIRE(p && out_keys, "null pointer");
+        REQUIRE(F >= 1 && F <= 65535 && words_per_frame >= 1 && words_per_frame <= ((int64_t)1 << 32),
+                "F must be 1 .. 65535, words_per_frame 1 .. 2^32");
+        unsigned long long* dk = nullptr;
+        HIP_CHECK(hipMalloc((void**)&dk, (size_t)2 * F * sizeof(unsigned long long)));
+        hipError_t e = hipMemsetAsync(dk, 0, (size_t)2 * F * sizeof(unsigned long long), st);
+        if (e == hipSuccess) {
+            launch_frame_hash(st, (const float*)p, F, (size_t)words_per_frame, dk);
+            e = hipStreamSynchronize(st);
+        }
+        if (e == hipSuccess) e = hipMemcpy(out_keys, dk, (size_t)2 * F * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        (void)hipFree(dk);
+        HIP_CHECK(e);
+        LAUNCH_CHECK("op_frame_hash");
     }
     // ---- attention ops.  An op resets the envs it uses on entry (never on exit: svln_op_kv_read sees what the op wrote) and gives each
     // the pages op_set_pages fixed for it, in that order, or else pages from the free list.
@@ -3232,6 +3343,24 @@ int svln_op_gemv_mxfp4_batched_argmax_pen(svln_engine* h, const void* q4, const 
 int svln_op_rmsnorm(svln_engine* h, const void* x, const void* g, void* y, int rows, int n, float eps) { API_BEGIN_H h->impl->op_rmsnorm(x, g, y, rows, n, eps); API_END }
 int svln_op_layernorm(svln_engine* h, const void* x, const void* g, const void* b, void* y, int rows, int n, float eps) {
     API_BEGIN_H h->impl->op_layernorm(x, g, b, y, rows, n, eps); API_END
+}
+int svln_op_rmsnorm_tap(svln_engine* h, const void* x, const void* g, void* y, int rows, int n, float eps, int skip_value, void* y2, int y2_row_value,
+                        int y2_cap) {
+    API_BEGIN_H h->impl->op_rmsnorm_tap(x, g, y, rows, n, eps, skip_value, y2, y2_row_value, y2_cap); API_END
+}
+int svln_op_rmsnorm_indexed(svln_engine* h, const void* x, int x_rows, const void* g, void* y, const int32_t* src_rows, const int32_t* tap_rows,
+                            void* tap, int tap_cap, int rows, int n, float eps) {
+    API_BEGIN_H h->impl->op_rmsnorm_indexed(x, x_rows, g, y, src_rows, tap_rows, tap, tap_cap, rows, n, eps); API_END
+}
+int svln_op_gather_rows(svln_engine* h, const int32_t* src, int rows, const void* embed, int embed_rows, const void* feats, int feat_rows, void* out,
+                        int n, int skip_value) {
+    API_BEGIN_H h->impl->op_gather_rows(src, rows, embed, embed_rows, feats, feat_rows, out, n, skip_value); API_END
+}
+int svln_op_gather_rows_ragged(svln_engine* h, const int32_t* list, int rows, const void* embed, int embed_rows, void* out, int out_rows, int n) {
+    API_BEGIN_H h->impl->op_gather_rows_ragged(list, rows, embed, embed_rows, out, out_rows, n); API_END
+}
+int svln_op_frame_hash(svln_engine* h, const void* pix_dev, int F, int64_t words_per_frame, uint64_t* out_keys) {
+    API_BEGIN_H h->impl->op_frame_hash(pix_dev, F, words_per_frame, out_keys); API_END
 }
 int svln_op_attention_llm(svln_engine* h, void* qkv, int ld, int T, int P, const void* ctx, int ctx_T, void* out, int o_stride, int nsplit) {
     API_BEGIN_H h->impl->op_attention_llm(qkv, ld, T, P, ctx, ctx_T, out, o_stride, nsplit); API_END
