@@ -184,6 +184,31 @@ int svln_set_sampling(svln_engine* h, int enable, float temperature, uint64_t se
 int svln_get_token_scores(svln_engine* h, float* host_out, int cap, int32_t* n);
 int svln_batch_scores(svln_engine* h, int slot, float* host_out, int cap, int32_t* n);
 int svln_generate_batch_scores(svln_engine* h, int index, float* host_out, int cap, int32_t* n);
+/* Opt-in, default off: allowed-token decode (HF's prefix_allowed_tokens_fn with a constant set; vLLM's allowed_token_ids).  ids[0 .. n) is
+ * the allowed list A = a_0 < a_1 < ... < a_{n-1}, 1 <= n <= 256, every id in [0, vocab); n == 0 switches it off.  While set, EVERY lm_head
+ * product of the engine (svln_generate / svln_turn, svln_generate_batch, the scheduler, verify passes, rides) is the product over the
+ * listed rows only: x_a = the fp32 dot of lm_head row a with the final-norm row (elements converted to fp32, fp32 fmaf, 16-byte chunks per
+ * lane, a summation order that depends on the hidden size alone -- not on the row count, the list or a's place in it, so the same pair
+ * gives the same bits on every path).  It reads the engine-dtype lm_head (bf16 or fp32) whichever weight-format switch is on: a product
+ * of <= 256 rows gains nothing from the e4m3 / MXFP4 copies, and one format makes the head the same function everywhere.
+ * Repetition penalty: as before, on the flag of the vocabulary id.  Greedy: token = argmax over A, lowest id on ties, -1 when no allowed
+ * id has a finite value (NaN and -inf never win).  Sampling (svln_set_sampling): y_a = fl(x_a * invT), z_a = y_a + G(seed, stream, draw,
+ * a) -- the noise column is the vocabulary id, so the turn is the full-vocabulary sampled turn conditioned on A, with the same noise.
+ * Scores (svln_set_token_scores): log softmax over the processed logits OF THE SET at the emitted id (HF's semantics with -inf elsewhere).
+ * The list is taken as given: without an EOS id in it a turn ends at max_new_tokens.
+ * Refused before any launch or state change (svln_last_error says which): n > 256 or n < 0, an id outside the vocabulary, a list that is
+ * not strictly ascending, a null list with n > 0, any call while scheduler turns are in flight.  A call that repeats the current list
+ * succeeds and changes nothing; a change synchronises the stream and drops the captured decode graphs.  Composes with every other
+ * switch: only the lm_head product is swapped, every existing refusal stays as it is.
+ * While svln_set_token_scores is on as well, the whole distribution over A of every emitted token is kept:
+ * allowed_logprobs[t][j] = y_j - logsumexp_i y_i (y = x after the penalty; x * invT under sampling); a NaN logit makes that row NaN.  It
+ * travels in the synchronisation that already reads ids and scores.  svln_get_allowed_logprobs / svln_batch_allowed_logprobs /
+ * svln_generate_batch_allowed_logprobs: lifetimes of the three score getters above; *n_tokens rows of *n_ids floats each, host_out
+ * receives min(*n_tokens * *n_ids, cap_floats) of them; each fails when the scores or the list were off for that turn. */
+int svln_set_allowed_tokens(svln_engine* h, const int64_t* ids, int n);
+int svln_get_allowed_logprobs(svln_engine* h, float* host_out, int cap_floats, int32_t* n_tokens, int32_t* n_ids);
+int svln_batch_allowed_logprobs(svln_engine* h, int slot, float* host_out, int cap_floats, int32_t* n_tokens, int32_t* n_ids);
+int svln_generate_batch_allowed_logprobs(svln_engine* h, int index, float* host_out, int cap_floats, int32_t* n_tokens, int32_t* n_ids);
 /* prefill taps of svln_generate (single env): enable != 0 records the LAST row of the residual stream after every decoder layer of the
  * next prefills (svln_get_layer_taps: host_out [layers][hidden]); probe_layer >= 0 additionally records, for every row of the prefill,
  * the operands the products of that one layer actually saw (svln_get_layer_probe, which: 0 = x entering the layer, 1 = x leaving it,
@@ -468,6 +493,15 @@ int svln_op_gemm_argmax_sample(svln_engine* h, const void* A, int lda, const voi
                                const int32_t* pen_rows, float penalty, float temperature, uint64_t seed, const int32_t* streams,
                                const int32_t* draws, int32_t* host_tokens, float* host_logprobs);
 int svln_op_gumbel(svln_engine* h, uint64_t seed, int32_t stream, int32_t draw, int32_t n0, int32_t count, float* host_out);
+/* TEST-ONLY: one subset product of svln_set_allowed_tokens (gemv_subset.hip) on caller-given operands; the engine's own list and switches
+ * are not touched.  W [V][ldw], x [B][ldx] device, engine dtype; ids [n] host (the rules of svln_set_allowed_tokens with vocab = V);
+ * 1 <= B <= 32; K a positive multiple of the 16-byte chunk, ldw, ldx >= K and multiples of it.  pen_flags (device, optional) [.][V] with
+ * pen_rows (device, optional, [B]; null = every row uses flag row 0) and penalty > 0.  temperature == 0: greedy; > 0: sampled with
+ * seed and the host arrays streams / draws [B]; anything else (negative, NaN, inf) is refused.  Returns host_tokens [B], host_logprobs
+ * [B], host_y [B][n] (the processed values y) and host_dist [B][n] (y - logsumexp y).  Malformed calls are refused before any launch. */
+int svln_op_subset_argmax(svln_engine* h, const void* W, int ldw, const void* x, int ldx, int V, int K, int B, const int64_t* ids, int n,
+                          const void* pen_flags, const int32_t* pen_rows, float penalty, float temperature, uint64_t seed, const int32_t* streams,
+                          const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* host_y, float* host_dist);
 /* the row helpers between the products (misc.hip), rows of n values of the engine type on the device.  Every op refuses null pointers,
  * rows < 0 and an n that is not a positive multiple of the 16-byte chunk (8 bf16 / 4 fp32 values: the kernels move whole chunks). */
 int svln_op_rmsnorm(svln_engine* h, const void* x, const void* g, void* y, int rows, int n, float eps);

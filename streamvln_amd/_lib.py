@@ -113,6 +113,10 @@ SIGNATURES = {
     "svln_batch_scores": (_I, [_P, _I, _PF, _I, _PI32]),
     "svln_generate_batch_scores": (_I, [_P, _I, _PF, _I, _PI32]),
     "svln_set_sampling": (_I, [_P, _I, _F, _U64]),
+    "svln_set_allowed_tokens": (_I, [_P, _PI64, _I]),
+    "svln_get_allowed_logprobs": (_I, [_P, _PF, _I, _PI32, _PI32]),
+    "svln_batch_allowed_logprobs": (_I, [_P, _I, _PF, _I, _PI32, _PI32]),
+    "svln_generate_batch_allowed_logprobs": (_I, [_P, _I, _PF, _I, _PI32, _PI32]),
     "svln_set_layer_taps": (_I, [_P, _I, _I]),
     "svln_get_layer_taps": (_I, [_P, _PF]),
     "svln_get_layer_probe": (_I, [_P, _I, _PF, _I64, _PI32, _PI32]),
@@ -159,6 +163,7 @@ SIGNATURES = {
     "svln_op_gemv_batched_argmax_sample": (_I, [_P, _P, _I, _P, _I, _P, _F, _I, _I, _I, _P, _P, _F, _F, _U64, _PI32, _PI32, _PI32, _PF]),
     "svln_op_gemm_argmax_sample": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _F, _U64, _PI32, _PI32, _PI32, _PF]),
     "svln_op_gumbel": (_I, [_P, _U64, _I, _I, _I, _I, _PF]),
+    "svln_op_subset_argmax": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _PI64, _I, _P, _P, _F, _F, _U64, _PI32, _PI32, _PI32, _PF, _PF, _PF]),
     "svln_op_rmsnorm": (_I, [_P, _P, _P, _P, _I, _I, _F]),
     "svln_op_layernorm": (_I, [_P, _P, _P, _P, _P, _I, _I, _F]),
     "svln_op_rmsnorm_tap": (_I, [_P, _P, _P, _P, _I, _I, _F, _I, _P, _I, _I]),

@@ -84,6 +84,9 @@ class StreamingAgent:
         # the joint log-probability of the turn; None when the model provides no scores
         self.last_token_logprobs = None
         self.last_turn_logprob = None
+        # the model's distribution over the allowed ids for every id of the last model turn (model.set_allowed_tokens with
+        # set_token_scores): [1, n_new, n_allowed]; None otherwise
+        self.last_allowed_logprobs = None
         self.step_id = 0
         self.last_image = None
         self.model.reset_for_env(self.env_id)
@@ -137,6 +140,7 @@ class StreamingAgent:
         lp = out.get("token_logprobs") if isinstance(out, dict) else getattr(out, "token_logprobs", None)
         self.last_token_logprobs = lp
         self.last_turn_logprob = None if lp is None else float(lp.sum())
+        self.last_allowed_logprobs = out.get("allowed_logprobs") if isinstance(out, dict) else getattr(out, "allowed_logprobs", None)
         self.turn_log.append(dict(self._pending, out=out))
         actions = list(self.decode_actions(out.sequences))
         return actions if len(actions) else [0]               # streamvln_eval.py:340-341

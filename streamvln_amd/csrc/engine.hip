@@ -108,6 +108,12 @@ struct EngineBase {
     virtual void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp) = 0;
     virtual void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp) = 0;
     virtual void set_sampling(int enable, float temperature, uint64_t seed) = 0;
+    virtual void set_allowed_tokens(const int64_t* ids, int n) = 0;
+    virtual void get_allowed_logprobs(float* out, int cap, int32_t* n_tokens, int32_t* n_ids) = 0;
+    virtual void batch_allowed_logprobs(int slot, float* out, int cap, int32_t* n_tokens, int32_t* n_ids) = 0;
+    virtual void generate_batch_allowed_logprobs(int index, float* out, int cap, int32_t* n_tokens, int32_t* n_ids) = 0;
+    virtual void op_subset_argmax(GemvSubsetArgs a, const int64_t* ids, const OpSample& smp, int32_t* host_tokens, float* host_logprobs, float* host_y,
+                                  float* host_dist) = 0;
     virtual void op_gumbel(uint64_t seed, int stream, int draw, int n0, int count, float* out) = 0;
     virtual void sync() = 0;
     virtual void set_graph(int enable) = 0;
@@ -246,6 +252,18 @@ public:
         q.seed_lo = (uint32_t)smp_seed; q.seed_hi = (uint32_t)(smp_seed >> 32); q.part_raw = raw; q.part_max = mx; return q;
     }
     std::vector<std::vector<float>> gb_scores; bool gb_scores_valid = false;  // of the last svln_generate_batch, per listed env
+    // Opt-in allowed-token decode (svln_set_allowed_tokens; HF's prefix_allowed_tokens_fn with a constant set): while a list is set every
+    // lm_head product of the engine -- head(), argmax_rows() on lm_head, the MXFP4 branch of head_batched() -- is the subset product
+    // (gemv_subset.hip) on the engine-dtype lm_head, whichever weight-format switch is on: n <= 256 rows gain nothing from an e4m3 or
+    // MXFP4 copy, and one format makes the head the same function on every path.  One arg-max partial per listed id; the merge kernels
+    // run unchanged on allow_n partials.  While svln_set_token_scores is on too, subset_logprobs_kernel writes the whole normalised row
+    // of every emitted token: d_alp[count][allow_n] beside d_scores, d_alp_b[tok0 + b][allow_n] beside d_score_b.
+    static constexpr int ALLOW_MAX = 256;
+    bool allow_on = false; int allow_n = 0; std::vector<int> allow_ids;
+    int *d_allow = nullptr, *d_op_allow = nullptr;   // the engine's list / the list of svln_op_subset_argmax, ALLOW_MAX ints each
+    float *d_alp = nullptr, *h_alp = nullptr, *d_alp_b = nullptr, *h_alp_b = nullptr;
+    std::vector<float> last_alp; int last_alp_n = 0; bool last_alp_valid = false;           // of the last single-env turn
+    std::vector<std::vector<float>> gb_alp; int gb_alp_n = 0; bool gb_alp_valid = false;    // of the last svln_generate_batch
 
     struct Env {
         T* embeds = nullptr; int n_embeds = 0; int kv_len = 0;
@@ -503,6 +521,8 @@ public:
         for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ph_ev[i]);
         (void)hipHostFree(h_ctl); (void)hipHostFree(h_out_ids); (void)hipHostFree(h_scores); (void)hipHostFree(h_score_b);
         if (h_smp) (void)hipHostFree(h_smp);
+        if (h_alp) (void)hipHostFree(h_alp);
+        if (h_alp_b) (void)hipHostFree(h_alp_b);
         if (h_giveup) (void)hipHostFree(h_giveup);
         if (h_hash) (void)hipHostFree(h_hash);
         for (void* p : allocs) (void)hipFree(p);
@@ -1093,6 +1113,12 @@ public:
     // and every launch is guarded by the done flag.
     // With `gen` the tap row is GenCtl.count on the device (= tap_row on the host: tokens emitted so far), so the three launches are the
     // same for every decode step and sit at the end of the captured step graph.
+    // the subset product of the engine's own list on its lm_head for B rows (svln_set_allowed_tokens); the epilogue follows the switches
+    GemvSubsetArgs subset_args(const void* xrows, int ldx, int B, float* pv, int* pi, float* psum) {
+        GemvSubsetArgs a; a.ids = d_allow; a.n = allow_n; a.W = lm_head; a.ldw = H; a.x = xrows; a.ldx = ldx; a.V = V; a.K = H; a.B = B;
+        a.epi = smp_on ? EPI_SAMPLE : scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX;
+        a.part_val = pv; a.part_idx = pi; a.part_sum = psum; return a;
+    }
     void head(const T* xrow, int tap_row, bool gen) {
         T* tap = hid_tap + (size_t)(tap_row < HID_TAP_ROWS ? tap_row : HID_TAP_ROWS - 1) * H;
         const int* skip = gen ? &d_ctl->done : nullptr;
@@ -1111,9 +1137,21 @@ public:
         // svln_set_sampling: stream and draw come from GenCtl on the device (the turn wrote them), so a captured step stays valid
         if (smp_on) a.smp = smp_args(&d_ctl->stream, &d_ctl->draw0, &d_ctl->count, part_raw, part_max);
         const float *pr = smp_on ? part_raw : nullptr, *pm = smp_on ? part_max : nullptr;
-        launch_gemv<T>(st, a);
-        if (gen) launch_argmax_step(st, part_val, part_idx, gemv_grid(V), d_token, d_top2, d_ctl, d_eos, d_out_ids, pen ? pen_flags : nullptr, ps, d_scores, pr, pm);
-        else launch_argmax_final(st, part_val, part_idx, gemv_grid(V), d_token, d_top2, ps, d_scores, pr, pm);
+        int n_part = gemv_grid(V);
+        if (allow_on) {
+            // svln_set_allowed_tokens: the subset product on the engine-dtype lm_head, one partial per listed id; with the scores on, the
+            // normalised row goes to d_alp[count] before the step kernel advances the count
+            GemvSubsetArgs sa = subset_args(tap, H, 1, part_val, part_idx, part_sum);
+            sa.skip = skip; sa.smp = a.smp;
+            if (pen) { sa.pen_flags = pen_flags; sa.pen = rep_penalty; }
+            launch_gemv_subset<T>(st, sa);
+            if (scores_on) launch_subset_logprobs(st, smp_on ? part_max : part_val, allow_n, 1, d_alp, gen ? &d_ctl->count : nullptr, skip);
+            n_part = allow_n;
+        } else {
+            launch_gemv<T>(st, a);
+        }
+        if (gen) launch_argmax_step(st, part_val, part_idx, n_part, d_token, d_top2, d_ctl, d_eos, d_out_ids, pen ? pen_flags : nullptr, ps, d_scores, pr, pm);
+        else launch_argmax_final(st, part_val, part_idx, n_part, d_token, d_top2, ps, d_scores, pr, pm);
     }
     // One decode step as a fixed op sequence; every run-time scalar is read from device memory (d_ctl,
     // d_token) so any sub-range [lo, hi) of the sequence can be captured once and graph-replayed.
@@ -1300,6 +1338,16 @@ public:
         const float* ps = scores_on || smp_on ? part_sum_b : nullptr;
         const float *pr = smp_on ? part_raw_b : nullptr, *pm = smp_on ? part_max_b : nullptr;
         const SampleArgs sa = smp_args(d_smp + tok0, d_smp + SMP_ROWS + tok0, nullptr, part_raw_b, part_max_b);
+        if (allow_on && W == (const void*)lm_head) {
+            // svln_set_allowed_tokens: the subset product whatever the row count; row b's normalised row -> d_alp_b[tok0 + b]
+            GemvSubsetArgs su = subset_args(xrows, ldx, B, part_val_b, part_idx_b, part_sum_b);
+            if (smp_on) su.smp = sa;
+            if (pen) { su.pen_flags = pen_flags_b; su.pen_rows = d_pen_rows; su.pen = rep_penalty; }
+            launch_gemv_subset<T>(st, su);
+            if (scores_on) launch_subset_logprobs(st, smp_on ? part_max_b : part_val_b, allow_n, B, d_alp_b + (size_t)tok0 * allow_n);
+            launch_argmax_final_batched(st, part_val_b, part_idx_b, allow_n, B, d_tok_b + tok0, ps, d_score_b + tok0, nullptr, pr, pm);
+            return;
+        }
         if (B >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048) {
             GemmArgs a = gemm_args(xrows, ldx, W, ldw, nullptr, 0, nullptr, nullptr, 0, 0, B, N, K, EPI_ARGMAX);
             a.part_val = part_val_b; a.part_idx = part_idx_b;
@@ -1319,7 +1367,7 @@ public:
     }
     void head_batched(const T* rows, int B, bool pen = false) {
         launch_rmsnorm<T>(st, rows, final_norm, xn, B, H, c.rms_eps);
-        if (mx4b_on) {
+        if (mx4b_on && !allow_on) {      // (an allowed list reads the engine-dtype lm_head on every path)
             GemvMx4BatchArgs hb = gemvb4_args(lm_head4, H, xn, H, nullptr, nullptr, 0, nullptr, 0, V, H, EPI_ARGMAX, B);
             if (pen) { hb.pen_flags = pen_flags_b; hb.pen_rows = d_pen_rows; hb.pen = rep_penalty; }
             launch_gemv_mx4b(st, hb);
@@ -1556,6 +1604,98 @@ public:
         for (int k = 0; k < m && k < cap; ++k) out[k] = gb_scores[index][k];
         *n = m;
     }
+    // ---- svln_set_allowed_tokens
+    void ensure_allow_buffers() {
+        if (d_allow) return;
+        d_allow = dalloc<int>(ALLOW_MAX, true); d_op_allow = dalloc<int>(ALLOW_MAX, true);
+        const size_t rows = (size_t)c.max_positions + 8, rows_b = HEAD_ROWS + MAXB;
+        d_alp = dalloc<float>(rows * ALLOW_MAX, true); d_alp_b = dalloc<float>(rows_b * ALLOW_MAX, true);
+        HIP_CHECK(hipHostMalloc((void**)&h_alp, rows * ALLOW_MAX * sizeof(float)));
+        HIP_CHECK(hipHostMalloc((void**)&h_alp_b, rows_b * ALLOW_MAX * sizeof(float)));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    // a list is 1 .. 256 strictly ascending ids of [0, vocab)
+    static void check_allowed_list(const std::string& who, const int64_t* ids, int n, int vocab) {
+        REQUIRE(n >= 1 && n <= ALLOW_MAX, who + ": the list holds 1 .. 256 ids");
+        REQUIRE(ids, who + ": null id list");
+        for (int k = 0; k < n; ++k) {
+            REQUIRE(ids[k] >= 0 && ids[k] < vocab, who + ": id " + std::to_string((long long)ids[k]) + " is outside the vocabulary");
+            REQUIRE(k == 0 || ids[k] > ids[k - 1], who + ": the ids must be strictly ascending (sorted, no duplicates)");
+        }
+    }
+    // Every refusal comes before any launch or state change.  The switch needs no refusal of its own against the other switches: only the
+    // lm_head product is swapped, the merge kernels, the verify rule, rides, penalty, sampling and scores see partials as before.
+    void set_allowed_tokens(const int64_t* ids, int n) override {
+        REQUIRE(n >= 0, "svln_set_allowed_tokens: n must be >= 0 (0 = off)");
+        REQUIRE(n <= ALLOW_MAX, "svln_set_allowed_tokens: at most 256 ids");
+        REQUIRE(n == 0 || ids, "svln_set_allowed_tokens: null id list with n > 0");
+        if (n > 0) check_allowed_list("svln_set_allowed_tokens", ids, n, V);
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_allowed_tokens cannot change while scheduler turns are in flight");
+        std::vector<int> want(n);
+        for (int k = 0; k < n; ++k) want[k] = (int)ids[k];
+        if (want == allow_ids) return;         // the current list (or off while off): nothing changes
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (n > 0) {
+            ensure_allow_buffers();
+            HIP_CHECK(hipMemcpy(d_allow, want.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+        }
+        drop_graphs();           // the captured lm_head launches hold the list length and the kernel choice
+        allow_ids.swap(want); allow_n = n; allow_on = n > 0;
+    }
+    static void alp_out(const std::vector<float>& v, int n_ids, float* out, int cap, int32_t* n_tokens, int32_t* n_ids_out) {
+        const size_t m = v.size();
+        for (size_t k = 0; k < m && k < (size_t)cap; ++k) out[k] = v[k];
+        *n_tokens = n_ids > 0 ? (int32_t)(m / (size_t)n_ids) : 0; *n_ids_out = n_ids;
+    }
+    void get_allowed_logprobs(float* out, int cap, int32_t* n_tokens, int32_t* n_ids) override {
+        REQUIRE(last_alp_valid, "svln_get_allowed_logprobs: token log-probabilities (svln_set_token_scores) or the allowed list (svln_set_allowed_tokens) were off for the last turn, or no turn has run");
+        alp_out(last_alp, last_alp_n, out, cap, n_tokens, n_ids);
+    }
+    void batch_allowed_logprobs(int slot, float* out, int cap, int32_t* n_tokens, int32_t* n_ids) override {
+        REQUIRE(slot >= 0 && slot < MAXB && jobs[slot].used && jobs[slot].finished, "no finished turn in this slot");
+        const Job& j = jobs[slot];
+        REQUIRE(j.alp_n > 0, "svln_batch_allowed_logprobs: token log-probabilities (svln_set_token_scores) or the allowed list (svln_set_allowed_tokens) were off for this turn");
+        alp_out(j.alp, j.alp_n, out, cap, n_tokens, n_ids);
+    }
+    void generate_batch_allowed_logprobs(int index, float* out, int cap, int32_t* n_tokens, int32_t* n_ids) override {
+        REQUIRE(gb_alp_valid, "svln_generate_batch_allowed_logprobs: token log-probabilities (svln_set_token_scores) or the allowed list (svln_set_allowed_tokens) were off for the last svln_generate_batch, or none has run");
+        REQUIRE(index >= 0 && index < (int)gb_alp.size(), "svln_generate_batch_allowed_logprobs: no such env index in the last batch");
+        alp_out(gb_alp[index], gb_alp_n, out, cap, n_tokens, n_ids);
+    }
+    // TEST-ONLY: one subset product (scored; sampled when smp.temperature > 0) on caller-given operands and list; the engine's own switches
+    // and list are not touched
+    void op_subset_argmax(GemvSubsetArgs a, const int64_t* ids, const OpSample& smp, int32_t* host_tokens, float* host_logprobs, float* host_y,
+                          float* host_dist) override {
+        constexpr int chunk = Elt<T>::PER_CHUNK;
+        REQUIRE(a.W && a.x && host_tokens && host_logprobs && host_y && host_dist, "svln_op_subset_argmax: null pointer");
+        REQUIRE(a.B >= 1 && a.B <= 32, "svln_op_subset_argmax: B must be 1 .. 32");
+        REQUIRE(a.V >= 1, "svln_op_subset_argmax: V must be >= 1");
+        REQUIRE(a.K >= chunk && a.K % chunk == 0, "svln_op_subset_argmax: K must be a positive multiple of the 16-byte chunk");
+        REQUIRE(a.ldw >= a.K && a.ldx >= a.K, "svln_op_subset_argmax: ldw and ldx must be >= K");
+        REQUIRE(a.ldw % chunk == 0 && a.ldx % chunk == 0 && ((size_t)a.W & 15) == 0 && ((size_t)a.x & 15) == 0,
+                "svln_op_subset_argmax: ldw, ldx multiples of the 16-byte chunk, W and x 16-byte aligned (aligned row loads)");
+        check_allowed_list("svln_op_subset_argmax", ids, a.n, a.V);
+        REQUIRE(!a.pen_flags || a.pen > 0.0f, "svln_op_subset_argmax: penalty flags need a factor > 0");
+        REQUIRE(std::isfinite(smp.temperature) && smp.temperature >= 0.0f, "svln_op_subset_argmax: the temperature must be finite and >= 0 (0 = greedy)");
+        const bool sampled = smp.temperature > 0.0f;
+        ensure_allow_buffers();
+        const int n = a.n, B = a.B;
+        a.epi = sampled ? EPI_SAMPLE : EPI_ARGMAX_LSE;
+        a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b; a.ids = d_op_allow; a.skip = nullptr;
+        if (sampled) a.smp = op_sample_args(smp, B, part_raw_b, part_max_b, true);
+        HIP_CHECK(hipStreamSynchronize(st));
+        std::vector<int> l(n);
+        for (int k = 0; k < n; ++k) l[k] = (int)ids[k];
+        HIP_CHECK(hipMemcpy(d_op_allow, l.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+        const float* ysrc = sampled ? part_max_b : part_val_b;
+        launch_gemv_subset<T>(st, a);
+        launch_subset_logprobs(st, ysrc, n, B, d_alp_b);
+        launch_argmax_final_batched(st, part_val_b, part_idx_b, n, B, d_tok_b, part_sum_b, d_score_b, nullptr, a.smp.part_raw, a.smp.part_max);
+        HIP_CHECK(hipMemcpyAsync(h_alp_b, d_alp_b, (size_t)B * n * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(host_y, ysrc, (size_t)B * n * sizeof(float), hipMemcpyDeviceToHost, st));
+        batched_scores_out(B, host_tokens, host_logprobs, "op_subset_argmax");
+        std::memcpy(host_dist, h_alp_b, (size_t)B * n * sizeof(float));
+    }
     void set_batch_draft(int on) override {
         const bool want = on != 0;
         if (want == bdraft_on) return;         // nothing changes
@@ -1632,6 +1772,7 @@ public:
         int env = -1, max_new = 0, count = 0, last_tok = -1;
         std::vector<int64_t> out, eos;
         std::vector<float> scores; bool scored = false;      // svln_set_token_scores: log-probability of every id of `out`
+        std::vector<float> alp; int alp_n = 0;               // with svln_set_allowed_tokens too: the normalised row [alp_n] of every id of `out`
         std::vector<int> draft;      // svln_set_batch_draft: the usable draft the submit consumed, kept until the job's prefill iteration
     };
     Job jobs[MAXB];
@@ -1705,6 +1846,7 @@ public:
         j.used = true; j.env = env; j.max_new = max_new < c.max_positions ? max_new : c.max_positions;
         j.eos.assign(eos, eos + n_eos);
         j.scored = scores_on;
+        j.alp_n = scores_on && allow_on ? allow_n : 0;
         n_generated_b[slot] = 0;
         // svln_set_batch_draft: the env's armed draft is consumed by the submit whether or not it helps (the rule of svln_generate); usable:
         // no repetition penalty, ids in the vocabulary (the first one outside ends the draft)
@@ -1886,6 +2028,7 @@ public:
         HIP_CHECK(hipEventRecord(ph_ev[3], st));
         HIP_CHECK(hipMemcpyAsync(h_tok_b + head0, d_tok_b, n_head * sizeof(int), hipMemcpyDeviceToHost, st));
         if (scores_on) HIP_CHECK(hipMemcpyAsync(h_score_b + head0, d_score_b, n_head * sizeof(float), hipMemcpyDeviceToHost, st));      // (never split: the switches exclude each other)
+        if (scores_on && allow_on) HIP_CHECK(hipMemcpyAsync(h_alp_b + (size_t)head0 * allow_n, d_alp_b, (size_t)n_head * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         LAUNCH_CHECK("batch_step");
         {
@@ -1916,6 +2059,7 @@ public:
                 REQUIRE(tok >= 0 && tok < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
                 j.out.push_back(tok);
                 if (j.scored) j.scores.push_back(h_score_b[hq + i]);
+                if (j.alp_n > 0) j.alp.insert(j.alp.end(), h_alp_b + (size_t)(hq + i) * j.alp_n, h_alp_b + (size_t)(hq + i + 1) * j.alp_n);
                 if (smp_on) env_draws[j.env] += 1;
                 j.count += 1;
                 ++emitted;
@@ -1966,7 +2110,7 @@ public:
         for (int s = 0; s < n_envs; ++s)
             for (int t = 0; t < s; ++t) REQUIRE(env_ids[t] != env_ids[s], "duplicate env in batch");
         std::vector<int> slots(n_envs);
-        gb_scores_valid = false;
+        gb_scores_valid = false; gb_alp_valid = false;
         try {
             for (int s = 0; s < n_envs; ++s) slots[s] = batch_submit(env_ids[s], max_new < cap ? max_new : cap, eos, n_eos);
             int32_t fin[MAXB], nf = 0;
@@ -1976,12 +2120,15 @@ public:
             throw;
         }
         gb_scores.assign(n_envs, std::vector<float>());
+        gb_alp.assign(n_envs, std::vector<float>());
         for (int s = 0; s < n_envs; ++s) {
             int32_t env = 0;
             if (scores_on) gb_scores[s] = jobs[slots[s]].scores;
+            if (scores_on && allow_on) gb_alp[s] = jobs[slots[s]].alp;
             batch_result(slots[s], &env, out + (size_t)s * cap, cap, &n_out[s]);
         }
         gb_scores_valid = scores_on;          // (only once every env's scores are in place)
+        gb_alp_n = allow_n; gb_alp_valid = scores_on && allow_on;
     }
     void get_hidden_batch(int slot, float* out, int max_rows, int32_t* n_rows) override {
         REQUIRE(slot >= 0 && slot < MAXB, "slot");
@@ -2004,7 +2151,7 @@ public:
     // enqueued past the end of the generation are no-ops (every kernel checks the done flag).
     void generate(int env, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, bool fixed) override {
         Env& e = env_at(env);
-        last_scores_valid = false;
+        last_scores_valid = false; last_alp_valid = false;
         const bool had_draft = disarm_draft(env);      // consumed by this call whether it helps, is ignored or the call fails
         REQUIRE(weights_missing() == 0, g_err);
         const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
@@ -2148,6 +2295,7 @@ public:
             HIP_CHECK(hipMemcpyAsync(h_ctl, d_ctl, sizeof(GenCtl), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipMemcpyAsync(h_out_ids, d_out_ids, (size_t)enq * sizeof(int), hipMemcpyDeviceToHost, st));
             if (scores_on) HIP_CHECK(hipMemcpyAsync(h_scores, d_scores, (size_t)enq * sizeof(float), hipMemcpyDeviceToHost, st));
+            if (scores_on && allow_on) HIP_CHECK(hipMemcpyAsync(h_alp, d_alp, (size_t)enq * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipMemcpyAsync(h_top2, d_top2, 2 * sizeof(float), hipMemcpyDeviceToHost, st));
             if (persistent_on) HIP_CHECK(hipMemcpyAsync(h_giveup, dl_giveup, sizeof(unsigned), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
@@ -2170,6 +2318,7 @@ public:
         }
         for (int k = 0; k < n; ++k) out[k] = h_out_ids[k];
         if (scores_on) { last_scores.assign(h_scores, h_scores + n); last_scores_valid = true; }      // (the draft modes are off: every id left the scored arg-max step)
+        if (scores_on && allow_on) { last_alp.assign(h_alp, h_alp + (size_t)n * allow_n); last_alp_n = allow_n; last_alp_valid = true; }
         e.kv_len = L + n - 1;             // EOS (or the last token) is appended to the ids but never fed
         {
             float t = 0.f;
@@ -3169,6 +3318,26 @@ int svln_op_gemm_argmax_sample(svln_engine* h, const void* A, int lda, const voi
     return op_gemm_argmax_any(h, A, lda, W, ldw, M, N, K, pen_flags, pen_rows, penalty, host_tokens, host_logprobs, &q);
 }
 int svln_set_sampling(svln_engine* h, int enable, float temperature, uint64_t seed) { API_BEGIN_H h->impl->set_sampling(enable, temperature, seed); API_END }
+int svln_set_allowed_tokens(svln_engine* h, const int64_t* ids, int n) { API_BEGIN_H h->impl->set_allowed_tokens(ids, n); API_END }
+int svln_get_allowed_logprobs(svln_engine* h, float* out, int cap_floats, int32_t* n_tokens, int32_t* n_ids) {
+    API_BEGIN_H REQUIRE(out && n_tokens && n_ids && cap_floats >= 0, "null output pointer"); h->impl->get_allowed_logprobs(out, cap_floats, n_tokens, n_ids); API_END
+}
+int svln_batch_allowed_logprobs(svln_engine* h, int slot, float* out, int cap_floats, int32_t* n_tokens, int32_t* n_ids) {
+    API_BEGIN_H REQUIRE(out && n_tokens && n_ids && cap_floats >= 0, "null output pointer"); h->impl->batch_allowed_logprobs(slot, out, cap_floats, n_tokens, n_ids); API_END
+}
+int svln_generate_batch_allowed_logprobs(svln_engine* h, int index, float* out, int cap_floats, int32_t* n_tokens, int32_t* n_ids) {
+    API_BEGIN_H REQUIRE(out && n_tokens && n_ids && cap_floats >= 0, "null output pointer"); h->impl->generate_batch_allowed_logprobs(index, out, cap_floats, n_tokens, n_ids); API_END
+}
+int svln_op_subset_argmax(svln_engine* h, const void* W, int ldw, const void* x, int ldx, int V, int K, int B, const int64_t* ids, int n,
+                          const void* pen_flags, const int32_t* pen_rows, float penalty, float temperature, uint64_t seed, const int32_t* streams,
+                          const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* host_y, float* host_dist) {
+    API_BEGIN_H
+    GemvSubsetArgs a; a.W = W; a.ldw = ldw; a.x = x; a.ldx = ldx; a.V = V; a.K = K; a.B = B; a.n = n;
+    a.pen_flags = (const uint8_t*)pen_flags; a.pen_rows = pen_rows; a.pen = penalty;
+    const OpSample q{temperature, seed, streams, draws};
+    h->impl->op_subset_argmax(a, ids, q, host_tokens, host_logprobs, host_y, host_dist);
+    API_END
+}
 int svln_op_gumbel(svln_engine* h, uint64_t seed, int32_t stream, int32_t draw, int32_t n0, int32_t count, float* host_out) {
     API_BEGIN_H h->impl->op_gumbel(seed, stream, draw, n0, count, host_out); API_END
 }

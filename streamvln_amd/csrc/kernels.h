@@ -182,6 +182,27 @@ struct GenCtl {
 void launch_argmax_step(hipStream_t s, const float* part_val, const int* part_idx, int n, int* out_token, float* out_top, GenCtl* ctl,
                         const int* eos, int* out_ids, uint8_t* pen_flags = nullptr, const float* part_sum = nullptr, float* scores = nullptr,
                         const float* part_raw = nullptr, const float* part_max = nullptr);
+// Allowed-token lm_head (svln_set_allowed_tokens; gemv_subset.hip): the product over the n <= 256 listed rows ids[0] < ... < ids[n - 1] of
+// W [V][ldw] for B <= 32 activation rows x [B][ldx], fp32 accumulate in an order that depends on K alone.  ONE arg-max partial per listed
+// id, row stride n: part_val[b][j] = the processed value (after the penalty; z under EPI_SAMPLE), part_idx[b][j] = ids[j], or 0x7FFFFFFF
+// (owns nothing) when the value is NaN or -inf, part_sum[b][j] = 1 (0 for -inf, NaN for NaN; EPI_ARGMAX_LSE / EPI_SAMPLE), and under
+// EPI_SAMPLE smp.part_max = smp.part_raw = y.  launch_argmax_step / launch_argmax_final / launch_argmax_final_batched reduce them with
+// n partials.  Penalty flags are indexed by the vocabulary id: pen_flags[(pen_rows ? pen_rows[b] : 0) * V + ids[j]].  EPI_SAMPLE: row b
+// uses smp.stream[b], smp.draw[b] (+ *smp.count), and the noise column is the vocabulary id.
+struct GemvSubsetArgs {
+    const int* ids = nullptr; int n = 0;          // device list
+    const void* W = nullptr; int ldw = 0;
+    const void* x = nullptr; int ldx = 0;
+    int V = 0, K = 0, B = 0, epi = EPI_ARGMAX;    // EPI_ARGMAX, EPI_ARGMAX_LSE or EPI_SAMPLE
+    float* part_val = nullptr; int* part_idx = nullptr; float* part_sum = nullptr;
+    const uint8_t* pen_flags = nullptr; const int* pen_rows = nullptr; float pen = 1.0f;
+    SampleArgs smp;
+    const int* skip = nullptr;                    // optional device flag: no-op when *skip != 0
+};
+template <typename T> void launch_gemv_subset(hipStream_t s, const GemvSubsetArgs& a);
+// out[row][j] = y_j - logsumexp_i y_i for the B partial rows src [B][n] (part_val under greedy decoding, part_max under sampling);
+// row = *row_dev when given (B = 1: GenCtl::count, launched before the step kernel advances it), else b.  out rows have stride n.
+void launch_subset_logprobs(hipStream_t s, const float* src, int n, int B, float* out, const int* row_dev = nullptr, const int* skip = nullptr);
 // TEST-ONLY: out[k] = gumbel_noise(seed, stream, draw, n0 + k) for k < count
 void launch_gumbel(hipStream_t s, uint32_t seed_lo, uint32_t seed_hi, int stream, int draw, int n0, int count, float* out);
 // Draft-verified greedy decode (svln_set_speculative; misc.hip).  launch_verify_feed builds the rows of the next verify pass from GenCtl,

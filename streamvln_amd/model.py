@@ -189,6 +189,7 @@ class StreamVLNForCausalLM:
         self._auto_draft = False                                   # set_auto_draft: guess that a turn repeats the env's previous one
         self._last_out: Dict[int, torch.Tensor] = {}
         self._token_scores = False                                 # set_token_scores: results carry token_logprobs
+        self.allowed_token_ids = None                              # set_allowed_tokens: the list in force (tuple), None when off
         self._sampling = None                                      # set_sampling: None (greedy) or (temperature, seed) the engine holds
         self.sampling_seed = 0                                     # seed of the noise of generate(do_sample=True) (see set_sampling)
         self._batch_draft = False                                  # set_batch_draft: the scheduler consumes drafts
@@ -525,6 +526,23 @@ class StreamVLNForCausalLM:
             raise RuntimeError(f"the engine holds {n.value} token scores for a turn of {n_new} ids")
         return torch.from_numpy(buf[:n_new].copy()).unsqueeze(0).to(device)
 
+    def _allowed(self, res, getter, *args):
+        """with set_token_scores and set_allowed_tokens both on: add `allowed_logprobs` [1, n_new, n_allowed] (fp32) and `allowed_token_ids`
+        [n_allowed] (int64) of a finished turn to its result, from the engine's allowed-logprob getter named `getter`"""
+        if not (self._token_scores and self.allowed_token_ids):
+            return res
+        getter = getattr(self._lib, getter)
+        n_new, n_ids = int(res.sequences.shape[1]), len(self.allowed_token_ids)
+        buf = np.empty(max(n_new * n_ids, 1), dtype=np.float32)
+        nt, ni = C.c_int32(), C.c_int32()
+        _check(getter(self._h, *args, buf.ctypes.data_as(C.POINTER(C.c_float)), int(buf.size), C.byref(nt), C.byref(ni)))
+        if nt.value != n_new or ni.value != n_ids:
+            raise RuntimeError(f"the engine holds {nt.value} x {ni.value} allowed log-probabilities for a turn of {n_new} ids over {n_ids} allowed ids")
+        dev = res.sequences.device
+        res["allowed_logprobs"] = torch.from_numpy(buf[: n_new * n_ids].reshape(1, n_new, n_ids).copy()).to(dev)
+        res["allowed_token_ids"] = torch.tensor(self.allowed_token_ids, dtype=torch.int64, device=dev)
+        return res
+
     @torch.no_grad()
     def generate(self, inputs=None, images=None, image_sizes=None, depths=None, poses=None, intrinsics=None, task_ids=None,
                  draft_ids=None, **kwargs):
@@ -571,7 +589,7 @@ class StreamVLNForCausalLM:
         res = GenerateOutput(sequences=seq, past_key_values=KVHandle(env_id, self._epoch[env_id], buf["kv"].value))
         if self._token_scores:
             res["token_logprobs"] = self._scores(self._lib.svln_get_token_scores, n_new=int(seq.shape[1]), device=seq.device)
-        return res
+        return self._allowed(res, "svln_get_allowed_logprobs")
 
     def _arm_batch_draft(self, env_id, draft):
         """set_batch_draft on: arm env_id's draft for the submit that follows -- explicit ids, or the env's previous output under
@@ -672,7 +690,8 @@ class StreamVLNForCausalLM:
         scores = [None] * len(parsed)
         if self._token_scores:
             scores = [self._scores(self._lib.svln_generate_batch_scores, k, n_new=int(n_out[k]), device="cpu") for k in range(len(parsed))]
-        return [self._batch_result(p[5], out[k, : n_out[k]], requests[k].get("inputs"), scores[k]) for k, p in enumerate(parsed)]
+        return [self._allowed(self._batch_result(p[5], out[k, : n_out[k]], requests[k].get("inputs"), scores[k]),
+                              "svln_generate_batch_allowed_logprobs", k) for k, p in enumerate(parsed)]
 
     # ---- iteration-level scheduler: envs whose turns fall due at different times (streamvln_dagger.py:232-313) ----
     @torch.no_grad()
@@ -732,9 +751,20 @@ class StreamVLNForCausalLM:
                 sbuf = np.empty(cap, dtype=np.float32)
                 _check(self._lib.svln_batch_scores(self._h, fin[k], sbuf.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(ns)))
                 scores = torch.from_numpy(sbuf[: ns.value].copy()).unsqueeze(0)
+            alp = None
+            if self._token_scores and self.allowed_token_ids:      # (read before svln_batch_result frees the slot)
+                abuf = np.empty(cap * len(self.allowed_token_ids), dtype=np.float32)
+                nt, ni = C.c_int32(), C.c_int32()
+                _check(self._lib.svln_batch_allowed_logprobs(self._h, fin[k], abuf.ctypes.data_as(C.POINTER(C.c_float)), int(abuf.size), C.byref(nt),
+                                                             C.byref(ni)))
+                alp = torch.from_numpy(abuf[: nt.value * ni.value].reshape(1, nt.value, ni.value).copy())
             _check(self._lib.svln_batch_result(self._h, fin[k], C.byref(env), out.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n)))
             env_id, inputs = self._tickets.pop(fin[k])
-            done.append((SimpleNamespace(env_id=env_id, slot=fin[k]), self._batch_result(env_id, out[: n.value], inputs, scores)))
+            res = self._batch_result(env_id, out[: n.value], inputs, scores)
+            if alp is not None:
+                res["allowed_logprobs"] = alp.to(res.sequences.device)
+                res["allowed_token_ids"] = torch.tensor(self.allowed_token_ids, dtype=torch.int64, device=res.sequences.device)
+            done.append((SimpleNamespace(env_id=env_id, slot=fin[k]), res))
         return done, running.value
 
     def cancel(self, ticket=None):
@@ -874,6 +904,30 @@ class StreamVLNForCausalLM:
         it is on), and while scheduler turns are in flight."""
         _check(self._lib.svln_set_token_scores(self._h, int(bool(enable))))
         self._token_scores = bool(enable)
+
+    def set_allowed_tokens(self, ids, add_eos: bool = True):
+        """Opt-in, default off (svln_set_allowed_tokens; HF's prefix_allowed_tokens_fn with a constant set, vLLM's allowed_token_ids): while a
+        list is set every turn chooses its ids among the listed ones only -- the lm_head product runs over those <= 256 weight rows
+        instead of the whole vocabulary, and the arg-max, the sample and `token_logprobs` are taken over the processed logits of the set
+        (HF's semantics when a logits processor puts -inf elsewhere).  `ids`: None or empty switches it off; otherwise the list is sorted,
+        de-duplicated and, with add_eos (the default), joined with the generation config's EOS ids that lie in the vocabulary -- a list
+        without an EOS id ends every turn at max_new_tokens.  The list in force is `self.allowed_token_ids` (a tuple; None when off).
+        With set_token_scores on as well, every result of generate / generate_batch / step_batch carries `allowed_logprobs`, fp32
+        [1, n_new, n_allowed] on the device of `sequences` -- log softmax over the allowed set for every emitted id -- and
+        `allowed_token_ids`, int64 [n_allowed], the columns.  Composes with every other switch; refused while scheduler turns are in
+        flight."""
+        want = sorted({int(i) for i in ids}) if ids is not None else []
+        if not want:
+            _check(self._lib.svln_set_allowed_tokens(self._h, None, 0))
+            self.allowed_token_ids = None
+            return
+        if add_eos:
+            eos = self.generation_config.eos_token_id
+            eos = eos if isinstance(eos, (list, tuple)) else [eos]
+            want = sorted(set(want) | {int(e) for e in eos if e is not None and 0 <= int(e) < self.cfg.vocab})
+        arr = np.asarray(want, dtype=np.int64)
+        _check(self._lib.svln_set_allowed_tokens(self._h, arr.ctypes.data_as(C.POINTER(C.c_int64)), int(arr.size)))
+        self.allowed_token_ids = tuple(want)
 
     def set_sampling(self, temperature: Optional[float] = 1.0, seed: int = 0):
         """Opt-in, default off (svln_set_sampling).  set_sampling(T, seed): every turn samples its ids from softmax(processed logits / T)
