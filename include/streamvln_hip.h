@@ -209,6 +209,46 @@ int svln_set_allowed_tokens(svln_engine* h, const int64_t* ids, int n);
 int svln_get_allowed_logprobs(svln_engine* h, float* host_out, int cap_floats, int32_t* n_tokens, int32_t* n_ids);
 int svln_batch_allowed_logprobs(svln_engine* h, int slot, float* host_out, int cap_floats, int32_t* n_tokens, int32_t* n_ids);
 int svln_generate_batch_allowed_logprobs(svln_engine* h, int index, float* host_out, int cap_floats, int32_t* n_tokens, int32_t* n_ids);
+/* Opt-in, no reference counterpart (HF: num_return_sequences under do_sample): a GROUP turn -- n_seq (2 .. 8) independently sampled
+ * continuations of ONE prefill of env's turn.  With L = n_embeds, limit = min(max_new_tokens, out_cap), q0 = L / 64 and B = the next power
+ * of two >= n_seq:
+ *   prefill   exactly svln_generate's (same launches, same K / V bits for positions < L);
+ *   token 0   the last prefill row replicated B times through the scheduler's batched lm_head; row g samples with
+ *             stream = env + g * max_envs and draw = the env's draw counter (stream 0 is the env's own: sequence 0 is what svln_generate
+ *             would have sampled wherever the two paths' logits agree; no stream collides with another env's);
+ *   fork      sequence 0 keeps the env's page table; sequence g >= 1 gets a table whose entries [0, q0) are the env's pages (shared, never
+ *             written: every write of the turn is at a position >= L) and whose n_tail = ceil((L + limit - 1) / 64) - q0 further entries
+ *             (0 when limit == 1) are fresh pages of the free pool; if L % 64 != 0 ONE launch (kv_page_copy_kernel) copies the env's partly
+ *             filled page q0 to the n_seq - 1 fresh q0 pages in every layer's K and V^T pool, else nothing is launched;
+ *   decode    up to limit - 1 iterations of the scheduler's pure batched decode step at B rows (the same launches or captured graph),
+ *             row g = {table g, position L + t, g's last token}, draws = counter + t + 1, one synchronisation each; the host applies the
+ *             stop rule per sequence (an EOS id, limit, a non-finite arg-max); a finished sequence's row and every pad row replay the first
+ *             live row (identical writes).
+ * The head and the products are whatever the batched step runs under the switches in force (svln_set_fp8_gemm, svln_set_allowed_tokens,
+ * ...): a group computes what svln_generate_batch would compute for n_seq envs holding this prompt.  out_ids [n_seq][out_cap], n_out [n_seq].
+ * Afterwards the env's draw counter has advanced by max_g n_out[g] (no (stream, draw) pair is ever used twice), its kv length is L and the
+ * group is PENDING on it: svln_group_select must say which continuation the env goes on with.  While a group is pending,
+ * svln_append_turn*, svln_generate*, svln_turn*, svln_batch_submit and svln_generate_batch on that env fail with a message that names
+ * svln_group_select; svln_reset_env / svln_kv_reset drop the group and free its pages; svln_set_sampling, svln_set_token_scores and
+ * svln_set_allowed_tokens fail, as they do while scheduler turns are in flight.
+ * Refused before any launch or state change: sampling off (greedy sequences would be identical); a repetition penalty != 1; scheduler
+ * turns in flight; a group pending on any env; n_seq outside 2 .. 8; nothing to prefill; L + limit - 1 > max_positions; a free pool that
+ * cannot hold the env's own missing pages plus (n_seq - 1) * n_tail.  An error after the fork returns every fork page to the pool, leaves
+ * no group pending and the env as after a failed svln_generate. */
+int svln_generate_group(svln_engine* h, int env, int n_seq, int max_new_tokens, const int64_t* eos_ids, int n_eos, int64_t* out_ids, int out_cap,
+                        int32_t* n_out);
+/* svln_turn's bookkeeping (encode, window / episode resets, splice), then the group turn, in one crossing */
+int svln_turn_group(svln_engine* h, const svln_turn_args* a, int n_seq, int64_t* out_ids, int out_cap, int32_t* n_out);
+/* The env goes on with sequence `index` of its pending group: for index >= 1 its table entries [q0, q0 + n_tail) become that sequence's
+ * private pages and its former pages at those entries go back to the free pool; every other fork's pages go back too.  The env's kv
+ * length becomes L + n_out[index] - 1 (-> *kv_len_out, may be null).  Refused: no group pending on env, index outside [0, n_seq). */
+int svln_group_select(svln_engine* h, int env, int index, int32_t* kv_len_out);
+/* Results of the pending group, valid until its select (or drop): the log-probability of every id of sequence `index` (refused when
+ * svln_set_token_scores was off for the turn); its rows over the allowed set, [n_rows][n_cols] (refused unless the scores and a list were
+ * on); the final-norm row of each of its first <= 8 tokens (a parity tap). */
+int svln_group_logprobs(svln_engine* h, int index, float* host_out, int cap, int32_t* n);
+int svln_group_dist(svln_engine* h, int index, float* host_out, int cap_rows, int32_t* n_rows, int32_t* n_cols);
+int svln_get_hidden_group(svln_engine* h, int index, float* host_out, int max_rows, int32_t* n_rows);
 /* prefill taps of svln_generate (single env): enable != 0 records the LAST row of the residual stream after every decoder layer of the
  * next prefills (svln_get_layer_taps: host_out [layers][hidden]); probe_layer >= 0 additionally records, for every row of the prefill,
  * the operands the products of that one layer actually saw (svln_get_layer_probe, which: 0 = x entering the layer, 1 = x leaving it,
@@ -553,6 +593,12 @@ int svln_op_verify_step(svln_engine* h, int rows, const int32_t* fed, const int3
  * the raw pools (position p = slot p % 64 of physical page p / 64).  The attention ops reset their envs on entry only, so this reads
  * what the last op wrote. */
 int svln_op_kv_read(svln_engine* h, int env, int start, int n, float* k_out, float* v_out);
+/* the same raw-pool read (env = -1 above) on the K / V^T pools of any layer */
+int svln_op_kv_pool_read(svln_engine* h, int layer, int start, int n, float* k_out, float* v_out);
+/* TEST-ONLY: one launch of kv_page_copy_kernel (the fork of svln_generate_group): physical page src_page is copied to the n_dst pages of the
+ * host list dst_pages in every layer's K and V^T pool.  Refused before any launch: a null list, n_dst outside 1 .. 7, a page outside the
+ * pool, a destination equal to the source or listed twice, a destination held by an env (or by a pending group). */
+int svln_op_kv_page_copy(svln_engine* h, int src_page, const int32_t* dst_pages, int n_dst);
 /* the prefill q|k|v product of one env's turn on layer 0 (env 0, positions P .. P + T - 1) as a prefill runs it: x = the normed input
  * rows [T][hidden] (device); roped q rows -> q_out [T][q_stride], roped k / v appended to env 0's pages; *fused = 1 when the product's
  * split-K reduce did the RoPE + append, 0 when the separate RoPE + append kernel did */

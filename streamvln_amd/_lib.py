@@ -117,6 +117,14 @@ SIGNATURES = {
     "svln_get_allowed_logprobs": (_I, [_P, _PF, _I, _PI32, _PI32]),
     "svln_batch_allowed_logprobs": (_I, [_P, _I, _PF, _I, _PI32, _PI32]),
     "svln_generate_batch_allowed_logprobs": (_I, [_P, _I, _PF, _I, _PI32, _PI32]),
+    "svln_generate_group": (_I, [_P, _I, _I, _I, _PI64, _I, _PI64, _I, _PI32]),
+    "svln_turn_group": (_I, [_P, C.POINTER(SvlnTurnArgs), _I, _PI64, _I, _PI32]),
+    "svln_group_select": (_I, [_P, _I, _I, _PI32]),
+    "svln_group_logprobs": (_I, [_P, _I, _PF, _I, _PI32]),
+    "svln_group_dist": (_I, [_P, _I, _PF, _I, _PI32, _PI32]),
+    "svln_get_hidden_group": (_I, [_P, _I, _PF, _I, _PI32]),
+    "svln_op_kv_page_copy": (_I, [_P, _I, _PI32, _I]),
+    "svln_op_kv_pool_read": (_I, [_P, _I, _I, _I, _PF, _PF]),
     "svln_set_layer_taps": (_I, [_P, _I, _I]),
     "svln_get_layer_taps": (_I, [_P, _PF]),
     "svln_get_layer_probe": (_I, [_P, _I, _PF, _I64, _PI32, _PI32]),

@@ -115,6 +115,14 @@ struct EngineBase {
     virtual void op_subset_argmax(GemvSubsetArgs a, const int64_t* ids, const OpSample& smp, int32_t* host_tokens, float* host_logprobs, float* host_y,
                                   float* host_dist) = 0;
     virtual void op_gumbel(uint64_t seed, int stream, int draw, int n0, int count, float* out) = 0;
+    virtual void generate_group(int env, int n_seq, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out) = 0;
+    virtual void turn_group(const svln_turn_args& a, int n_seq, int64_t* out, int cap, int32_t* n_out) = 0;
+    virtual void group_select(int env, int index, int32_t* kv_len) = 0;
+    virtual void group_logprobs(int index, float* out, int cap, int32_t* n) = 0;
+    virtual void group_dist(int index, float* out, int cap_rows, int32_t* n_rows, int32_t* n_cols) = 0;
+    virtual void get_hidden_group(int index, float* out, int max_rows, int32_t* n_rows) = 0;
+    virtual void op_kv_page_copy(int src_page, const int32_t* dst_pages, int n_dst) = 0;
+    virtual void op_kv_pool_read(int layer, int start, int n, float* k_out, float* v_out) = 0;
     virtual void sync() = 0;
     virtual void set_graph(int enable) = 0;
     virtual void set_decode_persistent(int enable) = 0;
@@ -265,6 +273,24 @@ public:
     std::vector<float> last_alp; int last_alp_n = 0; bool last_alp_valid = false;           // of the last single-env turn
     std::vector<std::vector<float>> gb_alp; int gb_alp_n = 0; bool gb_alp_valid = false;    // of the last svln_generate_batch
 
+    // Opt-in group sampling (svln_generate_group; HF's num_return_sequences): n_seq sampled continuations of one prefill.  Sequence 0 decodes
+    // on the env's own page table; sequence g >= 1 on fork_tab[g]: the env's pages below q0 = L / 64 (shared, never written: every write
+    // of the turn is at a position >= L) and private pages from q0 on (Group::tail[g]); the partly filled page q0 is copied by ONE launch
+    // of kv_page_copy_kernel over d_pool_tab (every layer's K and V^T pool base).  The group stays pending on its env until
+    // svln_group_select picks the continuation (or a reset drops it).
+    static constexpr int FORK_MAX_DST = MAXB - 1;
+    void** d_pool_tab = nullptr;                         // [2 * layers]: kpool, vpool per layer
+    int* fork_tab[MAXB] = {nullptr};                     // device page tables of sequences 1 .. 7 (allocated on first use)
+    int *d_fork_dst = nullptr, *h_fork_dst = nullptr;    // destination pages of the fork launch (device / pinned)
+    struct Group {
+        bool pending = false, scored = false;
+        int env = -1, n_seq = 0, L = 0, q0 = 0, n_tail = 0, alp_n = 0;
+        int n_out[MAXB] = {0};
+        std::vector<int> tail[MAXB];                     // private pages of sequence g >= 1: its table entries [q0, q0 + n_tail)
+        std::vector<float> scores[MAXB], alp[MAXB];
+    };
+    Group grp;
+
     struct Env {
         T* embeds = nullptr; int n_embeds = 0; int kv_len = 0;
         int* d_pages = nullptr; std::vector<int> pages; int n_pages = 0;
@@ -401,6 +427,14 @@ public:
             add_slot(P + "mlp.up_proj.weight", L.gu_w, H, I, H, RowMap{32, 2, 1});
             add_linear(P + "mlp.down_proj", L.down_w, nullptr, H, I);
         }
+        {   // base of every layer's K and V^T pool, for the one-launch page fork (kv_fork.hip)
+            std::vector<void*> tab;
+            for (const LLayer& L : ll) { tab.push_back(L.kpool); tab.push_back(L.vpool); }
+            d_pool_tab = dalloc<void*>(tab.size());
+            HIP_CHECK(hipMemcpy(d_pool_tab, tab.data(), tab.size() * sizeof(void*), hipMemcpyHostToDevice));
+            d_fork_dst = dalloc<int>(MAXB, true);
+            HIP_CHECK(hipHostMalloc((void**)&h_fork_dst, MAXB * sizeof(int)));
+        }
         final_norm = dalloc<T>(H); lm_head = dalloc<T>((size_t)V * H);
         add_slot("model.norm.weight", final_norm, H, 1, H);
         add_slot("lm_head.weight", lm_head, H, V, H);
@@ -521,6 +555,7 @@ public:
         for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ph_ev[i]);
         (void)hipHostFree(h_ctl); (void)hipHostFree(h_out_ids); (void)hipHostFree(h_scores); (void)hipHostFree(h_score_b);
         if (h_smp) (void)hipHostFree(h_smp);
+        if (h_fork_dst) (void)hipHostFree(h_fork_dst);
         if (h_alp) (void)hipHostFree(h_alp);
         if (h_alp_b) (void)hipHostFree(h_alp_b);
         if (h_giveup) (void)hipHostFree(h_giveup);
@@ -594,8 +629,23 @@ public:
     }
     // A reset drops the env's turn in the multi-env scheduler, if it has one (submitted, running or finished but not collected): its rows
     // and KV pages are gone, so the job must not reach another batch_step.
-    void reset_env(int env) override { Env& e = env_at(env); cancel_jobs_of(env); release_pages(e); e.n_embeds = 0; e.kv_len = 0; }
-    void kv_reset(int env) override { Env& e = env_at(env); cancel_jobs_of(env); release_pages(e); e.kv_len = 0; }
+    // ... and its pending group (svln_generate_group), whose fork pages go back to the pool
+    void reset_env(int env) override { Env& e = env_at(env); cancel_jobs_of(env); drop_group_of(env); release_pages(e); e.n_embeds = 0; e.kv_len = 0; }
+    void kv_reset(int env) override { Env& e = env_at(env); cancel_jobs_of(env); drop_group_of(env); release_pages(e); e.kv_len = 0; }
+    void drop_group() {
+        for (int g = 1; g < MAXB; ++g) {
+            for (int p : grp.tail[g]) free_pages.push_back(p);
+            grp.tail[g].clear();
+        }
+        grp.pending = false;
+    }
+    void drop_group_of(int env) { if (grp.pending && grp.env == env) drop_group(); }
+    void refuse_while_group_on(int env, const char* who) {
+        REQUIRE(!(grp.pending && grp.env == env), std::string(who) + ": a group turn is pending on this env; choose its continuation with svln_group_select first");
+    }
+    void refuse_while_group(const char* who) {
+        REQUIRE(!grp.pending, std::string(who) + " cannot change while a group turn is pending (svln_group_select)");
+    }
     void env_state(int env, int32_t* n_embeds, int32_t* kv_len) override { Env& e = env_at(env); *n_embeds = e.n_embeds; *kv_len = e.kv_len; }
     void ensure_pages(Env& e, int positions) {      // pages covering [0, positions)
         const int need = (positions + PAGE - 1) / PAGE;
@@ -859,6 +909,7 @@ public:
     // splice + greedy generation -- svln_encode_frames, svln_kv_reset / svln_reset_env, svln_append_turn, svln_generate in that order.
     void turn(const svln_turn_args& a, int64_t* out, int cap, int32_t* n_out, int32_t* kv_len) override {
         Env& e = env_at(a.env);
+        refuse_while_group_on(a.env, "svln_turn");
         try {
             REQUIRE(a.ids && a.n_ids >= 1 && out && n_out, "svln_turn: null / empty argument");
             encode_frames(a.pixels, a.n_frames, a.pixels_on_device);
@@ -936,6 +987,7 @@ public:
     hipEvent_t src_ev = nullptr; bool src_pending = false;      // h_src (pinned splice descriptor) is still being read by the last upload
     void append_turn(int env, const int64_t* ids, int n, int frame_base, int n_memory) override {
         Env& e = env_at(env);
+        refuse_while_group_on(env, "svln_append_turn");
         if (src_pending) { HIP_CHECK(hipEventSynchronize(src_ev)); src_pending = false; }
         REQUIRE(frame_base >= 0 && n_memory >= 0 && frame_base + n_memory <= n_feat_frames, "n_memory exceeds encoded frames");
         // rows of this turn, then the reference's per-turn truncation (new_input_embeds[:tokenizer_model_max_length], stream_video_vln.py:241-244),
@@ -1515,6 +1567,7 @@ public:
     void set_sampling(int enable, float temperature, uint64_t seed) override {
         const bool want = enable != 0;
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_sampling cannot change while scheduler turns are in flight");
+        refuse_while_group("svln_set_sampling");
         float inv_t = 1.0f;
         if (want) {
             REQUIRE(std::isfinite(temperature) && temperature > 0.0f, "svln_set_sampling: the temperature must be finite and > 0");
@@ -1572,6 +1625,7 @@ public:
     // tokens leave verify_step_kernel), the persistent decode layer and the batched MXFP4 weights (gemv_mx4b_kernel has no scored form).
     void set_token_scores(int enable) override {
         const bool want = enable != 0;
+        refuse_while_group("svln_set_token_scores");
         if (want == scores_on) return;         // nothing changes
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_token_scores cannot change while scheduler turns are in flight");
         if (want) {
@@ -1631,6 +1685,7 @@ public:
         REQUIRE(n == 0 || ids, "svln_set_allowed_tokens: null id list with n > 0");
         if (n > 0) check_allowed_list("svln_set_allowed_tokens", ids, n, V);
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_allowed_tokens cannot change while scheduler turns are in flight");
+        refuse_while_group("svln_set_allowed_tokens");
         std::vector<int> want(n);
         for (int k = 0; k < n; ++k) want[k] = (int)ids[k];
         if (want == allow_ids) return;         // the current list (or off while off): nothing changes
@@ -1832,6 +1887,7 @@ public:
     void set_turn_row_limit(int rows) override { REQUIRE(rows >= 0, "row limit must be >= 0 (0 = none)"); turn_row_limit = rows; }
     int batch_submit(int env, int max_new, const int64_t* eos, int n_eos) override {
         Env& e = env_at(env);
+        refuse_while_group_on(env, "svln_batch_submit");
         REQUIRE(weights_missing() == 0, g_err);
         REQUIRE(max_new >= 1, "max_new_tokens must be >= 1");
         REQUIRE(e.n_embeds - e.kv_len >= 1, "nothing to prefill for this env (append its turn first)");
@@ -1907,6 +1963,18 @@ public:
         }
         return nh;
     }
+    // the pure batched decode step for B rows (d_slots / d_tok_b / d_smp set): the launches, or their captured graph
+    void batched_step(int B, bool pen) {
+        if (use_graph) {
+            const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0) | (fp8_gemm_on && fp8_scaled_on ? 2048 : 0) | (scores_on ? 4096 : 0) | (smp_on ? 8192 : 0);
+            auto it = bgraphs.find(key);
+            if (it == bgraphs.end())      // (a failed capture leaves no entry behind)
+                it = bgraphs.emplace(key, capture_graph([&] { decode_ops_batched(B, pen); })).first;
+            HIP_CHECK(hipGraphLaunch(it->second, st));
+        } else {
+            decode_ops_batched(B, pen);
+        }
+    }
     int batch_step_run(int32_t* finished_slots, int32_t* n_finished) {
         std::vector<int> dec, pre;                      // job slots decoding / prefilling in this iteration
         for (int k = 0; k < MAXB; ++k)
@@ -1969,15 +2037,7 @@ public:
                 if (smp_on) upload_sample_rows(dec.data(), nd, B);
                 // gather + 28 layers + head for B decode rows -> d_tok_b, xn = final-norm rows.  With hipGraph replay on, the step of each
                 // (B, fp8, penalty) combination is captured once: every run-time value (page tables, positions, fed tokens) is in d_slots / d_tok_b.
-                if (use_graph) {
-                    const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0) | (fp8_gemm_on && fp8_scaled_on ? 2048 : 0) | (scores_on ? 4096 : 0) | (smp_on ? 8192 : 0);
-                    auto it = bgraphs.find(key);
-                    if (it == bgraphs.end())      // (a failed capture leaves no entry behind)
-                        it = bgraphs.emplace(key, capture_graph([&] { decode_ops_batched(B, pen); })).first;
-                    HIP_CHECK(hipGraphLaunch(it->second, st));
-                } else {
-                    decode_ops_batched(B, pen);
-                }
+                batched_step(B, pen);
             } else {
                 launch_gather_rows<T>(st, d_tok_b, embed, feats, x, nd, H);
             }
@@ -2109,6 +2169,7 @@ public:
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_generate_batch needs an idle scheduler (turns are in flight)");
         for (int s = 0; s < n_envs; ++s)
             for (int t = 0; t < s; ++t) REQUIRE(env_ids[t] != env_ids[s], "duplicate env in batch");
+        for (int s = 0; s < n_envs; ++s) refuse_while_group_on(env_ids[s], "svln_generate_batch");
         std::vector<int> slots(n_envs);
         gb_scores_valid = false; gb_alp_valid = false;
         try {
@@ -2151,6 +2212,7 @@ public:
     // enqueued past the end of the generation are no-ops (every kernel checks the done flag).
     void generate(int env, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, bool fixed) override {
         Env& e = env_at(env);
+        refuse_while_group_on(env, "svln_generate");
         last_scores_valid = false; last_alp_valid = false;
         const bool had_draft = disarm_draft(env);      // consumed by this call whether it helps, is ignored or the call fails
         REQUIRE(weights_missing() == 0, g_err);
@@ -2333,6 +2395,195 @@ public:
         top2_sampled = smp_on;
         if (smp_on) env_draws[env] += n;
         *n_out = n;
+    }
+
+    // ------------------------------------------------------------------------------- group sampling (svln_generate_group)
+    // the refusals of a group turn that need no state of the env (svln_turn_group checks them before it encodes a frame)
+    void group_refusals(int env, int n_seq) {
+        env_at(env);
+        REQUIRE(n_seq >= 2 && n_seq <= MAXB, "svln_generate_group: n_seq must be 2 .. 8");
+        REQUIRE(smp_on, "svln_generate_group: temperature sampling is off (svln_set_sampling): greedy sequences would be identical");
+        REQUIRE(rep_penalty == 1.0f, "svln_generate_group: a repetition penalty != 1 is set (svln_set_repetition_penalty); a group does not support it");
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_generate_group needs an idle scheduler (turns are in flight)");
+        REQUIRE(!grp.pending, "svln_generate_group: a group turn is pending on env " + std::to_string(grp.env) + "; choose its continuation with svln_group_select first");
+    }
+    std::vector<int> fork_host[MAXB];            // host copies of fork_tab (kept: an upload reads them after the call that wrote them)
+    void generate_group(int env, int n_seq, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out) override {
+        group_refusals(env, n_seq);
+        Env& e = envs[env];
+        REQUIRE(out && n_out, "svln_generate_group: null output pointer");
+        REQUIRE(weights_missing() == 0, g_err);
+        const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
+        REQUIRE(Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
+        REQUIRE(max_new >= 1 && cap >= 1, "max_new_tokens must be >= 1");
+        REQUIRE(n_eos >= 0 && (n_eos == 0 || eos), "svln_generate_group: null eos list");
+        const int limit = max_new < cap ? max_new : cap;                     // tokens each sequence may emit
+        REQUIRE((int64_t)L + limit - 1 <= c.max_positions, "svln_generate_group: n_embeds + min(max_new_tokens, out_cap) - 1 exceeds max_positions");
+        const int q0 = L / PAGE;
+        const int n_tail = limit == 1 ? 0 : (L + limit - 1 + PAGE - 1) / PAGE - q0;
+        const int env_need = std::max((limit == 1 ? (L + PAGE - 1) / PAGE : q0 + n_tail) - e.n_pages, 0);
+        REQUIRE((int64_t)free_pages.size() >= (int64_t)env_need + (int64_t)(n_seq - 1) * n_tail,
+                "svln_generate_group: the free KV pages cannot hold the env's own pages and (n_seq - 1) x the tail pages of the fork");
+        // ---- nothing was launched or changed up to here
+        disarm_draft(env);
+        last_scores_valid = false; last_alp_valid = false;
+        int B = 2; while (B < n_seq) B <<= 1;
+        for (int g = 1; g < n_seq; ++g)
+            if (!fork_tab[g]) { fork_tab[g] = dalloc<int>(pages_per_env, true); fork_host[g].assign(pages_per_env, 0); }
+        grp = Group();
+        grp.env = env; grp.n_seq = n_seq; grp.L = L; grp.q0 = q0; grp.n_tail = n_tail;
+        grp.scored = scores_on; grp.alp_n = scores_on && allow_on ? allow_n : 0;
+        std::vector<std::vector<int64_t>> ids(n_seq);
+        bool stopped[MAXB] = {false}; int last_tok[MAXB] = {0};
+        // the host's stop rule on head row `row` of sequence g: EOS id (appended, never fed), limit, a non-finite arg-max
+        auto accept = [&](int g, int row) {
+            const int tok = h_tok_b[row];
+            REQUIRE(tok >= 0 && tok < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+            ids[g].push_back(tok);
+            if (grp.scored) grp.scores[g].push_back(h_score_b[row]);
+            if (grp.alp_n > 0) grp.alp[g].insert(grp.alp[g].end(), h_alp_b + (size_t)row * grp.alp_n, h_alp_b + (size_t)(row + 1) * grp.alp_n);
+            last_tok[g] = tok;
+            bool stop = (int)ids[g].size() >= limit;
+            for (int k = 0; k < n_eos; ++k) stop |= eos[k] == tok;
+            stopped[g] = stop;
+        };
+        // the one synchronisation of a pass: ids (and scores) of its B head rows, then the phase timer
+        auto read_rows = [&](int phase) {
+            HIP_CHECK(hipEventRecord(ph_ev[3], st));
+            HIP_CHECK(hipMemcpyAsync(h_tok_b, d_tok_b, B * sizeof(int), hipMemcpyDeviceToHost, st));
+            if (scores_on) HIP_CHECK(hipMemcpyAsync(h_score_b, d_score_b, B * sizeof(float), hipMemcpyDeviceToHost, st));
+            if (scores_on && allow_on) HIP_CHECK(hipMemcpyAsync(h_alp_b, d_alp_b, (size_t)B * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            LAUNCH_CHECK("generate_group");
+            float t = 0.f;
+            HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[3])); ph_ms[phase] += t;
+            if (vision_pending) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
+        };
+        auto upload_streams = [&]() {
+            HIP_CHECK(hipMemcpyAsync(d_smp, h_smp, B * sizeof(int), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(d_smp + SMP_ROWS, h_smp + SMP_ROWS, B * sizeof(int), hipMemcpyHostToDevice, st));
+        };
+        try {
+            // prefill: svln_generate's, launch for launch
+            ensure_pages(e, L);
+            HIP_CHECK(hipEventRecord(ph_ev[2], st));
+            prefill(e, P, Tn);
+            e.kv_len = L;
+            // token 0: the last prefill row B times through the scheduler's head; row g draws from stream env + g * max_envs (pad rows replay row 0)
+            const T* last = x + (size_t)(Tn - 1) * H;
+            for (int k = 0; k < B; ++k)
+                HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)k * H, last, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
+            for (int k = 0; k < B; ++k) { h_smp[k] = env + (k < n_seq ? k : 0) * c.max_envs; h_smp[SMP_ROWS + k] = env_draws[env]; }
+            upload_streams();
+            head_batched(last_rows, B);
+            for (int g = 0; g < n_seq; ++g) tap_copy(xn + (size_t)g * H, 0, g);
+            // fork: the env's own tail pages, then per sequence g >= 1 a table = the env's pages below q0 + private pages from q0 on
+            if (limit > 1) ensure_pages(e, L + limit - 1);
+            for (int g = 1; g < n_seq && n_tail > 0; ++g) {
+                std::vector<int>& tab = fork_host[g];
+                for (int i = 0; i < q0; ++i) tab[i] = e.pages[i];
+                for (int i = 0; i < n_tail; ++i) {
+                    REQUIRE(!free_pages.empty(), "KV page pool exhausted");
+                    grp.tail[g].push_back(free_pages.back());
+                    free_pages.pop_back();
+                    tab[q0 + i] = grp.tail[g][i];
+                }
+                HIP_CHECK(hipMemcpyAsync(fork_tab[g], tab.data(), (size_t)(q0 + n_tail) * sizeof(int), hipMemcpyHostToDevice, st));
+            }
+            if (L % PAGE != 0 && n_tail > 0) {       // the partly filled page: one launch for every layer, both pools, all forks
+                for (int g = 1; g < n_seq; ++g) h_fork_dst[g - 1] = grp.tail[g][0];
+                HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)(n_seq - 1) * sizeof(int), hipMemcpyHostToDevice, st));
+                launch_kv_page_copy<T>(st, d_pool_tab, 2 * c.layers, e.pages[q0], d_fork_dst, n_seq - 1, (int64_t)nkv * PAGE * 128);
+            }
+            read_rows(1);
+            for (int g = 0; g < n_seq; ++g) accept(g, g);
+            // decode: the scheduler's pure batched step; a finished sequence's row and every pad row replay the first live row
+            for (int t = 0; t + 1 < limit; ++t) {
+                int first = -1;
+                for (int g = n_seq - 1; g >= 0; --g) if (!stopped[g]) first = g;
+                if (first < 0) break;
+                for (int k = 0; k < B; ++k) {
+                    const int g = k < n_seq && !stopped[k] ? k : first;
+                    h_slots[k].page_table = g == 0 ? e.d_pages : fork_tab[g]; h_slots[k].pos = L + t; h_slots[k].pad = 0;
+                    h_tok_b[k] = last_tok[g];
+                    h_smp[k] = env + g * c.max_envs; h_smp[SMP_ROWS + k] = env_draws[env] + t + 1;
+                }
+                HIP_CHECK(hipEventRecord(ph_ev[2], st));
+                HIP_CHECK(hipMemcpyAsync(d_slots, h_slots, B * sizeof(DecodeSlot), hipMemcpyHostToDevice, st));
+                HIP_CHECK(hipMemcpyAsync(d_tok_b, h_tok_b, B * sizeof(int), hipMemcpyHostToDevice, st));
+                upload_streams();
+                batched_step(B, false);
+                for (int g = 0; g < n_seq; ++g) if (!stopped[g]) tap_copy(xn + (size_t)g * H, t + 1, g);
+                read_rows(2);
+                for (int g = 0; g < n_seq; ++g) if (!stopped[g]) accept(g, g);
+            }
+        } catch (...) {
+            // every fork page goes back to the pool, no group is pending; the env is as after a failed svln_generate
+            (void)hipStreamSynchronize(st);
+            drop_group();
+            throw;
+        }
+        int longest = 0;
+        for (int g = 0; g < n_seq; ++g) {
+            const int n = (int)ids[g].size();
+            for (int k = 0; k < n; ++k) out[(size_t)g * cap + k] = ids[g][k];
+            n_out[g] = grp.n_out[g] = n;
+            longest = std::max(longest, n);
+        }
+        env_draws[env] += longest;        // every stream of the group has used draws [counter, counter + its length): none is used twice
+        e.kv_len = L;                     // until svln_group_select
+        n_generated = 0;                  // (the single-env tap rows were overwritten)
+        top2_sampled = true;
+        grp.pending = true;
+    }
+    void turn_group(const svln_turn_args& a, int n_seq, int64_t* out, int cap, int32_t* n_out) override {
+        group_refusals(a.env, n_seq);
+        REQUIRE(a.ids && a.n_ids >= 1 && out && n_out, "svln_turn_group: null / empty argument");
+        try {
+            encode_frames(a.pixels, a.n_frames, a.pixels_on_device);
+            if (a.new_window) kv_reset(a.env);
+            if (a.new_episode && envs[a.env].n_embeds != 0) reset_env(a.env);
+            append_turn(a.env, a.ids, a.n_ids, 0, a.n_memory);
+        } catch (...) {
+            disarm_draft(a.env);
+            throw;
+        }
+        generate_group(a.env, n_seq, a.max_new_tokens, a.eos_ids, a.n_eos, out, cap, n_out);
+    }
+    void group_select(int env, int index, int32_t* kv_len) override {
+        env_at(env);
+        REQUIRE(grp.pending && grp.env == env, "svln_group_select: no group turn is pending on this env");
+        REQUIRE(index >= 0 && index < grp.n_seq, "svln_group_select: index outside the group's sequences");
+        Env& e = envs[env];
+        if (index >= 1 && grp.n_tail > 0) {
+            // the env goes on with sequence `index`: its private tail becomes the env's, the env's former tail is freed with the other forks'
+            for (int i = 0; i < grp.n_tail; ++i) std::swap(e.pages[grp.q0 + i], grp.tail[index][i]);
+            HIP_CHECK(hipMemcpyAsync(e.d_pages + grp.q0, e.pages.data() + grp.q0, (size_t)grp.n_tail * sizeof(int), hipMemcpyHostToDevice, st));
+        }
+        drop_group();
+        e.kv_len = grp.L + grp.n_out[index] - 1;
+        if (kv_len) *kv_len = e.kv_len;
+    }
+    void group_logprobs(int index, float* out, int cap, int32_t* n) override {
+        REQUIRE(grp.pending && index >= 0 && index < grp.n_seq, "svln_group_logprobs: no pending group turn / no such sequence");
+        REQUIRE(grp.scored, "svln_group_logprobs: token log-probabilities were off for this turn (svln_set_token_scores)");
+        const int m = (int)grp.scores[index].size();
+        for (int k = 0; k < m && k < cap; ++k) out[k] = grp.scores[index][k];
+        *n = m;
+    }
+    void group_dist(int index, float* out, int cap_rows, int32_t* n_rows, int32_t* n_cols) override {
+        REQUIRE(grp.pending && index >= 0 && index < grp.n_seq, "svln_group_dist: no pending group turn / no such sequence");
+        REQUIRE(grp.alp_n > 0, "svln_group_dist: token log-probabilities (svln_set_token_scores) or the allowed list (svln_set_allowed_tokens) were off for this turn");
+        const size_t m = grp.alp[index].size(), lim = (size_t)cap_rows * grp.alp_n;
+        for (size_t k = 0; k < m && k < lim; ++k) out[k] = grp.alp[index][k];
+        *n_rows = (int32_t)(m / (size_t)grp.alp_n); *n_cols = grp.alp_n;
+    }
+    void get_hidden_group(int index, float* out, int max_rows, int32_t* n_rows) override {
+        REQUIRE(grp.pending && index >= 0 && index < grp.n_seq, "svln_get_hidden_group: no pending group turn / no such sequence");
+        int n = grp.n_out[index] < 8 ? grp.n_out[index] : 8;
+        if (n > max_rows) n = max_rows;
+        for (int t = 0; t < n; ++t) read_rows_f32(hid_tap + (size_t)(t * MAXB + index) * H, (size_t)H, out + (size_t)t * H);
+        *n_rows = n;
     }
 
     // ------------------------------------------------------------------------------- taps
@@ -2923,11 +3174,37 @@ public:
     }
     // roped K and V rows of positions [start, start + n) of env's layer-0 pages -> fp32 [n][nkv][128] each.  env = -1: the raw pools,
     // position p = slot p % 64 of physical page p / 64 (every page, whoever holds it)
-    void op_kv_read(int env, int start, int n, float* k_out, float* v_out) override {
+    void op_kv_read(int env, int start, int n, float* k_out, float* v_out) override { kv_read(ll[0], env, start, n, k_out, v_out); }
+    void op_kv_pool_read(int layer, int start, int n, float* k_out, float* v_out) override {
+        REQUIRE(layer >= 0 && layer < c.layers, "op_kv_pool_read: no such layer");
+        kv_read(ll[layer], -1, start, n, k_out, v_out);
+    }
+    // TEST-ONLY: the fork launch of svln_generate_group on caller-given pages; every refusal comes before the launch
+    void op_kv_page_copy(int src_page, const int32_t* dst_pages, int n_dst) override {
+        REQUIRE(dst_pages, "svln_op_kv_page_copy: null page list");
+        REQUIRE(n_dst >= 1 && n_dst <= FORK_MAX_DST, "svln_op_kv_page_copy: n_dst must be 1 .. 7");
+        REQUIRE(src_page >= 0 && src_page < pages_total, "svln_op_kv_page_copy: source page outside the pool");
+        for (int d = 0; d < n_dst; ++d) {
+            const int p = dst_pages[d];
+            REQUIRE(p >= 0 && p < pages_total, "svln_op_kv_page_copy: destination page outside the pool");
+            REQUIRE(p != src_page, "svln_op_kv_page_copy: a destination equals the source");
+            for (int q = 0; q < d; ++q) REQUIRE(dst_pages[q] != p, "svln_op_kv_page_copy: a destination is listed twice");
+            for (const Env& e : envs)
+                for (int i = 0; i < e.n_pages; ++i) REQUIRE(e.pages[i] != p, "svln_op_kv_page_copy: a destination is held by an env");
+            for (int g = 1; g < MAXB; ++g)
+                for (int t : grp.tail[g]) REQUIRE(t != p, "svln_op_kv_page_copy: a destination is held by a pending group");
+        }
+        sync();
+        for (int d = 0; d < n_dst; ++d) h_fork_dst[d] = dst_pages[d];
+        HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)n_dst * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_kv_page_copy<T>(st, d_pool_tab, 2 * c.layers, src_page, d_fork_dst, n_dst, (int64_t)nkv * PAGE * 128);
+        sync();
+        LAUNCH_CHECK("op_kv_page_copy");
+    }
+    void kv_read(const LLayer& L, int env, int start, int n, float* k_out, float* v_out) {
         REQUIRE(k_out && v_out, "null output pointer");
         const int limit = env < 0 ? pages_total * PAGE : env_at(env).n_pages * PAGE;
         REQUIRE(start >= 0 && n >= 0 && start + n <= limit, "op_kv_read: positions outside the env's pages");
-        const LLayer& L = ll[0];
         const size_t page_elems = (size_t)nkv * PAGE * 128;
         std::vector<T> kp(page_elems), vp(page_elems);
         sync();
@@ -3328,6 +3605,24 @@ int svln_batch_allowed_logprobs(svln_engine* h, int slot, float* out, int cap_fl
 int svln_generate_batch_allowed_logprobs(svln_engine* h, int index, float* out, int cap_floats, int32_t* n_tokens, int32_t* n_ids) {
     API_BEGIN_H REQUIRE(out && n_tokens && n_ids && cap_floats >= 0, "null output pointer"); h->impl->generate_batch_allowed_logprobs(index, out, cap_floats, n_tokens, n_ids); API_END
 }
+int svln_generate_group(svln_engine* h, int env, int n_seq, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out) {
+    API_BEGIN_H h->impl->generate_group(env, n_seq, max_new, eos, n_eos, out, cap, n_out); API_END
+}
+int svln_turn_group(svln_engine* h, const svln_turn_args* a, int n_seq, int64_t* out_ids, int out_cap, int32_t* n_out) {
+    API_BEGIN_H REQUIRE(a, "null argument"); h->impl->turn_group(*a, n_seq, out_ids, out_cap, n_out); API_END
+}
+int svln_group_select(svln_engine* h, int env, int index, int32_t* kv_len_out) { API_BEGIN_H h->impl->group_select(env, index, kv_len_out); API_END }
+int svln_group_logprobs(svln_engine* h, int index, float* out, int cap, int32_t* n) {
+    API_BEGIN_H REQUIRE(out && n && cap >= 0, "null output pointer"); h->impl->group_logprobs(index, out, cap, n); API_END
+}
+int svln_group_dist(svln_engine* h, int index, float* out, int cap_rows, int32_t* n_rows, int32_t* n_cols) {
+    API_BEGIN_H REQUIRE(out && n_rows && n_cols && cap_rows >= 0, "null output pointer"); h->impl->group_dist(index, out, cap_rows, n_rows, n_cols); API_END
+}
+int svln_get_hidden_group(svln_engine* h, int index, float* out, int max_rows, int32_t* n_rows) {
+    API_BEGIN_H REQUIRE(out && n_rows, "null output pointer"); h->impl->get_hidden_group(index, out, max_rows, n_rows); API_END
+}
+int svln_op_kv_page_copy(svln_engine* h, int src_page, const int32_t* dst_pages, int n_dst) { API_BEGIN_H h->impl->op_kv_page_copy(src_page, dst_pages, n_dst); API_END }
+int svln_op_kv_pool_read(svln_engine* h, int layer, int start, int n, float* k_out, float* v_out) { API_BEGIN_H h->impl->op_kv_pool_read(layer, start, n, k_out, v_out); API_END }
 int svln_op_subset_argmax(svln_engine* h, const void* W, int ldw, const void* x, int ldx, int V, int K, int B, const int64_t* ids, int n,
                           const void* pen_flags, const int32_t* pen_rows, float penalty, float temperature, uint64_t seed, const int32_t* streams,
                           const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* host_y, float* host_dist) {

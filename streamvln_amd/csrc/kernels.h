@@ -330,6 +330,13 @@ template <typename T> void launch_gather_rows(hipStream_t s, const int* src, con
 // ragged form: out[list[2 i]][:] = embed[list[2 i + 1]][:] for i < rows (list: device array of (destination row, token id) pairs)
 template <typename T> void launch_gather_rows_ragged(hipStream_t s, const int* list, const void* embed, void* out, int rows, int n);
 
+// Fork of a KV page (svln_generate_group; kv_fork.hip): in each of the n_pools pools of `pools` (device table of pool bases: every layer's
+// K pool and V^T pool) page src_page is copied to the n_dst pages of the device list dst_pages, in 16-byte chunks, each chunk loaded once
+// and stored n_dst times.  page_elems = elements of T per page of one pool.  The caller guarantees: every page inside the pools, the
+// destinations distinct and different from the source.
+template <typename T> void launch_kv_page_copy(hipStream_t s, void* const* pools, int n_pools, int src_page, const int* dst_pages, int n_dst,
+                                               int64_t page_elems);
+
 // weights: synthesize (see weights.py) or convert canonical rows into packed rows
 // dst row = (r / blk) * blk * nint + phase * blk + r % blk ; cols copied to [0, cols), dst_ld >= cols
 struct RowMap { int blk, nint, phase; };

@@ -193,6 +193,7 @@ class StreamVLNForCausalLM:
         self._sampling = None                                      # set_sampling: None (greedy) or (temperature, seed) the engine holds
         self.sampling_seed = 0                                     # seed of the noise of generate(do_sample=True) (see set_sampling)
         self._batch_draft = False                                  # set_batch_draft: the scheduler consumes drafts
+        self._group_pending: Dict[int, int] = {}                   # env_id -> sequences of its group turn awaiting select_sequence
         self.reset(max_envs)
 
     # ---- construction -------------------------------------------------------------------------
@@ -408,6 +409,7 @@ class StreamVLNForCausalLM:
         self._epoch = [0] * env_num
         self._slots: Dict[int, int] = {}
         self._last_out = {}                                        # auto-draft: the previous turn's ids per env_id
+        self._group_pending = {}                                   # (svln_reset_env below drops a pending group and frees its pages)
         _check(self._lib.svln_batch_cancel(self._h, -1))           # turns still in the scheduler belong to the old state
         self._tickets.clear()
         for i in range(self.max_envs):
@@ -430,6 +432,7 @@ class StreamVLNForCausalLM:
         self.curr_t[env_idx] = 0
         self._epoch[env_idx] += 1
         self._last_out.pop(env_idx, None)
+        self._group_pending.pop(env_idx, None)                     # (svln_reset_env drops the env's pending group)
         if env_idx in self._slots:
             _check(self._lib.svln_reset_env(self._h, self._slots[env_idx]))       # (drops the env's scheduler turn, if any)
         for slot in [k for k, v in self._tickets.items() if v[0] == env_idx]:
@@ -464,6 +467,9 @@ class StreamVLNForCausalLM:
             raise NotImplementedError("text-only turns are not part of the streaming path")
         if env_id is None or not (0 <= env_id < len(self.curr_t)):
             raise IndexError(f"env_id {env_id} out of range")
+        if env_id in self._group_pending:
+            raise RuntimeError(f"env_id {env_id}: a group turn (num_return_sequences={self._group_pending[env_id]}) is pending; call "
+                               f"select_sequence(index, env_id={env_id}) before the env's next turn")
         ids = torch.as_tensor(inputs).reshape(-1).to("cpu", torch.int64)
         if ids.numel() == 1:
             raise NotImplementedError("single-token `inputs` bypasses the multimodal path in the reference "
@@ -550,11 +556,16 @@ class StreamVLNForCausalLM:
         splice, prefill + greedy decode).  draft_ids (optional, set_speculative / set_prefill_draft): a guess of this turn's whole id sequence; with
         set_auto_draft(True) and no explicit draft, the env's previous turn output is the guess.
         While set_token_scores is on the result also carries `token_logprobs`, fp32 [1, n_new] aligned with `sequences` (see there).  HF's
-        `output_scores` / `output_logits` stay ignored: a [n_new, vocab] tensor is exactly what this engine exists not to build."""
+        `output_scores` / `output_logits` stay ignored: a [n_new, vocab] tensor is exactly what this engine exists not to build.
+        do_sample=True with num_return_sequences=G, 2 <= G <= 8: a group turn (see _group_result for the result, select_sequence for what
+        must follow); absent or 1: this path, launch for launch; a greedy call leaves the key unread."""
         draft = draft_ids
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
+        n_seq = self._num_return_sequences(kwargs)
         self._sync_call_config()
         self._sync_sampling(kwargs)
+        if n_seq > 1:
+            return self._generate_group(n_seq, inputs, ids, pix, V, n_memory, env_id, past, max_new, eos)
         # the reference's bookkeeping that needs no engine call: the KV handle must be this env's current one; curr_t counts the turns
         if past is not None and (not isinstance(past, KVHandle) or past.env_id != env_id or past.epoch != self._epoch[env_id]):
             raise ValueError("past_key_values does not belong to this env's current window")
@@ -590,6 +601,111 @@ class StreamVLNForCausalLM:
         if self._token_scores:
             res["token_logprobs"] = self._scores(self._lib.svln_get_token_scores, n_new=int(seq.shape[1]), device=seq.device)
         return self._allowed(res, "svln_get_allowed_logprobs")
+
+    # ---- group sampling: several sampled continuations of one prefill (svln_turn_group) ----------------
+    @staticmethod
+    def _num_return_sequences(kwargs) -> int:
+        """HF's `num_return_sequences` of a generate call: read under do_sample=True only (a greedy call leaves the key unread, as
+        before); 1 or absent = the plain turn; 2 .. 8 = a group turn; anything else raises."""
+        if not kwargs.get("do_sample", False):
+            return 1
+        g = kwargs.get("num_return_sequences")
+        g = 1 if g is None else int(g)
+        if not (1 <= g <= 8):
+            raise ValueError(f"num_return_sequences={g}: a group turn returns 1 .. 8 sequences")
+        return g
+
+    @staticmethod
+    def _reject_group_request(kwargs, who):
+        g = kwargs.get("num_return_sequences")
+        if g is not None and int(g) > 1:
+            raise NotImplementedError(f"num_return_sequences={g!r} in a {who} request: group turns run through generate() only")
+
+    def _generate_group(self, n_seq, inputs, ids, pix, V, n_memory, env_id, past, max_new, eos):
+        """generate(do_sample=True, num_return_sequences=G): ONE vision pass, ONE prefill, one batched decode phase for G sequences.
+        The fork reserves the pages of every sequence up front, so the engine refuses a call whose n_embeds + max_new_tokens - 1 exceeds
+        max_positions: pass the max_new_tokens the turn really needs (the default of 10000 never fits).  draft_ids are not used."""
+        if past is not None and (not isinstance(past, KVHandle) or past.env_id != env_id or past.epoch != self._epoch[env_id]):
+            raise ValueError("past_key_values does not belong to this env's current window")
+        slot = self._slot(env_id)
+        on_dev = int(pix.is_cuda)
+        ids_np = np.ascontiguousarray(ids.numpy())
+        eos_np = np.asarray(eos, dtype=np.int64)
+        cap = min(max_new, self.cfg.max_positions)
+        out = np.zeros((n_seq, cap), dtype=np.int64)
+        n_out = np.zeros(n_seq, dtype=np.int32)
+        a = _lib.SvlnTurnArgs()
+        a.pixels, a.n_frames, a.pixels_on_device, a.env = pix.data_ptr(), V, on_dev, slot
+        a.ids, a.n_ids, a.n_memory = ids_np.ctypes.data, ids_np.size, n_memory
+        a.new_window, a.new_episode, a.max_new_tokens = int(past is None), int(self.curr_t[env_id] == 0), max_new
+        a.eos_ids, a.n_eos = eos_np.ctypes.data, eos_np.size
+        if on_dev:
+            self._order_engine_after(pix)
+        rc = self._lib.svln_turn_group(self._h, C.byref(a), n_seq, out.ctypes.data_as(C.POINTER(C.c_int64)), cap,
+                                       n_out.ctypes.data_as(C.POINTER(C.c_int32)))
+        if on_dev:
+            self._order_torch_after(pix)
+        _check(rc)
+        self.curr_t[env_id] += 1
+        self._group_pending[env_id] = n_seq
+        dev = inputs.device if isinstance(inputs, torch.Tensor) else "cpu"
+        return self._group_result(out, n_out, eos, dev)
+
+    def _group_result(self, out, n_out, eos, device="cpu"):
+        """the GenerateOutput of a group turn from the engine's rows: `sequences` int64 [G, n_max] padded with
+        generation_config.pad_token_id (else the first EOS id, else 0), `sequence_lengths` int64 [G], `past_key_values` None (the env has
+        no cache length until select_sequence); with set_token_scores `token_logprobs` fp32 [G, n_max] padded with 0, so that a row sum is
+        the sequence's joint log-probability; with set_allowed_tokens too `allowed_logprobs` fp32 [G, n_max, n_allowed] (padded with 0)
+        and `allowed_token_ids`"""
+        G, lens = int(out.shape[0]), [int(v) for v in n_out]
+        n_max = max(lens)
+        pad = getattr(self.generation_config, "pad_token_id", None)
+        if pad is None:
+            pad = eos[0] if len(eos) else 0
+        seq = np.full((G, n_max), int(pad), dtype=np.int64)
+        for g in range(G):
+            seq[g, : lens[g]] = out[g, : lens[g]]
+        res = GenerateOutput(sequences=torch.from_numpy(seq).to(device), sequence_lengths=torch.tensor(lens, dtype=torch.int64, device=device),
+                             past_key_values=None)
+        if self._token_scores:
+            lp = np.zeros((G, n_max), dtype=np.float32)
+            buf, n = np.empty(max(n_max, 1), dtype=np.float32), C.c_int32()
+            for g in range(G):
+                _check(self._lib.svln_group_logprobs(self._h, g, buf.ctypes.data_as(C.POINTER(C.c_float)), int(buf.size), C.byref(n)))
+                if n.value != lens[g]:
+                    raise RuntimeError(f"the engine holds {n.value} token scores for a sequence of {lens[g]} ids")
+                lp[g, : lens[g]] = buf[: lens[g]]
+            res["token_logprobs"] = torch.from_numpy(lp).to(device)
+        if self._token_scores and self.allowed_token_ids:
+            n_ids = len(self.allowed_token_ids)
+            alp = np.zeros((G, n_max, n_ids), dtype=np.float32)
+            buf, nr, nc = np.empty(max(n_max, 1) * n_ids, dtype=np.float32), C.c_int32(), C.c_int32()
+            for g in range(G):
+                _check(self._lib.svln_group_dist(self._h, g, buf.ctypes.data_as(C.POINTER(C.c_float)), max(n_max, 1), C.byref(nr), C.byref(nc)))
+                if nr.value != lens[g] or nc.value != n_ids:
+                    raise RuntimeError(f"the engine holds {nr.value} x {nc.value} allowed log-probabilities for a sequence of {lens[g]} ids over {n_ids} allowed ids")
+                alp[g, : lens[g]] = buf[: lens[g] * n_ids].reshape(lens[g], n_ids)
+            res["allowed_logprobs"] = torch.from_numpy(alp).to(device)
+            res["allowed_token_ids"] = torch.tensor(self.allowed_token_ids, dtype=torch.int64, device=device)
+        return res
+
+    def select_sequence(self, index: int, env_id: int = 0) -> KVHandle:
+        """After generate(do_sample=True, num_return_sequences=G): the env goes on with sequence `index` of that group turn -- its K / V
+        pages become the env's, every other continuation's go back to the pool.  Returns the env's KVHandle (the `past_key_values` of its
+        next turn); must be called before that env's next turn."""
+        if env_id not in self._group_pending:
+            raise RuntimeError(f"env_id {env_id}: no group turn is pending")
+        kv = C.c_int32()
+        _check(self._lib.svln_group_select(self._h, self._slot(env_id), int(index), C.byref(kv)))
+        del self._group_pending[env_id]
+        return KVHandle(env_id, self._epoch[env_id], kv.value)
+
+    def last_hidden_group(self, index: int) -> np.ndarray:
+        """parity tap: the final-norm rows of the first <= 8 tokens of sequence `index` of the pending group turn"""
+        buf = np.empty((8, self.cfg.hidden), dtype=np.float32)
+        n = C.c_int32()
+        _check(self._lib.svln_get_hidden_group(self._h, int(index), buf.ctypes.data_as(C.POINTER(C.c_float)), 8, C.byref(n)))
+        return buf[: n.value].copy()
 
     def _arm_batch_draft(self, env_id, draft):
         """set_batch_draft on: arm env_id's draft for the submit that follows -- explicit ids, or the env's previous output under
@@ -637,6 +753,7 @@ class StreamVLNForCausalLM:
         parsed, drafts = [], []
         for r in requests:
             r = dict(r)
+            self._reject_group_request(r, "generate_batch")
             drafts.append(r.pop("draft_ids", None))
             r.setdefault("max_new_tokens", max_new_tokens)
             if eos_token_ids is not None:
@@ -701,6 +818,7 @@ class StreamVLNForCausalLM:
         `draft_ids` (or the env's previous output under set_auto_draft) is armed for the turn while set_batch_draft is on, and ignored
         otherwise.  Returns a ticket; the result arrives from `step_batch`."""
         draft = kwargs.pop("draft_ids", None)
+        self._reject_group_request(kwargs, "submit")
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
         # refuse BEFORE the env's state changes (frames encoded, curr_t advanced, rows spliced): a turn the scheduler cannot take must
         # leave the env exactly as it was, so that the caller can retry it later
