@@ -249,6 +249,35 @@ int svln_group_select(svln_engine* h, int env, int index, int32_t* kv_len_out);
 int svln_group_logprobs(svln_engine* h, int index, float* host_out, int cap, int32_t* n);
 int svln_group_dist(svln_engine* h, int index, float* host_out, int cap_rows, int32_t* n_rows, int32_t* n_cols);
 int svln_get_hidden_group(svln_engine* h, int index, float* host_out, int max_rows, int32_t* n_rows);
+/* Opt-in, no reference counterpart: a FORCED turn -- the turn's ids F[0 .. n), 1 <= n <= 32, come from the caller.  With L = n_embeds and
+ * Tn = L - kv_len, ONE prefill pass of Tn + n - 1 rows feeds F[0 .. n - 1) behind the prompt at positions L .. L + n - 2 (the ride's
+ * gather, RoPE, KV append and causal attention; the last id is never fed), the final norm of the last n rows goes to the tap rows
+ * (svln_get_hidden: n rows), one lm_head product in its EPI_TARGET form -- the scored partials plus the logit of column F[i] of row i,
+ * captured while the logits are in registers -- and one final kernel give, per position i:
+ *   logprobs[i]         log softmax(logits_i)[F[i]]: the policy's log-probability of F[i] given the prompt and F[0 .. i)
+ *   greedy_ids[i]       the policy's own arg-max there, greedy_logprobs[i] its log-probability (the value a scored turn reports)
+ * There is no decode launch, no [n, vocab] tensor, and one synchronisation.  Head rows: n <= 2 -> the batched GEMV at B = 2, n >= 3 -> the
+ * 32-row MFMA tiles (n = 3 padded to 4); pad rows carry target -1.  Afterwards kv_len = L + n - 1 (-> *kv_len, may be null) and the loop
+ * state is what a plain turn that emitted F leaves, so the next turn -- plain, ridden, sampled or grouped -- needs nothing special.
+ * svln_set_token_scores may be on or off: the call launches its own instantiations and never reads that switch; svln_get_token_scores
+ * returns logprobs afterwards.  With svln_set_sampling on the scores are of softmax(logits / T), as a sampled turn reports them; no noise
+ * is evaluated and the env's draw counter does not move.  With svln_set_allowed_tokens on the head is the subset product, every F[i] must
+ * be in the list, logprobs[i] is bit-equal to row i of svln_get_allowed_logprobs at F[i]'s list position, and greedy_* are over the list.
+ * svln_get_top2 is refused afterwards, as after a ride.  An armed draft is consumed by the call -- also by a call that is refused
+ * (svln_generate's rule: the one exception to "before any state change" below).  The draft switches may be on (no verify
+ * rule runs), svln_set_mxfp4_batched too (scheduler paths only).
+ * Refused before any launch or state change: everything svln_generate refuses (a pending group, nothing to prefill, ...); n outside
+ * 1 .. 32; an id outside the vocabulary; an id of the EOS set anywhere but last (an EOS is appended, never fed); L + n - 1 >
+ * max_positions; a repetition penalty != 1 (its flags change row by row); svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm
+ * or svln_set_decode_persistent on (a forced row must be computed in the numeric scheme of the step it stands in for); scheduler turns in
+ * flight; an id outside the allowed list. */
+int svln_generate_forced(svln_engine* h, int env, const int64_t* ids, int n, const int64_t* eos_ids, int n_eos, float* logprobs,
+                         int64_t* greedy_ids, float* greedy_logprobs, int32_t* kv_len);
+/* svln_turn's bookkeeping (encode, window / episode resets, splice), then the forced turn, in one crossing (a->max_new_tokens is not read).
+ * The refusals that need no state of the env come before a frame is encoded; those that depend on the spliced length (nothing to prefill,
+ * L + n - 1 > max_positions) come after the splice, as svln_turn's own do. */
+int svln_turn_forced(svln_engine* h, const svln_turn_args* a, const int64_t* ids, int n, float* logprobs, int64_t* greedy_ids,
+                     float* greedy_logprobs, int32_t* kv_len);
 /* prefill taps of svln_generate (single env): enable != 0 records the LAST row of the residual stream after every decoder layer of the
  * next prefills (svln_get_layer_taps: host_out [layers][hidden]); probe_layer >= 0 additionally records, for every row of the prefill,
  * the operands the products of that one layer actually saw (svln_get_layer_probe, which: 0 = x entering the layer, 1 = x leaving it,
@@ -519,6 +548,19 @@ int svln_op_gemv_batched_argmax_scores(svln_engine* h, const void* W, int ldw, c
                                        const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs);
 int svln_op_gemm_argmax_scores(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
                                const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs);
+/* TEST-ONLY entries: the EPI_TARGET forms (svln_generate_forced) of the two batched entries above and their final kernel, whatever the
+ * engine's switches say.  targets [B] / [M] host: -1 (no column: that row's log-probability is NaN and nothing is captured) or a column
+ * of [0, N); inv_t > 0 scales every logit before the compares, sums and the capture (1.0f: the scored form's bits).  host_tokens /
+ * host_greedy_logprobs: the arg-max and its log-probability, host_logprobs: the targets'.  No fused norm, no penalty.  The refusals of
+ * the entries above apply (B in {2, 4, 8}), plus a target outside [-1, N), inv_t not finite or <= 0, a null output -- before any launch.
+ * host_slots (optional, 32 floats): in, what the 32 capture slots hold before the launch; out, what they hold after it (row m's captured
+ * y in slot m, every other slot untouched).
+ * svln_op_read_argmax_partials: the [rows][n] arg-max partials (value, index, sum) the last batched test product left. */
+int svln_op_gemv_batched_target(svln_engine* h, const void* W, int ldw, const void* x, int ldx, int N, int K, int B, const int32_t* targets, float inv_t,
+                                int32_t* host_tokens, float* host_greedy_logprobs, float* host_logprobs, float* host_slots);
+int svln_op_gemm_target(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const int32_t* targets, float inv_t,
+                        int32_t* host_tokens, float* host_greedy_logprobs, float* host_logprobs, float* host_slots);
+int svln_op_read_argmax_partials(svln_engine* h, int rows, int n, float* val, int32_t* idx, float* sum);
 /* TEST-ONLY entries: the sampled forms (EPI_SAMPLE, see svln_set_sampling) of the three entries above, on the given temperature, seed
  * and per-row streams / draws (host values; the engine's own switch and counters are not touched).  host_logprob(s) receive
  * log softmax(x / T)[token] and must not be null.  The refusals of the entries above apply, plus: temperature not finite or <= 0,

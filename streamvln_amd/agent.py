@@ -87,6 +87,8 @@ class StreamingAgent:
         # the model's distribution over the allowed ids for every id of the last model turn (model.set_allowed_tokens with
         # set_token_scores): [1, n_new, n_allowed]; None otherwise
         self.last_allowed_logprobs = None
+        # the policy's own arg-max at every position of the last FORCED model turn (act(..., forced_ids=...)): [1, n]; None otherwise
+        self.last_greedy_ids = None
         self.step_id = 0
         self.last_image = None
         self.model.reset_for_env(self.env_id)
@@ -141,12 +143,16 @@ class StreamingAgent:
         self.last_token_logprobs = lp
         self.last_turn_logprob = None if lp is None else float(lp.sum())
         self.last_allowed_logprobs = out.get("allowed_logprobs") if isinstance(out, dict) else getattr(out, "allowed_logprobs", None)
+        self.last_greedy_ids = out.get("greedy_ids") if isinstance(out, dict) else getattr(out, "greedy_ids", None)
         self.turn_log.append(dict(self._pending, out=out))
         actions = list(self.decode_actions(out.sequences))
         return actions if len(actions) else [0]               # streamvln_eval.py:340-341
 
-    def _turn(self, instruction: str, env_id: Optional[int] = None):
-        return self._consume(self.model.generate(**self._build_request(instruction, env_id)))
+    def _turn(self, instruction: str, env_id: Optional[int] = None, forced_ids=None):
+        req = self._build_request(instruction, env_id)
+        if forced_ids is not None:
+            req["forced_ids"] = forced_ids
+        return self._consume(self.model.generate(**req))
 
     # -- split form of act() used by BatchedAgents: observe -> (maybe) request -> finish ----------
     def observe(self, rgb):
@@ -165,10 +171,15 @@ class StreamingAgent:
         return action
 
     # -- eval-loop flavour: one env step, returns the action taken -------------------
-    def act(self, rgb: np.ndarray, instruction: str = "") -> int:
-        """One environment step of the Habitat loop (streamvln_eval.py:247-350)."""
+    def act(self, rgb: np.ndarray, instruction: str = "", forced_ids=None) -> int:
+        """One environment step of the Habitat loop (streamvln_eval.py:247-350).
+        forced_ids (optional): the model turn that runs at this step is a forced turn on these ids (model.generate(forced_ids=...)): the
+        env goes on with them, `last_token_logprobs` / `last_turn_logprob` are the policy's log-probabilities of them and
+        `last_greedy_ids` its own picks.  Raises, before anything changes, when no model turn runs at this step."""
+        if forced_ids is not None and len(self.action_seq) != 0:
+            raise ValueError(f"forced_ids given at step {self.step_id}, but no model turn runs there: {len(self.action_seq)} actions of the last turn are still queued")
         if self.observe(rgb):
-            self.action_seq = self._turn(instruction)
+            self.action_seq = self._turn(instruction) if forced_ids is None else self._turn(instruction, forced_ids=forced_ids)
         return self.finish_step()
 
     # -- real-world flavour ------------------------------------------------------------

@@ -117,6 +117,15 @@ struct EngineBase {
     virtual void op_gumbel(uint64_t seed, int stream, int draw, int n0, int count, float* out) = 0;
     virtual void generate_group(int env, int n_seq, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out) = 0;
     virtual void turn_group(const svln_turn_args& a, int n_seq, int64_t* out, int cap, int32_t* n_out) = 0;
+    virtual void generate_forced(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos, float* logprobs, int64_t* greedy_ids,
+                                 float* greedy_logprobs, int32_t* kv_len) = 0;
+    virtual void turn_forced(const svln_turn_args& a, const int64_t* ids, int n, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs,
+                             int32_t* kv_len) = 0;
+    virtual void op_gemv_batched_target(GemvBatchArgs a, const int32_t* targets, float inv_t, int32_t* host_tokens, float* host_greedy,
+                                        float* host_logprobs, float* host_slots) = 0;
+    virtual void op_gemm_target(GemmArgs a, const int32_t* targets, float inv_t, int32_t* host_tokens, float* host_greedy, float* host_logprobs,
+                                float* host_slots) = 0;
+    virtual void op_read_argmax_partials(int rows, int n, float* val, int32_t* idx, float* sum) = 0;
     virtual void group_select(int env, int index, int32_t* kv_len) = 0;
     virtual void group_logprobs(int index, float* out, int cap, int32_t* n) = 0;
     virtual void group_dist(int index, float* out, int cap_rows, int32_t* n_rows, int32_t* n_cols) = 0;
@@ -2550,6 +2559,224 @@ public:
         }
         generate_group(a.env, n_seq, a.max_new_tokens, a.eos_ids, a.n_eos, out, cap, n_out);
     }
+    // ------------------------------------------------------------------------------- forced turns (svln_generate_forced)
+    // A turn on the CALLER's ids F[0 .. n): ids F[0 .. n - 1) ride the prefill pass as n - 1 more rows (the ride's gather, RoPE, KV append
+    // and causal attention), the final norm of the last n rows goes to xn and the tap rows, ONE lm_head product in its EPI_TARGET form
+    // keeps row i's logit of column F[i] beside the scored partials, and one final kernel writes the policy's arg-max, its log-probability
+    // and F[i]'s.  No decode launch, one synchronisation.  The env and the loop state end where a plain turn that emitted F leaves them.
+    static constexpr int FORCED_MAX = 32;
+    int* d_ftgt = nullptr; int* h_ftgt = nullptr; float* d_fval = nullptr; float* d_flp = nullptr; float* h_flp = nullptr;
+    void ensure_forced_buffers() {
+        if (d_ftgt) return;
+        d_ftgt = dalloc<int>(FORCED_MAX, true); d_fval = dalloc<float>(FORCED_MAX, true); d_flp = dalloc<float>(FORCED_MAX, true);
+        HIP_CHECK(hipHostMalloc((void**)&h_ftgt, FORCED_MAX * sizeof(int)));
+        HIP_CHECK(hipHostMalloc((void**)&h_flp, FORCED_MAX * sizeof(float)));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    // targets of `rows` head rows -> d_ftgt (pad rows: -1)
+    void upload_targets(const int32_t* tg, int n, int rows) {
+        HIP_CHECK(hipStreamSynchronize(st));       // (h_ftgt of an earlier call is no longer being read)
+        for (int k = 0; k < rows; ++k) h_ftgt[k] = k < n ? tg[k] : -1;
+        HIP_CHECK(hipMemcpyAsync(d_ftgt, h_ftgt, rows * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    TargetArgs target_args(float inv_t) { TargetArgs t; t.tgt = d_ftgt; t.tgt_val = d_fval; t.inv_t = inv_t; return t; }
+    // the EPI_TARGET lm_head over `rows` rows of xrows (the first n of them live) and its final kernel: greedy ids -> d_tok_b, their
+    // log-probabilities -> d_score_b, the targets' -> d_flp.  The routing is argmax_rows' own: MFMA tiles from batched_mfma_min rows.
+    void target_rows(const void* W, int ldw, const T* xrows, int ldx, int N, int K, int rows, int n, float inv_t) {
+        int np;
+        if (rows >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048) {
+            GemmArgs a = gemm_args(xrows, ldx, W, ldw, nullptr, 0, nullptr, nullptr, 0, 0, rows, N, K, EPI_ARGMAX);
+            a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b; a.tg = target_args(inv_t);
+            np = launch_gemm_argmax<T>(st, a);
+        } else {
+            GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, EPI_TARGET, rows);
+            hb.part_sum = part_sum_b; hb.tg = target_args(inv_t);
+            launch_gemv_batched<T>(st, hb);
+            np = gemv_batched_grid(N, EPI_ARGMAX, rows);
+        }
+        launch_target_final_batched(st, part_val_b, part_idx_b, part_sum_b, np, n, d_ftgt, d_fval, d_tok_b, d_score_b, d_flp);
+    }
+    // every refusal of a forced turn that needs no state of the env (svln_turn_forced checks them before it encodes a frame)
+    void forced_refusals(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos) {
+        env_at(env);
+        REQUIRE(ids, "svln_generate_forced: null id list");
+        REQUIRE(n >= 1 && n <= FORCED_MAX, "svln_generate_forced: n must be 1 .. 32");
+        REQUIRE(n_eos >= 0 && n_eos <= (V > 16 ? V : 16) && (n_eos == 0 || eos), "svln_generate_forced: bad eos list");
+        for (int k = 0; k < n; ++k) {
+            REQUIRE(ids[k] >= 0 && ids[k] < V, "svln_generate_forced: id " + std::to_string((long long)ids[k]) + " is outside the vocabulary");
+            if (k + 1 < n)
+                for (int q = 0; q < n_eos; ++q)
+                    REQUIRE(eos[q] != ids[k], "svln_generate_forced: an id of the EOS set may only be the last one (an EOS is appended, never fed)");
+        }
+        REQUIRE(rep_penalty == 1.0f, "svln_generate_forced: a repetition penalty != 1 is set (svln_set_repetition_penalty); its flags change row by row");
+        // a forced row must be computed in the numeric scheme of the step it stands in for (the ride's list)
+        REQUIRE(!(fp8_on || mx4_on || fp8_gemm_on || persistent_on),
+                "svln_generate_forced: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm, "
+                "svln_set_decode_persistent); switch it off first");
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_generate_forced needs an idle scheduler (turns are in flight)");
+        if (allow_on)
+            for (int k = 0; k < n; ++k)
+                REQUIRE(std::binary_search(allow_ids.begin(), allow_ids.end(), (int)ids[k]),
+                        "svln_generate_forced: id " + std::to_string((long long)ids[k]) + " is not in the allowed list (svln_set_allowed_tokens)");
+        REQUIRE(allow_on || ride_head_rows(n) >= n, "svln_generate_forced: this vocabulary / hidden size has no lm_head form for more than 8 rows");
+    }
+    void generate_forced(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs,
+                         int32_t* kv_len) override {
+        Env& e = env_at(env);
+        refuse_while_group_on(env, "svln_generate_forced");
+        disarm_draft(env);              // consumed by this call, as svln_generate consumes it
+        REQUIRE(logprobs && greedy_ids && greedy_logprobs, "svln_generate_forced: null output pointer");
+        forced_refusals(env, ids, n, eos, n_eos);
+        REQUIRE(weights_missing() == 0, g_err);
+        const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
+        REQUIRE(Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
+        REQUIRE((int64_t)L + n - 1 <= c.max_positions, "svln_generate_forced: n_embeds + n - 1 exceeds max_positions");
+        // ---- nothing was launched or changed up to here (but the armed draft)
+        last_scores_valid = false; last_alp_valid = false;
+        set_speculative_buffers();      // d_draft / h_draft: the fed ids
+        ensure_forced_buffers();
+        ensure_pages(e, L + n - 1);
+        const int k = n - 1;            // fed rows: the last id is never fed
+        const int M = Tn + k;
+        const int rows = allow_on ? n : ride_head_rows(n);
+        const float inv_t = smp_on ? smp_inv_t : 1.0f;
+        // (the pinned staging was last read by copies of calls that ended in a synchronisation)
+        for (int i = 0; i < n; ++i) h_draft[i] = (int)ids[i];
+        for (int i = 0; i < rows; ++i) h_ftgt[i] = i < n ? (int)ids[i] : -1;
+        HIP_CHECK(hipMemcpyAsync(d_draft, h_draft, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_ftgt, h_ftgt, (size_t)rows * sizeof(int), hipMemcpyHostToDevice, st));
+        // the loop state a plain turn that emitted F leaves: n ids listed, the last one appended and not fed
+        HIP_CHECK(hipMemcpyAsync(d_out_ids, h_draft, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+        h_ctl->pos = L - 1 + k; h_ctl->kv_len = L + k; h_ctl->done = 1; h_ctl->count = n; h_ctl->max_new = n; h_ctl->n_eos = n_eos;
+        h_ctl->draw0 = smp_on ? env_draws[env] : 0; h_ctl->stream = smp_on ? env : 0;
+        HIP_CHECK(hipMemcpyAsync(d_ctl, h_ctl, sizeof(GenCtl), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipEventRecord(ph_ev[2], st));
+        prefill(e, P, M, k);
+        e.kv_len = L;
+        launch_rmsnorm<T>(st, x + (size_t)(M - n) * H, final_norm, xn, n, H, c.rms_eps);
+        HIP_CHECK(hipMemcpyAsync(hid_tap, xn, (size_t)n * H * sizeof(T), hipMemcpyDeviceToDevice, st));
+        if (allow_on) {
+            // the subset product as on every other path: one partial per listed id on y; row i's normalised row -> d_alp_b[i], and the
+            // score of F[i] is that row's entry at the id's list position (the same bits svln_get_allowed_logprobs returns)
+            GemvSubsetArgs su = subset_args(xn, H, n, part_val_b, part_idx_b, part_sum_b);
+            su.epi = EPI_TARGET; su.tg_inv_t = inv_t;
+            launch_gemv_subset<T>(st, su);
+            launch_subset_logprobs(st, part_val_b, allow_n, n, d_alp_b);
+            launch_argmax_final_batched(st, part_val_b, part_idx_b, allow_n, n, d_tok_b, part_sum_b, d_score_b);
+        } else {
+            target_rows(lm_head, H, xn, H, V, H, rows, n, inv_t);
+        }
+        HIP_CHECK(hipEventRecord(ph_ev[3], st));
+        HIP_CHECK(hipMemcpyAsync(h_tok_b, d_tok_b, n * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h_score_b, d_score_b, n * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (allow_on) HIP_CHECK(hipMemcpyAsync(h_alp_b, d_alp_b, (size_t)n * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
+        else HIP_CHECK(hipMemcpyAsync(h_flp, d_flp, n * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        LAUNCH_CHECK("generate_forced");
+        for (int i = 0; i < n; ++i)
+            REQUIRE(h_tok_b[i] >= 0 && h_tok_b[i] < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+        for (int i = 0; i < n; ++i) {
+            greedy_ids[i] = h_tok_b[i]; greedy_logprobs[i] = h_score_b[i];
+            if (allow_on) {
+                const int pos = (int)(std::lower_bound(allow_ids.begin(), allow_ids.end(), (int)ids[i]) - allow_ids.begin());
+                logprobs[i] = h_alp_b[(size_t)i * allow_n + pos];
+            } else {
+                logprobs[i] = h_flp[i];
+            }
+        }
+        last_scores.assign(logprobs, logprobs + n); last_scores_valid = true;
+        if (allow_on) { last_alp.assign(h_alp_b, h_alp_b + (size_t)n * allow_n); last_alp_n = allow_n; last_alp_valid = true; }
+        e.kv_len = L + n - 1;
+        {
+            float t = 0.f;
+            HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[3])); ph_ms[1] += t;
+            if (vision_pending) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
+        }
+        n_generated = n;
+        top2_stale = true;              // no top-2 logits were kept, as after a ride
+        top2_sampled = false;
+        if (kv_len) *kv_len = e.kv_len;
+    }
+    void turn_forced(const svln_turn_args& a, const int64_t* ids, int n, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs,
+                     int32_t* kv_len) override {
+        env_at(a.env);
+        refuse_while_group_on(a.env, "svln_turn_forced");
+        try {
+            REQUIRE(a.ids && a.n_ids >= 1 && logprobs && greedy_ids && greedy_logprobs, "svln_turn_forced: null / empty argument");
+            forced_refusals(a.env, ids, n, a.eos_ids, a.n_eos);
+            encode_frames(a.pixels, a.n_frames, a.pixels_on_device);
+            if (a.new_window) kv_reset(a.env);
+            if (a.new_episode && envs[a.env].n_embeds != 0) reset_env(a.env);
+            append_turn(a.env, a.ids, a.n_ids, 0, a.n_memory);
+        } catch (...) {
+            disarm_draft(a.env);
+            throw;
+        }
+        generate_forced(a.env, ids, n, a.eos_ids, a.n_eos, logprobs, greedy_ids, greedy_logprobs, kv_len);
+    }
+    // TEST-ONLY: one EPI_TARGET product and its final kernel on caller-given device operands, whatever the engine's switches say
+    // host_slots (optional, [32]): in, what the capture slots hold before the launch; out, what they hold after it
+    void slots_in(const float* host_slots) {
+        if (host_slots) HIP_CHECK(hipMemcpy(d_fval, host_slots, FORCED_MAX * sizeof(float), hipMemcpyHostToDevice));
+    }
+    void target_out(int n, int32_t* host_tokens, float* host_greedy, float* host_logprobs, float* host_slots, const char* who) {
+        if (host_slots) HIP_CHECK(hipMemcpyAsync(host_slots, d_fval, FORCED_MAX * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h_tok_b, d_tok_b, n * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h_score_b, d_score_b, n * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h_flp, d_flp, n * sizeof(float), hipMemcpyDeviceToHost, st));
+        sync();
+        LAUNCH_CHECK(who);
+        for (int b = 0; b < n; ++b) { host_tokens[b] = h_tok_b[b]; host_greedy[b] = h_score_b[b]; host_logprobs[b] = h_flp[b]; }
+    }
+    void target_op_refusals(const int32_t* targets, int rows, int N, float inv_t, const void* o0, const void* o1, const void* o2) {
+        REQUIRE(targets && o0 && o1 && o2, "null pointer");
+        REQUIRE(std::isfinite(inv_t) && inv_t > 0.0f, "inv_t must be finite and > 0");
+        for (int k = 0; k < rows; ++k) REQUIRE(targets[k] >= -1 && targets[k] < N, "targets: -1 (none) or a column of [0, N)");
+    }
+    void op_gemv_batched_target(GemvBatchArgs a, const int32_t* targets, float inv_t, int32_t* host_tokens, float* host_greedy,
+                                float* host_logprobs, float* host_slots) override {
+        REQUIRE(a.W && a.x, "null pointer");
+        REQUIRE(a.B == 2 || a.B == 4 || a.B == 8, "B must be 2, 4 or 8");
+        REQUIRE(a.N >= 1 && a.K >= Elt<T>::PER_CHUNK && a.K % Elt<T>::PER_CHUNK == 0, "N >= 1, K a positive multiple of the 16-byte chunk");
+        REQUIRE(a.ldw >= a.K && a.ldw % Elt<T>::PER_CHUNK == 0 && a.ldx >= a.K && a.ldx % Elt<T>::PER_CHUNK == 0, "ldw, ldx >= K, multiples of the 16-byte chunk");
+        target_op_refusals(targets, a.B, a.N, inv_t, host_tokens, host_greedy, host_logprobs);
+        ensure_forced_buffers();
+        upload_targets(targets, a.B, a.B);
+        slots_in(host_slots);
+        a.epi = EPI_TARGET; a.norm_w = nullptr; a.pen_flags = nullptr;
+        a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b; a.tg = target_args(inv_t);
+        launch_gemv_batched<T>(st, a);
+        launch_target_final_batched(st, part_val_b, part_idx_b, part_sum_b, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), a.B, d_ftgt, d_fval, d_tok_b, d_score_b, d_flp);
+        target_out(a.B, host_tokens, host_greedy, host_logprobs, host_slots, "op_gemv_batched_target");
+    }
+    void op_gemm_target(GemmArgs a, const int32_t* targets, float inv_t, int32_t* host_tokens, float* host_greedy, float* host_logprobs,
+                        float* host_slots) override {
+        constexpr int chunk = Elt<T>::PER_CHUNK;
+        REQUIRE(a.A && a.W, "null pointer");
+        REQUIRE(a.M >= 1 && a.M <= 32 && a.N >= 1 && (a.N + 127) / 128 <= 2048, "1 <= M <= 32 rows, 1 <= N <= 262144");
+        REQUIRE(a.K >= chunk && a.K % chunk == 0 && a.lda >= a.K && a.ldw >= a.K && a.lda % chunk == 0 && a.ldw % chunk == 0,
+                "K a positive multiple of the 16-byte chunk; lda, ldw >= K, multiples of it (aligned LDS-DMA)");
+        REQUIRE(((size_t)a.A & 15) == 0 && ((size_t)a.W & 15) == 0, "A and W must be 16-byte aligned (LDS-DMA)");
+        target_op_refusals(targets, a.M, a.N, inv_t, host_tokens, host_greedy, host_logprobs);
+        ensure_forced_buffers();
+        upload_targets(targets, a.M, a.M);
+        slots_in(host_slots);
+        a.zeros = zero_line; a.epi = EPI_ARGMAX; a.pen_flags = nullptr;
+        a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b; a.tg = target_args(inv_t);
+        const int np = launch_gemm_argmax<T>(st, a);
+        launch_target_final_batched(st, part_val_b, part_idx_b, part_sum_b, np, a.M, d_ftgt, d_fval, d_tok_b, d_score_b, d_flp);
+        target_out(a.M, host_tokens, host_greedy, host_logprobs, host_slots, "op_gemm_target");
+    }
+    // TEST-ONLY: the batched arg-max partials [rows][n] the last lm_head product of a test op left (part_val, part_idx, part_sum)
+    void op_read_argmax_partials(int rows, int n, float* val, int32_t* idx, float* sum) override {
+        REQUIRE(val && idx && sum, "null pointer");
+        REQUIRE(rows >= 1 && rows <= HEAD_ROWS && n >= 1 && n <= 2048, "1 <= rows <= 64, 1 <= n <= 2048");
+        sync();
+        const size_t m = (size_t)rows * n;
+        HIP_CHECK(hipMemcpy(val, part_val_b, m * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(idx, part_idx_b, m * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(sum, part_sum_b, m * sizeof(float), hipMemcpyDeviceToHost));
+    }
     void group_select(int env, int index, int32_t* kv_len) override {
         env_at(env);
         REQUIRE(grp.pending && grp.env == env, "svln_group_select: no group turn is pending on this env");
@@ -3610,6 +3837,33 @@ int svln_generate_group(svln_engine* h, int env, int n_seq, int max_new, const i
 }
 int svln_turn_group(svln_engine* h, const svln_turn_args* a, int n_seq, int64_t* out_ids, int out_cap, int32_t* n_out) {
     API_BEGIN_H REQUIRE(a, "null argument"); h->impl->turn_group(*a, n_seq, out_ids, out_cap, n_out); API_END
+}
+int svln_generate_forced(svln_engine* h, int env, const int64_t* ids, int n, const int64_t* eos_ids, int n_eos, float* logprobs, int64_t* greedy_ids,
+                         float* greedy_logprobs, int32_t* kv_len) {
+    API_BEGIN_H h->impl->generate_forced(env, ids, n, eos_ids, n_eos, logprobs, greedy_ids, greedy_logprobs, kv_len); API_END
+}
+int svln_turn_forced(svln_engine* h, const svln_turn_args* a, const int64_t* ids, int n, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs,
+                     int32_t* kv_len) {
+    API_BEGIN_H REQUIRE(a, "null argument"); h->impl->turn_forced(*a, ids, n, logprobs, greedy_ids, greedy_logprobs, kv_len); API_END
+}
+int svln_op_gemv_batched_target(svln_engine* h, const void* W, int ldw, const void* x, int ldx, int N, int K, int B, const int32_t* targets, float inv_t,
+                                int32_t* host_tokens, float* host_greedy_logprobs, float* host_logprobs, float* host_slots) {
+    API_BEGIN_H
+    GemvBatchArgs a; a.W = W; a.ldw = ldw; a.x = x; a.ldx = ldx; a.norm_w = nullptr; a.eps = 0.0f; a.bias = nullptr; a.res = nullptr; a.ldr = 0;
+    a.y = nullptr; a.ldy = 0; a.N = N; a.K = K; a.epi = EPI_TARGET; a.B = B; a.part_val = nullptr; a.part_idx = nullptr;
+    h->impl->op_gemv_batched_target(a, targets, inv_t, host_tokens, host_greedy_logprobs, host_logprobs, host_slots);
+    API_END
+}
+int svln_op_gemm_target(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const int32_t* targets, float inv_t,
+                        int32_t* host_tokens, float* host_greedy_logprobs, float* host_logprobs, float* host_slots) {
+    API_BEGIN_H
+    GemmArgs a; std::memset(&a, 0, sizeof(a));
+    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.epi = EPI_ARGMAX; a.nsplit = 1; a.pen = 1.0f; a.smp.inv_t = 1.0f; a.tg.inv_t = 1.0f;
+    h->impl->op_gemm_target(a, targets, inv_t, host_tokens, host_greedy_logprobs, host_logprobs, host_slots);
+    API_END
+}
+int svln_op_read_argmax_partials(svln_engine* h, int rows, int n, float* val, int32_t* idx, float* sum) {
+    API_BEGIN_H h->impl->op_read_argmax_partials(rows, n, val, idx, sum); API_END
 }
 int svln_group_select(svln_engine* h, int env, int index, int32_t* kv_len_out) { API_BEGIN_H h->impl->group_select(env, index, kv_len_out); API_END }
 int svln_group_logprobs(svln_engine* h, int index, float* out, int cap, int32_t* n) {

@@ -474,8 +474,11 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
     const T* xg = (const T*)p.x;
     const T* gg = (const T*)p.norm_w;
     const int n_units = EPI == EPI_SWIGLU ? p.N / R : (p.N + R - 1) / R;      // one unit = R weight rows
-    constexpr bool AMAX = epi_is_argmax(EPI), LSE = EPI == EPI_ARGMAX_LSE, SMP = EPI == EPI_SAMPLE;
+    constexpr bool AMAX = epi_is_argmax(EPI), TGT = EPI == EPI_TARGET, LSE = EPI == EPI_ARGMAX_LSE || TGT, SMP = EPI == EPI_SAMPLE;
     static_assert(!(SMP && NORM), "EPI_SAMPLE has no fused-norm form");
+    static_assert(!(TGT && NORM), "EPI_TARGET has no fused-norm form");
+    [[maybe_unused]] int my_tgt = -1;                                         // EPI_TARGET: thread b < B holds env b's named column
+    if constexpr (TGT) if (tid < B) my_tgt = p.tg.tgt[tid];
     float best = -INFINITY;                                                   // EPI_ARGMAX: thread b < B tracks env b (EPI_SAMPLE: the best z)
     int best_i = 0x7FFFFFFF;
     float lm = -INFINITY, ls = 0.0f;                                          // EPI_ARGMAX_LSE: env b's (max, sum exp(l - max)) over the workgroup's units
@@ -580,6 +583,12 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
                 for (int r = 0; r < R; ++r) {
                     float v = total(r * B + tid);
                     if (fl && n0 + r < p.N && fl[n0 + r]) v = v < 0.0f ? v * p.pen : v / p.pen;
+                    if constexpr (TGT) {
+                        // y = fl(v * inv_t) (inv_t == 1.0f: v itself), then the scored form's compares and sums on y; the one thread of the
+                        // grid that meets column tgt[b] -- a unit belongs to one workgroup, row b to thread b -- stores it (-1 meets none)
+                        v *= p.tg.inv_t;
+                        if (n0 + r < p.N && n0 + r == my_tgt) p.tg.tgt_val[tid] = v;
+                    }
                     if constexpr (SMP) {
                         const float y = v * p.smp.inv_t, z = y + gn[r * B + tid];
                         if (n0 + r < p.N) {
@@ -662,19 +671,10 @@ SVLN_DEV SampleMerge sample_merge(const int* pi, const float* pr, const float* p
     return r;
 }
 
-// final arg-max of env b = blockIdx.x over its per-workgroup partials
-// LSE: also env b's log-probability of that token from its partial sums ps (NaN for token -1); rs (optional): the positive factor of
-// row b by which the producer scaled the logits it summed (a fused norm), so that partial k's maximum there is fl(pv[k] * rs[b])
-// SMP (with LSE): the EPI_SAMPLE merge -- the token on (pv, pi) as before; its y from pr of the partial that owns it; the log-sum-exp on
-// (pm, ps); score = y - V - log S
-template <bool LSE, bool SMP = false>
-__global__ __launch_bounds__(256) void argmax_final_batched_kernel(const float* pv, const int* pi, int n, int* out_tokens, const float* ps,
-                                                                   float* scores, const float* rs, const float* pr = nullptr,
-                                                                   const float* pm = nullptr) {
-    __shared__ float sv[256];
-    __shared__ int si[256];
-    const float* v0 = pv + (size_t)blockIdx.x * n;
-    const int* i0 = pi + (size_t)blockIdx.x * n;
+// The merge of one row's n partials on 256 threads, shared by argmax_final_batched_kernel and target_final_batched_kernel (one body: the
+// two kernels' ids and sums are the same bits by construction).
+// row_argmax_256: greatest value, lowest index on ties -> sv[0], si[0] (0x7FFFFFFF: no finite logit); ends synchronised.
+SVLN_DEV void row_argmax_256(const float* v0, const int* i0, int n, float* sv, int* si) {
     float v = -INFINITY;
     int i = 0x7FFFFFFF;
     for (int k = threadIdx.x; k < n; k += 256) {
@@ -692,6 +692,29 @@ __global__ __launch_bounds__(256) void argmax_final_batched_kernel(const float* 
         }
         __syncthreads();
     }
+}
+// row_lse_sum_256: S = sum_k lse_rescale(ps[k], v0[k] * sc, V) on the fixed tree; sv must have been read by every thread's caller already
+SVLN_DEV float row_lse_sum_256(const float* ps, const float* v0, int n, float sc, float V, float* sv) {
+    __syncthreads();                          // sv is reused by the sum
+    float mine = 0.0f;
+    for (int k = threadIdx.x; k < n; k += 256) mine += lse_rescale(ps[k], v0[k] * sc, V);
+    return block_sum_256(mine, sv);
+}
+
+// final arg-max of env b = blockIdx.x over its per-workgroup partials
+// LSE: also env b's log-probability of that token from its partial sums ps (NaN for token -1); rs (optional): the positive factor of
+// row b by which the producer scaled the logits it summed (a fused norm), so that partial k's maximum there is fl(pv[k] * rs[b])
+// SMP (with LSE): the EPI_SAMPLE merge -- the token on (pv, pi) as before; its y from pr of the partial that owns it; the log-sum-exp on
+// (pm, ps); score = y - V - log S
+template <bool LSE, bool SMP = false>
+__global__ __launch_bounds__(256) void argmax_final_batched_kernel(const float* pv, const int* pi, int n, int* out_tokens, const float* ps,
+                                                                   float* scores, const float* rs, const float* pr = nullptr,
+                                                                   const float* pm = nullptr) {
+    __shared__ float sv[256];
+    __shared__ int si[256];
+    const float* v0 = pv + (size_t)blockIdx.x * n;
+    const int* i0 = pi + (size_t)blockIdx.x * n;
+    row_argmax_256(v0, i0, n, sv, si);
     if (threadIdx.x == 0) out_tokens[blockIdx.x] = si[0] == 0x7FFFFFFF ? -1 : si[0];    // no finite logit: -1 (in-range for the next gather, an error on the host)
     if constexpr (SMP) {
         const int tok = si[0];
@@ -704,11 +727,31 @@ __global__ __launch_bounds__(256) void argmax_final_batched_kernel(const float* 
         const float sc = rs ? rs[blockIdx.x] : 1.0f;
         const float V = sv[0] * sc;
         const int tok = si[0];
-        __syncthreads();                          // sv is reused by the sum
-        float mine = 0.0f;
-        for (int k = threadIdx.x; k < n; k += 256) mine += lse_rescale(ps[(size_t)blockIdx.x * n + k], v0[k] * sc, V);
-        const float S = block_sum_256(mine, sv);
+        const float S = row_lse_sum_256(ps + (size_t)blockIdx.x * n, v0, n, sc, V, sv);
         if (threadIdx.x == 0) scores[blockIdx.x] = tok == 0x7FFFFFFF ? __builtin_nanf("") : lse_logprob(S);
+    }
+}
+
+// EPI_TARGET merge of row b = blockIdx.x: argmax_final_batched_kernel<true>'s arg-max and (V, S) through the two helpers above (so
+// greedy_ids / greedy_logprobs are that kernel's bits), then the named column's score from the captured y: (tgt_val - V) - log S.
+// tgt[b] < 0: NaN, tgt_val[b] is not read.  A NaN y gives NaN, a -inf y gives -inf (V is finite or the row is NaN already).
+__global__ __launch_bounds__(256) void target_final_batched_kernel(const float* pv, const int* pi, const float* ps, int n, const int* tgt,
+                                                                   const float* tgt_val, int* greedy_ids, float* greedy_logprobs, float* logprobs) {
+    __shared__ float sv[256];
+    __shared__ int si[256];
+    const float* v0 = pv + (size_t)blockIdx.x * n;
+    const int* i0 = pi + (size_t)blockIdx.x * n;
+    row_argmax_256(v0, i0, n, sv, si);
+    const float V = sv[0];
+    const int tok = si[0];
+    const float S = row_lse_sum_256(ps + (size_t)blockIdx.x * n, v0, n, 1.0f, V, sv);       // (factor 1: v0[k] * 1.0f is v0[k])
+    if (threadIdx.x == 0) {
+        const float lp = lse_logprob(S), nan = __builtin_nanf("");
+        greedy_ids[blockIdx.x] = tok == 0x7FFFFFFF ? -1 : tok;
+        greedy_logprobs[blockIdx.x] = tok == 0x7FFFFFFF ? nan : lp;
+        const int t = tgt[blockIdx.x];
+        // (t - V) - log S written as -(log S - (t - V)): the same rounding, and with t == V it is lp to the sign of a zero (S == 1: -0)
+        logprobs[blockIdx.x] = t < 0 || tok == 0x7FFFFFFF ? nan : -(-lp - (tgt_val[blockIdx.x] - V));
     }
 }
 
@@ -930,6 +973,10 @@ template <typename T> void launch_gemv_batched(hipStream_t s, const GemvBatchArg
             if (norm) throw std::runtime_error("batched GEMV: EPI_SAMPLE has no fused-norm form");
             launch_gb<T, EPI_SAMPLE, false>(s, a);
             break;
+        case EPI_TARGET:
+            if (norm || a.pen_flags || !a.tg.tgt || !a.tg.tgt_val) throw std::runtime_error("batched GEMV: EPI_TARGET takes targets, no fused norm and no penalty flags");
+            launch_gb<T, EPI_TARGET, false>(s, a);
+            break;
         default: break;
     }
 }
@@ -940,6 +987,10 @@ void launch_argmax_final_batched(hipStream_t s, const float* pv, const int* pi, 
     if (pr) hipLaunchKernelGGL((argmax_final_batched_kernel<true, true>), dim3(B), dim3(256), 0, s, pv, pi, n, out_tokens, ps, scores, rs, pr, pm);
     else if (ps) hipLaunchKernelGGL((argmax_final_batched_kernel<true, false>), dim3(B), dim3(256), 0, s, pv, pi, n, out_tokens, ps, scores, rs, pr, pm);
     else hipLaunchKernelGGL((argmax_final_batched_kernel<false, false>), dim3(B), dim3(256), 0, s, pv, pi, n, out_tokens, ps, scores, rs, pr, pm);
+}
+void launch_target_final_batched(hipStream_t s, const float* pv, const int* pi, const float* ps, int n, int B, const int* tgt, const float* tgt_val,
+                                 int* greedy_ids, float* greedy_logprobs, float* logprobs) {
+    hipLaunchKernelGGL(target_final_batched_kernel, dim3(B), dim3(256), 0, s, pv, pi, ps, n, tgt, tgt_val, greedy_ids, greedy_logprobs, logprobs);
 }
 template void launch_gemv_timed<bf16>(hipStream_t, const GemvArgs&, hipEvent_t, hipEvent_t);
 template void launch_gemv_timed<float>(hipStream_t, const GemvArgs&, hipEvent_t, hipEvent_t);

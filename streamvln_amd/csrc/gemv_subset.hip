@@ -25,7 +25,7 @@ constexpr int SUBSET_RB = 4;             // activation rows per pass over the we
 template <typename T, int EPI>
 __global__ __launch_bounds__(GEMV_SUBSET_WAVES * 64) void gemv_subset_kernel(GemvSubsetArgs p) {
     constexpr int EPC = Elt<T>::PER_CHUNK;
-    constexpr bool LSE = EPI == EPI_ARGMAX_LSE, SMP = EPI == EPI_SAMPLE;
+    constexpr bool TGT = EPI == EPI_TARGET, LSE = EPI == EPI_ARGMAX_LSE || TGT, SMP = EPI == EPI_SAMPLE;
     if (p.skip && *p.skip) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = blockIdx.x * GEMV_SUBSET_WAVES + wave;
@@ -67,6 +67,7 @@ __global__ __launch_bounds__(GEMV_SUBSET_WAVES * 64) void gemv_subset_kernel(Gem
             }
             const size_t o = (size_t)b * p.n + j;
             float y = v, val = v;
+            if constexpr (TGT) y = val = v * p.tg_inv_t;       // a forced turn: the scored partials on y, no noise (1.0f with sampling off)
             if constexpr (SMP) {
                 y = v * p.smp.inv_t;
                 val = y + gumbel_noise(p.smp.seed_lo, p.smp.seed_hi, p.smp.stream[b], p.smp.draw[b] + (p.smp.count ? *p.smp.count : 0), id);
@@ -118,6 +119,7 @@ template <typename T> void launch_gemv_subset(hipStream_t s, const GemvSubsetArg
         case EPI_ARGMAX: launch_subset_epi<T, EPI_ARGMAX>(s, a); break;
         case EPI_ARGMAX_LSE: launch_subset_epi<T, EPI_ARGMAX_LSE>(s, a); break;
         case EPI_SAMPLE: launch_subset_epi<T, EPI_SAMPLE>(s, a); break;
+        case EPI_TARGET: launch_subset_epi<T, EPI_TARGET>(s, a); break;
         default: break;
     }
 }

@@ -9,7 +9,7 @@
 
 namespace svln {
 
-enum Epi : int { EPI_NONE = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_SWIGLU = 3, EPI_ARGMAX = 4, EPI_ARGMAX_LSE = 5, EPI_SAMPLE = 6 };
+enum Epi : int { EPI_NONE = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_SWIGLU = 3, EPI_ARGMAX = 4, EPI_ARGMAX_LSE = 5, EPI_SAMPLE = 6, EPI_TARGET = 7 };
 // EPI_ARGMAX_LSE (svln_set_token_scores): EPI_ARGMAX -- same accumulators, same compares, same partials, hence the same tokens -- plus one
 // fp32 per partial, part_sum[k] = sum exp(l_j - part_val[k]) over the (penalised) logits partial k owns.  The final kernels merge them,
 // S = sum_k part_sum[k] * exp(part_val[k] - V) with V the winning value, and write the token's log-probability -log S.  A partial that
@@ -20,7 +20,13 @@ enum Epi : int { EPI_NONE = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_SWIGLU =
 // winner, part_max = max y, part_sum = sum exp(y - part_max) over the logits it owns (-inf, 0 for none).  The final kernels pick the token
 // on (part_val, part_idx), take the part_raw of the partial that owns it (a column belongs to one partial), V = max_k part_max[k],
 // S = sum_k part_sum[k] * exp(part_max[k] - V), and write the token's log-probability under softmax(x * inv_t): part_raw - V - log S.
-constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE || epi == EPI_SAMPLE; }
+// EPI_TARGET (svln_generate_forced): the EPI_ARGMAX_LSE partials on y = fl(x * inv_t) -- no penalty, no noise; inv_t is exactly 1.0f with
+// sampling off, so tokens and partials are then the scored form's bit for bit -- plus the capture of ONE named column per row: the lane
+// that holds column tgt[m] of a live row m stores tgt_val[m] = y (one plain store per row in the whole grid; -1 names no column).  The
+// final kernel (launch_target_final_batched) writes the arg-max, its log-probability -log S and the target's, (tgt_val - V) - log S.
+constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE || epi == EPI_SAMPLE || epi == EPI_TARGET; }
+// Inputs of EPI_TARGET: tgt [rows] device ids (-1: none), tgt_val [rows] the captured y
+struct TargetArgs { const int* tgt = nullptr; float* tgt_val = nullptr; float inv_t = 1.0f; };
 // Inputs of EPI_SAMPLE.  stream / draw are device arrays indexed by the row of the product (row 0 of a GEMV), read by the kernel: nothing a
 // captured launch would freeze.  count (GEMV only, optional): a device scalar added to draw[0] (GenCtl::count: the tokens of this turn).
 struct SampleArgs {
@@ -74,13 +80,14 @@ struct GemmArgs {
     const uint8_t* pen_flags = nullptr; const int* pen_rows = nullptr; float pen = 1.0f;
     float* part_sum = nullptr;    // non-null: the EPI_ARGMAX_LSE form, [m][tiles] beside part_val
     SampleArgs smp;               // smp.part_raw non-null: the EPI_SAMPLE form (part_sum too)
+    TargetArgs tg;                // tg.tgt non-null: the EPI_TARGET form (part_sum too; no penalty flags)
     VitPackArgs vp; int vp_on;    // filled by the launcher: device-side copy of *vitpack for the unsplit kernels that pack in their epilogue
     int force_cfg, force_split;   // tests: 0 = heuristic; force_cfg 129 -> 128x128 tiles with two in-workgroup K groups; force_cfg low bits 128 -> 128x128 tiles, 264 -> 256x64 tiles; force_split S -> 256x128 tiles, S splits
 };
 // true: a.norm_out was produced, or the K / V^T pages of a.vitpack were.  vit_packer (host, optional): the writer of those pages --
 // 0 = none (the caller runs launch_vit_kv_pack), 1 = the split-K reduce (splitk_qkv_vitpack_kernel), 2 = the 128x128 tile epilogue
 template <typename T> bool launch_gemm(hipStream_t s, const GemmArgs& a, int* vit_packer = nullptr);
-template <typename T> int launch_gemm_argmax(hipStream_t s, GemmArgs a);    // EPI_ARGMAX form (M <= 32; EPI_ARGMAX_LSE when a.part_sum is set, EPI_SAMPLE when a.smp.part_raw is); returns the partials per row
+template <typename T> int launch_gemm_argmax(hipStream_t s, GemmArgs a);    // EPI_ARGMAX form (M <= 32; EPI_ARGMAX_LSE when a.part_sum is set, EPI_SAMPLE when a.smp.part_raw is, EPI_TARGET when a.tg.tgt is); returns the partials per row
 
 // y[N] = epi(W[N,K] . x'[K] + bias) + res,  x' = x or rmsnorm(x) * norm_w (fused prologue).
 // EPI_SWIGLU as above (y has N/2 entries).  EPI_ARGMAX: no y; per-workgroup (max, lowest index)
@@ -134,6 +141,7 @@ struct GemvBatchArgs {
     const uint8_t* pen_flags = nullptr; const int* pen_rows = nullptr; float pen = 1.0f;
     float* part_sum = nullptr;    // EPI_ARGMAX_LSE / EPI_SAMPLE: [B][grid] beside part_val
     SampleArgs smp;               // EPI_SAMPLE only (no fused norm: launch_gemv_batched throws)
+    TargetArgs tg;                // EPI_TARGET only (no fused norm, no penalty flags: launch_gemv_batched throws)
     float* row_scale = nullptr;   // EPI_ARGMAX_LSE with norm_w only: [B], the norm's row factor (the arg-max ignores it, the sums are taken on the scaled logits)
 };
 template <typename T> void launch_gemv_batched(hipStream_t s, const GemvBatchArgs& a);
@@ -144,6 +152,10 @@ int gemv_batched_grid(int N, int epi, int B);
 void launch_argmax_final_batched(hipStream_t s, const float* part_val, const int* part_idx, int n, int B, int* out_tokens,
                                  const float* part_sum = nullptr, float* scores = nullptr, const float* row_scale = nullptr,
                                  const float* part_raw = nullptr, const float* part_max = nullptr);
+// the EPI_TARGET merge: row b's partials -> greedy_ids[b] (-1: no finite logit), greedy_logprobs[b] = -log S (the scored form's value)
+// and logprobs[b] = (tgt_val[b] - V) - log S; a row with tgt[b] < 0 gets NaN and tgt_val[b] is not read
+void launch_target_final_batched(hipStream_t s, const float* part_val, const int* part_idx, const float* part_sum, int n, int B, const int* tgt,
+                                 const float* tgt_val, int* greedy_ids, float* greedy_logprobs, float* logprobs);
 // B (1 .. 8) bf16 activation vectors against one MXFP4 weight stream on v_mfma_f32_16x16x32_bf16 (gemv_mx4b.hip; bf16 engine, opt-in):
 // q4 / e8 / ldw as GemvArgs::w4 / e8 / ldw (the layout of the batch-1 GEMVs), x [B][ldx], y [B][ldy], res [B][ldr]; K, ldw multiples of 32,
 // ldx a multiple of 8.  No fused RMSNorm.  EPI_SWIGLU as above.  EPI_ARGMAX: part_val / part_idx are [B][gemv_mx4b_grid(N, epi)], reduced
@@ -193,7 +205,8 @@ struct GemvSubsetArgs {
     const int* ids = nullptr; int n = 0;          // device list
     const void* W = nullptr; int ldw = 0;
     const void* x = nullptr; int ldx = 0;
-    int V = 0, K = 0, B = 0, epi = EPI_ARGMAX;    // EPI_ARGMAX, EPI_ARGMAX_LSE or EPI_SAMPLE
+    int V = 0, K = 0, B = 0, epi = EPI_ARGMAX;    // EPI_ARGMAX, EPI_ARGMAX_LSE, EPI_SAMPLE or EPI_TARGET (the LSE partials on y = v * tg_inv_t: a forced turn under sampling)
+    float tg_inv_t = 1.0f;
     float* part_val = nullptr; int* part_idx = nullptr; float* part_sum = nullptr;
     const uint8_t* pen_flags = nullptr; const int* pen_rows = nullptr; float pen = 1.0f;
     SampleArgs smp;

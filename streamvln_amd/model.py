@@ -551,19 +551,24 @@ class StreamVLNForCausalLM:
 
     @torch.no_grad()
     def generate(self, inputs=None, images=None, image_sizes=None, depths=None, poses=None, intrinsics=None, task_ids=None,
-                 draft_ids=None, **kwargs):
+                 draft_ids=None, forced_ids=None, **kwargs):
         """One model turn = ONE crossing into the engine (svln_turn: encode_rgbd, the KV / embeds bookkeeping of the reference's generate,
         splice, prefill + greedy decode).  draft_ids (optional, set_speculative / set_prefill_draft): a guess of this turn's whole id sequence; with
         set_auto_draft(True) and no explicit draft, the env's previous turn output is the guess.
         While set_token_scores is on the result also carries `token_logprobs`, fp32 [1, n_new] aligned with `sequences` (see there).  HF's
         `output_scores` / `output_logits` stay ignored: a [n_new, vocab] tensor is exactly what this engine exists not to build.
         do_sample=True with num_return_sequences=G, 2 <= G <= 8: a group turn (see _group_result for the result, select_sequence for what
-        must follow); absent or 1: this path, launch for launch; a greedy call leaves the key unread."""
+        must follow); absent or 1: this path, launch for launch; a greedy call leaves the key unread.
+        forced_ids (1 .. 32 ids): a forced turn -- the turn's ids are the caller's (see _generate_forced); `max_new_tokens` is not read."""
         draft = draft_ids
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
         n_seq = self._num_return_sequences(kwargs)
+        if forced_ids is not None and n_seq > 1:
+            raise NotImplementedError("forced_ids with num_return_sequences > 1: a forced turn has one sequence")
         self._sync_call_config()
         self._sync_sampling(kwargs)
+        if forced_ids is not None:
+            return self._generate_forced(forced_ids, inputs, ids, pix, V, n_memory, env_id, past, eos)
         if n_seq > 1:
             return self._generate_group(n_seq, inputs, ids, pix, V, n_memory, env_id, past, max_new, eos)
         # the reference's bookkeeping that needs no engine call: the KV handle must be this env's current one; curr_t counts the turns
@@ -602,6 +607,56 @@ class StreamVLNForCausalLM:
             res["token_logprobs"] = self._scores(self._lib.svln_get_token_scores, n_new=int(seq.shape[1]), device=seq.device)
         return self._allowed(res, "svln_get_allowed_logprobs")
 
+    # ---- forced turns: log-probabilities of given ids in one prefill pass (svln_turn_forced) --------------
+    def _generate_forced(self, forced, inputs, ids, pix, V, n_memory, env_id, past, eos):
+        """generate(..., forced_ids=F): ONE vision pass and ONE prefill pass that also feeds F[:-1]; no decode phase.  The result carries
+        `sequences` = F [1, n], `token_logprobs` fp32 [1, n] (the policy's log-probability of every F[i] given the prompt and F[:i];
+        always present, whatever set_token_scores says), `greedy_ids` int64 [1, n] and `greedy_logprobs` fp32 [1, n] (the policy's own
+        arg-max at every position), with an allowed list `allowed_logprobs` [1, n, n_allowed] / `allowed_token_ids`, and the usual
+        `past_key_values`: the env is where a plain turn that emitted F would have left it."""
+        if past is not None and (not isinstance(past, KVHandle) or past.env_id != env_id or past.epoch != self._epoch[env_id]):
+            raise ValueError("past_key_values does not belong to this env's current window")
+        f_np = np.ascontiguousarray(torch.as_tensor(forced).reshape(-1).to("cpu", torch.int64).numpy())
+        n = int(f_np.size)
+        if not (1 <= n <= 32):
+            raise ValueError(f"forced_ids holds {n} ids: a forced turn takes 1 .. 32")
+        slot = self._slot(env_id)
+        on_dev = int(pix.is_cuda)
+        ids_np = np.ascontiguousarray(ids.numpy())
+        eos_np = np.asarray(eos, dtype=np.int64)
+        lp, glp, gid, kv = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int64), C.c_int32()
+        a = _lib.SvlnTurnArgs()
+        a.pixels, a.n_frames, a.pixels_on_device, a.env = pix.data_ptr(), V, on_dev, slot
+        a.ids, a.n_ids, a.n_memory = ids_np.ctypes.data, ids_np.size, n_memory
+        a.new_window, a.new_episode, a.max_new_tokens = int(past is None), int(self.curr_t[env_id] == 0), n
+        a.eos_ids, a.n_eos = eos_np.ctypes.data, eos_np.size
+        if on_dev:
+            self._order_engine_after(pix)
+        PF, PI = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+        rc = self._lib.svln_turn_forced(self._h, C.byref(a), f_np.ctypes.data_as(PI), n, lp.ctypes.data_as(PF), gid.ctypes.data_as(PI),
+                                        glp.ctypes.data_as(PF), C.byref(kv))
+        if on_dev:
+            self._order_torch_after(pix)
+        _check(rc)
+        self.curr_t[env_id] += 1
+        dev = inputs.device if isinstance(inputs, torch.Tensor) else "cpu"
+        seq = torch.from_numpy(f_np.copy()).unsqueeze(0)
+        if self._auto_draft:
+            self._last_out[env_id] = seq[0].clone()
+        res = GenerateOutput(sequences=seq.to(dev), past_key_values=KVHandle(env_id, self._epoch[env_id], kv.value))
+        res["token_logprobs"] = torch.from_numpy(lp).unsqueeze(0).to(dev)
+        res["greedy_ids"] = torch.from_numpy(gid).unsqueeze(0).to(dev)
+        res["greedy_logprobs"] = torch.from_numpy(glp).unsqueeze(0).to(dev)
+        if self.allowed_token_ids:
+            n_ids = len(self.allowed_token_ids)
+            buf, nt, ni = np.empty(n * n_ids, dtype=np.float32), C.c_int32(), C.c_int32()
+            _check(self._lib.svln_get_allowed_logprobs(self._h, buf.ctypes.data_as(PF), int(buf.size), C.byref(nt), C.byref(ni)))
+            if nt.value != n or ni.value != n_ids:
+                raise RuntimeError(f"the engine holds {nt.value} x {ni.value} allowed log-probabilities for a forced turn of {n} ids over {n_ids} allowed ids")
+            res["allowed_logprobs"] = torch.from_numpy(buf.reshape(1, n, n_ids).copy()).to(dev)
+            res["allowed_token_ids"] = torch.tensor(self.allowed_token_ids, dtype=torch.int64, device=dev)
+        return res
+
     # ---- group sampling: several sampled continuations of one prefill (svln_turn_group) ----------------
     @staticmethod
     def _num_return_sequences(kwargs) -> int:
@@ -617,6 +672,8 @@ class StreamVLNForCausalLM:
 
     @staticmethod
     def _reject_group_request(kwargs, who):
+        if kwargs.get("forced_ids") is not None:
+            raise NotImplementedError(f"forced_ids in a {who} request: forced turns run through generate() only")
         g = kwargs.get("num_return_sequences")
         if g is not None and int(g) > 1:
             raise NotImplementedError(f"num_return_sequences={g!r} in a {who} request: group turns run through generate() only")
