@@ -316,6 +316,21 @@ int svln_set_fp8_decode(svln_engine* h, int enable);
  * is on fails.  Captured decode graphs are dropped when the
  * mode changes; while it is on the launched GEMVs are kept (svln_set_decode_persistent has no effect). */
 int svln_set_mxfp4_decode(svln_engine* h, int enable);
+/* Lossless, no reference counterpart, ON by default on bf16 engines: the single-env decode step's gate/up and down_proj GEMVs and the
+ * lm_head GEMV (the prefill's token included) stream a 12-bit packing of their bf16 weights instead of the bf16 bytes -- per row a table
+ * of the eight most frequent values of the high byte (without the sign), per weight the low byte and a 4-bit code (sign, table index); a
+ * 512-element block that holds a value outside the table is read from the bf16 original.  The decoded weight is the original bit
+ * pattern and the summation order is the bf16 kernel's, so ids, hidden rows and scores are bit-identical with the switch on or off;
+ * about 0.75 x the bytes of those products (svln_packed_stats).  Format: svln_op_pack_rows.  The packed copies are allocated at creation
+ * (~9.4 GB at the 7B size) and re-encoded on the engine stream whenever svln_synth_tensor / svln_set_tensor writes one of the matrices.
+ * q|k|v and o_proj (latency-bound launches), the persistent layer, svln_generate_batch / the scheduler, the verify passes, the
+ * allowed-token head and every GEMM keep the bf16 weights; svln_set_fp8_decode / svln_set_mxfp4_decode read their own copies and take
+ * precedence.  Composes with every other mode.  enable != 0 is refused on fp32 engines (and for hidden / intermediate sizes above 32768);
+ * a change drops the captured decode graphs. */
+int svln_set_packed_decode(svln_engine* h, int enable);
+/* totals over the packed matrices as they are encoded now: bytes of the packed form (blocks + 16-byte row records), bytes of the bf16
+ * originals, 512-element blocks, and the blocks among them that fall back to the bf16 original.  All 0 on an fp32 engine. */
+int svln_packed_stats(svln_engine* h, int64_t* packed_bytes, int64_t* bf16_bytes, int64_t* blocks, int64_t* fallback_blocks);
 /* Opt-in, no reference counterpart: the same MXFP4 weight copies for the envs that svln_generate_batch / svln_batch_step carry.  While it
  * is on, the batched decode step runs q|k|v, o_proj, gate/up and down_proj at every batch size (1, 2, 4, 8) on a weight-only MFMA kernel
  * (bf16 activations x exactly dequantised weights, fp32 accumulate: svln_op_gemv_mxfp4_batched), and every lm_head product of the
@@ -516,6 +531,23 @@ int svln_op_gemv_fp8(svln_engine* h, const void* w8, const float* scale, int ldw
 int svln_op_quant_mxfp4(svln_engine* h, const void* w_bf16, int64_t rows, int cols, void* q4, void* e8);
 int svln_op_gemv_mxfp4(svln_engine* h, const void* q4, const void* e8, int ldw, const void* x, const void* norm_w, float eps, const void* bias,
                        const void* res, void* y, int N, int K, int epi, int32_t* host_token);
+/* TEST-ONLY pieces of svln_set_packed_decode (bf16 engines; device pointers).  For bf16 bits b: lo = b & 0xFF, hi7 = (b >> 8) & 0x7F,
+ * s = b >> 15.  svln_op_pack_rows encodes w_bf16 [rows][cols] (row stride ldw; cols % 8 == 0, cols <= 32768) into
+ *   records [rows][16]: T[0..7] = the row's eight most frequent hi7 values, most frequent first, ties to the lower value, the last entry
+ *       repeated when the row has fewer; then a little-endian 64-bit mask, bit k = block k falls back;
+ *   packed [rows][ceil(cols / 512) * 768]: per block of 512 elements (64 chunks of 8; a ragged last block is zero padded) 512 low bytes
+ *       (chunk l's eight at offset 8 l) and 256 bytes of 4-bit codes c = s << 3 | j, T[j] == hi7, lowest such j (chunk l's dword at
+ *       512 + 4 l: byte k holds element k's code in the low nibble and element k + 4's in the high nibble).  A block with a hi7 outside T
+ *       has its mask bit set and its packed bytes zero.
+ * *fallback_blocks (host, optional) = the number of such blocks.  svln_op_unpack_rows writes the bf16 rows the packed form stands for to
+ * out [rows][cols]: s << 15 | T[j] << 8 | lo, and the bf16 original's bytes for a fallback block.  svln_op_gemv_packed is svln_op_gemv
+ * over such a matrix (W / ldw: the bf16 original); every output is bit-equal to svln_op_gemv on W.  The scored / sampled heads take it as
+ * fmt 3 of svln_op_gemv_argmax_scores / _sample: W = the bf16 original, aux = the N packed rows followed by the N records.
+ * Refused before any launch: an fp32 engine, a null plane, cols / K not a multiple of 8 or above 32768, ldw < K. */
+int svln_op_pack_rows(svln_engine* h, const void* w_bf16, int ldw, int64_t rows, int cols, void* packed, void* records, int64_t* fallback_blocks);
+int svln_op_unpack_rows(svln_engine* h, const void* packed, const void* records, const void* w_bf16, int ldw, int64_t rows, int cols, void* out);
+int svln_op_gemv_packed(svln_engine* h, const void* packed, const void* records, const void* W, int ldw, const void* x, const void* norm_w, float eps,
+                        const void* bias, const void* res, void* y, int N, int K, int epi, int32_t* host_token);
 /* the product behind svln_set_mxfp4_batched: B (1 .. 8) bf16 activation vectors x [B][ldx] against one MXFP4 weight stream (q4 / e8 / ldw
  * as svln_op_gemv_mxfp4: the layout is shared), Y[b][n] = epi(Wq[n] . x[b] + bias[n]) + res[b][n] with y [B][ldy], res [B][ldr]; epi =
  * EPI_NONE, EPI_SWIGLU (y has N / 2 columns) or EPI_ARGMAX (no y: one token per vector to host_tokens[B], lowest index on ties, -1 for a

@@ -141,6 +141,11 @@ SIGNATURES = {
     "svln_set_fp8_scaled_mfma": (_I, [_P, _I]),
     "svln_set_mxfp4_decode": (_I, [_P, _I]),
     "svln_set_mxfp4_batched": (_I, [_P, _I]),
+    "svln_set_packed_decode": (_I, [_P, _I]),
+    "svln_packed_stats": (_I, [_P, _PI64, _PI64, _PI64, _PI64]),
+    "svln_op_pack_rows": (_I, [_P, _P, _I, _I64, _I, _P, _P, _PI64]),
+    "svln_op_unpack_rows": (_I, [_P, _P, _P, _P, _I, _I64, _I, _P]),
+    "svln_op_gemv_packed": (_I, [_P, _P, _P, _P, _I, _P, _P, _F, _P, _P, _P, _I, _I, _I, _PI32]),
     "svln_set_speculative": (_I, [_P, _I]),
     "svln_set_draft": (_I, [_P, _I, _PI64, _I]),
     "svln_draft_stats": (_I, [_P, _PI64, _PI64, _PI64, _I]),

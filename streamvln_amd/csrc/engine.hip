@@ -165,6 +165,10 @@ struct EngineBase {
     virtual void op_gemv_batched(GemvBatchArgs a, int32_t* host_tokens) = 0;
     virtual void op_gemv_mxfp4_batched(GemvMx4BatchArgs a, int32_t* host_tokens) = 0;
     virtual void op_quant_fp8(const void* w, int64_t rows, int cols, void* w8, float* scale) = 0;
+    virtual void set_packed_decode(int enable) = 0;
+    virtual void packed_stats(int64_t* packed_bytes, int64_t* bf16_bytes, int64_t* blocks, int64_t* fallback_blocks) = 0;
+    virtual void op_pack_rows(const void* w, int ldw, int64_t rows, int cols, void* packed, void* rec, int64_t* fallback_blocks) = 0;
+    virtual void op_unpack_rows(const void* packed, const void* rec, const void* w, int ldw, int64_t rows, int cols, void* out) = 0;
     virtual void op_quant_mxfp4(const void* w, int64_t rows, int cols, void* q4, uint8_t* e8) = 0;
     virtual void op_rmsnorm(const void* x, const void* g, void* y, int rows, int n, float eps) = 0;
     virtual void op_layernorm(const void* x, const void* g, const void* b, void* y, int rows, int n, float eps) = 0;
@@ -209,7 +213,13 @@ public:
     struct VLayer { T *ln1_w, *ln1_b, *qkv_w, *qkv_b, *out_w, *out_b, *ln2_w, *ln2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b; };
     struct Q8 { uint8_t* q = nullptr; float* s = nullptr; };      // fp8 (e4m3) copy of a weight matrix + per-row scales (opt-in decode mode)
     struct Q4 { uint8_t* q = nullptr; uint8_t* e8 = nullptr; };   // MXFP4 copy of a weight matrix: E2M1 code pairs + one E8M0 scale byte per 32 (opt-in decode mode)
-    struct LLayer { T *in_norm, *qkv_w, *qkv_b, *o_w, *post_norm, *gu_w, *down_w, *kpool, *vpool; Q8 qkv8, o8, gu8, down8; Q4 qkv4, o4, gu4, down4; };
+    // lossless 12-bit packing of a bf16 weight matrix (svln_set_packed_decode; format: WP12 in gemv.hip): packed blocks, row records, and
+    // the device counter of the blocks that fall back to the bf16 original.  Only the products that gain are packed: gate/up, down_proj
+    // and the lm_head (q|k|v and o_proj are one-latency-round launches: DESIGN.md 4.1).
+    struct P12 { uint8_t* pk = nullptr; uint8_t* rec = nullptr; unsigned* fb = nullptr; const T* w = nullptr; int64_t rows = 0; int cols = 0; };
+    struct LLayer { T *in_norm, *qkv_w, *qkv_b, *o_w, *post_norm, *gu_w, *down_w, *kpool, *vpool; Q8 qkv8, o8, gu8, down8; Q4 qkv4, o4, gu4, down4; P12 gu12, down12; };
+    P12 lm_head12; bool p12_on = false;
+    std::unordered_map<const void*, P12*> p12_of;      // bf16 matrix -> its packed copy: a write of the matrix (synth / set_tensor) re-encodes it
     Q8 lm_head8; bool fp8_on = false, fp8_built = false;
     Q4 lm_head4; bool mx4_on = false, mx4_built = false;
     bool mx4b_on = false;            // opt-in MXFP4 weights in the batched (multi-env) decode step and the scheduler's lm_head: svln_set_mxfp4_batched
@@ -337,7 +347,7 @@ public:
     // envs through svln_generate replays instead of re-capturing); [0] = the whole step, [1] / [2] = the halves around the probed launch
     // (captured only while the roofline probe is on); a run-ahead batch of several steps is one graph.
     bool use_graph = false;
-    struct GraphSet { std::unordered_map<int, hipGraphExec_t> ex; };     // key: steps (whole batch) | 1000 (head of a probed step) | 2000 + steps (its tail) | 3000 + rows (verify pass); + 10000 with svln_set_token_scores
+    struct GraphSet { std::unordered_map<int, hipGraphExec_t> ex; };     // key: steps (whole batch) | 1000 (head of a probed step) | 2000 + steps (its tail) | 3000 + rows (verify pass); + 10000 with svln_set_token_scores, + 20000 with svln_set_sampling, + 40000 with svln_set_packed_decode
     std::vector<GraphSet> graphs;
     std::unordered_map<int, hipGraphExec_t> bgraphs;          // batched decode step: key = B | penalty << 8 | fp8 gemm << 9 | MXFP4 batched << 10 | scaled fp8 form << 11 | token scores << 12
     // per-turn truncation of the spliced rows (the reference's config.tokenizer_model_max_length, stream_video_vln.py:241-244); 0 = none
@@ -447,6 +457,17 @@ public:
         final_norm = dalloc<T>(H); lm_head = dalloc<T>((size_t)V * H);
         add_slot("model.norm.weight", final_norm, H, 1, H);
         add_slot("lm_head.weight", lm_head, H, V, H);
+        if (sizeof(T) == 2 && H <= P12_MAX_K && I <= P12_MAX_K) {      // packed copies of the decode GEMVs' big weight streams; on by default
+            unsigned* counters = dalloc<unsigned>(2 * (size_t)c.layers + 1, true);
+            auto make = [&](P12& m, const T* w, int64_t rows, int cols) {
+                m.pk = dalloc<uint8_t>((size_t)rows * p12_row_bytes(cols)); m.rec = dalloc<uint8_t>((size_t)rows * 16);
+                m.fb = counters++; m.w = w; m.rows = rows; m.cols = cols;
+                p12_of[w] = &m;
+            };
+            for (auto& L : ll) { make(L.gu12, L.gu_w, 2 * (int64_t)I, H); make(L.down12, L.down_w, H, I); }
+            make(lm_head12, lm_head, V, H);
+            p12_on = true;
+        }
 
         // vision workspaces
         const size_t rv = (size_t)c.max_frames * S;
@@ -592,6 +613,16 @@ public:
         Slot& s = slot(name);
         launch_synth<T>(st, s.dst, s.ld, s.rows, s.cols, s.map, seed_t, hw, base);
         s.filled = true;
+        p12_encode(s.dst);
+    }
+    // re-encode the packed copy of the matrix at `dst`, if it has one, on the engine stream (behind the write): the pointers stay, so
+    // captured graphs stay valid
+    void p12_encode(const void* dst) {
+        auto it = p12_of.find(dst);
+        if (it == p12_of.end()) return;
+        const P12& m = *it->second;
+        HIP_CHECK(hipMemsetAsync(m.fb, 0, sizeof(unsigned), st));
+        launch_p12_pack_rows(st, m.w, m.cols, m.pk, m.rec, m.fb, m.rows, m.cols);
     }
     void set_tensor(const char* name, const void* data, int dtype, int64_t numel, int on_device) override {
         Slot& s = slot(name);
@@ -605,6 +636,7 @@ public:
             src = tmp;
         }
         launch_convert<T>(st, s.dst, s.ld, s.rows, s.cols, s.map, src, dtype == SVLN_F32);
+        p12_encode(s.dst);
         HIP_CHECK(hipStreamSynchronize(st));
         if (tmp) HIP_CHECK(hipFree(tmp));
         s.filled = true;
@@ -1168,6 +1200,8 @@ public:
     }
     GemvArgs with8(GemvArgs a, const Q8& q) { if (fp8_on) { a.w8 = q.q; a.scale = q.s; } return a; }
     GemvArgs with4(GemvArgs a, const Q4& q) { if (mx4_on) { a.w4 = q.q; a.e8 = q.e8; } return a; }
+    // the losslessly packed copy (same outputs bit for bit); the e4m3 / MXFP4 modes read their own copies and take precedence
+    GemvArgs with12(GemvArgs a, const P12& m) { if (p12_on && !fp8_on && !mx4_on && m.pk) { a.wp = m.pk; a.prec = m.rec; } return a; }
     GemvArgs guarded(GemvArgs a) { a.skip = &d_ctl->done; return a; }      // decode-step launch: no-op once the generation is done
     // final norm -> hidden tap row -> lm_head arg-max -> d_token  (lm_head on the LAST position only).
     // `gen`: the arg-max also runs one step of the greedy loop on the device (GenCtl: append, EOS / max_new stop, advance the position)
@@ -1189,7 +1223,7 @@ public:
         } else {
             launch_rmsnorm<T>(st, xrow, final_norm, tap, 1, H, c.rms_eps, skip);
         }
-        GemvArgs a = with4(with8(gemv_args(lm_head, H, tap, nullptr, nullptr, nullptr, nullptr, V, H, smp_on ? EPI_SAMPLE : scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX), lm_head8), lm_head4);
+        GemvArgs a = with12(with4(with8(gemv_args(lm_head, H, tap, nullptr, nullptr, nullptr, nullptr, V, H, smp_on ? EPI_SAMPLE : scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX), lm_head8), lm_head4), lm_head12);
         a.skip = skip;
         const bool pen = gen && rep_penalty != 1.0f;
         if (pen) { a.pen_flags = pen_flags; a.pen = rep_penalty; }
@@ -1295,8 +1329,8 @@ public:
             if (on()) launch_attention<T>(st, a, 128, 1);
             if (on()) launch_attention_combine<T>(st, a, 128);
             if (on()) launch_gemv<T>(st, guarded(with4(with8(gemv_args(L.o_w, qd, attn, nullptr, nullptr, x, x, H, qd, EPI_NONE), L.o8), L.o4)));
-            if (on()) launch_gemv<T>(st, guarded(with4(with8(gemv_args(L.gu_w, H, x, L.post_norm, nullptr, nullptr, hbuf, 2 * I, H, EPI_SWIGLU), L.gu8), L.gu4)));
-            if (on()) launch_gemv<T>(st, guarded(with4(with8(gemv_args(L.down_w, I, hbuf, nullptr, nullptr, x, x, H, I, EPI_NONE), L.down8), L.down4)));
+            if (on()) launch_gemv<T>(st, guarded(with12(with4(with8(gemv_args(L.gu_w, H, x, L.post_norm, nullptr, nullptr, hbuf, 2 * I, H, EPI_SWIGLU), L.gu8), L.gu4), L.gu12)));
+            if (on()) launch_gemv<T>(st, guarded(with12(with4(with8(gemv_args(L.down_w, I, hbuf, nullptr, nullptr, x, x, H, I, EPI_NONE), L.down8), L.down4), L.down12)));
         }
     }
 
@@ -1304,7 +1338,7 @@ public:
     void probe_launch(Env&) {
         const LLayer& L = ll[0];
         if (persistent_active()) launch_decode_layer<T>(st, layer_args(0), n_cus, probe_ev[probe_used], probe_ev[probe_used + 1]);
-        else launch_gemv_timed<T>(st, guarded(with4(with8(gemv_args(L.gu_w, H, x, L.post_norm, nullptr, nullptr, hbuf, 2 * I, H, EPI_SWIGLU), L.gu8), L.gu4)),
+        else launch_gemv_timed<T>(st, guarded(with12(with4(with8(gemv_args(L.gu_w, H, x, L.post_norm, nullptr, nullptr, hbuf, 2 * I, H, EPI_SWIGLU), L.gu8), L.gu4), L.gu12)),
                                   probe_ev[probe_used], probe_ev[probe_used + 1]);
         probe_used += 2;
     }
@@ -1356,7 +1390,7 @@ public:
         const bool probing = probe_on && first_tap_row == 1 && probe_used + 2 <= probe_ev.size();
         if (use_graph) {
             GraphSet& gs = graphs[env];
-            const int sk = (scores_on ? 10000 : 0) + (smp_on ? 20000 : 0);      // the captured head is the plain, the scored or the sampled one
+            const int sk = (scores_on ? 10000 : 0) + (smp_on ? 20000 : 0) + (p12_on ? 40000 : 0);      // the captured head is the plain, the scored or the sampled one; the GEMVs read the packed weights or not
             auto get = [&](int key, int lo, int hi, int more) {
                 auto it = gs.ex.find(key);
                 if (it == gs.ex.end()) it = gs.ex.emplace(key, capture(e, lo, hi, more)).first;
@@ -2972,6 +3006,29 @@ public:
         if (!mx4_on) drop_graphs();
         mx4_on = true;
     }
+    // Lossless (no reference counterpart; same ids and hidden rows bit for bit): the single-env decode step's gate/up and down_proj GEMVs and
+    // head()'s lm_head GEMV stream the 12-bit packing of their bf16 weights (gemv.hip, WP12) -- about 0.75 x the bytes.  The copies are
+    // allocated at creation and encoded whenever a matrix is written.  On by default on the bf16 engine; the e4m3 / MXFP4 decode modes take
+    // precedence, and the persistent layer, the batched and verify passes, the subset head and every GEMM keep the bf16 weights.
+    void set_packed_decode(int enable) override {
+        const bool want = enable != 0;
+        REQUIRE(!want || sizeof(T) == 2, "svln_set_packed_decode: the packed weights are a bf16 format; the fp32 engine has none");
+        REQUIRE(!want || lm_head12.pk, "svln_set_packed_decode: hidden or intermediate size above 32768: no packed copies exist");
+        if (want == p12_on) return;
+        drop_graphs();
+        p12_on = want;
+    }
+    void packed_stats(int64_t* packed_bytes, int64_t* bf16_bytes, int64_t* blocks, int64_t* fallback_blocks) override {
+        HIP_CHECK(hipStreamSynchronize(st));
+        int64_t pb = 0, bb = 0, nb = 0, fb = 0;
+        for (auto& kv : p12_of) {
+            const P12& m = *kv.second;
+            unsigned f = 0;
+            HIP_CHECK(hipMemcpy(&f, m.fb, sizeof(unsigned), hipMemcpyDeviceToHost));
+            pb += m.rows * (int64_t)(p12_row_bytes(m.cols) + 16); bb += m.rows * (int64_t)m.cols * 2; nb += m.rows * (int64_t)((m.cols + 511) / 512); fb += f;
+        }
+        *packed_bytes = pb; *bf16_bytes = bb; *blocks = nb; *fallback_blocks = fb;
+    }
     // Opt-in (no reference counterpart): the batched decode step of svln_generate_batch / svln_batch_step (q|k|v, o_proj, gate/up and
     // down_proj at every B) and every lm_head product of the scheduler read the MXFP4 copies above through gemv_mx4b_kernel (weight-only:
     // bf16 activations on the MFMA path); prefill rows keep the bf16 products, and an iteration that holds decode rows and prefill rows is
@@ -3053,6 +3110,12 @@ public:
         probe_used = 0; probe_on = true; pprobe_used = 0; pprobe_rows = 0;
         probe_bytes = (double)2 * I * H * sizeof(T);
         if (mx4_on) probe_bytes = (double)2 * I * (H / 2) + (double)2 * I * (H / 32);                // E2M1 code pairs + E8M0 scale bytes
+        else if (!fp8_on && p12_on && ll[0].gu12.pk) {      // what the probed launch streams: packed blocks + records + the fallback blocks' bf16 bytes
+            unsigned f = 0;
+            HIP_CHECK(hipStreamSynchronize(st));
+            HIP_CHECK(hipMemcpy(&f, ll[0].gu12.fb, sizeof(unsigned), hipMemcpyDeviceToHost));
+            probe_bytes = (double)2 * I * (double)(p12_row_bytes(H) + 16) + (double)f * 1024.0;
+        }
         // persistent layer: the four products one launch streams (o, gate/up, down, the next layer's q|k|v)
         if (persistent_active()) probe_bytes = ((double)H * nq * 128 + (double)2 * I * H + (double)H * I + (double)qkv_dim * H) * sizeof(T);
     }
@@ -3109,9 +3172,45 @@ public:
         LAUNCH_CHECK("op_gemm");
         return fused;
     }
+    // the packed (P12) form of a test GEMV: both planes and the bf16 original, the bf16 engine, K inside the 64-block mask
+    void p12_refusals(const GemvArgs& a) {
+        if (!a.wp && !a.prec) return;
+        REQUIRE(sizeof(T) == 2, "packed weights need the bf16 engine");
+        REQUIRE(a.wp && a.prec && a.W, "null pointer (packed blocks, row records and the bf16 original are all needed)");
+        REQUIRE(!a.w4 && !a.w8, "one weight format per call");
+        REQUIRE(a.K % 8 == 0, "K must be a multiple of 8");
+        REQUIRE(a.K <= P12_MAX_K, "packed weights: K above 32768 (64 blocks of 512 per row)");
+    }
+    void op_pack_rows(const void* w, int ldw, int64_t rows, int cols, void* packed, void* rec, int64_t* fallback_blocks) override {
+        REQUIRE(sizeof(T) == 2, "packed weights need the bf16 engine");
+        REQUIRE(w && packed && rec, "null pointer");
+        REQUIRE(rows >= 0 && rows <= 0x7FFFFFFF && cols >= 8 && cols % 8 == 0, "cols must be a positive multiple of 8");
+        REQUIRE(cols <= P12_MAX_K, "packed weights: more than 32768 columns (64 blocks of 512 per row)");
+        REQUIRE(ldw >= cols && ldw % 8 == 0, "ldw >= cols, a multiple of 8 (aligned row loads)");
+        unsigned* cnt = nullptr;
+        HIP_CHECK(hipMalloc((void**)&cnt, sizeof(unsigned)));
+        HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(unsigned), st));
+        if (rows > 0) launch_p12_pack_rows(st, w, ldw, packed, rec, cnt, rows, cols);
+        unsigned f = 0;
+        HIP_CHECK(hipMemcpyAsync(&f, cnt, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        sync();
+        HIP_CHECK(hipFree(cnt));
+        LAUNCH_CHECK("op_pack_rows");
+        if (fallback_blocks) *fallback_blocks = f;
+    }
+    void op_unpack_rows(const void* packed, const void* rec, const void* w, int ldw, int64_t rows, int cols, void* out) override {
+        REQUIRE(sizeof(T) == 2, "packed weights need the bf16 engine");
+        REQUIRE(w && packed && rec && out, "null pointer");
+        REQUIRE(rows >= 0 && rows <= 0x7FFFFFFF && cols >= 8 && cols % 8 == 0 && cols <= P12_MAX_K, "cols: a positive multiple of 8, at most 32768");
+        REQUIRE(ldw >= cols && ldw % 8 == 0, "ldw >= cols, a multiple of 8 (aligned row loads)");
+        if (rows > 0) launch_p12_unpack_rows(st, packed, rec, w, ldw, out, cols, rows, cols);
+        sync();
+        LAUNCH_CHECK("op_unpack_rows");
+    }
     void op_gemv(GemvArgs a, int32_t* host_token) override {
         REQUIRE(a.w8 == nullptr || sizeof(T) == 2, "fp8 weights need the bf16 engine");
         REQUIRE(a.w4 == nullptr || sizeof(T) == 2, "MXFP4 weights need the bf16 engine");
+        p12_refusals(a);
         // refusals before launch, the same for every weight format: `chunk` = weights per 16-byte load of the format
         const int chunk = a.w4 ? 32 : a.w8 ? 16 : Elt<T>::PER_CHUNK;
         REQUIRE(a.x && (a.w4 ? a.e8 != nullptr : a.w8 ? a.scale != nullptr : a.W != nullptr), "null pointer");
@@ -3136,6 +3235,7 @@ public:
     void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob, const OpSample* smp) override {
         REQUIRE(a.w8 == nullptr || sizeof(T) == 2, "fp8 weights need the bf16 engine");
         REQUIRE(a.w4 == nullptr || sizeof(T) == 2, "MXFP4 weights need the bf16 engine");
+        p12_refusals(a);
         const int chunk = a.w4 ? 32 : a.w8 ? 16 : Elt<T>::PER_CHUNK;
         REQUIRE(a.x && host_token && (a.w4 ? a.e8 != nullptr : a.w8 ? a.scale != nullptr : a.W != nullptr), "null pointer");
         REQUIRE(a.N >= 1 && a.K >= chunk && a.K % chunk == 0, "N >= 1, K a positive multiple of the format's 16-byte chunk");
@@ -3762,12 +3862,16 @@ int svln_generate_batch_scores(svln_engine* h, int index, float* out, int cap, i
 static int op_gemv_argmax_any(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
                               float penalty, int32_t* host_token, float* host_logprob, const OpSample* smp) {
     API_BEGIN_H
-    REQUIRE(fmt >= 0 && fmt <= 2, "fmt: 0 = engine dtype, 1 = e4m3 + row scales, 2 = MXFP4");
+    REQUIRE(fmt >= 0 && fmt <= 3, "fmt: 0 = engine dtype, 1 = e4m3 + row scales, 2 = MXFP4, 3 = 12-bit packing");
     GemvArgs a; a.W = nullptr; a.ldw = ldw; a.x = x; a.norm_w = nullptr; a.eps = 0.0f; a.bias = nullptr; a.res = nullptr; a.y = nullptr; a.N = N; a.K = K;
     a.epi = EPI_ARGMAX; a.part_val = nullptr; a.part_idx = nullptr; a.w8 = nullptr; a.scale = nullptr; a.skip = nullptr;
     if (fmt == 0) a.W = W;
     else if (fmt == 1) { a.w8 = W; a.scale = (const float*)aux; }
-    else { a.w4 = W; a.e8 = (const uint8_t*)aux; }
+    else if (fmt == 2) { a.w4 = W; a.e8 = (const uint8_t*)aux; }
+    else {      // W = the bf16 original, aux = the N packed rows followed by the N row records
+        REQUIRE(aux && K >= 0 && N >= 0, "null pointer");
+        a.W = W; a.wp = aux; a.prec = (const uint8_t*)aux + (size_t)N * p12_row_bytes(K);
+    }
     REQUIRE(W, "null pointer");
     a.pen_flags = (const uint8_t*)pen_flags; a.pen = penalty;
     h->impl->op_gemv_scores(a, host_token, host_logprob, smp);
@@ -3899,6 +4003,28 @@ int svln_set_fp8_decode(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_f
 int svln_set_fp8_gemm(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_fp8_gemm(enable); API_END }
 int svln_set_fp8_scaled_mfma(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_fp8_scaled_mfma(enable); API_END }
 int svln_set_mxfp4_decode(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_mxfp4_decode(enable); API_END }
+int svln_set_packed_decode(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_packed_decode(enable); API_END }
+int svln_packed_stats(svln_engine* h, int64_t* packed_bytes, int64_t* bf16_bytes, int64_t* blocks, int64_t* fallback_blocks) {
+    API_BEGIN_H
+    REQUIRE(packed_bytes && bf16_bytes && blocks && fallback_blocks, "null output pointer");
+    h->impl->packed_stats(packed_bytes, bf16_bytes, blocks, fallback_blocks);
+    API_END
+}
+int svln_op_pack_rows(svln_engine* h, const void* w_bf16, int ldw, int64_t rows, int cols, void* packed, void* records, int64_t* fallback_blocks) {
+    API_BEGIN_H h->impl->op_pack_rows(w_bf16, ldw, rows, cols, packed, records, fallback_blocks); API_END
+}
+int svln_op_unpack_rows(svln_engine* h, const void* packed, const void* records, const void* w_bf16, int ldw, int64_t rows, int cols, void* out) {
+    API_BEGIN_H h->impl->op_unpack_rows(packed, records, w_bf16, ldw, rows, cols, out); API_END
+}
+int svln_op_gemv_packed(svln_engine* h, const void* packed, const void* records, const void* W, int ldw, const void* x, const void* norm_w, float eps,
+                        const void* bias, const void* res, void* y, int N, int K, int epi, int32_t* host_token) {
+    API_BEGIN_H
+    if (!packed || !records || !W) throw std::runtime_error("null pointer (packed blocks, row records and the bf16 original are all needed)");
+    GemvArgs a; a.W = W; a.ldw = ldw; a.x = x; a.norm_w = norm_w; a.eps = eps; a.bias = bias; a.res = res; a.y = y; a.N = N; a.K = K; a.epi = epi;
+    a.part_val = nullptr; a.part_idx = nullptr; a.w8 = nullptr; a.scale = nullptr; a.skip = nullptr; a.wp = packed; a.prec = records;
+    h->impl->op_gemv(a, host_token);
+    API_END
+}
 int svln_set_mxfp4_batched(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_mxfp4_batched(enable); API_END }
 int svln_set_speculative(svln_engine* h, int rows) { API_BEGIN_H h->impl->set_speculative(rows); API_END }
 int svln_set_draft(svln_engine* h, int env, const int64_t* ids, int n) { API_BEGIN_H h->impl->set_draft(env, ids, n); API_END }

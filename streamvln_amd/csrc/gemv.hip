@@ -1,7 +1,7 @@
 // Decode-path GEMV  y[N] = epi(W[N,K] . x'[K] + bias) + res  -- the HBM-bound weight stream that
 // dominates a batch-1 action-token decode (14.1 GB of bf16 weights per token).
 //
-// Two kernels, each written once over a WEIGHT-FORMAT POLICY (WPlain<T>, WE4m3, WMxfp4 below):
+// Two kernels, each written once over a WEIGHT-FORMAT POLICY (WPlain<T>, WE4m3, WMxfp4, WP12 below):
 //   gemv_rows_kernel<P, EPI>         256-thread workgroups; the activation vector is staged ONCE per workgroup into LDS as fp32 (with a
 //       fused RMSNorm the copy holds g * x and rsqrt(mean x^2 + eps) is applied once per output in the epilogue: one pass over x, one
 //       barrier), then every wave streams whole weight rows straight HBM -> VGPR with 16-byte loads (lane i takes chunks i, i+64, ... of
@@ -41,6 +41,7 @@ constexpr int GEMV_WAVES = GEMV_THREADS / 64;
 //   Acc, zero(), fma(chunk, x2, acc), sum(acc)   the accumulator and the chunk . x step (x2[k]: activations 2k, 2k + 1 under the chunk, fp32)
 //   row_scale(p, n)  factor applied to row n's dot product after the reduction
 //   X_LATE           row kernel: load the second chunk's activations only after the first chunk's products
+//   ROWS_GRID_CAP    row kernel without arg-max: most workgroups of a launch (0: gemv_grid alone decides)
 //   KS_R, KS_KW_NARROW, KS_PAIRED   K-split kernel: rows per row group; waves on K when K <= 4096 (4 above: see launch_gemv_fmt);
 //                    two chunks per row in flight in the un-normalised form
 // The per-format values of the last four are measured choices, not noise: keep them when touching a policy.
@@ -53,6 +54,7 @@ template <typename T> struct WPlain {
     using Chunk = uint4;
     using Acc = float;
     static constexpr bool X_LATE = false;
+    static constexpr int ROWS_GRID_CAP = 0;
     static constexpr int KS_R = 2;                  // (R = 4 / 8 measured slower at N <= 8192)
     static constexpr int KS_KW_NARROW = 4;
     static constexpr bool KS_PAIRED = true;         // two chunks per row in flight without the norm, one with it: both as measured
@@ -86,6 +88,7 @@ struct WE4m3 : WPacked {
     struct Row { const uint8_t* w; };
     using Chunk = uint4;
     static constexpr bool X_LATE = false;
+    static constexpr int ROWS_GRID_CAP = 0;
     static constexpr int KS_R = 4;
     static constexpr int KS_KW_NARROW = 4;
     static constexpr bool KS_PAIRED = false;
@@ -114,6 +117,7 @@ struct WMxfp4 : WPacked {
     struct Row { const uint8_t* q; const uint8_t* s; };
     struct Chunk { uint4 q; unsigned s; };
     static constexpr bool X_LATE = true;            // register pressure: the row kernels sit at 163-179 VGPRs
+    static constexpr int ROWS_GRID_CAP = 0;
     static constexpr int KS_R = 4;
     static constexpr int KS_KW_NARROW = 2;          // a row of K = 3584 is only 112 blocks, fewer than two waves' worth of lanes
     static constexpr bool KS_PAIRED = false;
@@ -132,6 +136,97 @@ struct WMxfp4 : WPacked {
             acc = __builtin_elementwise_fma((f32x2)__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(d[q], sc, 3), x2[4 * q + 3], acc);
         }
     }
+    SVLN_DEV static float row_scale(const GemvArgs&, size_t) { return 1.0f; }
+};
+
+// Lossless 12-bit packing of bf16 weights ("P12", svln_set_packed_decode; on by default for the products listed there).  The high
+// byte of a bf16 weight (sign, top seven exponent bits) takes few values within one row; the low byte is incompressible.  For bits
+// b = s | E[7:0] | m[6:0]:  lo = b & 0xFF, hi7 = (b >> 8) & 0x7F, s = b >> 15.
+//   row record, 16 bytes:  T[0..7] -- the row's eight most frequent hi7 values, most frequent first, ties to the lower value, a row with
+//       fewer distinct values repeats its last entry -- then a 64-bit mask, bit k = block k of the row "falls back" (K <= 32768).
+//   block = 512 consecutive elements = the 64 chunks one wave instruction covers in both kernels; 768 contiguous bytes:
+//       [0, 512)    low bytes: lane l's elements 8 l .. 8 l + 7 at offset 8 l
+//       [512, 768)  4-bit codes c = s << 3 | j with T[j] == hi7 (the lowest such j): lane l's dword at offset 512 + 4 l; byte k of that
+//                   dword holds element k's code in its LOW nibble and element k + 4's in its HIGH nibble (k = 0 .. 3), so that
+//                   x & 0x07070707 and (x >> 4) & 0x07070707 are the v_perm_b32 selectors of elements 0 .. 3 and 4 .. 7 into T.
+//   A block with an element whose hi7 is not in T has its mask bit set and packed bytes zero; it is read from the bf16 original
+//   (W / ldw, resident for prefill anyway).  Which of the two a wave reads is known from the record before any load of the row.
+//   A ragged last block (K % 512 != 0) is zero padded; the packed row stride is ceil(K / 512) * 768 bytes.
+// Decoding is s << 15 | T[j] << 8 | lo: the original bit pattern, whatever it means (NaN, Inf, -0, denormals).  The lane -> chunk
+// assignment, EPC and the fmaf chain are WPlain<bf16>'s, so every output is bit-equal to the bf16 kernel's.
+// v_perm_b32(hi, lo, sel): selector bytes 0 .. 3 pick bytes of `lo`, 4 .. 7 of `hi`, 12 is 0x00.
+// The high bytes s << 7 | T[j] of elements 0 .. 3 (ha) and 4 .. 7 (hb) of a chunk from its code dword and the table t0 = T[0..3], t1 = T[4..7]
+SVLN_DEV void p12_high_bytes(unsigned c, unsigned t0, unsigned t1, unsigned& ha, unsigned& hb) {
+    ha = __builtin_amdgcn_perm(t1, t0, c & 0x07070707u) | ((c << 4) & 0x80808080u);
+    hb = __builtin_amdgcn_perm(t1, t0, (c >> 4) & 0x07070707u) | (c & 0x80808080u);
+}
+// the chunk as 8 bf16 (TEST-ONLY decoder) ...
+SVLN_DEV uint4 p12_decode(unsigned lo0, unsigned lo1, unsigned c, unsigned t0, unsigned t1) {
+    unsigned ha, hb;
+    p12_high_bytes(c, t0, t1, ha, hb);
+    return make_uint4(__builtin_amdgcn_perm(ha, lo0, 0x05010400u), __builtin_amdgcn_perm(ha, lo0, 0x07030602u),
+                      __builtin_amdgcn_perm(hb, lo1, 0x05010400u), __builtin_amdgcn_perm(hb, lo1, 0x07030602u));
+}
+// ... and as the 8 floats chunk_to_f32<bf16> makes of those (bits hi << 24 | lo << 16): one v_perm_b32 per weight, no conversion
+SVLN_DEV void p12_decode_f32(unsigned lo0, unsigned lo1, unsigned c, unsigned t0, unsigned t1, float* f) {
+    unsigned ha, hb;
+    p12_high_bytes(c, t0, t1, ha, hb);
+    f[0] = __uint_as_float(__builtin_amdgcn_perm(ha, lo0, 0x04000C0Cu)); f[1] = __uint_as_float(__builtin_amdgcn_perm(ha, lo0, 0x05010C0Cu));
+    f[2] = __uint_as_float(__builtin_amdgcn_perm(ha, lo0, 0x06020C0Cu)); f[3] = __uint_as_float(__builtin_amdgcn_perm(ha, lo0, 0x07030C0Cu));
+    f[4] = __uint_as_float(__builtin_amdgcn_perm(hb, lo1, 0x04000C0Cu)); f[5] = __uint_as_float(__builtin_amdgcn_perm(hb, lo1, 0x05010C0Cu));
+    f[6] = __uint_as_float(__builtin_amdgcn_perm(hb, lo1, 0x06020C0Cu)); f[7] = __uint_as_float(__builtin_amdgcn_perm(hb, lo1, 0x07030C0Cu));
+}
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+struct WP12 {
+    using X = bf16;
+    static constexpr int EPC = 8;
+    // (table and mask are wave-uniform: they live in scalar registers, and the fallback decisions are scalar selects and branches)
+    struct Row { const uint8_t* pk; const bf16* w; unsigned t0, t1, m0, m1; };
+    // packed: a = the 8 low bytes, b = the aligned 8 bytes that hold the lane's code dword (lanes 2 k and 2 k + 1 read the same 8: an
+    // 8-byte load on an address of its own instead of a 4-byte one).  Fallback (fb): a, b = bytes 0 .. 7, 8 .. 15 of the bf16 chunk.  Both
+    // forms issue the SAME two loads on selected addresses, nothing behind a branch: a conditional load into registers the other form also
+    // writes makes the compiler wait for every load in flight first, and any conditional load makes its count of them a lower bound.
+    struct Chunk { u32x2 a, b; unsigned t0, t1; bool fb, odd; };
+    using Acc = float;
+    static constexpr bool X_LATE = false;
+    // 103-120 VGPRs: four workgroups per CU are resident.  With gate/up's 1184 workgroups the last 160 ran as a second round of a kernel
+    // that is not bandwidth-bound (41.3 us per launch; 1024: 39.0 us alone, 40.5 against 43.3 in the decode step: DESIGN.md 4.1)
+    static constexpr int ROWS_GRID_CAP = 1024;
+    static constexpr int KS_R = 2;                  // the bf16 policy's K-split geometry: the lane -> chunk assignment is part of the bit-equality contract
+    static constexpr int KS_KW_NARROW = 4;
+    static constexpr bool KS_PAIRED = true;
+    // a wave-uniform byte offset, said so (scalar base + lane offset addressing).  The offset, not the pointer: a pointer rebuilt from
+    // integers loses its address space, and every load through it becomes a flat load that also counts as an LDS operation
+    SVLN_DEV static size_t uniform(size_t v) {
+        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+        return ((size_t)hi << 32) | lo;
+    }
+    SVLN_DEV static Row row(const GemvArgs& p, size_t n) {
+        const uint4 rec = *(const uint4*)((const uint8_t*)p.prec + n * 16);
+        return {(const uint8_t*)p.wp + uniform(n * p12_row_bytes(p.K)), (const bf16*)p.W + uniform(n * (size_t)p.ldw),
+                (unsigned)__builtin_amdgcn_readfirstlane((int)rec.x), (unsigned)__builtin_amdgcn_readfirstlane((int)rec.y),
+                (unsigned)__builtin_amdgcn_readfirstlane((int)rec.z), (unsigned)__builtin_amdgcn_readfirstlane((int)rec.w)};
+    }
+    SVLN_DEV static Chunk load(const Row& r, int ci) {          // (ci = lane + a multiple of 64 in both kernels: the block is wave-uniform)
+        const int blk = __builtin_amdgcn_readfirstlane(ci >> 6);
+        const unsigned l = (unsigned)ci & 63u;
+        Chunk c; c.t0 = r.t0; c.t1 = r.t1; c.odd = l & 1u;
+        c.fb = (((blk & 32) ? r.m1 : r.m0) >> (blk & 31)) & 1u;
+        const uint8_t* wb = (const uint8_t*)r.w + (size_t)blk * 1024;
+        const uint8_t* pb = r.pk + (size_t)blk * 768;
+        c.a = __builtin_nontemporal_load((const u32x2*)((c.fb ? wb : pb) + (l << (c.fb ? 4 : 3))));
+        c.b = __builtin_nontemporal_load((const u32x2*)((c.fb ? wb + 8 : pb + 512) + (c.fb ? l << 4 : (l >> 1) << 3)));
+        return c;
+    }
+    SVLN_DEV static Acc zero() { return 0.0f; }
+    SVLN_DEV static void fma(const Chunk& w, const f32x2* x2, Acc& acc) {
+        float f[EPC];
+        if (w.fb) chunk_to_f32<bf16>(make_uint4(w.a.x, w.a.y, w.b.x, w.b.y), f);
+        else p12_decode_f32(w.a.x, w.a.y, w.odd ? w.b.y : w.b.x, w.t0, w.t1, f);
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) acc = fmaf(f[e], x2[e / 2][e % 2], acc);
+    }
+    SVLN_DEV static float sum(Acc a) { return a; }
     SVLN_DEV static float row_scale(const GemvArgs&, size_t) { return 1.0f; }
 };
 
@@ -828,6 +923,93 @@ __global__ __launch_bounds__(256) void quant_mxfp4_rows_kernel(const bf16* w, in
     }
 }
 
+// P12 encoder (format: WP12 above): one workgroup per row.  Histogram of hi7 in LDS; bin i's rank = the bins that beat it (greater count,
+// or the same count and a lower value); ranks 0 .. 7 with a non-zero count are the table; then wave w packs blocks w, w + 4, ...: a
+// block with a miss anywhere (wave vote) sets its mask bit, writes zeros and counts into *fb_count (one atomic per row).
+__global__ __launch_bounds__(256) void p12_pack_rows_kernel(const bf16* w, int ld, uint8_t* packed, uint8_t* rec, unsigned* fb_count, int cols) {
+    __shared__ unsigned hist[128];
+    __shared__ unsigned char code[128];
+    __shared__ unsigned tab[8], mask[2], nfb;
+    const size_t row = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nch = cols / 8, nblk = (cols + 511) / 512;
+    const bf16* wr = w + row * ld;
+    uint8_t* pr = packed + row * p12_row_bytes(cols);
+    if (tid < 128) hist[tid] = 0;
+    if (tid < 8) tab[tid] = 0xFFFFFFFFu;
+    if (tid < 2) mask[tid] = 0;
+    if (tid == 0) nfb = 0;
+    __syncthreads();
+    for (int ci = tid; ci < nch; ci += 256) {
+        const uint4 v = *(const uint4*)(wr + (size_t)ci * 8);
+        const unsigned d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { atomicAdd(&hist[(d[q] >> 8) & 0x7F], 1u); atomicAdd(&hist[(d[q] >> 24) & 0x7F], 1u); }
+    }
+    __syncthreads();
+    if (tid < 128 && hist[tid] > 0) {
+        int rank = 0;
+        for (int j = 0; j < 128; ++j) rank += hist[j] > hist[tid] || (hist[j] == hist[tid] && j < tid);
+        if (rank < 8) tab[rank] = (unsigned)tid;
+    }
+    __syncthreads();
+    if (tid == 0)                                   // fewer than eight distinct values: the last entry repeats (entry 0 exists: cols >= 8)
+        for (int j = 1; j < 8; ++j) if (tab[j] == 0xFFFFFFFFu) tab[j] = tab[j - 1];
+    __syncthreads();
+    if (tid < 128) {
+        unsigned c = 0xFF;
+        for (int j = 7; j >= 0; --j) if (tab[j] == (unsigned)tid) c = (unsigned)j;      // the lowest j of a repeated entry
+        code[tid] = (unsigned char)c;
+    }
+    __syncthreads();
+    for (int blk = wave; blk < nblk; blk += 4) {
+        const int ci = blk * 64 + lane;
+        unsigned lo0 = 0, lo1 = 0, cd = 0;
+        bool miss = false;
+        if (ci < nch) {
+            const uint4 v = *(const uint4*)(wr + (size_t)ci * 8);
+            const unsigned d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const unsigned b = (d[e / 2] >> (16 * (e % 2))) & 0xFFFFu;
+                const unsigned c = code[(b >> 8) & 0x7F];
+                miss |= c == 0xFF;
+                if (e < 4) lo0 |= (b & 0xFF) << (8 * e); else lo1 |= (b & 0xFF) << (8 * (e - 4));
+                cd |= (((b >> 15) << 3) | (c & 7)) << (8 * (e & 3) + 4 * (e >> 2));
+            }
+        }
+        const bool fb = __ballot(miss) != 0;
+        if (fb) { lo0 = lo1 = cd = 0; }
+        *(uint2*)(pr + (size_t)blk * 768 + 8 * lane) = make_uint2(lo0, lo1);
+        *(unsigned*)(pr + (size_t)blk * 768 + 512 + 4 * lane) = cd;
+        if (fb && lane == 0) { atomicOr(&mask[blk >> 5], 1u << (blk & 31)); atomicAdd(&nfb, 1u); }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        *(uint4*)(rec + row * 16) = make_uint4(tab[0] | tab[1] << 8 | tab[2] << 16 | tab[3] << 24, tab[4] | tab[5] << 8 | tab[6] << 16 | tab[7] << 24,
+                                               mask[0], mask[1]);
+        if (fb_count && nfb) atomicAdd(fb_count, nfb);
+    }
+}
+// TEST-ONLY: the bf16 rows a P12 matrix stands for -- p12_decode on the packed blocks, the bf16 original on the fallback blocks
+__global__ __launch_bounds__(256) void p12_unpack_rows_kernel(const uint8_t* packed, const uint8_t* rec, const bf16* w, int ld, bf16* out, int ldo,
+                                                              int cols) {
+    const size_t row = blockIdx.x;
+    const uint4 r = *(const uint4*)(rec + row * 16);
+    const uint8_t* pr = packed + row * p12_row_bytes(cols);
+    for (int ci = threadIdx.x; ci < cols / 8; ci += 256) {
+        const int blk = ci >> 6, l = ci & 63;
+        uint4 v;
+        if ((((blk & 32) ? r.w : r.z) >> (blk & 31)) & 1u) {
+            v = *(const uint4*)(w + row * ld + (size_t)ci * 8);
+        } else {
+            const uint2 lo = *(const uint2*)(pr + (size_t)blk * 768 + 8 * l);
+            v = p12_decode(lo.x, lo.y, *(const unsigned*)(pr + (size_t)blk * 768 + 512 + 4 * l), r.x, r.y);
+        }
+        *(uint4*)(out + row * ldo + (size_t)ci * 8) = v;
+    }
+}
+
 // final arg-max over per-workgroup partials: greatest value, lowest index on ties (torch.argmax on CPU)
 // With `ctl` it is also one step of the greedy loop (GenerationMixin._sample: append, stop on EOS / max_new_tokens): see GenCtl.
 // LSE: also the token's log-probability from the partial sums ps, to scores[ctl->count] before the count advances (scores[0] without ctl)
@@ -930,6 +1112,8 @@ template <typename P> static void launch_gemv_fmt(hipStream_t s, const GemvArgs&
     }
     const size_t lds = (size_t)a.K * sizeof(float);
     dim3 g(gemv_grid(a.N)), b(GEMV_THREADS);
+    // (the arg-max forms keep gemv_grid: the number of partials is part of their contract with the final kernels)
+    if (P::ROWS_GRID_CAP && !epi_is_argmax(a.epi) && g.x > (unsigned)P::ROWS_GRID_CAP) g.x = P::ROWS_GRID_CAP;
     switch (a.epi) {
         case EPI_NONE: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_NONE>), g, b, lds); break;
         case EPI_SWIGLU: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SWIGLU>), g, b, lds); break;
@@ -944,6 +1128,7 @@ template <typename T> void launch_gemv_timed(hipStream_t s, const GemvArgs& a, h
     // (MXFP4 / e4m3 weights: bf16 engine only; the engine refuses to enable them otherwise)
     if (a.w4) launch_gemv_fmt<WMxfp4>(s, a, start, stop);
     else if (a.w8) launch_gemv_fmt<WE4m3>(s, a, start, stop);
+    else if (a.wp) launch_gemv_fmt<WP12>(s, a, start, stop);        // (bf16 engine only too: W / ldw stay the bf16 original)
     else launch_gemv_fmt<WPlain<T>>(s, a, start, stop);
 }
 int gemv_batched_grid(int N, int epi, int B) {
@@ -1000,6 +1185,13 @@ void launch_quant_fp8_rows(hipStream_t s, const void* w_bf16, int ld, void* w8, 
 void launch_quant_mxfp4_rows(hipStream_t s, const void* w_bf16, int ld, void* q4, uint8_t* e8, int64_t rows, int cols) {
     hipLaunchKernelGGL(quant_mxfp4_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, (const bf16*)w_bf16, ld, (uint8_t*)q4, e8, cols);
 }
+void launch_p12_pack_rows(hipStream_t s, const void* w_bf16, int ld, void* packed, void* rec, unsigned* fb_count, int64_t rows, int cols) {
+    hipLaunchKernelGGL(p12_pack_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, (const bf16*)w_bf16, ld, (uint8_t*)packed, (uint8_t*)rec, fb_count, cols);
+}
+void launch_p12_unpack_rows(hipStream_t s, const void* packed, const void* rec, const void* w_bf16, int ld, void* out, int ldo, int64_t rows, int cols) {
+    hipLaunchKernelGGL(p12_unpack_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, (const uint8_t*)packed, (const uint8_t*)rec, (const bf16*)w_bf16, ld,
+                       (bf16*)out, ldo, cols);
+}
 // (every kernel that may ask for more than 64 KiB of dynamic LDS goes through set_max_lds: a refusal is reported at engine creation)
 template <typename P> static void gemv_rows_attrs() {
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_NONE>, GEMV_ROWS_MAX_LDS);
@@ -1009,7 +1201,7 @@ template <typename P> static void gemv_rows_attrs() {
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_SAMPLE>, GEMV_ROWS_MAX_LDS);
 }
 void gemv_init_attrs() {
-    gemv_rows_attrs<WMxfp4>(); gemv_rows_attrs<WE4m3>(); gemv_rows_attrs<WPlain<bf16>>(); gemv_rows_attrs<WPlain<float>>();
+    gemv_rows_attrs<WMxfp4>(); gemv_rows_attrs<WE4m3>(); gemv_rows_attrs<WP12>(); gemv_rows_attrs<WPlain<bf16>>(); gemv_rows_attrs<WPlain<float>>();
 }
 template void launch_gemv<bf16>(hipStream_t, const GemvArgs&);
 template void launch_gemv<float>(hipStream_t, const GemvArgs&);

@@ -109,6 +109,10 @@ struct GemvArgs {
     // nibble), e8 [N][ldw / 32] E8M0 scale bytes, W[n][k] = 2^(e8[n][k / 32] - 127) * e2m1(code); ldw in elements, a multiple of 32;
     // when set, W and w8 are ignored
     const void* w4 = nullptr; const uint8_t* e8 = nullptr;
+    // optional lossless 12-bit packing of the bf16 weights (bf16 engine; svln_set_packed_decode, format in gemv.hip): wp [N][p12_row_bytes(K)]
+    // packed blocks, prec [N][16] row records; W / ldw stay the bf16 original, which the blocks a record marks as fallback are read from.
+    // K <= 32768.  The outputs are bit-equal to the call without wp.  Ignored when w4 or w8 is set.
+    const void* wp = nullptr; const void* prec = nullptr;
     const int* skip;              // optional device flag: the launch is a no-op when *skip != 0 (generation finished: run-ahead decode steps)
     // EPI_ARGMAX only, optional: HF RepetitionPenaltyLogitsProcessor on the fp32 logits before the arg-max (a checkpoint's
     // generation_config.json `repetition_penalty`): pen_flags[n] != 0 marks token n as already generated in this turn;
@@ -122,6 +126,12 @@ template <typename T> void launch_gemv(hipStream_t s, const GemvArgs& a);
 void launch_quant_fp8_rows(hipStream_t s, const void* w_bf16, int ld, void* w8, float* scale, int64_t rows, int cols);
 // OCP MXFP4 quantisation of a bf16 matrix [rows][cols] (cols % 32 == 0): q4 [rows][cols / 2], e8 [rows][cols / 32] (see GemvArgs)
 void launch_quant_mxfp4_rows(hipStream_t s, const void* w_bf16, int ld, void* q4, uint8_t* e8, int64_t rows, int cols);
+// P12 (see GemvArgs::wp): bytes of one packed row; the encoder of a bf16 matrix [rows][cols] (row stride ld; cols % 8 == 0, cols <= 32768;
+// *fb_count, optional, is incremented by the fallback blocks); and, TEST-ONLY, the decoder back to bf16 rows out [rows][ldo]
+constexpr int P12_MAX_K = 32768;
+__host__ __device__ constexpr size_t p12_row_bytes(int K) { return (size_t)((K + 511) / 512) * 768; }
+void launch_p12_pack_rows(hipStream_t s, const void* w_bf16, int ld, void* packed, void* rec, unsigned* fb_count, int64_t rows, int cols);
+void launch_p12_unpack_rows(hipStream_t s, const void* packed, const void* rec, const void* w_bf16, int ld, void* out, int ldo, int64_t rows, int cols);
 template <typename T> void launch_gemv_timed(hipStream_t s, const GemvArgs& a, hipEvent_t start, hipEvent_t stop);   // events get the kernel's own begin/end
 int gemv_grid(int N);                       // workgroups launch_gemv uses for N rows
 constexpr int GEMV_ROWS_MAX_LDS = 160 * 1024 - 256;    // dynamic LDS the wave-per-rows kernel may ask for (K fp32 activations): N > 8192 or an epilogue

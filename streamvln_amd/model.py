@@ -1032,6 +1032,18 @@ class StreamVLNForCausalLM:
         way round)."""
         _check(self._lib.svln_set_mxfp4_decode(self._h, int(enable)))
 
+    def set_packed_decode(self, enable: bool):
+        """Lossless 12-bit packing of the bf16 weights that the single-env decode step's gate/up and down_proj GEMVs and the lm_head GEMV
+        stream (svln_set_packed_decode): about 0.75 x the bytes, ids and hidden rows bit-identical.  On by default on bf16 engines;
+        enabling is refused on fp32 engines.  set_fp8_decode / set_mxfp4_decode take precedence while they are on."""
+        _check(self._lib.svln_set_packed_decode(self._h, int(enable)))
+
+    def packed_stats(self):
+        """{packed_bytes, bf16_bytes, blocks, fallback_blocks} over the packed weight matrices as encoded now (svln_packed_stats)"""
+        v = [C.c_int64() for _ in range(4)]
+        _check(self._lib.svln_packed_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("packed_bytes", "bf16_bytes", "blocks", "fallback_blocks"), (x.value for x in v)))
+
     def set_mxfp4_batched(self, enable: bool):
         """Opt-in extension (the reference is bf16 only): the decode steps of generate_batch / submit + step_batch (every batch size)
         and every lm_head product of the scheduler read the MXFP4 weight copies of set_mxfp4_decode on a weight-only MFMA kernel;

@@ -130,6 +130,38 @@ def main():
             for i in range(reps):
                 q4, e8 = Ws[i % nw]
                 _lib.check(lib.svln_op_gemv_mxfp4(h, ptr(q4), ptr(e8), K, ptr(x), ptr(g), 1e-6, None, None, ptr(y), N, K, epi, C.byref(tok)))
+    elif what == "gemv12":
+        # the decode shapes over the lossless 12-bit packing (svln_set_packed_decode); KBENCH_DIST = uniform (the other cases' weights,
+        # default), gauss (sigma 0.02) or t4 (Student-t, 4 degrees of freedom: many fallback blocks); the fallback share is printed
+        import ctypes as C
+        dist = os.environ.get("KBENCH_DIST", "uniform")
+        for (N, K, norm, epi) in [(37888, 3584, True, _lib.EPI_SWIGLU), (4608, 3584, True, 0), (3584, 3584, False, 0),
+                                  (3584, 18944, False, 0), (152064, 3584, False, _lib.EPI_ARGMAX)]:
+            rb = -(-K // 512) * 768
+            nw = 1 if os.environ.get("KBENCH_HOT") else max(1, min(8, -(-768 * 2**20 // (N * rb))))
+            Ws = []
+            for _ in range(nw):
+                if dist == "uniform":
+                    W = ((torch.rand(N, K, device="cuda") - 0.5) * 0.05).to(dt)
+                elif dist == "gauss":
+                    W = (torch.randn(N, K, device="cuda") * 0.02).to(dt)
+                else:
+                    W = (torch.randn(N, K, device="cuda") / torch.sqrt(torch.randn(4, N, K, device="cuda").square().mean(0)) * 0.02).to(dt)
+                pk = torch.zeros(N, rb, dtype=torch.uint8, device="cuda")
+                rec = torch.zeros(N, 16, dtype=torch.uint8, device="cuda")
+                nfb = C.c_int64()
+                torch.cuda.synchronize()
+                _lib.check(lib.svln_op_pack_rows(h, ptr(W), K, N, K, ptr(pk), ptr(rec), C.byref(nfb)))
+                Ws.append((W, pk, rec))
+            print(f"gemv12 N={N} K={K} {dist}: fallback blocks {nfb.value} of {N * -(-K // 512)}, packed bytes {N * (rb + 16)} + {nfb.value * 1024}", flush=True)
+            x = (torch.rand(K, device="cuda") - 0.5).to(dt)
+            g = torch.ones(K, device="cuda", dtype=dt) if norm else None
+            y = torch.zeros(N, device="cuda", dtype=dt)
+            tok = C.c_int32()
+            torch.cuda.synchronize()
+            for i in range(reps):
+                W, pk, rec = Ws[i % nw]
+                _lib.check(lib.svln_op_gemv_packed(h, ptr(pk), ptr(rec), ptr(W), K, ptr(x), ptr(g), 1e-6, None, None, ptr(y), N, K, epi, C.byref(tok)))
     m.close()
 
 
