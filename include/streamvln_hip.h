@@ -41,7 +41,14 @@ int svln_sync(svln_engine* h);
 /* -- weights: HF state-dict names (model.layers.N.self_attn.q_proj.weight, ...).
  * svln_synth_tensor fills a tensor on the device from the counter-based generator of
  * streamvln_amd/weights.py (seed_t = fnv1a64(name) ^ splitmix64(seed)); svln_set_tensor uploads
- * a canonical row-major tensor (host or device memory, fp32 or bf16). */
+ * a canonical row-major tensor (host or device memory, fp32 or bf16).
+ * A write may come at any time between turns, also after switches were enabled and turns have run: everything the engine derives from
+ * the written tensor follows it, on the engine stream behind the write -- the 12-bit packed copy (svln_set_packed_decode), the e4m3 and
+ * MXFP4 copies of the matrix if they exist (svln_set_fp8_decode / svln_set_fp8_gemm, svln_set_mxfp4_decode / svln_set_mxfp4_batched;
+ * quantised again into the same buffers, so captured decode graphs stay valid), and the feature cache (svln_set_feature_cache), whose
+ * entries are dropped when a tensor of the vision tower or the projector is written.  An env's rows and KV cache are session state
+ * computed with the old weights: reset the envs (svln_reset_env) after a write.  Refused before anything changes, by name
+ * ("svln_set_tensor cannot change while ..."): while scheduler turns are in flight, and while a group turn is pending. */
 int svln_synth_tensor(svln_engine* h, const char* name, uint64_t seed_t, float half_width, float base);
 int svln_set_tensor(svln_engine* h, const char* name, const void* data, int dtype, int64_t numel, int on_device);
 int svln_weights_ready(svln_engine* h);            /* 0 when every tensor of the path has been provided */
@@ -225,13 +232,19 @@ int svln_generate_batch_allowed_logprobs(svln_engine* h, int index, float* host_
  *             stop rule per sequence (an EOS id, limit, a non-finite arg-max); a finished sequence's row and every pad row replay the first
  *             live row (identical writes).
  * The head and the products are whatever the batched step runs under the switches in force (svln_set_fp8_gemm, svln_set_allowed_tokens,
- * ...): a group computes what svln_generate_batch would compute for n_seq envs holding this prompt.  out_ids [n_seq][out_cap], n_out [n_seq].
+ * ...): a group computes what svln_generate_batch would compute for n_seq envs holding this prompt.  Which scheme each phase runs:
+ * the prefill is bf16, or e4m3 under svln_set_fp8_gemm; token 0 and every decode iteration are the batched lm_head and the batched
+ * decode step on the bf16 weights (e4m3 products at B >= 4 under svln_set_fp8_gemm), whatever svln_set_fp8_decode or
+ * svln_set_mxfp4_decode says: those two switch the single-env decode step and its lm_head, which a group never runs, so under either
+ * of them a group returns the bits it returns with both off.  out_ids [n_seq][out_cap], n_out [n_seq].
  * Afterwards the env's draw counter has advanced by max_g n_out[g] (no (stream, draw) pair is ever used twice), its kv length is L and the
  * group is PENDING on it: svln_group_select must say which continuation the env goes on with.  While a group is pending,
  * svln_append_turn*, svln_generate*, svln_turn*, svln_batch_submit and svln_generate_batch on that env fail with a message that names
  * svln_group_select; svln_reset_env / svln_kv_reset drop the group and free its pages; svln_set_sampling, svln_set_token_scores and
  * svln_set_allowed_tokens fail, as they do while scheduler turns are in flight.
- * Refused before any launch or state change: sampling off (greedy sequences would be identical); a repetition penalty != 1; scheduler
+ * Refused before any launch or state change: svln_set_speculative, svln_set_prefill_draft, svln_set_batch_draft,
+ * svln_set_decode_persistent or svln_set_mxfp4_batched on (svln_set_sampling is refused under each of them; the message names the
+ * one that is on); sampling off (greedy sequences would be identical); a repetition penalty != 1; scheduler
  * turns in flight; a group pending on any env; n_seq outside 2 .. 8; nothing to prefill; L + limit - 1 > max_positions; a free pool that
  * cannot hold the env's own missing pages plus (n_seq - 1) * n_tail.  An error after the fork returns every fork page to the pool, leaves
  * no group pending and the env as after a failed svln_generate. */
@@ -269,8 +282,9 @@ int svln_get_hidden_group(svln_engine* h, int index, float* host_out, int max_ro
  * Refused before any launch or state change: everything svln_generate refuses (a pending group, nothing to prefill, ...); n outside
  * 1 .. 32; an id outside the vocabulary; an id of the EOS set anywhere but last (an EOS is appended, never fed); L + n - 1 >
  * max_positions; a repetition penalty != 1 (its flags change row by row); svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm
- * or svln_set_decode_persistent on (a forced row must be computed in the numeric scheme of the step it stands in for); scheduler turns in
- * flight; an id outside the allowed list. */
+ * or svln_set_decode_persistent on (a forced row must be computed in the numeric scheme of the step it stands in for: the list the
+ * draft switches refuse, without svln_set_mxfp4_batched, which only the scheduler paths read and a forced turn never runs); scheduler
+ * turns in flight; an id outside the allowed list. */
 int svln_generate_forced(svln_engine* h, int env, const int64_t* ids, int n, const int64_t* eos_ids, int n_eos, float* logprobs,
                          int64_t* greedy_ids, float* greedy_logprobs, int32_t* kv_len);
 /* svln_turn's bookkeeping (encode, window / episode resets, splice), then the forced turn, in one crossing (a->max_new_tokens is not read).
@@ -303,14 +317,17 @@ int svln_set_decode_persistent(svln_engine* h, int enable);
  * stream.  Runs on whatever the engine's buffers hold (after a decode step); overwrites the residual row and the q|k|v buffer. */
 int svln_probe_decode_layer(svln_engine* h, int layer, unsigned long long* out, int max_wgs, int32_t* n_wgs);
 /* Opt-in, no reference counterpart: the single-env decode step and the lm_head stream OCP e4m3 copies of the LLM
- * weights (one fp32 scale per output row, quantised on the device from the loaded tensors at the first enable) instead of the bf16
- * ones -- half the HBM bytes per generated token.  bf16 engines only; prefill, vision and svln_generate_batch keep bf16 weights (the
- * batched paths have svln_set_fp8_gemm and svln_set_mxfp4_batched).  Refused while svln_set_mxfp4_batched is on. */
+ * weights (one fp32 scale per output row; allocated and quantised on the device at the first enable, quantised again whenever
+ * svln_set_tensor / svln_synth_tensor writes one of the matrices) instead of the bf16 ones -- half the HBM bytes per generated token.  bf16 engines only; prefill, vision and svln_generate_batch keep bf16 weights (the
+ * batched paths have svln_set_fp8_gemm and svln_set_mxfp4_batched).  Refused while svln_set_mxfp4_batched is on.  A call that would
+ * change the mode fails while scheduler turns are in flight ("svln_set_fp8_decode cannot change while scheduler turns are in flight";
+ * the same holds for svln_set_mxfp4_decode, svln_set_fp8_gemm and svln_set_decode_persistent: no env changes scheme inside a turn); a
+ * call that changes nothing always succeeds. */
 int svln_set_fp8_decode(svln_engine* h, int enable);
 /* Opt-in, no reference counterpart: the single-env decode step's four projections and every lm_head product (the
  * prefill's token included) stream OCP MXFP4 copies of the LLM weights instead of the bf16 ones -- E2M1 elements, one E8M0 power-of-two
- * scale per 32 consecutive elements of a row, 4.25 bits per weight, quantised on the device from the loaded tensors at the first enable
- * (~4.0 GB beside the bf16 copy at the 7B size).  Numeric scheme: svln_op_quant_mxfp4.  bf16 engines only; hidden, intermediate and
+ * scale per 32 consecutive elements of a row, 4.25 bits per weight; allocated and quantised on the device at the first enable, quantised
+ * again whenever svln_set_tensor / svln_synth_tensor writes one of the matrices (~4.0 GB beside the bf16 copy at the 7B size).  Numeric scheme: svln_op_quant_mxfp4.  bf16 engines only; hidden, intermediate and
  * q_heads * 128 must be multiples of 32.  Prefill, vision, attention and norms keep bf16 weights; svln_generate_batch and the scheduler
  * keep them too unless svln_set_mxfp4_batched (below) is on.  Mutually exclusive with svln_set_fp8_decode: enabling one while the other
  * is on fails.  Captured decode graphs are dropped when the
@@ -450,7 +467,8 @@ int svln_phase_times(svln_engine* h, double* vision_ms, double* prefill_ms, doub
 /* -- optional memoisation of pooled frame features keyed by a 128-bit content hash of the pixels:
  * the <memory> frames of a window restart were all encoded earlier as "current" frames, so with the cache on they
  * skip the ViT.  capacity_frames = 0 (default) disables it: every frame is re-encoded, as the reference does
- * (stream_video_vln.py:104). */
+ * (stream_video_vln.py:104).  The entries are features of the weights loaded when they were computed: a svln_set_tensor /
+ * svln_synth_tensor of a vision-tower or projector tensor drops them all. */
 int svln_set_feature_cache(svln_engine* h, int capacity_frames);
 int svln_feature_cache_stats(svln_engine* h, int64_t* hits, int64_t* misses);
 

@@ -62,6 +62,7 @@ constexpr int PREFILL_SPLIT_ROWS = 2048;                 // split-KV prefill onl
 
 struct Slot {            // canonical tensor -> where its rows live in the packed device layout
     void* dst; int ld; int64_t rows; int cols; RowMap map; bool filled;
+    bool vision;         // a tensor of the vision tower or the projector: the cached frame features depend on it
 };
 
 // the sampled form of a test-only lm_head op (svln_op_*_argmax_sample): streams / draws are host arrays, one entry per row of the product
@@ -368,7 +369,8 @@ public:
         return (U*)p;
     }
     void add_slot(const std::string& name, void* dst, int ld, int64_t rows, int cols, RowMap m = RowMap{1 << 30, 1, 0}) {
-        slots[name] = Slot{dst, ld, rows, cols, m, false};
+        const bool vision = name.rfind("model.vision_tower.", 0) == 0 || name.rfind("model.mm_projector.", 0) == 0;
+        slots[name] = Slot{dst, ld, rows, cols, m, false, vision};
     }
     void add_linear(const std::string& name, T* w, T* b, int out_f, int in_f) {
         add_slot(name + ".weight", w, in_f, out_f, in_f);
@@ -457,6 +459,11 @@ public:
         final_norm = dalloc<T>(H); lm_head = dalloc<T>((size_t)V * H);
         add_slot("model.norm.weight", final_norm, H, 1, H);
         add_slot("lm_head.weight", lm_head, H, V, H);
+        for (auto& L : ll) {        // what build_fp8_weights / build_mxfp4_weights copy (ll is never resized again: the pointers stay)
+            qmats.push_back(QMat{L.qkv_w, qkv_dim, H, &L.qkv8, &L.qkv4}); qmats.push_back(QMat{L.o_w, H, qd, &L.o8, &L.o4});
+            qmats.push_back(QMat{L.gu_w, 2 * (int64_t)I, H, &L.gu8, &L.gu4}); qmats.push_back(QMat{L.down_w, H, I, &L.down8, &L.down4});
+        }
+        qmats.push_back(QMat{lm_head, V, H, &lm_head8, &lm_head4});
         if (sizeof(T) == 2 && H <= P12_MAX_K && I <= P12_MAX_K) {      // packed copies of the decode GEMVs' big weight streams; on by default
             unsigned* counters = dalloc<unsigned>(2 * (size_t)c.layers + 1, true);
             auto make = [&](P12& m, const T* w, int64_t rows, int cols) {
@@ -611,9 +618,38 @@ public:
     }
     void synth_tensor(const char* name, uint64_t seed_t, float hw, float base) override {
         Slot& s = slot(name);
+        before_weight_write("svln_synth_tensor");
         launch_synth<T>(st, s.dst, s.ld, s.rows, s.cols, s.map, seed_t, hw, base);
         s.filled = true;
+        after_weight_write(s);
+    }
+    // The two hooks of every weight write (svln_synth_tensor, svln_set_tensor).  Before: a turn in flight or a pending group was computed
+    // partly with the old weights, so the write is refused by name before anything changes.  After: everything the engine derives from
+    // the written tensor follows it, on the engine stream behind the write -- the 12-bit packed copy, the e4m3 / MXFP4 copies of the
+    // matrix if they are built (into the same buffers: the pointers stay, so captured graphs stay valid), and the feature cache, whose
+    // entries are features of the old vision tower / projector.  Nothing on a turn's launch path reads a flag set here.
+    void before_weight_write(const char* who) {
+        refuse_while_jobs(who);
+        refuse_while_group(who);
+    }
+    void after_weight_write(const Slot& s) {
         p12_encode(s.dst);
+        requantise(s.dst);
+        if (s.vision) for (auto& e : fc_entries) e.used = false;
+    }
+    // the LLM matrices that svln_set_fp8_decode / svln_set_fp8_gemm (Q8) and svln_set_mxfp4_decode / svln_set_mxfp4_batched (Q4) copy; a
+    // canonical tensor is a row range of one of them (q | k | v fused, gate / up interleaved), and the row scales / block scales are per
+    // row, so the whole matrix is quantised again: the bytes of the untouched rows come out as they were
+    struct QMat { const T* w; int64_t rows; int cols; Q8* q8; Q4* q4; };
+    std::vector<QMat> qmats;
+    void requantise(const void* dst) {
+        if (!fp8_built && !mx4_built) return;
+        for (const QMat& m : qmats) {
+            const char* lo = (const char*)m.w; const char* hi = lo + (size_t)m.rows * m.cols * sizeof(T);
+            if ((const char*)dst < lo || (const char*)dst >= hi) continue;
+            if (fp8_built) launch_quant_fp8_rows(st, m.w, m.cols, m.q8->q, m.q8->s, m.rows, m.cols);
+            if (mx4_built) launch_quant_mxfp4_rows(st, m.w, m.cols, m.q4->q, m.q4->e8, m.rows, m.cols);
+        }
     }
     // re-encode the packed copy of the matrix at `dst`, if it has one, on the engine stream (behind the write): the pointers stay, so
     // captured graphs stay valid
@@ -627,6 +663,7 @@ public:
     void set_tensor(const char* name, const void* data, int dtype, int64_t numel, int on_device) override {
         Slot& s = slot(name);
         REQUIRE(numel == s.rows * s.cols, std::string("size mismatch for ") + name);
+        before_weight_write("svln_set_tensor");
         const size_t bytes = (size_t)numel * (dtype == SVLN_F32 ? 4 : 2);
         const void* src = data;
         void* tmp = nullptr;
@@ -636,7 +673,7 @@ public:
             src = tmp;
         }
         launch_convert<T>(st, s.dst, s.ld, s.rows, s.cols, s.map, src, dtype == SVLN_F32);
-        p12_encode(s.dst);
+        after_weight_write(s);
         HIP_CHECK(hipStreamSynchronize(st));
         if (tmp) HIP_CHECK(hipFree(tmp));
         s.filled = true;
@@ -686,6 +723,10 @@ public:
     }
     void refuse_while_group(const char* who) {
         REQUIRE(!grp.pending, std::string(who) + " cannot change while a group turn is pending (svln_group_select)");
+    }
+    // the one "turns in flight" refusal of every setter and of a weight write: no env changes scheme, head or weights in the middle of a turn
+    void refuse_while_jobs(const char* who) {
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, std::string(who) + " cannot change while scheduler turns are in flight");
     }
     void env_state(int env, int32_t* n_embeds, int32_t* kv_len) override { Env& e = env_at(env); *n_embeds = e.n_embeds; *kv_len = e.kv_len; }
     void ensure_pages(Env& e, int positions) {      // pages covering [0, positions)
@@ -1269,8 +1310,10 @@ public:
         return a;
     }
     void set_decode_persistent(int enable) override {
+        if ((enable != 0) == persistent_on) return;        // nothing changes
+        refuse_while_jobs("svln_set_decode_persistent");
         HIP_CHECK(hipStreamSynchronize(st));
-        if (!enable) { if (persistent_on) drop_graphs(); persistent_on = false; return; }
+        if (!enable) { drop_graphs(); persistent_on = false; return; }
         refuse_while_speculative("svln_set_decode_persistent");
         refuse_while_scores("svln_set_decode_persistent");
         refuse_while_sampling("svln_set_decode_persistent");
@@ -1287,7 +1330,7 @@ public:
             h_giveup[0] = 0;
             HIP_CHECK(hipStreamSynchronize(st));
         }
-        if (!persistent_on) drop_graphs();
+        drop_graphs();
         persistent_on = true;
     }
     // diagnostic: ONE persistent launch of `layer` on whatever the buffers hold after the last decode step, with phase stamps per workgroup
@@ -1573,11 +1616,15 @@ public:
         for (int k = 0; k < 16; ++k) h_vctl[k] = 0;
         HIP_CHECK(hipStreamSynchronize(st));
     }
-    bool spec_exclusive_on() const { return fp8_on || mx4_on || fp8_gemm_on || mx4b_on || persistent_on; }
+    // The switches that change the numeric scheme or the execution form of a step.  single_scheme_on: those the single-env paths read
+    // (svln_generate's decode step and prefill) -- a forced turn, which runs on those paths only, refuses them.  spec_exclusive_on adds
+    // svln_set_mxfp4_batched, which the scheduler paths alone read: the three draft switches refuse all five, and all five refuse them.
+    bool single_scheme_on() const { return fp8_on || mx4_on || fp8_gemm_on || persistent_on; }
+    bool spec_exclusive_on() const { return single_scheme_on() || mx4b_on; }
     void set_speculative(int rows) override {
         if (rows == spec_rows) return;         // nothing changes
         REQUIRE(rows == 0 || rows == 2 || rows == 4 || rows == 8, "svln_set_speculative: rows must be 0 (off), 2, 4 or 8");
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_speculative cannot change while scheduler turns are in flight");
+        refuse_while_jobs("svln_set_speculative");
         if (rows > 0) {
             refuse_while_scores("svln_set_speculative");
             refuse_while_sampling("svln_set_speculative");
@@ -1601,6 +1648,14 @@ public:
         REQUIRE(!ride_on, std::string(who) + ": drafts inside the prefill pass are on (svln_set_prefill_draft); switch them off first");
         REQUIRE(!bdraft_on, std::string(who) + ": drafts in the scheduler's prefill pass are on (svln_set_batch_draft); switch them off first");
     }
+    // the modes whose tokens come out of neither a scored nor a sampled arg-max: the three draft switches (their tokens leave the verify
+    // step, whose rule is written for greedy rows), the persistent decode layer and the batched MXFP4 weights (gemv_mx4b_kernel has the
+    // plain arg-max only).  svln_set_sampling, svln_set_token_scores and svln_generate_group (sampled by definition) share the list.
+    void refuse_while_plain_head_only(const char* who) {
+        refuse_while_speculative(who);
+        REQUIRE(!persistent_on, std::string(who) + ": the persistent decode layer is on (svln_set_decode_persistent); switch it off first");
+        REQUIRE(!mx4b_on, std::string(who) + ": the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
+    }
     void refuse_while_sampling(const char* who) {
         REQUIRE(!smp_on, std::string(who) + ": temperature sampling is on (svln_set_sampling); switch it off first");
     }
@@ -1609,16 +1664,14 @@ public:
     // Every call, on or off, restarts the draw counters and drops the captured steps (seed and 1 / T are launch scalars).
     void set_sampling(int enable, float temperature, uint64_t seed) override {
         const bool want = enable != 0;
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_sampling cannot change while scheduler turns are in flight");
+        refuse_while_jobs("svln_set_sampling");
         refuse_while_group("svln_set_sampling");
         float inv_t = 1.0f;
         if (want) {
             REQUIRE(std::isfinite(temperature) && temperature > 0.0f, "svln_set_sampling: the temperature must be finite and > 0");
             inv_t = 1.0f / temperature;
             REQUIRE(std::isfinite(inv_t), "svln_set_sampling: 1 / temperature overflows fp32");
-            refuse_while_speculative("svln_set_sampling");
-            REQUIRE(!persistent_on, "svln_set_sampling: the persistent decode layer is on (svln_set_decode_persistent); switch it off first");
-            REQUIRE(!mx4b_on, "svln_set_sampling: the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
+            refuse_while_plain_head_only("svln_set_sampling");
         }
         HIP_CHECK(hipStreamSynchronize(st));
         drop_graphs();
@@ -1670,11 +1723,9 @@ public:
         const bool want = enable != 0;
         refuse_while_group("svln_set_token_scores");
         if (want == scores_on) return;         // nothing changes
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_token_scores cannot change while scheduler turns are in flight");
+        refuse_while_jobs("svln_set_token_scores");
         if (want) {
-            refuse_while_speculative("svln_set_token_scores");
-            REQUIRE(!persistent_on, "svln_set_token_scores: the persistent decode layer is on (svln_set_decode_persistent); switch it off first");
-            REQUIRE(!mx4b_on, "svln_set_token_scores: the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
+            refuse_while_plain_head_only("svln_set_token_scores");
         }
         HIP_CHECK(hipStreamSynchronize(st));
         drop_graphs();           // the captured lm_head / arg-max launches are the plain or the scored kernels
@@ -1727,7 +1778,7 @@ public:
         REQUIRE(n <= ALLOW_MAX, "svln_set_allowed_tokens: at most 256 ids");
         REQUIRE(n == 0 || ids, "svln_set_allowed_tokens: null id list with n > 0");
         if (n > 0) check_allowed_list("svln_set_allowed_tokens", ids, n, V);
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_allowed_tokens cannot change while scheduler turns are in flight");
+        refuse_while_jobs("svln_set_allowed_tokens");
         refuse_while_group("svln_set_allowed_tokens");
         std::vector<int> want(n);
         for (int k = 0; k < n; ++k) want[k] = (int)ids[k];
@@ -1797,7 +1848,7 @@ public:
     void set_batch_draft(int on) override {
         const bool want = on != 0;
         if (want == bdraft_on) return;         // nothing changes
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_batch_draft cannot change while scheduler turns are in flight");
+        refuse_while_jobs("svln_set_batch_draft");
         if (want) {
             refuse_while_scores("svln_set_batch_draft");
             refuse_while_sampling("svln_set_batch_draft");
@@ -1820,7 +1871,7 @@ public:
     void set_prefill_draft(int on) override {
         const bool want = on != 0;
         if (want == ride_on) return;           // nothing changes
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_prefill_draft cannot change while scheduler turns are in flight");
+        refuse_while_jobs("svln_set_prefill_draft");
         if (want) {
             refuse_while_scores("svln_set_prefill_draft");
             refuse_while_sampling("svln_set_prefill_draft");
@@ -2445,6 +2496,7 @@ public:
     void group_refusals(int env, int n_seq) {
         env_at(env);
         REQUIRE(n_seq >= 2 && n_seq <= MAXB, "svln_generate_group: n_seq must be 2 .. 8");
+        refuse_while_plain_head_only("svln_generate_group");     // (svln_set_sampling is refused under each of them: name the cause)
         REQUIRE(smp_on, "svln_generate_group: temperature sampling is off (svln_set_sampling): greedy sequences would be identical");
         REQUIRE(rep_penalty == 1.0f, "svln_generate_group: a repetition penalty != 1 is set (svln_set_repetition_penalty); a group does not support it");
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_generate_group needs an idle scheduler (turns are in flight)");
@@ -2644,7 +2696,7 @@ public:
         }
         REQUIRE(rep_penalty == 1.0f, "svln_generate_forced: a repetition penalty != 1 is set (svln_set_repetition_penalty); its flags change row by row");
         // a forced row must be computed in the numeric scheme of the step it stands in for (the ride's list)
-        REQUIRE(!(fp8_on || mx4_on || fp8_gemm_on || persistent_on),
+        REQUIRE(!single_scheme_on(),
                 "svln_generate_forced: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm, "
                 "svln_set_decode_persistent); switch it off first");
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_generate_forced needs an idle scheduler (turns are in flight)");
@@ -2942,68 +2994,59 @@ public:
     }
     // Opt-in (no reference counterpart): the single-env decode step and the lm_head read e4m3 copies of the LLM
     // weights (per-row scale) instead of the bf16 ones; prefill, vision and the lockstep multi-env path keep bf16.  Both copies stay
-    // resident (15.2 + 7.6 GB of 288).  Quantised from the tensors loaded at the time of the first enable.
+    // resident (15.2 + 7.6 GB of 288).  Allocated and quantised at the first enable; a later svln_set_tensor / svln_synth_tensor quantises the
+    // written matrix again (after_weight_write), so the copies are always those of the weights loaded now.
     void build_fp8_weights() {
         REQUIRE(sizeof(T) == 2, "fp8 weights need the bf16 engine");
         REQUIRE(weights_missing() == 0, g_err);
         REQUIRE(H % 16 == 0 && I % 16 == 0, "fp8 weights need hidden and intermediate sizes that are multiples of 16");
         if (fp8_built) return;
-        auto build = [&](Q8& q, const T* w, int64_t rows, int cols) {
-            q.q = dalloc<uint8_t>((size_t)rows * cols);
-            q.s = dalloc<float>((size_t)rows);
-            launch_quant_fp8_rows(st, w, cols, q.q, q.s, rows, cols);
-        };
-        for (auto& L : ll) {
-            build(L.qkv8, L.qkv_w, qkv_dim, H);
-            build(L.o8, L.o_w, H, nq * 128);
-            build(L.gu8, L.gu_w, 2 * I, H);
-            build(L.down8, L.down_w, H, I);
+        for (const QMat& m : qmats) {
+            m.q8->q = dalloc<uint8_t>((size_t)m.rows * m.cols);
+            m.q8->s = dalloc<float>((size_t)m.rows);
+            launch_quant_fp8_rows(st, m.w, m.cols, m.q8->q, m.q8->s, m.rows, m.cols);
         }
-        build(lm_head8, lm_head, V, H);
         HIP_CHECK(hipStreamSynchronize(st));
         fp8_built = true;
     }
     void set_fp8_decode(int enable) override {
-        if (!enable) { if (fp8_on) drop_graphs(); fp8_on = false; return; }
+        if ((enable != 0) == fp8_on) return;       // nothing changes
+        refuse_while_jobs("svln_set_fp8_decode");
+        if (!enable) { drop_graphs(); fp8_on = false; return; }
         refuse_while_speculative("svln_set_fp8_decode");
         REQUIRE(!mx4_on, "svln_set_fp8_decode: the MXFP4 decode weights are on (svln_set_mxfp4_decode); switch them off first");
         REQUIRE(!mx4b_on, "svln_set_fp8_decode: the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
         build_fp8_weights();
-        if (!fp8_on) drop_graphs();
+        drop_graphs();
         fp8_on = true;
     }
     // Opt-in (no reference counterpart): the single-env decode step's four projections and every lm_head product read
     // OCP MXFP4 copies of the LLM weights (E2M1 elements, one E8M0 scale per 32 elements of a row: 4.25 bits per weight) instead of the
     // bf16 ones; prefill, vision, attention and norms keep bf16, and so does the lockstep multi-env path unless svln_set_mxfp4_batched is on.
     // Both copies stay resident (15.2 + 4.0 GB).
-    // Quantised from the tensors loaded at the time of the first enable.
+    // Allocated and quantised at the first enable, and kept in step with later weight writes as the e4m3 copies are (after_weight_write).
     void build_mxfp4_weights() {
         REQUIRE(sizeof(T) == 2, "MXFP4 weights need the bf16 engine");
         REQUIRE(weights_missing() == 0, g_err);
         REQUIRE(H % 32 == 0 && I % 32 == 0 && (nq * 128) % 32 == 0, "MXFP4 weights need hidden, intermediate and q sizes that are multiples of 32");
         if (mx4_built) return;
-        auto build = [&](Q4& q, const T* w, int64_t rows, int cols) {
-            q.q = dalloc<uint8_t>((size_t)rows * (cols / 2));
-            q.e8 = dalloc<uint8_t>((size_t)rows * (cols / 32));
-            launch_quant_mxfp4_rows(st, w, cols, q.q, q.e8, rows, cols);
-        };
-        for (auto& L : ll) {
-            build(L.qkv4, L.qkv_w, qkv_dim, H);
-            build(L.o4, L.o_w, H, nq * 128);
-            build(L.gu4, L.gu_w, 2 * I, H);
-            build(L.down4, L.down_w, H, I);
+        for (const QMat& m : qmats) {
+            m.q4->q = dalloc<uint8_t>((size_t)m.rows * (m.cols / 2));
+            m.q4->e8 = dalloc<uint8_t>((size_t)m.rows * (m.cols / 32));
+            launch_quant_mxfp4_rows(st, m.w, m.cols, m.q4->q, m.q4->e8, m.rows, m.cols);
         }
-        build(lm_head4, lm_head, V, H);
         HIP_CHECK(hipStreamSynchronize(st));
         LAUNCH_CHECK("build_mxfp4_weights");
         mx4_built = true;
     }
     void set_mxfp4_decode(int enable) override {
-        if (!enable) { if (mx4_on) drop_graphs(); mx4_on = false; return; }
+        if ((enable != 0) == mx4_on) return;       // nothing changes
+        refuse_while_jobs("svln_set_mxfp4_decode");
+        if (!enable) { drop_graphs(); mx4_on = false; return; }
         refuse_while_speculative("svln_set_mxfp4_decode");
         REQUIRE(!fp8_on, "svln_set_mxfp4_decode: the e4m3 decode weights are on (svln_set_fp8_decode); switch them off first");
         build_mxfp4_weights();
-        if (!mx4_on) drop_graphs();
+        drop_graphs();
         mx4_on = true;
     }
     // Lossless (no reference counterpart; same ids and hidden rows bit for bit): the single-env decode step's gate/up and down_proj GEMVs and
@@ -3036,7 +3079,7 @@ public:
     void set_mxfp4_batched(int enable) override {
         if ((enable != 0) == mx4b_on) return;      // nothing changes
         // an env must not change scheme in the middle of a turn, in either direction
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_mxfp4_batched cannot change while scheduler turns are in flight");
+        refuse_while_jobs("svln_set_mxfp4_batched");
         if (!enable) { drop_graphs(); mx4b_on = false; return; }
         refuse_while_speculative("svln_set_mxfp4_batched");
         refuse_while_scores("svln_set_mxfp4_batched");
@@ -3053,6 +3096,8 @@ public:
     // accumulate, bf16 out): per-row weight scales (the copies of svln_set_fp8_decode), per-row activation scales computed on the fly.
     // Half the operand bytes per k through HBM / L2 / LDS.  Vision, attention, norms and the lm_head stay bf16.
     void set_fp8_gemm(int enable) override {
+        if ((enable != 0) == fp8_gemm_on) return;  // nothing changes
+        refuse_while_jobs("svln_set_fp8_gemm");
         if (!enable) { fp8_gemm_on = false; return; }
         refuse_while_speculative("svln_set_fp8_gemm");
         REQUIRE(!mx4b_on, "svln_set_fp8_gemm: the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
@@ -3070,7 +3115,7 @@ public:
     void set_fp8_scaled_mfma(int enable) override {
         if ((enable != 0) == fp8_scaled_on) return;
         REQUIRE(sizeof(T) == 2, "svln_set_fp8_scaled_mfma: the e4m3 products need the bf16 engine");
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_set_fp8_scaled_mfma cannot change while scheduler turns are in flight");
+        refuse_while_jobs("svln_set_fp8_scaled_mfma");
         fp8_scaled_on = enable != 0;
     }
     // C = A . W^T (+ epilogue) for an LLM linear: bf16 operands, or -- with svln_set_fp8_gemm -- the rows of A quantised on the fly

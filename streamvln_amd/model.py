@@ -315,6 +315,10 @@ class StreamVLNForCausalLM:
         return self
 
     def set_tensor(self, name: str, value):
+        """Write one canonical tensor (host array / tensor, or a device tensor; fp32 or bf16).  May come at any time between turns: the
+        packed, e4m3 and MXFP4 copies of the matrix follow it and a vision-tower / projector write empties the feature cache
+        (svln_set_tensor); envs hold rows and KV computed with the old weights -- reset them.  Refused by name while scheduler turns are
+        in flight or a group turn is pending."""
         if isinstance(value, torch.Tensor):
             t = value.detach()
             if t.dtype not in (torch.float32, torch.bfloat16):
@@ -566,11 +570,18 @@ class StreamVLNForCausalLM:
         if forced_ids is not None and n_seq > 1:
             raise NotImplementedError("forced_ids with num_return_sequences > 1: a forced turn has one sequence")
         self._sync_call_config()
+        held = self._sampling
         self._sync_sampling(kwargs)
-        if forced_ids is not None:
-            return self._generate_forced(forced_ids, inputs, ids, pix, V, n_memory, env_id, past, eos)
-        if n_seq > 1:
-            return self._generate_group(n_seq, inputs, ids, pix, V, n_memory, env_id, past, max_new, eos)
+        if forced_ids is not None or n_seq > 1:
+            try:
+                if forced_ids is not None:
+                    return self._generate_forced(forced_ids, inputs, ids, pix, V, n_memory, env_id, past, eos)
+                return self._generate_group(n_seq, inputs, ids, pix, V, n_memory, env_id, past, max_new, eos)
+            except Exception:
+                # a refused call changes no state: the sampling switch this call flipped goes back to what the engine held
+                if self._sampling != held:
+                    self.set_sampling(None) if held is None else self.set_sampling(*held)
+                raise
         # the reference's bookkeeping that needs no engine call: the KV handle must be this env's current one; curr_t counts the turns
         if past is not None and (not isinstance(past, KVHandle) or past.env_id != env_id or past.epoch != self._epoch[env_id]):
             raise ValueError("past_key_values does not belong to this env's current window")
