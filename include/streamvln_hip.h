@@ -188,6 +188,33 @@ int svln_set_token_scores(svln_engine* h, int enable);
  * svln_set_batch_draft (their verify rule is written for greedy rows), svln_set_decode_persistent and svln_set_mxfp4_batched (its
  * lm_head kernel has no sampled form).  svln_get_top2 is refused after a sampled turn: the values are perturbed, not logits. */
 int svln_set_sampling(svln_engine* h, int enable, float temperature, uint64_t seed);
+/* Opt-in, default off (k = 0), no reference counterpart: top-k log-probabilities -- what else the policy considered.  While k is 1 .. 8
+ * every lm_head product (the single-env GEMV of svln_generate / svln_turn / svln_generate_fixed, the batched GEMV and the 32 x 128 MFMA
+ * tiles of svln_generate_batch and the scheduler) runs the sibling of its scored or sampled kernel that also keeps, beside every arg-max
+ * partial, the partial's 8 best (y, column) pairs, and one small merge kernel per head pass writes the k best of every row.  With x_n the PROCESSED fp32 logit (after the repetition penalty), y_n = x_n under greedy decoding and
+ * y_n = fl(x_n * invT) under svln_set_sampling (the unperturbed value, never y + noise).  The list is ordered y descending, then column
+ * ascending; NaN and -inf are never listed; a row with fewer than k listable columns is padded with (id -1, logprob -inf);
+ * logprob_j = (y_j - V) - log S with (V, S) the merge the scored kernels compute.  Hence under greedy decoding entry 0 is the emitted id
+ * and its log-probability is the bits of svln_get_token_scores; under sampling the emitted id's entry, when listed, is.  Tokens, scores
+ * and every partial are bit-identical to k = 0: same accumulators, same compares.  No logit reaches memory and the lm_head is not read
+ * twice.  Under svln_set_allowed_tokens the list is over the allowed set (k > n_allowed: the rest is padding).
+ * The name is deliberately not svln_set_*: the switch is tied to svln_set_token_scores and is no independent row of the switch-pair
+ * table the tests keep for every svln_set_* prototype.  Rules, in force only for k > 0: refused while svln_set_token_scores is off
+ * (naming it), and svln_set_token_scores(0) is refused while k > 0 (naming svln_top_logprobs) -- so every mode the scores refuse
+ * (the draft switches, svln_set_decode_persistent, svln_set_mxfp4_batched) is unreachable.  Composes with svln_set_fp8_decode /
+ * svln_set_mxfp4_decode / svln_set_packed_decode (the lists are of their own lm_head formats), svln_set_fp8_gemm /
+ * svln_set_fp8_scaled_mfma, the repetition penalty, svln_set_sampling, svln_set_allowed_tokens and graph replay (captured decode graphs
+ * are keyed by k and dropped when it changes).  Refused: k outside 0 .. 8; a change while scheduler turns are in flight or a group is
+ * pending; and, while k > 0, svln_generate_group / svln_turn_group (naming svln_top_logprobs: group turns carry no lists).  A forced
+ * turn runs as before and produces no lists.  A call that changes nothing succeeds.
+ * svln_get_topk: the lists of the last single-env turn, ids [n_rows][k] int32 and logprobs [n_rows][k] fp32 (min(n_rows, cap_rows) rows
+ * are written), read in the synchronisation that reads the ids; refused when k was 0 for that turn, after a forced turn, or before any. */
+int svln_top_logprobs(svln_engine* h, int k);
+int svln_get_topk(svln_engine* h, int32_t* host_ids, float* host_logprobs, int cap_rows, int32_t* n_rows, int32_t* k);
+/* ... those of the finished scheduler turn in `slot` (valid until svln_batch_result frees the slot), and of env index `index` of the
+ * last svln_generate_batch; both refused when k was 0 for that turn. */
+int svln_batch_topk(svln_engine* h, int slot, int32_t* host_ids, float* host_logprobs, int cap_rows, int32_t* n_rows, int32_t* k);
+int svln_generate_batch_topk(svln_engine* h, int index, int32_t* host_ids, float* host_logprobs, int cap_rows, int32_t* n_rows, int32_t* k);
 int svln_get_token_scores(svln_engine* h, float* host_out, int cap, int32_t* n);
 int svln_batch_scores(svln_engine* h, int slot, float* host_out, int cap, int32_t* n);
 int svln_generate_batch_scores(svln_engine* h, int index, float* host_out, int cap, int32_t* n);
@@ -594,6 +621,28 @@ int svln_op_gemv_mxfp4_batched_argmax_pen(svln_engine* h, const void* q4, const 
  * fmt 1 / 2 on an fp32 engine, A / W not 16-byte aligned (MFMA form). */
 int svln_op_gemv_argmax_scores(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
                                float penalty, int32_t* host_token, float* host_logprob);
+/* TEST-ONLY: the single-env head under svln_top_logprobs on caller-given operands (fmt / W / aux / pen_flags as
+ * svln_op_gemv_argmax_scores, plus fmt 3 = the 12-bit packing with W the bf16 original and aux the packed rows followed by the row
+ * records): the EPI_ARGMAX_LSE_TOPK product (sampled != 0: EPI_SAMPLE_TOPK on temperature, seed, stream, draw), the final kernel and
+ * the merge.  Outputs (host): the token and its score; the partial arrays [*n_part] (part_raw / part_max: sampled form only, may be null
+ * otherwise); the candidates [*n_part][8]; the merged lists [k].  Arrays must hold 1280 partials.  The refusals of
+ * svln_op_gemv_argmax_scores / _sample apply, plus k outside 1 .. 8 and null outputs -- before any launch. */
+int svln_op_gemv_argmax_topk(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
+                             float penalty, int k, int sampled, float temperature, uint64_t seed, int32_t stream, int32_t draw, int32_t* host_token,
+                             float* host_logprob, float* part_val, int32_t* part_idx, float* part_sum, float* part_raw, float* part_max,
+                             float* cand_val, int32_t* cand_idx, int32_t* top_ids, float* top_logprobs, int32_t* n_part);
+/* TEST-ONLY: the batched GEMV (B = 1, 2, 4, 8; no fused norm) and the 32 x 128 MFMA tiles (1 <= M <= 32) under svln_top_logprobs, arguments
+ * as svln_op_gemv_batched_argmax_sample / svln_op_gemm_argmax_sample (sampled == 0: the greedy form, streams / draws unread).  Outputs
+ * (host): tokens and scores [rows]; candidates [rows][*n_part][8]; lists [rows][k]; the partial arrays stay readable through
+ * svln_op_read_argmax_partials, as after the scored entries.  Same refusals, plus k outside 1 .. 8 and null outputs, before any launch. */
+int svln_op_gemv_batched_argmax_topk(svln_engine* h, const void* W, int ldw, const void* x, int ldx, int N, int K, int B, const void* pen_flags,
+                                     const int32_t* pen_rows, float penalty, int k, int sampled, float temperature, uint64_t seed, const int32_t* streams,
+                                     const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* cand_val, int32_t* cand_idx,
+                                     int32_t* top_ids, float* top_logprobs, int32_t* n_part);
+int svln_op_gemm_argmax_topk(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
+                             const int32_t* pen_rows, float penalty, int k, int sampled, float temperature, uint64_t seed, const int32_t* streams,
+                             const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* cand_val, int32_t* cand_idx, int32_t* top_ids,
+                             float* top_logprobs, int32_t* n_part);
 int svln_op_gemv_batched_argmax_scores(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
                                        const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs);
 int svln_op_gemm_argmax_scores(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,

@@ -109,6 +109,14 @@ SIGNATURES = {
     "svln_get_frame_feats": (_I, [_P, _I, _I, _PF]),
     "svln_get_top2": (_I, [_P, _PF]),
     "svln_set_token_scores": (_I, [_P, _I]),
+    "svln_top_logprobs": (_I, [_P, _I]),
+    "svln_get_topk": (_I, [_P, _PI32, _PF, _I, _PI32, _PI32]),
+    "svln_batch_topk": (_I, [_P, _I, _PI32, _PF, _I, _PI32, _PI32]),
+    "svln_generate_batch_topk": (_I, [_P, _I, _PI32, _PF, _I, _PI32, _PI32]),
+    "svln_op_gemv_batched_argmax_topk": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _I, _I, _F, _U64, _PI32, _PI32, _PI32, _PF, _PF,
+                                              _PI32, _PI32, _PF, _PI32]),
+    "svln_op_gemm_argmax_topk": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _I, _I, _F, _U64, _PI32, _PI32, _PI32, _PF, _PF, _PI32,
+                                      _PI32, _PF, _PI32]),
     "svln_get_token_scores": (_I, [_P, _PF, _I, _PI32]),
     "svln_batch_scores": (_I, [_P, _I, _PF, _I, _PI32]),
     "svln_generate_batch_scores": (_I, [_P, _I, _PF, _I, _PI32]),
@@ -175,6 +183,8 @@ SIGNATURES = {
     "svln_op_gemv_mxfp4_batched": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _PI32]),
     "svln_op_gemv_mxfp4_batched_argmax_pen": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _PI32]),
     "svln_op_gemv_argmax_scores": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _F, _PI32, _PF]),
+    "svln_op_gemv_argmax_topk": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _F, _I, _I, _F, _U64, _I, _I, _PI32, _PF, _PF, _PI32, _PF, _PF, _PF,
+                                      _PF, _PI32, _PI32, _PF, _PI32]),
     "svln_op_gemv_batched_argmax_scores": (_I, [_P, _P, _I, _P, _I, _P, _F, _I, _I, _I, _P, _P, _F, _PI32, _PF]),
     "svln_op_gemm_argmax_scores": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _PI32, _PF]),
     "svln_op_gemv_argmax_sample": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _F, _F, _U64, _I, _I, _PI32, _PF]),

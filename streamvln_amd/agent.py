@@ -87,6 +87,10 @@ class StreamingAgent:
         # the model's distribution over the allowed ids for every id of the last model turn (model.set_allowed_tokens with
         # set_token_scores): [1, n_new, n_allowed]; None otherwise
         self.last_allowed_logprobs = None
+        # what else the policy considered at every id of the last model turn (model.set_top_logprobs): ids [1, n_new, k] and their
+        # log-probabilities [1, n_new, k]; None otherwise
+        self.last_top_token_ids = None
+        self.last_top_logprobs = None
         # the policy's own arg-max at every position of the last FORCED model turn (act(..., forced_ids=...)): [1, n]; None otherwise
         self.last_greedy_ids = None
         self.step_id = 0
@@ -144,6 +148,8 @@ class StreamingAgent:
         self.last_turn_logprob = None if lp is None else float(lp.sum())
         self.last_allowed_logprobs = out.get("allowed_logprobs") if isinstance(out, dict) else getattr(out, "allowed_logprobs", None)
         self.last_greedy_ids = out.get("greedy_ids") if isinstance(out, dict) else getattr(out, "greedy_ids", None)
+        self.last_top_token_ids = out.get("top_token_ids") if isinstance(out, dict) else getattr(out, "top_token_ids", None)
+        self.last_top_logprobs = out.get("top_logprobs") if isinstance(out, dict) else getattr(out, "top_logprobs", None)
         self.turn_log.append(dict(self._pending, out=out))
         actions = list(self.decode_actions(out.sequences))
         return actions if len(actions) else [0]               # streamvln_eval.py:340-341

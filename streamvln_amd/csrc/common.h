@@ -140,6 +140,76 @@ SVLN_DEV float lse_rescale(float s, float m, float V) { return s == 0.0f ? 0.0f 
 // log-probability of the winning logit from S = sum exp(l - V) >= 1
 SVLN_DEV float lse_logprob(float S) { return -0.6931471805599453f * __builtin_amdgcn_logf(S); }
 
+// ---- merges of one row's arg-max partials on a 256-thread workgroup (the final kernels of gemv.hip, topk_merge_kernel of misc.hip)
+// S = sum over the 256 threads' shares `mine` of the rescaled partial sums, through `red` (a fixed tree: the same bits every launch)
+SVLN_DEV float block_sum_256(float mine, float* red) {
+    red[threadIdx.x] = mine;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// EPI_SAMPLE merge of one row's n partials on 256 threads: raw = pr[k] of the partial with pi[k] == tok (unique; 0 when tok owns none),
+// V = max_k pm[k], S = sum_k ps[k] * exp(pm[k] - V), all on fixed trees.  red / redi: 256 words each, free to overwrite; ends synchronised.
+struct SampleMerge { float raw, V, S; };
+SVLN_DEV SampleMerge sample_merge(const int* pi, const float* pr, const float* pm, const float* ps, int n, int tok, float* red, int* redi) {
+    __syncthreads();                              // red / redi have been read by every thread
+    float m = -INFINITY, raw = 0.0f;
+    for (int k = threadIdx.x; k < n; k += 256) {
+        m = pm[k] > m ? pm[k] : m;
+        if (pi[k] == tok) raw = pr[k];
+    }
+    red[threadIdx.x] = m; redi[threadIdx.x] = __float_as_int(raw);
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+            red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
+            redi[threadIdx.x] |= redi[threadIdx.x + s];       // one thread holds the bits, the others 0
+        }
+        __syncthreads();
+    }
+    SampleMerge r;
+    r.V = red[0]; r.raw = __int_as_float(redi[0]);
+    __syncthreads();
+    float mine = 0.0f;
+    for (int k = threadIdx.x; k < n; k += 256) mine += lse_rescale(ps[k], pm[k], r.V);
+    r.S = block_sum_256(mine, red);
+    return r;
+}
+
+// The merge of one row's n partials on 256 threads, shared by argmax_final_batched_kernel and target_final_batched_kernel (one body: the
+// two kernels' ids and sums are the same bits by construction).
+// row_argmax_256: greatest value, lowest index on ties -> sv[0], si[0] (0x7FFFFFFF: no finite logit); ends synchronised.
+SVLN_DEV void row_argmax_256(const float* v0, const int* i0, int n, float* sv, int* si) {
+    float v = -INFINITY;
+    int i = 0x7FFFFFFF;
+    for (int k = threadIdx.x; k < n; k += 256) {
+        const float c = v0[k];
+        const int ci = i0[k];
+        if (c > v || (c == v && ci < i)) { v = c; i = ci; }
+    }
+    sv[threadIdx.x] = v; si[threadIdx.x] = i;
+    __syncthreads();
+    for (int s2 = 128; s2 > 0; s2 >>= 1) {
+        if (threadIdx.x < s2) {
+            const float b = sv[threadIdx.x + s2];
+            const int bi = si[threadIdx.x + s2];
+            if (b > sv[threadIdx.x] || (b == sv[threadIdx.x] && bi < si[threadIdx.x])) { sv[threadIdx.x] = b; si[threadIdx.x] = bi; }
+        }
+        __syncthreads();
+    }
+}
+// row_lse_sum_256: S = sum_k lse_rescale(ps[k], v0[k] * sc, V) on the fixed tree; sv must have been read by every thread's caller already
+SVLN_DEV float row_lse_sum_256(const float* ps, const float* v0, int n, float sc, float V, float* sv) {
+    __syncthreads();                          // sv is reused by the sum
+    float mine = 0.0f;
+    for (int k = threadIdx.x; k < n; k += 256) mine += lse_rescale(ps[k], v0[k] * sc, V);
+    return block_sum_256(mine, sv);
+}
+
 // Noise of EPI_SAMPLE (kernels.h): a pure function of (seed, stream, draw, column), whatever kernel, tile, wave or row evaluates it.
 // Philox4x32-10 (Salmon et al., SC'11) on counter (column, draw, stream, 0) and key (seed lo, seed hi); output word 0.
 SVLN_DEV uint32_t philox4x32_10_w0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {

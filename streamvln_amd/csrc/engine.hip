@@ -67,6 +67,8 @@ struct Slot {            // canonical tensor -> where its rows live in the packe
 
 // the sampled form of a test-only lm_head op (svln_op_*_argmax_sample): streams / draws are host arrays, one entry per row of the product
 struct OpSample { float temperature; uint64_t seed; const int32_t* streams; const int32_t* draws; };
+// the outputs of the batched test entries under svln_top_logprobs (null: the scored / sampled entries): k, candidates [rows][n][8], lists [rows][k]
+struct OpTopkRows { int k; float* cv; int32_t* ci; int32_t* top_ids; float* top_lp; int32_t* n_part; };
 struct EngineBase {
     virtual ~EngineBase() {}
     virtual void synth_tensor(const char* name, uint64_t seed_t, float hw, float base) = 0;
@@ -102,12 +104,18 @@ struct EngineBase {
     virtual void get_feats(int start, int n, float* out) = 0;
     virtual void get_top2(float* out) = 0;
     virtual void set_token_scores(int enable) = 0;
+    virtual void top_logprobs(int k) = 0;
+    virtual void get_topk(int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) = 0;
+    virtual void batch_topk(int slot, int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) = 0;
+    virtual void generate_batch_topk(int index, int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) = 0;
+    virtual void op_gemv_topk(GemvArgs a, int k, const OpSample* smp, int32_t* host_token, float* host_logprob, float* pv, int32_t* pi, float* ps,
+                              float* pr, float* pm, float* cv, int32_t* ci, int32_t* top_ids, float* top_lp, int32_t* n_part) = 0;
     virtual void get_token_scores(float* out, int cap, int32_t* n) = 0;
     virtual void batch_scores(int slot, float* out, int cap, int32_t* n) = 0;
     virtual void generate_batch_scores(int index, float* out, int cap, int32_t* n) = 0;
     virtual void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob, const OpSample* smp) = 0;
-    virtual void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp) = 0;
-    virtual void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp) = 0;
+    virtual void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk = nullptr) = 0;
+    virtual void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk = nullptr) = 0;
     virtual void set_sampling(int enable, float temperature, uint64_t seed) = 0;
     virtual void set_allowed_tokens(const int64_t* ids, int n) = 0;
     virtual void get_allowed_logprobs(float* out, int cap, int32_t* n_tokens, int32_t* n_ids) = 0;
@@ -262,6 +270,27 @@ public:
     bool scores_on = false;
     float *part_sum = nullptr, *part_sum_b = nullptr, *d_scores = nullptr, *h_scores = nullptr, *d_score_b = nullptr, *h_score_b = nullptr;
     float* row_scale_b = nullptr;            // [MAXB]: the row factors of a scored batched GEMV with a fused norm (svln_op_gemv_batched_argmax_scores only)
+    // Opt-in top-k log-probabilities (svln_top_logprobs; single-env turns): while topk > 0 head() runs the EPI_*_TOPK sibling of its scored
+    // or sampled lm_head GEMV (cand_val / cand_idx: TOPK_C candidates beside every partial; under an allowed list the subset product's
+    // partials are the candidates) and topk_merge_kernel writes d_topi / d_topl [count][topk] beside d_scores[count].
+    int topk = 0;
+    float *cand_val = nullptr, *d_topl = nullptr, *h_topl = nullptr; int *cand_idx = nullptr, *d_topi = nullptr, *h_topi = nullptr;
+    std::vector<int32_t> last_topi; std::vector<float> last_topl; int last_topk = 0; bool last_topk_valid = false;
+    // ... and of the batched heads (argmax_rows): candidates [rows][partials][TOPK_C], lists d_topi_b / d_topl_b [tok0 + b][topk] beside d_score_b
+    float *cand_val_b = nullptr, *d_topl_b = nullptr, *h_topl_b = nullptr; int *cand_idx_b = nullptr, *d_topi_b = nullptr, *h_topi_b = nullptr;
+    std::vector<std::vector<int32_t>> gb_topi; std::vector<std::vector<float>> gb_topl; int gb_topk = 0; bool gb_topk_valid = false;
+    void ensure_topk_buffers() {
+        if (cand_val) return;
+        const size_t rows = (size_t)c.max_positions + 8;
+        cand_val = dalloc<float>((size_t)2048 * TOPK_C); cand_idx = dalloc<int>((size_t)2048 * TOPK_C);
+        d_topi = dalloc<int>(rows * TOPK_C, true); d_topl = dalloc<float>(rows * TOPK_C, true);
+        HIP_CHECK(hipHostMalloc((void**)&h_topi, rows * TOPK_C * sizeof(int)));
+        HIP_CHECK(hipHostMalloc((void**)&h_topl, rows * TOPK_C * sizeof(float)));
+        cand_val_b = dalloc<float>((size_t)HEAD_ROWS * 2048 * TOPK_C); cand_idx_b = dalloc<int>((size_t)HEAD_ROWS * 2048 * TOPK_C);
+        d_topi_b = dalloc<int>((size_t)(HEAD_ROWS + MAXB) * TOPK_C, true); d_topl_b = dalloc<float>((size_t)(HEAD_ROWS + MAXB) * TOPK_C, true);
+        HIP_CHECK(hipHostMalloc((void**)&h_topi_b, (size_t)(HEAD_ROWS + MAXB) * TOPK_C * sizeof(int)));
+        HIP_CHECK(hipHostMalloc((void**)&h_topl_b, (size_t)(HEAD_ROWS + MAXB) * TOPK_C * sizeof(float)));
+    }
     std::vector<float> last_scores; bool last_scores_valid = false;           // of the last svln_generate / svln_turn / svln_generate_fixed
     // Opt-in temperature sampling (svln_set_sampling; no reference counterpart): every lm_head product runs its EPI_SAMPLE sibling
     // (kernels.h): token = argmax_n (fl(x_n * inv_t) + G(seed, stream, draw, n)), an exact sample of softmax(x / T).  stream = the env slot,
@@ -348,7 +377,7 @@ public:
     // envs through svln_generate replays instead of re-capturing); [0] = the whole step, [1] / [2] = the halves around the probed launch
     // (captured only while the roofline probe is on); a run-ahead batch of several steps is one graph.
     bool use_graph = false;
-    struct GraphSet { std::unordered_map<int, hipGraphExec_t> ex; };     // key: steps (whole batch) | 1000 (head of a probed step) | 2000 + steps (its tail) | 3000 + rows (verify pass); + 10000 with svln_set_token_scores, + 20000 with svln_set_sampling, + 40000 with svln_set_packed_decode
+    struct GraphSet { std::unordered_map<int, hipGraphExec_t> ex; };     // key: steps (whole batch) | 1000 (head of a probed step) | 2000 + steps (its tail) | 3000 + rows (verify pass); + 10000 with svln_set_token_scores, + 20000 with svln_set_sampling, + 40000 with svln_set_packed_decode, + 100000 k with svln_top_logprobs(k)
     std::vector<GraphSet> graphs;
     std::unordered_map<int, hipGraphExec_t> bgraphs;          // batched decode step: key = B | penalty << 8 | fp8 gemm << 9 | MXFP4 batched << 10 | scaled fp8 form << 11 | token scores << 12
     // per-turn truncation of the spliced rows (the reference's config.tokenizer_model_max_length, stream_video_vln.py:241-244); 0 = none
@@ -591,6 +620,10 @@ public:
         for (auto e : pprobe_ev) (void)hipEventDestroy(e);
         for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ph_ev[i]);
         (void)hipHostFree(h_ctl); (void)hipHostFree(h_out_ids); (void)hipHostFree(h_scores); (void)hipHostFree(h_score_b);
+        if (h_topi) (void)hipHostFree(h_topi);
+        if (h_topl) (void)hipHostFree(h_topl);
+        if (h_topi_b) (void)hipHostFree(h_topi_b);
+        if (h_topl_b) (void)hipHostFree(h_topl_b);
         if (h_smp) (void)hipHostFree(h_smp);
         if (h_fork_dst) (void)hipHostFree(h_fork_dst);
         if (h_alp) (void)hipHostFree(h_alp);
@@ -1274,6 +1307,9 @@ public:
         if (smp_on) a.smp = smp_args(&d_ctl->stream, &d_ctl->draw0, &d_ctl->count, part_raw, part_max);
         const float *pr = smp_on ? part_raw : nullptr, *pm = smp_on ? part_max : nullptr;
         int n_part = gemv_grid(V);
+        // svln_top_logprobs: the lists of this token -> d_topi / d_topl [count], before the step kernel advances the count
+        const int* trow = gen ? &d_ctl->count : nullptr;
+        if (topk) { a.epi = smp_on ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK; a.cand_val = cand_val; a.cand_idx = cand_idx; }
         if (allow_on) {
             // svln_set_allowed_tokens: the subset product on the engine-dtype lm_head, one partial per listed id; with the scores on, the
             // normalised row goes to d_alp[count] before the step kernel advances the count
@@ -1283,8 +1319,10 @@ public:
             launch_gemv_subset<T>(st, sa);
             if (scores_on) launch_subset_logprobs(st, smp_on ? part_max : part_val, allow_n, 1, d_alp, gen ? &d_ctl->count : nullptr, skip);
             n_part = allow_n;
+            if (topk) launch_topk_merge(st, smp_on ? part_max : part_val, part_idx, n_part, 1, 1, topk, part_val, part_idx, part_sum, pm, d_topi, d_topl, trow, skip);
         } else {
             launch_gemv<T>(st, a);
+            if (topk) launch_topk_merge(st, cand_val, cand_idx, n_part, TOPK_C, 1, topk, part_val, part_idx, part_sum, pm, d_topi, d_topl, trow, skip);
         }
         if (gen) launch_argmax_step(st, part_val, part_idx, n_part, d_token, d_top2, d_ctl, d_eos, d_out_ids, pen ? pen_flags : nullptr, ps, d_scores, pr, pm);
         else launch_argmax_final(st, part_val, part_idx, n_part, d_token, d_top2, ps, d_scores, pr, pm);
@@ -1433,7 +1471,7 @@ public:
         const bool probing = probe_on && first_tap_row == 1 && probe_used + 2 <= probe_ev.size();
         if (use_graph) {
             GraphSet& gs = graphs[env];
-            const int sk = (scores_on ? 10000 : 0) + (smp_on ? 20000 : 0) + (p12_on ? 40000 : 0);      // the captured head is the plain, the scored or the sampled one; the GEMVs read the packed weights or not
+            const int sk = (scores_on ? 10000 : 0) + (smp_on ? 20000 : 0) + (p12_on ? 40000 : 0) + 100000 * topk;      // the captured head is the plain, the scored or the sampled one; the GEMVs read the packed weights or not
             auto get = [&](int key, int lo, int hi, int more) {
                 auto it = gs.ex.find(key);
                 if (it == gs.ex.end()) it = gs.ex.emplace(key, capture(e, lo, hi, more)).first;
@@ -1484,6 +1522,7 @@ public:
             launch_gemv_subset<T>(st, su);
             if (scores_on) launch_subset_logprobs(st, smp_on ? part_max_b : part_val_b, allow_n, B, d_alp_b + (size_t)tok0 * allow_n);
             launch_argmax_final_batched(st, part_val_b, part_idx_b, allow_n, B, d_tok_b + tok0, ps, d_score_b + tok0, nullptr, pr, pm);
+            if (topk) launch_topk_merge(st, smp_on ? part_max_b : part_val_b, part_idx_b, allow_n, 1, B, topk, part_val_b, part_idx_b, part_sum_b, pm, d_topi_b + (size_t)tok0 * topk, d_topl_b + (size_t)tok0 * topk);
             return;
         }
         if (B >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048) {
@@ -1492,16 +1531,20 @@ public:
             if (scores_on || smp_on) a.part_sum = part_sum_b;
             if (smp_on) a.smp = sa;
             if (pen) { a.pen_flags = pen_flags_b; a.pen_rows = d_pen_rows; a.pen = rep_penalty; }
+            if (topk) { a.cand_val = cand_val_b; a.cand_idx = cand_idx_b; }
             const int n = launch_gemm_argmax<T>(st, a);
             launch_argmax_final_batched(st, part_val_b, part_idx_b, n, B, d_tok_b + tok0, ps, d_score_b + tok0, nullptr, pr, pm);
+            if (topk) launch_topk_merge(st, cand_val_b, cand_idx_b, n, TOPK_C, B, topk, part_val_b, part_idx_b, part_sum_b, pm, d_topi_b + (size_t)tok0 * topk, d_topl_b + (size_t)tok0 * topk);
             return;
         }
         GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, smp_on ? EPI_SAMPLE : scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX, B);
         hb.part_sum = part_sum_b;
         if (smp_on) hb.smp = sa;
         if (pen) { hb.pen_flags = pen_flags_b; hb.pen_rows = d_pen_rows; hb.pen = rep_penalty; }
+        if (topk) { hb.epi = smp_on ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK; hb.cand_val = cand_val_b; hb.cand_idx = cand_idx_b; }
         launch_gemv_batched<T>(st, hb);
         launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(N, EPI_ARGMAX, B), B, d_tok_b + tok0, ps, d_score_b + tok0, nullptr, pr, pm);
+        if (topk) launch_topk_merge(st, cand_val_b, cand_idx_b, gemv_batched_grid(N, EPI_ARGMAX, B), TOPK_C, B, topk, part_val_b, part_idx_b, part_sum_b, pm, d_topi_b + (size_t)tok0 * topk, d_topl_b + (size_t)tok0 * topk);
     }
     void head_batched(const T* rows, int B, bool pen = false) {
         launch_rmsnorm<T>(st, rows, final_norm, xn, B, H, c.rms_eps);
@@ -1723,6 +1766,7 @@ public:
         const bool want = enable != 0;
         refuse_while_group("svln_set_token_scores");
         if (want == scores_on) return;         // nothing changes
+        REQUIRE(want || topk == 0, "svln_set_token_scores: top-k log-probabilities are on (svln_top_logprobs); switch them off first");
         refuse_while_jobs("svln_set_token_scores");
         if (want) {
             refuse_while_plain_head_only("svln_set_token_scores");
@@ -1730,6 +1774,44 @@ public:
         HIP_CHECK(hipStreamSynchronize(st));
         drop_graphs();           // the captured lm_head / arg-max launches are the plain or the scored kernels
         scores_on = want;
+    }
+    // svln_top_logprobs.  The lists ride on the scored kernels' partials, so the scores must be on (and stay on): every mode the scores
+    // refuse is thereby unreachable.  Lists exist for single-env turns only: the scheduler, svln_generate_batch and group turns refuse
+    // while k > 0.
+    void top_logprobs(int k) override {
+        REQUIRE(k >= 0 && k <= TOPK_C, "svln_top_logprobs: k must be 0 (off) .. 8");
+        refuse_while_group("svln_top_logprobs");
+        if (k == topk) return;                 // nothing changes
+        refuse_while_jobs("svln_top_logprobs");
+        REQUIRE(k == 0 || scores_on, "svln_top_logprobs: token log-probabilities are off (svln_set_token_scores); switch them on first");
+        REQUIRE(k == 0 || (size_t)H * sizeof(float) <= (size_t)GEMV_ROWS_TOPK_MAX_LDS, "svln_top_logprobs: the hidden size is too large for the candidate form of the lm_head GEMV");
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (k) ensure_topk_buffers();
+        drop_graphs();           // the captured lm_head launch is the sibling with or without candidates; the merge holds k
+        topk = k;
+    }
+    void refuse_while_topk(const char* who) {
+        REQUIRE(topk == 0, std::string(who) + ": top-k log-probabilities are on (svln_top_logprobs), which group turns do not carry; switch them off first");
+    }
+    void get_topk(int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) override {
+        REQUIRE(last_topk_valid, "svln_get_topk: top-k log-probabilities were off for the last turn (svln_top_logprobs), the last turn was forced, or no turn has run");
+        topk_out(last_topi, last_topl, last_topk, ids, logprobs, cap_rows, n_rows, k);
+    }
+    static void topk_out(const std::vector<int32_t>& ti, const std::vector<float>& tl, int kk, int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) {
+        const int m = (int)ti.size() / kk;
+        for (int q = 0; q < (m < cap_rows ? m : cap_rows) * kk; ++q) { ids[q] = ti[q]; logprobs[q] = tl[q]; }
+        *n_rows = m; *k = kk;
+    }
+    void batch_topk(int slot, int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) override {
+        REQUIRE(slot >= 0 && slot < MAXB && jobs[slot].used && jobs[slot].finished, "no finished turn in this slot");
+        const Job& j = jobs[slot];
+        REQUIRE(j.topk > 0, "svln_batch_topk: top-k log-probabilities were off for this turn (svln_top_logprobs)");
+        topk_out(j.topi, j.topl, j.topk, ids, logprobs, cap_rows, n_rows, k);
+    }
+    void generate_batch_topk(int index, int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) override {
+        REQUIRE(gb_topk_valid, "svln_generate_batch_topk: top-k log-probabilities were off for the last svln_generate_batch (svln_top_logprobs), or none has run");
+        REQUIRE(index >= 0 && index < (int)gb_topi.size(), "svln_generate_batch_topk: no such env index in the last batch");
+        topk_out(gb_topi[index], gb_topl[index], gb_topk, ids, logprobs, cap_rows, n_rows, k);
     }
     void get_token_scores(float* out, int cap, int32_t* n) override {
         REQUIRE(last_scores_valid, "svln_get_token_scores: token log-probabilities were off for the last turn (svln_set_token_scores), or no turn has run");
@@ -1921,6 +2003,7 @@ public:
         int env = -1, max_new = 0, count = 0, last_tok = -1;
         std::vector<int64_t> out, eos;
         std::vector<float> scores; bool scored = false;      // svln_set_token_scores: log-probability of every id of `out`
+        std::vector<int32_t> topi; std::vector<float> topl; int topk = 0;      // svln_top_logprobs: the [topk] lists of every id of `out`
         std::vector<float> alp; int alp_n = 0;               // with svln_set_allowed_tokens too: the normalised row [alp_n] of every id of `out`
         std::vector<int> draft;      // svln_set_batch_draft: the usable draft the submit consumed, kept until the job's prefill iteration
     };
@@ -1995,7 +2078,7 @@ public:
         j = Job();
         j.used = true; j.env = env; j.max_new = max_new < c.max_positions ? max_new : c.max_positions;
         j.eos.assign(eos, eos + n_eos);
-        j.scored = scores_on;
+        j.scored = scores_on; j.topk = topk;
         j.alp_n = scores_on && allow_on ? allow_n : 0;
         n_generated_b[slot] = 0;
         // svln_set_batch_draft: the env's armed draft is consumed by the submit whether or not it helps (the rule of svln_generate); usable:
@@ -2060,7 +2143,7 @@ public:
     // the pure batched decode step for B rows (d_slots / d_tok_b / d_smp set): the launches, or their captured graph
     void batched_step(int B, bool pen) {
         if (use_graph) {
-            const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0) | (fp8_gemm_on && fp8_scaled_on ? 2048 : 0) | (scores_on ? 4096 : 0) | (smp_on ? 8192 : 0);
+            const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0) | (fp8_gemm_on && fp8_scaled_on ? 2048 : 0) | (scores_on ? 4096 : 0) | (smp_on ? 8192 : 0) | (topk << 16);
             auto it = bgraphs.find(key);
             if (it == bgraphs.end())      // (a failed capture leaves no entry behind)
                 it = bgraphs.emplace(key, capture_graph([&] { decode_ops_batched(B, pen); })).first;
@@ -2183,6 +2266,10 @@ public:
         HIP_CHECK(hipMemcpyAsync(h_tok_b + head0, d_tok_b, n_head * sizeof(int), hipMemcpyDeviceToHost, st));
         if (scores_on) HIP_CHECK(hipMemcpyAsync(h_score_b + head0, d_score_b, n_head * sizeof(float), hipMemcpyDeviceToHost, st));      // (never split: the switches exclude each other)
         if (scores_on && allow_on) HIP_CHECK(hipMemcpyAsync(h_alp_b + (size_t)head0 * allow_n, d_alp_b, (size_t)n_head * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (topk) {
+            HIP_CHECK(hipMemcpyAsync(h_topi_b + (size_t)head0 * topk, d_topi_b, (size_t)n_head * topk * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(h_topl_b + (size_t)head0 * topk, d_topl_b, (size_t)n_head * topk * sizeof(float), hipMemcpyDeviceToHost, st));
+        }
         HIP_CHECK(hipStreamSynchronize(st));
         LAUNCH_CHECK("batch_step");
         {
@@ -2213,6 +2300,10 @@ public:
                 REQUIRE(tok >= 0 && tok < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
                 j.out.push_back(tok);
                 if (j.scored) j.scores.push_back(h_score_b[hq + i]);
+                if (j.topk) {
+                    j.topi.insert(j.topi.end(), h_topi_b + (size_t)(hq + i) * j.topk, h_topi_b + (size_t)(hq + i + 1) * j.topk);
+                    j.topl.insert(j.topl.end(), h_topl_b + (size_t)(hq + i) * j.topk, h_topl_b + (size_t)(hq + i + 1) * j.topk);
+                }
                 if (j.alp_n > 0) j.alp.insert(j.alp.end(), h_alp_b + (size_t)(hq + i) * j.alp_n, h_alp_b + (size_t)(hq + i + 1) * j.alp_n);
                 if (smp_on) env_draws[j.env] += 1;
                 j.count += 1;
@@ -2265,7 +2356,7 @@ public:
             for (int t = 0; t < s; ++t) REQUIRE(env_ids[t] != env_ids[s], "duplicate env in batch");
         for (int s = 0; s < n_envs; ++s) refuse_while_group_on(env_ids[s], "svln_generate_batch");
         std::vector<int> slots(n_envs);
-        gb_scores_valid = false; gb_alp_valid = false;
+        gb_scores_valid = false; gb_alp_valid = false; gb_topk_valid = false;
         try {
             for (int s = 0; s < n_envs; ++s) slots[s] = batch_submit(env_ids[s], max_new < cap ? max_new : cap, eos, n_eos);
             int32_t fin[MAXB], nf = 0;
@@ -2275,14 +2366,17 @@ public:
             throw;
         }
         gb_scores.assign(n_envs, std::vector<float>());
+        gb_topi.assign(n_envs, std::vector<int32_t>()); gb_topl.assign(n_envs, std::vector<float>());
         gb_alp.assign(n_envs, std::vector<float>());
         for (int s = 0; s < n_envs; ++s) {
             int32_t env = 0;
             if (scores_on) gb_scores[s] = jobs[slots[s]].scores;
+            if (topk) { gb_topi[s] = jobs[slots[s]].topi; gb_topl[s] = jobs[slots[s]].topl; }
             if (scores_on && allow_on) gb_alp[s] = jobs[slots[s]].alp;
             batch_result(slots[s], &env, out + (size_t)s * cap, cap, &n_out[s]);
         }
         gb_scores_valid = scores_on;          // (only once every env's scores are in place)
+        gb_topk = topk; gb_topk_valid = topk > 0;
         gb_alp_n = allow_n; gb_alp_valid = scores_on && allow_on;
     }
     void get_hidden_batch(int slot, float* out, int max_rows, int32_t* n_rows) override {
@@ -2307,7 +2401,7 @@ public:
     void generate(int env, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, bool fixed) override {
         Env& e = env_at(env);
         refuse_while_group_on(env, "svln_generate");
-        last_scores_valid = false; last_alp_valid = false;
+        last_scores_valid = false; last_alp_valid = false; last_topk_valid = false;
         const bool had_draft = disarm_draft(env);      // consumed by this call whether it helps, is ignored or the call fails
         REQUIRE(weights_missing() == 0, g_err);
         const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
@@ -2452,6 +2546,10 @@ public:
             HIP_CHECK(hipMemcpyAsync(h_out_ids, d_out_ids, (size_t)enq * sizeof(int), hipMemcpyDeviceToHost, st));
             if (scores_on) HIP_CHECK(hipMemcpyAsync(h_scores, d_scores, (size_t)enq * sizeof(float), hipMemcpyDeviceToHost, st));
             if (scores_on && allow_on) HIP_CHECK(hipMemcpyAsync(h_alp, d_alp, (size_t)enq * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
+            if (topk) {
+                HIP_CHECK(hipMemcpyAsync(h_topi, d_topi, (size_t)enq * topk * sizeof(int), hipMemcpyDeviceToHost, st));
+                HIP_CHECK(hipMemcpyAsync(h_topl, d_topl, (size_t)enq * topk * sizeof(float), hipMemcpyDeviceToHost, st));
+            }
             HIP_CHECK(hipMemcpyAsync(h_top2, d_top2, 2 * sizeof(float), hipMemcpyDeviceToHost, st));
             if (persistent_on) HIP_CHECK(hipMemcpyAsync(h_giveup, dl_giveup, sizeof(unsigned), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
@@ -2475,6 +2573,10 @@ public:
         for (int k = 0; k < n; ++k) out[k] = h_out_ids[k];
         if (scores_on) { last_scores.assign(h_scores, h_scores + n); last_scores_valid = true; }      // (the draft modes are off: every id left the scored arg-max step)
         if (scores_on && allow_on) { last_alp.assign(h_alp, h_alp + (size_t)n * allow_n); last_alp_n = allow_n; last_alp_valid = true; }
+        if (topk) {
+            last_topi.assign(h_topi, h_topi + (size_t)n * topk); last_topl.assign(h_topl, h_topl + (size_t)n * topk);
+            last_topk = topk; last_topk_valid = true;
+        }
         e.kv_len = L + n - 1;             // EOS (or the last token) is appended to the ids but never fed
         {
             float t = 0.f;
@@ -2496,6 +2598,7 @@ public:
     void group_refusals(int env, int n_seq) {
         env_at(env);
         REQUIRE(n_seq >= 2 && n_seq <= MAXB, "svln_generate_group: n_seq must be 2 .. 8");
+        refuse_while_topk("svln_generate_group");
         refuse_while_plain_head_only("svln_generate_group");     // (svln_set_sampling is refused under each of them: name the cause)
         REQUIRE(smp_on, "svln_generate_group: temperature sampling is off (svln_set_sampling): greedy sequences would be identical");
         REQUIRE(rep_penalty == 1.0f, "svln_generate_group: a repetition penalty != 1 is set (svln_set_repetition_penalty); a group does not support it");
@@ -2521,7 +2624,7 @@ public:
                 "svln_generate_group: the free KV pages cannot hold the env's own pages and (n_seq - 1) x the tail pages of the fork");
         // ---- nothing was launched or changed up to here
         disarm_draft(env);
-        last_scores_valid = false; last_alp_valid = false;
+        last_scores_valid = false; last_alp_valid = false; last_topk_valid = false;
         int B = 2; while (B < n_seq) B <<= 1;
         for (int g = 1; g < n_seq; ++g)
             if (!fork_tab[g]) { fork_tab[g] = dalloc<int>(pages_per_env, true); fork_host[g].assign(pages_per_env, 0); }
@@ -2718,7 +2821,7 @@ public:
         REQUIRE(Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
         REQUIRE((int64_t)L + n - 1 <= c.max_positions, "svln_generate_forced: n_embeds + n - 1 exceeds max_positions");
         // ---- nothing was launched or changed up to here (but the armed draft)
-        last_scores_valid = false; last_alp_valid = false;
+        last_scores_valid = false; last_alp_valid = false; last_topk_valid = false;
         set_speculative_buffers();      // d_draft / h_draft: the fed ids
         ensure_forced_buffers();
         ensure_pages(e, L + n - 1);
@@ -3277,7 +3380,8 @@ public:
     }
     // TEST-ONLY: one lm_head product in its plain (host_logprob null: EPI_ARGMAX) or scored (EPI_ARGMAX_LSE) form with optional penalty flags
     // smp: the sampled form (EPI_SAMPLE) on the given temperature, seed, streams and draws, whatever the engine's own switch says
-    void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob, const OpSample* smp) override {
+    // the refusals the single-env head's test entries share (max_lds: the dynamic LDS the instantiation may ask for)
+    void head_op_refusals(const GemvArgs& a, const int32_t* host_token, int max_lds) {
         REQUIRE(a.w8 == nullptr || sizeof(T) == 2, "fp8 weights need the bf16 engine");
         REQUIRE(a.w4 == nullptr || sizeof(T) == 2, "MXFP4 weights need the bf16 engine");
         p12_refusals(a);
@@ -3285,8 +3389,11 @@ public:
         REQUIRE(a.x && host_token && (a.w4 ? a.e8 != nullptr : a.w8 ? a.scale != nullptr : a.W != nullptr), "null pointer");
         REQUIRE(a.N >= 1 && a.K >= chunk && a.K % chunk == 0, "N >= 1, K a positive multiple of the format's 16-byte chunk");
         REQUIRE(a.ldw >= a.K && a.ldw % chunk == 0, "ldw >= K, a multiple of the format's 16-byte chunk (aligned row loads)");
-        REQUIRE((size_t)a.K * sizeof(float) <= (size_t)GEMV_ROWS_MAX_LDS, "the wave-per-rows kernel stages K fp32 activations in LDS: K too large");
+        REQUIRE((size_t)a.K * sizeof(float) <= (size_t)max_lds, "the wave-per-rows kernel stages K fp32 activations in LDS: K too large");
         REQUIRE(!a.pen_flags || a.pen > 0.0f, "penalty flags need a factor > 0");
+    }
+    void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob, const OpSample* smp) override {
+        head_op_refusals(a, host_token, GEMV_ROWS_MAX_LDS);
         a.epi = smp ? EPI_SAMPLE : host_logprob ? EPI_ARGMAX_LSE : EPI_ARGMAX;
         a.part_val = part_val; a.part_idx = part_idx; a.part_sum = part_sum;
         if (smp) a.smp = op_sample_args(*smp, 1, part_raw, part_max, host_logprob != nullptr);
@@ -3297,6 +3404,34 @@ public:
         if (host_logprob) *host_logprob = h_scores[0];
         LAUNCH_CHECK("op_gemv_scores");
     }
+    // TEST-ONLY: the single-env head with svln_top_logprobs on -- the EPI_*_TOPK product, the scored (or, with smp, sampled) final kernel
+    // and topk_merge_kernel -- on caller-given operands; everything the three launches wrote goes to the host
+    void op_gemv_topk(GemvArgs a, int k, const OpSample* smp, int32_t* host_token, float* host_logprob, float* pv, int32_t* pi, float* ps,
+                      float* pr, float* pm, float* cv, int32_t* ci, int32_t* top_ids, float* top_lp, int32_t* n_part) override {
+        head_op_refusals(a, host_token, GEMV_ROWS_TOPK_MAX_LDS);
+        REQUIRE(host_logprob && pv && pi && ps && cv && ci && top_ids && top_lp && n_part && (!smp || (pr && pm)), "null output pointer");
+        REQUIRE(k >= 1 && k <= TOPK_C, "k must be 1 .. 8");
+        const int np = gemv_grid(a.N);
+        ensure_topk_buffers();
+        float* d_cv = cand_val_b; int *d_ci = cand_idx_b, *d_ti = d_topi_b; float* d_tl = d_topl_b;      // (the batched heads' buffers: idle in a test entry)
+        a.part_val = part_val; a.part_idx = part_idx; a.part_sum = part_sum;
+        if (smp) a.smp = op_sample_args(*smp, 1, part_raw, part_max, true);
+        a.epi = smp ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK; a.cand_val = d_cv; a.cand_idx = d_ci;
+        launch_gemv<T>(st, a);
+        launch_topk_merge(st, d_cv, d_ci, np, TOPK_C, 1, k, part_val, part_idx, part_sum, a.smp.part_max, d_ti, d_tl);
+        launch_argmax_final(st, part_val, part_idx, np, d_token, d_top2, part_sum, d_scores, a.smp.part_raw, a.smp.part_max);
+        hipError_t err = hipMemcpyAsync(h_scores, d_scores, sizeof(float), hipMemcpyDeviceToHost, st);
+        auto back = [&](void* dst, const void* src, size_t bytes) { if (err == hipSuccess) err = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); };
+        back(pv, part_val, np * sizeof(float)); back(pi, part_idx, np * sizeof(int)); back(ps, part_sum, np * sizeof(float));
+        if (smp) { back(pr, part_raw, np * sizeof(float)); back(pm, part_max, np * sizeof(float)); }
+        back(cv, d_cv, (size_t)np * TOPK_C * sizeof(float)); back(ci, d_ci, (size_t)np * TOPK_C * sizeof(int));
+        back(top_ids, d_ti, k * sizeof(int)); back(top_lp, d_tl, k * sizeof(float));
+        back(h_token, d_token, sizeof(int));
+        const hipError_t err2 = hipStreamSynchronize(st);
+        HIP_CHECK(err); HIP_CHECK(err2);
+        *host_token = h_token[0]; *host_logprob = h_scores[0]; *n_part = np;
+        LAUNCH_CHECK("op_gemv_topk");
+    }
     void batched_scores_out(int B, int32_t* host_tokens, float* host_logprobs, const char* who) {
         HIP_CHECK(hipMemcpyAsync(h_tok_b, d_tok_b, B * sizeof(int), hipMemcpyDeviceToHost, st));
         if (host_logprobs) HIP_CHECK(hipMemcpyAsync(h_score_b, d_score_b, B * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -3304,23 +3439,44 @@ public:
         LAUNCH_CHECK(who);
         for (int b = 0; b < B; ++b) { host_tokens[b] = h_tok_b[b]; if (host_logprobs) host_logprobs[b] = h_score_b[b]; }
     }
-    void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp) override {
+    // the batched test entries under svln_top_logprobs: stage the candidate form (before the launch) ...
+    void op_topk_rows_refusals(const OpTopkRows* tk, const float* host_logprobs) {
+        if (!tk) return;
+        REQUIRE(host_logprobs && tk->cv && tk->ci && tk->top_ids && tk->top_lp && tk->n_part, "null output pointer");
+        REQUIRE(tk->k >= 1 && tk->k <= TOPK_C, "k must be 1 .. 8");
+    }
+    // ... and run the merge and read candidates and lists back (after the final kernel)
+    void op_topk_rows_out(const OpTopkRows& tk, int rows, int n, const float* pm) {
+        launch_topk_merge(st, cand_val_b, cand_idx_b, n, TOPK_C, rows, tk.k, part_val_b, part_idx_b, part_sum_b, pm, d_topi_b, d_topl_b);
+        const size_t nc = (size_t)rows * n * TOPK_C;
+        HIP_CHECK(hipMemcpyAsync(tk.cv, cand_val_b, nc * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(tk.ci, cand_idx_b, nc * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(tk.top_ids, d_topi_b, (size_t)rows * tk.k * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(tk.top_lp, d_topl_b, (size_t)rows * tk.k * sizeof(float), hipMemcpyDeviceToHost, st));
+        *tk.n_part = n;
+    }
+    void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk) override {
         REQUIRE(a.W && a.x && host_tokens, "null pointer");
         REQUIRE(a.B == 1 || a.B == 2 || a.B == 4 || a.B == 8, "B must be 1, 2, 4 or 8");
         REQUIRE(a.N >= 1 && a.K >= Elt<T>::PER_CHUNK && a.K % Elt<T>::PER_CHUNK == 0, "N >= 1, K a positive multiple of the 16-byte chunk");
         REQUIRE(a.ldw >= a.K && a.ldw % Elt<T>::PER_CHUNK == 0 && a.ldx >= a.K && a.ldx % Elt<T>::PER_CHUNK == 0, "ldw, ldx >= K, multiples of the 16-byte chunk");
         REQUIRE(!a.pen_flags || (a.pen_rows && a.pen > 0.0f), "penalty flags come with their row table and a factor > 0");
         REQUIRE(!smp || !a.norm_w, "the sampled batched GEMV has no fused-norm form");
-        a.epi = smp ? EPI_SAMPLE : host_logprobs ? EPI_ARGMAX_LSE : EPI_ARGMAX;
+        REQUIRE(!tk || !a.norm_w, "the candidate form of the batched GEMV has no fused-norm form");
+        op_topk_rows_refusals(tk, host_logprobs);
+        if (tk) ensure_topk_buffers();
+        a.epi = tk ? (smp ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK) : smp ? EPI_SAMPLE : host_logprobs ? EPI_ARGMAX_LSE : EPI_ARGMAX;
+        a.cand_val = cand_val_b; a.cand_idx = cand_idx_b;
         a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b;
         a.row_scale = row_scale_b;
         if (smp) a.smp = op_sample_args(*smp, a.B, part_raw_b, part_max_b, host_logprobs != nullptr);
         launch_gemv_batched<T>(st, a);
         launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), a.B, d_tok_b, host_logprobs ? part_sum_b : nullptr, d_score_b,
                                     host_logprobs && a.norm_w ? a.row_scale : nullptr, a.smp.part_raw, a.smp.part_max);
+        if (tk) op_topk_rows_out(*tk, a.B, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), a.smp.part_max);
         batched_scores_out(a.B, host_tokens, host_logprobs, "op_gemv_batched_scores");
     }
-    void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp) override {
+    void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk) override {
         constexpr int chunk = Elt<T>::PER_CHUNK;
         REQUIRE(a.A && a.W && host_tokens, "null pointer");
         REQUIRE(a.M >= 1 && a.M <= 32 && a.N >= 1 && (a.N + 127) / 128 <= 2048, "1 <= M <= 32 rows, 1 <= N <= 262144");
@@ -3328,11 +3484,15 @@ public:
                 "K a positive multiple of the 16-byte chunk; lda, ldw >= K, multiples of it (aligned LDS-DMA)");
         REQUIRE(((size_t)a.A & 15) == 0 && ((size_t)a.W & 15) == 0, "A and W must be 16-byte aligned (LDS-DMA)");
         REQUIRE(!a.pen_flags || (a.pen_rows && a.pen > 0.0f), "penalty flags come with their row table and a factor > 0");
+        op_topk_rows_refusals(tk, host_logprobs);
+        if (tk) ensure_topk_buffers();
         a.zeros = zero_line; a.epi = EPI_ARGMAX;
         a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = host_logprobs ? part_sum_b : nullptr;
         if (smp) a.smp = op_sample_args(*smp, a.M, part_raw_b, part_max_b, host_logprobs != nullptr);
+        if (tk) { a.cand_val = cand_val_b; a.cand_idx = cand_idx_b; }
         const int n = launch_gemm_argmax<T>(st, a);
         launch_argmax_final_batched(st, part_val_b, part_idx_b, n, a.M, d_tok_b, a.part_sum, d_score_b, nullptr, a.smp.part_raw, a.smp.part_max);
+        if (tk) op_topk_rows_out(*tk, a.M, n, a.smp.part_max);
         batched_scores_out(a.M, host_tokens, host_logprobs, "op_gemm_argmax_scores");
     }
     void op_gemv_batched(GemvBatchArgs a, int32_t* host_tokens) override {
@@ -3895,6 +4055,10 @@ int svln_get_embeds(svln_engine* h, int env, int start, int n, float* out) { API
 int svln_get_frame_feats(svln_engine* h, int start, int n, float* out) { API_BEGIN_H h->impl->get_feats(start, n, out); API_END }
 int svln_get_top2(svln_engine* h, float* out) { API_BEGIN_H h->impl->get_top2(out); API_END }
 int svln_set_token_scores(svln_engine* h, int enable) { API_BEGIN_H h->impl->set_token_scores(enable); API_END }
+int svln_top_logprobs(svln_engine* h, int k) { API_BEGIN_H h->impl->top_logprobs(k); API_END }
+int svln_get_topk(svln_engine* h, int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) {
+    API_BEGIN_H REQUIRE(ids && logprobs && n_rows && k && cap_rows >= 0, "null output pointer"); h->impl->get_topk(ids, logprobs, cap_rows, n_rows, k); API_END
+}
 int svln_get_token_scores(svln_engine* h, float* out, int cap, int32_t* n) {
     API_BEGIN_H REQUIRE(out && n && cap >= 0, "null output pointer"); h->impl->get_token_scores(out, cap, n); API_END
 }
@@ -3904,8 +4068,10 @@ int svln_batch_scores(svln_engine* h, int slot, float* out, int cap, int32_t* n)
 int svln_generate_batch_scores(svln_engine* h, int index, float* out, int cap, int32_t* n) {
     API_BEGIN_H REQUIRE(out && n && cap >= 0, "null output pointer"); h->impl->generate_batch_scores(index, out, cap, n); API_END
 }
+// the outputs of svln_op_gemv_argmax_topk beyond token and score (null: the scored / sampled entries)
+struct OpTopkOut { int k; float* pv; int32_t* pi; float *ps, *pr, *pm, *cv; int32_t *ci, *top_ids; float* top_lp; int32_t* n_part; };
 static int op_gemv_argmax_any(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
-                              float penalty, int32_t* host_token, float* host_logprob, const OpSample* smp) {
+                              float penalty, int32_t* host_token, float* host_logprob, const OpSample* smp, const OpTopkOut* tk = nullptr) {
     API_BEGIN_H
     REQUIRE(fmt >= 0 && fmt <= 3, "fmt: 0 = engine dtype, 1 = e4m3 + row scales, 2 = MXFP4, 3 = 12-bit packing");
     GemvArgs a; a.W = nullptr; a.ldw = ldw; a.x = x; a.norm_w = nullptr; a.eps = 0.0f; a.bias = nullptr; a.res = nullptr; a.y = nullptr; a.N = N; a.K = K;
@@ -3919,7 +4085,8 @@ static int op_gemv_argmax_any(svln_engine* h, int fmt, const void* W, const void
     }
     REQUIRE(W, "null pointer");
     a.pen_flags = (const uint8_t*)pen_flags; a.pen = penalty;
-    h->impl->op_gemv_scores(a, host_token, host_logprob, smp);
+    if (tk) h->impl->op_gemv_topk(a, tk->k, smp, host_token, host_logprob, tk->pv, tk->pi, tk->ps, tk->pr, tk->pm, tk->cv, tk->ci, tk->top_ids, tk->top_lp, tk->n_part);
+    else h->impl->op_gemv_scores(a, host_token, host_logprob, smp);
     API_END
 }
 int svln_op_gemv_argmax_scores(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
@@ -3931,14 +4098,22 @@ int svln_op_gemv_argmax_sample(svln_engine* h, int fmt, const void* W, const voi
     const OpSample q{temperature, seed, &stream, &draw};
     return op_gemv_argmax_any(h, fmt, W, aux, ldw, x, N, K, pen_flags, penalty, host_token, host_logprob, &q);
 }
+int svln_op_gemv_argmax_topk(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
+                             float penalty, int k, int sampled, float temperature, uint64_t seed, int32_t stream, int32_t draw, int32_t* host_token,
+                             float* host_logprob, float* part_val, int32_t* part_idx, float* part_sum, float* part_raw, float* part_max,
+                             float* cand_val, int32_t* cand_idx, int32_t* top_ids, float* top_logprobs, int32_t* n_part) {
+    const OpSample q{temperature, seed, &stream, &draw};
+    const OpTopkOut tk{k, part_val, part_idx, part_sum, part_raw, part_max, cand_val, cand_idx, top_ids, top_logprobs, n_part};
+    return op_gemv_argmax_any(h, fmt, W, aux, ldw, x, N, K, pen_flags, penalty, host_token, host_logprob, sampled ? &q : nullptr, &tk);
+}
 static int op_gemv_batched_argmax_any(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
                                       const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs,
-                                      const OpSample* smp) {
+                                      const OpSample* smp, const OpTopkRows* tk = nullptr) {
     API_BEGIN_H
     GemvBatchArgs a; a.W = W; a.ldw = ldw; a.x = x; a.ldx = ldx; a.norm_w = norm_w; a.eps = eps; a.bias = nullptr; a.res = nullptr; a.ldr = 0;
     a.y = nullptr; a.ldy = 0; a.N = N; a.K = K; a.epi = EPI_ARGMAX; a.B = B; a.part_val = nullptr; a.part_idx = nullptr;
     a.pen_flags = (const uint8_t*)pen_flags; a.pen_rows = pen_rows; a.pen = penalty;
-    h->impl->op_gemv_batched_scores(a, host_tokens, host_logprobs, smp);
+    h->impl->op_gemv_batched_scores(a, host_tokens, host_logprobs, smp, tk);
     API_END
 }
 int svln_op_gemv_batched_argmax_scores(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
@@ -3952,12 +4127,13 @@ int svln_op_gemv_batched_argmax_sample(svln_engine* h, const void* W, int ldw, c
     return op_gemv_batched_argmax_any(h, W, ldw, x, ldx, norm_w, eps, N, K, B, pen_flags, pen_rows, penalty, host_tokens, host_logprobs, &q);
 }
 static int op_gemm_argmax_any(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
-                              const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs, const OpSample* smp) {
+                              const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs, const OpSample* smp,
+                              const OpTopkRows* tk = nullptr) {
     API_BEGIN_H
     GemmArgs a; std::memset(&a, 0, sizeof(a));
     a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.epi = EPI_ARGMAX; a.nsplit = 1;
     a.pen_flags = (const uint8_t*)pen_flags; a.pen_rows = pen_rows; a.pen = penalty;
-    h->impl->op_gemm_argmax_scores(a, host_tokens, host_logprobs, smp);
+    h->impl->op_gemm_argmax_scores(a, host_tokens, host_logprobs, smp, tk);
     API_END
 }
 int svln_op_gemm_argmax_scores(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
@@ -3969,6 +4145,28 @@ int svln_op_gemm_argmax_sample(svln_engine* h, const void* A, int lda, const voi
                                const int32_t* draws, int32_t* host_tokens, float* host_logprobs) {
     const OpSample q{temperature, seed, streams, draws};
     return op_gemm_argmax_any(h, A, lda, W, ldw, M, N, K, pen_flags, pen_rows, penalty, host_tokens, host_logprobs, &q);
+}
+int svln_op_gemv_batched_argmax_topk(svln_engine* h, const void* W, int ldw, const void* x, int ldx, int N, int K, int B, const void* pen_flags,
+                                     const int32_t* pen_rows, float penalty, int k, int sampled, float temperature, uint64_t seed, const int32_t* streams,
+                                     const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* cand_val, int32_t* cand_idx,
+                                     int32_t* top_ids, float* top_logprobs, int32_t* n_part) {
+    const OpSample q{temperature, seed, streams, draws};
+    const OpTopkRows tk{k, cand_val, cand_idx, top_ids, top_logprobs, n_part};
+    return op_gemv_batched_argmax_any(h, W, ldw, x, ldx, nullptr, 0.0f, N, K, B, pen_flags, pen_rows, penalty, host_tokens, host_logprobs, sampled ? &q : nullptr, &tk);
+}
+int svln_op_gemm_argmax_topk(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
+                             const int32_t* pen_rows, float penalty, int k, int sampled, float temperature, uint64_t seed, const int32_t* streams,
+                             const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* cand_val, int32_t* cand_idx, int32_t* top_ids,
+                             float* top_logprobs, int32_t* n_part) {
+    const OpSample q{temperature, seed, streams, draws};
+    const OpTopkRows tk{k, cand_val, cand_idx, top_ids, top_logprobs, n_part};
+    return op_gemm_argmax_any(h, A, lda, W, ldw, M, N, K, pen_flags, pen_rows, penalty, host_tokens, host_logprobs, sampled ? &q : nullptr, &tk);
+}
+int svln_batch_topk(svln_engine* h, int slot, int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) {
+    API_BEGIN_H REQUIRE(ids && logprobs && n_rows && k && cap_rows >= 0, "null output pointer"); h->impl->batch_topk(slot, ids, logprobs, cap_rows, n_rows, k); API_END
+}
+int svln_generate_batch_topk(svln_engine* h, int index, int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) {
+    API_BEGIN_H REQUIRE(ids && logprobs && n_rows && k && cap_rows >= 0, "null output pointer"); h->impl->generate_batch_topk(index, ids, logprobs, cap_rows, n_rows, k); API_END
 }
 int svln_set_sampling(svln_engine* h, int enable, float temperature, uint64_t seed) { API_BEGIN_H h->impl->set_sampling(enable, temperature, seed); API_END }
 int svln_set_allowed_tokens(svln_engine* h, const int64_t* ids, int n) { API_BEGIN_H h->impl->set_allowed_tokens(ids, n); API_END }

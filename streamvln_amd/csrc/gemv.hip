@@ -375,7 +375,23 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
     const int gw = blockIdx.x * GEMV_WAVES + wave, nw = gridDim.x * GEMV_WAVES;
     const int n_out = EPI == EPI_SWIGLU ? p.N >> 1 : p.N;
 
-    constexpr bool AMAX = epi_is_argmax(EPI), LSE = EPI == EPI_ARGMAX_LSE, SMP = EPI == EPI_SAMPLE;
+    constexpr bool AMAX = epi_is_argmax(EPI), TOPK = epi_is_topk(EPI);
+    constexpr bool LSE = EPI == EPI_ARGMAX_LSE || EPI == EPI_ARGMAX_LSE_TOPK, SMP = EPI == EPI_SAMPLE || EPI == EPI_SAMPLE_TOPK;
+    // EPI_*_TOPK: the wave's TOPK_C best (y, column) pairs, entry l in lane l < TOPK_C, y descending then column ascending; a logit is
+    // wave-uniform, so is tk_thr = entry TOPK_C - 1, and the common case of a column costs one scalar compare against it
+    [[maybe_unused]] float tk_v = -INFINITY, tk_thr = -INFINITY;
+    [[maybe_unused]] int tk_i = 0x7FFFFFFF;
+    [[maybe_unused]] auto tk_insert = [&](float y, int col) {
+        if (!(y > tk_thr)) return;                // NaN, -inf, or not above the last entry (columns ascend: an equal value stays behind)
+        const float up_v = __shfl_up(tk_v, 1, 64);
+        const int up_i = __shfl_up(tk_i, 1, 64);
+        if (!(tk_v >= y)) {                       // entries at or above y stay; y lands behind them and the rest moves down one lane
+            const bool here = lane == 0 || up_v >= y;
+            tk_v = here ? y : up_v;
+            tk_i = here ? col : up_i;
+        }
+        tk_thr = __shfl(tk_v, TOPK_C - 1, 64);
+    };
     float best = -INFINITY;                       // EPI_ARGMAX (EPI_SAMPLE: the best perturbed value z)
     int best_i = 0x7FFFFFFF;
     float lm = -INFINITY, ls = 0.0f;              // EPI_ARGMAX_LSE: wave-uniform (max, sum exp(l - max)) over the wave's rows (EPI_SAMPLE: over y)
@@ -418,6 +434,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
                     if (n0 + r < p.N) {
                         if (z > best) { best = z; best_i = n0 + r; best_raw = y; }         // rows ascend: first max wins
                         lse_add(y, lm, ls);
+                        if constexpr (TOPK) tk_insert(y, n0 + r);
                     }
                 }
             } else {
@@ -428,7 +445,10 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
             if (LSE) {                            // the penalised values; the repeated rows of a ragged last group (n0 + r >= N) count once
 #pragma unroll
                 for (int r = 0; r < R; ++r)
-                    if (n0 + r < p.N) lse_add(acc[r], lm, ls);
+                    if (n0 + r < p.N) {
+                        lse_add(acc[r], lm, ls);
+                        if constexpr (TOPK) tk_insert(acc[r], n0 + r);
+                    }
             }
         } else if (lane < R && n0 + lane < p.N) {
             store_out<X>(p, n0 + lane, lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3]);
@@ -437,6 +457,28 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
     if (AMAX) {
         __shared__ float bv[GEMV_WAVES];
         __shared__ int bi[GEMV_WAVES];
+        if constexpr (TOPK) {
+            // the four waves' lists -> the workgroup's: candidate t is entry t % TOPK_C of wave t / TOPK_C; its place is the number of
+            // candidates before it in (y descending, column ascending) order -- padding, all alike, keeps its own order -- so the places
+            // are a permutation and the first TOPK_C of them are the partial's list
+            __shared__ float cv[GEMV_WAVES * TOPK_C];
+            __shared__ int ci[GEMV_WAVES * TOPK_C];
+            if (lane < TOPK_C) { cv[wave * TOPK_C + lane] = tk_v; ci[wave * TOPK_C + lane] = tk_i; }
+            __syncthreads();
+            if (threadIdx.x < GEMV_WAVES * TOPK_C) {
+                const int t = threadIdx.x;
+                const float v = cv[t];
+                const int i = ci[t];
+                int place = 0;
+#pragma unroll
+                for (int o = 0; o < GEMV_WAVES * TOPK_C; ++o)
+                    place += cv[o] > v || (cv[o] == v && (ci[o] < i || (ci[o] == i && o < t)));
+                if (place < TOPK_C) {
+                    p.cand_val[(size_t)blockIdx.x * TOPK_C + place] = v;
+                    p.cand_idx[(size_t)blockIdx.x * TOPK_C + place] = i;
+                }
+            }
+        }
         if (lane == 0) { bv[wave] = best; bi[wave] = best_i; }
         if constexpr (SMP) {
             __shared__ float bs[GEMV_WAVES], bm[GEMV_WAVES], br[GEMV_WAVES];
@@ -569,7 +611,30 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
     const T* xg = (const T*)p.x;
     const T* gg = (const T*)p.norm_w;
     const int n_units = EPI == EPI_SWIGLU ? p.N / R : (p.N + R - 1) / R;      // one unit = R weight rows
-    constexpr bool AMAX = epi_is_argmax(EPI), TGT = EPI == EPI_TARGET, LSE = EPI == EPI_ARGMAX_LSE || TGT, SMP = EPI == EPI_SAMPLE;
+    constexpr bool AMAX = epi_is_argmax(EPI), TGT = EPI == EPI_TARGET, TOPK = epi_is_topk(EPI);
+    constexpr bool LSE = EPI == EPI_ARGMAX_LSE || EPI == EPI_ARGMAX_LSE_TOPK || TGT, SMP = EPI == EPI_SAMPLE || EPI == EPI_SAMPLE_TOPK;
+    static_assert(!(TOPK && NORM), "EPI_*_TOPK has no fused-norm form");
+    // EPI_*_TOPK: thread b < B keeps env b's TOPK_C best (y, column) pairs of the workgroup's units in registers, y descending then column
+    // ascending (static indices: the insertion is an unrolled shift).  Units and their columns ascend, so an equal value stays behind.
+    [[maybe_unused]] float tk_v[TOPK ? TOPK_C : 1];
+    [[maybe_unused]] int tk_i[TOPK ? TOPK_C : 1];
+    if constexpr (TOPK) {
+#pragma unroll
+        for (int e = 0; e < TOPK_C; ++e) { tk_v[e] = -INFINITY; tk_i[e] = 0x7FFFFFFF; }
+    }
+    [[maybe_unused]] auto tk_insert = [&](float y, int col) {
+        if constexpr (TOPK) {
+            if (!(y > tk_v[TOPK_C - 1])) return;      // NaN, -inf, or not above the last entry
+            bool placed = false;
+#pragma unroll
+            for (int e = TOPK_C - 1; e >= 1; --e) {
+                if (placed) continue;
+                if (tk_v[e - 1] >= y) { tk_v[e] = y; tk_i[e] = col; placed = true; }
+                else { tk_v[e] = tk_v[e - 1]; tk_i[e] = tk_i[e - 1]; }
+            }
+            if (!placed) { tk_v[0] = y; tk_i[0] = col; }
+        }
+    };
     static_assert(!(SMP && NORM), "EPI_SAMPLE has no fused-norm form");
     static_assert(!(TGT && NORM), "EPI_TARGET has no fused-norm form");
     [[maybe_unused]] int my_tgt = -1;                                         // EPI_TARGET: thread b < B holds env b's named column
@@ -689,6 +754,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
                         if (n0 + r < p.N) {
                             if (z > best) { best = z; best_i = n0 + r; best_raw = y; }
                             lse_add(y, lm, ls);
+                            tk_insert(y, n0 + r);
                         }
                         continue;
                     }
@@ -697,6 +763,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
                     // form does; a probability cannot: the SUM takes fl(v * factor), whose maximum is fl(best * factor) -- rounding is
                     // monotone -- so the final kernel rebuilds the partial's maximum from part_val and row_scale[b])
                     if (LSE && n0 + r < p.N) lse_add(NORM ? v * rsqrtf(total(R * B + tid) / (float)p.K + p.eps) : v, lm, ls);
+                    if (TOPK && n0 + r < p.N) tk_insert(v, n0 + r);
                 }
             }
         } else if (tid < R * B) {
@@ -714,6 +781,13 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
     if (AMAX && tid < B) {
         p.part_val[(size_t)tid * gridDim.x + blockIdx.x] = best;
         p.part_idx[(size_t)tid * gridDim.x + blockIdx.x] = best_i;
+        if constexpr (TOPK) {
+#pragma unroll
+            for (int e = 0; e < TOPK_C; ++e) {
+                p.cand_val[((size_t)tid * gridDim.x + blockIdx.x) * TOPK_C + e] = tk_v[e];
+                p.cand_idx[((size_t)tid * gridDim.x + blockIdx.x) * TOPK_C + e] = tk_i[e];
+            }
+        }
         if constexpr (SMP) {
             p.part_sum[(size_t)tid * gridDim.x + blockIdx.x] = ls;
             p.smp.part_max[(size_t)tid * gridDim.x + blockIdx.x] = lm;
@@ -727,74 +801,8 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
     }
 }
 
-// S = sum over the 256 threads' shares `mine` of the rescaled partial sums, through `red` (a fixed tree: the same bits every launch)
-SVLN_DEV float block_sum_256(float mine, float* red) {
-    red[threadIdx.x] = mine;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
-// EPI_SAMPLE merge of one row's n partials on 256 threads: raw = pr[k] of the partial with pi[k] == tok (unique; 0 when tok owns none),
-// V = max_k pm[k], S = sum_k ps[k] * exp(pm[k] - V), all on fixed trees.  red / redi: 256 words each, free to overwrite; ends synchronised.
-struct SampleMerge { float raw, V, S; };
-SVLN_DEV SampleMerge sample_merge(const int* pi, const float* pr, const float* pm, const float* ps, int n, int tok, float* red, int* redi) {
-    __syncthreads();                              // red / redi have been read by every thread
-    float m = -INFINITY, raw = 0.0f;
-    for (int k = threadIdx.x; k < n; k += 256) {
-        m = pm[k] > m ? pm[k] : m;
-        if (pi[k] == tok) raw = pr[k];
-    }
-    red[threadIdx.x] = m; redi[threadIdx.x] = __float_as_int(raw);
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) {
-            red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-            redi[threadIdx.x] |= redi[threadIdx.x + s];       // one thread holds the bits, the others 0
-        }
-        __syncthreads();
-    }
-    SampleMerge r;
-    r.V = red[0]; r.raw = __int_as_float(redi[0]);
-    __syncthreads();
-    float mine = 0.0f;
-    for (int k = threadIdx.x; k < n; k += 256) mine += lse_rescale(ps[k], pm[k], r.V);
-    r.S = block_sum_256(mine, red);
-    return r;
-}
-
-// The merge of one row's n partials on 256 threads, shared by argmax_final_batched_kernel and target_final_batched_kernel (one body: the
-// two kernels' ids and sums are the same bits by construction).
-// row_argmax_256: greatest value, lowest index on ties -> sv[0], si[0] (0x7FFFFFFF: no finite logit); ends synchronised.
-SVLN_DEV void row_argmax_256(const float* v0, const int* i0, int n, float* sv, int* si) {
-    float v = -INFINITY;
-    int i = 0x7FFFFFFF;
-    for (int k = threadIdx.x; k < n; k += 256) {
-        const float c = v0[k];
-        const int ci = i0[k];
-        if (c > v || (c == v && ci < i)) { v = c; i = ci; }
-    }
-    sv[threadIdx.x] = v; si[threadIdx.x] = i;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) {
-            const float b = sv[threadIdx.x + s2];
-            const int bi = si[threadIdx.x + s2];
-            if (b > sv[threadIdx.x] || (b == sv[threadIdx.x] && bi < si[threadIdx.x])) { sv[threadIdx.x] = b; si[threadIdx.x] = bi; }
-        }
-        __syncthreads();
-    }
-}
-// row_lse_sum_256: S = sum_k lse_rescale(ps[k], v0[k] * sc, V) on the fixed tree; sv must have been read by every thread's caller already
-SVLN_DEV float row_lse_sum_256(const float* ps, const float* v0, int n, float sc, float V, float* sv) {
-    __syncthreads();                          // sv is reused by the sum
-    float mine = 0.0f;
-    for (int k = threadIdx.x; k < n; k += 256) mine += lse_rescale(ps[k], v0[k] * sc, V);
-    return block_sum_256(mine, sv);
-}
+// (block_sum_256, sample_merge, row_argmax_256, row_lse_sum_256 -- the merges of one row's partials on 256 threads -- live in common.h:
+// topk_merge_kernel of misc.hip computes its (V, S) through them too)
 
 // final arg-max of env b = blockIdx.x over its per-workgroup partials
 // LSE: also env b's log-probability of that token from its partial sums ps (NaN for token -1); rs (optional): the positive factor of
@@ -1120,6 +1128,8 @@ template <typename P> static void launch_gemv_fmt(hipStream_t s, const GemvArgs&
         case EPI_ARGMAX: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX>), g, b, lds); break;
         case EPI_ARGMAX_LSE: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX_LSE>), g, b, lds); break;
         case EPI_SAMPLE: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SAMPLE>), g, b, lds); break;
+        case EPI_ARGMAX_LSE_TOPK: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX_LSE_TOPK>), g, b, lds); break;
+        case EPI_SAMPLE_TOPK: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SAMPLE_TOPK>), g, b, lds); break;
         default: break;
     }
 }
@@ -1157,6 +1167,10 @@ template <typename T> void launch_gemv_batched(hipStream_t s, const GemvBatchArg
         case EPI_SAMPLE:
             if (norm) throw std::runtime_error("batched GEMV: EPI_SAMPLE has no fused-norm form");
             launch_gb<T, EPI_SAMPLE, false>(s, a);
+            break;
+        case EPI_ARGMAX_LSE_TOPK: case EPI_SAMPLE_TOPK:
+            if (norm || !a.cand_val || !a.cand_idx) throw std::runtime_error("batched GEMV: EPI_*_TOPK takes candidate arrays and no fused norm");
+            if (a.epi == EPI_SAMPLE_TOPK) launch_gb<T, EPI_SAMPLE_TOPK, false>(s, a); else launch_gb<T, EPI_ARGMAX_LSE_TOPK, false>(s, a);
             break;
         case EPI_TARGET:
             if (norm || a.pen_flags || !a.tg.tgt || !a.tg.tgt_val) throw std::runtime_error("batched GEMV: EPI_TARGET takes targets, no fused norm and no penalty flags");
@@ -1199,6 +1213,8 @@ template <typename P> static void gemv_rows_attrs() {
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX>, GEMV_ROWS_MAX_LDS);
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX_LSE>, GEMV_ROWS_MAX_LDS);
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_SAMPLE>, GEMV_ROWS_MAX_LDS);
+    set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX_LSE_TOPK>, GEMV_ROWS_TOPK_MAX_LDS);
+    set_max_lds((const void*)gemv_rows_kernel<P, EPI_SAMPLE_TOPK>, GEMV_ROWS_TOPK_MAX_LDS);
 }
 void gemv_init_attrs() {
     gemv_rows_attrs<WMxfp4>(); gemv_rows_attrs<WE4m3>(); gemv_rows_attrs<WP12>(); gemv_rows_attrs<WPlain<bf16>>(); gemv_rows_attrs<WPlain<float>>();

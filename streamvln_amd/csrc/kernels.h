@@ -9,7 +9,8 @@
 
 namespace svln {
 
-enum Epi : int { EPI_NONE = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_SWIGLU = 3, EPI_ARGMAX = 4, EPI_ARGMAX_LSE = 5, EPI_SAMPLE = 6, EPI_TARGET = 7 };
+enum Epi : int { EPI_NONE = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_SWIGLU = 3, EPI_ARGMAX = 4, EPI_ARGMAX_LSE = 5, EPI_SAMPLE = 6, EPI_TARGET = 7,
+                 EPI_ARGMAX_LSE_TOPK = 8, EPI_SAMPLE_TOPK = 9 };
 // EPI_ARGMAX_LSE (svln_set_token_scores): EPI_ARGMAX -- same accumulators, same compares, same partials, hence the same tokens -- plus one
 // fp32 per partial, part_sum[k] = sum exp(l_j - part_val[k]) over the (penalised) logits partial k owns.  The final kernels merge them,
 // S = sum_k part_sum[k] * exp(part_val[k] - V) with V the winning value, and write the token's log-probability -log S.  A partial that
@@ -24,7 +25,14 @@ enum Epi : int { EPI_NONE = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_SWIGLU =
 // sampling off, so tokens and partials are then the scored form's bit for bit -- plus the capture of ONE named column per row: the lane
 // that holds column tgt[m] of a live row m stores tgt_val[m] = y (one plain store per row in the whole grid; -1 names no column).  The
 // final kernel (launch_target_final_batched) writes the arg-max, its log-probability -log S and the target's, (tgt_val - V) - log S.
-constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE || epi == EPI_SAMPLE || epi == EPI_TARGET; }
+// EPI_ARGMAX_LSE_TOPK / EPI_SAMPLE_TOPK (svln_top_logprobs; every lm_head form: wave-per-rows GEMV, batched GEMV, 32 x 128 MFMA tiles): EPI_ARGMAX_LSE / EPI_SAMPLE -- the same accumulators,
+// compares and partials, hence the same tokens, scores and partial arrays bit for bit -- and beside every arg-max partial its TOPK_C best
+// (y, column) pairs among the columns it owns, y descending then column ascending, padded with (-inf, 0x7FFFFFFF): cand_val / cand_idx
+// [partials][TOPK_C].  y is the processed logit (after the penalty), times inv_t under sampling -- never the perturbed z.  NaN and -inf are
+// never listed.  A column of the row's top k <= TOPK_C is in the top k of the partial that owns it, so launch_topk_merge is exact.
+constexpr int TOPK_C = 8;
+constexpr bool epi_is_topk(int epi) { return epi == EPI_ARGMAX_LSE_TOPK || epi == EPI_SAMPLE_TOPK; }
+constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE || epi == EPI_SAMPLE || epi == EPI_TARGET || epi_is_topk(epi); }
 // Inputs of EPI_TARGET: tgt [rows] device ids (-1: none), tgt_val [rows] the captured y
 struct TargetArgs { const int* tgt = nullptr; float* tgt_val = nullptr; float inv_t = 1.0f; };
 // Inputs of EPI_SAMPLE.  stream / draw are device arrays indexed by the row of the product (row 0 of a GEMV), read by the kernel: nothing a
@@ -81,6 +89,7 @@ struct GemmArgs {
     float* part_sum = nullptr;    // non-null: the EPI_ARGMAX_LSE form, [m][tiles] beside part_val
     SampleArgs smp;               // smp.part_raw non-null: the EPI_SAMPLE form (part_sum too)
     TargetArgs tg;                // tg.tgt non-null: the EPI_TARGET form (part_sum too; no penalty flags)
+    float* cand_val = nullptr; int* cand_idx = nullptr;       // non-null (with part_sum): the EPI_*_TOPK form, [m][tiles][TOPK_C]
     VitPackArgs vp; int vp_on;    // filled by the launcher: device-side copy of *vitpack for the unsplit kernels that pack in their epilogue
     int force_cfg, force_split;   // tests: 0 = heuristic; force_cfg 129 -> 128x128 tiles with two in-workgroup K groups; force_cfg low bits 128 -> 128x128 tiles, 264 -> 256x64 tiles; force_split S -> 256x128 tiles, S splits
 };
@@ -120,6 +129,7 @@ struct GemvArgs {
     const uint8_t* pen_flags = nullptr; float pen = 1.0f;
     float* part_sum = nullptr;    // EPI_ARGMAX_LSE / EPI_SAMPLE: [gemv_grid(N)] beside part_val
     SampleArgs smp;               // EPI_SAMPLE only
+    float* cand_val = nullptr; int* cand_idx = nullptr;       // EPI_*_TOPK: [gemv_grid(N)][TOPK_C]
 };
 template <typename T> void launch_gemv(hipStream_t s, const GemvArgs& a);
 // per-row e4m3 quantisation of a bf16 matrix [rows][cols] (cols % 16 == 0): scale[r] = max|W[r]| / 448
@@ -135,6 +145,7 @@ void launch_p12_unpack_rows(hipStream_t s, const void* packed, const void* rec, 
 template <typename T> void launch_gemv_timed(hipStream_t s, const GemvArgs& a, hipEvent_t start, hipEvent_t stop);   // events get the kernel's own begin/end
 int gemv_grid(int N);                       // workgroups launch_gemv uses for N rows
 constexpr int GEMV_ROWS_MAX_LDS = 160 * 1024 - 256;    // dynamic LDS the wave-per-rows kernel may ask for (K fp32 activations): N > 8192 or an epilogue
+constexpr int GEMV_ROWS_TOPK_MAX_LDS = GEMV_ROWS_MAX_LDS - 256;   // the EPI_*_TOPK forms keep the four waves' lists (256 bytes) in static LDS
 
 // B (1, 2, 4 or 8) activation vectors against one weight stream: x [B][ldx], y [B][ldy], res [B][ldr].
 // EPI_ARGMAX: part_val / part_idx are [B][gemv_batched_grid(N, epi, B)]; launch_argmax_final_batched reduces them to B tokens.
@@ -153,6 +164,7 @@ struct GemvBatchArgs {
     SampleArgs smp;               // EPI_SAMPLE only (no fused norm: launch_gemv_batched throws)
     TargetArgs tg;                // EPI_TARGET only (no fused norm, no penalty flags: launch_gemv_batched throws)
     float* row_scale = nullptr;   // EPI_ARGMAX_LSE with norm_w only: [B], the norm's row factor (the arg-max ignores it, the sums are taken on the scaled logits)
+    float* cand_val = nullptr; int* cand_idx = nullptr;       // EPI_*_TOPK (no fused norm: launch_gemv_batched throws): [B][grid][TOPK_C]
 };
 template <typename T> void launch_gemv_batched(hipStream_t s, const GemvBatchArgs& a);
 int gemv_batched_grid(int N, int epi, int B);
@@ -226,6 +238,16 @@ template <typename T> void launch_gemv_subset(hipStream_t s, const GemvSubsetArg
 // out[row][j] = y_j - logsumexp_i y_i for the B partial rows src [B][n] (part_val under greedy decoding, part_max under sampling);
 // row = *row_dev when given (B = 1: GenCtl::count, launched before the step kernel advances it), else b.  out rows have stride n.
 void launch_subset_logprobs(hipStream_t s, const float* src, int n, int B, float* out, const int* row_dev = nullptr, const int* skip = nullptr);
+// svln_top_logprobs (misc.hip): the k <= TOPK_C best of the n_part x c candidates (cand_val, cand_idx) [B][n_part][c] of every row -- c =
+// TOPK_C from the EPI_*_TOPK epilogues, c = 1 for the subset product, whose partials are candidates as they stand (part_val, or part_max
+// under sampling, with part_idx) -- y descending then column ascending; entries that are NaN, -inf or own nothing (0x7FFFFFFF) are never
+// listed.  (V, S) of the row come from the device functions the scored final kernels use, on the same partials: part_max == nullptr is
+// the greedy merge on (part_val, part_idx, part_sum), else the sampled one on (part_max, part_sum).  top_ids[row][k] (-1: padding) and
+// top_logprobs[row][k] = (y - V) - log S (-inf: padding); row = *row_dev when given (B = 1: GenCtl::count, launched before the step kernel
+// advances it), else b.  Under greedy decoding entry 0 is the token's score bit for bit; under sampling the emitted id's entry is.
+void launch_topk_merge(hipStream_t s, const float* cand_val, const int* cand_idx, int n_part, int c, int B, int k, const float* part_val,
+                       const int* part_idx, const float* part_sum, const float* part_max, int* top_ids, float* top_logprobs,
+                       const int* row_dev = nullptr, const int* skip = nullptr);
 // TEST-ONLY: out[k] = gumbel_noise(seed, stream, draw, n0 + k) for k < count
 void launch_gumbel(hipStream_t s, uint32_t seed_lo, uint32_t seed_hi, int stream, int draw, int n0, int count, float* out);
 // Draft-verified greedy decode (svln_set_speculative; misc.hip).  launch_verify_feed builds the rows of the next verify pass from GenCtl,

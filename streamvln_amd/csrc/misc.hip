@@ -2,6 +2,8 @@
 // patch extraction, bilinear token pooling, embedding splice, weight synthesis / conversion).
 // All of them are HBM/L2-bound byte movers: 16-byte vector accesses, one wave per row where a
 // row reduction is needed, no LDS.
+#include <stdexcept>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -530,6 +532,104 @@ template <typename T> void launch_to_f32(hipStream_t s, const void* src, float* 
 template <typename T> void launch_from_f32(hipStream_t s, const float* src, void* dst, int64_t n) {
     if (n <= 0) return;
     hipLaunchKernelGGL((from_f32_kernel<T>), dim3(grid_for(n)), dim3(256), 0, s, src, (T*)dst, n);
+}
+
+// svln_top_logprobs: the merge of one row's candidates (contract: kernels.h, launch_topk_merge).  One workgroup per row.  (V, S) first, on
+// the device functions of the scored final kernels and the same partials, so that the emitted id's entry is its score bit for bit.  Then
+// every thread takes its share of the n_part x c candidates into registers once (TOPK_MERGE_PER_THREAD each; what may not be listed -- NaN, -inf, padding, a partial that owns nothing -- becomes (-inf, none)) and k
+// rounds pick the best pair strictly behind the previous winner in (y descending, column ascending) order: columns are unique, so the
+// rounds list distinct columns and nothing is marked.  A round is a scan of the registers, a wave reduction on shuffles and ONE barrier:
+// the four waves' winners go through LDS slots that alternate by round, and every thread merges them alike.
+namespace {
+// TOPK_MERGE_PER_THREAD x 256 threads candidates: 32 holds the full vocabulary's 1024 single-env partials x TOPK_C, 64 the 2048 partials
+// the batched GEMV and the MFMA tiles can give
+template <int TOPK_MERGE_PER_THREAD>
+__global__ __launch_bounds__(256) void topk_merge_kernel(const float* cand_val, const int* cand_idx, int n_part, int c, int k, const float* pv,
+                                                         const int* pi, const float* ps, const float* pm, int* top_ids, float* top_logprobs,
+                                                         const int* row_dev, const int* skip) {
+    __shared__ float sv[256];
+    __shared__ int si[256];
+    __shared__ float wv[2][4];
+    __shared__ int wi[2][4];
+    if (skip && *skip) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t o = (size_t)blockIdx.x * n_part;
+    float V, S;
+    if (pm) {                                     // sampled: V = max part_max, S on (part_max, part_sum); no token is looked up (-1 owns no partial)
+        const SampleMerge mg = sample_merge(pi + o, pm + o, pm + o, ps + o, n_part, -1, sv, si);
+        V = mg.V; S = mg.S;
+    } else {
+        row_argmax_256(pv + o, pi + o, n_part, sv, si);
+        V = sv[0];
+        S = row_lse_sum_256(ps + o, pv + o, n_part, 1.0f, V, sv);
+    }
+    const float* cv = cand_val + o * c;
+    const int* ci = cand_idx + o * c;
+    const int total = n_part * c;
+    float rv[TOPK_MERGE_PER_THREAD];
+    int ri[TOPK_MERGE_PER_THREAD];
+#pragma unroll
+    for (int u = 0; u < TOPK_MERGE_PER_THREAD; ++u) {
+        const int t = tid + 256 * u, tc = min(t, total - 1);      // (clamped, not conditional: every load is in flight at once)
+        const float a = cv[tc];
+        const int ai = ci[tc];
+        const bool listable = t < total && a > -INFINITY && ai != 0x7FFFFFFF;
+        rv[u] = listable ? a : -INFINITY;
+        ri[u] = listable ? ai : 0x7FFFFFFF;
+    }
+    float prev_v = INFINITY, my_v = -INFINITY;    // thread j < k keeps round j's winner
+    int prev_i = -1, my_i = 0x7FFFFFFF;
+    for (int j = 0; j < k; ++j) {
+        float v = -INFINITY;
+        int i = 0x7FFFFFFF;
+#pragma unroll
+        for (int u = 0; u < TOPK_MERGE_PER_THREAD; ++u) {
+            const float a = rv[u];
+            const int ai = ri[u];
+            const bool behind = a < prev_v || (a == prev_v && ai > prev_i);         // not listed yet
+            if (behind && ai != 0x7FFFFFFF && (a > v || (a == v && ai < i))) { v = a; i = ai; }
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const float ov = __shfl_xor(v, d, 64);
+            const int oi = __shfl_xor(i, d, 64);
+            if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+        }
+        if (lane == 0) { wv[j & 1][wave] = v; wi[j & 1][wave] = i; }
+        __syncthreads();                          // (the slots of round j are written again in round j + 2, behind round j + 1's barrier)
+        prev_v = wv[j & 1][0]; prev_i = wi[j & 1][0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            const float ov = wv[j & 1][w];
+            const int oi = wi[j & 1][w];
+            if (ov > prev_v || (ov == prev_v && oi < prev_i)) { prev_v = ov; prev_i = oi; }
+        }
+        // (-inf, none) once the row is exhausted: nothing lies behind it, the later rounds find nothing either
+        if (tid == j) { my_v = prev_v; my_i = prev_i; }
+    }
+    if (tid < k) {
+        const size_t row = row_dev ? (size_t)*row_dev : (size_t)blockIdx.x;
+        // the expressions of the final kernels: the sampled score is raw - V + lse_logprob(S); the greedy one is lse_logprob(S), and
+        // (y - V) - log S written as -(log S - (y - V)) equals it to the sign of a zero when y == V (target_final_batched_kernel)
+        float lp;
+        if (pm) lp = my_v - V + lse_logprob(S);
+        else lp = -(-lse_logprob(S) - (my_v - V));
+        top_ids[row * k + tid] = my_i == 0x7FFFFFFF ? -1 : my_i;
+        top_logprobs[row * k + tid] = my_i == 0x7FFFFFFF ? -INFINITY : lp;
+    }
+}
+}  // namespace
+void launch_topk_merge(hipStream_t s, const float* cand_val, const int* cand_idx, int n_part, int c, int B, int k, const float* part_val,
+                       const int* part_idx, const float* part_sum, const float* part_max, int* top_ids, float* top_logprobs, const int* row_dev,
+                       const int* skip) {
+    const size_t total = (size_t)n_part * c;
+    if (total > (size_t)256 * 64) throw std::runtime_error("topk merge: more candidates than the kernel's registers hold");
+    if (total <= (size_t)256 * 32)
+        hipLaunchKernelGGL(topk_merge_kernel<32>, dim3(B), dim3(256), 0, s, cand_val, cand_idx, n_part, c, k, part_val, part_idx, part_sum, part_max,
+                           top_ids, top_logprobs, row_dev, skip);
+    else
+        hipLaunchKernelGGL(topk_merge_kernel<64>, dim3(B), dim3(256), 0, s, cand_val, cand_idx, n_part, c, k, part_val, part_idx, part_sum, part_max,
+                           top_ids, top_logprobs, row_dev, skip);
 }
 
 #define SVLN_INST(T)                                                                                                              \

@@ -149,12 +149,17 @@ class KVHandle:
 
 class GenerateOutput(dict):
     """`return_dict_in_generate=True` result: `.sequences` (new tokens only, EOS included) and
-    `.past_key_values` (streamvln_eval.py:334-335)."""
+    `.past_key_values` (streamvln_eval.py:334-335).  `.top_token_ids` / `.top_logprobs` (set_top_logprobs) read as None while the
+    switch is off; like every optional entry they are keys only of a result that carries them."""
+
+    _OPTIONAL = ("top_token_ids", "top_logprobs")
 
     def __getattr__(self, k):
         try:
             return self[k]
         except KeyError as e:
+            if k in GenerateOutput._OPTIONAL:
+                return None
             raise AttributeError(k) from e
 
 
@@ -189,6 +194,7 @@ class StreamVLNForCausalLM:
         self._auto_draft = False                                   # set_auto_draft: guess that a turn repeats the env's previous one
         self._last_out: Dict[int, torch.Tensor] = {}
         self._token_scores = False                                 # set_token_scores: results carry token_logprobs
+        self.top_logprobs_k = 0                                    # set_top_logprobs: results carry the k best ids per token
         self.allowed_token_ids = None                              # set_allowed_tokens: the list in force (tuple), None when off
         self._sampling = None                                      # set_sampling: None (greedy) or (temperature, seed) the engine holds
         self.sampling_seed = 0                                     # seed of the noise of generate(do_sample=True) (see set_sampling)
@@ -536,6 +542,21 @@ class StreamVLNForCausalLM:
             raise RuntimeError(f"the engine holds {n.value} token scores for a turn of {n_new} ids")
         return torch.from_numpy(buf[:n_new].copy()).unsqueeze(0).to(device)
 
+    def _topk(self, n_new, device, getter=None, *args):
+        """top_token_ids int64 [1, n_new, k] and top_logprobs fp32 [1, n_new, k] (on `device`) of a finished turn from one of the engine's
+        list getters (default: svln_get_topk, the last single-env turn)"""
+        k = self.top_logprobs_k
+        getter = getter or self._lib.svln_get_topk
+        ids = np.empty(max(n_new, 1) * k, dtype=np.int32)
+        lps = np.empty(max(n_new, 1) * k, dtype=np.float32)
+        nr, nk = C.c_int32(), C.c_int32()
+        _check(getter(self._h, *args, ids.ctypes.data_as(C.POINTER(C.c_int32)), lps.ctypes.data_as(C.POINTER(C.c_float)), max(n_new, 1),
+                      C.byref(nr), C.byref(nk)))
+        if nr.value != n_new or nk.value != k:
+            raise RuntimeError(f"the engine holds {nr.value} x {nk.value} top log-probabilities for a turn of {n_new} ids at k = {k}")
+        return (torch.from_numpy(ids[: n_new * k].astype(np.int64).reshape(1, n_new, k)).to(device),
+                torch.from_numpy(lps[: n_new * k].reshape(1, n_new, k).copy()).to(device))
+
     def _allowed(self, res, getter, *args):
         """with set_token_scores and set_allowed_tokens both on: add `allowed_logprobs` [1, n_new, n_allowed] (fp32) and `allowed_token_ids`
         [n_allowed] (int64) of a finished turn to its result, from the engine's allowed-logprob getter named `getter`"""
@@ -616,6 +637,8 @@ class StreamVLNForCausalLM:
         res = GenerateOutput(sequences=seq, past_key_values=KVHandle(env_id, self._epoch[env_id], buf["kv"].value))
         if self._token_scores:
             res["token_logprobs"] = self._scores(self._lib.svln_get_token_scores, n_new=int(seq.shape[1]), device=seq.device)
+        if self.top_logprobs_k:
+            res["top_token_ids"], res["top_logprobs"] = self._topk(n_new=int(seq.shape[1]), device=seq.device)
         return self._allowed(res, "svln_get_allowed_logprobs")
 
     # ---- forced turns: log-probabilities of given ids in one prefill pass (svln_turn_forced) --------------
@@ -875,8 +898,12 @@ class StreamVLNForCausalLM:
         scores = [None] * len(parsed)
         if self._token_scores:
             scores = [self._scores(self._lib.svln_generate_batch_scores, k, n_new=int(n_out[k]), device="cpu") for k in range(len(parsed))]
-        return [self._allowed(self._batch_result(p[5], out[k, : n_out[k]], requests[k].get("inputs"), scores[k]),
-                              "svln_generate_batch_allowed_logprobs", k) for k, p in enumerate(parsed)]
+        res = [self._allowed(self._batch_result(p[5], out[k, : n_out[k]], requests[k].get("inputs"), scores[k]),
+                             "svln_generate_batch_allowed_logprobs", k) for k, p in enumerate(parsed)]
+        if self.top_logprobs_k:
+            for k, r in enumerate(res):
+                r["top_token_ids"], r["top_logprobs"] = self._topk(int(n_out[k]), r.sequences.device, self._lib.svln_generate_batch_topk, k)
+        return res
 
     # ---- iteration-level scheduler: envs whose turns fall due at different times (streamvln_dagger.py:232-313) ----
     @torch.no_grad()
@@ -937,6 +964,7 @@ class StreamVLNForCausalLM:
                 sbuf = np.empty(cap, dtype=np.float32)
                 _check(self._lib.svln_batch_scores(self._h, fin[k], sbuf.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(ns)))
                 scores = torch.from_numpy(sbuf[: ns.value].copy()).unsqueeze(0)
+            top = self._topk(int(ns.value), "cpu", self._lib.svln_batch_topk, fin[k]) if self.top_logprobs_k else None
             alp = None
             if self._token_scores and self.allowed_token_ids:      # (read before svln_batch_result frees the slot)
                 abuf = np.empty(cap * len(self.allowed_token_ids), dtype=np.float32)
@@ -947,6 +975,8 @@ class StreamVLNForCausalLM:
             _check(self._lib.svln_batch_result(self._h, fin[k], C.byref(env), out.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n)))
             env_id, inputs = self._tickets.pop(fin[k])
             res = self._batch_result(env_id, out[: n.value], inputs, scores)
+            if top is not None:
+                res["top_token_ids"], res["top_logprobs"] = (t.to(res.sequences.device) for t in top)
             if alp is not None:
                 res["allowed_logprobs"] = alp.to(res.sequences.device)
                 res["allowed_token_ids"] = torch.tensor(self.allowed_token_ids, dtype=torch.int64, device=res.sequences.device)
@@ -1102,6 +1132,18 @@ class StreamVLNForCausalLM:
         it is on), and while scheduler turns are in flight."""
         _check(self._lib.svln_set_token_scores(self._h, int(bool(enable))))
         self._token_scores = bool(enable)
+
+    def set_top_logprobs(self, k: int):
+        """Opt-in, default off (svln_top_logprobs; `logprobs=k` / `top_logprobs` of the serving stacks): while 1 <= k <= 8 every result of
+        generate / generate_batch / step_batch carries `top_token_ids` int64 [1, n_new, k] and `top_logprobs` fp32 [1, n_new, k] on the device of `sequences`: per emitted
+        id the k most probable ids (log-probability descending, then id ascending; under set_sampling of softmax(x / T), without the
+        noise) -- padded with (-1, -inf) where fewer exist, e.g. under a shorter allowed list.  Greedy: entry 0 is the emitted id and its
+        log-probability the bits of `token_logprobs`.  The lm_head kernels keep the candidates beside their fused arg-max: no logits in
+        memory, no second pass, ids and scores unchanged bit for bit.  Needs set_token_scores(True) first (which then cannot be switched
+        off); generate, generate_batch and step_batch carry the lists; group turns are refused while k > 0; a forced turn carries none.
+        k = 0: off, the entries read as None."""
+        _check(self._lib.svln_top_logprobs(self._h, int(k)))
+        self.top_logprobs_k = int(k)
 
     def set_allowed_tokens(self, ids, add_eos: bool = True):
         """Opt-in, default off (svln_set_allowed_tokens; HF's prefix_allowed_tokens_fn with a constant set, vLLM's allowed_token_ids): while a
