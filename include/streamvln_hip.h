@@ -521,7 +521,7 @@ int svln_op_gemm(svln_engine* h, const void* A, int lda, const void* W, int ldw,
 int svln_op_gemm_norm(svln_engine* h, const void* A, int lda, const void* W, int ldw, void* C, int ldc, const void* bias, const void* res, int ldr,
                       const void* norm_w, const void* norm_b, void* norm_out, float eps, int M, int N, int K, int force_split, int* fused);
 /* the RMSNorm form with the e4m3 copy of the normalised rows (opt-in fp8 products: the reduce that emits the norm also quantises it):
- * q8 [M][N] bytes, q8_scale [M] = max |norm_out row| / 448 */
+ * q8 [M][N] bytes, q8_scale [M] = max |norm_out row| / 448, with the floor and the NaN rule of svln_op_quant_fp8 (same arithmetic) */
 int svln_op_gemm_norm_q8(svln_engine* h, const void* A, int lda, const void* W, int ldw, void* C, int ldc, const void* res, int ldr,
                          const void* norm_w, void* norm_out, float eps, int M, int N, int K, int force_split, void* q8, float* q8_scale, int* fused);
 int svln_op_gemv(svln_engine* h, const void* W, int ldw, const void* x, const void* norm_w, float eps, const void* bias, const void* res,
@@ -561,7 +561,12 @@ int svln_op_gemv_batched(svln_engine* h, const void* W, int ldw, const void* x, 
  * (host), out_score [n_rows] cosine scores (host, optional) */
 int svln_op_memory_prune(svln_engine* h, const void* mem, int n_rows, int keep, int32_t* out_idx, float* out_score);
 /* fp8 weight-only pieces of svln_set_fp8_decode: per-row e4m3 quantisation of a bf16 matrix [rows][cols] (cols % 16 == 0,
- * scale[r] = max|W[r]| / 448, round to nearest even), and the GEMV over such a matrix (same epilogues as svln_op_gemv) */
+ * scale[r] = max|W[r]| / 448, round to nearest even), and the GEMV over such a matrix (same epilogues as svln_op_gemv).
+ * Scale floor: scale[r] = max(max|W[r]| / 448, 2^-126), 1 for an all-zero row, so 1 / scale is finite and normal and a zero element is
+ * byte 0 in every row; rows with max|W[r]| >= 448 * 2^-126 are not touched by the floor.  Non-finite elements: the maximum ignores a NaN,
+ * and the NaN element becomes a NaN byte (0x7F / 0xFF) while the row's scale and other bytes stay what they are without it; an infinite
+ * element makes the scale infinite, the row's finite elements 0 and the infinite one NaN.  A finite row never yields a NaN byte.
+ * Refused with a message before any launch: a null pointer, rows < 0, cols <= 0, cols % 16 != 0; rows == 0 does nothing. */
 int svln_op_quant_fp8(svln_engine* h, const void* w_bf16, int64_t rows, int cols, void* w8, float* scale);
 int svln_op_gemv_fp8(svln_engine* h, const void* w8, const float* scale, int ldw, const void* x, const void* norm_w, float eps, const void* bias,
                      const void* res, void* y, int N, int K, int epi, int32_t* host_token);
@@ -569,7 +574,9 @@ int svln_op_gemv_fp8(svln_engine* h, const void* w8, const float* scale, int ldw
  * matrix [rows][cols] (device, cols % 32 == 0).  Every run of 32 consecutive elements of a row is one block: e = floor(log2(max |w|)) - 2
  * clamped to [-127, 127] (0 for an all-zero block), e8 = e + 127 (E8M0, scale 2^e); element code = E2M1 of w / 2^e on the grid
  * {0, 0.5, 1, 1.5, 2, 3, 4, 6}, round to nearest even (5 -> 4, 3.5 -> 4, 2.5 -> 2, 1.75 -> 2, 1.25 -> 1, 0.75 -> 1, 0.25 -> 0),
- * saturating at 6, sign in bit 3; element 2j in the low nibble and 2j + 1 in the high nibble of byte j.
+ * saturating at 6, sign in bit 3; element 2j in the low nibble and 2j + 1 in the high nibble of byte j.  A block that holds a NaN or an
+ * infinity gets e8 = 0xFF (E8M0 NaN) and unspecified codes; the row's other blocks are what they are without it.  (How the GEMVs read a
+ * scale byte 0xFF is not specified here.)
  * q4 [rows][cols / 2] and e8 [rows][cols / 32] bytes, row-major (device): one 16-byte run of q4 is one block.
  * svln_op_gemv_mxfp4: the GEMV over such a matrix, y = epi(Wq . x' + bias) + res with the epilogues of svln_op_gemv; ldw (the row
  * stride) and K in elements, both multiples of 32.  fp32 engines refuse both. */

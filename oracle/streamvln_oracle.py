@@ -98,11 +98,13 @@ def linear(x, w, b=None):
 # ----------------------------------------------------------------------------- opt-in e4m3 modes (no reference counterpart)
 def qdq_e4m3_rows(x: torch.Tensor) -> torch.Tensor:
     """Per-row e4m3 quantise -> dequantise, the arithmetic of gemv.hip `quant_fp8_rows_kernel`: scale = amax / 448 (1 for an all-zero
-    row), q = e4m3_rne(clamp(x * (1 / scale), +-448)), value = q * scale.  fp32 in, fp32 out."""
-    amax = x.abs().amax(-1, keepdim=True)
-    sc = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+    row) floored at 2^-126 so that 1 / scale is finite, q = e4m3_rne(clamp(x * (1 / scale), +-448)), value = q * scale.  The maximum
+    ignores a NaN element (fmaxf) and the clamp keeps it, so a NaN stays a NaN and changes nothing else of its row.  fp32 in, fp32 out."""
+    a = x.abs()
+    amax = torch.where(a != a, torch.zeros_like(a), a).amax(-1, keepdim=True)
+    sc = torch.where(amax > 0, (amax / 448.0).clamp_min(2.0 ** -126), torch.ones_like(amax))
     inv = 1.0 / sc
-    q = (x * inv).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).to(torch.float32)
+    q = (x * inv).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).to(torch.float32)      # (torch.clamp keeps a NaN)
     return q * sc
 
 

@@ -127,6 +127,12 @@ SVLN_DEV float wave_max(float v) {
     return v;
 }
 
+// The per-row e4m3 scheme shared by quant_fp8_rows_kernel (gemv.hip) and splitk_rownorm_kernel (gemm.hip).  amax = max |w| with fmaxf, so
+// a NaN element does not enter it.  The scale is amax / 448 floored at 2^-126 (1 for an all-zero row): 1 / scale is then finite and
+// normal, and a zero of a tiny row stays zero instead of 0 * inf.  A NaN element passes the clamp and becomes a NaN byte.
+SVLN_DEV float e4m3_row_scale(float amax) { return amax > 0.0f ? fmaxf(amax / 448.0f, 0x1p-126f) : 1.0f; }
+SVLN_DEV float e4m3_clamp(float x) { return x != x ? x : fminf(fmaxf(x, -448.0f), 448.0f); }
+
 // Online log-sum-exp pieces of EPI_ARGMAX_LSE (kernels.h) on v_exp_f32 / v_log_f32.  A partial is (m, s): the maximum of the logits it
 // owns and s = sum exp(l - m) over them; the partial that owns nothing is (-inf, 0).
 SVLN_DEV float lse_exp(float d) { return __builtin_amdgcn_exp2f(1.4426950408889634f * d); }

@@ -3538,9 +3538,11 @@ public:
     }
     void op_quant_fp8(const void* w, int64_t rows, int cols, void* w8, float* scale) override {
         REQUIRE(sizeof(T) == 2, "fp8 quantisation reads bf16 weights");
-        REQUIRE(cols % 16 == 0, "cols must be a multiple of 16");
-        launch_quant_fp8_rows(st, w, cols, w8, scale, rows, cols);
+        REQUIRE(w && w8 && scale, "null pointer");
+        REQUIRE(rows >= 0 && rows <= INT32_MAX && cols > 0 && cols % 16 == 0, "rows must be >= 0 and cols a positive multiple of 16");
+        if (rows > 0) launch_quant_fp8_rows(st, w, cols, w8, scale, rows, cols);
         sync();
+        LAUNCH_CHECK("op_quant_fp8");
     }
     void op_quant_mxfp4(const void* w, int64_t rows, int cols, void* q4, uint8_t* e8) override {
         REQUIRE(sizeof(T) == 2, "MXFP4 quantisation reads bf16 weights");

@@ -858,7 +858,8 @@ __global__ __launch_bounds__(256) void target_final_batched_kernel(const float* 
     }
 }
 
-// per-row e4m3 quantisation: one workgroup per row, scale = max|w| / 448 (1 for an all-zero row), round-to-nearest-even
+// per-row e4m3 quantisation: one workgroup per row, scale = max|w| / 448 floored at 2^-126 (1 for an all-zero row), round-to-nearest-even;
+// a NaN element gives a NaN byte and leaves the scale alone (e4m3_row_scale / e4m3_clamp, common.h)
 __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16* w, int ld, uint8_t* q, float* scale, int cols) {
     __shared__ float red[4];
     const size_t row = blockIdx.x;
@@ -874,14 +875,14 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16* w, int 
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
     __syncthreads();
     amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const float sc = amax > 0.0f ? amax / 448.0f : 1.0f;
+    const float sc = e4m3_row_scale(amax);
     if (threadIdx.x == 0) scale[row] = sc;
     const float inv = 1.0f / sc;
     for (int ci = threadIdx.x; ci < cols / 8; ci += 256) {
         float f[8];
         chunk_to_f32<bf16>(*(const uint4*)(wr + (size_t)ci * 8), f);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = fminf(fmaxf(f[e] * inv, -448.0f), 448.0f);
+        for (int e = 0; e < 8; ++e) f[e] = e4m3_clamp(f[e] * inv);
         int lo = 0, hi = 0;
         lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
         lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
@@ -894,6 +895,7 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16* w, int 
 // MXFP4 quantisation of a bf16 matrix (OCP MX conversion): one workgroup per row, one thread per block of 32 elements.
 //   e = floor(log2(max |w|)) - 2 clamped to [-127, 127] (0 for an all-zero block), scale byte e + 127;
 //   code = E2M1 of w / 2^e (exact in fp32), round to nearest even, saturating at 6.
+// A block that holds a NaN or an infinity gets the scale byte 0xFF (E8M0 NaN, as the OCP MX conversion prescribes); its codes are unspecified.
 // The rounding is written as comparisons against the seven midpoints of the grid (ties to the code with an even mantissa bit) rather
 // than with v_cvt_scalef32_pk_fp4_f32: this runs once per weight load, and the bytes are then defined by this text alone.
 SVLN_DEV unsigned e2m1_code(float v) {
@@ -911,8 +913,13 @@ __global__ __launch_bounds__(256) void quant_mxfp4_rows_kernel(const bf16* w, in
 #pragma unroll
         for (int h = 0; h < 4; ++h) chunk_to_f32<bf16>(*(const uint4*)(wr + (size_t)bi * 32 + h * 8), f + 8 * h);
         float amax = 0.0f;
+        bool nonfinite = false;
 #pragma unroll
-        for (int e = 0; e < 32; ++e) amax = fmaxf(amax, fabsf(f[e]));
+        for (int e = 0; e < 32; ++e) {
+            const float a = fabsf(f[e]);
+            amax = fmaxf(amax, a);
+            nonfinite |= !(a < __builtin_inff());           // NaN or inf
+        }
         int ex = 0;
         if (amax > 0.0f) {
             ex = (int)((__float_as_uint(amax) >> 23) & 0xFF) - 127 - 2;        // (a subnormal amax reads as -129 and clamps)
@@ -927,7 +934,7 @@ __global__ __launch_bounds__(256) void quant_mxfp4_rows_kernel(const bf16* w, in
             d[k] = v;
         }
         *(uint4*)(q + row * (size_t)(cols / 2) + (size_t)bi * 16) = make_uint4(d[0], d[1], d[2], d[3]);
-        e8[row * (size_t)nblk + bi] = (uint8_t)(ex + 127);
+        e8[row * (size_t)nblk + bi] = nonfinite ? (uint8_t)0xFF : (uint8_t)(ex + 127);
     }
 }
 

@@ -102,6 +102,101 @@ def test_exponent_formula_idempotence_and_error_bound(rows, cols, sd, seed):
     assert float(err.max()) <= 2.0
 
 
+# the code of every member of mxfp4_ref.TIE_VALS, written out by hand (value in units of the block scale -> magnitude code)
+HAND_CODE = {0.0: 0, 0.125: 0, 0.25: 0, 0.375: 1, 0.5: 1, 0.625: 1, 0.75: 2, 0.875: 2, 1.0: 2, 1.25: 2, 1.5: 3, 1.75: 4, 2.0: 4, 2.25: 4,
+             2.5: 4, 2.75: 5, 3.0: 5, 3.5: 6, 4.0: 6, 4.5: 6, 5.0: 6, 5.5: 7, 6.0: 7, 7.0: 7, 7.5: 7}
+
+
+def _hand_nibbles(block, k):
+    """the 32 nibbles of a block whose scale is 2^k, from HAND_CODE"""
+    out = []
+    for w in block.double().tolist():
+        v = w / 2.0 ** k
+        out.append(HAND_CODE[abs(v)] | (8 if v < 0 and HAND_CODE[abs(v)] else 0))
+    return out
+
+
+def _fold_nibbles(codes):
+    return _nibbles(R.fold_zero(codes))
+
+
+def test_ties_where_the_block_exponent_clamps():
+    W, e8_exp = R.clamp_tie_matrix()
+    assert set(R.TIE_VALS) == set(HAND_CODE) and all(HAND_CODE[t] % 2 == 0 for t in R.TIES)      # every tie goes to an even code
+    codes, e8 = R.quant_mxfp4(W)
+    assert e8.tolist() == e8_exp
+    nib = _fold_nibbles(codes)
+    amax = W.reshape(len(W), 2, 32).abs().amax(-1)
+    assert float(amax[0, 0]) == 3 * 2.0 ** -127 and 2.0 ** -126 <= float(amax[0, 0]) < 2.0 ** -125       # floor(log2) - 2 = -128: clamped
+    assert 0 < float(amax[1, 0]) < 2.0 ** -126                                                          # a bf16 subnormal
+    assert float(amax[1, 1]) == 1.75 * 2.0 ** 127
+    for r in range(len(W)):
+        for b in range(2):
+            blk = W[r, 32 * b:32 * b + 32]
+            got = [n if n != 8 else 0 for n in nib[r, 32 * b:32 * b + 32].tolist()]
+            assert got == _hand_nibbles(blk, int(e8[r, b]) - 127), (r, b)
+            assert sum(1 for w in blk.tolist() if abs(w) / 2.0 ** (int(e8[r, b]) - 127) in R.TIES) >= 3, (r, b)      # ties are present
+    assert torch.equal(R.dequant_mxfp4(codes, e8)[:, 31], W[:, 31])                                      # each block-0 amax (3, 1.5, 6) is a grid value
+
+
+def test_ties_at_the_edge_of_the_second_loop_iteration():
+    W = R.wide_tie_matrix()
+    assert W.shape == (2, 8256) and {255, 256, 257} <= {b for b, _ in R.WIDE_BLOCKS}
+    codes, e8 = R.quant_mxfp4(W)
+    exp_e8 = torch.full((2, 258), 127, dtype=torch.uint8)
+    for b, k in R.WIDE_BLOCKS:
+        exp_e8[:, b] = 127 + k
+    assert torch.equal(e8, exp_e8)
+    assert all(exp_e8[0, b] != exp_e8[0, b + 1] for b in (254, 255, 256))                                # neighbours differ in exponent
+    nib = _fold_nibbles(codes)
+    for r in range(2):
+        for b, k in R.WIDE_BLOCKS:
+            assert nib[r, 32 * b:32 * b + 32].tolist() == _hand_nibbles(W[r, 32 * b:32 * b + 32], k), (r, b)
+    live = torch.zeros(258, dtype=torch.bool)
+    live[[b for b, _ in R.WIDE_BLOCKS]] = True
+    assert int(codes.reshape(2, 258, 16)[:, ~live].max()) == 0
+
+
+def test_a_block_with_a_nan_or_an_infinity_gets_the_scale_byte_0xff():
+    for what, W, twin, bad in R.nonfinite_matrices():
+        codes, e8 = R.quant_mxfp4(W)
+        ct, et = R.quant_mxfp4(twin)
+        is_bad = torch.zeros_like(e8, dtype=torch.bool)
+        for r, b in bad:
+            is_bad[r, b] = True
+        assert torch.equal(e8 == R.E8_NAN, is_bad), what                                                 # exactly the blocks that hold one
+        assert not bool((et == R.E8_NAN).any()) and torch.equal(e8[~is_bad], et[~is_bad]), what
+        keep = (~is_bad).repeat_interleave(16, dim=1)
+        assert torch.equal(codes[keep], ct[keep]), what                                                  # the other blocks are unchanged
+        assert torch.equal(R.mask_nonfinite(codes, e8)[keep], codes[keep]) and int(R.mask_nonfinite(codes, e8)[~keep].max()) == 0
+        ex = et.int() - 127
+        assert bool((ex[:, 1:] != ex[:, :-1]).float().mean() > 0.8), what                                # neighbouring exponents differ
+
+
+def _differs(ref, mut):
+    """what the device comparison sees: the scale bytes, and the code bytes outside the reference's 0xFF blocks (-0 folded)"""
+    return not torch.equal(ref[1], mut[1]) or not torch.equal(R.fold_zero(R.mask_nonfinite(ref[0], ref[1])), R.fold_zero(R.mask_nonfinite(mut[0], ref[1])))
+
+
+def test_the_designed_inputs_see_the_two_mutants():
+    """nan_code0 = the kernel before the 0xFF rule; iter2 = a thread's second loop iteration dropped.  Each is caught on every input
+    written for it, by a scale byte or (outside 0xFF blocks) a code byte; the narrow finite inputs cannot see iter2 and say so."""
+    nonfinite = R.nonfinite_matrices()
+    wide = [R.wide_tie_matrix()] + [W for what, W, _, _ in nonfinite if what == "wide"]
+    report = {}
+    for i, (what, W, _, bad) in enumerate(nonfinite):
+        ref, mut = R.quant_mxfp4(W), R.quant_mxfp4(W, "nan_code0")
+        report[f"nan_code0/{what}"] = int((ref[1] != mut[1]).sum())
+        assert report[f"nan_code0/{what}"] == len(bad) and _differs(ref, mut)
+    for i, W in enumerate(wide):
+        ref, mut = R.quant_mxfp4(W), R.quant_mxfp4(W, "iter2")
+        report[f"iter2/wide{i}"] = int((ref[1] != mut[1]).sum())
+        assert report[f"iter2/wide{i}"] >= 2 and _differs(ref, mut)
+    Wc, _ = R.clamp_tie_matrix()
+    assert not _differs(R.quant_mxfp4(Wc), R.quant_mxfp4(Wc, "iter2")) and not _differs(R.quant_mxfp4(Wc), R.quant_mxfp4(Wc, "nan_code0"))
+    print(report)
+
+
 # relative L2 distance between the product over the dequantised weights and the unquantised product on the inputs of the GEMV op tests
 # (util.rnd((N, K), 41, 1 / sqrt(K)) weights, rnd((K,), 42) x, both rounded to bf16).  `expected` = the figures stated with the scheme
 # (computed from its definition; re-measured with this restatement: 0.0971 / 0.1160 / 0.1220 / 0.1688 / 0.0972); the cap is 1.5 x expected.  A block exponent one

@@ -1,7 +1,9 @@
 """The opt-in MXFP4 decode weights (svln_set_mxfp4_decode; NO reference counterpart: the reference is bf16 only) against the same
 numeric scheme restated on the CPU (tests/mxfp4_ref.py): OCP MX blocks of 32 E2M1 elements with one E8M0 scale byte.
 
-  quantiser   bytes and scale bytes EQUAL to the restatement (-0 folded onto +0).
+  quantiser   bytes and scale bytes EQUAL to the restatement (-0 folded onto +0), also where the block exponent clamps, in a thread's
+              second loop iteration, and with NaN / inf elements: such a block gets the scale byte 0xFF and its codes are masked.  How the
+              GEMVs consume a scale byte 0xFF is out of scope here.
   GEMV        against the fp32 product over the DEQUANTISED weights: both sides multiply identical values, so what is left is fp32
               summation order and one bf16 rounding -- the bound util.assert_close is defined for.
   end to end  weight-only, so engine and emulation (mxfp4_ref.Mxfp4Emu) see the same quantised operands: every comparable hidden row --
@@ -84,6 +86,34 @@ def test_quantiser_bytes_equal_the_cpu_restatement():
         assert torch.equal(got, exp), f"{what}: {int((got != exp).sum())} of {exp.numel()} bytes differ"
     gq, ge = _gpu_quant(m, Wz)
     assert int(gq[4].max()) == 0 and ge[4].tolist() == [127] * 8 and int(ge[6, 1]) == 127
+
+
+def test_quantiser_at_the_exponent_clamps_and_in_the_second_loop_iteration():
+    """the ties of the element grid where the block exponent clamps (e8 = 0 from an amax in [2^-126, 2^-125) and from a bf16-subnormal
+    amax; e8 = 252 from amax = 1.75 * 2^127) and in blocks 255, 256, 257 of a row of 8256 columns, neighbouring blocks under different
+    exponents; tests/test_mxfp4_cpu.py holds the expected bytes to hand-written codes"""
+    m = engine(torch.bfloat16)
+    Wc, e8_exp = R.clamp_tie_matrix()
+    for what, W in (("clamps", Wc), ("wide", R.wide_tie_matrix())):
+        codes, e8 = R.quant_mxfp4(W)
+        gq, ge = _gpu_quant(m, W)
+        assert torch.equal(ge, e8), f"{what}: scale bytes differ at {torch.nonzero(ge != e8).tolist()[:8]}"
+        got, exp = R.fold_zero(gq), R.fold_zero(codes)
+        assert torch.equal(got, exp), f"{what}: {int((got != exp).sum())} of {exp.numel()} bytes differ, first at {torch.nonzero(got != exp).tolist()[:8]}"
+    assert _gpu_quant(m, Wc)[1].tolist() == e8_exp
+
+
+def test_quantiser_marks_a_block_with_a_nan_or_an_infinity_with_scale_byte_0xff():
+    """a block that holds a non-finite element gets E8M0 NaN (0xFF) and unspecified codes (masked); every other block of the row is
+    what the restatement makes of it, in a thread's first and second loop iteration"""
+    m = engine(torch.bfloat16)
+    for what, W, twin, bad in R.nonfinite_matrices():
+        codes, e8 = R.quant_mxfp4(W)
+        assert {tuple(x) for x in torch.nonzero(e8 == R.E8_NAN).tolist()} == bad
+        gq, ge = _gpu_quant(m, W)
+        assert torch.equal(ge, e8), f"{what}: scale bytes differ at {torch.nonzero(ge != e8).tolist()[:8]}"
+        got, exp = R.fold_zero(R.mask_nonfinite(gq, e8)), R.fold_zero(R.mask_nonfinite(codes, e8))
+        assert torch.equal(got, exp), f"{what}: {int((got != exp).sum())} of {exp.numel()} bytes differ"
 
 
 def _dev(t, dtype=torch.bfloat16):

@@ -413,9 +413,11 @@ def test_memory_prune_selection(dtype, N, keep):
 
 
 def _quant_ref(W):
-    """per-row e4m3 quantisation as the engine does it: scale = amax / 448, q = e4m3(clamp(w * (1 / scale)))"""
-    amax = W.abs().amax(dim=1)
-    scale = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax)).to(torch.float32)
+    """per-row e4m3 quantisation as the engine does it: scale = amax / 448 floored at 2^-126, q = e4m3(clamp(w * (1 / scale))); amax
+    ignores a NaN element and the clamp keeps it (tests/quant_ref.py restates the same without torch's encoder)"""
+    a = W.abs()
+    amax = torch.where(a != a, torch.zeros_like(a), a).amax(dim=1)
+    scale = torch.where(amax > 0, (amax / 448.0).clamp_min(2.0 ** -126), torch.ones_like(amax)).to(torch.float32)
     inv = (1.0 / scale).to(torch.float32)
     qf = (W * inv[:, None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
     return qf, scale
