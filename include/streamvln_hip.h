@@ -188,6 +188,31 @@ int svln_set_token_scores(svln_engine* h, int enable);
  * svln_set_batch_draft (their verify rule is written for greedy rows), svln_set_decode_persistent and svln_set_mxfp4_batched (its
  * lm_head kernel has no sampled form).  svln_get_top2 is refused after a sampled turn: the values are perturbed, not logits. */
 int svln_set_sampling(svln_engine* h, int enable, float temperature, uint64_t seed);
+/* Opt-in, default off (top_k = 0, top_p = 1), no reference counterpart: truncated sampling -- top-k then top-p over the lm_head's
+ * candidate lists.  While top_k is 1 .. 8 every lm_head product of a sampled pass (svln_generate / svln_turn / svln_generate_fixed,
+ * svln_generate_batch, the scheduler, group turns) runs its candidate form (the EPI_SAMPLE_TOPK kernels of svln_top_logprobs, lists on
+ * or off; under svln_set_allowed_tokens the subset product's partials are the candidates) and one small kernel per head pass applies,
+ * per row, HF's warpers in HF's order -- temperature, top-k, top-p -- on y_n = fl(x_n * invT):
+ *   1. the k' = min(top_k, listable columns) best (y, column) pairs, y descending then column ascending (NaN and -inf are never listed).
+ *      At an exact tie on the k-th value HF's TopKLogitsWarper keeps every tied column; this engine keeps exactly k, lowest columns first;
+ *   2. e_j = exp(y_j - y_0), c_j = c_{j-1} + e_j (fp32, serially), total = c_{k'-1}: entry 0 is kept, entry j >= 1 is kept iff top_p >= 1
+ *      or c_{j-1} < fl(top_p * total) -- HF's TopPLogitsWarper over the top-k set: keep an id iff the mass strictly before it is below top_p;
+ *   3. token = argmax over the kept j of fl(y_j + G(seed, stream, draw, column_j)), the noise and the expression of svln_set_sampling:
+ *      whenever the untruncated sampled token lies in the kept set the truncated turn emits that token, bit for bit -- a truncated turn
+ *      is the full sampled turn conditioned on the kept set, as an allowed list is.  One draw per emitted id, as without truncation;
+ *   4. the score (svln_set_token_scores) is the log-softmax over the kept set at the emitted id -- HF's `scores` after the warpers -- and
+ *      under svln_top_logprobs the lists are over the kept set, padded with (-1, -inf) beyond it; the emitted id's entry is the score's bits.
+ *      svln_get_allowed_logprobs rows stay the untruncated log-softmax over the allowed list.
+ * The name is deliberately not svln_set_*: this is an attribute of svln_set_sampling, not an independent row of the switch-pair table the
+ * tests keep for every svln_set_* prototype (the decision svln_top_logprobs made).  svln_set_sampling(h, 0, ..) clears it,
+ * svln_set_sampling(h, 1, ..) keeps it; every mode sampling refuses is thereby unreachable.  Refused, before any launch or state change:
+ * top_k outside 0 .. 8; top_p not in (0, 1] (NaN included); top_k = 0 with top_p < 1 (naming top_k: a nucleus is taken over at most 8
+ * listed ids); sampling off (naming svln_set_sampling); scheduler turns in flight; a group pending; a hidden size too large for the
+ * candidate form of the lm_head GEMV.  Composes with svln_set_token_scores, svln_top_logprobs, svln_set_allowed_tokens, the repetition
+ * penalty, svln_set_fp8_decode / svln_set_mxfp4_decode / svln_set_packed_decode (candidates of their own formats), svln_set_fp8_gemm,
+ * group turns and graph replay (captured steps are dropped when the setting changes; top_k / top_p are launch scalars).  Forced turns
+ * are unchanged: they score softmax(x / T) untruncated.  With truncation off every launch is what ran before. */
+int svln_sampling_truncation(svln_engine* h, int32_t top_k, float top_p);
 /* Opt-in, default off (k = 0), no reference counterpart: top-k log-probabilities -- what else the policy considered.  While k is 1 .. 8
  * every lm_head product (the single-env GEMV of svln_generate / svln_turn / svln_generate_fixed, the batched GEMV and the 32 x 128 MFMA
  * tiles of svln_generate_batch and the scheduler) runs the sibling of its scored or sampled kernel that also keeps, beside every arg-max
@@ -650,6 +675,15 @@ int svln_op_gemm_argmax_topk(svln_engine* h, const void* A, int lda, const void*
                              const int32_t* pen_rows, float penalty, int k, int sampled, float temperature, uint64_t seed, const int32_t* streams,
                              const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* cand_val, int32_t* cand_idx, int32_t* top_ids,
                              float* top_logprobs, int32_t* n_part);
+/* TEST-ONLY: the truncation kernel of svln_sampling_truncation followed by the batched sampled final kernel, on host candidates
+ * cand_val / cand_idx [B][n_part][c] (c = 8: lists as the EPI_SAMPLE_TOPK epilogues write them, padded with (-inf, 0x7FFFFFFF); c = 1:
+ * one candidate per partial, as under an allowed list).  The values are y as they stand (already times 1 / T: `temperature` is checked
+ * and otherwise unused); row b uses streams[b] / draws[b].  Outputs (host): the five 8-entry partial rows [B][8], tokens [B] and scores
+ * [B].  Refused before any launch: null pointers, B outside 1 .. 32, n_part < 1, c not 1 or 8, n_part x c > 16384, top_k outside 1 .. 8,
+ * top_p not in (0, 1], a negative column, stream or draw, a temperature that is not finite and > 0. */
+int svln_op_truncate(svln_engine* h, const float* cand_val, const int32_t* cand_idx, int B, int n_part, int c, const int32_t* streams,
+                     const int32_t* draws, uint64_t seed, float temperature, int32_t top_k, float top_p, float* part_val, int32_t* part_idx,
+                     float* part_raw, float* part_max, float* part_sum, int32_t* host_tokens, float* host_logprobs);
 int svln_op_gemv_batched_argmax_scores(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
                                        const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs);
 int svln_op_gemm_argmax_scores(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,

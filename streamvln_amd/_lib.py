@@ -121,6 +121,8 @@ SIGNATURES = {
     "svln_batch_scores": (_I, [_P, _I, _PF, _I, _PI32]),
     "svln_generate_batch_scores": (_I, [_P, _I, _PF, _I, _PI32]),
     "svln_set_sampling": (_I, [_P, _I, _F, _U64]),
+    "svln_sampling_truncation": (_I, [_P, _I, _F]),
+    "svln_op_truncate": (_I, [_P, _PF, _PI32, _I, _I, _I, _PI32, _PI32, _U64, _F, _I, _F, _PF, _PI32, _PF, _PF, _PF, _PI32, _PF]),
     "svln_set_allowed_tokens": (_I, [_P, _PI64, _I]),
     "svln_get_allowed_logprobs": (_I, [_P, _PF, _I, _PI32, _PI32]),
     "svln_batch_allowed_logprobs": (_I, [_P, _I, _PF, _I, _PI32, _PI32]),

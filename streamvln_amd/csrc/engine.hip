@@ -117,6 +117,9 @@ struct EngineBase {
     virtual void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk = nullptr) = 0;
     virtual void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk = nullptr) = 0;
     virtual void set_sampling(int enable, float temperature, uint64_t seed) = 0;
+    virtual void sampling_truncation(int top_k, float top_p) = 0;
+    virtual void op_truncate(const float* cv, const int32_t* ci, int B, int n_part, int cc, const OpSample* q, int top_k, float top_p, float* pv,
+                             int32_t* pi, float* pr, float* pm, float* ps, int32_t* host_tokens, float* host_logprobs) = 0;
     virtual void set_allowed_tokens(const int64_t* ids, int n) = 0;
     virtual void get_allowed_logprobs(float* out, int cap, int32_t* n_tokens, int32_t* n_ids) = 0;
     virtual void batch_allowed_logprobs(int slot, float* out, int cap, int32_t* n_tokens, int32_t* n_ids) = 0;
@@ -302,6 +305,20 @@ public:
     float *part_raw = nullptr, *part_max = nullptr, *part_raw_b = nullptr, *part_max_b = nullptr;
     int *d_smp = nullptr, *h_smp = nullptr;
     std::vector<int> env_draws;              // tokens every env has emitted since the last svln_set_sampling
+    // Opt-in truncated sampling (svln_sampling_truncation; an attribute of svln_set_sampling): while trunc_k > 0 every lm_head product of a
+    // sampled pass runs its EPI_SAMPLE_TOPK form (the candidates of ensure_topk_buffers, lists on or off), truncate_partials_kernel
+    // (kernels.h, launch_truncate_partials) turns them into an 8-entry partial row -- tr_* [1][TOPK_C] for head(), tr_*_b
+    // [SMP_ROWS][TOPK_C] for argmax_rows() -- and the unchanged final / step kernel reduces that row.  top_k / top_p are launch scalars.
+    int trunc_k = 0; float trunc_p = 1.0f;
+    float *tr_val = nullptr, *tr_raw = nullptr, *tr_max = nullptr, *tr_sum = nullptr, *tr_val_b = nullptr, *tr_raw_b = nullptr, *tr_max_b = nullptr, *tr_sum_b = nullptr;
+    int *tr_idx = nullptr, *tr_idx_b = nullptr;
+    void ensure_trunc_buffers() {
+        ensure_topk_buffers();
+        if (tr_val) return;
+        tr_val = dalloc<float>(TOPK_C); tr_raw = dalloc<float>(TOPK_C); tr_max = dalloc<float>(TOPK_C); tr_sum = dalloc<float>(TOPK_C); tr_idx = dalloc<int>(TOPK_C);
+        const size_t nb = (size_t)SMP_ROWS * TOPK_C;
+        tr_val_b = dalloc<float>(nb); tr_raw_b = dalloc<float>(nb); tr_max_b = dalloc<float>(nb); tr_sum_b = dalloc<float>(nb); tr_idx_b = dalloc<int>(nb);
+    }
     bool top2_sampled = false;               // the last turn was sampled: d_top2 holds perturbed values, not logits
     // an op-level override of the engine's own switch (svln_op_*_argmax_sample): the product's SampleArgs scalars
     SampleArgs smp_args(const int* stream, const int* draw, const int* count, float* raw, float* mx) const {
@@ -1309,7 +1326,26 @@ public:
         int n_part = gemv_grid(V);
         // svln_top_logprobs: the lists of this token -> d_topi / d_topl [count], before the step kernel advances the count
         const int* trow = gen ? &d_ctl->count : nullptr;
-        if (topk) { a.epi = smp_on ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK; a.cand_val = cand_val; a.cand_idx = cand_idx; }
+        if (topk || trunc_k) { a.epi = smp_on ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK; a.cand_val = cand_val; a.cand_idx = cand_idx; }
+        if (trunc_k) {
+            // svln_sampling_truncation: the product as it stands, then the candidates -> the 8-entry row tr_*, which the step / final
+            // kernel and the lists' merge read in place of the product's partials (under an allowed list: its partials are the candidates)
+            if (allow_on) {
+                GemvSubsetArgs sa = subset_args(tap, H, 1, part_val, part_idx, part_sum);
+                sa.skip = skip; sa.smp = a.smp;
+                if (pen) { sa.pen_flags = pen_flags; sa.pen = rep_penalty; }
+                launch_gemv_subset<T>(st, sa);
+                if (scores_on) launch_subset_logprobs(st, part_max, allow_n, 1, d_alp, gen ? &d_ctl->count : nullptr, skip);
+                launch_truncate_partials(st, part_max, part_idx, allow_n, 1, 1, trunc_k, trunc_p, smp_args(a.smp.stream, a.smp.draw, a.smp.count, tr_raw, tr_max), tr_val, tr_idx, tr_sum, skip);
+            } else {
+                launch_gemv<T>(st, a);
+                launch_truncate_partials(st, cand_val, cand_idx, n_part, TOPK_C, 1, trunc_k, trunc_p, smp_args(a.smp.stream, a.smp.draw, a.smp.count, tr_raw, tr_max), tr_val, tr_idx, tr_sum, skip);
+            }
+            if (topk) launch_topk_merge(st, tr_max, tr_idx, TOPK_C, 1, 1, topk, tr_val, tr_idx, tr_sum, tr_max, d_topi, d_topl, trow, skip);
+            if (gen) launch_argmax_step(st, tr_val, tr_idx, TOPK_C, d_token, d_top2, d_ctl, d_eos, d_out_ids, pen ? pen_flags : nullptr, tr_sum, d_scores, tr_raw, tr_max);
+            else launch_argmax_final(st, tr_val, tr_idx, TOPK_C, d_token, d_top2, tr_sum, d_scores, tr_raw, tr_max);
+            return;
+        }
         if (allow_on) {
             // svln_set_allowed_tokens: the subset product on the engine-dtype lm_head, one partial per listed id; with the scores on, the
             // normalised row goes to d_alp[count] before the step kernel advances the count
@@ -1514,6 +1550,36 @@ public:
         const float* ps = scores_on || smp_on ? part_sum_b : nullptr;
         const float *pr = smp_on ? part_raw_b : nullptr, *pm = smp_on ? part_max_b : nullptr;
         const SampleArgs sa = smp_args(d_smp + tok0, d_smp + SMP_ROWS + tok0, nullptr, part_raw_b, part_max_b);
+        if (trunc_k) {
+            // svln_sampling_truncation: the product of the branch below in its candidate form, then rows [0, B) of tr_*_b -> the unchanged
+            // final kernel (and the lists' merge) on TOPK_C partials per row
+            const float* cv = cand_val_b; const int* ci = cand_idx_b; int n = 0, cc = TOPK_C;
+            if (allow_on && W == (const void*)lm_head) {
+                GemvSubsetArgs su = subset_args(xrows, ldx, B, part_val_b, part_idx_b, part_sum_b);
+                su.smp = sa;
+                if (pen) { su.pen_flags = pen_flags_b; su.pen_rows = d_pen_rows; su.pen = rep_penalty; }
+                launch_gemv_subset<T>(st, su);
+                if (scores_on) launch_subset_logprobs(st, part_max_b, allow_n, B, d_alp_b + (size_t)tok0 * allow_n);
+                cv = part_max_b; ci = part_idx_b; n = allow_n; cc = 1;
+            } else if (B >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048) {
+                GemmArgs a = gemm_args(xrows, ldx, W, ldw, nullptr, 0, nullptr, nullptr, 0, 0, B, N, K, EPI_ARGMAX);
+                a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b; a.smp = sa;
+                if (pen) { a.pen_flags = pen_flags_b; a.pen_rows = d_pen_rows; a.pen = rep_penalty; }
+                a.cand_val = cand_val_b; a.cand_idx = cand_idx_b;
+                n = launch_gemm_argmax<T>(st, a);
+            } else {
+                GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, EPI_SAMPLE_TOPK, B);
+                hb.part_sum = part_sum_b; hb.smp = sa;
+                if (pen) { hb.pen_flags = pen_flags_b; hb.pen_rows = d_pen_rows; hb.pen = rep_penalty; }
+                hb.cand_val = cand_val_b; hb.cand_idx = cand_idx_b;
+                launch_gemv_batched<T>(st, hb);
+                n = gemv_batched_grid(N, EPI_ARGMAX, B);
+            }
+            launch_truncate_partials(st, cv, ci, n, cc, B, trunc_k, trunc_p, smp_args(sa.stream, sa.draw, nullptr, tr_raw_b, tr_max_b), tr_val_b, tr_idx_b, tr_sum_b);
+            launch_argmax_final_batched(st, tr_val_b, tr_idx_b, TOPK_C, B, d_tok_b + tok0, tr_sum_b, d_score_b + tok0, nullptr, tr_raw_b, tr_max_b);
+            if (topk) launch_topk_merge(st, tr_max_b, tr_idx_b, TOPK_C, 1, B, topk, tr_val_b, tr_idx_b, tr_sum_b, tr_max_b, d_topi_b + (size_t)tok0 * topk, d_topl_b + (size_t)tok0 * topk);
+            return;
+        }
         if (allow_on && W == (const void*)lm_head) {
             // svln_set_allowed_tokens: the subset product whatever the row count; row b's normalised row -> d_alp_b[tok0 + b]
             GemvSubsetArgs su = subset_args(xrows, ldx, B, part_val_b, part_idx_b, part_sum_b);
@@ -1719,7 +1785,48 @@ public:
         HIP_CHECK(hipStreamSynchronize(st));
         drop_graphs();
         smp_on = want; smp_inv_t = inv_t; smp_seed = want ? seed : 0;
+        if (!want) { trunc_k = 0; trunc_p = 1.0f; }      // svln_sampling_truncation is an attribute of the sampling: kept by an "on" call, cleared by "off"
         std::fill(env_draws.begin(), env_draws.end(), 0);
+    }
+    // svln_sampling_truncation.  An attribute of svln_set_sampling (every mode sampling refuses is thereby unreachable); every refusal
+    // comes before any launch or state change.  The draw counters are not touched: one draw per emitted id, truncated or not.
+    void sampling_truncation(int top_k, float top_p) override {
+        REQUIRE(top_k >= 0 && top_k <= TOPK_C, "svln_sampling_truncation: top_k must be 0 (off) .. 8");
+        REQUIRE(top_p > 0.0f && top_p <= 1.0f, "svln_sampling_truncation: top_p must lie in (0, 1]");
+        REQUIRE(top_k > 0 || top_p >= 1.0f, "svln_sampling_truncation: top_p < 1 needs top_k = 1 .. 8 (the nucleus is taken over at most 8 listed ids)");
+        refuse_while_group("svln_sampling_truncation");
+        refuse_while_jobs("svln_sampling_truncation");
+        if (top_k == trunc_k && top_p == trunc_p) return;      // nothing changes (off stays off whatever the switches are)
+        REQUIRE(smp_on, "svln_sampling_truncation: temperature sampling is off (svln_set_sampling); switch it on first");
+        REQUIRE((size_t)H * sizeof(float) <= (size_t)GEMV_ROWS_TOPK_MAX_LDS, "svln_sampling_truncation: the hidden size is too large for the candidate form of the lm_head GEMV");
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (top_k) ensure_trunc_buffers();
+        drop_graphs();           // the captured head is the truncated or the plain sampled one; top_k / top_p are launch scalars
+        trunc_k = top_k; trunc_p = top_k ? top_p : 1.0f;
+    }
+    // TEST-ONLY: truncate_partials_kernel + launch_argmax_final_batched on host candidate rows [B][n_part][c]
+    void op_truncate(const float* cv, const int32_t* ci, int B, int n_part, int cc, const OpSample* q, int top_k, float top_p, float* pv,
+                     int32_t* pi, float* pr, float* pm, float* ps, int32_t* host_tokens, float* host_logprobs) override {
+        REQUIRE(cv && ci && q && pv && pi && pr && pm && ps && host_tokens && host_logprobs, "svln_op_truncate: null pointer");
+        REQUIRE(B >= 1 && B <= 32, "svln_op_truncate: 1 <= B <= 32 rows");
+        REQUIRE(n_part >= 1 && (cc == 1 || cc == TOPK_C) && (size_t)n_part * cc <= (size_t)2048 * TOPK_C, "svln_op_truncate: n_part >= 1, c = 1 or 8, n_part x c <= 16384");
+        REQUIRE(top_k >= 1 && top_k <= TOPK_C, "svln_op_truncate: top_k must be 1 .. 8");
+        REQUIRE(top_p > 0.0f && top_p <= 1.0f, "svln_op_truncate: top_p must lie in (0, 1]");
+        const size_t nc = (size_t)B * n_part * cc;
+        for (size_t i = 0; i < nc; ++i) REQUIRE(ci[i] >= 0, "svln_op_truncate: candidate columns must be >= 0 (0x7FFFFFFF: none)");
+        ensure_trunc_buffers();
+        SampleArgs sa = op_sample_args(*q, B, tr_raw_b, tr_max_b, true);
+        HIP_CHECK(hipMemcpyAsync(cand_val_b, cv, nc * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(cand_idx_b, ci, nc * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_truncate_partials(st, cand_val_b, cand_idx_b, n_part, cc, B, top_k, top_p, sa, tr_val_b, tr_idx_b, tr_sum_b);
+        launch_argmax_final_batched(st, tr_val_b, tr_idx_b, TOPK_C, B, d_tok_b, tr_sum_b, d_score_b, nullptr, tr_raw_b, tr_max_b);
+        const size_t nb = (size_t)B * TOPK_C;
+        HIP_CHECK(hipMemcpyAsync(pv, tr_val_b, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(pi, tr_idx_b, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(pr, tr_raw_b, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(pm, tr_max_b, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(ps, tr_sum_b, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+        batched_scores_out(B, host_tokens, host_logprobs, "op_truncate");
     }
     // rows [0, n) of the next sampled lm_head pass: job slot order[k] per row (rows beyond n_jobs replay row 0)
     void upload_sample_rows(const int* job_of_row, int n_jobs, int n) {
@@ -4171,6 +4278,15 @@ int svln_generate_batch_topk(svln_engine* h, int index, int32_t* ids, float* log
     API_BEGIN_H REQUIRE(ids && logprobs && n_rows && k && cap_rows >= 0, "null output pointer"); h->impl->generate_batch_topk(index, ids, logprobs, cap_rows, n_rows, k); API_END
 }
 int svln_set_sampling(svln_engine* h, int enable, float temperature, uint64_t seed) { API_BEGIN_H h->impl->set_sampling(enable, temperature, seed); API_END }
+int svln_sampling_truncation(svln_engine* h, int32_t top_k, float top_p) { API_BEGIN_H h->impl->sampling_truncation(top_k, top_p); API_END }
+int svln_op_truncate(svln_engine* h, const float* cand_val, const int32_t* cand_idx, int B, int n_part, int c, const int32_t* streams,
+                     const int32_t* draws, uint64_t seed, float temperature, int32_t top_k, float top_p, float* part_val, int32_t* part_idx,
+                     float* part_raw, float* part_max, float* part_sum, int32_t* host_tokens, float* host_logprobs) {
+    API_BEGIN_H
+    const OpSample q{temperature, seed, streams, draws};
+    h->impl->op_truncate(cand_val, cand_idx, B, n_part, c, &q, top_k, top_p, part_val, part_idx, part_raw, part_max, part_sum, host_tokens, host_logprobs);
+    API_END
+}
 int svln_set_allowed_tokens(svln_engine* h, const int64_t* ids, int n) { API_BEGIN_H h->impl->set_allowed_tokens(ids, n); API_END }
 int svln_get_allowed_logprobs(svln_engine* h, float* out, int cap_floats, int32_t* n_tokens, int32_t* n_ids) {
     API_BEGIN_H REQUIRE(out && n_tokens && n_ids && cap_floats >= 0, "null output pointer"); h->impl->get_allowed_logprobs(out, cap_floats, n_tokens, n_ids); API_END

@@ -430,7 +430,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
                 const float gq = gumbel_noise(p.smp.seed_lo, p.smp.seed_hi, smp_stream, smp_draw, n0 + (lane & 3));
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    const float y = acc[r] * p.smp.inv_t, z = y + __shfl(gq, r, 64);
+                    const float y = acc[r] * p.smp.inv_t, z = __fadd_rn(y, __shfl(gq, r, 64));       // (fl(y + G), never fma(acc, inv_t, G): truncate_partials_kernel adds the same G to the stored y)
                     if (n0 + r < p.N) {
                         if (z > best) { best = z; best_i = n0 + r; best_raw = y; }         // rows ascend: first max wins
                         lse_add(y, lm, ls);
@@ -750,7 +750,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
                         if (n0 + r < p.N && n0 + r == my_tgt) p.tg.tgt_val[tid] = v;
                     }
                     if constexpr (SMP) {
-                        const float y = v * p.smp.inv_t, z = y + gn[r * B + tid];
+                        const float y = v * p.smp.inv_t, z = __fadd_rn(y, gn[r * B + tid]);       // (fl(y + G), as in gemv_rows_kernel)
                         if (n0 + r < p.N) {
                             if (z > best) { best = z; best_i = n0 + r; best_raw = y; }
                             lse_add(y, lm, ls);

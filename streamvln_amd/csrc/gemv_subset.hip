@@ -70,7 +70,7 @@ __global__ __launch_bounds__(GEMV_SUBSET_WAVES * 64) void gemv_subset_kernel(Gem
             if constexpr (TGT) y = val = v * p.tg_inv_t;       // a forced turn: the scored partials on y, no noise (1.0f with sampling off)
             if constexpr (SMP) {
                 y = v * p.smp.inv_t;
-                val = y + gumbel_noise(p.smp.seed_lo, p.smp.seed_hi, p.smp.stream[b], p.smp.draw[b] + (p.smp.count ? *p.smp.count : 0), id);
+                val = __fadd_rn(y, gumbel_noise(p.smp.seed_lo, p.smp.seed_hi, p.smp.stream[b], p.smp.draw[b] + (p.smp.count ? *p.smp.count : 0), id));       // (fl(y + G), never fma(v, inv_t, G))
                 p.smp.part_raw[o] = y;
                 p.smp.part_max[o] = y;
             }

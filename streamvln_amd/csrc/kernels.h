@@ -248,6 +248,21 @@ void launch_subset_logprobs(hipStream_t s, const float* src, int n, int B, float
 void launch_topk_merge(hipStream_t s, const float* cand_val, const int* cand_idx, int n_part, int c, int B, int k, const float* part_val,
                        const int* part_idx, const float* part_sum, const float* part_max, int* top_ids, float* top_logprobs,
                        const int* row_dev = nullptr, const int* skip = nullptr);
+// svln_sampling_truncation (misc.hip): top-k then top-p over one row's candidates, as an 8-entry partial row the sampled final kernels
+// (launch_argmax_step / launch_argmax_final / launch_argmax_final_batched with n = TOPK_C) reduce unchanged.  Candidates as in
+// launch_topk_merge ([B][n_part][c], c = TOPK_C or 1; n_part x c <= 16384).  Rule per row, one 256-thread workgroup each:
+//   1. the k' = min(top_k, listable candidates) winners of launch_topk_merge's rounds, (y_j, col_j), y descending then column ascending;
+//   2. e_j = lse_exp(y_j - y_0), c_j = c_{j-1} + e_j serially in fp32, total = c_{k'-1}; entry 0 is kept, entry j >= 1 iff
+//      top_p >= 1 or c_{j-1} < fl(top_p * total) -- a prefix of the list (HF's TopPLogitsWarper over the top-k set: temperature, top-k,
+//      top-p).  At an exact tie on the k-th value HF's TopKLogitsWarper keeps every tied column; this rule keeps exactly k, lowest columns;
+//   3. a kept entry becomes the partial (part_val = fl(y_j + G(seed, stream[b], draw[b] + *count, col_j)), part_idx = col_j, part_raw =
+//      part_max = y_j, part_sum = 1): the noise and the sum of the untruncated epilogues, so whenever the untruncated sampled token is
+//      kept the truncated turn emits it; every other entry of the eight is the owns-nothing partial (-inf, 0x7FFFFFFF, 0, -inf, 0).
+// The final kernel's score is then the log-softmax over the kept set at the emitted id; a row with nothing listable gives token -1.
+// smp: stream / draw / count / seed as the producer's; smp.part_raw / smp.part_max are the OUTPUT rows [B][TOPK_C] beside tr_val / tr_idx /
+// tr_sum (never the producer's partial arrays: launch_topk_merge and the tests still read those); smp.inv_t is not used (y is scaled).
+void launch_truncate_partials(hipStream_t s, const float* cand_val, const int* cand_idx, int n_part, int c, int B, int top_k, float top_p,
+                              const SampleArgs& smp, float* tr_val, int* tr_idx, float* tr_sum, const int* skip = nullptr);
 // TEST-ONLY: out[k] = gumbel_noise(seed, stream, draw, n0 + k) for k < count
 void launch_gumbel(hipStream_t s, uint32_t seed_lo, uint32_t seed_hi, int stream, int draw, int n0, int count, float* out);
 // Draft-verified greedy decode (svln_set_speculative; misc.hip).  launch_verify_feed builds the rows of the next verify pass from GenCtl,

@@ -541,31 +541,12 @@ template <typename T> void launch_from_f32(hipStream_t s, const float* src, void
 // rounds list distinct columns and nothing is marked.  A round is a scan of the registers, a wave reduction on shuffles and ONE barrier:
 // the four waves' winners go through LDS slots that alternate by round, and every thread merges them alike.
 namespace {
-// TOPK_MERGE_PER_THREAD x 256 threads candidates: 32 holds the full vocabulary's 1024 single-env partials x TOPK_C, 64 the 2048 partials
-// the batched GEMV and the MFMA tiles can give
+// The selection rounds of topk_merge_kernel and truncate_partials_kernel (one body: the two kernels list the same winners by construction).
+// cv / ci: one row's `total` candidates; wv / wi: [2][4] LDS slots; thread j < k leaves with round j's winner in (my_v, my_i), every
+// other thread -- and a round behind the last listable candidate -- with (-inf, 0x7FFFFFFF).
 template <int TOPK_MERGE_PER_THREAD>
-__global__ __launch_bounds__(256) void topk_merge_kernel(const float* cand_val, const int* cand_idx, int n_part, int c, int k, const float* pv,
-                                                         const int* pi, const float* ps, const float* pm, int* top_ids, float* top_logprobs,
-                                                         const int* row_dev, const int* skip) {
-    __shared__ float sv[256];
-    __shared__ int si[256];
-    __shared__ float wv[2][4];
-    __shared__ int wi[2][4];
-    if (skip && *skip) return;
+SVLN_DEV void topk_select_256(const float* cv, const int* ci, int total, int k, float (*wv)[4], int (*wi)[4], float& my_v, int& my_i) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t o = (size_t)blockIdx.x * n_part;
-    float V, S;
-    if (pm) {                                     // sampled: V = max part_max, S on (part_max, part_sum); no token is looked up (-1 owns no partial)
-        const SampleMerge mg = sample_merge(pi + o, pm + o, pm + o, ps + o, n_part, -1, sv, si);
-        V = mg.V; S = mg.S;
-    } else {
-        row_argmax_256(pv + o, pi + o, n_part, sv, si);
-        V = sv[0];
-        S = row_lse_sum_256(ps + o, pv + o, n_part, 1.0f, V, sv);
-    }
-    const float* cv = cand_val + o * c;
-    const int* ci = cand_idx + o * c;
-    const int total = n_part * c;
     float rv[TOPK_MERGE_PER_THREAD];
     int ri[TOPK_MERGE_PER_THREAD];
 #pragma unroll
@@ -577,8 +558,9 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* cand_val, 
         rv[u] = listable ? a : -INFINITY;
         ri[u] = listable ? ai : 0x7FFFFFFF;
     }
-    float prev_v = INFINITY, my_v = -INFINITY;    // thread j < k keeps round j's winner
-    int prev_i = -1, my_i = 0x7FFFFFFF;
+    float prev_v = INFINITY;
+    int prev_i = -1;
+    my_v = -INFINITY; my_i = 0x7FFFFFFF;
     for (int j = 0; j < k; ++j) {
         float v = -INFINITY;
         int i = 0x7FFFFFFF;
@@ -607,6 +589,32 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* cand_val, 
         // (-inf, none) once the row is exhausted: nothing lies behind it, the later rounds find nothing either
         if (tid == j) { my_v = prev_v; my_i = prev_i; }
     }
+}
+// TOPK_MERGE_PER_THREAD x 256 threads candidates: 32 holds the full vocabulary's 1024 single-env partials x TOPK_C, 64 the 2048 partials
+// the batched GEMV and the MFMA tiles can give
+template <int TOPK_MERGE_PER_THREAD>
+__global__ __launch_bounds__(256) void topk_merge_kernel(const float* cand_val, const int* cand_idx, int n_part, int c, int k, const float* pv,
+                                                         const int* pi, const float* ps, const float* pm, int* top_ids, float* top_logprobs,
+                                                         const int* row_dev, const int* skip) {
+    __shared__ float sv[256];
+    __shared__ int si[256];
+    __shared__ float wv[2][4];
+    __shared__ int wi[2][4];
+    if (skip && *skip) return;
+    const int tid = threadIdx.x;
+    const size_t o = (size_t)blockIdx.x * n_part;
+    float V, S;
+    if (pm) {                                     // sampled: V = max part_max, S on (part_max, part_sum); no token is looked up (-1 owns no partial)
+        const SampleMerge mg = sample_merge(pi + o, pm + o, pm + o, ps + o, n_part, -1, sv, si);
+        V = mg.V; S = mg.S;
+    } else {
+        row_argmax_256(pv + o, pi + o, n_part, sv, si);
+        V = sv[0];
+        S = row_lse_sum_256(ps + o, pv + o, n_part, 1.0f, V, sv);
+    }
+    float my_v;                                   // thread j < k keeps round j's winner
+    int my_i;
+    topk_select_256<TOPK_MERGE_PER_THREAD>(cand_val + o * c, cand_idx + o * c, n_part * c, k, wv, wi, my_v, my_i);
     if (tid < k) {
         const size_t row = row_dev ? (size_t)*row_dev : (size_t)blockIdx.x;
         // the expressions of the final kernels: the sampled score is raw - V + lse_logprob(S); the greedy one is lse_logprob(S), and
@@ -616,6 +624,60 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* cand_val, 
         else lp = -(-lse_logprob(S) - (my_v - V));
         top_ids[row * k + tid] = my_i == 0x7FFFFFFF ? -1 : my_i;
         top_logprobs[row * k + tid] = my_i == 0x7FFFFFFF ? -INFINITY : lp;
+    }
+}
+// svln_sampling_truncation: one row's candidates -> the 8-entry partial row of the truncated turn (contract: kernels.h,
+// launch_truncate_partials).  The selection rounds above leave winner j with thread j; the eight (y, column) pairs go through LDS to
+// thread 0, which accumulates the prefix c_j serially in fp32 and counts the kept prefix; threads 0 .. 7 then write one entry each, the
+// kept ones with the noise of their own column.
+template <int TOPK_MERGE_PER_THREAD>
+__global__ __launch_bounds__(256) void truncate_partials_kernel(const float* cand_val, const int* cand_idx, int n_part, int c, int k, float top_p,
+                                                                SampleArgs smp, float* tr_val, int* tr_idx, float* tr_sum, const int* skip) {
+    __shared__ float wv[2][4];
+    __shared__ int wi[2][4];
+    __shared__ float ly[TOPK_C];
+    __shared__ int li[TOPK_C];
+    __shared__ int n_keep;
+    if (skip && *skip) return;
+    const int tid = threadIdx.x;
+    const size_t o = (size_t)blockIdx.x * n_part;
+    float my_v;
+    int my_i;
+    topk_select_256<TOPK_MERGE_PER_THREAD>(cand_val + o * c, cand_idx + o * c, n_part * c, k, wv, wi, my_v, my_i);
+    if (tid < TOPK_C) { ly[tid] = my_v; li[tid] = my_i; }
+    __syncthreads();
+    if (tid == 0) {
+        int kept = 0;
+        if (li[0] != 0x7FFFFFFF) {
+            int kk = 1;                           // k' = the listed prefix
+            while (kk < TOPK_C && li[kk] != 0x7FFFFFFF) ++kk;
+            float total = 0.0f;                   // c_j = c_{j-1} + e_j, serially in index order
+            for (int j = 0; j < kk; ++j) total += lse_exp(ly[j] - ly[0]);
+            const float bound = top_p * total;
+            float before = 0.0f;                  // c_{j-1}: the same additions in the same order, hence the same bits
+            kept = 1;                             // entry 0 is always kept; the kept set is a prefix: the masses ascend
+            for (int j = 1; j < kk; ++j) {
+                before += lse_exp(ly[j - 1] - ly[0]);
+                if (!(top_p >= 1.0f || before < bound)) break;
+                kept = j + 1;
+            }
+        }
+        n_keep = kept;
+    }
+    __syncthreads();
+    if (tid < TOPK_C) {
+        const bool keep = tid < n_keep;
+        float z = -INFINITY;
+        if (keep) {
+            const int b = blockIdx.x;
+            z = __fadd_rn(my_v, gumbel_noise(smp.seed_lo, smp.seed_hi, smp.stream[b], smp.draw[b] + (smp.count ? *smp.count : 0), my_i));      // the epilogues' fl(y + G)
+        }
+        const size_t q = (size_t)blockIdx.x * TOPK_C + tid;
+        tr_val[q] = z;
+        tr_idx[q] = keep ? my_i : 0x7FFFFFFF;
+        smp.part_raw[q] = keep ? my_v : 0.0f;
+        smp.part_max[q] = keep ? my_v : -INFINITY;
+        tr_sum[q] = keep ? 1.0f : 0.0f;
     }
 }
 }  // namespace
@@ -630,6 +692,20 @@ void launch_topk_merge(hipStream_t s, const float* cand_val, const int* cand_idx
     else
         hipLaunchKernelGGL(topk_merge_kernel<64>, dim3(B), dim3(256), 0, s, cand_val, cand_idx, n_part, c, k, part_val, part_idx, part_sum, part_max,
                            top_ids, top_logprobs, row_dev, skip);
+}
+
+void launch_truncate_partials(hipStream_t s, const float* cand_val, const int* cand_idx, int n_part, int c, int B, int top_k, float top_p,
+                              const SampleArgs& smp, float* tr_val, int* tr_idx, float* tr_sum, const int* skip) {
+    const size_t total = (size_t)n_part * c;
+    if (n_part < 1 || c < 1 || B < 1) throw std::runtime_error("truncate partials: empty candidate rows");
+    if (total > (size_t)256 * 64) throw std::runtime_error("truncate partials: more candidates than the kernel's registers hold");
+    if (top_k < 1 || top_k > TOPK_C || !(top_p > 0.0f && top_p <= 1.0f)) throw std::runtime_error("truncate partials: top_k must be 1 .. 8 and top_p in (0, 1]");
+    if (total <= (size_t)256 * 32)
+        hipLaunchKernelGGL(truncate_partials_kernel<32>, dim3(B), dim3(256), 0, s, cand_val, cand_idx, n_part, c, top_k, top_p, smp, tr_val, tr_idx,
+                           tr_sum, skip);
+    else
+        hipLaunchKernelGGL(truncate_partials_kernel<64>, dim3(B), dim3(256), 0, s, cand_val, cand_idx, n_part, c, top_k, top_p, smp, tr_val, tr_idx,
+                           tr_sum, skip);
 }
 
 #define SVLN_INST(T)                                                                                                              \

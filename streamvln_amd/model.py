@@ -198,6 +198,7 @@ class StreamVLNForCausalLM:
         self.allowed_token_ids = None                              # set_allowed_tokens: the list in force (tuple), None when off
         self._sampling = None                                      # set_sampling: None (greedy) or (temperature, seed) the engine holds
         self.sampling_seed = 0                                     # seed of the noise of generate(do_sample=True) (see set_sampling)
+        self.sampling_truncation = None                            # None or (top_k, top_p): applied whenever sampling is switched on (see set_sampling_truncation)
         self._batch_draft = False                                  # set_batch_draft: the scheduler consumes drafts
         self._group_pending: Dict[int, int] = {}                   # env_id -> sequences of its group turn awaiting select_sequence
         self.reset(max_envs)
@@ -465,11 +466,14 @@ class StreamVLNForCausalLM:
         if kwargs.get("num_beams", 1) != 1:
             raise NotImplementedError(f"num_beams={kwargs.get('num_beams')!r}: only greedy decoding and temperature sampling (num_beams=1) are on the path")
         if kwargs.get("do_sample", False):
-            # temperature sampling only (set_sampling): truncated sampling would need the sorted distribution, which the engine never builds
+            # the per-call keys stay refused: truncation is a setting of the model (set_sampling_truncation / sampling_truncation), as
+            # the seed is, so that every call of a run samples under the same rule
             if kwargs.get("top_k") not in (None, 0):
-                raise NotImplementedError(f"top_k={kwargs['top_k']!r}: do_sample=True supports the temperature only (top_k None or 0)")
+                raise NotImplementedError(f"top_k={kwargs['top_k']!r}: do_sample=True takes the temperature only (top_k None or 0); "
+                                          f"truncated sampling is set on the model: set_sampling_truncation(top_k, top_p)")
             if kwargs.get("top_p") not in (None, 1.0):
-                raise NotImplementedError(f"top_p={kwargs['top_p']!r}: do_sample=True supports the temperature only (top_p None or 1.0)")
+                raise NotImplementedError(f"top_p={kwargs['top_p']!r}: do_sample=True takes the temperature only (top_p None or 1.0); "
+                                          f"truncated sampling is set on the model: set_sampling_truncation(top_k, top_p)")
         if eos is None:
             eos = self.generation_config.eos_token_id
         eos = [int(e) for e in (eos if isinstance(eos, (list, tuple)) else [eos])]
@@ -531,7 +535,7 @@ class StreamVLNForCausalLM:
                 t = getattr(self.generation_config, "temperature", None)
             want = (float(1.0 if t is None else t), int(self.sampling_seed))
         if want != self._sampling:
-            self.set_sampling(None) if want is None else self.set_sampling(*want)
+            self.set_sampling(None) if want is None else self._switch_sampling_on(*want)
 
     def _scores(self, getter, *args, n_new, device):
         """token_logprobs [1, n_new] (fp32, on `device`) of a finished turn from one of the engine's score getters"""
@@ -601,7 +605,7 @@ class StreamVLNForCausalLM:
             except Exception:
                 # a refused call changes no state: the sampling switch this call flipped goes back to what the engine held
                 if self._sampling != held:
-                    self.set_sampling(None) if held is None else self.set_sampling(*held)
+                    self.set_sampling(None) if held is None else self._switch_sampling_on(*held)
                 raise
         # the reference's bookkeeping that needs no engine call: the KV handle must be this env's current one; curr_t counts the turns
         if past is not None and (not isinstance(past, KVHandle) or past.env_id != env_id or past.epoch != self._epoch[env_id]):
@@ -1169,6 +1173,42 @@ class StreamVLNForCausalLM:
         _check(self._lib.svln_set_allowed_tokens(self._h, arr.ctypes.data_as(C.POINTER(C.c_int64)), int(arr.size)))
         self.allowed_token_ids = tuple(want)
 
+    @staticmethod
+    def _check_truncation(top_k, top_p):
+        """(top_k, top_p) -> None (off) or the pair the engine takes; the engine's own refusals, raised before any switch"""
+        k = 0 if top_k is None else int(top_k)
+        p = 1.0 if top_p is None else float(top_p)
+        if not 0 <= k <= 8:
+            raise ValueError(f"set_sampling_truncation: top_k must be None / 0 (off) or 1 .. 8, got {top_k!r}")
+        if not (0.0 < p <= 1.0):
+            raise ValueError(f"set_sampling_truncation: top_p must lie in (0, 1], got {top_p!r}")
+        if k == 0 and p < 1.0:
+            raise ValueError(f"set_sampling_truncation: top_p={top_p!r} needs top_k = 1 .. 8 (the nucleus is taken over at most 8 listed ids)")
+        return (k, p) if k else None
+
+    def _switch_sampling_on(self, t, sd):
+        """the engine switch, then self.sampling_truncation (an "on" call keeps the engine's truncation; applying it again changes nothing)"""
+        tr = self._check_truncation(*(self.sampling_truncation or (None, None)))
+        _check(self._lib.svln_set_sampling(self._h, 1, t, sd & 0xFFFFFFFFFFFFFFFF))
+        self._sampling = (t, sd)
+        _check(self._lib.svln_sampling_truncation(self._h, *(tr or (0, 1.0))))
+
+    def set_sampling_truncation(self, top_k: Optional[int] = None, top_p: Optional[float] = None):
+        """Opt-in, default off (svln_sampling_truncation): truncated sampling, an attribute of set_sampling.  top_k in 1 .. 8, top_p in
+        (0, 1] (with a top_k); no argument, or top_k None / 0 with top_p None / 1: off.  HF's warper order -- temperature, then the top_k
+        most probable ids (an exact tie on the k-th value keeps the lowest ids, exactly k; HF keeps every tied id), then the smallest
+        prefix of those whose mass under their own softmax reaches top_p.  The id is the untruncated sample conditioned on the kept set
+        (the same noise: whenever the untruncated id is kept, it is the id), and `token_logprobs` / `top_logprobs` are taken over the
+        kept set (HF's `scores` after the warpers; as under an allowed list).  The pair is held in self.sampling_truncation (None: off)
+        and applied whenever Python switches sampling on -- set_sampling(T, seed) and the automatic flip of generate(do_sample=True),
+        as self.sampling_seed is; while sampling is on, this call applies it at once (the draw counters go on).  set_sampling(None)
+        clears it in the engine, not on the model.  Per-call `top_k=` / `top_p=` keys of generate stay refused.  Forced turns score the
+        untruncated softmax.  Refused (nothing changes) on bad values, while scheduler turns are in flight and while a group is pending."""
+        tr = self._check_truncation(top_k, top_p)
+        if self._sampling is not None:
+            _check(self._lib.svln_sampling_truncation(self._h, *(tr or (0, 1.0))))
+        self.sampling_truncation = tr
+
     def set_sampling(self, temperature: Optional[float] = 1.0, seed: int = 0):
         """Opt-in, default off (svln_set_sampling).  set_sampling(T, seed): every turn samples its ids from softmax(processed logits / T)
         instead of taking the arg-max -- exactly, by the Gumbel-max identity: the lm_head kernels add noise G(seed, env slot, draw, column)
@@ -1177,6 +1217,7 @@ class StreamVLNForCausalLM:
         their logits agree, and a run is reproducible.  `draw` counts the ids the env has emitted since this call: EVERY call, also
         one that repeats the current setting, restarts the counters.  With set_token_scores on, `token_logprobs` is
         log softmax(processed / T)[id] (HF's `scores` under sampling).  set_sampling(None): off, the greedy path.
+        Truncated (top-k / top-p) sampling is set_sampling_truncation: the pair it holds is applied after every switch-on here.
         generate / generate_batch / submit flip the switch themselves from `do_sample=` / `temperature=` (see _sync_sampling), with
         self.sampling_seed as the seed.  An explicit `do_sample=False` -- StreamingAgent's default request carries it -- switches the
         engine back to greedy: set_sampling alone samples only for calls that pass do_sample=True or leave the key out; build the agents
@@ -1189,8 +1230,7 @@ class StreamVLNForCausalLM:
         t, sd = float(temperature), int(seed)
         if not (t > 0 and np.isfinite(t)):
             raise ValueError(f"set_sampling: the temperature must be finite and > 0, got {temperature!r}")
-        _check(self._lib.svln_set_sampling(self._h, 1, t, sd & 0xFFFFFFFFFFFFFFFF))
-        self._sampling = (t, sd)
+        self._switch_sampling_on(t, sd)
 
     def set_batch_draft(self, enable: bool):
         """opt-in drafts in the scheduler's prefill pass (svln_set_batch_draft): the first ids of a turn's draft (`draft_ids` of submit /
