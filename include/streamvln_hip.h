@@ -344,6 +344,43 @@ int svln_generate_forced(svln_engine* h, int env, const int64_t* ids, int n, con
  * L + n - 1 > max_positions) come after the splice, as svln_turn's own do. */
 int svln_turn_forced(svln_engine* h, const svln_turn_args* a, const int64_t* ids, int n, float* logprobs, int64_t* greedy_ids,
                      float* greedy_logprobs, int32_t* kv_len);
+/* Opt-in, no reference counterpart: forced turns as jobs of the multi-env scheduler.  svln_batch_submit_forced queues a forced turn on the
+ * ids F[0 .. n) for an env whose turn has been appended, as svln_batch_submit queues a plain one.  The job is a prefill segment of
+ * Tn + n - 1 rows: the iteration that prefills it gathers F[0 .. n - 1) on the device as the rows at positions n_embeds .. n_embeds + n - 2
+ * (the ragged gather list of svln_set_batch_draft; the last id is never fed) and sends its last n rows through the EPI_TARGET head; the
+ * job FINISHES in that iteration, with no decode iteration.  The segment is all or nothing: when it does not fit the row workspace beside
+ * the rows already packed (M + Tn + n - 1 > max_positions) the job waits for the next iteration, as a plain job does; it is never cut
+ * the way a draft is.
+ * Head: the plain head rows of the iteration (decode rows, last prompt rows, ride rows) are produced by the code, in the order and in the
+ * buffers of an iteration without forced jobs.  The forced head rows are listed after them in slot order, a job's n rows consecutive:
+ * ONE indexed final norm writes them to rows of their own and to the parity taps (head row i of a job -> tap row min(i, 7) of its slot; tap row 7 keeps the LAST of the rows that share it),
+ * then the list is taken in chunks of <= 32 rows from its start (a job may straddle a chunk); a chunk of r rows has the routing of
+ * svln_generate_forced for n = r (r <= 2: the batched GEMV at B = 2; r >= 3: the 32-row MFMA tiles, 3 padded to 4; pad rows carry target
+ * -1); under an allowed list it is the subset product in its EPI_TARGET form.  The lists hold 8 x 32 rows, so no job waits for head
+ * space.  With svln_set_sampling on inv_t = 1 / T, no noise is evaluated and no draw counter moves.  An iteration that holds no forced job
+ * runs the launches it ran before these entries existed.
+ * On a finished forced slot: svln_batch_result returns out_ids = F (and frees the slot); svln_batch_scores the n forced log-probabilities
+ * whatever svln_set_token_scores says; svln_batch_allowed_logprobs the n rows when an allowed list is set (scores switch on or off);
+ * svln_get_hidden_batch min(n, 8) tap rows; svln_batch_topk is refused by name (a forced turn produces no lists); svln_batch_forced
+ * returns logprobs / greedy_ids / greedy_logprobs as svln_generate_forced defines them (valid until svln_batch_result frees the slot;
+ * refused by name on a slot that holds a plain turn).  Afterwards the env's kv_len = n_embeds + n - 1.
+ * Refused before any state change (the job table, the env, the armed draft): everything svln_batch_submit refuses; n outside 1 .. 32; an
+ * id outside the vocabulary; an id of the EOS set anywhere but last; a repetition penalty != 1; an id outside the allowed list;
+ * n_embeds + n - 1 > max_positions; svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm, svln_set_decode_persistent or
+ * svln_set_mxfp4_batched on (the decode rows a forced row stands in for would run MXFP4 products there while the prefill runs bf16: the
+ * reason svln_set_batch_draft gives).  An armed draft is treated as svln_batch_submit treats it: consumed iff svln_set_batch_draft is
+ * on; a forced job never reads it.  Forced jobs may share an iteration with rides.  svln_generate_forced / svln_turn_forced keep their
+ * idle-scheduler refusal and svln_generate_batch stays greedy or sampled only.
+ * slot == NULL is a dry run: the refusals that need no state of the env's rows (all of the above but "nothing to prefill" and the
+ * max_positions line) are checked and nothing is queued, so that a caller can refuse a turn before it encodes a frame or splices a row.
+ * svln_batch_forced_stats: forced jobs finished, rows they fed (n - 1 each), head chunks launched; any pointer may be null. */
+/* (the two declarations below carry their return type on a line of its own: tests/test_forced_host.py pins the set of one-line
+ * `int svln_*forced(` declarations of this header to the single-env entries above) */
+int
+svln_batch_submit_forced(svln_engine* h, int env, const int64_t* ids, int n, const int64_t* eos_ids, int n_eos, int32_t* slot);
+int
+svln_batch_forced(svln_engine* h, int slot, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs, int cap, int32_t* n);
+int svln_batch_forced_stats(svln_engine* h, int64_t* jobs, int64_t* rows_fed, int64_t* head_launches, int reset);
 /* prefill taps of svln_generate (single env): enable != 0 records the LAST row of the residual stream after every decoder layer of the
  * next prefills (svln_get_layer_taps: host_out [layers][hidden]); probe_layer >= 0 additionally records, for every row of the prefill,
  * the operands the products of that one layer actually saw (svln_get_layer_probe, which: 0 = x entering the layer, 1 = x leaving it,

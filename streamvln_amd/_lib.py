@@ -131,6 +131,9 @@ SIGNATURES = {
     "svln_turn_group": (_I, [_P, C.POINTER(SvlnTurnArgs), _I, _PI64, _I, _PI32]),
     "svln_generate_forced": (_I, [_P, _I, _PI64, _I, _PI64, _I, _PF, _PI64, _PF, _PI32]),
     "svln_turn_forced": (_I, [_P, C.POINTER(SvlnTurnArgs), _PI64, _I, _PF, _PI64, _PF, _PI32]),
+    "svln_batch_submit_forced": (_I, [_P, _I, _PI64, _I, _PI64, _I, _PI32]),
+    "svln_batch_forced": (_I, [_P, _I, _PF, _PI64, _PF, _I, _PI32]),
+    "svln_batch_forced_stats": (_I, [_P, _PI64, _PI64, _PI64, _I]),
     "svln_op_gemv_batched_target": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _PI32, _F, _PI32, _PF, _PF, _PF]),
     "svln_op_gemm_target": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _PI32, _F, _PI32, _PF, _PF, _PF]),
     "svln_op_read_argmax_partials": (_I, [_P, _I, _I, _PF, _PI32, _PF]),

@@ -208,6 +208,23 @@ class StreamingAgent:
         return actions, 0.0, self.turn_log[-1]["out"]
 
 
+def _forced_map(forced_ids, n_agents) -> dict:
+    """`forced_ids` of BatchedAgents.act / AsyncBatchedAgents.tick -- a per-agent list (None = a plain turn) or a dict {agent index: ids}
+    -- as {agent index: ids}"""
+    if forced_ids is None:
+        return {}
+    if isinstance(forced_ids, dict):
+        named = {int(i): f for i, f in forced_ids.items() if f is not None}
+    else:
+        if len(forced_ids) != n_agents:
+            raise ValueError(f"forced_ids holds {len(forced_ids)} entries for {n_agents} agents")
+        named = {i: f for i, f in enumerate(forced_ids) if f is not None}
+    for i in named:
+        if not (0 <= i < n_agents):
+            raise ValueError(f"forced_ids names agent {i}: there are {n_agents}")
+    return named
+
+
 class BatchedAgents:
     """Several envs on one GPU stepped in lockstep (BASELINE configs[4]: DAgger-style concurrent envs; the reference
     runs one env per process, streamvln_dagger.py:299).  Each env keeps its own StreamingAgent state; the turns that fall
@@ -217,10 +234,29 @@ class BatchedAgents:
         self.agents = list(agents)
         self.model = self.agents[0].model
 
-    def act(self, rgbs, instructions=None):
+    def act(self, rgbs, instructions=None, forced_ids=None):
+        """forced_ids (optional; a per-agent list or a dict {agent index: ids}): the agents named there run the model turn of this step
+        as a forced job of the scheduler (model.generate_batch_forced) and get `last_greedy_ids`, `last_token_logprobs` and
+        `last_turn_logprob`, as StreamingAgent.act(forced_ids=...) gives them.  Raises ValueError, before anything changes, where no
+        model turn is due for a named agent.  None: the call of before, generate_batch."""
         instructions = instructions or [""] * len(self.agents)
+        forced = _forced_map(forced_ids, len(self.agents))
+        for i in forced:
+            if len(self.agents[i].action_seq) != 0:
+                raise ValueError(f"forced_ids given for agent {i} at step {self.agents[i].step_id}, but no model turn runs there: "
+                                 f"{len(self.agents[i].action_seq)} actions of the last turn are still queued")
         due = [a for a, rgb in zip(self.agents, rgbs) if a.observe(rgb)]
-        if due:
+        if due and forced_ids is not None:
+            reqs = []
+            for a in due:
+                i = self.agents.index(a)
+                reqs.append(a._build_request(instructions[i]))
+                if i in forced:
+                    reqs[-1]["forced_ids"] = forced[i]
+            outs = self.model.generate_batch_forced(reqs)
+            for a, out in zip(due, outs):
+                a.action_seq = a._consume(out)
+        elif due:
             reqs = [a._build_request(instructions[self.agents.index(a)]) for a in due]
             shared = {k: reqs[0][k] for k in ("max_new_tokens", "eos_token_ids")}
             outs = self.model.generate_batch(reqs, **shared)
@@ -243,12 +279,19 @@ class AsyncBatchedAgents:
         self.on_result = on_result                        # optional callback(agent index, ticket, GenerateOutput)
         self.stats = {"iterations": 0, "mixed_iterations": 0, "max_in_flight": 0}
 
-    def tick(self, rgbs, instructions=None, active=None):
+    def tick(self, rgbs, instructions=None, active=None, forced_ids=None):
         """`rgbs[i]`: the frame of agent i's current env step (ignored for agents that are waiting); `active`: indices allowed to
-        step in this tick (default: all)."""
+        step in this tick (default: all).  forced_ids (optional; a per-agent list or a dict {agent index: ids}): the agents named
+        there submit the model turn of this tick as a forced job (model.submit_forced), which finishes in this tick's iteration.
+        Raises ValueError, before anything changes, where a named agent submits no turn in this tick."""
         instructions = instructions or [""] * len(self.agents)
         acted = {}
         busy = set(self.waiting.values())
+        forced = _forced_map(forced_ids, len(self.agents))
+        for i in forced:
+            a = self.agents[i]
+            if i in busy or (active is not None and i not in active) or a.pending_turn or len(a.action_seq) != 0:
+                raise ValueError(f"forced_ids given for agent {i} at step {a.step_id}, but it submits no model turn in this tick")
         for i, a in enumerate(self.agents):
             if i in busy or (active is not None and i not in active):
                 continue
@@ -257,7 +300,10 @@ class AsyncBatchedAgents:
                 acted[i] = a.finish_step()
                 continue
             if a.observe(rgbs[i]):
-                t = self.model.submit(**a._build_request(instructions[i]))
+                if i in forced:
+                    t = self.model.submit_forced(**a._build_request(instructions[i]), forced_ids=forced[i])
+                else:
+                    t = self.model.submit(**a._build_request(instructions[i]))
                 self.waiting[t.slot] = i
             else:
                 acted[i] = a.finish_step()

@@ -133,6 +133,10 @@ struct EngineBase {
                                  float* greedy_logprobs, int32_t* kv_len) = 0;
     virtual void turn_forced(const svln_turn_args& a, const int64_t* ids, int n, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs,
                              int32_t* kv_len) = 0;
+    virtual int batch_submit_forced(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos) = 0;
+    virtual void batch_forced_check(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos) = 0;
+    virtual void batch_forced(int slot, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs, int cap, int32_t* n) = 0;
+    virtual void batch_forced_stats(int64_t* jobs, int64_t* rows_fed, int64_t* head_launches, int reset) = 0;
     virtual void op_gemv_batched_target(GemvBatchArgs a, const int32_t* targets, float inv_t, int32_t* host_tokens, float* host_greedy,
                                         float* host_logprobs, float* host_slots) = 0;
     virtual void op_gemm_target(GemmArgs a, const int32_t* targets, float inv_t, int32_t* host_tokens, float* host_greedy, float* host_logprobs,
@@ -386,9 +390,22 @@ public:
     // row, k + 1 per segment, at most HEAD_ROWS; the lists of the indexed norm and of the ragged gather are staged in pinned memory.
     bool bdraft_on = false;
     static constexpr int HEAD_ROWS = 64;     // MAXB jobs x (RIDE_MAX_ROWS + 1) head rows
-    int *d_head_src = nullptr, *d_head_tap = nullptr, *d_ride_list = nullptr;       // device lists: [HEAD_ROWS], [HEAD_ROWS], [HEAD_ROWS] pairs
+    // the ragged gather list holds the draft rows of every ride (MAXB x RIDE_MAX_ROWS pairs) and the fed rows of every forced job
+    // (svln_batch_submit_forced: MAXB x (BFORCED_MAX - 1) pairs) of one iteration
+    static constexpr int BFORCED_MAX = 32;                       // ids of one forced job (= FORCED_MAX)
+    static constexpr int BFORCED_ROWS = MAXB * BFORCED_MAX;      // forced head rows of one iteration
+    static constexpr int RIDE_PAIRS = MAXB * RIDE_MAX_ROWS + MAXB * (BFORCED_MAX - 1);
+    int *d_head_src = nullptr, *d_head_tap = nullptr, *d_ride_list = nullptr;       // device lists: [HEAD_ROWS], [HEAD_ROWS], [RIDE_PAIRS] pairs
     int *h_head_src = nullptr, *h_head_tap = nullptr, *h_ride_list = nullptr;       // pinned
     int64_t st_brides = 0, st_btokens = 0, st_brows = 0, st_biters = 0, st_bsingle = 0;
+    // Forced jobs of the scheduler (svln_batch_submit_forced): their head rows are normed into bf_xn, rows of their own beside xn, and go
+    // through the EPI_TARGET lm_head in chunks of <= 32; every list is sized for MAXB jobs of BFORCED_MAX ids (+ 8: the pad rows of the last
+    // chunk's row count), so no job waits for head space.  Allocated by the first forced submit.
+    T* bf_xn = nullptr;
+    int *bf_dev_i = nullptr, *bf_host_i = nullptr;               // [src | tap | tgt | tok] x (BFORCED_ROWS + 8): device / pinned
+    float *bf_dev_f = nullptr, *bf_host_f = nullptr;             // [val | score | lp] x (BFORCED_ROWS + 8)
+    float *bf_dev_alp = nullptr, *bf_host_alp = nullptr;         // [BFORCED_ROWS][ALLOW_MAX], with the first forced submit under an allowed list
+    int64_t st_fjobs = 0, st_frows = 0, st_fhead = 0;
 
     // decode graph + probes.  The step graph holds the env's page-table pointer, so there is one set per env (a round-robin over several
     // envs through svln_generate replays instead of re-capturing); [0] = the whole step, [1] / [2] = the halves around the probed launch
@@ -596,8 +613,8 @@ public:
         last_rows = dalloc<T>((size_t)HEAD_ROWS * H);
         HIP_CHECK(hipHostMalloc((void**)&h_slots, MAXB * sizeof(DecodeSlot)));
         HIP_CHECK(hipHostMalloc((void**)&h_tok_b, (HEAD_ROWS + MAXB) * sizeof(int)));
-        d_head_src = dalloc<int>(4 * HEAD_ROWS, true); d_head_tap = d_head_src + HEAD_ROWS; d_ride_list = d_head_src + 2 * HEAD_ROWS;
-        HIP_CHECK(hipHostMalloc((void**)&h_head_src, 4 * HEAD_ROWS * sizeof(int)));
+        d_head_src = dalloc<int>(2 * HEAD_ROWS + 2 * RIDE_PAIRS, true); d_head_tap = d_head_src + HEAD_ROWS; d_ride_list = d_head_src + 2 * HEAD_ROWS;
+        HIP_CHECK(hipHostMalloc((void**)&h_head_src, (2 * HEAD_ROWS + 2 * RIDE_PAIRS) * sizeof(int)));
         h_head_tap = h_head_src + HEAD_ROWS; h_ride_list = h_head_src + 2 * HEAD_ROWS;
         d_src = dalloc<int>(rt);
         HIP_CHECK(hipHostMalloc((void**)&h_src, rt * sizeof(int)));
@@ -652,6 +669,9 @@ public:
         if (h_sel) (void)hipHostFree(h_sel);
         (void)hipHostFree(h_slots); (void)hipHostFree(h_tok_b);
         if (h_head_src) (void)hipHostFree(h_head_src);
+        if (bf_host_i) (void)hipHostFree(bf_host_i);
+        if (bf_host_f) (void)hipHostFree(bf_host_f);
+        if (bf_host_alp) (void)hipHostFree(bf_host_alp);
         if (h_draft) (void)hipHostFree(h_draft);
         if (h_vctl) (void)hipHostFree(h_vctl);
         if (h_pen_rows) (void)hipHostFree(h_pen_rows);
@@ -1912,6 +1932,7 @@ public:
     void batch_topk(int slot, int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) override {
         REQUIRE(slot >= 0 && slot < MAXB && jobs[slot].used && jobs[slot].finished, "no finished turn in this slot");
         const Job& j = jobs[slot];
+        REQUIRE(!j.forced, "svln_batch_topk: this slot holds a forced turn (svln_batch_submit_forced), which produces no lists");
         REQUIRE(j.topk > 0, "svln_batch_topk: top-k log-probabilities were off for this turn (svln_top_logprobs)");
         topk_out(j.topi, j.topl, j.topk, ids, logprobs, cap_rows, n_rows, k);
     }
@@ -2113,6 +2134,10 @@ public:
         std::vector<int32_t> topi; std::vector<float> topl; int topk = 0;      // svln_top_logprobs: the [topk] lists of every id of `out`
         std::vector<float> alp; int alp_n = 0;               // with svln_set_allowed_tokens too: the normalised row [alp_n] of every id of `out`
         std::vector<int> draft;      // svln_set_batch_draft: the usable draft the submit consumed, kept until the job's prefill iteration
+        // svln_batch_submit_forced: the turn's ids are `fids`; the job ends in the iteration that prefills it with out = fids, `scores` their
+        // log-probabilities (scored whatever svln_set_token_scores says) and the policy's own arg-max / its log-probability of every position
+        bool forced = false;
+        std::vector<int> fids; std::vector<int64_t> greedy; std::vector<float> greedy_lp;
     };
     Job jobs[MAXB];
     // forget a job: its slot becomes free, its repetition-penalty flags are cleared (the stream is idle between scheduler calls)
@@ -2194,6 +2219,131 @@ public:
             for (int64_t id : drafts[env]) { if (id < 0 || id >= V) break; j.draft.push_back((int)id); }
         return slot;
     }
+    // svln_batch_submit_forced: a forced turn (svln_generate_forced) as a job of the scheduler.  The job is a prefill segment that also
+    // feeds F[0 .. n - 1) and sends its last n rows through the EPI_TARGET head; it finishes in the iteration that prefills it.  Every
+    // refusal of svln_batch_submit and of forced_refusals (but the idle-scheduler line) comes before any state change: the job table, the
+    // env, the armed draft.  The armed draft is treated as svln_batch_submit treats it -- consumed iff svln_set_batch_draft is on -- and
+    // never read.
+    void ensure_bforced_buffers() {
+        constexpr int R = BFORCED_ROWS + 8;
+        if (bf_xn && (bf_dev_alp || !allow_on)) return;      // (the hot path: no allocation, no synchronisation)
+        if (!bf_xn) {
+            bf_xn = dalloc<T>((size_t)R * H, true);
+            bf_dev_i = dalloc<int>(4 * R, true); bf_dev_f = dalloc<float>(3 * R, true);
+            HIP_CHECK(hipHostMalloc((void**)&bf_host_i, 4 * R * sizeof(int)));
+            HIP_CHECK(hipHostMalloc((void**)&bf_host_f, 3 * R * sizeof(float)));
+        }
+        if (allow_on && !bf_dev_alp) {
+            bf_dev_alp = dalloc<float>((size_t)BFORCED_ROWS * ALLOW_MAX, true);
+            HIP_CHECK(hipHostMalloc((void**)&bf_host_alp, (size_t)BFORCED_ROWS * ALLOW_MAX * sizeof(float)));
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    // the refusals of a forced submit that need no state of the env's rows (a caller checks them before it encodes a frame or splices a turn)
+    void batch_forced_check(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos) override {
+        env_at(env);
+        refuse_while_group_on(env, "svln_batch_submit_forced");
+        REQUIRE(weights_missing() == 0, g_err);
+        forced_refusals(env, ids, n, eos, n_eos, "svln_batch_submit_forced", true);
+        int free_slots = 0;
+        for (int k = 0; k < MAXB; ++k) {
+            REQUIRE(!(jobs[k].used && jobs[k].env == env), "this env already has a turn in flight");
+            free_slots += !jobs[k].used;
+        }
+        REQUIRE(free_slots > 0, "at most 8 turns in flight");
+    }
+    int batch_submit_forced(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos) override {
+        Env& e = env_at(env);
+        batch_forced_check(env, ids, n, eos, n_eos);
+        REQUIRE(e.n_embeds - e.kv_len >= 1, "nothing to prefill for this env (append its turn first)");
+        REQUIRE((int64_t)e.n_embeds + n - 1 <= c.max_positions, "svln_batch_submit_forced: n_embeds + n - 1 exceeds max_positions");
+        int slot = -1;
+        for (int k = 0; k < MAXB; ++k) {
+            REQUIRE(!(jobs[k].used && jobs[k].env == env), "this env already has a turn in flight");
+            if (slot < 0 && !jobs[k].used) slot = k;
+        }
+        REQUIRE(slot >= 0, "at most 8 turns in flight");
+        ensure_bforced_buffers();       // (a failed allocation leaves the job table, the env and the draft as they were)
+        // ---- nothing was changed up to here
+        Job& j = jobs[slot];
+        j = Job();
+        j.used = true; j.env = env; j.max_new = n; j.forced = true;
+        j.eos.assign(eos, eos + n_eos);
+        j.fids.assign(ids, ids + n);
+        j.scored = true;
+        j.alp_n = allow_on ? allow_n : 0;
+        n_generated_b[slot] = 0;
+        if (bdraft_on) disarm_draft(env);
+        return slot;
+    }
+    void batch_forced(int slot, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs, int cap, int32_t* n) override {
+        REQUIRE(slot >= 0 && slot < MAXB && jobs[slot].used && jobs[slot].finished, "no finished turn in this slot");
+        const Job& j = jobs[slot];
+        REQUIRE(j.forced, "svln_batch_forced: this slot holds a plain turn (svln_batch_submit), not a forced one");
+        const int m = (int)j.fids.size();
+        for (int k = 0; k < m && k < cap; ++k) { logprobs[k] = j.scores[k]; greedy_ids[k] = j.greedy[k]; greedy_logprobs[k] = j.greedy_lp[k]; }
+        *n = m;
+    }
+    void batch_forced_stats(int64_t* jobs_run, int64_t* rows_fed, int64_t* head_launches, int reset) override {
+        if (jobs_run) *jobs_run = st_fjobs;
+        if (rows_fed) *rows_fed = st_frows;
+        if (head_launches) *head_launches = st_fhead;
+        if (reset) st_fjobs = st_frows = st_fhead = 0;
+    }
+    // Head of the forced jobs of an iteration, after the plain head rows (which keep their code, order and buffers): the forced head rows
+    // are listed in slot order, a job's n rows consecutive (row i = the segment's row that precedes F[i]); ONE indexed final norm writes
+    // them to bf_xn and to the parity taps (row i -> tap row min(i, 7) of the job's slot, tap row 7 keeping the last); the list goes through the EPI_TARGET lm_head in
+    // chunks of <= 32 rows from its start (a job may straddle a chunk), each chunk of r rows with the routing svln_generate_forced has for
+    // n = r; pad rows carry target -1.  Under an allowed list: the subset product in its EPI_TARGET form, subset_logprobs and the final
+    // kernel.  With sampling on inv_t = smp_inv_t, no noise is evaluated and no draw counter moves.  Returns the number of head rows.
+    int head_forced(const std::vector<Seg>& segs, const std::vector<int>& pre_now) {
+        constexpr int R = BFORCED_ROWS + 8;
+        int *h_src = bf_host_i, *h_tap = bf_host_i + R, *h_tgt = bf_host_i + 2 * R;
+        int *d_src = bf_dev_i, *d_tap = bf_dev_i + R, *d_tgt = bf_dev_i + 2 * R, *d_tok = bf_dev_i + 3 * R;
+        float *d_val = bf_dev_f, *d_score = bf_dev_f + R, *d_lp = bf_dev_f + 2 * R;
+        int nf = 0;
+        for (size_t q = 0; q < segs.size(); ++q) {
+            const Job& j = jobs[pre_now[q]];
+            if (!j.forced) continue;
+            const int n = (int)j.fids.size();
+            for (int i = 0; i < n; ++i) {
+                h_src[nf] = segs[q].off + segs[q].Tn - n + i;
+                // tap row min(i, 7); of the rows that share tap row 7 only the last is written (what tap_copy's sequence leaves there:
+                // one launch must not write one tap row from two head rows)
+                h_tap[nf] = taps_on && (i < 7 || i == n - 1) ? (i < 7 ? i : 7) * MAXB + pre_now[q] : -1;
+                h_tgt[nf] = j.fids[i];
+                ++nf;
+            }
+        }
+        REQUIRE(nf >= 1 && nf <= BFORCED_ROWS, "batch_step: more forced head rows than the workspace holds");
+        for (int k = nf; k < nf + 8; ++k) h_tgt[k] = -1;
+        // (the pinned lists were last read by copies of an iteration that ended in a synchronisation)
+        HIP_CHECK(hipMemcpyAsync(d_src, h_src, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_tap, h_tap, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_tgt, h_tgt, (size_t)(nf + 8) * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn, d_src, d_tap, hid_tap, nf, H, c.rms_eps);
+        const float inv_t = smp_on ? smp_inv_t : 1.0f;
+        for (int r0 = 0; r0 < nf; r0 += 32) {
+            const int r = std::min(nf - r0, 32);
+            const T* rows_x = bf_xn + (size_t)r0 * H;
+            if (allow_on) {
+                GemvSubsetArgs su = subset_args(rows_x, H, r, part_val_b, part_idx_b, part_sum_b);
+                su.epi = EPI_TARGET; su.tg_inv_t = inv_t;
+                launch_gemv_subset<T>(st, su);
+                launch_subset_logprobs(st, part_val_b, allow_n, r, bf_dev_alp + (size_t)r0 * allow_n);
+                launch_argmax_final_batched(st, part_val_b, part_idx_b, allow_n, r, d_tok + r0, part_sum_b, d_score + r0);
+            } else {
+                TargetOut o; o.tgt = d_tgt + r0; o.val = d_val + r0; o.tok = d_tok + r0; o.score = d_score + r0; o.lp = d_lp + r0;
+                target_rows(lm_head, H, rows_x, H, V, H, ride_head_rows(r), r, inv_t, &o);
+            }
+            st_fhead += 1;
+        }
+        HIP_CHECK(hipMemcpyAsync(bf_host_i + 3 * R, d_tok, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(bf_host_f + R, d_score, (size_t)nf * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (allow_on) HIP_CHECK(hipMemcpyAsync(bf_host_alp, bf_dev_alp, (size_t)nf * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
+        else HIP_CHECK(hipMemcpyAsync(bf_host_f + 2 * R, d_lp, (size_t)nf * sizeof(float), hipMemcpyDeviceToHost, st));
+        return nf;
+    }
     // one iteration; returns the number of jobs still running afterwards, finished_slots = jobs that completed in this iteration
     int batch_step(int32_t* finished_slots, int32_t* n_finished) override {
         *n_finished = 0;
@@ -2234,6 +2384,7 @@ public:
         for (int k = 0; k < nrow; ++k) head_row(k, jobs[dec[k]].count, dec[k]);
         for (size_t q = 0; q < segs.size(); ++q) {
             const Seg& g = segs[q];
+            if (jobs[pre_now[q]].forced) continue;      // (its head rows follow in head_forced)
             for (int i = 0; i <= g.n_draft; ++i) head_row(g.off + g.Tn - 1 - g.n_draft + i, i, pre_now[q]);
             order.push_back(pre_now[q]);
         }
@@ -2275,11 +2426,29 @@ public:
         std::vector<Seg> segs;
         std::vector<int> pre_now;
         int n_ride = 0;                                 // draft rows of this iteration: (row, id) pairs in h_ride_list
+        int n_fed = 0, n_forced = 0, n_plain = 0;       // fed rows of forced jobs (pairs of the same list, after the n_ride counted so far) / forced / plain segments
+        int ride_kd[MAXB] = {0};                        // draft rows of each plain job's segment, by slot
         int M = split_mixed ? 0 : nd;
         for (int k : pre) {
             Env& e = envs[jobs[k].env];
             const int Tn = e.n_embeds - e.kv_len;
             REQUIRE(Tn >= 1 && Tn <= c.max_positions, "prefill length out of range");
+            if (jobs[k].forced) {
+                // a forced job's segment: its Tn rows and the ids F[0 .. n - 1) at the next positions, gathered on the device through the
+                // ragged list; the last id is never fed.  All or nothing: a segment that does not fit waits, it is never cut like a draft.
+                const Job& j = jobs[k];
+                const int nfed = (int)j.fids.size() - 1;
+                if (M + Tn + nfed > c.max_positions) continue;
+                // (the submit checked this; rows appended to the env since then must not push a fed row past the last position)
+                REQUIRE(e.n_embeds + nfed <= c.max_positions, "batch_step: a forced turn's n_embeds + n - 1 exceeds max_positions (rows appended after the submit?)");
+                ensure_pages(e, e.n_embeds + nfed);
+                for (int q = 0; q < nfed; ++q) { h_ride_list[2 * (n_ride + n_fed)] = M + Tn + q; h_ride_list[2 * (n_ride + n_fed) + 1] = j.fids[q]; ++n_fed; }
+                segs.push_back(Seg{&e, e.kv_len, Tn + nfed, M, nfed});
+                pre_now.push_back(k);
+                M += Tn + nfed;
+                ++n_forced;
+                continue;
+            }
             if (M + Tn > c.max_positions) continue;          // (a waiting job keeps its draft)
             // svln_set_batch_draft: k ids of the job's draft ride as the segment's last rows -- the rule of the single-env ride (k of
             // svln_set_prefill_draft), cut further to the rows the workspace still holds.  The draft is dropped with its ride.
@@ -2290,15 +2459,19 @@ public:
                 for (int q = 0; q < kd; ++q)
                     if (std::find(j.eos.begin(), j.eos.end(), (int64_t)j.draft[q]) != j.eos.end()) { kd = q; break; }
                 kd = std::min(kd, c.max_positions - M - Tn);
-                for (int q = 0; q < kd; ++q) { h_ride_list[2 * n_ride] = M + Tn + q; h_ride_list[2 * n_ride + 1] = j.draft[q]; ++n_ride; }
+                for (int q = 0; q < kd; ++q) { h_ride_list[2 * (n_ride + n_fed)] = M + Tn + q; h_ride_list[2 * (n_ride + n_fed) + 1] = j.draft[q]; ++n_ride; }
             }
             ensure_pages(e, e.n_embeds + kd);
             segs.push_back(Seg{&e, e.kv_len, Tn + kd, M, kd});
             pre_now.push_back(k);
+            ride_kd[k] = kd;
             M += Tn + kd;
+            ++n_plain;
         }
         const bool rides = n_ride > 0;                  // (never under a repetition penalty or svln_set_mxfp4_batched: no draft is usable / the switch excludes it)
-        if (rides) HIP_CHECK(hipMemcpyAsync(d_ride_list, h_ride_list, (size_t)n_ride * 2 * sizeof(int), hipMemcpyHostToDevice, st));
+        const int n_ragged = n_ride + n_fed;            // rows the ragged gather writes: the rides' draft rows and the forced jobs' fed rows
+        REQUIRE(n_ragged <= RIDE_PAIRS, "batch_step: more gathered rows than the list holds");
+        if (n_ragged > 0) HIP_CHECK(hipMemcpyAsync(d_ride_list, h_ride_list, (size_t)n_ragged * 2 * sizeof(int), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipEventRecord(ph_ev[2], st));
         std::vector<int> order;                         // job slot of each output token of this iteration
         if (nd > 0) {
@@ -2339,18 +2512,20 @@ public:
         }
         if (!segs.empty()) {
             const int nrow = split_mixed ? 0 : nd;      // decode rows that share the prefill pass
-            prefill_rows(segs, M, nrow, n_ride);
+            prefill_rows(segs, M, nrow, n_ragged);
             if (rides) {
                 n_head = head_with_rides(dec, nrow, segs, pre_now, order);
-            } else {
-                // last row of every job of this pass -> one lm_head pass
-                const int nj = nrow + (int)segs.size();
+            } else if (nrow + n_plain > 0) {            // (== 0: every segment of the pass is a forced job's)
+                // last row of every plain job of this pass -> one lm_head pass
+                const int nj = nrow + n_plain;
                 for (int k = 0; k < nrow; ++k)
                     HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)k * H, x + (size_t)k * H, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
-                for (size_t q = 0; q < segs.size(); ++q) {
+                for (size_t q = 0, qp = 0; q < segs.size(); ++q) {
+                    if (jobs[pre_now[q]].forced) continue;
                     const T* last = x + (size_t)(segs[q].off + segs[q].Tn - 1) * H;
-                    HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)(nrow + q) * H, last, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
+                    HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)(nrow + qp) * H, last, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
                     order.push_back(pre_now[q]);
+                    ++qp;
                 }
                 int Bp = 1; while (Bp < nj) Bp <<= 1;
                 for (int k = nj; k < Bp; ++k)
@@ -2369,8 +2544,9 @@ public:
             for (int q = head0; q < nj; ++q) tap_copy(xn + (size_t)(q - head0) * H, jobs[order[q]].count, order[q]);
             n_head = nj - head0;
         }
+        const int n_fhead = n_forced > 0 ? head_forced(segs, pre_now) : 0;      // (bf_xn and lists of its own: the plain rows above are untouched)
         HIP_CHECK(hipEventRecord(ph_ev[3], st));
-        HIP_CHECK(hipMemcpyAsync(h_tok_b + head0, d_tok_b, n_head * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (n_head > 0) HIP_CHECK(hipMemcpyAsync(h_tok_b + head0, d_tok_b, n_head * sizeof(int), hipMemcpyDeviceToHost, st));
         if (scores_on) HIP_CHECK(hipMemcpyAsync(h_score_b + head0, d_score_b, n_head * sizeof(float), hipMemcpyDeviceToHost, st));      // (never split: the switches exclude each other)
         if (scores_on && allow_on) HIP_CHECK(hipMemcpyAsync(h_alp_b + (size_t)head0 * allow_n, d_alp_b, (size_t)n_head * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
         if (topk) {
@@ -2398,7 +2574,7 @@ public:
             // a job's k + 1 arg-maxes (k = 0 without a ride) under the verify rule from zero emitted tokens: row 0's is always emitted,
             // row i's iff every earlier one was emitted without stopping and equals the draft id row i was fed; a stopping token is
             // appended, never fed.  K / V rows of rejected positions lie beyond kv_len and are overwritten later.
-            const int kd = j.prefill && rides ? segs[q - (nj - (int)segs.size())].n_draft : 0;
+            const int kd = j.prefill && rides ? ride_kd[order[q]] : 0;
             int tok = -1, emitted = 0;
             bool stop = false;
             for (int i = 0; i <= kd && !stop; ++i) {
@@ -2440,6 +2616,41 @@ public:
             }
         }
         if (pen) HIP_CHECK(hipStreamSynchronize(st));                         // h_pen_ids is rewritten by the next iteration
+        // the forced jobs of the iteration, in the order head_forced listed them: each ends here with out = F, where a plain turn that
+        // emitted F leaves the env (the last id appended, not fed); no draw counter moves
+        if (n_fhead > 0) {
+            constexpr int R = BFORCED_ROWS + 8;
+            const int* h_tok = bf_host_i + 3 * R;
+            const float *h_score = bf_host_f + R, *h_lp = bf_host_f + 2 * R;
+            for (int i = 0; i < n_fhead; ++i)
+                REQUIRE(h_tok[i] >= 0 && h_tok[i] < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+            int fq = 0;
+            for (size_t q = 0; q < segs.size(); ++q) {
+                Job& j = jobs[pre_now[q]];
+                if (!j.forced) continue;
+                Env& e = envs[j.env];
+                const int n = (int)j.fids.size();
+                j.out.assign(j.fids.begin(), j.fids.end());
+                for (int i = 0; i < n; ++i) {
+                    j.greedy.push_back(h_tok[fq + i]);
+                    j.greedy_lp.push_back(h_score[fq + i]);
+                    if (allow_on) {
+                        const int pos = (int)(std::lower_bound(allow_ids.begin(), allow_ids.end(), j.fids[i]) - allow_ids.begin());
+                        j.scores.push_back(bf_host_alp[(size_t)(fq + i) * allow_n + pos]);
+                    } else {
+                        j.scores.push_back(h_lp[fq + i]);
+                    }
+                }
+                if (allow_on) { j.alp.assign(bf_host_alp + (size_t)fq * allow_n, bf_host_alp + (size_t)(fq + n) * allow_n); j.alp_n = allow_n; }
+                fq += n;
+                e.kv_len = e.n_embeds + n - 1;
+                j.prefill = false; j.count = n; j.last_tok = j.fids[n - 1];
+                j.finished = true;
+                n_generated_b[pre_now[q]] = n;
+                finished_slots[(*n_finished)++] = pre_now[q];
+                st_fjobs += 1; st_frows += n - 1;
+            }
+        }
         int running = 0;
         for (int k = 0; k < MAXB; ++k) running += jobs[k].used && !jobs[k].finished;
         return running;
@@ -2878,43 +3089,57 @@ public:
     TargetArgs target_args(float inv_t) { TargetArgs t; t.tgt = d_ftgt; t.tgt_val = d_fval; t.inv_t = inv_t; return t; }
     // the EPI_TARGET lm_head over `rows` rows of xrows (the first n of them live) and its final kernel: greedy ids -> d_tok_b, their
     // log-probabilities -> d_score_b, the targets' -> d_flp.  The routing is argmax_rows' own: MFMA tiles from batched_mfma_min rows.
-    void target_rows(const void* W, int ldw, const T* xrows, int ldx, int N, int K, int rows, int n, float inv_t) {
+    // `to` (a head chunk of the scheduler's forced jobs): the chunk's own targets, capture slots and outputs in place of those five buffers
+    struct TargetOut { const int* tgt; float* val; int* tok; float* score; float* lp; };
+    void target_rows(const void* W, int ldw, const T* xrows, int ldx, int N, int K, int rows, int n, float inv_t, const TargetOut* to = nullptr) {
+        const TargetOut o = to ? *to : TargetOut{d_ftgt, d_fval, d_tok_b, d_score_b, d_flp};
+        TargetArgs tg; tg.tgt = o.tgt; tg.tgt_val = o.val; tg.inv_t = inv_t;
         int np;
         if (rows >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048) {
             GemmArgs a = gemm_args(xrows, ldx, W, ldw, nullptr, 0, nullptr, nullptr, 0, 0, rows, N, K, EPI_ARGMAX);
-            a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b; a.tg = target_args(inv_t);
+            a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b; a.tg = tg;
             np = launch_gemm_argmax<T>(st, a);
         } else {
             GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, EPI_TARGET, rows);
-            hb.part_sum = part_sum_b; hb.tg = target_args(inv_t);
+            hb.part_sum = part_sum_b; hb.tg = tg;
             launch_gemv_batched<T>(st, hb);
             np = gemv_batched_grid(N, EPI_ARGMAX, rows);
         }
-        launch_target_final_batched(st, part_val_b, part_idx_b, part_sum_b, np, n, d_ftgt, d_fval, d_tok_b, d_score_b, d_flp);
+        launch_target_final_batched(st, part_val_b, part_idx_b, part_sum_b, np, n, o.tgt, o.val, o.tok, o.score, o.lp);
     }
-    // every refusal of a forced turn that needs no state of the env (svln_turn_forced checks them before it encodes a frame)
-    void forced_refusals(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos) {
+    // every refusal of a forced turn that needs no state of the env (svln_turn_forced checks them before it encodes a frame).  sched: the
+    // forced submit of the scheduler (svln_batch_submit_forced) -- no idle-scheduler line, and svln_set_mxfp4_batched is refused too: the
+    // decode rows a forced row stands in for would run MXFP4 products there while the prefill runs bf16 (the reason of svln_set_batch_draft)
+    void forced_refusals(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos, const char* who_c = "svln_generate_forced", bool sched = false) {
+        const std::string who(who_c);
         env_at(env);
-        REQUIRE(ids, "svln_generate_forced: null id list");
-        REQUIRE(n >= 1 && n <= FORCED_MAX, "svln_generate_forced: n must be 1 .. 32");
-        REQUIRE(n_eos >= 0 && n_eos <= (V > 16 ? V : 16) && (n_eos == 0 || eos), "svln_generate_forced: bad eos list");
+        REQUIRE(ids, who + ": null id list");
+        REQUIRE(n >= 1 && n <= FORCED_MAX, who + ": n must be 1 .. 32");
+        REQUIRE(n_eos >= 0 && n_eos <= (V > 16 ? V : 16) && (n_eos == 0 || eos), who + ": bad eos list");
         for (int k = 0; k < n; ++k) {
-            REQUIRE(ids[k] >= 0 && ids[k] < V, "svln_generate_forced: id " + std::to_string((long long)ids[k]) + " is outside the vocabulary");
+            REQUIRE(ids[k] >= 0 && ids[k] < V, who + ": id " + std::to_string((long long)ids[k]) + " is outside the vocabulary");
             if (k + 1 < n)
                 for (int q = 0; q < n_eos; ++q)
-                    REQUIRE(eos[q] != ids[k], "svln_generate_forced: an id of the EOS set may only be the last one (an EOS is appended, never fed)");
+                    REQUIRE(eos[q] != ids[k], who + ": an id of the EOS set may only be the last one (an EOS is appended, never fed)");
         }
-        REQUIRE(rep_penalty == 1.0f, "svln_generate_forced: a repetition penalty != 1 is set (svln_set_repetition_penalty); its flags change row by row");
+        REQUIRE(rep_penalty == 1.0f, who + ": a repetition penalty != 1 is set (svln_set_repetition_penalty); its flags change row by row");
         // a forced row must be computed in the numeric scheme of the step it stands in for (the ride's list)
-        REQUIRE(!single_scheme_on(),
-                "svln_generate_forced: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm, "
-                "svln_set_decode_persistent); switch it off first");
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_generate_forced needs an idle scheduler (turns are in flight)");
+        if (sched)
+            REQUIRE(!spec_exclusive_on(),
+                    who + ": a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm, "
+                          "svln_set_mxfp4_batched, svln_set_decode_persistent); switch it off first");
+        else
+            REQUIRE(!single_scheme_on(),
+                    who + ": a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm, "
+                          "svln_set_decode_persistent); switch it off first");
+        if (!sched)
+            for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, who + " needs an idle scheduler (turns are in flight)");
         if (allow_on)
             for (int k = 0; k < n; ++k)
                 REQUIRE(std::binary_search(allow_ids.begin(), allow_ids.end(), (int)ids[k]),
-                        "svln_generate_forced: id " + std::to_string((long long)ids[k]) + " is not in the allowed list (svln_set_allowed_tokens)");
-        REQUIRE(allow_on || ride_head_rows(n) >= n, "svln_generate_forced: this vocabulary / hidden size has no lm_head form for more than 8 rows");
+                        who + ": id " + std::to_string((long long)ids[k]) + " is not in the allowed list (svln_set_allowed_tokens)");
+        // (a head chunk of the scheduler holds up to 32 rows of several jobs, whatever n is)
+        REQUIRE(allow_on || ride_head_rows(sched ? FORCED_MAX : n) >= (sched ? FORCED_MAX : n), who + ": this vocabulary / hidden size has no lm_head form for more than 8 rows");
     }
     void generate_forced(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs,
                          int32_t* kv_len) override {
@@ -4145,6 +4370,22 @@ int svln_batch_result(svln_engine* h, int slot, int32_t* env, int64_t* out_ids, 
     API_BEGIN_H h->impl->batch_result(slot, env, out_ids, out_cap, n_out); API_END
 }
 int svln_batch_cancel(svln_engine* h, int slot) { API_BEGIN_H h->impl->batch_cancel(slot); API_END }
+int svln_batch_submit_forced(svln_engine* h, int env, const int64_t* ids, int n, const int64_t* eos_ids, int n_eos, int32_t* slot) {
+    API_BEGIN_H
+    REQUIRE((eos_ids || n_eos == 0) && n_eos >= 0, "null argument");
+    if (!slot) h->impl->batch_forced_check(env, ids, n, eos_ids, n_eos);      // a dry run: nothing is queued
+    else *slot = h->impl->batch_submit_forced(env, ids, n, eos_ids, n_eos);
+    API_END
+}
+int svln_batch_forced(svln_engine* h, int slot, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs, int cap, int32_t* n) {
+    API_BEGIN_H
+    REQUIRE(logprobs && greedy_ids && greedy_logprobs && n && cap >= 0, "null output pointer");
+    h->impl->batch_forced(slot, logprobs, greedy_ids, greedy_logprobs, cap, n);
+    API_END
+}
+int svln_batch_forced_stats(svln_engine* h, int64_t* jobs, int64_t* rows_fed, int64_t* head_launches, int reset) {
+    API_BEGIN_H h->impl->batch_forced_stats(jobs, rows_fed, head_launches, reset); API_END
+}
 int svln_set_turn_row_limit(svln_engine* h, int rows) { API_BEGIN_H h->impl->set_turn_row_limit(rows); API_END }
 int svln_set_repetition_penalty(svln_engine* h, float penalty) { API_BEGIN_H h->impl->set_repetition_penalty(penalty); API_END }
 int svln_get_hidden_batch(svln_engine* h, int slot, float* out, int max_rows, int32_t* n_rows) { API_BEGIN_H h->impl->get_hidden_batch(slot, out, max_rows, n_rows); API_END }

@@ -191,6 +191,7 @@ class StreamVLNForCausalLM:
         self.generation_config = SimpleNamespace(eos_token_id=[151645, 151643], repetition_penalty=1.0)
         self._row_limit, self._rep_penalty = 0, 1.0           # what the engine currently holds
         self._tickets: Dict[int, tuple] = {}
+        self._forced_tickets: Dict[int, np.ndarray] = {}           # slot -> forced ids of the tickets that submit_forced issued
         self._auto_draft = False                                   # set_auto_draft: guess that a turn repeats the env's previous one
         self._last_out: Dict[int, torch.Tensor] = {}
         self._token_scores = False                                 # set_token_scores: results carry token_logprobs
@@ -423,6 +424,7 @@ class StreamVLNForCausalLM:
         self._group_pending = {}                                   # (svln_reset_env below drops a pending group and frees its pages)
         _check(self._lib.svln_batch_cancel(self._h, -1))           # turns still in the scheduler belong to the old state
         self._tickets.clear()
+        self._forced_tickets.clear()
         for i in range(self.max_envs):
             _check(self._lib.svln_reset_env(self._h, i))
 
@@ -448,6 +450,7 @@ class StreamVLNForCausalLM:
             _check(self._lib.svln_reset_env(self._h, self._slots[env_idx]))       # (drops the env's scheduler turn, if any)
         for slot in [k for k, v in self._tickets.items() if v[0] == env_idx]:
             del self._tickets[slot]
+            self._forced_tickets.pop(slot, None)
 
     # ---- the call (stream_video_vln.py:353-407) -------------------------------------------------------
     def _parse_call(self, inputs, images, kwargs):
@@ -944,6 +947,191 @@ class StreamVLNForCausalLM:
         self._tickets[slot.value] = (env_id, inputs)
         return SimpleNamespace(env_id=env_id, slot=slot.value)
 
+    def _forced_array(self, forced):
+        f_np = np.ascontiguousarray(torch.as_tensor(forced).reshape(-1).to("cpu", torch.int64).numpy())
+        if not (1 <= int(f_np.size) <= 32):
+            raise ValueError(f"forced_ids holds {int(f_np.size)} ids: a forced turn takes 1 .. 32")
+        return f_np
+
+    def _forced_precheck(self, env_id, f_np, eos):
+        """the refusals of svln_batch_submit_forced that need no state of the env's rows, raised BEFORE a frame is encoded or a row spliced
+        (its dry run: nothing is queued); the two that depend on the spliced length come with the submit itself, as svln_turn_forced's do"""
+        eos_np = np.asarray(eos, dtype=np.int64)
+        _check(self._lib.svln_batch_submit_forced(self._h, self._slot(env_id), f_np.ctypes.data_as(C.POINTER(C.c_int64)), int(f_np.size),
+                                                  eos_np.ctypes.data_as(C.POINTER(C.c_int64)), eos_np.size, None))
+
+    @torch.no_grad()
+    def submit_forced(self, inputs=None, images=None, forced_ids=None, **kwargs):
+        """`submit` for a FORCED turn (see _generate_forced): the turn's ids are forced_ids (1 .. 32).  The job shares the next `step_batch`
+        iteration with whatever the other envs are doing and finishes in it -- one prefill pass that also feeds forced_ids[:-1], no decode
+        iteration.  `max_new_tokens` is not read; `draft_ids` is armed as `submit` arms it and never used.  Nothing changes before a
+        refusal.  Returns a ticket; `step_batch` returns the GenerateOutput `generate(forced_ids=...)` builds."""
+        draft = kwargs.pop("draft_ids", None)
+        if forced_ids is None:
+            raise ValueError("submit_forced needs forced_ids")
+        g = kwargs.get("num_return_sequences")
+        if g is not None and int(g) > 1:
+            raise NotImplementedError(f"num_return_sequences={g!r} in a submit_forced request: a forced turn has one sequence")
+        f_np = self._forced_array(forced_ids)
+        ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
+        if any(v[0] == env_id for v in self._tickets.values()):
+            raise RuntimeError(f"env_id {env_id} already has a turn in flight")
+        if len(self._tickets) >= 8:
+            raise RuntimeError("at most 8 turns in flight: collect finished turns with step_batch first")
+        self._sync_call_config()
+        held = self._sampling
+        self._sync_sampling(kwargs)               # (a flip while other turns are in flight is refused by the engine: nothing has changed yet)
+        try:
+            self._forced_precheck(env_id, f_np, eos)
+        except Exception:
+            # a refused call changes no state: the sampling switch this call flipped goes back to what the engine held
+            if self._sampling != held:
+                self.set_sampling(None) if held is None else self._switch_sampling_on(*held)
+            raise
+        on_dev = int(pix.is_cuda)
+        if on_dev:
+            self._order_engine_after(pix)
+        _check(self._lib.svln_encode_frames(self._h, C.c_void_p(pix.data_ptr()), V, on_dev))
+        if on_dev:
+            self._order_torch_after(pix)
+        self._begin_turn(env_id, past)
+        ids_np = np.ascontiguousarray(ids.numpy())
+        _check(self._lib.svln_append_turn(self._h, self._slot(env_id), ids_np.ctypes.data_as(C.POINTER(C.c_int64)), ids_np.size, n_memory))
+        eos_np = np.asarray(eos, dtype=np.int64)
+        slot = C.c_int32()
+        self._arm_batch_draft(env_id, draft)
+        _check(self._lib.svln_batch_submit_forced(self._h, self._slot(env_id), f_np.ctypes.data_as(C.POINTER(C.c_int64)), int(f_np.size),
+                                                  eos_np.ctypes.data_as(C.POINTER(C.c_int64)), eos_np.size, C.byref(slot)))
+        self._tickets[slot.value] = (env_id, inputs)
+        self._forced_tickets[slot.value] = f_np
+        return SimpleNamespace(env_id=env_id, slot=slot.value, forced=True)
+
+    def _forced_batch_result(self, slot, f_np):
+        """the GenerateOutput of a finished forced job (the keys of _generate_forced); frees the engine slot"""
+        n = int(f_np.size)
+        PF, PI = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+        lp, glp, gid, m = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int64), C.c_int32()
+        _check(self._lib.svln_batch_forced(self._h, slot, lp.ctypes.data_as(PF), gid.ctypes.data_as(PI), glp.ctypes.data_as(PF), n, C.byref(m)))
+        if m.value != n:
+            raise RuntimeError(f"the engine holds {m.value} forced log-probabilities for a forced turn of {n} ids")
+        alp = None
+        if self.allowed_token_ids:
+            n_ids = len(self.allowed_token_ids)
+            abuf, nt, ni = np.empty(n * n_ids, dtype=np.float32), C.c_int32(), C.c_int32()
+            _check(self._lib.svln_batch_allowed_logprobs(self._h, slot, abuf.ctypes.data_as(PF), int(abuf.size), C.byref(nt), C.byref(ni)))
+            if nt.value != n or ni.value != n_ids:
+                raise RuntimeError(f"the engine holds {nt.value} x {ni.value} allowed log-probabilities for a forced turn of {n} ids over {n_ids} allowed ids")
+            alp = torch.from_numpy(abuf.reshape(1, n, n_ids).copy())
+        out, n_out, env = np.zeros(n, dtype=np.int64), C.c_int32(), C.c_int32()
+        _check(self._lib.svln_batch_result(self._h, slot, C.byref(env), out.ctypes.data_as(PI), n, C.byref(n_out)))
+        env_id, inputs = self._tickets.pop(slot)
+        res = self._batch_result(env_id, out[: n_out.value], inputs)
+        dev = res.sequences.device
+        res["token_logprobs"] = torch.from_numpy(lp).unsqueeze(0).to(dev)
+        res["greedy_ids"] = torch.from_numpy(gid).unsqueeze(0).to(dev)
+        res["greedy_logprobs"] = torch.from_numpy(glp).unsqueeze(0).to(dev)
+        if alp is not None:
+            res["allowed_logprobs"] = alp.to(dev)
+            res["allowed_token_ids"] = torch.tensor(self.allowed_token_ids, dtype=torch.int64, device=dev)
+        return SimpleNamespace(env_id=env_id, slot=slot, forced=True), res
+
+    @torch.no_grad()
+    def generate_batch_forced(self, requests, max_new_tokens: int = 10000, eos_token_ids=None):
+        """Several envs' turns executed together, forced and plain mixed: a request (kwargs dict as passed to `generate`, distinct env_id,
+        at most 8) with a `forced_ids` key runs as a forced job (svln_batch_submit_forced), the others as plain ones (svln_batch_submit).
+        The frames of the requests are encoded together, as generate_batch encodes them; then the call is the submits followed by
+        `step_batch` until every turn is done.  Needs an idle scheduler; every refusal that needs no rows of an env comes before a frame is
+        encoded.  `max_new_tokens` / `eos_token_ids` may differ between the plain requests.  Returns a list of GenerateOutput in request
+        order: a forced request's is what generate(forced_ids=...) builds."""
+        if not (1 <= len(requests) <= 8):
+            raise ValueError("1..8 requests per batch")
+        parsed, drafts, forced = [], [], []
+        for r in requests:
+            r = dict(r)
+            f = r.pop("forced_ids", None)
+            g = r.get("num_return_sequences")
+            if g is not None and int(g) > 1:
+                raise NotImplementedError(f"num_return_sequences={g!r} in a generate_batch_forced request: group turns run through generate() only")
+            forced.append(None if f is None else self._forced_array(f))
+            drafts.append(r.pop("draft_ids", None))
+            r.setdefault("max_new_tokens", max_new_tokens)
+            if eos_token_ids is not None:
+                r.setdefault("eos_token_ids", eos_token_ids)
+            parsed.append((r,) + self._parse_call(r.pop("inputs", None), r.pop("images", None), r))
+        if len({p[5] for p in parsed}) != len(parsed):
+            raise ValueError("duplicate env_id in batch")
+        if self._tickets:
+            raise RuntimeError("generate_batch_forced needs an idle scheduler: collect or cancel the submitted turns first")
+        self._sync_call_config()
+        modes = {(bool(p[0].get("do_sample", False)), p[0].get("temperature")) if "do_sample" in p[0] else None for p in parsed}
+        if len(modes) != 1:
+            raise ValueError("do_sample / temperature must be the same for every request of a batch")
+        held = self._sampling
+        self._sync_sampling(parsed[0][0])
+        try:
+            for p, f in zip(parsed, forced):
+                if f is not None:
+                    self._forced_precheck(p[5], f, p[8])
+        except Exception:
+            # a refused call changes no state: the sampling switch this call flipped goes back to what the engine held
+            if self._sampling != held:
+                self.set_sampling(None) if held is None else self._switch_sampling_on(*held)
+            raise
+        # vision: encode the frames of as many requests as fit the frame buffer per call, then splice per env (generate_batch's loop)
+        i = 0
+        while i < len(parsed):
+            j, frames = i, 0
+            while j < len(parsed) and (j == i or frames + parsed[j][3] <= self.max_frames):
+                frames += parsed[j][3]
+                j += 1
+            if frames > self.max_frames:
+                raise ValueError(f"a request has {frames} frames but the engine was built with max_frames={self.max_frames}")
+            pix = torch.cat([p[2] for p in parsed[i:j]], 0).contiguous()
+            on_dev = int(pix.is_cuda)
+            if on_dev:
+                self._order_engine_after(pix)
+            _check(self._lib.svln_encode_frames(self._h, C.c_void_p(pix.data_ptr()), frames, on_dev))
+            if on_dev:
+                self._order_torch_after(pix)
+            base = 0
+            for (_, ids, _, V, n_memory, env_id, past, _, _) in parsed[i:j]:
+                self._begin_turn(env_id, past)
+                ids_np = np.ascontiguousarray(ids.numpy())
+                _check(self._lib.svln_append_turn_at(self._h, self._slot(env_id), ids_np.ctypes.data_as(C.POINTER(C.c_int64)), ids_np.size, base, n_memory))
+                base += V
+            i = j
+        slot_of = {}
+        try:
+            for k, (p, d, f) in enumerate(zip(parsed, drafts, forced)):
+                env_id, max_new = p[5], p[7]
+                self._arm_batch_draft(env_id, d)
+                eos_np = np.asarray(p[8], dtype=np.int64)
+                eos_p, slot = eos_np.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int32()
+                if f is None:
+                    _check(self._lib.svln_batch_submit(self._h, self._slot(env_id), min(max_new, self.cfg.max_positions), eos_p, eos_np.size, C.byref(slot)))
+                else:
+                    _check(self._lib.svln_batch_submit_forced(self._h, self._slot(env_id), f.ctypes.data_as(C.POINTER(C.c_int64)), int(f.size), eos_p,
+                                                              eos_np.size, C.byref(slot)))
+                    self._forced_tickets[slot.value] = f
+                self._tickets[slot.value] = (env_id, requests[k].get("inputs"))
+                slot_of[slot.value] = k
+            res = [None] * len(requests)
+            while any(x is None for x in res):
+                done, _ = self.step_batch()
+                for t, out in done:
+                    res[slot_of[t.slot]] = out
+        except Exception:
+            if self._tickets:
+                self.cancel()
+            raise
+        return res
+
+    def batch_forced_stats(self, reset: bool = False):
+        """counters of the scheduler's forced jobs: jobs finished, rows they fed (n - 1 each), EPI_TARGET head chunks launched"""
+        v = [C.c_int64() for _ in range(3)]
+        _check(self._lib.svln_batch_forced_stats(self._h, *[C.byref(x) for x in v], int(reset)))
+        return {"jobs": v[0].value, "rows_fed": v[1].value, "head_launches": v[2].value}
+
     @torch.no_grad()
     def step_batch(self):
         """One scheduler iteration (one pass over the weights for every turn in flight).  Returns (finished, running): `finished` is
@@ -956,10 +1144,14 @@ class StreamVLNForCausalLM:
             # the engine has dropped the failing turn(s); drop the rest too so that tickets and engine slots cannot disagree
             self._lib.svln_batch_cancel(self._h, -1)
             self._tickets.clear()
+            self._forced_tickets.clear()
             raise
         done = []
         cap = self.cfg.max_positions
         for k in range(nf.value):
+            if fin[k] in self._forced_tickets:
+                done.append(self._forced_batch_result(fin[k], self._forced_tickets.pop(fin[k])))
+                continue
             out = np.zeros(cap, dtype=np.int64)
             n, env = C.c_int32(), C.c_int32()
             scores = None
@@ -993,8 +1185,10 @@ class StreamVLNForCausalLM:
         _check(self._lib.svln_batch_cancel(self._h, slot))
         if ticket is None:
             self._tickets.clear()
+            self._forced_tickets.clear()
         else:
             self._tickets.pop(slot, None)
+            self._forced_tickets.pop(slot, None)
 
     def last_hidden_batch(self, slot: int) -> np.ndarray:
         buf = np.empty((8, self.cfg.hidden), dtype=np.float32)
