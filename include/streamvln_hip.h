@@ -344,6 +344,33 @@ int svln_generate_forced(svln_engine* h, int env, const int64_t* ids, int n, con
  * L + n - 1 > max_positions) come after the splice, as svln_turn's own do. */
 int svln_turn_forced(svln_engine* h, const svln_turn_args* a, const int64_t* ids, int n, float* logprobs, int64_t* greedy_ids,
                      float* greedy_logprobs, int32_t* kv_len);
+/* Opt-in, no reference counterpart: CANDIDATE scoring -- n_seq (2 .. 8) caller-given continuations F_g[0 .. n_g), 1 <= n_g <= 32, of ONE
+ * prompt, scored in one prefill and ceil(max_g (n_g - 1) / r) scoring passes.  ids holds the sequences back to back (sum_g n_g ids), lens
+ * their lengths; logprobs / greedy_ids / greedy_logprobs are laid out like ids and defined per position as by svln_generate_forced.
+ *   prefill   svln_generate's, launch for launch: Tn = L - kv_len rows, nothing appended behind the prompt (L = n_embeds).
+ *   fork      the group turn's: sequence 0 keeps the env's table; sequence g >= 1 with n_g >= 2 gets the env's pages below q0 = L / 64 and
+ *             fresh pages covering positions up to L + n_g - 1; the partly filled page is copied by one launch when L % 64 != 0.
+ *   passes    r = min(32 / (q_heads / kv_heads), 32 / n_seq).  Pass p feeds F_g[p r .. min((p + 1) r, n_g - 1)) of every sequence as the
+ *             row slots [g r, g r + r) at positions L + p r + i through ONE sweep of the batched step's products (the 32-row MFMA tiles
+ *             from 4 rows up, else the batched GEMV at its padded row count) with the batched verify attention (every sequence on its
+ *             own table, RoPE / append / causal mask per row) in place of the decode attention; the last id of a sequence is never
+ *             fed.  Unused row slots are fed id 0: the attention writes nothing for them and nothing reads them afterwards.
+ *   head      the prompt's last row (target F_g[0], once per sequence) and every fed row (target the next id) are normed into rows of their
+ *             own by indexed final norms and go through the EPI_TARGET lm_head in chunks of <= 32 rows + its final kernel, as the forced
+ *             jobs of the scheduler do; under an allowed list the subset product.  With svln_set_sampling on inv_t = 1 / T, no noise is
+ *             evaluated and no draw is consumed.
+ * Afterwards a group is PENDING on the env (svln_group_select and everything a pending group blocks, as after svln_generate_group): its
+ * sequence g has fed n_g - 1 ids, so svln_group_select makes the env go on where a forced turn on F_g would have left it
+ * (kv_len = L + n_g - 1).  svln_group_logprobs returns sequence g's scores, svln_group_dist its rows over the allowed list,
+ * svln_get_hidden_group its first <= 8 tap rows.  An armed draft is consumed, as by a forced turn; the draft switches may be on.
+ * Refused before any launch or state change: everything svln_generate_forced refuses, for every sequence; svln_set_mxfp4_batched on (a
+ * scoring pass runs the batched step and would change its numeric scheme); svln_top_logprobs k > 0; n_seq outside 2 .. 8; a length outside
+ * 1 .. 32; L + max_g n_g - 1 > max_positions; a free pool that cannot hold the env's own missing pages and the forks' tails. */
+int svln_generate_candidates(svln_engine* h, int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos_ids, int n_eos,
+                             float* logprobs, int64_t* greedy_ids, float* greedy_logprobs);
+/* svln_turn's bookkeeping (encode, window / episode resets, splice), then the candidates call, in one crossing (a->max_new_tokens is not read) */
+int svln_turn_candidates(svln_engine* h, const svln_turn_args* a, int n_seq, const int64_t* ids, const int32_t* lens, float* logprobs,
+                         int64_t* greedy_ids, float* greedy_logprobs);
 /* Opt-in, no reference counterpart: forced turns as jobs of the multi-env scheduler.  svln_batch_submit_forced queues a forced turn on the
  * ids F[0 .. n) for an env whose turn has been appended, as svln_batch_submit queues a plain one.  The job is a prefill segment of
  * Tn + n - 1 rows: the iteration that prefills it gathers F[0 .. n - 1) on the device as the rows at positions n_embeds .. n_embeds + n - 2
@@ -803,6 +830,15 @@ int svln_op_attention_decode(svln_engine* h, int B, const void* ctx_qkv, int ld,
  * with the decode op. */
 int svln_op_attention_verify(svln_engine* h, int rows, const void* ctx_qkv, int ld, int ctx_rows, const void* qkv_new, void* out,
                              int o_stride);
+/* TEST-ONLY: the batched verify attention (a scoring pass of svln_generate_candidates) on layer 0 / envs 0 .. n_seq - 1.  Sequence s gets
+ * ctx_len[s] context rows (ctx_qkv + s * ctx_rows * ld), then rows[s] (0 .. rows_max) of its rows_max row slots qkv_new[s * rows_max ..]
+ * are verified at positions ctx_len[s] ...; out [n_seq * rows_max][o_stride] keeps the caller's bytes in every row the launch leaves alone.
+ * share != 0: the fork layout (equal context lengths; sequence s >= 1 runs on env 0's pages below ctx_len / 64 and on env s's own pages
+ * from there on, the partly filled page copied by the fork launch).  Refused before any launch: n_seq outside 1 .. 8,
+ * rows_max * (q_heads / kv_heads) > 32, a row count outside 0 .. rows_max, a position at or past max_positions, a position in a page the
+ * sequence's list (svln_op_set_pages) does not hold. */
+int svln_op_attention_verify_multi(svln_engine* h, int n_seq, int rows_max, const void* ctx_qkv, int ld, int ctx_rows, const int32_t* ctx_len,
+                                   const void* qkv_new, const int32_t* rows, int share, void* out, int o_stride);
 /* one verify-step launch on caller-given host arrays: fed[rows] = the tokens the rows were fed (fed[0] is not read), cand[rows] = their
  * arg-maxes, from `count` emitted tokens, with max_new and eos[n_eos <= 16] as svln_generate takes them.  *new_count, *done, the emitted
  * ids in emitted[0 .. *new_count - count) (the rest of emitted[rows] = -3) and *next_token (the last emitted token; -3 when none). */

@@ -93,6 +93,9 @@ class StreamingAgent:
         self.last_top_logprobs = None
         # the policy's own arg-max at every position of the last FORCED model turn (act(..., forced_ids=...)): [1, n]; None otherwise
         self.last_greedy_ids = None
+        # the joint log-probability of every candidate of the last candidates turn (act(..., candidate_ids=...)): [G]; the index taken
+        self.last_candidate_logprobs = None
+        self.last_candidate_index = None
         self.step_id = 0
         self.last_image = None
         self.model.reset_for_env(self.env_id)
@@ -160,6 +163,36 @@ class StreamingAgent:
             req["forced_ids"] = forced_ids
         return self._consume(self.model.generate(**req))
 
+    def _turn_candidates(self, instruction: str, candidate_ids, select=None, env_id: Optional[int] = None):
+        """the model turn as a candidates call (model.generate(candidate_ids=...)): every candidate is scored against one prefill, the
+        env goes on with candidate `select` (default: the largest joint log-probability) as a forced turn on it would"""
+        req = self._build_request(instruction, env_id)
+        req["candidate_ids"] = candidate_ids
+        req.pop("do_sample", None)              # (no token is drawn; the sampling switch of the model stays as it is)
+        req.pop("temperature", None)
+        out = self.model.generate(**req)
+        joint = out.token_logprobs.sum(1)
+        G = int(joint.numel())
+        index = int(joint.argmax()) if select is None else int(select)
+        if not (0 <= index < G):
+            index_err = ValueError(f"select={select!r}: the call scored {G} candidates")
+            self.model.select_sequence(0, req["env_id"])      # the env must not stay blocked by the pending group
+            raise index_err
+        kv = self.model.select_sequence(index, req["env_id"])
+        n = int(out.sequence_lengths[index])
+        self.last_candidate_logprobs = joint
+        self.last_candidate_index = index
+        one = type(out)(sequences=out.sequences[index:index + 1, :n], past_key_values=kv)
+        one["token_logprobs"] = out.token_logprobs[index:index + 1, :n]
+        one["greedy_ids"] = out.greedy_ids[index:index + 1, :n]
+        one["greedy_logprobs"] = out.greedy_logprobs[index:index + 1, :n]
+        alp = out.get("allowed_logprobs") if isinstance(out, dict) else getattr(out, "allowed_logprobs", None)
+        if alp is not None:
+            one["allowed_logprobs"] = alp[index:index + 1, :n]
+            one["allowed_token_ids"] = out["allowed_token_ids"]
+        one["candidates"] = out
+        return self._consume(one)
+
     # -- split form of act() used by BatchedAgents: observe -> (maybe) request -> finish ----------
     def observe(self, rgb):
         self.time_ids.append(self.step_id)
@@ -186,6 +219,22 @@ class StreamingAgent:
             raise ValueError(f"forced_ids given at step {self.step_id}, but no model turn runs there: {len(self.action_seq)} actions of the last turn are still queued")
         if self.observe(rgb):
             self.action_seq = self._turn(instruction) if forced_ids is None else self._turn(instruction, forced_ids=forced_ids)
+        return self.finish_step()
+
+    def act_candidates(self, rgb: np.ndarray, instruction: str = "", candidate_ids=None, select=None) -> int:
+        """`act` whose model turn scores candidates: the 2 .. 8 id lists of candidate_ids are scored against one prefill
+        (model.generate(candidate_ids=...)) and the env goes on with candidate `select` (default: the largest joint log-probability), as
+        a forced turn on it would.  `last_candidate_logprobs` keeps every candidate's joint log-probability, `last_candidate_index` the
+        one taken, and the `last_*` fields of a forced turn describe it.  Raises, before anything changes, when no model turn runs at
+        this step.  (A method of its own: `act` keeps its argument list.)"""
+        if candidate_ids is None:
+            raise ValueError("act_candidates needs candidate_ids")
+        if len(self.action_seq) != 0:
+            raise ValueError(f"candidate_ids given at step {self.step_id}, but no model turn runs there: {len(self.action_seq)} actions of the last turn are still queued")
+        if select is not None and not (0 <= int(select) < len(candidate_ids)):
+            raise ValueError(f"select={select!r}: {len(candidate_ids)} candidates were given")
+        if self.observe(rgb):
+            self.action_seq = self._turn_candidates(instruction, candidate_ids, select)
         return self.finish_step()
 
     # -- real-world flavour ------------------------------------------------------------

@@ -616,22 +616,22 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs p) {
 // page boundary and so two key splits), and the causal mask is per row (key <= pos0 + i).  A row of an earlier position sees no key of
 // the page a straddling pass opens: there the first key of the tile is NOT valid for it, so a row without a visible key keeps m = -inf,
 // l = 0, O = 0 (no exp2(-inf - -inf)) and still writes that partial -- the workspace may hold anything, and the merge gives it weight 0.
+// The body is shared with attn_verify_multi_kernel (several sequences, one per blockIdx.z): `page_table`, `pos0`, `rows`, the q|k|v rows `Qrows`
+// and the partials `part` are the sequence's own; every operation below is the same for both kernels.
 template <typename T>
-__global__ __launch_bounds__(256) void attn_verify_kernel(AttnArgs p) {
+__device__ __forceinline__ void attn_verify_body(const AttnArgs& p, const int* page_table, const int pos0, const int rows, const T* Qrows,
+                                                 float* part, char* smem) {
     using G = AttnGeom<T, 128>;
     constexpr int EPC = G::EPC, NT = 256;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (p.skip && *p.skip) return;
     char* sK = smem;
     char* sV = smem + G::K_TILE_BYTES;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int kh = blockIdx.x, z = blockIdx.y;
     const int kt0 = z * p.tiles_per_split;
-    const int page0 = p.page_table[kt0];
-    const int pos0 = *p.dyn_pos;
-    const int R = min(*p.dyn_rows, p.T);
+    const int R = min(rows, p.T);
     if (R <= 0) return;
+    const int page0 = page_table[kt0];
     const int kv_len = pos0 + R;
     const int tiles = (kv_len + 63) >> 6;
     if (kt0 >= tiles) return;                                   // the merge only reads splits below ceil(tiles / tiles_per_split)
@@ -644,7 +644,7 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(AttnArgs p) {
     // roped Q fragments of row rho = r (query position qi, q head kh*G + qg), identical in every wave
     uint4 qf[G::HDC / 2];
     {
-        const T* qrow = (const T*)p.Q + (size_t)qi * p.q_stride + (size_t)(kh * p.G + qg) * 128;
+        const T* qrow = Qrows + (size_t)qi * p.q_stride + (size_t)(kh * p.G + qg) * 128;
 #pragma unroll
         for (int s = 0; s < G::HDC / 2; ++s) qf[s] = valid ? *(const uint4*)(qrow + (2 * s + h) * EPC) : zero_chunk();
         const float* tab = p.rope_tab + (size_t)qpos * 128;
@@ -672,7 +672,7 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(AttnArgs p) {
     float m = -INFINITY, l = 0.0f;
 
     for (int kt = kt0; kt < kt_end; ++kt) {
-        const int page = kt == kt0 ? page0 : p.page_table[kt];
+        const int page = kt == kt0 ? page0 : page_table[kt];
         const char* gK = (const char*)p.Kpool + (size_t)page * k_page_stride + (size_t)kh * 64 * 128 * sizeof(T);
         const char* gV = (const char*)p.Vpool + (size_t)page * k_page_stride + (size_t)kh * 128 * 64 * sizeof(T);
         constexpr int KL = 64 * G::HDC / NT, VL = 128 * G::VC / NT;
@@ -703,7 +703,7 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(AttnArgs p) {
                 const int i = w >> 6, d = w & 63, pos = pos0 + i;
                 if ((pos >> 6) != kt) continue;
                 const int off = pos & 63;
-                const T* qkv_row = (const T*)p.Q + (size_t)i * p.q_stride;
+                const T* qkv_row = Qrows + (size_t)i * p.q_stride;
                 const T* krow = qkv_row + (size_t)(p.nq_heads + kh) * 128;
                 const T* vrow = qkv_row + (size_t)(p.nq_heads + p.n_kv_total + kh) * 128;
                 const float* tab = p.rope_tab + (size_t)pos * 128;
@@ -798,11 +798,30 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(AttnArgs p) {
     }
     l += __shfl_xor(l, 32, 64);
     if (!valid) return;
-    float* dst = p.part + (((size_t)z * p.n_kv_total + kh) * p.rows_pad + r) * (128 + ATTN_PART_PAD);
+    float* dst = part + (((size_t)z * p.n_kv_total + kh) * p.rows_pad + r) * (128 + ATTN_PART_PAD);
 #pragma unroll
     for (int e4 = 0; e4 < 4; ++e4)
         *(float4*)(dst + wave * 32 + acc_row(e4 * 4, lane)) = make_float4(O[4 * e4], O[4 * e4 + 1], O[4 * e4 + 2], O[4 * e4 + 3]);
     if (wave == 0 && h == 0) { dst[128] = m; dst[129] = l; }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_verify_kernel(AttnArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (p.skip && *p.skip) return;
+    attn_verify_body<T>(p, p.page_table, *p.dyn_pos, *p.dyn_rows, (const T*)p.Q, p.part, smem);
+}
+// Batched verify attention: gridDim.z sequences (<= 8, the decode partial workspace), sequence s = blockIdx.z on its own page table at its own
+// start position with its own row count (DecodeSlot: page_table, pos, pad = rows, 0 <= rows <= p.T); its q|k|v rows are rows
+// [s * p.T, s * p.T + rows) of Q, its partials start at part + s * part_bstride.  Per sequence the arithmetic is attn_verify_kernel's (one
+// body).  A sequence of 0 rows returns before it reads its table.  Sequences may share every page below the page of their start position
+// (a fork): a pass only writes pool slots of positions >= pos.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_verify_multi_kernel(AttnArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int s = blockIdx.z;
+    const DecodeSlot sl = p.slots[s];
+    attn_verify_body<T>(p, sl.page_table, sl.pos, sl.pad, (const T*)p.Q + (size_t)s * p.T * p.q_stride, p.part + (size_t)s * p.part_bstride, smem);
 }
 
 // merge split-KV partials: one wave per (kh, rho).  Pass 1: lane z owns split z (m_z, l_z) -> wave max / weights;
@@ -810,7 +829,8 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(AttnArgs p) {
 // A wave per row; four rows per workgroup when there are many rows (prefill / ViT: thousands of single-wave workgroups are dispatch-bound),
 // one row per workgroup for the few rows of a decode step (spread over as many CUs as possible: 5.8 us against 9.4 with four per workgroup).
 // VERIFY (attn_verify_kernel's partials): *dyn_rows query positions from *dyn_pos on, so the keys reach *dyn_pos + rows, not GenCtl.kv_len
-template <typename T, int HD, bool VERIFY = false>
+// VERIFY + MULTI (attn_verify_multi_kernel's): sequence env = blockIdx.z, rows / position from its DecodeSlot, output rows env * T + qi
+template <typename T, int HD, bool VERIFY = false, bool MULTI = false>
 __global__ __launch_bounds__(256) void attn_combine_kernel(AttnArgs p) {
     __shared__ float wsh_all[4][64];
     if (p.skip && *p.skip) return;
@@ -818,7 +838,11 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(AttnArgs p) {
     float* wsh = wsh_all[wave];         // written and read by this wave only
     const int rho = blockIdx.x * (blockDim.x >> 6) + wave, kh = blockIdx.y, env = blockIdx.z;
     int kv_len;
-    if constexpr (VERIFY) {
+    if constexpr (VERIFY && MULTI) {
+        const int rows = min(p.slots[env].pad, p.T);
+        if (rho >= rows * p.G) return;
+        kv_len = p.slots[env].pos + rows;
+    } else if constexpr (VERIFY) {
         const int rows = min(*p.dyn_rows, p.T);
         if (rho >= rows * p.G) return;
         kv_len = *p.dyn_pos + rows;
@@ -847,7 +871,7 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(AttnArgs p) {
     const float inv = lsum > 0.0f ? 1.0f / lsum : 0.0f;
     const int qi = rho / p.G, qg = rho - qi * p.G;
     const int frame = kh / p.hpf, head0 = (kh % p.hpf) * p.G;
-    T* orow = (T*)p.O + (size_t)(frame * p.T + qi + env) * p.o_stride + (size_t)(head0 + qg) * HD;     // env > 0 only when T == 1
+    T* orow = (T*)p.O + (size_t)(frame * p.T + qi + (MULTI ? env * p.T : env)) * p.o_stride + (size_t)(head0 + qg) * HD;     // env > 0 only when T == 1 (or MULTI)
     if (lane < HD) orow[lane] = from_f32<T>(o0 * inv);
     if (lane + 64 < HD) orow[lane + 64] = from_f32<T>(o1 * inv);
 }
@@ -913,6 +937,15 @@ template <typename T> void launch_attention_verify(hipStream_t s, const AttnArgs
     hipLaunchKernelGGL((attn_verify_kernel<T>), dim3(a.n_kv_total, a.nsplit), dim3(256), G::K_TILE_BYTES + G::V_TILE_BYTES, s, a);
     hipLaunchKernelGGL((attn_combine_kernel<T, 128, true>), dim3(a.T * a.G, a.n_kv_total), dim3(64), 0, s, a);
 }
+// the verify pass of a.batch sequences (a.slots[s]: page table, start position, pad = row count), a.T = the most rows a sequence may carry
+template <typename T> void launch_attention_verify_multi(hipStream_t s, const AttnArgs& a) {
+    using G = AttnGeom<T, 128>;
+    if (!(a.T >= 1 && a.T * a.G <= 32 && a.slots && a.batch >= 1 && a.batch <= 8 && a.rows_pad >= 32 && a.fuse_rope_append && a.nsplit >= 1 &&
+          a.part_bstride >= (size_t)a.nsplit * a.n_kv_total * a.rows_pad * (128 + ATTN_PART_PAD)))
+        throw std::runtime_error("batched verify attention: 1 <= rows, rows * G <= 32, 1 .. 8 sequences with device slots, a partial stride that holds one sequence's splits");
+    hipLaunchKernelGGL((attn_verify_multi_kernel<T>), dim3(a.n_kv_total, a.nsplit, a.batch), dim3(256), G::K_TILE_BYTES + G::V_TILE_BYTES, s, a);
+    hipLaunchKernelGGL((attn_combine_kernel<T, 128, true, true>), dim3(a.T * a.G, a.n_kv_total, a.batch), dim3(64), 0, s, a);
+}
 template <typename T, int HD, int WAVES> static void attn_attr() {
     using G = AttnGeom<T, HD>;
     set_max_lds((const void*)attn_kernel<T, HD, WAVES>, G::K_TILE_BYTES + G::V_TILE_BYTES);
@@ -920,6 +953,7 @@ template <typename T, int HD, int WAVES> static void attn_attr() {
 void attention_init_attrs() {
     set_max_lds((const void*)attn_decode_kernel<float>, AttnGeom<float, 128>::K_TILE_BYTES + AttnGeom<float, 128>::V_TILE_BYTES);
     set_max_lds((const void*)attn_verify_kernel<float>, AttnGeom<float, 128>::K_TILE_BYTES + AttnGeom<float, 128>::V_TILE_BYTES);
+    set_max_lds((const void*)attn_verify_multi_kernel<float>, AttnGeom<float, 128>::K_TILE_BYTES + AttnGeom<float, 128>::V_TILE_BYTES);
     attn_attr<bf16, 128, 1>(); attn_attr<bf16, 128, 4>(); attn_attr<bf16, 72, 1>(); attn_attr<bf16, 72, 4>();
     attn_attr<float, 128, 1>(); attn_attr<float, 128, 4>(); attn_attr<float, 72, 1>(); attn_attr<float, 72, 4>();
     set_max_lds((const void*)attn_kernel<bf16, 72, 2, VitGroups<bf16>::KG, VitGroups<bf16>::PF>, GroupGeom<bf16, 72, VitGroups<bf16>::KG>::LDS);
@@ -932,6 +966,8 @@ template void launch_attention<bf16>(hipStream_t, const AttnArgs&, int, int);
 template void launch_attention<float>(hipStream_t, const AttnArgs&, int, int);
 template void launch_attention_verify<bf16>(hipStream_t, const AttnArgs&);
 template void launch_attention_verify<float>(hipStream_t, const AttnArgs&);
+template void launch_attention_verify_multi<bf16>(hipStream_t, const AttnArgs&);
+template void launch_attention_verify_multi<float>(hipStream_t, const AttnArgs&);
 template void launch_attention_combine<bf16>(hipStream_t, const AttnArgs&, int);
 template void launch_attention_combine<float>(hipStream_t, const AttnArgs&, int);
 

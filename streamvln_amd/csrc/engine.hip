@@ -133,6 +133,10 @@ struct EngineBase {
                                  float* greedy_logprobs, int32_t* kv_len) = 0;
     virtual void turn_forced(const svln_turn_args& a, const int64_t* ids, int n, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs,
                              int32_t* kv_len) = 0;
+    virtual void generate_candidates(int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos, int n_eos, float* logprobs,
+                                     int64_t* greedy_ids, float* greedy_logprobs) = 0;
+    virtual void turn_candidates(const svln_turn_args& a, int n_seq, const int64_t* ids, const int32_t* lens, float* logprobs, int64_t* greedy_ids,
+                                 float* greedy_logprobs) = 0;
     virtual int batch_submit_forced(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos) = 0;
     virtual void batch_forced_check(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos) = 0;
     virtual void batch_forced(int slot, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs, int cap, int32_t* n) = 0;
@@ -165,6 +169,8 @@ struct EngineBase {
     virtual void set_batch_draft(int on) = 0;
     virtual void batch_draft_stats(int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int64_t* iterations, int64_t* single_rows, int reset) = 0;
     virtual void op_attention_verify(int rows, const void* ctx, int ld, int ctx_rows, const void* qkv_new, void* out, int o_stride) = 0;
+    virtual void op_attention_verify_multi(int S, int T, const void* ctx, int ld, int ctx_rows, const int32_t* ctx_len, const void* qkv_new,
+                                           const int32_t* rows, int share, void* out, int o_stride) = 0;
     virtual void op_verify_step(int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos, int n_eos,
                                 int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token) = 0;
     virtual bool op_gemm_fp8(const GemmArgs& a) = 0;
@@ -670,6 +676,8 @@ public:
         (void)hipHostFree(h_slots); (void)hipHostFree(h_tok_b);
         if (h_head_src) (void)hipHostFree(h_head_src);
         if (bf_host_i) (void)hipHostFree(bf_host_i);
+        if (h_cfeed) (void)hipHostFree(h_cfeed);
+        if (h_cslots) (void)hipHostFree(h_cslots);
         if (bf_host_f) (void)hipHostFree(bf_host_f);
         if (bf_host_alp) (void)hipHostFree(bf_host_alp);
         if (h_draft) (void)hipHostFree(h_draft);
@@ -1295,6 +1303,17 @@ public:
         a.T = rows; a.dyn_rows = d_vctl + 1;
         return a;
     }
+    // a scoring pass of svln_generate_candidates: S sequences of up to `rows` row slots each, d_slots[s] = {table, first position, row count}
+    // kv_max: the most keys any sequence of the pass reaches (known on the host: the pass is not captured) -- the grid covers the key
+    // splits below it only; the partial layout and the merge do not depend on the number of splits launched
+    AttnArgs verify_multi_attn_args(const LLayer& L, int S, int rows, int kv_max, const DecodeSlot* slots = nullptr) {
+        AttnArgs a = batched_decode_attn_args(L, S);
+        a.T = rows;
+        const int tiles = (kv_max + PAGE - 1) / PAGE;
+        a.nsplit = std::max(1, std::min(nsplit_max, (tiles + tiles_per_split - 1) / tiles_per_split));
+        if (slots) a.slots = slots;
+        return a;
+    }
     void decode_attention(const AttnArgs& a) {
         launch_attention<T>(st, a, 128, 1);
         launch_attention_combine<T>(st, a, 128);
@@ -1688,12 +1707,16 @@ public:
     // A pass that uses fewer than B rows (d_vctl[1]) still carries B rows through the products: the unused rows are fed row 0's token,
     // the verify attention writes no output for them, so from o_proj on they hold stale buffer contents -- the products are independent
     // per row and the verify step never reads their arg-maxes.
-    void decode_ops_batched(int B, bool pen = false, const Env* verify = nullptr) {
+    // multi != null (a scoring pass of svln_generate_candidates): the rows are multi->S sequences x multi->rows row slots, fed the ids
+    // multi->tok; the attention is the batched verify attention on multi->slots; the sweep ends before the head (the caller norms the
+    // rows it keeps).
+    struct MultiPass { const int* tok; const DecodeSlot* slots; int S; int rows; int kv_max; };
+    void decode_ops_batched(int B, bool pen = false, const Env* verify = nullptr, const MultiPass* multi = nullptr) {
         if (mx4b_on) { decode_ops_batched_mx4(B, pen); return; }
         const int qd = nq * 128;
         const bool mfma = B >= batched_mfma_min;
         if (verify) launch_gather_rows<T>(st, d_vctl + 8, embed, feats, x, B, H, &d_ctl->done);
-        else launch_gather_rows<T>(st, d_tok_b, embed, feats, x, B, H);
+        else launch_gather_rows<T>(st, multi ? multi->tok : d_tok_b, embed, feats, x, B, H);
         bool xn_ready = false;
         for (int i = 0; i < c.layers; ++i) {
             const LLayer& L = ll[i];
@@ -1702,6 +1725,7 @@ public:
             if (mfma) llm_gemm(gemm_args(xn, H, L.qkv_w, H, qkv, qkv_dim, L.qkv_b, nullptr, 0, 0, B, qkv_dim, H, EPI_NONE), L.qkv8);
             else launch_gemv_batched<T>(st, gemvb_args(L.qkv_w, H, xn, H, nullptr, L.qkv_b, nullptr, 0, qkv, qkv_dim, qkv_dim, H, EPI_NONE, B));
             if (verify) launch_attention_verify<T>(st, verify_attn_args(L, *verify, B));
+            else if (multi) launch_attention_verify_multi<T>(st, verify_multi_attn_args(L, multi->S, multi->rows, multi->kv_max, multi->slots));
             else decode_attention(batched_decode_attn_args(L, B));
             if (mfma) {
                 GemmArgs ao = gemm_args(attn, qd, L.o_w, qd, x, H, nullptr, x, H, 0, B, H, qd, EPI_NONE);
@@ -1718,6 +1742,7 @@ public:
                 launch_gemv_batched<T>(st, gemvb_args(L.down_w, I, hbuf, I, nullptr, nullptr, x, H, x, H, H, I, EPI_NONE, B));
             }
         }
+        if (multi) return;
         head_batched(x, B, pen);
     }
     // One verify pass of env e, enqueued only (GenCtl, the fed token and the draft live in device memory, so the pass is one fixed launch
@@ -2299,8 +2324,7 @@ public:
     int head_forced(const std::vector<Seg>& segs, const std::vector<int>& pre_now) {
         constexpr int R = BFORCED_ROWS + 8;
         int *h_src = bf_host_i, *h_tap = bf_host_i + R, *h_tgt = bf_host_i + 2 * R;
-        int *d_src = bf_dev_i, *d_tap = bf_dev_i + R, *d_tgt = bf_dev_i + 2 * R, *d_tok = bf_dev_i + 3 * R;
-        float *d_val = bf_dev_f, *d_score = bf_dev_f + R, *d_lp = bf_dev_f + 2 * R;
+        int *d_src = bf_dev_i, *d_tap = bf_dev_i + R, *d_tgt = bf_dev_i + 2 * R;
         int nf = 0;
         for (size_t q = 0; q < segs.size(); ++q) {
             const Job& j = jobs[pre_now[q]];
@@ -2322,6 +2346,15 @@ public:
         HIP_CHECK(hipMemcpyAsync(d_tap, h_tap, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipMemcpyAsync(d_tgt, h_tgt, (size_t)(nf + 8) * sizeof(int), hipMemcpyHostToDevice, st));
         launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn, d_src, d_tap, hid_tap, nf, H, c.rms_eps);
+        head_target_chunks(nf);
+        return nf;
+    }
+    // rows [0, nf) of bf_xn (targets bf_dev_i + 2 R) through the EPI_TARGET head in chunks of <= 32 rows; the results are copied to the
+    // pinned lists (the caller synchronises).  Shared by the forced jobs of an iteration and by svln_generate_candidates.
+    void head_target_chunks(int nf) {
+        constexpr int R = BFORCED_ROWS + 8;
+        int *d_tgt = bf_dev_i + 2 * R, *d_tok = bf_dev_i + 3 * R;
+        float *d_val = bf_dev_f, *d_score = bf_dev_f + R, *d_lp = bf_dev_f + 2 * R;
         const float inv_t = smp_on ? smp_inv_t : 1.0f;
         for (int r0 = 0; r0 < nf; r0 += 32) {
             const int r = std::min(nf - r0, 32);
@@ -2342,7 +2375,6 @@ public:
         HIP_CHECK(hipMemcpyAsync(bf_host_f + R, d_score, (size_t)nf * sizeof(float), hipMemcpyDeviceToHost, st));
         if (allow_on) HIP_CHECK(hipMemcpyAsync(bf_host_alp, bf_dev_alp, (size_t)nf * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
         else HIP_CHECK(hipMemcpyAsync(bf_host_f + 2 * R, d_lp, (size_t)nf * sizeof(float), hipMemcpyDeviceToHost, st));
-        return nf;
     }
     // one iteration; returns the number of jobs still running afterwards, finished_slots = jobs that completed in this iteration
     int batch_step(int32_t* finished_slots, int32_t* n_finished) override {
@@ -3066,6 +3098,198 @@ public:
         }
         generate_group(a.env, n_seq, a.max_new_tokens, a.eos_ids, a.n_eos, out, cap, n_out);
     }
+    // ------------------------------------------------------------------------------- candidate scoring (svln_generate_candidates)
+    // n_seq caller-given continuations of ONE prompt: the prompt is prefilled once (svln_generate's prefill), forked as a group turn forks
+    // it, and the fed ids of all sequences go through the batched step's products in passes of n_seq x r row slots with the batched verify
+    // attention; the head rows (the prompt's last row once per sequence, every fed row) are normed into bf_xn and scored by the
+    // EPI_TARGET head of the scheduler's forced jobs.  The result is a pending group whose sequence g has fed n_g - 1 ids.
+    static constexpr int CAND_PASSES = BFORCED_MAX - 1, CAND_FEED = CAND_PASSES * 32;
+    int *d_cfeed = nullptr, *h_cfeed = nullptr;                   // fed ids of every pass: [pass][B]
+    DecodeSlot *d_cslots = nullptr, *h_cslots = nullptr;          // slots of every pass: [pass][MAXB]
+    void ensure_cand_buffers() {
+        if (d_cfeed) return;
+        d_cfeed = dalloc<int>(CAND_FEED, true); d_cslots = dalloc<DecodeSlot>((size_t)CAND_PASSES * MAXB, true);
+        HIP_CHECK(hipHostMalloc((void**)&h_cfeed, CAND_FEED * sizeof(int)));
+        HIP_CHECK(hipHostMalloc((void**)&h_cslots, (size_t)CAND_PASSES * MAXB * sizeof(DecodeSlot)));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    // rows of a sequence per scoring pass
+    int cand_rows_per_pass(int n_seq) const { return std::min(32 / (nq / nkv), 32 / n_seq); }
+    // every refusal that needs no state of the env's rows (svln_turn_candidates checks them before it encodes a frame)
+    void cand_refusals(int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos, int n_eos) {
+        const char* who = "svln_generate_candidates";
+        env_at(env);
+        REQUIRE(n_seq >= 2 && n_seq <= MAXB, std::string(who) + ": n_seq must be 2 .. 8");
+        REQUIRE(ids && lens, std::string(who) + ": null id list / lengths");
+        for (int g = 0; g < n_seq; ++g) REQUIRE(lens[g] >= 1 && lens[g] <= FORCED_MAX, std::string(who) + ": a sequence length (lens) must be 1 .. 32");
+        refuse_while_topk(who);
+        REQUIRE(!mx4b_on, std::string(who) + ": the batched MXFP4 weights are on (svln_set_mxfp4_batched): a scoring pass runs the batched step; switch them off first");
+        REQUIRE(!grp.pending, std::string(who) + ": a group turn is pending on env " + std::to_string(grp.env) + "; choose its continuation with svln_group_select first");
+        int off = 0;
+        for (int g = 0; g < n_seq; ++g) { forced_refusals(env, ids + off, lens[g], eos, n_eos, who); off += lens[g]; }
+    }
+    void generate_candidates(int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos, int n_eos, float* logprobs,
+                             int64_t* greedy_ids, float* greedy_logprobs) override {
+        Env& e = env_at(env);
+        disarm_draft(env);              // consumed by this call, as svln_generate_forced consumes it
+        REQUIRE(logprobs && greedy_ids && greedy_logprobs, "svln_generate_candidates: null output pointer");
+        cand_refusals(env, n_seq, ids, lens, eos, n_eos);
+        REQUIRE(weights_missing() == 0, g_err);
+        const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
+        REQUIRE(Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
+        int n_max = 0, nf = 0, off[MAXB + 1] = {0};
+        for (int g = 0; g < n_seq; ++g) { n_max = std::max(n_max, (int)lens[g]); off[g + 1] = off[g] + lens[g]; }
+        nf = off[n_seq];
+        REQUIRE((int64_t)L + n_max - 1 <= c.max_positions, "svln_generate_candidates: n_embeds + max(lens) - 1 exceeds max_positions");
+        const int q0 = L / PAGE;
+        int tail_n[MAXB] = {0};
+        int64_t need = std::max((L + lens[0] - 1 + PAGE - 1) / PAGE - e.n_pages, 0);
+        for (int g = 1; g < n_seq; ++g) { tail_n[g] = lens[g] == 1 ? 0 : (L + lens[g] - 1 + PAGE - 1) / PAGE - q0; need += tail_n[g]; }
+        REQUIRE((int64_t)free_pages.size() >= need,
+                "svln_generate_candidates: the free KV pages cannot hold the env's own pages and the tail pages of the fork");
+        const int r = cand_rows_per_pass(n_seq);
+        const int passes = (n_max - 1 + r - 1) / r;
+        const int Bu = n_seq * r, B = Bu >= batched_mfma_min ? Bu : (Bu <= 2 ? 2 : 4);
+        REQUIRE(passes <= CAND_PASSES && passes * B <= CAND_FEED && nf <= BFORCED_ROWS && B <= c.max_positions, "svln_generate_candidates: workspace");
+        ensure_bforced_buffers();
+        ensure_cand_buffers();
+        // ---- nothing was launched or changed up to here (but the armed draft)
+        last_scores_valid = false; last_alp_valid = false; last_topk_valid = false;
+        for (int g = 1; g < n_seq; ++g)
+            if (!fork_tab[g]) { fork_tab[g] = dalloc<int>(pages_per_env, true); fork_host[g].assign(pages_per_env, 0); }
+        grp = Group();
+        grp.env = env; grp.n_seq = n_seq; grp.L = L; grp.q0 = q0; grp.scored = true; grp.alp_n = allow_on ? allow_n : 0;
+        for (int g = 1; g < n_seq; ++g) grp.n_tail = std::max(grp.n_tail, tail_n[g]);
+        constexpr int R = BFORCED_ROWS + 8;
+        // head row lists.  Block 0: the prompt's last row once per sequence (target F_g[0]); block p + 1: the rows pass p fed, sequence by
+        // sequence (row slot g r + j fed F_g[p r + j], target F_g[p r + j + 1]).  hrow[off[g] + i] = the head row that scores F_g[i].
+        int *h_src = bf_host_i, *h_tap = bf_host_i + R, *h_tgt = bf_host_i + 2 * R;
+        int *d_src = bf_dev_i, *d_tap = bf_dev_i + R, *d_tgt = bf_dev_i + 2 * R;
+        std::vector<int> hrow(nf), base(passes + 2, 0);
+        HIP_CHECK(hipStreamSynchronize(st));       // (the pinned lists of an earlier call are no longer being read)
+        int k = 0;
+        for (int g = 0; g < n_seq; ++g) { h_src[k] = Tn - 1; h_tap[k] = taps_on ? g : -1; h_tgt[k] = (int)ids[off[g]]; hrow[off[g]] = k; ++k; }
+        base[1] = k;
+        for (int p = 0; p < passes; ++p) {
+            for (int q = 0; q < B; ++q) h_cfeed[p * B + q] = 0;
+            for (int g = 0; g < n_seq; ++g) {
+                const int lo = p * r, hi = std::min((p + 1) * r, (int)lens[g] - 1), cnt = std::max(hi - lo, 0);
+                DecodeSlot& sl = h_cslots[p * MAXB + g];
+                sl.page_table = g == 0 ? e.d_pages : fork_tab[g]; sl.pos = L + lo; sl.pad = cnt;
+                for (int j = 0; j < cnt; ++j) {
+                    const int i = lo + j + 1;       // the position of the turn this row scores
+                    h_cfeed[p * B + g * r + j] = (int)ids[off[g] + lo + j];
+                    h_src[k] = g * r + j;
+                    // tap row min(i, 7); of the rows of one launch that share tap row 7 only the last is written (later passes overwrite it)
+                    h_tap[k] = taps_on && (i < 7 || j == cnt - 1) ? (i < 7 ? i : 7) * MAXB + g : -1;
+                    h_tgt[k] = (int)ids[off[g] + i];
+                    hrow[off[g] + i] = k;
+                    ++k;
+                }
+            }
+            base[p + 2] = k;
+        }
+        REQUIRE(k == nf, "svln_generate_candidates: head row count");
+        for (int q = nf; q < nf + 8; ++q) h_tgt[q] = -1;
+        try {
+            HIP_CHECK(hipMemcpyAsync(d_src, h_src, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(d_tap, h_tap, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(d_tgt, h_tgt, (size_t)(nf + 8) * sizeof(int), hipMemcpyHostToDevice, st));
+            if (passes > 0) {
+                HIP_CHECK(hipMemcpyAsync(d_cfeed, h_cfeed, (size_t)passes * B * sizeof(int), hipMemcpyHostToDevice, st));
+                HIP_CHECK(hipMemcpyAsync(d_cslots, h_cslots, (size_t)passes * MAXB * sizeof(DecodeSlot), hipMemcpyHostToDevice, st));
+            }
+            // prefill: svln_generate's, launch for launch
+            ensure_pages(e, L);
+            HIP_CHECK(hipEventRecord(ph_ev[2], st));
+            prefill(e, P, Tn);
+            e.kv_len = L;
+            launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn, d_src, d_tap, hid_tap, n_seq, H, c.rms_eps);
+            HIP_CHECK(hipEventRecord(ph_ev[3], st));
+            // fork: the env's own tail pages, then per sequence g >= 1 a table = the env's pages below q0 + private pages from q0 on
+            ensure_pages(e, L + lens[0] - 1);
+            int n_dst = 0;
+            for (int g = 1; g < n_seq; ++g) {
+                if (tail_n[g] == 0) continue;
+                std::vector<int>& tab = fork_host[g];
+                for (int i = 0; i < q0; ++i) tab[i] = e.pages[i];
+                for (int i = 0; i < tail_n[g]; ++i) {
+                    REQUIRE(!free_pages.empty(), "KV page pool exhausted");
+                    grp.tail[g].push_back(free_pages.back());
+                    free_pages.pop_back();
+                    tab[q0 + i] = grp.tail[g][i];
+                }
+                HIP_CHECK(hipMemcpyAsync(fork_tab[g], tab.data(), (size_t)(q0 + tail_n[g]) * sizeof(int), hipMemcpyHostToDevice, st));
+                h_fork_dst[n_dst++] = grp.tail[g][0];
+            }
+            if (L % PAGE != 0 && n_dst > 0) {       // the partly filled page: one launch for every layer, both pools, all forks
+                HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)n_dst * sizeof(int), hipMemcpyHostToDevice, st));
+                launch_kv_page_copy<T>(st, d_pool_tab, 2 * c.layers, e.pages[q0], d_fork_dst, n_dst, (int64_t)nkv * PAGE * 128);
+            }
+            // scoring passes: one sweep of the batched step's products each, then the final norm of the rows it fed
+            for (int p = 0; p < passes; ++p) {
+                const MultiPass mp{d_cfeed + p * B, d_cslots + (size_t)p * MAXB, n_seq, r, std::min(L + (p + 1) * r, L + n_max - 1)};
+                decode_ops_batched(B, false, nullptr, &mp);
+                const int cnt = base[p + 2] - base[p + 1];
+                launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn + (size_t)base[p + 1] * H, d_src + base[p + 1], d_tap + base[p + 1], hid_tap, cnt, H, c.rms_eps);
+            }
+            head_target_chunks(nf);
+            HIP_CHECK(hipEventRecord(ph_ev[4], st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            LAUNCH_CHECK("generate_candidates");
+            const int* h_tok = bf_host_i + 3 * R;
+            const float *h_score = bf_host_f + R, *h_lp = bf_host_f + 2 * R;
+            for (int q = 0; q < nf; ++q)
+                REQUIRE(h_tok[q] >= 0 && h_tok[q] < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+            for (int g = 0; g < n_seq; ++g) {
+                for (int i = 0; i < lens[g]; ++i) {
+                    const int q = hrow[off[g] + i], o = off[g] + i;
+                    greedy_ids[o] = h_tok[q]; greedy_logprobs[o] = h_score[q];
+                    if (allow_on) {
+                        const int pos = (int)(std::lower_bound(allow_ids.begin(), allow_ids.end(), (int)ids[o]) - allow_ids.begin());
+                        logprobs[o] = bf_host_alp[(size_t)q * allow_n + pos];
+                        grp.alp[g].insert(grp.alp[g].end(), bf_host_alp + (size_t)q * allow_n, bf_host_alp + (size_t)(q + 1) * allow_n);
+                    } else {
+                        logprobs[o] = h_lp[q];
+                    }
+                    grp.scores[g].push_back(logprobs[o]);
+                }
+                grp.n_out[g] = lens[g];
+            }
+        } catch (...) {
+            // every fork page goes back to the pool, no group is pending; the env is as after a failed svln_generate
+            (void)hipStreamSynchronize(st);
+            drop_group();
+            throw;
+        }
+        {
+            float t = 0.f;
+            HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[3])); ph_ms[1] += t;
+            HIP_CHECK(hipEventElapsedTime(&t, ph_ev[3], ph_ev[4])); ph_ms[2] += t;
+            if (vision_pending) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
+        }
+        e.kv_len = L;                     // until svln_group_select
+        n_generated = 0;                  // (the single-env tap rows were overwritten)
+        top2_stale = true;
+        top2_sampled = false;
+        grp.pending = true;
+    }
+    void turn_candidates(const svln_turn_args& a, int n_seq, const int64_t* ids, const int32_t* lens, float* logprobs, int64_t* greedy_ids,
+                         float* greedy_logprobs) override {
+        env_at(a.env);
+        try {
+            REQUIRE(a.ids && a.n_ids >= 1 && logprobs && greedy_ids && greedy_logprobs, "svln_turn_candidates: null / empty argument");
+            cand_refusals(a.env, n_seq, ids, lens, a.eos_ids, a.n_eos);
+            encode_frames(a.pixels, a.n_frames, a.pixels_on_device);
+            if (a.new_window) kv_reset(a.env);
+            if (a.new_episode && envs[a.env].n_embeds != 0) reset_env(a.env);
+            append_turn(a.env, a.ids, a.n_ids, 0, a.n_memory);
+        } catch (...) {
+            disarm_draft(a.env);
+            throw;
+        }
+        generate_candidates(a.env, n_seq, ids, lens, a.eos_ids, a.n_eos, logprobs, greedy_ids, greedy_logprobs);
+    }
     // ------------------------------------------------------------------------------- forced turns (svln_generate_forced)
     // A turn on the CALLER's ids F[0 .. n): ids F[0 .. n - 1) ride the prefill pass as n - 1 more rows (the ride's gather, RoPE, KV append
     // and causal attention), the final norm of the last n rows goes to xn and the tap rows, ONE lm_head product in its EPI_TARGET form
@@ -3303,10 +3527,19 @@ public:
         REQUIRE(grp.pending && grp.env == env, "svln_group_select: no group turn is pending on this env");
         REQUIRE(index >= 0 && index < grp.n_seq, "svln_group_select: index outside the group's sequences");
         Env& e = envs[env];
-        if (index >= 1 && grp.n_tail > 0) {
+        if (index >= 1 && !grp.tail[index].empty()) {
             // the env goes on with sequence `index`: its private tail becomes the env's, the env's former tail is freed with the other forks'
-            for (int i = 0; i < grp.n_tail; ++i) std::swap(e.pages[grp.q0 + i], grp.tail[index][i]);
-            HIP_CHECK(hipMemcpyAsync(e.d_pages + grp.q0, e.pages.data() + grp.q0, (size_t)grp.n_tail * sizeof(int), hipMemcpyHostToDevice, st));
+            // (a group turn's tails all have n_tail pages, as has the env; the candidates of svln_generate_candidates are ragged: a page the
+            // env does not hold yet is handed over)
+            std::vector<int>& tl = grp.tail[index];
+            const int nt = (int)tl.size();
+            std::vector<int> back;
+            for (int i = 0; i < nt; ++i) {
+                if (grp.q0 + i < e.n_pages) { back.push_back(e.pages[grp.q0 + i]); e.pages[grp.q0 + i] = tl[i]; }
+                else e.pages[e.n_pages++] = tl[i];
+            }
+            tl = back;
+            HIP_CHECK(hipMemcpyAsync(e.d_pages + grp.q0, e.pages.data() + grp.q0, (size_t)nt * sizeof(int), hipMemcpyHostToDevice, st));
         }
         drop_group();
         e.kv_len = grp.L + grp.n_out[index] - 1;
@@ -4206,6 +4439,72 @@ public:
         sync();
         LAUNCH_CHECK("op_attention_verify");
     }
+    // the batched verify attention (verify_multi_attn_args + launch_attention_verify_multi, as a scoring pass of svln_generate_candidates
+    // runs it) on layer 0 / envs 0 .. S - 1.  Sequence s: ctx_len[s] context rows (ctx + s * ctx_rows * ld; roped + appended like
+    // op_attention_llm), then rows[s] (0 .. T) of its T un-roped q|k|v row slots qkv_new[s * T ..] verified at positions ctx_len[s] ...
+    // share != 0: the fork layout -- every ctx_len equals ctx_len[0], only env 0 gets the context, and sequence s >= 1 runs on a table of
+    // env 0's pages below q0 = ctx_len / 64 followed by env s's own pages from q0 on (the partly filled page copied by the fork launch);
+    // env s's pages below q0 stay unused.  Every refusal comes before the first launch.
+    void op_attention_verify_multi(int S, int Tm, const void* ctx, int ld, int ctx_rows, const int32_t* ctx_len, const void* qkv_new,
+                                   const int32_t* rows, int share, void* out, int o_stride) override {
+        REQUIRE(S >= 1 && S <= MAXB, "svln_op_attention_verify_multi: 1 .. 8 sequences");
+        REQUIRE(S <= c.max_envs, "svln_op_attention_verify_multi: more sequences than max_envs");
+        REQUIRE(Tm >= 1 && Tm * (nq / nkv) <= 32, "svln_op_attention_verify_multi: T * (q_heads / kv_heads) must be 1 .. 32");
+        REQUIRE(ctx_len && rows && qkv_new && out, "null pointer");
+        REQUIRE(S * Tm <= c.max_positions, "svln_op_attention_verify_multi: more row slots than the row buffers hold");
+        REQUIRE(ld >= qkv_dim && o_stride >= nq * 128, "row strides");
+        int q0 = 0;
+        for (int s = 0; s < S; ++s) {
+            REQUIRE(rows[s] >= 0 && rows[s] <= Tm, "svln_op_attention_verify_multi: a row count outside 0 .. T");
+            REQUIRE(ctx_len[s] >= 0 && ctx_len[s] <= ctx_rows && (int64_t)ctx_len[s] + rows[s] <= c.max_positions,
+                    "svln_op_attention_verify_multi: a position at or past max_positions (or more context than context rows)");
+            REQUIRE(ctx_len[s] == 0 || ctx, "null context rows");
+            REQUIRE(!share || ctx_len[s] == ctx_len[0], "svln_op_attention_verify_multi: shared context needs equal context lengths");
+            // a page the sequence does not hold: the caller's page list (svln_op_set_pages) must cover every position the pass touches
+            const int need = (ctx_len[s] + rows[s] + PAGE - 1) / PAGE;
+            if (s < (int)op_pages.size() && !op_pages[s].empty())
+                REQUIRE(need <= (int)op_pages[s].size(), "svln_op_attention_verify_multi: a sequence's position lies in a page it does not hold");
+        }
+        if (share) q0 = ctx_len[0] / PAGE;
+        set_speculative_buffers();
+        const LLayer& L = ll[0];
+        for (int s = 0; s < S; ++s) reset_env(s);
+        for (int s = 0; s < S; ++s) {
+            Env& e = env_at(s);
+            op_env_begin(s, ctx_len[s] + rows[s]);
+            if (ctx_len[s] > 0 && (!share || s == 0))
+                op_rope_append(e, L, (char*)const_cast<void*>(ctx) + (size_t)s * ctx_rows * ld * sizeof(T), ld, ctx_len[s], 0);
+        }
+        int n_dst = 0;
+        for (int s = 0; s < S; ++s) {
+            h_slots[s].pos = ctx_len[s]; h_slots[s].pad = rows[s];
+            if (!share || s == 0) { h_slots[s].page_table = envs[s].d_pages; continue; }
+            if (!fork_tab[s]) { fork_tab[s] = dalloc<int>(pages_per_env, true); fork_host[s].assign(pages_per_env, 0); }
+            std::vector<int>& tab = fork_host[s];
+            for (int i = 0; i < q0; ++i) tab[i] = envs[0].pages[i];
+            for (int i = q0; i < envs[s].n_pages; ++i) tab[i] = envs[s].pages[i];
+            HIP_CHECK(hipMemcpyAsync(fork_tab[s], tab.data(), (size_t)pages_per_env * sizeof(int), hipMemcpyHostToDevice, st));
+            h_slots[s].page_table = fork_tab[s];
+            if (ctx_len[0] % PAGE != 0 && envs[s].n_pages > q0) h_fork_dst[n_dst++] = envs[s].pages[q0];
+        }
+        if (n_dst > 0) {
+            HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)n_dst * sizeof(int), hipMemcpyHostToDevice, st));
+            launch_kv_page_copy<T>(st, d_pool_tab, 2 * c.layers, envs[0].pages[q0], d_fork_dst, n_dst, (int64_t)nkv * PAGE * 128);
+        }
+        HIP_CHECK(hipMemcpyAsync(d_slots, h_slots, S * sizeof(DecodeSlot), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpy2DAsync(qkv, (size_t)qkv_dim * sizeof(T), qkv_new, (size_t)ld * sizeof(T), (size_t)qkv_dim * sizeof(T), (size_t)S * Tm,
+                                   hipMemcpyDeviceToDevice, st));
+        // the output rows the launch leaves alone keep the caller's bytes: attn := out first
+        HIP_CHECK(hipMemcpy2DAsync(attn, (size_t)nq * 128 * sizeof(T), out, (size_t)o_stride * sizeof(T), (size_t)nq * 128 * sizeof(T), (size_t)S * Tm,
+                                   hipMemcpyDeviceToDevice, st));
+        int kv_max = 1;
+        for (int s = 0; s < S; ++s) kv_max = std::max(kv_max, (int)(ctx_len[s] + rows[s]));
+        launch_attention_verify_multi<T>(st, verify_multi_attn_args(L, S, Tm, kv_max));
+        HIP_CHECK(hipMemcpy2DAsync(out, (size_t)o_stride * sizeof(T), attn, (size_t)nq * 128 * sizeof(T), (size_t)nq * 128 * sizeof(T), (size_t)S * Tm,
+                                   hipMemcpyDeviceToDevice, st));
+        sync();
+        LAUNCH_CHECK("op_attention_verify_multi");
+    }
     // one verify-step launch on caller-given row tokens and arg-maxes, from `count` emitted tokens (host arrays)
     void op_verify_step(int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos, int n_eos,
                         int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token) override {
@@ -4548,6 +4847,14 @@ int svln_generate_forced(svln_engine* h, int env, const int64_t* ids, int n, con
                          float* greedy_logprobs, int32_t* kv_len) {
     API_BEGIN_H h->impl->generate_forced(env, ids, n, eos_ids, n_eos, logprobs, greedy_ids, greedy_logprobs, kv_len); API_END
 }
+int svln_generate_candidates(svln_engine* h, int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos_ids, int n_eos,
+                             float* logprobs, int64_t* greedy_ids, float* greedy_logprobs) {
+    API_BEGIN_H h->impl->generate_candidates(env, n_seq, ids, lens, eos_ids, n_eos, logprobs, greedy_ids, greedy_logprobs); API_END
+}
+int svln_turn_candidates(svln_engine* h, const svln_turn_args* a, int n_seq, const int64_t* ids, const int32_t* lens, float* logprobs,
+                         int64_t* greedy_ids, float* greedy_logprobs) {
+    API_BEGIN_H REQUIRE(a, "null turn args"); h->impl->turn_candidates(*a, n_seq, ids, lens, logprobs, greedy_ids, greedy_logprobs); API_END
+}
 int svln_turn_forced(svln_engine* h, const svln_turn_args* a, const int64_t* ids, int n, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs,
                      int32_t* kv_len) {
     API_BEGIN_H REQUIRE(a, "null argument"); h->impl->turn_forced(*a, ids, n, logprobs, greedy_ids, greedy_logprobs, kv_len); API_END
@@ -4818,6 +5125,9 @@ int svln_op_attention_decode(svln_engine* h, int B, const void* ctx_qkv, int ld,
 }
 int svln_op_attention_verify(svln_engine* h, int rows, const void* ctx_qkv, int ld, int ctx_rows, const void* qkv_new, void* out, int o_stride) {
     API_BEGIN_H h->impl->op_attention_verify(rows, ctx_qkv, ld, ctx_rows, qkv_new, out, o_stride); API_END
+}
+int svln_op_attention_verify_multi(svln_engine* h, int n_seq, int rows_max, const void* ctx_qkv, int ld, int ctx_rows, const int32_t* ctx_len, const void* qkv_new, const int32_t* rows, int share, void* out, int o_stride) {
+    API_BEGIN_H h->impl->op_attention_verify_multi(n_seq, rows_max, ctx_qkv, ld, ctx_rows, ctx_len, qkv_new, rows, share, out, o_stride); API_END
 }
 int svln_op_verify_step(svln_engine* h, int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos, int n_eos,
                         int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token) {

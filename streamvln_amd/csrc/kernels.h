@@ -321,6 +321,9 @@ template <typename T> void launch_attention(hipStream_t s, const AttnArgs& a, in
 // [T][q_stride]; RoPE at each row's own position, K / V^T append of every row, per-row causal mask, decode split-KV partials + merge
 // -> O [T][o_stride].  T * G <= 32; a no-op when *skip != 0 or *dyn_rows <= 0.  The caller owns the pages of every position written.
 template <typename T> void launch_attention_verify(hipStream_t s, const AttnArgs& a);
+// the same for a.batch <= 8 sequences at once: a.slots[s] = {page table, start position, pad = rows of the sequence (0 .. a.T)}, its q|k|v /
+// output rows [s * a.T, (s + 1) * a.T), its partials at a.part + s * a.part_bstride; per sequence bit for bit launch_attention_verify
+template <typename T> void launch_attention_verify_multi(hipStream_t s, const AttnArgs& a);
 template <typename T> void launch_attention_combine(hipStream_t s, const AttnArgs& a, int head_dim);
 template <typename T> int attn_key_groups(int head_dim);       // the key-group count launch_attention<T> is built for at this head dim (AttnArgs::key_groups)
 

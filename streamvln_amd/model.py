@@ -583,7 +583,7 @@ class StreamVLNForCausalLM:
 
     @torch.no_grad()
     def generate(self, inputs=None, images=None, image_sizes=None, depths=None, poses=None, intrinsics=None, task_ids=None,
-                 draft_ids=None, forced_ids=None, **kwargs):
+                 draft_ids=None, forced_ids=None, candidate_ids=None, **kwargs):
         """One model turn = ONE crossing into the engine (svln_turn: encode_rgbd, the KV / embeds bookkeeping of the reference's generate,
         splice, prefill + greedy decode).  draft_ids (optional, set_speculative / set_prefill_draft): a guess of this turn's whole id sequence; with
         set_auto_draft(True) and no explicit draft, the env's previous turn output is the guess.
@@ -591,17 +591,25 @@ class StreamVLNForCausalLM:
         `output_scores` / `output_logits` stay ignored: a [n_new, vocab] tensor is exactly what this engine exists not to build.
         do_sample=True with num_return_sequences=G, 2 <= G <= 8: a group turn (see _group_result for the result, select_sequence for what
         must follow); absent or 1: this path, launch for launch; a greedy call leaves the key unread.
-        forced_ids (1 .. 32 ids): a forced turn -- the turn's ids are the caller's (see _generate_forced); `max_new_tokens` is not read."""
+        forced_ids (1 .. 32 ids): a forced turn -- the turn's ids are the caller's (see _generate_forced); `max_new_tokens` is not read.
+        candidate_ids (2 .. 8 id lists of 1 .. 32 ids): the candidates are scored against ONE prefill of the prompt (see
+        _generate_candidates for the result, select_sequence for what must follow); `max_new_tokens` is not read."""
         draft = draft_ids
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
         n_seq = self._num_return_sequences(kwargs)
         if forced_ids is not None and n_seq > 1:
             raise NotImplementedError("forced_ids with num_return_sequences > 1: a forced turn has one sequence")
+        if candidate_ids is not None and forced_ids is not None:
+            raise NotImplementedError("candidate_ids together with forced_ids: a forced turn scores one sequence, a candidates call several")
+        if candidate_ids is not None and n_seq > 1:
+            raise NotImplementedError("candidate_ids with num_return_sequences > 1: the candidates are the call's sequences")
         self._sync_call_config()
         held = self._sampling
         self._sync_sampling(kwargs)
-        if forced_ids is not None or n_seq > 1:
+        if forced_ids is not None or candidate_ids is not None or n_seq > 1:
             try:
+                if candidate_ids is not None:
+                    return self._generate_candidates(candidate_ids, inputs, ids, pix, V, n_memory, env_id, past, eos)
                 if forced_ids is not None:
                     return self._generate_forced(forced_ids, inputs, ids, pix, V, n_memory, env_id, past, eos)
                 return self._generate_group(n_seq, inputs, ids, pix, V, n_memory, env_id, past, max_new, eos)
@@ -698,6 +706,82 @@ class StreamVLNForCausalLM:
             res["allowed_token_ids"] = torch.tensor(self.allowed_token_ids, dtype=torch.int64, device=dev)
         return res
 
+    # ---- candidate scoring: several given continuations of one prompt in one prefill (svln_turn_candidates) ----
+    @staticmethod
+    def _candidate_arrays(cands):
+        """candidate_ids -> (flat int64 ids, int32 lengths); 2 .. 8 sequences of 1 .. 32 ids"""
+        if isinstance(cands, torch.Tensor) and cands.dim() != 2:
+            raise ValueError("candidate_ids: a list of id sequences (or a [G, n] tensor)")
+        rows = [np.ascontiguousarray(torch.as_tensor(c).reshape(-1).to("cpu", torch.int64).numpy()) for c in cands]
+        if not (2 <= len(rows) <= 8):
+            raise ValueError(f"candidate_ids holds {len(rows)} sequences: a candidates call takes 2 .. 8")
+        for g, r in enumerate(rows):
+            if not (1 <= r.size <= 32):
+                raise ValueError(f"candidate_ids[{g}] holds {int(r.size)} ids: a candidate has 1 .. 32")
+        return np.ascontiguousarray(np.concatenate(rows)), np.asarray([r.size for r in rows], dtype=np.int32)
+
+    def _generate_candidates(self, cands, inputs, ids, pix, V, n_memory, env_id, past, eos):
+        """generate(..., candidate_ids=[F_0, ..., F_{G-1}]): ONE vision pass, ONE prefill of the prompt and ceil(max_g (n_g - 1) / r) scoring
+        passes for all candidates together; no decode phase.  The result is shaped like a group turn's: `sequences` int64 [G, n_max]
+        (padded like a group's), `sequence_lengths` [G], `token_logprobs` fp32 [G, n_max] (log p(F_g[i] | prompt, F_g[:i]), pad 0: a row
+        sum is the candidate's joint log-probability; always present), `greedy_ids` int64 / `greedy_logprobs` fp32 [G, n_max] (the
+        policy's own arg-max at every position; pads: the pad id / 0), with an allowed list `allowed_logprobs` [G, n_max, n_allowed] /
+        `allowed_token_ids`, and `past_key_values` None: select_sequence(index, env_id) must follow, and leaves the env where
+        generate(forced_ids=F_index) would have."""
+        if past is not None and (not isinstance(past, KVHandle) or past.env_id != env_id or past.epoch != self._epoch[env_id]):
+            raise ValueError("past_key_values does not belong to this env's current window")
+        flat, lens = self._candidate_arrays(cands)
+        G, n_max, total = int(lens.size), int(lens.max()), int(flat.size)
+        slot = self._slot(env_id)
+        on_dev = int(pix.is_cuda)
+        ids_np = np.ascontiguousarray(ids.numpy())
+        eos_np = np.asarray(eos, dtype=np.int64)
+        lp, glp, gid = np.zeros(total, dtype=np.float32), np.zeros(total, dtype=np.float32), np.zeros(total, dtype=np.int64)
+        a = _lib.SvlnTurnArgs()
+        a.pixels, a.n_frames, a.pixels_on_device, a.env = pix.data_ptr(), V, on_dev, slot
+        a.ids, a.n_ids, a.n_memory = ids_np.ctypes.data, ids_np.size, n_memory
+        a.new_window, a.new_episode, a.max_new_tokens = int(past is None), int(self.curr_t[env_id] == 0), n_max
+        a.eos_ids, a.n_eos = eos_np.ctypes.data, eos_np.size
+        if on_dev:
+            self._order_engine_after(pix)
+        PF, PI = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+        rc = self._lib.svln_turn_candidates(self._h, C.byref(a), G, flat.ctypes.data_as(PI), lens.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            lp.ctypes.data_as(PF), gid.ctypes.data_as(PI), glp.ctypes.data_as(PF))
+        if on_dev:
+            self._order_torch_after(pix)
+        _check(rc)
+        self.curr_t[env_id] += 1
+        self._group_pending[env_id] = G
+        dev = inputs.device if isinstance(inputs, torch.Tensor) else "cpu"
+        pad = getattr(self.generation_config, "pad_token_id", None)
+        if pad is None:
+            pad = eos[0] if len(eos) else 0
+        seq, gids = np.full((G, n_max), int(pad), dtype=np.int64), np.full((G, n_max), int(pad), dtype=np.int64)
+        tlp, tglp = np.zeros((G, n_max), dtype=np.float32), np.zeros((G, n_max), dtype=np.float32)
+        off = 0
+        for g in range(G):
+            n = int(lens[g])
+            seq[g, :n], gids[g, :n], tlp[g, :n], tglp[g, :n] = flat[off:off + n], gid[off:off + n], lp[off:off + n], glp[off:off + n]
+            off += n
+        res = GenerateOutput(sequences=torch.from_numpy(seq).to(dev), sequence_lengths=torch.from_numpy(lens.astype(np.int64)).to(dev),
+                             past_key_values=None)
+        res["token_logprobs"] = torch.from_numpy(tlp).to(dev)
+        res["greedy_ids"] = torch.from_numpy(gids).to(dev)
+        res["greedy_logprobs"] = torch.from_numpy(tglp).to(dev)
+        if self.allowed_token_ids:
+            n_ids = len(self.allowed_token_ids)
+            alp = np.zeros((G, n_max, n_ids), dtype=np.float32)
+            buf, nr, nc = np.empty(n_max * n_ids, dtype=np.float32), C.c_int32(), C.c_int32()
+            for g in range(G):
+                n = int(lens[g])
+                _check(self._lib.svln_group_dist(self._h, g, buf.ctypes.data_as(PF), n_max, C.byref(nr), C.byref(nc)))
+                if nr.value != n or nc.value != n_ids:
+                    raise RuntimeError(f"the engine holds {nr.value} x {nc.value} allowed log-probabilities for a candidate of {n} ids over {n_ids} allowed ids")
+                alp[g, :n] = buf[: n * n_ids].reshape(n, n_ids)
+            res["allowed_logprobs"] = torch.from_numpy(alp).to(dev)
+            res["allowed_token_ids"] = torch.tensor(self.allowed_token_ids, dtype=torch.int64, device=dev)
+        return res
+
     # ---- group sampling: several sampled continuations of one prefill (svln_turn_group) ----------------
     @staticmethod
     def _num_return_sequences(kwargs) -> int:
@@ -715,6 +799,8 @@ class StreamVLNForCausalLM:
     def _reject_group_request(kwargs, who):
         if kwargs.get("forced_ids") is not None:
             raise NotImplementedError(f"forced_ids in a {who} request: forced turns run through generate() only")
+        if kwargs.get("candidate_ids") is not None:
+            raise NotImplementedError(f"candidate_ids in a {who} request: candidates are scored through generate() only")
         g = kwargs.get("num_return_sequences")
         if g is not None and int(g) > 1:
             raise NotImplementedError(f"num_return_sequences={g!r} in a {who} request: group turns run through generate() only")
@@ -972,6 +1058,8 @@ class StreamVLNForCausalLM:
         g = kwargs.get("num_return_sequences")
         if g is not None and int(g) > 1:
             raise NotImplementedError(f"num_return_sequences={g!r} in a submit_forced request: a forced turn has one sequence")
+        if kwargs.get("candidate_ids") is not None:
+            raise NotImplementedError("candidate_ids in a submit_forced request: candidates are scored through generate() only")
         f_np = self._forced_array(forced_ids)
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
         if any(v[0] == env_id for v in self._tickets.values()):
@@ -1049,6 +1137,8 @@ class StreamVLNForCausalLM:
         for r in requests:
             r = dict(r)
             f = r.pop("forced_ids", None)
+            if r.get("candidate_ids") is not None:
+                raise NotImplementedError("candidate_ids in a generate_batch_forced request: candidates are scored through generate() only")
             g = r.get("num_return_sequences")
             if g is not None and int(g) > 1:
                 raise NotImplementedError(f"num_return_sequences={g!r} in a generate_batch_forced request: group turns run through generate() only")
