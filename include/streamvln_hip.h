@@ -59,6 +59,8 @@ int svln_get_tensor_f32(svln_engine* h, const char* name, float* host_out, int64
 int svln_reset_env(svln_engine* h, int env);
 int svln_kv_reset(svln_engine* h, int env);
 int svln_env_state(svln_engine* h, int env, int32_t* n_embeds, int32_t* kv_len);
+/* pages of the KV pool that no env and no pending group holds (tests: page accounting) */
+int svln_kv_free_pages(svln_engine* h, int32_t* n);
 
 /* -- vision: encode_rgbd (stream_video_vln.py:102-142) minus the memory/image split:
  * pixels fp32 [F,3,S,S] (device or host) -> F*196 pooled rows kept in the engine's frame buffer. */
@@ -304,6 +306,28 @@ int svln_generate_group(svln_engine* h, int env, int n_seq, int max_new_tokens, 
                         int32_t* n_out);
 /* svln_turn's bookkeeping (encode, window / episode resets, splice), then the group turn, in one crossing */
 int svln_turn_group(svln_engine* h, const svln_turn_args* a, int n_seq, int64_t* out_ids, int out_cap, int32_t* n_out);
+/* Beam turn: the n_beams (1 .. 8) most probable turns of env's prompt in ONE prefill.  limit = min(max_new_tokens, out_cap).  The set of
+ * at most n_beams hypotheses is kept in rank order; a step pools every finished hypothesis (score unchanged) with every listable entry
+ * (rank r, entry j) of the top-n_beams list of every live one (score fl(score_r + lp), lp as svln_top_logprobs defines it under greedy
+ * decoding) and keeps the best n_beams by score descending, then r, then j ascending; a hypothesis is finished when its last id is in the
+ * EOS set (appended, never fed) or its length equals limit; no length penalty.  n_beams = 1 is the greedy turn.
+ *   out_ids [n_beams][out_cap], n_out [n_beams] (0 for ranks the set does not hold), scores [n_beams] (fp32 sum of the log-probabilities).
+ * The prefill, the fork of the partly filled page and the batched step are svln_generate_group's; the head of every step is the top-k
+ * form at k = n_beams whatever svln_set_token_scores / svln_top_logprobs say.  The call leaves a pending group turn: sequence g = rank g
+ * owns exactly the pages that hold its rows; svln_group_select (kv_len = L + n_g - 1), svln_group_logprobs, svln_get_hidden_group, the
+ * resets work as after svln_generate_group.  Needs env_need + (2 n_beams - 1) x n_tail free pages.  An armed draft is consumed.
+ * Refused by name before any launch or state change: n_beams outside 1 .. 8, sampling on, an allowed list shorter than n_beams, a
+ * repetition penalty != 1, svln_set_fp8_decode / svln_set_mxfp4_decode / svln_set_fp8_gemm / svln_set_decode_persistent /
+ * svln_set_mxfp4_batched on, scheduler turns in flight, a group pending, nothing to prefill, L + limit - 1 > max_positions, more
+ * than 8 tail pages, a pool that cannot hold the tails. */
+int svln_generate_beams(svln_engine* h, int env, int n_beams, int max_new_tokens, const int64_t* eos_ids, int n_eos, int64_t* out_ids, int out_cap,
+                        int32_t* n_out, float* scores);
+/* svln_turn (encode, bookkeeping, splice) followed by svln_generate_beams */
+int svln_turn_beams(svln_engine* h, const svln_turn_args* a, int n_beams, int64_t* out_ids, int out_cap, int32_t* n_out, float* scores);
+/* The steps of the last beam turn, for tests: *n_steps, *width = n_beams; for step s < min(*n_steps, cap_steps): list_ids / list_lps
+ * [s][8][8] = the list of head row r (= rank r before the step; step 0: row 0 only; -1 / -inf = none; rows of finished ranks replay the
+ * first live row) and records [s][28] = the record of svln_op_beam_select. */
+int svln_beam_trace(svln_engine* h, int cap_steps, int32_t* n_steps, int32_t* width, int32_t* list_ids, float* list_lps, int32_t* records);
 /* The env goes on with sequence `index` of its pending group: for index >= 1 its table entries [q0, q0 + n_tail) become that sequence's
  * private pages and its former pages at those entries go back to the free pool; every other fork's pages go back too.  The env's kv
  * length becomes L + n_out[index] - 1 (-> *kv_len_out, may be null).  Refused: no group pending on env, index outside [0, n_seq). */
@@ -854,6 +878,31 @@ int svln_op_kv_pool_read(svln_engine* h, int layer, int start, int n, float* k_o
  * host list dst_pages in every layer's K and V^T pool.  Refused before any launch: a null list, n_dst outside 1 .. 7, a page outside the
  * pool, a destination equal to the source or listed twice, a destination held by an env (or by a pending group). */
 int svln_op_kv_page_copy(svln_engine* h, int src_page, const int32_t* dst_pages, int n_dst);
+/* TEST-ONLY: one launch of kv_page_gather_kernel (the KV hand-over between the hypotheses of a beam step): physical page src_pages[i] is
+ * copied to page dst_pages[i], i < n, in every layer's K and V^T pool; one source may serve several destinations.  Refused before any
+ * launch: a null list, n outside 1 .. 64, a page outside the pool, a page that is both a source and a destination, a destination listed
+ * twice, a destination held by an env (or by a pending group). */
+int svln_op_beam_page_gather(svln_engine* h, const int32_t* src_pages, const int32_t* dst_pages, int n);
+/* TEST-ONLY: one launch of beam_select_kernel, the select step of a beam search over the lm_head's top-W lists, on a caller-given
+ * hypothesis set (rank = index, at most 8 hypotheses of at most len_cap <= 64 ids).
+ *   in : hdr_in int32 [25] = n, len[8], fin[8], set_of[8]; score_in [8]; ids_in / lps_in [8][len_cap]; list_ids / list_lps [8][W], row =
+ *        rank (rows of finished ranks are not read; id -1 = no entry); eos [n_eos]; set_pages [16][n_cp] (may be null when n_cp = 0);
+ *        tok_b [B] holds the caller's bytes on entry
+ *   rule: pool = every finished hypothesis (score unchanged) + every entry (r, j) with id >= 0 of a live one, score fl(score_r + lp_rj);
+ *        the new set = the best W by score descending, then r, then j ascending; a new hypothesis is finished when its last id is in eos
+ *        or its length equals limit; tok_b[k] = the last id of rank k if it is live, else of the first live rank (untouched: none is
+ *        live); rank c keeps its parent's page set if no earlier rank took it, else takes the lowest set that neither the old set holds
+ *        nor an earlier rank took, and the first n_cp pages of the two sets are listed in pair_src / pair_dst [8 * n_cp]
+ *   out: hdr_out / score_out / ids_out / lps_out as the inputs (entries past the new n are unspecified; ids_out / lps_out keep the caller's
+ *        bytes where the kernel writes nothing); rec int32 [28] = n_new, live now, live before, pairs, parent rank [8], entry [8], page
+ *        set [8] (-1 = unused)
+ * Refused before any launch: a null pointer, W outside 1 .. 8, len_cap outside 1 .. 64, limit outside 1 .. len_cap, B or n_eos outside
+ * their ranges, n_cp outside 0 .. 8, n outside 0 .. 8, a flag that is not 0 / 1, a length outside 0 .. len_cap or not below limit for a
+ * live hypothesis, a page set outside 0 .. 15 or held twice. */
+int svln_op_beam_select(svln_engine* h, int W, int limit, int B, int n_cp, int len_cap, const int32_t* eos, int n_eos, const int32_t* list_ids,
+                        const float* list_lps, const int32_t* hdr_in, const float* score_in, const int32_t* ids_in, const float* lps_in,
+                        const int32_t* set_pages, int32_t* hdr_out, float* score_out, int32_t* ids_out, float* lps_out, int32_t* tok_b,
+                        int32_t* pair_src, int32_t* pair_dst, int32_t* rec);
 /* the prefill q|k|v product of one env's turn on layer 0 (env 0, positions P .. P + T - 1) as a prefill runs it: x = the normed input
  * rows [T][hidden] (device); roped q rows -> q_out [T][q_stride], roped k / v appended to env 0's pages; *fused = 1 when the product's
  * split-K reduce did the RoPE + append, 0 when the separate RoPE + append kernel did */

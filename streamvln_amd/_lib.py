@@ -84,6 +84,7 @@ SIGNATURES = {
     "svln_reset_env": (_I, [_P, _I]),
     "svln_kv_reset": (_I, [_P, _I]),
     "svln_env_state": (_I, [_P, _I, _PI32, _PI32]),
+    "svln_kv_free_pages": (_I, [_P, _PI32]),
     "svln_encode_frames": (_I, [_P, _P, _I, _I]),
     "svln_preprocess_frames": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "svln_preprocess_frames_enqueue": (_I, [_P, _P, _I, _I, _I, _I, _P]),
@@ -144,6 +145,12 @@ SIGNATURES = {
     "svln_group_dist": (_I, [_P, _I, _PF, _I, _PI32, _PI32]),
     "svln_get_hidden_group": (_I, [_P, _I, _PF, _I, _PI32]),
     "svln_op_kv_page_copy": (_I, [_P, _I, _PI32, _I]),
+    "svln_generate_beams": (_I, [_P, _I, _I, _I, _PI64, _I, _PI64, _I, _PI32, _PF]),
+    "svln_turn_beams": (_I, [_P, C.POINTER(SvlnTurnArgs), _I, _PI64, _I, _PI32, _PF]),
+    "svln_beam_trace": (_I, [_P, _I, _PI32, _PI32, _PI32, _PF, _PI32]),
+    "svln_op_beam_page_gather": (_I, [_P, _PI32, _PI32, _I]),
+    "svln_op_beam_select": (_I, [_P, _I, _I, _I, _I, _I, _PI32, _I, _PI32, _PF, _PI32, _PF, _PI32, _PF, _PI32, _PI32, _PF, _PI32, _PF, _PI32,
+                                 _PI32, _PI32, _PI32]),
     "svln_op_kv_pool_read": (_I, [_P, _I, _I, _I, _PF, _PF]),
     "svln_set_layer_taps": (_I, [_P, _I, _I]),
     "svln_get_layer_taps": (_I, [_P, _PF]),

@@ -96,6 +96,9 @@ class StreamingAgent:
         # the joint log-probability of every candidate of the last candidates turn (act(..., candidate_ids=...)): [G]; the index taken
         self.last_candidate_logprobs = None
         self.last_candidate_index = None
+        self.last_beam_ids = None               # of the last act_beams turn: every hypothesis' ids, in rank order
+        self.last_beam_scores = None
+        self.last_beam_index = None
         self.step_id = 0
         self.last_image = None
         self.model.reset_for_env(self.env_id)
@@ -193,6 +196,29 @@ class StreamingAgent:
         one["candidates"] = out
         return self._consume(one)
 
+    def _turn_beams(self, instruction: str, beam_width: int, select=None, env_id: Optional[int] = None):
+        """the model turn as a beam turn (model.generate(beam_width=W)): the env goes on with hypothesis `select` (default: rank 0)"""
+        req = self._build_request(instruction, env_id)
+        req["beam_width"] = int(beam_width)
+        req.pop("do_sample", None)              # (beams are greedy; the sampling switch of the model stays as it is)
+        req.pop("temperature", None)
+        out = self.model.generate(**req)
+        n_hyp = int(out.sequences.shape[0])
+        index = 0 if select is None else int(select)
+        if not (0 <= index < n_hyp):
+            index_err = ValueError(f"select={select!r}: the beam turn returned {n_hyp} hypotheses")
+            self.model.select_sequence(0, req["env_id"])      # the env must not stay blocked by the pending group
+            raise index_err
+        kv = self.model.select_sequence(index, req["env_id"])
+        n = int(out.sequence_lengths[index])
+        self.last_beam_ids = [out.sequences[g, : int(out.sequence_lengths[g])].tolist() for g in range(n_hyp)]
+        self.last_beam_scores = out.sequences_scores
+        self.last_beam_index = index
+        one = type(out)(sequences=out.sequences[index:index + 1, :n], past_key_values=kv)
+        one["token_logprobs"] = out.token_logprobs[index:index + 1, :n]
+        one["beams"] = out
+        return self._consume(one)
+
     # -- split form of act() used by BatchedAgents: observe -> (maybe) request -> finish ----------
     def observe(self, rgb):
         self.time_ids.append(self.step_id)
@@ -235,6 +261,20 @@ class StreamingAgent:
             raise ValueError(f"select={select!r}: {len(candidate_ids)} candidates were given")
         if self.observe(rgb):
             self.action_seq = self._turn_candidates(instruction, candidate_ids, select)
+        return self.finish_step()
+
+    def act_beams(self, rgb: np.ndarray, instruction: str = "", beam_width: int = 4, select=None) -> int:
+        """`act` whose model turn is a beam turn (model.generate(beam_width=W)): the env goes on with hypothesis `select` (default: rank
+        0, the most probable).  `last_beam_ids` / `last_beam_scores` keep every hypothesis in rank order, `last_beam_index` the one
+        taken.  Raises, before anything changes, when no model turn runs at this step.  (`act` keeps its argument list.)"""
+        if not (1 <= int(beam_width) <= 8):
+            raise ValueError(f"beam_width={beam_width!r}: a beam turn keeps 1 .. 8 hypotheses")
+        if len(self.action_seq) != 0:
+            raise ValueError(f"beam_width given at step {self.step_id}, but no model turn runs there: {len(self.action_seq)} actions of the last turn are still queued")
+        if select is not None and not (0 <= int(select) < int(beam_width)):
+            raise ValueError(f"select={select!r}: at most {int(beam_width)} hypotheses are returned")
+        if self.observe(rgb):
+            self.action_seq = self._turn_beams(instruction, beam_width, select)
         return self.finish_step()
 
     # -- real-world flavour ------------------------------------------------------------

@@ -78,6 +78,7 @@ struct EngineBase {
     virtual void reset_env(int env) = 0;
     virtual void kv_reset(int env) = 0;
     virtual void env_state(int env, int32_t* n_embeds, int32_t* kv_len) = 0;
+    virtual int kv_free_pages() = 0;
     virtual void encode_frames(const float* pixels, int F, int on_device) = 0;
     virtual void preprocess_frames(const uint8_t* rgb, int n, int height, int width, int on_device, float* out_dev, bool wait) = 0;
     virtual void* stream_handle() = 0;
@@ -129,6 +130,9 @@ struct EngineBase {
     virtual void op_gumbel(uint64_t seed, int stream, int draw, int n0, int count, float* out) = 0;
     virtual void generate_group(int env, int n_seq, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out) = 0;
     virtual void turn_group(const svln_turn_args& a, int n_seq, int64_t* out, int cap, int32_t* n_out) = 0;
+    virtual void generate_beams(int env, int W, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, float* scores) = 0;
+    virtual void turn_beams(const svln_turn_args& a, int W, int64_t* out, int cap, int32_t* n_out, float* scores) = 0;
+    virtual void beam_trace(int cap_steps, int32_t* n_steps, int32_t* width, int32_t* list_ids, float* list_lps, int32_t* records) = 0;
     virtual void generate_forced(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos, float* logprobs, int64_t* greedy_ids,
                                  float* greedy_logprobs, int32_t* kv_len) = 0;
     virtual void turn_forced(const svln_turn_args& a, const int64_t* ids, int n, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs,
@@ -151,6 +155,11 @@ struct EngineBase {
     virtual void group_dist(int index, float* out, int cap_rows, int32_t* n_rows, int32_t* n_cols) = 0;
     virtual void get_hidden_group(int index, float* out, int max_rows, int32_t* n_rows) = 0;
     virtual void op_kv_page_copy(int src_page, const int32_t* dst_pages, int n_dst) = 0;
+    virtual void op_beam_page_gather(const int32_t* src_pages, const int32_t* dst_pages, int n) = 0;
+    virtual void op_beam_select(int W, int limit, int B, int n_cp, int len_cap, const int32_t* eos, int n_eos, const int32_t* list_ids,
+                                const float* list_lps, const int32_t* hdr_in, const float* score_in, const int32_t* ids_in, const float* lps_in,
+                                const int32_t* set_pages, int32_t* hdr_out, float* score_out, int32_t* ids_out, float* lps_out, int32_t* tok_b,
+                                int32_t* pair_src, int32_t* pair_dst, int32_t* rec) = 0;
     virtual void op_kv_pool_read(int layer, int start, int n, float* k_out, float* v_out) = 0;
     virtual void sync() = 0;
     virtual void set_graph(int enable) = 0;
@@ -806,6 +815,7 @@ public:
     void refuse_while_jobs(const char* who) {
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, std::string(who) + " cannot change while scheduler turns are in flight");
     }
+    int kv_free_pages() override { return (int)free_pages.size(); }
     void env_state(int env, int32_t* n_embeds, int32_t* kv_len) override { Env& e = env_at(env); *n_embeds = e.n_embeds; *kv_len = e.kv_len; }
     void ensure_pages(Env& e, int positions) {      // pages covering [0, positions)
         const int need = (positions + PAGE - 1) / PAGE;
@@ -3098,6 +3108,253 @@ public:
         }
         generate_group(a.env, n_seq, a.max_new_tokens, a.eos_ids, a.n_eos, out, cap, n_out);
     }
+    // ------------------------------------------------------------------------------- beam turns (svln_generate_beams)
+    // The W most probable turns of one prompt.  The prefill, the fork of the partly filled page and the batched step are the group turn's;
+    // the head of every step is the EPI_ARGMAX_LSE_TOPK form at k = W (scores_on / topk / trunc_k are overridden for the call), whose
+    // lists d_topi_b / d_topl_b [row = rank][W] feed beam_select_kernel.  The hypothesis set lives in bm_hdr / bm_ids / bm_lps (two
+    // states, swapped every step).  Pages: 2 W sets of n_tail tail pages (set 0 = the env's own), each with a device page table
+    // beam_tab[s] = the env's pages below q0 + the set's pages; the select kernel hands the sets out and lists the (src, dst) pages of
+    // every child that cannot keep its parent's set, kv_page_gather_kernel copies them.  Sources are held by the old set, destinations
+    // are not, so nothing is permuted in place.  One synchronisation per step reads the record, the new header and the lists.
+    int* beam_tab[2 * BEAM_MAX_W] = {nullptr};
+    std::vector<int> beam_set[2 * BEAM_MAX_W];               // the tail pages of every set during a call (set 0: the env's own)
+    struct BeamTrace { int W = 0; std::vector<int32_t> list_ids, rec; std::vector<float> list_lps; int steps = 0; };
+    BeamTrace beam_trace_last;
+    void beam_refusals(int env, int W) {
+        const char* who = "svln_generate_beams";
+        env_at(env);
+        REQUIRE(W >= 1 && W <= BEAM_MAX_W, std::string(who) + ": n_beams must be 1 .. 8");
+        REQUIRE(!smp_on, std::string(who) + ": temperature sampling is on (svln_set_sampling); beams are greedy: switch it off first");
+        REQUIRE(!allow_on || allow_n >= W, std::string(who) + ": the allowed list (svln_set_allowed_tokens) is shorter than n_beams");
+        REQUIRE(rep_penalty == 1.0f, std::string(who) + ": a repetition penalty != 1 is set (svln_set_repetition_penalty); beams do not support it");
+        REQUIRE(!fp8_on, std::string(who) + ": the e4m3 decode weights are on (svln_set_fp8_decode); switch them off first");
+        REQUIRE(!mx4_on, std::string(who) + ": the MXFP4 decode weights are on (svln_set_mxfp4_decode); switch them off first");
+        REQUIRE(!fp8_gemm_on, std::string(who) + ": the fp8 MFMA products are on (svln_set_fp8_gemm); switch them off first");
+        REQUIRE(!persistent_on, std::string(who) + ": the persistent decode layer is on (svln_set_decode_persistent); switch it off first");
+        REQUIRE(!mx4b_on, std::string(who) + ": the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
+        REQUIRE((size_t)H * sizeof(float) <= (size_t)GEMV_ROWS_TOPK_MAX_LDS, std::string(who) + ": the hidden size is too large for the candidate form of the lm_head GEMV");
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, std::string(who) + " needs an idle scheduler (turns are in flight)");
+        REQUIRE(!grp.pending, std::string(who) + ": a group turn is pending on env " + std::to_string(grp.env) + "; choose its continuation with svln_group_select first");
+    }
+    void generate_beams(int env, int W, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, float* scores) override {
+        const char* who = "svln_generate_beams";
+        beam_refusals(env, W);
+        Env& e = envs[env];
+        REQUIRE(out && n_out && scores, std::string(who) + ": null output pointer");
+        REQUIRE(weights_missing() == 0, g_err);
+        const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
+        REQUIRE(Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
+        REQUIRE(max_new >= 1 && cap >= 1, "max_new_tokens must be >= 1");
+        REQUIRE(n_eos >= 0 && n_eos <= std::max(V, 64) && (n_eos == 0 || eos), std::string(who) + ": null eos list / too many eos ids");
+        const int limit = max_new < cap ? max_new : cap;
+        REQUIRE((int64_t)L + limit - 1 <= c.max_positions, std::string(who) + ": n_embeds + min(max_new_tokens, out_cap) - 1 exceeds max_positions");
+        const int q0 = L / PAGE;
+        const int n_tail = limit == 1 ? 0 : (L + limit - 1 + PAGE - 1) / PAGE - q0;
+        REQUIRE(n_tail <= BEAM_CP_MAX, std::string(who) + ": a turn of more than 8 tail pages does not fit the page lists of a beam step");
+        const int env_need = std::max((limit == 1 ? (L + PAGE - 1) / PAGE : q0 + n_tail) - e.n_pages, 0);
+        REQUIRE((int64_t)free_pages.size() >= (int64_t)env_need + (int64_t)(2 * W - 1) * n_tail,
+                std::string(who) + ": the free KV pages cannot hold the env's own pages and (2 n_beams - 1) x the tail pages of the hypotheses");
+        // ---- nothing was launched or changed up to here
+        disarm_draft(env);
+        last_scores_valid = false; last_alp_valid = false; last_topk_valid = false;
+        ensure_topk_buffers();
+        ensure_beam_buffers();
+        int B = 2; while (B < W) B <<= 1;
+        const int n_sets = 2 * W;
+        const bool held_scores = scores_on; const int held_topk = topk, held_trunc = trunc_k;
+        scores_on = true; topk = W; trunc_k = 0;
+        BeamTrace tr; tr.W = W;
+        BeamHdr hh;
+        std::vector<int> anc[BEAM_MAX_W];                 // per hypothesis: the head row that gave each of its ids (parity taps)
+        int rec[BEAM_REC];
+        int cur = 0;
+        auto read_step = [&](int rows, int phase) {
+            HIP_CHECK(hipEventRecord(ph_ev[3], st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            LAUNCH_CHECK("generate_beams");
+            HIP_CHECK(hipMemcpy(rec, bm_rec, sizeof(rec), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(&hh, bm_hdr[cur], sizeof(BeamHdr), hipMemcpyDeviceToHost));
+            const size_t o = tr.list_ids.size();
+            tr.list_ids.resize(o + BEAM_MAX_W * BEAM_MAX_W, -1); tr.list_lps.resize(o + BEAM_MAX_W * BEAM_MAX_W, -INFINITY);
+            std::vector<int> li((size_t)rows * W); std::vector<float> ll((size_t)rows * W);
+            HIP_CHECK(hipMemcpy(li.data(), d_topi_b, li.size() * sizeof(int), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(ll.data(), d_topl_b, ll.size() * sizeof(float), hipMemcpyDeviceToHost));
+            for (int r = 0; r < rows; ++r)
+                for (int j = 0; j < W; ++j) { tr.list_ids[o + r * BEAM_MAX_W + j] = li[(size_t)r * W + j]; tr.list_lps[o + r * BEAM_MAX_W + j] = ll[(size_t)r * W + j]; }
+            tr.rec.insert(tr.rec.end(), rec, rec + BEAM_REC);
+            ++tr.steps;
+            float t = 0.f;
+            HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[3])); ph_ms[phase] += t;
+            if (vision_pending) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
+            REQUIRE(hh.n >= 0 && hh.n <= W && rec[0] == hh.n && rec[3] >= 0 && rec[3] <= BEAM_MAX_W * BEAM_CP_MAX, "beam state out of range");
+            for (int q = 0; q < hh.n; ++q) REQUIRE(hh.set_of[q] >= 0 && hh.set_of[q] < n_sets && rec[4 + q] >= 0 && rec[4 + q] < BEAM_MAX_W, "beam state out of range");
+        };
+        auto select = [&](int n_cp) {
+            BeamSelectArgs a;
+            a.list_ids = d_topi_b; a.list_lps = d_topl_b; a.in = bm_hdr[cur]; a.in_ids = bm_ids[cur]; a.in_lps = bm_lps[cur];
+            a.out = bm_hdr[cur ^ 1]; a.out_ids = bm_ids[cur ^ 1]; a.out_lps = bm_lps[cur ^ 1];
+            a.len_cap = bm_len_cap; a.W = W; a.limit = limit; a.n_eos = n_eos; a.B = B; a.n_cp = n_cp; a.set_stride = BEAM_CP_MAX;
+            a.eos = bm_eos; a.set_pages = bm_sets; a.tok_b = d_tok_b; a.pair_src = bm_pair_src; a.pair_dst = bm_pair_dst; a.rec = bm_rec;
+            launch_beam_select(st, a);
+            cur ^= 1;
+        };
+        // the ancestry of the new set from the record: child c's rows are its parent's, plus the row that listed its last id
+        auto follow = [&](int row_of_parent_is_rank) {
+            std::vector<int> next[BEAM_MAX_W];
+            for (int q = 0; q < hh.n; ++q) {
+                const int pr = rec[4 + q];
+                next[q] = anc[pr];
+                if ((int)next[q].size() < hh.len[q]) next[q].push_back(row_of_parent_is_rank ? pr : 0);
+            }
+            for (int q = 0; q < BEAM_MAX_W; ++q) anc[q].swap(next[q]);
+        };
+        try {
+            HIP_CHECK(hipStreamSynchronize(st));
+            {   // the root of step 0, the EOS list, the page sets
+                BeamHdr root; std::memset(&root, 0, sizeof(root)); root.n = 1;
+                HIP_CHECK(hipMemcpy(bm_hdr[0], &root, sizeof(BeamHdr), hipMemcpyHostToDevice));
+                std::vector<int> ev(n_eos);
+                for (int k = 0; k < n_eos; ++k) ev[k] = eos[k] >= 0 && eos[k] < V ? (int)eos[k] : -2;      // ids outside the vocabulary never match
+                if (n_eos) HIP_CHECK(hipMemcpy(bm_eos, ev.data(), (size_t)n_eos * sizeof(int), hipMemcpyHostToDevice));
+            }
+            // prefill: svln_generate's, launch for launch
+            ensure_pages(e, L);
+            HIP_CHECK(hipEventRecord(ph_ev[2], st));
+            prefill(e, P, Tn);
+            e.kv_len = L;
+            const T* last = x + (size_t)(Tn - 1) * H;
+            for (int k = 0; k < B; ++k)
+                HIP_CHECK(hipMemcpyAsync(last_rows + (size_t)k * H, last, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
+            head_batched(last_rows, B);
+            tap_copy(xn, 0, 0);
+            // the page sets: set 0 = the env's own tail, the others fresh pages; one device table each
+            if (limit > 1) ensure_pages(e, L + limit - 1);
+            if (n_tail > 0) {
+                std::vector<int> flat((size_t)2 * BEAM_MAX_W * BEAM_CP_MAX, 0), tab(pages_per_env, 0);
+                for (int s = 0; s < n_sets; ++s) {
+                    beam_set[s].clear();
+                    for (int i = 0; i < n_tail; ++i) {
+                        if (s == 0) { beam_set[s].push_back(e.pages[q0 + i]); continue; }
+                        REQUIRE(!free_pages.empty(), "KV page pool exhausted");
+                        beam_set[s].push_back(free_pages.back());
+                        free_pages.pop_back();
+                    }
+                    if (!beam_tab[s]) beam_tab[s] = dalloc<int>(pages_per_env);       // (not zeroed: the stream's memset would land after the blocking upload below)
+                    for (int i = 0; i < q0; ++i) tab[i] = e.pages[i];
+                    for (int i = 0; i < n_tail; ++i) { tab[q0 + i] = beam_set[s][i]; flat[(size_t)s * BEAM_CP_MAX + i] = beam_set[s][i]; }
+                    HIP_CHECK(hipMemcpy(beam_tab[s], tab.data(), (size_t)(q0 + n_tail) * sizeof(int), hipMemcpyHostToDevice));
+                }
+                HIP_CHECK(hipMemcpy(bm_sets, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
+                if (L % PAGE != 0 && W > 1) {       // the partly filled page: the group turn's fork, to the sets the step-0 children take
+                    for (int s = 1; s < W; ++s) h_fork_dst[s - 1] = beam_set[s][0];
+                    HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)(W - 1) * sizeof(int), hipMemcpyHostToDevice, st));
+                    launch_kv_page_copy<T>(st, d_pool_tab, 2 * c.layers, e.pages[q0], d_fork_dst, W - 1, (int64_t)nkv * PAGE * 128);
+                }
+            }
+            select(0);
+            read_step(1, 1);
+            REQUIRE(hh.n >= 1, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+            follow(0);
+            for (int t = 0; rec[1] > 0; ++t) {
+                REQUIRE(t + 1 < limit && n_tail > 0, "beam state out of range");
+                int first = -1;
+                for (int q = hh.n - 1; q >= 0; --q) if (!hh.fin[q]) first = q;
+                REQUIRE(first >= 0, "beam state out of range");
+                for (int k = 0; k < B; ++k) {
+                    const int q = k < hh.n && !hh.fin[k] ? k : first;
+                    h_slots[k].page_table = beam_tab[hh.set_of[q]]; h_slots[k].pos = L + t; h_slots[k].pad = 0;
+                }
+                HIP_CHECK(hipEventRecord(ph_ev[2], st));
+                HIP_CHECK(hipMemcpyAsync(d_slots, h_slots, B * sizeof(DecodeSlot), hipMemcpyHostToDevice, st));
+                batched_step(B, false);
+                // (tokens 0 .. 7 are tapped, as svln_get_hidden_group reads them: a later step would overwrite tap row 7 with a row the
+                // rank reorder below cannot place)
+                for (int q = 0; q < hh.n && t + 1 < 8; ++q) if (!hh.fin[q]) tap_copy(xn + (size_t)q * H, t + 1, q);
+                select((L + t) / PAGE - q0 + 1);
+                read_step(hh.n, 2);          // (hh still holds the old set while the argument is evaluated)
+                follow(1);
+                if (rec[3] > 0) launch_kv_page_gather<T>(st, d_pool_tab, 2 * c.layers, bm_pair_src, bm_pair_dst, rec[3], (int64_t)nkv * PAGE * 128);
+            }
+            HIP_CHECK(hipStreamSynchronize(st));
+            LAUNCH_CHECK("generate_beams");
+            // the result: ids, log-probabilities and scores of the final set, in rank order
+            std::vector<int> ids((size_t)BEAM_MAX_W * bm_len_cap); std::vector<float> lps((size_t)BEAM_MAX_W * bm_len_cap);
+            HIP_CHECK(hipMemcpy(ids.data(), bm_ids[cur], ids.size() * sizeof(int), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(lps.data(), bm_lps[cur], lps.size() * sizeof(float), hipMemcpyDeviceToHost));
+            grp = Group();
+            grp.env = env; grp.n_seq = hh.n; grp.L = L; grp.q0 = q0; grp.n_tail = n_tail; grp.scored = true; grp.alp_n = 0;
+            for (int g = 0; g < W; ++g) { n_out[g] = 0; scores[g] = -INFINITY; }
+            for (int g = 0; g < hh.n; ++g) {
+                const int n = hh.len[g];
+                REQUIRE(n >= 1 && n <= limit && hh.fin[g], "beam state out of range");
+                for (int k = 0; k < n; ++k) {
+                    const int tok = ids[(size_t)g * bm_len_cap + k];
+                    REQUIRE(tok >= 0 && tok < V, "beam state out of range");
+                    out[(size_t)g * cap + k] = tok;
+                    grp.scores[g].push_back(lps[(size_t)g * bm_len_cap + k]);
+                }
+                n_out[g] = grp.n_out[g] = n; scores[g] = hh.score[g];
+            }
+            // pages: rank 0's set becomes the env's tail, rank g's set the group's tail[g], every other set goes back to the pool
+            if (n_tail > 0) {
+                bool used[2 * BEAM_MAX_W] = {false};
+                for (int g = 0; g < hh.n; ++g) used[hh.set_of[g]] = true;
+                for (int i = 0; i < n_tail; ++i) e.pages[q0 + i] = beam_set[hh.set_of[0]][i];
+                HIP_CHECK(hipMemcpyAsync(e.d_pages + q0, e.pages.data() + q0, (size_t)n_tail * sizeof(int), hipMemcpyHostToDevice, st));
+                for (int g = 1; g < hh.n; ++g) grp.tail[g] = beam_set[hh.set_of[g]];
+                for (int s = 0; s < n_sets; ++s) {
+                    if (!used[s]) for (int p : beam_set[s]) free_pages.push_back(p);
+                    beam_set[s].clear();
+                }
+            }
+            if (taps_on) {      // the parity taps in rank order: token i of rank g left head row anc[g][i] of step i
+                const size_t n_tap = (size_t)8 * MAXB * H;
+                if (!bm_tap) bm_tap = dalloc<T>(n_tap);
+                HIP_CHECK(hipMemcpyAsync(bm_tap, hid_tap, n_tap * sizeof(T), hipMemcpyDeviceToDevice, st));
+                for (int g = 0; g < hh.n; ++g)
+                    for (int i = 0; i < (int)anc[g].size() && i < 8; ++i)
+                        HIP_CHECK(hipMemcpyAsync(hid_tap + (size_t)(i * MAXB + g) * H, bm_tap + (size_t)(i * MAXB + anc[g][i]) * H, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
+            }
+            HIP_CHECK(hipStreamSynchronize(st));
+        } catch (...) {
+            // every page of sets 1 .. goes back to the pool, no group is pending; the env is as after a failed svln_generate
+            (void)hipStreamSynchronize(st);
+            for (int s = 1; s < 2 * BEAM_MAX_W; ++s) { for (int p : beam_set[s]) free_pages.push_back(p); beam_set[s].clear(); }
+            beam_set[0].clear();
+            grp = Group();
+            scores_on = held_scores; topk = held_topk; trunc_k = held_trunc;
+            throw;
+        }
+        scores_on = held_scores; topk = held_topk; trunc_k = held_trunc;
+        beam_trace_last = std::move(tr);
+        e.kv_len = L;                     // until svln_group_select
+        n_generated = 0;                  // (the single-env tap rows were overwritten)
+        top2_stale = true;
+        top2_sampled = false;
+        grp.pending = true;
+    }
+    void turn_beams(const svln_turn_args& a, int W, int64_t* out, int cap, int32_t* n_out, float* scores) override {
+        beam_refusals(a.env, W);
+        REQUIRE(a.ids && a.n_ids >= 1 && out && n_out && scores, "svln_turn_beams: null / empty argument");
+        try {
+            encode_frames(a.pixels, a.n_frames, a.pixels_on_device);
+            if (a.new_window) kv_reset(a.env);
+            if (a.new_episode && envs[a.env].n_embeds != 0) reset_env(a.env);
+            append_turn(a.env, a.ids, a.n_ids, 0, a.n_memory);
+        } catch (...) {
+            disarm_draft(a.env);
+            throw;
+        }
+        generate_beams(a.env, W, a.max_new_tokens, a.eos_ids, a.n_eos, out, cap, n_out, scores);
+    }
+    void beam_trace(int cap_steps, int32_t* n_steps, int32_t* width, int32_t* list_ids, float* list_lps, int32_t* records) override {
+        const BeamTrace& tr = beam_trace_last;
+        REQUIRE(tr.steps > 0, "svln_beam_trace: no beam turn has run");
+        const int m = std::min(tr.steps, cap_steps);
+        for (int q = 0; q < m * BEAM_MAX_W * BEAM_MAX_W; ++q) { list_ids[q] = tr.list_ids[q]; list_lps[q] = tr.list_lps[q]; }
+        for (int q = 0; q < m * BEAM_REC; ++q) records[q] = tr.rec[q];
+        *n_steps = tr.steps; *width = tr.W;
+    }
     // ------------------------------------------------------------------------------- candidate scoring (svln_generate_candidates)
     // n_seq caller-given continuations of ONE prompt: the prompt is prefilled once (svln_generate's prefill), forked as a group turn forks
     // it, and the fed ids of all sequences go through the batched step's products in passes of n_seq x r row slots with the batched verify
@@ -4300,6 +4557,116 @@ public:
         sync();
         LAUNCH_CHECK("op_kv_page_copy");
     }
+    // the device workspace of the beam ops (allocated on first use): two hypothesis states of BEAM_OP_LEN ids per row, the lists of 8 rows,
+    // the page sets, the pair lists, the record, the EOS list and the fed tokens
+    static constexpr int BEAM_OP_LEN = 64, BEAM_OP_PAIRS = BEAM_MAX_W * BEAM_CP_MAX;
+    BeamHdr* bm_hdr[2] = {nullptr, nullptr};
+    int *bm_ids[2] = {nullptr, nullptr}, *bm_list_ids = nullptr, *bm_sets = nullptr, *bm_pair_src = nullptr, *bm_pair_dst = nullptr, *bm_rec = nullptr,
+        *bm_eos = nullptr, *bm_tok = nullptr;
+    float *bm_lps[2] = {nullptr, nullptr}, *bm_list_lps = nullptr;
+    int bm_len_cap = 0;                              // ids per row of the two states: what a beam turn can emit
+    T* bm_tap = nullptr;                             // copy of the parity taps while a beam turn reorders them by rank
+    void ensure_beam_buffers() {
+        if (bm_hdr[0]) return;
+        bm_len_cap = std::min(std::max(BEAM_OP_LEN, c.max_positions), BEAM_CP_MAX * PAGE + 64);     // (a turn of <= 8 tail pages emits <= 513 ids)
+        for (int k = 0; k < 2; ++k) {
+            bm_hdr[k] = dalloc<BeamHdr>(1, true);
+            bm_ids[k] = dalloc<int>((size_t)BEAM_MAX_W * bm_len_cap, true); bm_lps[k] = dalloc<float>((size_t)BEAM_MAX_W * bm_len_cap, true);
+        }
+        bm_list_ids = dalloc<int>(BEAM_MAX_W * BEAM_MAX_W, true); bm_list_lps = dalloc<float>(BEAM_MAX_W * BEAM_MAX_W, true);
+        bm_sets = dalloc<int>(2 * BEAM_MAX_W * BEAM_CP_MAX, true);
+        bm_pair_src = dalloc<int>(BEAM_OP_PAIRS, true); bm_pair_dst = dalloc<int>(BEAM_OP_PAIRS, true);
+        bm_rec = dalloc<int>(BEAM_REC, true); bm_eos = dalloc<int>((size_t)std::max(V, 64), true); bm_tok = dalloc<int>(64, true);
+    }
+    // TEST-ONLY: one launch of kv_page_gather_kernel on caller-given pairs; every refusal comes before the launch
+    void op_beam_page_gather(const int32_t* src_pages, const int32_t* dst_pages, int n) override {
+        const char* who = "svln_op_beam_page_gather";
+        REQUIRE(src_pages && dst_pages, std::string(who) + ": null page list");
+        REQUIRE(n >= 1 && n <= BEAM_OP_PAIRS, std::string(who) + ": n must be 1 .. 64");
+        for (int i = 0; i < n; ++i) {
+            const int s = src_pages[i], p = dst_pages[i];
+            REQUIRE(s >= 0 && s < pages_total, std::string(who) + ": source page outside the pool");
+            REQUIRE(p >= 0 && p < pages_total, std::string(who) + ": destination page outside the pool");
+            for (int q = 0; q < n; ++q) REQUIRE(src_pages[q] != p, std::string(who) + ": a page is both a source and a destination");
+            for (int q = 0; q < i; ++q) REQUIRE(dst_pages[q] != p, std::string(who) + ": a destination is listed twice");
+            for (const Env& e : envs)
+                for (int k = 0; k < e.n_pages; ++k) REQUIRE(e.pages[k] != p, std::string(who) + ": a destination is held by an env");
+            for (int g = 1; g < MAXB; ++g)
+                for (int t : grp.tail[g]) REQUIRE(t != p, std::string(who) + ": a destination is held by a pending group");
+        }
+        ensure_beam_buffers();
+        sync();
+        HIP_CHECK(hipMemcpy(bm_pair_src, src_pages, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(bm_pair_dst, dst_pages, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+        launch_kv_page_gather<T>(st, d_pool_tab, 2 * c.layers, bm_pair_src, bm_pair_dst, n, (int64_t)nkv * PAGE * 128);
+        sync();
+        LAUNCH_CHECK("op_beam_page_gather");
+    }
+    // TEST-ONLY: one launch of beam_select_kernel on a caller-given hypothesis set and lists; every refusal comes before the launch.
+    // hdr = int32 [25]: n, len[8], fin[8], set_of[8]
+    void op_beam_select(int W, int limit, int B, int n_cp, int len_cap, const int32_t* eos, int n_eos, const int32_t* list_ids, const float* list_lps,
+                        const int32_t* hdr_in, const float* score_in, const int32_t* ids_in, const float* lps_in, const int32_t* set_pages,
+                        int32_t* hdr_out, float* score_out, int32_t* ids_out, float* lps_out, int32_t* tok_b, int32_t* pair_src, int32_t* pair_dst,
+                        int32_t* rec) override {
+        const char* who = "svln_op_beam_select";
+        REQUIRE(list_ids && list_lps && hdr_in && score_in && ids_in && lps_in && hdr_out && score_out && ids_out && lps_out && tok_b && pair_src &&
+                    pair_dst && rec, std::string(who) + ": null pointer");
+        REQUIRE(W >= 1 && W <= BEAM_MAX_W, std::string(who) + ": W must be 1 .. 8");
+        REQUIRE(len_cap >= 1 && len_cap <= BEAM_OP_LEN, std::string(who) + ": len_cap must be 1 .. 64");
+        REQUIRE(limit >= 1 && limit <= len_cap, std::string(who) + ": limit must be 1 .. len_cap");
+        REQUIRE(B >= 1 && B <= 64, std::string(who) + ": B must be 1 .. 64");
+        REQUIRE(n_cp >= 0 && n_cp <= BEAM_CP_MAX && (n_cp == 0 || set_pages), std::string(who) + ": n_cp must be 0 .. 8 (with the page sets)");
+        REQUIRE(n_eos >= 0 && n_eos <= 64 && (n_eos == 0 || eos), std::string(who) + ": n_eos must be 0 .. 64 (with the list)");
+        BeamHdr hi;
+        hi.n = hdr_in[0];
+        REQUIRE(hi.n >= 0 && hi.n <= BEAM_MAX_W, std::string(who) + ": the set holds 0 .. 8 hypotheses");
+        for (int r = 0; r < BEAM_MAX_W; ++r) {
+            hi.len[r] = hdr_in[1 + r]; hi.fin[r] = hdr_in[1 + BEAM_MAX_W + r]; hi.set_of[r] = hdr_in[1 + 2 * BEAM_MAX_W + r]; hi.score[r] = score_in[r];
+            if (r >= hi.n) continue;
+            REQUIRE(hi.fin[r] == 0 || hi.fin[r] == 1, std::string(who) + ": a finished flag must be 0 or 1");
+            REQUIRE(hi.len[r] >= 0 && hi.len[r] <= len_cap && (hi.fin[r] || hi.len[r] < limit), std::string(who) + ": a length must be 0 .. len_cap, below limit for a live hypothesis");
+            REQUIRE(hi.set_of[r] >= 0 && hi.set_of[r] < 2 * BEAM_MAX_W, std::string(who) + ": a page set must be 0 .. 15");
+            for (int q = 0; q < r; ++q) REQUIRE(hi.set_of[q] != hi.set_of[r], std::string(who) + ": two hypotheses hold one page set");
+        }
+        ensure_beam_buffers();
+        sync();
+        const size_t rows = (size_t)BEAM_MAX_W * len_cap;
+        HIP_CHECK(hipMemcpy(bm_hdr[0], &hi, sizeof(BeamHdr), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemsetAsync(bm_hdr[1], 0xff, sizeof(BeamHdr), st));
+        HIP_CHECK(hipMemcpy(bm_ids[0], ids_in, rows * sizeof(int), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(bm_lps[0], lps_in, rows * sizeof(float), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(bm_ids[1], ids_out, rows * sizeof(int), hipMemcpyHostToDevice));        // (what the kernel leaves alone keeps the caller's bytes)
+        HIP_CHECK(hipMemcpy(bm_lps[1], lps_out, rows * sizeof(float), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(bm_list_ids, list_ids, (size_t)BEAM_MAX_W * W * sizeof(int), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(bm_list_lps, list_lps, (size_t)BEAM_MAX_W * W * sizeof(float), hipMemcpyHostToDevice));
+        if (n_cp) HIP_CHECK(hipMemcpy(bm_sets, set_pages, (size_t)2 * BEAM_MAX_W * n_cp * sizeof(int), hipMemcpyHostToDevice));
+        if (n_eos) HIP_CHECK(hipMemcpy(bm_eos, eos, (size_t)n_eos * sizeof(int), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(bm_tok, tok_b, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemsetAsync(bm_pair_src, 0xff, BEAM_OP_PAIRS * sizeof(int), st));
+        HIP_CHECK(hipMemsetAsync(bm_pair_dst, 0xff, BEAM_OP_PAIRS * sizeof(int), st));
+        BeamSelectArgs a;
+        a.list_ids = bm_list_ids; a.list_lps = bm_list_lps; a.in = bm_hdr[0]; a.in_ids = bm_ids[0]; a.in_lps = bm_lps[0];
+        a.out = bm_hdr[1]; a.out_ids = bm_ids[1]; a.out_lps = bm_lps[1];
+        a.len_cap = len_cap; a.W = W; a.limit = limit; a.n_eos = n_eos; a.B = B; a.n_cp = n_cp; a.set_stride = n_cp;
+        a.eos = bm_eos; a.set_pages = bm_sets; a.tok_b = bm_tok; a.pair_src = bm_pair_src; a.pair_dst = bm_pair_dst; a.rec = bm_rec;
+        launch_beam_select(st, a);
+        sync();
+        LAUNCH_CHECK("op_beam_select");
+        BeamHdr ho;
+        HIP_CHECK(hipMemcpy(&ho, bm_hdr[1], sizeof(BeamHdr), hipMemcpyDeviceToHost));
+        hdr_out[0] = ho.n;
+        for (int r = 0; r < BEAM_MAX_W; ++r) {
+            hdr_out[1 + r] = ho.len[r]; hdr_out[1 + BEAM_MAX_W + r] = ho.fin[r]; hdr_out[1 + 2 * BEAM_MAX_W + r] = ho.set_of[r]; score_out[r] = ho.score[r];
+        }
+        HIP_CHECK(hipMemcpy(ids_out, bm_ids[1], rows * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(lps_out, bm_lps[1], rows * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(tok_b, bm_tok, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+        if (n_cp) {
+            HIP_CHECK(hipMemcpy(pair_src, bm_pair_src, (size_t)BEAM_MAX_W * n_cp * sizeof(int), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(pair_dst, bm_pair_dst, (size_t)BEAM_MAX_W * n_cp * sizeof(int), hipMemcpyDeviceToHost));
+        }
+        HIP_CHECK(hipMemcpy(rec, bm_rec, BEAM_REC * sizeof(int), hipMemcpyDeviceToHost));
+    }
     void kv_read(const LLayer& L, int env, int start, int n, float* k_out, float* v_out) {
         REQUIRE(k_out && v_out, "null output pointer");
         const int limit = env < 0 ? pages_total * PAGE : env_at(env).n_pages * PAGE;
@@ -4628,6 +4995,7 @@ int svln_weights_ready(svln_engine* h) { API_BEGIN_H if (h->impl->weights_missin
 int svln_get_tensor_f32(svln_engine* h, const char* name, float* out, int64_t numel) { API_BEGIN_H h->impl->get_tensor_f32(name, out, numel); API_END }
 int svln_reset_env(svln_engine* h, int env) { API_BEGIN_H h->impl->reset_env(env); API_END }
 int svln_kv_reset(svln_engine* h, int env) { API_BEGIN_H h->impl->kv_reset(env); API_END }
+int svln_kv_free_pages(svln_engine* h, int32_t* n) { API_BEGIN_H REQUIRE(n, "null output pointer"); *n = h->impl->kv_free_pages(); API_END }
 int svln_env_state(svln_engine* h, int env, int32_t* n_embeds, int32_t* kv_len) { API_BEGIN_H h->impl->env_state(env, n_embeds, kv_len); API_END }
 int svln_encode_frames(svln_engine* h, const float* pixels, int n_frames, int on_device) { API_BEGIN_H h->impl->encode_frames(pixels, n_frames, on_device); API_END }
 int svln_preprocess_frames(svln_engine* h, const uint8_t* rgb, int n_frames, int height, int width, int on_device, float* out_dev) {
@@ -4840,6 +5208,16 @@ int svln_generate_batch_allowed_logprobs(svln_engine* h, int index, float* out, 
 int svln_generate_group(svln_engine* h, int env, int n_seq, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out) {
     API_BEGIN_H h->impl->generate_group(env, n_seq, max_new, eos, n_eos, out, cap, n_out); API_END
 }
+int svln_generate_beams(svln_engine* h, int env, int n_beams, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, float* scores) {
+    API_BEGIN_H h->impl->generate_beams(env, n_beams, max_new, eos, n_eos, out, cap, n_out, scores); API_END
+}
+int svln_turn_beams(svln_engine* h, const svln_turn_args* a, int n_beams, int64_t* out_ids, int out_cap, int32_t* n_out, float* scores) {
+    API_BEGIN_H REQUIRE(a, "null argument"); h->impl->turn_beams(*a, n_beams, out_ids, out_cap, n_out, scores); API_END
+}
+int svln_beam_trace(svln_engine* h, int cap_steps, int32_t* n_steps, int32_t* width, int32_t* list_ids, float* list_lps, int32_t* records) {
+    API_BEGIN_H REQUIRE(cap_steps >= 0 && n_steps && width && list_ids && list_lps && records, "null output pointer");
+    h->impl->beam_trace(cap_steps, n_steps, width, list_ids, list_lps, records); API_END
+}
 int svln_turn_group(svln_engine* h, const svln_turn_args* a, int n_seq, int64_t* out_ids, int out_cap, int32_t* n_out) {
     API_BEGIN_H REQUIRE(a, "null argument"); h->impl->turn_group(*a, n_seq, out_ids, out_cap, n_out); API_END
 }
@@ -4889,6 +5267,14 @@ int svln_get_hidden_group(svln_engine* h, int index, float* out, int max_rows, i
     API_BEGIN_H REQUIRE(out && n_rows, "null output pointer"); h->impl->get_hidden_group(index, out, max_rows, n_rows); API_END
 }
 int svln_op_kv_page_copy(svln_engine* h, int src_page, const int32_t* dst_pages, int n_dst) { API_BEGIN_H h->impl->op_kv_page_copy(src_page, dst_pages, n_dst); API_END }
+int svln_op_beam_page_gather(svln_engine* h, const int32_t* src_pages, const int32_t* dst_pages, int n) { API_BEGIN_H h->impl->op_beam_page_gather(src_pages, dst_pages, n); API_END }
+int svln_op_beam_select(svln_engine* h, int W, int limit, int B, int n_cp, int len_cap, const int32_t* eos, int n_eos, const int32_t* list_ids,
+                        const float* list_lps, const int32_t* hdr_in, const float* score_in, const int32_t* ids_in, const float* lps_in,
+                        const int32_t* set_pages, int32_t* hdr_out, float* score_out, int32_t* ids_out, float* lps_out, int32_t* tok_b,
+                        int32_t* pair_src, int32_t* pair_dst, int32_t* rec) {
+    API_BEGIN_H h->impl->op_beam_select(W, limit, B, n_cp, len_cap, eos, n_eos, list_ids, list_lps, hdr_in, score_in, ids_in, lps_in, set_pages, hdr_out,
+                                        score_out, ids_out, lps_out, tok_b, pair_src, pair_dst, rec); API_END
+}
 int svln_op_kv_pool_read(svln_engine* h, int layer, int start, int n, float* k_out, float* v_out) { API_BEGIN_H h->impl->op_kv_pool_read(layer, start, n, k_out, v_out); API_END }
 int svln_op_subset_argmax(svln_engine* h, const void* W, int ldw, const void* x, int ldx, int V, int K, int B, const int64_t* ids, int n,
                           const void* pen_flags, const int32_t* pen_rows, float penalty, float temperature, uint64_t seed, const int32_t* streams,

@@ -400,6 +400,38 @@ template <typename T> void launch_gather_rows_ragged(hipStream_t s, const int* l
 template <typename T> void launch_kv_page_copy(hipStream_t s, void* const* pools, int n_pools, int src_page, const int* dst_pages, int n_dst,
                                                int64_t page_elems);
 
+// Hand-over of KV pages between the hypotheses of a beam turn (kv_fork.hip): kv_page_copy with one source per destination.  In each of the
+// n_pools pools, page src_pages[i] is copied to page dst_pages[i] for i < n (device lists), in 16-byte chunks, all pairs in one launch.
+// The caller guarantees: every page inside the pools, the destinations distinct, no page both a source and a destination (so the order
+// of the pairs does not matter and nothing is permuted in place).  One source may serve several destinations.
+template <typename T> void launch_kv_page_gather(hipStream_t s, void* const* pools, int n_pools, const int* src_pages, const int* dst_pages, int n,
+                                                 int64_t page_elems);
+
+// One select step of a beam turn (misc.hip, beam_select_kernel; one workgroup).  The hypothesis set lives in device memory: a BeamHdr and
+// the rows ids / lps [BEAM_MAX_W][len_cap]; rank = index.  `in` is the set before the step, `out` the set after it (two different
+// states: children copy their parents' rows).  list_ids / list_lps [rank][W]: the lm_head list of every live hypothesis (the layout of
+// the batched heads' top-k lists at k = W; rows of finished ranks are not read; -1 = no entry).  Rule:
+//   pool    = every finished hypothesis (item (r, 0), score unchanged) + every (r, j) of a live one with id >= 0, score fl(score_r + lp_rj)
+//   new set = the best W of the pool by score descending, then r, then j ascending; finished = id in eos[0 .. n_eos) or length == limit
+//   tok_b   : row k < B of the next step feeds the last id of rank k if it is live, else of the first live rank (untouched: none live)
+//   pages   : rank c in order keeps its parent's page set if no earlier rank took it, else takes the lowest of the 16 sets that neither
+//             the old set holds nor an earlier rank took and lists (src, dst) for the first n_cp pages of the two sets
+//             (set_pages[set * set_stride + i]) in pair_src / pair_dst (room for BEAM_MAX_W * n_cp pairs)
+//   rec     : int [BEAM_REC]: n_new, n_live, live hypotheses before, pairs, then parent rank [8], chosen entry [8], page set [8] (-1 unused)
+// The caller guarantees: in->n <= 8, every length <= len_cap and < limit for a live hypothesis, limit <= len_cap, in->set_of distinct
+// values of 0 .. 15.
+constexpr int BEAM_MAX_W = 8, BEAM_CP_MAX = 8, BEAM_REC = 4 + 3 * BEAM_MAX_W;
+struct BeamHdr { int n; int len[BEAM_MAX_W]; int fin[BEAM_MAX_W]; int set_of[BEAM_MAX_W]; float score[BEAM_MAX_W]; };
+struct BeamSelectArgs {
+    const int* list_ids = nullptr; const float* list_lps = nullptr;
+    const BeamHdr* in = nullptr; const int* in_ids = nullptr; const float* in_lps = nullptr;
+    BeamHdr* out = nullptr; int* out_ids = nullptr; float* out_lps = nullptr;
+    int len_cap = 0, W = 0, limit = 0, n_eos = 0, B = 0, n_cp = 0, set_stride = 0;
+    const int* eos = nullptr; const int* set_pages = nullptr;
+    int *tok_b = nullptr, *pair_src = nullptr, *pair_dst = nullptr, *rec = nullptr;
+};
+void launch_beam_select(hipStream_t s, const BeamSelectArgs& a);
+
 // weights: synthesize (see weights.py) or convert canonical rows into packed rows
 // dst row = (r / blk) * blk * nint + phase * blk + r % blk ; cols copied to [0, cols), dst_ld >= cols
 struct RowMap { int blk, nint, phase; };

@@ -708,6 +708,103 @@ void launch_truncate_partials(hipStream_t s, const float* cand_val, const int* c
                            tr_sum, skip);
 }
 
+// One select step of a beam turn (contract: kernels.h, launch_beam_select).  One wave: thread r * 8 + j owns pool item (r, j) -- the
+// finished hypothesis r itself (j = 0) or child j of the live hypothesis r -- and its place in the new set is the number of items that
+// beat it (score descending, then r, then j ascending: the thread index).  Thread c < n_new then builds hypothesis c from its parent's
+// row of the old state; thread 0 hands out the page sets serially (a child's set depends on the children before it) and writes the record.
+namespace {
+__global__ __launch_bounds__(64) void beam_select_kernel(BeamSelectArgs a) {
+    __shared__ float s_score[64];
+    __shared__ int s_valid[64];
+    __shared__ int s_sel[BEAM_MAX_W];
+    __shared__ int s_live[BEAM_MAX_W];
+    const int tid = threadIdx.x, r = tid >> 3, j = tid & 7;
+    const int n = a.in->n;
+    bool valid = false;
+    float s = -INFINITY;
+    if (r < n) {
+        if (a.in->fin[r]) {
+            valid = j == 0;
+            s = a.in->score[r];
+        } else if (j < a.W && a.list_ids[r * a.W + j] >= 0) {
+            valid = true;
+            s = __fadd_rn(a.in->score[r], a.list_lps[r * a.W + j]);
+        }
+    }
+    valid = valid && s == s;                       // a NaN score has no place in an order: the item is not in the pool (beam_ref.step)
+    s_score[tid] = s; s_valid[tid] = valid;
+    if (tid < BEAM_MAX_W) s_sel[tid] = -1;
+    __syncthreads();
+    int place = 0, n_valid = 0;
+    for (int o = 0; o < 64; ++o) {
+        if (!s_valid[o]) continue;
+        ++n_valid;
+        const float os = s_score[o];
+        place += (os > s || (os == s && o < tid)) ? 1 : 0;
+    }
+    if (valid && place < a.W) s_sel[place] = tid;
+    __syncthreads();
+    const int n_new = n_valid < a.W ? n_valid : a.W;
+    if (tid < BEAM_MAX_W) {
+        int fin = 1;
+        if (tid < n_new) {
+            const int it = s_sel[tid], pr = it >> 3, pj = it & 7;
+            const int len = a.in->len[pr];
+            const int* ii = a.in_ids + (size_t)pr * a.len_cap;
+            const float* il = a.in_lps + (size_t)pr * a.len_cap;
+            int* oi = a.out_ids + (size_t)tid * a.len_cap;
+            float* ol = a.out_lps + (size_t)tid * a.len_cap;
+            for (int k = 0; k < len; ++k) { oi[k] = ii[k]; ol[k] = il[k]; }
+            int nlen = len;
+            if (!a.in->fin[pr]) {
+                const int tok = a.list_ids[pr * a.W + pj];
+                oi[len] = tok; ol[len] = a.list_lps[pr * a.W + pj];
+                nlen = len + 1;
+                fin = nlen >= a.limit;
+                for (int k = 0; k < a.n_eos; ++k) fin |= a.eos[k] == tok;
+            }
+            a.out->len[tid] = nlen; a.out->fin[tid] = fin; a.out->score[tid] = s_score[it];
+        }
+        s_live[tid] = !fin;
+    }
+    __syncthreads();
+    int first = -1, n_live = 0;
+    for (int c = BEAM_MAX_W - 1; c >= 0; --c) if (s_live[c]) { first = c; ++n_live; }
+    if (tid < a.B && first >= 0) {
+        const int c = tid < n_new && s_live[tid] ? tid : first;
+        a.tok_b[tid] = a.out_ids[(size_t)c * a.len_cap + a.out->len[c] - 1];
+    }
+    if (tid == 0) {
+        unsigned held = 0, claimed = 0;
+        int n_rows = 0, np = 0;
+        for (int q = 0; q < n; ++q) { held |= 1u << a.in->set_of[q]; n_rows += a.in->fin[q] ? 0 : 1; }
+        for (int c = 0; c < BEAM_MAX_W; ++c) {
+            if (c >= n_new) { a.rec[4 + c] = -1; a.rec[4 + BEAM_MAX_W + c] = -1; a.rec[4 + 2 * BEAM_MAX_W + c] = -1; continue; }
+            const int it = s_sel[c], src = a.in->set_of[it >> 3];
+            int dst = src;
+            if ((claimed >> src) & 1u) {
+                dst = __ffs((int)(~(held | claimed) & 0xFFFFu)) - 1;       // 16 sets, at most 8 held and 7 taken: one is always left
+                for (int i = 0; i < a.n_cp; ++i) {
+                    a.pair_src[np] = a.set_pages[src * a.set_stride + i];
+                    a.pair_dst[np] = a.set_pages[dst * a.set_stride + i];
+                    ++np;
+                }
+            }
+            claimed |= 1u << dst;
+            a.out->set_of[c] = dst;
+            a.rec[4 + c] = it >> 3; a.rec[4 + BEAM_MAX_W + c] = it & 7; a.rec[4 + 2 * BEAM_MAX_W + c] = dst;
+        }
+        a.out->n = n_new;
+        a.rec[0] = n_new; a.rec[1] = n_live; a.rec[2] = n_rows; a.rec[3] = np;
+    }
+}
+}  // namespace
+void launch_beam_select(hipStream_t s, const BeamSelectArgs& a) {
+    if (a.W < 1 || a.W > BEAM_MAX_W || a.B < 1 || a.B > 64 || a.limit < 1 || a.limit > a.len_cap || a.n_cp < 0 || a.n_cp > BEAM_CP_MAX || a.n_eos < 0)
+        throw std::runtime_error("beam select: W must be 1 .. 8, limit 1 .. len_cap, n_cp 0 .. 8");
+    hipLaunchKernelGGL(beam_select_kernel, dim3(1), dim3(64), 0, s, a);
+}
+
 #define SVLN_INST(T)                                                                                                              \
     template void launch_rmsnorm<T>(hipStream_t, const void*, const void*, void*, int, int, float, const int*, void*, const int*, int);                              \
     template void launch_rmsnorm_indexed<T>(hipStream_t, const void*, const void*, void*, const int*, const int*, void*, int, int, float);                          \

@@ -583,7 +583,7 @@ class StreamVLNForCausalLM:
 
     @torch.no_grad()
     def generate(self, inputs=None, images=None, image_sizes=None, depths=None, poses=None, intrinsics=None, task_ids=None,
-                 draft_ids=None, forced_ids=None, candidate_ids=None, **kwargs):
+                 draft_ids=None, forced_ids=None, candidate_ids=None, beam_width=None, **kwargs):
         """One model turn = ONE crossing into the engine (svln_turn: encode_rgbd, the KV / embeds bookkeeping of the reference's generate,
         splice, prefill + greedy decode).  draft_ids (optional, set_speculative / set_prefill_draft): a guess of this turn's whole id sequence; with
         set_auto_draft(True) and no explicit draft, the env's previous turn output is the guess.
@@ -593,8 +593,11 @@ class StreamVLNForCausalLM:
         must follow); absent or 1: this path, launch for launch; a greedy call leaves the key unread.
         forced_ids (1 .. 32 ids): a forced turn -- the turn's ids are the caller's (see _generate_forced); `max_new_tokens` is not read.
         candidate_ids (2 .. 8 id lists of 1 .. 32 ids): the candidates are scored against ONE prefill of the prompt (see
-        _generate_candidates for the result, select_sequence for what must follow); `max_new_tokens` is not read."""
+        _generate_candidates for the result, select_sequence for what must follow); `max_new_tokens` is not read.
+        beam_width (1 .. 8): a beam turn -- the beam_width most probable turns of the prompt (see _generate_beams for the result,
+        select_sequence for what must follow); HF's `num_beams` stays refused."""
         draft = draft_ids
+        W = self._beam_request(beam_width, forced_ids, candidate_ids, kwargs)
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
         n_seq = self._num_return_sequences(kwargs)
         if forced_ids is not None and n_seq > 1:
@@ -606,8 +609,10 @@ class StreamVLNForCausalLM:
         self._sync_call_config()
         held = self._sampling
         self._sync_sampling(kwargs)
-        if forced_ids is not None or candidate_ids is not None or n_seq > 1:
+        if W or forced_ids is not None or candidate_ids is not None or n_seq > 1:
             try:
+                if W:
+                    return self._generate_beams(W, inputs, ids, pix, V, n_memory, env_id, past, max_new, eos)
                 if candidate_ids is not None:
                     return self._generate_candidates(candidate_ids, inputs, ids, pix, V, n_memory, env_id, past, eos)
                 if forced_ids is not None:
@@ -796,7 +801,86 @@ class StreamVLNForCausalLM:
         return g
 
     @staticmethod
+    def _beam_request(beam_width, forced_ids, candidate_ids, kwargs) -> int:
+        """`beam_width` of a generate call: None = no beam turn (0); 1 .. 8 = the width; the combinations a beam turn does not have raise"""
+        if beam_width is None:
+            return 0
+        W = int(beam_width)
+        if not (1 <= W <= 8):
+            raise ValueError(f"beam_width={beam_width!r}: a beam turn keeps 1 .. 8 hypotheses")
+        if forced_ids is not None:
+            raise NotImplementedError("beam_width together with forced_ids: a forced turn's ids are the caller's, a beam turn's the policy's")
+        if candidate_ids is not None:
+            raise NotImplementedError("beam_width together with candidate_ids: a candidates call scores given turns, a beam turn finds them")
+        if kwargs.get("do_sample", False):
+            raise NotImplementedError("beam_width together with do_sample=True: beams are greedy (no beam sampling on the path)")
+        g = kwargs.get("num_return_sequences")
+        if g is not None and int(g) > 1:
+            raise NotImplementedError(f"beam_width together with num_return_sequences={g!r}: a beam turn returns its whole set")
+        return W
+
+    def _generate_beams(self, W, inputs, ids, pix, V, n_memory, env_id, past, max_new, eos):
+        """generate(..., beam_width=W): ONE vision pass, ONE prefill and one batched decode phase for at most W hypotheses (svln_turn_beams).
+        The result is shaped like a group turn's: `sequences` int64 [n, n_max] in rank order (n <= W; padded like a group's),
+        `sequence_lengths` [n], `token_logprobs` fp32 [n, n_max] (pad 0), `sequences_scores` fp32 [n] (the fp32 sum of a row's
+        log-probabilities, no length penalty), `past_key_values` None: select_sequence(index, env_id) must follow.  The pages of every
+        hypothesis are reserved up front: pass the max_new_tokens the turn really needs (see _generate_group)."""
+        if past is not None and (not isinstance(past, KVHandle) or past.env_id != env_id or past.epoch != self._epoch[env_id]):
+            raise ValueError("past_key_values does not belong to this env's current window")
+        slot = self._slot(env_id)
+        on_dev = int(pix.is_cuda)
+        ids_np = np.ascontiguousarray(ids.numpy())
+        eos_np = np.asarray(eos, dtype=np.int64)
+        cap = min(max_new, self.cfg.max_positions)
+        out, n_out, sc = np.zeros((W, cap), dtype=np.int64), np.zeros(W, dtype=np.int32), np.zeros(W, dtype=np.float32)
+        a = _lib.SvlnTurnArgs()
+        a.pixels, a.n_frames, a.pixels_on_device, a.env = pix.data_ptr(), V, on_dev, slot
+        a.ids, a.n_ids, a.n_memory = ids_np.ctypes.data, ids_np.size, n_memory
+        a.new_window, a.new_episode, a.max_new_tokens = int(past is None), int(self.curr_t[env_id] == 0), max_new
+        a.eos_ids, a.n_eos = eos_np.ctypes.data, eos_np.size
+        if on_dev:
+            self._order_engine_after(pix)
+        rc = self._lib.svln_turn_beams(self._h, C.byref(a), W, out.ctypes.data_as(C.POINTER(C.c_int64)), cap,
+                                       n_out.ctypes.data_as(C.POINTER(C.c_int32)), sc.ctypes.data_as(C.POINTER(C.c_float)))
+        if on_dev:
+            self._order_torch_after(pix)
+        _check(rc)
+        self.curr_t[env_id] += 1
+        n = int((n_out > 0).sum())
+        self._group_pending[env_id] = n
+        dev = inputs.device if isinstance(inputs, torch.Tensor) else "cpu"
+        lens = [int(v) for v in n_out[:n]]
+        n_max = max(lens)
+        pad = getattr(self.generation_config, "pad_token_id", None)
+        if pad is None:
+            pad = eos[0] if len(eos) else 0
+        seq, lp = np.full((n, n_max), int(pad), dtype=np.int64), np.zeros((n, n_max), dtype=np.float32)
+        buf, m = np.empty(n_max, dtype=np.float32), C.c_int32()
+        for g in range(n):
+            seq[g, : lens[g]] = out[g, : lens[g]]
+            _check(self._lib.svln_group_logprobs(self._h, g, buf.ctypes.data_as(C.POINTER(C.c_float)), n_max, C.byref(m)))
+            if m.value != lens[g]:
+                raise RuntimeError(f"the engine holds {m.value} token scores for a hypothesis of {lens[g]} ids")
+            lp[g, : lens[g]] = buf[: lens[g]]
+        res = GenerateOutput(sequences=torch.from_numpy(seq).to(dev), sequence_lengths=torch.tensor(lens, dtype=torch.int64, device=dev),
+                             past_key_values=None)
+        res["token_logprobs"] = torch.from_numpy(lp).to(dev)
+        res["sequences_scores"] = torch.from_numpy(sc[:n].copy()).to(dev)
+        return res
+
+    def beam_trace(self):
+        """test tap: the steps of the last beam turn -> (W, list_ids int32 [steps, 8, 8], list_lps fp32 [steps, 8, 8], records int32 [steps, 28])"""
+        cap = self.cfg.max_positions
+        li, ll, rec = np.zeros((cap, 8, 8), dtype=np.int32), np.zeros((cap, 8, 8), dtype=np.float32), np.zeros((cap, 28), dtype=np.int32)
+        ns, w = C.c_int32(), C.c_int32()
+        _check(self._lib.svln_beam_trace(self._h, cap, C.byref(ns), C.byref(w), li.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         ll.ctypes.data_as(C.POINTER(C.c_float)), rec.ctypes.data_as(C.POINTER(C.c_int32))))
+        return w.value, li[: ns.value].copy(), ll[: ns.value].copy(), rec[: ns.value].copy()
+
+    @staticmethod
     def _reject_group_request(kwargs, who):
+        if kwargs.get("beam_width") is not None:
+            raise NotImplementedError(f"beam_width in a {who} request: beam turns run through generate() only")
         if kwargs.get("forced_ids") is not None:
             raise NotImplementedError(f"forced_ids in a {who} request: forced turns run through generate() only")
         if kwargs.get("candidate_ids") is not None:
@@ -1060,6 +1144,8 @@ class StreamVLNForCausalLM:
             raise NotImplementedError(f"num_return_sequences={g!r} in a submit_forced request: a forced turn has one sequence")
         if kwargs.get("candidate_ids") is not None:
             raise NotImplementedError("candidate_ids in a submit_forced request: candidates are scored through generate() only")
+        if kwargs.get("beam_width") is not None:
+            raise NotImplementedError("beam_width in a submit_forced request: beam turns run through generate() only")
         f_np = self._forced_array(forced_ids)
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
         if any(v[0] == env_id for v in self._tickets.values()):
