@@ -456,6 +456,44 @@ int svln_set_decode_persistent(svln_engine* h, int enable);
  * [6] down_proj done, [7] edge 3 gathered, [8] q|k|v done (consumer wave 0); [10..14] the loader at the start / after each product's
  * stream.  Runs on whatever the engine's buffers hold (after a decode step); overwrites the residual row and the q|k|v buffer. */
 int svln_probe_decode_layer(svln_engine* h, int layer, unsigned long long* out, int max_wgs, int32_t* n_wgs);
+/* Test hook: ONE launch of the persistent decode layer kernel with `cus` workgroups on the caller's device buffers, then a
+ * synchronisation.  Nothing of the engine's own persistent-layer state is used: granules, launch counter and give-up word are the
+ * caller's.  T = the engine dtype; qd = n_q * 128.  Refused by error, WITHOUT a launch, when the shape is outside what
+ * svln_decode_layer_supported admits or when cus exceeds the device's CU count (every workgroup must be resident at once).
+ * Buffer layouts (all device memory):
+ *   o_w [H][qd], gu_w [2 I][H] in the EPI_SWIGLU packing (64-row blocks = [gate 32 | up 32]), down_w [H][I], next_qkv_w [qkv_dim][H],
+ *   all T, rows dense; post_norm [H], next_norm [H], next_qkv_b [qkv_dim] T.  next_norm / next_qkv_w null = last layer (qkv_out and
+ *   gran[3] are then not touched); next_qkv_b may be null.
+ *   part    float [nsplit][n_kv][32][132]: per split and q head (kv head kh, q head rho of it at row kh * 32 + rho) 128 un-normalised
+ *           outputs, then m (log2 domain) at [128] and l at [129]; splits at or past ceil(ceil(*kv_len / 64) / tiles_per_split) are
+ *           not read
+ *   kv_len  int32 [1];  skip: optional int32 [1], the launch is a no-op when it is non-zero
+ *   x       T [H]: residual row in, layer output out;  qkv_out T [qkv_dim]
+ *   gran[e] uint64 [n_e / VPG], n = {qd, H, I, H}, VPG = 2 (bf16) or 1 (fp32) values per granule: bits 63..32 the tag
+ *           *seq * 4 + e + 1 of the launch that wrote it, bits 31..0 the payload (bf16: value 2g in bits 15..0, value 2g + 1 in bits
+ *           31..16; fp32: the value's bits); a granule whose tag is not this launch's is never consumed
+ *   seq     uint32 [1]: launch counter, read at the start, + 1 at the end;  giveup uint32 [1]: 0, or the code of a spin that timed out */
+typedef struct svln_decode_layer_op {
+    const void *o_w, *post_norm, *gu_w, *down_w, *next_norm, *next_qkv_w, *next_qkv_b;
+    const float* part; const int32_t* kv_len; const int32_t* skip;
+    void *x, *qkv_out;
+    uint64_t* gran[4]; uint32_t* seq; uint32_t* giveup;
+    int32_t nsplit, tiles_per_split, n_q, n_kv, H, I, qkv_dim, cus;
+    float eps;
+} svln_decode_layer_op;
+int svln_op_decode_layer(svln_engine* h, const svln_decode_layer_op* op);
+/* host only, no engine: *supported = whether the persistent layer kernel covers (H, I, qd, qkv_dim) with `cus` workgroups */
+int svln_decode_layer_supported(int dtype, int H, int I, int qd, int qkv_dim, int cus, int32_t* supported);
+/* host only, no engine: how the persistent layer kernel deals one product's weight blocks (1 KiB each) to its 8 waves.  `op`: this
+ * workgroup's share, nrows stream rows of K elements of elem_size bytes from output index `first` (pair: rows are gate j, up j of the
+ * EPI_SWIGLU packing); `next`: the product whose first 16 slots refill the last group (the same op after the last product).  For one
+ * wave and lane: slots[k], k < *n_slots: load_off = the byte offset (from the start of the weight matrix) of the load that filled
+ * the register slot k consumes; valid / row / pb = whether slot k is computed and which (stream row, block of the row) it is;
+ * row_done = the wave's partial sum of that row is complete after it.  refill[16]: the offsets in `next` loaded by the last group. */
+typedef struct svln_decode_layer_walk_op { int32_t elem_size, K, nrows, pair, first; } svln_decode_layer_walk_op;
+typedef struct svln_decode_layer_slot { int64_t load_off; int32_t valid, row, pb, row_done; } svln_decode_layer_slot;
+int svln_decode_layer_walk(const svln_decode_layer_walk_op* op, const svln_decode_layer_walk_op* next, int wave, int lane,
+                           svln_decode_layer_slot* slots, int max_slots, int32_t* n_slots, int64_t* refill);
 /* Opt-in, no reference counterpart: the single-env decode step and the lm_head stream OCP e4m3 copies of the LLM
  * weights (one fp32 scale per output row; allocated and quantised on the device at the first enable, quantised again whenever
  * svln_set_tensor / svln_synth_tensor writes one of the matrices) instead of the bf16 ones -- half the HBM bytes per generated token.  bf16 engines only; prefill, vision and svln_generate_batch keep bf16 weights (the

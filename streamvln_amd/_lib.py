@@ -56,6 +56,22 @@ class SvlnGemmPlan(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("nt_w", "bn_fast", "n_launches", "fused", "vit_packer")] + [("launch", SvlnGemmLaunch * 2)]
 
 
+class SvlnDecodeLayerOp(C.Structure):
+    """svln_decode_layer_op of include/streamvln_hip.h"""
+    _fields_ = [(n, C.c_void_p) for n in ("o_w", "post_norm", "gu_w", "down_w", "next_norm", "next_qkv_w", "next_qkv_b", "part", "kv_len", "skip",
+                                          "x", "qkv_out")] + \
+               [("gran", C.c_void_p * 4), ("seq", C.c_void_p), ("giveup", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("nsplit", "tiles_per_split", "n_q", "n_kv", "H", "I", "qkv_dim", "cus")] + [("eps", C.c_float)]
+
+
+class SvlnDecodeLayerWalkOp(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("elem_size", "K", "nrows", "pair", "first")]
+
+
+class SvlnDecodeLayerSlot(C.Structure):
+    _fields_ = [("load_off", C.c_int64)] + [(n, C.c_int32) for n in ("valid", "row", "pb", "row_done")]
+
+
 GEMM_TILES = ("skinny", "c64", "c128", "c128L", "c128K2", "c256", "c256n64", "big", "p8", "p8_32")      # svln_gemm_launch.tile
 GEMM_FORCE_FP8_SCALED = 0x40000        # force_cfg bit of svln_op_gemm_fp8: the block-scaled MFMA form (svln_set_fp8_scaled_mfma)
 GEMM_REDUCERS = (None, "epilogue", "rownorm", "qkv_rope", "vitpack")                                     # svln_gemm_launch.reducer
@@ -158,6 +174,10 @@ SIGNATURES = {
     "svln_set_decode_graph": (_I, [_P, _I]),
     "svln_set_decode_persistent": (_I, [_P, _I]),
     "svln_probe_decode_layer": (_I, [_P, _I, C.POINTER(C.c_uint64), _I, _PI32]),
+    "svln_op_decode_layer": (_I, [_P, C.POINTER(SvlnDecodeLayerOp)]),
+    "svln_decode_layer_supported": (_I, [_I, _I, _I, _I, _I, _I, _PI32]),
+    "svln_decode_layer_walk": (_I, [C.POINTER(SvlnDecodeLayerWalkOp), C.POINTER(SvlnDecodeLayerWalkOp), _I, _I, C.POINTER(SvlnDecodeLayerSlot), _I,
+                                    _PI32, _PI64]),
     "svln_set_fp8_decode": (_I, [_P, _I]),
     "svln_set_fp8_gemm": (_I, [_P, _I]),
     "svln_set_fp8_scaled_mfma": (_I, [_P, _I]),

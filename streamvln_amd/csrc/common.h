@@ -19,6 +19,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #define SVLN_DEV __device__ __forceinline__
+#define SVLN_HD __host__ __device__ __forceinline__        // also host code: the dealing logic of decode_layer_walk.h
 
 struct fp8_t { uint8_t v; };        // OCP e4m3 storage (operands of the opt-in fp8 MFMA products; never an output type)
 template <typename T> struct Elt;
@@ -256,7 +257,7 @@ SVLN_DEV float gelu_erf_f(float x) {       // nn.GELU()  (multimodal_projector/b
 SVLN_DEV float silu_f(float x) { return x * sigmoid_f(x); }
 
 // EPI_SWIGLU weight packing: 64-row blocks = [gate 32 | up 32].  The gate row of output j; its up row lies 32 further.
-SVLN_DEV size_t swiglu_gate_row(int j) { return (size_t)(j >> 5) * 64 + (j & 31); }
+SVLN_HD size_t swiglu_gate_row(int j) { return (size_t)(j >> 5) * 64 + (j & 31); }
 
 // ---- synthetic weights: identical arithmetic to streamvln_amd/weights.py ---------------------
 SVLN_DEV uint64_t splitmix64(uint64_t z) {

@@ -28,6 +28,7 @@
 #include <hip/hip_ext.h>
 
 #include "common.h"
+#include "decode_layer_walk.h"
 #include "kernels.h"
 
 namespace svln {
@@ -39,75 +40,11 @@ typedef __attribute__((address_space(1))) unsigned long long gu64;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 #define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-constexpr int BLK = 1024;                       // bytes one wave instruction moves (64 lanes x 16 B)
-constexpr int NW = 8, NTHREADS = 64 * NW;       // waves per workgroup: all of them stream and compute
-constexpr int PF = 16;                          // blocks in flight per wave (16 KB: 128 KB per CU; 24 measured slower -- 230 VGPRs -- and 32 no longer unrolls into registers)
-constexpr int ROWMODE_MAX_BPR = 15;             // rows of at most this many blocks go to one wave whole
+constexpr int NTHREADS = 64 * NW;
 constexpr unsigned SPIN_LIMIT = 50000u;
 constexpr size_t LDS_FLOOR = 100 * 1024;        // dynamic LDS requested at least: two workgroups never share a CU
 
-struct Op {            // one product as this CU sees it
-    const char* W; size_t ld_bytes;      // weight matrix, row pitch in bytes
-    int bpr;                             // 1 KiB blocks per row
-    int nrows, pair, first;              // stream rows; pair: rows come as (gate j, up j) of the [gate 32 | up 32] packing; first output index
-    int nblk;                            // blocks of this CU's share
-    int ch;                              // blocks dealt to a wave at a time: bpr (whole rows) or 1
-    int bm;                              // block mode: rows longer than ROWMODE_MAX_BPR blocks, dealt block by block (ch = 1)
-};
-
-SVLN_DEV size_t op_row(const Op& o, int j) {                   // matrix row of stream row j
-    if (!o.pair) return (size_t)(o.first + j);
-    return swiglu_gate_row(o.first + (j >> 1)) + (j & 1) * 32;
-}
-// slots of wave w in op o (chunks of o.ch blocks dealt round-robin), rounded up to whole groups of PF
-SVLN_DEV int op_slots(const Op& o, int w) {
-    const int nchunk = (o.nblk + o.ch - 1) / o.ch;
-    const int mine = nchunk > w ? (nchunk - w + NW - 1) / NW : 0;
-    const int ns = (mine * o.ch + PF - 1) / PF * PF;
-    return ns < PF ? PF : ns;            // at least one group, even without work: the last group of an op is where the next op's first PF slots are loaded
-}
-// Walking the slots of one wave through one op.  Row mode (o.ch == o.bpr): a chunk is one stream row, rows w, w + NW, ...; block mode
-// (o.ch == 1, rows longer than ROWMODE_MAX_BPR blocks, stored back to back): blocks w, w + NW, ... of the CU's contiguous share.
-// LoadCur yields the source address of every slot (a padding slot re-reads the op's first block); CompCur says which (row, block) a
-// slot is and when a row's partial sum is complete.
-struct LoadCur {
-    const char* ptr; int kc, row, gb;
-    SVLN_DEV const char* row_ptr(const Op& o, int r, int lane) const { return o.W + op_row(o, r < o.nrows ? r : 0) * o.ld_bytes + lane * 16; }
-    SVLN_DEV void start(const Op& o, int w, int lane) {
-        kc = 0; row = w; gb = w;
-        ptr = o.bm ? (w < o.nblk ? o.W + (size_t)o.first * o.ld_bytes + (size_t)w * BLK + lane * 16 : o.W + lane * 16) : row_ptr(o, w, lane);
-    }
-    SVLN_DEV void next(const Op& o, int lane) {
-        if (o.bm) {
-            gb += NW;
-            ptr = gb < o.nblk ? ptr + (size_t)NW * BLK : o.W + (size_t)o.first * o.ld_bytes + lane * 16;
-        } else if (++kc == o.ch) {
-            kc = 0; row += NW;
-            ptr = row_ptr(o, row, lane);
-        } else {
-            ptr += BLK;
-        }
-    }
-};
-struct CompCur {
-    int kc, row, pb, gb;
-    SVLN_DEV void start(const Op& o, int w) {
-        kc = 0; gb = w;
-        if (o.bm) { row = w / o.bpr; pb = w - row * o.bpr; } else { row = w; pb = 0; }
-    }
-    SVLN_DEV bool valid(const Op& o) const { return o.bm ? gb < o.nblk : row < o.nrows; }
-    // returns true when the slot just consumed was the last one of its row FOR THIS WAVE (its partial sum is complete)
-    SVLN_DEV bool next(const Op& o) {
-        if (o.bm) {
-            gb += NW; pb += NW;
-            if (pb >= o.bpr) { pb -= o.bpr; ++row; return true; }
-            return false;
-        }
-        if (++kc == o.ch) { kc = 0; row += NW; pb = 0; return true; }
-        ++pb;
-        return false;
-    }
-};
+// (BLK, NW, PF, ROWMODE_MAX_BPR, Op, op_row, op_slots, LoadCur, CompCur: decode_layer_walk.h)
 
 template <typename T> struct Gran;       // payload of one 8-byte granule: two bf16 values, or one fp32 value
 template <> struct Gran<bf16> {
@@ -184,6 +121,8 @@ __global__ __launch_bounds__(NTHREADS) void decode_layer_kernel(DecodeLayerArgs 
     // One product: this wave walks its slots in groups of PF; slot k is computed from buf[k % PF], which is then refilled with slot k + PF --
     // of this op, or, in the last group, of the NEXT op (its first PF slots: what `prefetch` would load).  xt: the input vector is T values
     // in `hvec` (down_proj) instead of fp32 planes in `xs`.  A row's partial sum (this wave's blocks of it) goes to part[row][wave].
+    // (The slot order of `prefetch` + this loop is restated on the host in decode_layer_walk() at the bottom of this file -- what
+    //  svln_decode_layer_walk returns and tests/test_decode_layer_walk.py checks; keep the two in step.)
     auto product = [&](const Op& o, const Op& rf, bool xt) {      // rf: the op whose first PF slots refill the last group (the next op; o itself after the last)
         const int ns = op_slots(o, wave), nch = o.bpr * 64;
         CompCur cc; cc.start(o, wave);
@@ -448,6 +387,58 @@ void decode_layer_init_attrs() {
     set_max_lds((const void*)decode_layer_kernel<bf16>, 160 * 1024, NTHREADS);
     set_max_lds((const void*)decode_layer_kernel<float>, 160 * 1024, NTHREADS);
 }
+// Host restatement of the slot loop of `prefetch` + `product` above (the cursors themselves are shared: decode_layer_walk.h) for one
+// wave and lane of one op: what svln_decode_layer_walk returns.  Keep the two in step; tests/test_decode_layer_gpu.py is the check that
+// the kernel does what this walk says.  Offsets are bytes from the start of the op's weight matrix.
+namespace {
+Op walk_op(const DecodeLayerWalkOp& d, const char* base) {          // the kernel's `mk`
+    Op o;
+    o.W = base; o.ld_bytes = (size_t)d.K * d.elem_size; o.bpr = d.K * d.elem_size / BLK;
+    o.nrows = d.nrows; o.pair = d.pair; o.first = d.first; o.nblk = d.nrows * o.bpr; o.bm = o.bpr > ROWMODE_MAX_BPR ? 1 : 0; o.ch = o.bm ? 1 : o.bpr;
+    return o;
+}
+}  // namespace
+int decode_layer_walk(const DecodeLayerWalkOp& od, const DecodeLayerWalkOp& rd, int wave, int lane, DecodeLayerWalkSlot* out, int max_slots,
+                      int64_t* refill) {
+    static char anchor;                                                // offsets are differences against it; nothing is read
+    const char* base = &anchor;
+    const Op o = walk_op(od, base), rf = walk_op(rd, base);
+    const int ns = op_slots(o, wave);
+    if (ns > max_slots) return -ns;
+    {   // `prefetch`
+        LoadCur lc; lc.start(o, wave, lane);
+        for (int j = 0; j < PF; ++j) {
+            out[j].load_off = lc.ptr - base;
+            lc.next(o, lane);
+        }
+    }
+    CompCur cc; cc.start(o, wave);
+    LoadCur lc; lc.start(o, wave, lane);
+    for (int j = 0; j < PF; ++j) lc.next(o, lane);
+    auto slot = [&](int k) {
+        out[k].valid = cc.valid(o) ? 1 : 0;
+        out[k].row = cc.row; out[k].pb = cc.pb;
+        out[k].row_done = cc.next(o) ? 1 : 0;
+    };
+    int k0 = 0;
+    for (; k0 + PF < ns; k0 += PF) {
+        for (int j = 0; j < PF; ++j) {
+            const char* src = lc.ptr;
+            lc.next(o, lane);
+            slot(k0 + j);
+            out[k0 + j + PF].load_off = src - base;
+        }
+    }
+    LoadCur nc; nc.start(rf, wave, lane);
+    for (int j = 0; j < PF; ++j) {
+        const char* src = nc.ptr;
+        nc.next(rf, lane);
+        slot(k0 + j);
+        refill[j] = src - base;
+    }
+    return ns;
+}
+
 template bool decode_layer_supported<bf16>(const DecodeLayerArgs&, int);
 template bool decode_layer_supported<float>(const DecodeLayerArgs&, int);
 template void launch_decode_layer<bf16>(hipStream_t, const DecodeLayerArgs&, int, hipEvent_t, hipEvent_t);

@@ -165,6 +165,7 @@ struct EngineBase {
     virtual void set_graph(int enable) = 0;
     virtual void set_decode_persistent(int enable) = 0;
     virtual void probe_decode_layer(int layer, unsigned long long* out, int max_wgs, int32_t* n_wgs) = 0;
+    virtual void op_decode_layer(const svln_decode_layer_op& q) = 0;
     virtual void set_fp8_decode(int enable) = 0;
     virtual void set_fp8_gemm(int enable) = 0;
     virtual void set_fp8_scaled_mfma(int enable) = 0;
@@ -1470,6 +1471,28 @@ public:
         HIP_CHECK(hipStreamSynchronize(st));
         HIP_CHECK(hipFree(d));
         *n_wgs = n;
+    }
+    // svln_op_decode_layer: ONE persistent launch on the caller's buffers (granules, seq and give-up word included: not the engine's)
+    void op_decode_layer(const svln_decode_layer_op& q) override {
+        REQUIRE(q.o_w && q.post_norm && q.gu_w && q.down_w && q.part && q.kv_len && q.x && q.seq && q.giveup, "null pointer");
+        for (int k = 0; k < 4; ++k) REQUIRE(q.gran[k] != nullptr, "null granule buffer");
+        const bool has_next = q.next_qkv_w != nullptr;
+        REQUIRE(has_next == (q.next_norm != nullptr) && (has_next || !q.next_qkv_b), "next_norm / next_qkv_w come together; a bias needs them");
+        REQUIRE(!has_next || q.qkv_out, "null pointer");
+        REQUIRE(q.n_q >= 1 && q.n_kv >= 1 && q.n_q % q.n_kv == 0 && q.n_q / q.n_kv <= 32, "heads: n_q a multiple of n_kv, at most 32 q heads per kv head");
+        REQUIRE(q.nsplit >= 1 && q.tiles_per_split >= 1 && q.H >= 1 && q.I >= 1 && q.qkv_dim >= 1, "extent");
+        DecodeLayerArgs a; std::memset(&a, 0, sizeof(a));
+        a.part = q.part; a.nsplit = q.nsplit; a.tiles_per_split = q.tiles_per_split; a.dyn_kv_len = q.kv_len; a.n_kv = q.n_kv; a.Gq = q.n_q / q.n_kv;
+        a.o_w = q.o_w; a.post_norm = q.post_norm; a.gu_w = q.gu_w; a.down_w = q.down_w;
+        a.next_norm = q.next_norm; a.next_qkv_w = q.next_qkv_w; a.next_qkv_b = q.next_qkv_b;
+        a.x = q.x; a.qkv_out = q.qkv_out; a.H = q.H; a.I = q.I; a.qd = q.n_q * 128; a.qkv_dim = q.qkv_dim; a.eps = q.eps;
+        for (int k = 0; k < 4; ++k) a.gran[k] = (unsigned long long*)q.gran[k];
+        a.seq = q.seq; a.giveup = q.giveup; a.skip = q.skip;
+        REQUIRE(q.cus >= 1 && decode_layer_supported<T>(a, q.cus), "persistent decode layer: this configuration is not supported");
+        hipDeviceProp_t pr; HIP_CHECK(hipGetDeviceProperties(&pr, device));
+        REQUIRE(q.cus <= pr.multiProcessorCount, "persistent decode layer: more workgroups than CUs (all of them must be resident)");
+        launch_decode_layer<T>(st, a, q.cus);
+        HIP_CHECK(hipStreamSynchronize(st));
     }
     bool persistent_active() const { return persistent_on && !fp8_on && !mx4_on; }       // (the e4m3 / MXFP4 decode weights keep the launched GEMVs)
     int probe_op() const { return persistent_active() ? 3 : 1 + 4; }          // the launch the roofline probe times (layer 0)
@@ -5376,6 +5399,37 @@ int svln_op_gemm_norm_q8(svln_engine* h, const void* A, int lda, const void* W, 
     a.norm_q8 = q8; a.norm_q8_scale = q8_scale; a.pen = 1.0f;
     const bool f = h->impl->op_gemm(a);
     if (fused) *fused = f ? 1 : 0;
+    API_END
+}
+int svln_op_decode_layer(svln_engine* h, const svln_decode_layer_op* op) {
+    API_BEGIN_H REQUIRE(op, "null argument"); h->impl->op_decode_layer(*op); API_END
+}
+int svln_decode_layer_supported(int dtype, int H, int I, int qd, int qkv_dim, int cus, int32_t* supported) {
+    API_BEGIN
+    REQUIRE(supported, "null argument");
+    REQUIRE(dtype == SVLN_BF16 || dtype == SVLN_F32, "dtype: SVLN_BF16 or SVLN_F32");
+    DecodeLayerArgs a; std::memset(&a, 0, sizeof(a));
+    a.H = H; a.I = I; a.qd = qd; a.qkv_dim = qkv_dim;
+    *supported = (dtype == SVLN_BF16 ? decode_layer_supported<bf16>(a, cus) : decode_layer_supported<float>(a, cus)) ? 1 : 0;
+    API_END
+}
+int svln_decode_layer_walk(const svln_decode_layer_walk_op* op, const svln_decode_layer_walk_op* next, int wave, int lane,
+                           svln_decode_layer_slot* slots, int max_slots, int32_t* n_slots, int64_t* refill) {
+    API_BEGIN
+    REQUIRE(op && next && slots && n_slots && refill, "null argument");
+    static_assert(sizeof(svln_decode_layer_slot) == sizeof(DecodeLayerWalkSlot), "slot layout");
+    for (const svln_decode_layer_walk_op* d : {op, next}) {
+        REQUIRE(d->elem_size == 2 || d->elem_size == 4, "element size: 2 or 4");
+        REQUIRE(d->K >= 1 && d->K <= (1 << 24) && (int64_t)d->K * d->elem_size % 1024 == 0, "rows must be whole KiB");
+        REQUIRE(d->nrows >= 0 && d->nrows <= (1 << 16) && d->first >= 0 && d->first <= (1 << 24), "nrows / first out of range");
+        const int64_t bpr = (int64_t)d->K * d->elem_size / 1024;
+        REQUIRE(d->pair == 0 || (d->pair == 1 && d->nrows % 2 == 0 && bpr <= 15), "pair: 0, or 1 on an even number of whole-row-dealt rows");
+    }
+    REQUIRE(wave >= 0 && wave < 8 && lane >= 0 && lane < 64, "wave < 8, lane < 64");
+    const DecodeLayerWalkOp o{op->elem_size, op->K, op->nrows, op->pair, op->first}, r{next->elem_size, next->K, next->nrows, next->pair, next->first};
+    const int ns = decode_layer_walk(o, r, wave, lane, (DecodeLayerWalkSlot*)slots, max_slots, refill);
+    REQUIRE(ns > 0, "max_slots too small");
+    *n_slots = ns;
     API_END
 }
 int svln_gemm_plan(const svln_gemm_problem* q, svln_gemm_plan_out* out) {

@@ -346,6 +346,12 @@ struct DecodeLayerArgs {
 template <typename T> bool decode_layer_supported(const DecodeLayerArgs& a, int cus);
 template <typename T> void launch_decode_layer(hipStream_t s, const DecodeLayerArgs& a, int cus, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 void decode_layer_init_attrs();
+// Host only (svln_decode_layer_walk): the slot sequence of one wave and lane through one op, as `prefetch` + `product` order it.
+struct DecodeLayerWalkOp { int elem_size, K, nrows, pair, first; };
+struct DecodeLayerWalkSlot { int64_t load_off; int32_t valid, row, pb, row_done; };      // = svln_decode_layer_slot
+// Returns the slot count ns (out[0 .. ns) filled, refill[0 .. PF) = offsets in `next` loaded by the last group); -ns if ns > max_slots.
+int decode_layer_walk(const DecodeLayerWalkOp& op, const DecodeLayerWalkOp& next, int wave, int lane, DecodeLayerWalkSlot* out, int max_slots,
+                      int64_t* refill);
 
 // RMSNorm / LayerNorm over rows of length n (T in, T out).
 // y2 / y2_row / y2_cap: optional second copy of the rows at row *y2_row (device scalar) of y2, clamped to y2_cap rows
