@@ -418,8 +418,14 @@ public:
     // through the EPI_TARGET lm_head in chunks of <= 32; every list is sized for MAXB jobs of BFORCED_MAX ids (+ 8: the pad rows of the last
     // chunk's row count), so no job waits for head space.  Allocated by the first forced submit.
     T* bf_xn = nullptr;
-    int *bf_dev_i = nullptr, *bf_host_i = nullptr;               // [src | tap | tgt | tok] x (BFORCED_ROWS + 8): device / pinned
-    float *bf_dev_f = nullptr, *bf_host_f = nullptr;             // [val | score | lp] x (BFORCED_ROWS + 8)
+    // the lists of the target head, BFORCED_ROWS + 8 entries each, cut from one int and one float block: source row, tap row, target id,
+    // greedy id / capture slot, greedy log-probability, target log-probability
+    struct HeadLists {
+        static constexpr int R = BFORCED_ROWS + 8;
+        int *src = nullptr, *tap = nullptr, *tgt = nullptr, *tok = nullptr; float *val = nullptr, *score = nullptr, *lp = nullptr;
+        void cut(int* i, float* f) { src = i; tap = i + R; tgt = i + 2 * R; tok = i + 3 * R; val = f; score = f + R; lp = f + 2 * R; }
+    };
+    HeadLists bf_dev, bf_host;                                   // device / pinned (bf_host.src and bf_host.val own the pinned blocks)
     float *bf_dev_alp = nullptr, *bf_host_alp = nullptr;         // [BFORCED_ROWS][ALLOW_MAX], with the first forced submit under an allowed list
     int64_t st_fjobs = 0, st_frows = 0, st_fhead = 0;
 
@@ -685,10 +691,10 @@ public:
         if (h_sel) (void)hipHostFree(h_sel);
         (void)hipHostFree(h_slots); (void)hipHostFree(h_tok_b);
         if (h_head_src) (void)hipHostFree(h_head_src);
-        if (bf_host_i) (void)hipHostFree(bf_host_i);
+        if (bf_host.src) (void)hipHostFree(bf_host.src);
         if (h_cfeed) (void)hipHostFree(h_cfeed);
         if (h_cslots) (void)hipHostFree(h_cslots);
-        if (bf_host_f) (void)hipHostFree(bf_host_f);
+        if (bf_host.val) (void)hipHostFree(bf_host.val);
         if (bf_host_alp) (void)hipHostFree(bf_host_alp);
         if (h_draft) (void)hipHostFree(h_draft);
         if (h_vctl) (void)hipHostFree(h_vctl);
@@ -812,9 +818,25 @@ public:
     void refuse_while_group(const char* who) {
         REQUIRE(!grp.pending, std::string(who) + " cannot change while a group turn is pending (svln_group_select)");
     }
+    void refuse_while_any_group(const char* who) {
+        REQUIRE(!grp.pending, std::string(who) + ": a group turn is pending on env " + std::to_string(grp.env) + "; choose its continuation with svln_group_select first");
+    }
     // the one "turns in flight" refusal of every setter and of a weight write: no env changes scheme, head or weights in the middle of a turn
     void refuse_while_jobs(const char* who) {
         for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, std::string(who) + " cannot change while scheduler turns are in flight");
+    }
+    // ... and of the turn forms that run the scheduler's batched step themselves
+    void refuse_unless_idle(const char* who) {
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, std::string(who) + " needs an idle scheduler (turns are in flight)");
+    }
+    // the small lines every turn form shares: the results of the last single-env turn, the phase timers (events v0 v1 p0 p1 d1 of ph_ev,
+    // read after a synchronisation), the check of the ids a synchronisation read
+    void invalidate_last_results() { last_scores_valid = false; last_alp_valid = false; last_topk_valid = false; }
+    void add_phase(int k, int ev_from, int ev_to) { float t = 0.f; HIP_CHECK(hipEventElapsedTime(&t, ph_ev[ev_from], ph_ev[ev_to])); ph_ms[k] += t; }
+    void settle_vision() { if (vision_pending) { add_phase(0, 0, 1); vision_pending = false; } }
+    void require_finite_tokens(const int* tok, int n) {
+        for (int k = 0; k < n; ++k)
+            REQUIRE(tok[k] >= 0 && tok[k] < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
     }
     int kv_free_pages() override { return (int)free_pages.size(); }
     void env_state(int env, int32_t* n_embeds, int32_t* kv_len) override { Env& e = env_at(env); *n_embeds = e.n_embeds; *kv_len = e.kv_len; }
@@ -1078,19 +1100,27 @@ public:
     }
     // One model turn behind ONE call (SURVEY.md 8b `svln_turn`): encode_rgbd + the KV / embeds bookkeeping of StreamVLNForCausalLM.generate +
     // splice + greedy generation -- svln_encode_frames, svln_kv_reset / svln_reset_env, svln_append_turn, svln_generate in that order.
-    void turn(const svln_turn_args& a, int64_t* out, int cap, int32_t* n_out, int32_t* kv_len) override {
-        Env& e = env_at(a.env);
-        refuse_while_group_on(a.env, "svln_turn");
+    // The shared body of every svln_turn_*, up to the generate call (a.env is in range: the caller checked).  `checks` = the form's
+    // argument check and refusals, run inside the guard: a refusal of svln_turn, svln_turn_forced or svln_turn_candidates consumes the
+    // armed draft.  svln_turn_group and svln_turn_beams refuse BEFORE they call this and pass nothing: their refusals leave the draft armed.
+    template <typename Checks>
+    void begin_turn(const svln_turn_args& a, Checks checks) {
         try {
-            REQUIRE(a.ids && a.n_ids >= 1 && out && n_out, "svln_turn: null / empty argument");
+            checks();
             encode_frames(a.pixels, a.n_frames, a.pixels_on_device);
-            if (a.new_window) kv_reset(a.env);                      // past_key_values = None (streamvln_eval.py:349)
-            if (a.new_episode && e.n_embeds != 0) reset_env(a.env); // curr_t == 0: the env's inputs_embeds start over (stream_video_vln.py:396-401)
+            if (a.new_window) kv_reset(a.env);                                  // past_key_values = None (streamvln_eval.py:349)
+            if (a.new_episode && envs[a.env].n_embeds != 0) reset_env(a.env);   // curr_t == 0: the env's inputs_embeds start over (stream_video_vln.py:396-401)
             append_turn(a.env, a.ids, a.n_ids, 0, a.n_memory);
         } catch (...) {
             disarm_draft(a.env);          // an armed draft (svln_set_draft) is consumed by this call even when it fails before generating
             throw;
         }
+    }
+    void begin_turn(const svln_turn_args& a) { begin_turn(a, [] {}); }
+    void turn(const svln_turn_args& a, int64_t* out, int cap, int32_t* n_out, int32_t* kv_len) override {
+        Env& e = env_at(a.env);
+        refuse_while_group_on(a.env, "svln_turn");
+        begin_turn(a, [&] { REQUIRE(a.ids && a.n_ids >= 1 && out && n_out, "svln_turn: null / empty argument"); });
         generate(a.env, a.max_new_tokens, a.eos_ids, a.n_eos, out, cap, n_out, false);
         if (kv_len) *kv_len = e.kv_len;
     }
@@ -2283,13 +2313,15 @@ public:
     // env, the armed draft.  The armed draft is treated as svln_batch_submit treats it -- consumed iff svln_set_batch_draft is on -- and
     // never read.
     void ensure_bforced_buffers() {
-        constexpr int R = BFORCED_ROWS + 8;
+        constexpr int R = HeadLists::R;
         if (bf_xn && (bf_dev_alp || !allow_on)) return;      // (the hot path: no allocation, no synchronisation)
         if (!bf_xn) {
             bf_xn = dalloc<T>((size_t)R * H, true);
-            bf_dev_i = dalloc<int>(4 * R, true); bf_dev_f = dalloc<float>(3 * R, true);
-            HIP_CHECK(hipHostMalloc((void**)&bf_host_i, 4 * R * sizeof(int)));
-            HIP_CHECK(hipHostMalloc((void**)&bf_host_f, 3 * R * sizeof(float)));
+            int* di = dalloc<int>(4 * R, true); float* df = dalloc<float>(3 * R, true);
+            bf_dev.cut(di, df);
+            HIP_CHECK(hipHostMalloc((void**)&bf_host.src, 4 * R * sizeof(int)));
+            HIP_CHECK(hipHostMalloc((void**)&bf_host.val, 3 * R * sizeof(float)));
+            bf_host.cut(bf_host.src, bf_host.val);
         }
         if (allow_on && !bf_dev_alp) {
             bf_dev_alp = dalloc<float>((size_t)BFORCED_ROWS * ALLOW_MAX, true);
@@ -2355,39 +2387,40 @@ public:
     // n = r; pad rows carry target -1.  Under an allowed list: the subset product in its EPI_TARGET form, subset_logprobs and the final
     // kernel.  With sampling on inv_t = smp_inv_t, no noise is evaluated and no draw counter moves.  Returns the number of head rows.
     int head_forced(const std::vector<Seg>& segs, const std::vector<int>& pre_now) {
-        constexpr int R = BFORCED_ROWS + 8;
-        int *h_src = bf_host_i, *h_tap = bf_host_i + R, *h_tgt = bf_host_i + 2 * R;
-        int *d_src = bf_dev_i, *d_tap = bf_dev_i + R, *d_tgt = bf_dev_i + 2 * R;
+        const HeadLists& h = bf_host;
         int nf = 0;
         for (size_t q = 0; q < segs.size(); ++q) {
             const Job& j = jobs[pre_now[q]];
             if (!j.forced) continue;
             const int n = (int)j.fids.size();
             for (int i = 0; i < n; ++i) {
-                h_src[nf] = segs[q].off + segs[q].Tn - n + i;
+                h.src[nf] = segs[q].off + segs[q].Tn - n + i;
                 // tap row min(i, 7); of the rows that share tap row 7 only the last is written (what tap_copy's sequence leaves there:
                 // one launch must not write one tap row from two head rows)
-                h_tap[nf] = taps_on && (i < 7 || i == n - 1) ? (i < 7 ? i : 7) * MAXB + pre_now[q] : -1;
-                h_tgt[nf] = j.fids[i];
+                h.tap[nf] = taps_on && (i < 7 || i == n - 1) ? (i < 7 ? i : 7) * MAXB + pre_now[q] : -1;
+                h.tgt[nf] = j.fids[i];
                 ++nf;
             }
         }
         REQUIRE(nf >= 1 && nf <= BFORCED_ROWS, "batch_step: more forced head rows than the workspace holds");
-        for (int k = nf; k < nf + 8; ++k) h_tgt[k] = -1;
         // (the pinned lists were last read by copies of an iteration that ended in a synchronisation)
-        HIP_CHECK(hipMemcpyAsync(d_src, h_src, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(d_tap, h_tap, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(d_tgt, h_tgt, (size_t)(nf + 8) * sizeof(int), hipMemcpyHostToDevice, st));
-        launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn, d_src, d_tap, hid_tap, nf, H, c.rms_eps);
+        upload_head_lists(nf);
+        launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn, bf_dev.src, bf_dev.tap, hid_tap, nf, H, c.rms_eps);
         head_target_chunks(nf);
         return nf;
     }
-    // rows [0, nf) of bf_xn (targets bf_dev_i + 2 R) through the EPI_TARGET head in chunks of <= 32 rows; the results are copied to the
+    // the source, tap and target lists of nf head rows -> the device (8 pad targets of -1 behind them: the last chunk's row count)
+    void upload_head_lists(int nf) {
+        const HeadLists &h = bf_host, &d = bf_dev;
+        for (int k = nf; k < nf + 8; ++k) h.tgt[k] = -1;
+        HIP_CHECK(hipMemcpyAsync(d.src, h.src, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d.tap, h.tap, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d.tgt, h.tgt, (size_t)(nf + 8) * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    // rows [0, nf) of bf_xn (targets bf_dev.tgt) through the EPI_TARGET head in chunks of <= 32 rows; the results are copied to the
     // pinned lists (the caller synchronises).  Shared by the forced jobs of an iteration and by svln_generate_candidates.
     void head_target_chunks(int nf) {
-        constexpr int R = BFORCED_ROWS + 8;
-        int *d_tgt = bf_dev_i + 2 * R, *d_tok = bf_dev_i + 3 * R;
-        float *d_val = bf_dev_f, *d_score = bf_dev_f + R, *d_lp = bf_dev_f + 2 * R;
+        const HeadLists &h = bf_host, &d = bf_dev;
         const float inv_t = smp_on ? smp_inv_t : 1.0f;
         for (int r0 = 0; r0 < nf; r0 += 32) {
             const int r = std::min(nf - r0, 32);
@@ -2397,17 +2430,24 @@ public:
                 su.epi = EPI_TARGET; su.tg_inv_t = inv_t;
                 launch_gemv_subset<T>(st, su);
                 launch_subset_logprobs(st, part_val_b, allow_n, r, bf_dev_alp + (size_t)r0 * allow_n);
-                launch_argmax_final_batched(st, part_val_b, part_idx_b, allow_n, r, d_tok + r0, part_sum_b, d_score + r0);
+                launch_argmax_final_batched(st, part_val_b, part_idx_b, allow_n, r, d.tok + r0, part_sum_b, d.score + r0);
             } else {
-                TargetOut o; o.tgt = d_tgt + r0; o.val = d_val + r0; o.tok = d_tok + r0; o.score = d_score + r0; o.lp = d_lp + r0;
+                const TargetOut o{d.tgt + r0, d.val + r0, d.tok + r0, d.score + r0, d.lp + r0};
                 target_rows(lm_head, H, rows_x, H, V, H, ride_head_rows(r), r, inv_t, &o);
             }
             st_fhead += 1;
         }
-        HIP_CHECK(hipMemcpyAsync(bf_host_i + 3 * R, d_tok, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(bf_host_f + R, d_score, (size_t)nf * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h.tok, d.tok, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h.score, d.score, (size_t)nf * sizeof(float), hipMemcpyDeviceToHost, st));
         if (allow_on) HIP_CHECK(hipMemcpyAsync(bf_host_alp, bf_dev_alp, (size_t)nf * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
-        else HIP_CHECK(hipMemcpyAsync(bf_host_f + 2 * R, d_lp, (size_t)nf * sizeof(float), hipMemcpyDeviceToHost, st));
+        else HIP_CHECK(hipMemcpyAsync(h.lp, d.lp, (size_t)nf * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    // the log-probability of forced id `id` on head row `row`: the row's entry of the target list, or under an allowed list the id's entry
+    // of the row's normalised allowed-list row (the same bits svln_get_allowed_logprobs returns)
+    float forced_score(int row, int id, const float* lp_rows, const float* alp_rows) const {
+        if (!allow_on) return lp_rows[row];
+        const int pos = (int)(std::lower_bound(allow_ids.begin(), allow_ids.end(), id) - allow_ids.begin());
+        return alp_rows[(size_t)row * allow_n + pos];
     }
     // one iteration; returns the number of jobs still running afterwards, finished_slots = jobs that completed in this iteration
     int batch_step(int32_t* finished_slots, int32_t* n_finished) override {
@@ -2620,16 +2660,9 @@ public:
         }
         HIP_CHECK(hipStreamSynchronize(st));
         LAUNCH_CHECK("batch_step");
-        {
-            float t = 0.f;
-            if (split) {
-                HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[4])); ph_ms[2] += t;
-                HIP_CHECK(hipEventElapsedTime(&t, ph_ev[4], ph_ev[3])); ph_ms[1] += t;
-            } else {
-                HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[3])); ph_ms[segs.empty() ? 2 : 1] += t;
-            }
-            if (vision_pending) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
-        }
+        if (split) { add_phase(2, 2, 4); add_phase(1, 4, 3); }
+        else add_phase(segs.empty() ? 2 : 1, 2, 3);
+        settle_vision();
         st_biters += 1;
         st_bsingle += nd;
         int hq = 0;                                     // head row of h_tok_b the next job starts at
@@ -2645,7 +2678,7 @@ public:
             for (int i = 0; i <= kd && !stop; ++i) {
                 if (i > 0 && tok != j.draft[i - 1]) break;
                 tok = h_tok_b[hq + i];
-                REQUIRE(tok >= 0 && tok < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+                require_finite_tokens(&tok, 1);
                 j.out.push_back(tok);
                 if (j.scored) j.scores.push_back(h_score_b[hq + i]);
                 if (j.topk) {
@@ -2684,11 +2717,8 @@ public:
         // the forced jobs of the iteration, in the order head_forced listed them: each ends here with out = F, where a plain turn that
         // emitted F leaves the env (the last id appended, not fed); no draw counter moves
         if (n_fhead > 0) {
-            constexpr int R = BFORCED_ROWS + 8;
-            const int* h_tok = bf_host_i + 3 * R;
-            const float *h_score = bf_host_f + R, *h_lp = bf_host_f + 2 * R;
-            for (int i = 0; i < n_fhead; ++i)
-                REQUIRE(h_tok[i] >= 0 && h_tok[i] < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+            const HeadLists& h = bf_host;
+            require_finite_tokens(h.tok, n_fhead);
             int fq = 0;
             for (size_t q = 0; q < segs.size(); ++q) {
                 Job& j = jobs[pre_now[q]];
@@ -2697,14 +2727,9 @@ public:
                 const int n = (int)j.fids.size();
                 j.out.assign(j.fids.begin(), j.fids.end());
                 for (int i = 0; i < n; ++i) {
-                    j.greedy.push_back(h_tok[fq + i]);
-                    j.greedy_lp.push_back(h_score[fq + i]);
-                    if (allow_on) {
-                        const int pos = (int)(std::lower_bound(allow_ids.begin(), allow_ids.end(), j.fids[i]) - allow_ids.begin());
-                        j.scores.push_back(bf_host_alp[(size_t)(fq + i) * allow_n + pos]);
-                    } else {
-                        j.scores.push_back(h_lp[fq + i]);
-                    }
+                    j.greedy.push_back(h.tok[fq + i]);
+                    j.greedy_lp.push_back(h.score[fq + i]);
+                    j.scores.push_back(forced_score(fq + i, j.fids[i], h.lp, bf_host_alp));
                 }
                 if (allow_on) { j.alp.assign(bf_host_alp + (size_t)fq * allow_n, bf_host_alp + (size_t)(fq + n) * allow_n); j.alp_n = allow_n; }
                 fq += n;
@@ -2734,7 +2759,7 @@ public:
                         int32_t* n_out) override {
         REQUIRE(n_envs >= 1 && n_envs <= MAXB, "1..8 envs per batch");
         REQUIRE(max_new >= 1 && cap >= 1, "max_new_tokens must be >= 1");
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_generate_batch needs an idle scheduler (turns are in flight)");
+        refuse_unless_idle("svln_generate_batch");
         for (int s = 0; s < n_envs; ++s)
             for (int t = 0; t < s; ++t) REQUIRE(env_ids[t] != env_ids[s], "duplicate env in batch");
         for (int s = 0; s < n_envs; ++s) refuse_while_group_on(env_ids[s], "svln_generate_batch");
@@ -2784,7 +2809,7 @@ public:
     void generate(int env, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, bool fixed) override {
         Env& e = env_at(env);
         refuse_while_group_on(env, "svln_generate");
-        last_scores_valid = false; last_alp_valid = false; last_topk_valid = false;
+        invalidate_last_results();
         const bool had_draft = disarm_draft(env);      // consumed by this call whether it helps, is ignored or the call fails
         REQUIRE(weights_missing() == 0, g_err);
         const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
@@ -2869,8 +2894,7 @@ public:
             n = h_ctl->count;
             done = h_ctl->done != 0;
             REQUIRE(n >= 1 && n <= n_head, "generation state out of range");
-            for (int k = 0; k < n; ++k)
-                REQUIRE(h_out_ids[k] >= 0 && h_out_ids[k] < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+            require_finite_tokens(h_out_ids, n);
             for (int k = 0; k < n && k < dlen; ++k) ride_held = ride_held && h_out_ids[k] == h_draft[k];
             rtokens = h_vctl[5];
             st_rides += h_vctl[4]; st_rtokens += rtokens; st_rrows += k_ride;
@@ -2903,8 +2927,7 @@ public:
                 n = h_ctl->count;
                 done = h_ctl->done != 0;
                 REQUIRE(n >= cnt && n <= cnt + r, "generation state out of range");
-                for (int k = 0; k < n; ++k)
-                    REQUIRE(h_out_ids[k] >= 0 && h_out_ids[k] < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+                require_finite_tokens(h_out_ids, n);
                 bool held = n > cnt;
                 for (int k = 1; k < n && k < dlen; ++k) held = held && h_out_ids[k] == h_draft[k];
                 cnt = n;
@@ -2948,8 +2971,7 @@ public:
             n = h_ctl->count;
             done = h_ctl->done != 0;
             REQUIRE(n >= 1 && n <= enq, "generation state out of range");
-            for (int k = 0; k < n; ++k)
-                REQUIRE(h_out_ids[k] >= 0 && h_out_ids[k] < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+            require_finite_tokens(h_out_ids, n);
             if (done) break;
             REQUIRE(steps > 0, "sequence exceeds max_positions during decode");
         }
@@ -2961,12 +2983,9 @@ public:
             last_topk = topk; last_topk_valid = true;
         }
         e.kv_len = L + n - 1;             // EOS (or the last token) is appended to the ids but never fed
-        {
-            float t = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[3])); ph_ms[1] += t;
-            if (vision_pending) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
-            if (decoded) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[3], ph_ev[4])); ph_ms[2] += t; }
-        }
+        add_phase(1, 2, 3);
+        settle_vision();
+        if (decoded) add_phase(2, 3, 4);
         n_generated = n;
         const int singles = n - vtokens - (ride ? rtokens : 1);      // (the prefill's own token counts in none of the draft counters)
         st_vtokens += vtokens; st_single += singles;
@@ -2985,32 +3004,68 @@ public:
         refuse_while_plain_head_only("svln_generate_group");     // (svln_set_sampling is refused under each of them: name the cause)
         REQUIRE(smp_on, "svln_generate_group: temperature sampling is off (svln_set_sampling): greedy sequences would be identical");
         REQUIRE(rep_penalty == 1.0f, "svln_generate_group: a repetition penalty != 1 is set (svln_set_repetition_penalty); a group does not support it");
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "svln_generate_group needs an idle scheduler (turns are in flight)");
-        REQUIRE(!grp.pending, "svln_generate_group: a group turn is pending on env " + std::to_string(grp.env) + "; choose its continuation with svln_group_select first");
+        refuse_unless_idle("svln_generate_group");
+        refuse_while_any_group("svln_generate_group");
+    }
+    // The plan of a turn form that shares one prefill: P cached rows, L rows in all, Tn = L - P rows to prefill, limit = min(max_new, cap)
+    // ids after them (emitted or fed; the last one is never fed), q0 = the page L falls in, n_tail = the private pages of a fork from q0
+    // on, env_need = the pages the env itself still lacks.  Issues the refusals the forms share, in the order they always had; arg_fault
+    // (the form's own argument fault, if it found one: the text after `who`) is reported in its old place.  Nothing is launched or changed.
+    struct TurnPlan { int P, L, Tn, limit, q0, n_tail, env_need; };
+    static int fork_tail_pages(int L, int limit) { return limit == 1 ? 0 : (L + limit - 1 + PAGE - 1) / PAGE - L / PAGE; }
+    TurnPlan plan_turn(const Env& e, const char* who, int max_new, int cap, const char* limit_text, const char* arg_fault = nullptr) {
+        REQUIRE(weights_missing() == 0, g_err);
+        TurnPlan p;
+        p.P = e.kv_len; p.L = e.n_embeds; p.Tn = p.L - p.P; p.limit = max_new < cap ? max_new : cap;
+        REQUIRE(p.Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
+        REQUIRE(max_new >= 1 && cap >= 1, "max_new_tokens must be >= 1");
+        REQUIRE(!arg_fault, std::string(who) + arg_fault);
+        REQUIRE((int64_t)p.L + p.limit - 1 <= c.max_positions, std::string(who) + ": n_embeds + " + limit_text + " - 1 exceeds max_positions");
+        p.q0 = p.L / PAGE;
+        p.n_tail = fork_tail_pages(p.L, p.limit);
+        p.env_need = std::max((p.limit == 1 ? (p.L + PAGE - 1) / PAGE : p.q0 + p.n_tail) - e.n_pages, 0);
+        return p;
     }
     std::vector<int> fork_host[MAXB];            // host copies of fork_tab (kept: an upload reads them after the call that wrote them)
+    void ensure_fork_tab(int g) { if (!fork_tab[g]) { fork_tab[g] = dalloc<int>(pages_per_env, true); fork_host[g].assign(pages_per_env, 0); } }
+    // h_fork_dst[0 .. n_dst) -> the device, then the ONE fork launch: page src_page of every layer's K and V^T pool to each listed page
+    void fork_page_copy(int src_page, int n_dst) {
+        HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)n_dst * sizeof(int), hipMemcpyHostToDevice, st));
+        launch_kv_page_copy<T>(st, d_pool_tab, 2 * c.layers, src_page, d_fork_dst, n_dst, (int64_t)nkv * PAGE * 128);
+    }
+    // The fork of the pending group grp (its L set): per sequence g >= 1 with tail_n[g] > 0 a table = the env's pages below q0 + tail_n[g]
+    // private pages from q0 on (grp.tail[g]), uploaded to fork_tab[g]; then the partly filled page q0, if the prompt ends inside one.
+    void fork_tails(Env& e, int q0, const int* tail_n, int n_seq) {
+        int n_dst = 0;
+        for (int g = 1; g < n_seq; ++g) {
+            if (tail_n[g] == 0) continue;
+            std::vector<int>& tab = fork_host[g];
+            for (int i = 0; i < q0; ++i) tab[i] = e.pages[i];
+            for (int i = 0; i < tail_n[g]; ++i) {
+                REQUIRE(!free_pages.empty(), "KV page pool exhausted");
+                grp.tail[g].push_back(free_pages.back());
+                free_pages.pop_back();
+                tab[q0 + i] = grp.tail[g][i];
+            }
+            HIP_CHECK(hipMemcpyAsync(fork_tab[g], tab.data(), (size_t)(q0 + tail_n[g]) * sizeof(int), hipMemcpyHostToDevice, st));
+            h_fork_dst[n_dst++] = grp.tail[g][0];
+        }
+        if (grp.L % PAGE != 0 && n_dst > 0) fork_page_copy(e.pages[q0], n_dst);      // one launch for every layer, both pools, all forks
+    }
     void generate_group(int env, int n_seq, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out) override {
         group_refusals(env, n_seq);
         Env& e = envs[env];
         REQUIRE(out && n_out, "svln_generate_group: null output pointer");
-        REQUIRE(weights_missing() == 0, g_err);
-        const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
-        REQUIRE(Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
-        REQUIRE(max_new >= 1 && cap >= 1, "max_new_tokens must be >= 1");
-        REQUIRE(n_eos >= 0 && (n_eos == 0 || eos), "svln_generate_group: null eos list");
-        const int limit = max_new < cap ? max_new : cap;                     // tokens each sequence may emit
-        REQUIRE((int64_t)L + limit - 1 <= c.max_positions, "svln_generate_group: n_embeds + min(max_new_tokens, out_cap) - 1 exceeds max_positions");
-        const int q0 = L / PAGE;
-        const int n_tail = limit == 1 ? 0 : (L + limit - 1 + PAGE - 1) / PAGE - q0;
-        const int env_need = std::max((limit == 1 ? (L + PAGE - 1) / PAGE : q0 + n_tail) - e.n_pages, 0);
-        REQUIRE((int64_t)free_pages.size() >= (int64_t)env_need + (int64_t)(n_seq - 1) * n_tail,
+        const TurnPlan pl = plan_turn(e, "svln_generate_group", max_new, cap, "min(max_new_tokens, out_cap)",
+                                      n_eos >= 0 && (n_eos == 0 || eos) ? nullptr : ": null eos list");
+        const int P = pl.P, L = pl.L, Tn = pl.Tn, limit = pl.limit, q0 = pl.q0, n_tail = pl.n_tail;      // limit: tokens each sequence may emit
+        REQUIRE((int64_t)free_pages.size() >= (int64_t)pl.env_need + (int64_t)(n_seq - 1) * n_tail,
                 "svln_generate_group: the free KV pages cannot hold the env's own pages and (n_seq - 1) x the tail pages of the fork");
         // ---- nothing was launched or changed up to here
         disarm_draft(env);
-        last_scores_valid = false; last_alp_valid = false; last_topk_valid = false;
+        invalidate_last_results();
         int B = 2; while (B < n_seq) B <<= 1;
-        for (int g = 1; g < n_seq; ++g)
-            if (!fork_tab[g]) { fork_tab[g] = dalloc<int>(pages_per_env, true); fork_host[g].assign(pages_per_env, 0); }
+        for (int g = 1; g < n_seq; ++g) ensure_fork_tab(g);
         grp = Group();
         grp.env = env; grp.n_seq = n_seq; grp.L = L; grp.q0 = q0; grp.n_tail = n_tail;
         grp.scored = scores_on; grp.alp_n = scores_on && allow_on ? allow_n : 0;
@@ -3019,7 +3074,7 @@ public:
         // the host's stop rule on head row `row` of sequence g: EOS id (appended, never fed), limit, a non-finite arg-max
         auto accept = [&](int g, int row) {
             const int tok = h_tok_b[row];
-            REQUIRE(tok >= 0 && tok < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+            require_finite_tokens(&tok, 1);
             ids[g].push_back(tok);
             if (grp.scored) grp.scores[g].push_back(h_score_b[row]);
             if (grp.alp_n > 0) grp.alp[g].insert(grp.alp[g].end(), h_alp_b + (size_t)row * grp.alp_n, h_alp_b + (size_t)(row + 1) * grp.alp_n);
@@ -3036,9 +3091,8 @@ public:
             if (scores_on && allow_on) HIP_CHECK(hipMemcpyAsync(h_alp_b, d_alp_b, (size_t)B * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
             LAUNCH_CHECK("generate_group");
-            float t = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[3])); ph_ms[phase] += t;
-            if (vision_pending) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
+            add_phase(phase, 2, 3);
+            settle_vision();
         };
         auto upload_streams = [&]() {
             HIP_CHECK(hipMemcpyAsync(d_smp, h_smp, B * sizeof(int), hipMemcpyHostToDevice, st));
@@ -3060,22 +3114,9 @@ public:
             for (int g = 0; g < n_seq; ++g) tap_copy(xn + (size_t)g * H, 0, g);
             // fork: the env's own tail pages, then per sequence g >= 1 a table = the env's pages below q0 + private pages from q0 on
             if (limit > 1) ensure_pages(e, L + limit - 1);
-            for (int g = 1; g < n_seq && n_tail > 0; ++g) {
-                std::vector<int>& tab = fork_host[g];
-                for (int i = 0; i < q0; ++i) tab[i] = e.pages[i];
-                for (int i = 0; i < n_tail; ++i) {
-                    REQUIRE(!free_pages.empty(), "KV page pool exhausted");
-                    grp.tail[g].push_back(free_pages.back());
-                    free_pages.pop_back();
-                    tab[q0 + i] = grp.tail[g][i];
-                }
-                HIP_CHECK(hipMemcpyAsync(fork_tab[g], tab.data(), (size_t)(q0 + n_tail) * sizeof(int), hipMemcpyHostToDevice, st));
-            }
-            if (L % PAGE != 0 && n_tail > 0) {       // the partly filled page: one launch for every layer, both pools, all forks
-                for (int g = 1; g < n_seq; ++g) h_fork_dst[g - 1] = grp.tail[g][0];
-                HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)(n_seq - 1) * sizeof(int), hipMemcpyHostToDevice, st));
-                launch_kv_page_copy<T>(st, d_pool_tab, 2 * c.layers, e.pages[q0], d_fork_dst, n_seq - 1, (int64_t)nkv * PAGE * 128);
-            }
+            int tail_n[MAXB];
+            std::fill(tail_n, tail_n + MAXB, n_tail);
+            fork_tails(e, q0, tail_n, n_seq);
             read_rows(1);
             for (int g = 0; g < n_seq; ++g) accept(g, g);
             // decode: the scheduler's pure batched step; a finished sequence's row and every pad row replay the first live row
@@ -3120,15 +3161,7 @@ public:
     void turn_group(const svln_turn_args& a, int n_seq, int64_t* out, int cap, int32_t* n_out) override {
         group_refusals(a.env, n_seq);
         REQUIRE(a.ids && a.n_ids >= 1 && out && n_out, "svln_turn_group: null / empty argument");
-        try {
-            encode_frames(a.pixels, a.n_frames, a.pixels_on_device);
-            if (a.new_window) kv_reset(a.env);
-            if (a.new_episode && envs[a.env].n_embeds != 0) reset_env(a.env);
-            append_turn(a.env, a.ids, a.n_ids, 0, a.n_memory);
-        } catch (...) {
-            disarm_draft(a.env);
-            throw;
-        }
+        begin_turn(a);                    // (the refusals above came first: they leave an armed draft in place)
         generate_group(a.env, n_seq, a.max_new_tokens, a.eos_ids, a.n_eos, out, cap, n_out);
     }
     // ------------------------------------------------------------------------------- beam turns (svln_generate_beams)
@@ -3156,35 +3189,32 @@ public:
         REQUIRE(!persistent_on, std::string(who) + ": the persistent decode layer is on (svln_set_decode_persistent); switch it off first");
         REQUIRE(!mx4b_on, std::string(who) + ": the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
         REQUIRE((size_t)H * sizeof(float) <= (size_t)GEMV_ROWS_TOPK_MAX_LDS, std::string(who) + ": the hidden size is too large for the candidate form of the lm_head GEMV");
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, std::string(who) + " needs an idle scheduler (turns are in flight)");
-        REQUIRE(!grp.pending, std::string(who) + ": a group turn is pending on env " + std::to_string(grp.env) + "; choose its continuation with svln_group_select first");
+        refuse_unless_idle(who);
+        refuse_while_any_group(who);
     }
     void generate_beams(int env, int W, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, float* scores) override {
         const char* who = "svln_generate_beams";
         beam_refusals(env, W);
         Env& e = envs[env];
         REQUIRE(out && n_out && scores, std::string(who) + ": null output pointer");
-        REQUIRE(weights_missing() == 0, g_err);
-        const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
-        REQUIRE(Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
-        REQUIRE(max_new >= 1 && cap >= 1, "max_new_tokens must be >= 1");
-        REQUIRE(n_eos >= 0 && n_eos <= std::max(V, 64) && (n_eos == 0 || eos), std::string(who) + ": null eos list / too many eos ids");
-        const int limit = max_new < cap ? max_new : cap;
-        REQUIRE((int64_t)L + limit - 1 <= c.max_positions, std::string(who) + ": n_embeds + min(max_new_tokens, out_cap) - 1 exceeds max_positions");
-        const int q0 = L / PAGE;
-        const int n_tail = limit == 1 ? 0 : (L + limit - 1 + PAGE - 1) / PAGE - q0;
+        const TurnPlan pl = plan_turn(e, who, max_new, cap, "min(max_new_tokens, out_cap)",
+                                      n_eos >= 0 && n_eos <= std::max(V, 64) && (n_eos == 0 || eos) ? nullptr : ": null eos list / too many eos ids");
+        const int P = pl.P, L = pl.L, Tn = pl.Tn, limit = pl.limit, q0 = pl.q0, n_tail = pl.n_tail;
         REQUIRE(n_tail <= BEAM_CP_MAX, std::string(who) + ": a turn of more than 8 tail pages does not fit the page lists of a beam step");
-        const int env_need = std::max((limit == 1 ? (L + PAGE - 1) / PAGE : q0 + n_tail) - e.n_pages, 0);
-        REQUIRE((int64_t)free_pages.size() >= (int64_t)env_need + (int64_t)(2 * W - 1) * n_tail,
+        REQUIRE((int64_t)free_pages.size() >= (int64_t)pl.env_need + (int64_t)(2 * W - 1) * n_tail,
                 std::string(who) + ": the free KV pages cannot hold the env's own pages and (2 n_beams - 1) x the tail pages of the hypotheses");
         // ---- nothing was launched or changed up to here
         disarm_draft(env);
-        last_scores_valid = false; last_alp_valid = false; last_topk_valid = false;
+        invalidate_last_results();
         ensure_topk_buffers();
         ensure_beam_buffers();
         int B = 2; while (B < W) B <<= 1;
         const int n_sets = 2 * W;
-        const bool held_scores = scores_on; const int held_topk = topk, held_trunc = trunc_k;
+        // the head of the call: restored however the call ends (the step graphs are keyed on these three)
+        struct HeadOverride {
+            bool& scores; int &topk, &trunc; const bool scores0; const int topk0, trunc0;
+            ~HeadOverride() { scores = scores0; topk = topk0; trunc = trunc0; }
+        } held{scores_on, topk, trunc_k, scores_on, topk, trunc_k};
         scores_on = true; topk = W; trunc_k = 0;
         BeamTrace tr; tr.W = W;
         BeamHdr hh;
@@ -3206,9 +3236,8 @@ public:
                 for (int j = 0; j < W; ++j) { tr.list_ids[o + r * BEAM_MAX_W + j] = li[(size_t)r * W + j]; tr.list_lps[o + r * BEAM_MAX_W + j] = ll[(size_t)r * W + j]; }
             tr.rec.insert(tr.rec.end(), rec, rec + BEAM_REC);
             ++tr.steps;
-            float t = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[3])); ph_ms[phase] += t;
-            if (vision_pending) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
+            add_phase(phase, 2, 3);
+            settle_vision();
             REQUIRE(hh.n >= 0 && hh.n <= W && rec[0] == hh.n && rec[3] >= 0 && rec[3] <= BEAM_MAX_W * BEAM_CP_MAX, "beam state out of range");
             for (int q = 0; q < hh.n; ++q) REQUIRE(hh.set_of[q] >= 0 && hh.set_of[q] < n_sets && rec[4 + q] >= 0 && rec[4 + q] < BEAM_MAX_W, "beam state out of range");
         };
@@ -3270,8 +3299,7 @@ public:
                 HIP_CHECK(hipMemcpy(bm_sets, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
                 if (L % PAGE != 0 && W > 1) {       // the partly filled page: the group turn's fork, to the sets the step-0 children take
                     for (int s = 1; s < W; ++s) h_fork_dst[s - 1] = beam_set[s][0];
-                    HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)(W - 1) * sizeof(int), hipMemcpyHostToDevice, st));
-                    launch_kv_page_copy<T>(st, d_pool_tab, 2 * c.layers, e.pages[q0], d_fork_dst, W - 1, (int64_t)nkv * PAGE * 128);
+                    fork_page_copy(e.pages[q0], W - 1);
                 }
             }
             select(0);
@@ -3345,10 +3373,8 @@ public:
             for (int s = 1; s < 2 * BEAM_MAX_W; ++s) { for (int p : beam_set[s]) free_pages.push_back(p); beam_set[s].clear(); }
             beam_set[0].clear();
             grp = Group();
-            scores_on = held_scores; topk = held_topk; trunc_k = held_trunc;
             throw;
         }
-        scores_on = held_scores; topk = held_topk; trunc_k = held_trunc;
         beam_trace_last = std::move(tr);
         e.kv_len = L;                     // until svln_group_select
         n_generated = 0;                  // (the single-env tap rows were overwritten)
@@ -3359,15 +3385,7 @@ public:
     void turn_beams(const svln_turn_args& a, int W, int64_t* out, int cap, int32_t* n_out, float* scores) override {
         beam_refusals(a.env, W);
         REQUIRE(a.ids && a.n_ids >= 1 && out && n_out && scores, "svln_turn_beams: null / empty argument");
-        try {
-            encode_frames(a.pixels, a.n_frames, a.pixels_on_device);
-            if (a.new_window) kv_reset(a.env);
-            if (a.new_episode && envs[a.env].n_embeds != 0) reset_env(a.env);
-            append_turn(a.env, a.ids, a.n_ids, 0, a.n_memory);
-        } catch (...) {
-            disarm_draft(a.env);
-            throw;
-        }
+        begin_turn(a);                    // (the refusals above came first: they leave an armed draft in place)
         generate_beams(a.env, W, a.max_new_tokens, a.eos_ids, a.n_eos, out, cap, n_out, scores);
     }
     void beam_trace(int cap_steps, int32_t* n_steps, int32_t* width, int32_t* list_ids, float* list_lps, int32_t* records) override {
@@ -3404,7 +3422,7 @@ public:
         for (int g = 0; g < n_seq; ++g) REQUIRE(lens[g] >= 1 && lens[g] <= FORCED_MAX, std::string(who) + ": a sequence length (lens) must be 1 .. 32");
         refuse_while_topk(who);
         REQUIRE(!mx4b_on, std::string(who) + ": the batched MXFP4 weights are on (svln_set_mxfp4_batched): a scoring pass runs the batched step; switch them off first");
-        REQUIRE(!grp.pending, std::string(who) + ": a group turn is pending on env " + std::to_string(grp.env) + "; choose its continuation with svln_group_select first");
+        refuse_while_any_group(who);
         int off = 0;
         for (int g = 0; g < n_seq; ++g) { forced_refusals(env, ids + off, lens[g], eos, n_eos, who); off += lens[g]; }
     }
@@ -3414,17 +3432,15 @@ public:
         disarm_draft(env);              // consumed by this call, as svln_generate_forced consumes it
         REQUIRE(logprobs && greedy_ids && greedy_logprobs, "svln_generate_candidates: null output pointer");
         cand_refusals(env, n_seq, ids, lens, eos, n_eos);
-        REQUIRE(weights_missing() == 0, g_err);
-        const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
-        REQUIRE(Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
         int n_max = 0, nf = 0, off[MAXB + 1] = {0};
         for (int g = 0; g < n_seq; ++g) { n_max = std::max(n_max, (int)lens[g]); off[g + 1] = off[g] + lens[g]; }
         nf = off[n_seq];
-        REQUIRE((int64_t)L + n_max - 1 <= c.max_positions, "svln_generate_candidates: n_embeds + max(lens) - 1 exceeds max_positions");
-        const int q0 = L / PAGE;
+        const TurnPlan pl = plan_turn(e, "svln_generate_candidates", n_max, n_max, "max(lens)");
+        const int P = pl.P, L = pl.L, Tn = pl.Tn, q0 = pl.q0;
+        // (the plan's page counts are those of the longest sequence: here the env feeds lens[0] ids and every fork its own)
         int tail_n[MAXB] = {0};
         int64_t need = std::max((L + lens[0] - 1 + PAGE - 1) / PAGE - e.n_pages, 0);
-        for (int g = 1; g < n_seq; ++g) { tail_n[g] = lens[g] == 1 ? 0 : (L + lens[g] - 1 + PAGE - 1) / PAGE - q0; need += tail_n[g]; }
+        for (int g = 1; g < n_seq; ++g) { tail_n[g] = fork_tail_pages(L, lens[g]); need += tail_n[g]; }
         REQUIRE((int64_t)free_pages.size() >= need,
                 "svln_generate_candidates: the free KV pages cannot hold the env's own pages and the tail pages of the fork");
         const int r = cand_rows_per_pass(n_seq);
@@ -3434,21 +3450,18 @@ public:
         ensure_bforced_buffers();
         ensure_cand_buffers();
         // ---- nothing was launched or changed up to here (but the armed draft)
-        last_scores_valid = false; last_alp_valid = false; last_topk_valid = false;
-        for (int g = 1; g < n_seq; ++g)
-            if (!fork_tab[g]) { fork_tab[g] = dalloc<int>(pages_per_env, true); fork_host[g].assign(pages_per_env, 0); }
+        invalidate_last_results();
+        for (int g = 1; g < n_seq; ++g) ensure_fork_tab(g);
         grp = Group();
         grp.env = env; grp.n_seq = n_seq; grp.L = L; grp.q0 = q0; grp.scored = true; grp.alp_n = allow_on ? allow_n : 0;
         for (int g = 1; g < n_seq; ++g) grp.n_tail = std::max(grp.n_tail, tail_n[g]);
-        constexpr int R = BFORCED_ROWS + 8;
         // head row lists.  Block 0: the prompt's last row once per sequence (target F_g[0]); block p + 1: the rows pass p fed, sequence by
         // sequence (row slot g r + j fed F_g[p r + j], target F_g[p r + j + 1]).  hrow[off[g] + i] = the head row that scores F_g[i].
-        int *h_src = bf_host_i, *h_tap = bf_host_i + R, *h_tgt = bf_host_i + 2 * R;
-        int *d_src = bf_dev_i, *d_tap = bf_dev_i + R, *d_tgt = bf_dev_i + 2 * R;
+        const HeadLists &h = bf_host, &d = bf_dev;
         std::vector<int> hrow(nf), base(passes + 2, 0);
         HIP_CHECK(hipStreamSynchronize(st));       // (the pinned lists of an earlier call are no longer being read)
         int k = 0;
-        for (int g = 0; g < n_seq; ++g) { h_src[k] = Tn - 1; h_tap[k] = taps_on ? g : -1; h_tgt[k] = (int)ids[off[g]]; hrow[off[g]] = k; ++k; }
+        for (int g = 0; g < n_seq; ++g) { h.src[k] = Tn - 1; h.tap[k] = taps_on ? g : -1; h.tgt[k] = (int)ids[off[g]]; hrow[off[g]] = k; ++k; }
         base[1] = k;
         for (int p = 0; p < passes; ++p) {
             for (int q = 0; q < B; ++q) h_cfeed[p * B + q] = 0;
@@ -3459,10 +3472,10 @@ public:
                 for (int j = 0; j < cnt; ++j) {
                     const int i = lo + j + 1;       // the position of the turn this row scores
                     h_cfeed[p * B + g * r + j] = (int)ids[off[g] + lo + j];
-                    h_src[k] = g * r + j;
+                    h.src[k] = g * r + j;
                     // tap row min(i, 7); of the rows of one launch that share tap row 7 only the last is written (later passes overwrite it)
-                    h_tap[k] = taps_on && (i < 7 || j == cnt - 1) ? (i < 7 ? i : 7) * MAXB + g : -1;
-                    h_tgt[k] = (int)ids[off[g] + i];
+                    h.tap[k] = taps_on && (i < 7 || j == cnt - 1) ? (i < 7 ? i : 7) * MAXB + g : -1;
+                    h.tgt[k] = (int)ids[off[g] + i];
                     hrow[off[g] + i] = k;
                     ++k;
                 }
@@ -3470,11 +3483,8 @@ public:
             base[p + 2] = k;
         }
         REQUIRE(k == nf, "svln_generate_candidates: head row count");
-        for (int q = nf; q < nf + 8; ++q) h_tgt[q] = -1;
         try {
-            HIP_CHECK(hipMemcpyAsync(d_src, h_src, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync(d_tap, h_tap, (size_t)nf * sizeof(int), hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync(d_tgt, h_tgt, (size_t)(nf + 8) * sizeof(int), hipMemcpyHostToDevice, st));
+            upload_head_lists(nf);
             if (passes > 0) {
                 HIP_CHECK(hipMemcpyAsync(d_cfeed, h_cfeed, (size_t)passes * B * sizeof(int), hipMemcpyHostToDevice, st));
                 HIP_CHECK(hipMemcpyAsync(d_cslots, h_cslots, (size_t)passes * MAXB * sizeof(DecodeSlot), hipMemcpyHostToDevice, st));
@@ -3484,54 +3494,29 @@ public:
             HIP_CHECK(hipEventRecord(ph_ev[2], st));
             prefill(e, P, Tn);
             e.kv_len = L;
-            launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn, d_src, d_tap, hid_tap, n_seq, H, c.rms_eps);
+            launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn, d.src, d.tap, hid_tap, n_seq, H, c.rms_eps);
             HIP_CHECK(hipEventRecord(ph_ev[3], st));
             // fork: the env's own tail pages, then per sequence g >= 1 a table = the env's pages below q0 + private pages from q0 on
             ensure_pages(e, L + lens[0] - 1);
-            int n_dst = 0;
-            for (int g = 1; g < n_seq; ++g) {
-                if (tail_n[g] == 0) continue;
-                std::vector<int>& tab = fork_host[g];
-                for (int i = 0; i < q0; ++i) tab[i] = e.pages[i];
-                for (int i = 0; i < tail_n[g]; ++i) {
-                    REQUIRE(!free_pages.empty(), "KV page pool exhausted");
-                    grp.tail[g].push_back(free_pages.back());
-                    free_pages.pop_back();
-                    tab[q0 + i] = grp.tail[g][i];
-                }
-                HIP_CHECK(hipMemcpyAsync(fork_tab[g], tab.data(), (size_t)(q0 + tail_n[g]) * sizeof(int), hipMemcpyHostToDevice, st));
-                h_fork_dst[n_dst++] = grp.tail[g][0];
-            }
-            if (L % PAGE != 0 && n_dst > 0) {       // the partly filled page: one launch for every layer, both pools, all forks
-                HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)n_dst * sizeof(int), hipMemcpyHostToDevice, st));
-                launch_kv_page_copy<T>(st, d_pool_tab, 2 * c.layers, e.pages[q0], d_fork_dst, n_dst, (int64_t)nkv * PAGE * 128);
-            }
+            fork_tails(e, q0, tail_n, n_seq);
             // scoring passes: one sweep of the batched step's products each, then the final norm of the rows it fed
             for (int p = 0; p < passes; ++p) {
                 const MultiPass mp{d_cfeed + p * B, d_cslots + (size_t)p * MAXB, n_seq, r, std::min(L + (p + 1) * r, L + n_max - 1)};
                 decode_ops_batched(B, false, nullptr, &mp);
                 const int cnt = base[p + 2] - base[p + 1];
-                launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn + (size_t)base[p + 1] * H, d_src + base[p + 1], d_tap + base[p + 1], hid_tap, cnt, H, c.rms_eps);
+                launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn + (size_t)base[p + 1] * H, d.src + base[p + 1], d.tap + base[p + 1], hid_tap, cnt, H, c.rms_eps);
             }
             head_target_chunks(nf);
             HIP_CHECK(hipEventRecord(ph_ev[4], st));
             HIP_CHECK(hipStreamSynchronize(st));
             LAUNCH_CHECK("generate_candidates");
-            const int* h_tok = bf_host_i + 3 * R;
-            const float *h_score = bf_host_f + R, *h_lp = bf_host_f + 2 * R;
-            for (int q = 0; q < nf; ++q)
-                REQUIRE(h_tok[q] >= 0 && h_tok[q] < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+            require_finite_tokens(h.tok, nf);
             for (int g = 0; g < n_seq; ++g) {
                 for (int i = 0; i < lens[g]; ++i) {
                     const int q = hrow[off[g] + i], o = off[g] + i;
-                    greedy_ids[o] = h_tok[q]; greedy_logprobs[o] = h_score[q];
-                    if (allow_on) {
-                        const int pos = (int)(std::lower_bound(allow_ids.begin(), allow_ids.end(), (int)ids[o]) - allow_ids.begin());
-                        logprobs[o] = bf_host_alp[(size_t)q * allow_n + pos];
-                        grp.alp[g].insert(grp.alp[g].end(), bf_host_alp + (size_t)q * allow_n, bf_host_alp + (size_t)(q + 1) * allow_n);
-                    } else {
-                        logprobs[o] = h_lp[q];
-                    }
+                    greedy_ids[o] = h.tok[q]; greedy_logprobs[o] = h.score[q];
+                    logprobs[o] = forced_score(q, (int)ids[o], h.lp, bf_host_alp);
+                    if (allow_on) grp.alp[g].insert(grp.alp[g].end(), bf_host_alp + (size_t)q * allow_n, bf_host_alp + (size_t)(q + 1) * allow_n);
                     grp.scores[g].push_back(logprobs[o]);
                 }
                 grp.n_out[g] = lens[g];
@@ -3542,12 +3527,9 @@ public:
             drop_group();
             throw;
         }
-        {
-            float t = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[3])); ph_ms[1] += t;
-            HIP_CHECK(hipEventElapsedTime(&t, ph_ev[3], ph_ev[4])); ph_ms[2] += t;
-            if (vision_pending) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
-        }
+        add_phase(1, 2, 3);
+        add_phase(2, 3, 4);
+        settle_vision();
         e.kv_len = L;                     // until svln_group_select
         n_generated = 0;                  // (the single-env tap rows were overwritten)
         top2_stale = true;
@@ -3557,17 +3539,10 @@ public:
     void turn_candidates(const svln_turn_args& a, int n_seq, const int64_t* ids, const int32_t* lens, float* logprobs, int64_t* greedy_ids,
                          float* greedy_logprobs) override {
         env_at(a.env);
-        try {
+        begin_turn(a, [&] {
             REQUIRE(a.ids && a.n_ids >= 1 && logprobs && greedy_ids && greedy_logprobs, "svln_turn_candidates: null / empty argument");
             cand_refusals(a.env, n_seq, ids, lens, a.eos_ids, a.n_eos);
-            encode_frames(a.pixels, a.n_frames, a.pixels_on_device);
-            if (a.new_window) kv_reset(a.env);
-            if (a.new_episode && envs[a.env].n_embeds != 0) reset_env(a.env);
-            append_turn(a.env, a.ids, a.n_ids, 0, a.n_memory);
-        } catch (...) {
-            disarm_draft(a.env);
-            throw;
-        }
+        });
         generate_candidates(a.env, n_seq, ids, lens, a.eos_ids, a.n_eos, logprobs, greedy_ids, greedy_logprobs);
     }
     // ------------------------------------------------------------------------------- forced turns (svln_generate_forced)
@@ -3636,8 +3611,7 @@ public:
             REQUIRE(!single_scheme_on(),
                     who + ": a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm, "
                           "svln_set_decode_persistent); switch it off first");
-        if (!sched)
-            for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, who + " needs an idle scheduler (turns are in flight)");
+        if (!sched) refuse_unless_idle(who_c);
         if (allow_on)
             for (int k = 0; k < n; ++k)
                 REQUIRE(std::binary_search(allow_ids.begin(), allow_ids.end(), (int)ids[k]),
@@ -3652,12 +3626,10 @@ public:
         disarm_draft(env);              // consumed by this call, as svln_generate consumes it
         REQUIRE(logprobs && greedy_ids && greedy_logprobs, "svln_generate_forced: null output pointer");
         forced_refusals(env, ids, n, eos, n_eos);
-        REQUIRE(weights_missing() == 0, g_err);
-        const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
-        REQUIRE(Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
-        REQUIRE((int64_t)L + n - 1 <= c.max_positions, "svln_generate_forced: n_embeds + n - 1 exceeds max_positions");
+        const TurnPlan pl = plan_turn(e, "svln_generate_forced", n, n, "n");
+        const int P = pl.P, L = pl.L, Tn = pl.Tn;
         // ---- nothing was launched or changed up to here (but the armed draft)
-        last_scores_valid = false; last_alp_valid = false; last_topk_valid = false;
+        invalidate_last_results();
         set_speculative_buffers();      // d_draft / h_draft: the fed ids
         ensure_forced_buffers();
         ensure_pages(e, L + n - 1);
@@ -3698,25 +3670,16 @@ public:
         else HIP_CHECK(hipMemcpyAsync(h_flp, d_flp, n * sizeof(float), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         LAUNCH_CHECK("generate_forced");
-        for (int i = 0; i < n; ++i)
-            REQUIRE(h_tok_b[i] >= 0 && h_tok_b[i] < V, "non-finite logits: the arg-max found no finite value (check the weights / fp8 scales)");
+        require_finite_tokens(h_tok_b, n);
         for (int i = 0; i < n; ++i) {
             greedy_ids[i] = h_tok_b[i]; greedy_logprobs[i] = h_score_b[i];
-            if (allow_on) {
-                const int pos = (int)(std::lower_bound(allow_ids.begin(), allow_ids.end(), (int)ids[i]) - allow_ids.begin());
-                logprobs[i] = h_alp_b[(size_t)i * allow_n + pos];
-            } else {
-                logprobs[i] = h_flp[i];
-            }
+            logprobs[i] = forced_score(i, (int)ids[i], h_flp, h_alp_b);
         }
         last_scores.assign(logprobs, logprobs + n); last_scores_valid = true;
         if (allow_on) { last_alp.assign(h_alp_b, h_alp_b + (size_t)n * allow_n); last_alp_n = allow_n; last_alp_valid = true; }
         e.kv_len = L + n - 1;
-        {
-            float t = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&t, ph_ev[2], ph_ev[3])); ph_ms[1] += t;
-            if (vision_pending) { HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
-        }
+        add_phase(1, 2, 3);
+        settle_vision();
         n_generated = n;
         top2_stale = true;              // no top-2 logits were kept, as after a ride
         top2_sampled = false;
@@ -3726,17 +3689,10 @@ public:
                      int32_t* kv_len) override {
         env_at(a.env);
         refuse_while_group_on(a.env, "svln_turn_forced");
-        try {
+        begin_turn(a, [&] {
             REQUIRE(a.ids && a.n_ids >= 1 && logprobs && greedy_ids && greedy_logprobs, "svln_turn_forced: null / empty argument");
             forced_refusals(a.env, ids, n, a.eos_ids, a.n_eos);
-            encode_frames(a.pixels, a.n_frames, a.pixels_on_device);
-            if (a.new_window) kv_reset(a.env);
-            if (a.new_episode && envs[a.env].n_embeds != 0) reset_env(a.env);
-            append_turn(a.env, a.ids, a.n_ids, 0, a.n_memory);
-        } catch (...) {
-            disarm_draft(a.env);
-            throw;
-        }
+        });
         generate_forced(a.env, ids, n, a.eos_ids, a.n_eos, logprobs, greedy_ids, greedy_logprobs, kv_len);
     }
     // TEST-ONLY: one EPI_TARGET product and its final kernel on caller-given device operands, whatever the engine's switches say
@@ -4130,7 +4086,7 @@ public:
     }
     void phase_times(double* v, double* p, double* d, int reset) override {
         HIP_CHECK(hipStreamSynchronize(st));
-        if (vision_pending) { float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ph_ev[0], ph_ev[1])); ph_ms[0] += t; vision_pending = false; }
+        settle_vision();
         *v = ph_ms[0]; *p = ph_ms[1]; *d = ph_ms[2];
         if (reset) ph_ms[0] = ph_ms[1] = ph_ms[2] = 0;
     }
@@ -4575,8 +4531,7 @@ public:
         }
         sync();
         for (int d = 0; d < n_dst; ++d) h_fork_dst[d] = dst_pages[d];
-        HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)n_dst * sizeof(int), hipMemcpyHostToDevice, st));
-        launch_kv_page_copy<T>(st, d_pool_tab, 2 * c.layers, src_page, d_fork_dst, n_dst, (int64_t)nkv * PAGE * 128);
+        fork_page_copy(src_page, n_dst);
         sync();
         LAUNCH_CHECK("op_kv_page_copy");
     }
@@ -4869,7 +4824,7 @@ public:
         for (int s = 0; s < S; ++s) {
             h_slots[s].pos = ctx_len[s]; h_slots[s].pad = rows[s];
             if (!share || s == 0) { h_slots[s].page_table = envs[s].d_pages; continue; }
-            if (!fork_tab[s]) { fork_tab[s] = dalloc<int>(pages_per_env, true); fork_host[s].assign(pages_per_env, 0); }
+            ensure_fork_tab(s);
             std::vector<int>& tab = fork_host[s];
             for (int i = 0; i < q0; ++i) tab[i] = envs[0].pages[i];
             for (int i = q0; i < envs[s].n_pages; ++i) tab[i] = envs[s].pages[i];
@@ -4877,10 +4832,7 @@ public:
             h_slots[s].page_table = fork_tab[s];
             if (ctx_len[0] % PAGE != 0 && envs[s].n_pages > q0) h_fork_dst[n_dst++] = envs[s].pages[q0];
         }
-        if (n_dst > 0) {
-            HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)n_dst * sizeof(int), hipMemcpyHostToDevice, st));
-            launch_kv_page_copy<T>(st, d_pool_tab, 2 * c.layers, envs[0].pages[q0], d_fork_dst, n_dst, (int64_t)nkv * PAGE * 128);
-        }
+        if (n_dst > 0) fork_page_copy(envs[0].pages[q0], n_dst);
         HIP_CHECK(hipMemcpyAsync(d_slots, h_slots, S * sizeof(DecodeSlot), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipMemcpy2DAsync(qkv, (size_t)qkv_dim * sizeof(T), qkv_new, (size_t)ld * sizeof(T), (size_t)qkv_dim * sizeof(T), (size_t)S * Tm,
                                    hipMemcpyDeviceToDevice, st));
