@@ -242,6 +242,35 @@ int svln_get_topk(svln_engine* h, int32_t* host_ids, float* host_logprobs, int c
  * last svln_generate_batch; both refused when k was 0 for that turn. */
 int svln_batch_topk(svln_engine* h, int slot, int32_t* host_ids, float* host_logprobs, int cap_rows, int32_t* n_rows, int32_t* k);
 int svln_generate_batch_topk(svln_engine* h, int index, int32_t* host_ids, float* host_logprobs, int cap_rows, int32_t* n_rows, int32_t* k);
+/* Opt-in, default off, no reference counterpart: token entropies -- how spread the policy's distribution was at every emitted id.
+ * While on, every lm_head product (the single-env GEMV in all four weight formats, the batched GEMV and the 32 x 128 MFMA tiles) runs
+ * the sibling of its scored or sampled kernel that keeps, beside every partial's (max m, sum s = sum exp(y - m)), one more fp32
+ * t = sum (y - m) exp(y - m), and one small merge kernel per head pass writes H = log S - T / S in nats, fp32, with (V, S) the very merge
+ * the scored kernels compute and T = sum_n (y_n - V) exp(y_n - V) merged like S.  y_n is the PROCESSED fp32 logit x_n (after the
+ * repetition penalty) under greedy decoding and fl(x_n * invT) under svln_set_sampling (the unperturbed value, never y + noise).  A -inf
+ * column adds 0; a NaN logit makes the row's entropy NaN; a row without a finite value (token -1) gives NaN; a one-column row gives
+ * exactly 0.  Under svln_set_allowed_tokens the entropy is over the allowed set.  Tokens, scores, hidden rows, cache lengths and every
+ * existing partial are bit-identical to the switch off: same accumulators, same compares, same orders; with the switch off every launch
+ * is the kernel that ran before.  No logit reaches memory and the lm_head is not read twice.
+ * The name is deliberately not svln_set_*: like svln_top_logprobs the switch is tied to svln_set_token_scores and is no independent row
+ * of the switch-pair table the tests keep for every svln_set_* prototype.  Rules: switching on is refused while svln_set_token_scores
+ * is off (naming it), and svln_set_token_scores(0) is refused while on (naming svln_token_entropy) -- so every mode the scores refuse
+ * (the draft switches, svln_set_decode_persistent, svln_set_mxfp4_batched) is unreachable.  Composes with svln_set_fp8_decode /
+ * svln_set_mxfp4_decode / svln_set_packed_decode (the entropy is of their own lm_head formats), svln_set_fp8_gemm /
+ * svln_set_fp8_scaled_mfma, the repetition penalty, svln_set_sampling without truncation, svln_set_allowed_tokens, graph replay (captured
+ * decode graphs are keyed by the switch and dropped when it changes), svln_generate / svln_turn, svln_generate_batch and the scheduler's
+ * plain turns.  Refused both ways, naming the other function: svln_top_logprobs with k > 0 and svln_sampling_truncation with top_k > 0
+ * (their epilogues are the candidate siblings, which have no entropy form yet).  Refused while on, naming svln_token_entropy: group,
+ * beam, candidate and forced turns and svln_batch_submit_forced.  Refused: a change while scheduler turns are in flight or a group is
+ * pending.  A call that changes nothing succeeds.
+ * svln_get_token_entropy: the entropies of the last single-env turn, one per emitted id (min(n, cap) are written), read in the
+ * synchronisation that reads the ids; refused when the switch was off for that turn, after a forced turn, or before any.
+ * svln_batch_entropy / svln_generate_batch_entropy: those of the finished scheduler turn in `slot` (valid until svln_batch_result frees
+ * the slot) and of env index `index` of the last svln_generate_batch; both refused when the switch was off for that turn. */
+int svln_token_entropy(svln_engine* h, int enable);
+int svln_get_token_entropy(svln_engine* h, float* host_out, int cap, int32_t* n);
+int svln_batch_entropy(svln_engine* h, int slot, float* host_out, int cap, int32_t* n);
+int svln_generate_batch_entropy(svln_engine* h, int index, float* host_out, int cap, int32_t* n);
 int svln_get_token_scores(svln_engine* h, float* host_out, int cap, int32_t* n);
 int svln_batch_scores(svln_engine* h, int slot, float* host_out, int cap, int32_t* n);
 int svln_generate_batch_scores(svln_engine* h, int index, float* host_out, int cap, int32_t* n);
@@ -801,6 +830,30 @@ int svln_op_gemm_argmax_topk(svln_engine* h, const void* A, int lda, const void*
                              const int32_t* pen_rows, float penalty, int k, int sampled, float temperature, uint64_t seed, const int32_t* streams,
                              const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* cand_val, int32_t* cand_idx, int32_t* top_ids,
                              float* top_logprobs, int32_t* n_part);
+/* TEST-ONLY: the three lm_head forms under svln_token_entropy on caller-given operands -- the EPI_ARGMAX_LSE_ENT product (sampled != 0:
+ * EPI_SAMPLE_ENT on temperature, seed, stream(s), draw(s)), the entropy merge and the scored / sampled final kernel.  Arguments as
+ * svln_op_gemv_argmax_topk (fmt 0 .. 3), svln_op_gemv_batched_argmax_topk and svln_op_gemm_argmax_topk without k and the lists.  Outputs
+ * (host): tokens, scores and entropies [rows]; the partial arrays [rows][*n_part] including part_ent (part_raw / part_max: sampled form
+ * only, may be null otherwise).  Arrays must hold 2048 partials per row.  The refusals of the _scores / _sample entries apply, plus null
+ * outputs -- before any launch. */
+int svln_op_gemv_argmax_entropy(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
+                                float penalty, int sampled, float temperature, uint64_t seed, int32_t stream, int32_t draw, int32_t* host_token,
+                                float* host_logprob, float* host_entropy, float* part_val, int32_t* part_idx, float* part_sum, float* part_raw,
+                                float* part_max, float* part_ent, int32_t* n_part);
+int svln_op_gemv_batched_argmax_entropy(svln_engine* h, const void* W, int ldw, const void* x, int ldx, int N, int K, int B, const void* pen_flags,
+                                        const int32_t* pen_rows, float penalty, int sampled, float temperature, uint64_t seed, const int32_t* streams,
+                                        const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* host_entropies, float* part_val,
+                                        int32_t* part_idx, float* part_sum, float* part_raw, float* part_max, float* part_ent, int32_t* n_part);
+int svln_op_gemm_argmax_entropy(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
+                                const int32_t* pen_rows, float penalty, int sampled, float temperature, uint64_t seed, const int32_t* streams,
+                                const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* host_entropies, float* part_val,
+                                int32_t* part_idx, float* part_sum, float* part_raw, float* part_max, float* part_ent, int32_t* n_part);
+/* TEST-ONLY: the merge kernel of svln_token_entropy on host partial rows [B][n_part] (layout and meaning of the epilogues' arrays).
+ * part_max null: the greedy form, the sums are relative to part_val and (V, none) come from (part_val, part_idx); else the sampled form
+ * on (part_max, part_sum).  part_ent null: every t is 0 (one id per partial, the subset product).  host_entropies [B].  Refused before
+ * any launch: B outside 1 .. 32, n_part outside 1 .. 2048 (checked first), then null part_val / part_idx / part_sum / host_entropies. */
+int svln_op_entropy_merge(svln_engine* h, const float* part_val, const int32_t* part_idx, const float* part_sum, const float* part_max,
+                          const float* part_ent, int B, int n_part, float* host_entropies);
 /* TEST-ONLY: the truncation kernel of svln_sampling_truncation followed by the batched sampled final kernel, on host candidates
  * cand_val / cand_idx [B][n_part][c] (c = 8: lists as the EPI_SAMPLE_TOPK epilogues write them, padded with (-inf, 0x7FFFFFFF); c = 1:
  * one candidate per partial, as under an allowed list).  The values are y as they stand (already times 1 / T: `temperature` is checked

@@ -134,6 +134,17 @@ SIGNATURES = {
                                               _PI32, _PI32, _PF, _PI32]),
     "svln_op_gemm_argmax_topk": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _I, _I, _F, _U64, _PI32, _PI32, _PI32, _PF, _PF, _PI32,
                                       _PI32, _PF, _PI32]),
+    "svln_token_entropy": (_I, [_P, _I]),
+    "svln_get_token_entropy": (_I, [_P, _PF, _I, _PI32]),
+    "svln_batch_entropy": (_I, [_P, _I, _PF, _I, _PI32]),
+    "svln_generate_batch_entropy": (_I, [_P, _I, _PF, _I, _PI32]),
+    "svln_op_gemv_argmax_entropy": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _F, _I, _F, _U64, C.c_int32, C.c_int32, _PI32, _PF, _PF, _PF, _PI32, _PF,
+                                         _PF, _PF, _PF, _PI32]),
+    "svln_op_gemv_batched_argmax_entropy": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _I, _F, _U64, _PI32, _PI32, _PI32, _PF, _PF, _PF, _PI32,
+                                                 _PF, _PF, _PF, _PF, _PI32]),
+    "svln_op_gemm_argmax_entropy": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _I, _F, _U64, _PI32, _PI32, _PI32, _PF, _PF, _PF, _PI32, _PF,
+                                         _PF, _PF, _PF, _PI32]),
+    "svln_op_entropy_merge": (_I, [_P, _PF, _PI32, _PF, _PF, _PF, _I, _I, _PF]),
     "svln_get_token_scores": (_I, [_P, _PF, _I, _PI32]),
     "svln_batch_scores": (_I, [_P, _I, _PF, _I, _PI32]),
     "svln_generate_batch_scores": (_I, [_P, _I, _PF, _I, _PI32]),

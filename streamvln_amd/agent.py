@@ -91,6 +91,10 @@ class StreamingAgent:
         # log-probabilities [1, n_new, k]; None otherwise
         self.last_top_token_ids = None
         self.last_top_logprobs = None
+        # how undecided the policy was at every id of the last model turn (model.set_token_entropy): the entropy, in nats, of the
+        # distribution each id was taken from [1, n_new] and their mean over the turn; None when the model provides none
+        self.last_token_entropies = None
+        self.last_turn_entropy = None
         # the policy's own arg-max at every position of the last FORCED model turn (act(..., forced_ids=...)): [1, n]; None otherwise
         self.last_greedy_ids = None
         # the joint log-probability of every candidate of the last candidates turn (act(..., candidate_ids=...)): [G]; the index taken
@@ -156,6 +160,9 @@ class StreamingAgent:
         self.last_greedy_ids = out.get("greedy_ids") if isinstance(out, dict) else getattr(out, "greedy_ids", None)
         self.last_top_token_ids = out.get("top_token_ids") if isinstance(out, dict) else getattr(out, "top_token_ids", None)
         self.last_top_logprobs = out.get("top_logprobs") if isinstance(out, dict) else getattr(out, "top_logprobs", None)
+        ent = out.get("token_entropies") if isinstance(out, dict) else getattr(out, "token_entropies", None)
+        self.last_token_entropies = ent
+        self.last_turn_entropy = None if ent is None else float(ent.mean())
         self.turn_log.append(dict(self._pending, out=out))
         actions = list(self.decode_actions(out.sequences))
         return actions if len(actions) else [0]               # streamvln_eval.py:340-341

@@ -146,6 +146,20 @@ SVLN_DEV void lse_add(float v, float& m, float& s) {
 SVLN_DEV float lse_rescale(float s, float m, float V) { return s == 0.0f ? 0.0f : s * lse_exp(m - V); }
 // log-probability of the winning logit from S = sum exp(l - V) >= 1
 SVLN_DEV float lse_logprob(float S) { return -0.6931471805599453f * __builtin_amdgcn_logf(S); }
+// Entropy pieces of the EPI_*_ENT forms (svln_token_entropy): a partial carries t = sum (l - m) exp(l - m) beside (m, s); the row's
+// entropy is log S - T / S with T merged like S.  ent_term: one logit's share seen from m (a -inf logit adds 0, not -inf * 0; NaN stays).
+SVLN_DEV float ent_term(float v, float m) { const float d = v - m; return v == -INFINITY ? 0.0f : d * lse_exp(d); }
+// logit v joins (m, s, t): lse_add's own (m, s) update -- the same expressions, hence the same bits -- and t beside it.  A new maximum
+// shifts t by (m - v) s before the rescale; the empty state stays t = 0 (not (-inf - v) * 0)
+SVLN_DEV void ent_add(float v, float& m, float& s, float& t) {
+    if (v > m) t = s == 0.0f ? 0.0f : (t + (m - v) * s) * lse_exp(m - v);
+    else t += ent_term(v, m);
+    lse_add(v, m, s);
+}
+// (m, s, t) seen from a maximum V >= m: the t beside lse_rescale(s, m, V); the empty partial is 0 whatever V is (a NaN sum stays NaN)
+SVLN_DEV float ent_rescale(float t, float s, float m, float V) { return s == 0.0f ? 0.0f : (t + (m - V) * s) * lse_exp(m - V); }
+// H = log S - T / S in nats
+SVLN_DEV float ent_value(float S, float T) { return 0.6931471805599453f * __builtin_amdgcn_logf(S) - T / S; }
 
 // ---- merges of one row's arg-max partials on a 256-thread workgroup (the final kernels of gemv.hip, topk_merge_kernel of misc.hip)
 // S = sum over the 256 threads' shares `mine` of the rescaled partial sums, through `red` (a fixed tree: the same bits every launch)

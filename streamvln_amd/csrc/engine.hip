@@ -69,6 +69,9 @@ struct Slot {            // canonical tensor -> where its rows live in the packe
 struct OpSample { float temperature; uint64_t seed; const int32_t* streams; const int32_t* draws; };
 // the outputs of the batched test entries under svln_top_logprobs (null: the scored / sampled entries): k, candidates [rows][n][8], lists [rows][k]
 struct OpTopkRows { int k; float* cv; int32_t* ci; int32_t* top_ids; float* top_lp; int32_t* n_part; };
+// the outputs of the test entries under svln_token_entropy (null: the scored / sampled entries): the entropies [rows], every partial array
+// [rows][n] (pr / pm: the sampled form only) and n
+struct OpEntOut { float* ent; float* pv; int32_t* pi; float *ps, *pr, *pm, *pe; int32_t* n_part; };
 struct EngineBase {
     virtual ~EngineBase() {}
     virtual void synth_tensor(const char* name, uint64_t seed_t, float hw, float base) = 0;
@@ -114,9 +117,16 @@ struct EngineBase {
     virtual void get_token_scores(float* out, int cap, int32_t* n) = 0;
     virtual void batch_scores(int slot, float* out, int cap, int32_t* n) = 0;
     virtual void generate_batch_scores(int index, float* out, int cap, int32_t* n) = 0;
-    virtual void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob, const OpSample* smp) = 0;
-    virtual void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk = nullptr) = 0;
-    virtual void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk = nullptr) = 0;
+    virtual void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob, const OpSample* smp, const OpEntOut* en = nullptr) = 0;
+    virtual void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk = nullptr,
+                                        const OpEntOut* en = nullptr) = 0;
+    virtual void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk = nullptr,
+                                       const OpEntOut* en = nullptr) = 0;
+    virtual void token_entropy(int enable) = 0;
+    virtual void get_token_entropy(float* out, int cap, int32_t* n) = 0;
+    virtual void batch_entropy(int slot, float* out, int cap, int32_t* n) = 0;
+    virtual void generate_batch_entropy(int index, float* out, int cap, int32_t* n) = 0;
+    virtual void op_entropy_merge(const float* pv, const int32_t* pi, const float* ps, const float* pm, const float* pe, int B, int n_part, float* out) = 0;
     virtual void set_sampling(int enable, float temperature, uint64_t seed) = 0;
     virtual void sampling_truncation(int top_k, float top_p) = 0;
     virtual void op_truncate(const float* cv, const int32_t* ci, int B, int n_part, int cc, const OpSample* q, int top_k, float top_p, float* pv,
@@ -315,6 +325,22 @@ public:
         HIP_CHECK(hipHostMalloc((void**)&h_topl_b, (size_t)(HEAD_ROWS + MAXB) * TOPK_C * sizeof(float)));
     }
     std::vector<float> last_scores; bool last_scores_valid = false;           // of the last svln_generate / svln_turn / svln_generate_fixed
+    // Opt-in token entropies (svln_token_entropy; tied to svln_set_token_scores as svln_top_logprobs is): while ent_on every lm_head product
+    // runs the EPI_*_ENT sibling of its scored or sampled form (part_ent / part_ent_b: one more fp32 beside every partial sum; the subset
+    // product of an allowed list stays as it is: one id per partial, t = 0) and entropy_merge_kernel writes d_ent[count] beside
+    // d_scores[count], d_ent_b[tok0 + b] beside d_score_b.  The final / step kernels are untouched.
+    bool ent_on = false;
+    float *part_ent = nullptr, *part_ent_b = nullptr, *d_ent = nullptr, *h_ent = nullptr, *d_ent_b = nullptr, *h_ent_b = nullptr;
+    std::vector<float> last_ent; bool last_ent_valid = false;
+    std::vector<std::vector<float>> gb_ent; bool gb_ent_valid = false;
+    void ensure_ent_buffers() {
+        if (part_ent) return;
+        const size_t rows = (size_t)c.max_positions + 8;
+        part_ent = dalloc<float>(2048); part_ent_b = dalloc<float>((size_t)HEAD_ROWS * 2048);
+        d_ent = dalloc<float>(rows, true); d_ent_b = dalloc<float>(HEAD_ROWS + MAXB, true);
+        HIP_CHECK(hipHostMalloc((void**)&h_ent, rows * sizeof(float)));
+        HIP_CHECK(hipHostMalloc((void**)&h_ent_b, (HEAD_ROWS + MAXB) * sizeof(float)));
+    }
     // Opt-in temperature sampling (svln_set_sampling; no reference counterpart): every lm_head product runs its EPI_SAMPLE sibling
     // (kernels.h): token = argmax_n (fl(x_n * inv_t) + G(seed, stream, draw, n)), an exact sample of softmax(x / T).  stream = the env slot,
     // draw = env_draws[env] + the tokens of this turn.  A single-env turn carries both in GenCtl (draw0, stream); the scheduler uploads
@@ -433,7 +459,7 @@ public:
     // envs through svln_generate replays instead of re-capturing); [0] = the whole step, [1] / [2] = the halves around the probed launch
     // (captured only while the roofline probe is on); a run-ahead batch of several steps is one graph.
     bool use_graph = false;
-    struct GraphSet { std::unordered_map<int, hipGraphExec_t> ex; };     // key: steps (whole batch) | 1000 (head of a probed step) | 2000 + steps (its tail) | 3000 + rows (verify pass); + 10000 with svln_set_token_scores, + 20000 with svln_set_sampling, + 40000 with svln_set_packed_decode, + 100000 k with svln_top_logprobs(k)
+    struct GraphSet { std::unordered_map<int, hipGraphExec_t> ex; };     // key: steps (whole batch) | 1000 (head of a probed step) | 2000 + steps (its tail) | 3000 + rows (verify pass); + 10000 with svln_set_token_scores, + 20000 with svln_set_sampling, + 40000 with svln_set_packed_decode, + 100000 k with svln_top_logprobs(k), + 1000000 with svln_token_entropy
     std::vector<GraphSet> graphs;
     std::unordered_map<int, hipGraphExec_t> bgraphs;          // batched decode step: key = B | penalty << 8 | fp8 gemm << 9 | MXFP4 batched << 10 | scaled fp8 form << 11 | token scores << 12
     // per-turn truncation of the spliced rows (the reference's config.tokenizer_model_max_length, stream_video_vln.py:241-244); 0 = none
@@ -680,6 +706,8 @@ public:
         if (h_topl) (void)hipHostFree(h_topl);
         if (h_topi_b) (void)hipHostFree(h_topi_b);
         if (h_topl_b) (void)hipHostFree(h_topl_b);
+        if (h_ent) (void)hipHostFree(h_ent);
+        if (h_ent_b) (void)hipHostFree(h_ent_b);
         if (h_smp) (void)hipHostFree(h_smp);
         if (h_fork_dst) (void)hipHostFree(h_fork_dst);
         if (h_alp) (void)hipHostFree(h_alp);
@@ -831,7 +859,7 @@ public:
     }
     // the small lines every turn form shares: the results of the last single-env turn, the phase timers (events v0 v1 p0 p1 d1 of ph_ev,
     // read after a synchronisation), the check of the ids a synchronisation read
-    void invalidate_last_results() { last_scores_valid = false; last_alp_valid = false; last_topk_valid = false; }
+    void invalidate_last_results() { last_scores_valid = false; last_alp_valid = false; last_topk_valid = false; last_ent_valid = false; }
     void add_phase(int k, int ev_from, int ev_to) { float t = 0.f; HIP_CHECK(hipEventElapsedTime(&t, ph_ev[ev_from], ph_ev[ev_to])); ph_ms[k] += t; }
     void settle_vision() { if (vision_pending) { add_phase(0, 0, 1); vision_pending = false; } }
     void require_finite_tokens(const int* tok, int n) {
@@ -1407,6 +1435,8 @@ public:
         // svln_top_logprobs: the lists of this token -> d_topi / d_topl [count], before the step kernel advances the count
         const int* trow = gen ? &d_ctl->count : nullptr;
         if (topk || trunc_k) { a.epi = smp_on ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK; a.cand_val = cand_val; a.cand_idx = cand_idx; }
+        // svln_token_entropy (never with the lists or the truncation): the entropy of this token's distribution -> d_ent[count]
+        if (ent_on) { a.epi = smp_on ? EPI_SAMPLE_ENT : EPI_ARGMAX_LSE_ENT; a.part_ent = part_ent; }
         if (trunc_k) {
             // svln_sampling_truncation: the product as it stands, then the candidates -> the 8-entry row tr_*, which the step / final
             // kernel and the lists' merge read in place of the product's partials (under an allowed list: its partials are the candidates)
@@ -1436,9 +1466,11 @@ public:
             if (scores_on) launch_subset_logprobs(st, smp_on ? part_max : part_val, allow_n, 1, d_alp, gen ? &d_ctl->count : nullptr, skip);
             n_part = allow_n;
             if (topk) launch_topk_merge(st, smp_on ? part_max : part_val, part_idx, n_part, 1, 1, topk, part_val, part_idx, part_sum, pm, d_topi, d_topl, trow, skip);
+            if (ent_on) launch_entropy_merge(st, part_val, part_idx, part_sum, pm, nullptr, n_part, 1, d_ent, trow, skip);
         } else {
             launch_gemv<T>(st, a);
             if (topk) launch_topk_merge(st, cand_val, cand_idx, n_part, TOPK_C, 1, topk, part_val, part_idx, part_sum, pm, d_topi, d_topl, trow, skip);
+            if (ent_on) launch_entropy_merge(st, part_val, part_idx, part_sum, pm, part_ent, n_part, 1, d_ent, trow, skip);
         }
         if (gen) launch_argmax_step(st, part_val, part_idx, n_part, d_token, d_top2, d_ctl, d_eos, d_out_ids, pen ? pen_flags : nullptr, ps, d_scores, pr, pm);
         else launch_argmax_final(st, part_val, part_idx, n_part, d_token, d_top2, ps, d_scores, pr, pm);
@@ -1609,7 +1641,7 @@ public:
         const bool probing = probe_on && first_tap_row == 1 && probe_used + 2 <= probe_ev.size();
         if (use_graph) {
             GraphSet& gs = graphs[env];
-            const int sk = (scores_on ? 10000 : 0) + (smp_on ? 20000 : 0) + (p12_on ? 40000 : 0) + 100000 * topk;      // the captured head is the plain, the scored or the sampled one; the GEMVs read the packed weights or not
+            const int sk = (scores_on ? 10000 : 0) + (smp_on ? 20000 : 0) + (p12_on ? 40000 : 0) + 100000 * topk + (ent_on ? 1000000 : 0);      // the captured head is the plain, the scored or the sampled one; the GEMVs read the packed weights or not
             auto get = [&](int key, int lo, int hi, int more) {
                 auto it = gs.ex.find(key);
                 if (it == gs.ex.end()) it = gs.ex.emplace(key, capture(e, lo, hi, more)).first;
@@ -1691,6 +1723,7 @@ public:
             if (scores_on) launch_subset_logprobs(st, smp_on ? part_max_b : part_val_b, allow_n, B, d_alp_b + (size_t)tok0 * allow_n);
             launch_argmax_final_batched(st, part_val_b, part_idx_b, allow_n, B, d_tok_b + tok0, ps, d_score_b + tok0, nullptr, pr, pm);
             if (topk) launch_topk_merge(st, smp_on ? part_max_b : part_val_b, part_idx_b, allow_n, 1, B, topk, part_val_b, part_idx_b, part_sum_b, pm, d_topi_b + (size_t)tok0 * topk, d_topl_b + (size_t)tok0 * topk);
+            if (ent_on) launch_entropy_merge(st, part_val_b, part_idx_b, part_sum_b, pm, nullptr, allow_n, B, d_ent_b + tok0);
             return;
         }
         if (B >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048) {
@@ -1700,9 +1733,11 @@ public:
             if (smp_on) a.smp = sa;
             if (pen) { a.pen_flags = pen_flags_b; a.pen_rows = d_pen_rows; a.pen = rep_penalty; }
             if (topk) { a.cand_val = cand_val_b; a.cand_idx = cand_idx_b; }
+            if (ent_on) a.part_ent = part_ent_b;
             const int n = launch_gemm_argmax<T>(st, a);
             launch_argmax_final_batched(st, part_val_b, part_idx_b, n, B, d_tok_b + tok0, ps, d_score_b + tok0, nullptr, pr, pm);
             if (topk) launch_topk_merge(st, cand_val_b, cand_idx_b, n, TOPK_C, B, topk, part_val_b, part_idx_b, part_sum_b, pm, d_topi_b + (size_t)tok0 * topk, d_topl_b + (size_t)tok0 * topk);
+            if (ent_on) launch_entropy_merge(st, part_val_b, part_idx_b, part_sum_b, pm, part_ent_b, n, B, d_ent_b + tok0);
             return;
         }
         GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, smp_on ? EPI_SAMPLE : scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX, B);
@@ -1710,9 +1745,11 @@ public:
         if (smp_on) hb.smp = sa;
         if (pen) { hb.pen_flags = pen_flags_b; hb.pen_rows = d_pen_rows; hb.pen = rep_penalty; }
         if (topk) { hb.epi = smp_on ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK; hb.cand_val = cand_val_b; hb.cand_idx = cand_idx_b; }
+        if (ent_on) { hb.epi = smp_on ? EPI_SAMPLE_ENT : EPI_ARGMAX_LSE_ENT; hb.part_ent = part_ent_b; }
         launch_gemv_batched<T>(st, hb);
         launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(N, EPI_ARGMAX, B), B, d_tok_b + tok0, ps, d_score_b + tok0, nullptr, pr, pm);
         if (topk) launch_topk_merge(st, cand_val_b, cand_idx_b, gemv_batched_grid(N, EPI_ARGMAX, B), TOPK_C, B, topk, part_val_b, part_idx_b, part_sum_b, pm, d_topi_b + (size_t)tok0 * topk, d_topl_b + (size_t)tok0 * topk);
+        if (ent_on) launch_entropy_merge(st, part_val_b, part_idx_b, part_sum_b, pm, part_ent_b, gemv_batched_grid(N, EPI_ARGMAX, B), B, d_ent_b + tok0);
     }
     void head_batched(const T* rows, int B, bool pen = false) {
         launch_rmsnorm<T>(st, rows, final_norm, xn, B, H, c.rms_eps);
@@ -1902,6 +1939,7 @@ public:
         REQUIRE(top_k >= 0 && top_k <= TOPK_C, "svln_sampling_truncation: top_k must be 0 (off) .. 8");
         REQUIRE(top_p > 0.0f && top_p <= 1.0f, "svln_sampling_truncation: top_p must lie in (0, 1]");
         REQUIRE(top_k > 0 || top_p >= 1.0f, "svln_sampling_truncation: top_p < 1 needs top_k = 1 .. 8 (the nucleus is taken over at most 8 listed ids)");
+        REQUIRE(top_k == 0 || !ent_on, "svln_sampling_truncation: token entropies are on (svln_token_entropy), whose epilogue has no candidate form; switch them off first");
         refuse_while_group("svln_sampling_truncation");
         refuse_while_jobs("svln_sampling_truncation");
         if (top_k == trunc_k && top_p == trunc_p) return;      // nothing changes (off stays off whatever the switches are)
@@ -1982,6 +2020,7 @@ public:
         refuse_while_group("svln_set_token_scores");
         if (want == scores_on) return;         // nothing changes
         REQUIRE(want || topk == 0, "svln_set_token_scores: top-k log-probabilities are on (svln_top_logprobs); switch them off first");
+        REQUIRE(want || !ent_on, "svln_set_token_scores: token entropies are on (svln_token_entropy); switch them off first");
         refuse_while_jobs("svln_set_token_scores");
         if (want) {
             refuse_while_plain_head_only("svln_set_token_scores");
@@ -1999,6 +2038,7 @@ public:
         if (k == topk) return;                 // nothing changes
         refuse_while_jobs("svln_top_logprobs");
         REQUIRE(k == 0 || scores_on, "svln_top_logprobs: token log-probabilities are off (svln_set_token_scores); switch them on first");
+        REQUIRE(k == 0 || !ent_on, "svln_top_logprobs: token entropies are on (svln_token_entropy), whose epilogue has no candidate form; switch them off first");
         REQUIRE(k == 0 || (size_t)H * sizeof(float) <= (size_t)GEMV_ROWS_TOPK_MAX_LDS, "svln_top_logprobs: the hidden size is too large for the candidate form of the lm_head GEMV");
         HIP_CHECK(hipStreamSynchronize(st));
         if (k) ensure_topk_buffers();
@@ -2028,6 +2068,64 @@ public:
         REQUIRE(gb_topk_valid, "svln_generate_batch_topk: top-k log-probabilities were off for the last svln_generate_batch (svln_top_logprobs), or none has run");
         REQUIRE(index >= 0 && index < (int)gb_topi.size(), "svln_generate_batch_topk: no such env index in the last batch");
         topk_out(gb_topi[index], gb_topl[index], gb_topk, ids, logprobs, cap_rows, n_rows, k);
+    }
+    // svln_token_entropy.  The entropies ride on the scored / sampled kernels' partials, so the scores must be on (and stay on): every
+    // mode the scores refuse is thereby unreachable.  The _TOPK epilogues (svln_top_logprobs, svln_sampling_truncation) have no entropy
+    // form: refused both ways.  Group, beam, candidate and forced turns carry no entropies: refused while on.
+    void token_entropy(int enable) override {
+        const bool want = enable != 0;
+        refuse_while_group("svln_token_entropy");
+        if (want == ent_on) return;            // nothing changes
+        refuse_while_jobs("svln_token_entropy");
+        if (want) {
+            REQUIRE(scores_on, "svln_token_entropy: token log-probabilities are off (svln_set_token_scores); switch them on first");
+            REQUIRE(topk == 0, "svln_token_entropy: top-k log-probabilities are on (svln_top_logprobs), whose epilogue has no entropy form; switch them off first");
+            REQUIRE(trunc_k == 0, "svln_token_entropy: truncated sampling is on (svln_sampling_truncation), whose epilogue has no entropy form; switch it off first");
+        }
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (want) ensure_ent_buffers();
+        drop_graphs();           // the captured lm_head launch is the sibling with or without t; the merge is in the graph or not
+        ent_on = want;
+    }
+    void refuse_while_entropy(const std::string& who) {
+        REQUIRE(!ent_on, who + ": token entropies are on (svln_token_entropy), which this turn form does not carry; switch them off first");
+    }
+    static void floats_out(const std::vector<float>& v, float* out, int cap, int32_t* n) {
+        const int m = (int)v.size();
+        for (int k = 0; k < m && k < cap; ++k) out[k] = v[k];
+        *n = m;
+    }
+    void get_token_entropy(float* out, int cap, int32_t* n) override {
+        REQUIRE(last_ent_valid, "svln_get_token_entropy: token entropies were off for the last turn (svln_token_entropy), the last turn was forced, or no turn has run");
+        floats_out(last_ent, out, cap, n);
+    }
+    void batch_entropy(int slot, float* out, int cap, int32_t* n) override {
+        REQUIRE(slot >= 0 && slot < MAXB && jobs[slot].used && jobs[slot].finished, "no finished turn in this slot");
+        REQUIRE(jobs[slot].ent_on, "svln_batch_entropy: token entropies were off for this turn (svln_token_entropy)");
+        floats_out(jobs[slot].ent, out, cap, n);
+    }
+    void generate_batch_entropy(int index, float* out, int cap, int32_t* n) override {
+        REQUIRE(gb_ent_valid, "svln_generate_batch_entropy: token entropies were off for the last svln_generate_batch (svln_token_entropy), or none has run");
+        REQUIRE(index >= 0 && index < (int)gb_ent.size(), "svln_generate_batch_entropy: no such env index in the last batch");
+        floats_out(gb_ent[index], out, cap, n);
+    }
+    // TEST-ONLY: entropy_merge_kernel on host partial rows [B][n_part]; pm null: the greedy form, pe null: every t = 0
+    void op_entropy_merge(const float* pv, const int32_t* pi, const float* ps, const float* pm, const float* pe, int B, int n_part, float* out) override {
+        REQUIRE(B >= 1 && B <= 32, "svln_op_entropy_merge: 1 <= B <= 32 rows");
+        REQUIRE(n_part >= 1 && n_part <= 2048, "svln_op_entropy_merge: 1 <= n_part <= 2048 partials per row");
+        REQUIRE(pv && pi && ps && out, "svln_op_entropy_merge: null pointer");
+        ensure_ent_buffers();
+        const size_t nb = (size_t)B * n_part;
+        HIP_CHECK(hipMemcpyAsync(part_val_b, pv, nb * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(part_idx_b, pi, nb * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(part_sum_b, ps, nb * sizeof(float), hipMemcpyHostToDevice, st));
+        if (pm) HIP_CHECK(hipMemcpyAsync(part_max_b, pm, nb * sizeof(float), hipMemcpyHostToDevice, st));
+        if (pe) HIP_CHECK(hipMemcpyAsync(part_ent_b, pe, nb * sizeof(float), hipMemcpyHostToDevice, st));
+        launch_entropy_merge(st, part_val_b, part_idx_b, part_sum_b, pm ? part_max_b : nullptr, pe ? part_ent_b : nullptr, n_part, B, d_ent_b);
+        HIP_CHECK(hipMemcpyAsync(h_ent_b, d_ent_b, B * sizeof(float), hipMemcpyDeviceToHost, st));
+        sync();
+        LAUNCH_CHECK("op_entropy_merge");
+        for (int b = 0; b < B; ++b) out[b] = h_ent_b[b];
     }
     void get_token_scores(float* out, int cap, int32_t* n) override {
         REQUIRE(last_scores_valid, "svln_get_token_scores: token log-probabilities were off for the last turn (svln_set_token_scores), or no turn has run");
@@ -2220,6 +2318,7 @@ public:
         std::vector<int64_t> out, eos;
         std::vector<float> scores; bool scored = false;      // svln_set_token_scores: log-probability of every id of `out`
         std::vector<int32_t> topi; std::vector<float> topl; int topk = 0;      // svln_top_logprobs: the [topk] lists of every id of `out`
+        std::vector<float> ent; bool ent_on = false;         // svln_token_entropy: the entropy of the distribution every id of `out` was taken from
         std::vector<float> alp; int alp_n = 0;               // with svln_set_allowed_tokens too: the normalised row [alp_n] of every id of `out`
         std::vector<int> draft;      // svln_set_batch_draft: the usable draft the submit consumed, kept until the job's prefill iteration
         // svln_batch_submit_forced: the turn's ids are `fids`; the job ends in the iteration that prefills it with out = fids, `scores` their
@@ -2298,7 +2397,7 @@ public:
         j = Job();
         j.used = true; j.env = env; j.max_new = max_new < c.max_positions ? max_new : c.max_positions;
         j.eos.assign(eos, eos + n_eos);
-        j.scored = scores_on; j.topk = topk;
+        j.scored = scores_on; j.topk = topk; j.ent_on = ent_on;
         j.alp_n = scores_on && allow_on ? allow_n : 0;
         n_generated_b[slot] = 0;
         // svln_set_batch_draft: the env's armed draft is consumed by the submit whether or not it helps (the rule of svln_generate); usable:
@@ -2506,7 +2605,7 @@ public:
     // the pure batched decode step for B rows (d_slots / d_tok_b / d_smp set): the launches, or their captured graph
     void batched_step(int B, bool pen) {
         if (use_graph) {
-            const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0) | (fp8_gemm_on && fp8_scaled_on ? 2048 : 0) | (scores_on ? 4096 : 0) | (smp_on ? 8192 : 0) | (topk << 16);
+            const int key = B | (pen ? 256 : 0) | (fp8_gemm_on ? 512 : 0) | (mx4b_on ? 1024 : 0) | (fp8_gemm_on && fp8_scaled_on ? 2048 : 0) | (scores_on ? 4096 : 0) | (smp_on ? 8192 : 0) | (topk << 16) | (ent_on ? 1 << 24 : 0);
             auto it = bgraphs.find(key);
             if (it == bgraphs.end())      // (a failed capture leaves no entry behind)
                 it = bgraphs.emplace(key, capture_graph([&] { decode_ops_batched(B, pen); })).first;
@@ -2654,6 +2753,7 @@ public:
         if (n_head > 0) HIP_CHECK(hipMemcpyAsync(h_tok_b + head0, d_tok_b, n_head * sizeof(int), hipMemcpyDeviceToHost, st));
         if (scores_on) HIP_CHECK(hipMemcpyAsync(h_score_b + head0, d_score_b, n_head * sizeof(float), hipMemcpyDeviceToHost, st));      // (never split: the switches exclude each other)
         if (scores_on && allow_on) HIP_CHECK(hipMemcpyAsync(h_alp_b + (size_t)head0 * allow_n, d_alp_b, (size_t)n_head * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (ent_on) HIP_CHECK(hipMemcpyAsync(h_ent_b + head0, d_ent_b, n_head * sizeof(float), hipMemcpyDeviceToHost, st));
         if (topk) {
             HIP_CHECK(hipMemcpyAsync(h_topi_b + (size_t)head0 * topk, d_topi_b, (size_t)n_head * topk * sizeof(int), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipMemcpyAsync(h_topl_b + (size_t)head0 * topk, d_topl_b, (size_t)n_head * topk * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -2681,6 +2781,7 @@ public:
                 require_finite_tokens(&tok, 1);
                 j.out.push_back(tok);
                 if (j.scored) j.scores.push_back(h_score_b[hq + i]);
+                if (j.ent_on) j.ent.push_back(h_ent_b[hq + i]);
                 if (j.topk) {
                     j.topi.insert(j.topi.end(), h_topi_b + (size_t)(hq + i) * j.topk, h_topi_b + (size_t)(hq + i + 1) * j.topk);
                     j.topl.insert(j.topl.end(), h_topl_b + (size_t)(hq + i) * j.topk, h_topl_b + (size_t)(hq + i + 1) * j.topk);
@@ -2764,7 +2865,7 @@ public:
             for (int t = 0; t < s; ++t) REQUIRE(env_ids[t] != env_ids[s], "duplicate env in batch");
         for (int s = 0; s < n_envs; ++s) refuse_while_group_on(env_ids[s], "svln_generate_batch");
         std::vector<int> slots(n_envs);
-        gb_scores_valid = false; gb_alp_valid = false; gb_topk_valid = false;
+        gb_scores_valid = false; gb_alp_valid = false; gb_topk_valid = false; gb_ent_valid = false;
         try {
             for (int s = 0; s < n_envs; ++s) slots[s] = batch_submit(env_ids[s], max_new < cap ? max_new : cap, eos, n_eos);
             int32_t fin[MAXB], nf = 0;
@@ -2776,15 +2877,18 @@ public:
         gb_scores.assign(n_envs, std::vector<float>());
         gb_topi.assign(n_envs, std::vector<int32_t>()); gb_topl.assign(n_envs, std::vector<float>());
         gb_alp.assign(n_envs, std::vector<float>());
+        gb_ent.assign(n_envs, std::vector<float>());
         for (int s = 0; s < n_envs; ++s) {
             int32_t env = 0;
             if (scores_on) gb_scores[s] = jobs[slots[s]].scores;
             if (topk) { gb_topi[s] = jobs[slots[s]].topi; gb_topl[s] = jobs[slots[s]].topl; }
             if (scores_on && allow_on) gb_alp[s] = jobs[slots[s]].alp;
+            if (ent_on) gb_ent[s] = jobs[slots[s]].ent;
             batch_result(slots[s], &env, out + (size_t)s * cap, cap, &n_out[s]);
         }
         gb_scores_valid = scores_on;          // (only once every env's scores are in place)
         gb_topk = topk; gb_topk_valid = topk > 0;
+        gb_ent_valid = ent_on;
         gb_alp_n = allow_n; gb_alp_valid = scores_on && allow_on;
     }
     void get_hidden_batch(int slot, float* out, int max_rows, int32_t* n_rows) override {
@@ -2952,6 +3056,7 @@ public:
             HIP_CHECK(hipMemcpyAsync(h_out_ids, d_out_ids, (size_t)enq * sizeof(int), hipMemcpyDeviceToHost, st));
             if (scores_on) HIP_CHECK(hipMemcpyAsync(h_scores, d_scores, (size_t)enq * sizeof(float), hipMemcpyDeviceToHost, st));
             if (scores_on && allow_on) HIP_CHECK(hipMemcpyAsync(h_alp, d_alp, (size_t)enq * allow_n * sizeof(float), hipMemcpyDeviceToHost, st));
+            if (ent_on) HIP_CHECK(hipMemcpyAsync(h_ent, d_ent, (size_t)enq * sizeof(float), hipMemcpyDeviceToHost, st));
             if (topk) {
                 HIP_CHECK(hipMemcpyAsync(h_topi, d_topi, (size_t)enq * topk * sizeof(int), hipMemcpyDeviceToHost, st));
                 HIP_CHECK(hipMemcpyAsync(h_topl, d_topl, (size_t)enq * topk * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -2978,6 +3083,7 @@ public:
         for (int k = 0; k < n; ++k) out[k] = h_out_ids[k];
         if (scores_on) { last_scores.assign(h_scores, h_scores + n); last_scores_valid = true; }      // (the draft modes are off: every id left the scored arg-max step)
         if (scores_on && allow_on) { last_alp.assign(h_alp, h_alp + (size_t)n * allow_n); last_alp_n = allow_n; last_alp_valid = true; }
+        if (ent_on) { last_ent.assign(h_ent, h_ent + n); last_ent_valid = true; }
         if (topk) {
             last_topi.assign(h_topi, h_topi + (size_t)n * topk); last_topl.assign(h_topl, h_topl + (size_t)n * topk);
             last_topk = topk; last_topk_valid = true;
@@ -3001,6 +3107,7 @@ public:
         env_at(env);
         REQUIRE(n_seq >= 2 && n_seq <= MAXB, "svln_generate_group: n_seq must be 2 .. 8");
         refuse_while_topk("svln_generate_group");
+        refuse_while_entropy("svln_generate_group");
         refuse_while_plain_head_only("svln_generate_group");     // (svln_set_sampling is refused under each of them: name the cause)
         REQUIRE(smp_on, "svln_generate_group: temperature sampling is off (svln_set_sampling): greedy sequences would be identical");
         REQUIRE(rep_penalty == 1.0f, "svln_generate_group: a repetition penalty != 1 is set (svln_set_repetition_penalty); a group does not support it");
@@ -3180,6 +3287,7 @@ public:
         const char* who = "svln_generate_beams";
         env_at(env);
         REQUIRE(W >= 1 && W <= BEAM_MAX_W, std::string(who) + ": n_beams must be 1 .. 8");
+        refuse_while_entropy(who);
         REQUIRE(!smp_on, std::string(who) + ": temperature sampling is on (svln_set_sampling); beams are greedy: switch it off first");
         REQUIRE(!allow_on || allow_n >= W, std::string(who) + ": the allowed list (svln_set_allowed_tokens) is shorter than n_beams");
         REQUIRE(rep_penalty == 1.0f, std::string(who) + ": a repetition penalty != 1 is set (svln_set_repetition_penalty); beams do not support it");
@@ -3602,6 +3710,7 @@ public:
                     REQUIRE(eos[q] != ids[k], who + ": an id of the EOS set may only be the last one (an EOS is appended, never fed)");
         }
         REQUIRE(rep_penalty == 1.0f, who + ": a repetition penalty != 1 is set (svln_set_repetition_penalty); its flags change row by row");
+        refuse_while_entropy(who);
         // a forced row must be computed in the numeric scheme of the step it stands in for (the ride's list)
         if (sched)
             REQUIRE(!spec_exclusive_on(),
@@ -4193,12 +4302,37 @@ public:
         REQUIRE((size_t)a.K * sizeof(float) <= (size_t)max_lds, "the wave-per-rows kernel stages K fp32 activations in LDS: K too large");
         REQUIRE(!a.pen_flags || a.pen > 0.0f, "penalty flags need a factor > 0");
     }
-    void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob, const OpSample* smp) override {
+    // en: the single-env head with svln_token_entropy on -- the EPI_*_ENT product, entropy_merge_kernel and the scored (or, with smp,
+    // sampled) final kernel; everything the three launches wrote goes to the host
+    void op_ent_refusals(const OpEntOut* en, const float* host_logprobs, bool sampled) {
+        if (!en) return;
+        REQUIRE(host_logprobs && en->ent && en->pv && en->pi && en->ps && en->pe && en->n_part && (!sampled || (en->pr && en->pm)), "null output pointer");
+    }
+    // the merge and the copies of `rows` rows of n partials each (device arrays pv .. pe, entropies -> de) to the host, on the stream
+    void op_ent_out(const OpEntOut& en, int rows, int n, const float* pv, const int* pi, const float* ps, const float* pr, const float* pm, const float* pe,
+                    float* de) {
+        launch_entropy_merge(st, pv, pi, ps, pm, pe, n, rows, de);
+        const size_t nb = (size_t)rows * n;
+        HIP_CHECK(hipMemcpyAsync(en.ent, de, rows * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(en.pv, pv, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(en.pi, pi, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(en.ps, ps, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(en.pe, pe, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (pm) {
+            HIP_CHECK(hipMemcpyAsync(en.pr, pr, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(en.pm, pm, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+        }
+        *en.n_part = n;
+    }
+    void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob, const OpSample* smp, const OpEntOut* en) override {
         head_op_refusals(a, host_token, GEMV_ROWS_MAX_LDS);
-        a.epi = smp ? EPI_SAMPLE : host_logprob ? EPI_ARGMAX_LSE : EPI_ARGMAX;
-        a.part_val = part_val; a.part_idx = part_idx; a.part_sum = part_sum;
+        op_ent_refusals(en, host_logprob, smp != nullptr);
+        if (en) ensure_ent_buffers();
+        a.epi = en ? (smp ? EPI_SAMPLE_ENT : EPI_ARGMAX_LSE_ENT) : smp ? EPI_SAMPLE : host_logprob ? EPI_ARGMAX_LSE : EPI_ARGMAX;
+        a.part_val = part_val; a.part_idx = part_idx; a.part_sum = part_sum; a.part_ent = part_ent;
         if (smp) a.smp = op_sample_args(*smp, 1, part_raw, part_max, host_logprob != nullptr);
         launch_gemv<T>(st, a);
+        if (en) op_ent_out(*en, 1, gemv_grid(a.N), part_val, part_idx, part_sum, a.smp.part_raw, a.smp.part_max, part_ent, d_ent);
         launch_argmax_final(st, part_val, part_idx, gemv_grid(a.N), d_token, d_top2, host_logprob ? part_sum : nullptr, d_scores, a.smp.part_raw, a.smp.part_max);
         if (host_logprob) HIP_CHECK(hipMemcpyAsync(h_scores, d_scores, sizeof(float), hipMemcpyDeviceToHost, st));
         *host_token = read_token();
@@ -4256,7 +4390,8 @@ public:
         HIP_CHECK(hipMemcpyAsync(tk.top_lp, d_topl_b, (size_t)rows * tk.k * sizeof(float), hipMemcpyDeviceToHost, st));
         *tk.n_part = n;
     }
-    void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk) override {
+    void op_gemv_batched_scores(GemvBatchArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk,
+                                const OpEntOut* en) override {
         REQUIRE(a.W && a.x && host_tokens, "null pointer");
         REQUIRE(a.B == 1 || a.B == 2 || a.B == 4 || a.B == 8, "B must be 1, 2, 4 or 8");
         REQUIRE(a.N >= 1 && a.K >= Elt<T>::PER_CHUNK && a.K % Elt<T>::PER_CHUNK == 0, "N >= 1, K a positive multiple of the 16-byte chunk");
@@ -4264,9 +4399,13 @@ public:
         REQUIRE(!a.pen_flags || (a.pen_rows && a.pen > 0.0f), "penalty flags come with their row table and a factor > 0");
         REQUIRE(!smp || !a.norm_w, "the sampled batched GEMV has no fused-norm form");
         REQUIRE(!tk || !a.norm_w, "the candidate form of the batched GEMV has no fused-norm form");
+        REQUIRE(!en || (!a.norm_w && !tk), "the entropy form of the batched GEMV has no fused-norm form and no candidates");
         op_topk_rows_refusals(tk, host_logprobs);
+        op_ent_refusals(en, host_logprobs, smp != nullptr);
         if (tk) ensure_topk_buffers();
-        a.epi = tk ? (smp ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK) : smp ? EPI_SAMPLE : host_logprobs ? EPI_ARGMAX_LSE : EPI_ARGMAX;
+        if (en) ensure_ent_buffers();
+        a.epi = tk ? (smp ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK) : en ? (smp ? EPI_SAMPLE_ENT : EPI_ARGMAX_LSE_ENT) : smp ? EPI_SAMPLE : host_logprobs ? EPI_ARGMAX_LSE : EPI_ARGMAX;
+        a.part_ent = part_ent_b;
         a.cand_val = cand_val_b; a.cand_idx = cand_idx_b;
         a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b;
         a.row_scale = row_scale_b;
@@ -4275,9 +4414,11 @@ public:
         launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), a.B, d_tok_b, host_logprobs ? part_sum_b : nullptr, d_score_b,
                                     host_logprobs && a.norm_w ? a.row_scale : nullptr, a.smp.part_raw, a.smp.part_max);
         if (tk) op_topk_rows_out(*tk, a.B, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), a.smp.part_max);
+        if (en) op_ent_out(*en, a.B, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), part_val_b, part_idx_b, part_sum_b, a.smp.part_raw, a.smp.part_max, part_ent_b, d_ent_b);
         batched_scores_out(a.B, host_tokens, host_logprobs, "op_gemv_batched_scores");
     }
-    void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk) override {
+    void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk,
+                               const OpEntOut* en) override {
         constexpr int chunk = Elt<T>::PER_CHUNK;
         REQUIRE(a.A && a.W && host_tokens, "null pointer");
         REQUIRE(a.M >= 1 && a.M <= 32 && a.N >= 1 && (a.N + 127) / 128 <= 2048, "1 <= M <= 32 rows, 1 <= N <= 262144");
@@ -4285,15 +4426,20 @@ public:
                 "K a positive multiple of the 16-byte chunk; lda, ldw >= K, multiples of it (aligned LDS-DMA)");
         REQUIRE(((size_t)a.A & 15) == 0 && ((size_t)a.W & 15) == 0, "A and W must be 16-byte aligned (LDS-DMA)");
         REQUIRE(!a.pen_flags || (a.pen_rows && a.pen > 0.0f), "penalty flags come with their row table and a factor > 0");
+        REQUIRE(!en || !tk, "the entropy form has no candidates");
         op_topk_rows_refusals(tk, host_logprobs);
+        op_ent_refusals(en, host_logprobs, smp != nullptr);
         if (tk) ensure_topk_buffers();
+        if (en) ensure_ent_buffers();
         a.zeros = zero_line; a.epi = EPI_ARGMAX;
         a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = host_logprobs ? part_sum_b : nullptr;
         if (smp) a.smp = op_sample_args(*smp, a.M, part_raw_b, part_max_b, host_logprobs != nullptr);
         if (tk) { a.cand_val = cand_val_b; a.cand_idx = cand_idx_b; }
+        if (en) a.part_ent = part_ent_b;
         const int n = launch_gemm_argmax<T>(st, a);
         launch_argmax_final_batched(st, part_val_b, part_idx_b, n, a.M, d_tok_b, a.part_sum, d_score_b, nullptr, a.smp.part_raw, a.smp.part_max);
         if (tk) op_topk_rows_out(*tk, a.M, n, a.smp.part_max);
+        if (en) op_ent_out(*en, a.M, n, part_val_b, part_idx_b, part_sum_b, a.smp.part_raw, a.smp.part_max, part_ent_b, d_ent_b);
         batched_scores_out(a.M, host_tokens, host_logprobs, "op_gemm_argmax_scores");
     }
     void op_gemv_batched(GemvBatchArgs a, int32_t* host_tokens) override {
@@ -5063,7 +5209,8 @@ int svln_generate_batch_scores(svln_engine* h, int index, float* out, int cap, i
 // the outputs of svln_op_gemv_argmax_topk beyond token and score (null: the scored / sampled entries)
 struct OpTopkOut { int k; float* pv; int32_t* pi; float *ps, *pr, *pm, *cv; int32_t *ci, *top_ids; float* top_lp; int32_t* n_part; };
 static int op_gemv_argmax_any(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
-                              float penalty, int32_t* host_token, float* host_logprob, const OpSample* smp, const OpTopkOut* tk = nullptr) {
+                              float penalty, int32_t* host_token, float* host_logprob, const OpSample* smp, const OpTopkOut* tk = nullptr,
+                              const OpEntOut* en = nullptr) {
     API_BEGIN_H
     REQUIRE(fmt >= 0 && fmt <= 3, "fmt: 0 = engine dtype, 1 = e4m3 + row scales, 2 = MXFP4, 3 = 12-bit packing");
     GemvArgs a; a.W = nullptr; a.ldw = ldw; a.x = x; a.norm_w = nullptr; a.eps = 0.0f; a.bias = nullptr; a.res = nullptr; a.y = nullptr; a.N = N; a.K = K;
@@ -5078,7 +5225,7 @@ static int op_gemv_argmax_any(svln_engine* h, int fmt, const void* W, const void
     REQUIRE(W, "null pointer");
     a.pen_flags = (const uint8_t*)pen_flags; a.pen = penalty;
     if (tk) h->impl->op_gemv_topk(a, tk->k, smp, host_token, host_logprob, tk->pv, tk->pi, tk->ps, tk->pr, tk->pm, tk->cv, tk->ci, tk->top_ids, tk->top_lp, tk->n_part);
-    else h->impl->op_gemv_scores(a, host_token, host_logprob, smp);
+    else h->impl->op_gemv_scores(a, host_token, host_logprob, smp, en);
     API_END
 }
 int svln_op_gemv_argmax_scores(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
@@ -5100,12 +5247,12 @@ int svln_op_gemv_argmax_topk(svln_engine* h, int fmt, const void* W, const void*
 }
 static int op_gemv_batched_argmax_any(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
                                       const void* pen_flags, const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs,
-                                      const OpSample* smp, const OpTopkRows* tk = nullptr) {
+                                      const OpSample* smp, const OpTopkRows* tk = nullptr, const OpEntOut* en = nullptr) {
     API_BEGIN_H
     GemvBatchArgs a; a.W = W; a.ldw = ldw; a.x = x; a.ldx = ldx; a.norm_w = norm_w; a.eps = eps; a.bias = nullptr; a.res = nullptr; a.ldr = 0;
     a.y = nullptr; a.ldy = 0; a.N = N; a.K = K; a.epi = EPI_ARGMAX; a.B = B; a.part_val = nullptr; a.part_idx = nullptr;
     a.pen_flags = (const uint8_t*)pen_flags; a.pen_rows = pen_rows; a.pen = penalty;
-    h->impl->op_gemv_batched_scores(a, host_tokens, host_logprobs, smp, tk);
+    h->impl->op_gemv_batched_scores(a, host_tokens, host_logprobs, smp, tk, en);
     API_END
 }
 int svln_op_gemv_batched_argmax_scores(svln_engine* h, const void* W, int ldw, const void* x, int ldx, const void* norm_w, float eps, int N, int K, int B,
@@ -5120,12 +5267,12 @@ int svln_op_gemv_batched_argmax_sample(svln_engine* h, const void* W, int ldw, c
 }
 static int op_gemm_argmax_any(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
                               const int32_t* pen_rows, float penalty, int32_t* host_tokens, float* host_logprobs, const OpSample* smp,
-                              const OpTopkRows* tk = nullptr) {
+                              const OpTopkRows* tk = nullptr, const OpEntOut* en = nullptr) {
     API_BEGIN_H
     GemmArgs a; std::memset(&a, 0, sizeof(a));
     a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.epi = EPI_ARGMAX; a.nsplit = 1;
     a.pen_flags = (const uint8_t*)pen_flags; a.pen_rows = pen_rows; a.pen = penalty;
-    h->impl->op_gemm_argmax_scores(a, host_tokens, host_logprobs, smp, tk);
+    h->impl->op_gemm_argmax_scores(a, host_tokens, host_logprobs, smp, tk, en);
     API_END
 }
 int svln_op_gemm_argmax_scores(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
@@ -5153,6 +5300,44 @@ int svln_op_gemm_argmax_topk(svln_engine* h, const void* A, int lda, const void*
     const OpSample q{temperature, seed, streams, draws};
     const OpTopkRows tk{k, cand_val, cand_idx, top_ids, top_logprobs, n_part};
     return op_gemm_argmax_any(h, A, lda, W, ldw, M, N, K, pen_flags, pen_rows, penalty, host_tokens, host_logprobs, sampled ? &q : nullptr, &tk);
+}
+int svln_token_entropy(svln_engine* h, int enable) { API_BEGIN_H h->impl->token_entropy(enable); API_END }
+int svln_get_token_entropy(svln_engine* h, float* out, int cap, int32_t* n) {
+    API_BEGIN_H REQUIRE(out && n && cap >= 0, "null output pointer"); h->impl->get_token_entropy(out, cap, n); API_END
+}
+int svln_batch_entropy(svln_engine* h, int slot, float* out, int cap, int32_t* n) {
+    API_BEGIN_H REQUIRE(out && n && cap >= 0, "null output pointer"); h->impl->batch_entropy(slot, out, cap, n); API_END
+}
+int svln_generate_batch_entropy(svln_engine* h, int index, float* out, int cap, int32_t* n) {
+    API_BEGIN_H REQUIRE(out && n && cap >= 0, "null output pointer"); h->impl->generate_batch_entropy(index, out, cap, n); API_END
+}
+int svln_op_gemv_argmax_entropy(svln_engine* h, int fmt, const void* W, const void* aux, int ldw, const void* x, int N, int K, const void* pen_flags,
+                                float penalty, int sampled, float temperature, uint64_t seed, int32_t stream, int32_t draw, int32_t* host_token,
+                                float* host_logprob, float* host_entropy, float* part_val, int32_t* part_idx, float* part_sum, float* part_raw,
+                                float* part_max, float* part_ent, int32_t* n_part) {
+    const OpSample q{temperature, seed, &stream, &draw};
+    const OpEntOut en{host_entropy, part_val, part_idx, part_sum, part_raw, part_max, part_ent, n_part};
+    return op_gemv_argmax_any(h, fmt, W, aux, ldw, x, N, K, pen_flags, penalty, host_token, host_logprob, sampled ? &q : nullptr, nullptr, &en);
+}
+int svln_op_gemv_batched_argmax_entropy(svln_engine* h, const void* W, int ldw, const void* x, int ldx, int N, int K, int B, const void* pen_flags,
+                                        const int32_t* pen_rows, float penalty, int sampled, float temperature, uint64_t seed, const int32_t* streams,
+                                        const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* host_entropies, float* part_val,
+                                        int32_t* part_idx, float* part_sum, float* part_raw, float* part_max, float* part_ent, int32_t* n_part) {
+    const OpSample q{temperature, seed, streams, draws};
+    const OpEntOut en{host_entropies, part_val, part_idx, part_sum, part_raw, part_max, part_ent, n_part};
+    return op_gemv_batched_argmax_any(h, W, ldw, x, ldx, nullptr, 0.0f, N, K, B, pen_flags, pen_rows, penalty, host_tokens, host_logprobs, sampled ? &q : nullptr, nullptr, &en);
+}
+int svln_op_gemm_argmax_entropy(svln_engine* h, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const void* pen_flags,
+                                const int32_t* pen_rows, float penalty, int sampled, float temperature, uint64_t seed, const int32_t* streams,
+                                const int32_t* draws, int32_t* host_tokens, float* host_logprobs, float* host_entropies, float* part_val,
+                                int32_t* part_idx, float* part_sum, float* part_raw, float* part_max, float* part_ent, int32_t* n_part) {
+    const OpSample q{temperature, seed, streams, draws};
+    const OpEntOut en{host_entropies, part_val, part_idx, part_sum, part_raw, part_max, part_ent, n_part};
+    return op_gemm_argmax_any(h, A, lda, W, ldw, M, N, K, pen_flags, pen_rows, penalty, host_tokens, host_logprobs, sampled ? &q : nullptr, nullptr, &en);
+}
+int svln_op_entropy_merge(svln_engine* h, const float* part_val, const int32_t* part_idx, const float* part_sum, const float* part_max,
+                          const float* part_ent, int B, int n_part, float* host_entropies) {
+    API_BEGIN_H h->impl->op_entropy_merge(part_val, part_idx, part_sum, part_max, part_ent, B, n_part, host_entropies); API_END
 }
 int svln_batch_topk(svln_engine* h, int slot, int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) {
     API_BEGIN_H REQUIRE(ids && logprobs && n_rows && k && cap_rows >= 0, "null output pointer"); h->impl->batch_topk(slot, ids, logprobs, cap_rows, n_rows, k); API_END

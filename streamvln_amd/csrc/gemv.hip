@@ -375,8 +375,9 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
     const int gw = blockIdx.x * GEMV_WAVES + wave, nw = gridDim.x * GEMV_WAVES;
     const int n_out = EPI == EPI_SWIGLU ? p.N >> 1 : p.N;
 
-    constexpr bool AMAX = epi_is_argmax(EPI), TOPK = epi_is_topk(EPI);
-    constexpr bool LSE = EPI == EPI_ARGMAX_LSE || EPI == EPI_ARGMAX_LSE_TOPK, SMP = EPI == EPI_SAMPLE || EPI == EPI_SAMPLE_TOPK;
+    constexpr bool AMAX = epi_is_argmax(EPI), TOPK = epi_is_topk(EPI), ENT = epi_is_ent(EPI);
+    constexpr bool LSE = EPI == EPI_ARGMAX_LSE || EPI == EPI_ARGMAX_LSE_TOPK || EPI == EPI_ARGMAX_LSE_ENT;
+    constexpr bool SMP = EPI == EPI_SAMPLE || EPI == EPI_SAMPLE_TOPK || EPI == EPI_SAMPLE_ENT;
     // EPI_*_TOPK: the wave's TOPK_C best (y, column) pairs, entry l in lane l < TOPK_C, y descending then column ascending; a logit is
     // wave-uniform, so is tk_thr = entry TOPK_C - 1, and the common case of a column costs one scalar compare against it
     [[maybe_unused]] float tk_v = -INFINITY, tk_thr = -INFINITY;
@@ -395,6 +396,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
     float best = -INFINITY;                       // EPI_ARGMAX (EPI_SAMPLE: the best perturbed value z)
     int best_i = 0x7FFFFFFF;
     float lm = -INFINITY, ls = 0.0f;              // EPI_ARGMAX_LSE: wave-uniform (max, sum exp(l - max)) over the wave's rows (EPI_SAMPLE: over y)
+    [[maybe_unused]] float lt = 0.0f;             // EPI_*_ENT: sum (l - max) exp(l - max) beside ls
     [[maybe_unused]] float best_raw = -INFINITY;  // EPI_SAMPLE: the y of the best z
     [[maybe_unused]] int smp_stream = 0, smp_draw = 0;
     if constexpr (SMP) { smp_stream = p.smp.stream[0]; smp_draw = p.smp.draw[0] + (p.smp.count ? *p.smp.count : 0); }
@@ -433,7 +435,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
                     const float y = acc[r] * p.smp.inv_t, z = __fadd_rn(y, __shfl(gq, r, 64));       // (fl(y + G), never fma(acc, inv_t, G): truncate_partials_kernel adds the same G to the stored y)
                     if (n0 + r < p.N) {
                         if (z > best) { best = z; best_i = n0 + r; best_raw = y; }         // rows ascend: first max wins
-                        lse_add(y, lm, ls);
+                        if constexpr (ENT) ent_add(y, lm, ls, lt); else lse_add(y, lm, ls);
                         if constexpr (TOPK) tk_insert(y, n0 + r);
                     }
                 }
@@ -446,7 +448,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
 #pragma unroll
                 for (int r = 0; r < R; ++r)
                     if (n0 + r < p.N) {
-                        lse_add(acc[r], lm, ls);
+                        if constexpr (ENT) ent_add(acc[r], lm, ls, lt); else lse_add(acc[r], lm, ls);
                         if constexpr (TOPK) tk_insert(acc[r], n0 + r);
                     }
             }
@@ -497,11 +499,27 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
                 p.part_val[blockIdx.x] = v; p.part_idx[blockIdx.x] = i; p.smp.part_raw[blockIdx.x] = raw;
                 p.smp.part_max[blockIdx.x] = m; p.part_sum[blockIdx.x] = sum;
             }
+            if constexpr (ENT) {                  // the four waves' t, each seen from the workgroup's maximum (bs / bm are unchanged)
+                __shared__ float bt[GEMV_WAVES];
+                if (lane == 0) bt[wave] = lt;
+                __syncthreads();
+                if (threadIdx.x == 0) {
+                    float m = bm[0];
+#pragma unroll
+                    for (int w = 1; w < GEMV_WAVES; ++w) m = bm[w] > m ? bm[w] : m;
+                    float te = 0.0f;
+#pragma unroll
+                    for (int w = 0; w < GEMV_WAVES; ++w) te += ent_rescale(bt[w], bs[w], bm[w], m);
+                    p.part_ent[blockIdx.x] = te;
+                }
+            }
             return;
         }
         if constexpr (LSE) {
             __shared__ float bs[GEMV_WAVES];
+            [[maybe_unused]] __shared__ float bt[ENT ? GEMV_WAVES : 1];
             if (lane == 0) bs[wave] = ls;         // (lm == best: the same compares in the same order)
+            if constexpr (ENT) if (lane == 0) bt[wave] = lt;
             __syncthreads();
             if (threadIdx.x == 0) {               // a wave without a row is (-inf, 0) and adds 0
                 float v = bv[0];
@@ -511,6 +529,12 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
 #pragma unroll
                 for (int w = 0; w < GEMV_WAVES; ++w) sum += lse_rescale(bs[w], bv[w], v);
                 p.part_sum[blockIdx.x] = sum;
+                if constexpr (ENT) {
+                    float te = 0.0f;
+#pragma unroll
+                    for (int w = 0; w < GEMV_WAVES; ++w) te += ent_rescale(bt[w], bs[w], bv[w], v);
+                    p.part_ent[blockIdx.x] = te;
+                }
             }
         } else {
             __syncthreads();
@@ -611,9 +635,11 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
     const T* xg = (const T*)p.x;
     const T* gg = (const T*)p.norm_w;
     const int n_units = EPI == EPI_SWIGLU ? p.N / R : (p.N + R - 1) / R;      // one unit = R weight rows
-    constexpr bool AMAX = epi_is_argmax(EPI), TGT = EPI == EPI_TARGET, TOPK = epi_is_topk(EPI);
-    constexpr bool LSE = EPI == EPI_ARGMAX_LSE || EPI == EPI_ARGMAX_LSE_TOPK || TGT, SMP = EPI == EPI_SAMPLE || EPI == EPI_SAMPLE_TOPK;
+    constexpr bool AMAX = epi_is_argmax(EPI), TGT = EPI == EPI_TARGET, TOPK = epi_is_topk(EPI), ENT = epi_is_ent(EPI);
+    constexpr bool LSE = EPI == EPI_ARGMAX_LSE || EPI == EPI_ARGMAX_LSE_TOPK || EPI == EPI_ARGMAX_LSE_ENT || TGT;
+    constexpr bool SMP = EPI == EPI_SAMPLE || EPI == EPI_SAMPLE_TOPK || EPI == EPI_SAMPLE_ENT;
     static_assert(!(TOPK && NORM), "EPI_*_TOPK has no fused-norm form");
+    static_assert(!(ENT && NORM), "EPI_*_ENT has no fused-norm form");
     // EPI_*_TOPK: thread b < B keeps env b's TOPK_C best (y, column) pairs of the workgroup's units in registers, y descending then column
     // ascending (static indices: the insertion is an unrolled shift).  Units and their columns ascend, so an equal value stays behind.
     [[maybe_unused]] float tk_v[TOPK ? TOPK_C : 1];
@@ -642,6 +668,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
     float best = -INFINITY;                                                   // EPI_ARGMAX: thread b < B tracks env b (EPI_SAMPLE: the best z)
     int best_i = 0x7FFFFFFF;
     float lm = -INFINITY, ls = 0.0f;                                          // EPI_ARGMAX_LSE: env b's (max, sum exp(l - max)) over the workgroup's units
+    [[maybe_unused]] float lt = 0.0f;                                         // EPI_*_ENT: env b's sum (l - max) exp(l - max) beside ls
     [[maybe_unused]] float best_raw = -INFINITY;                              // EPI_SAMPLE: the y of the best z
     // EPI_SAMPLE: thread r * B + b evaluates the noise of column n0 + r for env b (one Philox per thread and unit); thread b reads its R values
     [[maybe_unused]] __shared__ float gn[SMP ? R * B : 1];
@@ -753,7 +780,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
                         const float y = v * p.smp.inv_t, z = __fadd_rn(y, gn[r * B + tid]);       // (fl(y + G), as in gemv_rows_kernel)
                         if (n0 + r < p.N) {
                             if (z > best) { best = z; best_i = n0 + r; best_raw = y; }
-                            lse_add(y, lm, ls);
+                            if constexpr (ENT) ent_add(y, lm, ls, lt); else lse_add(y, lm, ls);
                             tk_insert(y, n0 + r);
                         }
                         continue;
@@ -762,7 +789,8 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
                     // (the clamped rows of the last unit count once.  The arg-max ignores a fused norm's positive row factor, as the plain
                     // form does; a probability cannot: the SUM takes fl(v * factor), whose maximum is fl(best * factor) -- rounding is
                     // monotone -- so the final kernel rebuilds the partial's maximum from part_val and row_scale[b])
-                    if (LSE && n0 + r < p.N) lse_add(NORM ? v * rsqrtf(total(R * B + tid) / (float)p.K + p.eps) : v, lm, ls);
+                    if constexpr (ENT) { if (n0 + r < p.N) ent_add(v, lm, ls, lt); }
+                    else if (LSE && n0 + r < p.N) lse_add(NORM ? v * rsqrtf(total(R * B + tid) / (float)p.K + p.eps) : v, lm, ls);
                     if (TOPK && n0 + r < p.N) tk_insert(v, n0 + r);
                 }
             }
@@ -788,6 +816,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
                 p.cand_idx[((size_t)tid * gridDim.x + blockIdx.x) * TOPK_C + e] = tk_i[e];
             }
         }
+        if constexpr (ENT) p.part_ent[(size_t)tid * gridDim.x + blockIdx.x] = lt;
         if constexpr (SMP) {
             p.part_sum[(size_t)tid * gridDim.x + blockIdx.x] = ls;
             p.smp.part_max[(size_t)tid * gridDim.x + blockIdx.x] = lm;
@@ -1137,6 +1166,8 @@ template <typename P> static void launch_gemv_fmt(hipStream_t s, const GemvArgs&
         case EPI_SAMPLE: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SAMPLE>), g, b, lds); break;
         case EPI_ARGMAX_LSE_TOPK: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX_LSE_TOPK>), g, b, lds); break;
         case EPI_SAMPLE_TOPK: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SAMPLE_TOPK>), g, b, lds); break;
+        case EPI_ARGMAX_LSE_ENT: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX_LSE_ENT>), g, b, lds); break;
+        case EPI_SAMPLE_ENT: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SAMPLE_ENT>), g, b, lds); break;
         default: break;
     }
 }
@@ -1178,6 +1209,10 @@ template <typename T> void launch_gemv_batched(hipStream_t s, const GemvBatchArg
         case EPI_ARGMAX_LSE_TOPK: case EPI_SAMPLE_TOPK:
             if (norm || !a.cand_val || !a.cand_idx) throw std::runtime_error("batched GEMV: EPI_*_TOPK takes candidate arrays and no fused norm");
             if (a.epi == EPI_SAMPLE_TOPK) launch_gb<T, EPI_SAMPLE_TOPK, false>(s, a); else launch_gb<T, EPI_ARGMAX_LSE_TOPK, false>(s, a);
+            break;
+        case EPI_ARGMAX_LSE_ENT: case EPI_SAMPLE_ENT:
+            if (norm || !a.part_ent) throw std::runtime_error("batched GEMV: EPI_*_ENT takes part_ent and no fused norm");
+            if (a.epi == EPI_SAMPLE_ENT) launch_gb<T, EPI_SAMPLE_ENT, false>(s, a); else launch_gb<T, EPI_ARGMAX_LSE_ENT, false>(s, a);
             break;
         case EPI_TARGET:
             if (norm || a.pen_flags || !a.tg.tgt || !a.tg.tgt_val) throw std::runtime_error("batched GEMV: EPI_TARGET takes targets, no fused norm and no penalty flags");
@@ -1222,6 +1257,8 @@ template <typename P> static void gemv_rows_attrs() {
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_SAMPLE>, GEMV_ROWS_MAX_LDS);
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX_LSE_TOPK>, GEMV_ROWS_TOPK_MAX_LDS);
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_SAMPLE_TOPK>, GEMV_ROWS_TOPK_MAX_LDS);
+    set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX_LSE_ENT>, GEMV_ROWS_MAX_LDS);
+    set_max_lds((const void*)gemv_rows_kernel<P, EPI_SAMPLE_ENT>, GEMV_ROWS_MAX_LDS);
 }
 void gemv_init_attrs() {
     gemv_rows_attrs<WMxfp4>(); gemv_rows_attrs<WE4m3>(); gemv_rows_attrs<WP12>(); gemv_rows_attrs<WPlain<bf16>>(); gemv_rows_attrs<WPlain<float>>();

@@ -10,7 +10,7 @@
 namespace svln {
 
 enum Epi : int { EPI_NONE = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_SWIGLU = 3, EPI_ARGMAX = 4, EPI_ARGMAX_LSE = 5, EPI_SAMPLE = 6, EPI_TARGET = 7,
-                 EPI_ARGMAX_LSE_TOPK = 8, EPI_SAMPLE_TOPK = 9 };
+                 EPI_ARGMAX_LSE_TOPK = 8, EPI_SAMPLE_TOPK = 9, EPI_ARGMAX_LSE_ENT = 10, EPI_SAMPLE_ENT = 11 };
 // EPI_ARGMAX_LSE (svln_set_token_scores): EPI_ARGMAX -- same accumulators, same compares, same partials, hence the same tokens -- plus one
 // fp32 per partial, part_sum[k] = sum exp(l_j - part_val[k]) over the (penalised) logits partial k owns.  The final kernels merge them,
 // S = sum_k part_sum[k] * exp(part_val[k] - V) with V the winning value, and write the token's log-probability -log S.  A partial that
@@ -30,9 +30,15 @@ enum Epi : int { EPI_NONE = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_SWIGLU =
 // (y, column) pairs among the columns it owns, y descending then column ascending, padded with (-inf, 0x7FFFFFFF): cand_val / cand_idx
 // [partials][TOPK_C].  y is the processed logit (after the penalty), times inv_t under sampling -- never the perturbed z.  NaN and -inf are
 // never listed.  A column of the row's top k <= TOPK_C is in the top k of the partial that owns it, so launch_topk_merge is exact.
+// EPI_ARGMAX_LSE_ENT / EPI_SAMPLE_ENT (svln_token_entropy; every lm_head form): EPI_ARGMAX_LSE / EPI_SAMPLE -- the same accumulators, compares
+// and partials, hence the same tokens, scores and partial arrays bit for bit -- plus one more fp32 per partial, part_ent[k] = sum (y_j -
+// m_k) exp(y_j - m_k) over the columns partial k owns, m_k the maximum part_sum[k] is relative to (part_val when greedy, smp.part_max when
+// sampled); y as in the _TOPK forms, never the perturbed z.  A -inf column adds 0, the partial that owns nothing has 0.
+// launch_entropy_merge turns them into the row's entropy log S - T / S.
 constexpr int TOPK_C = 8;
 constexpr bool epi_is_topk(int epi) { return epi == EPI_ARGMAX_LSE_TOPK || epi == EPI_SAMPLE_TOPK; }
-constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE || epi == EPI_SAMPLE || epi == EPI_TARGET || epi_is_topk(epi); }
+constexpr bool epi_is_ent(int epi) { return epi == EPI_ARGMAX_LSE_ENT || epi == EPI_SAMPLE_ENT; }
+constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE || epi == EPI_SAMPLE || epi == EPI_TARGET || epi_is_topk(epi) || epi_is_ent(epi); }
 // Inputs of EPI_TARGET: tgt [rows] device ids (-1: none), tgt_val [rows] the captured y
 struct TargetArgs { const int* tgt = nullptr; float* tgt_val = nullptr; float inv_t = 1.0f; };
 // Inputs of EPI_SAMPLE.  stream / draw are device arrays indexed by the row of the product (row 0 of a GEMV), read by the kernel: nothing a
@@ -90,6 +96,7 @@ struct GemmArgs {
     SampleArgs smp;               // smp.part_raw non-null: the EPI_SAMPLE form (part_sum too)
     TargetArgs tg;                // tg.tgt non-null: the EPI_TARGET form (part_sum too; no penalty flags)
     float* cand_val = nullptr; int* cand_idx = nullptr;       // non-null (with part_sum): the EPI_*_TOPK form, [m][tiles][TOPK_C]
+    float* part_ent = nullptr;    // non-null (with part_sum, without cand_val): the EPI_*_ENT form, [m][tiles] beside part_sum
     VitPackArgs vp; int vp_on;    // filled by the launcher: device-side copy of *vitpack for the unsplit kernels that pack in their epilogue
     int force_cfg, force_split;   // tests: 0 = heuristic; force_cfg 129 -> 128x128 tiles with two in-workgroup K groups; force_cfg low bits 128 -> 128x128 tiles, 264 -> 256x64 tiles; force_split S -> 256x128 tiles, S splits
 };
@@ -130,6 +137,7 @@ struct GemvArgs {
     float* part_sum = nullptr;    // EPI_ARGMAX_LSE / EPI_SAMPLE: [gemv_grid(N)] beside part_val
     SampleArgs smp;               // EPI_SAMPLE only
     float* cand_val = nullptr; int* cand_idx = nullptr;       // EPI_*_TOPK: [gemv_grid(N)][TOPK_C]
+    float* part_ent = nullptr;    // EPI_*_ENT: [gemv_grid(N)] beside part_sum
 };
 template <typename T> void launch_gemv(hipStream_t s, const GemvArgs& a);
 // per-row e4m3 quantisation of a bf16 matrix [rows][cols] (cols % 16 == 0): scale[r] = max|W[r]| / 448
@@ -165,6 +173,7 @@ struct GemvBatchArgs {
     TargetArgs tg;                // EPI_TARGET only (no fused norm, no penalty flags: launch_gemv_batched throws)
     float* row_scale = nullptr;   // EPI_ARGMAX_LSE with norm_w only: [B], the norm's row factor (the arg-max ignores it, the sums are taken on the scaled logits)
     float* cand_val = nullptr; int* cand_idx = nullptr;       // EPI_*_TOPK (no fused norm: launch_gemv_batched throws): [B][grid][TOPK_C]
+    float* part_ent = nullptr;    // EPI_*_ENT (no fused norm: launch_gemv_batched throws): [B][grid] beside part_sum
 };
 template <typename T> void launch_gemv_batched(hipStream_t s, const GemvBatchArgs& a);
 int gemv_batched_grid(int N, int epi, int B);
@@ -248,6 +257,13 @@ void launch_subset_logprobs(hipStream_t s, const float* src, int n, int B, float
 void launch_topk_merge(hipStream_t s, const float* cand_val, const int* cand_idx, int n_part, int c, int B, int k, const float* part_val,
                        const int* part_idx, const float* part_sum, const float* part_max, int* top_ids, float* top_logprobs,
                        const int* row_dev = nullptr, const int* skip = nullptr);
+// svln_token_entropy (misc.hip): the entropy of every row's distribution from its n_part partials [B][n_part]: (V, S) through the device
+// functions the scored final kernels use, on the same partials -- part_max == nullptr is the greedy merge on (part_val, part_idx,
+// part_sum), else the sampled one on (part_max, part_sum) -- T = sum_k ent_rescale(part_ent[k], part_sum[k], m_k, V) on the same fixed
+// tree, out[row] = log S - T / S in nats (NaN for a row without a finite value).  part_ent == nullptr: every t_k is 0 (the subset product:
+// one id per partial).  row = *row_dev when given (B = 1: GenCtl::count, launched before the step kernel advances it), else b.
+void launch_entropy_merge(hipStream_t s, const float* part_val, const int* part_idx, const float* part_sum, const float* part_max,
+                          const float* part_ent, int n_part, int B, float* out, const int* row_dev = nullptr, const int* skip = nullptr);
 // svln_sampling_truncation (misc.hip): top-k then top-p over one row's candidates, as an 8-entry partial row the sampled final kernels
 // (launch_argmax_step / launch_argmax_final / launch_argmax_final_batched with n = TOPK_C) reduce unchanged.  Candidates as in
 // launch_topk_merge ([B][n_part][c], c = TOPK_C or 1; n_part x c <= 16384).  Rule per row, one 256-thread workgroup each:

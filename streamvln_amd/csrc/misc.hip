@@ -680,7 +680,42 @@ __global__ __launch_bounds__(256) void truncate_partials_kernel(const float* can
         tr_sum[q] = keep ? 1.0f : 0.0f;
     }
 }
+// svln_token_entropy: the entropy of one row from its partials (contract: kernels.h, launch_entropy_merge).  One workgroup per row.
+// (V, S) as in topk_merge_kernel -- the device functions of the scored final kernels on the same partials, the same bits -- then T on the
+// same fixed tree, every partial's t seen from V by ent_rescale (pe == nullptr: t = 0, one id per partial), and H = log S - T / S.
+__global__ __launch_bounds__(256) void entropy_merge_kernel(const float* pv, const int* pi, const float* ps, const float* pm, const float* pe,
+                                                            int n_part, float* out, const int* row_dev, const int* skip) {
+    __shared__ float sv[256];
+    __shared__ int si[256];
+    if (skip && *skip) return;
+    const size_t o = (size_t)blockIdx.x * n_part;
+    float V, S;
+    bool none;
+    const float* m0 = pm ? pm + o : pv + o;       // the maxima the partial sums are relative to
+    if (pm) {                                     // sampled: V = max part_max, S on (part_max, part_sum); no token is looked up
+        const SampleMerge mg = sample_merge(pi + o, pm + o, pm + o, ps + o, n_part, -1, sv, si);
+        V = mg.V; S = mg.S;
+        none = V == -INFINITY;
+    } else {
+        row_argmax_256(pv + o, pi + o, n_part, sv, si);
+        V = sv[0];
+        none = si[0] == 0x7FFFFFFF;
+        S = row_lse_sum_256(ps + o, pv + o, n_part, 1.0f, V, sv);
+    }
+    __syncthreads();                              // sv[0] has been read by every thread
+    float mine = 0.0f;
+    for (int k = threadIdx.x; k < n_part; k += 256) mine += ent_rescale(pe ? pe[o + k] : 0.0f, ps[o + k], m0[k], V);
+    const float T = block_sum_256(mine, sv);
+    if (threadIdx.x == 0) {
+        const size_t row = row_dev ? (size_t)*row_dev : (size_t)blockIdx.x;
+        out[row] = none ? __builtin_nanf("") : ent_value(S, T);
+    }
+}
 }  // namespace
+void launch_entropy_merge(hipStream_t s, const float* part_val, const int* part_idx, const float* part_sum, const float* part_max,
+                          const float* part_ent, int n_part, int B, float* out, const int* row_dev, const int* skip) {
+    hipLaunchKernelGGL(entropy_merge_kernel, dim3(B), dim3(256), 0, s, part_val, part_idx, part_sum, part_max, part_ent, n_part, out, row_dev, skip);
+}
 void launch_topk_merge(hipStream_t s, const float* cand_val, const int* cand_idx, int n_part, int c, int B, int k, const float* part_val,
                        const int* part_idx, const float* part_sum, const float* part_max, int* top_ids, float* top_logprobs, const int* row_dev,
                        const int* skip) {

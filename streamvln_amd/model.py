@@ -149,10 +149,10 @@ class KVHandle:
 
 class GenerateOutput(dict):
     """`return_dict_in_generate=True` result: `.sequences` (new tokens only, EOS included) and
-    `.past_key_values` (streamvln_eval.py:334-335).  `.top_token_ids` / `.top_logprobs` (set_top_logprobs) read as None while the
-    switch is off; like every optional entry they are keys only of a result that carries them."""
+    `.past_key_values` (streamvln_eval.py:334-335).  `.top_token_ids` / `.top_logprobs` (set_top_logprobs) and `.token_entropies`
+    (set_token_entropy) read as None while their switch is off; like every optional entry they are keys only of a result that carries them."""
 
-    _OPTIONAL = ("top_token_ids", "top_logprobs")
+    _OPTIONAL = ("top_token_ids", "top_logprobs", "token_entropies")
 
     def __getattr__(self, k):
         try:
@@ -196,6 +196,7 @@ class StreamVLNForCausalLM:
         self._last_out: Dict[int, torch.Tensor] = {}
         self._token_scores = False                                 # set_token_scores: results carry token_logprobs
         self.top_logprobs_k = 0                                    # set_top_logprobs: results carry the k best ids per token
+        self._token_entropy = False                                # set_token_entropy: results carry token_entropies
         self.allowed_token_ids = None                              # set_allowed_tokens: the list in force (tuple), None when off
         self._sampling = None                                      # set_sampling: None (greedy) or (temperature, seed) the engine holds
         self.sampling_seed = 0                                     # seed of the noise of generate(do_sample=True) (see set_sampling)
@@ -659,6 +660,8 @@ class StreamVLNForCausalLM:
             res["token_logprobs"] = self._scores(self._lib.svln_get_token_scores, n_new=int(seq.shape[1]), device=seq.device)
         if self.top_logprobs_k:
             res["top_token_ids"], res["top_logprobs"] = self._topk(n_new=int(seq.shape[1]), device=seq.device)
+        if self._token_entropy:
+            res["token_entropies"] = self._scores(self._lib.svln_get_token_entropy, n_new=int(seq.shape[1]), device=seq.device)
         return self._allowed(res, "svln_get_allowed_logprobs")
 
     # ---- forced turns: log-probabilities of given ids in one prefill pass (svln_turn_forced) --------------
@@ -1080,6 +1083,9 @@ class StreamVLNForCausalLM:
         if self.top_logprobs_k:
             for k, r in enumerate(res):
                 r["top_token_ids"], r["top_logprobs"] = self._topk(int(n_out[k]), r.sequences.device, self._lib.svln_generate_batch_topk, k)
+        if self._token_entropy:
+            for k, r in enumerate(res):
+                r["token_entropies"] = self._scores(self._lib.svln_generate_batch_entropy, k, n_new=int(n_out[k]), device=r.sequences.device)
         return res
 
     # ---- iteration-level scheduler: envs whose turns fall due at different times (streamvln_dagger.py:232-313) ----
@@ -1337,6 +1343,7 @@ class StreamVLNForCausalLM:
                 _check(self._lib.svln_batch_scores(self._h, fin[k], sbuf.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(ns)))
                 scores = torch.from_numpy(sbuf[: ns.value].copy()).unsqueeze(0)
             top = self._topk(int(ns.value), "cpu", self._lib.svln_batch_topk, fin[k]) if self.top_logprobs_k else None
+            ent = self._scores(self._lib.svln_batch_entropy, fin[k], n_new=int(ns.value), device="cpu") if self._token_entropy else None
             alp = None
             if self._token_scores and self.allowed_token_ids:      # (read before svln_batch_result frees the slot)
                 abuf = np.empty(cap * len(self.allowed_token_ids), dtype=np.float32)
@@ -1349,6 +1356,8 @@ class StreamVLNForCausalLM:
             res = self._batch_result(env_id, out[: n.value], inputs, scores)
             if top is not None:
                 res["top_token_ids"], res["top_logprobs"] = (t.to(res.sequences.device) for t in top)
+            if ent is not None:
+                res["token_entropies"] = ent.to(res.sequences.device)
             if alp is not None:
                 res["allowed_logprobs"] = alp.to(res.sequences.device)
                 res["allowed_token_ids"] = torch.tensor(self.allowed_token_ids, dtype=torch.int64, device=res.sequences.device)
@@ -1506,6 +1515,17 @@ class StreamVLNForCausalLM:
         it is on), and while scheduler turns are in flight."""
         _check(self._lib.svln_set_token_scores(self._h, int(bool(enable))))
         self._token_scores = bool(enable)
+
+    def set_token_entropy(self, enable: bool):
+        """Opt-in, default off (svln_token_entropy): while on, every GenerateOutput of generate / generate_batch / step_batch carries
+        `token_entropies`: fp32 [1, n_new] on the device of `sequences`, aligned with it -- the entropy H = -sum_n p_n log p_n, in nats, of
+        the distribution every id was taken from: softmax over the processed fp32 logits (after the repetition penalty), of logits / T under
+        sampling, over the allowed set under set_allowed_tokens.  The lm_head kernels carry one more running sum beside their fused
+        arg-max: no logits in memory, no second pass, ids and scores unchanged bit for bit.  Needs set_token_scores(True) first (which then
+        cannot be switched off); refused together with set_top_logprobs(k > 0) and a sampling truncation, and group, beam, candidate and
+        forced turns are refused while on (ValueError from the engine, naming the function)."""
+        _check(self._lib.svln_token_entropy(self._h, int(bool(enable))))
+        self._token_entropy = bool(enable)
 
     def set_top_logprobs(self, k: int):
         """Opt-in, default off (svln_top_logprobs; `logprobs=k` / `top_logprobs` of the serving stacks): while 1 <= k <= 8 every result of
