@@ -459,7 +459,7 @@ public:
     // envs through svln_generate replays instead of re-capturing); [0] = the whole step, [1] / [2] = the halves around the probed launch
     // (captured only while the roofline probe is on); a run-ahead batch of several steps is one graph.
     bool use_graph = false;
-    struct GraphSet { std::unordered_map<int, hipGraphExec_t> ex; };     // key: steps (whole batch) | 1000 (head of a probed step) | 2000 + steps (its tail) | 3000 + rows (verify pass); + 10000 with svln_set_token_scores, + 20000 with svln_set_sampling, + 40000 with svln_set_packed_decode, + 100000 k with svln_top_logprobs(k), + 1000000 with svln_token_entropy
+    struct GraphSet { std::unordered_map<int, hipGraphExec_t> ex; };     // key: steps (whole batch) | 1000 (head of a probed step) | 2000 + steps (its tail) | 3000 + rows (verify pass); + head_graph_key() (10000 with svln_set_token_scores, 20000 with svln_set_sampling, 100000 k with svln_top_logprobs(k), 1000000 with svln_token_entropy) + 40000 with svln_set_packed_decode
     std::vector<GraphSet> graphs;
     std::unordered_map<int, hipGraphExec_t> bgraphs;          // batched decode step: key = B | penalty << 8 | fp8 gemm << 9 | MXFP4 batched << 10 | scaled fp8 form << 11 | token scores << 12
     // per-turn truncation of the spliced rows (the reference's config.tokenizer_model_max_length, stream_video_vln.py:241-244); 0 = none
@@ -1402,17 +1402,74 @@ public:
     // the losslessly packed copy (same outputs bit for bit); the e4m3 / MXFP4 modes read their own copies and take precedence
     GemvArgs with12(GemvArgs a, const P12& m) { if (p12_on && !fp8_on && !mx4_on && m.pk) { a.wp = m.pk; a.prec = m.rec; } return a; }
     GemvArgs guarded(GemvArgs a) { a.skip = &d_ctl->done; return a; }      // decode-step launch: no-op once the generation is done
+    // ------------------------------------------------------------------------------- the lm_head ("Anatomy of the lm_head")
+    // The form the switches ask for.  The setters keep: topk > 0 and ent_on only while scores_on, trunc_k only while smp_on, ent_on with
+    // neither -- so head_epi(form) names a kernel (aim refuses otherwise).  A truncated pass runs the candidate form, lists on or off.
+    HeadForm head_form_now() const { return HeadForm{scores_on && !smp_on, smp_on, false, topk > 0 || trunc_k > 0, ent_on}; }
+    // the head's share of the decode-graph key (GraphSet): the captured launches differ with every term
+    int head_graph_key() const { return (scores_on ? 10000 : 0) + (smp_on ? 20000 : 0) + 100000 * topk + (ent_on ? 1000000 : 0); }
+    // A view of one set of partial arrays, read when called (the ensure_*_buffers allocate lazily): the single-env set [partials], the
+    // batched set [rows][partials], and the 8-entry rows launch_truncate_partials writes ([1][TOPK_C], [SMP_ROWS][TOPK_C])
+    struct HeadParts { float* val; int* idx; float* sum; float* raw; float* max; float* cand_val; int* cand_idx; float* ent; };
+    HeadParts parts() const { return {part_val, part_idx, part_sum, part_raw, part_max, cand_val, cand_idx, part_ent}; }
+    HeadParts parts_b() const { return {part_val_b, part_idx_b, part_sum_b, part_raw_b, part_max_b, cand_val_b, cand_idx_b, part_ent_b}; }
+    HeadParts trunc_parts() const { return {tr_val, tr_idx, tr_sum, tr_raw, tr_max, nullptr, nullptr, nullptr}; }
+    HeadParts trunc_parts_b() const { return {tr_val_b, tr_idx_b, tr_sum_b, tr_raw_b, tr_max_b, nullptr, nullptr, nullptr}; }
+    // where a sampled product of the engine's own switch reads its stream, its draw counter and (optional) the tokens of this turn
+    struct Draws { const int *stream, *draw, *count; };
+    // aim a product at a set of partials in form f: epi and every array pointer (a kernel reads the arrays of its form only); dr: the
+    // sampling scalars are the engine's own too (a test entry has set its own before)
+    template <class A> void aim(A& a, const HeadParts& p, HeadForm f, const Draws* dr = nullptr) {
+        constexpr bool subset = std::is_same<A, GemvSubsetArgs>::value;
+        if (subset) f.topk = f.ent = false;      // one id per partial: the partials are the candidates as they stand, and t = 0
+        a.epi = head_epi(f);
+        REQUIRE(a.epi >= 0, "lm_head: no kernel carries this combination of scores, sampling, targets, lists and entropies");
+        if (dr && f.smp) a.smp = smp_args(dr->stream, dr->draw, dr->count, nullptr, nullptr);
+        a.part_val = p.val; a.part_idx = p.idx; a.part_sum = p.sum; a.smp.part_raw = p.raw; a.smp.part_max = p.max;
+        if constexpr (!subset) { a.cand_val = p.cand_val; a.cand_idx = p.cand_idx; a.part_ent = p.ent; }
+    }
+    // the repetition penalty of a generating turn: the single-env flags, or the flag row d_pen_rows[b] of every batch row
+    void with_penalty(GemvArgs& a, bool on) { if (on) { a.pen_flags = pen_flags; a.pen = rep_penalty; } }
+    template <class A> void with_penalty(A& a, bool on, bool rows) {
+        if (on) { a.pen_flags = rows ? pen_flags_b : pen_flags; a.pen_rows = rows ? d_pen_rows : nullptr; a.pen = rep_penalty; }
+    }
+    // the routing of a head of several rows: one pass of 32-row MFMA tiles from batched_mfma_min rows, else the batched GEMV
+    static bool mfma_head_fits(int rows, int N, int K) { return rows >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048; }
+    // Where a merge writes.  single: launch_argmax_final on one row (gen: launch_argmax_step, guarded by the done flag; lists and entropy go
+    // to row GenCtl::count, the token's penalty flag is set in step_flags); else launch_argmax_final_batched (row_scale: the producer's).  k = 0: no lists.
+    struct HeadOut { bool single, gen; int* tok; float* score; int k; int* top_ids; float* top_lp; float* ent; uint8_t* step_flags = nullptr; const float* row_scale = nullptr; };
+    HeadOut out_single(bool gen, bool pen, int k) { return {true, gen, d_token, d_scores, k, d_topi, d_topl, d_ent, pen ? pen_flags : nullptr}; }
+    HeadOut out_rows(int tok0, int k) { return {false, false, d_tok_b + tok0, d_score_b + tok0, k, d_topi_b + (size_t)tok0 * k, d_topl_b + (size_t)tok0 * k, d_ent_b + tok0}; }
+    // What follows every product: the lists' merge (k > 0), the entropy merge (f.ent), then the step / final kernel -- in this order: the
+    // step kernel advances GenCtl::count, which the merges index by.  n_part partials per row with c candidates each; c == 1: the partials
+    // are the candidates as they stand (the subset product, a truncated row) and there is no part_ent (t = 0).
+    void merge_head(const HeadParts& p, int n_part, int c, int rows, HeadForm f, const HeadOut& o) {
+        const float *ps = f.lse || f.smp ? p.sum : nullptr, *pr = f.smp ? p.raw : nullptr, *pm = f.smp ? p.max : nullptr;
+        const int *row = o.gen ? &d_ctl->count : nullptr, *skip = o.gen ? &d_ctl->done : nullptr;
+        if (o.k) launch_topk_merge(st, c == 1 ? (f.smp ? p.max : p.val) : p.cand_val, c == 1 ? p.idx : p.cand_idx, n_part, c, rows, o.k, p.val, p.idx, p.sum, pm, o.top_ids, o.top_lp, row, skip);
+        if (f.ent) launch_entropy_merge(st, p.val, p.idx, p.sum, pm, c == 1 ? nullptr : p.ent, n_part, rows, o.ent, row, skip);
+        if (o.gen) launch_argmax_step(st, p.val, p.idx, n_part, o.tok, d_top2, d_ctl, d_eos, d_out_ids, o.step_flags, ps, o.score, pr, pm);
+        else if (o.single) launch_argmax_final(st, p.val, p.idx, n_part, o.tok, d_top2, ps, o.score, pr, pm);
+        else launch_argmax_final_batched(st, p.val, p.idx, n_part, rows, o.tok, ps, o.score, o.row_scale, pr, pm);
+    }
+    // svln_sampling_truncation, in front of the merge: the product's candidates -> the 8-entry row(s) tr_*, which the final kernel and the
+    // lists' merge then read in place of the product's partials (n_part and c become those of the row)
+    HeadParts truncate(const HeadParts& p, const HeadParts& tr, int& n_part, int& c, int rows, const Draws& dr, const int* skip) {
+        launch_truncate_partials(st, c == 1 ? p.max : p.cand_val, c == 1 ? p.idx : p.cand_idx, n_part, c, rows, trunc_k, trunc_p,
+                                 smp_args(dr.stream, dr.draw, dr.count, tr.raw, tr.max), tr.val, tr.idx, tr.sum, skip);
+        n_part = TOPK_C; c = 1;
+        return tr;
+    }
+    // the subset product of the engine's own list on its lm_head for B rows (svln_set_allowed_tokens), aimed at p in form f
+    GemvSubsetArgs subset_args(const void* xrows, int ldx, int B, const HeadParts& p, HeadForm f, const Draws* dr = nullptr) {
+        GemvSubsetArgs a; a.ids = d_allow; a.n = allow_n; a.W = lm_head; a.ldw = H; a.x = xrows; a.ldx = ldx; a.V = V; a.K = H; a.B = B;
+        aim(a, p, f, dr); return a;
+    }
     // final norm -> hidden tap row -> lm_head arg-max -> d_token  (lm_head on the LAST position only).
     // `gen`: the arg-max also runs one step of the greedy loop on the device (GenCtl: append, EOS / max_new stop, advance the position)
     // and every launch is guarded by the done flag.
     // With `gen` the tap row is GenCtl.count on the device (= tap_row on the host: tokens emitted so far), so the three launches are the
     // same for every decode step and sit at the end of the captured step graph.
-    // the subset product of the engine's own list on its lm_head for B rows (svln_set_allowed_tokens); the epilogue follows the switches
-    GemvSubsetArgs subset_args(const void* xrows, int ldx, int B, float* pv, int* pi, float* psum) {
-        GemvSubsetArgs a; a.ids = d_allow; a.n = allow_n; a.W = lm_head; a.ldw = H; a.x = xrows; a.ldx = ldx; a.V = V; a.K = H; a.B = B;
-        a.epi = smp_on ? EPI_SAMPLE : scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX;
-        a.part_val = pv; a.part_idx = pi; a.part_sum = psum; return a;
-    }
     void head(const T* xrow, int tap_row, bool gen) {
         T* tap = hid_tap + (size_t)(tap_row < HID_TAP_ROWS ? tap_row : HID_TAP_ROWS - 1) * H;
         const int* skip = gen ? &d_ctl->done : nullptr;
@@ -1422,58 +1479,31 @@ public:
         } else {
             launch_rmsnorm<T>(st, xrow, final_norm, tap, 1, H, c.rms_eps, skip);
         }
-        GemvArgs a = with12(with4(with8(gemv_args(lm_head, H, tap, nullptr, nullptr, nullptr, nullptr, V, H, smp_on ? EPI_SAMPLE : scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX), lm_head8), lm_head4), lm_head12);
-        a.skip = skip;
+        const HeadForm f = head_form_now();
+        HeadParts p = parts();
         const bool pen = gen && rep_penalty != 1.0f;
-        if (pen) { a.pen_flags = pen_flags; a.pen = rep_penalty; }
-        const float* ps = scores_on || smp_on ? part_sum : nullptr;          // svln_set_token_scores: the sibling kernels, scores[count] beside out_ids[count]
-        a.part_sum = part_sum;
         // svln_set_sampling: stream and draw come from GenCtl on the device (the turn wrote them), so a captured step stays valid
-        if (smp_on) a.smp = smp_args(&d_ctl->stream, &d_ctl->draw0, &d_ctl->count, part_raw, part_max);
-        const float *pr = smp_on ? part_raw : nullptr, *pm = smp_on ? part_max : nullptr;
-        int n_part = gemv_grid(V);
-        // svln_top_logprobs: the lists of this token -> d_topi / d_topl [count], before the step kernel advances the count
-        const int* trow = gen ? &d_ctl->count : nullptr;
-        if (topk || trunc_k) { a.epi = smp_on ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK; a.cand_val = cand_val; a.cand_idx = cand_idx; }
-        // svln_token_entropy (never with the lists or the truncation): the entropy of this token's distribution -> d_ent[count]
-        if (ent_on) { a.epi = smp_on ? EPI_SAMPLE_ENT : EPI_ARGMAX_LSE_ENT; a.part_ent = part_ent; }
-        if (trunc_k) {
-            // svln_sampling_truncation: the product as it stands, then the candidates -> the 8-entry row tr_*, which the step / final
-            // kernel and the lists' merge read in place of the product's partials (under an allowed list: its partials are the candidates)
-            if (allow_on) {
-                GemvSubsetArgs sa = subset_args(tap, H, 1, part_val, part_idx, part_sum);
-                sa.skip = skip; sa.smp = a.smp;
-                if (pen) { sa.pen_flags = pen_flags; sa.pen = rep_penalty; }
-                launch_gemv_subset<T>(st, sa);
-                if (scores_on) launch_subset_logprobs(st, part_max, allow_n, 1, d_alp, gen ? &d_ctl->count : nullptr, skip);
-                launch_truncate_partials(st, part_max, part_idx, allow_n, 1, 1, trunc_k, trunc_p, smp_args(a.smp.stream, a.smp.draw, a.smp.count, tr_raw, tr_max), tr_val, tr_idx, tr_sum, skip);
-            } else {
-                launch_gemv<T>(st, a);
-                launch_truncate_partials(st, cand_val, cand_idx, n_part, TOPK_C, 1, trunc_k, trunc_p, smp_args(a.smp.stream, a.smp.draw, a.smp.count, tr_raw, tr_max), tr_val, tr_idx, tr_sum, skip);
-            }
-            if (topk) launch_topk_merge(st, tr_max, tr_idx, TOPK_C, 1, 1, topk, tr_val, tr_idx, tr_sum, tr_max, d_topi, d_topl, trow, skip);
-            if (gen) launch_argmax_step(st, tr_val, tr_idx, TOPK_C, d_token, d_top2, d_ctl, d_eos, d_out_ids, pen ? pen_flags : nullptr, tr_sum, d_scores, tr_raw, tr_max);
-            else launch_argmax_final(st, tr_val, tr_idx, TOPK_C, d_token, d_top2, tr_sum, d_scores, tr_raw, tr_max);
-            return;
-        }
+        const Draws dr{&d_ctl->stream, &d_ctl->draw0, &d_ctl->count};
+        int n_part = gemv_grid(V), cc = TOPK_C;
         if (allow_on) {
             // svln_set_allowed_tokens: the subset product on the engine-dtype lm_head, one partial per listed id; with the scores on, the
             // normalised row goes to d_alp[count] before the step kernel advances the count
-            GemvSubsetArgs sa = subset_args(tap, H, 1, part_val, part_idx, part_sum);
-            sa.skip = skip; sa.smp = a.smp;
-            if (pen) { sa.pen_flags = pen_flags; sa.pen = rep_penalty; }
+            GemvSubsetArgs sa = subset_args(tap, H, 1, p, f, &dr);
+            sa.skip = skip;
+            with_penalty(sa, pen, false);
             launch_gemv_subset<T>(st, sa);
-            if (scores_on) launch_subset_logprobs(st, smp_on ? part_max : part_val, allow_n, 1, d_alp, gen ? &d_ctl->count : nullptr, skip);
-            n_part = allow_n;
-            if (topk) launch_topk_merge(st, smp_on ? part_max : part_val, part_idx, n_part, 1, 1, topk, part_val, part_idx, part_sum, pm, d_topi, d_topl, trow, skip);
-            if (ent_on) launch_entropy_merge(st, part_val, part_idx, part_sum, pm, nullptr, n_part, 1, d_ent, trow, skip);
+            if (scores_on) launch_subset_logprobs(st, f.smp ? p.max : p.val, allow_n, 1, d_alp, gen ? &d_ctl->count : nullptr, skip);
+            n_part = allow_n; cc = 1;
         } else {
+            GemvArgs a = with12(with4(with8(gemv_args(lm_head, H, tap, nullptr, nullptr, nullptr, nullptr, V, H, EPI_ARGMAX), lm_head8), lm_head4), lm_head12);
+            a.skip = skip;
+            aim(a, p, f, &dr);
+            with_penalty(a, pen);
             launch_gemv<T>(st, a);
-            if (topk) launch_topk_merge(st, cand_val, cand_idx, n_part, TOPK_C, 1, topk, part_val, part_idx, part_sum, pm, d_topi, d_topl, trow, skip);
-            if (ent_on) launch_entropy_merge(st, part_val, part_idx, part_sum, pm, part_ent, n_part, 1, d_ent, trow, skip);
         }
-        if (gen) launch_argmax_step(st, part_val, part_idx, n_part, d_token, d_top2, d_ctl, d_eos, d_out_ids, pen ? pen_flags : nullptr, ps, d_scores, pr, pm);
-        else launch_argmax_final(st, part_val, part_idx, n_part, d_token, d_top2, ps, d_scores, pr, pm);
+        if (trunc_k) p = truncate(p, trunc_parts(), n_part, cc, 1, dr, skip);
+        // svln_top_logprobs / svln_token_entropy: the lists / the entropy of this token -> d_topi / d_topl / d_ent [count]
+        merge_head(p, n_part, cc, 1, f, out_single(gen, pen, topk));
     }
     // One decode step as a fixed op sequence; every run-time scalar is read from device memory (d_ctl,
     // d_token) so any sub-range [lo, hi) of the sequence can be captured once and graph-replayed.
@@ -1641,7 +1671,7 @@ public:
         const bool probing = probe_on && first_tap_row == 1 && probe_used + 2 <= probe_ev.size();
         if (use_graph) {
             GraphSet& gs = graphs[env];
-            const int sk = (scores_on ? 10000 : 0) + (smp_on ? 20000 : 0) + (p12_on ? 40000 : 0) + 100000 * topk + (ent_on ? 1000000 : 0);      // the captured head is the plain, the scored or the sampled one; the GEMVs read the packed weights or not
+            const int sk = head_graph_key() + (p12_on ? 40000 : 0);      // the captured head is the plain, the scored or the sampled one; the GEMVs read the packed weights or not
             auto get = [&](int key, int lo, int hi, int more) {
                 auto it = gs.ex.find(key);
                 if (it == gs.ex.end()) it = gs.ex.emplace(key, capture(e, lo, hi, more)).first;
@@ -1674,90 +1704,45 @@ public:
         GemvBatchArgs a; a.W = W; a.ldw = ldw; a.x = xin; a.ldx = ldx; a.norm_w = norm_w; a.eps = c.rms_eps; a.bias = bias; a.res = res; a.ldr = ldr;
         a.y = y; a.ldy = ldy; a.N = N; a.K = K; a.epi = epi; a.B = B; a.part_val = part_val_b; a.part_idx = part_idx_b; return a;
     }
-    // final norm of rows[0..B) -> lm_head once for all B envs -> d_tok_b[0..B)
-    // pen: the repetition penalty is on and d_pen_rows[0..B) holds the job slot (= flag row) of every batch row
     // arg-max over W [N][K] . x_b for B rows -> d_tok_b.  B >= 4: one pass of 32-row MFMA tiles with the arg-max in the epilogue (the
     // batched GEMV is dot-product-issue bound from B = 4: 386 us at B = 8 on the full vocabulary); B <= 2: the batched GEMV.
+    // pen: the repetition penalty is on and d_pen_rows[0..B) holds the job slot (= flag row) of every batch row
     // svln_set_token_scores: the EPI_ARGMAX_LSE siblings, row b's log-probability -> d_score_b[tok0 + b]
     void argmax_rows(const void* W, int ldw, const T* xrows, int ldx, int N, int K, int B, bool pen, int tok0 = 0) {       // -> d_tok_b[tok0 ..)
+        const HeadForm f = head_form_now();
+        HeadParts p = parts_b();
         // svln_set_sampling: the EPI_SAMPLE siblings; row b's stream / draw are d_smp[tok0 + b] / d_smp[SMP_ROWS + tok0 + b]
-        const float* ps = scores_on || smp_on ? part_sum_b : nullptr;
-        const float *pr = smp_on ? part_raw_b : nullptr, *pm = smp_on ? part_max_b : nullptr;
-        const SampleArgs sa = smp_args(d_smp + tok0, d_smp + SMP_ROWS + tok0, nullptr, part_raw_b, part_max_b);
-        if (trunc_k) {
-            // svln_sampling_truncation: the product of the branch below in its candidate form, then rows [0, B) of tr_*_b -> the unchanged
-            // final kernel (and the lists' merge) on TOPK_C partials per row
-            const float* cv = cand_val_b; const int* ci = cand_idx_b; int n = 0, cc = TOPK_C;
-            if (allow_on && W == (const void*)lm_head) {
-                GemvSubsetArgs su = subset_args(xrows, ldx, B, part_val_b, part_idx_b, part_sum_b);
-                su.smp = sa;
-                if (pen) { su.pen_flags = pen_flags_b; su.pen_rows = d_pen_rows; su.pen = rep_penalty; }
-                launch_gemv_subset<T>(st, su);
-                if (scores_on) launch_subset_logprobs(st, part_max_b, allow_n, B, d_alp_b + (size_t)tok0 * allow_n);
-                cv = part_max_b; ci = part_idx_b; n = allow_n; cc = 1;
-            } else if (B >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048) {
-                GemmArgs a = gemm_args(xrows, ldx, W, ldw, nullptr, 0, nullptr, nullptr, 0, 0, B, N, K, EPI_ARGMAX);
-                a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b; a.smp = sa;
-                if (pen) { a.pen_flags = pen_flags_b; a.pen_rows = d_pen_rows; a.pen = rep_penalty; }
-                a.cand_val = cand_val_b; a.cand_idx = cand_idx_b;
-                n = launch_gemm_argmax<T>(st, a);
-            } else {
-                GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, EPI_SAMPLE_TOPK, B);
-                hb.part_sum = part_sum_b; hb.smp = sa;
-                if (pen) { hb.pen_flags = pen_flags_b; hb.pen_rows = d_pen_rows; hb.pen = rep_penalty; }
-                hb.cand_val = cand_val_b; hb.cand_idx = cand_idx_b;
-                launch_gemv_batched<T>(st, hb);
-                n = gemv_batched_grid(N, EPI_ARGMAX, B);
-            }
-            launch_truncate_partials(st, cv, ci, n, cc, B, trunc_k, trunc_p, smp_args(sa.stream, sa.draw, nullptr, tr_raw_b, tr_max_b), tr_val_b, tr_idx_b, tr_sum_b);
-            launch_argmax_final_batched(st, tr_val_b, tr_idx_b, TOPK_C, B, d_tok_b + tok0, tr_sum_b, d_score_b + tok0, nullptr, tr_raw_b, tr_max_b);
-            if (topk) launch_topk_merge(st, tr_max_b, tr_idx_b, TOPK_C, 1, B, topk, tr_val_b, tr_idx_b, tr_sum_b, tr_max_b, d_topi_b + (size_t)tok0 * topk, d_topl_b + (size_t)tok0 * topk);
-            return;
-        }
+        const Draws dr{d_smp + tok0, d_smp + SMP_ROWS + tok0, nullptr};
+        int n = allow_n, cc = TOPK_C;
         if (allow_on && W == (const void*)lm_head) {
             // svln_set_allowed_tokens: the subset product whatever the row count; row b's normalised row -> d_alp_b[tok0 + b]
-            GemvSubsetArgs su = subset_args(xrows, ldx, B, part_val_b, part_idx_b, part_sum_b);
-            if (smp_on) su.smp = sa;
-            if (pen) { su.pen_flags = pen_flags_b; su.pen_rows = d_pen_rows; su.pen = rep_penalty; }
+            GemvSubsetArgs su = subset_args(xrows, ldx, B, p, f, &dr);
+            with_penalty(su, pen, true);
             launch_gemv_subset<T>(st, su);
-            if (scores_on) launch_subset_logprobs(st, smp_on ? part_max_b : part_val_b, allow_n, B, d_alp_b + (size_t)tok0 * allow_n);
-            launch_argmax_final_batched(st, part_val_b, part_idx_b, allow_n, B, d_tok_b + tok0, ps, d_score_b + tok0, nullptr, pr, pm);
-            if (topk) launch_topk_merge(st, smp_on ? part_max_b : part_val_b, part_idx_b, allow_n, 1, B, topk, part_val_b, part_idx_b, part_sum_b, pm, d_topi_b + (size_t)tok0 * topk, d_topl_b + (size_t)tok0 * topk);
-            if (ent_on) launch_entropy_merge(st, part_val_b, part_idx_b, part_sum_b, pm, nullptr, allow_n, B, d_ent_b + tok0);
-            return;
-        }
-        if (B >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048) {
+            if (scores_on) launch_subset_logprobs(st, f.smp ? p.max : p.val, allow_n, B, d_alp_b + (size_t)tok0 * allow_n);
+            cc = 1;
+        } else if (mfma_head_fits(B, N, K)) {
             GemmArgs a = gemm_args(xrows, ldx, W, ldw, nullptr, 0, nullptr, nullptr, 0, 0, B, N, K, EPI_ARGMAX);
-            a.part_val = part_val_b; a.part_idx = part_idx_b;
-            if (scores_on || smp_on) a.part_sum = part_sum_b;
-            if (smp_on) a.smp = sa;
-            if (pen) { a.pen_flags = pen_flags_b; a.pen_rows = d_pen_rows; a.pen = rep_penalty; }
-            if (topk) { a.cand_val = cand_val_b; a.cand_idx = cand_idx_b; }
-            if (ent_on) a.part_ent = part_ent_b;
-            const int n = launch_gemm_argmax<T>(st, a);
-            launch_argmax_final_batched(st, part_val_b, part_idx_b, n, B, d_tok_b + tok0, ps, d_score_b + tok0, nullptr, pr, pm);
-            if (topk) launch_topk_merge(st, cand_val_b, cand_idx_b, n, TOPK_C, B, topk, part_val_b, part_idx_b, part_sum_b, pm, d_topi_b + (size_t)tok0 * topk, d_topl_b + (size_t)tok0 * topk);
-            if (ent_on) launch_entropy_merge(st, part_val_b, part_idx_b, part_sum_b, pm, part_ent_b, n, B, d_ent_b + tok0);
-            return;
+            aim(a, p, f, &dr);
+            with_penalty(a, pen, true);
+            n = launch_gemm_argmax<T>(st, a);
+        } else {
+            GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, EPI_ARGMAX, B);
+            aim(hb, p, f, &dr);
+            with_penalty(hb, pen, true);
+            launch_gemv_batched<T>(st, hb);
+            n = gemv_batched_grid(N, EPI_ARGMAX, B);
         }
-        GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, smp_on ? EPI_SAMPLE : scores_on ? EPI_ARGMAX_LSE : EPI_ARGMAX, B);
-        hb.part_sum = part_sum_b;
-        if (smp_on) hb.smp = sa;
-        if (pen) { hb.pen_flags = pen_flags_b; hb.pen_rows = d_pen_rows; hb.pen = rep_penalty; }
-        if (topk) { hb.epi = smp_on ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK; hb.cand_val = cand_val_b; hb.cand_idx = cand_idx_b; }
-        if (ent_on) { hb.epi = smp_on ? EPI_SAMPLE_ENT : EPI_ARGMAX_LSE_ENT; hb.part_ent = part_ent_b; }
-        launch_gemv_batched<T>(st, hb);
-        launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(N, EPI_ARGMAX, B), B, d_tok_b + tok0, ps, d_score_b + tok0, nullptr, pr, pm);
-        if (topk) launch_topk_merge(st, cand_val_b, cand_idx_b, gemv_batched_grid(N, EPI_ARGMAX, B), TOPK_C, B, topk, part_val_b, part_idx_b, part_sum_b, pm, d_topi_b + (size_t)tok0 * topk, d_topl_b + (size_t)tok0 * topk);
-        if (ent_on) launch_entropy_merge(st, part_val_b, part_idx_b, part_sum_b, pm, part_ent_b, gemv_batched_grid(N, EPI_ARGMAX, B), B, d_ent_b + tok0);
+        if (trunc_k) p = truncate(p, trunc_parts_b(), n, cc, B, dr, nullptr);
+        merge_head(p, n, cc, B, f, out_rows(tok0, topk));
     }
     void head_batched(const T* rows, int B, bool pen = false) {
         launch_rmsnorm<T>(st, rows, final_norm, xn, B, H, c.rms_eps);
         if (mx4b_on && !allow_on) {      // (an allowed list reads the engine-dtype lm_head on every path)
             GemvMx4BatchArgs hb = gemvb4_args(lm_head4, H, xn, H, nullptr, nullptr, 0, nullptr, 0, V, H, EPI_ARGMAX, B);
-            if (pen) { hb.pen_flags = pen_flags_b; hb.pen_rows = d_pen_rows; hb.pen = rep_penalty; }
+            with_penalty(hb, pen, true);
             launch_gemv_mx4b(st, hb);
-            launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_mx4b_grid(V, EPI_ARGMAX), B, d_tok_b);
+            merge_head(parts_b(), gemv_mx4b_grid(V, EPI_ARGMAX), TOPK_C, B, head_form(EPI_ARGMAX), out_rows(0, 0));
             return;
         }
         argmax_rows(lm_head, H, xn, H, V, H, B, pen);
@@ -1765,7 +1750,7 @@ public:
     // rows argmax_rows is given for n >= 2 head rows of a ride: the 32-row MFMA tiles take any row count from batched_mfma_min up, the
     // batched GEMV 2, 4 or 8 (the pad rows are stale rows of xn: readable, their arg-maxes never read)
     int ride_head_rows(int n) const {
-        if (n >= batched_mfma_min && H % Elt<T>::PER_CHUNK == 0 && (V + 127) / 128 <= 2048) return n;
+        if (mfma_head_fits(n, V, H)) return n;
         return n <= 2 ? 2 : n <= 4 ? 4 : 8;
     }
     // head of a ride: final norm of the last n rows of the M prefill rows -> xn[0 .. n), lm_head arg-max of every row -> d_tok_b, then
@@ -1965,7 +1950,7 @@ public:
         HIP_CHECK(hipMemcpyAsync(cand_val_b, cv, nc * sizeof(float), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipMemcpyAsync(cand_idx_b, ci, nc * sizeof(int), hipMemcpyHostToDevice, st));
         launch_truncate_partials(st, cand_val_b, cand_idx_b, n_part, cc, B, top_k, top_p, sa, tr_val_b, tr_idx_b, tr_sum_b);
-        launch_argmax_final_batched(st, tr_val_b, tr_idx_b, TOPK_C, B, d_tok_b, tr_sum_b, d_score_b, nullptr, tr_raw_b, tr_max_b);
+        merge_head(trunc_parts_b(), TOPK_C, 1, B, head_form(EPI_SAMPLE), out_rows(0, 0));
         const size_t nb = (size_t)B * TOPK_C;
         HIP_CHECK(hipMemcpyAsync(pv, tr_val_b, nb * sizeof(float), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipMemcpyAsync(pi, tr_idx_b, nb * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2225,9 +2210,10 @@ public:
         const bool sampled = smp.temperature > 0.0f;
         ensure_allow_buffers();
         const int n = a.n, B = a.B;
-        a.epi = sampled ? EPI_SAMPLE : EPI_ARGMAX_LSE;
-        a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b; a.ids = d_op_allow; a.skip = nullptr;
+        const HeadForm f = head_form(sampled ? EPI_SAMPLE : EPI_ARGMAX_LSE);
+        a.ids = d_op_allow; a.skip = nullptr;
         if (sampled) a.smp = op_sample_args(smp, B, part_raw_b, part_max_b, true);
+        aim(a, parts_b(), f);
         HIP_CHECK(hipStreamSynchronize(st));
         std::vector<int> l(n);
         for (int k = 0; k < n; ++k) l[k] = (int)ids[k];
@@ -2235,7 +2221,7 @@ public:
         const float* ysrc = sampled ? part_max_b : part_val_b;
         launch_gemv_subset<T>(st, a);
         launch_subset_logprobs(st, ysrc, n, B, d_alp_b);
-        launch_argmax_final_batched(st, part_val_b, part_idx_b, n, B, d_tok_b, part_sum_b, d_score_b, nullptr, a.smp.part_raw, a.smp.part_max);
+        merge_head(parts_b(), n, 1, B, f, out_rows(0, 0));
         HIP_CHECK(hipMemcpyAsync(h_alp_b, d_alp_b, (size_t)B * n * sizeof(float), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipMemcpyAsync(host_y, ysrc, (size_t)B * n * sizeof(float), hipMemcpyDeviceToHost, st));
         batched_scores_out(B, host_tokens, host_logprobs, "op_subset_argmax");
@@ -2525,11 +2511,7 @@ public:
             const int r = std::min(nf - r0, 32);
             const T* rows_x = bf_xn + (size_t)r0 * H;
             if (allow_on) {
-                GemvSubsetArgs su = subset_args(rows_x, H, r, part_val_b, part_idx_b, part_sum_b);
-                su.epi = EPI_TARGET; su.tg_inv_t = inv_t;
-                launch_gemv_subset<T>(st, su);
-                launch_subset_logprobs(st, part_val_b, allow_n, r, bf_dev_alp + (size_t)r0 * allow_n);
-                launch_argmax_final_batched(st, part_val_b, part_idx_b, allow_n, r, d.tok + r0, part_sum_b, d.score + r0);
+                target_subset_rows(rows_x, r, inv_t, bf_dev_alp + (size_t)r0 * allow_n, d.tok + r0, d.score + r0);
             } else {
                 const TargetOut o{d.tgt + r0, d.val + r0, d.tok + r0, d.score + r0, d.lp + r0};
                 target_rows(lm_head, H, rows_x, H, V, H, ride_head_rows(r), r, inv_t, &o);
@@ -3681,18 +3663,31 @@ public:
     void target_rows(const void* W, int ldw, const T* xrows, int ldx, int N, int K, int rows, int n, float inv_t, const TargetOut* to = nullptr) {
         const TargetOut o = to ? *to : TargetOut{d_ftgt, d_fval, d_tok_b, d_score_b, d_flp};
         TargetArgs tg; tg.tgt = o.tgt; tg.tgt_val = o.val; tg.inv_t = inv_t;
+        const HeadParts p = parts_b();
         int np;
-        if (rows >= batched_mfma_min && K % Elt<T>::PER_CHUNK == 0 && (N + 127) / 128 <= 2048) {
+        if (mfma_head_fits(rows, N, K)) {        // (the callers take the subset product themselves: target_subset_rows)
             GemmArgs a = gemm_args(xrows, ldx, W, ldw, nullptr, 0, nullptr, nullptr, 0, 0, rows, N, K, EPI_ARGMAX);
-            a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b; a.tg = tg;
+            aim(a, p, head_form(EPI_TARGET)); a.tg = tg;
             np = launch_gemm_argmax<T>(st, a);
         } else {
-            GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, EPI_TARGET, rows);
-            hb.part_sum = part_sum_b; hb.tg = tg;
+            GemvBatchArgs hb = gemvb_args(W, ldw, xrows, ldx, nullptr, nullptr, nullptr, 0, nullptr, 0, N, K, EPI_ARGMAX, rows);
+            aim(hb, p, head_form(EPI_TARGET)); hb.tg = tg;
             launch_gemv_batched<T>(st, hb);
             np = gemv_batched_grid(N, EPI_ARGMAX, rows);
         }
-        launch_target_final_batched(st, part_val_b, part_idx_b, part_sum_b, np, n, o.tgt, o.val, o.tok, o.score, o.lp);
+        // (its own final kernel, with the targets' outputs: not merge_head's)
+        launch_target_final_batched(st, p.val, p.idx, p.sum, np, n, o.tgt, o.val, o.tok, o.score, o.lp);
+    }
+    // the same head under an allowed list: the subset product in its forced form on n rows, row i's normalised row -> alp[i] (the score of
+    // a forced id is that row's entry at the id's list position), the greedy ids and their scores through the scored final kernel
+    void target_subset_rows(const T* xrows, int n, float inv_t, float* alp, int* tok, float* score) {
+        const HeadForm f = head_form(EPI_TARGET);
+        GemvSubsetArgs su = subset_args(xrows, H, n, parts_b(), f);
+        su.tg_inv_t = inv_t;
+        launch_gemv_subset<T>(st, su);
+        launch_subset_logprobs(st, part_val_b, allow_n, n, alp);
+        HeadOut o = out_rows(0, 0); o.tok = tok; o.score = score;
+        merge_head(parts_b(), allow_n, 1, n, f, o);
     }
     // every refusal of a forced turn that needs no state of the env (svln_turn_forced checks them before it encodes a frame).  sched: the
     // forced submit of the scheduler (svln_batch_submit_forced) -- no idle-scheduler line, and svln_set_mxfp4_batched is refused too: the
@@ -3764,11 +3759,7 @@ public:
         if (allow_on) {
             // the subset product as on every other path: one partial per listed id on y; row i's normalised row -> d_alp_b[i], and the
             // score of F[i] is that row's entry at the id's list position (the same bits svln_get_allowed_logprobs returns)
-            GemvSubsetArgs su = subset_args(xn, H, n, part_val_b, part_idx_b, part_sum_b);
-            su.epi = EPI_TARGET; su.tg_inv_t = inv_t;
-            launch_gemv_subset<T>(st, su);
-            launch_subset_logprobs(st, part_val_b, allow_n, n, d_alp_b);
-            launch_argmax_final_batched(st, part_val_b, part_idx_b, allow_n, n, d_tok_b, part_sum_b, d_score_b);
+            target_subset_rows(xn, n, inv_t, d_alp_b, d_tok_b, d_score_b);
         } else {
             target_rows(lm_head, H, xn, H, V, H, rows, n, inv_t);
         }
@@ -3833,8 +3824,8 @@ public:
         ensure_forced_buffers();
         upload_targets(targets, a.B, a.B);
         slots_in(host_slots);
-        a.epi = EPI_TARGET; a.norm_w = nullptr; a.pen_flags = nullptr;
-        a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b; a.tg = target_args(inv_t);
+        a.norm_w = nullptr; a.pen_flags = nullptr; a.tg = target_args(inv_t);
+        aim(a, parts_b(), head_form(EPI_TARGET));
         launch_gemv_batched<T>(st, a);
         launch_target_final_batched(st, part_val_b, part_idx_b, part_sum_b, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), a.B, d_ftgt, d_fval, d_tok_b, d_score_b, d_flp);
         target_out(a.B, host_tokens, host_greedy, host_logprobs, host_slots, "op_gemv_batched_target");
@@ -3851,8 +3842,8 @@ public:
         ensure_forced_buffers();
         upload_targets(targets, a.M, a.M);
         slots_in(host_slots);
-        a.zeros = zero_line; a.epi = EPI_ARGMAX; a.pen_flags = nullptr;
-        a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b; a.tg = target_args(inv_t);
+        a.zeros = zero_line; a.pen_flags = nullptr; a.tg = target_args(inv_t);
+        aim(a, parts_b(), head_form(EPI_TARGET));
         const int np = launch_gemm_argmax<T>(st, a);
         launch_target_final_batched(st, part_val_b, part_idx_b, part_sum_b, np, a.M, d_ftgt, d_fval, d_tok_b, d_score_b, d_flp);
         target_out(a.M, host_tokens, host_greedy, host_logprobs, host_slots, "op_gemm_target");
@@ -4282,7 +4273,7 @@ public:
         a.part_val = part_val; a.part_idx = part_idx;
         launch_gemv<T>(st, a);
         if (a.epi == EPI_ARGMAX) {
-            launch_argmax_final(st, part_val, part_idx, gemv_grid(a.N), d_token, d_top2);
+            merge_head(parts(), gemv_grid(a.N), TOPK_C, 1, head_form(EPI_ARGMAX), out_single(false, false, 0));
             const int t = read_token();
             if (host_token) *host_token = t;
         }
@@ -4308,32 +4299,32 @@ public:
         if (!en) return;
         REQUIRE(host_logprobs && en->ent && en->pv && en->pi && en->ps && en->pe && en->n_part && (!sampled || (en->pr && en->pm)), "null output pointer");
     }
-    // the merge and the copies of `rows` rows of n partials each (device arrays pv .. pe, entropies -> de) to the host, on the stream
-    void op_ent_out(const OpEntOut& en, int rows, int n, const float* pv, const int* pi, const float* ps, const float* pr, const float* pm, const float* pe,
-                    float* de) {
-        launch_entropy_merge(st, pv, pi, ps, pm, pe, n, rows, de);
+    // after merge_head: the copies of `rows` rows of n partials each (the arrays of p; the entropies de) to the host, on the stream
+    void op_ent_out(const OpEntOut& en, int rows, int n, const HeadParts& p, bool sampled, const float* de) {
         const size_t nb = (size_t)rows * n;
         HIP_CHECK(hipMemcpyAsync(en.ent, de, rows * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(en.pv, pv, nb * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(en.pi, pi, nb * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(en.ps, ps, nb * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(en.pe, pe, nb * sizeof(float), hipMemcpyDeviceToHost, st));
-        if (pm) {
-            HIP_CHECK(hipMemcpyAsync(en.pr, pr, nb * sizeof(float), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipMemcpyAsync(en.pm, pm, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(en.pv, p.val, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(en.pi, p.idx, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(en.ps, p.sum, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(en.pe, p.ent, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (sampled) {
+            HIP_CHECK(hipMemcpyAsync(en.pr, p.raw, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(en.pm, p.max, nb * sizeof(float), hipMemcpyDeviceToHost, st));
         }
         *en.n_part = n;
     }
+    // the form a test entry asks for with its arguments, whatever the engine's switches say
+    static HeadForm op_form(bool scored, bool sampled, bool lists, bool ent) { return HeadForm{scored && !sampled, sampled, false, lists, ent}; }
     void op_gemv_scores(GemvArgs a, int32_t* host_token, float* host_logprob, const OpSample* smp, const OpEntOut* en) override {
         head_op_refusals(a, host_token, GEMV_ROWS_MAX_LDS);
         op_ent_refusals(en, host_logprob, smp != nullptr);
         if (en) ensure_ent_buffers();
-        a.epi = en ? (smp ? EPI_SAMPLE_ENT : EPI_ARGMAX_LSE_ENT) : smp ? EPI_SAMPLE : host_logprob ? EPI_ARGMAX_LSE : EPI_ARGMAX;
-        a.part_val = part_val; a.part_idx = part_idx; a.part_sum = part_sum; a.part_ent = part_ent;
+        const HeadForm f = op_form(host_logprob, smp, false, en);
         if (smp) a.smp = op_sample_args(*smp, 1, part_raw, part_max, host_logprob != nullptr);
+        aim(a, parts(), f);
         launch_gemv<T>(st, a);
-        if (en) op_ent_out(*en, 1, gemv_grid(a.N), part_val, part_idx, part_sum, a.smp.part_raw, a.smp.part_max, part_ent, d_ent);
-        launch_argmax_final(st, part_val, part_idx, gemv_grid(a.N), d_token, d_top2, host_logprob ? part_sum : nullptr, d_scores, a.smp.part_raw, a.smp.part_max);
+        merge_head(parts(), gemv_grid(a.N), TOPK_C, 1, f, out_single(false, false, 0));
+        if (en) op_ent_out(*en, 1, gemv_grid(a.N), parts(), f.smp, d_ent);
         if (host_logprob) HIP_CHECK(hipMemcpyAsync(h_scores, d_scores, sizeof(float), hipMemcpyDeviceToHost, st));
         *host_token = read_token();
         if (host_logprob) *host_logprob = h_scores[0];
@@ -4349,12 +4340,13 @@ public:
         const int np = gemv_grid(a.N);
         ensure_topk_buffers();
         float* d_cv = cand_val_b; int *d_ci = cand_idx_b, *d_ti = d_topi_b; float* d_tl = d_topl_b;      // (the batched heads' buffers: idle in a test entry)
-        a.part_val = part_val; a.part_idx = part_idx; a.part_sum = part_sum;
+        const HeadForm f = op_form(true, smp, true, false);
+        HeadParts p = parts(); p.cand_val = d_cv; p.cand_idx = d_ci;
+        HeadOut o = out_single(false, false, k); o.top_ids = d_ti; o.top_lp = d_tl;
         if (smp) a.smp = op_sample_args(*smp, 1, part_raw, part_max, true);
-        a.epi = smp ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK; a.cand_val = d_cv; a.cand_idx = d_ci;
+        aim(a, p, f);
         launch_gemv<T>(st, a);
-        launch_topk_merge(st, d_cv, d_ci, np, TOPK_C, 1, k, part_val, part_idx, part_sum, a.smp.part_max, d_ti, d_tl);
-        launch_argmax_final(st, part_val, part_idx, np, d_token, d_top2, part_sum, d_scores, a.smp.part_raw, a.smp.part_max);
+        merge_head(p, np, TOPK_C, 1, f, o);
         hipError_t err = hipMemcpyAsync(h_scores, d_scores, sizeof(float), hipMemcpyDeviceToHost, st);
         auto back = [&](void* dst, const void* src, size_t bytes) { if (err == hipSuccess) err = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); };
         back(pv, part_val, np * sizeof(float)); back(pi, part_idx, np * sizeof(int)); back(ps, part_sum, np * sizeof(float));
@@ -4380,9 +4372,8 @@ public:
         REQUIRE(host_logprobs && tk->cv && tk->ci && tk->top_ids && tk->top_lp && tk->n_part, "null output pointer");
         REQUIRE(tk->k >= 1 && tk->k <= TOPK_C, "k must be 1 .. 8");
     }
-    // ... and run the merge and read candidates and lists back (after the final kernel)
-    void op_topk_rows_out(const OpTopkRows& tk, int rows, int n, const float* pm) {
-        launch_topk_merge(st, cand_val_b, cand_idx_b, n, TOPK_C, rows, tk.k, part_val_b, part_idx_b, part_sum_b, pm, d_topi_b, d_topl_b);
+    // ... and read candidates and lists back (after merge_head)
+    void op_topk_rows_out(const OpTopkRows& tk, int rows, int n) {
         const size_t nc = (size_t)rows * n * TOPK_C;
         HIP_CHECK(hipMemcpyAsync(tk.cv, cand_val_b, nc * sizeof(float), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipMemcpyAsync(tk.ci, cand_idx_b, nc * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -4404,17 +4395,17 @@ public:
         op_ent_refusals(en, host_logprobs, smp != nullptr);
         if (tk) ensure_topk_buffers();
         if (en) ensure_ent_buffers();
-        a.epi = tk ? (smp ? EPI_SAMPLE_TOPK : EPI_ARGMAX_LSE_TOPK) : en ? (smp ? EPI_SAMPLE_ENT : EPI_ARGMAX_LSE_ENT) : smp ? EPI_SAMPLE : host_logprobs ? EPI_ARGMAX_LSE : EPI_ARGMAX;
-        a.part_ent = part_ent_b;
-        a.cand_val = cand_val_b; a.cand_idx = cand_idx_b;
-        a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = part_sum_b;
+        const HeadForm f = op_form(host_logprobs, smp, tk, en);
+        const int n = gemv_batched_grid(a.N, EPI_ARGMAX, a.B);
+        HeadOut o = out_rows(0, tk ? tk->k : 0);
         a.row_scale = row_scale_b;
+        if (host_logprobs && a.norm_w) o.row_scale = row_scale_b;
         if (smp) a.smp = op_sample_args(*smp, a.B, part_raw_b, part_max_b, host_logprobs != nullptr);
+        aim(a, parts_b(), f);
         launch_gemv_batched<T>(st, a);
-        launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), a.B, d_tok_b, host_logprobs ? part_sum_b : nullptr, d_score_b,
-                                    host_logprobs && a.norm_w ? a.row_scale : nullptr, a.smp.part_raw, a.smp.part_max);
-        if (tk) op_topk_rows_out(*tk, a.B, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), a.smp.part_max);
-        if (en) op_ent_out(*en, a.B, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), part_val_b, part_idx_b, part_sum_b, a.smp.part_raw, a.smp.part_max, part_ent_b, d_ent_b);
+        merge_head(parts_b(), n, TOPK_C, a.B, f, o);
+        if (tk) op_topk_rows_out(*tk, a.B, n);
+        if (en) op_ent_out(*en, a.B, n, parts_b(), f.smp, d_ent_b);
         batched_scores_out(a.B, host_tokens, host_logprobs, "op_gemv_batched_scores");
     }
     void op_gemm_argmax_scores(GemmArgs a, int32_t* host_tokens, float* host_logprobs, const OpSample* smp, const OpTopkRows* tk,
@@ -4431,15 +4422,14 @@ public:
         op_ent_refusals(en, host_logprobs, smp != nullptr);
         if (tk) ensure_topk_buffers();
         if (en) ensure_ent_buffers();
-        a.zeros = zero_line; a.epi = EPI_ARGMAX;
-        a.part_val = part_val_b; a.part_idx = part_idx_b; a.part_sum = host_logprobs ? part_sum_b : nullptr;
+        const HeadForm f = op_form(host_logprobs, smp, tk, en);
+        a.zeros = zero_line;
         if (smp) a.smp = op_sample_args(*smp, a.M, part_raw_b, part_max_b, host_logprobs != nullptr);
-        if (tk) { a.cand_val = cand_val_b; a.cand_idx = cand_idx_b; }
-        if (en) a.part_ent = part_ent_b;
+        aim(a, parts_b(), f);
         const int n = launch_gemm_argmax<T>(st, a);
-        launch_argmax_final_batched(st, part_val_b, part_idx_b, n, a.M, d_tok_b, a.part_sum, d_score_b, nullptr, a.smp.part_raw, a.smp.part_max);
-        if (tk) op_topk_rows_out(*tk, a.M, n, a.smp.part_max);
-        if (en) op_ent_out(*en, a.M, n, part_val_b, part_idx_b, part_sum_b, a.smp.part_raw, a.smp.part_max, part_ent_b, d_ent_b);
+        merge_head(parts_b(), n, TOPK_C, a.M, f, out_rows(0, tk ? tk->k : 0));
+        if (tk) op_topk_rows_out(*tk, a.M, n);
+        if (en) op_ent_out(*en, a.M, n, parts_b(), f.smp, d_ent_b);
         batched_scores_out(a.M, host_tokens, host_logprobs, "op_gemm_argmax_scores");
     }
     void op_gemv_batched(GemvBatchArgs a, int32_t* host_tokens) override {
@@ -4452,7 +4442,7 @@ public:
         if (a.epi == EPI_ARGMAX && !a.norm_w) argmax_rows(a.W, a.ldw, (const T*)a.x, a.ldx, a.N, a.K, a.B, false);      // the engine's own routing (MFMA tiles from B = 4)
         else launch_gemv_batched<T>(st, a);
         if (a.epi == EPI_ARGMAX) {
-            if (a.norm_w) launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_batched_grid(a.N, EPI_ARGMAX, a.B), a.B, d_tok_b);
+            if (a.norm_w) merge_head(parts_b(), gemv_batched_grid(a.N, EPI_ARGMAX, a.B), TOPK_C, a.B, head_form(EPI_ARGMAX), out_rows(0, 0));
             HIP_CHECK(hipMemcpyAsync(h_tok_b, d_tok_b, a.B * sizeof(int), hipMemcpyDeviceToHost, st));
             sync();
             if (host_tokens) for (int b = 0; b < a.B; ++b) host_tokens[b] = h_tok_b[b];
@@ -4475,7 +4465,7 @@ public:
         a.part_val = part_val_b; a.part_idx = part_idx_b;
         launch_gemv_mx4b(st, a);
         if (a.epi == EPI_ARGMAX) {
-            launch_argmax_final_batched(st, part_val_b, part_idx_b, gemv_mx4b_grid(a.N, EPI_ARGMAX), a.B, d_tok_b);
+            merge_head(parts_b(), gemv_mx4b_grid(a.N, EPI_ARGMAX), TOPK_C, a.B, head_form(EPI_ARGMAX), out_rows(0, 0));
             HIP_CHECK(hipMemcpyAsync(h_tok_b, d_tok_b, a.B * sizeof(int), hipMemcpyDeviceToHost, st));
             sync();
             if (host_tokens) for (int b = 0; b < a.B; ++b) host_tokens[b] = h_tok_b[b];

@@ -375,9 +375,9 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
     const int gw = blockIdx.x * GEMV_WAVES + wave, nw = gridDim.x * GEMV_WAVES;
     const int n_out = EPI == EPI_SWIGLU ? p.N >> 1 : p.N;
 
-    constexpr bool AMAX = epi_is_argmax(EPI), TOPK = epi_is_topk(EPI), ENT = epi_is_ent(EPI);
-    constexpr bool LSE = EPI == EPI_ARGMAX_LSE || EPI == EPI_ARGMAX_LSE_TOPK || EPI == EPI_ARGMAX_LSE_ENT;
-    constexpr bool SMP = EPI == EPI_SAMPLE || EPI == EPI_SAMPLE_TOPK || EPI == EPI_SAMPLE_ENT;
+    constexpr HeadForm F = head_form(EPI);
+    constexpr bool AMAX = epi_is_argmax(EPI), TOPK = F.topk, ENT = F.ent, LSE = F.lse, SMP = F.smp;
+    static_assert(!F.tgt, "the wave-per-rows GEMV has no forced form");
     // EPI_*_TOPK: the wave's TOPK_C best (y, column) pairs, entry l in lane l < TOPK_C, y descending then column ascending; a logit is
     // wave-uniform, so is tk_thr = entry TOPK_C - 1, and the common case of a column costs one scalar compare against it
     [[maybe_unused]] float tk_v = -INFINITY, tk_thr = -INFINITY;
@@ -635,9 +635,8 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_batched_kernel(GemvBatchArg
     const T* xg = (const T*)p.x;
     const T* gg = (const T*)p.norm_w;
     const int n_units = EPI == EPI_SWIGLU ? p.N / R : (p.N + R - 1) / R;      // one unit = R weight rows
-    constexpr bool AMAX = epi_is_argmax(EPI), TGT = EPI == EPI_TARGET, TOPK = epi_is_topk(EPI), ENT = epi_is_ent(EPI);
-    constexpr bool LSE = EPI == EPI_ARGMAX_LSE || EPI == EPI_ARGMAX_LSE_TOPK || EPI == EPI_ARGMAX_LSE_ENT || TGT;
-    constexpr bool SMP = EPI == EPI_SAMPLE || EPI == EPI_SAMPLE_TOPK || EPI == EPI_SAMPLE_ENT;
+    constexpr HeadForm F = head_form(EPI);
+    constexpr bool AMAX = epi_is_argmax(EPI), TGT = F.tgt, TOPK = F.topk, ENT = F.ent, LSE = F.lse, SMP = F.smp;
     static_assert(!(TOPK && NORM), "EPI_*_TOPK has no fused-norm form");
     static_assert(!(ENT && NORM), "EPI_*_ENT has no fused-norm form");
     // EPI_*_TOPK: thread b < B keeps env b's TOPK_C best (y, column) pairs of the workgroup's units in registers, y descending then column
@@ -1158,18 +1157,9 @@ template <typename P> static void launch_gemv_fmt(hipStream_t s, const GemvArgs&
     dim3 g(gemv_grid(a.N)), b(GEMV_THREADS);
     // (the arg-max forms keep gemv_grid: the number of partials is part of their contract with the final kernels)
     if (P::ROWS_GRID_CAP && !epi_is_argmax(a.epi) && g.x > (unsigned)P::ROWS_GRID_CAP) g.x = P::ROWS_GRID_CAP;
-    switch (a.epi) {
-        case EPI_NONE: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_NONE>), g, b, lds); break;
-        case EPI_SWIGLU: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SWIGLU>), g, b, lds); break;
-        case EPI_ARGMAX: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX>), g, b, lds); break;
-        case EPI_ARGMAX_LSE: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX_LSE>), g, b, lds); break;
-        case EPI_SAMPLE: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SAMPLE>), g, b, lds); break;
-        case EPI_ARGMAX_LSE_TOPK: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX_LSE_TOPK>), g, b, lds); break;
-        case EPI_SAMPLE_TOPK: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SAMPLE_TOPK>), g, b, lds); break;
-        case EPI_ARGMAX_LSE_ENT: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_ARGMAX_LSE_ENT>), g, b, lds); break;
-        case EPI_SAMPLE_ENT: SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SAMPLE_ENT>), g, b, lds); break;
-        default: break;
-    }
+    if (a.epi == EPI_NONE) SVLN_LAUNCH((gemv_rows_kernel<P, EPI_NONE>), g, b, lds);
+    else if (a.epi == EPI_SWIGLU) SVLN_LAUNCH((gemv_rows_kernel<P, EPI_SWIGLU>), g, b, lds);
+    else with_head_epi<GEMV_ROWS_EPIS>(a.epi, [&](auto e) { SVLN_LAUNCH((gemv_rows_kernel<P, decltype(e)::value>), g, b, lds); });
 }
 #undef SVLN_LAUNCH
 template <typename T> void launch_gemv_timed(hipStream_t s, const GemvArgs& a, hipEvent_t start, hipEvent_t stop) {
@@ -1197,29 +1187,19 @@ template <typename T, int EPI, bool NORM> static void launch_gb(hipStream_t s, c
 }
 template <typename T> void launch_gemv_batched(hipStream_t s, const GemvBatchArgs& a) {
     const bool norm = a.norm_w != nullptr;
-    switch (a.epi) {
-        case EPI_NONE: if (norm) launch_gb<T, EPI_NONE, true>(s, a); else launch_gb<T, EPI_NONE, false>(s, a); break;
-        case EPI_SWIGLU: if (norm) launch_gb<T, EPI_SWIGLU, true>(s, a); else launch_gb<T, EPI_SWIGLU, false>(s, a); break;
-        case EPI_ARGMAX: if (norm) launch_gb<T, EPI_ARGMAX, true>(s, a); else launch_gb<T, EPI_ARGMAX, false>(s, a); break;
-        case EPI_ARGMAX_LSE: if (norm) launch_gb<T, EPI_ARGMAX_LSE, true>(s, a); else launch_gb<T, EPI_ARGMAX_LSE, false>(s, a); break;
-        case EPI_SAMPLE:
-            if (norm) throw std::runtime_error("batched GEMV: EPI_SAMPLE has no fused-norm form");
-            launch_gb<T, EPI_SAMPLE, false>(s, a);
-            break;
-        case EPI_ARGMAX_LSE_TOPK: case EPI_SAMPLE_TOPK:
-            if (norm || !a.cand_val || !a.cand_idx) throw std::runtime_error("batched GEMV: EPI_*_TOPK takes candidate arrays and no fused norm");
-            if (a.epi == EPI_SAMPLE_TOPK) launch_gb<T, EPI_SAMPLE_TOPK, false>(s, a); else launch_gb<T, EPI_ARGMAX_LSE_TOPK, false>(s, a);
-            break;
-        case EPI_ARGMAX_LSE_ENT: case EPI_SAMPLE_ENT:
-            if (norm || !a.part_ent) throw std::runtime_error("batched GEMV: EPI_*_ENT takes part_ent and no fused norm");
-            if (a.epi == EPI_SAMPLE_ENT) launch_gb<T, EPI_SAMPLE_ENT, false>(s, a); else launch_gb<T, EPI_ARGMAX_LSE_ENT, false>(s, a);
-            break;
-        case EPI_TARGET:
-            if (norm || a.pen_flags || !a.tg.tgt || !a.tg.tgt_val) throw std::runtime_error("batched GEMV: EPI_TARGET takes targets, no fused norm and no penalty flags");
-            launch_gb<T, EPI_TARGET, false>(s, a);
-            break;
-        default: break;
-    }
+    if (a.epi == EPI_NONE) { if (norm) launch_gb<T, EPI_NONE, true>(s, a); else launch_gb<T, EPI_NONE, false>(s, a); return; }
+    if (a.epi == EPI_SWIGLU) { if (norm) launch_gb<T, EPI_SWIGLU, true>(s, a); else launch_gb<T, EPI_SWIGLU, false>(s, a); return; }
+    // the refusals of the arg-max forms: after them a fused norm meets a form that has it (gemv_batched_norm_has)
+    const HeadForm f = head_form(a.epi);
+    if (f.topk && (norm || !a.cand_val || !a.cand_idx)) throw std::runtime_error("batched GEMV: EPI_*_TOPK takes candidate arrays and no fused norm");
+    if (f.ent && (norm || !a.part_ent)) throw std::runtime_error("batched GEMV: EPI_*_ENT takes part_ent and no fused norm");
+    if (f.tgt && (norm || a.pen_flags || !a.tg.tgt || !a.tg.tgt_val)) throw std::runtime_error("batched GEMV: EPI_TARGET takes targets, no fused norm and no penalty flags");
+    if (f.smp && norm) throw std::runtime_error("batched GEMV: EPI_SAMPLE has no fused-norm form");
+    with_head_epi<GEMV_BATCHED_EPIS>(a.epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if constexpr (gemv_batched_norm_has(E)) if (norm) return launch_gb<T, E, true>(s, a);
+        launch_gb<T, E, false>(s, a);
+    });
 }
 template void launch_gemv_batched<bf16>(hipStream_t, const GemvBatchArgs&);
 template void launch_gemv_batched<float>(hipStream_t, const GemvBatchArgs&);
@@ -1252,13 +1232,10 @@ void launch_p12_unpack_rows(hipStream_t s, const void* packed, const void* rec, 
 template <typename P> static void gemv_rows_attrs() {
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_NONE>, GEMV_ROWS_MAX_LDS);
     set_max_lds((const void*)gemv_rows_kernel<P, EPI_SWIGLU>, GEMV_ROWS_MAX_LDS);
-    set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX>, GEMV_ROWS_MAX_LDS);
-    set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX_LSE>, GEMV_ROWS_MAX_LDS);
-    set_max_lds((const void*)gemv_rows_kernel<P, EPI_SAMPLE>, GEMV_ROWS_MAX_LDS);
-    set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX_LSE_TOPK>, GEMV_ROWS_TOPK_MAX_LDS);
-    set_max_lds((const void*)gemv_rows_kernel<P, EPI_SAMPLE_TOPK>, GEMV_ROWS_TOPK_MAX_LDS);
-    set_max_lds((const void*)gemv_rows_kernel<P, EPI_ARGMAX_LSE_ENT>, GEMV_ROWS_MAX_LDS);
-    set_max_lds((const void*)gemv_rows_kernel<P, EPI_SAMPLE_ENT>, GEMV_ROWS_MAX_LDS);
+    for_each_head_epi<GEMV_ROWS_EPIS>([](auto e) {
+        constexpr int E = decltype(e)::value;
+        set_max_lds((const void*)gemv_rows_kernel<P, E>, head_form(E).topk ? GEMV_ROWS_TOPK_MAX_LDS : GEMV_ROWS_MAX_LDS);
+    });
 }
 void gemv_init_attrs() {
     gemv_rows_attrs<WMxfp4>(); gemv_rows_attrs<WE4m3>(); gemv_rows_attrs<WP12>(); gemv_rows_attrs<WPlain<bf16>>(); gemv_rows_attrs<WPlain<float>>();

@@ -25,7 +25,8 @@ constexpr int SUBSET_RB = 4;             // activation rows per pass over the we
 template <typename T, int EPI>
 __global__ __launch_bounds__(GEMV_SUBSET_WAVES * 64) void gemv_subset_kernel(GemvSubsetArgs p) {
     constexpr int EPC = Elt<T>::PER_CHUNK;
-    constexpr bool TGT = EPI == EPI_TARGET, LSE = EPI == EPI_ARGMAX_LSE || TGT, SMP = EPI == EPI_SAMPLE;
+    constexpr HeadForm F = head_form(EPI);
+    constexpr bool TGT = F.tgt, LSE = F.lse, SMP = F.smp;
     if (p.skip && *p.skip) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = blockIdx.x * GEMV_SUBSET_WAVES + wave;
@@ -115,13 +116,7 @@ template <typename T, int EPI> void launch_subset_epi(hipStream_t s, const GemvS
 }  // namespace
 
 template <typename T> void launch_gemv_subset(hipStream_t s, const GemvSubsetArgs& a) {
-    switch (a.epi) {
-        case EPI_ARGMAX: launch_subset_epi<T, EPI_ARGMAX>(s, a); break;
-        case EPI_ARGMAX_LSE: launch_subset_epi<T, EPI_ARGMAX_LSE>(s, a); break;
-        case EPI_SAMPLE: launch_subset_epi<T, EPI_SAMPLE>(s, a); break;
-        case EPI_TARGET: launch_subset_epi<T, EPI_TARGET>(s, a); break;
-        default: break;
-    }
+    with_head_epi<GEMV_SUBSET_EPIS>(a.epi, [&](auto e) { launch_subset_epi<T, decltype(e)::value>(s, a); });
 }
 template void launch_gemv_subset<bf16>(hipStream_t, const GemvSubsetArgs&);
 template void launch_gemv_subset<float>(hipStream_t, const GemvSubsetArgs&);

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace svln {
@@ -36,9 +38,44 @@ enum Epi : int { EPI_NONE = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_SWIGLU =
 // sampled); y as in the _TOPK forms, never the perturbed z.  A -inf column adds 0, the partial that owns nothing has 0.
 // launch_entropy_merge turns them into the row's entropy log S - T / S.
 constexpr int TOPK_C = 8;
-constexpr bool epi_is_topk(int epi) { return epi == EPI_ARGMAX_LSE_TOPK || epi == EPI_SAMPLE_TOPK; }
-constexpr bool epi_is_ent(int epi) { return epi == EPI_ARGMAX_LSE_ENT || epi == EPI_SAMPLE_ENT; }
-constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE || epi == EPI_SAMPLE || epi == EPI_TARGET || epi_is_topk(epi) || epi_is_ent(epi); }
+// The lm_head form: the five facts every EPI_* arg-max sibling is made of.  ONE table, read by the kernels (constexpr HeadForm F =
+// head_form(EPI)), the launchers (with_head_epi) and the engine (which builds a form from its switches and asks head_epi for the kernel).
+//   lse   part_sum is kept relative to part_val (the greedy scored sums).  EPI_TARGET carries it too: where a kernel body says LSE it means
+//         F.lse, forced form included (batched GEMV, MFMA epilogue, subset product; the wave-per-rows GEMV has no forced sibling)
+//   smp   Gumbel-max sampling: part_sum is relative to smp.part_max, beside smp.part_raw; never together with lse
+//   tgt   the capture of one named column per row (with lse, nothing else)
+//   topk  TOPK_C candidates beside every partial (cand_val / cand_idx);  ent: part_ent beside every partial sum (never with topk)
+struct HeadForm { bool lse, smp, tgt, topk, ent; };
+constexpr bool operator==(HeadForm a, HeadForm b) { return a.lse == b.lse && a.smp == b.smp && a.tgt == b.tgt && a.topk == b.topk && a.ent == b.ent; }
+constexpr int HEAD_EPIS[] = {EPI_TARGET, EPI_SAMPLE_TOPK, EPI_ARGMAX_LSE_TOPK, EPI_SAMPLE_ENT, EPI_ARGMAX_LSE_ENT, EPI_SAMPLE, EPI_ARGMAX_LSE, EPI_ARGMAX};      // all eight
+constexpr HeadForm head_form(int epi) {      // (an epilogue that is no arg-max form has no fact)
+    return HeadForm{epi == EPI_ARGMAX_LSE || epi == EPI_TARGET || epi == EPI_ARGMAX_LSE_TOPK || epi == EPI_ARGMAX_LSE_ENT,
+                    epi == EPI_SAMPLE || epi == EPI_SAMPLE_TOPK || epi == EPI_SAMPLE_ENT, epi == EPI_TARGET,
+                    epi == EPI_ARGMAX_LSE_TOPK || epi == EPI_SAMPLE_TOPK, epi == EPI_ARGMAX_LSE_ENT || epi == EPI_SAMPLE_ENT};
+}
+constexpr int head_epi(HeadForm f) {         // -1: a combination nobody has built a kernel for
+    for (int e : HEAD_EPIS) if (head_form(e) == f) return e;
+    return -1;
+}
+constexpr bool epi_is_argmax(int epi) { return head_epi(head_form(epi)) == epi; }
+constexpr bool head_round_trip() { for (int e : HEAD_EPIS) if (!epi_is_argmax(e)) return false; return true; }
+static_assert(sizeof(HEAD_EPIS) / sizeof(int) == 8 && head_round_trip() && !epi_is_argmax(EPI_NONE) && !epi_is_argmax(EPI_SWIGLU), "head_form / head_epi: the eight arg-max forms round-trip");
+static_assert(head_epi({true, false, false, true, true}) == -1 && head_epi({false, true, false, true, true}) == -1, "no entropy form with candidates");
+static_assert(head_epi({false, false, true, false, false}) == -1 && head_epi({true, true, true, false, false}) == -1 && head_epi({true, false, true, true, false}) == -1 &&
+              head_epi({true, false, true, false, true}) == -1 && head_epi({true, true, false, false, false}) == -1, "tgt rides on lse alone; lse and smp exclude each other");
+// Which siblings each product form is instantiated for: the 32 x 128 MFMA epilogue has all of HEAD_EPIS, gemv_mx4b has EPI_ARGMAX only.
+// ONE dispatcher (with_head_epi<LIST>) turns a run-time epi into a kernel and for_each_head_epi<LIST> visits the same set for the attributes.
+// The ORDER of a list (HEAD_EPIS too) is the order in which the product's kernels stand in the code object, kept so that it stays byte for byte.
+constexpr int GEMV_ROWS_EPIS[] = {EPI_ARGMAX, EPI_ARGMAX_LSE, EPI_SAMPLE, EPI_ARGMAX_LSE_TOPK, EPI_SAMPLE_TOPK, EPI_ARGMAX_LSE_ENT, EPI_SAMPLE_ENT};      // wave-per-rows GEMV: no forced form
+constexpr int GEMV_BATCHED_EPIS[] = {EPI_ARGMAX, EPI_ARGMAX_LSE, EPI_SAMPLE, EPI_SAMPLE_TOPK, EPI_ARGMAX_LSE_TOPK, EPI_SAMPLE_ENT, EPI_ARGMAX_LSE_ENT, EPI_TARGET};
+constexpr bool gemv_batched_norm_has(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_LSE; }    // ... of which the fused-norm variant exists for two
+constexpr int GEMV_SUBSET_EPIS[] = {EPI_ARGMAX, EPI_ARGMAX_LSE, EPI_SAMPLE, EPI_TARGET};                // subset product: one id per partial, so no lists and t = 0
+// f(std::integral_constant<int, EPI_...>{}) for the form `epi` names if list L has it, else false (L backwards: a fold's kernels are emitted last first)
+template <auto& L, class F, size_t... I> bool with_head_epi_at(int epi, F&& f, std::index_sequence<I...>) {
+    return ((epi == L[sizeof...(I) - 1 - I] ? (f(std::integral_constant<int, L[sizeof...(I) - 1 - I]>{}), true) : false) || ...);
+}
+template <auto& L, class F> bool with_head_epi(int epi, F&& f) { return with_head_epi_at<L>(epi, f, std::make_index_sequence<sizeof(L) / sizeof(int)>{}); }
+template <auto& L, class F> void for_each_head_epi(F&& f) { for (int e : L) with_head_epi<L>(e, f); }
 // Inputs of EPI_TARGET: tgt [rows] device ids (-1: none), tgt_val [rows] the captured y
 struct TargetArgs { const int* tgt = nullptr; float* tgt_val = nullptr; float inv_t = 1.0f; };
 // Inputs of EPI_SAMPLE.  stream / draw are device arrays indexed by the row of the product (row 0 of a GEMV), read by the kernel: nothing a
@@ -87,23 +124,24 @@ struct GemmArgs {
     // opt-in fp8 (OCP e4m3) operands (bf16 engine): when a_scale is set, A [M][K] and W [N][K] are e4m3 bytes (lda / ldw in
     // elements), C = a_scale[m] * w_scale[n] * (A . W^T) then the usual epilogue in bf16; K % 16 == 0
     const float* a_scale; const float* w_scale;
-    // EPI_ARGMAX (M <= 32 rows, 32x128 tiles, no K split: the lm_head of several envs decoded together): no C; row m's (max, lowest index)
-    // over the 128 columns of tile t goes to part_val / part_idx [m][tiles], reduced by launch_argmax_final_batched.  Optional repetition
-    // penalty as in GemvBatchArgs.
+    // The arg-max forms (launch_gemm_argmax; epi = one of the eight of head_form; M <= 32 rows, 32x128 tiles, no K split: the lm_head of
+    // several envs decoded together): no C; row m's (max, lowest index) over the 128 columns of tile t goes to part_val / part_idx
+    // [m][tiles], reduced by launch_argmax_final_batched.  Optional repetition penalty as in GemvBatchArgs.  The arrays below are read
+    // by the forms that carry the fact, ignored by the others.
     float* part_val = nullptr; int* part_idx = nullptr;
     const uint8_t* pen_flags = nullptr; const int* pen_rows = nullptr; float pen = 1.0f;
-    float* part_sum = nullptr;    // non-null: the EPI_ARGMAX_LSE form, [m][tiles] beside part_val
-    SampleArgs smp;               // smp.part_raw non-null: the EPI_SAMPLE form (part_sum too)
-    TargetArgs tg;                // tg.tgt non-null: the EPI_TARGET form (part_sum too; no penalty flags)
-    float* cand_val = nullptr; int* cand_idx = nullptr;       // non-null (with part_sum): the EPI_*_TOPK form, [m][tiles][TOPK_C]
-    float* part_ent = nullptr;    // non-null (with part_sum, without cand_val): the EPI_*_ENT form, [m][tiles] beside part_sum
+    float* part_sum = nullptr;    // lse / smp: [m][tiles] beside part_val
+    SampleArgs smp;               // smp (smp.part_raw / part_max beside part_sum)
+    TargetArgs tg;                // tgt (no penalty flags)
+    float* cand_val = nullptr; int* cand_idx = nullptr;       // topk: [m][tiles][TOPK_C]
+    float* part_ent = nullptr;    // ent: [m][tiles] beside part_sum
     VitPackArgs vp; int vp_on;    // filled by the launcher: device-side copy of *vitpack for the unsplit kernels that pack in their epilogue
     int force_cfg, force_split;   // tests: 0 = heuristic; force_cfg 129 -> 128x128 tiles with two in-workgroup K groups; force_cfg low bits 128 -> 128x128 tiles, 264 -> 256x64 tiles; force_split S -> 256x128 tiles, S splits
 };
 // true: a.norm_out was produced, or the K / V^T pages of a.vitpack were.  vit_packer (host, optional): the writer of those pages --
 // 0 = none (the caller runs launch_vit_kv_pack), 1 = the split-K reduce (splitk_qkv_vitpack_kernel), 2 = the 128x128 tile epilogue
 template <typename T> bool launch_gemm(hipStream_t s, const GemmArgs& a, int* vit_packer = nullptr);
-template <typename T> int launch_gemm_argmax(hipStream_t s, GemmArgs a);    // EPI_ARGMAX form (M <= 32; EPI_ARGMAX_LSE when a.part_sum is set, EPI_SAMPLE when a.smp.part_raw is, EPI_TARGET when a.tg.tgt is); returns the partials per row
+template <typename T> int launch_gemm_argmax(hipStream_t s, GemmArgs a);    // the arg-max form a.epi names (M <= 32); throws on a form whose arrays are null; returns the partials per row
 
 // y[N] = epi(W[N,K] . x'[K] + bias) + res,  x' = x or rmsnorm(x) * norm_w (fused prologue).
 // EPI_SWIGLU as above (y has N/2 entries).  EPI_ARGMAX: no y; per-workgroup (max, lowest index)
