@@ -424,6 +424,31 @@ int svln_generate_candidates(svln_engine* h, int env, int n_seq, const int64_t* 
 /* svln_turn's bookkeeping (encode, window / episode resets, splice), then the candidates call, in one crossing (a->max_new_tokens is not read) */
 int svln_turn_candidates(svln_engine* h, const svln_turn_args* a, int n_seq, const int64_t* ids, const int32_t* lens, float* logprobs,
                          int64_t* greedy_ids, float* greedy_logprobs);
+/* Opt-in: svln_generate_candidates with the rows of scoring pass 0 FOLDED into the prefill pass.  Arguments, results, refusals, the
+ * pending group and what svln_group_select leaves are svln_generate_candidates'; what changes is where the rows are computed.
+ *   rows      one pass of M = Tn + n_seq r rows: rows [0, Tn) are the prompt's new rows; row Tn + g r + j is the token embedding of
+ *             F_g[j], j < min(r, n_g - 1), at position L + j of sequence g (pad slots are fed id 0, as in a scoring pass).  Every dense
+ *             product of every layer runs once on the M rows; the q|k|v product does not rope or append (its fused reduce is not used).
+ *   prompt    rows [0, Tn): the separate RoPE + append launch, then the prefill's causal attention.
+ *   branches  rows [Tn, M): the batched verify attention of a scoring pass -- sequence g on its own table from position L, RoPE, append
+ *             and causal mask per row.  Candidates longer than r + 1 ids go on with svln_generate_candidates' passes from pass 1.
+ *   mirror    the tables of the fork are built BEFORE the pass.  When L % 64 != 0 the forks' first private pages must hold the prompt's
+ *             rows of page q0 = L / 64 in every layer while the pass is still running: the RoPE + append launch stores each k / v row of
+ *             logical page q0 to the env's page and, same values and offsets, to every fork's first page (at most 7).  Rows of EARLIER
+ *             turns in page q0 (kv_len > 64 q0) are copied by one page-copy launch before the pass; the fork launch after the prefill
+ *             is gone.  When L % 64 == 0 nothing is mirrored or copied.
+ *   head      ONE indexed final norm for the prompt's last row (once per sequence) and the folded rows; then as svln_generate_candidates.
+ * Candidates of one id each feed nothing: the call is svln_generate_candidates, launch for launch (and bit for bit).
+ * Otherwise NO result is bit-equal to svln_generate_candidates' by contract: the row count of a product selects its plan (tile,
+ * split-K), so the prompt's rows and the candidates' rows may both differ in rounding from the unfolded call's -- the caveat stated for
+ * svln_set_prefill_draft.  Both calls lie inside the same bounds of the exact result.
+ * Results of one candidate still do not depend on the other candidates' ids.
+ * Refused besides, by name and before any launch or change: a row workspace (max_positions rows) that cannot hold Tn + n_seq r rows. */
+int svln_generate_candidates_folded(svln_engine* h, int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos_ids,
+                                    int n_eos, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs);
+/* svln_turn_candidates with the folded call */
+int svln_turn_candidates_folded(svln_engine* h, const svln_turn_args* a, int n_seq, const int64_t* ids, const int32_t* lens, float* logprobs,
+                                int64_t* greedy_ids, float* greedy_logprobs);
 /* Opt-in, no reference counterpart: forced turns as jobs of the multi-env scheduler.  svln_batch_submit_forced queues a forced turn on the
  * ids F[0 .. n) for an env whose turn has been appended, as svln_batch_submit queues a plain one.  The job is a prefill segment of
  * Tn + n - 1 rows: the iteration that prefills it gathers F[0 .. n - 1) on the device as the rows at positions n_embeds .. n_embeds + n - 2
@@ -998,6 +1023,14 @@ int svln_op_beam_select(svln_engine* h, int W, int limit, int B, int n_cp, int l
  * rows [T][hidden] (device); roped q rows -> q_out [T][q_stride], roped k / v appended to env 0's pages; *fused = 1 when the product's
  * split-K reduce did the RoPE + append, 0 when the separate RoPE + append kernel did */
 int svln_op_llm_qkv_rope(svln_engine* h, const void* x, int T, int P, void* q_out, int q_stride, int32_t* fused);
+/* TEST-ONLY: the separate RoPE + append launch on caller rows: rows [T][ld] (device, engine dtype; q | k | v of one row side by side,
+ * ld >= (q_heads + 2 kv_heads) * 128) at positions P .. P + T - 1 of env 0 on the layer-0 pools, through the pages svln_op_set_pages
+ * fixed for env 0.  q is roped in place; roped k and v go to the env's pages.  With n_mirror > 0 (the folded candidates call's form) every
+ * k / v row whose position lies in logical page q0 = (P + T) / 64 is stored a second time, same values and in-page offsets, to each of
+ * the physical pages mirror_pages[0 .. n_mirror) in every kv head; n_mirror == 0 is the plain launch.
+ * Refused before the env is reset or anything is launched: n_mirror outside 0 .. 7; a mirror page outside the pool, equal to the env's
+ * page q0 (or any page fixed for the env), or listed twice; positions beyond the env's pages or max_positions; no pages fixed. */
+int svln_op_rope_kv_mirror(svln_engine* h, void* rows, int ld, int T, int P, const int32_t* mirror_pages, int n_mirror);
 /* test control: the attention ops give env these pages (in this order: logical page i -> pages[i]); n = 0 restores the free list */
 int svln_op_set_pages(svln_engine* h, int env, const int32_t* pages, int n);
 /* test control: fill the layer-0 K / V pools with a finite value and (part_nan) the split-KV partial workspace with NaN */

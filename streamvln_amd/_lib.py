@@ -161,6 +161,8 @@ SIGNATURES = {
     "svln_turn_forced": (_I, [_P, C.POINTER(SvlnTurnArgs), _PI64, _I, _PF, _PI64, _PF, _PI32]),
     "svln_generate_candidates": (_I, [_P, _I, _I, _PI64, _PI32, _PI64, _I, _PF, _PI64, _PF]),
     "svln_turn_candidates": (_I, [_P, C.POINTER(SvlnTurnArgs), _I, _PI64, _PI32, _PF, _PI64, _PF]),
+    "svln_generate_candidates_folded": (_I, [_P, _I, _I, _PI64, _PI32, _PI64, _I, _PF, _PI64, _PF]),
+    "svln_turn_candidates_folded": (_I, [_P, C.POINTER(SvlnTurnArgs), _I, _PI64, _PI32, _PF, _PI64, _PF]),
     "svln_batch_submit_forced": (_I, [_P, _I, _PI64, _I, _PI64, _I, _PI32]),
     "svln_batch_forced": (_I, [_P, _I, _PF, _PI64, _PF, _I, _PI32]),
     "svln_batch_forced_stats": (_I, [_P, _PI64, _PI64, _PI64, _I]),
@@ -252,6 +254,7 @@ SIGNATURES = {
     "svln_op_verify_step": (_I, [_P, _I, _PI32, _PI32, _I, _I, _PI64, _I, _PI32, _PI32, _PI64, _PI32]),
     "svln_op_kv_read": (_I, [_P, _I, _I, _I, _PF, _PF]),
     "svln_op_llm_qkv_rope": (_I, [_P, _P, _I, _I, _P, _I, _PI32]),
+    "svln_op_rope_kv_mirror": (_I, [_P, _P, _I, _I, _I, _PI32, _I]),
     "svln_op_set_pages": (_I, [_P, _I, _PI32, _I]),
     "svln_op_fill_attn_state": (_I, [_P, _F, _I]),
     "svln_op_vit_qkv_attention": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _PI32]),

@@ -56,6 +56,8 @@ class StreamingAgent:
         self.model = model
         # sampled turns (model.set_sampling): passed through to generate / submit; the defaults are the reference's greedy call
         self.do_sample, self.temperature = bool(do_sample), temperature
+        # act_candidates: let the candidates' first rows ride the prefill pass (model.generate(fold_candidates=True)); set it on the agent
+        self.fold_candidates = False
         self.prompt_encoder = prompt_encoder
         self.num_frames, self.num_future_steps, self.num_history = num_frames, num_future_steps, num_history
         self.env_id, self.device, self.image_dtype = env_id, device, image_dtype
@@ -178,7 +180,9 @@ class StreamingAgent:
         env goes on with candidate `select` (default: the largest joint log-probability) as a forced turn on it would"""
         req = self._build_request(instruction, env_id)
         req["candidate_ids"] = candidate_ids
-        req.pop("do_sample", None)              # (no token is drawn; the sampling switch of the model stays as it is)
+        if getattr(self, "fold_candidates", False):
+            req["fold_candidates"] = True
+        req.pop("do_sample", None)             # (no token is drawn; the sampling switch of the model stays as it is)
         req.pop("temperature", None)
         out = self.model.generate(**req)
         joint = out.token_logprobs.sum(1)

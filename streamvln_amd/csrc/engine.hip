@@ -149,6 +149,11 @@ struct EngineBase {
                              int32_t* kv_len) = 0;
     virtual void generate_candidates(int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos, int n_eos, float* logprobs,
                                      int64_t* greedy_ids, float* greedy_logprobs) = 0;
+    virtual void generate_candidates_folded(int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos, int n_eos, float* logprobs,
+                                            int64_t* greedy_ids, float* greedy_logprobs) = 0;
+    virtual void turn_candidates_folded(const svln_turn_args& a, int n_seq, const int64_t* ids, const int32_t* lens, float* logprobs,
+                                        int64_t* greedy_ids, float* greedy_logprobs) = 0;
+    virtual void op_rope_kv_mirror(void* rows, int ld, int Tn, int P, const int32_t* mirror_pages, int n_mirror) = 0;
     virtual void turn_candidates(const svln_turn_args& a, int n_seq, const int64_t* ids, const int32_t* lens, float* logprobs, int64_t* greedy_ids,
                                  float* greedy_logprobs) = 0;
     virtual int batch_submit_forced(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos) = 0;
@@ -1301,7 +1306,16 @@ public:
         if (single) { r0 = rope_kv_args(L, *single); aq.rope = &r0; }
         return llm_gemm(aq, L.qkv8);
     }
-    void prefill_rope_append(const LLayer& L, const Seg& g) { launch_rope_kv<T>(st, rope_kv_args(L, g)); }
+    // The candidate rows folded into a prefill (svln_generate_candidates_folded): the last S * rows rows of the batch are S sequences x
+    // `rows` row slots that branch off the ONE segment's last position, fed the ids `feed` (slot g rows + j = F_g[j], pad slots id 0);
+    // slots[g] = {table g, first position, row count}, kv_max as a scoring pass's.  The segment's k / v rows of logical page mirror_page
+    // also go to the n_mirror physical pages mirror_dst lists (a device array): the forks' private copies of the prompt's last page.
+    struct Fold { const int* feed; const DecodeSlot* slots; int S, rows, kv_max, mirror_page; const int* mirror_dst; int n_mirror; };
+    void prefill_rope_append(const LLayer& L, const Seg& g, const Fold* fold = nullptr) {
+        RopeKvArgs r = rope_kv_args(L, g);
+        if (fold) { r.mirror_page = fold->mirror_page; r.mirror_dst = fold->mirror_dst; r.n_mirror = fold->n_mirror; }
+        launch_rope_kv<T>(st, r);
+    }
     // Qwen2DecoderLayer stack (modeling_qwen2.py:269-299) over the concatenated new rows of one or several envs:
     // the dense products run once on all rows; RoPE + KV append and attention run per env (own pages / positions).
     // n_dec > 0 (mixed iteration of the multi-env scheduler): rows [0, n_dec) are single-token decode rows of n_dec other envs
@@ -1311,14 +1325,20 @@ public:
     // here; RoPE, KV append and the causal attention treat them as the next positions of the same sequence.  n_ragged = 0
     // (svln_set_prefill_draft; one env alone in the batch): the ids are d_draft[0 .. n_draft).  n_ragged > 0 (svln_set_batch_draft): the
     // draft rows of all segments are the n_ragged (row, id) pairs of d_ride_list, written by one launch.
-    void prefill_rows(const std::vector<Seg>& segs, int M, int n_dec = 0, int n_ragged = 0) {
+    // fold != null (one segment at row 0, no decode rows): rows [M - S rows, M) are the Fold's candidate rows.  They share every dense
+    // product; the q|k|v product leaves RoPE and append to launch_rope_kv (mirror form) for the segment and to the batched verify
+    // attention for the candidate rows, which reads q|k|v and writes its output Tn rows into the buffers.
+    void prefill_rows(const std::vector<Seg>& segs, int M, int n_dec = 0, int n_ragged = 0, const Fold* fold = nullptr) {
         const int qd = nq * 128;
+        const int row0 = fold ? M - fold->S * fold->rows : M;        // the first candidate row
+        REQUIRE(!fold || (segs.size() == 1 && n_dec == 0 && n_ragged == 0 && segs[0].off == 0 && segs[0].Tn == row0), "prefill_rows: a fold rides one segment");
         for (const Seg& g : segs) {
             HIP_CHECK(hipMemcpyAsync(x + (size_t)g.off * H, g.e->embeds + (size_t)g.P * H, (size_t)(g.Tn - g.n_draft) * H * sizeof(T), hipMemcpyDeviceToDevice, st));
             if (g.n_draft > 0 && n_ragged == 0)
                 launch_gather_rows<T>(st, d_draft, embed, feats, x + (size_t)(g.off + g.Tn - g.n_draft) * H, g.n_draft, H);
         }
         launch_gather_rows_ragged<T>(st, d_ride_list, embed, x, n_ragged, H);
+        if (fold) launch_gather_rows<T>(st, fold->feed, embed, feats, x + (size_t)row0 * H, M - row0, H);
         bool xn_ready = false;        // xn already holds rmsnorm(x) * in_norm (written by the previous layer's down_proj epilogue)
         const bool taps = layer_taps_on && segs.size() == 1 && n_dec == 0;
         for (int i = 0; i < c.layers; ++i) {
@@ -1327,14 +1347,19 @@ public:
             if (probing) { probe_copy(0, x, M); probe_rows = M; }
             if (!xn_ready) launch_rmsnorm<T>(st, x, L.in_norm, xn, M, H, c.rms_eps);
             if (probing) probe_copy(6, xn, M);
-            const bool roped = prefill_qkv(L, M, segs.size() == 1 && n_dec == 0 ? &segs[0] : nullptr);
+            const bool roped = prefill_qkv(L, M, segs.size() == 1 && n_dec == 0 && !fold ? &segs[0] : nullptr);
             if (n_dec > 0) decode_attention(batched_decode_attn_args(L, n_dec));
             for (const Seg& g : segs) {
                 T* q_g = qkv + (size_t)g.off * qkv_dim;
-                if (!roped) prefill_rope_append(L, g);
+                if (!roped) prefill_rope_append(L, g, fold);
                 AttnArgs a = llm_attn_args(L, *g.e, q_g, qkv_dim, attn + (size_t)g.off * qd, qd, g.Tn, g.P, g.P + g.Tn, false);
                 launch_attention<T>(st, a, 128, 4);
                 if (a.nsplit > 1) launch_attention_combine<T>(st, a, 128);
+            }
+            if (fold) {
+                AttnArgs a = verify_multi_attn_args(L, fold->S, fold->rows, fold->kv_max, fold->slots);
+                a.Q = qkv + (size_t)row0 * qkv_dim; a.O = attn + (size_t)row0 * qd;
+                launch_attention_verify_multi<T>(st, a);
             }
             // the split-K reduce of o_proj / down_proj also emits the following RMSNorm when it can (T <= 256 rows)
             GemmArgs ao = gemm_args(attn, qd, L.o_w, qd, x, H, nullptr, x, H, 0, M, H, qd, EPI_NONE);
@@ -1351,7 +1376,7 @@ public:
             if (i + 1 < c.layers) { ad.norm_w = ll[i + 1].in_norm; ad.norm_out = xn; ad.norm_eps = c.rms_eps; }
             xn_ready = llm_gemm(ad, L.down8);
             if (taps) {
-                HIP_CHECK(hipMemcpyAsync(layer_tap + (size_t)i * H, x + (size_t)(M - 1) * H, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
+                HIP_CHECK(hipMemcpyAsync(layer_tap + (size_t)i * H, x + (size_t)(row0 - 1) * H, (size_t)H * sizeof(T), hipMemcpyDeviceToDevice, st));
                 if (probing) probe_copy(1, x, M);
             }
         }
@@ -3117,14 +3142,20 @@ public:
     }
     std::vector<int> fork_host[MAXB];            // host copies of fork_tab (kept: an upload reads them after the call that wrote them)
     void ensure_fork_tab(int g) { if (!fork_tab[g]) { fork_tab[g] = dalloc<int>(pages_per_env, true); fork_host[g].assign(pages_per_env, 0); } }
+    void upload_fork_dst(int n_dst) { HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)n_dst * sizeof(int), hipMemcpyHostToDevice, st)); }
     // h_fork_dst[0 .. n_dst) -> the device, then the ONE fork launch: page src_page of every layer's K and V^T pool to each listed page
     void fork_page_copy(int src_page, int n_dst) {
-        HIP_CHECK(hipMemcpyAsync(d_fork_dst, h_fork_dst, (size_t)n_dst * sizeof(int), hipMemcpyHostToDevice, st));
+        upload_fork_dst(n_dst);
         launch_kv_page_copy<T>(st, d_pool_tab, 2 * c.layers, src_page, d_fork_dst, n_dst, (int64_t)nkv * PAGE * 128);
     }
     // The fork of the pending group grp (its L set): per sequence g >= 1 with tail_n[g] > 0 a table = the env's pages below q0 + tail_n[g]
     // private pages from q0 on (grp.tail[g]), uploaded to fork_tab[g]; then the partly filled page q0, if the prompt ends inside one.
+    // fork_tables is the table half: it returns the number of forks, whose first private pages it leaves in h_fork_dst.
     void fork_tails(Env& e, int q0, const int* tail_n, int n_seq) {
+        const int n_dst = fork_tables(e, q0, tail_n, n_seq);
+        if (grp.L % PAGE != 0 && n_dst > 0) fork_page_copy(e.pages[q0], n_dst);      // one launch for every layer, both pools, all forks
+    }
+    int fork_tables(Env& e, int q0, const int* tail_n, int n_seq) {
         int n_dst = 0;
         for (int g = 1; g < n_seq; ++g) {
             if (tail_n[g] == 0) continue;
@@ -3139,7 +3170,7 @@ public:
             HIP_CHECK(hipMemcpyAsync(fork_tab[g], tab.data(), (size_t)(q0 + tail_n[g]) * sizeof(int), hipMemcpyHostToDevice, st));
             h_fork_dst[n_dst++] = grp.tail[g][0];
         }
-        if (grp.L % PAGE != 0 && n_dst > 0) fork_page_copy(e.pages[q0], n_dst);      // one launch for every layer, both pools, all forks
+        return n_dst;
     }
     void generate_group(int env, int n_seq, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out) override {
         group_refusals(env, n_seq);
@@ -3504,8 +3535,8 @@ public:
     // rows of a sequence per scoring pass
     int cand_rows_per_pass(int n_seq) const { return std::min(32 / (nq / nkv), 32 / n_seq); }
     // every refusal that needs no state of the env's rows (svln_turn_candidates checks them before it encodes a frame)
-    void cand_refusals(int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos, int n_eos) {
-        const char* who = "svln_generate_candidates";
+    void cand_refusals(int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos, int n_eos,
+                       const char* who = "svln_generate_candidates") {
         env_at(env);
         REQUIRE(n_seq >= 2 && n_seq <= MAXB, std::string(who) + ": n_seq must be 2 .. 8");
         REQUIRE(ids && lens, std::string(who) + ": null id list / lengths");
@@ -3518,25 +3549,42 @@ public:
     }
     void generate_candidates(int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos, int n_eos, float* logprobs,
                              int64_t* greedy_ids, float* greedy_logprobs) override {
+        candidates_call(env, n_seq, ids, lens, eos, n_eos, logprobs, greedy_ids, greedy_logprobs, false);
+    }
+    // svln_generate_candidates_folded: the same call with the rows of scoring pass 0 folded into the prefill pass (Fold, prefill_rows):
+    // the tables of the fork are built BEFORE the prefill, every layer's launch_rope_kv mirrors the prompt's rows of page q0 into the
+    // forks' first private pages (rows of earlier turns in that page: ONE fork_page_copy before the prefill), and the fork launch after
+    // the prefill is gone.  Passes 1 .. are unchanged.  Candidates of one id each feed nothing: the unfolded call, launch for launch.
+    void generate_candidates_folded(int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos, int n_eos, float* logprobs,
+                                    int64_t* greedy_ids, float* greedy_logprobs) override {
+        candidates_call(env, n_seq, ids, lens, eos, n_eos, logprobs, greedy_ids, greedy_logprobs, true);
+    }
+    void candidates_call(int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos, int n_eos, float* logprobs,
+                         int64_t* greedy_ids, float* greedy_logprobs, bool folded) {
+        const char* who = folded ? "svln_generate_candidates_folded" : "svln_generate_candidates";
         Env& e = env_at(env);
         disarm_draft(env);              // consumed by this call, as svln_generate_forced consumes it
-        REQUIRE(logprobs && greedy_ids && greedy_logprobs, "svln_generate_candidates: null output pointer");
-        cand_refusals(env, n_seq, ids, lens, eos, n_eos);
+        REQUIRE(logprobs && greedy_ids && greedy_logprobs, std::string(who) + ": null output pointer");
+        cand_refusals(env, n_seq, ids, lens, eos, n_eos, who);
         int n_max = 0, nf = 0, off[MAXB + 1] = {0};
         for (int g = 0; g < n_seq; ++g) { n_max = std::max(n_max, (int)lens[g]); off[g + 1] = off[g] + lens[g]; }
         nf = off[n_seq];
-        const TurnPlan pl = plan_turn(e, "svln_generate_candidates", n_max, n_max, "max(lens)");
+        const TurnPlan pl = plan_turn(e, who, n_max, n_max, "max(lens)");
         const int P = pl.P, L = pl.L, Tn = pl.Tn, q0 = pl.q0;
         // (the plan's page counts are those of the longest sequence: here the env feeds lens[0] ids and every fork its own)
         int tail_n[MAXB] = {0};
         int64_t need = std::max((L + lens[0] - 1 + PAGE - 1) / PAGE - e.n_pages, 0);
         for (int g = 1; g < n_seq; ++g) { tail_n[g] = fork_tail_pages(L, lens[g]); need += tail_n[g]; }
         REQUIRE((int64_t)free_pages.size() >= need,
-                "svln_generate_candidates: the free KV pages cannot hold the env's own pages and the tail pages of the fork");
+                std::string(who) + ": the free KV pages cannot hold the env's own pages and the tail pages of the fork");
         const int r = cand_rows_per_pass(n_seq);
         const int passes = (n_max - 1 + r - 1) / r;
         const int Bu = n_seq * r, B = Bu >= batched_mfma_min ? Bu : (Bu <= 2 ? 2 : 4);
-        REQUIRE(passes <= CAND_PASSES && passes * B <= CAND_FEED && nf <= BFORCED_ROWS && B <= c.max_positions, "svln_generate_candidates: workspace");
+        REQUIRE(passes <= CAND_PASSES && passes * B <= CAND_FEED && nf <= BFORCED_ROWS && B <= c.max_positions, std::string(who) + ": workspace");
+        const bool fold = folded && n_max >= 2;        // (nothing is fed otherwise)
+        const int row0 = fold ? Tn : 0;                // the row of x that slot 0 of pass 0 is
+        REQUIRE(!fold || (int64_t)Tn + Bu <= c.max_positions,
+                std::string(who) + ": the row workspace (max_positions rows) cannot hold the prompt's new rows and n_seq x r candidate rows");
         ensure_bforced_buffers();
         ensure_cand_buffers();
         // ---- nothing was launched or changed up to here (but the armed draft)
@@ -3562,7 +3610,7 @@ public:
                 for (int j = 0; j < cnt; ++j) {
                     const int i = lo + j + 1;       // the position of the turn this row scores
                     h_cfeed[p * B + g * r + j] = (int)ids[off[g] + lo + j];
-                    h.src[k] = g * r + j;
+                    h.src[k] = (p == 0 ? row0 : 0) + g * r + j;
                     // tap row min(i, 7); of the rows of one launch that share tap row 7 only the last is written (later passes overwrite it)
                     h.tap[k] = taps_on && (i < 7 || j == cnt - 1) ? (i < 7 ? i : 7) * MAXB + g : -1;
                     h.tgt[k] = (int)ids[off[g] + i];
@@ -3572,25 +3620,42 @@ public:
             }
             base[p + 2] = k;
         }
-        REQUIRE(k == nf, "svln_generate_candidates: head row count");
+        REQUIRE(k == nf, std::string(who) + ": head row count");
         try {
             upload_head_lists(nf);
             if (passes > 0) {
                 HIP_CHECK(hipMemcpyAsync(d_cfeed, h_cfeed, (size_t)passes * B * sizeof(int), hipMemcpyHostToDevice, st));
                 HIP_CHECK(hipMemcpyAsync(d_cslots, h_cslots, (size_t)passes * MAXB * sizeof(DecodeSlot), hipMemcpyHostToDevice, st));
             }
-            // prefill: svln_generate's, launch for launch
-            ensure_pages(e, L);
-            HIP_CHECK(hipEventRecord(ph_ev[2], st));
-            prefill(e, P, Tn);
-            e.kv_len = L;
-            launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn, d.src, d.tap, hid_tap, n_seq, H, c.rms_eps);
-            HIP_CHECK(hipEventRecord(ph_ev[3], st));
-            // fork: the env's own tail pages, then per sequence g >= 1 a table = the env's pages below q0 + private pages from q0 on
-            ensure_pages(e, L + lens[0] - 1);
-            fork_tails(e, q0, tail_n, n_seq);
+            if (fold) {
+                // the tables of the fork first; the prompt's rows of page q0 reach the forks' first pages layer by layer (the mirror list),
+                // rows of earlier turns in that page by one copy now -- what it copies at positions >= P the stream overwrites
+                HIP_CHECK(hipEventRecord(ph_ev[2], st));
+                ensure_pages(e, L + lens[0] - 1);
+                const int n_dst = fork_tables(e, q0, tail_n, n_seq);
+                const int n_mirror = L % PAGE != 0 ? n_dst : 0;
+                if (n_mirror > 0) { if (P > q0 * PAGE) fork_page_copy(e.pages[q0], n_dst); else upload_fork_dst(n_dst); }
+                const Fold f{d_cfeed, d_cslots, n_seq, r, L + std::min(r, n_max - 1), q0, d_fork_dst, n_mirror};
+                std::vector<Seg> segs{Seg{&e, P, Tn, 0}};
+                prefill_rows(segs, Tn + Bu, 0, 0, &f);
+                e.kv_len = L;
+                // block 0 and the folded rows in one launch
+                launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn, d.src, d.tap, hid_tap, base[2], H, c.rms_eps);
+                HIP_CHECK(hipEventRecord(ph_ev[3], st));
+            } else {
+                // prefill: svln_generate's, launch for launch
+                ensure_pages(e, L);
+                HIP_CHECK(hipEventRecord(ph_ev[2], st));
+                prefill(e, P, Tn);
+                e.kv_len = L;
+                launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn, d.src, d.tap, hid_tap, n_seq, H, c.rms_eps);
+                HIP_CHECK(hipEventRecord(ph_ev[3], st));
+                // fork: the env's own tail pages, then per sequence g >= 1 a table = the env's pages below q0 + private pages from q0 on
+                ensure_pages(e, L + lens[0] - 1);
+                fork_tails(e, q0, tail_n, n_seq);
+            }
             // scoring passes: one sweep of the batched step's products each, then the final norm of the rows it fed
-            for (int p = 0; p < passes; ++p) {
+            for (int p = fold ? 1 : 0; p < passes; ++p) {
                 const MultiPass mp{d_cfeed + p * B, d_cslots + (size_t)p * MAXB, n_seq, r, std::min(L + (p + 1) * r, L + n_max - 1)};
                 decode_ops_batched(B, false, nullptr, &mp);
                 const int cnt = base[p + 2] - base[p + 1];
@@ -3599,7 +3664,7 @@ public:
             head_target_chunks(nf);
             HIP_CHECK(hipEventRecord(ph_ev[4], st));
             HIP_CHECK(hipStreamSynchronize(st));
-            LAUNCH_CHECK("generate_candidates");
+            LAUNCH_CHECK(folded ? "generate_candidates_folded" : "generate_candidates");
             require_finite_tokens(h.tok, nf);
             for (int g = 0; g < n_seq; ++g) {
                 for (int i = 0; i < lens[g]; ++i) {
@@ -3634,6 +3699,15 @@ public:
             cand_refusals(a.env, n_seq, ids, lens, a.eos_ids, a.n_eos);
         });
         generate_candidates(a.env, n_seq, ids, lens, a.eos_ids, a.n_eos, logprobs, greedy_ids, greedy_logprobs);
+    }
+    void turn_candidates_folded(const svln_turn_args& a, int n_seq, const int64_t* ids, const int32_t* lens, float* logprobs, int64_t* greedy_ids,
+                                float* greedy_logprobs) override {
+        env_at(a.env);
+        begin_turn(a, [&] {
+            REQUIRE(a.ids && a.n_ids >= 1 && logprobs && greedy_ids && greedy_logprobs, "svln_turn_candidates_folded: null / empty argument");
+            cand_refusals(a.env, n_seq, ids, lens, a.eos_ids, a.n_eos, "svln_turn_candidates_folded");
+        });
+        generate_candidates_folded(a.env, n_seq, ids, lens, a.eos_ids, a.n_eos, logprobs, greedy_ids, greedy_logprobs);
     }
     // ------------------------------------------------------------------------------- forced turns (svln_generate_forced)
     // A turn on the CALLER's ids F[0 .. n): ids F[0 .. n - 1) ride the prefill pass as n - 1 more rows (the ride's gather, RoPE, KV append
@@ -4824,6 +4898,39 @@ public:
         LAUNCH_CHECK("op_llm_qkv_rope");
         *fused = roped ? 1 : 0;
     }
+    // TEST-ONLY: launch_rope_kv on caller rows [Tn][ld] (q|k|v, q roped in place) at positions P .. of env 0 on the layer-0 pools, through
+    // the pages svln_op_set_pages fixed for it, with the mirror list of the folded candidates call: mirror_page = (P + Tn) / 64, the
+    // page a fork's branch would open.  n_mirror == 0 is the plain launch.  Every refusal comes before the env is reset or a launch is made.
+    void op_rope_kv_mirror(void* rows, int ld, int Tn, int P, const int32_t* mirror_pages, int n_mirror) override {
+        const char* who = "svln_op_rope_kv_mirror";
+        REQUIRE(rows && ld >= qkv_dim, std::string(who) + ": null rows / a row pitch below (q_heads + 2 kv_heads) * 128");
+        REQUIRE(n_mirror >= 0 && n_mirror <= ROPE_MIRROR_MAX && (n_mirror == 0 || mirror_pages), std::string(who) + ": n_mirror must be 0 .. 7");
+        REQUIRE(Tn >= 1 && P >= 0 && (int64_t)P + Tn <= c.max_positions, std::string(who) + ": positions out of range");
+        const int L = P + Tn, need = (L + PAGE - 1) / PAGE, q0 = L / PAGE;
+        REQUIRE(!op_pages.empty() && !op_pages[0].empty(), std::string(who) + ": fix the pages of env 0 with svln_op_set_pages first");
+        const std::vector<int>& want = op_pages[0];
+        REQUIRE(need <= (int)want.size() && need <= pages_per_env, std::string(who) + ": positions beyond the env's pages");
+        for (int d = 0; d < n_mirror; ++d) {
+            const int p = mirror_pages[d];
+            REQUIRE(p >= 0 && p < pages_total, std::string(who) + ": a mirror page outside the pool");
+            for (int i = 0; i < (int)want.size(); ++i)
+                REQUIRE(want[i] != p, std::string(who) + (i == q0 ? ": a mirror page equals the env's page q0" : ": a mirror page is a page of the env"));
+            for (int q = 0; q < d; ++q) REQUIRE(mirror_pages[q] != p, std::string(who) + ": a mirror page is listed twice");
+        }
+        Env& e = env_at(0);
+        sync();
+        op_env_begin(0, L);
+        RopeKvArgs r = rope_kv_args(ll[0], Seg{&e, P, Tn, 0});
+        r.qkv = rows; r.ld = ld;
+        if (n_mirror > 0) {
+            for (int d = 0; d < n_mirror; ++d) h_fork_dst[d] = mirror_pages[d];
+            upload_fork_dst(n_mirror);
+            r.mirror_page = q0; r.mirror_dst = d_fork_dst; r.n_mirror = n_mirror;
+        }
+        launch_rope_kv<T>(st, r);
+        sync();
+        LAUNCH_CHECK("op_rope_kv_mirror");
+    }
     void op_rope_append(Env& e, const LLayer& L, void* rows, int ld, int Tn, int P) {
         RopeKvArgs r; r.Kpool = L.kpool; r.Vpool = L.vpool; r.page_table = e.d_pages; r.rope_tab = rope_tab; r.nq = nq; r.nkv = nkv; r.dyn_pos = nullptr;
         r.ld = ld; r.qkv = rows; r.T = Tn; r.P = P;
@@ -5382,6 +5489,17 @@ int svln_generate_candidates(svln_engine* h, int env, int n_seq, const int64_t* 
 int svln_turn_candidates(svln_engine* h, const svln_turn_args* a, int n_seq, const int64_t* ids, const int32_t* lens, float* logprobs,
                          int64_t* greedy_ids, float* greedy_logprobs) {
     API_BEGIN_H REQUIRE(a, "null turn args"); h->impl->turn_candidates(*a, n_seq, ids, lens, logprobs, greedy_ids, greedy_logprobs); API_END
+}
+int svln_generate_candidates_folded(svln_engine* h, int env, int n_seq, const int64_t* ids, const int32_t* lens, const int64_t* eos_ids,
+                                    int n_eos, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs) {
+    API_BEGIN_H h->impl->generate_candidates_folded(env, n_seq, ids, lens, eos_ids, n_eos, logprobs, greedy_ids, greedy_logprobs); API_END
+}
+int svln_turn_candidates_folded(svln_engine* h, const svln_turn_args* a, int n_seq, const int64_t* ids, const int32_t* lens, float* logprobs,
+                                int64_t* greedy_ids, float* greedy_logprobs) {
+    API_BEGIN_H REQUIRE(a, "null turn args"); h->impl->turn_candidates_folded(*a, n_seq, ids, lens, logprobs, greedy_ids, greedy_logprobs); API_END
+}
+int svln_op_rope_kv_mirror(svln_engine* h, void* rows, int ld, int T, int P, const int32_t* mirror_pages, int n_mirror) {
+    API_BEGIN_H h->impl->op_rope_kv_mirror(rows, ld, T, P, mirror_pages, n_mirror); API_END
 }
 int svln_turn_forced(svln_engine* h, const svln_turn_args* a, const int64_t* ids, int n, float* logprobs, int64_t* greedy_ids, float* greedy_logprobs,
                      int32_t* kv_len) {

@@ -426,7 +426,14 @@ struct RopeKvArgs {
     const float* rope_tab;        // [max_positions][128]: cos[64] | sin[64]  (launch_rope_table)
     int T, nq, nkv, P;
     const int* dyn_pos;
+    // mirror form (n_mirror > 0; the folded candidates call): a k / v row whose position lies in LOGICAL page mirror_page is also stored,
+    // same values and in-page offsets, to the n_mirror <= ROPE_MIRROR_MAX PHYSICAL pages mirror_dst lists (a device array), in every kv
+    // head.  n_mirror == 0 launches the plain instantiation, which reads none of the three.
+    int mirror_page = 0;
+    const int* mirror_dst = nullptr;
+    int n_mirror = 0;
 };
+constexpr int ROPE_MIRROR_MAX = 7;
 template <typename T> void launch_rope_kv(hipStream_t s, const RopeKvArgs& a);
 void launch_rope_table(hipStream_t s, float* tab, const float* inv_freq, int positions);
 // out[2f], out[2f+1] += 128-bit content key of frame f (caller zeroes `out` first)

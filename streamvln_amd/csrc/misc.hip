@@ -102,7 +102,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* x, const T* g, 
 // grid (T, nq + nkv + nkv), 64 threads: lane d pairs (d, d + 64) of a 128-wide head.
 // q heads: rotate in place.  k heads: rotate, write K page row.  v heads: write transposed Vt page.
 // A wave per (row, head), four heads per workgroup (70 000 single-wave workgroups at T = 1952 are dispatch-bound).
-template <typename T>
+// MIRROR (the folded candidates call): a k / v wave whose position lies in logical page p.mirror_page repeats its stores at the same
+// in-page offsets of the p.n_mirror physical pages p.mirror_dst lists -- the values are computed once and stored 1 + n_mirror times.
+// q heads and rows of other pages do what the plain form does; the plain form (MIRROR = false) carries none of this.
+template <typename T, bool MIRROR = false>
 __global__ __launch_bounds__(256) void rope_kv_kernel(RopeKvArgs p) {
     const int i = blockIdx.x, hd = blockIdx.y * 4 + (threadIdx.x >> 6), d = threadIdx.x & 63;
     if (hd >= p.nq + 2 * p.nkv) return;
@@ -120,14 +123,32 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(RopeKvArgs p) {
         } else {
             const int kh = hd - p.nq;
             T* kr = (T*)p.Kpool + (((size_t)page * p.nkv + kh) * 64 + off) * 128;
-            kr[d] = from_f32<T>(o1);
-            kr[d + 64] = from_f32<T>(o2);
+            const T k1 = from_f32<T>(o1), k2 = from_f32<T>(o2);
+            kr[d] = k1;
+            kr[d + 64] = k2;
+            if constexpr (MIRROR) {
+                if ((pos >> 6) == p.mirror_page)
+                    for (int m = 0; m < p.n_mirror; ++m) {
+                        T* mr = (T*)p.Kpool + (((size_t)p.mirror_dst[m] * p.nkv + kh) * 64 + off) * 128;
+                        mr[d] = k1;
+                        mr[d + 64] = k2;
+                    }
+            }
         }
     } else {
         const int kh = hd - p.nq - p.nkv;
         T* vt = (T*)p.Vpool + ((size_t)page * p.nkv + kh) * 128 * 64;
-        vt[(size_t)d * 64 + off] = from_f32<T>(x1);
-        vt[(size_t)(d + 64) * 64 + off] = from_f32<T>(x2);
+        const T v1 = from_f32<T>(x1), v2 = from_f32<T>(x2);
+        vt[(size_t)d * 64 + off] = v1;
+        vt[(size_t)(d + 64) * 64 + off] = v2;
+        if constexpr (MIRROR) {
+            if ((pos >> 6) == p.mirror_page)
+                for (int m = 0; m < p.n_mirror; ++m) {
+                    T* mt = (T*)p.Vpool + ((size_t)p.mirror_dst[m] * p.nkv + kh) * 128 * 64;
+                    mt[(size_t)d * 64 + off] = v1;
+                    mt[(size_t)(d + 64) * 64 + off] = v2;
+                }
+        }
     }
 }
 
@@ -463,7 +484,11 @@ template <typename T> void launch_layernorm(hipStream_t s, const void* x, const 
     hipLaunchKernelGGL((layernorm_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, (const T*)x, (const T*)g, (const T*)b, (T*)y, rows, n, eps);
 }
 template <typename T> void launch_rope_kv(hipStream_t s, const RopeKvArgs& a) {
-    hipLaunchKernelGGL((rope_kv_kernel<T>), dim3(a.T, (a.nq + 2 * a.nkv + 3) / 4), dim3(256), 0, s, a);
+    if (a.n_mirror < 0 || a.n_mirror > ROPE_MIRROR_MAX || (a.n_mirror > 0 && !a.mirror_dst))
+        throw std::runtime_error("rope_kv: 0 .. 7 mirror pages with a device list");
+    const dim3 grid(a.T, (a.nq + 2 * a.nkv + 3) / 4);
+    if (a.n_mirror > 0) hipLaunchKernelGGL((rope_kv_kernel<T, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((rope_kv_kernel<T>), grid, dim3(256), 0, s, a);
 }
 void launch_frame_hash(hipStream_t s, const float* pix, int F, size_t words_per_frame, unsigned long long* out) {
     hipLaunchKernelGGL(frame_hash_kernel, dim3(64, F), dim3(256), 0, s, (const uint32_t*)pix, words_per_frame, out);

@@ -584,7 +584,7 @@ class StreamVLNForCausalLM:
 
     @torch.no_grad()
     def generate(self, inputs=None, images=None, image_sizes=None, depths=None, poses=None, intrinsics=None, task_ids=None,
-                 draft_ids=None, forced_ids=None, candidate_ids=None, beam_width=None, **kwargs):
+                 draft_ids=None, forced_ids=None, candidate_ids=None, beam_width=None, fold_candidates=False, **kwargs):
         """One model turn = ONE crossing into the engine (svln_turn: encode_rgbd, the KV / embeds bookkeeping of the reference's generate,
         splice, prefill + greedy decode).  draft_ids (optional, set_speculative / set_prefill_draft): a guess of this turn's whole id sequence; with
         set_auto_draft(True) and no explicit draft, the env's previous turn output is the guess.
@@ -595,9 +595,13 @@ class StreamVLNForCausalLM:
         forced_ids (1 .. 32 ids): a forced turn -- the turn's ids are the caller's (see _generate_forced); `max_new_tokens` is not read.
         candidate_ids (2 .. 8 id lists of 1 .. 32 ids): the candidates are scored against ONE prefill of the prompt (see
         _generate_candidates for the result, select_sequence for what must follow); `max_new_tokens` is not read.
+        fold_candidates=True (with candidate_ids only): the candidates' first rows ride the prefill pass (svln_turn_candidates_folded) --
+        same result layout and follow-up, one weight pass less; no result is bit-equal to the unfolded call's.
         beam_width (1 .. 8): a beam turn -- the beam_width most probable turns of the prompt (see _generate_beams for the result,
         select_sequence for what must follow); HF's `num_beams` stays refused."""
         draft = draft_ids
+        if fold_candidates and candidate_ids is None:
+            raise ValueError("fold_candidates without candidate_ids: only a candidates call has rows to fold into the prefill")
         W = self._beam_request(beam_width, forced_ids, candidate_ids, kwargs)
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
         n_seq = self._num_return_sequences(kwargs)
@@ -615,7 +619,7 @@ class StreamVLNForCausalLM:
                 if W:
                     return self._generate_beams(W, inputs, ids, pix, V, n_memory, env_id, past, max_new, eos)
                 if candidate_ids is not None:
-                    return self._generate_candidates(candidate_ids, inputs, ids, pix, V, n_memory, env_id, past, eos)
+                    return self._generate_candidates(candidate_ids, inputs, ids, pix, V, n_memory, env_id, past, eos, fold=bool(fold_candidates))
                 if forced_ids is not None:
                     return self._generate_forced(forced_ids, inputs, ids, pix, V, n_memory, env_id, past, eos)
                 return self._generate_group(n_seq, inputs, ids, pix, V, n_memory, env_id, past, max_new, eos)
@@ -728,14 +732,15 @@ class StreamVLNForCausalLM:
                 raise ValueError(f"candidate_ids[{g}] holds {int(r.size)} ids: a candidate has 1 .. 32")
         return np.ascontiguousarray(np.concatenate(rows)), np.asarray([r.size for r in rows], dtype=np.int32)
 
-    def _generate_candidates(self, cands, inputs, ids, pix, V, n_memory, env_id, past, eos):
+    def _generate_candidates(self, cands, inputs, ids, pix, V, n_memory, env_id, past, eos, *, fold=False):
         """generate(..., candidate_ids=[F_0, ..., F_{G-1}]): ONE vision pass, ONE prefill of the prompt and ceil(max_g (n_g - 1) / r) scoring
         passes for all candidates together; no decode phase.  The result is shaped like a group turn's: `sequences` int64 [G, n_max]
         (padded like a group's), `sequence_lengths` [G], `token_logprobs` fp32 [G, n_max] (log p(F_g[i] | prompt, F_g[:i]), pad 0: a row
         sum is the candidate's joint log-probability; always present), `greedy_ids` int64 / `greedy_logprobs` fp32 [G, n_max] (the
         policy's own arg-max at every position; pads: the pad id / 0), with an allowed list `allowed_logprobs` [G, n_max, n_allowed] /
         `allowed_token_ids`, and `past_key_values` None: select_sequence(index, env_id) must follow, and leaves the env where
-        generate(forced_ids=F_index) would have."""
+        generate(forced_ids=F_index) would have.  fold=True (generate's fold_candidates): the first min(r, n_g - 1) fed rows of every
+        candidate ride the prefill pass (svln_turn_candidates_folded); the result has the same layout."""
         if past is not None and (not isinstance(past, KVHandle) or past.env_id != env_id or past.epoch != self._epoch[env_id]):
             raise ValueError("past_key_values does not belong to this env's current window")
         flat, lens = self._candidate_arrays(cands)
@@ -753,8 +758,9 @@ class StreamVLNForCausalLM:
         if on_dev:
             self._order_engine_after(pix)
         PF, PI = C.POINTER(C.c_float), C.POINTER(C.c_int64)
-        rc = self._lib.svln_turn_candidates(self._h, C.byref(a), G, flat.ctypes.data_as(PI), lens.ctypes.data_as(C.POINTER(C.c_int32)),
-                                            lp.ctypes.data_as(PF), gid.ctypes.data_as(PI), glp.ctypes.data_as(PF))
+        turn = self._lib.svln_turn_candidates_folded if fold else self._lib.svln_turn_candidates
+        rc = turn(self._h, C.byref(a), G, flat.ctypes.data_as(PI), lens.ctypes.data_as(C.POINTER(C.c_int32)),
+                  lp.ctypes.data_as(PF), gid.ctypes.data_as(PI), glp.ctypes.data_as(PF))
         if on_dev:
             self._order_torch_after(pix)
         _check(rc)
@@ -888,6 +894,8 @@ class StreamVLNForCausalLM:
             raise NotImplementedError(f"forced_ids in a {who} request: forced turns run through generate() only")
         if kwargs.get("candidate_ids") is not None:
             raise NotImplementedError(f"candidate_ids in a {who} request: candidates are scored through generate() only")
+        if kwargs.get("fold_candidates"):
+            raise NotImplementedError(f"fold_candidates in a {who} request: candidates are scored through generate() only")
         g = kwargs.get("num_return_sequences")
         if g is not None and int(g) > 1:
             raise NotImplementedError(f"num_return_sequences={g!r} in a {who} request: group turns run through generate() only")
@@ -1150,6 +1158,8 @@ class StreamVLNForCausalLM:
             raise NotImplementedError(f"num_return_sequences={g!r} in a submit_forced request: a forced turn has one sequence")
         if kwargs.get("candidate_ids") is not None:
             raise NotImplementedError("candidate_ids in a submit_forced request: candidates are scored through generate() only")
+        if kwargs.get("fold_candidates"):
+            raise NotImplementedError("fold_candidates in a submit_forced request: candidates are scored through generate() only")
         if kwargs.get("beam_width") is not None:
             raise NotImplementedError("beam_width in a submit_forced request: beam turns run through generate() only")
         f_np = self._forced_array(forced_ids)
@@ -1231,6 +1241,8 @@ class StreamVLNForCausalLM:
             f = r.pop("forced_ids", None)
             if r.get("candidate_ids") is not None:
                 raise NotImplementedError("candidate_ids in a generate_batch_forced request: candidates are scored through generate() only")
+            if r.get("fold_candidates"):
+                raise NotImplementedError("fold_candidates in a generate_batch_forced request: candidates are scored through generate() only")
             g = r.get("num_return_sequences")
             if g is not None and int(g) > 1:
                 raise NotImplementedError(f"num_return_sequences={g!r} in a generate_batch_forced request: group turns run through generate() only")

@@ -11,15 +11,17 @@ with candidate 0, so every pass leaves it where the plain run does.
   plain8         the feature unused: generate_batch on 8 envs (both builds);
   replicated     G envs fed the same frames and the same prompt, env g forced onto candidate g by ONE generate_batch_forced call: the
                  yardstick, the vision tower and the prefill G times (both builds; the parent's figure is the one to beat);
-  candidates     ONE candidates call on ONE env (this build).
+  candidates     ONE candidates call on ONE env (both builds, where the build exports it: the parent's figure is the one `folded` is
+                 held against);
+  folded         the same call with fold_candidates (svln_turn_candidates_folded; this build): the candidates' rows ride the prefill.
 Per pass and G: scored sequences/s, ms per model turn, phase_ms_per_turn (svln_phase_times; a candidates call books its prefill under
 `prefill` and its scoring passes + head under `decode`).
 
 --ref-lib: the library of ANOTHER build of the engine (tools/build_ref_lib.sh <commit>), so that the code under test is not its own
 yardstick: its passes run in a child process of their own, alternating with this build's `--rounds` times.  The parent process never
 opens the GPU; every child runs under its own time limit, and nothing is started after a child that failed.
-Prints ONE JSON line (committed as profiles/candidates.json).  Per-launch kernel times come from a run of one pass under the profiler:
-    rocprofv3 --kernel-trace --stats --output-format csv -d out -- python tools/candidates_bench.py --child --passes candidates --groups 8
+Prints ONE JSON line (committed as profiles/candidates.json; the run with the folded pass as profiles/candidates_fold.json).  Per-launch kernel times come from a run of one pass under the profiler:
+    rocprofv3 --kernel-trace --stats --output-format csv -d out -- python tools/candidates_bench.py --child --passes folded --groups 8
 """
 import argparse
 import ctypes as C
@@ -31,8 +33,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 TAG = "CANDIDATES_BENCH_CHILD "
-BOTH = ("single", "plain8", "replicated")
-NEW = ("candidates",)
+BOTH = ("single", "plain8", "replicated", "candidates")
+NEW = ("folded",)
 
 
 def child(a):
@@ -143,9 +145,12 @@ def child(a):
             r = measure(lambda: got.append(turn_r()), G)
             r["ids_are_the_candidates_per_timed_turn"] = [g == cands(a.warmup + k, G) for k, g in enumerate(got[a.warmup:])]
             res[str(G)]["replicated"] = r
-        if "candidates" in passes and not ref:
+        for mode, fold in (("candidates", False), ("folded", True)):
+            if mode not in passes or (fold and ref) or not hasattr(lib, "svln_turn_candidates"):
+                continue
             model.reset(1)
             ags = make_agents(1, True)
+            ags[0].fold_candidates = fold
 
             def step_cand(frames, t, ag=ags[0], G=G):
                 if len(ag.action_seq) == 0:
@@ -157,7 +162,7 @@ def child(a):
             got = [turn_c() for _ in range(a.warmup)]
             r = measure(lambda: got.append(turn_c()), G)
             r["ids_equal_plain_run_per_timed_turn"] = [g[0] == plain[a.warmup + k] for k, g in enumerate(got[a.warmup:])]
-            res[str(G)]["candidates"] = r
+            res[str(G)][mode] = r
     model.close()
     print(TAG + json.dumps(res), flush=True)
 
@@ -210,7 +215,7 @@ def main():
             if col:
                 summary[f"{key} ({build})"] = best(col)
         for G in a.groups.split(","):
-            for mode in ("replicated", "candidates"):
+            for mode in ("replicated", "candidates", "folded"):
                 col = [r[build][G][mode] for r in out["rounds"] if mode in r.get(build, {}).get(G, {})]
                 if col:
                     summary[f"G={G} {mode} ({build})"] = best(col)
