@@ -490,7 +490,8 @@ int svln_batch_forced_stats(svln_engine* h, int64_t* jobs, int64_t* rows_fed, in
  * next prefills (svln_get_layer_taps: host_out [layers][hidden]); probe_layer >= 0 additionally records, for every row of the prefill,
  * the operands the products of that one layer actually saw (svln_get_layer_probe, which: 0 = x entering the layer, 1 = x leaving it,
  * 2 = attention output [q_heads * 128], 3 = x after the attention residual, 4 = post_attention_layernorm(x), 5 = silu(gate) * up
- * [inter], 6 = input_layernorm(x), 7 = the q | k | v rows after bias and RoPE [(q_heads + 2 kv_heads) * 128]; the others [hidden]),
+ * [inter], 6 = input_layernorm(x), 7 = the q | k | v buffer after bias and RoPE [(q_heads + 2 kv_heads) * 128]: the q columns are rotated; the rotated k goes to the
+ * KV pages only, so the k and v columns hold the plain product (and nothing where the product's reduce did the append); the others [hidden]),
  * so that each fused stage can be checked against the oracle on the engine's own inputs, at its own scale.  enable = 0 switches
  * both off. */
 int svln_set_layer_taps(svln_engine* h, int enable, int probe_layer);

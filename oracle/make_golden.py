@@ -15,13 +15,18 @@ Scenarios
                  step 32 (9 views, 1568-row <memory> block, T=1952); decode capped at 3 tokens.
   true4_episode  true dimensions, 4 ViT + 4 LLM layers, FULL vocabulary 152 064: first turn + one
                  steady turn, 4 tokens each (inter-layer fused norms, full-size lm_head / arg-max).
+  true2_restart  true dimensions, 2 ViT + 2 LLM layers, vocab 8192, a window of 8 frames, 16 env steps = 4 turns: first turn (T=376), a
+                 steady turn (T=214), the window restart at step 8 (9 views, 1568-row <memory> block, T=1952) and the steady turn
+                 behind it (T=214 on 1954 cached positions).  The last two are tapped row by row (scenario key `row_taps`): every
+                 decoder layer's output on all T rows of the prefill call, kept as 8 full-width rows + 16 sign projections of every
+                 row + the oracle-vs-reference noise of those projections, and layer 1's post-RoPE K rows (tests/restart_ref.py).
   tiny_truncate  TINY, config.tokenizer_model_max_length = 150: the reference truncates every turn's spliced rows
                  (stream_video_vln.py:241-244).
   tiny_penalty   TINY, generation_config.repetition_penalty = 1.3 through transformers' own
                  RepetitionPenaltyLogitsProcessor in the restated 4.45.1 greedy loop.
 Usage: python -m oracle.make_golden [scenario ... | preprocess]   (default: everything)
 Each scenario is driven through the same `StreamingAgent` twice (reference, oracle); the
-script asserts ids equal and hidden/features within 2e-4 abs+rel before writing.
+script asserts ids equal and hidden/features (and the row taps) within 2e-4 abs+rel before writing.
 """
 from __future__ import annotations
 
@@ -43,10 +48,12 @@ from oracle import streamvln_oracle as O                      # noqa: E402
 GOLD = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from scenarios import SCENARIOS, SEED, apply_knobs, run_scenario            # noqa: E402
+import restart_ref as RR                                                     # noqa: E402
 
 
 class _RefOut:
-    def __init__(self, ids, cache, hidden, embeds):
+    def __init__(self, ids, cache, hidden, embeds, row_taps=None, k1=None, inputs=None):
+        self.row_taps, self.k1, self.inputs = row_taps, k1, inputs
         self.sequences = torch.tensor([ids], dtype=torch.long)
         self.past_key_values = cache
         self.hidden = hidden
@@ -57,16 +64,24 @@ class _RefOut:
 class RefAdapter:
     """Reference model behind the agent's call surface."""
 
-    def __init__(self, model):
+    def __init__(self, model, tap_turns=()):
         self.m = model
+        self.tap_turns, self.turn = set(tap_turns), 0        # model turns whose prefill is tapped row by row
 
     def reset_for_env(self, i):
         self.m.reset_for_env(i)
 
     def generate(self, inputs, images, env_id, time_ids, past_key_values, max_new_tokens, eos_token_ids, **_):
+        rows = [] if self.turn in self.tap_turns else None
+        self.turn += 1
+        P = 0 if past_key_values is None else past_key_values.get_seq_length()
         ids, cache, hid, emb = RH.reference_turn(self.m, env_id, inputs, images.float(), time_ids, past_key_values,
-                                                 max_new_tokens, eos_token_ids)
-        return _RefOut(ids, cache, hid, emb)
+                                                 max_new_tokens, eos_token_ids, row_taps=rows)
+        k1 = None
+        if rows is not None:                                 # layer 1's post-RoPE K of this prefill's rows, [T, kv_dim]
+            T = rows[0].shape[0]
+            k1 = RH.cache_keys(cache, 1)[:, P:P + T].transpose(0, 1).reshape(T, -1).clone()
+        return _RefOut(ids, cache, hid, emb, rows, k1, [int(i) for i in np.asarray(inputs).reshape(-1)])
 
 
 def run(model, sc, tap_embeds):
@@ -74,6 +89,31 @@ def run(model, sc, tap_embeds):
     log = run_scenario(model, sc, preprocess=lambda rgb: torch.from_numpy(O.siglip_preprocess(rgb)),
                        on_turn=lambda t, rec: embeds.append(tap_embeds(rec["out"])))
     return log, embeds
+
+
+def row_tap_fixture(fx, cfg, sc, t, r, o):
+    """the row taps of tapped turn t (tests/restart_ref.py): reference values, after oracle == reference within 2e-4"""
+    ref_rows, orc_rows = r["out"].row_taps, o["out"].row_taps
+    assert len(ref_rows) == len(orc_rows) == cfg.layers
+    T = ref_rows[0].shape[0]
+    sel = RR.select_rows(T, r["out"].inputs, cfg.pool_tokens, (sc["num_history"] or 0) * cfg.pool_tokens, SEED + t)
+    for l in range(cfg.layers):
+        xr, xo = ref_rows[l].numpy(), orc_rows[l].numpy()
+        assert xr.shape == xo.shape == (T, cfg.hidden)
+        assert close(xo, xr), (t, l, "row taps")
+        pr, po = RR.project(xr), RR.project(xo)
+        fx[f"t{t}_L{l}_rows_idx"] = sel
+        fx[f"t{t}_L{l}_rows"] = xr[sel].astype(np.float32)
+        fx[f"t{t}_L{l}_proj"] = pr.astype(np.float32)
+        fx[f"t{t}_L{l}_proj_noise"] = np.float32(np.abs(po - pr).max())
+        print(f"  turn {t} layer {l}: T {T} rows {sel.tolist()} row rms {np.sqrt((xr.astype(np.float64) ** 2).mean(1)).min():.2f}.."
+              f"{np.sqrt((xr.astype(np.float64) ** 2).mean(1)).max():.2f} max |x| {np.abs(xr).max():.2f} "
+              f"oracle-ref max {np.abs(xo - xr).max():.2e} proj noise {np.abs(po - pr).max():.3e}")
+    P = o["out"].prefill_span[0]
+    k_o = o["out"].past_key_values.k[1][:, P:P + T].transpose(0, 1).reshape(T, -1).numpy()
+    k_r = r["out"].k1.numpy()
+    assert k_r.shape == (T, cfg.kv_dim) and close(k_o, k_r), (t, "K rows")
+    fx[f"t{t}_K1_rows"] = k_r[sel].astype(np.float32)
 
 
 def close(a, b, tol=2e-4):
@@ -133,7 +173,8 @@ def main():
         orc = O.OracleStreamVLN(cfg, sd, num_history=sc["num_history"])
         apply_knobs(ref, sc)
         apply_knobs(orc, sc)
-        log_r, emb_r = run(RefAdapter(ref), sc, lambda out: out.embeds)
+        orc.tap_rows = bool(sc.get("row_taps"))
+        log_r, emb_r = run(RefAdapter(ref, sc.get("row_taps", ())), sc, lambda out: out.embeds)
         # oracle: per-turn embeds = the rows appended to its cache this turn
         seen = [0]
 
@@ -170,6 +211,8 @@ def main():
             fx[f"t{t}_embeds_cols"] = e[:, [0, 1, e.shape[1] // 2, e.shape[1] - 1]].astype(np.float32)
             fx[f"t{t}_embeds_sel"] = e[[0, e.shape[0] // 2, e.shape[0] - 1]].astype(np.float32)
             fx[f"t{t}_embeds_rowsum"] = e.sum(1).astype(np.float32)
+            if t in sc.get("row_taps", ()):
+                row_tap_fixture(fx, cfg, sc, t, r, o)
             print(f"{name} turn {t}: step {r['step_id']} views {r['views']} mem {r['memory']} "
                   f"T_embeds {e.shape[0]} ids {ids_r} min-margin {min(o['out'].margins):.4f}")
         np.savez_compressed(os.path.join(GOLD, name + ".npz"), **fx)

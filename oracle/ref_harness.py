@@ -102,11 +102,22 @@ def build_reference_model(cfg, weights, num_history):
     return model
 
 
+def cache_keys(cache, layer):
+    """post-RoPE K of one layer as the reference's cache object holds it, [kv_heads, len, head_dim] (the attribute moved between
+    transformers versions)"""
+    if hasattr(cache, "layers"):
+        return cache.layers[layer].keys[0]
+    return cache.key_cache[layer][0]
+
+
 @torch.no_grad()
-def reference_turn(model, env_id, inputs, images, time_ids, past, max_new_tokens, eos_ids):
+def reference_turn(model, env_id, inputs, images, time_ids, past, max_new_tokens, eos_ids, row_taps=None):
     """One `generate` turn through the reference's own code paths, restating only the
     4.45.1 GenerationMixin bookkeeping that 5.x no longer matches.
-    Returns (new token ids, cache, final-norm hidden per generated token, inputs_embeds of this turn)."""
+    Returns (new token ids, cache, final-norm hidden per generated token, inputs_embeds of this turn).
+    row_taps (a list, optional): receives every decoder layer's output on all rows of the PREFILL call, [T,H] each, through forward
+    hooks on the reference's own decoder layers (not `output_hidden_states`, whose contents differ between transformers versions);
+    the decode calls are not tapped."""
     from transformers import DynamicCache
     V = images.shape[1]
     dummy = dict(depths=torch.zeros(1, V, 4, 4), poses=torch.zeros(1, V, 4, 4), intrinsics=torch.zeros(1, V, 4, 4))
@@ -136,7 +147,16 @@ def reference_turn(model, env_id, inputs, images, time_ids, past, max_new_tokens
     if pen != 1.0:
         from transformers import RepetitionPenaltyLogitsProcessor
         proc = RepetitionPenaltyLogitsProcessor(penalty=pen)
-    h, logits = fwd(inputs_embeds=E[:, P:])
+    hooks = []
+    if row_taps is not None:
+        def keep(_mod, _args, output):
+            row_taps.append((output[0] if isinstance(output, (tuple, list)) else output)[0].detach().clone())
+        hooks = [layer.register_forward_hook(keep) for layer in model.model.layers]
+    try:
+        h, logits = fwd(inputs_embeds=E[:, P:])
+    finally:
+        for hk in hooks:
+            hk.remove()
     out, hid = [], []
     while True:
         scores = logits.float()

@@ -373,15 +373,18 @@ def qwen2_layer(w: W, cfg, i: int, x: torch.Tensor, pos: torch.Tensor, cache: KV
 
 
 def qwen2_forward(w: W, cfg, x: torch.Tensor, start: int, cache: KVCache, q8: Optional[Fp8Emu] = None, phase: str = "prefill",
-                  layer_taps: Optional[list] = None):
+                  layer_taps: Optional[list] = None, row_taps: Optional[list] = None):
     """Run T new positions [start, start+T) through all layers; returns final-norm hidden [T,H].
-    layer_taps (test tap): receives the LAST row of the residual stream after every layer."""
+    layer_taps (test tap): receives the LAST row of the residual stream after every layer.
+    row_taps (test tap): receives EVERY row of it after every layer, [T,H] each."""
     assert len(cache) == start
     pos = torch.arange(start, start + x.shape[0])
     for i in range(cfg.layers):
         x = qwen2_layer(w, cfg, i, x, pos, cache, q8, phase)
         if layer_taps is not None:
             layer_taps.append(x[-1].clone())
+        if row_taps is not None:
+            row_taps.append(x.clone())
     return rms_norm(x, w["model.norm.weight"], cfg.rms_eps)
 
 
@@ -432,6 +435,8 @@ class OracleStreamVLN:
         self.cfg = cfg
         self.fp8 = fp8                          # opt-in e4m3 emulation (extension, no reference counterpart); None = the reference's arithmetic
         self.layer_taps: List[torch.Tensor] = []   # last-row residual stream after every layer of the latest prefill (test tap)
+        self.tap_rows = False                      # test tap: keep ALL rows of it too, in `row_taps` ([T,H] per layer, latest prefill)
+        self.row_taps: List[torch.Tensor] = []
         # test mode (no reference counterpart): a queue of token lists, one per coming generate() call -- the call decodes exactly those tokens
         # (teacher forcing) while `own_picks` keeps what this model would have picked at each step and `margins` its top-1 / top-2 gap
         self.teacher_tokens: List[List[int]] = []
@@ -476,7 +481,9 @@ class OracleStreamVLN:
         assert L_total > P
         eos = set(int(e) for e in eos_token_ids)
         self.layer_taps = []
-        h = qwen2_forward(w, cfg, E[P:], P, cache, self.fp8, "prefill", self.layer_taps)[-1]
+        self.row_taps = []
+        h = qwen2_forward(w, cfg, E[P:], P, cache, self.fp8, "prefill", self.layer_taps, self.row_taps if self.tap_rows else None)[-1]
+        prefill_span = (P, L_total)
         out, hid, margins = [], [], []
         pen = float(getattr(self.generation_config, "repetition_penalty", 1.0) or 1.0)
         forced = self.teacher_tokens.pop(0) if self.teacher_tokens else None
@@ -494,4 +501,6 @@ class OracleStreamVLN:
         assert len(cache) == L_total + len(out) - 1
         go = GenerateOutput(torch.tensor([out], dtype=torch.long), cache, torch.stack(hid), margins)
         go.own_picks = list(self.own_picks)                  # == the sequence unless teacher_tokens steered this turn
+        go.row_taps = self.row_taps                          # tap_rows: every layer's output on all rows of this turn's prefill
+        go.prefill_span = prefill_span                       # cache positions [P, L_total) this turn's prefill appended
         return go

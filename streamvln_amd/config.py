@@ -96,7 +96,11 @@ TRUE1 = StreamVLNConfig(name="true_dims_1layer", v_layers=1, layers=1, vocab=819
 #: (down_proj reduce -> next input_layernorm, fc2 reduce -> next layer_norm1) and the full-size lm_head / arg-max at true width.
 TRUE4 = StreamVLNConfig(name="true_dims_4layer", v_layers=4, layers=4)
 
-CONFIGS = {c.name: c for c in (TRUE, TINY, TRUE1, TRUE4)}
+#: True dimensions, two ViT layers + two LLM layers, small vocab: the smallest depth at which layer 1's K/V and output depend on every
+#: prefill row layer 0 produced and at which both inter-layer hand-offs run (the window-restart turn pinned row by row).
+TRUE2 = StreamVLNConfig(name="true_dims_2layer", v_layers=2, layers=2, vocab=8192)
+
+CONFIGS = {c.name: c for c in (TRUE, TINY, TRUE1, TRUE4, TRUE2)}
 
 IGNORE_INDEX = -100          # streamvln/utils/utils.py:8
 IMAGE_TOKEN_INDEX = -200     # streamvln/utils/utils.py:9

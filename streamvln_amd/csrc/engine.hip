@@ -3983,7 +3983,7 @@ public:
     // the oracle at its own scale, on the engine's own inputs: a whole-stack tolerance would hide an O(1)-wrong stage).
     // probe buffers of the probed layer: 0 = x entering the layer, 1 = x leaving it, 2 = attention output (the A operand of o_proj),
     // 3 = x after the attention residual, 4 = post_attention_layernorm(x) (A of gate/up), 5 = silu(gate) * up (A of down_proj)
-    // 6 = input_layernorm(x) (A of the q/k/v product), 7 = the q | k | v buffer after bias and RoPE (v columns: the plain product)
+    // 6 = input_layernorm(x) (A of the q/k/v product), 7 = the q | k | v buffer after bias and RoPE (q columns rotated; k / v columns: the plain product, the rotated k is in the pages)
     static constexpr int N_PROBE = 8;
     bool layer_taps_on = false; int probe_layer = -1; int probe_rows = 0;
     T* layer_tap = nullptr; T* probe_buf[N_PROBE] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

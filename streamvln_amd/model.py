@@ -1411,9 +1411,10 @@ class StreamVLNForCausalLM:
 
     def layer_probe(self, which: int, max_rows: int = 512) -> np.ndarray:
         """operand `which` of the probed layer as the last prefill saw it (0 x_in, 1 x_out, 2 attention out, 3 x after attention,
-        4 post-attention norm, 5 SwiGLU product, 6 input norm, 7 q|k|v after RoPE): fp32 [rows, cols]"""
-        widest = max(self.cfg.inter, self.cfg.q_dim + 2 * self.cfg.kv_dim, self.cfg.hidden)
-        out = np.empty(max_rows * widest, dtype=np.float32)
+        4 post-attention norm, 5 SwiGLU product, 6 input norm, 7 the q|k|v buffer after RoPE -- q rotated, k / v as the product left them,
+        the rotated k lives in the KV pages): fp32 [rows, cols].  The host buffer is sized by the probe's own width."""
+        width = {2: self.cfg.q_dim, 5: self.cfg.inter, 7: self.cfg.q_dim + 2 * self.cfg.kv_dim}.get(int(which), self.cfg.hidden)
+        out = np.empty(max_rows * width, dtype=np.float32)
         n, cols = C.c_int32(), C.c_int32()
         _check(self._lib.svln_get_layer_probe(self._h, int(which), out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(n), C.byref(cols)))
         return out[: n.value * cols.value].reshape(n.value, cols.value).copy()

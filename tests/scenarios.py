@@ -3,7 +3,7 @@ parity tests (test infrastructure)."""
 import torch
 
 from streamvln_amd.agent import StreamingAgent
-from streamvln_amd.config import TINY, TRUE1, TRUE4
+from streamvln_amd.config import TINY, TRUE1, TRUE2, TRUE4
 from streamvln_amd.synthetic import SyntheticPromptEncoder, synthetic_frame
 
 SEED = 1234
@@ -25,6 +25,12 @@ SCENARIOS = {
     # generation_config.repetition_penalty = 1.3 (transformers RepetitionPenaltyLogitsProcessor under greedy decoding): the unpenalised
     # tiny run repeats ids inside a turn ([1507, 153, 153, 153, ...]), so the penalty changes the sequence
     "tiny_penalty": dict(cfg=TINY, steps=16, num_frames=12, nfs=4, num_history=2, max_new=6, eos_mod=0, lens=(40, 48, 16), rep_penalty=1.3),
+    # true dimensions, 2 ViT + 2 LLM layers, a window of 8 frames: first turn (T=376), a steady turn (T=214), the window restart at step 8
+    # (history slice rgb_list[0:8:1]: 9 views, 1568-row <memory> block, T=1952) and the steady turn behind it, 3 tokens each.
+    # row_taps: the turns whose prefill the fixture records row by row (every decoder layer's output; tests/restart_ref.py)
+    # max_positions: the engine buffer a GPU test needs (the last turn ends at position 1954 + 212 + 2; the tests' default is 2048)
+    "true2_restart": dict(cfg=TRUE2, steps=16, num_frames=8, nfs=4, num_history=8, max_new=3, eos_mod=0, lens=(181, 190, 16),
+                          row_taps=(2, 3), max_positions=2304),
 }
 
 

@@ -1,9 +1,11 @@
 """CPU: the oracle (fp32 restatement) reproduces the fixtures generated from the REFERENCE's own modules
-(oracle/make_golden.py).  tiny_episode is replayed in full; true1_episode (true dimensions) for its first turn."""
+(oracle/make_golden.py).  tiny_episode is replayed in full; true1_episode (true dimensions) for its first turn; true2_restart (true
+dimensions, 2 + 2 layers) in full, its restart turn and the turn behind it row by row (tests/restart_ref.py)."""
 import numpy as np
 import pytest
 import torch
 
+import restart_ref as RR
 from oracle import streamvln_oracle as O
 from scenarios import SCENARIOS, SEED, apply_knobs, run_scenario
 from streamvln_amd import weights as W
@@ -11,12 +13,13 @@ from streamvln_amd.synthetic import synthetic_frame
 from util import load_golden
 
 
-def _replay(name, steps=None):
+def _replay(name, steps=None, on_turn=None, tap_rows=False):
     sc, g = SCENARIOS[name], load_golden(name)
     cfg = sc["cfg"]
     orc = O.OracleStreamVLN(cfg, W.synth_state_dict(cfg, SEED), num_history=sc["num_history"])
+    orc.tap_rows = tap_rows
     apply_knobs(orc, sc)
-    log = run_scenario(orc, sc, preprocess=lambda rgb: torch.from_numpy(O.siglip_preprocess(rgb)), steps=steps)
+    log = run_scenario(orc, sc, preprocess=lambda rgb: torch.from_numpy(O.siglip_preprocess(rgb)), steps=steps, on_turn=on_turn)
     for t, rec in enumerate(log):
         out = rec["out"]
         assert out.sequences[0].tolist() == g[f"t{t}_ids"].tolist()
@@ -53,6 +56,75 @@ def test_repetition_penalty_matches_reference_fixture_and_transformers():
 
 def test_true_dims_first_turn_matches_reference_fixture():
     assert _replay("true1_episode", steps=1) == 1
+
+
+@pytest.fixture(scope="module")
+def restart_taps():
+    """true2_restart once through the oracle (ids, hidden, cache lengths against the fixture as for every replay), keeping for the tapped
+    turns every layer's output on all prefill rows and layer 1's post-RoPE K rows: {turn: (rows per layer, K [T, kv_dim])}.  Read-only."""
+    sc = SCENARIOS["true2_restart"]
+    taps = {}
+
+    def keep(t, rec):
+        if t in sc["row_taps"]:
+            out = rec["out"]
+            P, T = out.prefill_span[0], out.row_taps[0].shape[0]
+            k1 = out.past_key_values.k[1][:, P:P + T].transpose(0, 1).reshape(T, -1).numpy().copy()
+            taps[t] = ([x.numpy() for x in out.row_taps], k1)
+    assert _replay("true2_restart", on_turn=keep, tap_rows=True) == 4
+    for rows, k1 in taps.values():
+        for a in rows + [k1]:
+            a.setflags(write=False)
+    return taps
+
+
+def test_restart_prefill_rows_match_reference_fixture(restart_taps):
+    """Every row of the T = 1952 restart prefill and of the steady turn behind it, after each of the two decoder layers, against the rows
+    and sign projections recorded from the reference's own decoder layers: pins the oracle row by row, and shows that a correct
+    implementation stays inside the helper's bounds."""
+    sc, g = SCENARIOS["true2_restart"], load_golden("true2_restart")
+    assert sorted(restart_taps) == list(sc["row_taps"]) == [2, 3]
+    assert restart_taps[2][0][0].shape == (1952, sc["cfg"].hidden) and restart_taps[3][0][0].shape == (212, sc["cfg"].hidden)
+    assert g["t2_L0_rows_idx"].tolist()[:6] == [0, 255, 256, 1791, 1792, 1951]
+    for t, (rows, k1) in restart_taps.items():
+        for l, x in enumerate(rows):
+            r = RR.compare_rows(g, t, l, x)
+            print(f"oracle turn {t} layer {l}: selected rows {r['sel_err']:.2e}, projections {r['proj_err']:.2e} (bound {r['proj_bound']:.2e})")
+        RR.compare_k_rows(g, t, 1, k1[g[f"t{t}_L1_rows_idx"]])
+
+
+def _planted(x, kind, idx):
+    """a copy of `x` with one defect a kernel could produce, away from the selected rows `idx` so that only the projections can see it"""
+    y = np.array(x, dtype=np.float32)
+    free = [r for r in range(y.shape[0]) if r not in set(int(i) for i in idx)]
+    if kind == "row":                                   # (a) one row x (1 + 1e-3)
+        y[free[len(free) // 3]] *= np.float32(1 + 1e-3)
+    elif kind == "tile":                                # (b) a 32-row x 128-column tile x (1 + 2^-8), inside one 256-row tile
+        r0 = next(r for r in range(32, y.shape[0] - 32, 32) if not set(range(r, r + 32)) & set(int(i) for i in idx))
+        y[r0:r0 + 32, 1280:1408] *= np.float32(1 + 2.0 ** -8)
+    elif kind == "swap":                                # (c) two neighbouring rows swapped
+        a = free[len(free) // 2]
+        b = a + 1 if a + 1 in free else a - 1
+        y[[a, b]] = y[[b, a]]
+    return y
+
+
+@pytest.mark.parametrize("kind", ["row", "tile", "swap"])
+def test_restart_row_helper_rejects_planted_defects(restart_taps, kind):
+    """Self-check of tests/restart_ref.compare_rows: the oracle's tensors pass; the same tensors with (a) one row scaled by 1 + 1e-3,
+    (b) a 32 x 128 tile scaled by 1 + 2^-8, (c) two rows swapped -- each planted away from the 8 full-width rows -- must FAIL, on both
+    layers of both tapped turns.  A bound that lets one of them through is not acceptable."""
+    g = load_golden("true2_restart")
+    for t, (rows, _) in restart_taps.items():
+        for l, x in enumerate(rows):
+            idx = g[f"t{t}_L{l}_rows_idx"]
+            clean = RR.compare_rows(g, t, l, x)
+            bad = _planted(x, kind, idx)
+            assert np.array_equal(bad[idx], x[idx]) and not np.array_equal(bad, x)
+            err = float(np.abs(RR.project(bad) - g[f"t{t}_L{l}_proj"]).max(1).max())
+            print(f"planted {kind} turn {t} layer {l}: projection error {err:.3e} = {err / clean['proj_bound']:.1f} x bound")
+            with pytest.raises(AssertionError, match="projection of row"):
+                RR.compare_rows(g, t, l, bad)
 
 
 def test_preprocess_matches_reference_fixture():
