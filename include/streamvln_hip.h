@@ -985,6 +985,37 @@ int svln_op_attention_verify_multi(svln_engine* h, int n_seq, int rows_max, cons
  * ids in emitted[0 .. *new_count - count) (the rest of emitted[rows] = -3) and *next_token (the last emitted token; -3 when none). */
 int svln_op_verify_step(svln_engine* h, int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos,
                         int n_eos, int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token);
+/* TEST-ONLY: `steps` launches of the greedy loop's step kernel (launch_argmax_step; use_ctl = 0: ONE launch_argmax_final on set 0) on
+ * caller-given host partials, enqueued back to back with no host synchronisation between them; launch s reads partial set s.
+ *   part_val / part_idx [steps][n]; part_sum (optional: the scored merge), part_raw / part_max (optional, both or neither, with
+ *   part_sum: the sampled merge); the GenCtl start state pos, kv_len, done, count, max_new; eos[n_eos] (n_eos may be 0);
+ *   flag_bytes > 0: the step kernel sets the emitted token's byte in a flag array of that many bytes (every live part_idx must lie
+ *   below it), 0: no flags.
+ * Before the first launch every output is filled with a sentinel: out_ids[rows] -7, scores[rows] NaN, *last_token -7, out_top[2] NaN,
+ * flags[flag_bytes] 0x5A.  Afterwards ctl_out[8] = the final GenCtl (pos, kv_len, done, count, max_new, n_eos, draw0, stream) and the
+ * five arrays as the launches left them.  `rows` is the capacity of out_ids / scores the launches run against.
+ * Refused before any launch: n outside 1 .. 2048, steps outside 1 .. 8, count < 0 or count + steps > rows, rows beyond the engine's id
+ * buffer, n_eos beyond its EOS buffer, part_raw without part_max or either without part_sum, a null array the chosen form reads, a live
+ * part_idx outside the flag array.  The engine's own generation state is restored afterwards. */
+typedef struct svln_argmax_step_op {
+    const float* part_val; const int32_t* part_idx; const float* part_sum; const float* part_raw; const float* part_max;
+    const int64_t* eos;
+    int32_t* ctl_out; int32_t* out_ids; int32_t* last_token; float* out_top; float* scores; uint8_t* flags;
+    int32_t n, steps, use_ctl, pos, kv_len, done, count, max_new, n_eos, flag_bytes, rows;
+} svln_argmax_step_op;
+int svln_op_argmax_step(svln_engine* h, const svln_argmax_step_op* op);
+/* TEST-ONLY: one decode step behind a finished (done != 0) or a running (done = 0) generation.  Env 0 must hold a prompt that the public
+ * calls have prefilled and generated from.  The entry sets GenCtl.done = done, fills the id rows behind the generation
+ * (d_out_ids[count ..), never read) with -7 so that a live append always shows, snapshots every buffer a step may touch, enqueues exactly
+ * what one replayed step enqueues (decode_ops over the whole step, then head(x, count, true); the captured one-step graph while
+ * svln_set_decode_graph is on), and compares.  report (report_cap bytes, NUL-terminated) gets one line per buffer:
+ *   "<name> <bytes> <changed bytes> <first changed offset or -1> <last changed offset or -1>\n"
+ * for the K and V^T pools of every layer (kpool.<i>, vpool.<i>), attn_part, x, qkv, attn, hbuf, head_xn, hid_tap, the partial, candidate
+ * and truncation arrays, d_token, d_out_ids, d_scores, d_topi, d_topl, d_ent, d_alp, pen_flags, d_top2, the granule and sequence words
+ * of the persistent layer (dl_gran.<k>, dl_seq) and ctl (GenCtl itself, compared with the state AFTER done was set); buffers the engine
+ * has not allocated are left out.  *n_changed = the buffers with a changed byte.  With done = 0 the step is live: it writes the KV slot
+ * of GenCtl.pos and appends a token; the env's host-side bookkeeping does not follow, so reset the env before the next public call. */
+int svln_op_dead_step(svln_engine* h, int done, char* report, int report_cap, int32_t* n_changed);
 /* roped K and V rows of positions [start, start + n) of env's layer-0 KV pages -> host fp32 [n][kv_heads][128] each; env = -1 reads
  * the raw pools (position p = slot p % 64 of physical page p / 64).  The attention ops reset their envs on entry only, so this reads
  * what the last op wrote. */

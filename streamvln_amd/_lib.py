@@ -64,6 +64,13 @@ class SvlnDecodeLayerOp(C.Structure):
                [(n, C.c_int32) for n in ("nsplit", "tiles_per_split", "n_q", "n_kv", "H", "I", "qkv_dim", "cus")] + [("eps", C.c_float)]
 
 
+class SvlnArgmaxStepOp(C.Structure):
+    """svln_argmax_step_op of include/streamvln_hip.h"""
+    _fields_ = [(n, C.c_void_p) for n in ("part_val", "part_idx", "part_sum", "part_raw", "part_max", "eos", "ctl_out", "out_ids", "last_token",
+                                          "out_top", "scores", "flags")] + \
+               [(n, C.c_int32) for n in ("n", "steps", "use_ctl", "pos", "kv_len", "done", "count", "max_new", "n_eos", "flag_bytes", "rows")]
+
+
 class SvlnDecodeLayerWalkOp(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("elem_size", "K", "nrows", "pair", "first")]
 
@@ -252,6 +259,8 @@ SIGNATURES = {
     "svln_op_attention_verify": (_I, [_P, _I, _P, _I, _I, _P, _P, _I]),
     "svln_op_attention_verify_multi": (_I, [_P, _I, _I, _P, _I, _I, _PI32, _P, _PI32, _I, _P, _I]),
     "svln_op_verify_step": (_I, [_P, _I, _PI32, _PI32, _I, _I, _PI64, _I, _PI32, _PI32, _PI64, _PI32]),
+    "svln_op_argmax_step": (_I, [_P, C.POINTER(SvlnArgmaxStepOp)]),
+    "svln_op_dead_step": (_I, [_P, _I, C.c_char_p, _I, _PI32]),
     "svln_op_kv_read": (_I, [_P, _I, _I, _I, _PF, _PF]),
     "svln_op_llm_qkv_rope": (_I, [_P, _P, _I, _I, _P, _I, _PI32]),
     "svln_op_rope_kv_mirror": (_I, [_P, _P, _I, _I, _I, _PI32, _I]),

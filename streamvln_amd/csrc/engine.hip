@@ -198,6 +198,8 @@ struct EngineBase {
                                            const int32_t* rows, int share, void* out, int o_stride) = 0;
     virtual void op_verify_step(int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos, int n_eos,
                                 int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token) = 0;
+    virtual void op_argmax_step(const svln_argmax_step_op& q) = 0;
+    virtual void op_dead_step(int done, char* report, int report_cap, int32_t* n_changed) = 0;
     virtual bool op_gemm_fp8(const GemmArgs& a) = 0;
     virtual void set_memory_prune(int keep) = 0;
     virtual void op_memory_prune(const void* m, int n_rows, int keep, int32_t* out_idx, float* out_score) = 0;
@@ -5124,6 +5126,155 @@ public:
         HIP_CHECK(hipMemcpy(&tk, d_token, sizeof(int), hipMemcpyDeviceToHost));
         *new_count = g.count; *done = g.done; *next_token = tk;
     }
+    // TEST-ONLY: `steps` step-kernel launches back to back on caller-given partial sets (use_ctl = 0: one launch_argmax_final on set 0),
+    // on the engine's own d_ctl / d_eos / d_out_ids / d_scores / d_token / d_top2, which are saved before and restored afterwards
+    void op_argmax_step(const svln_argmax_step_op& q) override {
+        const size_t cap = (size_t)c.max_positions + 8, eos_cap = (size_t)(V > 16 ? V : 16);
+        REQUIRE(q.n >= 1 && q.n <= 2048, "op_argmax_step: n must be 1 .. 2048");
+        REQUIRE(q.steps >= 1 && q.steps <= 8, "op_argmax_step: steps must be 1 .. 8");
+        REQUIRE(q.rows >= 1 && (size_t)q.rows <= cap, "op_argmax_step: rows beyond the id buffer");
+        REQUIRE(q.count >= 0 && q.count + q.steps <= q.rows, "op_argmax_step: count leaves no room in out_ids");
+        REQUIRE(q.n_eos >= 0 && (size_t)q.n_eos <= eos_cap && (q.n_eos == 0 || q.eos), "op_argmax_step: eos list");
+        REQUIRE(q.part_val && q.part_idx && q.ctl_out && q.out_ids && q.last_token && q.out_top && q.scores, "op_argmax_step: null pointer");
+        REQUIRE((q.part_raw != nullptr) == (q.part_max != nullptr) && (!q.part_raw || q.part_sum), "op_argmax_step: part_raw / part_max come together, with part_sum");
+        REQUIRE(q.flag_bytes >= 0 && q.flag_bytes <= (1 << 24) && (q.flag_bytes == 0 || q.flags), "op_argmax_step: flag array");
+        const size_t np = (size_t)q.steps * q.n;
+        if (q.flag_bytes)
+            for (size_t k = 0; k < np; ++k)
+                REQUIRE(q.part_idx[k] == 0x7FFFFFFF || (q.part_idx[k] >= 0 && q.part_idx[k] < q.flag_bytes), "op_argmax_step: a part_idx outside the flag array");
+        sync();
+        eos_valid = false;                 // d_eos is rewritten here
+        std::vector<int> he(q.n_eos);
+        for (int k = 0; k < q.n_eos; ++k) he[k] = q.eos[k] >= 0 && q.eos[k] < 0x7FFFFFFF ? (int)q.eos[k] : -2;
+        // the engine's own state, restored at the end
+        GenCtl g0; int tok0[4]; float top0[4];
+        std::vector<int> ids0(q.rows); std::vector<float> sc0(q.rows);
+        HIP_CHECK(hipMemcpy(&g0, d_ctl, sizeof(g0), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(tok0, d_token, sizeof(tok0), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(top0, d_top2, sizeof(top0), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(ids0.data(), d_out_ids, ids0.size() * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(sc0.data(), d_scores, sc0.size() * sizeof(float), hipMemcpyDeviceToHost));
+        float *pv = nullptr, *ps = nullptr, *pr = nullptr, *pm = nullptr; int* pi = nullptr; uint8_t* fl = nullptr;
+        auto up = [&](auto*& dst, const void* src, size_t bytes) {
+            HIP_CHECK(hipMalloc((void**)&dst, bytes));
+            HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+        };
+        auto cleanup = [&] {
+            for (void* p : {(void*)pv, (void*)ps, (void*)pr, (void*)pm, (void*)pi, (void*)fl}) if (p) (void)hipFree(p);
+        };
+        try {
+            up(pv, q.part_val, np * 4); up(pi, q.part_idx, np * 4);
+            if (q.part_sum) up(ps, q.part_sum, np * 4);
+            if (q.part_raw) { up(pr, q.part_raw, np * 4); up(pm, q.part_max, np * 4); }
+            if (q.flag_bytes) { HIP_CHECK(hipMalloc((void**)&fl, (size_t)q.flag_bytes)); HIP_CHECK(hipMemset(fl, 0x5A, (size_t)q.flag_bytes)); }
+            if (q.n_eos) HIP_CHECK(hipMemcpy(d_eos, he.data(), (size_t)q.n_eos * sizeof(int), hipMemcpyHostToDevice));
+            const float nanv = __builtin_nanf("");
+            std::vector<int> ids(q.rows, -7); std::vector<float> sc(q.rows, nanv);
+            const int tk[4] = {-7, -7, -7, -7}; const float tp[4] = {nanv, nanv, nanv, nanv};
+            HIP_CHECK(hipMemcpy(d_out_ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(d_scores, sc.data(), sc.size() * sizeof(float), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(d_token, tk, sizeof(tk), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(d_top2, tp, sizeof(tp), hipMemcpyHostToDevice));
+            GenCtl g; g.pos = q.pos; g.kv_len = q.kv_len; g.done = q.done; g.count = q.count; g.max_new = q.max_new; g.n_eos = q.n_eos; g.draw0 = g.stream = 0;
+            HIP_CHECK(hipMemcpy(d_ctl, &g, sizeof(g), hipMemcpyHostToDevice));
+            if (q.use_ctl) {
+                for (int s = 0; s < q.steps; ++s) {
+                    const size_t o = (size_t)s * q.n;
+                    launch_argmax_step(st, pv + o, pi + o, q.n, d_token, d_top2, d_ctl, d_eos, d_out_ids, fl, ps ? ps + o : nullptr, ps ? d_scores : nullptr,
+                                       pr ? pr + o : nullptr, pm ? pm + o : nullptr);
+                }
+            } else {
+                launch_argmax_final(st, pv, pi, q.n, d_token, d_top2, ps, ps ? d_scores : nullptr, pr, pm);
+            }
+            sync();
+            LAUNCH_CHECK("op_argmax_step");
+            HIP_CHECK(hipMemcpy(&g, d_ctl, sizeof(g), hipMemcpyDeviceToHost));
+            static_assert(sizeof(GenCtl) == 8 * sizeof(int), "GenCtl: eight ints");
+            std::memcpy(q.ctl_out, &g, sizeof(g));
+            HIP_CHECK(hipMemcpy(q.out_ids, d_out_ids, (size_t)q.rows * sizeof(int), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(q.scores, d_scores, (size_t)q.rows * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(q.last_token, d_token, sizeof(int), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(q.out_top, d_top2, 2 * sizeof(float), hipMemcpyDeviceToHost));
+            if (q.flag_bytes) HIP_CHECK(hipMemcpy(q.flags, fl, (size_t)q.flag_bytes, hipMemcpyDeviceToHost));
+        } catch (...) {
+            cleanup();
+            throw;
+        }
+        cleanup();
+        HIP_CHECK(hipMemcpy(d_ctl, &g0, sizeof(g0), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_token, tok0, sizeof(tok0), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_top2, top0, sizeof(top0), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_out_ids, ids0.data(), ids0.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_scores, sc0.data(), sc0.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    // TEST-ONLY: one decode step on env 0 with GenCtl.done forced to `done`, every buffer a step may touch compared with a host snapshot
+    void op_dead_step(int done, char* report, int report_cap, int32_t* n_changed) override {
+        REQUIRE(report && report_cap >= 1 && n_changed, "op_dead_step: null pointer");
+        Env& e = env_at(0);
+        REQUIRE(e.n_embeds >= 1 && e.kv_len >= 1 && e.n_pages >= 1, "op_dead_step: env 0 holds no prefilled prompt");
+        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "op_dead_step: scheduler turns are in flight");
+        REQUIRE(!probe_on, "op_dead_step: the roofline probe is on");
+        REQUIRE(spec_rows == 0 && !ride_on, "op_dead_step: the draft modes have their own step");
+        sync();
+        GenCtl g;
+        HIP_CHECK(hipMemcpy(&g, d_ctl, sizeof(g), hipMemcpyDeviceToHost));
+        REQUIRE(g.pos >= 0 && g.pos < c.max_positions && g.kv_len == g.pos + 1, "op_dead_step: GenCtl holds no generation");
+        REQUIRE(g.count >= 1 && g.count < c.max_positions, "op_dead_step: GenCtl holds no generation");
+        if (!done) ensure_pages(e, g.pos + 1);
+        g.done = done ? 1 : 0;
+        HIP_CHECK(hipMemcpy(d_ctl, &g, sizeof(g), hipMemcpyHostToDevice));
+        {   // the id rows behind the generation hold whatever the allocation held: a sentinel, so that a live step's append always shows
+            std::vector<int> fill((size_t)c.max_positions + 8 - g.count, -7);
+            HIP_CHECK(hipMemcpy(d_out_ids + g.count, fill.data(), fill.size() * sizeof(int), hipMemcpyHostToDevice));
+        }
+        struct Buf { std::string name; const void* p; size_t bytes; };
+        std::vector<Buf> bufs;
+        auto add = [&](const std::string& name, const void* p, size_t bytes) { if (p && bytes) bufs.push_back({name, p, bytes}); };
+        const size_t rt = (size_t)c.max_positions, rows = rt + 8, pool = (size_t)pages_total * nkv * PAGE * 128 * sizeof(T);
+        for (int i = 0; i < c.layers; ++i) { add("kpool." + std::to_string(i), ll[i].kpool, pool); add("vpool." + std::to_string(i), ll[i].vpool, pool); }
+        add("attn_part", attn_part, attn_part_elems * sizeof(float));
+        add("x", x, rt * H * sizeof(T)); add("qkv", qkv, rt * qkv_dim * sizeof(T)); add("attn", attn, rt * nq * 128 * sizeof(T));
+        add("hbuf", hbuf, rt * I * sizeof(T)); add("head_xn", head_xn, (size_t)H * sizeof(T)); add("hid_tap", hid_tap, (size_t)HID_TAP_ROWS * H * sizeof(T));
+        add("part_val", part_val, 2048 * 4); add("part_idx", part_idx, 2048 * 4); add("part_sum", part_sum, 2048 * 4);
+        add("part_raw", part_raw, 2048 * 4); add("part_max", part_max, 2048 * 4); add("part_ent", part_ent, 2048 * 4);
+        add("cand_val", cand_val, (size_t)2048 * TOPK_C * 4); add("cand_idx", cand_idx, (size_t)2048 * TOPK_C * 4);
+        add("tr_val", tr_val, TOPK_C * 4); add("tr_idx", tr_idx, TOPK_C * 4); add("tr_sum", tr_sum, TOPK_C * 4);
+        add("tr_raw", tr_raw, TOPK_C * 4); add("tr_max", tr_max, TOPK_C * 4);
+        add("d_token", d_token, 4 * sizeof(int)); add("d_out_ids", d_out_ids, rows * sizeof(int)); add("d_scores", d_scores, rows * sizeof(float));
+        add("d_topi", d_topi, rows * TOPK_C * sizeof(int)); add("d_topl", d_topl, rows * TOPK_C * sizeof(float));
+        add("d_ent", d_ent, rows * sizeof(float)); add("d_alp", d_alp, rows * ALLOW_MAX * sizeof(float));
+        add("pen_flags", pen_flags, (size_t)V); add("d_top2", d_top2, 4 * sizeof(float));
+        if (dl_seq) {
+            const size_t ng[4] = {(size_t)nq * 128, (size_t)H, (size_t)I, (size_t)H};
+            for (int k = 0; k < 4; ++k) add("dl_gran." + std::to_string(k), dl_gran[k], ng[k] * sizeof(unsigned long long));
+            add("dl_seq", dl_seq, 64 * sizeof(unsigned));
+        }
+        add("ctl", d_ctl, sizeof(GenCtl));
+        std::vector<std::vector<uint8_t>> before(bufs.size());
+        for (size_t b = 0; b < bufs.size(); ++b) {
+            before[b].resize(bufs[b].bytes);
+            HIP_CHECK(hipMemcpy(before[b].data(), bufs[b].p, bufs[b].bytes, hipMemcpyDeviceToHost));
+        }
+        decode_steps(e, 0, g.count, 1);
+        sync();
+        LAUNCH_CHECK("op_dead_step");
+        std::string out;
+        int changed = 0;
+        std::vector<uint8_t> after;
+        for (size_t b = 0; b < bufs.size(); ++b) {
+            after.resize(bufs[b].bytes);
+            HIP_CHECK(hipMemcpy(after.data(), bufs[b].p, bufs[b].bytes, hipMemcpyDeviceToHost));
+            long long n = 0, first = -1, last = -1;
+            if (std::memcmp(after.data(), before[b].data(), bufs[b].bytes) != 0)
+                for (size_t k = 0; k < bufs[b].bytes; ++k)
+                    if (after[k] != before[b][k]) { if (first < 0) first = (long long)k; last = (long long)k; ++n; }
+            changed += n != 0;
+            out += bufs[b].name + " " + std::to_string(bufs[b].bytes) + " " + std::to_string(n) + " " + std::to_string(first) + " " + std::to_string(last) + "\n";
+        }
+        REQUIRE(out.size() + 1 <= (size_t)report_cap, "op_dead_step: the report does not fit");
+        std::memcpy(report, out.c_str(), out.size() + 1);
+        *n_changed = changed;
+    }
     void op_attention_vit(const void* qkv_buf, int ld, int F, void* out, int o_stride) override {
         REQUIRE(F >= 1 && F <= c.max_frames, "frames");
         vit_attention(qkv_buf, ld, F, out, o_stride); sync();
@@ -5817,6 +5968,15 @@ int svln_op_attention_verify_multi(svln_engine* h, int n_seq, int rows_max, cons
 int svln_op_verify_step(svln_engine* h, int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos, int n_eos,
                         int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token) {
     API_BEGIN_H h->impl->op_verify_step(rows, fed, cand, count, max_new, eos, n_eos, new_count, done, emitted, next_token); API_END
+}
+int svln_op_argmax_step(svln_engine* h, const svln_argmax_step_op* op) {
+    API_BEGIN_H
+    if (!op) throw std::runtime_error("null pointer");
+    h->impl->op_argmax_step(*op);
+    API_END
+}
+int svln_op_dead_step(svln_engine* h, int done, char* report, int report_cap, int32_t* n_changed) {
+    API_BEGIN_H h->impl->op_dead_step(done, report, report_cap, n_changed); API_END
 }
 int svln_op_kv_read(svln_engine* h, int env, int start, int n, float* k_out, float* v_out) { API_BEGIN_H h->impl->op_kv_read(env, start, n, k_out, v_out); API_END }
 int svln_op_llm_qkv_rope(svln_engine* h, const void* x, int T, int P, void* q_out, int q_stride, int32_t* fused) {
