@@ -5,8 +5,8 @@
 //   gemv_rows_kernel<P, EPI>         256-thread workgroups; the activation vector is staged ONCE per workgroup into LDS as fp32 (with a
 //       fused RMSNorm the copy holds g * x and rsqrt(mean x^2 + eps) is applied once per output in the epilogue: one pass over x, one
 //       barrier), then every wave streams whole weight rows straight HBM -> VGPR with 16-byte loads (lane i takes chunks i, i+64, ... of
-//       the row: each wave instruction reads 1 KiB contiguous), 4 rows per wave and two chunks per row in flight for memory-level
-//       parallelism, wave-shuffle reduction, fused epilogue (bias / residual / SwiGLU / arg-max).  No LDS round trip for weights (each
+//       the row: each wave instruction reads 1 KiB contiguous), 4 rows per wave and two chunks per row in flight (WP12: three) for
+//       memory-level parallelism, wave-shuffle reduction, fused epilogue (bias / residual / SwiGLU / arg-max).  No LDS round trip for weights (each
 //       byte is used once).
 //   gemv_ksplit_kernel<P, NORM, KW>  small N (qkv / o / down of a decode step): a workgroup owns a few rows and its waves split K.
 // A policy says what a weight format is and nothing else: elements per 16-byte chunk (hence the LDS planes of the staged activations),
@@ -20,6 +20,7 @@
 
 #include <cstdlib>
 #include <stdexcept>
+#include <type_traits>
 
 #include "common.h"
 #include "kernels.h"
@@ -41,6 +42,8 @@ constexpr int GEMV_WAVES = GEMV_THREADS / 64;
 //   Acc, zero(), fma(chunk, x2, acc), sum(acc)   the accumulator and the chunk . x step (x2[k]: activations 2k, 2k + 1 under the chunk, fp32)
 //   row_scale(p, n)  factor applied to row n's dot product after the reduction
 //   X_LATE           row kernel: load the second chunk's activations only after the first chunk's products
+//   DEPTH, KS_DEPTH, ROWS_RESIDENT, KS_RESIDENT   (optional; WP12 only) chunks per row in flight in the row / K-split kernel instead of
+//                    two (dot_accum_deep instead of dot_accum), and the workgroups per CU the registers must leave room for
 //   ROWS_GRID_CAP    row kernel without arg-max: most workgroups of a launch (0: gemv_grid alone decides)
 //   KS_R, KS_KW_NARROW, KS_PAIRED   K-split kernel: rows per row group; waves on K when K <= 4096 (4 above: see launch_gemv_fmt);
 //                    two chunks per row in flight in the un-normalised form
@@ -150,7 +153,9 @@ struct WMxfp4 : WPacked {
 //                   dword holds element k's code in its LOW nibble and element k + 4's in its HIGH nibble (k = 0 .. 3), so that
 //                   x & 0x07070707 and (x >> 4) & 0x07070707 are the v_perm_b32 selectors of elements 0 .. 3 and 4 .. 7 into T.
 //   A block with an element whose hi7 is not in T has its mask bit set and packed bytes zero; it is read from the bf16 original
-//   (W / ldw, resident for prefill anyway).  Which of the two a wave reads is known from the record before any load of the row.
+//   (W / ldw, resident for prefill anyway).  The packed bytes of EVERY block are loaded without a look at the record (zeros inside the
+//   fixed row stride for a fallback block); the record is looked at when a step's chunks are consumed, and only then a fallback block
+//   is fetched from the original (WP12 below, consume()).
 //   A ragged last block (K % 512 != 0) is zero padded; the packed row stride is ceil(K / 512) * 768 bytes.
 // Decoding is s << 15 | T[j] << 8 | lo: the original bit pattern, whatever it means (NaN, Inf, -0, denormals).  The lane -> chunk
 // assignment, EPC and the fmaf chain are WPlain<bf16>'s, so every output is bit-equal to the bf16 kernel's.
@@ -177,20 +182,30 @@ SVLN_DEV void p12_decode_f32(unsigned lo0, unsigned lo1, unsigned c, unsigned t0
     f[6] = __uint_as_float(__builtin_amdgcn_perm(hb, lo1, 0x06020C0Cu)); f[7] = __uint_as_float(__builtin_amdgcn_perm(hb, lo1, 0x07030C0Cu));
 }
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+typedef __attribute__((address_space(4))) const u32x4 p12_record_t;
 struct WP12 {
     using X = bf16;
     static constexpr int EPC = 8;
-    // (table and mask are wave-uniform: they live in scalar registers, and the fallback decisions are scalar selects and branches)
-    struct Row { const uint8_t* pk; const bf16* w; unsigned t0, t1, m0, m1; };
-    // packed: a = the 8 low bytes, b = the aligned 8 bytes that hold the lane's code dword (lanes 2 k and 2 k + 1 read the same 8: an
-    // 8-byte load on an address of its own instead of a 4-byte one).  Fallback (fb): a, b = bytes 0 .. 7, 8 .. 15 of the bf16 chunk.  Both
-    // forms issue the SAME two loads on selected addresses, nothing behind a branch: a conditional load into registers the other form also
-    // writes makes the compiler wait for every load in flight first, and any conditional load makes its count of them a lower bound.
-    struct Chunk { u32x2 a, b; unsigned t0, t1; bool fb, odd; };
+    // The record is needed to DECODE a chunk, not to load it: table and mask come in with one uniform-address scalar load per row (SGPRs,
+    // counted on lgkmcnt, so vmcnt stays exact for the stream), issued in front of the row group's weight loads and first looked at behind
+    // the loads of the group's first step (consume()).  No load address depends on it.
+    struct Row { const uint8_t* pk; const bf16* W; unsigned ldw, n, t0, t1, m0, m1; };      // (W, ldw: the launch's, one copy for all rows)
+    // A chunk in flight is 12 bytes in 3 VGPRs: the 8 low bytes and the lane's own code dword, loaded UNCONDITIONALLY at addresses the
+    // record has no part in.  In bounds for every block of every row: the packed row stride p12_row_bytes(K) covers ceil(K / 512) whole
+    // blocks -- a fallback block's bytes are zeros, a ragged last block is zero padded -- and blk < ceil(K / 512) whenever a lane of it is
+    // active.  (blk: the wave-uniform block index, a scalar.)
+    struct Chunk { u32x2 a; unsigned c; int blk; };
     using Acc = float;
-    static constexpr bool X_LATE = false;
-    // 103-120 VGPRs: four workgroups per CU are resident.  With gate/up's 1184 workgroups the last 160 ran as a second round of a kernel
-    // that is not bandwidth-bound (41.3 us per launch; 1024: 39.0 us alone, 40.5 against 43.3 in the decode step: DESIGN.md 4.1)
+    // Chunks per row in flight (a CU streams bytes in flight / ~4.5-5 us of loaded HBM latency: profiles/r04_stream_layout_bench.txt).
+    // Row kernels: 3 -> 4 rows x 3 x 768 B = 9 KB per wave, 100-121 VGPRs, 4 waves per SIMD as at depth 2: 144 KB per CU instead of 96.
+    // K-split (down_proj): 3 -> 2 rows x 3 x 768 B = 4.5 KB per wave at 70 VGPRs, its 7 workgroups per CU still resident: 126 KB
+    // instead of 84; depth 4 takes 84 VGPRs (5 waves per SIMD: 120 KB) or, held to 72, spills.  Measured: DESIGN.md 4.1.
+    static constexpr int DEPTH = 3, KS_DEPTH = 3;
+    // ... and the workgroups per CU (= waves per SIMD) the register allocation is held to in the row kernels, so that no epilogue pays
+    // for the depth in waves (without it EPI_SAMPLE_TOPK took 133 VGPRs); the K-split kernel fits on its own (1: no bound)
+    static constexpr int ROWS_RESIDENT = 4, KS_RESIDENT = 1;
+    // four workgroups per CU are resident, at depth 3 as at depth 2.  With gate/up's 1184 workgroups the last 160 ran as a second round of
+    // a kernel that is not bandwidth-bound (depth 2: 41.3 us per launch; 1024: 39.0 us alone, 40.5 against 43.3 in the decode step: DESIGN.md 4.1)
     static constexpr int ROWS_GRID_CAP = 1024;
     static constexpr int KS_R = 2;                  // the bf16 policy's K-split geometry: the lane -> chunk assignment is part of the bit-equality contract
     static constexpr int KS_KW_NARROW = 4;
@@ -202,33 +217,103 @@ struct WP12 {
         return ((size_t)hi << 32) | lo;
     }
     SVLN_DEV static Row row(const GemvArgs& p, size_t n) {
-        const uint4 rec = *(const uint4*)((const uint8_t*)p.prec + n * 16);
-        return {(const uint8_t*)p.wp + uniform(n * p12_row_bytes(p.K)), (const bf16*)p.W + uniform(n * (size_t)p.ldw),
-                (unsigned)__builtin_amdgcn_readfirstlane((int)rec.x), (unsigned)__builtin_amdgcn_readfirstlane((int)rec.y),
-                (unsigned)__builtin_amdgcn_readfirstlane((int)rec.z), (unsigned)__builtin_amdgcn_readfirstlane((int)rec.w)};
+        // (the records are read-only for the whole launch and the address is wave-uniform: the constant address space makes it a scalar load)
+        const u32x4 rec = *(p12_record_t*)((size_t)p.prec + uniform(n * 16));
+        return {(const uint8_t*)p.wp + uniform(n * p12_row_bytes(p.K)), (const bf16*)p.W, (unsigned)p.ldw, (unsigned)__builtin_amdgcn_readfirstlane((int)n), rec.x, rec.y, rec.z,
+                rec.w};
     }
     SVLN_DEV static Chunk load(const Row& r, int ci) {          // (ci = lane + a multiple of 64 in both kernels: the block is wave-uniform)
-        const int blk = __builtin_amdgcn_readfirstlane(ci >> 6);
+        Chunk c;
+        c.blk = __builtin_amdgcn_readfirstlane(ci >> 6);
         const unsigned l = (unsigned)ci & 63u;
-        Chunk c; c.t0 = r.t0; c.t1 = r.t1; c.odd = l & 1u;
-        c.fb = (((blk & 32) ? r.m1 : r.m0) >> (blk & 31)) & 1u;
-        const uint8_t* wb = (const uint8_t*)r.w + (size_t)blk * 1024;
-        const uint8_t* pb = r.pk + (size_t)blk * 768;
-        c.a = __builtin_nontemporal_load((const u32x2*)((c.fb ? wb : pb) + (l << (c.fb ? 4 : 3))));
-        c.b = __builtin_nontemporal_load((const u32x2*)((c.fb ? wb + 8 : pb + 512) + (c.fb ? l << 4 : (l >> 1) << 3)));
+        const uint8_t* pb = r.pk + (size_t)c.blk * 768;
+        c.a = __builtin_nontemporal_load((const u32x2*)(pb + (l << 3)));
+        c.c = __builtin_nontemporal_load((const unsigned*)(pb + 512 + (l << 2)));
         return c;
     }
     SVLN_DEV static Acc zero() { return 0.0f; }
-    SVLN_DEV static void fma(const Chunk& w, const f32x2* x2, Acc& acc) {
-        float f[EPC];
-        if (w.fb) chunk_to_f32<bf16>(make_uint4(w.a.x, w.a.y, w.b.x, w.b.y), f);
-        else p12_decode_f32(w.a.x, w.a.y, w.odd ? w.b.y : w.b.x, w.t0, w.t1, f);
+    SVLN_DEV static bool falls_back(const Row& r, int blk) { return (((blk & 32) ? r.m1 : r.m0) >> (blk & 31)) & 1u; }
+    // does no row of the group fall back on a block of `blocks` (bit k = block k)?  One scalar AND per row.
+    template <int R> SVLN_DEV static bool all_packed(const Row (&rows)[R], unsigned long long blocks) {
+        // (the empty asm keeps the look at the masks HERE, behind the step's loads: the union of the rows' masks does not change from step to
+        // step, and formed in front of the loop it makes the wave wait for the records before its first weight load)
+        unsigned long long hit = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            unsigned long long m = ((unsigned long long)rows[r].m1 << 32) | rows[r].m0;
+            asm volatile("" : "+s"(m));
+            hit |= m & blocks;
+        }
+        return hit == 0;
+    }
+    SVLN_DEV static void chain(const float* f, const f32x2* x2, Acc& acc) {
 #pragma unroll
         for (int e = 0; e < EPC; ++e) acc = fmaf(f[e], x2[e / 2][e % 2], acc);
+    }
+    // the step of a group without a fallback block: decode and multiply, nothing else
+    SVLN_DEV static void fma(const Row& r, const Chunk& w, const f32x2* x2, Acc& acc) {
+        float f[EPC];
+        p12_decode_f32(w.a.x, w.a.y, w.c, r.t0, r.t1, f);
+        chain(f, x2, acc);
+    }
+    // ... and of a group with one (0.2 % of the blocks of real weights, so this path may drain the stream).  A fallback block (a scalar
+    // branch) is fetched HERE, when the row's chain reaches it, from the bf16 original -- lane l's 16 bytes at element blk * 512 + 8 l
+    // of the row, below K for every active lane exactly as in WPlain -- and waited for at once; its zero packed bytes are never decoded.
+    // (the empty asm pins each chunk's products where they stand: left alone, the compiler moves every chain of the group behind the
+    // last branch and keeps all the decoded values in registers until then)
+    SVLN_DEV static void fma_checked(const Row& r, int ci, const Chunk& w, const f32x2* x2, Acc& acc) {
+        float f[EPC];
+        if (falls_back(r, w.blk)) {
+            unsigned off = ((unsigned)ci & 63u) << 4;
+            asm volatile("" : "+v"(off));           // (the address is formed here: hoisted, it is two registers per row held through the whole kernel)
+            chunk_to_f32<bf16>(load_nt((const uint8_t*)(r.W + (size_t)r.n * r.ldw) + (size_t)w.blk * 1024 + off), f);
+        } else p12_decode_f32(w.a.x, w.a.y, w.c, r.t0, r.t1, f);
+        chain(f, x2, acc);
+        asm volatile("" : "+v"(acc));
     }
     SVLN_DEV static float sum(Acc a) { return a; }
     SVLN_DEV static float row_scale(const GemvArgs&, size_t) { return 1.0f; }
 };
+// chunks per row in flight: two, unless the policy says otherwise (WP12: a chunk in flight is 3 registers, not 4)
+template <typename P, typename = void> struct StreamDepth { static constexpr bool OWN = false; static constexpr int ROWS = 2, KSPLIT = 2, ROWS_WG = 1, KS_WG = 1; };
+template <typename P> struct StreamDepth<P, decltype((void)P::DEPTH)> {
+    static constexpr bool OWN = true;
+    static constexpr int ROWS = P::DEPTH, KSPLIT = P::KS_DEPTH, ROWS_WG = P::ROWS_RESIDENT, KS_WG = P::KS_RESIDENT;
+};
+// acc[r] += w[d][r] . x[d] for the D chunk positions ci, ci + stride, ... of R rows, every row's chunks in ascending order.  WP12: all
+// loads of the step have been issued; only now the records are looked at (sched_barrier: the scalar test, and with it the wait for the
+// records, stays behind the loads), ONE wave-uniform branch per step: no fallback block among the D x R -> the plain decode, a basic
+// block of its own whose waits on the loads are counted; otherwise the checked form.  Every load of w is used on both sides, so none can
+// sink behind the branch.
+template <typename P, int R, int D>
+SVLN_DEV void consume(const typename P::Row (&rows)[R], int ci, int stride, const typename P::Chunk (&w)[D][R], const f32x2 (&x)[D][P::EPC / 2],
+                      typename P::Acc (&acc)[R]) {
+    if constexpr (std::is_same<P, WP12>::value) {
+        unsigned long long blocks = 0;
+#pragma unroll
+        for (int d = 0; d < D; ++d) blocks |= 1ull << w[d][0].blk;
+        __builtin_amdgcn_sched_barrier(0);
+        if (P::all_packed(rows, blocks)) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+#pragma unroll
+                for (int d = 0; d < D; ++d) P::fma(rows[r], w[d][r], x[d], acc[r]);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+#pragma unroll
+                for (int d = 0; d < D; ++d) P::fma_checked(rows[r], ci + d * stride, w[d][r], x[d], acc[r]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) P::fma(w[d][r], x[d], acc[r]);
+        }
+    }
+}
 
 // ------------------------------------------------------------------------------------------------ shared pieces
 // x in LDS as fp32, split in PLANES 16-byte planes per weight chunk so that consecutive lanes read consecutive 16 B (conflict-free):
@@ -351,6 +436,56 @@ SVLN_DEV void dot_accum(const typename P::Row (&rows)[R], const float* xs, const
     }
 }
 
+// the same over D chunks per row in flight (StreamDepth<P>: a policy with its own DEPTH), in the same ascending chunk order: a main loop
+// of D positions, then the remainders one by one.  The two-deep form above stays as it is for the policies that were tuned on it.
+// A step issues its loads and nothing else (sched_barrier) -- without LDS the raw activation chunks first: they are the oldest loads, so
+// unpacking them waits for them alone -- and only then turns to the activations and the products.
+template <typename P, int R, bool XLDS, int D>
+SVLN_DEV void deep_step(const typename P::Row (&rows)[R], const float* xs, const typename P::X* xg, int nch, int ci, int stride,
+                        typename P::Acc (&acc)[R]) {
+    using X = typename P::X;
+    constexpr int EPC = P::EPC, XEPC = Elt<X>::PER_CHUNK, XH = EPC / XEPC;
+    [[maybe_unused]] uint4 raw[D][XH];
+    if constexpr (!XLDS) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+#pragma unroll
+            for (int h = 0; h < XH; ++h) raw[d][h] = *(const uint4*)(xg + (size_t)(ci + d * stride) * EPC + h * XEPC);
+        }
+    }
+    typename P::Chunk w[D][R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) w[d][r] = P::load(rows[r], ci + d * stride);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    f32x2 x[D][EPC / 2];
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        if constexpr (XLDS) {
+            load_x<EPC / 4>(xs, nch, ci + d * stride, x[d]);
+        } else {
+#pragma unroll
+            for (int h = 0; h < XH; ++h) {
+                float fh[XEPC];
+                chunk_to_f32<X>(raw[d][h], fh);
+#pragma unroll
+                for (int e = 0; e < XEPC / 2; ++e) x[d][h * (XEPC / 2) + e] = f32x2{fh[2 * e], fh[2 * e + 1]};
+            }
+        }
+    }
+    consume<P, R, D>(rows, ci, stride, w, x, acc);
+}
+template <typename P, int R, bool XLDS, int D>
+SVLN_DEV void dot_accum_deep(const typename P::Row (&rows)[R], const float* xs, const typename P::X* xg, int nch, int c0, int cstep, int lane,
+                             typename P::Acc (&acc)[R]) {
+    const int stride = 64 * cstep;
+    int ci = c0 + lane;
+    for (; ci + (D - 1) * stride < nch; ci += D * stride) deep_step<P, R, XLDS, D>(rows, xs, xg, nch, ci, stride, acc);
+    for (; ci < nch; ci += stride) deep_step<P, R, XLDS, 1>(rows, xs, xg, nch, ci, stride, acc);
+}
+
 // bias / residual / store of output n
 template <typename X>
 SVLN_DEV void store_out(const GemvArgs& p, int n, float v) {
@@ -362,7 +497,7 @@ SVLN_DEV void store_out(const GemvArgs& p, int n, float v) {
 // ------------------------------------------------------------------------------------------------ wave-per-rows kernel
 // A wave takes groups of R = 4 weight rows: R consecutive outputs, or with EPI_SWIGLU the (gate, up) rows of 2 consecutive outputs.
 template <typename P, int EPI>
-__global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
+__global__ __launch_bounds__(GEMV_THREADS, StreamDepth<P>::ROWS_WG) void gemv_rows_kernel(GemvArgs p) {
     using X = typename P::X;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* xs = (float*)smem_raw;
@@ -412,7 +547,8 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
         typename P::Acc a[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) { rows[r] = P::row(p, rn[r]); a[r] = P::zero(); }
-        dot_accum<P, R, true>(rows, xs, nullptr, nch, 0, 1, lane, a);
+        if constexpr (!StreamDepth<P>::OWN) dot_accum<P, R, true>(rows, xs, nullptr, nch, 0, 1, lane, a);
+        else dot_accum_deep<P, R, true, StreamDepth<P>::ROWS>(rows, xs, nullptr, nch, 0, 1, lane, a);
         float acc[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] = wave_sum(P::sum(a[r])) * (P::row_scale(p, rn[r]) * xscale);
@@ -558,7 +694,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_rows_kernel(GemvArgs p) {
 // K share of x and g from global memory next to its weight chunks (L2-resident, 7 KB each).  No staging to hide the skip flag's load
 // behind: the kernel returns at once.
 template <typename P, bool NORM, int KW>
-__global__ __launch_bounds__(GEMV_THREADS) void gemv_ksplit_kernel(GemvArgs p) {
+__global__ __launch_bounds__(GEMV_THREADS, StreamDepth<P>::KS_WG) void gemv_ksplit_kernel(GemvArgs p) {
     using X = typename P::X;
     constexpr int R = P::KS_R, EPC = P::EPC;
     constexpr int RG = GEMV_WAVES / KW;             // row groups per workgroup
@@ -577,19 +713,19 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_ksplit_kernel(GemvArgs p) {
         for (int r = 0; r < R; ++r) { rows[r] = P::row(p, (size_t)min(n0 + r, p.N - 1)); a[r] = P::zero(); }
         float ss = 0.0f;
         if (!NORM && P::KS_PAIRED) {
-            dot_accum<P, R, false>(rows, nullptr, xg, nch, kw * 64, KW, lane, a);
+            if constexpr (!StreamDepth<P>::OWN) dot_accum<P, R, false>(rows, nullptr, xg, nch, kw * 64, KW, lane, a);
+            else dot_accum_deep<P, R, false, StreamDepth<P>::KSPLIT>(rows, nullptr, xg, nch, kw * 64, KW, lane, a);
         } else {
             for (int ci = kw * 64 + lane; ci < nch; ci += 64 * KW) {
-                typename P::Chunk w[R];
+                typename P::Chunk w[1][R];
 #pragma unroll
-                for (int r = 0; r < R; ++r) w[r] = P::load(rows[r], ci);
+                for (int r = 0; r < R; ++r) w[0][r] = P::load(rows[r], ci);
                 // all R weight loads are issued before anything else of the iteration: left alone, the scheduler sinks some of them
                 // below the norm arithmetic and waits for each in turn (seen in the e4m3 NORM form)
                 __builtin_amdgcn_sched_barrier(0);
-                f32x2 xf[EPC / 2];
-                ss = load_xg<P, NORM>(xg, gg, ci, xf, ss);
-#pragma unroll
-                for (int r = 0; r < R; ++r) P::fma(w[r], xf, a[r]);
+                f32x2 xf[1][EPC / 2];
+                ss = load_xg<P, NORM>(xg, gg, ci, xf[0], ss);
+                consume<P, R, 1>(rows, ci, 64 * KW, w, xf, a);
             }
         }
         // the accumulators stay R separate values: without this the SLP vectoriser, seeded by the R horizontal sums below, fuses the
