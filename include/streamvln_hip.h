@@ -232,8 +232,10 @@ int svln_sampling_truncation(svln_engine* h, int32_t top_k, float top_p);
  * svln_set_mxfp4_decode / svln_set_packed_decode (the lists are of their own lm_head formats), svln_set_fp8_gemm /
  * svln_set_fp8_scaled_mfma, the repetition penalty, svln_set_sampling, svln_set_allowed_tokens and graph replay (captured decode graphs
  * are keyed by k and dropped when it changes).  Refused: k outside 0 .. 8; a change while scheduler turns are in flight or a group is
- * pending; and, while k > 0, svln_generate_group / svln_turn_group (naming svln_top_logprobs: group turns carry no lists).  A forced
- * turn runs as before and produces no lists.  A call that changes nothing succeeds.
+ * pending; k > 0 while svln_token_entropy is on (naming it); and, while k > 0, svln_generate_group / svln_turn_group and the candidates
+ * forms (naming svln_top_logprobs: group turns carry no lists).  The scheduler and svln_generate_batch carry lists (svln_batch_topk,
+ * svln_generate_batch_topk).  A forced turn runs as before and produces no lists; a beam turn runs its own k = n_beams head.  A call
+ * that changes nothing succeeds, but for a pending group.  The rule table behind svln_mode_refusal is the reference for all of this.
  * svln_get_topk: the lists of the last single-env turn, ids [n_rows][k] int32 and logprobs [n_rows][k] fp32 (min(n_rows, cap_rows) rows
  * are written), read in the synchronisation that reads the ids; refused when k was 0 for that turn, after a forced turn, or before any. */
 int svln_top_logprobs(svln_engine* h, int k);
@@ -755,6 +757,33 @@ typedef struct svln_gemm_plan_out {
     svln_gemm_launch launch[2];
 } svln_gemm_plan_out;
 int svln_gemm_plan(const svln_gemm_problem* problem, svln_gemm_plan_out* plan);
+/* Which modes may be on together, and which turn forms run under them, without an engine and without a device: the ONE rule table every
+ * setter, the weight write and every turn form read (csrc/modes.h), which is the reference for every refusal the comments of this file
+ * mention.  A state is one 0 / 1 field per mode the rules read (topk: k > 0, truncation: top_k > 0, penalty: a factor != 1), jobs =
+ * scheduler turns in flight, group = a group turn is pending, on env group_env.  A caller is a number of the Caller enumeration of
+ * modes.h: a setter in one direction (where the directions differ), the weight write, a turn form; svln_mode_rule names it.
+ * svln_mode_refusal: *refused = 0 and an empty message, or 1 and the message the engine raises -- that of the caller's first violated
+ * rule, beginning with `who` (null: the caller's own name; svln_synth_tensor and the candidates forms pass theirs).  no_change != 0: the
+ * call would change nothing (on while on, off while off), where some setters return before some of their rules.
+ * svln_mode_rule: rule `index` of svln_mode_rule_count's n_rules, in table order: the caller and its name, the part (a caller whose
+ * rules are interrupted by an argument check asks part by part), the field index of the bit, whether the bit must be ON (else off),
+ * whether the rule holds for a no-change call, and the message as what + tail (static strings).
+ * Refused with a message: a null argument, an unknown caller, a message longer than cap - 1, an index outside the table. */
+typedef struct svln_mode_state {
+    int32_t decode_graph, persistent, fp8_decode, mxfp4_decode, mxfp4_batched, fp8_gemm, fp8_scaled, packed;
+    int32_t speculative, prefill_draft, batch_draft;
+    int32_t scores, topk, entropy, sampling, truncation, allowed;
+    int32_t penalty, jobs, group, group_env;
+} svln_mode_state;
+typedef struct svln_mode_rule_out {
+    int32_t caller, part, bit, must_be_on, on_no_change;
+    const char* caller_name;
+    const char* what;
+    const char* tail;
+} svln_mode_rule_out;
+int svln_mode_refusal(int caller, const char* who, const svln_mode_state* state, int no_change, char* message, int cap, int32_t* refused);
+int svln_mode_rule_count(int32_t* n_rules, int32_t* n_callers, int32_t* n_bits);
+int svln_mode_rule(int index, svln_mode_rule_out* out);
 /* the product behind svln_set_fp8_gemm: C [M][N] (bf16) = epi(a_scale[m] * w_scale[n] * (A8 [M][K] . W8 [N][K]^T) + bias) + res, e4m3 operands
  * (svln_op_quant_fp8 makes them), epi = EPI_NONE or EPI_SWIGLU, K % 16 == 0 */
 int svln_op_gemm_fp8(svln_engine* h, const void* A8, const float* a_scale, int lda, const void* W8, const float* w_scale, int ldw, void* C, int ldc,

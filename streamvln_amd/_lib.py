@@ -91,6 +91,54 @@ def gemm_plan(**problem) -> SvlnGemmPlan:
     return plan
 
 
+MODE_BITS = ("decode_graph", "persistent", "fp8_decode", "mxfp4_decode", "mxfp4_batched", "fp8_gemm", "fp8_scaled", "packed", "speculative",
+             "prefill_draft", "batch_draft", "scores", "topk", "entropy", "sampling", "truncation", "allowed", "penalty", "jobs", "group")
+
+# the Caller enumeration of csrc/modes.h, in order (svln_mode_refusal's `caller` is an index into it)
+MODE_CALLERS = ("set_decode_persistent:on", "set_decode_persistent:off", "set_fp8_decode:on", "set_fp8_decode:off", "set_mxfp4_decode:on",
+                "set_mxfp4_decode:off", "set_mxfp4_batched:on", "set_mxfp4_batched:off", "set_fp8_gemm:on", "set_fp8_gemm:off", "set_fp8_scaled_mfma",
+                "set_speculative:on", "set_speculative:off", "set_prefill_draft:on", "set_prefill_draft:off", "set_batch_draft:on",
+                "set_batch_draft:off", "set_token_scores:on", "set_token_scores:off", "top_logprobs:on", "top_logprobs:off", "token_entropy:on",
+                "token_entropy:off", "set_sampling:on", "set_sampling:off", "sampling_truncation:on", "sampling_truncation:off",
+                "set_allowed_tokens", "set_repetition_penalty", "weight_write", "generate_batch", "generate_group", "generate_beams",
+                "generate_forced", "batch_submit_forced", "generate_candidates", "op_gemv_batched_argmax")
+
+
+class SvlnModeState(C.Structure):
+    """svln_mode_state of include/streamvln_hip.h"""
+    _fields_ = [(n, C.c_int32) for n in MODE_BITS + ("group_env",)]
+
+
+class SvlnModeRule(C.Structure):
+    """svln_mode_rule_out of include/streamvln_hip.h"""
+    _fields_ = [(n, C.c_int32) for n in ("caller", "part", "bit", "must_be_on", "on_no_change")] + \
+               [(n, C.c_char_p) for n in ("caller_name", "what", "tail")]
+
+
+def mode_rules():
+    """the engine's mode rule table (csrc/modes.h) in order, as dicts (bit: its MODE_BITS name); no GPU needed"""
+    n, nc, nb = C.c_int32(), C.c_int32(), C.c_int32()
+    check(load().svln_mode_rule_count(C.byref(n), C.byref(nc), C.byref(nb)))
+    assert (nb.value, nc.value) == (len(MODE_BITS), len(MODE_CALLERS)), (nb.value, nc.value)
+    out = []
+    for i in range(n.value):
+        r = SvlnModeRule()
+        check(load().svln_mode_rule(i, C.byref(r)))
+        out.append({"caller": r.caller, "part": r.part, "bit": MODE_BITS[r.bit], "must_be_on": bool(r.must_be_on),
+                    "on_no_change": bool(r.on_no_change), "caller_name": r.caller_name.decode(), "text": (r.what + r.tail).decode()})
+    return out
+
+
+def mode_refusal(caller, on=(), no_change=False, who=None, group_env=0):
+    """svln_mode_refusal: None if `caller` (a MODE_CALLERS name or its index) is accepted while the MODE_BITS named in `on` are on, else the engine's message; no GPU needed"""
+    st = SvlnModeState(**{b: 1 for b in on}, group_env=group_env)
+    buf, refused = C.create_string_buffer(1024), C.c_int32()
+    if isinstance(caller, str):
+        caller = MODE_CALLERS.index(caller)
+    check(load().svln_mode_refusal(int(caller), who.encode() if who else None, C.byref(st), int(no_change), buf, len(buf), C.byref(refused)))
+    return buf.value.decode() if refused.value else None
+
+
 _P, _I, _F, _I64, _U64 = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64
 _PI32, _PI64, _PF, _PD = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_double)
 
@@ -227,6 +275,9 @@ SIGNATURES = {
     "svln_op_gemm_norm": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _F, _I, _I, _I, _I, _PI32]),
     "svln_op_gemm_norm_q8": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _F, _I, _I, _I, _I, _P, _P, _PI32]),
     "svln_gemm_plan": (_I, [C.POINTER(SvlnGemmProblem), C.POINTER(SvlnGemmPlan)]),
+    "svln_mode_refusal": (_I, [_I, C.c_char_p, C.POINTER(SvlnModeState), _I, C.c_char_p, _I, _PI32]),
+    "svln_mode_rule_count": (_I, [_PI32, _PI32, _PI32]),
+    "svln_mode_rule": (_I, [_I, C.POINTER(SvlnModeRule)]),
     "svln_op_gemv": (_I, [_P, _P, _I, _P, _P, _F, _P, _P, _P, _I, _I, _I, _PI32]),
     "svln_op_gemm_fp8": (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
     "svln_op_gemv_batched": (_I, [_P, _P, _I, _P, _I, _P, _F, _P, _P, _I, _P, _I, _I, _I, _I, _I, _PI32]),

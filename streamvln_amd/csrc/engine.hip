@@ -21,6 +21,7 @@
 #include "../../include/streamvln_hip.h"
 #include "common.h"
 #include "gemm_plan.h"
+#include "modes.h"
 #include "kernels.h"
 
 namespace svln {
@@ -757,10 +758,7 @@ public:
     // the written tensor follows it, on the engine stream behind the write -- the 12-bit packed copy, the e4m3 / MXFP4 copies of the
     // matrix if they are built (into the same buffers: the pointers stay, so captured graphs stay valid), and the feature cache, whose
     // entries are features of the old vision tower / projector.  Nothing on a turn's launch path reads a flag set here.
-    void before_weight_write(const char* who) {
-        refuse_while_jobs(who);
-        refuse_while_group(who);
-    }
+    void before_weight_write(const char* who) { refuse(C_WEIGHT_WRITE, who); }
     void after_weight_write(const Slot& s) {
         p12_encode(s.dst);
         requantise(s.dst);
@@ -850,19 +848,23 @@ public:
     void refuse_while_group_on(int env, const char* who) {
         REQUIRE(!(grp.pending && grp.env == env), std::string(who) + ": a group turn is pending on this env; choose its continuation with svln_group_select first");
     }
-    void refuse_while_group(const char* who) {
-        REQUIRE(!grp.pending, std::string(who) + " cannot change while a group turn is pending (svln_group_select)");
+    // Which modes may be on together and which turn forms run under them is ONE table (modes.h): every setter, the weight write and every
+    // turn form ask it here, with the state the engine is in, and hold no such rule themselves.  The hot paths keep reading the flags.
+    ModeState modes_now() const {
+        ModeState s;
+        s.set(M_DECODE_GRAPH, use_graph); s.set(M_PERSISTENT, persistent_on); s.set(M_FP8_DECODE, fp8_on); s.set(M_MXFP4_DECODE, mx4_on);
+        s.set(M_MXFP4_BATCHED, mx4b_on); s.set(M_FP8_GEMM, fp8_gemm_on); s.set(M_FP8_SCALED, fp8_scaled_on); s.set(M_PACKED, p12_on);
+        s.set(M_SPECULATIVE, spec_rows > 0); s.set(M_PREFILL_DRAFT, ride_on); s.set(M_BATCH_DRAFT, bdraft_on);
+        s.set(M_SCORES, scores_on); s.set(M_TOPK, topk > 0); s.set(M_ENTROPY, ent_on); s.set(M_SAMPLING, smp_on); s.set(M_TRUNCATION, trunc_k > 0);
+        s.set(M_ALLOWED, allow_on); s.set(M_PENALTY, rep_penalty != 1.0f);
+        for (int k = 0; k < MAXB; ++k) s.set(M_JOBS, jobs[k].used);
+        s.set(M_GROUP, grp.pending); s.group_env = grp.env;
+        return s;
     }
-    void refuse_while_any_group(const char* who) {
-        REQUIRE(!grp.pending, std::string(who) + ": a group turn is pending on env " + std::to_string(grp.env) + "; choose its continuation with svln_group_select first");
-    }
-    // the one "turns in flight" refusal of every setter and of a weight write: no env changes scheme, head or weights in the middle of a turn
-    void refuse_while_jobs(const char* who) {
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, std::string(who) + " cannot change while scheduler turns are in flight");
-    }
-    // ... and of the turn forms that run the scheduler's batched step themselves
-    void refuse_unless_idle(const char* who) {
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, std::string(who) + " needs an idle scheduler (turns are in flight)");
+    // who: the name the message begins with, where it is not the caller's own; part: see ModeRule
+    void refuse(Caller caller, const char* who = nullptr, bool no_change = false, int part = MODE_ALL_PARTS) const {
+        const std::string m = mode_refusal(caller, modes_now(), who ? who : CALLER_NAME[caller], no_change, part);
+        REQUIRE(m.empty(), m);
     }
     // the small lines every turn form shares: the results of the last single-env turn, the phase timers (events v0 v1 p0 p1 d1 of ph_ev,
     // read after a synchronisation), the check of the ids a synchronisation read
@@ -1554,12 +1556,9 @@ public:
     }
     void set_decode_persistent(int enable) override {
         if ((enable != 0) == persistent_on) return;        // nothing changes
-        refuse_while_jobs("svln_set_decode_persistent");
+        refuse(enable ? C_SET_DECODE_PERSISTENT_ON : C_SET_DECODE_PERSISTENT_OFF);
         HIP_CHECK(hipStreamSynchronize(st));
         if (!enable) { drop_graphs(); persistent_on = false; return; }
-        refuse_while_speculative("svln_set_decode_persistent");
-        refuse_while_scores("svln_set_decode_persistent");
-        refuse_while_sampling("svln_set_decode_persistent");
         if (!n_cus) { hipDeviceProp_t pr; HIP_CHECK(hipGetDeviceProperties(&pr, device)); n_cus = pr.multiProcessorCount; }
         DecodeLayerArgs a = layer_args(0);
         REQUIRE(decode_layer_supported<T>(a, n_cus), "persistent decode layer: this configuration is not supported (per-CU slices of hidden / inter / q|k|v "
@@ -1882,22 +1881,13 @@ public:
         for (int k = 0; k < 16; ++k) h_vctl[k] = 0;
         HIP_CHECK(hipStreamSynchronize(st));
     }
-    // The switches that change the numeric scheme or the execution form of a step.  single_scheme_on: those the single-env paths read
-    // (svln_generate's decode step and prefill) -- a forced turn, which runs on those paths only, refuses them.  spec_exclusive_on adds
-    // svln_set_mxfp4_batched, which the scheduler paths alone read: the three draft switches refuse all five, and all five refuse them.
-    bool single_scheme_on() const { return fp8_on || mx4_on || fp8_gemm_on || persistent_on; }
-    bool spec_exclusive_on() const { return single_scheme_on() || mx4b_on; }
     void set_speculative(int rows) override {
         if (rows == spec_rows) return;         // nothing changes
         REQUIRE(rows == 0 || rows == 2 || rows == 4 || rows == 8, "svln_set_speculative: rows must be 0 (off), 2, 4 or 8");
-        refuse_while_jobs("svln_set_speculative");
+        refuse(rows > 0 ? C_SET_SPECULATIVE_ON : C_SET_SPECULATIVE_OFF, nullptr, false, 0);
         if (rows > 0) {
-            refuse_while_scores("svln_set_speculative");
-            refuse_while_sampling("svln_set_speculative");
             REQUIRE(rows * (nq / nkv) <= 32, "svln_set_speculative: rows * (q_heads / kv_heads) must be <= 32 (the verify attention keeps 32 query rows per kv head)");
-            // a verify pass must compute each row in the numeric scheme of the single step it replaces
-            REQUIRE(!spec_exclusive_on(), "svln_set_speculative: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, "
-                                          "svln_set_fp8_gemm, svln_set_mxfp4_batched, svln_set_decode_persistent); switch it off first");
+            refuse(C_SET_SPECULATIVE_ON, nullptr, false, 1);       // a verify pass must compute each row in the numeric scheme of the single step it replaces
             set_speculative_buffers();
         }
         HIP_CHECK(hipStreamSynchronize(st));
@@ -1909,35 +1899,17 @@ public:
         draft_armed[env] = 0;
         return true;
     }
-    void refuse_while_speculative(const char* who) {
-        REQUIRE(spec_rows == 0, std::string(who) + ": draft-verified decode is on (svln_set_speculative); switch it off first");
-        REQUIRE(!ride_on, std::string(who) + ": drafts inside the prefill pass are on (svln_set_prefill_draft); switch them off first");
-        REQUIRE(!bdraft_on, std::string(who) + ": drafts in the scheduler's prefill pass are on (svln_set_batch_draft); switch them off first");
-    }
-    // the modes whose tokens come out of neither a scored nor a sampled arg-max: the three draft switches (their tokens leave the verify
-    // step, whose rule is written for greedy rows), the persistent decode layer and the batched MXFP4 weights (gemv_mx4b_kernel has the
-    // plain arg-max only).  svln_set_sampling, svln_set_token_scores and svln_generate_group (sampled by definition) share the list.
-    void refuse_while_plain_head_only(const char* who) {
-        refuse_while_speculative(who);
-        REQUIRE(!persistent_on, std::string(who) + ": the persistent decode layer is on (svln_set_decode_persistent); switch it off first");
-        REQUIRE(!mx4b_on, std::string(who) + ": the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
-    }
-    void refuse_while_sampling(const char* who) {
-        REQUIRE(!smp_on, std::string(who) + ": temperature sampling is on (svln_set_sampling); switch it off first");
-    }
-    // svln_set_sampling.  Refused with the modes whose tokens do not come out of a sampled arg-max: the three draft switches (their verify
-    // rule is written for greedy rows), the persistent decode layer and the batched MXFP4 weights (gemv_mx4b_kernel has no sampled form).
+    // svln_set_sampling.  Refused with the modes whose tokens do not come out of a sampled arg-max (modes.h: SVLN_PLAIN_HEAD_ONLY).
     // Every call, on or off, restarts the draw counters and drops the captured steps (seed and 1 / T are launch scalars).
     void set_sampling(int enable, float temperature, uint64_t seed) override {
         const bool want = enable != 0;
-        refuse_while_jobs("svln_set_sampling");
-        refuse_while_group("svln_set_sampling");
+        refuse(want ? C_SET_SAMPLING_ON : C_SET_SAMPLING_OFF, nullptr, false, 0);
         float inv_t = 1.0f;
         if (want) {
             REQUIRE(std::isfinite(temperature) && temperature > 0.0f, "svln_set_sampling: the temperature must be finite and > 0");
             inv_t = 1.0f / temperature;
             REQUIRE(std::isfinite(inv_t), "svln_set_sampling: 1 / temperature overflows fp32");
-            refuse_while_plain_head_only("svln_set_sampling");
+            refuse(C_SET_SAMPLING_ON, nullptr, false, 1);
         }
         HIP_CHECK(hipStreamSynchronize(st));
         drop_graphs();
@@ -1951,11 +1923,9 @@ public:
         REQUIRE(top_k >= 0 && top_k <= TOPK_C, "svln_sampling_truncation: top_k must be 0 (off) .. 8");
         REQUIRE(top_p > 0.0f && top_p <= 1.0f, "svln_sampling_truncation: top_p must lie in (0, 1]");
         REQUIRE(top_k > 0 || top_p >= 1.0f, "svln_sampling_truncation: top_p < 1 needs top_k = 1 .. 8 (the nucleus is taken over at most 8 listed ids)");
-        REQUIRE(top_k == 0 || !ent_on, "svln_sampling_truncation: token entropies are on (svln_token_entropy), whose epilogue has no candidate form; switch them off first");
-        refuse_while_group("svln_sampling_truncation");
-        refuse_while_jobs("svln_sampling_truncation");
-        if (top_k == trunc_k && top_p == trunc_p) return;      // nothing changes (off stays off whatever the switches are)
-        REQUIRE(smp_on, "svln_sampling_truncation: temperature sampling is off (svln_set_sampling); switch it on first");
+        const bool same = top_k == trunc_k && top_p == trunc_p;
+        refuse(top_k ? C_SAMPLING_TRUNCATION_ON : C_SAMPLING_TRUNCATION_OFF, nullptr, same);
+        if (same) return;                                      // nothing changes (off stays off whatever the switches are)
         REQUIRE((size_t)H * sizeof(float) <= (size_t)GEMV_ROWS_TOPK_MAX_LDS, "svln_sampling_truncation: the hidden size is too large for the candidate form of the lm_head GEMV");
         HIP_CHECK(hipStreamSynchronize(st));
         if (top_k) ensure_trunc_buffers();
@@ -2022,43 +1992,28 @@ public:
         a.seed_lo = (uint32_t)q.seed; a.seed_hi = (uint32_t)(q.seed >> 32); a.part_raw = raw; a.part_max = mx;
         return a;
     }
-    void refuse_while_scores(const char* who) {
-        REQUIRE(!scores_on, std::string(who) + ": token log-probabilities are on (svln_set_token_scores); switch them off first");
-    }
-    // svln_set_token_scores.  Refused with the modes whose tokens do not come out of a scored arg-max: the three draft switches (their
-    // tokens leave verify_step_kernel), the persistent decode layer and the batched MXFP4 weights (gemv_mx4b_kernel has no scored form).
+    // svln_set_token_scores.  Refused with the modes whose tokens do not come out of a scored arg-max (modes.h: SVLN_PLAIN_HEAD_ONLY);
+    // off is refused under the top-k lists and the entropies, which ride on the scored partials.
     void set_token_scores(int enable) override {
         const bool want = enable != 0;
-        refuse_while_group("svln_set_token_scores");
+        refuse(want ? C_SET_TOKEN_SCORES_ON : C_SET_TOKEN_SCORES_OFF, nullptr, want == scores_on);
         if (want == scores_on) return;         // nothing changes
-        REQUIRE(want || topk == 0, "svln_set_token_scores: top-k log-probabilities are on (svln_top_logprobs); switch them off first");
-        REQUIRE(want || !ent_on, "svln_set_token_scores: token entropies are on (svln_token_entropy); switch them off first");
-        refuse_while_jobs("svln_set_token_scores");
-        if (want) {
-            refuse_while_plain_head_only("svln_set_token_scores");
-        }
         HIP_CHECK(hipStreamSynchronize(st));
         drop_graphs();           // the captured lm_head / arg-max launches are the plain or the scored kernels
         scores_on = want;
     }
     // svln_top_logprobs.  The lists ride on the scored kernels' partials, so the scores must be on (and stay on): every mode the scores
-    // refuse is thereby unreachable.  Lists exist for single-env turns only: the scheduler, svln_generate_batch and group turns refuse
-    // while k > 0.
+    // refuse is thereby unreachable.  Single-env turns, the scheduler's jobs (Job::topk) and svln_generate_batch carry lists; group and
+    // candidates turns refuse while k > 0, beam and forced turns run their own head and ignore k (modes.h).
     void top_logprobs(int k) override {
         REQUIRE(k >= 0 && k <= TOPK_C, "svln_top_logprobs: k must be 0 (off) .. 8");
-        refuse_while_group("svln_top_logprobs");
+        refuse(k ? C_TOP_LOGPROBS_ON : C_TOP_LOGPROBS_OFF, nullptr, k == topk);
         if (k == topk) return;                 // nothing changes
-        refuse_while_jobs("svln_top_logprobs");
-        REQUIRE(k == 0 || scores_on, "svln_top_logprobs: token log-probabilities are off (svln_set_token_scores); switch them on first");
-        REQUIRE(k == 0 || !ent_on, "svln_top_logprobs: token entropies are on (svln_token_entropy), whose epilogue has no candidate form; switch them off first");
         REQUIRE(k == 0 || (size_t)H * sizeof(float) <= (size_t)GEMV_ROWS_TOPK_MAX_LDS, "svln_top_logprobs: the hidden size is too large for the candidate form of the lm_head GEMV");
         HIP_CHECK(hipStreamSynchronize(st));
         if (k) ensure_topk_buffers();
         drop_graphs();           // the captured lm_head launch is the sibling with or without candidates; the merge holds k
         topk = k;
-    }
-    void refuse_while_topk(const char* who) {
-        REQUIRE(topk == 0, std::string(who) + ": top-k log-probabilities are on (svln_top_logprobs), which group turns do not carry; switch them off first");
     }
     void get_topk(int32_t* ids, float* logprobs, int cap_rows, int32_t* n_rows, int32_t* k) override {
         REQUIRE(last_topk_valid, "svln_get_topk: top-k log-probabilities were off for the last turn (svln_top_logprobs), the last turn was forced, or no turn has run");
@@ -2086,21 +2041,12 @@ public:
     // form: refused both ways.  Group, beam, candidate and forced turns carry no entropies: refused while on.
     void token_entropy(int enable) override {
         const bool want = enable != 0;
-        refuse_while_group("svln_token_entropy");
+        refuse(want ? C_TOKEN_ENTROPY_ON : C_TOKEN_ENTROPY_OFF, nullptr, want == ent_on);
         if (want == ent_on) return;            // nothing changes
-        refuse_while_jobs("svln_token_entropy");
-        if (want) {
-            REQUIRE(scores_on, "svln_token_entropy: token log-probabilities are off (svln_set_token_scores); switch them on first");
-            REQUIRE(topk == 0, "svln_token_entropy: top-k log-probabilities are on (svln_top_logprobs), whose epilogue has no entropy form; switch them off first");
-            REQUIRE(trunc_k == 0, "svln_token_entropy: truncated sampling is on (svln_sampling_truncation), whose epilogue has no entropy form; switch it off first");
-        }
         HIP_CHECK(hipStreamSynchronize(st));
         if (want) ensure_ent_buffers();
         drop_graphs();           // the captured lm_head launch is the sibling with or without t; the merge is in the graph or not
         ent_on = want;
-    }
-    void refuse_while_entropy(const std::string& who) {
-        REQUIRE(!ent_on, who + ": token entropies are on (svln_token_entropy), which this turn form does not carry; switch them off first");
     }
     static void floats_out(const std::vector<float>& v, float* out, int cap, int32_t* n) {
         const int m = (int)v.size();
@@ -2186,8 +2132,7 @@ public:
         REQUIRE(n <= ALLOW_MAX, "svln_set_allowed_tokens: at most 256 ids");
         REQUIRE(n == 0 || ids, "svln_set_allowed_tokens: null id list with n > 0");
         if (n > 0) check_allowed_list("svln_set_allowed_tokens", ids, n, V);
-        refuse_while_jobs("svln_set_allowed_tokens");
-        refuse_while_group("svln_set_allowed_tokens");
+        refuse(C_SET_ALLOWED_TOKENS);
         std::vector<int> want(n);
         for (int k = 0; k < n; ++k) want[k] = (int)ids[k];
         if (want == allow_ids) return;         // the current list (or off while off): nothing changes
@@ -2257,13 +2202,8 @@ public:
     void set_batch_draft(int on) override {
         const bool want = on != 0;
         if (want == bdraft_on) return;         // nothing changes
-        refuse_while_jobs("svln_set_batch_draft");
+        refuse(want ? C_SET_BATCH_DRAFT_ON : C_SET_BATCH_DRAFT_OFF);      // a ridden row must be computed in the numeric scheme of the decode row it replaces
         if (want) {
-            refuse_while_scores("svln_set_batch_draft");
-            refuse_while_sampling("svln_set_batch_draft");
-            // a ridden row must be computed in the numeric scheme of the decode row it replaces
-            REQUIRE(!spec_exclusive_on(), "svln_set_batch_draft: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, "
-                                          "svln_set_fp8_gemm, svln_set_mxfp4_batched, svln_set_decode_persistent); switch it off first");
             REQUIRE(c.max_positions >= HEAD_ROWS + MAXB, "svln_set_batch_draft: max_positions too small");
         }
         HIP_CHECK(hipStreamSynchronize(st));
@@ -2280,13 +2220,8 @@ public:
     void set_prefill_draft(int on) override {
         const bool want = on != 0;
         if (want == ride_on) return;           // nothing changes
-        refuse_while_jobs("svln_set_prefill_draft");
+        refuse(want ? C_SET_PREFILL_DRAFT_ON : C_SET_PREFILL_DRAFT_OFF);      // a ridden row must be computed in the numeric scheme of the pass it replaces
         if (want) {
-            refuse_while_scores("svln_set_prefill_draft");
-            refuse_while_sampling("svln_set_prefill_draft");
-            // a ridden row must be computed in the numeric scheme of the pass it replaces
-            REQUIRE(!spec_exclusive_on(), "svln_set_prefill_draft: a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, "
-                                          "svln_set_fp8_gemm, svln_set_mxfp4_batched, svln_set_decode_persistent); switch it off first");
             REQUIRE(c.max_positions >= MAXB, "svln_set_prefill_draft: max_positions too small");
             set_speculative_buffers();
         }
@@ -2378,7 +2313,7 @@ public:
     // transformers 4.45.1 applies it under greedy decoding too).  1 = off (the default: no kernel sees a flag pointer).
     void set_repetition_penalty(float penalty) override {
         REQUIRE(penalty > 0.0f, "repetition_penalty must be > 0");
-        for (int k = 0; k < MAXB; ++k) REQUIRE(!jobs[k].used, "repetition_penalty cannot change while turns are in flight");
+        refuse(C_SET_REPETITION_PENALTY);
         HIP_CHECK(hipStreamSynchronize(st));
         if (penalty != 1.0f) ensure_pen_buffers();
         if (penalty != rep_penalty) {
@@ -2869,7 +2804,7 @@ public:
                         int32_t* n_out) override {
         REQUIRE(n_envs >= 1 && n_envs <= MAXB, "1..8 envs per batch");
         REQUIRE(max_new >= 1 && cap >= 1, "max_new_tokens must be >= 1");
-        refuse_unless_idle("svln_generate_batch");
+        refuse(C_GENERATE_BATCH);
         for (int s = 0; s < n_envs; ++s)
             for (int t = 0; t < s; ++t) REQUIRE(env_ids[t] != env_ids[s], "duplicate env in batch");
         for (int s = 0; s < n_envs; ++s) refuse_while_group_on(env_ids[s], "svln_generate_batch");
@@ -3115,13 +3050,7 @@ public:
     void group_refusals(int env, int n_seq) {
         env_at(env);
         REQUIRE(n_seq >= 2 && n_seq <= MAXB, "svln_generate_group: n_seq must be 2 .. 8");
-        refuse_while_topk("svln_generate_group");
-        refuse_while_entropy("svln_generate_group");
-        refuse_while_plain_head_only("svln_generate_group");     // (svln_set_sampling is refused under each of them: name the cause)
-        REQUIRE(smp_on, "svln_generate_group: temperature sampling is off (svln_set_sampling): greedy sequences would be identical");
-        REQUIRE(rep_penalty == 1.0f, "svln_generate_group: a repetition penalty != 1 is set (svln_set_repetition_penalty); a group does not support it");
-        refuse_unless_idle("svln_generate_group");
-        refuse_while_any_group("svln_generate_group");
+        refuse(C_GENERATE_GROUP);
     }
     // The plan of a turn form that shares one prefill: P cached rows, L rows in all, Tn = L - P rows to prefill, limit = min(max_new, cap)
     // ids after them (emitted or fed; the last one is never fed), q0 = the page L falls in, n_tail = the private pages of a fork from q0
@@ -3302,18 +3231,11 @@ public:
         const char* who = "svln_generate_beams";
         env_at(env);
         REQUIRE(W >= 1 && W <= BEAM_MAX_W, std::string(who) + ": n_beams must be 1 .. 8");
-        refuse_while_entropy(who);
-        REQUIRE(!smp_on, std::string(who) + ": temperature sampling is on (svln_set_sampling); beams are greedy: switch it off first");
+        refuse(C_GENERATE_BEAMS, who, false, 0);
         REQUIRE(!allow_on || allow_n >= W, std::string(who) + ": the allowed list (svln_set_allowed_tokens) is shorter than n_beams");
-        REQUIRE(rep_penalty == 1.0f, std::string(who) + ": a repetition penalty != 1 is set (svln_set_repetition_penalty); beams do not support it");
-        REQUIRE(!fp8_on, std::string(who) + ": the e4m3 decode weights are on (svln_set_fp8_decode); switch them off first");
-        REQUIRE(!mx4_on, std::string(who) + ": the MXFP4 decode weights are on (svln_set_mxfp4_decode); switch them off first");
-        REQUIRE(!fp8_gemm_on, std::string(who) + ": the fp8 MFMA products are on (svln_set_fp8_gemm); switch them off first");
-        REQUIRE(!persistent_on, std::string(who) + ": the persistent decode layer is on (svln_set_decode_persistent); switch it off first");
-        REQUIRE(!mx4b_on, std::string(who) + ": the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
+        refuse(C_GENERATE_BEAMS, who, false, 1);
         REQUIRE((size_t)H * sizeof(float) <= (size_t)GEMV_ROWS_TOPK_MAX_LDS, std::string(who) + ": the hidden size is too large for the candidate form of the lm_head GEMV");
-        refuse_unless_idle(who);
-        refuse_while_any_group(who);
+        refuse(C_GENERATE_BEAMS, who, false, 2);
     }
     void generate_beams(int env, int W, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, float* scores) override {
         const char* who = "svln_generate_beams";
@@ -3543,9 +3465,7 @@ public:
         REQUIRE(n_seq >= 2 && n_seq <= MAXB, std::string(who) + ": n_seq must be 2 .. 8");
         REQUIRE(ids && lens, std::string(who) + ": null id list / lengths");
         for (int g = 0; g < n_seq; ++g) REQUIRE(lens[g] >= 1 && lens[g] <= FORCED_MAX, std::string(who) + ": a sequence length (lens) must be 1 .. 32");
-        refuse_while_topk(who);
-        REQUIRE(!mx4b_on, std::string(who) + ": the batched MXFP4 weights are on (svln_set_mxfp4_batched): a scoring pass runs the batched step; switch them off first");
-        refuse_while_any_group(who);
+        refuse(C_GENERATE_CANDIDATES, who);
         int off = 0;
         for (int g = 0; g < n_seq; ++g) { forced_refusals(env, ids + off, lens[g], eos, n_eos, who); off += lens[g]; }
     }
@@ -3766,8 +3686,7 @@ public:
         merge_head(parts_b(), allow_n, 1, n, f, o);
     }
     // every refusal of a forced turn that needs no state of the env (svln_turn_forced checks them before it encodes a frame).  sched: the
-    // forced submit of the scheduler (svln_batch_submit_forced) -- no idle-scheduler line, and svln_set_mxfp4_batched is refused too: the
-    // decode rows a forced row stands in for would run MXFP4 products there while the prefill runs bf16 (the reason of svln_set_batch_draft)
+    // forced submit of the scheduler (svln_batch_submit_forced), whose mode rules are its own (modes.h: C_BATCH_SUBMIT_FORCED)
     void forced_refusals(int env, const int64_t* ids, int n, const int64_t* eos, int n_eos, const char* who_c = "svln_generate_forced", bool sched = false) {
         const std::string who(who_c);
         env_at(env);
@@ -3780,18 +3699,7 @@ public:
                 for (int q = 0; q < n_eos; ++q)
                     REQUIRE(eos[q] != ids[k], who + ": an id of the EOS set may only be the last one (an EOS is appended, never fed)");
         }
-        REQUIRE(rep_penalty == 1.0f, who + ": a repetition penalty != 1 is set (svln_set_repetition_penalty); its flags change row by row");
-        refuse_while_entropy(who);
-        // a forced row must be computed in the numeric scheme of the step it stands in for (the ride's list)
-        if (sched)
-            REQUIRE(!spec_exclusive_on(),
-                    who + ": a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm, "
-                          "svln_set_mxfp4_batched, svln_set_decode_persistent); switch it off first");
-        else
-            REQUIRE(!single_scheme_on(),
-                    who + ": a reduced-precision or persistent decode mode is on (svln_set_fp8_decode, svln_set_mxfp4_decode, svln_set_fp8_gemm, "
-                          "svln_set_decode_persistent); switch it off first");
-        if (!sched) refuse_unless_idle(who_c);
+        refuse(sched ? C_BATCH_SUBMIT_FORCED : C_GENERATE_FORCED, who_c);
         if (allow_on)
             for (int k = 0; k < n; ++k)
                 REQUIRE(std::binary_search(allow_ids.begin(), allow_ids.end(), (int)ids[k]),
@@ -4091,11 +3999,8 @@ public:
     }
     void set_fp8_decode(int enable) override {
         if ((enable != 0) == fp8_on) return;       // nothing changes
-        refuse_while_jobs("svln_set_fp8_decode");
+        refuse(enable ? C_SET_FP8_DECODE_ON : C_SET_FP8_DECODE_OFF);
         if (!enable) { drop_graphs(); fp8_on = false; return; }
-        refuse_while_speculative("svln_set_fp8_decode");
-        REQUIRE(!mx4_on, "svln_set_fp8_decode: the MXFP4 decode weights are on (svln_set_mxfp4_decode); switch them off first");
-        REQUIRE(!mx4b_on, "svln_set_fp8_decode: the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
         build_fp8_weights();
         drop_graphs();
         fp8_on = true;
@@ -4121,10 +4026,8 @@ public:
     }
     void set_mxfp4_decode(int enable) override {
         if ((enable != 0) == mx4_on) return;       // nothing changes
-        refuse_while_jobs("svln_set_mxfp4_decode");
+        refuse(enable ? C_SET_MXFP4_DECODE_ON : C_SET_MXFP4_DECODE_OFF);
         if (!enable) { drop_graphs(); mx4_on = false; return; }
-        refuse_while_speculative("svln_set_mxfp4_decode");
-        REQUIRE(!fp8_on, "svln_set_mxfp4_decode: the e4m3 decode weights are on (svln_set_fp8_decode); switch them off first");
         build_mxfp4_weights();
         drop_graphs();
         mx4_on = true;
@@ -4159,14 +4062,10 @@ public:
     void set_mxfp4_batched(int enable) override {
         if ((enable != 0) == mx4b_on) return;      // nothing changes
         // an env must not change scheme in the middle of a turn, in either direction
-        refuse_while_jobs("svln_set_mxfp4_batched");
+        refuse(enable ? C_SET_MXFP4_BATCHED_ON : C_SET_MXFP4_BATCHED_OFF, nullptr, false, 0);
         if (!enable) { drop_graphs(); mx4b_on = false; return; }
-        refuse_while_speculative("svln_set_mxfp4_batched");
-        refuse_while_scores("svln_set_mxfp4_batched");
-        refuse_while_sampling("svln_set_mxfp4_batched");
         REQUIRE(sizeof(T) == 2, "svln_set_mxfp4_batched: MXFP4 weights need the bf16 engine");
-        REQUIRE(!fp8_on, "svln_set_mxfp4_batched: the e4m3 decode weights are on (svln_set_fp8_decode); switch them off first");
-        REQUIRE(!fp8_gemm_on, "svln_set_mxfp4_batched: the e4m3 MFMA products are on (svln_set_fp8_gemm); switch them off first");
+        refuse(C_SET_MXFP4_BATCHED_ON, nullptr, false, 1);
         build_mxfp4_weights();
         drop_graphs();
         mx4b_on = true;
@@ -4177,10 +4076,8 @@ public:
     // Half the operand bytes per k through HBM / L2 / LDS.  Vision, attention, norms and the lm_head stay bf16.
     void set_fp8_gemm(int enable) override {
         if ((enable != 0) == fp8_gemm_on) return;  // nothing changes
-        refuse_while_jobs("svln_set_fp8_gemm");
+        refuse(enable ? C_SET_FP8_GEMM_ON : C_SET_FP8_GEMM_OFF);
         if (!enable) { fp8_gemm_on = false; return; }
-        refuse_while_speculative("svln_set_fp8_gemm");
-        REQUIRE(!mx4b_on, "svln_set_fp8_gemm: the batched MXFP4 weights are on (svln_set_mxfp4_batched); switch them off first");
         build_fp8_weights();
         if (!act8) {
             const size_t widest = (size_t)(I > nq * 128 ? I : nq * 128);
@@ -4195,7 +4092,7 @@ public:
     void set_fp8_scaled_mfma(int enable) override {
         if ((enable != 0) == fp8_scaled_on) return;
         REQUIRE(sizeof(T) == 2, "svln_set_fp8_scaled_mfma: the e4m3 products need the bf16 engine");
-        refuse_while_jobs("svln_set_fp8_scaled_mfma");
+        refuse(C_SET_FP8_SCALED_MFMA);
         fp8_scaled_on = enable != 0;
     }
     // C = A . W^T (+ epilogue) for an LLM linear: bf16 operands, or -- with svln_set_fp8_gemm -- the rows of A quantised on the fly
@@ -4514,7 +4411,7 @@ public:
         REQUIRE(a.epi != EPI_SWIGLU || a.N % 64 == 0, "SwiGLU needs N % 64 == 0 (32-row gate / up blocks)");
         a.part_val = part_val_b; a.part_idx = part_idx_b;
         // (argmax_rows follows the engine's switches: under svln_set_sampling it would sample on whatever rows d_smp last held)
-        REQUIRE(!(smp_on && a.epi == EPI_ARGMAX && !a.norm_w), "svln_op_gemv_batched: temperature sampling is on (svln_set_sampling); switch it off first, or use svln_op_gemv_batched_argmax_sample");
+        if (a.epi == EPI_ARGMAX && !a.norm_w) refuse(C_OP_GEMV_BATCHED_ARGMAX);
         if (a.epi == EPI_ARGMAX && !a.norm_w) argmax_rows(a.W, a.ldw, (const T*)a.x, a.ldx, a.N, a.K, a.B, false);      // the engine's own routing (MFMA tiles from B = 4)
         else launch_gemv_batched<T>(st, a);
         if (a.epi == EPI_ARGMAX) {
@@ -5856,6 +5753,37 @@ int svln_gemm_plan(const svln_gemm_problem* q, svln_gemm_plan_out* out) {
         o.reducer = l.reducer; o.reducer_block = l.rblock; o.reduce_too_large = l.reduce_too_large;
         for (int j = 0; j < 3; ++j) o.reducer_grid[j] = (int32_t)l.rgrid[j];
     }
+    API_END
+}
+// the fields of svln_mode_state are the bits of ModeBit, in order, then group_env
+static_assert(sizeof(svln_mode_state) == (M_COUNT + 1) * sizeof(int32_t), "svln_mode_state: one int32 per ModeBit, then group_env");
+int svln_mode_refusal(int caller, const char* who, const svln_mode_state* state, int no_change, char* message, int cap, int32_t* refused) {
+    API_BEGIN
+    REQUIRE(state && message && refused && cap >= 1, "svln_mode_refusal: null argument");
+    REQUIRE(caller >= 0 && caller < C_COUNT, "svln_mode_refusal: unknown caller");
+    const int32_t* f = &state->decode_graph;
+    ModeState s;
+    for (int b = 0; b < M_COUNT; ++b) s.set((ModeBit)b, f[b] != 0);
+    s.group_env = state->group_env;
+    const std::string m = mode_refusal((Caller)caller, s, who ? who : CALLER_NAME[caller], no_change != 0);
+    REQUIRE((int)m.size() < cap, "svln_mode_refusal: the message does not fit");
+    std::memcpy(message, m.c_str(), m.size() + 1);
+    *refused = !m.empty();
+    API_END
+}
+int svln_mode_rule_count(int32_t* n_rules, int32_t* n_callers, int32_t* n_bits) {
+    API_BEGIN
+    REQUIRE(n_rules && n_callers && n_bits, "svln_mode_rule_count: null argument");
+    *n_rules = mode_rows::N_RULES; *n_callers = C_COUNT; *n_bits = M_COUNT;
+    API_END
+}
+int svln_mode_rule(int index, svln_mode_rule_out* out) {
+    API_BEGIN
+    REQUIRE(out, "svln_mode_rule: null argument");
+    REQUIRE(index >= 0 && index < mode_rows::N_RULES, "svln_mode_rule: no such rule");
+    const ModeRule& r = mode_rows::RULES[index];
+    out->caller = r.caller; out->part = r.part; out->bit = r.bit; out->must_be_on = r.must_be_on; out->on_no_change = r.on_no_change;
+    out->caller_name = CALLER_NAME[r.caller]; out->what = r.what; out->tail = r.tail;
     API_END
 }
 int svln_op_gemv(svln_engine* h, const void* W, int ldw, const void* x, const void* norm_w, float eps, const void* bias, const void* res, void* y,

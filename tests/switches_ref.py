@@ -2,8 +2,8 @@
 tests/test_switches_inputs.py checks against include/streamvln_hip.h and tests/test_switch_pairs_gpu.py against the engine).
 
 A row is one `svln_set_*` switch of the C ABI, or one call-time mode (`svln_generate_group`, `svln_generate_forced`: their "on" is the
-call).  The matrix is DERIVED from the header text and the setters of engine.hip -- the rule that produces an entry stands beside it --
-and is total: PAIRS holds every unordered pair of rows exactly once.
+call).  The matrix is DERIVED from the header text and the rule table of csrc/modes.h -- the rule that produces an entry stands beside it;
+tests/test_mode_table.py compares the two without a GPU -- and is total: PAIRS holds every unordered pair of rows exactly once.
 
   REFUSED   with A on, switching B on (or making the call B) raises, and the message names A's C function; the same with the roles
             swapped.  Call-time modes leave nothing switched on behind them, so a pair with one is refused in the one order that exists
@@ -121,9 +121,9 @@ BASE_ON = ["packed_decode", "decode_graph", "draft"]          # packed_decode: t
 Entry = namedtuple("Entry", "kind names inert reason excluded")     # names: REFUSED -> {row on first: C function the message must name}
 
 DRAFT3 = ("speculative", "prefill_draft", "batch_draft")
-SCHEME5 = ("fp8_decode", "mxfp4_decode", "fp8_gemm", "mxfp4_batched", "decode_persistent")      # engine.hip spec_exclusive_on()
-PLAIN_HEAD = DRAFT3 + ("decode_persistent", "mxfp4_batched")                                     # engine.hip refuse_while_plain_head_only()
-SINGLE_SCHEME = ("fp8_decode", "mxfp4_decode", "fp8_gemm", "decode_persistent")                  # engine.hip single_scheme_on()
+SCHEME5 = ("fp8_decode", "mxfp4_decode", "fp8_gemm", "mxfp4_batched", "decode_persistent")      # csrc/modes.h SVLN_SCHEME5
+PLAIN_HEAD = DRAFT3 + ("decode_persistent", "mxfp4_batched")                                     # csrc/modes.h SVLN_PLAIN_HEAD_ONLY
+SINGLE_SCHEME = ("fp8_decode", "mxfp4_decode", "fp8_gemm", "decode_persistent")                  # csrc/modes.h SVLN_SCHEME4
 PERSISTENT_RUNS = ("decode_graph", "packed_decode", "repetition_penalty", "layer_taps")
 EXCLUDED_WHY = ("the persistent layer spins on inter-workgroup flags: a combination no test has run before is not tried first on a shared "
                 "machine (setter outcomes are still checked)")
@@ -146,7 +146,7 @@ def _build():
     def no_effect(other, who, reason):
         inert.setdefault(_key(other, who), Entry(NO_EFFECT, None, who, reason, None))
 
-    # -- refusals between setters (each holds in both orders: every setter of a refused pair checks the other's flag)
+    # -- refusals between setters (each holds in both orders: each setter's "on" caller has a row for the other's bit)
     for d in DRAFT3:
         for s in SCHEME5:                # a verify pass / ridden row must be computed in the scheme of the step it replaces
             refuse(d, s)
