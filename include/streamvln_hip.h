@@ -658,6 +658,39 @@ int svln_set_prefill_draft(svln_engine* h, int on);
 /* Counters since the last reset: rides run, tokens they emitted (the turn's token 0 included), draft rows they fed (the k's summed).
  * svln_draft_stats keeps its meaning: a token emitted by a ride counts in none of its three counters.  Any pointer may be null. */
 int svln_prefill_draft_stats(svln_engine* h, int64_t* rides, int64_t* tokens_from_rides, int64_t* rows_fed, int reset);
+/* MULTI-DRAFT turns, no switch, no reference counterpart: svln_generate with hints -- n_drafts <= 8 guessed id sequences D_0 .. D_{G-1}
+ * of THIS turn (ids = the sequences back to back, lens[g] = 0 .. 32 ids each), all verified by ONE prefill pass.  Ids, the EOS / max_new
+ * stop, the cache length and every getter are svln_generate's on the same state; no guess can change a greedy output: every emitted token
+ * is the arg-max of a row that was fed the true prefix.  fp32 engine: ids identical on the fixtures; bf16 engine: a near-tie arg-max may
+ * fall the other way, because a product's row count selects its plan (as under svln_set_prefill_draft).
+ *   plan    r = min(32 / (q_heads / kv_heads), 32 / G) row slots per draft.  Draft g feeds k_g = min(len D_g, r, tokens the call may emit
+ *           - 1, max_positions - L) ids, cut at the first id outside the vocabulary and at the first id in the EOS set (an EOS id is
+ *           compared, never fed).  Trailing drafts are dropped one at a time while the row workspace (Tn + G r rows within max_positions)
+ *           or the free pages (the env's pages up to L + k_0, plus the fork tails of drafts 1 ..) fall short, possibly down to none.  A
+ *           draft with k_g = 0 feeds nothing and takes no page.  Duplicates are not merged.
+ *   pass    the row layout of svln_generate_candidates_folded: M = Tn + G r rows, row Tn + g r + j = the embedding of D_g[j], sequence 0
+ *           on the env's own page table, sequence g >= 1 on a fork whose first private page mirrors the prompt's last page (L % 64 != 0).
+ *   head    one indexed final norm of the prompt's last row (once) and of the fed rows, the lm_head arg-max in chunks of <= 32 rows in the
+ *           form the switches ask for (token scores, an allowed list), then ONE select launch: per draft the verify rule of
+ *           svln_set_speculative on [row 0, rows of g] from zero emitted tokens; the largest emitted count wins, a tie goes to the lowest g.
+ *   after   one synchronisation; the winner's private pages become the env's, every other fork page and the env's displaced pages go back
+ *           to the pool, no group is left pending.  A finished turn returns with no decode launch; otherwise single decode steps finish
+ *           it (no verify passes behind a multi-draft pass).
+ * Hints are IGNORED -- the call is then svln_generate launch for launch and bit for bit, never a refusal -- with svln_set_sampling on, a
+ * repetition penalty != 1, svln_set_fp8_decode / svln_set_mxfp4_decode / svln_set_fp8_gemm / svln_set_decode_persistent on,
+ * svln_top_logprobs k > 0, svln_token_entropy on, svln_set_token_scores together with svln_set_allowed_tokens, a group turn pending on
+ * another env (its forks hold the one fork scaffold), or no draft with a usable first id.  Everything svln_generate refuses is refused the same way; an armed svln_set_draft draft is consumed and not used.  Argument
+ * faults are refused by name before any launch: n_drafts outside 0 .. 8, a length outside 0 .. 32, a null pointer.
+ * *winner_out (optional) = the winning draft, -1 when no pass ran; *pass_tokens_out (optional) = the tokens the pass emitted (0 then). */
+int svln_generate_drafts(svln_engine* h, int env, int n_drafts, const int64_t* ids, const int32_t* lens, int max_new_tokens,
+                         const int64_t* eos_ids, int n_eos, int64_t* out_ids, int out_cap, int32_t* n_out, int32_t* winner_out,
+                         int32_t* pass_tokens_out);
+/* svln_turn's bookkeeping (encode, window / episode resets, splice), then svln_generate_drafts, in one crossing */
+int svln_turn_drafts(svln_engine* h, const svln_turn_args* a, int n_drafts, const int64_t* ids, const int32_t* lens, int64_t* out_ids, int out_cap,
+                     int32_t* n_out, int32_t* kv_len, int32_t* winner_out, int32_t* pass_tokens_out);
+/* Counters of the multi-draft calls since the engine was created, out[8]: calls, passes run, tokens the passes emitted (token 0 included),
+ * draft rows fed, turns finished in the pass, calls whose hints were ignored, page handovers (winner >= 1), tokens of single steps. */
+int svln_drafts_stats(svln_engine* h, int64_t* out);
 /* Opt-in, default off, no reference counterpart: drafts in the prefill pass of the multi-env scheduler (svln_batch_submit /
  * svln_batch_step / svln_generate_batch) -- a lockstep turn whose drafts are all right is ONE scheduler iteration.  Independent of
  * svln_set_speculative and svln_set_prefill_draft, which the scheduler goes on ignoring.  With the switch on, svln_batch_submit consumes
@@ -1014,6 +1047,21 @@ int svln_op_attention_verify_multi(svln_engine* h, int n_seq, int rows_max, cons
  * ids in emitted[0 .. *new_count - count) (the rest of emitted[rows] = -3) and *next_token (the last emitted token; -3 when none). */
 int svln_op_verify_step(svln_engine* h, int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos,
                         int n_eos, int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token);
+/* TEST-ONLY: one launch of draft_select_kernel (the select step of svln_generate_drafts) on caller-given host arrays: k[G] rows per draft,
+ * fed[G][r] the ids the row slots were fed, cand[1 + sum k] the head rows' arg-maxes (row 0 = the prompt's last row, then the rows of
+ * draft 0, 1, ...), cand_score (optional, with scores) their log-probabilities; the GenCtl start state pos, kv_len, done, count, max_new;
+ * eos[n_eos].  Final-norm row q holds q + 1 + (column % 4) / 4 in every column.  Before the launch every output is filled with a
+ * sentinel: out_ids[rows] -7, scores[rows] NaN, *last_token -7, rec[4] -7, the tap rows -1; stats[2] is read and written (passes, tokens).
+ * Afterwards ctl_out[8] = the final GenCtl, rec = {winner, emitted, stop, head rows read}, taps [tap_rows][hidden] = the first tap rows.
+ * Refused before any launch: G outside 1 .. 8, r < 1 or 1 + G r > 33, a k outside 0 .. r, count < 0 or count + r + 1 > rows, rows beyond
+ * the engine's id buffer, n_eos beyond its EOS buffer, cand_score without scores or the reverse, more than 64 tap rows, a null array.
+ * The engine's own d_ctl, d_out_ids, d_scores and d_token are restored afterwards. */
+typedef struct svln_draft_select_op {
+    const int32_t* k; const int32_t* fed; const int32_t* cand; const float* cand_score; const int64_t* eos;
+    int32_t* ctl_out; int32_t* out_ids; int32_t* last_token; float* scores; int32_t* rec; int32_t* stats; float* taps;
+    int32_t G, r, pos, kv_len, done, count, max_new, n_eos, rows, tap_rows;
+} svln_draft_select_op;
+int svln_op_draft_select(svln_engine* h, const svln_draft_select_op* op);
 /* TEST-ONLY: `steps` launches of the greedy loop's step kernel (launch_argmax_step; use_ctl = 0: ONE launch_argmax_final on set 0) on
  * caller-given host partials, enqueued back to back with no host synchronisation between them; launch s reads partial set s.
  *   part_val / part_idx [steps][n]; part_sum (optional: the scored merge), part_raw / part_max (optional, both or neither, with

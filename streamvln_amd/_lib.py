@@ -71,6 +71,13 @@ class SvlnArgmaxStepOp(C.Structure):
                [(n, C.c_int32) for n in ("n", "steps", "use_ctl", "pos", "kv_len", "done", "count", "max_new", "n_eos", "flag_bytes", "rows")]
 
 
+class SvlnDraftSelectOp(C.Structure):
+    """svln_draft_select_op of include/streamvln_hip.h"""
+    _fields_ = [(n, C.c_void_p) for n in ("k", "fed", "cand", "cand_score", "eos", "ctl_out", "out_ids", "last_token", "scores", "rec",
+                                          "stats", "taps")] + \
+               [(n, C.c_int32) for n in ("G", "r", "pos", "kv_len", "done", "count", "max_new", "n_eos", "rows", "tap_rows")]
+
+
 class SvlnDecodeLayerWalkOp(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("elem_size", "K", "nrows", "pair", "first")]
 
@@ -261,6 +268,10 @@ SIGNATURES = {
     "svln_draft_stats": (_I, [_P, _PI64, _PI64, _PI64, _I]),
     "svln_set_prefill_draft": (_I, [_P, _I]),
     "svln_prefill_draft_stats": (_I, [_P, _PI64, _PI64, _PI64, _I]),
+    "svln_generate_drafts": (_I, [_P, _I, _I, _PI64, _PI32, _I, _PI64, _I, _PI64, _I, _PI32, _PI32, _PI32]),
+    "svln_turn_drafts": (_I, [_P, C.POINTER(SvlnTurnArgs), _I, _PI64, _PI32, _PI64, _I, _PI32, _PI32, _PI32, _PI32]),
+    "svln_drafts_stats": (_I, [_P, _PI64]),
+    "svln_op_draft_select": (_I, [_P, C.POINTER(SvlnDraftSelectOp)]),
     "svln_set_batch_draft": (_I, [_P, _I]),
     "svln_batch_draft_stats": (_I, [_P, _PI64, _PI64, _PI64, _PI64, _PI64, _I]),
     "svln_set_memory_prune": (_I, [_P, _I]),

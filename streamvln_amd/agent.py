@@ -42,6 +42,15 @@ def parse_actions(output: str) -> List[int]:
     return list(itertools.chain.from_iterable(ACTIONS2IDX[m] for m in matches))
 
 
+def update_draft_history(history, ids, cap: int = 8):
+    """The draft history of an env after a turn that emitted `ids`: the env's distinct turn outputs, most recent first, at most `cap`.
+    A pure function: `history` (a list of id lists) is not changed."""
+    ids = [int(t) for t in ids]
+    if not ids:
+        return [list(h) for h in history][:cap]
+    return ([ids] + [list(h) for h in history if list(h) != ids])[:cap]
+
+
 class StreamingAgent:
     """Stateful single-env agent.  `prompt_encoder(first_turn, with_memory, instruction)`
     returns the new turn's token ids (with -200/-300 sentinels); `decode_actions(ids)` turns the
@@ -58,6 +67,9 @@ class StreamingAgent:
         self.do_sample, self.temperature = bool(do_sample), temperature
         # act_candidates: let the candidates' first rows ride the prefill pass (model.generate(fold_candidates=True)); set it on the agent
         self.fold_candidates = False
+        # multi-draft turns (model.generate(draft_set=...)): G > 0 passes the env's G most recent distinct turn outputs as this turn's
+        # guesses; 0 = off.  Set it on the agent; the actions are the plain agent's either way
+        self.draft_history = 0
         self.prompt_encoder = prompt_encoder
         self.num_frames, self.num_future_steps, self.num_history = num_frames, num_future_steps, num_history
         self.env_id, self.device, self.image_dtype = env_id, device, image_dtype
@@ -82,6 +94,7 @@ class StreamingAgent:
         self.action_seq: List[int] = []
         self.output_ids = None
         self.past_key_values = None
+        self.turn_history: List[List[int]] = []            # the env's distinct turn outputs, most recent first (draft_history)
         # model confidence of the last model turn (model.set_token_scores): log-probability of every emitted id [1, n_new] and their sum,
         # the joint log-probability of the turn; None when the model provides no scores
         self.last_token_logprobs = None
@@ -173,7 +186,14 @@ class StreamingAgent:
         req = self._build_request(instruction, env_id)
         if forced_ids is not None:
             req["forced_ids"] = forced_ids
-        return self._consume(self.model.generate(**req))
+        G = int(getattr(self, "draft_history", 0) or 0)
+        if G <= 0:
+            return self._consume(self.model.generate(**req))
+        if forced_ids is None:
+            req["draft_set"] = [list(h) for h in self.turn_history[:G]]
+        out = self.model.generate(**req)
+        self.turn_history = update_draft_history(self.turn_history, out.sequences.reshape(-1).tolist())
+        return self._consume(out)
 
     def _turn_candidates(self, instruction: str, candidate_ids, select=None, env_id: Optional[int] = None):
         """the model turn as a candidates call (model.generate(candidate_ids=...)): every candidate is scored against one prefill, the

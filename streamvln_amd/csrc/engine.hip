@@ -200,6 +200,12 @@ struct EngineBase {
     virtual void op_verify_step(int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos, int n_eos,
                                 int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token) = 0;
     virtual void op_argmax_step(const svln_argmax_step_op& q) = 0;
+    virtual void generate_drafts(int env, int n_drafts, const int64_t* ids, const int32_t* lens, int max_new, const int64_t* eos, int n_eos,
+                                 int64_t* out, int cap, int32_t* n_out, int32_t* winner_out, int32_t* pass_tokens_out) = 0;
+    virtual void turn_drafts(const svln_turn_args& a, int n_drafts, const int64_t* ids, const int32_t* lens, int64_t* out, int cap,
+                             int32_t* n_out, int32_t* kv_len, int32_t* winner_out, int32_t* pass_tokens_out) = 0;
+    virtual void drafts_stats(int64_t* out8) = 0;
+    virtual void op_draft_select(const svln_draft_select_op& q) = 0;
     virtual void op_dead_step(int done, char* report, int report_cap, int32_t* n_changed) = 0;
     virtual bool op_gemm_fp8(const GemmArgs& a) = 0;
     virtual void set_memory_prune(int keep) = 0;
@@ -2854,18 +2860,21 @@ public:
     // one is in the EOS set (appended, not fed) or max_new_tokens.  The loop state lives on the device (GenCtl): the prefill, its
     // arg-max and RUN_AHEAD decode steps are enqueued back to back, then ONE synchronisation reads the ids emitted so far; steps
     // enqueued past the end of the generation are no-ops (every kernel checks the done flag).
-    void generate(int env, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, bool fixed) override {
+    // What svln_generate and svln_generate_drafts do before their first launch: the refusals, the armed draft (consumed by the call whether
+    // it helps, is ignored or the call fails) and the EOS set on the device.  limit = the tokens the call may emit.
+    struct GenBegin { bool had_draft; int P, L, Tn, limit; };
+    GenBegin gen_begin(int env, int max_new, const int64_t* eos, int n_eos, int cap) {
         Env& e = env_at(env);
         refuse_while_group_on(env, "svln_generate");
         invalidate_last_results();
-        const bool had_draft = disarm_draft(env);      // consumed by this call whether it helps, is ignored or the call fails
+        GenBegin b;
+        b.had_draft = disarm_draft(env);
         REQUIRE(weights_missing() == 0, g_err);
-        const int P = e.kv_len, L = e.n_embeds, Tn = L - P;
-        REQUIRE(Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
+        b.P = e.kv_len; b.L = e.n_embeds; b.Tn = b.L - b.P;
+        REQUIRE(b.Tn >= 1, "nothing to prefill: inputs_embeds not longer than the KV cache");
         REQUIRE(max_new >= 1 && cap >= 1, "max_new_tokens must be >= 1");
-        if (fixed) n_eos = 0;
         REQUIRE(n_eos >= 0 && n_eos <= (V > 16 ? V : 16), "too many eos ids");
-        const int limit = max_new < cap ? max_new : cap;                     // tokens this call may emit
+        b.limit = max_new < cap ? max_new : cap;
         {   // EOS set -> device (cached across calls: the harness passes the same list every turn)
             std::vector<int> ev(n_eos);
             for (int k = 0; k < n_eos; ++k) ev[k] = eos[k] >= 0 && eos[k] < V ? (int)eos[k] : -2;      // ids outside the vocabulary never match
@@ -2876,6 +2885,23 @@ public:
                 eos_valid = true;
             }
         }
+        return b;
+    }
+    // the loop state of a turn that has emitted nothing: the first decode step feeds token 0 at position L (pos / kv_len advance when the
+    // arg-max step appends without stopping); the penalty flags of the previous turn's tokens are cleared first
+    void gen_ctl_start(int env, int L, int limit, int n_eos) {
+        h_ctl->pos = L - 1; h_ctl->kv_len = L; h_ctl->done = 0; h_ctl->count = 0; h_ctl->max_new = limit; h_ctl->n_eos = n_eos;
+        h_ctl->draw0 = smp_on ? env_draws[env] : 0; h_ctl->stream = smp_on ? env : 0;
+        if (rep_penalty != 1.0f)      // tokens of the previous generate (still listed in d_out_ids[0 .. d_ctl.count)) no longer count
+            launch_set_flags(st, pen_flags, d_out_ids, &d_ctl->count, 0, 0);
+        HIP_CHECK(hipMemcpyAsync(d_ctl, h_ctl, sizeof(GenCtl), hipMemcpyHostToDevice, st));
+    }
+    void generate(int env, int max_new, const int64_t* eos, int n_eos, int64_t* out, int cap, int32_t* n_out, bool fixed) override {
+        Env& e = env_at(env);
+        if (fixed) n_eos = 0;
+        const GenBegin gb = gen_begin(env, max_new, eos, n_eos, cap);
+        const bool had_draft = gb.had_draft;
+        const int P = gb.P, L = gb.L, Tn = gb.Tn, limit = gb.limit;
         // the env's armed draft is consumed by this call whether or not it helps; usable: a draft mode is on, no repetition penalty (its
         // flags change the logits token by token), ids in the vocabulary (the first one outside ends the draft); verify passes need a guess
         // beyond index 0, a ride is served by index 0 alone
@@ -2909,12 +2935,7 @@ public:
             HIP_CHECK(hipMemcpyAsync(d_draft, h_draft, (size_t)dlen * sizeof(int), hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemcpyAsync(d_vctl, h_vctl, 16 * sizeof(int), hipMemcpyHostToDevice, st));
         }
-        // the first decode step feeds token 0 at position L: pos / kv_len advance when the arg-max step appends without stopping
-        h_ctl->pos = L - 1; h_ctl->kv_len = L; h_ctl->done = 0; h_ctl->count = 0; h_ctl->max_new = limit; h_ctl->n_eos = n_eos;
-        h_ctl->draw0 = smp_on ? env_draws[env] : 0; h_ctl->stream = smp_on ? env : 0;
-        if (rep_penalty != 1.0f)      // tokens of the previous generate (still listed in d_out_ids[0 .. d_ctl.count)) no longer count
-            launch_set_flags(st, pen_flags, d_out_ids, &d_ctl->count, 0, 0);
-        HIP_CHECK(hipMemcpyAsync(d_ctl, h_ctl, sizeof(GenCtl), hipMemcpyHostToDevice, st));
+        gen_ctl_start(env, L, limit, n_eos);
         HIP_CHECK(hipEventRecord(ph_ev[2], st));
         if (ride) {
             prefill(e, P, Tn + k_ride, k_ride);
@@ -2985,6 +3006,14 @@ public:
             vtokens = h_vctl[3];
             st_passes += h_vctl[2];
         }
+        finish_turn(e, env, L, limit, enq, n, done, decoded, vtokens, ride ? rtokens : 1, ride, out, n_out);
+    }
+    // The rest of a single-env turn, shared by svln_generate and svln_generate_drafts: single decode steps until the turn is done (enq =
+    // tokens whose arg-max step has been enqueued, n / done = what the last synchronisation read, if any), then the results: ids, scores,
+    // lists, e.kv_len, the phase timers, n_generated, the draft counters and top2_stale.  vtokens: tokens of verify passes; head_tokens:
+    // tokens the prefill pass itself emitted (1 without a draft); drafted: the pass carried draft rows.  Returns the single-step tokens.
+    int finish_turn(Env& e, int env, int L, int limit, int enq, int n, bool done, bool decoded, int vtokens, int head_tokens, bool drafted,
+                    int64_t* out, int32_t* n_out) {
         while (!done) {
             int steps = limit - enq;
             if (steps > RUN_AHEAD) steps = RUN_AHEAD;
@@ -3037,12 +3066,13 @@ public:
         settle_vision();
         if (decoded) add_phase(2, 3, 4);
         n_generated = n;
-        const int singles = n - vtokens - (ride ? rtokens : 1);      // (the prefill's own token counts in none of the draft counters)
+        const int singles = n - vtokens - head_tokens;      // (the prefill's own token counts in none of the draft counters)
         st_vtokens += vtokens; st_single += singles;
-        top2_stale = (vtokens > 0 || ride) && singles == 0;
+        top2_stale = (vtokens > 0 || drafted) && singles == 0;
         top2_sampled = smp_on;
         if (smp_on) env_draws[env] += n;
         *n_out = n;
+        return singles;
     }
 
     // ------------------------------------------------------------------------------- group sampling (svln_generate_group)
@@ -3631,6 +3661,181 @@ public:
         });
         generate_candidates_folded(a.env, n_seq, ids, lens, a.eos_ids, a.n_eos, logprobs, greedy_ids, greedy_logprobs);
     }
+    // ------------------------------------------------------------------------------- multi-draft turns (svln_generate_drafts)
+    // svln_generate with hints: up to 8 guessed id sequences of this turn ride ONE prefill pass in the folded candidates call's row layout
+    // (Fold: sequence g on its own page table, page q0 mirrored into the forks), one indexed final norm and the arg-max head score the
+    // prompt's last row and every fed row, draft_select_kernel applies the verify rule to every branch and picks the winner, the host
+    // hands the winner's pages to the env and the single-step loop of svln_generate finishes the turn.  Every emitted token is the arg-max
+    // of a row that was fed the true prefix, so no guess changes a greedy output.  Hints that cannot be used are ignored: the call is then
+    // svln_generate itself.
+    static constexpr int DRAFTS_MAX = MAXB, DRAFT_LEN_MAX = 32;
+    int* d_dsel = nullptr; int* h_dsel = nullptr;      // [0 .. 8) k_g, [8 .. 12) the result record, [12], [13] passes / tokens (device counters)
+    // calls, passes, tokens from passes, rows fed, turns finished in the pass, calls ignored, page handovers (winner >= 1), single steps
+    int64_t st_drafts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    void ensure_dsel_buffers() {
+        if (d_dsel) return;
+        d_dsel = dalloc<int>(16, true);
+        HIP_CHECK(hipHostMalloc((void**)&h_dsel, 16 * sizeof(int)));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    // The plan: how many of the drafts ride (G, trailing ones dropped while the row workspace or the free pages fall short, possibly to 0 =
+    // the plain turn) and how many ids k[g] each feeds.  A pure function of the arguments and the env's counts; nothing is changed.
+    struct DraftPlan { int G = 0, r = 0, k[DRAFTS_MAX] = {0}; };
+    DraftPlan plan_drafts(const Env& e, int n_drafts, const int64_t* ids, const int32_t* lens, int limit, const int64_t* eos, int n_eos) const {
+        DraftPlan p;
+        const int L = e.n_embeds, Tn = L - e.kv_len;
+        if (Tn < 1 || limit < 1) return p;            // (svln_generate refuses the call)
+        for (int G = n_drafts; G >= 1; --G) {
+            const int r = cand_rows_per_pass(G);
+            int k[DRAFTS_MAX] = {0}, off = 0;
+            int64_t need = 0;
+            for (int g = 0; g < G; ++g) {
+                int kg = std::max(std::min(std::min((int)lens[g], r), std::min(limit - 1, c.max_positions - L)), 0);
+                for (int j = 0; j < kg; ++j) {
+                    const int64_t id = ids[off + j];
+                    bool cut = id < 0 || id >= V;                       // an id outside the vocabulary ends the draft
+                    for (int q = 0; q < n_eos && !cut; ++q) cut = eos[q] == id;      // an EOS id is compared, never fed
+                    if (cut) { kg = j; break; }
+                }
+                k[g] = kg; off += lens[g];
+                need += g == 0 ? std::max((L + kg + PAGE - 1) / PAGE - e.n_pages, 0) : fork_tail_pages(L, kg + 1);
+            }
+            if ((int64_t)Tn + (int64_t)G * r > c.max_positions || need > (int64_t)free_pages.size()) continue;
+            p.G = G; p.r = r;
+            for (int g = 0; g < G; ++g) p.k[g] = k[g];
+            break;
+        }
+        int fed = 0;
+        for (int g = 0; g < p.G; ++g) fed += p.k[g];
+        if (fed == 0) p.G = 0;                        // no draft with a usable first id
+        return p;
+    }
+    void drafts_arg_check(const char* who_c, int n_drafts, const int64_t* ids, const int32_t* lens, const int64_t* out, const int32_t* n_out) {
+        const std::string who(who_c);
+        REQUIRE(n_drafts >= 0 && n_drafts <= DRAFTS_MAX, who + ": n_drafts must be 0 .. 8");
+        REQUIRE(out && n_out, who + ": null output pointer");
+        REQUIRE(n_drafts == 0 || lens, who + ": null draft lengths");
+        int total = 0;
+        for (int g = 0; g < n_drafts; ++g) {
+            REQUIRE(lens[g] >= 0 && lens[g] <= DRAFT_LEN_MAX, who + ": a draft length (lens) must be 0 .. 32");
+            total += lens[g];
+        }
+        REQUIRE(total == 0 || ids, who + ": null draft ids");
+    }
+    void generate_drafts(int env, int n_drafts, const int64_t* ids, const int32_t* lens, int max_new, const int64_t* eos, int n_eos, int64_t* out,
+                         int cap, int32_t* n_out, int32_t* winner_out, int32_t* pass_tokens_out) override {
+        const char* who = "svln_generate_drafts";
+        Env& e = env_at(env);
+        drafts_arg_check(who, n_drafts, ids, lens, out, n_out);
+        REQUIRE(n_eos >= 0 && (n_eos == 0 || eos), std::string(who) + ": null eos list");
+        if (winner_out) *winner_out = -1;
+        if (pass_tokens_out) *pass_tokens_out = 0;
+        // a ridden row must be in the numeric scheme and the head form of the step it replaces; the select kernel carries ids, scores and
+        // final-norm rows, not lists, entropies, noise or penalty flags
+        const bool usable = !smp_on && rep_penalty == 1.0f && !fp8_on && !mx4_on && !fp8_gemm_on && !persistent_on && topk == 0 && !ent_on &&
+                            !(scores_on && allow_on) && !grp.pending;      // (one fork scaffold: a group pending on another env keeps it)
+        DraftPlan pl;
+        if (usable && max_new >= 1 && cap >= 1) pl = plan_drafts(e, n_drafts, ids, lens, max_new < cap ? max_new : cap, eos, n_eos);
+        st_drafts[0] += 1;
+        if (pl.G == 0) {                              // hints ignored: svln_generate, launch for launch
+            st_drafts[5] += 1;
+            generate(env, max_new, eos, n_eos, out, cap, n_out, false);
+            st_drafts[7] += *n_out - 1;
+            return;
+        }
+        const GenBegin gb = gen_begin(env, max_new, eos, n_eos, cap);      // (an armed svln_set_draft draft is consumed and not used)
+        const int P = gb.P, L = gb.L, Tn = gb.Tn, limit = gb.limit, G = pl.G, r = pl.r, q0 = L / PAGE;
+        ensure_bforced_buffers();
+        ensure_cand_buffers();
+        ensure_dsel_buffers();
+        for (int g = 1; g < G; ++g) ensure_fork_tab(g);
+        // ---- nothing was launched up to here
+        int tail_n[MAXB] = {0}, k_max = 0, nh = 1, off = 0;
+        const HeadLists &h = bf_host, &d = bf_dev;
+        // (the pinned staging was last read by copies of calls that ended in a synchronisation)
+        for (int q = 0; q < G * r; ++q) h_cfeed[q] = 0;
+        h.src[0] = Tn - 1; h.tap[0] = -1;
+        for (int g = 0; g < G; ++g) {
+            const int kg = pl.k[g];
+            if (g >= 1) tail_n[g] = fork_tail_pages(L, kg + 1);
+            DecodeSlot& sl = h_cslots[g];
+            sl.page_table = g == 0 ? e.d_pages : fork_tab[g]; sl.pos = L; sl.pad = kg;
+            for (int j = 0; j < kg; ++j) { h_cfeed[g * r + j] = (int)ids[off + j]; h.src[nh] = Tn + g * r + j; h.tap[nh] = -1; ++nh; }
+            h_dsel[g] = kg;
+            k_max = std::max(k_max, kg); off += lens[g];
+        }
+        for (int g = G; g < 16; ++g) h_dsel[g] = 0;
+        grp = Group();
+        grp.env = env; grp.n_seq = G; grp.L = L; grp.q0 = q0;
+        for (int g = 1; g < G; ++g) grp.n_tail = std::max(grp.n_tail, tail_n[g]);
+        int n = 0, winner = 0;
+        bool done = false;
+        try {
+            HIP_CHECK(hipMemcpyAsync(d.src, h.src, (size_t)nh * sizeof(int), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(d.tap, h.tap, (size_t)nh * sizeof(int), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(d_cfeed, h_cfeed, (size_t)G * r * sizeof(int), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(d_cslots, h_cslots, (size_t)G * sizeof(DecodeSlot), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(d_dsel, h_dsel, 16 * sizeof(int), hipMemcpyHostToDevice, st));
+            gen_ctl_start(env, L, limit, n_eos);
+            HIP_CHECK(hipEventRecord(ph_ev[2], st));
+            // the folded candidates call's pass: the tables of the fork first, rows of earlier turns in page q0 by one copy, the prompt's rows
+            // of that page layer by layer through the mirror list
+            ensure_pages(e, L + pl.k[0]);
+            const int n_dst = fork_tables(e, q0, tail_n, G);
+            const int n_mirror = L % PAGE != 0 ? n_dst : 0;
+            if (n_mirror > 0) { if (P > q0 * PAGE) fork_page_copy(e.pages[q0], n_dst); else upload_fork_dst(n_dst); }
+            const Fold f{d_cfeed, d_cslots, G, r, L + k_max, q0, d_fork_dst, n_mirror};
+            std::vector<Seg> segs{Seg{&e, P, Tn, 0}};
+            prefill_rows(segs, Tn + G * r, 0, 0, &f);
+            e.kv_len = L;
+            // head: the prompt's last row once, then the fed rows sequence by sequence; no tap scatter (the select kernel copies the winner's)
+            launch_rmsnorm_indexed<T>(st, x, final_norm, bf_xn, d.src, d.tap, hid_tap, nh, H, c.rms_eps);
+            for (int r0 = 0; r0 < nh; r0 += 32) {
+                const int m = std::min(nh - r0, 32);
+                argmax_rows(lm_head, H, bf_xn + (size_t)r0 * H, H, V, H, m == 1 ? 1 : ride_head_rows(m), false, r0);
+            }
+            DraftSelectArgs a;
+            a.cand = d_tok_b; a.cand_score = scores_on ? d_score_b : nullptr; a.fed = d_cfeed; a.k = d_dsel; a.G = G; a.r = r;
+            a.ctl = d_ctl; a.eos = d_eos; a.out_ids = d_out_ids; a.out_token = d_token; a.xn = bf_xn; a.hid_tap = hid_tap; a.H = H;
+            a.tap_cap = HID_TAP_ROWS; a.scores = d_scores; a.rec = d_dsel + 8; a.stats = d_dsel + 12;
+            launch_draft_select<T>(st, a);
+            HIP_CHECK(hipEventRecord(ph_ev[3], st));
+            // ONE synchronisation reads the loop state, the ids and the result record
+            HIP_CHECK(hipMemcpyAsync(h_ctl, d_ctl, sizeof(GenCtl), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(h_out_ids, d_out_ids, (size_t)(k_max + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(h_dsel, d_dsel, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
+            if (scores_on) HIP_CHECK(hipMemcpyAsync(h_scores, d_scores, (size_t)(k_max + 1) * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            LAUNCH_CHECK("generate_drafts");
+            n = h_ctl->count; done = h_ctl->done != 0; winner = h_dsel[8];
+            REQUIRE(n >= 1 && n <= k_max + 1 && n == h_dsel[9] && winner >= 0 && winner < G && n <= pl.k[winner] + 1, "generation state out of range");
+            require_finite_tokens(h_out_ids, n);
+        } catch (...) {
+            // every fork page goes back to the pool, no group is pending; the env is as after a failed svln_generate
+            (void)hipStreamSynchronize(st);
+            drop_group();
+            throw;
+        }
+        // the winner's private tail becomes the env's; the other forks' pages and the env's displaced tail go back to the pool
+        promote_fork(e, winner, h_ctl->kv_len);
+        if (!done) ensure_pages(e, L + n);            // the next step writes position L + n - 1
+        st_drafts[1] += 1; st_drafts[2] += n; st_drafts[3] += nh - 1; st_drafts[4] += done ? 1 : 0; st_drafts[6] += winner >= 1 ? 1 : 0;
+        if (winner_out) *winner_out = winner;
+        if (pass_tokens_out) *pass_tokens_out = n;
+        st_drafts[7] += finish_turn(e, env, L, limit, n, n, done, false, 0, n, true, out, n_out);
+    }
+    void turn_drafts(const svln_turn_args& a, int n_drafts, const int64_t* ids, const int32_t* lens, int64_t* out, int cap, int32_t* n_out,
+                     int32_t* kv_len, int32_t* winner_out, int32_t* pass_tokens_out) override {
+        Env& e = env_at(a.env);
+        refuse_while_group_on(a.env, "svln_turn_drafts");
+        begin_turn(a, [&] {
+            REQUIRE(a.ids && a.n_ids >= 1, "svln_turn_drafts: null / empty argument");
+            drafts_arg_check("svln_turn_drafts", n_drafts, ids, lens, out, n_out);
+        });
+        generate_drafts(a.env, n_drafts, ids, lens, a.max_new_tokens, a.eos_ids, a.n_eos, out, cap, n_out, winner_out, pass_tokens_out);
+        if (kv_len) *kv_len = e.kv_len;
+    }
+    void drafts_stats(int64_t* out8) override { for (int q = 0; q < 8; ++q) out8[q] = st_drafts[q]; }
     // ------------------------------------------------------------------------------- forced turns (svln_generate_forced)
     // A turn on the CALLER's ids F[0 .. n): ids F[0 .. n - 1) ride the prefill pass as n - 1 more rows (the ride's gather, RoPE, KV append
     // and causal attention), the final norm of the last n rows goes to xn and the tap rows, ONE lm_head product in its EPI_TARGET form
@@ -3846,7 +4051,12 @@ public:
         env_at(env);
         REQUIRE(grp.pending && grp.env == env, "svln_group_select: no group turn is pending on this env");
         REQUIRE(index >= 0 && index < grp.n_seq, "svln_group_select: index outside the group's sequences");
-        Env& e = envs[env];
+        promote_fork(envs[env], index, grp.L + grp.n_out[index] - 1);
+        if (kv_len) *kv_len = envs[env].kv_len;
+    }
+    // The page handover of a fork turn: the env goes on with sequence `index` of the group at kv length kv_final.  The group is dropped:
+    // every other fork page and the env's displaced tail go back to the pool exactly once, no group is left pending.
+    void promote_fork(Env& e, int index, int kv_final) {
         if (index >= 1 && !grp.tail[index].empty()) {
             // the env goes on with sequence `index`: its private tail becomes the env's, the env's former tail is freed with the other forks'
             // (a group turn's tails all have n_tail pages, as has the env; the candidates of svln_generate_candidates are ragged: a page the
@@ -3862,8 +4072,7 @@ public:
             HIP_CHECK(hipMemcpyAsync(e.d_pages + grp.q0, e.pages.data() + grp.q0, (size_t)nt * sizeof(int), hipMemcpyHostToDevice, st));
         }
         drop_group();
-        e.kv_len = grp.L + grp.n_out[index] - 1;
-        if (kv_len) *kv_len = e.kv_len;
+        e.kv_len = kv_final;
     }
     void group_logprobs(int index, float* out, int cap, int32_t* n) override {
         REQUIRE(grp.pending && index >= 0 && index < grp.n_seq, "svln_group_logprobs: no pending group turn / no such sequence");
@@ -5104,6 +5313,87 @@ public:
         HIP_CHECK(hipMemcpy(d_out_ids, ids0.data(), ids0.size() * sizeof(int), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(d_scores, sc0.data(), sc0.size() * sizeof(float), hipMemcpyHostToDevice));
     }
+    // TEST-ONLY: one draft_select_kernel launch on caller-given host arrays, on the engine's own d_ctl / d_out_ids / d_scores / d_token, which
+    // are saved before and restored afterwards.  Final-norm row q holds q + 1 + (column % 4) / 4, the tap rows start at -1.
+    void op_draft_select(const svln_draft_select_op& q) override {
+        const size_t cap = (size_t)c.max_positions + 8, eos_cap = (size_t)(V > 16 ? V : 16);
+        REQUIRE(q.G >= 1 && q.G <= DRAFTS_MAX, "op_draft_select: G must be 1 .. 8");
+        REQUIRE(q.r >= 1 && 1 + q.G * q.r <= DRAFT_SELECT_ROWS, "op_draft_select: 1 + G r head rows must be <= 33");
+        REQUIRE(q.k && q.fed && q.cand && q.ctl_out && q.out_ids && q.last_token && q.rec && q.stats, "op_draft_select: null pointer");
+        REQUIRE(!q.cand_score == !q.scores, "op_draft_select: cand_score and scores come together");
+        for (int g = 0; g < q.G; ++g) REQUIRE(q.k[g] >= 0 && q.k[g] <= q.r, "op_draft_select: a row count (k) outside 0 .. r");
+        REQUIRE(q.rows >= 1 && (size_t)q.rows <= cap, "op_draft_select: rows beyond the id buffer");
+        REQUIRE(q.count >= 0 && q.count + q.r + 1 <= q.rows, "op_draft_select: count leaves no room in out_ids");
+        REQUIRE(q.n_eos >= 0 && (size_t)q.n_eos <= eos_cap && (q.n_eos == 0 || q.eos), "op_draft_select: eos list");
+        REQUIRE(q.tap_rows >= 0 && q.tap_rows <= HID_TAP_ROWS && (q.tap_rows == 0 || q.taps), "op_draft_select: tap rows");
+        ensure_bforced_buffers();
+        ensure_cand_buffers();
+        ensure_dsel_buffers();
+        sync();
+        eos_valid = false;                 // d_eos is rewritten here
+        int nh = 1;
+        for (int g = 0; g < q.G; ++g) nh += q.k[g];
+        std::vector<int> he(q.n_eos);
+        for (int k = 0; k < q.n_eos; ++k) he[k] = q.eos[k] >= 0 && q.eos[k] < 0x7FFFFFFF ? (int)q.eos[k] : -2;
+        // the engine's own state, restored at the end
+        GenCtl g0; int tok0 = 0;
+        std::vector<int> ids0(q.rows); std::vector<float> sc0(q.rows);
+        HIP_CHECK(hipMemcpy(&g0, d_ctl, sizeof(g0), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(&tok0, d_token, sizeof(int), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(ids0.data(), d_out_ids, ids0.size() * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(sc0.data(), d_scores, sc0.size() * sizeof(float), hipMemcpyDeviceToHost));
+        auto restore = [&] {
+            (void)hipMemcpy(d_ctl, &g0, sizeof(g0), hipMemcpyHostToDevice);
+            (void)hipMemcpy(d_token, &tok0, sizeof(int), hipMemcpyHostToDevice);
+            (void)hipMemcpy(d_out_ids, ids0.data(), ids0.size() * sizeof(int), hipMemcpyHostToDevice);
+            (void)hipMemcpy(d_scores, sc0.data(), sc0.size() * sizeof(float), hipMemcpyHostToDevice);
+        };
+        try {
+            if (q.n_eos) HIP_CHECK(hipMemcpy(d_eos, he.data(), (size_t)q.n_eos * sizeof(int), hipMemcpyHostToDevice));
+            const float nanv = __builtin_nanf("");
+            std::vector<int> ids(q.rows, -7); std::vector<float> sc(q.rows, nanv);
+            const int tk = -7;
+            HIP_CHECK(hipMemcpy(d_out_ids, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(d_scores, sc.data(), sc.size() * sizeof(float), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(d_token, &tk, sizeof(int), hipMemcpyHostToDevice));
+            int sel[16] = {0};
+            for (int g = 0; g < q.G; ++g) sel[g] = q.k[g];
+            for (int j = 0; j < 4; ++j) sel[8 + j] = -7;
+            sel[12] = q.stats[0]; sel[13] = q.stats[1];
+            HIP_CHECK(hipMemcpy(d_dsel, sel, sizeof(sel), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(d_cfeed, q.fed, (size_t)q.G * q.r * sizeof(int), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(d_tok_b, q.cand, (size_t)nh * sizeof(int), hipMemcpyHostToDevice));
+            if (q.cand_score) HIP_CHECK(hipMemcpy(d_score_b, q.cand_score, (size_t)nh * sizeof(float), hipMemcpyHostToDevice));
+            std::vector<T> rows_x((size_t)DRAFT_SELECT_ROWS * H), rows_t((size_t)HID_TAP_ROWS * H);
+            for (int row = 0; row < DRAFT_SELECT_ROWS; ++row)
+                for (int col = 0; col < H; ++col) host_from_f32((float)(row + 1) + (float)(col % 4) * 0.25f, rows_x[(size_t)row * H + col]);
+            for (size_t j = 0; j < rows_t.size(); ++j) host_from_f32(-1.0f, rows_t[j]);
+            HIP_CHECK(hipMemcpy(bf_xn, rows_x.data(), rows_x.size() * sizeof(T), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(hid_tap, rows_t.data(), rows_t.size() * sizeof(T), hipMemcpyHostToDevice));
+            GenCtl g; g.pos = q.pos; g.kv_len = q.kv_len; g.done = q.done; g.count = q.count; g.max_new = q.max_new; g.n_eos = q.n_eos; g.draw0 = g.stream = 0;
+            HIP_CHECK(hipMemcpy(d_ctl, &g, sizeof(g), hipMemcpyHostToDevice));
+            DraftSelectArgs a;
+            a.cand = d_tok_b; a.cand_score = q.cand_score ? d_score_b : nullptr; a.fed = d_cfeed; a.k = d_dsel; a.G = q.G; a.r = q.r;
+            a.ctl = d_ctl; a.eos = d_eos; a.out_ids = d_out_ids; a.out_token = d_token; a.xn = bf_xn; a.hid_tap = hid_tap; a.H = H;
+            a.tap_cap = HID_TAP_ROWS; a.scores = d_scores; a.rec = d_dsel + 8; a.stats = d_dsel + 12;
+            launch_draft_select<T>(st, a);
+            sync();
+            LAUNCH_CHECK("op_draft_select");
+            HIP_CHECK(hipMemcpy(&g, d_ctl, sizeof(g), hipMemcpyDeviceToHost));
+            std::memcpy(q.ctl_out, &g, sizeof(g));
+            HIP_CHECK(hipMemcpy(q.out_ids, d_out_ids, (size_t)q.rows * sizeof(int), hipMemcpyDeviceToHost));
+            if (q.scores) HIP_CHECK(hipMemcpy(q.scores, d_scores, (size_t)q.rows * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(q.last_token, d_token, sizeof(int), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(sel, d_dsel, sizeof(sel), hipMemcpyDeviceToHost));
+            for (int j = 0; j < 4; ++j) q.rec[j] = sel[8 + j];
+            q.stats[0] = sel[12]; q.stats[1] = sel[13];
+            if (q.tap_rows) read_rows_f32(hid_tap, (size_t)q.tap_rows * H, q.taps);
+        } catch (...) {
+            restore();
+            throw;
+        }
+        restore();
+    }
     // TEST-ONLY: one decode step on env 0 with GenCtl.done forced to `done`, every buffer a step may touch compared with a host snapshot
     void op_dead_step(int done, char* report, int report_cap, int32_t* n_changed) override {
         REQUIRE(report && report_cap >= 1 && n_changed, "op_dead_step: null pointer");
@@ -5896,6 +6186,21 @@ int svln_op_attention_verify_multi(svln_engine* h, int n_seq, int rows_max, cons
 int svln_op_verify_step(svln_engine* h, int rows, const int32_t* fed, const int32_t* cand, int count, int max_new, const int64_t* eos, int n_eos,
                         int32_t* new_count, int32_t* done, int64_t* emitted, int32_t* next_token) {
     API_BEGIN_H h->impl->op_verify_step(rows, fed, cand, count, max_new, eos, n_eos, new_count, done, emitted, next_token); API_END
+}
+int svln_generate_drafts(svln_engine* h, int env, int n_drafts, const int64_t* ids, const int32_t* lens, int max_new_tokens, const int64_t* eos_ids,
+                         int n_eos, int64_t* out_ids, int out_cap, int32_t* n_out, int32_t* winner_out, int32_t* pass_tokens_out) {
+    API_BEGIN_H h->impl->generate_drafts(env, n_drafts, ids, lens, max_new_tokens, eos_ids, n_eos, out_ids, out_cap, n_out, winner_out, pass_tokens_out); API_END
+}
+int svln_turn_drafts(svln_engine* h, const svln_turn_args* a, int n_drafts, const int64_t* ids, const int32_t* lens, int64_t* out_ids, int out_cap,
+                     int32_t* n_out, int32_t* kv_len, int32_t* winner_out, int32_t* pass_tokens_out) {
+    API_BEGIN_H REQUIRE(a, "svln_turn_drafts: null argument"); h->impl->turn_drafts(*a, n_drafts, ids, lens, out_ids, out_cap, n_out, kv_len, winner_out, pass_tokens_out); API_END
+}
+int svln_drafts_stats(svln_engine* h, int64_t* out) { API_BEGIN_H REQUIRE(out, "svln_drafts_stats: null output pointer"); h->impl->drafts_stats(out); API_END }
+int svln_op_draft_select(svln_engine* h, const svln_draft_select_op* op) {
+    API_BEGIN_H
+    REQUIRE(op, "svln_op_draft_select: null pointer");
+    h->impl->op_draft_select(*op);
+    API_END
 }
 int svln_op_argmax_step(svln_engine* h, const svln_argmax_step_op* op) {
     API_BEGIN_H

@@ -328,6 +328,19 @@ void launch_verify_feed(hipStream_t s, const GenCtl* ctl, const int* token, cons
 template <typename T> void launch_verify_step(hipStream_t s, const int* fed, const int* cand, const int* n_rows, int max_rows, GenCtl* ctl,
                                               const int* eos, int* out_ids, int* out_token, const void* xn, void* hid_tap, int H, int tap_cap,
                                               int* stats);
+// Several drafts of one turn verified by one prefill pass (svln_generate_drafts; misc.hip).  cand [1 + sum k_g]: the arg-maxes of the head
+// rows -- row 0 = the prompt's last row, then the rows draft g fed, sequence by sequence; cand_score: their log-probabilities (null: not
+// scored); fed [G][r]: the ids the row slots were fed (the folded candidates call's layout); k [G]: rows draft g fed (clamped to 0 .. r).
+// The verify rule of launch_verify_step runs for every g on [row 0, rows of g]; the largest emitted count wins, a tie goes to the lowest
+// g.  The winner's tokens go to out_ids / *out_token / GenCtl as launch_verify_step leaves them, the final-norm rows xn[row] of its
+// emitted tokens to hid_tap[min(token index, tap_cap - 1)], scores[index] when scored; rec = {winner, emitted, stop, head rows read},
+// stats[0] += 1, stats[1] += emitted.  No-op once done is set.  G <= 8, 1 + G r <= DRAFT_SELECT_ROWS.
+constexpr int DRAFT_SELECT_ROWS = 33;
+struct DraftSelectArgs {
+    const int* cand; const float* cand_score; const int* fed; const int* k; int G, r;
+    GenCtl* ctl; const int* eos; int* out_ids; int* out_token; const void* xn; void* hid_tap; int H, tap_cap; float* scores; int* rec; int* stats;
+};
+template <typename T> void launch_draft_select(hipStream_t s, const DraftSelectArgs& a);
 // flags[ids[k]] = value for k < *count (count: device scalar) or k < n_host when count is null; ids < 0 are skipped
 void launch_set_flags(hipStream_t s, uint8_t* flags, const int* ids, const int* count, int n_host, int value);
 

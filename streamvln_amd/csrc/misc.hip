@@ -349,6 +349,73 @@ __global__ __launch_bounds__(256) void verify_step_kernel(const int* fed, const 
     }
 }
 
+// Several drafts of ONE turn, verified by one prefill pass (svln_generate_drafts).  Head rows: row 0 = the prompt's last row, then the
+// rows draft g fed, k_g = clamp(k[g], 0, r) of them, sequence by sequence (row 1 + k_0 + .. + k_{g-1} + j was fed fed[g r + j]).  For every
+// g the rule of verify_step_kernel runs on the row list [row 0, rows of g]: token 0 is always emitted, token i iff every earlier one was
+// emitted without stopping and the arg-max of list row i - 1 equals fed[g r + i - 1]; stops are an EOS id (appended, never fed), the
+// max_new-th token and a non-finite arg-max (-1).  The winner is the largest emitted count, a tie goes to the lowest g.  For the winner:
+// out_ids, *out_token, GenCtl (count += e, pos / kv_len advance by e, by e - 1 on a stop, done), the final-norm row of every emitted token
+// to hid_tap[min(its index, tap_cap - 1)], scores[index] = the row's log-probability when cand_score is given, rec = {winner, e, stop,
+// head rows read}, stats[0] += 1 (passes), stats[1] += e (tokens).  One workgroup of 256 threads; no-op when done is set.
+template <typename T>
+__global__ __launch_bounds__(256) void draft_select_kernel(const DraftSelectArgs a) {
+    constexpr int EPC = Elt<T>::PER_CHUNK;
+    __shared__ int s_eos[DRAFT_SELECT_ROWS], s_emit, s_c0, s_base;
+    GenCtl* ctl = a.ctl;
+    const int was_done = ctl->done, n_eos = ctl->n_eos, G = min(a.G, 8), r = a.r;
+    if (was_done) return;                  // (uniform: thread 0 writes the flag only behind the barriers below)
+    int nh = 1;
+    for (int g = 0; g < G; ++g) nh += min(max(a.k[g], 0), r);
+    nh = min(nh, DRAFT_SELECT_ROWS);
+    for (int i = 0; i < nh; ++i) {         // is cand[i] an EOS id?  (the set may be large: all threads search it)
+        int hit = 0;
+        for (int q = threadIdx.x; q < n_eos; q += 256) hit |= a.eos[q] == a.cand[i];
+        hit = __syncthreads_or(hit);
+        if (threadIdx.x == 0) s_eos[i] = hit;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int c = ctl->count, max_new = ctl->max_new;
+        int best = -1, best_e = 0, best_stop = 0, best_base = 1, base = 1;
+        for (int g = 0; g < G; ++g) {
+            const int kg = min(max(a.k[g], 0), r);
+            int e = 0, stop = 0, prev = 0;
+            for (int i = 0; i <= kg && !stop && base + i - 1 < nh; ++i) {
+                if (i > 0 && prev != a.fed[g * r + i - 1]) break;
+                const int row = i == 0 ? 0 : base + i - 1;
+                prev = a.cand[row];
+                ++e;
+                stop = prev < 0 || c + e >= max_new || s_eos[row];
+            }
+            if (e > best_e) { best = g; best_e = e; best_stop = stop; best_base = base; }
+            base += kg;
+        }
+        int last = -1;
+        for (int i = 0; i < best_e; ++i) {
+            last = a.cand[i == 0 ? 0 : best_base + i - 1];
+            a.out_ids[c + i] = last;
+        }
+        if (best_e > 0) {
+            *a.out_token = last;
+            ctl->count = c + best_e;
+            const int adv = best_stop ? best_e - 1 : best_e;          // the stopping token is appended, never fed
+            ctl->pos += adv; ctl->kv_len += adv;
+            if (best_stop) ctl->done = 1;
+        }
+        a.rec[0] = best; a.rec[1] = best_e; a.rec[2] = best_stop; a.rec[3] = nh;
+        a.stats[0] += 1; a.stats[1] += best_e;
+        s_emit = best_e; s_c0 = c; s_base = best_base;
+    }
+    __syncthreads();
+    const int e = s_emit, c0 = s_c0, wb = s_base, nch = a.H / EPC;
+    const T* xn = (const T*)a.xn; T* tap = (T*)a.hid_tap;
+    for (int q = threadIdx.x; q < e * nch; q += 256) {
+        const int j = q / nch, ci = q - j * nch, row = j == 0 ? 0 : wb + j - 1;
+        *(uint4*)(tap + (size_t)min(c0 + j, a.tap_cap - 1) * a.H + (size_t)ci * EPC) = *(const uint4*)(xn + (size_t)row * a.H + (size_t)ci * EPC);
+    }
+    if (a.cand_score && (int)threadIdx.x < e) a.scores[c0 + threadIdx.x] = a.cand_score[threadIdx.x == 0 ? 0 : wb + (int)threadIdx.x - 1];
+}
+
 // --------------------------------------------------------------------------- slow-memory token pruning
 // OPT-IN EXTENSION (BASELINE configs[3]; SURVEY.md a-13: the reference has no counterpart, parity is pinned only by this
 // project's own CPU restatement oracle/streamvln_oracle.py: prune_memory_tokens).  Rule: score_i = cos(M_i, mean_j M_j) over the
@@ -530,6 +597,9 @@ template <typename T> void launch_verify_step(hipStream_t s, const int* fed, con
                                               int* stats) {
     hipLaunchKernelGGL((verify_step_kernel<T>), dim3(1), dim3(256), 0, s, fed, cand, n_rows, max_rows, ctl, eos, out_ids, out_token, (const T*)xn,
                        (T*)hid_tap, H, tap_cap, stats);
+}
+template <typename T> void launch_draft_select(hipStream_t s, const DraftSelectArgs& a) {
+    hipLaunchKernelGGL((draft_select_kernel<T>), dim3(1), dim3(256), 0, s, a);
 }
 // scratch: partial [ceil(n/64)][H] floats, mean [H], score [n]; sel [keep] ints (ascending row indices)
 template <typename T> void launch_memory_prune(hipStream_t s, const void* m, int n_rows, int H, int keep, float* partial, float* mean, float* score,
@@ -877,6 +947,7 @@ void launch_beam_select(hipStream_t s, const BeamSelectArgs& a) {
     template void launch_gather_rows<T>(hipStream_t, const int*, const void*, const void*, void*, int, int, const int*);                      \
     template void launch_verify_step<T>(hipStream_t, const int*, const int*, const int*, int, GenCtl*, const int*, int*, int*, const void*,    \
                                         void*, int, int, int*);                                                                  \
+    template void launch_draft_select<T>(hipStream_t, const DraftSelectArgs&);                                                    \
     template void launch_memory_prune<T>(hipStream_t, const void*, int, int, int, float*, float*, float*, int*);                   \
     template void launch_synth<T>(hipStream_t, void*, int, int64_t, int, RowMap, uint64_t, float, float);                          \
     template void launch_convert<T>(hipStream_t, void*, int, int64_t, int, RowMap, const void*, int);                              \

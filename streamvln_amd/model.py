@@ -150,9 +150,9 @@ class KVHandle:
 class GenerateOutput(dict):
     """`return_dict_in_generate=True` result: `.sequences` (new tokens only, EOS included) and
     `.past_key_values` (streamvln_eval.py:334-335).  `.top_token_ids` / `.top_logprobs` (set_top_logprobs) and `.token_entropies`
-    (set_token_entropy) read as None while their switch is off; like every optional entry they are keys only of a result that carries them."""
+    (set_token_entropy) read as None while their switch is off, `.draft_index` / `.draft_tokens` on a turn without draft_set; like every optional entry they are keys only of a result that carries them."""
 
-    _OPTIONAL = ("top_token_ids", "top_logprobs", "token_entropies")
+    _OPTIONAL = ("top_token_ids", "top_logprobs", "token_entropies", "draft_index", "draft_tokens")
 
     def __getattr__(self, k):
         try:
@@ -584,7 +584,7 @@ class StreamVLNForCausalLM:
 
     @torch.no_grad()
     def generate(self, inputs=None, images=None, image_sizes=None, depths=None, poses=None, intrinsics=None, task_ids=None,
-                 draft_ids=None, forced_ids=None, candidate_ids=None, beam_width=None, fold_candidates=False, **kwargs):
+                 draft_ids=None, forced_ids=None, candidate_ids=None, beam_width=None, fold_candidates=False, draft_set=None, **kwargs):
         """One model turn = ONE crossing into the engine (svln_turn: encode_rgbd, the KV / embeds bookkeeping of the reference's generate,
         splice, prefill + greedy decode).  draft_ids (optional, set_speculative / set_prefill_draft): a guess of this turn's whole id sequence; with
         set_auto_draft(True) and no explicit draft, the env's previous turn output is the guess.
@@ -598,13 +598,24 @@ class StreamVLNForCausalLM:
         fold_candidates=True (with candidate_ids only): the candidates' first rows ride the prefill pass (svln_turn_candidates_folded) --
         same result layout and follow-up, one weight pass less; no result is bit-equal to the unfolded call's.
         beam_width (1 .. 8): a beam turn -- the beam_width most probable turns of the prompt (see _generate_beams for the result,
-        select_sequence for what must follow); HF's `num_beams` stays refused."""
+        select_sequence for what must follow); HF's `num_beams` stays refused.
+        draft_set (0 .. 8 guessed id sequences of 0 .. 32 ids): a multi-draft turn (svln_turn_drafts) -- the plain greedy turn with hints,
+        all verified in the one prefill pass; ids, cache length and getters are the plain turn's.  The result also carries `draft_index`
+        (the winning draft; -1: no pass ran, the hints were ignored) and `draft_tokens` (the tokens the pass emitted)."""
         draft = draft_ids
         if fold_candidates and candidate_ids is None:
             raise ValueError("fold_candidates without candidate_ids: only a candidates call has rows to fold into the prefill")
+        dset = None
+        if draft_set is not None:
+            for name, v in (("draft_ids", draft_ids), ("forced_ids", forced_ids), ("candidate_ids", candidate_ids), ("beam_width", beam_width)):
+                if v is not None:
+                    raise NotImplementedError(f"draft_set together with {name}: a multi-draft turn is a plain greedy turn with hints")
+            dset = self._draft_set_arrays(draft_set)
         W = self._beam_request(beam_width, forced_ids, candidate_ids, kwargs)
         ids, pix, V, n_memory, env_id, past, max_new, eos = self._parse_call(inputs, images, kwargs)
         n_seq = self._num_return_sequences(kwargs)
+        if dset is not None and n_seq > 1:
+            raise NotImplementedError("draft_set together with num_return_sequences > 1: a multi-draft turn returns one sequence")
         if forced_ids is not None and n_seq > 1:
             raise NotImplementedError("forced_ids with num_return_sequences > 1: a forced turn has one sequence")
         if candidate_ids is not None and forced_ids is not None:
@@ -641,14 +652,22 @@ class StreamVLNForCausalLM:
         a.ids, a.n_ids, a.n_memory = ids_np.ctypes.data, ids_np.size, n_memory
         a.new_window, a.new_episode, a.max_new_tokens = int(past is None), int(self.curr_t[env_id] == 0), max_new
         auto = self._auto_draft
-        if draft is None and auto:
+        if draft is None and auto and dset is None:
             draft = self._last_out.get(env_id)
         if draft is not None:
             d_np = np.ascontiguousarray(torch.as_tensor(draft).reshape(-1).to("cpu", torch.int64).numpy())
             _check(self._lib.svln_set_draft(self._h, slot, d_np.ctypes.data_as(C.POINTER(C.c_int64)), int(d_np.size)))
         if on_dev:
             self._order_engine_after(pix)
-        rc = self._lib.svln_turn(self._h, buf["args_ref"], buf["out_p"], cap, buf["n_out_ref"], buf["kv_ref"])
+        if dset is not None:
+            # a multi-draft turn (svln_turn_drafts): the plain turn with hints; the result says which draft won and what the pass emitted
+            flat, lens = dset
+            win, ptok = C.c_int32(-1), C.c_int32(0)
+            rc = self._lib.svln_turn_drafts(self._h, buf["args_ref"], int(lens.size), flat.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            lens.ctypes.data_as(C.POINTER(C.c_int32)), buf["out_p"], cap, buf["n_out_ref"], buf["kv_ref"],
+                                            C.byref(win), C.byref(ptok))
+        else:
+            rc = self._lib.svln_turn(self._h, buf["args_ref"], buf["out_p"], cap, buf["n_out_ref"], buf["kv_ref"])
         if on_dev:
             self._order_torch_after(pix)
         _check(rc)
@@ -660,6 +679,8 @@ class StreamVLNForCausalLM:
         if dev != "cpu" and str(dev) != "cpu":
             seq = seq.to(dev)
         res = GenerateOutput(sequences=seq, past_key_values=KVHandle(env_id, self._epoch[env_id], buf["kv"].value))
+        if dset is not None:
+            res["draft_index"], res["draft_tokens"] = int(win.value), int(ptok.value)
         if self._token_scores:
             res["token_logprobs"] = self._scores(self._lib.svln_get_token_scores, n_new=int(seq.shape[1]), device=seq.device)
         if self.top_logprobs_k:
@@ -667,6 +688,20 @@ class StreamVLNForCausalLM:
         if self._token_entropy:
             res["token_entropies"] = self._scores(self._lib.svln_get_token_entropy, n_new=int(seq.shape[1]), device=seq.device)
         return self._allowed(res, "svln_get_allowed_logprobs")
+
+    @staticmethod
+    def _draft_set_arrays(draft_set):
+        """draft_set -> (flat int64 ids, int32 lengths); 0 .. 8 guessed id sequences of 0 .. 32 ids"""
+        rows = [np.ascontiguousarray(torch.as_tensor(d).reshape(-1).to("cpu", torch.int64).numpy()) for d in draft_set]
+        if len(rows) > 8:
+            raise ValueError(f"draft_set holds {len(rows)} drafts: a multi-draft turn takes 0 .. 8")
+        for g, r in enumerate(rows):
+            if r.size > 32:
+                raise ValueError(f"draft_set[{g}] holds {int(r.size)} ids: a draft has 0 .. 32")
+        flat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, np.int64), dtype=np.int64)
+        if flat.size == 0:
+            flat = np.zeros(1, np.int64)              # (never read: every length is 0)
+        return flat, np.asarray([r.size for r in rows], np.int32).reshape(-1)
 
     # ---- forced turns: log-probabilities of given ids in one prefill pass (svln_turn_forced) --------------
     def _generate_forced(self, forced, inputs, ids, pix, V, n_memory, env_id, past, eos):
@@ -896,6 +931,8 @@ class StreamVLNForCausalLM:
             raise NotImplementedError(f"candidate_ids in a {who} request: candidates are scored through generate() only")
         if kwargs.get("fold_candidates"):
             raise NotImplementedError(f"fold_candidates in a {who} request: candidates are scored through generate() only")
+        if kwargs.get("draft_set") is not None:
+            raise NotImplementedError(f"draft_set in a {who} request: multi-draft turns run through generate() only")
         g = kwargs.get("num_return_sequences")
         if g is not None and int(g) > 1:
             raise NotImplementedError(f"num_return_sequences={g!r} in a {who} request: group turns run through generate() only")
@@ -1160,6 +1197,8 @@ class StreamVLNForCausalLM:
             raise NotImplementedError("candidate_ids in a submit_forced request: candidates are scored through generate() only")
         if kwargs.get("fold_candidates"):
             raise NotImplementedError("fold_candidates in a submit_forced request: candidates are scored through generate() only")
+        if kwargs.get("draft_set") is not None:
+            raise NotImplementedError("draft_set in a submit_forced request: multi-draft turns run through generate() only")
         if kwargs.get("beam_width") is not None:
             raise NotImplementedError("beam_width in a submit_forced request: beam turns run through generate() only")
         f_np = self._forced_array(forced_ids)
@@ -1243,6 +1282,8 @@ class StreamVLNForCausalLM:
                 raise NotImplementedError("candidate_ids in a generate_batch_forced request: candidates are scored through generate() only")
             if r.get("fold_candidates"):
                 raise NotImplementedError("fold_candidates in a generate_batch_forced request: candidates are scored through generate() only")
+            if r.get("draft_set") is not None:
+                raise NotImplementedError("draft_set in a generate_batch_forced request: multi-draft turns run through generate() only")
             g = r.get("num_return_sequences")
             if g is not None and int(g) > 1:
                 raise NotImplementedError(f"num_return_sequences={g!r} in a generate_batch_forced request: group turns run through generate() only")
@@ -1517,6 +1558,14 @@ class StreamVLNForCausalLM:
         v = [C.c_int64() for _ in range(3)]
         _check(self._lib.svln_prefill_draft_stats(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), int(reset)))
         return tuple(int(x.value) for x in v)
+
+    def drafts_stats(self):
+        """counters of the multi-draft turns (generate(draft_set=...)) since the engine was created: (calls, passes run, tokens the passes
+        emitted -- token 0 included, draft rows fed, turns finished in the pass, calls whose hints were ignored, page handovers, tokens of
+        single steps)"""
+        v = np.zeros(8, np.int64)
+        _check(self._lib.svln_drafts_stats(self._h, v.ctypes.data_as(C.POINTER(C.c_int64))))
+        return tuple(int(x) for x in v)
 
     def set_token_scores(self, enable: bool):
         """Opt-in, default off (svln_set_token_scores): while on, every GenerateOutput of generate / generate_batch / step_batch carries
